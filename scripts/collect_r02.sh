@@ -2,7 +2,7 @@
 # Everything profiles/ holds for round 2, from one GPU box and one tree (run on the GPU box; copy the files named at the
 # end from gpurun_out/r02/ into profiles/).  Usage: bash scripts/collect_r02.sh
 OUT=gpurun_out/r02; mkdir -p $OUT
-python bench.py > $OUT/r02_bench.json 2> $OUT/bench.err || echo "bench failed"
+python bench.py --full > $OUT/r02_bench.json 2> $OUT/bench.err || echo "bench failed"
 bash scripts/prof_bench.sh $OUT/prof --no-cpu-baseline > $OUT/kernel_stats_top.txt
 cp $OUT/prof/run_kernel_stats.csv $OUT/r02_kernel_stats.csv; cp $OUT/prof/bench.json $OUT/r02_bench_under_rocprof.json
 python3 scripts/trace_window.py $OUT/prof $OUT/prof/bench.json > $OUT/r02_trace_window.json

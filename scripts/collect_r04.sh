@@ -7,7 +7,7 @@ FIRST=${1:-1}; LAST=${2:-99}
 step() { echo "[$(date +%T)] step $1: $2"; }
 want() { [ $1 -ge $FIRST ] && [ $1 -le $LAST ]; }
 if want 1; then
-  timeout -k 10 1100 python -u bench.py > $OUT/r04_bench.json 2> $OUT/bench.err; step 1 "bench rc=$?"
+  timeout -k 10 1100 python -u bench.py --full > $OUT/r04_bench.json 2> $OUT/bench.err; step 1 "bench rc=$?"
 fi
 if want 2; then
   bash scripts/prof_bench.sh $OUT/prof --no-cpu-baseline > $OUT/kernel_stats_top.txt; step 2 "bench under rocprofv3 rc=$?"

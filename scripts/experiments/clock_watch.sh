@@ -5,7 +5,7 @@ H=$(ls -d /sys/class/drm/card*/device/hwmon/hwmon* 2>/dev/null | head -1)
 echo "hwmon: $H"; ls $H 2>/dev/null | tr '\n' ' '; echo
 ( for i in $(seq 1 4000); do echo "$(date +%s.%N) $(cat $H/freq1_input 2>/dev/null) $(cat $H/power1_average 2>/dev/null || cat $H/power1_input 2>/dev/null) $(cat $H/temp1_input 2>/dev/null)"; sleep 0.004; done > $OUT/samples.txt ) &
 W=$!
-timeout -k 10 300 python bench.py --no-cpu-baseline --modes-reads 0 --rounds 0 > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --modes-reads 0 --rounds 0 > $OUT/bench.json 2> $OUT/bench.err
 kill $W 2>/dev/null
 python3 - $OUT <<'PY'
 import sys, json, collections

@@ -6,7 +6,7 @@
 OUT=${1:-gpurun_out/large}; GENOME=${2:-1000000000}; mkdir -p $OUT
 export RAWDTW_SYNTH_CACHE=/tmp/rawdtw_synth
 step() { echo "[$(date +%T)] $1"; }
-timeout -k 10 900 python -u bench.py --genome $GENOME --modes-reads 0 --rounds 0 --mapper-reads 0 --cpu-seconds 1.5 > $OUT/bench_large.json 2> $OUT/bench_large.err; step "bench rc=$?"
+timeout -k 10 900 python -u bench.py --full --genome $GENOME --modes-reads 0 --rounds 0 --mapper-reads 0 --cpu-seconds 1.5 > $OUT/bench_large.json 2> $OUT/bench_large.err; step "bench rc=$?"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for c in FETCH_SIZE WRITE_SIZE; do
   RAWDTW_PROBE_GENOME=$GENOME timeout -k 10 600 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmc/$c -- python3 scripts/stream_probe.py 16384 > $OUT/pmc_$c.log 2>&1; step "pmc $c rc=$?"

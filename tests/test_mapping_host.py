@@ -1,17 +1,17 @@
 """Host consumers downstream of the DTW block (pure host code): primary-chain selection + MAPQ,
 the stop rule, PAF formatting and sequence-until, against plain-Python restatements of the
 reference (rmap.cpp:65-128, 594-665, 696-801, 918-965; sequence_until.c:4-18).
-The reference's rmap.cpp cannot be built here (HDF5), so these are pinned by restatement only --
-except find_outlier, whose translation unit compiles on its own."""
+The reference's rmap.cpp cannot be built on its own (HDF5), so these are pinned by restatement only --
+except find_outlier, whose translation unit compiles on its own (its answers: tests/golden/find_outlier_ref.npz)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import rawalign_amd as ra
 from rawalign_amd import mapping as M
+from tests.golden_util import bits, load_find_outlier_golden
 
 f32 = np.float32
 
@@ -120,8 +120,7 @@ def test_paf_line_mapped_and_unmapped():
     assert "ci:i:3" in l2
 
 
-def test_find_outlier_against_compiled_reference(tmp_path):
-    src = "/root/reference/src/sequence_until.c"
+def test_find_outlier_against_compiled_reference():
     rng = np.random.default_rng(2)
     xs = [rng.random((5, n)).astype(np.float32) for n in (1, 3, 8, 17, 40)]
     ours = [M.find_outlier(x) for x in xs]
@@ -136,21 +135,26 @@ def test_find_outlier_against_compiled_reference(tmp_path):
             if d > best:
                 best, outl = d, i
         assert o == best
-    if not os.path.exists(src):
-        pytest.skip("no /root/reference here")
-    # the reference's translation unit, built twice from where it lies: with contraction off (the source's
-    # arithmetic) and as its Makefile builds it on an FMA host (-O3, FMA available): both matched bit for bit
+    # the reference's translation unit, built twice: with contraction off (the source's arithmetic) and as its
+    # Makefile builds it on an FMA host (-O3, FMA available) -- its answers on these inputs and twelve more, recorded
+    # by scripts/make_golden_ref.py (oracle/Makefile ref_outlier): both matched bit for bit
     xs += [rng.random((4, n)).astype(np.float32) for n in (2, 4, 5, 7, 9, 12, 15, 16, 31, 33, 100, 257)]
-    for flags, contracted in ((["-ffp-contract=off", "-march=x86-64-v3"], False), (["-march=x86-64-v3"], True)):
-        so = tmp_path / f"libsu{int(contracted)}.so"
-        subprocess.run(["gcc", "-O3", *flags, "-shared", "-fPIC", "-I/root/reference/src", "-o", str(so), src],
-                       check=True)
-        lib = C.CDLL(str(so))
+    golden = load_find_outlier_golden()
+    assert len(golden) == len(xs) and all(np.array_equal(x, g[0]) for x, g in zip(xs, golden))
+    for x, plain, contracted in golden:
+        assert bits(M.find_outlier(x, contracted=False)) == plain, x.shape
+        assert bits(M.find_outlier(x, contracted=True)) == contracted, x.shape
+    # ... and the builds themselves, where oracle/_ref holds them
+    ref_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref")
+    for so, contracted in (("libsu0.so", False), ("libsu1.so", True)):
+        if not os.path.exists(os.path.join(ref_dir, so)):
+            continue
+        lib = C.CDLL(os.path.join(ref_dir, so))
         lib.find_outlier.restype = C.c_float
-        for x in xs:
+        for x, _, _ in golden:
             rows = (C.c_void_p * len(x))(*[x[i].ctypes.data for i in range(len(x))])
             ref = np.float32(lib.find_outlier(rows, x.shape[1], len(x)))
-            assert ref == M.find_outlier(x, contracted=contracted), (flags, x.shape)
+            assert bits(ref) == bits(M.find_outlier(x, contracted=contracted)), (so, x.shape)
 
 
 def test_sequence_until_state_machine():

@@ -1,10 +1,10 @@
 """The CPU oracle against (1) the golden vectors captured from the reference's own dtw.cpp,
-(2) the known answers and visited-cell masks recorded in SURVEY.md, and (3) -- where
-oracle/_ref is present -- the compiled reference itself on fresh random inputs."""
+(2) the known answers and visited-cell masks recorded in SURVEY.md, and (3) the compiled reference's
+answers on fresh random inputs (recorded; checked live as well where oracle/_ref is present)."""
 import numpy as np
 import pytest
 
-from tests.golden_util import bits
+from tests.golden_util import bits, dtw_random_inputs, golden_path, path_digest
 
 # (n, m, R0) -> DTW_global excl F/T, banded excl F/T, tb path length
 KNOWN = [
@@ -113,22 +113,27 @@ def test_square_band_is_diagonal_strip(oracle):
 
 
 def test_against_compiled_reference(oracle):
+    """3000 fresh random cases against the compiled reference's answers (tests/golden/dtw_ref_random.npz, recorded by
+    scripts/make_golden_ref.py) -- and against the compiled reference itself where oracle/_ref is built."""
     from oracle.loader import RefDTW
 
-    if not RefDTW.available():
-        pytest.skip("oracle/_ref not built (no /root/reference here)")
-    ref = RefDTW()
-    rng = np.random.default_rng(99)
-    for t in range(3000):
-        n, m = int(rng.integers(1, 120)), int(rng.integers(1, 120))
-        a = rng.normal(size=n).astype(np.float32)
-        b = rng.normal(size=m).astype(np.float32)
-        R0 = int(rng.integers(0, 14))
-        ex = t & 1
-        assert bits(oracle.dtw_global(a, b, ex)) == bits(ref.dtw_global(a, b, ex))
-        assert bits(oracle.dtw_banded(a, b, R0, ex)) == bits(ref.dtw_banded(a, b, R0, ex))
+    z = np.load(golden_path("dtw_ref_random.npz"))
+    cases, digest = dtw_random_inputs()
+    assert digest == z["inputs_sha256"].tobytes(), "the seeded inputs differ from those the answers were recorded for"
+    ref = RefDTW() if RefDTW.available() else None
+    tb = {int(t): k for k, t in enumerate(z["tb_case"])}
+    assert sorted(tb) == list(range(0, len(cases), 7))
+    for t, (a, b, R0, ex) in enumerate(cases):
+        g, bd = bits(oracle.dtw_global(a, b, ex)), bits(oracle.dtw_banded(a, b, R0, ex))
+        assert g == int(z["global_"][t]) and bd == int(z["banded"][t]), t
+        if ref is not None:
+            assert g == bits(ref.dtw_global(a, b, ex)) and bd == bits(ref.dtw_banded(a, b, R0, ex))
         if t % 7 == 0:
+            k = tb[t]
             c1, i1, j1, d1 = oracle.dtw_global_tb(a, b, ex)
-            c2, i2, j2, d2 = ref.dtw_global_tb(a, b, ex)
-            assert bits(c1) == bits(c2) and np.array_equal(i1, i2) and np.array_equal(j1, j2)
-            assert np.array_equal(d1.view(np.uint32), d2.view(np.uint32))
+            assert bits(c1) == int(z["tb_cost"][k]) and len(i1) == int(z["tb_len"][k]), t
+            assert path_digest(i1, j1, d1) == z["tb_digest"][k].tobytes(), t
+            if ref is not None:
+                c2, i2, j2, d2 = ref.dtw_global_tb(a, b, ex)
+                assert bits(c1) == bits(c2) and np.array_equal(i1, i2) and np.array_equal(j1, j2)
+                assert np.array_equal(d1.view(np.uint32), d2.view(np.uint32))
