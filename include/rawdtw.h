@@ -304,6 +304,31 @@ int rawdtw_is_mapped_with_high_confidence(const rawdtw_chain_t *primary, uint32_
 float rawdtw_find_outlier(const float *const *x, uint32_t n, uint32_t m);
 float rawdtw_find_outlier_contracted(const float *const *x, uint32_t n, uint32_t m);
 
+/* ---- sequence-until (RI_M_SEQUENCEUNTIL, rmap.cpp:918-944): the real-time relative-abundance stop, as a state of its own.
+ * A record is one read's (mapped, ref_id, fragment_length) as rmap.cpp:750-756 leaves them in reg0; it counts only when it is
+ * mapped and ref_id < n_seq.  The counters are uint32_t and wrap as the reference's do (rmap.h:74-76).  Every ttest_freq
+ * counted reads past tmin_reads an estimation (float)c / ab_count goes into a ring of tn_samples rows; from the
+ * (tn_samples+1)-th estimation on, find_outlier over the ring (rawdtw_find_outlier, or rawdtw_find_outlier_contracted when
+ * `contracted`) at or below t_threshold stops the run. ---- */
+typedef struct {
+    float t_threshold;         /* roptions.c:43 (1.5) */
+    uint32_t tn_samples;       /* roptions.c:44 (5) */
+    uint32_t ttest_freq;       /* roptions.c:45 (500) */
+    uint32_t tmin_reads;       /* roptions.c:46 (500) */
+    int contracted;            /* 1: find_outlier as the reference's FMA build computes it */
+} rawdtw_su_opt_t;
+typedef struct rawdtw_su rawdtw_su;
+/* opt NULL: the defaults above.  n_seq, tn_samples or ttest_freq of 0: RAWDTW_ERR_INVALID (the reference divides by zero or
+ * writes into calloc(0)). */
+int rawdtw_su_create(uint32_t n_seq, const rawdtw_su_opt_t *opt, rawdtw_su **out);
+/* n records in read order.  *stop = 0: keep going; k + 1: the test passed at record k (p->su_stop = k+1) and the accounting
+ * ends there.  Once stopped, every later call counts nothing and returns the same *stop. */
+int rawdtw_su_feed(rawdtw_su *su, uint32_t n, const uint8_t *mapped, const uint32_t *ref_id, const uint32_t *fragment_length,
+                   uint32_t *stop);
+/* su_nreads, su_nestimations, ab_count and su_c_estimations[n_seq] (any of them may be NULL) */
+int rawdtw_su_state(const rawdtw_su *su, uint32_t *n_reads, uint32_t *n_estimations, uint32_t *ab_count, uint32_t *c_estimations);
+int rawdtw_su_destroy(rawdtw_su *su);
+
 /* ---- chaining DP of gen_chains (src/rmap.cpp:430-507) and traceback_chains (src/rmap.cpp:130-173) for
  * one (reference sequence, strand): anchors must be sorted by (target_position, query_position) as
  * rmap.cpp:396-401 does.  Emits up to num_best_chains chains; chain k owns
@@ -557,7 +582,8 @@ int rawdtw_batch_submit_device(rawdtw_ctx *ctx, const rawdtw_align_opt_t *opt, u
  * seq_len[s] is the length of sequence s's signal arrays.  rawalign_amd/mapper.py is the Python mirror. ---- */
 typedef struct rawdtw_mapper rawdtw_mapper;
 typedef struct {
-    int flag;                  /* RI_M_DTW_EVALUATE_CHAINS 0x2 | RI_M_DTW_OUTPUT_CIGAR 0x4 | RI_M_DTW_LOG_SCORES 0x8 (roptions.h:13-15) */
+    int flag;                  /* RI_M_SEQUENCEUNTIL 0x1 | RI_M_DTW_EVALUATE_CHAINS 0x2 | RI_M_DTW_OUTPUT_CIGAR 0x4 | RI_M_DTW_LOG_SCORES 0x8 |
+                                  RI_M_OUTPUT_CHAINS 0x20 (roptions.h:9-20) */
     rawdtw_align_opt_t align;
     rawdtw_chain_opt_t chain;
     float min_bestmap_ratio, min_meanmap_ratio; /* roptions.c:28,31 */
@@ -600,8 +626,36 @@ int rawdtw_mapper_round(rawdtw_mapper *m, uint32_t n_reads, const uint32_t *read
  * copy into the mapper's own staging.) */
 int rawdtw_mapper_read_state(const rawdtw_mapper *m, uint32_t read_id, int *finished, uint32_t *chunks_done);
 int rawdtw_mapper_finish(rawdtw_mapper *m);
-/* *len = the line's length; RAWDTW_ERR_RANGE when buf (cap bytes) is too small for it and its terminator */
+/* *len = the line's length; RAWDTW_ERR_RANGE when buf (cap bytes) is too small for it and its terminator.  With flag 0x20 a
+ * mapped line ends in anchors:s: (rmap.cpp:745-747).  A read sequence-until dropped has no line: *len = 0, "". */
 int rawdtw_mapper_paf(const rawdtw_mapper *m, uint32_t read_id, char *buf, uint32_t cap, uint32_t *len);
+/* ---- sequence-until in the mapper (flag 0x1; the reference's deterministic behaviour, that of one pipeline thread).  The
+ * caller closes its mini-batches in input order, every read of a batch finished; the mapper takes each read's record from its
+ * final chains (mapped = is_mapped_with_high_confidence, ref_id = chains[0]'s sequence, fragment_length = end - start + 1;
+ * unmapped: 0, 0) and feeds them to its own rawdtw_su.  When the test passes at read k of a batch (su_stop = k + 1):
+ *   - reads k' < su_stop keep their lines; mapped reads k' >= su_stop get the rmap.cpp:965 form (gated at :960) -- name,
+ *     read_length, nine '*', mapq, every tag of the mapped line; unmapped reads keep theirs;
+ *   - every read added but not in a closed batch is finished at once (no further rounds) and has no line, as is every read
+ *     added afterwards (chunks_done 0): the reference's pipeline ends at step 0 of the next mini-batch (rmap.cpp:885).
+ * Slot ids are reused after release_read: the batch's order is the caller's read_ids, never the ids. ---- */
+/* the parameters (NULL: the defaults), before the first batch is closed; turns sequence-until on */
+int rawdtw_mapper_set_sequence_until(rawdtw_mapper *m, const rawdtw_su_opt_t *opt);
+/* close one mini-batch: records, rawdtw_su_feed, rawdtw_mapper_su_apply.  An unknown, released, unfinished or already closed
+ * read, or sequence-until off: RAWDTW_ERR_INVALID and nothing changes. */
+int rawdtw_mapper_su_batch(rawdtw_mapper *m, uint32_t n, const uint32_t *read_ids, uint32_t *stop);
+/* The split form, for a host with the reads of a mini-batch on several ranks: each rank's records, all-gathered and replayed in
+ * read order on every rank (rawalign_amd.shard.sequence_until_round), decide the stop, which each rank then applies to its own
+ * block of the batch.  batch_records changes nothing.  su_apply closes the block with the decision: first_gated =
+ * RAWDTW_SU_NO_STOP, or the stop fired and the block's reads at positions >= first_gated are gated -- 0: the whole block (the
+ * stop fell in a block before it), n: none of it (the stop fell at or after its last read), and the run stops all the same.
+ * su_batch is batch_records + rawdtw_su_feed + su_apply(stop ? stop : RAWDTW_SU_NO_STOP). */
+#define RAWDTW_SU_NO_STOP (~(uint32_t)0)
+int rawdtw_mapper_batch_records(const rawdtw_mapper *m, uint32_t n, const uint32_t *read_ids, uint8_t *mapped, uint32_t *ref_id,
+                                uint32_t *fragment_length);
+int rawdtw_mapper_su_apply(rawdtw_mapper *m, uint32_t n, const uint32_t *read_ids, uint32_t first_gated);
+/* *stopped: the stop has fired; *n_mapped_at_stop: the mapped reads of closed batches before the gate -- with su_batch the
+ * number the reference's "[M::...] Sequence Until is activated ... %d mapped reads" prints (with su_apply, this rank's share) */
+int rawdtw_mapper_su_state(const rawdtw_mapper *m, int *stopped, uint32_t *n_mapped_at_stop);
 /* the lines --dtw-log-scores writes to stderr (rmap.cpp:308-312), in order */
 int rawdtw_mapper_log(const rawdtw_mapper *m, const char **text);
 int rawdtw_mapper_stats(const rawdtw_mapper *m, uint64_t *rounds, uint64_t *parts_scored, uint64_t *parts_reused);

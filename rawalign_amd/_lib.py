@@ -89,6 +89,15 @@ class MapperOpt(C.Structure):
     ]
 
 
+class SuOpt(C.Structure):
+    """rawdtw_su_opt_t, defaults of src/roptions.c:43-46"""
+    _fields_ = [("t_threshold", C.c_float), ("tn_samples", C.c_uint32), ("ttest_freq", C.c_uint32), ("tmin_reads", C.c_uint32),
+                ("contracted", C.c_int)]
+
+
+RAWDTW_SU_NO_STOP = 0xFFFFFFFF  # rawdtw_mapper_su_apply: no stop
+
+
 class SeedHit(C.Structure):
     """rawdtw_seed_hit_t"""
     _fields_ = [("ref_seq", C.c_uint32), ("strand", C.c_int32), ("target_position", C.c_uint32), ("query_position", C.c_uint32)]
@@ -163,6 +172,10 @@ SYMBOLS = {
     "rawdtw_is_mapped_with_high_confidence": (I32, [VP, U32, C.POINTER(SelectOpt)]),
     "rawdtw_find_outlier": (F32, [VP, U32, U32]),
     "rawdtw_find_outlier_contracted": (F32, [VP, U32, U32]),
+    "rawdtw_su_create": (I32, [U32, VP, C.POINTER(VP)]),
+    "rawdtw_su_feed": (I32, [VP, U32, VP, VP, VP, C.POINTER(U32)]),
+    "rawdtw_su_state": (I32, [VP, VP, VP, VP, VP]),
+    "rawdtw_su_destroy": (I32, [VP]),
     "rawdtw_chain_anchors": (I32, [C.POINTER(ChainOpt), VP, U32, C.POINTER(F32), VP, VP, VP, U32, U64]),
     "rawdtw_sort_by_chaining_score": (I32, [VP, U32, VP]),
     "rawdtw_batch_build_jobs": (I32, [C.POINTER(AlignOpt), U64, VP, VP, VP, VP, VP, VP, U64, C.POINTER(U64)]),
@@ -204,6 +217,11 @@ SYMBOLS = {
     "rawdtw_mapper_release_read": (I32, [VP, U32]),
     "rawdtw_mapper_timing": (I32, [VP, VP]),
     "rawdtw_mapper_set_scorer": (I32, [VP, VP, VP]),
+    "rawdtw_mapper_set_sequence_until": (I32, [VP, VP]),
+    "rawdtw_mapper_su_batch": (I32, [VP, U32, VP, C.POINTER(U32)]),
+    "rawdtw_mapper_batch_records": (I32, [VP, U32, VP, VP, VP, VP]),
+    "rawdtw_mapper_su_apply": (I32, [VP, U32, VP, U32]),
+    "rawdtw_mapper_su_state": (I32, [VP, C.POINTER(I32), C.POINTER(U32)]),
     "rawdtw_context_device": (I32, [VP, C.POINTER(I32)]),
     "rawdtw_anchors_pack": (I32, [U64, VP, VP, VP, VP, VP, VP, U64, VP]),
     "rawdtw_anchors_unpack": (I32, [U64, VP, VP, VP, VP, VP, U64, VP]),

@@ -66,6 +66,9 @@ struct MRead {
     uint64_t last_round = 0;     // the round it was last scored in, and its position among its group's reads then
     uint64_t last_pos = 0;
     uint64_t seen_round = 0;     // (duplicate check)
+    bool closed = false;         // sequence-until: in a closed mini-batch
+    bool gated = false;          // ... at or after the stop point of its batch (rmap.cpp:960: a mapped read's line loses its fields)
+    bool dropped = false;        // ... added but in no closed batch when the stop fired, or added after it: finished, no line
 };
 
 // growable array in page-locked memory (plain memory for a mapper without a device); contents are NOT kept over a growth
@@ -288,6 +291,10 @@ struct rawdtw_mapper {
     void *scorer_user = nullptr;
     bool keep_host_events = true; // (false: scored on the device only and no CIGAR asked for -- nothing reads the host's copy of a read's events)
     std::string err;
+    rawdtw_su *su = nullptr;      // sequence-until (flag 0x1 or rawdtw_mapper_set_sequence_until): the state su_batch feeds
+    bool su_closed_any = false;   // a batch has been closed (the parameters are fixed from then on)
+    bool su_stopped = false;
+    uint32_t su_mapped = 0;       // mapped reads of closed batches before the gate
 };
 
 namespace {
@@ -451,6 +458,37 @@ void host_phase_chain(rawdtw_mapper *m, MRead &rd, RoundRead &rr, const rawdtw_s
     }
 }
 
+// sequence-until: a mini-batch the caller closes -- every read known, held, finished, in no closed batch, once
+int su_check_batch(rawdtw_mapper *m, uint32_t n, const uint32_t *read_ids)
+{
+    if (n && !read_ids) return fail(m, RAWDTW_ERR_INVALID, "null read ids");
+    if (!m->su) return fail(m, RAWDTW_ERR_INVALID, "sequence-until is off (flag 0x1 or rawdtw_mapper_set_sequence_until)");
+    int st = RAWDTW_OK;
+    const char *msg = "";
+    const uint64_t stamp = ~(uint64_t)0; // (duplicate check through seen_round, which a round clears again)
+    uint32_t k = 0;
+    for (; k < n && st == RAWDTW_OK; k++) {
+        if (read_ids[k] >= m->reads.size()) { st = RAWDTW_ERR_INVALID; msg = "unknown read id"; break; }
+        MRead &rd = m->reads[read_ids[k]];
+        if (rd.seen_round == stamp) { st = RAWDTW_ERR_INVALID; msg = "a read twice in one batch"; break; }
+        if (rd.released) { st = RAWDTW_ERR_INVALID; msg = "a released read in a batch"; }
+        else if (!rd.finished) { st = RAWDTW_ERR_INVALID; msg = "an unfinished read in a batch"; }
+        else if (rd.closed) { st = RAWDTW_ERR_INVALID; msg = "a read of a batch closed before"; }
+        rd.seen_round = stamp;
+    }
+    for (uint32_t q = 0; q < k && q < n; q++) m->reads[read_ids[q]].seen_round = 0;
+    return st == RAWDTW_OK ? RAWDTW_OK : fail(m, st, msg);
+}
+
+// a read's record as rmap.cpp:750-756 / 790-799 leave it in reg0: (mapped, ref_id, fragment_length); (0, 0, 0) for a read without a line
+void su_record(const rawdtw_mapper *m, const MRead &rd, uint8_t *mapped, uint32_t *ref_id, uint32_t *fragment_length)
+{
+    const bool mp = !rd.dropped && high_confidence(m, rd.chains);
+    *mapped = mp ? 1 : 0;
+    *ref_id = mp ? rd.chains[0].ref : 0u;
+    *fragment_length = mp ? rd.chains[0].end_position - rd.chains[0].start_position + 1u : 0u;
+}
+
 } // namespace
 
 extern "C" {
@@ -489,6 +527,8 @@ int rawdtw_mapper_create(rawdtw_ctx *ctx, const rawdtw_mapper_opt_t *opt, uint32
     for (Group &g : m->groups)
         if (st == RAWDTW_OK && g.ctx) st = rawdtw_events_reserve(g.ctx, (uint64_t)opt->slot_events * per_group);
     if (st != RAWDTW_OK) { rawdtw_mapper_destroy(m); return st; }
+    if (st == RAWDTW_OK && (opt->flag & 0x1)) st = rawdtw_su_create(n_seq, nullptr, &m->su); // RI_M_SEQUENCEUNTIL with roptions.c:43-46
+    if (st != RAWDTW_OK) { rawdtw_mapper_destroy(m); return st; }
     m->pool = new (std::nothrow) Pool(m->opt.threads);
     if (!m->pool) { rawdtw_mapper_destroy(m); return RAWDTW_ERR_OOM; }
     *out = m;
@@ -507,6 +547,7 @@ int rawdtw_mapper_destroy(rawdtw_mapper *m)
         }
         if (g.own_ctx && g.ctx) rawdtw_destroy(g.ctx);
     }
+    rawdtw_su_destroy(m->su);
     delete m->pool;
     delete m;
     return RAWDTW_OK;
@@ -537,6 +578,7 @@ int rawdtw_mapper_add_read(rawdtw_mapper *m, const char *name, uint32_t qlen, ui
     else return fail(m, RAWDTW_ERR_RANGE, "more reads than the mapper has slots for (rawdtw_mapper_release_read gives a finished read's slot back)");
     MRead r;
     r.name = name; r.qlen = qlen; r.n_chunks = n_chunks_available; r.slot = slot;
+    if (m->su_stopped) { r.finished = true; r.dropped = true; } // sequence-until: the pipeline reads no further mini-batch (rmap.cpp:885)
     *read_id = (uint32_t)m->reads.size();
     m->reads.push_back(std::move(r));
     return RAWDTW_OK;
@@ -1012,7 +1054,7 @@ int rawdtw_mapper_finish(rawdtw_mapper *m)
     std::vector<float> events;
     for (uint32_t r = 0; r < m->reads.size(); r++) {
         MRead &rd = m->reads[r];
-        if (rd.released || !high_confidence(m, rd.chains)) continue;
+        if (rd.released || rd.dropped || !high_confidence(m, rd.chains)) continue;
         MChain &ch = rd.chains[0];
         const uint32_t na = (uint32_t)ch.anchors.size();
         const uint32_t nj = rawdtw_chain_job_count(&m->opt.align, na);
@@ -1081,6 +1123,11 @@ int rawdtw_mapper_paf(const rawdtw_mapper *m, uint32_t read_id, char *buf, uint3
 {
     if (!m || read_id >= m->reads.size() || !len || m->reads[read_id].released) return RAWDTW_ERR_INVALID;
     const MRead &rd = m->reads[read_id];
+    if (rd.dropped) { // sequence-until: no line
+        *len = 0;
+        if (buf && cap) buf[0] = 0;
+        return buf && !cap ? RAWDTW_ERR_RANGE : RAWDTW_OK;
+    }
     const uint32_t l_chunk = m->opt.chunk_size, max_chunk = m->opt.max_num_chunk;
     uint32_t current_chunk = rd.broke_early ? rd.chunks_done - 1 : rd.chunks_done; // the loop's current_chunk when it exits
     const uint64_t chunk_start = (uint64_t)current_chunk * l_chunk;
@@ -1116,14 +1163,21 @@ int rawdtw_mapper_paf(const rawdtw_mapper *m, uint32_t read_id, char *buf, uint3
         const MChain &c0 = chains[0];
         if ((m->opt.flag & 0x4) && c0.has_aln) tags += "\talns:f:" + fmt_f(c0.alignment_score) + "\taln:s:" + c0.aln;
         const std::vector<rawdtw_anchor_t> &a = c0.anchors;
+        if (m->opt.flag & 0x20) { // --output-chains (rmap.cpp:745-747, anchors_to_string at 53-63): "(query,target)" per anchor, end-first
+            tags += "\tanchors:s:";
+            for (const rawdtw_anchor_t &x : a) tags += "(" + std::to_string(x.query_position) + "," + std::to_string(x.target_position) + ")";
+        }
         const uint32_t read_end = (uint32_t)(scale * (float)a[0].query_position);
         const uint32_t read_start = (uint32_t)(scale * (float)a[n_anchors0 - 1].query_position);
         const uint32_t ref_len = m->seq_len[c0.ref];
         const uint32_t frag_start = c0.strand ? ref_len + 1u - c0.end_position : c0.start_position; // rmap.cpp:751
         const uint32_t frag_len = c0.end_position - c0.start_position + 1u;
-        snprintf(head, sizeof head, "%s\t%u\t%u\t%u\t%s\t%s\t%u\t%u\t%u\t%u\t%u\t%d\t", rd.name.c_str(), read_end, read_start, read_end,
-                 c0.strand ? "-" : "+", m->seq_names[c0.ref].c_str(), ref_len, frag_start, frag_start + frag_len, read_end - read_start - 1u, frag_len,
-                 (int)c0.mapq); // rmap.cpp:961-963
+        if (rd.gated) // sequence-until: at or after the stop point of its batch (rmap.cpp:960, 965 with the mapped read's values)
+            snprintf(head, sizeof head, "%s\t%u\t*\t*\t*\t*\t*\t*\t*\t*\t*\t%d\t", rd.name.c_str(), read_end, (int)c0.mapq);
+        else
+            snprintf(head, sizeof head, "%s\t%u\t%u\t%u\t%s\t%s\t%u\t%u\t%u\t%u\t%u\t%d\t", rd.name.c_str(), read_end, read_start, read_end,
+                     c0.strand ? "-" : "+", m->seq_names[c0.ref].c_str(), ref_len, frag_start, frag_start + frag_len, read_end - read_start - 1u, frag_len,
+                     (int)c0.mapq); // rmap.cpp:961-963
         line = head + tags;
     } else {
         const uint32_t read_length = offset ? (uint32_t)(scale * (float)offset) : 0u;
@@ -1137,6 +1191,77 @@ int rawdtw_mapper_paf(const rawdtw_mapper *m, uint32_t read_id, char *buf, uint3
         buf[n] = 0;
     }
     return (buf && cap > line.size()) || !buf ? RAWDTW_OK : RAWDTW_ERR_RANGE;
+}
+
+int rawdtw_mapper_set_sequence_until(rawdtw_mapper *m, const rawdtw_su_opt_t *opt)
+{
+    if (!m) return RAWDTW_ERR_INVALID;
+    if (m->su_closed_any) return fail(m, RAWDTW_ERR_INVALID, "set sequence-until before the first batch is closed");
+    rawdtw_su *su = nullptr;
+    const int st = rawdtw_su_create((uint32_t)m->seq_len.size(), opt, &su);
+    if (st != RAWDTW_OK) return fail(m, st, "bad sequence-until parameters (n_seq, tn_samples and ttest_freq must be > 0)");
+    rawdtw_su_destroy(m->su);
+    m->su = su;
+    return RAWDTW_OK;
+}
+
+int rawdtw_mapper_batch_records(const rawdtw_mapper *m, uint32_t n, const uint32_t *read_ids, uint8_t *mapped, uint32_t *ref_id,
+                                uint32_t *fragment_length)
+{
+    if (!m || (n && (!read_ids || !mapped || !ref_id || !fragment_length))) return RAWDTW_ERR_INVALID;
+    for (uint32_t k = 0; k < n; k++)
+        if (read_ids[k] >= m->reads.size() || m->reads[read_ids[k]].released || !m->reads[read_ids[k]].finished) return RAWDTW_ERR_INVALID;
+    for (uint32_t k = 0; k < n; k++) su_record(m, m->reads[read_ids[k]], mapped + k, ref_id + k, fragment_length + k);
+    return RAWDTW_OK;
+}
+
+int rawdtw_mapper_su_apply(rawdtw_mapper *m, uint32_t n, const uint32_t *read_ids, uint32_t first_gated)
+{
+    if (!m) return RAWDTW_ERR_INVALID;
+    if (first_gated != RAWDTW_SU_NO_STOP && first_gated > n) return fail(m, RAWDTW_ERR_INVALID, "first_gated past the batch");
+    const int st = su_check_batch(m, n, read_ids);
+    if (st != RAWDTW_OK) return st;
+    m->su_closed_any = true;
+    const bool was_stopped = m->su_stopped;
+    for (uint32_t k = 0; k < n; k++) {
+        MRead &rd = m->reads[read_ids[k]];
+        rd.closed = true;
+        if (was_stopped) continue; // (dropped when the stop fired: still no line)
+        if (first_gated != RAWDTW_SU_NO_STOP && k >= first_gated) rd.gated = true;
+        else if (high_confidence(m, rd.chains)) m->su_mapped++;
+    }
+    if (was_stopped || first_gated == RAWDTW_SU_NO_STOP) return RAWDTW_OK;
+    // the stop: the pipeline ends at step 0 of the next mini-batch (rmap.cpp:885) -- what is not in a closed batch is never mapped
+    m->su_stopped = true;
+    for (MRead &rd : m->reads)
+        if (!rd.released && !rd.closed) { rd.finished = true; rd.dropped = true; }
+    return RAWDTW_OK;
+}
+
+int rawdtw_mapper_su_batch(rawdtw_mapper *m, uint32_t n, const uint32_t *read_ids, uint32_t *stop)
+{
+    if (!m || !stop) return RAWDTW_ERR_INVALID;
+    int st = su_check_batch(m, n, read_ids);
+    if (st != RAWDTW_OK) return st;
+    std::vector<uint8_t> mapped(n);
+    std::vector<uint32_t> ref_id(n), frag(n);
+    for (uint32_t k = 0; k < n; k++) su_record(m, m->reads[read_ids[k]], &mapped[k], &ref_id[k], &frag[k]);
+    uint32_t s = 0;
+    st = rawdtw_su_feed(m->su, n, mapped.data(), ref_id.data(), frag.data(), &s);
+    if (st != RAWDTW_OK) return fail(m, st, "rawdtw_su_feed failed");
+    // (a batch after the stop: its reads were dropped and stay without a line; the feed counted nothing and repeats the stop)
+    st = rawdtw_mapper_su_apply(m, n, read_ids, s && !m->su_stopped ? s : RAWDTW_SU_NO_STOP);
+    if (st != RAWDTW_OK) return st;
+    *stop = s;
+    return RAWDTW_OK;
+}
+
+int rawdtw_mapper_su_state(const rawdtw_mapper *m, int *stopped, uint32_t *n_mapped_at_stop)
+{
+    if (!m) return RAWDTW_ERR_INVALID;
+    if (stopped) *stopped = m->su_stopped ? 1 : 0;
+    if (n_mapped_at_stop) *n_mapped_at_stop = m->su_stopped ? m->su_mapped : 0u;
+    return RAWDTW_OK;
 }
 
 } // extern "C"

@@ -22,6 +22,9 @@ import numpy as np
 from . import mapping as M
 from .align import (RI_M_DTW_EVALUATE_CHAINS, RI_M_DTW_LOG_SCORES, RI_M_DTW_OUTPUT_CIGAR, Batch, CandidateBatch, Chain,
                     MapOpt, align_chain)
+
+RI_M_SEQUENCEUNTIL = 0x1    # src/roptions.h: --sequence-until
+RI_M_OUTPUT_CHAINS = 0x20   # --output-chains
 from .dtw import ANCHOR_DTYPE
 
 CARRY_DTYPE = np.dtype([("prev_src", "<u8"), ("parts", "<u4"), ("flags", "<u4"), ("start_t", "<u4"), ("start_q", "<u4")])  # rawdtw_carry_t
@@ -380,7 +383,7 @@ def _vp(a):
     return C.c_void_p(a.ctypes.data)
 
 
-def map_reads(seeds, read_ids, scorer, opt: MapOpt, stop: M.StopOpt = M.StopOpt(), e: int = 6, log=None):
+def map_reads(seeds, read_ids, scorer, opt: MapOpt, stop: M.StopOpt = M.StopOpt(), e: int = 6, log=None, output_chains: bool = False):
     """Runs chunk rounds until every read stopped; returns the PAF lines in read order.
 
     Flags (src/roptions.h:13-15): DTW runs when RI_M_DTW_EVALUATE_CHAINS or RI_M_DTW_LOG_SCORES is set
@@ -388,7 +391,8 @@ def map_reads(seeds, read_ids, scorer, opt: MapOpt, stop: M.StopOpt = M.StopOpt(
     (rmap.cpp:525) -- with LOG_SCORES alone every chain stays, carrying its alignment score (which the
     sort of gen_primary_chains then sees first, rmap.h:41-45).  With RI_M_DTW_OUTPUT_CIGAR the best chain of
     a mapped read is aligned once more with traceback (rmap.cpp:715-717).  `log`, when given, receives the
-    lines --dtw-log-scores writes to stderr (rmap.cpp:308-312), in order."""
+    lines --dtw-log-scores writes to stderr (rmap.cpp:308-312), in order.  `output_chains`: --output-chains
+    (RI_M_OUTPUT_CHAINS, the anchors:s: tag of rmap.cpp:745-747)."""
     copt = M.default_chain_opt(e)
     jobs = {r: seeds.read_job(r) for r in read_ids}
     names = [f"seq{s}" for s in range(len(seeds.lens))]
@@ -458,7 +462,7 @@ def map_reads(seeds, read_ids, scorer, opt: MapOpt, stop: M.StopOpt = M.StopOpt(
                 log.append(score_log_line(rj.chains[0]))
         rs = M.ReadState(rj.name, rj.qlen, rj.offset, rj.chunks_done if not rj.broke_early else rj.chunks_done - 1,
                          rj.broke_early, 0.0, rj.chains)
-        lines.append(M.paf_line(rs, names, [int(x) for x in seeds.lens], opt, stop))
+        lines.append(M.paf_line(rs, names, [int(x) for x in seeds.lens], opt, stop, output_chains=output_chains))
     return lines, rounds
 
 
@@ -490,7 +494,10 @@ class CMapper:
     `set_scorer` only (CPU harnesses)."""
 
     def __init__(self, engine, opt: MapOpt, stop: M.StopOpt, seq_names, seq_lens, slot_events: int, max_reads: int, carry: bool = True,
-                 threads: int = 1, groups: int = 1, e: int = 6, device_chain: bool = False):
+                 threads: int = 1, groups: int = 1, e: int = 6, device_chain: bool = False, output_chains: bool = False,
+                 sequence_until=None):
+        """`output_chains`: --output-chains (flag 0x20).  `sequence_until`: --sequence-until (flag 0x1) -- True for the defaults of
+        roptions.c:43-46, or a dict of rawdtw_su_opt_t's fields (t_threshold, tn_samples, ttest_freq, tmin_reads, contracted)."""
         import ctypes as C
 
         from ._lib import MapperOpt, load_library
@@ -498,7 +505,7 @@ class CMapper:
         self.lib = engine.lib if engine is not None else load_library()
         self.engine = engine
         mo = MapperOpt()
-        mo.flag = opt.flag
+        mo.flag = opt.flag | (RI_M_OUTPUT_CHAINS if output_chains else 0) | (RI_M_SEQUENCEUNTIL if sequence_until else 0)
         mo.align = opt.c_struct()
         mo.chain = M.default_chain_opt(e)
         mo.min_bestmap_ratio, mo.min_meanmap_ratio, mo.min_chain_anchor = stop.min_bestmap_ratio, stop.min_meanmap_ratio, stop.min_chain_anchor
@@ -512,6 +519,9 @@ class CMapper:
         if st != 0:
             raise RuntimeError(f"rawdtw_mapper_create -> {st}")
         self._cb = None
+        self.sequence_until = bool(mo.flag & RI_M_SEQUENCEUNTIL)
+        if isinstance(sequence_until, dict):
+            self.set_sequence_until(**sequence_until)
 
     def _check(self, st):
         if st != 0:
@@ -590,6 +600,51 @@ class CMapper:
         return dict(host_phase_ms=t[0], layout_ms=t[1], submit_ms=t[2], fetch_wait_ms=t[3], round_end_ms=t[4], anchor_bytes=int(t[5]),
                     event_bytes=int(t[6]), other_bytes=int(t[7]))
 
+    # ---- --sequence-until (rawdtw_mapper_set_sequence_until / su_batch / batch_records / su_apply / su_state) ----
+    def set_sequence_until(self, t_threshold=1.5, tn_samples=5, ttest_freq=500, tmin_reads=500, contracted=False):
+        """the parameters, before the first batch is closed; turns sequence-until on"""
+        import ctypes as C
+
+        from ._lib import SuOpt
+
+        o = SuOpt(float(t_threshold), int(tn_samples), int(ttest_freq), int(tmin_reads), int(bool(contracted)))
+        self._check(self.lib.rawdtw_mapper_set_sequence_until(self._h, C.byref(o)))
+        self.sequence_until = True
+
+    def su_batch(self, read_ids) -> int:
+        """close one mini-batch (its reads in input order, every one finished); returns the stop (0, or k + 1: the test passed at
+        read k of the batch that fired)"""
+        import ctypes as C
+
+        ids = np.ascontiguousarray(read_ids, np.uint32)
+        s = C.c_uint32()
+        self._check(self.lib.rawdtw_mapper_su_batch(self._h, len(ids), _vp(ids), C.byref(s)))
+        return s.value
+
+    def batch_records(self, read_ids):
+        """the batch's records (mapped u8, ref_id u32, fragment_length u32), as the reference leaves them in reg0"""
+        ids = np.ascontiguousarray(read_ids, np.uint32)
+        n = len(ids)
+        mapped, ref_id, frag = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        self._check(self.lib.rawdtw_mapper_batch_records(self._h, n, _vp(ids), _vp(mapped), _vp(ref_id), _vp(frag)))
+        return mapped[:n], ref_id[:n], frag[:n]
+
+    def su_apply(self, read_ids, first_gated=None):
+        """close this mapper's block of a mini-batch with a decision taken elsewhere: None = no stop; else the stop fired and the
+        block's reads from position first_gated on are gated (0: all, len(read_ids): none)"""
+        from ._lib import RAWDTW_SU_NO_STOP
+
+        ids = np.ascontiguousarray(read_ids, np.uint32)
+        self._check(self.lib.rawdtw_mapper_su_apply(self._h, len(ids), _vp(ids), RAWDTW_SU_NO_STOP if first_gated is None else int(first_gated)))
+
+    def su_state(self):
+        """(stopped, mapped reads before the gate -- the number the reference's "Sequence Until is activated" message prints)"""
+        import ctypes as C
+
+        st, n = C.c_int(), C.c_uint32()
+        self._check(self.lib.rawdtw_mapper_su_state(self._h, C.byref(st), C.byref(n)))
+        return bool(st.value), n.value
+
     def set_scorer(self, fn):
         """fn(chain_off, anchor_off, anchors, chain_seq, chain_strand, read_events: list of arrays) -> (score f32, keep u8);
         harnesses only (bench.py's cpu_baseline, the CPU tests) -- see rawdtw_mapper_set_scorer"""
@@ -633,19 +688,57 @@ class CMapper:
             self._h = None
 
 
-def map_reads_c(seeds, read_ids, cm: CMapper):
-    """map_reads through the library's mapper: chunk rounds until every read stopped; the PAF lines in read order, the rounds."""
+def map_reads_c(seeds, read_ids, cm: CMapper, batch_size=None, su=None):
+    """map_reads through the library's mapper: chunk rounds until every read stopped; the PAF lines in read order, the rounds.
+
+    The reads go in mini-batches of `batch_size` (None: one of all of them), at most two at a time -- the next batch's reads are
+    added while the one before is still mapped, as the reference's pipeline reads a mini-batch ahead.  With sequence-until on in
+    `cm`, every batch is closed in input order once all its reads are finished: through CMapper.su_batch, or -- when `su`, a
+    host-side state with the interface of mapping.SequenceUntil (CSequenceUntil), is given -- through the split form a multi-rank
+    host uses (batch_records, the walk of shard.sequence_until_round, su_apply).  After the stop no read is added; a read
+    without a line (sequence-until dropped it, or it was never added) has "" in the list."""
+    from . import shard
+
+    read_ids = list(read_ids)
     jobs = {r: seeds.read_job(r) for r in read_ids}
-    ids = {r: cm.add_read(jobs[r].name, jobs[r].qlen, jobs[r].n_chunks_available) for r in read_ids}
-    rounds = 0
+    closing = cm.sequence_until
+    if su is not None and not closing:
+        raise ValueError("a host-side sequence-until state needs a mapper with sequence-until on")
+    bs = max(1, int(batch_size)) if batch_size else max(1, len(read_ids))
+    batches = [read_ids[i:i + bs] for i in range(0, len(read_ids), bs)]
+
+    def close(b):
+        rid = [ids[r] for r in b]
+        if su is None:
+            return cm.su_batch(rid) != 0
+        mapped, ref_id, frag = cm.batch_records(rid)
+        s = shard.sequence_until_round(None, su, mapped, ref_id, frag, len(rid))
+        cm.su_apply(rid, s if s else None)
+        return s != 0
+
+    ids, pending = {}, []   # pending: batches added and not closed yet, oldest first
+    nxt, rounds, stopped = 0, 0, False
     while True:
+        while not stopped and nxt < len(batches) and len(pending) < 2:
+            for r in batches[nxt]:
+                ids[r] = cm.add_read(jobs[r].name, jobs[r].qlen, jobs[r].n_chunks_available)
+            pending.append(batches[nxt])
+            nxt += 1
+        while pending and all(cm.state(ids[r])[0] for r in pending[0]):
+            b = pending.pop(0)
+            if closing and close(b):
+                stopped = True
+                pending.clear()   # (the mapper finished their reads: no line)
+        if not stopped and nxt < len(batches) and len(pending) < 2:
+            continue
         act, chunks = [], []
-        for r in read_ids:
-            fin, done = cm.state(ids[r])
-            if fin or done >= jobs[r].n_chunks_available:
-                continue
-            act.append(ids[r])
-            chunks.append(seeds.chunk(r, done))
+        for b in pending:
+            for r in b:
+                fin, done = cm.state(ids[r])
+                if fin or done >= jobs[r].n_chunks_available:
+                    continue
+                act.append(ids[r])
+                chunks.append(seeds.chunk(r, done))
         if not act:
             break
         cm.round(act, chunks)
@@ -653,4 +746,86 @@ def map_reads_c(seeds, read_ids, cm: CMapper):
     st = cm.finish()
     if st != 0:
         raise RuntimeError(f"rawdtw_mapper_finish -> {st}")
-    return [cm.paf(ids[r]) for r in read_ids], rounds
+    return [cm.paf(ids[r]) if r in ids else "" for r in read_ids], rounds
+
+
+class CSequenceUntil:
+    """The library's sequence-until state (rawdtw_su_*, rawalign_amd/csrc/rawdtw_su.cpp) behind the interface of
+    mapping.SequenceUntil (add_mapped_read, stop, nreads, c_estimations), so that shard.sequence_until_round works with either."""
+
+    def __init__(self, n_seq: int, t_threshold: float = 1.5, tn_samples: int = 5, ttest_freq: int = 500, tmin_reads: int = 500,
+                 contracted: bool = False):
+        import ctypes as C
+
+        from ._lib import RawDTWError, SuOpt, load_library
+
+        self.lib = load_library()
+        self.n_seq = int(n_seq)
+        self._h = C.c_void_p()
+        o = SuOpt(float(t_threshold), int(tn_samples), int(ttest_freq), int(tmin_reads), int(bool(contracted)))
+        st = self.lib.rawdtw_su_create(self.n_seq, C.byref(o), C.byref(self._h))
+        if st != 0:
+            self._h = None
+            raise RawDTWError(st, "rawdtw_su_create: n_seq, tn_samples and ttest_freq must be > 0")
+        self.stop = 0
+
+    def feed(self, mapped, ref_id, fragment_length) -> int:
+        """records in read order; returns rawdtw_su_feed's stop (0, or k + 1 with k counted from the first record of the call
+        that fired -- every later call repeats it)"""
+        import ctypes as C
+
+        mapped = np.ascontiguousarray(mapped, np.uint8)
+        ref_id = np.ascontiguousarray(ref_id, np.uint32)
+        frag = np.ascontiguousarray(fragment_length, np.uint32)
+        assert len(mapped) == len(ref_id) == len(frag)
+        s = C.c_uint32()
+        st = self.lib.rawdtw_su_feed(self._h, len(mapped), _vp(mapped), _vp(ref_id), _vp(frag), C.byref(s))
+        if st != 0:
+            raise RuntimeError(f"rawdtw_su_feed -> {st}")
+        if s.value and not self.stop:
+            self.stop = s.value
+        return s.value
+
+    def add_mapped_read(self, ref_id: int, fragment_length: int, k: int) -> bool:
+        """one mapped read, in output order; k is its index in the mini-batch.  True when the stop fires (stop = k + 1)."""
+        if self.stop:
+            return True
+        if self.feed([1], [int(ref_id)], [int(fragment_length) & 0xFFFFFFFF]):
+            self.stop = k + 1
+            return True
+        return False
+
+    def _state(self):
+        import ctypes as C
+
+        n, ne, ab = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        c = np.zeros(self.n_seq, np.uint32)
+        self.lib.rawdtw_su_state(self._h, C.byref(n), C.byref(ne), C.byref(ab), _vp(c))
+        return n.value, ne.value, ab.value, c
+
+    @property
+    def nreads(self) -> int:
+        return self._state()[0]
+
+    @property
+    def nestimations(self) -> int:
+        return self._state()[1]
+
+    @property
+    def ab_count(self) -> int:
+        return self._state()[2]
+
+    @property
+    def c_estimations(self) -> np.ndarray:
+        return self._state()[3]
+
+    def close(self):
+        if self._h:
+            self.lib.rawdtw_su_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 -- interpreter shutdown
+            pass

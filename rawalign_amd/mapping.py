@@ -177,8 +177,8 @@ def paf_line(rs: ReadState, seq_names, seq_lens, opt: MapOpt, stop: StopOpt = St
                  "sm:f:" + _to_string(mean_chain_score), "at:f:" + _to_string(at), "aq:f:" + _to_string(aq)]
         if opt.flag & RI_M_DTW_OUTPUT_CIGAR:
             tags += ["alns:f:" + _to_string(f32(c0.alignment_score)), "aln:s:" + dtwresult_to_string(c0.dtw_result)]
-        if output_chains:
-            tags += ["anchors:s:" + "".join("(%d,%d)" % (int(x["target_position"]), int(x["query_position"]))
+        if output_chains:  # rmap.cpp:745-747, anchors_to_string (rmap.cpp:53-63): "(query,target)" per anchor, end-first
+            tags += ["anchors:s:" + "".join("(%d,%d)" % (int(x["query_position"]), int(x["target_position"]))
                                             for x in c0.anchors)]
         a = c0.anchors
         read_end = int(np.uint32(scale * f32(np.uint32(a[0]["query_position"]))))
@@ -216,6 +216,7 @@ class SequenceUntil:
     tn_samples: int = 5
     ttest_freq: int = 500
     tmin_reads: int = 500
+    contracted: bool = False   # find_outlier as the reference's FMA build computes it (mapping.find_outlier)
 
     def __post_init__(self):
         self.c_estimations = np.zeros(self.n_seq, np.uint32)  # rmap.h:76: uint32_t (wraps like the reference's)
@@ -241,7 +242,7 @@ class SequenceUntil:
                 self.cur = 0
             fire = self.nestimations >= self.tn_samples
             self.nestimations += 1
-            if fire and find_outlier(self.estimations) <= np.float32(self.t_threshold):
+            if fire and find_outlier(self.estimations, self.contracted) <= np.float32(self.t_threshold):
                 self.stop = k + 1
                 return True
         return False
