@@ -618,8 +618,8 @@ int rawdtw_mapper_add_read(rawdtw_mapper *m, const char *name, uint32_t qlen /* 
 /* a finished read whose line has been written: its slot in the event arena goes to the next rawdtw_mapper_add_read */
 int rawdtw_mapper_release_read(rawdtw_mapper *m, uint32_t read_id);
 /* one chunk round: read read_ids[k] gets events[event_off[k] .. event_off[k+1]) and hits[hit_off[k] .. hit_off[k+1]).
- * All reads are checked before anything changes; when the device round fails afterwards, the reads are put back as they
- * were (a failed round can be repeated). */
+ * All reads are checked before anything changes; when the round fails afterwards (the device or the scorer), the reads and
+ * the mapper are put back as they were (a failed round can be repeated). */
 int rawdtw_mapper_round(rawdtw_mapper *m, uint32_t n_reads, const uint32_t *read_ids, const uint64_t *event_off,
                         const float *events, const uint64_t *hit_off, const rawdtw_seed_hit_t *hits);
 /* (With device_chain and one read group a page-locked `events` array -- rawdtw_host_alloc -- goes to the device as it is, without a

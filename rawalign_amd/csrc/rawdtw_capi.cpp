@@ -67,6 +67,7 @@ int rawdtw_create(int device_ordinal, rawdtw_ctx **out)
         int v = atoi(e);
         ctx->lane_max_radius = v < 0 ? 0 : (v > kMaxLaneRadius ? kMaxLaneRadius : v);
     }
+    if (const char *e = getenv("RAWDTW_CHAIN_MAX_SEEDS")) ctx->chain_max_seeds = (uint32_t)std::max(1l, strtol(e, nullptr, 10));
     if (const char *e = getenv("RAWDTW_OPTS")) { // "name=value,name=value": rawdtw_set_option for each (tuning runs)
         std::string all(e);
         size_t pos = 0;

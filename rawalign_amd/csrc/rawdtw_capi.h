@@ -143,6 +143,7 @@ struct rawdtw_ctx {
     uint64_t n_ev = 0, cap_ev = 0;
     bool own_ev = false;
     struct rawdtw_chain_ws *chain_ws = nullptr; // rawdtw_chain_round's device block (rawdtw_chain.hip), grow-only
+    uint32_t chain_max_seeds = 0; // tests: RAWDTW_CHAIN_MAX_SEEDS lowers rawdtw_chain_round's cap on seeds a read, so that small rounds take the declined path (0: no)
     std::string err;
 };
 

@@ -338,8 +338,7 @@ int rawdtw_chain_round_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uin
         if (seed_off[r + 1] < seed_off[r]) return fail(ctx, RAWDTW_ERR_INVALID, "offsets do not ascend");
         most = (uint32_t)std::max<uint64_t>(most, std::min<uint64_t>(seed_off[r + 1] - seed_off[r], 0xffffffffull));
     }
-    uint32_t seed_cap = kChainMaxSeeds; // (tests: RAWDTW_CHAIN_MAX_SEEDS lowers the cap, so that small rounds take the declined path)
-    if (const char *e = getenv("RAWDTW_CHAIN_MAX_SEEDS")) seed_cap = std::min<uint32_t>(kChainMaxSeeds, (uint32_t)std::max(1l, strtol(e, nullptr, 10)));
+    const uint32_t seed_cap = ctx->chain_max_seeds ? std::min(kChainMaxSeeds, ctx->chain_max_seeds) : kChainMaxSeeds;
     if (most > seed_cap) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, "a read has more seeds than the device chains (2048): chain this round on the host");
     uint32_t n2 = 64;
     while (n2 < most) n2 <<= 1;

@@ -14,9 +14,9 @@
 //                (or the whole lists for a round without a predecessor), the new events' segments
 //   submit       rawdtw_events_append + rawdtw_batch_submit_carry / rawdtw_batch_submit: enqueued, not waited for
 // then, group by group: fetch (the only wait), and the round's end per read on the pool: gen_primary_chains, comp_mapq, the
-// stop rule (532-541, 692).  With two groups one group's host phase runs while the other's batch is on the device, and one
-// group's round end while the other's batch finishes -- the overlap the reference gets from its two pipeline workers
-// (rmap.cpp:1015,1033).
+// stop rule (532-541, 692), into the round's own state -- the commit after the last group is the one place it reaches the reads.
+// With two groups one group's host phase runs while the other's batch is on the device, and one group's round end while the
+// other's batch finishes -- the overlap the reference gets from its two pipeline workers (rmap.cpp:1015,1033).
 //
 // Event detection and seeding stay in RawAlign (revent.c, rsketch.c, rawindex.cpp): the caller hands in each chunk's events
 // and seed hits.  rawalign_amd/mapper.py is the Python mirror of the control flow; tests/test_mapper.py and
@@ -36,6 +36,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -79,6 +80,7 @@ template <typename T> struct PinBuf {
     PinBuf() = default;
     PinBuf(const PinBuf &) = delete;
     PinBuf &operator=(const PinBuf &) = delete;
+    PinBuf &operator=(PinBuf &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); std::swap(pinned, o.pinned); return *this; }
     ~PinBuf() { release(); }
     void release()
     {
@@ -116,10 +118,9 @@ struct RoundArrays {
     PinBuf<uint64_t> seed_off;           // device chaining (opt.device_chain): the reads' seed lists in, the chains' records out
     PinBuf<rawdtw_seed_t> seeds;
     PinBuf<rawdtw_chain_rec_t> recs;
-    bool device_chained = false;
     std::vector<uint32_t> chain_seq; // (the external scorer's view)
     std::vector<int32_t> chain_strand;
-    uint64_t n_reads = 0, n_chains = 0, n_anchors = 0, n_new = 0, n_new_events = 0, n_seg = 0;
+    uint64_t n_reads = 0, n_chains = 0, n_anchors = 0; // (the sizes the next round's matching reads again)
     rawdtw_batch *batch = nullptr;
     uint64_t round_id = 0;
     bool carried = false;
@@ -136,12 +137,12 @@ struct Group {
     uint64_t hw_reads = 0, hw_chains = 0, hw_anchors = 0, hw_new = 0, hw_events = 0, hw_seg = 0, hw_seeds = 0;
 };
 
-// what the host phase leaves per read of the round
+// what a round leaves per read until its commit (the host phase, the round's end)
 struct RoundRead {
     std::vector<MChain> chains;          // the round's candidate chains in evaluation order
     std::vector<rawdtw_carry_t> carry;   // per chain
     std::vector<uint64_t> ref_base;      // per chain
-    std::vector<uint8_t> keep;
+    std::vector<MChain> primary;         // the round's end: its primary chains, best first (rd.chains at the commit)
     std::string log;
     uint64_t ne = 0;
     uint32_t ev_before = 0, off_before = 0;
@@ -337,59 +338,43 @@ int fail(rawdtw_mapper *m, int st, const std::string &msg)
     return st;
 }
 
-void drop_batches(rawdtw_mapper *m)
+void drop_batches(rawdtw_mapper *m) // (and with them what a round could carry from)
 {
-    for (Group &g : m->groups)
+    for (Group &g : m->groups) {
         for (RoundArrays &ra : g.buf) {
             if (ra.batch) rawdtw_batch_destroy(ra.batch);
             ra.batch = nullptr;
         }
+        g.has_prev = false;
+    }
 }
 
-struct Seed { uint32_t key, t, q; };
-
-// The host phase of one read: the chunk's events, the round's anchors, chaining, evaluation order, carry records.
-// `pv` = the arrays of the round before of the read's group (null: none, or the read was not in it).
-// the chunk's events (rmap.cpp:554-575); false: the chunk is below min_events -- no gen_chains this round
-bool host_phase_events(rawdtw_mapper *m, MRead &rd, RoundRead &rr, const float *ev, uint64_t ne)
+// a read's seeds for the round, unsorted: the previous chains' anchors (rmap.cpp:344-357), then the chunk's seed hits with their query
+// positions from the chunk's start (371-391)
+uint64_t seed_count(const MRead &rd, uint64_t n_hits)
 {
-    rr.ne = ne;
-    rr.ev_before = rd.n_events;
-    rr.off_before = rd.offset;
-    if (m->keep_host_events) rd.events.insert(rd.events.end(), ev, ev + ne); // rmap.cpp:554-567
-    rd.n_events += (uint32_t)ne;
-    if (ne < m->opt.min_events) { rr.skipped = true; return false; } // rmap.cpp:569-572: no gen_chains, reg->offset stays
-    rr.chunk_start = rd.offset;  // reg->offset (rmap.cpp:574)
-    rd.offset += (uint32_t)ne;   // rmap.cpp:575
-    return true;
+    for (const MChain &ch : rd.chains) n_hits += ch.anchors.size();
+    return n_hits;
 }
 
-void host_phase_chain(rawdtw_mapper *m, MRead &rd, RoundRead &rr, const rawdtw_seed_hit_t *hits, uint64_t n_hits, const RoundArrays *pv, bool runs_dtw);
-
-void host_phase_read(rawdtw_mapper *m, MRead &rd, RoundRead &rr, const float *ev, uint64_t ne, const rawdtw_seed_hit_t *hits, uint64_t n_hits,
-                     const RoundArrays *pv, bool runs_dtw)
+void write_seeds(const MRead &rd, const rawdtw_seed_hit_t *hits, uint64_t n_hits, uint32_t chunk_start, rawdtw_seed_t *out)
 {
-    if (host_phase_events(m, rd, rr, ev, ne)) host_phase_chain(m, rd, rr, hits, n_hits, pv, runs_dtw);
-}
-
-void host_phase_chain(rawdtw_mapper *m, MRead &rd, RoundRead &rr, const rawdtw_seed_hit_t *hits, uint64_t n_hits, const RoundArrays *pv, bool runs_dtw)
-{
-    const uint32_t chunk_start = rr.chunk_start;
-    // rmap.cpp:344-357: re-seed with the previous chains' anchors; rmap.cpp:371-391: the chunk's seed hits
-    std::vector<Seed> seeds;
-    size_t n_prev = 0;
-    for (const MChain &ch : rd.chains) n_prev += ch.anchors.size();
-    seeds.reserve(n_prev + n_hits);
     for (const MChain &ch : rd.chains)
-        for (const rawdtw_anchor_t &a : ch.anchors) seeds.push_back(Seed{ch.ref * 2u + (uint32_t)ch.strand, a.target_position, a.query_position});
+        for (const rawdtw_anchor_t &a : ch.anchors) *out++ = rawdtw_seed_t{ch.ref * 2u + (uint32_t)ch.strand, a.target_position, a.query_position};
     for (uint64_t h = 0; h < n_hits; h++)
-        seeds.push_back(Seed{hits[h].ref_seq * 2u + (uint32_t)(hits[h].strand ? 1 : 0), hits[h].target_position, hits[h].query_position + chunk_start});
+        *out++ = rawdtw_seed_t{hits[h].ref_seq * 2u + (uint32_t)(hits[h].strand ? 1 : 0), hits[h].target_position, hits[h].query_position + chunk_start};
+}
+
+// The host phase of one read after its events: the round's anchors, chaining, evaluation order, carry records -- the round's chains
+// in rr.chains.  `pv` = the arrays of the round before of the read's group (null: none, or the read was not in it).
+void host_phase_chain(rawdtw_mapper *m, const MRead &rd, RoundRead &rr, const rawdtw_seed_hit_t *hits, uint64_t n_hits, const RoundArrays *pv, bool runs_dtw)
+{
+    std::vector<rawdtw_seed_t> seeds(seed_count(rd, n_hits));
+    write_seeds(rd, hits, n_hits, rr.chunk_start, seeds.data());
     // by (sequence, strand), then (target, query): rmap.cpp:396-401 sorts every list; rmap.cpp:432-433 walks them sequence-major,
     // strand 0 then 1
-    std::sort(seeds.begin(), seeds.end(), [](const Seed &a, const Seed &b) {
-        if (a.key != b.key) return a.key < b.key;
-        if (a.t != b.t) return a.t < b.t;
-        return a.q < b.q;
+    std::sort(seeds.begin(), seeds.end(), [](const rawdtw_seed_t &a, const rawdtw_seed_t &b) {
+        return std::tie(a.key, a.target_position, a.query_position) < std::tie(b.key, b.target_position, b.query_position);
     });
     std::vector<MChain> chains;
     float maxs = 0.0f;
@@ -401,7 +386,7 @@ void host_phase_chain(rawdtw_mapper *m, MRead &rd, RoundRead &rr, const rawdtw_s
         size_t s1 = s0;
         while (s1 < seeds.size() && seeds[s1].key == seeds[s0].key) s1++;
         a.resize(s1 - s0);
-        for (size_t q = s0; q < s1; q++) a[q - s0] = rawdtw_anchor_t{seeds[q].t, seeds[q].q};
+        for (size_t q = s0; q < s1; q++) a[q - s0] = rawdtw_anchor_t{seeds[q].target_position, seeds[q].query_position};
         outa.resize(std::max<size_t>(a.size(), 1));
         const int nc = rawdtw_chain_anchors(&m->opt.chain, a.data(), (uint32_t)a.size(), &maxs, outc.data(), off.data(), outa.data(), cap, outa.size());
         if (nc < 0) { rr.err = RAWDTW_ERR_RANGE; return; }
@@ -489,6 +474,392 @@ void su_record(const rawdtw_mapper *m, const MRead &rd, uint8_t *mapped, uint32_
     *fragment_length = mp ? rd.chains[0].end_position - rd.chains[0].start_position + 1u : 0u;
 }
 
+// a chaining round begun on the device and not to be used: ended, its results dropped
+void discard_chain_round(rawdtw_ctx *ctx)
+{
+    const rawdtw_anchor_t *a = nullptr; const uint64_t *rb = nullptr; const uint32_t *qb = nullptr;
+    (void)rawdtw_chain_round_end(ctx, &a, &rb, &qb);
+}
+
+// a round's sizes in one group (0 where its path does not know them)
+struct Sizes { uint64_t reads = 0, chains = 0, anchors = 0, new_anchors = 0, events = 0, seg = 0, seeds = 0; };
+
+// One rawdtw_mapper_round after its checks.  The phases write only into the round's own state (rr, the groups' buffers of the round
+// at hand, per); commit() is the one place the result reaches the reads and the mapper, and rollback() drops it.  The exception is
+// the host's copy of a read's events, which the external scorer reads during the round: appended early, cut back by the rollback.
+struct Round {
+    rawdtw_mapper *m;
+    uint32_t n_reads;
+    const uint32_t *read_ids; const uint64_t *event_off; const float *events; const uint64_t *hit_off; const rawdtw_seed_hit_t *hits;
+    double t0; // (the last lap)
+    uint32_t G = (uint32_t)m->groups.size(); // (1 or 2)
+    uint64_t id = m->rounds + 1;
+    bool runs_dtw = (m->opt.flag & (0x2 | 0x8)) != 0, on_device = runs_dtw && !m->scorer;
+    // the caller's event array goes to the device as it is when it is page-locked (rawdtw_host_alloc) and one read group takes the whole round:
+    // its reads' chunks ARE the segments, in order -- no copy into the mapper's own staging (a third of the host phase)
+    bool events_in_place = on_device && m->opt.device_chain && G == 1 && event_off[n_reads] > 0 && rawdtw_host_is_page_locked(events) == 1;
+    std::vector<RoundRead> rr = std::vector<RoundRead>(n_reads);
+    struct PerGroup { bool chaining = false; uint64_t ns = 0, nev = 0, nseg = 0, scored = 0, reused = 0; } per[2];
+    int status = RAWDTW_OK;
+    std::string msg;
+
+    MRead &read(uint32_t k) const { return m->reads[read_ids[k]]; }
+    uint32_t arena_base(const MRead &rd) const { return (G == 2 ? rd.slot / 2 : rd.slot) * m->opt.slot_events; } // its slot in its group's event arena
+    bool ok() const { return status == RAWDTW_OK; }
+    void failed(int st, const std::string &s) { if (ok()) { status = st; msg = s; } }
+    void lap(int slot) { const double t = now_ms(); m->timing[slot] += t - t0; t0 = t; } // (include/rawdtw.h: rawdtw_mapper_timing)
+
+    void deal() // the round's reads over the groups, into each group's other buffer
+    {
+        for (Group &g : m->groups) { g.cur ^= 1; g.buf[g.cur].ks.clear(); }
+        for (uint32_t k = 0; k < n_reads; k++) { Group &g = m->groups[read(k).slot % G]; g.buf[g.cur].ks.push_back(k); }
+    }
+
+    // The host phase of one read: the chunk's events (rmap.cpp:554-575); false: the chunk is below min_events -- no gen_chains this round.
+    // Then host_phase_chain, or with device chaining its seed list.
+    bool append_events(uint32_t k)
+    {
+        MRead &rd = read(k);
+        RoundRead &r = rr[k];
+        r.ne = event_off[k + 1] - event_off[k];
+        r.ev_before = rd.n_events; r.off_before = rd.offset;
+        if (m->keep_host_events) rd.events.insert(rd.events.end(), events + event_off[k], events + event_off[k + 1]); // rmap.cpp:554-567
+        rd.n_events += (uint32_t)r.ne;
+        if (r.ne < m->opt.min_events) { r.skipped = true; return false; } // rmap.cpp:569-572: no gen_chains, reg->offset stays
+        r.chunk_start = rd.offset;  // reg->offset (rmap.cpp:574)
+        rd.offset += (uint32_t)r.ne; // rmap.cpp:575
+        return true;
+    }
+
+    // Both of a group's buffers grown to its high-water marks, as its path needs them: chaining on the device (seed lists in, chains out)
+    // or on the host (anchor lists, the events' staging, carry records), page-locked unless an external scorer takes the round.  The
+    // round before's first n_reads + 1 / n_chains + 1 / n_anchors + 1 entries survive a growth (the host chaining's matching reads them).
+    bool size_arrays(Group &g, const Sizes &n, bool dev)
+    {
+        const bool pin = on_device, carry = on_device && !dev && m->opt.carry;
+        g.hw_reads = std::max(g.hw_reads, n.reads); g.hw_chains = std::max(g.hw_chains, n.chains); g.hw_anchors = std::max(g.hw_anchors, n.anchors);
+        g.hw_new = std::max(g.hw_new, n.new_anchors); g.hw_events = std::max(g.hw_events, n.events); g.hw_seg = std::max(g.hw_seg, n.seg);
+        g.hw_seeds = std::max(g.hw_seeds, n.seeds);
+        if (dev) g.hw_chains = std::max<uint64_t>(g.hw_chains, g.hw_reads * 32); // (the device's cap on chains a read)
+        const uint64_t nr = g.hw_reads + 1, nc = g.hw_chains + 1;
+        for (int b = 0; b < 2; b++) {
+            RoundArrays &x = g.buf[g.cur ^ b];
+            const bool kept = b == 1 && !dev;
+            const size_t k_r = kept ? x.n_reads + 1 : 0, k_c = kept ? x.n_chains + 1 : 0, k_a = kept ? x.n_anchors + 1 : 0;
+            bool ok = x.chain_off.ensure(nr, pin, k_r) && x.anchor_off.ensure(nc, pin, k_c) && x.read_base.ensure(nc, pin, k_c) &&
+                      x.anchors.ensure((dev ? g.hw_seeds : g.hw_anchors) + 1, pin && !(m->opt.carry && g.has_prev), k_a) && x.score.ensure(nc, pin) &&
+                      x.keep.ensure(nc, pin);
+            if (dev) ok = ok && x.seed_off.ensure(nr, pin) && x.seeds.ensure(g.hw_seeds + 1, pin) && x.recs.ensure(nc, pin);
+            else ok = ok && x.ref_base.ensure(nc, pin, k_c);
+            if (carry) ok = ok && x.new_off.ensure(nc, pin) && x.new_anchors.ensure(g.hw_new + 1, pin) && x.carry.ensure(nc, pin);
+            if (pin)
+                ok = ok && x.new_events.ensure((events_in_place ? 0 : g.hw_events) + 1, pin) && x.seg_src.ensure(g.hw_seg + 2, pin) &&
+                     x.seg_dst.ensure((dev ? g.hw_reads : g.hw_seg) + 1, pin);
+            if (!ok) { failed(RAWDTW_ERR_OOM, "host allocation failed"); return false; }
+        }
+        return true;
+    }
+
+    // ---- a group's first half: the host phase, lay-out and submission; with device chaining the chaining begun instead ----
+    void begin_group(uint32_t gi)
+    {
+        Group &g = m->groups[gi]; RoundArrays &ra = g.buf[g.cur];
+        const RoundArrays &pb = g.buf[g.cur ^ 1];
+        ra.carried = false; ra.round_id = id; ra.n_reads = ra.ks.size();
+        if (on_device && m->opt.device_chain) {
+            if (!device_begin(gi) && ok()) host_round(gi, nullptr, true);
+            return;
+        }
+        const RoundArrays *pv = nullptr;
+        if (on_device && m->opt.carry && g.has_prev && pb.batch && rawdtw_batch_can_carry(g.ctx, pb.batch, &m->opt.align)) {
+            size_t known = 0; // (a round none of whose reads was in the round before has nothing to take over: submitted whole)
+            for (size_t i = 0; i < ra.ks.size() && !known; i++) known += read(ra.ks[i]).last_round == pb.round_id;
+            if (known) { pv = &pb; ra.carried = true; }
+        }
+        host_round(gi, pv, false);
+    }
+
+    // ---- device chaining, first half: the host phase is the events and the seed lists; sort, chaining DP, traceback and order are
+    // enqueued (rawdtw_chain_round_begin) and run while the next group's host phase does.  false: the device declined (its cap on seeds a
+    // read) -- the events are in place on both sides, the round is chained on the host.
+    bool device_begin(uint32_t gi)
+    {
+        Group &g = m->groups[gi]; RoundArrays &ra = g.buf[g.cur];
+        const size_t nr = ra.ks.size();
+        if (nr == 0) return true; // (none of the round's reads is this group's)
+        m->pool->run(nr, 64, [&](size_t i) {
+            const uint32_t k = ra.ks[i];
+            if (append_events(k)) rr[k].n_seeds = seed_count(read(k), hit_off[k + 1] - hit_off[k]);
+        });
+        uint64_t ns = 0, nev = 0, nseg = 0;
+        for (uint32_t k : ra.ks) { RoundRead &r = rr[k]; r.seed0 = ns; ns += r.n_seeds; r.ev0 = nev; nev += r.ne; nseg += r.ne ? 1 : 0; }
+        const Sizes n{nr, 0, 0, 0, nev, nseg, ns};
+        if (!size_arrays(g, n, true)) return true;
+        write_segments(ra, events_in_place);
+        ra.seed_off[nr] = n.seeds;
+        m->pool->run(nr, 64, [&](size_t i) {
+            const uint32_t k = ra.ks[i];
+            const RoundRead &r = rr[k];
+            ra.seed_off[i] = r.seed0;
+            ra.read_base[i] = arena_base(read(k));
+            if (!r.skipped) write_seeds(read(k), hits + hit_off[k], hit_off[k + 1] - hit_off[k], r.chunk_start, ra.seeds.p + r.seed0);
+            if (r.ne && !events_in_place) memcpy(ra.new_events.p + r.ev0, events + event_off[k], r.ne * sizeof(float));
+        });
+        lap(0);
+        // the chaining first, the events behind it: the sort + DP does not read them, and rawdtw_chain_round_end waits for the round's own work only
+        // -- the events' upload (the round's largest) runs on while the host goes on
+        int st = rawdtw_chain_round_begin(g.ctx, &m->opt.chain, nr, ra.seed_off.p, ra.seeds.p, ra.read_base.p, (uint32_t)m->ref_off.size(), m->ref_off.data(),
+                                          ra.chain_off.p, ra.anchor_off.p, ra.recs.p, g.hw_chains, ra.anchors.p);
+        const bool declined = st == RAWDTW_ERR_UNSUPPORTED;
+        if (st == RAWDTW_OK || declined) {
+            int se = RAWDTW_OK;
+            if (n.seg && events_in_place) se = rawdtw_events_append(g.ctx, events, event_off[n_reads], (uint32_t)nr, event_off, ra.seg_dst.p);
+            else if (n.seg) se = rawdtw_events_append(g.ctx, ra.new_events.p, n.events, (uint32_t)n.seg, ra.seg_src.p, ra.seg_dst.p);
+            if (se != RAWDTW_OK && st == RAWDTW_OK) discard_chain_round(g.ctx);
+            if (se != RAWDTW_OK) st = se;
+        }
+        lap(2);
+        if (declined && st == RAWDTW_ERR_UNSUPPORTED) return false;
+        if (st != RAWDTW_OK) { failed(st, rawdtw_last_error(g.ctx)); return true; }
+        per[gi] = PerGroup{true, n.seeds, n.events, n.seg};
+        return true;
+    }
+
+    // second half: the wait, the DTW submission straight from the device's arrays, and -- while that batch runs -- the round's chains per read, as
+    // the host phase would have left them; a round the device declined (a read with too many chains, or an order only std::sort knows) is
+    // chained on the host.  After a failure elsewhere the chaining begun is discarded.
+    void end_device_chain(uint32_t gi)
+    {
+        Group &g = m->groups[gi]; RoundArrays &ra = g.buf[g.cur];
+        PerGroup &p = per[gi];
+        if (!p.chaining) return;
+        p.chaining = false;
+        if (!ok()) return discard_chain_round(g.ctx);
+        const size_t nr = ra.ks.size();
+        const rawdtw_anchor_t *d_anchors = nullptr; const uint64_t *d_ref_base = nullptr; const uint32_t *d_read_base = nullptr;
+        int st = rawdtw_chain_round_end(g.ctx, &d_anchors, &d_ref_base, &d_read_base);
+        if (st == RAWDTW_ERR_UNSUPPORTED) { lap(2); return host_round(gi, nullptr, true); }
+        if (st != RAWDTW_OK) return failed(st, rawdtw_last_error(g.ctx));
+        const uint64_t nc = ra.chain_off[nr], na = ra.anchor_off[nc];
+        ra.n_chains = nc; ra.n_anchors = na;
+        st = rawdtw_batch_submit_device(g.ctx, &m->opt.align, nr, ra.chain_off.p, ra.anchor_off.p, d_anchors, d_ref_base, d_read_base, &ra.batch);
+        if (st != RAWDTW_OK) return failed(st, rawdtw_last_error(g.ctx));
+        m->timing[6] += (double)(p.nev * sizeof(float));
+        m->timing[7] += (double)(p.ns * sizeof(rawdtw_seed_t) + (nr + 1) * 16 + nr * 4 + (nc + 1) * 8 + p.nseg * 12);
+        lap(2);
+        m->pool->run(nr, 32, [&](size_t i) {
+            RoundRead &r = rr[ra.ks[i]];
+            r.chain0 = ra.chain_off[i];
+            r.chains.resize(ra.chain_off[i + 1] - ra.chain_off[i]);
+            for (uint64_t c = 0; c < r.chains.size(); c++) {
+                const rawdtw_chain_rec_t &rec = ra.recs[r.chain0 + c];
+                MChain &ch = r.chains[c];
+                ch.chaining_score = rec.chaining_score; ch.ref = rec.key >> 1; ch.strand = (int32_t)(rec.key & 1u);
+                ch.start_position = rec.start_position; ch.end_position = rec.end_position;
+                const rawdtw_anchor_t *an = ra.anchors.p + ra.anchor_off[r.chain0 + c];
+                ch.anchors.assign(an, an + rec.n_anchors);
+            }
+        });
+        lap(1);
+    }
+
+    // ---- a group's round with the chains made on the host: host phase, lay-out, submit (`events_done`: a round the device declined to chain --
+    // its events are appended already, on both sides) ----
+    void host_round(uint32_t gi, const RoundArrays *pv, bool events_done)
+    {
+        const RoundArrays &ra = m->groups[gi].buf[m->groups[gi].cur];
+        m->pool->run(ra.ks.size(), 16, [&](size_t i) {
+            const uint32_t k = ra.ks[i];
+            const MRead &rd = read(k);
+            if (events_done ? !rr[k].skipped : append_events(k))
+                host_phase_chain(m, rd, rr[k], hits + hit_off[k], hit_off[k + 1] - hit_off[k], pv && rd.last_round == pv->round_id ? pv : nullptr, runs_dtw);
+        });
+        lap(0);
+        for (uint32_t k : ra.ks) if (rr[k].err != RAWDTW_OK) failed(rr[k].err, "chaining failed (chain output buffers too small)");
+        if (ok() && runs_dtw) lay_out_and_submit(gi, events_done);
+    }
+
+    // ---- lay-out: offsets by a running sum, then every read copies its own stretch; then the submission ----
+    void lay_out_and_submit(uint32_t gi, bool events_done)
+    {
+        Group &g = m->groups[gi]; RoundArrays &ra = g.buf[g.cur];
+        const size_t nr = ra.ks.size();
+        Sizes n{nr};
+        for (uint32_t k : ra.ks) {
+            RoundRead &r = rr[k];
+            r.chain0 = n.chains; r.anchor0 = n.anchors; r.new0 = n.new_anchors; r.ev0 = n.events;
+            n.chains += r.chains.size();
+            for (size_t c = 0; c < r.chains.size(); c++) {
+                n.anchors += r.chains[c].anchors.size();
+                n.new_anchors += r.chains[c].anchors.size() - r.carry[c].parts; // (the new entries and, when a stretch is taken over, the junction)
+            }
+            n.events += events_done ? 0 : r.ne;
+            n.seg += !events_done && r.ne ? 1 : 0;
+        }
+        const uint64_t nc = n.chains, na = n.anchors;
+        ra.n_chains = nc; ra.n_anchors = na;
+        if (!size_arrays(g, n, false)) return;
+        if (m->scorer) { ra.chain_seq.resize(nc); ra.chain_strand.resize(nc); }
+        ra.chain_off[nr] = nc; ra.anchor_off[nc] = na;
+        if (ra.carried) ra.new_off[nc] = n.new_anchors;
+        ra.ref_base[nc] = 0; ra.read_base[nc] = 0; // (non-null, initialised arrays for a round without chains)
+        ra.anchors[na] = rawdtw_anchor_t{0, 0};
+        const bool stage = on_device && !events_done;
+        if (stage) write_segments(ra, false);
+        m->pool->run(nr, 32, [&](size_t i) {
+            const uint32_t k = ra.ks[i];
+            const RoundRead &r = rr[k];
+            const uint32_t rb = arena_base(read(k));
+            ra.chain_off[i] = r.chain0;
+            uint64_t at = r.anchor0, nat = r.new0;
+            for (size_t c = 0; c < r.chains.size(); c++) {
+                const std::vector<rawdtw_anchor_t> &an = r.chains[c].anchors;
+                const uint64_t cc = r.chain0 + c;
+                ra.anchor_off[cc] = at;
+                ra.ref_base[cc] = r.ref_base[c];
+                ra.read_base[cc] = rb;
+                if (m->scorer) { ra.chain_seq[cc] = r.chains[c].ref; ra.chain_strand[cc] = r.chains[c].strand; }
+                memcpy(ra.anchors.p + at, an.data(), an.size() * sizeof(rawdtw_anchor_t));
+                if (ra.carried) {
+                    const uint64_t n_new = an.size() - r.carry[c].parts; // (with the junction)
+                    ra.carry[cc] = r.carry[c];
+                    ra.new_off[cc] = nat;
+                    memcpy(ra.new_anchors.p + nat, an.data(), n_new * sizeof(rawdtw_anchor_t));
+                    nat += n_new;
+                }
+                at += an.size();
+            }
+            if (stage && r.ne) memcpy(ra.new_events.p + r.ev0, events + event_off[k], r.ne * sizeof(float));
+        });
+        lap(1);
+        // ---- submit: the DTW block of gen_chains for every read of the group (rmap.cpp:509-530), one device submission ----
+        if (on_device) {
+            int st = RAWDTW_OK;
+            if (n.seg) st = rawdtw_events_append(g.ctx, ra.new_events.p, n.events, (uint32_t)n.seg, ra.seg_src.p, ra.seg_dst.p);
+            if (st == RAWDTW_OK && ra.carried) {
+                st = rawdtw_batch_submit_carry(g.ctx, &m->opt.align, nr, ra.chain_off.p, ra.anchor_off.p, ra.anchors.p, ra.new_off.p, ra.new_anchors.p,
+                                               ra.ref_base.p, ra.read_base.p, g.buf[g.cur ^ 1].batch, ra.carry.p, &ra.batch);
+                if (st == RAWDTW_ERR_UNSUPPORTED) { ra.carried = false; st = RAWDTW_OK; } // (e.g. a round without a chain: nothing to plan on the device)
+            }
+            if (st == RAWDTW_OK && !ra.carried)
+                st = rawdtw_batch_submit(g.ctx, &m->opt.align, nr, ra.chain_off.p, ra.anchor_off.p, ra.anchors.p, ra.ref_base.p, ra.read_base.p, &ra.batch);
+            if (st != RAWDTW_OK) failed(st, rawdtw_last_error(g.ctx));
+            m->timing[5] += (double)((ra.carried ? n.new_anchors : na) * sizeof(rawdtw_anchor_t));
+            m->timing[6] += (double)(n.events * sizeof(float));
+            m->timing[7] += (double)((nr + 1) * 8 + (nc + 1) * 8 + nc * 12 + (ra.carried ? nc * 32 + 8 : 0) + n.seg * 12);
+        } else {
+            std::vector<const float *> evp(nr);
+            std::vector<uint32_t> evn(nr);
+            for (size_t i = 0; i < nr; i++) { const MRead &rd = read(ra.ks[i]); evp[i] = rd.events.data(); evn[i] = (uint32_t)rd.events.size(); }
+            if (m->scorer(m->scorer_user, nr, ra.chain_off.p, ra.anchor_off.p, ra.anchors.p, ra.chain_seq.data(), ra.chain_strand.data(), evp.data(), evn.data(),
+                          ra.score.p, ra.keep.p) != 0)
+                failed(RAWDTW_ERR_DEVICE, "the external scorer failed");
+        }
+        lap(2);
+    }
+
+    // the new events' segments: where each stretch of the staged events goes in the group's event arena -- the reads with a chunk this
+    // round, in order.  In place: every read a segment, empty ones too (event_off itself is the table of sources).
+    void write_segments(RoundArrays &ra, bool in_place)
+    {
+        uint64_t s = 0, at = 0;
+        for (uint32_t k : ra.ks) {
+            if (!rr[k].ne && !in_place) continue;
+            if (!in_place) ra.seg_src[s] = at;
+            ra.seg_dst[s++] = arena_base(read(k)) + rr[k].ev_before;
+            at += rr[k].ne;
+        }
+        if (!in_place) ra.seg_src[s] = at;
+    }
+
+    // ---- per group: fetch (the only wait), then the round's end per read: gen_primary_chains, comp_mapq, the stop rule ----
+    void fetch_and_end(uint32_t gi)
+    {
+        Group &g = m->groups[gi]; RoundArrays &ra = g.buf[g.cur];
+        if (on_device && ra.batch) {
+            const int st = rawdtw_batch_fetch(g.ctx, ra.batch, ra.score.p, ra.keep.p, nullptr); // (also after a failure elsewhere: the arrays it reads go out of use here)
+            if (st != RAWDTW_OK) failed(st, rawdtw_last_error(g.ctx));
+            uint64_t sc = 0, ru = 0;
+            if (ok() && rawdtw_batch_round_stats(g.ctx, ra.batch, &sc, &ru) == RAWDTW_OK) { per[gi].scored = sc; per[gi].reused = ru; }
+        }
+        lap(3);
+        if (!ok()) return;
+        const bool evaluate = (m->opt.flag & 0x2) != 0, log_scores = (m->opt.flag & 0x8) != 0;
+        m->pool->run(ra.ks.size(), 16, [&](size_t i) {
+            const uint32_t k = ra.ks[i];
+            RoundRead &r = rr[k];
+            if (r.skipped) { r.high = high_confidence(m, read(k).chains); return; } // rmap.cpp:569-572: the chains stay as they were
+            std::vector<MChain> post;
+            post.reserve(r.chains.size());
+            for (size_t c = 0; c < r.chains.size(); c++) {
+                MChain &ch = r.chains[c];
+                bool keep = true;
+                if (runs_dtw) {
+                    ch.alignment_score = ra.score[r.chain0 + c];
+                    keep = ra.keep[r.chain0 + c] != 0;
+                    // --dtw-log-scores (rmap.cpp:308-312): in evaluation order; a cut chain returns before the fprintf
+                    if (log_scores && ch.alignment_score != -1e10f) {
+                        char line[128];
+                        snprintf(line, sizeof line, "chaining_score=%f alignment_score=%f\n", (double)ch.chaining_score, (double)ch.alignment_score);
+                        r.log += line;
+                    }
+                }
+                if (!evaluate || !runs_dtw || keep) post.push_back(std::move(ch)); // rmap.cpp:525: replaced only under EVALUATE_CHAINS
+            }
+            r.primary = primary_chains(m, post);
+            r.high = high_confidence(m, r.primary);
+        });
+        lap(4);
+    }
+
+    // ---- a failed round: the reads' events cut back, each group's round before stays the round before; nothing else was written ----
+    int rollback()
+    {
+        for (uint32_t k = 0; k < n_reads; k++) {
+            MRead &rd = read(k); const RoundRead &r = rr[k];
+            if (rd.n_events >= r.ev_before && r.ne + r.ev_before == rd.n_events) {
+                rd.n_events = r.ev_before; rd.offset = r.off_before;
+                if (rd.events.size() > rd.n_events) rd.events.resize(rd.n_events);
+            }
+        }
+        for (Group &g : m->groups) {
+            RoundArrays &ra = g.buf[g.cur];
+            if (ra.batch) { rawdtw_batch_destroy(ra.batch); ra.batch = nullptr; }
+            g.cur ^= 1;
+        }
+        return fail(m, status, msg);
+    }
+
+    // ---- commit ----
+    void commit()
+    {
+        m->rounds = id;
+        for (uint32_t gi = 0; gi < G; gi++) {
+            Group &g = m->groups[gi];
+            RoundArrays &ra = g.buf[g.cur], &pb = g.buf[g.cur ^ 1];
+            if (pb.batch) { rawdtw_batch_destroy(pb.batch); pb.batch = nullptr; }
+            g.has_prev = on_device && m->opt.carry && !m->opt.device_chain && ra.batch != nullptr;
+            if (!g.has_prev && ra.batch) { rawdtw_batch_destroy(ra.batch); ra.batch = nullptr; }
+            m->parts_scored += per[gi].scored; m->parts_reused += per[gi].reused;
+            for (size_t i = 0; i < ra.ks.size(); i++) { read(ra.ks[i]).last_round = id; read(ra.ks[i]).last_pos = i; }
+        }
+        for (uint32_t k = 0; k < n_reads; k++) {
+            MRead &rd = read(k); RoundRead &r = rr[k];
+            if (!r.log.empty()) m->log += r.log;
+            rd.chunks_done++;
+            if (r.high) { rd.finished = true; rd.broke_early = true; } // rmap.cpp:692 (evaluated with the round's end, per read on the pool)
+            else if (rd.chunks_done >= std::min(rd.n_chunks, m->opt.max_num_chunk)) rd.finished = true;
+        }
+        // the new chains in place, and the round's per-read state with the old chains freed, on the pool (ten vectors a read and more: freed one
+        // read after the other they were milliseconds of a large round).  rmap.cpp:569-572: a skipped read's chains stay.
+        m->pool->run(n_reads, 16, [&](size_t k) {
+            if (!rr[k].skipped) std::swap(read((uint32_t)k).chains, rr[k].primary);
+            RoundRead gone; std::swap(gone, rr[k]);
+        });
+        m->timing[4] += now_ms() - t0;
+    }
+};
+
 } // namespace
 
 extern "C" {
@@ -540,11 +911,7 @@ int rawdtw_mapper_destroy(rawdtw_mapper *m)
     if (!m) return RAWDTW_OK;
     drop_batches(m);
     for (Group &g : m->groups) {
-        for (RoundArrays &ra : g.buf) { // (pinned memory goes before the context that may own the device)
-            ra.chain_off.release(); ra.anchor_off.release(); ra.ref_base.release(); ra.new_off.release(); ra.seg_src.release();
-            ra.read_base.release(); ra.seg_dst.release(); ra.anchors.release(); ra.new_anchors.release(); ra.carry.release();
-            ra.new_events.release(); ra.score.release(); ra.keep.release();
-        }
+        for (RoundArrays &ra : g.buf) ra = RoundArrays(); // (pinned memory goes before the context that may own the device)
         if (g.own_ctx && g.ctx) rawdtw_destroy(g.ctx);
     }
     rawdtw_su_destroy(m->su);
@@ -565,7 +932,6 @@ int rawdtw_mapper_set_scorer(rawdtw_mapper *m, rawdtw_scorer_fn fn, void *user)
     }
     m->scorer = fn; m->scorer_user = user;
     drop_batches(m); // (a round scored elsewhere leaves nothing to carry from)
-    for (Group &g : m->groups) g.has_prev = false;
     return RAWDTW_OK;
 }
 
@@ -634,7 +1000,7 @@ int rawdtw_mapper_round(rawdtw_mapper *m, uint32_t n_reads, const uint32_t *read
     if (!m || (n_reads && (!read_ids || !event_off || !hit_off)) || (n_reads && event_off[n_reads] && !events) || (n_reads && hit_off[n_reads] && !hits))
         return RAWDTW_ERR_INVALID;
     if (n_reads == 0) return RAWDTW_OK;
-    double t0 = now_ms(); // (the checks and the round's set-up count as host phase, its commit as round end: the five times add up to the call)
+    const double t0 = now_ms(); // (the checks and the round's set-up count as host phase, its commit as round end: the five times add up to the call)
     const uint32_t n_seq = (uint32_t)m->seq_len.size();
     const bool runs_dtw = (m->opt.flag & (0x2 | 0x8)) != 0; // rmap.cpp:509
     if (runs_dtw && !m->scorer && !m->ctx) return fail(m, RAWDTW_ERR_NO_DEVICE, "a mapper without a context needs a scorer (rawdtw_mapper_set_scorer)");
@@ -657,383 +1023,13 @@ int rawdtw_mapper_round(rawdtw_mapper *m, uint32_t n_reads, const uint32_t *read
         for (uint64_t h = hit_off[k]; h < hit_off[k + 1]; h++)
             if (hits[h].ref_seq >= n_seq) return fail(m, RAWDTW_ERR_INVALID, "seed hit on an unknown sequence");
     }
-    const uint64_t round_id = m->rounds + 1;
-    const uint32_t G = (uint32_t)m->groups.size();
-    const bool on_device = runs_dtw && !m->scorer;
-    std::vector<RoundRead> rr(n_reads);
-    for (Group &g : m->groups) { g.cur ^= 1; g.buf[g.cur].ks.clear(); }
-    for (uint32_t k = 0; k < n_reads; k++) { Group &g = m->groups[m->reads[read_ids[k]].slot % G]; g.buf[g.cur].ks.push_back(k); }
-    int status = RAWDTW_OK;
-    std::string status_msg;
-    auto set_fail = [&](int st, const std::string &msg) { if (status == RAWDTW_OK) { status = st; status_msg = msg; } };
-    // ---- device chaining (opt.device_chain), first half: the host phase is the events and the seed lists; sort, chaining DP, traceback and order
-    // are enqueued (rawdtw_chain_round_begin) and run while the next group's host phase does.  false: the device declined (its cap on seeds a read)
-    // -- the events are in place on both sides, the round is chained on the host.
-    struct DevRound { bool pending = false; uint64_t ns = 0, nev = 0, nseg = 0; };
-    std::vector<DevRound> dev(G);
-    // the caller's event array goes to the device as it is when it is page-locked (rawdtw_host_alloc) and one read group takes the whole round:
-    // its reads' chunks ARE the segments, in order -- no copy into the mapper's own staging (a third of the host phase)
-    const bool events_in_place = on_device && m->opt.device_chain && G == 1 && event_off[n_reads] > 0 && rawdtw_host_is_page_locked(events) == 1;
-    auto device_begin = [&](const uint32_t gi) -> bool {
-        Group &g = m->groups[gi];
-        RoundArrays &ra = g.buf[g.cur];
-        const size_t nr = ra.ks.size();
-        if (nr == 0) return true; // (none of the round's reads is this group's)
-        {
-            m->pool->run(nr, 64, [&](size_t i) {
-                const uint32_t k = ra.ks[i];
-                MRead &rd = m->reads[read_ids[k]];
-                RoundRead &r = rr[k];
-                if (!host_phase_events(m, rd, r, events + event_off[k], event_off[k + 1] - event_off[k])) return;
-                uint64_t n = hit_off[k + 1] - hit_off[k];
-                for (const MChain &ch : rd.chains) n += ch.anchors.size(); // rmap.cpp:344-357: re-seeding with the previous chains' anchors
-                r.n_seeds = n;
-            });
-            uint64_t ns = 0, nev = 0, nseg = 0;
-            for (size_t i = 0; i < nr; i++) { RoundRead &r = rr[ra.ks[i]]; r.seed0 = ns; ns += r.n_seeds; r.ev0 = nev; nev += r.ne; nseg += r.ne ? 1 : 0; }
-            g.hw_reads = std::max<uint64_t>(g.hw_reads, nr); g.hw_seeds = std::max(g.hw_seeds, ns); g.hw_events = std::max(g.hw_events, nev); g.hw_seg = std::max(g.hw_seg, nseg);
-            g.hw_chains = std::max<uint64_t>(g.hw_chains, g.hw_reads * 32);
-            bool ok = true;
-            for (RoundArrays *x : {&ra, &g.buf[g.cur ^ 1]})
-                ok = ok && x->seed_off.ensure(g.hw_reads + 1, true) && x->seeds.ensure(g.hw_seeds + 1, true) && x->read_base.ensure(std::max(g.hw_reads, g.hw_chains) + 1, true) &&
-                     x->chain_off.ensure(g.hw_reads + 1, true) && x->anchor_off.ensure(g.hw_chains + 1, true) && x->recs.ensure(g.hw_chains + 1, true) &&
-                     x->anchors.ensure(g.hw_seeds + 1, true) && x->score.ensure(g.hw_chains + 1, true) && x->keep.ensure(g.hw_chains + 1, true) &&
-                     x->new_events.ensure((events_in_place ? 0 : g.hw_events) + 1, true) && x->seg_src.ensure(g.hw_seg + 2, true) &&
-                     x->seg_dst.ensure(std::max(g.hw_seg, g.hw_reads) + 1, true);
-            if (!ok) { set_fail(RAWDTW_ERR_OOM, "host allocation failed"); return true; }
-            if (events_in_place) { // (every read a segment, empty ones too: event_off itself is the table of sources)
-                for (size_t i = 0; i < nr; i++) ra.seg_dst[i] = m->reads[read_ids[ra.ks[i]]].slot * m->opt.slot_events + rr[ra.ks[i]].ev_before;
-            } else {
-                uint64_t sg = 0, at = 0;
-                for (size_t i = 0; i < nr; i++) {
-                    const RoundRead &r = rr[ra.ks[i]];
-                    if (!r.ne) continue;
-                    const MRead &rd = m->reads[read_ids[ra.ks[i]]];
-                    ra.seg_src[sg] = at;
-                    ra.seg_dst[sg] = (rd.slot / G) * m->opt.slot_events + r.ev_before;
-                    at += r.ne; sg++;
-                }
-                ra.seg_src[sg] = at;
-            }
-            ra.seed_off[nr] = ns;
-            m->pool->run(nr, 64, [&](size_t i) {
-                const uint32_t k = ra.ks[i];
-                const RoundRead &r = rr[k];
-                const MRead &rd = m->reads[read_ids[k]];
-                ra.seed_off[i] = r.seed0;
-                ra.read_base[i] = (rd.slot / G) * m->opt.slot_events;
-                rawdtw_seed_t *out = ra.seeds.p + r.seed0;
-                if (r.n_seeds) {
-                    for (const MChain &ch : rd.chains) {
-                        const uint32_t key = ch.ref * 2u + (uint32_t)ch.strand;
-                        for (const rawdtw_anchor_t &an : ch.anchors) *out++ = rawdtw_seed_t{key, an.target_position, an.query_position};
-                    }
-                    for (uint64_t h = hit_off[k]; h < hit_off[k + 1]; h++) // rmap.cpp:371-391
-                        *out++ = rawdtw_seed_t{hits[h].ref_seq * 2u + (uint32_t)(hits[h].strand ? 1 : 0), hits[h].target_position, hits[h].query_position + r.chunk_start};
-                }
-                if (r.ne && !events_in_place) memcpy(ra.new_events.p + r.ev0, events + event_off[k], r.ne * sizeof(float));
-            });
-            double td = now_ms();
-            m->timing[0] += td - t0; t0 = td;
-            // the chaining first, the events behind it: the sort + DP does not read them, and rawdtw_chain_round_end waits for the round's own work only
-            // -- the events' upload (the round's largest) runs on while the host goes on
-            int st = rawdtw_chain_round_begin(g.ctx, &m->opt.chain, nr, ra.seed_off.p, ra.seeds.p, ra.read_base.p, (uint32_t)m->ref_off.size(), m->ref_off.data(),
-                                              ra.chain_off.p, ra.anchor_off.p, ra.recs.p, g.hw_chains, ra.anchors.p);
-            const bool declined = st == RAWDTW_ERR_UNSUPPORTED;
-            if (st == RAWDTW_OK || declined) {
-                int se = RAWDTW_OK;
-                if (nseg && events_in_place) se = rawdtw_events_append(g.ctx, events, event_off[n_reads], (uint32_t)nr, event_off, ra.seg_dst.p);
-                else if (nseg) se = rawdtw_events_append(g.ctx, ra.new_events.p, nev, (uint32_t)nseg, ra.seg_src.p, ra.seg_dst.p);
-                if (se != RAWDTW_OK) {
-                    if (st == RAWDTW_OK) { const rawdtw_anchor_t *x = nullptr; const uint64_t *y = nullptr; const uint32_t *z = nullptr; (void)rawdtw_chain_round_end(g.ctx, &x, &y, &z); }
-                    st = se;
-                }
-            }
-            td = now_ms();
-            m->timing[2] += td - t0; t0 = td;
-            if (declined && st == RAWDTW_ERR_UNSUPPORTED) return false;
-            if (st != RAWDTW_OK) { set_fail(st, rawdtw_last_error(g.ctx)); return true; }
-            dev[gi].pending = true; dev[gi].ns = ns; dev[gi].nev = nev; dev[gi].nseg = nseg;
-            return true;
-        }
-    };
-    // second half: the wait, the DTW submission straight from the device's arrays, and -- while that batch runs -- the round's chains per read, as
-    // the host phase would have left them.  false: declined (a read with too many chains, or an order only std::sort knows)
-    auto device_end = [&](const uint32_t gi) -> bool {
-        Group &g = m->groups[gi];
-        RoundArrays &ra = g.buf[g.cur];
-        const size_t nr = ra.ks.size();
-        dev[gi].pending = false;
-        const rawdtw_anchor_t *d_anchors = nullptr;
-        const uint64_t *d_ref_base = nullptr;
-        const uint32_t *d_read_base = nullptr;
-        int st = rawdtw_chain_round_end(g.ctx, &d_anchors, &d_ref_base, &d_read_base);
-        if (st == RAWDTW_ERR_UNSUPPORTED) { double td = now_ms(); m->timing[2] += td - t0; t0 = td; return false; }
-        if (st != RAWDTW_OK) { set_fail(st, rawdtw_last_error(g.ctx)); return true; }
-        const uint64_t nc = ra.chain_off[nr], na = ra.anchor_off[nc];
-        ra.n_chains = nc; ra.n_anchors = na; ra.n_new = 0; ra.n_new_events = dev[gi].nev; ra.n_seg = dev[gi].nseg;
-        st = rawdtw_batch_submit_device(g.ctx, &m->opt.align, nr, ra.chain_off.p, ra.anchor_off.p, d_anchors, d_ref_base, d_read_base, &ra.batch);
-        if (st != RAWDTW_OK) { set_fail(st, rawdtw_last_error(g.ctx)); return true; }
-        ra.device_chained = true;
-        m->timing[6] += (double)(dev[gi].nev * sizeof(float));
-        m->timing[7] += (double)(dev[gi].ns * sizeof(rawdtw_seed_t) + (nr + 1) * 16 + nr * 4 + (nc + 1) * 8 + dev[gi].nseg * 12);
-        double td = now_ms();
-        m->timing[2] += td - t0; t0 = td;
-        m->pool->run(nr, 32, [&](size_t i) {
-            RoundRead &r = rr[ra.ks[i]];
-            r.chain0 = ra.chain_off[i];
-            const uint64_t n = ra.chain_off[i + 1] - ra.chain_off[i];
-            r.chains.resize(n);
-            for (uint64_t c = 0; c < n; c++) {
-                const rawdtw_chain_rec_t &rec = ra.recs[r.chain0 + c];
-                MChain &ch = r.chains[c];
-                ch.chaining_score = rec.chaining_score; ch.ref = rec.key >> 1; ch.strand = (int32_t)(rec.key & 1u);
-                ch.start_position = rec.start_position; ch.end_position = rec.end_position;
-                const rawdtw_anchor_t *an = ra.anchors.p + ra.anchor_off[r.chain0 + c];
-                ch.anchors.assign(an, an + rec.n_anchors);
-            }
-        });
-        td = now_ms();
-        m->timing[1] += td - t0; t0 = td;
-        return true;
-    };
-    // ---- a group's round with the chains made on the host: host phase, lay-out, submit (`events_done`: a round the device declined to chain --
-    // its events are appended already, on both sides) ----
-    auto host_round = [&](const uint32_t gi, const RoundArrays *pv, const bool events_done) {
-        Group &g = m->groups[gi];
-        RoundArrays &ra = g.buf[g.cur];
-        const RoundArrays &pb = g.buf[g.cur ^ 1];
-        const size_t nr = ra.ks.size();
-        if (events_done)
-            m->pool->run(nr, 16, [&](size_t i) {
-                const uint32_t k = ra.ks[i];
-                RoundRead &r = rr[k];
-                if (!r.skipped) host_phase_chain(m, m->reads[read_ids[k]], r, hits + hit_off[k], hit_off[k + 1] - hit_off[k], nullptr, runs_dtw);
-            });
-        else
-            m->pool->run(nr, 16, [&](size_t i) {
-                const uint32_t k = ra.ks[i];
-                MRead &rd = m->reads[read_ids[k]];
-                const bool in_prev = pv && rd.last_round == pv->round_id;
-                host_phase_read(m, rd, rr[k], events + event_off[k], event_off[k + 1] - event_off[k], hits + hit_off[k], hit_off[k + 1] - hit_off[k],
-                                in_prev ? pv : nullptr, runs_dtw);
-            });
-        double t1 = now_ms();
-        m->timing[0] += t1 - t0; t0 = t1;
-        for (size_t i = 0; i < nr; i++) if (rr[ra.ks[i]].err != RAWDTW_OK) set_fail(rr[ra.ks[i]].err, "chaining failed (chain output buffers too small)");
-        if (status != RAWDTW_OK || !runs_dtw) return;
-        // ---- lay-out: offsets by a running sum, then every read copies its own stretch ----
-        uint64_t nc = 0, na = 0, nn = 0, nev = 0, nseg = 0;
-        for (size_t i = 0; i < nr; i++) {
-            RoundRead &r = rr[ra.ks[i]];
-            r.chain0 = nc; r.anchor0 = na; r.new0 = nn; r.ev0 = nev;
-            nc += r.chains.size();
-            for (size_t c = 0; c < r.chains.size(); c++) {
-                const uint64_t n = r.chains[c].anchors.size();
-                na += n;
-                nn += n - r.carry[c].parts; // (the new entries and, when a stretch is taken over, the junction)
-            }
-            nev += events_done ? 0 : r.ne;
-            nseg += !events_done && r.ne ? 1 : 0;
-        }
-        ra.n_chains = nc; ra.n_anchors = na; ra.n_new = nn; ra.n_new_events = nev; ra.n_seg = nseg;
-        const bool pin = on_device;
-        g.hw_reads = std::max<uint64_t>(g.hw_reads, nr); g.hw_chains = std::max(g.hw_chains, nc); g.hw_anchors = std::max(g.hw_anchors, na);
-        g.hw_new = std::max(g.hw_new, nn); g.hw_events = std::max(g.hw_events, nev); g.hw_seg = std::max(g.hw_seg, nseg);
-        auto size_arrays = [&](RoundArrays &x, const bool kept) { // (`kept`: the round before's arrays, read again by the next round's matching)
-            const size_t k_r = kept ? x.n_reads + 1 : 0, k_c = kept ? x.n_chains + 1 : 0, k_a = kept ? x.n_anchors + 1 : 0;
-            return x.chain_off.ensure(g.hw_reads + 1, pin, k_r) && x.anchor_off.ensure(g.hw_chains + 1, pin, k_c) && x.ref_base.ensure(g.hw_chains + 1, pin, k_c) &&
-                   x.read_base.ensure(g.hw_chains + 1, pin, k_c) && x.anchors.ensure(g.hw_anchors + 1, pin && !(m->opt.carry && g.has_prev), k_a) &&
-                   x.score.ensure(g.hw_chains + 1, pin) && x.keep.ensure(g.hw_chains + 1, pin) &&
-                   (!(on_device && m->opt.carry) || (x.new_off.ensure(g.hw_chains + 1, pin) && x.new_anchors.ensure(g.hw_new + 1, pin) && x.carry.ensure(g.hw_chains + 1, pin))) &&
-                   (!on_device || (x.new_events.ensure(g.hw_events + 1, pin) && x.seg_src.ensure(g.hw_seg + 2, pin) && x.seg_dst.ensure(g.hw_seg + 1, pin)));
-        };
-        const bool ok = size_arrays(ra, false) && size_arrays(g.buf[g.cur ^ 1], true);
-        if (!ok) { set_fail(RAWDTW_ERR_OOM, "host allocation failed"); return; }
-        if (m->scorer) { ra.chain_seq.resize(nc); ra.chain_strand.resize(nc); }
-        ra.chain_off[nr] = nc; ra.anchor_off[nc] = na;
-        if (ra.carried) ra.new_off[nc] = nn;
-        ra.ref_base[nc] = 0; ra.read_base[nc] = 0; // (non-null, initialised arrays for a round without chains)
-        ra.anchors[na] = rawdtw_anchor_t{0, 0};
-        {   // the new events' segments (reads with a chunk this round, in order)
-            uint64_t s = 0, at = 0;
-            for (size_t i = 0; i < nr && on_device && !events_done; i++) {
-                const RoundRead &r = rr[ra.ks[i]];
-                if (!r.ne) continue;
-                const MRead &rd = m->reads[read_ids[ra.ks[i]]];
-                ra.seg_src[s] = at;
-                ra.seg_dst[s] = (rd.slot / G) * m->opt.slot_events + r.ev_before;
-                at += r.ne; s++;
-            }
-            if (on_device) ra.seg_src[s] = at;
-        }
-        m->pool->run(nr, 32, [&](size_t i) {
-            const uint32_t k = ra.ks[i];
-            const RoundRead &r = rr[k];
-            const MRead &rd = m->reads[read_ids[k]];
-            ra.chain_off[i] = r.chain0;
-            uint64_t at = r.anchor0, nat = r.new0;
-            for (size_t c = 0; c < r.chains.size(); c++) {
-                const std::vector<rawdtw_anchor_t> &an = r.chains[c].anchors;
-                const uint64_t cc = r.chain0 + c;
-                ra.anchor_off[cc] = at;
-                ra.ref_base[cc] = r.ref_base[c];
-                ra.read_base[cc] = (rd.slot / G) * m->opt.slot_events;
-                if (m->scorer) { ra.chain_seq[cc] = r.chains[c].ref; ra.chain_strand[cc] = r.chains[c].strand; }
-                memcpy(ra.anchors.p + at, an.data(), an.size() * sizeof(rawdtw_anchor_t));
-                if (ra.carried) {
-                    const uint64_t n_new = an.size() - r.carry[c].parts; // (with the junction)
-                    ra.carry[cc] = r.carry[c];
-                    ra.new_off[cc] = nat;
-                    memcpy(ra.new_anchors.p + nat, an.data(), n_new * sizeof(rawdtw_anchor_t));
-                    nat += n_new;
-                }
-                at += an.size();
-            }
-            if (on_device && r.ne && !events_done) memcpy(ra.new_events.p + r.ev0, events + event_off[k], r.ne * sizeof(float));
-        });
-        t1 = now_ms();
-        m->timing[1] += t1 - t0; t0 = t1;
-        // ---- submit: the DTW block of gen_chains for every read of the group (rmap.cpp:509-530), one device submission ----
-        if (on_device) {
-            int st = RAWDTW_OK;
-            if (nseg) st = rawdtw_events_append(g.ctx, ra.new_events.p, nev, (uint32_t)nseg, ra.seg_src.p, ra.seg_dst.p);
-            if (st == RAWDTW_OK) {
-                if (ra.carried) {
-                    st = rawdtw_batch_submit_carry(g.ctx, &m->opt.align, nr, ra.chain_off.p, ra.anchor_off.p, ra.anchors.p, ra.new_off.p, ra.new_anchors.p,
-                                                   ra.ref_base.p, ra.read_base.p, pb.batch, ra.carry.p, &ra.batch);
-                    if (st == RAWDTW_ERR_UNSUPPORTED) { ra.carried = false; st = RAWDTW_OK; } // (e.g. a round without a chain: nothing to plan on the device)
-                }
-                if (st == RAWDTW_OK && !ra.carried)
-                    st = rawdtw_batch_submit(g.ctx, &m->opt.align, nr, ra.chain_off.p, ra.anchor_off.p, ra.anchors.p, ra.ref_base.p, ra.read_base.p, &ra.batch);
-            }
-            if (st != RAWDTW_OK) set_fail(st, rawdtw_last_error(g.ctx));
-            m->timing[5] += (double)((ra.carried ? nn : na) * sizeof(rawdtw_anchor_t));
-            m->timing[6] += (double)(nev * sizeof(float));
-            m->timing[7] += (double)((nr + 1) * 8 + (nc + 1) * 8 + nc * 12 + (ra.carried ? nc * 32 + 8 : 0) + nseg * 12);
-        } else {
-            std::vector<const float *> evp(nr);
-            std::vector<uint32_t> evn(nr);
-            for (size_t i = 0; i < nr; i++) { const MRead &rd = m->reads[read_ids[ra.ks[i]]]; evp[i] = rd.events.data(); evn[i] = (uint32_t)rd.events.size(); }
-            if (m->scorer(m->scorer_user, nr, ra.chain_off.p, ra.anchor_off.p, ra.anchors.p, ra.chain_seq.data(), ra.chain_strand.data(), evp.data(), evn.data(),
-                          ra.score.p, ra.keep.p) != 0)
-                set_fail(RAWDTW_ERR_DEVICE, "the external scorer failed");
-        }
-        t1 = now_ms();
-        m->timing[2] += t1 - t0; t0 = t1;
-    };
-    for (uint32_t gi = 0; gi < G && status == RAWDTW_OK; gi++) {
-        Group &g = m->groups[gi];
-        RoundArrays &ra = g.buf[g.cur];
-        const RoundArrays &pb = g.buf[g.cur ^ 1];
-        const RoundArrays *pv = nullptr;
-        const size_t nr = ra.ks.size();
-        ra.carried = false;
-        ra.round_id = round_id;
-        ra.n_reads = nr;
-        ra.device_chained = false;
-        if (on_device && m->opt.device_chain) {
-            if (!device_begin(gi) && status == RAWDTW_OK) host_round(gi, nullptr, true);
-            continue;
-        }
-        if (on_device && m->opt.carry && g.has_prev && pb.batch && rawdtw_batch_can_carry(g.ctx, pb.batch, &m->opt.align)) {
-            size_t known = 0; // (a round none of whose reads was in the round before has nothing to take over: submitted whole)
-            for (size_t i = 0; i < nr && !known; i++) known += m->reads[read_ids[ra.ks[i]]].last_round == pb.round_id;
-            if (known) { pv = &pb; ra.carried = true; }
-        }
-        host_round(gi, pv, false);
-    }
-    for (uint32_t gi = 0; gi < G; gi++) {
-        if (!dev[gi].pending) continue;
-        if (status != RAWDTW_OK) { // (a failure elsewhere: the round begun is ended, nothing of it is used)
-            const rawdtw_anchor_t *x = nullptr; const uint64_t *y = nullptr; const uint32_t *z = nullptr;
-            (void)rawdtw_chain_round_end(m->groups[gi].ctx, &x, &y, &z);
-            dev[gi].pending = false;
-            continue;
-        }
-        if (!device_end(gi) && status == RAWDTW_OK) host_round(gi, nullptr, true);
-    }
-    // ---- per group: fetch, then the round's end per read ----
-    for (uint32_t gi = 0; gi < G; gi++) {
-        Group &g = m->groups[gi];
-        RoundArrays &ra = g.buf[g.cur];
-        const size_t nr = ra.ks.size();
-        if (on_device && ra.batch) {
-            int st = rawdtw_batch_fetch(g.ctx, ra.batch, ra.score.p, ra.keep.p, nullptr); // (also after a failure elsewhere: the arrays it reads go out of use here)
-            if (st != RAWDTW_OK) set_fail(st, rawdtw_last_error(g.ctx));
-            uint64_t sc = 0, ru = 0;
-            if (st == RAWDTW_OK && status == RAWDTW_OK && rawdtw_batch_round_stats(g.ctx, ra.batch, &sc, &ru) == RAWDTW_OK) { m->parts_scored += sc; m->parts_reused += ru; }
-        }
-        double t1 = now_ms();
-        m->timing[3] += t1 - t0; t0 = t1;
-        if (status != RAWDTW_OK) continue;
-        const bool evaluate = (m->opt.flag & 0x2) != 0, log_scores = (m->opt.flag & 0x8) != 0;
-        m->pool->run(nr, 16, [&](size_t i) {
-            const uint32_t k = ra.ks[i];
-            RoundRead &r = rr[k];
-            MRead &rd = m->reads[read_ids[k]];
-            if (r.skipped) { r.high = high_confidence(m, rd.chains); return; } // rmap.cpp:569-572: the chains stay as they were
-            std::vector<MChain> post;
-            post.reserve(r.chains.size());
-            for (size_t c = 0; c < r.chains.size(); c++) {
-                MChain &ch = r.chains[c];
-                bool keep = true;
-                if (runs_dtw) {
-                    ch.alignment_score = ra.score[r.chain0 + c];
-                    keep = ra.keep[r.chain0 + c] != 0;
-                    // --dtw-log-scores (rmap.cpp:308-312): in evaluation order; a cut chain returns before the fprintf
-                    if (log_scores && ch.alignment_score != -1e10f) {
-                        char line[128];
-                        snprintf(line, sizeof line, "chaining_score=%f alignment_score=%f\n", (double)ch.chaining_score, (double)ch.alignment_score);
-                        r.log += line;
-                    }
-                }
-                if (!evaluate || !runs_dtw || keep) post.push_back(std::move(ch)); // rmap.cpp:525: replaced only under EVALUATE_CHAINS
-            }
-            rd.chains = primary_chains(m, post);
-            r.high = high_confidence(m, rd.chains);
-        });
-        t1 = now_ms();
-        m->timing[4] += t1 - t0; t0 = t1;
-    }
-    if (status != RAWDTW_OK) { // put the reads back as they were; nothing of the round stays
-        for (uint32_t k = 0; k < n_reads; k++) {
-            MRead &rd = m->reads[read_ids[k]];
-            if (rd.n_events >= rr[k].ev_before && rr[k].ne + rr[k].ev_before == rd.n_events) {
-                rd.n_events = rr[k].ev_before; rd.offset = rr[k].off_before;
-                if (rd.events.size() > rd.n_events) rd.events.resize(rd.n_events);
-            }
-        }
-        for (Group &g : m->groups) {
-            RoundArrays &ra = g.buf[g.cur];
-            if (ra.batch) { rawdtw_batch_destroy(ra.batch); ra.batch = nullptr; }
-            g.cur ^= 1; // (the round before stays the round before)
-        }
-        return fail(m, status, status_msg);
-    }
-    // ---- commit ----
-    m->rounds = round_id;
-    for (uint32_t gi = 0; gi < G; gi++) {
-        Group &g = m->groups[gi];
-        RoundArrays &ra = g.buf[g.cur], &pb = g.buf[g.cur ^ 1];
-        if (pb.batch) { rawdtw_batch_destroy(pb.batch); pb.batch = nullptr; }
-        g.has_prev = on_device && m->opt.carry && !m->opt.device_chain && ra.batch != nullptr;
-        if (!g.has_prev && ra.batch) { rawdtw_batch_destroy(ra.batch); ra.batch = nullptr; }
-        for (size_t i = 0; i < ra.ks.size(); i++) {
-            MRead &rd = m->reads[read_ids[ra.ks[i]]];
-            rd.last_round = round_id; rd.last_pos = i;
-        }
-    }
-    for (uint32_t k = 0; k < n_reads; k++) {
-        MRead &rd = m->reads[read_ids[k]];
-        if (!rr[k].log.empty()) m->log += rr[k].log;
-        rd.chunks_done++;
-        if (rr[k].high) { rd.finished = true; rd.broke_early = true; } // rmap.cpp:692 (evaluated with the round's end, per read on the pool)
-        else if (rd.chunks_done >= std::min(rd.n_chunks, m->opt.max_num_chunk)) rd.finished = true;
-    }
-    // (the round's per-read state goes on the pool: ten vectors a read, freed one read after the other they were milliseconds of a large round)
-    m->pool->run(n_reads, 64, [&](size_t k) { RoundRead gone; std::swap(gone, rr[k]); });
-    m->timing[4] += now_ms() - t0;
+    Round r{m, n_reads, read_ids, event_off, events, hit_off, hits, t0};
+    r.deal();
+    for (uint32_t gi = 0; gi < r.G && r.ok(); gi++) r.begin_group(gi); // (with device chaining: every group's begun before the first is ended)
+    for (uint32_t gi = 0; gi < r.G; gi++) r.end_device_chain(gi);
+    for (uint32_t gi = 0; gi < r.G; gi++) r.fetch_and_end(gi);         // (group gi's round end while group gi + 1's batch is on the device)
+    if (!r.ok()) return r.rollback();
+    r.commit();
     return RAWDTW_OK;
 }
 
@@ -1047,7 +1043,6 @@ int rawdtw_mapper_finish(rawdtw_mapper *m)
     if (!(m->opt.flag & 0x4)) return RAWDTW_OK;
     if (!m->ctx) return fail(m, RAWDTW_ERR_NO_DEVICE, "--dtw-output-cigar needs a device context");
     drop_batches(m); // (the traceback call replaces the event arena's contents: the mapper's rounds are over)
-    for (Group &g : m->groups) g.has_prev = false;
     struct Item { uint32_t read; uint64_t job0; uint32_t nj; uint64_t ev0; };
     std::vector<Item> items;
     std::vector<rawdtw_job_t> jobs;

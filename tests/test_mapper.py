@@ -355,3 +355,46 @@ def test_a_round_declined_after_the_device_chained_it_is_chained_on_the_host(ora
         eng.close()
     assert out[0][0] == out[1][0] and out[0][1] == out[1][1]
     assert 0 < out[1][2] < out[0][2]  # one round (of one group) went up as anchor lists from the host, the others did not
+
+
+class _EveryReadTwice:
+    """every read of `seeds` twice, side by side: with two read groups (slot % 2) the two copies land in different groups and
+    finish in the same round, so every round calls the scorer once for each group with reads in it"""
+
+    def __init__(self, seeds):
+        self.seeds, self.lens = seeds, seeds.lens
+
+    def read_job(self, r):
+        return self.seeds.read_job(r // 2)
+
+    def chunk(self, r, c):
+        return self.seeds.chunk(r // 2, c)
+
+
+@pytest.mark.gpu
+def test_a_round_that_fails_in_the_scorer_with_two_groups_leaves_nothing(oracle):
+    """The CPU test's failed round (test_mapper_cpu.py) on a mapper with a context and two read groups: the scorer fails on the
+    second group's call, after the first group's round is laid out -- both groups' buffers and the reads' events are put back,
+    and the run, with that round made again, writes the oracle-scored flow's lines and log."""
+    from rawalign_amd.mapping import StopOpt
+    from tests.test_mapper_cpu import _fail_once, _oracle_scorer, map_reads_through_a_failed_round
+
+    ref = synth.make_reference([29903, 12000], seed=20231005 + 1)
+    n = 30
+    seeds = _EveryReadTwice(mapper.SyntheticSeeds(ref, n // 2, seed=11, max_chunks=4))
+    opt = ra.MapOpt(flag=0x2 | 0x8)
+    lo = []
+    want, rounds = mapper.map_reads(seeds, list(range(n)), OracleScorer(oracle, ref), opt, StopOpt(), log=lo)
+    assert rounds >= 3
+    eng = ra.Engine(0)
+    eng.upload_reference(ref.forward, ref.reverse)
+    for threads in (1, 4):
+        cm = mapper.CMapper(eng, opt, StopOpt(), [f"seq{s}" for s in range(ref.n_seq)], [len(x) for x in ref.forward],
+                            slot_events=max(rd["n_ev"] for rd in seeds.seeds.reads) + 8, max_reads=n, carry=True, threads=threads, groups=2)
+        cm.set_scorer(_fail_once(_oracle_scorer(oracle, ref, opt), 2 * (rounds // 2) + 1))   # (two groups: a call each a round)
+        got, rounds_c, failed = map_reads_through_a_failed_round(seeds, n, cm)
+        assert failed == 1
+        assert got == want and rounds_c == rounds and cm.stats()[0] == rounds
+        assert cm.log() == "".join(lo) and lo
+        cm.close()
+    eng.close()

@@ -94,3 +94,57 @@ def test_cpp_mapper_round_is_checked_before_anything_changes(oracle):
     cm.round([c], [seeds.chunk(2, 0)])
     assert cm.state(c)[1] == 1 and line.startswith("read_0\t")
     cm.close()
+
+
+def _fail_once(score, at):
+    """`score`, raising on its call number `at` (from 0) and on no other"""
+    calls = [0]
+
+    def wrapped(*args):
+        k = calls[0]
+        calls[0] += 1
+        if k == at:
+            raise RuntimeError("the scorer fails once")
+        return score(*args)
+    return wrapped
+
+
+def map_reads_through_a_failed_round(seeds, n, cm):
+    """map_reads_c on reads 0..n-1 (one batch: all are added before the first round), every round that fails checked: the
+    mapper is as it was before that round -- every read's state, the stats, the log -- and the same round, made again, goes
+    through.  Returns the lines, the rounds and the number of rounds that failed."""
+    failed = [0]
+    go = cm.round
+
+    def round_(ids, chunks):
+        before = ([cm.state(r) for r in range(n)], cm.stats(), cm.log())
+        try:
+            return go(ids, chunks)
+        except RuntimeError:
+            failed[0] += 1
+        assert ([cm.state(r) for r in range(n)], cm.stats(), cm.log()) == before
+        go(ids, chunks)
+    cm.round = round_
+    lines, rounds = mapper.map_reads_c(seeds, list(range(n)), cm)
+    return lines, rounds, failed[0]
+
+
+@pytest.mark.parametrize("threads", [1, 4])
+def test_cpp_mapper_round_that_fails_in_the_scorer_leaves_nothing(oracle, threads):
+    """A round whose scorer fails, after the checks: it raises, nothing of it stays (the reads' chains, counts and events, the
+    mapper's rounds, parts and log), and the same round made again continues the run to the oracle-scored flow's lines and log."""
+    ref = synth.make_reference([29903, 12000], seed=20231005 + 1)
+    n = 30
+    seeds = mapper.SyntheticSeeds(ref, n, seed=11, max_chunks=4)
+    opt = ra.MapOpt(flag=0x2 | 0x8)
+    lo = []
+    want, rounds = mapper.map_reads(seeds, list(range(n)), OracleScorer(oracle, ref), opt, StopOpt(), log=lo)
+    assert rounds >= 3
+    cm = mapper.CMapper(None, opt, StopOpt(), [f"seq{s}" for s in range(ref.n_seq)], [len(x) for x in ref.forward],
+                        slot_events=max(rd["n_ev"] for rd in seeds.reads) + 8, max_reads=n, carry=True, threads=threads)
+    cm.set_scorer(_fail_once(_oracle_scorer(oracle, ref, opt), rounds // 2))   # (one group: a call a round)
+    got, rounds_c, failed = map_reads_through_a_failed_round(seeds, n, cm)
+    assert failed == 1
+    assert got == want and rounds_c == rounds and cm.stats()[0] == rounds
+    assert cm.log() == "".join(lo) and lo
+    cm.close()
