@@ -569,6 +569,38 @@ int rawdtw_batch_submit_device(rawdtw_ctx *ctx, const rawdtw_align_opt_t *opt, u
                                const uint64_t *anchor_off, const rawdtw_anchor_t *d_anchors, const uint64_t *d_ref_base,
                                const uint32_t *d_read_base, rawdtw_batch **out);
 
+/* ---- event detection: detect_events (src/revent.c:190-210), called once a chunk by ri_map_frag (rmap.cpp:551), bit for bit.
+ *   prefix sums    revent.c:22-32    fp32, serial in sample order (contracted: the squares' sum with one fmaf a sample)
+ *   t-statistics   revent.c:34-75    per window w: all 0 when s_len < 2w or w < 2; else at i in [w, s_len - w] the fp32 means and
+ *                                    variance (contracted: two fmaf), fmaxf(var, FLT_MIN), a double sqrt and a double division
+ *   peaks          revent.c:77-138   the short (window_length1 / threshold1) and long (window_length2 / threshold2) detectors,
+ *                                    whichever window is really shorter; peaks in emission order, never sorted
+ *   events         revent.c:140-188  fp32 segment means, double sums in order, (float)((e - mean) / std) (contracted: one fma in the std)
+ * No peak: no events (*n = 0, as rmap.cpp:547 starts the count).  s_len == 0 (revent.c:24 asserts), a window above 65 535 (our own
+ * bound: the reference's 2 * w_len wraps near 2^31) and offsets that do not ascend strictly: RAWDTW_ERR_INVALID.  A chunk has at most
+ * s_len - 1 peaks and at most as many events as peaks, so s_len slots a chunk (events_cap = sig_off[n_chunks]) always suffice. ---- */
+typedef struct {
+    uint32_t window_length1, window_length2; /* roptions.c:37-38 (3, 6) */
+    float threshold1, threshold2;            /* roptions.c:39-40 (4.30265f, 2.57058f) */
+    float peak_height;                       /* roptions.c:41 (1.0f) */
+    int contracted;                          /* 1: as the reference's Makefile builds revent.c on an FMA host (-O3 -march=native) */
+} rawdtw_event_opt_t;                        /* NULL anywhere = these defaults, contracted 0 */
+
+/* host restatement, one chunk: events has room for s_len; *n = 0 when no boundary is found */
+int rawdtw_detect_events(const rawdtw_event_opt_t *opt, uint32_t s_len, const float *sig, float *events, uint32_t *n);
+/* host, many chunks (chunk k = sig[sig_off[k] .. sig_off[k+1])) on `threads` threads (<= 1: the caller's).  A total above
+ * events_cap: RAWDTW_ERR_RANGE with event_off filled and no event written. */
+int rawdtw_detect_events_host(const rawdtw_event_opt_t *opt, uint32_t n_chunks, const uint64_t *sig_off, const float *sig,
+                              uint64_t *event_off /* n_chunks+1 */, float *events, uint64_t events_cap, int threads);
+/* device, in two halves like rawdtw_chain_round_begin/_end: one detection at a time a context.  _begin checks everything
+ * (nothing is enqueued when it refuses), enqueues the upload and the launches on the context's stream and returns; the host
+ * arrays must stay valid until _end.  _end waits and fills event_off and events: page-locked ones (rawdtw_host_alloc) the
+ * device writes itself, others are copied.  A total above events_cap: RAWDTW_ERR_RANGE from _end with event_off filled; the
+ * device checks the total before it writes a single event.  The detection has its own grow-only workspace on the context. */
+int rawdtw_detect_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint32_t n_chunks, const uint64_t *sig_off,
+                        const float *sig, uint64_t *event_off, float *events, uint64_t events_cap);
+int rawdtw_detect_end(rawdtw_ctx *ctx, float *kernel_ms /* may be NULL: the launches' device time */);
+
 /* ---- the chunk-round mapping loop on the host side of the library: the control flow of map_worker_for / ri_map_frag /
  * gen_chains (src/rmap.cpp:667-822, 545-578, 315-541) turned inside out so that every chunk round makes ONE device
  * submission for all active reads, and the PAF line of a read (src/rmap.cpp:696-801, 950-965).  The caller keeps event

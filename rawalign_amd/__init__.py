@@ -23,10 +23,13 @@ from .align import (  # noqa: F401
     evaluate_reads,
 )
 
+from .events import EventOptions, chunks_of, detect_events, detect_events_host  # noqa: F401
+
 __all__ = [
     "Engine", "Plan", "DtwResult", "JOB_DTYPE", "ANCHOR_DTYPE", "RAWDTW_FULL",
     "MapOpt", "Chain", "Batch", "CandidateBatch", "ReadCandidates", "align_chain", "evaluate_reads",
     "load_library", "library_path", "LibraryMissing", "RawDTWError",
+    "EventOptions", "detect_events", "detect_events_host", "chunks_of",
 ]
 
 DEFAULT_FOLD_MODE = 4  # rawdtw_set_option("fold_mode"): the library's default chain-fold kernel

@@ -95,6 +95,12 @@ class SuOpt(C.Structure):
                 ("contracted", C.c_int)]
 
 
+class EventOpt(C.Structure):
+    """rawdtw_event_opt_t, defaults of src/roptions.c:37-41"""
+    _fields_ = [("window_length1", C.c_uint32), ("window_length2", C.c_uint32), ("threshold1", C.c_float), ("threshold2", C.c_float),
+                ("peak_height", C.c_float), ("contracted", C.c_int)]
+
+
 RAWDTW_SU_NO_STOP = 0xFFFFFFFF  # rawdtw_mapper_su_apply: no stop
 
 
@@ -228,6 +234,10 @@ SYMBOLS = {
     "rawdtw_batch_submit_compact": (I32, [VP, VP, U64, VP, VP, VP, VP, VP, VP, U64, VP, VP, VP]),
     "rawdtw_traceback_timing": (I32, [VP, VP, VP, VP, VP]),
     "rawdtw_batch_replay": (I32, [C.POINTER(AlignOpt), U64, VP, VP, VP, VP, VP, VP, VP]),
+    "rawdtw_detect_events": (I32, [C.POINTER(EventOpt), U32, VP, VP, C.POINTER(U32)]),
+    "rawdtw_detect_events_host": (I32, [C.POINTER(EventOpt), U32, VP, VP, VP, VP, U64, I32]),
+    "rawdtw_detect_begin": (I32, [VP, C.POINTER(EventOpt), U32, VP, VP, VP, VP, U64]),
+    "rawdtw_detect_end": (I32, [VP, C.POINTER(F32)]),
 }
 
 

@@ -143,6 +143,7 @@ struct rawdtw_ctx {
     uint64_t n_ev = 0, cap_ev = 0;
     bool own_ev = false;
     struct rawdtw_chain_ws *chain_ws = nullptr; // rawdtw_chain_round's device block (rawdtw_chain.hip), grow-only
+    struct rawdtw_detect_ws *detect_ws = nullptr; // rawdtw_detect_begin's device block (rawdtw_events.hip), grow-only
     uint32_t chain_max_seeds = 0; // tests: RAWDTW_CHAIN_MAX_SEEDS lowers rawdtw_chain_round's cap on seeds a read, so that small rounds take the declined path (0: no)
     std::string err;
 };
@@ -264,6 +265,7 @@ inline int hip_fail(rawdtw_ctx *ctx, hipError_t e, const char *what)
 }
 
 void chain_ws_free(rawdtw_ctx *ctx); // rawdtw_chain.hip
+void detect_ws_free(rawdtw_ctx *ctx); // rawdtw_events.hip
 
 #define HIP_TRY(ctx, expr)                                                                            \
     do {                                                                                              \

@@ -1,0 +1,20 @@
+// rawdtw_events.h -- what the host restatement (rawdtw_events_host.cpp) and the device path (rawdtw_events.hip) of event
+// detection share.  Internal: nothing here is part of the ABI.
+#pragma once
+#include <cstdint>
+
+#include "../../include/rawdtw.h"
+
+namespace rawdtw {
+namespace events {
+
+// our own bound on the windows: near 2^31 the reference's 2 * w_len wraps and its loop runs off the array (revent.c:46,50)
+constexpr uint32_t kMaxWindow = 65535;
+
+// the options, NULL = roptions.c:37-41 with contracted 0; RAWDTW_ERR_INVALID for a window above kMaxWindow
+int resolve_opt(const rawdtw_event_opt_t *opt, rawdtw_event_opt_t *out);
+// RAWDTW_ERR_INVALID unless every chunk is non-empty (revent.c:24 asserts) and shorter than 2^32
+int check_offsets(uint32_t n_chunks, const uint64_t *sig_off);
+
+} // namespace events
+} // namespace rawdtw

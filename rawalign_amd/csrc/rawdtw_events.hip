@@ -1,0 +1,465 @@
+// rawdtw_events.hip -- event detection (detect_events, src/revent.c:190-210) for a whole chunk round on the device, bit for bit
+// equal to the host restatement (rawdtw_events_host.cpp) and so to the reference, in the plain and the contracted form.
+//
+// Three recurrences are serial per chunk (the prefix sums, the peak state machine, the two double sums of the normalisation);
+// everything else is parallel across positions or events.  Five launches:
+//   k_ev_prefix   a lane per chunk, 64 chunks a wave: samples staged through LDS in 64 x 64 tiles (coalesced loads), each lane
+//                 walks its own row in sample order, the prefix sums go out through LDS again (coalesced stores)
+//   k_ev_tstat    a thread per position over the whole batch, both windows: the bulk of the arithmetic (five correctly
+//                 rounded fp32 divisions, one f64 sqrt and one f64 division per position and window)
+//   k_ev_peaks    a lane per chunk: the two-detector state machine over LDS tiles of both t-statistics; peaks into the chunk's
+//                 own s_len slots, then the chunk's event count
+//   k_ev_scan     one workgroup: exclusive scan of the counts -> event_off and the total
+//   k_ev_events   a wave per chunk: segment means in parallel, the double sums on one lane in emission order, normalisation in
+//                 parallel, written at event_off -- into device memory, or straight into the caller's page-locked array
+// A batch lasts as long as its longest chunk's serial chain: ~4 000 steps for the mapper's chunks; a whole read passed as one
+// chunk works but costs its full length.
+//
+// Exactness: the library is built with -ffp-contract=off -fno-fast-math (and the pragma below says it again for this file);
+// the contracted form names its fused operations (__fmaf_rn, __fma_rn), fp32 division is __fdiv_rn, and f64 `/` and sqrt
+// lower to correctly rounded sequences on gfx950.  Denormals are not flushed.
+#include "rawdtw_capi.h"
+#include "rawdtw_events.h"
+
+#include <cfloat>
+
+#pragma clang fp contract(off)
+
+namespace rawdtw {
+namespace {
+
+constexpr uint32_t kW = 64;       // chunks a wave, and samples a tile
+constexpr uint32_t kPad = kW + 1; // LDS row stride: a lane's row walk and the wave's column loads both hit 64 banks
+constexpr uint32_t kEvLds = 2048; // k_ev_events: a chunk's events up to this many are summed out of LDS
+
+struct EvArgs {
+    const uint64_t *off; // n + 1 sample offsets, rebased to the uploaded samples (off[0] = 0)
+    const float *sig;
+    float *ps, *pss;     // chunk k: s_len + 1 entries from off[k] + k
+    float *t1, *t2;      // chunk k: s_len entries from off[k]
+    uint32_t *peaks;     // chunk k: s_len slots from off[k]
+    uint32_t *npk, *nev; // per chunk: peaks emitted, events
+    uint64_t *eoff;      // n + 1
+    uint64_t *tot;       // [0] the total of events
+    float *ev;           // the events, at eoff (device; n_samples entries)
+    uint32_t n;
+    uint64_t n_samples;
+    rawdtw_event_opt_t opt;
+};
+
+__device__ __forceinline__ uint32_t wave_max(uint32_t x)
+{
+    for (int o = 32; o; o >>= 1) x = max(x, (uint32_t)__shfl_xor((int)x, o));
+    return x;
+}
+
+// lane c's chunk start and length, as every lane sees them
+__device__ __forceinline__ uint64_t lane_u64(uint64_t x, int c)
+{
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)x, c), hi = (uint32_t)__shfl((int)(uint32_t)(x >> 32), c);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// one 64 x 64 tile of a per-sample array into LDS (row c = chunk c, column = sample t0 + lane): all 64 loads are issued before
+// the first LDS store, so a tile costs one memory latency rather than 64
+__device__ __forceinline__ void load_tile(const float *src, uint64_t b, uint32_t len, uint32_t t0, float *tile)
+{
+    const uint32_t i = t0 + threadIdx.x;
+    float v[kW];
+#pragma unroll
+    for (int c = 0; c < (int)kW; c++) {
+        const uint64_t bc = lane_u64(b, c);
+        const uint32_t lc = (uint32_t)__shfl((int)len, c);
+        v[c] = i < lc ? src[bc + i] : 0.0f;
+    }
+#pragma unroll
+    for (int c = 0; c < (int)kW; c++) tile[c * kPad + threadIdx.x] = v[c];
+}
+
+// revent.c:22-32
+__global__ __launch_bounds__(64) void k_ev_prefix(EvArgs a)
+{
+    __shared__ float tx[kW * kPad], tp[kW * kPad], tq[kW * kPad];
+    __shared__ uint64_t sb[kW];
+    __shared__ uint32_t sl[kW];
+    const uint32_t lane = threadIdx.x, c0 = blockIdx.x * kW, me = c0 + lane, nc = min(kW, a.n - c0);
+    uint64_t b = 0;
+    uint32_t len = 0;
+    if (lane < nc) { b = a.off[me]; len = (uint32_t)(a.off[me + 1] - b); }
+    sb[lane] = b; sl[lane] = len;
+    const uint32_t most = wave_max(len);
+    if (lane < nc) { a.ps[b + me] = 0.0f; a.pss[b + me] = 0.0f; }
+    const bool fused = a.opt.contracted != 0;
+    float s = 0.0f, q = 0.0f;
+    __syncthreads();
+    for (uint32_t t0 = 0; t0 < most; t0 += kW) {
+        const uint32_t i = t0 + lane;
+        load_tile(a.sig, b, len, t0, tx);
+        __syncthreads();
+        const uint32_t lim = len > t0 ? min(kW, len - t0) : 0u;
+        for (uint32_t j = 0; j < lim; j++) {
+            const float x = tx[lane * kPad + j];
+            s = s + x;
+            q = fused ? __fmaf_rn(x, x, q) : q + x * x;
+            tp[lane * kPad + j] = s;
+            tq[lane * kPad + j] = q;
+        }
+        __syncthreads();
+        for (uint32_t c = 0; c < nc; c++)
+            if (i < sl[c]) {
+                const uint64_t d = sb[c] + c0 + c + 1 + i;
+                a.ps[d] = tp[c * kPad + lane];
+                a.pss[d] = tq[c * kPad + lane];
+            }
+        __syncthreads();
+    }
+}
+
+// the largest k in [lo, hi] with off[k] <= j
+__device__ __forceinline__ uint32_t chunk_of(const uint64_t *off, uint32_t lo, uint32_t hi, uint64_t j)
+{
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (off[mid] <= j) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// revent.c:46-70 at position i of a chunk of n samples (P, Q: its prefix sums)
+__device__ __forceinline__ float tstat_at(const float *P, const float *Q, uint32_t n, uint32_t i, uint32_t w, bool fused)
+{
+    if (n < 2 * w || w < 2 || i < w || i > n - w) return 0.0f;
+    float s1 = P[i], q1 = Q[i];
+    if (i > w) {
+        s1 = s1 - P[i - w];
+        q1 = q1 - Q[i - w];
+    }
+    const float s2 = P[i + w] - P[i], q2 = Q[i + w] - Q[i];
+    const float wf = (float)w;
+    const float m1 = __fdiv_rn(s1, wf), m2 = __fdiv_rn(s2, wf);
+    float cv = fused ? __fmaf_rn(-m2, m2, __fmaf_rn(-m1, m1, __fdiv_rn(q1, wf)) + __fdiv_rn(q2, wf))
+                     : __fdiv_rn(q1, wf) - m1 * m1 + __fdiv_rn(q2, wf) - m2 * m2;
+    cv = fmaxf(cv, FLT_MIN);
+    return (float)(fabs((double)(m2 - m1)) / sqrt((double)__fdiv_rn(cv, wf)));
+}
+
+__global__ __launch_bounds__(256) void k_ev_tstat(EvArgs a)
+{
+    __shared__ uint32_t kr[2];
+    const uint64_t j0 = (uint64_t)blockIdx.x * 256, j = j0 + threadIdx.x;
+    if (threadIdx.x == 0) kr[0] = chunk_of(a.off, 0, a.n - 1, j0);
+    if (threadIdx.x == 1) kr[1] = chunk_of(a.off, 0, a.n - 1, min(j0 + 255, a.n_samples - 1));
+    __syncthreads();
+    if (j >= a.n_samples) return;
+    const uint32_t k = chunk_of(a.off, kr[0], kr[1], j);
+    const uint64_t b = a.off[k];
+    const uint32_t len = (uint32_t)(a.off[k + 1] - b), i = (uint32_t)(j - b);
+    const float *P = a.ps + b + k, *Q = a.pss + b + k;
+    const bool fused = a.opt.contracted != 0;
+    a.t1[j] = tstat_at(P, Q, len, i, a.opt.window_length1, fused);
+    a.t2[j] = tstat_at(P, Q, len, i, a.opt.window_length2, fused);
+}
+
+struct Det {
+    float pv;     // peak_value
+    int pp;       // peak_pos
+    uint32_t mt;  // masked_to
+    bool valid;
+};
+
+// revent.c:77-138.  Peaks: at most s_len - 1 a chunk (a detector emits from step 2 on, at most once every window_length / 2 + 2
+// >= 2 steps), so the chunk's s_len slots always suffice; the guard below only keeps a broken invariant inside the chunk.
+__global__ __launch_bounds__(64) void k_ev_peaks(EvArgs a)
+{
+    __shared__ float ta[kW * kPad], tb[kW * kPad];
+    const uint32_t lane = threadIdx.x, c0 = blockIdx.x * kW, me = c0 + lane, nc = min(kW, a.n - c0);
+    uint64_t b = 0;
+    uint32_t len = 0;
+    if (lane < nc) { b = a.off[me]; len = (uint32_t)(a.off[me + 1] - b); }
+    const uint32_t most = wave_max(len);
+    const float th[2] = {a.opt.threshold1, a.opt.threshold2}, ph = a.opt.peak_height;
+    const uint32_t wl[2] = {a.opt.window_length1, a.opt.window_length2};
+    Det d[2] = {{FLT_MAX, -1, 0u, false}, {FLT_MAX, -1, 0u, false}};
+    uint32_t cur = 0, inside = 0;
+    uint32_t *pk = a.peaks + b;
+    __syncthreads();
+    for (uint32_t t0 = 0; t0 < most; t0 += kW) {
+        load_tile(a.t1, b, len, t0, ta);
+        load_tile(a.t2, b, len, t0, tb);
+        __syncthreads();
+        const uint32_t lim = len > t0 ? min(kW, len - t0) : 0u;
+        for (uint32_t j = 0; j < lim; j++) {
+            const uint32_t i = t0 + j;
+            const float x[2] = {ta[lane * kPad + j], tb[lane * kPad + j]};
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                Det &D = d[k];
+                if (D.mt >= i) continue;
+                const float v = x[k];
+                if (D.pp == -1) {
+                    if (v < D.pv) D.pv = v;
+                    else if (v - D.pv > ph) { D.pv = v; D.pp = (int)i; }
+                } else {
+                    if (v > D.pv) { D.pv = v; D.pp = (int)i; }
+                    if (k == 0 && D.pv > th[0]) d[1] = Det{FLT_MAX, -1, (uint32_t)D.pp + wl[0], false};
+                    if (D.pv - v > ph && D.pv > th[k]) D.valid = true;
+                    if (D.valid && (i - (uint32_t)D.pp) > wl[k] / 2) {
+                        const uint32_t p = (uint32_t)D.pp;
+                        if (cur < len) pk[cur] = p;
+                        if (cur >= 1 && p > 0 && p < len) inside++; // revent.c:145-147
+                        cur++;
+                        D.pp = -1;
+                        D.pv = v;
+                        D.valid = false;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (lane < nc) {
+        a.npk[me] = min(cur, len);
+        a.nev[me] = cur ? min(1 + inside, len) : 0; // revent.c:206: no peak, no events (the min: see above)
+    }
+}
+
+// exclusive scan of the event counts
+__global__ __launch_bounds__(1024) void k_ev_scan(const uint32_t *nev, uint32_t n, uint64_t *eoff, uint64_t *tot, uint64_t *h_eoff)
+{
+    __shared__ uint64_t part[1024];
+    const uint32_t t = threadIdx.x;
+    const uint64_t per = (n + 1023ull) / 1024, lo = min((uint64_t)n, t * per), hi = min((uint64_t)n, lo + per);
+    uint64_t s = 0;
+    for (uint64_t k = lo; k < hi; k++) s += nev[k];
+    part[t] = s;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024; d <<= 1) {
+        const uint64_t v = t >= d ? part[t - d] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    uint64_t run = part[t] - s;
+    for (uint64_t k = lo; k < hi; k++) {
+        eoff[k] = run;
+        if (h_eoff) h_eoff[k] = run;
+        run += nev[k];
+    }
+    if (t == 1023) {
+        eoff[n] = part[1023];
+        if (h_eoff) h_eoff[n] = part[1023];
+        tot[0] = part[1023];
+    }
+}
+
+// revent.c:140-188.  Nothing is written unless the whole round's events fit below `bound` (the caller's events_cap, and the
+// device array's size).
+__global__ __launch_bounds__(64) void k_ev_events(EvArgs a, uint64_t bound, float *out)
+{
+    __shared__ double stat[2];
+    __shared__ float se[kEvLds]; // the chunk's events for the serial sums, when they fit
+    if (a.tot[0] > bound) return;
+    const uint32_t k = blockIdx.x, lane = threadIdx.x, nev = a.nev[k];
+    if (!nev) return;
+    const uint64_t b = a.off[k], eo = a.eoff[k];
+    const uint32_t len = (uint32_t)(a.off[k + 1] - b);
+    const float *P = a.ps + b + k;
+    const uint32_t *pk = a.peaks + b;
+    float *ev = a.ev + eo;
+    for (uint32_t p = lane; p < nev; p += kW) {
+        const uint32_t l = p ? pk[p - 1] : 0u, e = p + 1 < nev ? pk[p] : len;
+        const float l_ps = p ? P[l] : 0.0f, l_peak = p ? (float)l : 0.0f;
+        const float x = __fdiv_rn(P[e] - l_ps, (float)e - l_peak);
+        ev[p] = x;
+        if (nev <= kEvLds) se[p] = x;
+    }
+    __syncthreads();
+    if (lane == 0) {
+        const float *src = nev <= kEvLds ? se : ev;
+        double sum = 0, sum2 = 0;
+        for (uint32_t p = 0; p < nev; p++) {
+            const float e = src[p];
+            sum += (double)e;
+            sum2 += (double)(e * e); // (the float product, widened)
+        }
+        const double mean = sum / (double)nev, m2 = sum2 / (double)nev;
+        stat[0] = mean;
+        stat[1] = sqrt(a.opt.contracted ? __fma_rn(-mean, mean, m2) : m2 - mean * mean);
+    }
+    __syncthreads();
+    const double mean = stat[0], sd = stat[1];
+    float *dst = (out ? out : a.ev) + eo;
+    for (uint32_t p = lane; p < nev; p += kW) dst[p] = (float)(((double)ev[p] - mean) / sd);
+}
+
+struct DetectWs {
+    void *dev = nullptr;
+    size_t dev_bytes = 0;
+    uint64_t *pin = nullptr; // [0] the total; then the rebased offsets
+    size_t pin_bytes = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, done = nullptr;
+    // a detection begun and not ended
+    bool pending = false, direct_off = false, direct_ev = false;
+    uint32_t n = 0;
+    uint64_t n_samples = 0, cap = 0;
+    uint64_t *h_eoff = nullptr;
+    float *h_ev = nullptr;
+    const uint64_t *d_eoff = nullptr;
+    const float *d_ev = nullptr;
+};
+
+// the device address of a page-locked host array of `bytes` bytes, or null (pageable memory, or an allocation that does not
+// extend that far: then the array is copied in rawdtw_detect_end)
+void *device_view(void *p, size_t bytes)
+{
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (at.type != hipMemoryTypeHost || !at.devicePointer) return nullptr;
+    hipDeviceptr_t start = nullptr;
+    size_t size = 0;
+    if (hipPointerGetAttribute(&start, HIP_POINTER_ATTRIBUTE_RANGE_START_ADDR, p) != hipSuccess ||
+        hipPointerGetAttribute(&size, HIP_POINTER_ATTRIBUTE_RANGE_SIZE, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    const char *s = static_cast<const char *>(start), *q = static_cast<const char *>(p);
+    if (q < s || (size_t)(q - s) > size || size - (size_t)(q - s) < bytes) return nullptr;
+    return at.devicePointer;
+}
+
+} // namespace
+} // namespace rawdtw
+
+using namespace rawdtw;
+using namespace rawdtw::capi;
+
+struct rawdtw_detect_ws { DetectWs w; };
+
+extern "C" {
+
+int rawdtw_detect_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint32_t n_chunks, const uint64_t *sig_off, const float *sig,
+                        uint64_t *event_off, float *events, uint64_t events_cap)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (!sig_off || !event_off || (n_chunks && (!sig || !events))) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    if (ctx->detect_ws && ctx->detect_ws->w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "a detection is begun on this context and not ended");
+    rawdtw_event_opt_t o;
+    if (events::resolve_opt(opt, &o) != RAWDTW_OK) return fail(ctx, RAWDTW_ERR_INVALID, "a window length above 65535");
+    if (events::check_offsets(n_chunks, sig_off) != RAWDTW_OK)
+        return fail(ctx, RAWDTW_ERR_INVALID, "an empty chunk (revent.c:24 asserts), a chunk of 2^32 samples or more, or offsets that descend");
+    if (n_chunks >= 0x7fffffffu) return fail(ctx, RAWDTW_ERR_INVALID, "2^31 chunks or more");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t n = n_chunks, N = sig_off[n] - sig_off[0];
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t b_off = al((n + 1) * 8), b_sig = al(N * 4), b_ps = al((N + n) * 4), b_t = al(N * 4), b_cnt = al(n * 4), b_eoff = al((n + 1) * 8),
+                 b_tot = al(32);
+    // sig, ps, pss, t1, t2, peaks, events: 28 bytes a sample
+    const size_t need = b_off + b_sig + 2 * b_ps + 2 * b_t + b_t + 2 * b_cnt + b_eoff + b_tot + b_t;
+    if (!ctx->detect_ws) ctx->detect_ws = new (std::nothrow) rawdtw_detect_ws;
+    if (!ctx->detect_ws) return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed");
+    DetectWs &w = ctx->detect_ws->w;
+    if (w.dev_bytes < need) {
+        if (w.dev) (void)hipFree(w.dev);
+        w.dev = nullptr; w.dev_bytes = 0;
+        const size_t want = need + need / 4;
+        if (hipMalloc(&w.dev, want) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, RAWDTW_ERR_OOM, "detection workspace allocation failed"); }
+        w.dev_bytes = want;
+    }
+    const size_t pin_need = (n + 2) * 8;
+    if (w.pin_bytes < pin_need) {
+        if (w.pin) (void)hipHostFree(w.pin);
+        w.pin = nullptr; w.pin_bytes = 0;
+        const size_t want = pin_need + pin_need / 4;
+        if (hipHostMalloc(reinterpret_cast<void **>(&w.pin), want, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError(); w.pin = nullptr;
+            return fail(ctx, RAWDTW_ERR_OOM, "pinned allocation failed");
+        }
+        w.pin_bytes = want;
+    }
+    if (!w.ev0) HIP_TRY(ctx, hipEventCreate(&w.ev0));
+    if (!w.ev1) HIP_TRY(ctx, hipEventCreate(&w.ev1));
+    if (!w.done) HIP_TRY(ctx, hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
+    w.pending = true; w.n = n_chunks; w.n_samples = N; w.cap = events_cap;
+    w.h_eoff = event_off; w.h_ev = events;
+    if (n == 0) { w.direct_off = w.direct_ev = false; return RAWDTW_OK; }
+    char *p = static_cast<char *>(w.dev);
+    EvArgs a{};
+    uint64_t *d_off = reinterpret_cast<uint64_t *>(p); p += b_off;
+    float *d_sig = reinterpret_cast<float *>(p); p += b_sig;
+    a.ps = reinterpret_cast<float *>(p); p += b_ps;
+    a.pss = reinterpret_cast<float *>(p); p += b_ps;
+    a.t1 = reinterpret_cast<float *>(p); p += b_t;
+    a.t2 = reinterpret_cast<float *>(p); p += b_t;
+    a.peaks = reinterpret_cast<uint32_t *>(p); p += b_t;
+    a.npk = reinterpret_cast<uint32_t *>(p); p += b_cnt;
+    a.nev = reinterpret_cast<uint32_t *>(p); p += b_cnt;
+    a.eoff = reinterpret_cast<uint64_t *>(p); p += b_eoff;
+    a.tot = reinterpret_cast<uint64_t *>(p); p += b_tot;
+    a.ev = reinterpret_cast<float *>(p);
+    a.off = d_off; a.sig = d_sig; a.n = n_chunks; a.n_samples = N; a.opt = o;
+    uint64_t *h_off = w.pin + 1;
+    for (uint64_t k = 0; k <= n; k++) h_off[k] = sig_off[k] - sig_off[0];
+    uint64_t *dv_eoff = static_cast<uint64_t *>(device_view(event_off, (n + 1) * 8));
+    float *dv_ev = static_cast<float *>(device_view(events, events_cap * 4));
+    w.direct_off = dv_eoff != nullptr; w.direct_ev = dv_ev != nullptr;
+    w.d_eoff = a.eoff; w.d_ev = a.ev;
+    hipStream_t s = ctx->stream;
+    auto undo = [&](int st) { w.pending = false; return st; };
+    if (hipMemcpyAsync(d_off, h_off, (n + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(d_sig, sig + sig_off[0], N * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipEventRecord(w.ev0, s) != hipSuccess)
+        return undo(hip_fail(ctx, hipGetLastError(), "detection upload"));
+    const uint32_t waves = (uint32_t)((n + kW - 1) / kW);
+    hipLaunchKernelGGL(k_ev_prefix, dim3(waves), dim3(kW), 0, s, a);
+    hipLaunchKernelGGL(k_ev_tstat, dim3((uint32_t)((N + 255) / 256)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_ev_peaks, dim3(waves), dim3(kW), 0, s, a);
+    hipLaunchKernelGGL(k_ev_scan, dim3(1), dim3(1024), 0, s, a.nev, n_chunks, a.eoff, a.tot, dv_eoff);
+    hipLaunchKernelGGL(k_ev_events, dim3(n_chunks), dim3(kW), 0, s, a, std::min<uint64_t>(events_cap, N), dv_ev);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(w.ev1, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(w.pin, a.tot, 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipEventRecord(w.done, s);
+    if (e != hipSuccess) return undo(hip_fail(ctx, e, "detection launches"));
+    return RAWDTW_OK;
+}
+
+int rawdtw_detect_end(rawdtw_ctx *ctx, float *kernel_ms)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (!ctx->detect_ws || !ctx->detect_ws->w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "no detection begun on this context");
+    DetectWs &w = ctx->detect_ws->w;
+    w.pending = false;
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if (w.n == 0) { w.h_eoff[0] = 0; return RAWDTW_OK; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    HIP_TRY(ctx, hipEventSynchronize(w.done)); // (the detection's own work: what the caller enqueued behind it goes on)
+    const uint64_t tot = w.pin[0];
+    if (!w.direct_off) {
+        HIP_TRY(ctx, hipMemcpyAsync(w.h_eoff, w.d_eoff, ((uint64_t)w.n + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+    }
+    if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, w.ev0, w.ev1));
+    if (tot > w.cap) return fail(ctx, RAWDTW_ERR_RANGE, "events_cap is below the round's events (event_off is filled)");
+    if (tot > w.n_samples) return fail(ctx, RAWDTW_ERR_DEVICE, "more events than samples");
+    if (!w.direct_ev && tot) {
+        HIP_TRY(ctx, hipMemcpyAsync(w.h_ev, w.d_ev, tot * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+    }
+    return RAWDTW_OK;
+}
+
+} // extern "C"
+
+namespace rawdtw { namespace capi {
+void detect_ws_free(rawdtw_ctx *ctx)
+{
+    if (!ctx || !ctx->detect_ws) return;
+    DetectWs &w = ctx->detect_ws->w;
+    if (w.dev) (void)hipFree(w.dev);
+    if (w.pin) (void)hipHostFree(w.pin);
+    for (hipEvent_t e : {w.ev0, w.ev1, w.done}) if (e) (void)hipEventDestroy(e);
+    delete ctx->detect_ws;
+    ctx->detect_ws = nullptr;
+}
+} }

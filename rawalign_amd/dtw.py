@@ -192,6 +192,41 @@ class Engine:
         self._check(self.lib.rawdtw_set_events_device(self._ctx, C.c_void_p(data_ptr), n_floats))
         self._keep_ev = keepalive
 
+    # -- event detection (detect_events, src/revent.c:190-210) ---------------------
+    def detect_events(self, sig, sig_off, opt=None, pinned: bool = True, events_cap=None, kernel_ms: bool = False):
+        """Every chunk k = sig[sig_off[k] .. sig_off[k+1]) on the device: rawdtw_detect_begin, then _end.  The samples go up
+        from, and the results come back into, page-locked staging that the engine keeps (pinned=False: pageable arrays, which
+        _end copies into).  Returns (event_off, events), and the launches' device time in ms too when kernel_ms."""
+        from .events import PinnedArray, _opt
+
+        sig = np.asarray(sig, np.float32)
+        off = np.ascontiguousarray(sig_off, np.uint64)
+        n = len(off) - 1
+        cap = int(off[-1]) if events_cap is None else int(events_cap)
+        if pinned:
+            st = getattr(self, "_ev_stage", None)
+            if st is None or st["sig"].array.size < len(sig) or st["off"].array.size < n + 1 or st["ev"].array.size < cap:
+                st = self._ev_stage = {"sig": PinnedArray(len(sig), np.float32), "off": PinnedArray(n + 1, np.uint64),
+                                       "eoff": PinnedArray(n + 1, np.uint64), "ev": PinnedArray(cap, np.float32)}
+            if st["eoff"].array.size < n + 1:
+                st["eoff"] = PinnedArray(n + 1, np.uint64)
+            h_sig, h_off, eoff, ev = st["sig"].array, st["off"].array, st["eoff"].array, st["ev"].array
+            h_sig[:len(sig)] = sig
+            h_off[:n + 1] = off
+        else:
+            h_sig, h_off = np.ascontiguousarray(sig), off
+            eoff, ev = np.zeros(n + 1, np.uint64), np.empty(max(cap, 1), np.float32)
+        ms = C.c_float()
+        self._check(self.lib.rawdtw_detect_begin(self._ctx, _opt(opt), n, h_off.ctypes.data, h_sig.ctypes.data, eoff.ctypes.data,
+                                                 ev.ctypes.data, cap))
+        st = self.lib.rawdtw_detect_end(self._ctx, C.byref(ms))
+        if st != 0:
+            err = RawDTWError(st, self.lib.rawdtw_last_error(self._ctx).decode())
+            err.event_off = eoff[:n + 1].copy()
+            raise err
+        out = (eoff[:n + 1].copy(), ev[:int(eoff[n])].copy())
+        return out + (float(ms.value),) if kernel_ms else out
+
     # -- batches ----------------------------------------------------------------
     def plan(self, jobs) -> Plan:
         jobs = np.ascontiguousarray(jobs, dtype=JOB_DTYPE)

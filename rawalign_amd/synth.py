@@ -11,7 +11,7 @@ FAST5 reader exists in this environment, so bench.py and the larger tests build 
                     hit probability) plus decoy chains at random reference positions, listed in
                     evaluation order (true chain first = highest chaining score)
 
-Event detection, seeding and chaining themselves stay on the host in RawAlign and are out of scope
+Seeding and chaining themselves stay on the host in RawAlign and are out of scope
 here; this module only imitates their OUTPUT so that the job-shape mix
 (thousands of 2..50-event segments plus occasional long decoy segments) is realistic."""
 from __future__ import annotations
@@ -351,3 +351,29 @@ def make_seed_chunks(ref: Reference, n_reads: int, seed: int, events_per_chunk: 
         hits[f] = allh[f]
     return {"n_reads": n_reads, "n_chunks": n_chunks.astype(np.int64), "qlen": (n_chunks * 4000).astype(np.int64), "chunk_first": chunk_first,
             "ev_off": ev_off, "events": events, "hit_off": hit_off, "hits": hits, "mappable": mappable, "n_ev": n_ev, "seq_lens": lens}
+
+
+def make_raw_reads(n_reads: int, n_samples=4000, seed: int = 0, sample_rate: int = 4000, bp_per_sec: int = 450,
+                   noise_pA: float = 2.0, k: int = 6) -> list:
+    """Raw nanopore reads in pA, the input of event detection (src/revent.c:190): a random sequence's k-mer levels from
+    make_pore_model (pA, not z-normalised), each held for a geometric dwell of mean sample_rate / bp_per_sec samples
+    (roptions.c:9-10: ~8.9), Gaussian noise of noise_pA, and a per-read scale and offset.  n_samples: one length for every read or
+    one a read.  Returns float32 arrays."""
+    pore = make_pore_model(k)
+    rng = np.random.default_rng(seed)
+    lens = np.broadcast_to(np.asarray(n_samples, np.int64), (n_reads,))
+    p = bp_per_sec / sample_rate
+    reads = []
+    for L in lens:
+        L = int(L)
+        n_kmers = int(L * p * 1.5) + 16
+        levels = np.zeros(0, np.float32)
+        while len(levels) < L:
+            codes = rng.integers(0, 4, n_kmers + k - 1, dtype=np.uint8)
+            idx = np.zeros(n_kmers, np.int64)
+            for j in range(k):
+                idx = (idx << 2) | codes[j:j + n_kmers].astype(np.int64)
+            levels = np.concatenate([levels, np.repeat(pore[idx], rng.geometric(p, n_kmers))])
+        scale, offset = rng.uniform(0.85, 1.15), rng.uniform(-8.0, 8.0)
+        reads.append((levels[:L].astype(np.float64) * scale + offset + rng.normal(0.0, noise_pA, L)).astype(np.float32))
+    return reads
