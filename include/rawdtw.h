@@ -601,11 +601,50 @@ int rawdtw_detect_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint32_t
                         const float *sig, uint64_t *event_off, float *events, uint64_t events_cap);
 int rawdtw_detect_end(rawdtw_ctx *ctx, float *kernel_ms /* may be NULL: the launches' device time */);
 
+/* ---- raw signal in: the int16 DAC samples of a signal file to pA, and the outlier filter (ri_read_sig, src/rsig.cpp:216-224),
+ * bit for bit.  Per read, with the channel's three numbers as floats (ri_sig_t, src/rsig.h:16):
+ *   scale = range / digitisation             one fp32 division
+ *   pA    = ((float)raw[i] + offset) * scale one fp32 add, then one fp32 multiply (nothing to contract)
+ *   kept  iff pA > 30 && pA < 200            ordered compares: NaN and infinities are dropped
+ * sig = the kept pA values in order, l_sig = how many.  A digitisation of 0 and non-finite channel values are not refused:
+ * IEEE arithmetic decides, the same on the host and on the device.  The filter runs BEFORE map_worker_for cuts chunks
+ * (rmap.cpp:685-690), so a chunk's place in raw positions depends on the data: rawdtw_signal_chunk_table finds it in one pass. ---- */
+typedef struct {
+    float digitisation, range, offset; /* ri_sig_t dig, ran, offset */
+} rawdtw_channel_t;
+
+/* one read on the host.  pa: n_raw slots (the first *l_sig are written), or NULL to count only.  *l_sig = the kept samples. */
+int rawdtw_signal_to_pa(const rawdtw_channel_t *ch, uint64_t n_raw, const int16_t *raw, float *pa, uint64_t *l_sig);
+/* one pass over a read when it is taken in: *l_sig of the WHOLE read (the PAF line's read length, rmap.cpp:678; what
+ * rawdtw_mapper_add_read takes as qlen), *n_chunks = min(max_num_chunk, ceil(l_sig / chunk_size)), and where each chunk begins
+ * in raw positions: raw_start[c] = the index of kept sample number c * chunk_size, raw_start[n_chunks] = 1 + the index of the
+ * last kept sample of the last chunk (raw_start[0] = 0 when nothing is kept).  The kept samples of
+ * raw[raw_start[c] .. raw_start[c+1]) are exactly chunk c.  raw_start has max_num_chunk + 1 slots.  chunk_size 0: INVALID. */
+int rawdtw_signal_chunk_table(const rawdtw_channel_t *ch, uint64_t n_raw, const int16_t *raw, uint32_t chunk_size,
+                              uint32_t max_num_chunk, uint64_t *l_sig, uint32_t *n_chunks, uint64_t *raw_start);
+/* host, many windows on `threads` threads: window k = raw[raw_off[k] .. raw_off[k+1]) with channel chan[k]; its kept pA
+ * samples are the chunk, s_len[k] how many (0, an empty or all-outlier window: no events, not an error), events as
+ * rawdtw_detect_events_host's.  events_cap = raw_off[n_chunks] - raw_off[0] always suffices. */
+int rawdtw_detect_raw_host(const rawdtw_event_opt_t *opt, uint32_t n_chunks, const uint64_t *raw_off, const int16_t *raw,
+                           const rawdtw_channel_t *chan /* n_chunks */, uint32_t *s_len /* n_chunks */,
+                           uint64_t *event_off /* n_chunks+1 */, float *events, uint64_t events_cap, int threads);
+/* device: rawdtw_detect_begin for raw windows.  The int16 samples go up as they are (2 bytes a sample), are converted,
+ * filtered and compacted in order on the device, and the kept samples run through the same detection launches.  One detection
+ * at a time a context, of either kind; rawdtw_detect_end ends this one too and fills s_len, event_off and events (page-locked
+ * arrays the device writes itself, others are copied).  Refused before anything is enqueued: null arguments, offsets that
+ * descend, a window of 2^32 samples or more, a detection already begun, a window length above 65 535.  An EMPTY window
+ * (raw_off[k+1] == raw_off[k]) is allowed: s_len 0 and no events. */
+int rawdtw_detect_raw_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint32_t n_chunks, const uint64_t *raw_off,
+                            const int16_t *raw, const rawdtw_channel_t *chan /* n_chunks */, uint32_t *s_len /* n_chunks */,
+                            uint64_t *event_off /* n_chunks+1 */, float *events, uint64_t events_cap);
+
 /* ---- the chunk-round mapping loop on the host side of the library: the control flow of map_worker_for / ri_map_frag /
  * gen_chains (src/rmap.cpp:667-822, 545-578, 315-541) turned inside out so that every chunk round makes ONE device
- * submission for all active reads, and the PAF line of a read (src/rmap.cpp:696-801, 950-965).  The caller keeps event
- * detection and seeding (revent.c, rsketch.c, rawindex.cpp) and hands in, per round and active read, the chunk's events and
- * seed hits; the mapper appends the events to the read's slot in the event arena (rmap.cpp:554-567), re-seeds with the
+ * submission for all active reads, and the PAF line of a read (src/rmap.cpp:696-801, 950-965).  The caller keeps reading the
+ * signal file (the int16 samples and the channel's three numbers: rsig.cpp up to line 215), the calls of event detection
+ * (rawdtw_detect_raw_begin on the raw samples, which takes ri_read_sig's pA conversion and outlier filter, rsig.cpp:216-224,
+ * with it; rawdtw_signal_chunk_table gives the read's qlen and its chunks' places) and seeding (rsketch.c, rawindex.cpp), and
+ * hands in, per round and active read, the chunk's events and seed hits; the mapper appends the events to the read's slot in the event arena (rmap.cpp:554-567), re-seeds with the
  * previous chains' anchors (344-357), chains (396-507), orders the chains (512), scores them all in one batch on the
  * device (509-530; with `carry` the unchanged parts' costs are taken over from the round before), and finishes the round:
  * gen_primary_chains, comp_mapq, the stop rule (532-541, 692).  rawdtw_mapper_finish runs the --dtw-output-cigar

@@ -24,12 +24,14 @@ from .align import (  # noqa: F401
 )
 
 from .events import EventOptions, chunks_of, detect_events, detect_events_host  # noqa: F401
+from .rawsig import CHANNEL_DTYPE, Channel, chunk_table, detect_events_raw_host, to_pa  # noqa: F401
 
 __all__ = [
     "Engine", "Plan", "DtwResult", "JOB_DTYPE", "ANCHOR_DTYPE", "RAWDTW_FULL",
     "MapOpt", "Chain", "Batch", "CandidateBatch", "ReadCandidates", "align_chain", "evaluate_reads",
     "load_library", "library_path", "LibraryMissing", "RawDTWError",
     "EventOptions", "detect_events", "detect_events_host", "chunks_of",
+    "Channel", "CHANNEL_DTYPE", "to_pa", "chunk_table", "detect_events_raw_host",
 ]
 
 DEFAULT_FOLD_MODE = 4  # rawdtw_set_option("fold_mode"): the library's default chain-fold kernel

@@ -101,6 +101,11 @@ class EventOpt(C.Structure):
                 ("peak_height", C.c_float), ("contracted", C.c_int)]
 
 
+class Channel(C.Structure):
+    """rawdtw_channel_t: ri_sig_t's dig, ran, offset (src/rsig.h:16)"""
+    _fields_ = [("digitisation", C.c_float), ("range", C.c_float), ("offset", C.c_float)]
+
+
 RAWDTW_SU_NO_STOP = 0xFFFFFFFF  # rawdtw_mapper_su_apply: no stop
 
 
@@ -238,6 +243,10 @@ SYMBOLS = {
     "rawdtw_detect_events_host": (I32, [C.POINTER(EventOpt), U32, VP, VP, VP, VP, U64, I32]),
     "rawdtw_detect_begin": (I32, [VP, C.POINTER(EventOpt), U32, VP, VP, VP, VP, U64]),
     "rawdtw_detect_end": (I32, [VP, C.POINTER(F32)]),
+    "rawdtw_signal_to_pa": (I32, [VP, U64, VP, VP, C.POINTER(U64)]),
+    "rawdtw_signal_chunk_table": (I32, [VP, U64, VP, U32, U32, C.POINTER(U64), C.POINTER(U32), VP]),
+    "rawdtw_detect_raw_host": (I32, [C.POINTER(EventOpt), U32, VP, VP, VP, VP, VP, VP, U64, I32]),
+    "rawdtw_detect_raw_begin": (I32, [VP, C.POINTER(EventOpt), U32, VP, VP, VP, VP, VP, VP, U64]),
 }
 
 

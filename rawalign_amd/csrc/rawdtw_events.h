@@ -15,6 +15,11 @@ constexpr uint32_t kMaxWindow = 65535;
 int resolve_opt(const rawdtw_event_opt_t *opt, rawdtw_event_opt_t *out);
 // RAWDTW_ERR_INVALID unless every chunk is non-empty (revent.c:24 asserts) and shorter than 2^32
 int check_offsets(uint32_t n_chunks, const uint64_t *sig_off);
+// the raw entries' rule: an empty window is allowed (a read whose tail is all outliers has one)
+int check_raw_offsets(uint32_t n_chunks, const uint64_t *raw_off);
+
+// rsig.cpp:216-224 (rawdtw_rawsig.cpp): the kept pA samples of raw[0 .. n) into pa (n slots, or null: count only); returns how many
+uint64_t to_pa(const rawdtw_channel_t &ch, uint64_t n, const int16_t *raw, float *pa);
 
 } // namespace events
 } // namespace rawdtw

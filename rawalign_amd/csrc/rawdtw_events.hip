@@ -12,6 +12,14 @@
 //   k_ev_scan     one workgroup: exclusive scan of the counts -> event_off and the total
 //   k_ev_events   a wave per chunk: segment means in parallel, the double sums on one lane in emission order, normalisation in
 //                 parallel, written at event_off -- into device memory, or straight into the caller's page-locked array
+// The raw entry (rawdtw_detect_raw_begin) puts three launches in front, which turn windows of int16 DAC samples into the same dense
+// pA chunks (ri_read_sig, src/rsig.cpp:216-224: convert, drop the outliers, keep the order):
+//   k_raw_count   a wave per window: 16 bytes = 8 samples a lane and load, the kept samples counted -> s_len
+//   k_ev_scan     the same scan, over s_len -> the chunks' sample offsets and the sample total, which stay on the device
+//   k_raw_compact a wave per window: the same conversion, the kept samples ranked across the wave, gathered in LDS and written
+//                 out lane by lane (coalesced) at the chunk's offset
+// after which EvArgs.off means what it always means; k_ev_tstat, which takes the sample total from the host, reads it from device
+// memory instead (EvArgs.n_dev) under a grid sized by the raw total.
 // A batch lasts as long as its longest chunk's serial chain: ~4 000 steps for the mapper's chunks; a whole read passed as one
 // chunk works but costs its full length.
 //
@@ -44,6 +52,7 @@ struct EvArgs {
     float *ev;           // the events, at eoff (device; n_samples entries)
     uint32_t n;
     uint64_t n_samples;
+    const uint64_t *n_dev; // the raw entry: the kept samples' total, known to the device alone (n_samples then bounds it)
     rawdtw_event_opt_t opt;
 };
 
@@ -147,10 +156,12 @@ __global__ __launch_bounds__(256) void k_ev_tstat(EvArgs a)
 {
     __shared__ uint32_t kr[2];
     const uint64_t j0 = (uint64_t)blockIdx.x * 256, j = j0 + threadIdx.x;
+    const uint64_t n_samples = a.n_dev ? a.n_dev[0] : a.n_samples;
+    if (j0 >= n_samples) return; // (the whole workgroup: only the raw entry's grid reaches past the total)
     if (threadIdx.x == 0) kr[0] = chunk_of(a.off, 0, a.n - 1, j0);
-    if (threadIdx.x == 1) kr[1] = chunk_of(a.off, 0, a.n - 1, min(j0 + 255, a.n_samples - 1));
+    if (threadIdx.x == 1) kr[1] = chunk_of(a.off, 0, a.n - 1, min(j0 + 255, n_samples - 1));
     __syncthreads();
-    if (j >= a.n_samples) return;
+    if (j >= n_samples) return;
     const uint32_t k = chunk_of(a.off, kr[0], kr[1], j);
     const uint64_t b = a.off[k];
     const uint32_t len = (uint32_t)(a.off[k + 1] - b), i = (uint32_t)(j - b);
@@ -292,6 +303,95 @@ __global__ __launch_bounds__(64) void k_ev_events(EvArgs a, uint64_t bound, floa
     for (uint32_t p = lane; p < nev; p += kW) dst[p] = (float)(((double)ev[p] - mean) / sd);
 }
 
+// ---- raw int16 samples in: ri_read_sig's conversion and filter (src/rsig.cpp:216-224) ----
+
+struct RawArgs {
+    const uint64_t *roff;         // n + 1 raw offsets, rebased to the uploaded samples (roff[0] = 0)
+    const int16_t *raw;           // 16-byte aligned, readable up to the next multiple of 8 samples past roff[n]
+    const rawdtw_channel_t *chan; // one a window
+    uint32_t *cnt;                // per window: the kept samples (s_len)
+    uint32_t *h_cnt;              // the caller's page-locked s_len, or null
+    const uint64_t *off;          // n + 1 sample offsets of the kept samples (k_ev_scan over cnt)
+    float *sig;                   // the kept pA samples, dense
+};
+
+// the 8 samples of the aligned group g (raw[8g .. 8g + 8)) to pA; bit j of the result: sample 8g + j lies in [s, e) and is kept.
+// The three operations of rsig.cpp:216-224 and no other: the scale's division is the caller's.
+__device__ __forceinline__ uint32_t convert8(const uint4 v, uint64_t g, uint64_t s, uint64_t e, float offset, float scale, float *pa)
+{
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint32_t keep = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const int16_t r = (int16_t)(w[j >> 1] >> (16 * (j & 1)));
+        const float x = __fmul_rn(__fadd_rn((float)r, offset), scale);
+        const uint64_t i = g * 8 + j;
+        pa[j] = x;
+        if (i >= s && i < e && x > 30.0f && x < 200.0f) keep |= 1u << j;
+    }
+    return keep;
+}
+
+// group g of a window that ends at e; a lane whose group lies past the end loads nothing
+__device__ __forceinline__ uint4 load8(const int16_t *raw, uint64_t g, uint64_t e)
+{
+    return g * 8 < e ? *reinterpret_cast<const uint4 *>(raw + g * 8) : make_uint4(0, 0, 0, 0);
+}
+
+__global__ __launch_bounds__(64) void k_raw_count(RawArgs a)
+{
+    const uint32_t k = blockIdx.x, lane = threadIdx.x;
+    const uint64_t s = a.roff[k], e = a.roff[k + 1];
+    const rawdtw_channel_t ch = a.chan[k];
+    const float scale = __fdiv_rn(ch.range, ch.digitisation);
+    uint32_t c = 0;
+    for (uint64_t g = s / 8 + lane; g * 8 < e; g += kW) {
+        float pa[8];
+        c += (uint32_t)__popc(convert8(load8(a.raw, g, e), g, s, e, ch.offset, scale, pa));
+    }
+    for (int o = 32; o; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o);
+    if (lane == 0) {
+        a.cnt[k] = c;
+        if (a.h_cnt) a.h_cnt[k] = c;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_raw_compact(RawArgs a)
+{
+    __shared__ float out[kW * 8];
+    const uint32_t k = blockIdx.x, lane = threadIdx.x;
+    const uint64_t s = a.roff[k], e = a.roff[k + 1], b = a.off[k];
+    const uint32_t len = (uint32_t)(a.off[k + 1] - b); // what k_raw_count counted: nothing is written past it
+    const rawdtw_channel_t ch = a.chan[k];
+    const float scale = __fdiv_rn(ch.range, ch.digitisation);
+    float *dst = a.sig + b;
+    uint32_t run = 0;
+    uint4 cur = load8(a.raw, s / 8 + lane, e);
+    for (uint64_t g0 = s / 8; g0 * 8 < e; g0 += kW) { // (the same trip count in every lane)
+        const uint64_t g = g0 + lane;
+        const uint4 nxt = load8(a.raw, g + kW, e); // the next piece is on its way while this one is ranked
+        float pa[8];
+        const uint32_t keep = g * 8 < e ? convert8(cur, g, s, e, ch.offset, scale, pa) : 0u;
+        const uint32_t c = (uint32_t)__popc(keep);
+        uint32_t incl = c; // kept samples of lanes 0 .. lane
+#pragma unroll
+        for (int o = 1; o < (int)kW; o <<= 1) {
+            const uint32_t t = (uint32_t)__shfl_up((int)incl, o);
+            if (lane >= (uint32_t)o) incl += t;
+        }
+        const uint32_t tot = (uint32_t)__shfl((int)incl, kW - 1);
+        uint32_t p = incl - c;
+#pragma unroll
+        for (int j = 0; j < 8; j++)
+            if (keep >> j & 1) out[p++] = pa[j];
+        __syncthreads();
+        for (uint32_t i = lane; i < tot && run + i < len; i += kW) dst[run + i] = out[i];
+        __syncthreads();
+        run += tot;
+        cur = nxt;
+    }
+}
+
 struct DetectWs {
     void *dev = nullptr;
     size_t dev_bytes = 0;
@@ -306,6 +406,18 @@ struct DetectWs {
     float *h_ev = nullptr;
     const uint64_t *d_eoff = nullptr;
     const float *d_ev = nullptr;
+    // the raw entry: s_len
+    bool direct_slen = false;
+    uint32_t *h_slen = nullptr;
+    const uint32_t *d_slen = nullptr;
+};
+
+// what a detection reads: pA chunks (sig), or raw windows with a channel each
+struct Input {
+    const float *sig = nullptr;
+    const int16_t *raw = nullptr;
+    const rawdtw_channel_t *chan = nullptr;
+    uint32_t *s_len = nullptr;
 };
 
 // the device address of a page-locked host array of `bytes` bytes, or null (pageable memory, or an allocation that does not
@@ -335,26 +447,26 @@ using namespace rawdtw::capi;
 
 struct rawdtw_detect_ws { DetectWs w; };
 
-extern "C" {
+namespace {
 
-int rawdtw_detect_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint32_t n_chunks, const uint64_t *sig_off, const float *sig,
-                        uint64_t *event_off, float *events, uint64_t events_cap)
+// everything after the entry's own checks: the workspace, the upload and the launches.  off: the caller's n + 1 offsets (of
+// samples, or of raw samples), N = off[n] - off[0].
+int detect_enqueue(rawdtw_ctx *ctx, const rawdtw_event_opt_t &o, uint32_t n_chunks, const uint64_t *off, const Input &in,
+                   uint64_t *event_off, float *events, uint64_t events_cap)
 {
-    if (!ctx) return RAWDTW_ERR_INVALID;
-    if (!sig_off || !event_off || (n_chunks && (!sig || !events))) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
-    if (ctx->detect_ws && ctx->detect_ws->w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "a detection is begun on this context and not ended");
-    rawdtw_event_opt_t o;
-    if (events::resolve_opt(opt, &o) != RAWDTW_OK) return fail(ctx, RAWDTW_ERR_INVALID, "a window length above 65535");
-    if (events::check_offsets(n_chunks, sig_off) != RAWDTW_OK)
-        return fail(ctx, RAWDTW_ERR_INVALID, "an empty chunk (revent.c:24 asserts), a chunk of 2^32 samples or more, or offsets that descend");
     if (n_chunks >= 0x7fffffffu) return fail(ctx, RAWDTW_ERR_INVALID, "2^31 chunks or more");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint64_t n = n_chunks, N = sig_off[n] - sig_off[0];
+    const bool is_raw = in.raw != nullptr;
+    const uint64_t n = n_chunks, N = off[n] - off[0];
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t b_off = al((n + 1) * 8), b_sig = al(N * 4), b_ps = al((N + n) * 4), b_t = al(N * 4), b_cnt = al(n * 4), b_eoff = al((n + 1) * 8),
                  b_tot = al(32);
-    // sig, ps, pss, t1, t2, peaks, events: 28 bytes a sample
-    const size_t need = b_off + b_sig + 2 * b_ps + 2 * b_t + b_t + 2 * b_cnt + b_eoff + b_tot + b_t;
+    // the raw entry's own: the samples as they came (8 more, which the last window's last load may touch), the raw offsets,
+    // the channels, s_len
+    const size_t b_raw = is_raw ? al(N * 2 + 16) : 0, b_roff = is_raw ? b_off : 0, b_chan = is_raw ? al(n * sizeof(rawdtw_channel_t)) : 0,
+                 b_slen = is_raw ? b_cnt : 0;
+    // sig, ps, pss, t1, t2, peaks, events: 28 bytes a sample (30 a raw sample)
+    const size_t need = b_off + b_sig + 2 * b_ps + 2 * b_t + b_t + 2 * b_cnt + b_eoff + b_tot + b_t + b_raw + b_roff + b_chan + b_slen;
     if (!ctx->detect_ws) ctx->detect_ws = new (std::nothrow) rawdtw_detect_ws;
     if (!ctx->detect_ws) return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed");
     DetectWs &w = ctx->detect_ws->w;
@@ -380,8 +492,9 @@ int rawdtw_detect_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint32_t
     if (!w.ev1) HIP_TRY(ctx, hipEventCreate(&w.ev1));
     if (!w.done) HIP_TRY(ctx, hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
     w.pending = true; w.n = n_chunks; w.n_samples = N; w.cap = events_cap;
-    w.h_eoff = event_off; w.h_ev = events;
-    if (n == 0) { w.direct_off = w.direct_ev = false; return RAWDTW_OK; }
+    w.h_eoff = event_off; w.h_ev = events; w.h_slen = in.s_len;
+    w.direct_off = w.direct_ev = w.direct_slen = false;
+    if (n == 0 || N == 0) return RAWDTW_OK; // (N == 0: every raw window is empty; rawdtw_detect_end fills the zeros)
     char *p = static_cast<char *>(w.dev);
     EvArgs a{};
     uint64_t *d_off = reinterpret_cast<uint64_t *>(p); p += b_off;
@@ -395,21 +508,39 @@ int rawdtw_detect_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint32_t
     a.nev = reinterpret_cast<uint32_t *>(p); p += b_cnt;
     a.eoff = reinterpret_cast<uint64_t *>(p); p += b_eoff;
     a.tot = reinterpret_cast<uint64_t *>(p); p += b_tot;
-    a.ev = reinterpret_cast<float *>(p);
+    a.ev = reinterpret_cast<float *>(p); p += b_t;
+    RawArgs r{};
+    int16_t *d_raw = reinterpret_cast<int16_t *>(p); p += b_raw;
+    uint64_t *d_roff = reinterpret_cast<uint64_t *>(p); p += b_roff;
+    rawdtw_channel_t *d_chan = reinterpret_cast<rawdtw_channel_t *>(p); p += b_chan;
+    r.cnt = reinterpret_cast<uint32_t *>(p);
     a.off = d_off; a.sig = d_sig; a.n = n_chunks; a.n_samples = N; a.opt = o;
+    a.n_dev = is_raw ? a.tot + 1 : nullptr;
     uint64_t *h_off = w.pin + 1;
-    for (uint64_t k = 0; k <= n; k++) h_off[k] = sig_off[k] - sig_off[0];
+    for (uint64_t k = 0; k <= n; k++) h_off[k] = off[k] - off[0];
     uint64_t *dv_eoff = static_cast<uint64_t *>(device_view(event_off, (n + 1) * 8));
     float *dv_ev = static_cast<float *>(device_view(events, events_cap * 4));
     w.direct_off = dv_eoff != nullptr; w.direct_ev = dv_ev != nullptr;
     w.d_eoff = a.eoff; w.d_ev = a.ev;
     hipStream_t s = ctx->stream;
     auto undo = [&](int st) { w.pending = false; return st; };
-    if (hipMemcpyAsync(d_off, h_off, (n + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(d_sig, sig + sig_off[0], N * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipEventRecord(w.ev0, s) != hipSuccess)
-        return undo(hip_fail(ctx, hipGetLastError(), "detection upload"));
     const uint32_t waves = (uint32_t)((n + kW - 1) / kW);
+    if (is_raw) {
+        r.roff = d_roff; r.raw = d_raw; r.chan = d_chan; r.off = d_off; r.sig = d_sig;
+        r.h_cnt = static_cast<uint32_t *>(device_view(in.s_len, n * 4));
+        w.direct_slen = r.h_cnt != nullptr; w.d_slen = r.cnt;
+        if (hipMemcpyAsync(d_roff, h_off, (n + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(d_chan, in.chan, n * sizeof(rawdtw_channel_t), hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(d_raw, in.raw + off[0], N * 2, hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipEventRecord(w.ev0, s) != hipSuccess)
+            return undo(hip_fail(ctx, hipGetLastError(), "detection upload"));
+        hipLaunchKernelGGL(k_raw_count, dim3(n_chunks), dim3(kW), 0, s, r);
+        hipLaunchKernelGGL(k_ev_scan, dim3(1), dim3(1024), 0, s, r.cnt, n_chunks, d_off, a.tot + 1, (uint64_t *)nullptr);
+        hipLaunchKernelGGL(k_raw_compact, dim3(n_chunks), dim3(kW), 0, s, r);
+    } else if (hipMemcpyAsync(d_off, h_off, (n + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+               hipMemcpyAsync(d_sig, in.sig + off[0], N * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
+               hipEventRecord(w.ev0, s) != hipSuccess)
+        return undo(hip_fail(ctx, hipGetLastError(), "detection upload"));
     hipLaunchKernelGGL(k_ev_prefix, dim3(waves), dim3(kW), 0, s, a);
     hipLaunchKernelGGL(k_ev_tstat, dim3((uint32_t)((N + 255) / 256)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_ev_peaks, dim3(waves), dim3(kW), 0, s, a);
@@ -423,6 +554,40 @@ int rawdtw_detect_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint32_t
     return RAWDTW_OK;
 }
 
+} // namespace
+
+extern "C" {
+
+int rawdtw_detect_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint32_t n_chunks, const uint64_t *sig_off, const float *sig,
+                        uint64_t *event_off, float *events, uint64_t events_cap)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (!sig_off || !event_off || (n_chunks && (!sig || !events))) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    if (ctx->detect_ws && ctx->detect_ws->w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "a detection is begun on this context and not ended");
+    rawdtw_event_opt_t o;
+    if (events::resolve_opt(opt, &o) != RAWDTW_OK) return fail(ctx, RAWDTW_ERR_INVALID, "a window length above 65535");
+    if (events::check_offsets(n_chunks, sig_off) != RAWDTW_OK)
+        return fail(ctx, RAWDTW_ERR_INVALID, "an empty chunk (revent.c:24 asserts), a chunk of 2^32 samples or more, or offsets that descend");
+    Input in;
+    in.sig = sig;
+    return detect_enqueue(ctx, o, n_chunks, sig_off, in, event_off, events, events_cap);
+}
+
+int rawdtw_detect_raw_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint32_t n_chunks, const uint64_t *raw_off, const int16_t *raw,
+                            const rawdtw_channel_t *chan, uint32_t *s_len, uint64_t *event_off, float *events, uint64_t events_cap)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (!raw_off || !event_off || (n_chunks && (!raw || !chan || !s_len || !events))) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    if (ctx->detect_ws && ctx->detect_ws->w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "a detection is begun on this context and not ended");
+    rawdtw_event_opt_t o;
+    if (events::resolve_opt(opt, &o) != RAWDTW_OK) return fail(ctx, RAWDTW_ERR_INVALID, "a window length above 65535");
+    if (events::check_raw_offsets(n_chunks, raw_off) != RAWDTW_OK)
+        return fail(ctx, RAWDTW_ERR_INVALID, "a window of 2^32 raw samples or more, or offsets that descend");
+    Input in;
+    in.raw = raw; in.chan = chan; in.s_len = s_len;
+    return detect_enqueue(ctx, o, n_chunks, raw_off, in, event_off, events, events_cap);
+}
+
 int rawdtw_detect_end(rawdtw_ctx *ctx, float *kernel_ms)
 {
     if (!ctx) return RAWDTW_ERR_INVALID;
@@ -430,13 +595,21 @@ int rawdtw_detect_end(rawdtw_ctx *ctx, float *kernel_ms)
     DetectWs &w = ctx->detect_ws->w;
     w.pending = false;
     if (kernel_ms) *kernel_ms = 0.0f;
-    if (w.n == 0) { w.h_eoff[0] = 0; return RAWDTW_OK; }
+    if (w.n == 0 || w.n_samples == 0) { // nothing was enqueued
+        for (uint64_t k = 0; k <= w.n; k++) w.h_eoff[k] = 0;
+        for (uint64_t k = 0; w.h_slen && k < w.n; k++) w.h_slen[k] = 0;
+        return RAWDTW_OK;
+    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     HIP_TRY(ctx, hipEventSynchronize(w.done)); // (the detection's own work: what the caller enqueued behind it goes on)
     const uint64_t tot = w.pin[0];
     if (!w.direct_off) {
         HIP_TRY(ctx, hipMemcpyAsync(w.h_eoff, w.d_eoff, ((uint64_t)w.n + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+    }
+    if (w.h_slen && !w.direct_slen) {
+        HIP_TRY(ctx, hipMemcpyAsync(w.h_slen, w.d_slen, (uint64_t)w.n * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(ctx, hipStreamSynchronize(s));
     }
     if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, w.ev0, w.ev1));

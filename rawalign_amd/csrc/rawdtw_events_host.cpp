@@ -1,5 +1,7 @@
 // rawdtw_events_host.cpp -- detect_events (src/revent.c:190-210) restated on the host, one chunk or many on std::threads: the
 // CPU baseline of event detection and the comparator of the device path (rawdtw_events.hip).  Pure host code, no device.
+// rawdtw_detect_raw_host takes windows of int16 DAC samples instead: each is converted and filtered (rawdtw_rawsig.cpp) and then
+// goes the same way.
 //
 // Every line below keeps the reference's order and types (include/rawdtw.h lists what the bits depend on); the library is
 // built with -ffp-contract=off, so the plain form has one rounding per operation, and the contracted form names its
@@ -123,7 +125,7 @@ uint32_t gen_events(const uint32_t *peaks, uint32_t n_peaks, const float *ps, ui
 
 // scratch of one chunk, reused across a thread's chunks
 struct Scratch {
-    std::vector<float> ps, pss, t1, t2;
+    std::vector<float> ps, pss, t1, t2, pa; // (pa: the raw entry's converted window)
     std::vector<uint32_t> peaks;
     void fit(uint32_t n)
     {
@@ -145,6 +147,45 @@ uint32_t detect_one(const rawdtw_event_opt_t &o, uint32_t n, const float *sig, f
     Detector ld{s.t2.data(), o.threshold2, o.window_length2, 0, -1, FLT_MAX, 0};
     const uint32_t n_peaks = gen_peaks(sd, ld, o.peak_height, n, s.peaks.data());
     return n_peaks ? gen_events(s.peaks.data(), n_peaks, s.ps.data(), n, fused, ev) : 0; // revent.c:206
+}
+
+// many chunks on `threads` threads: one(k, ev, scratch) writes chunk k's events at ev and returns how many.  Each chunk's events
+// land in a staging array at the chunk's own offset (never more events than samples), then move to their place once every
+// count is known.
+template <class One>
+int detect_many(uint32_t n_chunks, const uint64_t *off, uint64_t *event_off, float *events, uint64_t events_cap, int threads, One one)
+{
+    std::vector<float> stage;
+    std::vector<uint32_t> count;
+    try {
+        stage.resize(off[n_chunks] - off[0]);
+        count.resize(n_chunks);
+    } catch (const std::bad_alloc &) {
+        return RAWDTW_ERR_OOM;
+    }
+    const int T = std::max(1, std::min(threads, 256));
+    std::atomic<uint32_t> next{0};
+    std::atomic<int> oom{0};
+    auto work = [&]() {
+        try {
+            Scratch s;
+            for (uint32_t k; (k = next.fetch_add(1)) < n_chunks;) count[k] = one(k, stage.data() + (off[k] - off[0]), s);
+        } catch (const std::bad_alloc &) {
+            oom = 1;
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < T; t++) th.emplace_back(work);
+    work();
+    for (auto &x : th) x.join();
+    if (oom) return RAWDTW_ERR_OOM;
+    uint64_t tot = 0;
+    for (uint32_t k = 0; k < n_chunks; k++) { event_off[k] = tot; tot += count[k]; }
+    event_off[n_chunks] = tot;
+    if (tot > events_cap) return RAWDTW_ERR_RANGE;
+    for (uint32_t k = 0; k < n_chunks; k++)
+        if (count[k]) std::memcpy(events + event_off[k], stage.data() + (off[k] - off[0]), (size_t)count[k] * sizeof(float));
+    return RAWDTW_OK;
 }
 
 } // namespace
@@ -190,42 +231,26 @@ int rawdtw_detect_events_host(const rawdtw_event_opt_t *opt, uint32_t n_chunks, 
     if (!sig_off || !event_off || (n_chunks && (!sig || !events))) return RAWDTW_ERR_INVALID;
     if (rawdtw::events::resolve_opt(opt, &o) != RAWDTW_OK || rawdtw::events::check_offsets(n_chunks, sig_off) != RAWDTW_OK)
         return RAWDTW_ERR_INVALID;
-    // each chunk's events land in a staging array at the chunk's own sample offset (never more events than samples), then move
-    // to their place once every count is known
-    std::vector<float> stage;
-    std::vector<uint32_t> count;
-    try {
-        stage.resize(sig_off[n_chunks] - sig_off[0]);
-        count.resize(n_chunks);
-    } catch (const std::bad_alloc &) {
-        return RAWDTW_ERR_OOM;
-    }
-    const int T = std::max(1, std::min(threads, 256));
-    std::atomic<uint32_t> next{0};
-    std::atomic<int> oom{0};
-    auto work = [&]() {
-        try {
-            Scratch s;
-            for (uint32_t k; (k = next.fetch_add(1)) < n_chunks;) {
-                const uint64_t b = sig_off[k];
-                count[k] = detect_one(o, (uint32_t)(sig_off[k + 1] - b), sig + b, stage.data() + (b - sig_off[0]), s);
-            }
-        } catch (const std::bad_alloc &) {
-            oom = 1;
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < T; t++) th.emplace_back(work);
-    work();
-    for (auto &x : th) x.join();
-    if (oom) return RAWDTW_ERR_OOM;
-    uint64_t tot = 0;
-    for (uint32_t k = 0; k < n_chunks; k++) { event_off[k] = tot; tot += count[k]; }
-    event_off[n_chunks] = tot;
-    if (tot > events_cap) return RAWDTW_ERR_RANGE;
-    for (uint32_t k = 0; k < n_chunks; k++)
-        if (count[k]) std::memcpy(events + event_off[k], stage.data() + (sig_off[k] - sig_off[0]), (size_t)count[k] * sizeof(float));
-    return RAWDTW_OK;
+    return detect_many(n_chunks, sig_off, event_off, events, events_cap, threads, [&](uint32_t k, float *ev, Scratch &s) {
+        return detect_one(o, (uint32_t)(sig_off[k + 1] - sig_off[k]), sig + sig_off[k], ev, s);
+    });
+}
+
+int rawdtw_detect_raw_host(const rawdtw_event_opt_t *opt, uint32_t n_chunks, const uint64_t *raw_off, const int16_t *raw,
+                           const rawdtw_channel_t *chan, uint32_t *s_len, uint64_t *event_off, float *events, uint64_t events_cap,
+                           int threads)
+{
+    rawdtw_event_opt_t o;
+    if (!raw_off || !event_off || (n_chunks && (!raw || !chan || !s_len || !events))) return RAWDTW_ERR_INVALID;
+    if (rawdtw::events::resolve_opt(opt, &o) != RAWDTW_OK || rawdtw::events::check_raw_offsets(n_chunks, raw_off) != RAWDTW_OK)
+        return RAWDTW_ERR_INVALID;
+    return detect_many(n_chunks, raw_off, event_off, events, events_cap, threads, [&](uint32_t k, float *ev, Scratch &s) {
+        const uint64_t n = raw_off[k + 1] - raw_off[k];
+        if (s.pa.size() < n) s.pa.resize(n);
+        const uint32_t l = (uint32_t)rawdtw::events::to_pa(chan[k], n, raw + raw_off[k], s.pa.data()); // rsig.cpp:216-224
+        s_len[k] = l;
+        return l ? detect_one(o, l, s.pa.data(), ev, s) : 0u; // nothing kept: no events
+    });
 }
 
 } // extern "C"

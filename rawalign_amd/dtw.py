@@ -227,6 +227,44 @@ class Engine:
         out = (eoff[:n + 1].copy(), ev[:int(eoff[n])].copy())
         return out + (float(ms.value),) if kernel_ms else out
 
+    def detect_events_raw(self, raw, raw_off, chan, opt=None, pinned: bool = True, events_cap=None, kernel_ms: bool = False):
+        """Every window k = raw[raw_off[k] .. raw_off[k+1]) of int16 DAC samples with channel chan[k] on the device:
+        rawdtw_detect_raw_begin (pA conversion and outlier filter of src/rsig.cpp:216-224, then the detection), then _end.
+        Staging as detect_events keeps it.  Returns (s_len, event_off, events), and the launches' device time in ms too when
+        kernel_ms."""
+        from .events import PinnedArray, _opt
+        from .rawsig import CHANNEL_DTYPE, channels
+
+        raw = np.asarray(raw, np.int16)
+        off = np.ascontiguousarray(raw_off, np.uint64)
+        n = len(off) - 1
+        ch = channels(chan, n)
+        cap = int(off[-1] - off[0]) if events_cap is None else int(events_cap)
+        if pinned:
+            st = getattr(self, "_raw_stage", None)
+            if st is None or st["raw"].array.size < len(raw) or st["off"].array.size < n + 1 or st["ev"].array.size < cap:
+                st = self._raw_stage = {"raw": PinnedArray(len(raw), np.int16), "off": PinnedArray(n + 1, np.uint64),
+                                        "chan": PinnedArray(n, CHANNEL_DTYPE), "slen": PinnedArray(n, np.uint32),
+                                        "eoff": PinnedArray(n + 1, np.uint64), "ev": PinnedArray(cap, np.float32)}
+            h_raw, h_off, h_ch = st["raw"].array, st["off"].array, st["chan"].array
+            s_len, eoff, ev = st["slen"].array, st["eoff"].array, st["ev"].array
+            h_raw[:len(raw)] = raw
+            h_off[:n + 1] = off
+            h_ch[:n] = ch
+        else:
+            h_raw, h_off, h_ch = np.ascontiguousarray(raw), off, ch
+            s_len, eoff, ev = np.zeros(max(n, 1), np.uint32), np.zeros(n + 1, np.uint64), np.empty(max(cap, 1), np.float32)
+        ms = C.c_float()
+        self._check(self.lib.rawdtw_detect_raw_begin(self._ctx, _opt(opt), n, h_off.ctypes.data, h_raw.ctypes.data, h_ch.ctypes.data,
+                                                     s_len.ctypes.data, eoff.ctypes.data, ev.ctypes.data, cap))
+        st = self.lib.rawdtw_detect_end(self._ctx, C.byref(ms))
+        if st != 0:
+            err = RawDTWError(st, self.lib.rawdtw_last_error(self._ctx).decode())
+            err.event_off, err.s_len = eoff[:n + 1].copy(), s_len[:n].copy()
+            raise err
+        out = (s_len[:n].copy(), eoff[:n + 1].copy(), ev[:int(eoff[n])].copy())
+        return out + (float(ms.value),) if kernel_ms else out
+
     # -- batches ----------------------------------------------------------------
     def plan(self, jobs) -> Plan:
         jobs = np.ascontiguousarray(jobs, dtype=JOB_DTYPE)

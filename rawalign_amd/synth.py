@@ -377,3 +377,33 @@ def make_raw_reads(n_reads: int, n_samples=4000, seed: int = 0, sample_rate: int
         scale, offset = rng.uniform(0.85, 1.15), rng.uniform(-8.0, 8.0)
         reads.append((levels[:L].astype(np.float64) * scale + offset + rng.normal(0.0, noise_pA, L)).astype(np.float32))
     return reads
+
+
+def make_dac_reads(n_reads: int, n_samples=4000, seed: int = 0, outlier_rate: float = 0.0, **raw_kw):
+    """make_raw_reads as a signal file holds them: int16 DAC samples and a channel record a read (digitisation 8192, range
+    1 400-1 500, an integer offset of a few units either side of zero), the input of ri_read_sig's conversion and filter
+    (src/rsig.cpp:216-224: pA = (raw + offset) * range / digitisation, kept iff 30 < pA < 200).  Every sample converts to a kept
+    pA value, except a share of outlier_rate planted at random places: values that land at or below 30 pA and at or above 200 pA
+    (half each).  Returns (list of int16 arrays, array of (digitisation, range, offset) float32 records, one a read)."""
+    from .rawsig import CHANNEL_DTYPE
+
+    reads = make_raw_reads(n_reads, n_samples, seed=seed, **raw_kw)
+    rng = np.random.default_rng([seed, 0xDAC])
+    chan = np.zeros(n_reads, CHANNEL_DTYPE)
+    chan["digitisation"] = 8192.0
+    chan["range"] = rng.uniform(1400.0, 1500.0, n_reads)
+    chan["offset"] = rng.integers(-12, 13, n_reads)
+    all_raw = np.arange(-32768, 32768, dtype=np.int64)
+    out = []
+    for pa, ch in zip(reads, chan):
+        scale = ch["range"] / ch["digitisation"]  # float32, as the conversion's
+        conv = (all_raw.astype(np.float32) + ch["offset"]) * scale
+        ok = all_raw[(conv > np.float32(30)) & (conv < np.float32(200))]
+        lo, hi = int(ok[0]), int(ok[-1])  # the kept DAC values: contiguous, the scale is positive
+        raw = np.clip(np.rint(pa.astype(np.float64) / float(scale) - float(ch["offset"])), lo, hi).astype(np.int16)
+        bad = np.nonzero(rng.random(len(raw)) < outlier_rate)[0]
+        low = rng.random(len(bad)) < 0.5
+        depth = rng.integers(0, 400, len(bad))
+        raw[bad] = np.where(low, lo - 1 - depth, hi + 1 + depth).astype(np.int16)
+        out.append(raw)
+    return out, chan
