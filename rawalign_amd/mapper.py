@@ -383,7 +383,8 @@ def _vp(a):
     return C.c_void_p(a.ctypes.data)
 
 
-def map_reads(seeds, read_ids, scorer, opt: MapOpt, stop: M.StopOpt = M.StopOpt(), e: int = 6, log=None, output_chains: bool = False):
+def map_reads(seeds, read_ids, scorer, opt: MapOpt, stop: M.StopOpt = M.StopOpt(), e: int = 6, log=None, output_chains: bool = False,
+              chain_opt=None, on_round=None):
     """Runs chunk rounds until every read stopped; returns the PAF lines in read order.
 
     Flags (src/roptions.h:13-15): DTW runs when RI_M_DTW_EVALUATE_CHAINS or RI_M_DTW_LOG_SCORES is set
@@ -392,8 +393,10 @@ def map_reads(seeds, read_ids, scorer, opt: MapOpt, stop: M.StopOpt = M.StopOpt(
     sort of gen_primary_chains then sees first, rmap.h:41-45).  With RI_M_DTW_OUTPUT_CIGAR the best chain of
     a mapped read is aligned once more with traceback (rmap.cpp:715-717).  `log`, when given, receives the
     lines --dtw-log-scores writes to stderr (rmap.cpp:308-312), in order.  `output_chains`: --output-chains
-    (RI_M_OUTPUT_CHAINS, the anchors:s: tag of rmap.cpp:745-747)."""
-    copt = M.default_chain_opt(e)
+    (RI_M_OUTPUT_CHAINS, the anchors:s: tag of rmap.cpp:745-747).  `chain_opt`: the chaining options (a ChainOpt; None: the
+    defaults of roptions.c:13-19 with `e`).  `on_round(round, {read id: primary chains})`, when given, is called at the end of
+    every round with the chains of the reads that were in it (reg->chains as the round leaves them)."""
+    copt = chain_opt if chain_opt is not None else M.default_chain_opt(e)
     jobs = {r: seeds.read_job(r) for r in read_ids}
     names = [f"seq{s}" for s in range(len(seeds.lens))]
     rounds = 0
@@ -453,6 +456,8 @@ def map_reads(seeds, read_ids, scorer, opt: MapOpt, stop: M.StopOpt = M.StopOpt(
                 rj.finished, rj.broke_early = True, True
             elif rj.chunks_done >= min(rj.n_chunks_available, stop.max_num_chunk):
                 rj.finished = True
+        if on_round is not None:
+            on_round(rounds, {r: list(jobs[r].chains) for r in active})
     lines = []
     for r in read_ids:
         rj = jobs[r]
@@ -495,9 +500,10 @@ class CMapper:
 
     def __init__(self, engine, opt: MapOpt, stop: M.StopOpt, seq_names, seq_lens, slot_events: int, max_reads: int, carry: bool = True,
                  threads: int = 1, groups: int = 1, e: int = 6, device_chain: bool = False, output_chains: bool = False,
-                 sequence_until=None):
+                 sequence_until=None, chain_opt=None):
         """`output_chains`: --output-chains (flag 0x20).  `sequence_until`: --sequence-until (flag 0x1) -- True for the defaults of
-        roptions.c:43-46, or a dict of rawdtw_su_opt_t's fields (t_threshold, tn_samples, ttest_freq, tmin_reads, contracted)."""
+        roptions.c:43-46, or a dict of rawdtw_su_opt_t's fields (t_threshold, tn_samples, ttest_freq, tmin_reads, contracted).
+        `chain_opt`: the chaining options (a ChainOpt; None: the defaults of roptions.c:13-19 with `e`)."""
         import ctypes as C
 
         from ._lib import MapperOpt, load_library
@@ -507,7 +513,7 @@ class CMapper:
         mo = MapperOpt()
         mo.flag = opt.flag | (RI_M_OUTPUT_CHAINS if output_chains else 0) | (RI_M_SEQUENCEUNTIL if sequence_until else 0)
         mo.align = opt.c_struct()
-        mo.chain = M.default_chain_opt(e)
+        mo.chain = chain_opt if chain_opt is not None else M.default_chain_opt(e)
         mo.min_bestmap_ratio, mo.min_meanmap_ratio, mo.min_chain_anchor = stop.min_bestmap_ratio, stop.min_meanmap_ratio, stop.min_chain_anchor
         mo.bp_per_sec, mo.sample_rate, mo.chunk_size, mo.max_num_chunk = stop.bp_per_sec, stop.sample_rate, stop.chunk_size, stop.max_num_chunk
         mo.slot_events, mo.max_reads, mo.carry, mo.min_events = int(slot_events), int(max_reads), int(bool(carry)), int(stop.min_events)

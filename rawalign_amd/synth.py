@@ -407,3 +407,25 @@ def make_dac_reads(n_reads: int, n_samples=4000, seed: int = 0, outlier_rate: fl
         raw[bad] = np.where(low, lo - 1 - depth, hi + 1 + depth).astype(np.int16)
         out.append(raw)
     return out, chan
+
+
+def make_genome_raw_reads(genome, starts, n_kmers, strands, seed: int = 0, dwell=(6, 13), noise_pA: float = 1.2, k: int = 6) -> list:
+    """make_raw_reads on substrings of a genome instead of random sequences, so that the reads map: read r emits the k-mer
+    levels (make_pore_model, pA) of n_kmers[r] consecutive k-mers from position starts[r] of the strand's own sequence --
+    strand 1 the genome as given (the forward signal of make_reference, rmap.cpp:183-188), strand 0 its reverse complement --
+    each held for a dwell drawn uniformly from dwell[0]..dwell[1] samples, with Gaussian noise of noise_pA and a per-read
+    scale and offset.  `genome`: 0..3 codes (make_genome).  Returns float32 arrays."""
+    pore = make_pore_model(k)
+    rng = np.random.default_rng(seed)
+    genome = np.asarray(genome, np.uint8)
+    reads = []
+    for start, n, strand in zip(starts, n_kmers, strands):
+        seq = genome if strand else (3 - genome[::-1])
+        codes = seq[int(start):int(start) + int(n) + k - 1]
+        idx = np.zeros(int(n), np.int64)
+        for j in range(k):
+            idx = (idx << 2) | codes[j:j + int(n)].astype(np.int64)
+        levels = np.repeat(pore[idx], rng.integers(dwell[0], dwell[1] + 1, int(n)))
+        scale, offset = rng.uniform(0.85, 1.15), rng.uniform(-8.0, 8.0)
+        reads.append((levels.astype(np.float64) * scale + offset + rng.normal(0.0, noise_pA, len(levels))).astype(np.float32))
+    return reads

@@ -1,6 +1,6 @@
 """The anchor sort and the chaining DP on the device (rawdtw_chain_round, rawalign_amd/csrc/rawdtw_chain.hip) against the host
 restatement of rmap.cpp:396-401, 430-507, 130-173 and 512 (rawdtw_chain_anchors + rawdtw_sort_by_chaining_score, themselves checked against the
-oracle in tests/test_chaining.py): per read the same chains in the same order -- scores bit for bit, positions, every anchor -- and the batch
+reference's own compiled rmap.cpp in tests/test_map_ref.py, and the device against it in tests/test_map_ref_gpu.py): per read the same chains in the same order -- scores bit for bit, positions, every anchor -- and the batch
 arrays the DTW takes in device memory."""
 import ctypes as C
 

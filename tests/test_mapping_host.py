@@ -1,8 +1,9 @@
 """Host consumers downstream of the DTW block (pure host code): primary-chain selection + MAPQ,
 the stop rule, PAF formatting and sequence-until, against plain-Python restatements of the
 reference (rmap.cpp:65-128, 594-665, 696-801, 918-965; sequence_until.c:4-18).
-The reference's rmap.cpp cannot be built on its own (HDF5), so these are pinned by restatement only --
-except find_outlier, whose translation unit compiles on its own (its answers: tests/golden/find_outlier_ref.npz)."""
+These are restatement against restatement; the tie to the reference's own compiled rmap.cpp (which builds without HDF5 once the
+FAST5 header is skipped: oracle/Makefile, ref_map) is tests/test_map_ref.py with tests/golden/map_ref_*.npz.  find_outlier's
+translation unit compiles on its own (its answers: tests/golden/find_outlier_ref.npz)."""
 import ctypes as C
 import os
 
@@ -171,8 +172,9 @@ def test_sequence_until_state_machine():
 
 
 def py_chain(anchors, e=6, max_gap=2000, max_tgap=5000, band=5000, max_skips=25, min_anchors=2, nbest=3,
-             min_score=10.0, maxs=0.0):
-    """Plain-Python restatement of the chaining DP + traceback (rmap.cpp:430-507, 130-173), fp32 scores."""
+             min_score=10.0, maxs=0.0, dp_out=None):
+    """Plain-Python restatement of the chaining DP + traceback (rmap.cpp:430-507, 130-173), fp32 scores.  `dp_out`, a list, receives
+    every anchor's DP value."""
     n = len(anchors)
     score = [f32(e)] * n
     pred = list(range(n))
@@ -208,6 +210,8 @@ def py_chain(anchors, e=6, max_gap=2000, max_tgap=5000, band=5000, max_skips=25,
         if score[ai] >= f32(min_score) and score[ai] > f32(maxs / f32(2)):
             ends.append((score[ai], ai))
     ends.sort(key=lambda x: (-float(x[0]), -x[1]))
+    if dp_out is not None:
+        dp_out.extend(score)
     chains = []
     for k, (_, end) in enumerate(ends[:nbest]):
         if not used[end]:
