@@ -643,7 +643,8 @@ int rawdtw_detect_raw_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint
  * submission for all active reads, and the PAF line of a read (src/rmap.cpp:696-801, 950-965).  The caller keeps reading the
  * signal file (the int16 samples and the channel's three numbers: rsig.cpp up to line 215), the calls of event detection
  * (rawdtw_detect_raw_begin on the raw samples, which takes ri_read_sig's pA conversion and outlier filter, rsig.cpp:216-224,
- * with it; rawdtw_signal_chunk_table gives the read's qlen and its chunks' places) and seeding (rsketch.c, rawindex.cpp), and
+ * with it; rawdtw_signal_chunk_table gives the read's qlen and its chunks' places) and seeding (rsketch.c, rawindex.cpp:
+ * rawdtw_seed_begin, or rawdtw_mapper_round_seeded, which seeds the round itself), and
  * hands in, per round and active read, the chunk's events and seed hits; the mapper appends the events to the read's slot in the event arena (rmap.cpp:554-567), re-seeds with the
  * previous chains' anchors (344-357), chains (396-507), orders the chains (512), scores them all in one batch on the
  * device (509-530; with `carry` the unchanged parts' costs are taken over from the round before), and finishes the round:
@@ -749,6 +750,75 @@ typedef int (*rawdtw_scorer_fn)(void *user, uint64_t n_reads, const uint64_t *ch
 int rawdtw_mapper_set_scorer(rawdtw_mapper *m, rawdtw_scorer_fn fn, void *user);
 const char *rawdtw_mapper_last_error(const rawdtw_mapper *m);
 int rawdtw_mapper_destroy(rawdtw_mapper *m);
+
+/* ---- seeding: a chunk's events to seed hits -- ri_sketch (src/rsketch.c:276-284) followed by ri_idx_get
+ * (src/rawindex.cpp:256-273), as gen_chains calls them (src/rmap.cpp:364-391) -- bit for bit and in the reference's order.
+ *   sketch, w == 0  rsketch.c:223-274  event i is skipped when i > 0 && fabs(ev[i] - ev[last kept]) < 0.3F (an fp32 subtraction,
+ *                                      an ordered compare: a NaN is kept, and so is the event after it) or ev[i] ==
+ *                                      RI_MASK_SIGNAL; a kept event's code is its sign and top exponent bit followed by lq
+ *                                      bits from bit 32 - q down; the last e codes, (lq + 2) bits each, are hashed with hash64
+ *                                      under the 32-bit mask (rsketch.c:6-15); from the e-th kept event on, every kept event
+ *                                      emits (hash, i), i = the position of the LAST event of the e-mer
+ *   sketch, w > 0   rsketch.c:146-221  the minimizer sketch: no RI_MASK_SIGNAL test, the position is the e-mer's first event,
+ *                                      and of each window of w e-mers the smallest hash is emitted.  Host only.
+ *   lookup          rmap.cpp:371-391   per sketch element in order, per position y of its hash in the index's order:
+ *                                      ref_seq = y >> 32, strand = y & 1, target_position = (y >> 1) & 0x7fffffff,
+ *                                      query_position = i (inside the chunk; the mapper adds the chunk's start)
+ * There is no occurrence cap (rmap.cpp:368 is commented out).  Refused with RAWDTW_ERR_INVALID: e outside 2..9 (rsketch.c:278
+ * asserts), w >= 256 (rsketch.c:154), q == 0 or q > 32, lq > 30 and (lq + 2) * e >= 64 (the reference's shifts are undefined
+ * there).  A chunk with fewer than e kept events, an empty one included, has no hits. ---- */
+typedef struct {
+    uint32_t w, e, n, q, lq, k; /* ri_idx_t's, the order of the .ind header (rawindex.cpp:279) */
+} rawdtw_seed_pars_t;
+typedef struct rawdtw_seed_index rawdtw_seed_index;
+/* the index of ri_idx_add / ri_idx_sort (rawindex.cpp:91-97, 194-246) from signal arrays: both strands of every sequence are
+ * sketched, forward with strand bit 1 and reverse with strand bit 0 (rawindex.cpp:141-147); a hash's positions
+ * id << 32 | pos << 1 | strand are kept in ascending order (radix_sort_64, rawindex.cpp:233).  `threads` sketches sequences in
+ * parallel; the result never depends on it. */
+int rawdtw_seed_index_build(uint32_t n_seq, const float *const *fwd, const float *const *rev, const uint32_t *len,
+                            const rawdtw_seed_pars_t *pars, int threads, rawdtw_seed_index **out);
+/* the same from the hash buckets of a .ind file (rawindex.cpp:297-312, 354-374): 2^14 buckets (ri_idx_load always uses b = 14),
+ * each u32 n, n x u64 positions, u32 size, size x (u64 key, u64 val); hash = (key >> 1) << 14 | bucket; key & 1: val is the one
+ * position, else val = start << 32 | count into the bucket's positions.  A short file, a list outside its bucket, a hash above
+ * 32 bits or one listed twice: RAWDTW_ERR_INVALID. */
+int rawdtw_seed_index_load(const rawdtw_index *idx, rawdtw_seed_index **out);
+/* ri_idx_get: *pos (valid while the index lives) and *n, 0 for a hash the index does not hold */
+int rawdtw_seed_index_get(const rawdtw_seed_index *six, uint64_t hash, const uint64_t **pos, uint32_t *n);
+int rawdtw_seed_index_info(const rawdtw_seed_index *six, uint32_t *n_seq, uint64_t *n_keys, uint64_t *n_positions,
+                           uint64_t *table_bytes, rawdtw_seed_pars_t *pars);
+/* every hash the index holds, in table order (tests, and the writer of a .ind file's buckets); hashes has room for n_keys */
+int rawdtw_seed_index_keys(const rawdtw_seed_index *six, uint32_t *hashes);
+int rawdtw_seed_index_destroy(rawdtw_seed_index *six);
+/* ri_sketch for one chunk: hash_out and pos_out have room for n entries */
+int rawdtw_seed_sketch(const rawdtw_seed_pars_t *pars, const float *events, uint32_t n, uint32_t *hash_out, uint32_t *pos_out,
+                       uint32_t *n_out);
+/* host, many chunks (chunk k = events[event_off[k] .. event_off[k+1]), which may be empty) on `threads` threads, a thread whole
+ * chunks: chunk k's hits are hits[hit_off[k] .. hit_off[k+1]).  A total above hits_cap: RAWDTW_ERR_RANGE with hit_off filled and
+ * no hit written. */
+int rawdtw_seed_hits_host(const rawdtw_seed_index *six, uint32_t n_chunks, const uint64_t *event_off, const float *events,
+                          uint64_t *hit_off /* n_chunks+1 */, rawdtw_seed_hit_t *hits, uint64_t hits_cap, int threads);
+/* device.  _upload puts the index's table into the context's device memory (it replaces an earlier one and is freed with the
+ * context; the index may be destroyed afterwards; an index is known by a serial number of its own, never by its address, and
+ * uploading the one that is there already does nothing).  _begin / _end are the two halves, as rawdtw_detect_begin / _end: one seeding
+ * at a time a context, with its own grow-only workspace; _begin checks everything (nothing is enqueued when it refuses) and
+ * returns, the arrays must stay valid until _end; page-locked hit_off / hits (rawdtw_host_alloc) the device writes itself, others
+ * are copied in _end (through a device array of hits_cap entries: keep hits_cap near the need).  A total above hits_cap:
+ * RAWDTW_ERR_RANGE from _end with hit_off filled; the device checks the total before it writes a single hit.  An index with
+ * w > 0 is RAWDTW_ERR_UNSUPPORTED from _begin (seed such chunks with rawdtw_seed_hits_host); no table on the context is
+ * RAWDTW_ERR_INVALID.  No w == 0 input is declined for its size or its repeats. */
+int rawdtw_seed_index_upload(rawdtw_ctx *ctx, const rawdtw_seed_index *six);
+int rawdtw_seed_begin(rawdtw_ctx *ctx, uint32_t n_chunks, const uint64_t *event_off, const float *events,
+                      uint64_t *hit_off /* n_chunks+1 */, rawdtw_seed_hit_t *hits, uint64_t hits_cap);
+int rawdtw_seed_end(rawdtw_ctx *ctx, float *kernel_ms /* may be NULL: the launches' device time */);
+/* rawdtw_mapper_round with the seeding in front of it: the round's hits come from `six` instead of from the caller (the lines
+ * of gen_chains a host would otherwise keep, rmap.cpp:364-391), then the unchanged rawdtw_mapper_round runs on them.  A mapper
+ * with a context seeds on the device (the table of `six` is uploaded at the first round and whenever the context holds another index's; the
+ * whole round is seeded on the mapper's own context, whichever group a read belongs to, so a second group needs no table) into
+ * a page-locked buffer of its own; a mapper without one (a scorer's), and an index with
+ * w > 0, seed on the host with opt.threads.  `six` must hold as many sequences as the mapper (RAWDTW_ERR_INVALID).  A failed
+ * seeding changes nothing in the mapper. */
+int rawdtw_mapper_round_seeded(rawdtw_mapper *m, const rawdtw_seed_index *six, uint32_t n_reads, const uint32_t *read_ids,
+                               const uint64_t *event_off, const float *events);
 
 #ifdef __cplusplus
 }

@@ -25,6 +25,7 @@ from .align import (  # noqa: F401
 
 from .events import EventOptions, chunks_of, detect_events, detect_events_host  # noqa: F401
 from .rawsig import CHANNEL_DTYPE, Channel, chunk_table, detect_events_raw_host, to_pa  # noqa: F401
+from .seeding import HIT_DTYPE, SeedIndex, SeedParams, seed_hits_host, sketch  # noqa: F401
 
 __all__ = [
     "Engine", "Plan", "DtwResult", "JOB_DTYPE", "ANCHOR_DTYPE", "RAWDTW_FULL",
@@ -32,6 +33,7 @@ __all__ = [
     "load_library", "library_path", "LibraryMissing", "RawDTWError",
     "EventOptions", "detect_events", "detect_events_host", "chunks_of",
     "Channel", "CHANNEL_DTYPE", "to_pa", "chunk_table", "detect_events_raw_host",
+    "SeedIndex", "SeedParams", "HIT_DTYPE", "sketch", "seed_hits_host",
 ]
 
 DEFAULT_FOLD_MODE = 4  # rawdtw_set_option("fold_mode"): the library's default chain-fold kernel

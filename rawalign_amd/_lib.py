@@ -114,6 +114,11 @@ class SeedHit(C.Structure):
     _fields_ = [("ref_seq", C.c_uint32), ("strand", C.c_int32), ("target_position", C.c_uint32), ("query_position", C.c_uint32)]
 
 
+class SeedPars(C.Structure):
+    """rawdtw_seed_pars_t: ri_idx_t's w, e, n, q, lq, k (defaults of ri_idxopt_init, src/rawindex.cpp:465-472)"""
+    _fields_ = [("w", C.c_uint32), ("e", C.c_uint32), ("n", C.c_uint32), ("q", C.c_uint32), ("lq", C.c_uint32), ("k", C.c_uint32)]
+
+
 # rawdtw_scorer_fn (rawdtw_mapper_set_scorer)
 SCORER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                         C.c_void_p, C.c_void_p)
@@ -247,6 +252,18 @@ SYMBOLS = {
     "rawdtw_signal_chunk_table": (I32, [VP, U64, VP, U32, U32, C.POINTER(U64), C.POINTER(U32), VP]),
     "rawdtw_detect_raw_host": (I32, [C.POINTER(EventOpt), U32, VP, VP, VP, VP, VP, VP, U64, I32]),
     "rawdtw_detect_raw_begin": (I32, [VP, C.POINTER(EventOpt), U32, VP, VP, VP, VP, VP, VP, U64]),
+    "rawdtw_seed_index_build": (I32, [U32, VP, VP, VP, C.POINTER(SeedPars), I32, C.POINTER(VP)]),
+    "rawdtw_seed_index_load": (I32, [VP, C.POINTER(VP)]),
+    "rawdtw_seed_index_get": (I32, [VP, U64, C.POINTER(VP), C.POINTER(U32)]),
+    "rawdtw_seed_index_info": (I32, [VP, C.POINTER(U32), C.POINTER(U64), C.POINTER(U64), C.POINTER(U64), C.POINTER(SeedPars)]),
+    "rawdtw_seed_index_keys": (I32, [VP, VP]),
+    "rawdtw_seed_index_destroy": (I32, [VP]),
+    "rawdtw_seed_sketch": (I32, [C.POINTER(SeedPars), VP, U32, VP, VP, C.POINTER(U32)]),
+    "rawdtw_seed_hits_host": (I32, [VP, U32, VP, VP, VP, VP, U64, I32]),
+    "rawdtw_seed_index_upload": (I32, [VP, VP]),
+    "rawdtw_seed_begin": (I32, [VP, U32, VP, VP, VP, VP, U64]),
+    "rawdtw_seed_end": (I32, [VP, C.POINTER(F32)]),
+    "rawdtw_mapper_round_seeded": (I32, [VP, VP, U32, VP, VP, VP]),
 }
 
 

@@ -144,6 +144,7 @@ struct rawdtw_ctx {
     bool own_ev = false;
     struct rawdtw_chain_ws *chain_ws = nullptr; // rawdtw_chain_round's device block (rawdtw_chain.hip), grow-only
     struct rawdtw_detect_ws *detect_ws = nullptr; // rawdtw_detect_begin's device block (rawdtw_events.hip), grow-only
+    struct rawdtw_seed_ws *seed_ws = nullptr;     // rawdtw_seed_index_upload's table and rawdtw_seed_begin's device block (rawdtw_seed.hip), grow-only
     uint32_t chain_max_seeds = 0; // tests: RAWDTW_CHAIN_MAX_SEEDS lowers rawdtw_chain_round's cap on seeds a read, so that small rounds take the declined path (0: no)
     std::string err;
 };
@@ -182,6 +183,7 @@ struct rawdtw_index {
     std::vector<std::string> names;
     std::vector<uint32_t> lens;
     std::vector<uint64_t> fwd_pos; // file offset of each sequence's forward array (reverse follows it)
+    uint64_t bucket_pos = 0;       // file offset of the first hash bucket (rawdtw_seed_index_load reads from there)
 };
 
 struct rawdtw_batch {
@@ -266,6 +268,7 @@ inline int hip_fail(rawdtw_ctx *ctx, hipError_t e, const char *what)
 
 void chain_ws_free(rawdtw_ctx *ctx); // rawdtw_chain.hip
 void detect_ws_free(rawdtw_ctx *ctx); // rawdtw_events.hip
+void seed_ws_free(rawdtw_ctx *ctx);   // rawdtw_seed.hip
 
 #define HIP_TRY(ctx, expr)                                                                            \
     do {                                                                                              \

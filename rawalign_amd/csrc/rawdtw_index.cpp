@@ -34,6 +34,7 @@ int rawdtw_index_open(const char *path, rawdtw_index **out)
         ix->fwd_pos.push_back((uint64_t)ftello(f));
         ok = fseeko(f, (off_t)len * 8, SEEK_CUR) == 0; // skip forward + reverse arrays
     }
+    if (ok) ix->bucket_pos = (uint64_t)ftello(f); // the hash buckets (rawindex.cpp:297-312): rawdtw_seed_index_load's part
     fclose(f);
     if (!ok) { delete ix; return RAWDTW_ERR_INVALID; }
     *out = ix;

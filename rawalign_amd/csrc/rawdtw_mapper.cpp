@@ -296,6 +296,11 @@ struct rawdtw_mapper {
     bool su_closed_any = false;   // a batch has been closed (the parameters are fixed from then on)
     bool su_stopped = false;
     uint32_t su_mapped = 0;       // mapped reads of closed batches before the gate
+    // rawdtw_mapper_round_seeded: the round's hits, page-locked when the mapper has a context (the device writes them itself), grow-only
+    uint64_t *seed_off = nullptr;
+    rawdtw_seed_hit_t *seed_hits = nullptr;
+    uint64_t seed_off_cap = 0, seed_hits_cap = 0;
+    bool seed_pinned = false;
 };
 
 namespace {
@@ -336,6 +341,28 @@ int fail(rawdtw_mapper *m, int st, const std::string &msg)
 {
     if (m) m->err = msg;
     return st;
+}
+
+void seed_buffers_free(rawdtw_mapper *m)
+{
+    for (void *p : {(void *)m->seed_off, (void *)m->seed_hits})
+        if (p) { if (m->seed_pinned) rawdtw_host_free(p); else free(p); }
+    m->seed_off = nullptr; m->seed_hits = nullptr; m->seed_off_cap = m->seed_hits_cap = 0;
+}
+
+// room for `count` records in one of the seeding's buffers (contents are not kept)
+template <typename T> int seed_buffer(rawdtw_mapper *m, T **p, uint64_t *cap, uint64_t count)
+{
+    if (*cap >= count) return RAWDTW_OK;
+    if (*p) { if (m->seed_pinned) rawdtw_host_free(*p); else free(*p); }
+    *p = nullptr; *cap = 0;
+    const uint64_t want = count + count / 4 + 64;
+    void *q = nullptr;
+    if (m->seed_pinned) { if (rawdtw_host_alloc(want * sizeof(T), &q) != RAWDTW_OK) q = nullptr; }
+    else q = malloc(want * sizeof(T));
+    if (!q) return RAWDTW_ERR_OOM;
+    *p = static_cast<T *>(q); *cap = want;
+    return RAWDTW_OK;
 }
 
 void drop_batches(rawdtw_mapper *m) // (and with them what a round could carry from)
@@ -914,6 +941,7 @@ int rawdtw_mapper_destroy(rawdtw_mapper *m)
         for (RoundArrays &ra : g.buf) ra = RoundArrays(); // (pinned memory goes before the context that may own the device)
         if (g.own_ctx && g.ctx) rawdtw_destroy(g.ctx);
     }
+    seed_buffers_free(m);
     rawdtw_su_destroy(m->su);
     delete m->pool;
     delete m;
@@ -1031,6 +1059,45 @@ int rawdtw_mapper_round(rawdtw_mapper *m, uint32_t n_reads, const uint32_t *read
     if (!r.ok()) return r.rollback();
     r.commit();
     return RAWDTW_OK;
+}
+
+// The seeding of gen_chains (rmap.cpp:364-391) in front of the round.  Everything the seeding touches is the mapper's own buffers:
+// the reads change only inside rawdtw_mapper_round, which runs on the finished hits or not at all.
+int rawdtw_mapper_round_seeded(rawdtw_mapper *m, const rawdtw_seed_index *six, uint32_t n_reads, const uint32_t *read_ids,
+                               const uint64_t *event_off, const float *events)
+{
+    if (!m || !six || (n_reads && (!read_ids || !event_off)) || (n_reads && event_off[n_reads] > event_off[0] && !events)) return RAWDTW_ERR_INVALID;
+    uint32_t six_seq = 0;
+    rawdtw_seed_pars_t pars;
+    if (rawdtw_seed_index_info(six, &six_seq, nullptr, nullptr, nullptr, &pars) != RAWDTW_OK) return RAWDTW_ERR_INVALID;
+    if (six_seq != m->seq_len.size()) return fail(m, RAWDTW_ERR_INVALID, "the seed index and the mapper hold different numbers of sequences");
+    if (n_reads == 0) return RAWDTW_OK;
+    const bool on_device = m->ctx && pars.w == 0; // (the minimizer sketch is the host's)
+    if (!m->seed_off && !m->seed_hits) m->seed_pinned = m->ctx != nullptr;
+    if (seed_buffer(m, &m->seed_off, &m->seed_off_cap, (uint64_t)n_reads + 1) != RAWDTW_OK) return fail(m, RAWDTW_ERR_OOM, "no memory for the round's hit offsets");
+    if (!on_device) {
+        int st = rawdtw_seed_hits_host(six, n_reads, event_off, events, m->seed_off, nullptr, 0, m->opt.threads); // (counts)
+        if (st != RAWDTW_OK && st != RAWDTW_ERR_RANGE) return fail(m, st, "seeding: bad event offsets");
+        if (seed_buffer(m, &m->seed_hits, &m->seed_hits_cap, m->seed_off[n_reads]) != RAWDTW_OK) return fail(m, RAWDTW_ERR_OOM, "no memory for the round's hits");
+        st = rawdtw_seed_hits_host(six, n_reads, event_off, events, m->seed_off, m->seed_hits, m->seed_hits_cap, m->opt.threads);
+        if (st != RAWDTW_OK) return fail(m, st, "seeding failed");
+    } else {
+        // (every round: the context knows its table by the index's serial and does nothing when this index is there already --
+        // also right after the caller uploaded another index to the context, or rebuilt one at the old address)
+        const int up = rawdtw_seed_index_upload(m->ctx, six);
+        if (up != RAWDTW_OK) return fail(m, up, rawdtw_last_error(m->ctx));
+        // the first guess: what the buffer holds, or four hits an event; a round with more says how many and is seeded once more
+        uint64_t want = std::max<uint64_t>(m->seed_hits_cap, 4 * (event_off[n_reads] - event_off[0]) + 1024);
+        for (int attempt = 0;; attempt++) {
+            if (seed_buffer(m, &m->seed_hits, &m->seed_hits_cap, want) != RAWDTW_OK) return fail(m, RAWDTW_ERR_OOM, "no page-locked memory for the round's hits");
+            int st = rawdtw_seed_begin(m->ctx, n_reads, event_off, events, m->seed_off, m->seed_hits, m->seed_hits_cap);
+            if (st == RAWDTW_OK) st = rawdtw_seed_end(m->ctx, nullptr);
+            if (st == RAWDTW_ERR_RANGE && attempt == 0 && m->seed_off[n_reads] > m->seed_hits_cap) { want = m->seed_off[n_reads]; continue; }
+            if (st != RAWDTW_OK) return fail(m, st, rawdtw_last_error(m->ctx));
+            break;
+        }
+    }
+    return rawdtw_mapper_round(m, n_reads, read_ids, event_off, events, m->seed_off, m->seed_hits);
 }
 
 // --dtw-output-cigar (rmap.cpp:715-717): the best chain of every mapped read through DTW_global_tb once more, its path as the

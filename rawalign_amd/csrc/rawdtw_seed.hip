@@ -1,0 +1,443 @@
+// rawdtw_seed.hip -- seeding for a whole chunk round on the device: ri_sketch_reg (src/rsketch.c:223-274) and the lookup and hit
+// loop of gen_chains (src/rmap.cpp:371-391), equal to the host restatement (rawdtw_seed_host.cpp) hit for hit and in its order.  The
+// minimizer sketch (w > 0) stays on the host.
+//
+// One recurrence is serial per chunk: an event is compared with the last KEPT one.  Everything else is parallel.  Four launches:
+//   k_seed_filter  a lane per chunk, 64 chunks a wave: events staged through LDS in 64 x 64 tiles (coalesced loads), each lane
+//                  walks its own row and leaves every kept event's rank in its chunk; the tile then goes out row by row: a kept
+//                  event's code and position land densely at the chunk's offset (stores nearly coalesced: ranks ascend)
+//   k_seed_probe   a wave per chunk, a lane per kept event with e - 1 kept events in front of it: the last e codes packed, hashed
+//                  (32-bit arithmetic, rawdtw_seed.h) and looked up in the table -- one 16-byte load a probe, uncoalesced by nature;
+//                  what hides its latency is the number of independent probes in flight (every lane of every resident wave has
+//                  one).  The element's hit count and its position-or-list word are stored; the wave sums the chunk's hits
+//   k_seed_scan    one workgroup: exclusive scan of the chunks' hits -> hit_off and the total
+//   k_seed_write   a wave per chunk, 64 elements a step: a wave scan of the counts places every element's hits; an element with
+//                  up to kOwn hits is written by its own lane, a longer list by all 64 lanes together (no occurrence cap in the
+//                  reference: a repeat gives one element thousands of positions, which one lane must not write alone).  One
+//                  16-byte store a hit -- into device memory, or straight into the caller's page-locked array.  Nothing is
+//                  written unless the round's total fits.
+#include "rawdtw_capi.h"
+#include "rawdtw_seed.h"
+
+#pragma clang fp contract(off)
+
+namespace rawdtw {
+namespace {
+
+using seed::Slot;
+
+constexpr uint32_t kW = 64;       // chunks a wave, and events a tile
+constexpr uint32_t kPad = kW + 1; // LDS row stride (rawdtw_events.hip)
+constexpr uint32_t kOwn = 4;      // hits an element's own lane writes
+constexpr uint32_t kNone = ~0u;
+
+struct SeedArgs {
+    const uint64_t *off; // n + 1 event offsets, rebased to the uploaded events (off[0] = 0)
+    const float *ev;
+    uint32_t *code, *pos; // per chunk, dense from off[k]: the kept events' codes and positions
+    uint32_t *kept;       // per chunk
+    uint32_t *cnt;        // per kept event (at off[k] + rank): hits of the e-mer that ends there
+    uint64_t *val;        // ... and the position (cnt == 1) or the list's start in the position array
+    uint64_t *chits;      // per chunk: hits
+    uint64_t *hoff;       // n + 1
+    uint64_t *tot;        // [0] the total of hits
+    const Slot *slots;
+    const uint64_t *list;
+    uint32_t log2_slots;
+    uint32_t n, e, q, lq;
+};
+
+__device__ __forceinline__ uint32_t wave_max(uint32_t x)
+{
+    for (int o = 32; o; o >>= 1) x = max(x, (uint32_t)__shfl_xor((int)x, o));
+    return x;
+}
+
+__device__ __forceinline__ uint64_t lane_u64(uint64_t x, int c)
+{
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)x, c), hi = (uint32_t)__shfl((int)(uint32_t)(x >> 32), c);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// rsketch.c:242-247
+__global__ __launch_bounds__(64) void k_seed_filter(SeedArgs a)
+{
+    __shared__ float tx[kW * kPad];
+    __shared__ uint32_t tr[kW * kPad];
+    __shared__ uint64_t sb[kW];
+    __shared__ uint32_t sl[kW];
+    const uint32_t lane = threadIdx.x, c0 = blockIdx.x * kW, me = c0 + lane, nc = min(kW, a.n - c0);
+    uint64_t b = 0;
+    uint32_t len = 0;
+    if (lane < nc) { b = a.off[me]; len = (uint32_t)(a.off[me + 1] - b); }
+    sb[lane] = b; sl[lane] = len;
+    const uint32_t most = wave_max(len);
+    float last = 0.0f;
+    uint32_t rank = 0;
+    __syncthreads();
+    for (uint32_t t0 = 0; t0 < most; t0 += kW) {
+        const uint32_t i = t0 + lane;
+        {   // the tile: all 64 loads are issued before the first LDS store (one memory latency a tile)
+            float v[kW];
+#pragma unroll
+            for (int c = 0; c < (int)kW; c++) {
+                const uint64_t bc = lane_u64(b, c);
+                const uint32_t lc = (uint32_t)__shfl((int)len, c);
+                v[c] = i < lc ? a.ev[bc + i] : 0.0f;
+            }
+#pragma unroll
+            for (int c = 0; c < (int)kW; c++) tx[c * kPad + lane] = v[c];
+        }
+        __syncthreads();
+        const uint32_t lim = len > t0 ? min(kW, len - t0) : 0u;
+        for (uint32_t j = 0; j < lim; j++) {
+            const float x = tx[lane * kPad + j];
+            const bool skip = seed::skipped(x, last, t0 + j == 0);
+            tr[lane * kPad + j] = skip ? kNone : rank;
+            // ev[l_sigpos] with l_sigpos = 0 until an event is kept (rsketch.c:233,243-245): a chunk whose event 0 is RI_MASK_SIGNAL
+            // compares what follows with that value, not with nothing
+            if (t0 + j == 0 || !skip) last = x;
+            if (!skip) rank++;
+        }
+        __syncthreads();
+        for (uint32_t c = 0; c < nc; c++)
+            if (i < sl[c]) {
+                const uint32_t r = tr[c * kPad + lane];
+                if (r != kNone) { // r <= i < the chunk's length: inside the chunk's own stretch
+                    a.code[sb[c] + r] = seed::code_of(__float_as_uint(tx[c * kPad + lane]), a.q, a.lq);
+                    a.pos[sb[c] + r] = i;
+                }
+            }
+        __syncthreads();
+    }
+    if (lane < nc) a.kept[me] = rank;
+}
+
+// rsketch.c:254-255, rawindex.cpp:256-273
+__global__ __launch_bounds__(64) void k_seed_probe(SeedArgs a)
+{
+    const uint32_t k = blockIdx.x, lane = threadIdx.x, kept = a.kept[k], e = a.e, qb = a.lq + 2;
+    const uint64_t b = a.off[k];
+    const uint64_t mask_events = (1ull << (qb * e)) - 1;
+    const uint32_t smask = (1u << a.log2_slots) - 1;
+    uint64_t sum = 0;
+    for (uint32_t r = lane; r < kept; r += kW) {
+        uint32_t c = 0;
+        uint64_t v = 0;
+        if (r + 1 >= e) {
+            uint64_t quant = 0;
+            for (uint32_t j = 0; j < e; j++) quant = quant << qb | a.code[b + r + 1 - e + j];
+            const uint32_t h = seed::hash32((uint32_t)(quant & mask_events));
+            uint32_t at = seed::first_slot(h, a.log2_slots);
+            for (uint32_t tries = 0; tries <= smask; tries++, at = (at + 1) & smask) { // (the table is at most half full: an empty slot ends it)
+                const uint4 s = *reinterpret_cast<const uint4 *>(a.slots + at);
+                if (s.y == 0) break;
+                if (s.x == h) { c = s.y; v = (uint64_t)s.w << 32 | s.z; break; }
+            }
+        }
+        a.cnt[b + r] = c;
+        a.val[b + r] = v;
+        sum += c;
+    }
+    for (int o = 32; o; o >>= 1) sum += lane_u64(sum, (int)(lane ^ (uint32_t)o));
+    if (lane == 0) a.chits[k] = sum;
+}
+
+// exclusive scan of the chunks' hits (the shape of rawdtw_events.hip's k_ev_scan)
+__global__ __launch_bounds__(1024) void k_seed_scan(const uint64_t *cnt, uint32_t n, uint64_t *off, uint64_t *tot, uint64_t *h_off)
+{
+    __shared__ uint64_t part[1024];
+    const uint32_t t = threadIdx.x;
+    const uint64_t per = (n + 1023ull) / 1024, lo = min((uint64_t)n, t * per), hi = min((uint64_t)n, lo + per);
+    uint64_t s = 0;
+    for (uint64_t k = lo; k < hi; k++) s += cnt[k];
+    part[t] = s;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024; d <<= 1) {
+        const uint64_t v = t >= d ? part[t - d] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    uint64_t run = part[t] - s;
+    for (uint64_t k = lo; k < hi; k++) {
+        off[k] = run;
+        if (h_off) h_off[k] = run;
+        run += cnt[k];
+    }
+    if (t == 1023) {
+        off[n] = part[1023];
+        if (h_off) h_off[n] = part[1023];
+        tot[0] = part[1023];
+    }
+}
+
+__device__ __forceinline__ uint4 hit_of(uint64_t y, uint32_t query)
+{
+    return make_uint4((uint32_t)(y >> 32), (uint32_t)(y & 1), (uint32_t)(y >> 1) & 0x7fffffffu, query); // rmap.cpp:387-388
+}
+
+// rmap.cpp:385-389.  Nothing is written unless the whole round's hits fit below `bound` (the caller's hits_cap, and the device
+// array's size).
+__global__ __launch_bounds__(64) void k_seed_write(SeedArgs a, uint64_t bound, uint4 *out)
+{
+    if (a.tot[0] > bound) return;
+    const uint32_t k = blockIdx.x, lane = threadIdx.x, kept = a.kept[k];
+    if (!a.chits[k]) return;
+    const uint64_t b = a.off[k];
+    uint4 *dst = out + a.hoff[k];
+    uint64_t run = 0; // hits of the elements before this step
+    for (uint32_t r0 = 0; r0 < kept; r0 += kW) { // (the same trip count in every lane)
+        const uint32_t r = r0 + lane;
+        const uint32_t c = r < kept ? a.cnt[b + r] : 0u;
+        const uint64_t v = r < kept ? a.val[b + r] : 0ull;
+        const uint32_t query = r < kept ? a.pos[b + r] : 0u;
+        uint64_t incl = c; // (64 bits: 64 lists of up to 2^32 - 1 positions)
+#pragma unroll
+        for (int o = 1; o < (int)kW; o <<= 1) {
+            const uint64_t t = lane_u64(incl, (int)((lane - (uint32_t)o) & (kW - 1)));
+            if (lane >= (uint32_t)o) incl += t;
+        }
+        const uint64_t at = run + incl - c;
+        if (c == 1) dst[at] = hit_of(v, query);
+        else if (c <= kOwn)
+            for (uint32_t s = 0; s < c; s++) dst[at + s] = hit_of(a.list[v + s], query);
+        unsigned long long longs = __ballot(c > kOwn);
+        while (longs) { // a long list: all 64 lanes, 64 consecutive 16-byte stores a step
+            const int l = __ffsll(longs) - 1;
+            longs &= longs - 1;
+            const uint32_t lc = (uint32_t)__shfl((int)c, l), lquery = (uint32_t)__shfl((int)query, l);
+            const uint64_t lv = lane_u64(v, l), lat = lane_u64(at, l);
+            for (uint32_t s = lane; s < lc; s += kW) dst[lat + s] = hit_of(a.list[lv + s], lquery);
+        }
+        run += lane_u64(incl, kW - 1);
+    }
+}
+
+struct SeedWs {
+    // the table (rawdtw_seed_index_upload)
+    uint64_t table_serial = 0; // the uploaded index's serial (0: none): the same index again is not uploaded twice
+    Slot *d_slots = nullptr;
+    uint64_t *d_list = nullptr;
+    uint32_t log2_slots = 0;
+    rawdtw_seed_pars_t pars{};
+    bool has_table = false;
+    // the seeding's own block
+    void *dev = nullptr;
+    size_t dev_bytes = 0;
+    void *d_hits = nullptr; // only for a caller whose hits are pageable
+    size_t hits_bytes = 0;
+    uint64_t *pin = nullptr; // [0] the total; then the rebased offsets
+    size_t pin_bytes = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, done = nullptr;
+    // a seeding begun and not ended
+    bool pending = false, direct_off = false, direct_hits = false;
+    uint32_t n = 0;
+    uint64_t n_events = 0, cap = 0;
+    uint64_t *h_hoff = nullptr;
+    rawdtw_seed_hit_t *h_hits = nullptr;
+    const uint64_t *d_hoff = nullptr;
+};
+
+// the device address of a page-locked host array of `bytes` bytes, or null (rawdtw_events.hip's rule: pageable memory, or an
+// allocation that does not extend that far, is copied in _end)
+void *device_view(void *p, size_t bytes)
+{
+    if (!p) return nullptr;
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (at.type != hipMemoryTypeHost || !at.devicePointer) return nullptr;
+    hipDeviceptr_t start = nullptr;
+    size_t size = 0;
+    if (hipPointerGetAttribute(&start, HIP_POINTER_ATTRIBUTE_RANGE_START_ADDR, p) != hipSuccess ||
+        hipPointerGetAttribute(&size, HIP_POINTER_ATTRIBUTE_RANGE_SIZE, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    const char *s = static_cast<const char *>(start), *q = static_cast<const char *>(p);
+    if (q < s || (size_t)(q - s) > size || size - (size_t)(q - s) < bytes) return nullptr;
+    return at.devicePointer;
+}
+
+} // namespace
+} // namespace rawdtw
+
+using namespace rawdtw;
+using namespace rawdtw::capi;
+
+struct rawdtw_seed_ws { SeedWs w; };
+
+namespace {
+
+SeedWs *ws_of(rawdtw_ctx *ctx)
+{
+    if (!ctx->seed_ws) ctx->seed_ws = new (std::nothrow) rawdtw_seed_ws;
+    return ctx->seed_ws ? &ctx->seed_ws->w : nullptr;
+}
+
+} // namespace
+
+extern "C" {
+
+int rawdtw_seed_index_upload(rawdtw_ctx *ctx, const rawdtw_seed_index *six)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (!six) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    SeedWs *w = ws_of(ctx);
+    if (!w) return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed");
+    if (w->pending) return fail(ctx, RAWDTW_ERR_INVALID, "a seeding is begun on this context and not ended");
+    if (w->has_table && w->table_serial == six->serial) return RAWDTW_OK; // (this very index is there already)
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // (an earlier table may still be read)
+    if (w->d_slots) (void)hipFree(w->d_slots);
+    if (w->d_list) (void)hipFree(w->d_list);
+    w->d_slots = nullptr; w->d_list = nullptr; w->has_table = false; w->table_serial = 0;
+    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&w->d_slots), std::max<size_t>(six->slots.size(), 1) * sizeof(Slot)));
+    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&w->d_list), std::max<size_t>(six->pos.size(), 1) * 8));
+    if (!six->slots.empty()) HIP_TRY(ctx, hipMemcpyAsync(w->d_slots, six->slots.data(), six->slots.size() * sizeof(Slot), hipMemcpyHostToDevice, ctx->stream));
+    else HIP_TRY(ctx, hipMemsetAsync(w->d_slots, 0, sizeof(Slot), ctx->stream));
+    if (!six->pos.empty()) HIP_TRY(ctx, hipMemcpyAsync(w->d_list, six->pos.data(), six->pos.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // (the index may be destroyed when this returns)
+    w->log2_slots = six->slots.empty() ? 0 : six->log2_slots;
+    w->pars = six->pars;
+    w->table_serial = six->serial;
+    w->has_table = true;
+    return RAWDTW_OK;
+}
+
+int rawdtw_seed_begin(rawdtw_ctx *ctx, uint32_t n_chunks, const uint64_t *event_off, const float *events, uint64_t *hit_off,
+                      rawdtw_seed_hit_t *hits, uint64_t hits_cap)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (!hit_off || (n_chunks && !event_off)) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    if (n_chunks >= 0x7fffffffu) return fail(ctx, RAWDTW_ERR_INVALID, "2^31 chunks or more");
+    for (uint32_t k = 0; k < n_chunks; k++)
+        if (event_off[k + 1] < event_off[k] || event_off[k + 1] - event_off[k] > 0xffffffffull)
+            return fail(ctx, RAWDTW_ERR_INVALID, "a chunk of 2^32 events or more, or offsets that descend");
+    const uint64_t n = n_chunks, N = n ? event_off[n] - event_off[0] : 0;
+    if ((N && !events) || (hits_cap && !hits)) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    SeedWs *wp = ctx->seed_ws ? &ctx->seed_ws->w : nullptr;
+    if (!wp || !wp->has_table) return fail(ctx, RAWDTW_ERR_INVALID, "no seed index on this context (rawdtw_seed_index_upload)");
+    SeedWs &w = *wp;
+    if (w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "a seeding is begun on this context and not ended");
+    if (w.pars.w) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, "the minimizer sketch (w > 0) is seeded on the host (rawdtw_seed_hits_host)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    // offsets, events, codes, positions, counts (4 bytes an event each) and list words (8): 24 bytes an event
+    const size_t b_off = al((n + 1) * 8), b_ev = al(N * 4), b_val = al(N * 8), b_cnt = al(n * 4), b_tot = al(32);
+    const size_t need = 3 * b_off + 4 * b_ev + b_val + b_cnt + b_tot;
+    if (w.dev_bytes < need) {
+        if (w.dev) (void)hipFree(w.dev);
+        w.dev = nullptr; w.dev_bytes = 0;
+        const size_t want = need + need / 4;
+        if (hipMalloc(&w.dev, want) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, RAWDTW_ERR_OOM, "seeding workspace allocation failed"); }
+        w.dev_bytes = want;
+    }
+    const size_t pin_need = (n + 3) * 8;
+    if (w.pin_bytes < pin_need) {
+        if (w.pin) (void)hipHostFree(w.pin);
+        w.pin = nullptr; w.pin_bytes = 0;
+        const size_t want = pin_need + pin_need / 4;
+        if (hipHostMalloc(reinterpret_cast<void **>(&w.pin), want, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError(); w.pin = nullptr;
+            return fail(ctx, RAWDTW_ERR_OOM, "pinned allocation failed");
+        }
+        w.pin_bytes = want;
+    }
+    uint64_t *dv_hoff = static_cast<uint64_t *>(device_view(hit_off, (n + 1) * 8));
+    uint4 *dv_hits = hits_cap ? static_cast<uint4 *>(device_view(hits, hits_cap * sizeof(rawdtw_seed_hit_t))) : nullptr;
+    if (n && N && hits_cap && !dv_hits && w.hits_bytes < hits_cap * sizeof(rawdtw_seed_hit_t)) {
+        if (w.d_hits) (void)hipFree(w.d_hits);
+        w.d_hits = nullptr; w.hits_bytes = 0;
+        if (hipMalloc(&w.d_hits, hits_cap * sizeof(rawdtw_seed_hit_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ctx, RAWDTW_ERR_OOM, "no device memory for hits_cap hits (page-locked hits need none)");
+        }
+        w.hits_bytes = hits_cap * sizeof(rawdtw_seed_hit_t);
+    }
+    if (!w.ev0) HIP_TRY(ctx, hipEventCreate(&w.ev0));
+    if (!w.ev1) HIP_TRY(ctx, hipEventCreate(&w.ev1));
+    if (!w.done) HIP_TRY(ctx, hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
+    w.pending = true; w.n = n_chunks; w.n_events = N; w.cap = hits_cap;
+    w.h_hoff = hit_off; w.h_hits = hits;
+    w.direct_off = w.direct_hits = false;
+    if (n == 0 || N == 0) return RAWDTW_OK; // (nothing to enqueue: rawdtw_seed_end fills the zeros)
+    char *p = static_cast<char *>(w.dev);
+    SeedArgs a{};
+    uint64_t *d_off = reinterpret_cast<uint64_t *>(p); p += b_off;
+    float *d_ev = reinterpret_cast<float *>(p); p += b_ev;
+    a.code = reinterpret_cast<uint32_t *>(p); p += b_ev;
+    a.pos = reinterpret_cast<uint32_t *>(p); p += b_ev;
+    a.cnt = reinterpret_cast<uint32_t *>(p); p += b_ev;
+    a.val = reinterpret_cast<uint64_t *>(p); p += b_val;
+    a.kept = reinterpret_cast<uint32_t *>(p); p += b_cnt;
+    a.chits = reinterpret_cast<uint64_t *>(p); p += b_off;
+    a.hoff = reinterpret_cast<uint64_t *>(p); p += b_off;
+    a.tot = reinterpret_cast<uint64_t *>(p);
+    a.off = d_off; a.ev = d_ev; a.n = n_chunks;
+    a.e = w.pars.e; a.q = w.pars.q; a.lq = w.pars.lq;
+    a.slots = w.d_slots; a.list = w.d_list; a.log2_slots = w.log2_slots;
+    uint64_t *h_off = w.pin + 2;
+    for (uint64_t k = 0; k <= n; k++) h_off[k] = event_off[k] - event_off[0];
+    w.direct_off = dv_hoff != nullptr; w.direct_hits = dv_hits != nullptr;
+    w.d_hoff = a.hoff;
+    hipStream_t s = ctx->stream;
+    auto undo = [&](int st) { w.pending = false; return st; };
+    if (hipMemcpyAsync(d_off, h_off, (n + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(d_ev, events + event_off[0], N * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemsetAsync(a.tot, 0, 32, s) != hipSuccess || hipEventRecord(w.ev0, s) != hipSuccess)
+        return undo(hip_fail(ctx, hipGetLastError(), "seeding upload"));
+    hipLaunchKernelGGL(k_seed_filter, dim3((uint32_t)((n + kW - 1) / kW)), dim3(kW), 0, s, a);
+    hipLaunchKernelGGL(k_seed_probe, dim3(n_chunks), dim3(kW), 0, s, a);
+    hipLaunchKernelGGL(k_seed_scan, dim3(1), dim3(1024), 0, s, a.chits, n_chunks, a.hoff, a.tot, dv_hoff);
+    if (hits_cap) hipLaunchKernelGGL(k_seed_write, dim3(n_chunks), dim3(kW), 0, s, a, hits_cap, dv_hits ? dv_hits : static_cast<uint4 *>(w.d_hits));
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(w.ev1, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(w.pin, a.tot, 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipEventRecord(w.done, s);
+    if (e != hipSuccess) return undo(hip_fail(ctx, e, "seeding launches"));
+    return RAWDTW_OK;
+}
+
+int rawdtw_seed_end(rawdtw_ctx *ctx, float *kernel_ms)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (!ctx->seed_ws || !ctx->seed_ws->w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "no seeding begun on this context");
+    SeedWs &w = ctx->seed_ws->w;
+    w.pending = false;
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if (w.n == 0 || w.n_events == 0) { // nothing was enqueued
+        for (uint64_t k = 0; k <= w.n; k++) w.h_hoff[k] = 0;
+        return RAWDTW_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    HIP_TRY(ctx, hipEventSynchronize(w.done)); // (the seeding's own work: what the caller enqueued behind it goes on)
+    const uint64_t tot = w.pin[0];
+    if (!w.direct_off) {
+        HIP_TRY(ctx, hipMemcpyAsync(w.h_hoff, w.d_hoff, ((uint64_t)w.n + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+    }
+    if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, w.ev0, w.ev1));
+    if (tot > w.cap) return fail(ctx, RAWDTW_ERR_RANGE, "hits_cap is below the round's hits (hit_off is filled)");
+    if (!w.direct_hits && tot) {
+        HIP_TRY(ctx, hipMemcpyAsync(w.h_hits, w.d_hits, tot * sizeof(rawdtw_seed_hit_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+    }
+    return RAWDTW_OK;
+}
+
+} // extern "C"
+
+namespace rawdtw { namespace capi {
+void seed_ws_free(rawdtw_ctx *ctx)
+{
+    if (!ctx || !ctx->seed_ws) return;
+    SeedWs &w = ctx->seed_ws->w;
+    for (void *p : {(void *)w.d_slots, (void *)w.d_list, w.dev, w.d_hits}) if (p) (void)hipFree(p);
+    if (w.pin) (void)hipHostFree(w.pin);
+    for (hipEvent_t e : {w.ev0, w.ev1, w.done}) if (e) (void)hipEventDestroy(e);
+    delete ctx->seed_ws;
+    ctx->seed_ws = nullptr;
+}
+} }

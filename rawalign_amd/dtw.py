@@ -265,6 +265,48 @@ class Engine:
         out = (s_len[:n].copy(), eoff[:n + 1].copy(), ev[:int(eoff[n])].copy())
         return out + (float(ms.value),) if kernel_ms else out
 
+    # -- seeding (ri_sketch + ri_idx_get, src/rmap.cpp:364-391) ---------------------
+    def upload_seed_index(self, index):
+        """The table of a seeding.SeedIndex into this context's device memory (replaces an earlier one)."""
+        self._check(self.lib.rawdtw_seed_index_upload(self._ctx, index._h))
+
+    def seed_hits(self, events, event_off, pinned: bool = True, hits_cap=None, kernel_ms: bool = False):
+        """Every chunk k = events[event_off[k] .. event_off[k+1]) on the device: rawdtw_seed_begin, then _end.  Staging as
+        detect_events keeps it.  hits_cap None: a first guess, and one more call with the exact total when it was too small.
+        Returns (hit_off, hits as seeding.HIT_DTYPE), and the launches' device time in ms too when kernel_ms."""
+        from .events import PinnedArray
+        from .seeding import HIT_DTYPE
+
+        ev = np.asarray(events, np.float32)
+        off = np.ascontiguousarray(event_off, np.uint64)
+        n = len(off) - 1
+        cap = max(4 * len(ev), 1024) if hits_cap is None else int(hits_cap)
+        while True:
+            if pinned:
+                st = getattr(self, "_seed_stage", None)
+                if st is None or st["ev"].array.size < len(ev) or st["off"].array.size < n + 1 or st["hits"].array.size < cap:
+                    st = self._seed_stage = {"ev": PinnedArray(len(ev), np.float32), "off": PinnedArray(n + 1, np.uint64),
+                                             "hoff": PinnedArray(n + 1, np.uint64), "hits": PinnedArray(cap, HIT_DTYPE)}
+                h_ev, h_off, hoff, hits = st["ev"].array, st["off"].array, st["hoff"].array, st["hits"].array
+                h_ev[:len(ev)] = ev
+                h_off[:n + 1] = off
+            else:
+                h_ev, h_off = np.ascontiguousarray(ev), off
+                hoff, hits = np.zeros(n + 1, np.uint64), np.zeros(max(cap, 1), HIT_DTYPE)
+            ms = C.c_float()
+            self._check(self.lib.rawdtw_seed_begin(self._ctx, n, h_off.ctypes.data, h_ev.ctypes.data, hoff.ctypes.data,
+                                                   hits.ctypes.data if cap else None, cap))
+            st = self.lib.rawdtw_seed_end(self._ctx, C.byref(ms))
+            if st == 4 and hits_cap is None:  # RAWDTW_ERR_RANGE: hit_off is filled
+                cap = int(hoff[n])
+                continue
+            if st != 0:
+                err = RawDTWError(st, self.lib.rawdtw_last_error(self._ctx).decode())
+                err.hit_off = hoff[:n + 1].copy()
+                raise err
+            out = (hoff[:n + 1].copy(), hits[:int(hoff[n])].copy())
+            return out + (float(ms.value),) if kernel_ms else out
+
     # -- batches ----------------------------------------------------------------
     def plan(self, jobs) -> Plan:
         jobs = np.ascontiguousarray(jobs, dtype=JOB_DTYPE)

@@ -96,6 +96,29 @@ class SyntheticSeeds:
         return ev, hits
 
 
+class IndexSeeds:
+    """SyntheticSeeds' interface over real seeding: reads[r] is the list of read r's chunks (each the chunk's events), and a
+    chunk's hits are ri_sketch + ri_idx_get on `seed_index` (seeding.seed_hits_host), in the reference's order.  `seq_lens`: the
+    reference sequences' lengths; `qlens`: the reads' lengths in samples (default 4000 a chunk)."""
+
+    def __init__(self, seed_index, reads, seq_lens, qlens=None, names=None):
+        self.seed_index = seed_index
+        self.lens = np.asarray(seq_lens)   # (the sequences' lengths: the PAF line's)
+        self.reads = [[np.ascontiguousarray(c, np.float32) for c in chunks] for chunks in reads]
+        self.qlens = list(qlens) if qlens is not None else [4000 * len(c) for c in self.reads]
+        self.names = list(names) if names is not None else [f"read_{r}" for r in range(len(self.reads))]
+
+    def read_job(self, r) -> ReadJob:
+        return ReadJob(self.names[r], qlen=int(self.qlens[r]), n_chunks_available=len(self.reads[r]))
+
+    def chunk(self, r, c):
+        from .seeding import seed_hits_host
+
+        ev = self.reads[r][c]
+        _, h = seed_hits_host(self.seed_index, ev, [0, len(ev)])
+        return ev, list(zip(h["ref_seq"].tolist(), h["strand"].tolist(), h["target_position"].tolist(), h["query_position"].tolist()))
+
+
 def score_log_line(chain) -> str:
     """rmap.cpp:308-312: sprintf("chaining_score=%f alignment_score=%f\\n", ...)."""
     return "chaining_score=%f alignment_score=%f\n" % (float(np.float32(chain.chaining_score)),
@@ -547,9 +570,16 @@ class CMapper:
         """one chunk round from flat arrays (read_ids u32, event_off / hit_off u64, events f32, hits HIT_DTYPE)"""
         self._check(self.lib.rawdtw_mapper_round(self._h, len(read_ids), _vp(read_ids), _vp(event_off), _vp(events), _vp(hit_off), _vp(hits)))
 
-    def round(self, read_ids, chunks):
-        """chunks[k] = (events, hits as (seq, strand, target, query) tuples) of read read_ids[k]"""
+    def round(self, read_ids, chunks, seed_index=None):
+        """chunks[k] = (events, hits as (seq, strand, target, query) tuples) of read read_ids[k].  With `seed_index` (a
+        seeding.SeedIndex) the library seeds the round itself (rawdtw_mapper_round_seeded) and the chunks' hits are not looked at."""
         ids = np.ascontiguousarray(read_ids, np.uint32)
+        if seed_index is not None:
+            eoff = np.zeros(len(ids) + 1, np.uint64)
+            eoff[1:] = np.cumsum([len(c[0]) for c in chunks])
+            ev = np.concatenate([np.ascontiguousarray(c[0], np.float32) for c in chunks] + [np.zeros(1, np.float32)])
+            self._check(self.lib.rawdtw_mapper_round_seeded(self._h, seed_index._h, len(ids), _vp(ids), _vp(eoff), _vp(ev)))
+            return
         eoff = np.zeros(len(ids) + 1, np.uint64)
         hoff = np.zeros(len(ids) + 1, np.uint64)
         for k, (ev, hits) in enumerate(chunks):
@@ -694,7 +724,7 @@ class CMapper:
             self._h = None
 
 
-def map_reads_c(seeds, read_ids, cm: CMapper, batch_size=None, su=None):
+def map_reads_c(seeds, read_ids, cm: CMapper, batch_size=None, su=None, seed_index=None):
     """map_reads through the library's mapper: chunk rounds until every read stopped; the PAF lines in read order, the rounds.
 
     The reads go in mini-batches of `batch_size` (None: one of all of them), at most two at a time -- the next batch's reads are
@@ -747,7 +777,10 @@ def map_reads_c(seeds, read_ids, cm: CMapper, batch_size=None, su=None):
                 chunks.append(seeds.chunk(r, done))
         if not act:
             break
-        cm.round(act, chunks)
+        if seed_index is None:
+            cm.round(act, chunks)
+        else:
+            cm.round(act, chunks, seed_index=seed_index)   # (the library seeds: seeds.chunk's hits are not used)
         rounds += 1
     st = cm.finish()
     if st != 0:
