@@ -820,6 +820,46 @@ int rawdtw_seed_end(rawdtw_ctx *ctx, float *kernel_ms /* may be NULL: the launch
 int rawdtw_mapper_round_seeded(rawdtw_mapper *m, const rawdtw_seed_index *six, uint32_t n_reads, const uint32_t *read_ids,
                                const uint64_t *event_off, const float *events);
 
+/* ---- a chunk round whose seed hits stay on the device.  rawdtw_mapper_round_seeded brings every hit home (16 bytes) and sends it
+ * up again as a seed (12 bytes), although the chaining reads its seeds on the device; the entries below leave the hits where the
+ * seeding found them.
+ *   rawdtw_seed_resident_begin / _end  rawdtw_seed_begin / _end on events that are in the context's event arena already (after the
+ *       round's rawdtw_events_append: nothing goes up twice): chunk k is the arena's ev_len[k] events from ev_start[k].  Only
+ *       hit_off (n_chunks + 1 entries, 8 bytes a chunk) comes home; the hits stay in the seeding's workspace until the context's
+ *       next seeding of either kind, or its next rawdtw_seed_index_upload of another index.  The rules are rawdtw_seed_begin's:
+ *       refused before anything is enqueued, one seeding a context at a time (of either kind; a resident one is ended by
+ *       rawdtw_seed_resident_end only), w > 0 RAWDTW_ERR_UNSUPPORTED, no table RAWDTW_ERR_INVALID, a chunk outside the arena
+ *       RAWDTW_ERR_RANGE, 64-bit counts.
+ *   rawdtw_seed_resident_fetch  the ended resident seeding's hits into hits[0 .. hit_off[n_chunks]), in rawdtw_seed_begin's order
+ *       (page-locked: written by the device itself); RAWDTW_ERR_RANGE when hits_cap is below the total.  For fall-backs and tests.
+ *   rawdtw_chain_round_begin_resident  rawdtw_chain_round_begin without a seed list from the host: read r's seeds are its previous
+ *       chains' anchors prev_seeds[prev_off[r] .. prev_off[r+1]) (host, small) followed by chunk r's hits of the ended resident
+ *       seeding as {ref_seq * 2 + strand, target_position, query_position + chunk_start[r]} (rmap.cpp:385-391), written on the device
+ *       into seed_off[r] ..; a read with sits_out[r] != 0 (its chunk is below min_events, rmap.cpp:569-572) gets nothing and must
+ *       have an empty stretch and no previous seeds.  RAWDTW_ERR_INVALID: no ended resident seeding, n_reads other than its
+ *       chunks, or a seed_off stretch that is not previous + hits.  Caps, RAWDTW_ERR_UNSUPPORTED and rawdtw_chain_round_end as for
+ *       rawdtw_chain_round_begin; the arrays must stay valid until _end.
+ *   rawdtw_mapper_round_seeded_resident  rawdtw_mapper_round_seeded through the three above: append the events, seed from the
+ *       arena, size the round by hit_off, chain, and from there the unchanged round.  Only for a mapper that chains on the
+ *       device (device_chain, a context, no scorer; with or without a DTW stage) with one read group and a w == 0 index: anything else is
+ *       RAWDTW_ERR_UNSUPPORTED with nothing changed (use rawdtw_mapper_round_seeded).  A round the device chaining declines (its
+ *       caps) fetches the hits once and is chained on the host: the same lines.  A failed round leaves the mapper as it was.
+ *   rawdtw_mapper_resident_stats  rounds that stayed resident, rounds that fell back, bytes of hits fetched to the host (16 a hit
+ *       of the fall-back rounds), bytes of seeds sent up (12 a previous anchor of the resident rounds).  Any pointer may be NULL. ---- */
+int rawdtw_seed_resident_begin(rawdtw_ctx *ctx, uint32_t n_chunks, const uint64_t *ev_start, const uint32_t *ev_len,
+                               uint64_t *hit_off /* n_chunks+1 */);
+int rawdtw_seed_resident_end(rawdtw_ctx *ctx, float *kernel_ms /* may be NULL */);
+int rawdtw_seed_resident_fetch(rawdtw_ctx *ctx, rawdtw_seed_hit_t *hits, uint64_t hits_cap);
+int rawdtw_chain_round_begin_resident(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads, const uint64_t *seed_off,
+                                      const uint64_t *prev_off, const rawdtw_seed_t *prev_seeds, const uint32_t *chunk_start,
+                                      const uint8_t *sits_out, const uint32_t *read_base, uint32_t n_keys, const uint64_t *key_base,
+                                      uint64_t *chain_off, uint64_t *anchor_off, rawdtw_chain_rec_t *recs, uint64_t chains_cap,
+                                      rawdtw_anchor_t *anchors);
+int rawdtw_mapper_round_seeded_resident(rawdtw_mapper *m, const rawdtw_seed_index *six, uint32_t n_reads, const uint32_t *read_ids,
+                                        const uint64_t *event_off, const float *events);
+int rawdtw_mapper_resident_stats(const rawdtw_mapper *m, uint64_t *resident_rounds, uint64_t *fallback_rounds,
+                                 uint64_t *hit_bytes_to_host, uint64_t *seed_bytes_to_device);
+
 #ifdef __cplusplus
 }
 #endif

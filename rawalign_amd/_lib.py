@@ -264,6 +264,12 @@ SYMBOLS = {
     "rawdtw_seed_begin": (I32, [VP, U32, VP, VP, VP, VP, U64]),
     "rawdtw_seed_end": (I32, [VP, C.POINTER(F32)]),
     "rawdtw_mapper_round_seeded": (I32, [VP, VP, U32, VP, VP, VP]),
+    "rawdtw_seed_resident_begin": (I32, [VP, U32, VP, VP, VP]),
+    "rawdtw_seed_resident_end": (I32, [VP, C.POINTER(F32)]),
+    "rawdtw_seed_resident_fetch": (I32, [VP, VP, U64]),
+    "rawdtw_chain_round_begin_resident": (I32, [VP, C.POINTER(ChainOpt), U64, VP, VP, VP, VP, VP, VP, U32, VP, VP, VP, VP, U64, VP]),
+    "rawdtw_mapper_round_seeded_resident": (I32, [VP, VP, U32, VP, VP, VP]),
+    "rawdtw_mapper_resident_stats": (I32, [VP, VP, VP, VP, VP]),
 }
 
 

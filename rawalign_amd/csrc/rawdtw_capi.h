@@ -269,6 +269,11 @@ inline int hip_fail(rawdtw_ctx *ctx, hipError_t e, const char *what)
 void chain_ws_free(rawdtw_ctx *ctx); // rawdtw_chain.hip
 void detect_ws_free(rawdtw_ctx *ctx); // rawdtw_events.hip
 void seed_ws_free(rawdtw_ctx *ctx);   // rawdtw_seed.hip
+// the context's ended resident seeding (rawdtw_seed.hip) as rawdtw_chain_round_begin_resident uses it: its hit offsets on the host
+// (null: there is none), and the launch that lays reads' previous anchors and hits down as the chaining's seed list, on the context's stream
+const uint64_t *seed_resident_hit_off(const rawdtw_ctx *ctx, uint64_t *n_chunks);
+void seed_resident_write_chain(rawdtw_ctx *ctx, rawdtw_seed_t *d_seeds, const uint64_t *d_seed_off, const uint64_t *d_prev_off, const rawdtw_seed_t *d_prev,
+                               const uint32_t *d_chunk_start, const uint8_t *d_sits_out);
 
 #define HIP_TRY(ctx, expr)                                                                            \
     do {                                                                                              \

@@ -320,17 +320,44 @@ using namespace rawdtw::capi;
 
 struct rawdtw_chain_ws { ChainWs w; };
 
-extern "C" {
+namespace {
 
-int rawdtw_chain_round_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads, const uint64_t *seed_off, const rawdtw_seed_t *seeds,
-                             const uint32_t *read_base, uint32_t n_keys, const uint64_t *key_base, uint64_t *chain_off, uint64_t *anchor_off,
-                             rawdtw_chain_rec_t *recs, uint64_t chains_cap, rawdtw_anchor_t *anchors)
+// where a resident round's seeds come from (rawdtw_chain_round_begin_resident): the previous chains' anchors from the host, the hits from the
+// context's ended resident seeding
+struct ResidentSeeds {
+    const uint64_t *prev_off;
+    const rawdtw_seed_t *prev_seeds;
+    const uint32_t *chunk_start;
+    const uint8_t *sits_out;
+};
+
+// rawdtw_chain_round_begin; `res`: the seed list is not the caller's `seeds` but laid down on the device
+int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads, const uint64_t *seed_off, const rawdtw_seed_t *seeds, const ResidentSeeds *res,
+                const uint32_t *read_base, uint32_t n_keys, const uint64_t *key_base, uint64_t *chain_off, uint64_t *anchor_off,
+                rawdtw_chain_rec_t *recs, uint64_t chains_cap, rawdtw_anchor_t *anchors)
 {
     if (!ctx) return RAWDTW_ERR_INVALID;
-    if (!opt || !seed_off || (!seeds && n_reads && seed_off[n_reads]) || !read_base || (!key_base && n_keys) || !chain_off || !anchor_off || !recs)
+    if (!opt || !seed_off || (!res && !seeds && n_reads && seed_off[n_reads]) || !read_base || (!key_base && n_keys) || !chain_off || !anchor_off || !recs)
         return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    if (res && (!res->prev_off || !res->chunk_start || !res->sits_out)) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
     if (ctx->chain_ws && ctx->chain_ws->w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "a chaining round is begun on this context and not ended");
     if (n_reads == 0 || n_reads > 0xffffffffull) return fail(ctx, RAWDTW_ERR_INVALID, "no reads, or more than 2^32");
+    uint64_t n_prev = 0;
+    if (res) { // every read's stretch is its previous anchors plus its chunk's hits, or empty: the device writes exactly that and nothing else
+        uint64_t nc = 0;
+        const uint64_t *hoff = seed_resident_hit_off(ctx, &nc);
+        if (!hoff) return fail(ctx, RAWDTW_ERR_INVALID, "no ended resident seeding on this context (rawdtw_seed_resident_begin / _end)");
+        if (nc != n_reads) return fail(ctx, RAWDTW_ERR_INVALID, "the resident seeding's chunks are not this round's reads");
+        if (seed_off[0] != 0 || res->prev_off[0] != 0) return fail(ctx, RAWDTW_ERR_INVALID, "offsets do not start at 0");
+        for (uint64_t r = 0; r < n_reads; r++) {
+            if (seed_off[r + 1] < seed_off[r] || res->prev_off[r + 1] < res->prev_off[r]) return fail(ctx, RAWDTW_ERR_INVALID, "offsets do not ascend");
+            const uint64_t pv = res->prev_off[r + 1] - res->prev_off[r], want = res->sits_out[r] ? 0 : pv + (hoff[r + 1] - hoff[r]);
+            if ((res->sits_out[r] && pv) || seed_off[r + 1] - seed_off[r] != want)
+                return fail(ctx, RAWDTW_ERR_INVALID, "a read's seed_off stretch is not its previous anchors plus its chunk's hits (empty for a read that sits out)");
+        }
+        n_prev = res->prev_off[n_reads];
+        if (n_prev && !res->prev_seeds) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint64_t n_seeds = seed_off[n_reads];
     uint32_t most = 0;
@@ -348,7 +375,10 @@ int rawdtw_chain_round_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uin
                  b_tmpa = al((size_t)n_seeds * 8 + 16), b_trec = al(n_reads * kChainCap * sizeof(ChainRecDev)), b_cnt = al(n_reads * sizeof(ChainCnt)),
                  b_coff = al((n_reads + 1) * 8), b_ra0 = al(n_reads * 8), b_tot = al(32), b_aoff = al((n_reads * kChainCap + 1) * 8), b_anch = al((size_t)n_seeds * 8 + 16),
                  b_refb = al(n_reads * kChainCap * 8 + 8), b_rbc = al(n_reads * kChainCap * 4 + 8), b_recs = al(n_reads * kChainCap * sizeof(rawdtw_chain_rec_t) + 8);
-    const size_t need = b_soff + b_seeds + b_rb + b_kb + b_tmpa + b_trec + b_cnt + b_coff + b_ra0 + b_tot + b_aoff + b_anch + b_refb + b_rbc + b_recs;
+    // (a resident round: the previous anchors, dense, their offsets, the chunk starts and the sits-out flags, behind everything else)
+    const size_t b_prev = res ? al((size_t)n_prev * sizeof(rawdtw_seed_t) + 16) : 0, b_poff = res ? al((n_reads + 1) * 8) : 0, b_cs = res ? al(n_reads * 4) : 0,
+                 b_so = res ? al(n_reads) : 0;
+    const size_t need = b_soff + b_seeds + b_rb + b_kb + b_tmpa + b_trec + b_cnt + b_coff + b_ra0 + b_tot + b_aoff + b_anch + b_refb + b_rbc + b_recs + b_prev + b_poff + b_cs + b_so;
     if (!ctx->chain_ws) ctx->chain_ws = new (std::nothrow) rawdtw_chain_ws;
     if (!ctx->chain_ws) return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed");
     ChainWs &w = ctx->chain_ws->w;
@@ -375,10 +405,21 @@ int rawdtw_chain_round_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uin
     rawdtw_anchor_t *d_anch = reinterpret_cast<rawdtw_anchor_t *>(p); p += b_anch;
     uint64_t *d_refb = reinterpret_cast<uint64_t *>(p); p += b_refb;
     uint32_t *d_rbc = reinterpret_cast<uint32_t *>(p); p += b_rbc;
-    rawdtw_chain_rec_t *d_recs = reinterpret_cast<rawdtw_chain_rec_t *>(p);
+    rawdtw_chain_rec_t *d_recs = reinterpret_cast<rawdtw_chain_rec_t *>(p); p += b_recs;
+    rawdtw_seed_t *d_prev = reinterpret_cast<rawdtw_seed_t *>(p); p += b_prev;
+    uint64_t *d_poff = reinterpret_cast<uint64_t *>(p); p += b_poff;
+    uint32_t *d_cs = reinterpret_cast<uint32_t *>(p); p += b_cs;
+    uint8_t *d_so = reinterpret_cast<uint8_t *>(p);
     hipStream_t s = ctx->stream;
     HIP_TRY(ctx, hipMemcpyAsync(d_soff, seed_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, s));
-    if (n_seeds) HIP_TRY(ctx, hipMemcpyAsync(d_seeds, seeds, (size_t)n_seeds * sizeof(rawdtw_seed_t), hipMemcpyHostToDevice, s));
+    if (res) { // only the previous anchors go up; rawdtw_seed.hip's writer puts them and the hits in place
+        if (n_prev) HIP_TRY(ctx, hipMemcpyAsync(d_prev, res->prev_seeds, (size_t)n_prev * sizeof(rawdtw_seed_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d_poff, res->prev_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d_cs, res->chunk_start, n_reads * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d_so, res->sits_out, n_reads, hipMemcpyHostToDevice, s));
+        seed_resident_write_chain(ctx, d_seeds, d_soff, d_poff, d_prev, d_cs, d_so);
+        HIP_TRY(ctx, hipGetLastError());
+    } else if (n_seeds) HIP_TRY(ctx, hipMemcpyAsync(d_seeds, seeds, (size_t)n_seeds * sizeof(rawdtw_seed_t), hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemcpyAsync(d_rb, read_base, n_reads * 4, hipMemcpyHostToDevice, s));
     if (n_keys) HIP_TRY(ctx, hipMemcpyAsync(d_kb, key_base, (size_t)n_keys * 8, hipMemcpyHostToDevice, s));
     ChainArgs a{d_soff, d_seeds, (uint32_t)n_reads, n2, *opt, d_tmpa, d_trec, d_cnt};
@@ -405,6 +446,26 @@ int rawdtw_chain_round_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uin
     w.h_anchor_off = anchor_off; w.h_recs = recs; w.h_anchors = anchors;
     w.d_aoff = d_aoff; w.d_recs = d_recs; w.d_anch = d_anch; w.d_refb = d_refb; w.d_rbc = d_rbc;
     return RAWDTW_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int rawdtw_chain_round_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads, const uint64_t *seed_off, const rawdtw_seed_t *seeds,
+                             const uint32_t *read_base, uint32_t n_keys, const uint64_t *key_base, uint64_t *chain_off, uint64_t *anchor_off,
+                             rawdtw_chain_rec_t *recs, uint64_t chains_cap, rawdtw_anchor_t *anchors)
+{
+    return chain_begin(ctx, opt, n_reads, seed_off, seeds, nullptr, read_base, n_keys, key_base, chain_off, anchor_off, recs, chains_cap, anchors);
+}
+
+int rawdtw_chain_round_begin_resident(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads, const uint64_t *seed_off, const uint64_t *prev_off,
+                                      const rawdtw_seed_t *prev_seeds, const uint32_t *chunk_start, const uint8_t *sits_out, const uint32_t *read_base,
+                                      uint32_t n_keys, const uint64_t *key_base, uint64_t *chain_off, uint64_t *anchor_off, rawdtw_chain_rec_t *recs,
+                                      uint64_t chains_cap, rawdtw_anchor_t *anchors)
+{
+    const ResidentSeeds res{prev_off, prev_seeds, chunk_start, sits_out};
+    return chain_begin(ctx, opt, n_reads, seed_off, nullptr, &res, read_base, n_keys, key_base, chain_off, anchor_off, recs, chains_cap, anchors);
 }
 
 int rawdtw_chain_round_end(rawdtw_ctx *ctx, const rawdtw_anchor_t **d_anchors, const uint64_t **d_ref_base, const uint32_t **d_read_base)

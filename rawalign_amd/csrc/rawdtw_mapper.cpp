@@ -118,6 +118,9 @@ struct RoundArrays {
     PinBuf<uint64_t> seed_off;           // device chaining (opt.device_chain): the reads' seed lists in, the chains' records out
     PinBuf<rawdtw_seed_t> seeds;
     PinBuf<rawdtw_chain_rec_t> recs;
+    PinBuf<uint64_t> prev_off, ev_start;  // a resident round (rawdtw_mapper_round_seeded_resident): the previous anchors' offsets (the anchors themselves, dense, in
+    PinBuf<uint32_t> chunk_start, ev_len; // `seeds`), the chunks' places in the event arena, and what the device's writer needs per read
+    PinBuf<uint8_t> sits_out;
     std::vector<uint32_t> chain_seq; // (the external scorer's view)
     std::vector<int32_t> chain_strand;
     uint64_t n_reads = 0, n_chains = 0, n_anchors = 0; // (the sizes the next round's matching reads again)
@@ -301,6 +304,8 @@ struct rawdtw_mapper {
     rawdtw_seed_hit_t *seed_hits = nullptr;
     uint64_t seed_off_cap = 0, seed_hits_cap = 0;
     bool seed_pinned = false;
+    // rawdtw_mapper_round_seeded_resident (rawdtw_mapper_resident_stats)
+    uint64_t res_rounds = 0, res_fallbacks = 0, res_hit_bytes = 0, res_seed_bytes = 0;
 };
 
 namespace {
@@ -519,6 +524,9 @@ struct Round {
     uint32_t n_reads;
     const uint32_t *read_ids; const uint64_t *event_off; const float *events; const uint64_t *hit_off; const rawdtw_seed_hit_t *hits;
     double t0; // (the last lap)
+    // a resident round: the hits are on the device (hit_off / hits are set only by its fall-back, which fetches them)
+    bool resident = false, fell_back = false;
+    uint64_t res_prev = 0, res_hits = 0; // previous anchors sent up as seeds; hits fetched by the fall-back
     uint32_t G = (uint32_t)m->groups.size(); // (1 or 2)
     uint64_t id = m->rounds + 1;
     bool runs_dtw = (m->opt.flag & (0x2 | 0x8)) != 0, on_device = runs_dtw && !m->scorer;
@@ -526,7 +534,7 @@ struct Round {
     // its reads' chunks ARE the segments, in order -- no copy into the mapper's own staging (a third of the host phase)
     bool events_in_place = on_device && m->opt.device_chain && G == 1 && event_off[n_reads] > 0 && rawdtw_host_is_page_locked(events) == 1;
     std::vector<RoundRead> rr = std::vector<RoundRead>(n_reads);
-    struct PerGroup { bool chaining = false; uint64_t ns = 0, nev = 0, nseg = 0, scored = 0, reused = 0; } per[2];
+    struct PerGroup { bool chaining = false; uint64_t ns = 0, nev = 0, nseg = 0, scored = 0, reused = 0, extra = 0; } per[2]; // (ns: seeds sent up; extra: other bytes)
     int status = RAWDTW_OK;
     std::string msg;
 
@@ -652,6 +660,89 @@ struct Round {
         return true;
     }
 
+    // ---- a resident round's first half (one group): the events go up first, the seeding reads them in the arena and sends the hit counts
+    // home -- the one wait --, the arrays are sized by them, and the chaining is begun on seeds the device lays down itself: only the previous
+    // chains' anchors go up.  A round the chaining declines fetches the hits and is chained on the host, as device_begin's is.
+    void resident_begin(uint32_t gi)
+    {
+        Group &g = m->groups[gi]; RoundArrays &ra = g.buf[g.cur];
+        ra.carried = false; ra.round_id = id; ra.n_reads = ra.ks.size();
+        const size_t nr = ra.ks.size();
+        m->pool->run(nr, 64, [&](size_t i) { append_events(ra.ks[i]); });
+        uint64_t nev = 0, nseg = 0;
+        for (uint32_t k : ra.ks) { RoundRead &r = rr[k]; r.ev0 = nev; nev += r.ne; nseg += r.ne ? 1 : 0; }
+        if (!size_arrays(g, Sizes{nr, 0, 0, 0, nev, nseg, 0}, true)) return;
+        for (int b = 0; b < 2; b++) {
+            RoundArrays &x = g.buf[g.cur ^ b];
+            if (!(x.prev_off.ensure(g.hw_reads + 1, true) && x.ev_start.ensure(g.hw_reads + 1, true) && x.ev_len.ensure(g.hw_reads + 1, true) &&
+                  x.chunk_start.ensure(g.hw_reads + 1, true) && x.sits_out.ensure(g.hw_reads + 1, true)))
+                return failed(RAWDTW_ERR_OOM, "host allocation failed");
+        }
+        write_segments(ra, events_in_place);
+        m->pool->run(nr, 64, [&](size_t i) {
+            const uint32_t k = ra.ks[i];
+            const RoundRead &r = rr[k];
+            ra.ev_start[i] = (uint64_t)arena_base(read(k)) + r.ev_before;
+            ra.ev_len[i] = (uint32_t)r.ne;
+            if (r.ne && !events_in_place) memcpy(ra.new_events.p + r.ev0, events + event_off[k], r.ne * sizeof(float));
+        });
+        lap(0);
+        int st = RAWDTW_OK;
+        if (nseg && events_in_place) st = rawdtw_events_append(g.ctx, events, event_off[n_reads], (uint32_t)nr, event_off, ra.seg_dst.p);
+        else if (nseg) st = rawdtw_events_append(g.ctx, ra.new_events.p, nev, (uint32_t)nseg, ra.seg_src.p, ra.seg_dst.p);
+        if (st == RAWDTW_OK) st = rawdtw_seed_resident_begin(g.ctx, (uint32_t)nr, ra.ev_start.p, ra.ev_len.p, m->seed_off);
+        if (st == RAWDTW_OK) st = rawdtw_seed_resident_end(g.ctx, nullptr);
+        lap(2);
+        if (st != RAWDTW_OK) return failed(st, rawdtw_last_error(g.ctx));
+        const uint64_t *hoff = m->seed_off; // (chunk i is read ks[i]: one group, the round's reads in order)
+        uint64_t ns = 0, np = 0;
+        for (size_t i = 0; i < nr; i++) {
+            RoundRead &r = rr[ra.ks[i]];
+            const uint64_t pv = r.skipped ? 0 : seed_count(read(ra.ks[i]), 0);
+            r.seed0 = np; np += pv;
+            r.n_seeds = r.skipped ? 0 : pv + (hoff[i + 1] - hoff[i]);
+            ns += r.n_seeds;
+        }
+        if (!size_arrays(g, Sizes{nr, 0, 0, 0, nev, nseg, ns}, true)) return; // (the seed list's size: room for the round's anchors coming back)
+        uint64_t at = 0;
+        for (size_t i = 0; i < nr; i++) { const RoundRead &r = rr[ra.ks[i]]; ra.seed_off[i] = at; ra.prev_off[i] = r.seed0; at += r.n_seeds; }
+        ra.seed_off[nr] = ns; ra.prev_off[nr] = np;
+        m->pool->run(nr, 64, [&](size_t i) {
+            const uint32_t k = ra.ks[i];
+            const RoundRead &r = rr[k];
+            ra.read_base[i] = arena_base(read(k));
+            ra.chunk_start[i] = r.chunk_start;
+            ra.sits_out[i] = r.skipped ? 1 : 0;
+            if (!r.skipped) write_seeds(read(k), nullptr, 0, 0, ra.seeds.p + r.seed0); // (the previous chains' anchors only)
+        });
+        lap(0);
+        st = rawdtw_chain_round_begin_resident(g.ctx, &m->opt.chain, nr, ra.seed_off.p, ra.prev_off.p, ra.seeds.p, ra.chunk_start.p, ra.sits_out.p, ra.read_base.p,
+                                               (uint32_t)m->ref_off.size(), m->ref_off.data(), ra.chain_off.p, ra.anchor_off.p, ra.recs.p, g.hw_chains, ra.anchors.p);
+        lap(2);
+        if (st == RAWDTW_ERR_UNSUPPORTED) { // a read above the device's cap on seeds: nothing was enqueued
+            m->timing[6] += (double)(nev * sizeof(float));
+            if (fetch_resident_hits(gi)) host_round(gi, nullptr, true);
+            return;
+        }
+        if (st != RAWDTW_OK) return failed(st, rawdtw_last_error(g.ctx));
+        res_prev = np;
+        // (beside the chaining's own arrays: prev_off, chunk_start, sits_out; the seeding's offsets and source starts)
+        per[gi] = PerGroup{true, np, nev, nseg, 0, 0, (nr + 1) * 8 + nr * 5 + (nr + 1) * 8 + nr * 8};
+    }
+
+    // the fall-back of a resident round: its hits to the host, once, where host_round reads them
+    bool fetch_resident_hits(uint32_t gi)
+    {
+        const uint64_t tot = m->seed_off[n_reads];
+        if (seed_buffer(m, &m->seed_hits, &m->seed_hits_cap, tot + 1) != RAWDTW_OK) { failed(RAWDTW_ERR_OOM, "no page-locked memory for the round's hits"); return false; }
+        const int st = rawdtw_seed_resident_fetch(m->groups[gi].ctx, m->seed_hits, m->seed_hits_cap);
+        if (st != RAWDTW_OK) { failed(st, rawdtw_last_error(m->groups[gi].ctx)); return false; }
+        hit_off = m->seed_off; hits = m->seed_hits;
+        fell_back = true; res_hits = tot;
+        lap(2);
+        return true;
+    }
+
     // second half: the wait, the DTW submission straight from the device's arrays, and -- while that batch runs -- the round's chains per read, as
     // the host phase would have left them; a round the device declined (a read with too many chains, or an order only std::sort knows) is
     // chained on the host.  After a failure elsewhere the chaining begun is discarded.
@@ -665,14 +756,19 @@ struct Round {
         const size_t nr = ra.ks.size();
         const rawdtw_anchor_t *d_anchors = nullptr; const uint64_t *d_ref_base = nullptr; const uint32_t *d_read_base = nullptr;
         int st = rawdtw_chain_round_end(g.ctx, &d_anchors, &d_ref_base, &d_read_base);
-        if (st == RAWDTW_ERR_UNSUPPORTED) { lap(2); return host_round(gi, nullptr, true); }
+        if (st == RAWDTW_ERR_UNSUPPORTED) {
+            lap(2);
+            if (resident) { m->timing[6] += (double)(p.nev * sizeof(float)); if (!fetch_resident_hits(gi)) return; }
+            return host_round(gi, nullptr, true);
+        }
         if (st != RAWDTW_OK) return failed(st, rawdtw_last_error(g.ctx));
         const uint64_t nc = ra.chain_off[nr], na = ra.anchor_off[nc];
         ra.n_chains = nc; ra.n_anchors = na;
-        st = rawdtw_batch_submit_device(g.ctx, &m->opt.align, nr, ra.chain_off.p, ra.anchor_off.p, d_anchors, d_ref_base, d_read_base, &ra.batch);
+        // (a resident round of a mapper that runs no DTW -- neither EVALUATE_CHAINS nor LOG_SCORES -- ends with the chains: rmap.cpp:509)
+        if (runs_dtw) st = rawdtw_batch_submit_device(g.ctx, &m->opt.align, nr, ra.chain_off.p, ra.anchor_off.p, d_anchors, d_ref_base, d_read_base, &ra.batch);
         if (st != RAWDTW_OK) return failed(st, rawdtw_last_error(g.ctx));
         m->timing[6] += (double)(p.nev * sizeof(float));
-        m->timing[7] += (double)(p.ns * sizeof(rawdtw_seed_t) + (nr + 1) * 16 + nr * 4 + (nc + 1) * 8 + p.nseg * 12);
+        m->timing[7] += (double)(p.ns * sizeof(rawdtw_seed_t) + (nr + 1) * 16 + nr * 4 + (nc + 1) * 8 + p.nseg * 12 + p.extra);
         lap(2);
         m->pool->run(nr, 32, [&](size_t i) {
             RoundRead &r = rr[ra.ks[i]];
@@ -861,6 +957,11 @@ struct Round {
     void commit()
     {
         m->rounds = id;
+        if (resident) {
+            if (fell_back) { m->res_fallbacks++; m->res_hit_bytes += res_hits * sizeof(rawdtw_seed_hit_t); }
+            else m->res_rounds++;
+            m->res_seed_bytes += res_prev * sizeof(rawdtw_seed_t);
+        }
         for (uint32_t gi = 0; gi < G; gi++) {
             Group &g = m->groups[gi];
             RoundArrays &ra = g.buf[g.cur], &pb = g.buf[g.cur ^ 1];
@@ -1022,24 +1123,21 @@ int rawdtw_mapper_log(const rawdtw_mapper *m, const char **text)
     return RAWDTW_OK;
 }
 
-int rawdtw_mapper_round(rawdtw_mapper *m, uint32_t n_reads, const uint32_t *read_ids, const uint64_t *event_off, const float *events,
-                        const uint64_t *hit_off, const rawdtw_seed_hit_t *hits)
+} // extern "C"
+
+namespace {
+
+// a round's reads, every one checked before anything changes (`hit_off` null: a resident round, whose hits the host never sees)
+int check_round(rawdtw_mapper *m, uint32_t n_reads, const uint32_t *read_ids, const uint64_t *event_off, const uint64_t *hit_off, const rawdtw_seed_hit_t *hits)
 {
-    if (!m || (n_reads && (!read_ids || !event_off || !hit_off)) || (n_reads && event_off[n_reads] && !events) || (n_reads && hit_off[n_reads] && !hits))
-        return RAWDTW_ERR_INVALID;
-    if (n_reads == 0) return RAWDTW_OK;
-    const double t0 = now_ms(); // (the checks and the round's set-up count as host phase, its commit as round end: the five times add up to the call)
     const uint32_t n_seq = (uint32_t)m->seq_len.size();
-    const bool runs_dtw = (m->opt.flag & (0x2 | 0x8)) != 0; // rmap.cpp:509
-    if (runs_dtw && !m->scorer && !m->ctx) return fail(m, RAWDTW_ERR_NO_DEVICE, "a mapper without a context needs a scorer (rawdtw_mapper_set_scorer)");
-    // ---- every read is checked before anything changes ----
     const uint64_t stamp = m->rounds + 1;
     for (uint32_t k = 0; k < n_reads; k++) {
         if (read_ids[k] >= m->reads.size()) return fail(m, RAWDTW_ERR_INVALID, "unknown read id");
         MRead &rd = m->reads[read_ids[k]];
         bool dup = rd.seen_round == stamp;
         rd.seen_round = stamp;
-        if (dup || rd.finished || rd.released || event_off[k + 1] < event_off[k] || hit_off[k + 1] < hit_off[k]) {
+        if (dup || rd.finished || rd.released || event_off[k + 1] < event_off[k] || (hit_off && hit_off[k + 1] < hit_off[k])) {
             for (uint32_t q = 0; q <= k; q++) m->reads[read_ids[q]].seen_round = 0;
             return fail(m, RAWDTW_ERR_INVALID, dup ? "a read twice in one round" : rd.finished || rd.released ? "a finished read in a round" : "offsets do not ascend");
         }
@@ -1048,9 +1146,27 @@ int rawdtw_mapper_round(rawdtw_mapper *m, uint32_t n_reads, const uint32_t *read
     for (uint32_t k = 0; k < n_reads; k++) {
         const MRead &rd = m->reads[read_ids[k]];
         if ((uint64_t)rd.n_events + (event_off[k + 1] - event_off[k]) > m->opt.slot_events) return fail(m, RAWDTW_ERR_RANGE, "a read outgrew its slot in the event arena");
-        for (uint64_t h = hit_off[k]; h < hit_off[k + 1]; h++)
+        for (uint64_t h = hit_off ? hit_off[k] : 0; hit_off && h < hit_off[k + 1]; h++)
             if (hits[h].ref_seq >= n_seq) return fail(m, RAWDTW_ERR_INVALID, "seed hit on an unknown sequence");
     }
+    return RAWDTW_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int rawdtw_mapper_round(rawdtw_mapper *m, uint32_t n_reads, const uint32_t *read_ids, const uint64_t *event_off, const float *events,
+                        const uint64_t *hit_off, const rawdtw_seed_hit_t *hits)
+{
+    if (!m || (n_reads && (!read_ids || !event_off || !hit_off)) || (n_reads && event_off[n_reads] && !events) || (n_reads && hit_off[n_reads] && !hits))
+        return RAWDTW_ERR_INVALID;
+    if (n_reads == 0) return RAWDTW_OK;
+    const double t0 = now_ms(); // (the checks and the round's set-up count as host phase, its commit as round end: the five times add up to the call)
+    const bool runs_dtw = (m->opt.flag & (0x2 | 0x8)) != 0; // rmap.cpp:509
+    if (runs_dtw && !m->scorer && !m->ctx) return fail(m, RAWDTW_ERR_NO_DEVICE, "a mapper without a context needs a scorer (rawdtw_mapper_set_scorer)");
+    const int chk = check_round(m, n_reads, read_ids, event_off, hit_off, hits);
+    if (chk != RAWDTW_OK) return chk;
     Round r{m, n_reads, read_ids, event_off, events, hit_off, hits, t0};
     r.deal();
     for (uint32_t gi = 0; gi < r.G && r.ok(); gi++) r.begin_group(gi); // (with device chaining: every group's begun before the first is ended)
@@ -1098,6 +1214,54 @@ int rawdtw_mapper_round_seeded(rawdtw_mapper *m, const rawdtw_seed_index *six, u
         }
     }
     return rawdtw_mapper_round(m, n_reads, read_ids, event_off, events, m->seed_off, m->seed_hits);
+}
+
+// rawdtw_mapper_round_seeded with the hits left on the device: the events are appended, the seeding reads them in the arena, and the
+// chaining's seed list is written where the chaining reads it.  Everything it cannot do is refused before anything changes.
+int rawdtw_mapper_round_seeded_resident(rawdtw_mapper *m, const rawdtw_seed_index *six, uint32_t n_reads, const uint32_t *read_ids,
+                                        const uint64_t *event_off, const float *events)
+{
+    if (!m || !six || (n_reads && (!read_ids || !event_off)) || (n_reads && event_off[n_reads] > event_off[0] && !events)) return RAWDTW_ERR_INVALID;
+    uint32_t six_seq = 0;
+    rawdtw_seed_pars_t pars;
+    if (rawdtw_seed_index_info(six, &six_seq, nullptr, nullptr, nullptr, &pars) != RAWDTW_OK) return RAWDTW_ERR_INVALID;
+    if (six_seq != m->seq_len.size()) return fail(m, RAWDTW_ERR_INVALID, "the seed index and the mapper hold different numbers of sequences");
+    if (!m->ctx || m->scorer || !m->opt.device_chain || m->groups.size() != 1 || pars.w != 0)
+        return fail(m, RAWDTW_ERR_UNSUPPORTED, "a resident round needs a context, device chaining, one read group, no external scorer and a w == 0 index "
+                                               "(rawdtw_mapper_round_seeded maps the round)");
+    if (n_reads == 0) return RAWDTW_OK;
+    const double t0 = now_ms();
+    const int chk = check_round(m, n_reads, read_ids, event_off, nullptr, nullptr);
+    if (chk != RAWDTW_OK) return chk;
+    if (!m->seed_off && !m->seed_hits) m->seed_pinned = true;
+    if (seed_buffer(m, &m->seed_off, &m->seed_off_cap, (uint64_t)n_reads + 1) != RAWDTW_OK) return fail(m, RAWDTW_ERR_OOM, "no memory for the round's hit offsets");
+    const int up = rawdtw_seed_index_upload(m->ctx, six);
+    // (the one thing the upload refuses here: a seeding somebody began on the mapper's context and has not ended)
+    if (up == RAWDTW_ERR_INVALID) return fail(m, RAWDTW_ERR_UNSUPPORTED, rawdtw_last_error(m->ctx));
+    if (up != RAWDTW_OK) return fail(m, up, rawdtw_last_error(m->ctx));
+    Round r{m, n_reads, read_ids, event_off, events, nullptr, nullptr, t0};
+    r.resident = true;
+    // (seeding and chaining run on the device whether or not a DTW follows them: the round's arrays are the device path's, page-locked)
+    r.on_device = true;
+    r.events_in_place = event_off[n_reads] > 0 && rawdtw_host_is_page_locked(events) == 1;
+    r.deal();
+    r.resident_begin(0);
+    r.end_device_chain(0);
+    r.fetch_and_end(0);
+    if (!r.ok()) return r.rollback();
+    r.commit();
+    return RAWDTW_OK;
+}
+
+int rawdtw_mapper_resident_stats(const rawdtw_mapper *m, uint64_t *resident_rounds, uint64_t *fallback_rounds, uint64_t *hit_bytes_to_host,
+                                 uint64_t *seed_bytes_to_device)
+{
+    if (!m) return RAWDTW_ERR_INVALID;
+    if (resident_rounds) *resident_rounds = m->res_rounds;
+    if (fallback_rounds) *fallback_rounds = m->res_fallbacks;
+    if (hit_bytes_to_host) *hit_bytes_to_host = m->res_hit_bytes;
+    if (seed_bytes_to_device) *seed_bytes_to_device = m->res_seed_bytes;
+    return RAWDTW_OK;
 }
 
 // --dtw-output-cigar (rmap.cpp:715-717): the best chain of every mapped read through DTW_global_tb once more, its path as the

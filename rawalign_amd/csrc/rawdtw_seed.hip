@@ -16,6 +16,13 @@
 //                  reference: a repeat gives one element thousands of positions, which one lane must not write alone).  One
 //                  16-byte store a hit -- into device memory, or straight into the caller's page-locked array.  Nothing is
 //                  written unless the round's total fits.
+// A RESIDENT seeding (rawdtw_seed_resident_begin) runs filter, probe and scan on events that are in the context's event arena already
+// (a source start a chunk, apart from the dense workspace offset) and stops there: the hit counts go home, the per-element words
+// stay in the workspace.  Two launches read them afterwards:
+//   k_seed_write        on request (rawdtw_seed_resident_fetch): the 16-byte hits, as above
+//   k_seed_write_chain  k_seed_write's shape, but what it lays down is the chaining's seed list (rmap.cpp:385-391 as the mapper's
+//                       write_seeds restates it): 12-byte {sequence * 2 + strand, target, query + the chunk's start} records straight
+//                       into rawdtw_chain.hip's workspace, behind the read's previous anchors -- the hits never exist in host memory
 #include "rawdtw_capi.h"
 #include "rawdtw_seed.h"
 
@@ -33,6 +40,7 @@ constexpr uint32_t kNone = ~0u;
 
 struct SeedArgs {
     const uint64_t *off; // n + 1 event offsets, rebased to the uploaded events (off[0] = 0)
+    const uint64_t *src; // resident: per chunk, where its events start in `ev` (the event arena); else unused (they start at off[k])
     const float *ev;
     uint32_t *code, *pos; // per chunk, dense from off[k]: the kept events' codes and positions
     uint32_t *kept;       // per chunk
@@ -59,8 +67,8 @@ __device__ __forceinline__ uint64_t lane_u64(uint64_t x, int c)
     return ((uint64_t)hi << 32) | lo;
 }
 
-// rsketch.c:242-247
-__global__ __launch_bounds__(64) void k_seed_filter(SeedArgs a)
+// rsketch.c:242-247.  kSrc: the chunks' events are read from a.src[k] on (the event arena) rather than from the dense offset.
+template <bool kSrc> __global__ __launch_bounds__(64) void k_seed_filter(SeedArgs a)
 {
     __shared__ float tx[kW * kPad];
     __shared__ uint32_t tr[kW * kPad];
@@ -71,6 +79,7 @@ __global__ __launch_bounds__(64) void k_seed_filter(SeedArgs a)
     uint32_t len = 0;
     if (lane < nc) { b = a.off[me]; len = (uint32_t)(a.off[me + 1] - b); }
     sb[lane] = b; sl[lane] = len;
+    if (kSrc && lane < nc) b = a.src[me]; // (from here on b is where the lane's chunk is READ; the dense offsets are in sb)
     const uint32_t most = wave_max(len);
     float last = 0.0f;
     uint32_t rank = 0;
@@ -214,6 +223,64 @@ __global__ __launch_bounds__(64) void k_seed_write(SeedArgs a, uint64_t bound, u
     }
 }
 
+// ---- the hits as the chaining's seed list ----
+struct ChainDst {
+    rawdtw_seed_t *seeds;          // the chaining workspace's seed list
+    const uint64_t *seed_off;      // n + 1: read k's stretch
+    const uint64_t *prev_off;      // n + 1: read k's previous anchors in `prev`, dense
+    const rawdtw_seed_t *prev;
+    const uint32_t *chunk_start;   // per read: reg->offset before this chunk (rmap.cpp:574)
+    const uint8_t *sits_out;       // per read: the chunk is below min_events -- nothing is written (rmap.cpp:569-572)
+};
+
+__device__ __forceinline__ rawdtw_seed_t seed_of(uint64_t y, uint32_t query)
+{
+    return rawdtw_seed_t{(uint32_t)(y >> 32) * 2u + (uint32_t)(y & 1), (uint32_t)(y >> 1) & 0x7fffffffu, query}; // rmap.cpp:387-391
+}
+
+// A wave a read: its previous anchors from the dense upload into the front of its stretch, then chunk k's hits behind them, placed as
+// k_seed_write places them.  The host has checked seed_off[k + 1] - seed_off[k] == previous + hits against the counts this seeding
+// sent home, so every store is inside the read's own stretch.
+__global__ __launch_bounds__(64) void k_seed_write_chain(SeedArgs a, ChainDst d)
+{
+    const uint32_t k = blockIdx.x, lane = threadIdx.x;
+    if (d.sits_out[k]) return;
+    const uint64_t p0 = d.prev_off[k];
+    const uint32_t np = (uint32_t)(d.prev_off[k + 1] - p0);
+    rawdtw_seed_t *dst = d.seeds + d.seed_off[k];
+    for (uint32_t i = lane; i < np; i += kW) dst[i] = d.prev[p0 + i];
+    if (!a.chits[k]) return;
+    dst += np;
+    const uint32_t kept = a.kept[k], start = d.chunk_start[k];
+    const uint64_t b = a.off[k];
+    uint64_t run = 0;
+    for (uint32_t r0 = 0; r0 < kept; r0 += kW) { // (the same trip count in every lane)
+        const uint32_t r = r0 + lane;
+        const uint32_t c = r < kept ? a.cnt[b + r] : 0u;
+        const uint64_t v = r < kept ? a.val[b + r] : 0ull;
+        const uint32_t query = r < kept ? a.pos[b + r] + start : 0u;
+        uint64_t incl = c;
+#pragma unroll
+        for (int o = 1; o < (int)kW; o <<= 1) {
+            const uint64_t t = lane_u64(incl, (int)((lane - (uint32_t)o) & (kW - 1)));
+            if (lane >= (uint32_t)o) incl += t;
+        }
+        const uint64_t at = run + incl - c;
+        if (c == 1) dst[at] = seed_of(v, query);
+        else if (c <= kOwn)
+            for (uint32_t s = 0; s < c; s++) dst[at + s] = seed_of(a.list[v + s], query);
+        unsigned long long longs = __ballot(c > kOwn);
+        while (longs) { // a long list: all 64 lanes, 64 consecutive 12-byte stores a step
+            const int l = __ffsll(longs) - 1;
+            longs &= longs - 1;
+            const uint32_t lc = (uint32_t)__shfl((int)c, l), lquery = (uint32_t)__shfl((int)query, l);
+            const uint64_t lv = lane_u64(v, l), lat = lane_u64(at, l);
+            for (uint32_t s = lane; s < lc; s += kW) dst[lat + s] = seed_of(a.list[lv + s], lquery);
+        }
+        run += lane_u64(incl, kW - 1);
+    }
+}
+
 struct SeedWs {
     // the table (rawdtw_seed_index_upload)
     uint64_t table_serial = 0; // the uploaded index's serial (0: none): the same index again is not uploaded twice
@@ -237,6 +304,11 @@ struct SeedWs {
     uint64_t *h_hoff = nullptr;
     rawdtw_seed_hit_t *h_hits = nullptr;
     const uint64_t *d_hoff = nullptr;
+    // a resident seeding: begun (pending && resident), then ended and readable (ready) until the context's next seeding of either kind
+    bool resident = false, ready = false;
+    SeedArgs ra{};                // the launches' arguments: where the retained words are
+    uint64_t r_total = 0;
+    const uint64_t *r_hoff = nullptr; // n + 1 hit offsets, the library's own host copy (in `pin`)
 };
 
 // the device address of a page-locked host array of `bytes` bytes, or null (rawdtw_events.hip's rule: pageable memory, or an
@@ -292,6 +364,7 @@ int rawdtw_seed_index_upload(rawdtw_ctx *ctx, const rawdtw_seed_index *six)
     if (w->d_slots) (void)hipFree(w->d_slots);
     if (w->d_list) (void)hipFree(w->d_list);
     w->d_slots = nullptr; w->d_list = nullptr; w->has_table = false; w->table_serial = 0;
+    w->ready = false; // (an ended resident seeding's list words point into the table that went)
     HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&w->d_slots), std::max<size_t>(six->slots.size(), 1) * sizeof(Slot)));
     HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&w->d_list), std::max<size_t>(six->pos.size(), 1) * 8));
     if (!six->slots.empty()) HIP_TRY(ctx, hipMemcpyAsync(w->d_slots, six->slots.data(), six->slots.size() * sizeof(Slot), hipMemcpyHostToDevice, ctx->stream));
@@ -322,6 +395,7 @@ int rawdtw_seed_begin(rawdtw_ctx *ctx, uint32_t n_chunks, const uint64_t *event_
     if (w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "a seeding is begun on this context and not ended");
     if (w.pars.w) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, "the minimizer sketch (w > 0) is seeded on the host (rawdtw_seed_hits_host)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    w.ready = false; w.resident = false; // (the workspace is this seeding's from here on: an ended resident seeding's words are gone)
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     // offsets, events, codes, positions, counts (4 bytes an event each) and list words (8): 24 bytes an event
     const size_t b_off = al((n + 1) * 8), b_ev = al(N * 4), b_val = al(N * 8), b_cnt = al(n * 4), b_tot = al(32);
@@ -387,7 +461,7 @@ int rawdtw_seed_begin(rawdtw_ctx *ctx, uint32_t n_chunks, const uint64_t *event_
         hipMemcpyAsync(d_ev, events + event_off[0], N * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemsetAsync(a.tot, 0, 32, s) != hipSuccess || hipEventRecord(w.ev0, s) != hipSuccess)
         return undo(hip_fail(ctx, hipGetLastError(), "seeding upload"));
-    hipLaunchKernelGGL(k_seed_filter, dim3((uint32_t)((n + kW - 1) / kW)), dim3(kW), 0, s, a);
+    hipLaunchKernelGGL(k_seed_filter<false>, dim3((uint32_t)((n + kW - 1) / kW)), dim3(kW), 0, s, a);
     hipLaunchKernelGGL(k_seed_probe, dim3(n_chunks), dim3(kW), 0, s, a);
     hipLaunchKernelGGL(k_seed_scan, dim3(1), dim3(1024), 0, s, a.chits, n_chunks, a.hoff, a.tot, dv_hoff);
     if (hits_cap) hipLaunchKernelGGL(k_seed_write, dim3(n_chunks), dim3(kW), 0, s, a, hits_cap, dv_hits ? dv_hits : static_cast<uint4 *>(w.d_hits));
@@ -403,6 +477,7 @@ int rawdtw_seed_end(rawdtw_ctx *ctx, float *kernel_ms)
 {
     if (!ctx) return RAWDTW_ERR_INVALID;
     if (!ctx->seed_ws || !ctx->seed_ws->w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "no seeding begun on this context");
+    if (ctx->seed_ws->w.resident) return fail(ctx, RAWDTW_ERR_INVALID, "the seeding begun on this context is a resident one (rawdtw_seed_resident_end)");
     SeedWs &w = ctx->seed_ws->w;
     w.pending = false;
     if (kernel_ms) *kernel_ms = 0.0f;
@@ -427,9 +502,158 @@ int rawdtw_seed_end(rawdtw_ctx *ctx, float *kernel_ms)
     return RAWDTW_OK;
 }
 
+// ---- resident seeding: the events are in the arena, the hits stay in the workspace ----
+int rawdtw_seed_resident_begin(rawdtw_ctx *ctx, uint32_t n_chunks, const uint64_t *ev_start, const uint32_t *ev_len, uint64_t *hit_off)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (!hit_off || (n_chunks && (!ev_start || !ev_len))) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    if (n_chunks >= 0x7fffffffu) return fail(ctx, RAWDTW_ERR_INVALID, "2^31 chunks or more");
+    SeedWs *wp = ctx->seed_ws ? &ctx->seed_ws->w : nullptr;
+    if (!wp || !wp->has_table) return fail(ctx, RAWDTW_ERR_INVALID, "no seed index on this context (rawdtw_seed_index_upload)");
+    SeedWs &w = *wp;
+    if (w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "a seeding is begun on this context and not ended");
+    if (w.pars.w) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, "the minimizer sketch (w > 0) is seeded on the host (rawdtw_seed_hits_host)");
+    const uint64_t n = n_chunks;
+    uint64_t N = 0;
+    for (uint64_t k = 0; k < n; k++) {
+        if (ev_len[k] && (!ctx->d_ev || ev_start[k] > ctx->n_ev || ctx->n_ev - ev_start[k] < ev_len[k]))
+            return fail(ctx, RAWDTW_ERR_RANGE, "a chunk outside the context's event arena");
+        N += ev_len[k];
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    w.ready = false; w.resident = false;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    // as rawdtw_seed_begin's block without the events: offsets, source starts, codes, positions, counts (4 bytes an event each), list words (8)
+    const size_t b_off = al((n + 1) * 8), b_ev = al(N * 4), b_val = al(N * 8), b_cnt = al(n * 4), b_tot = al(32);
+    const size_t need = 4 * b_off + 3 * b_ev + b_val + b_cnt + b_tot;
+    if (w.dev_bytes < need) {
+        if (w.dev) (void)hipFree(w.dev);
+        w.dev = nullptr; w.dev_bytes = 0;
+        const size_t want = need + need / 4;
+        if (hipMalloc(&w.dev, want) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, RAWDTW_ERR_OOM, "seeding workspace allocation failed"); }
+        w.dev_bytes = want;
+    }
+    // pinned: [0] the total; the dense offsets and the source starts going up; the hit offsets coming home
+    const size_t pin_need = (3 * (n + 1) + 4) * 8;
+    if (w.pin_bytes < pin_need) {
+        if (w.pin) (void)hipHostFree(w.pin);
+        w.pin = nullptr; w.pin_bytes = 0;
+        const size_t want = pin_need + pin_need / 4;
+        if (hipHostMalloc(reinterpret_cast<void **>(&w.pin), want, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError(); w.pin = nullptr;
+            return fail(ctx, RAWDTW_ERR_OOM, "pinned allocation failed");
+        }
+        w.pin_bytes = want;
+    }
+    if (!w.ev0) HIP_TRY(ctx, hipEventCreate(&w.ev0));
+    if (!w.ev1) HIP_TRY(ctx, hipEventCreate(&w.ev1));
+    if (!w.done) HIP_TRY(ctx, hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
+    uint64_t *h_off = w.pin + 2, *h_src = h_off + (n + 1), *h_hoff = h_src + (n + 1);
+    h_off[0] = 0;
+    for (uint64_t k = 0; k < n; k++) { h_off[k + 1] = h_off[k] + ev_len[k]; h_src[k] = ev_start[k]; }
+    for (uint64_t k = 0; k <= n; k++) h_hoff[k] = 0;
+    w.pin[0] = 0;
+    w.pending = true; w.resident = true; w.n = n_chunks; w.n_events = N; w.cap = 0;
+    w.h_hoff = hit_off; w.h_hits = nullptr; w.direct_off = w.direct_hits = false;
+    w.r_hoff = h_hoff; w.r_total = 0;
+    if (n == 0) return RAWDTW_OK; // (nothing to enqueue)
+    char *p = static_cast<char *>(w.dev);
+    SeedArgs a{};
+    uint64_t *d_off = reinterpret_cast<uint64_t *>(p); p += b_off;
+    uint64_t *d_src = reinterpret_cast<uint64_t *>(p); p += b_off;
+    a.code = reinterpret_cast<uint32_t *>(p); p += b_ev;
+    a.pos = reinterpret_cast<uint32_t *>(p); p += b_ev;
+    a.cnt = reinterpret_cast<uint32_t *>(p); p += b_ev;
+    a.val = reinterpret_cast<uint64_t *>(p); p += b_val;
+    a.kept = reinterpret_cast<uint32_t *>(p); p += b_cnt;
+    a.chits = reinterpret_cast<uint64_t *>(p); p += b_off;
+    a.hoff = reinterpret_cast<uint64_t *>(p); p += b_off;
+    a.tot = reinterpret_cast<uint64_t *>(p);
+    a.off = d_off; a.src = d_src; a.ev = ctx->d_ev; a.n = n_chunks;
+    a.e = w.pars.e; a.q = w.pars.q; a.lq = w.pars.lq;
+    a.slots = w.d_slots; a.list = w.d_list; a.log2_slots = w.log2_slots;
+    w.ra = a; w.d_hoff = a.hoff;
+    hipStream_t s = ctx->stream;
+    auto undo = [&](int st) { w.pending = false; w.resident = false; return st; };
+    if (hipMemcpyAsync(d_off, h_off, (n + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(d_src, h_src, n * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemsetAsync(a.tot, 0, 32, s) != hipSuccess || hipEventRecord(w.ev0, s) != hipSuccess)
+        return undo(hip_fail(ctx, hipGetLastError(), "seeding upload"));
+    hipLaunchKernelGGL(k_seed_filter<true>, dim3((uint32_t)((n + kW - 1) / kW)), dim3(kW), 0, s, a);
+    hipLaunchKernelGGL(k_seed_probe, dim3(n_chunks), dim3(kW), 0, s, a);
+    hipLaunchKernelGGL(k_seed_scan, dim3(1), dim3(1024), 0, s, a.chits, n_chunks, a.hoff, a.tot, static_cast<uint64_t *>(nullptr));
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(w.ev1, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_hoff, a.hoff, (n + 1) * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipEventRecord(w.done, s);
+    if (e != hipSuccess) return undo(hip_fail(ctx, e, "seeding launches"));
+    return RAWDTW_OK;
+}
+
+int rawdtw_seed_resident_end(rawdtw_ctx *ctx, float *kernel_ms)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (!ctx->seed_ws || !ctx->seed_ws->w.pending || !ctx->seed_ws->w.resident)
+        return fail(ctx, RAWDTW_ERR_INVALID, "no resident seeding begun on this context");
+    SeedWs &w = ctx->seed_ws->w;
+    w.pending = false; w.resident = false;
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if (w.n) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipEventSynchronize(w.done));
+        if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, w.ev0, w.ev1));
+    }
+    for (uint64_t k = 0; k <= w.n; k++) w.h_hoff[k] = w.r_hoff[k];
+    w.r_total = w.r_hoff[w.n];
+    w.ready = true;
+    return RAWDTW_OK;
+}
+
+int rawdtw_seed_resident_fetch(rawdtw_ctx *ctx, rawdtw_seed_hit_t *hits, uint64_t hits_cap)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    SeedWs *wp = ctx->seed_ws ? &ctx->seed_ws->w : nullptr;
+    if (!wp || !wp->ready || wp->pending) return fail(ctx, RAWDTW_ERR_INVALID, "no ended resident seeding on this context");
+    SeedWs &w = *wp;
+    const uint64_t tot = w.r_total;
+    if (tot > hits_cap) return fail(ctx, RAWDTW_ERR_RANGE, "hits_cap is below the seeding's hits");
+    if (tot == 0) return RAWDTW_OK;
+    if (!hits) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint4 *dv = static_cast<uint4 *>(device_view(hits, tot * sizeof(rawdtw_seed_hit_t)));
+    if (!dv && w.hits_bytes < tot * sizeof(rawdtw_seed_hit_t)) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // (an earlier seeding's copy may still read the old array)
+        if (w.d_hits) (void)hipFree(w.d_hits);
+        w.d_hits = nullptr; w.hits_bytes = 0;
+        if (hipMalloc(&w.d_hits, tot * sizeof(rawdtw_seed_hit_t)) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, RAWDTW_ERR_OOM, "no device memory for the hits"); }
+        w.hits_bytes = tot * sizeof(rawdtw_seed_hit_t);
+    }
+    hipStream_t s = ctx->stream;
+    hipLaunchKernelGGL(k_seed_write, dim3(w.n), dim3(kW), 0, s, w.ra, tot, dv ? dv : static_cast<uint4 *>(w.d_hits));
+    HIP_TRY(ctx, hipGetLastError());
+    if (!dv) HIP_TRY(ctx, hipMemcpyAsync(hits, w.d_hits, tot * sizeof(rawdtw_seed_hit_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    return RAWDTW_OK;
+}
+
 } // extern "C"
 
 namespace rawdtw { namespace capi {
+const uint64_t *seed_resident_hit_off(const rawdtw_ctx *ctx, uint64_t *n_chunks)
+{
+    const SeedWs *w = ctx && ctx->seed_ws ? &ctx->seed_ws->w : nullptr;
+    if (!w || !w->ready || w->pending) return nullptr;
+    *n_chunks = w->n;
+    return w->r_hoff;
+}
+
+void seed_resident_write_chain(rawdtw_ctx *ctx, rawdtw_seed_t *d_seeds, const uint64_t *d_seed_off, const uint64_t *d_prev_off, const rawdtw_seed_t *d_prev,
+                               const uint32_t *d_chunk_start, const uint8_t *d_sits_out)
+{
+    const SeedWs &w = ctx->seed_ws->w;
+    hipLaunchKernelGGL(k_seed_write_chain, dim3(w.n), dim3(kW), 0, ctx->stream, w.ra, ChainDst{d_seeds, d_seed_off, d_prev_off, d_prev, d_chunk_start, d_sits_out});
+}
+
 void seed_ws_free(rawdtw_ctx *ctx)
 {
     if (!ctx || !ctx->seed_ws) return;

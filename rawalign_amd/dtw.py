@@ -114,6 +114,24 @@ class Plan:
             pass
 
 
+class ResidentSeeding:
+    """An ended resident seeding of an Engine (Engine.seed_resident): its hit offsets; the hits are on the device."""
+
+    def __init__(self, engine, hit_off, kernel_ms):
+        self.engine, self.hit_off, self.kernel_ms = engine, hit_off, kernel_ms
+
+    def fetch(self, pinned: bool = True):
+        """the hits as seeding.HIT_DTYPE, in rawdtw_seed_begin's order (valid until the engine's next seeding)"""
+        from .events import PinnedArray
+        from .seeding import HIT_DTYPE
+
+        n = int(self.hit_off[-1])
+        keep = PinnedArray(n, HIT_DTYPE) if pinned else None
+        hits = keep.array if pinned else np.zeros(max(n, 1), HIT_DTYPE)
+        self.engine._check(self.engine.lib.rawdtw_seed_resident_fetch(self.engine._ctx, hits.ctypes.data, n))
+        return hits[:n].copy()
+
+
 class Engine:
     """One rawdtw_ctx (one HIP device, one stream)."""
 
@@ -306,6 +324,30 @@ class Engine:
                 raise err
             out = (hoff[:n + 1].copy(), hits[:int(hoff[n])].copy())
             return out + (float(ms.value),) if kernel_ms else out
+
+    def reserve_events(self, n_floats: int):
+        """rawdtw_events_reserve: the event arena grown to n_floats (contents kept)"""
+        self._check(self.lib.rawdtw_events_reserve(self._ctx, int(n_floats)))
+
+    def append_events(self, new_events, seg_src_off, seg_dst_off):
+        """rawdtw_events_append, waited for: new_events[seg_src_off[s] .. seg_src_off[s+1]) to arena offset seg_dst_off[s]"""
+        ev, src, dst = _f32(new_events), np.ascontiguousarray(seg_src_off, np.uint64), np.ascontiguousarray(seg_dst_off, np.uint32)
+        self._check(self.lib.rawdtw_events_append(self._ctx, _ptr(ev), len(ev), len(dst), _ptr(src), _ptr(dst)))
+        self.sync()
+
+    def seed_resident(self, ev_start, ev_len, kernel_ms: bool = False):
+        """Chunk k = the event arena's ev_len[k] events from ev_start[k] on, seeded where they are (rawdtw_seed_resident_begin, then
+        _end): only the hit counts come home.  Returns a ResidentSeeding -- hit_off, kernel_ms, and fetch() for the hits themselves
+        (rawdtw_seed_resident_fetch), which stay on the device until this context's next seeding."""
+        start, ln = np.ascontiguousarray(ev_start, np.uint64), np.ascontiguousarray(ev_len, np.uint32)
+        n = len(ln)
+        if len(start) != n:
+            raise ValueError("ev_start and ev_len differ in length")
+        hoff = np.zeros(n + 1, np.uint64)
+        ms = C.c_float()
+        self._check(self.lib.rawdtw_seed_resident_begin(self._ctx, n, _ptr(start), _ptr(ln), _ptr(hoff)))
+        self._check(self.lib.rawdtw_seed_resident_end(self._ctx, C.byref(ms)))
+        return ResidentSeeding(self, hoff, float(ms.value))
 
     # -- batches ----------------------------------------------------------------
     def plan(self, jobs) -> Plan:

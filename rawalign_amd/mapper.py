@@ -570,15 +570,19 @@ class CMapper:
         """one chunk round from flat arrays (read_ids u32, event_off / hit_off u64, events f32, hits HIT_DTYPE)"""
         self._check(self.lib.rawdtw_mapper_round(self._h, len(read_ids), _vp(read_ids), _vp(event_off), _vp(events), _vp(hit_off), _vp(hits)))
 
-    def round(self, read_ids, chunks, seed_index=None):
+    def round(self, read_ids, chunks, seed_index=None, resident=False):
         """chunks[k] = (events, hits as (seq, strand, target, query) tuples) of read read_ids[k].  With `seed_index` (a
-        seeding.SeedIndex) the library seeds the round itself (rawdtw_mapper_round_seeded) and the chunks' hits are not looked at."""
+        seeding.SeedIndex) the library seeds the round itself (rawdtw_mapper_round_seeded) and the chunks' hits are not looked at;
+        with `resident` too the hits stay on the device (rawdtw_mapper_round_seeded_resident: device chaining, one group)."""
         ids = np.ascontiguousarray(read_ids, np.uint32)
+        if resident and seed_index is None:
+            raise ValueError("a resident round needs a seed_index")
         if seed_index is not None:
             eoff = np.zeros(len(ids) + 1, np.uint64)
             eoff[1:] = np.cumsum([len(c[0]) for c in chunks])
             ev = np.concatenate([np.ascontiguousarray(c[0], np.float32) for c in chunks] + [np.zeros(1, np.float32)])
-            self._check(self.lib.rawdtw_mapper_round_seeded(self._h, seed_index._h, len(ids), _vp(ids), _vp(eoff), _vp(ev)))
+            fn = self.lib.rawdtw_mapper_round_seeded_resident if resident else self.lib.rawdtw_mapper_round_seeded
+            self._check(fn(self._h, seed_index._h, len(ids), _vp(ids), _vp(eoff), _vp(ev)))
             return
         eoff = np.zeros(len(ids) + 1, np.uint64)
         hoff = np.zeros(len(ids) + 1, np.uint64)
@@ -629,6 +633,14 @@ class CMapper:
         r, s, u = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._check(self.lib.rawdtw_mapper_stats(self._h, C.byref(r), C.byref(s), C.byref(u)))
         return r.value, s.value, u.value
+
+    def resident_stats(self):
+        """rawdtw_mapper_resident_stats: rounds that stayed resident, rounds that fell back, bytes of hits fetched, bytes of seeds sent up"""
+        import ctypes as C
+
+        v = [C.c_uint64() for _ in range(4)]
+        self._check(self.lib.rawdtw_mapper_resident_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(resident_rounds=v[0].value, fallback_rounds=v[1].value, hit_bytes_to_host=v[2].value, seed_bytes_to_device=v[3].value)
 
     def timing(self):
         t = np.zeros(8, np.float64)
@@ -724,7 +736,7 @@ class CMapper:
             self._h = None
 
 
-def map_reads_c(seeds, read_ids, cm: CMapper, batch_size=None, su=None, seed_index=None):
+def map_reads_c(seeds, read_ids, cm: CMapper, batch_size=None, su=None, seed_index=None, resident=False):
     """map_reads through the library's mapper: chunk rounds until every read stopped; the PAF lines in read order, the rounds.
 
     The reads go in mini-batches of `batch_size` (None: one of all of them), at most two at a time -- the next batch's reads are
@@ -732,7 +744,8 @@ def map_reads_c(seeds, read_ids, cm: CMapper, batch_size=None, su=None, seed_ind
     `cm`, every batch is closed in input order once all its reads are finished: through CMapper.su_batch, or -- when `su`, a
     host-side state with the interface of mapping.SequenceUntil (CSequenceUntil), is given -- through the split form a multi-rank
     host uses (batch_records, the walk of shard.sequence_until_round, su_apply).  After the stop no read is added; a read
-    without a line (sequence-until dropped it, or it was never added) has "" in the list."""
+    without a line (sequence-until dropped it, or it was never added) has "" in the list.  `resident` (with `seed_index`): the
+    rounds leave their hits on the device (CMapper.round)."""
     from . import shard
 
     read_ids = list(read_ids)
@@ -780,7 +793,7 @@ def map_reads_c(seeds, read_ids, cm: CMapper, batch_size=None, su=None, seed_ind
         if seed_index is None:
             cm.round(act, chunks)
         else:
-            cm.round(act, chunks, seed_index=seed_index)   # (the library seeds: seeds.chunk's hits are not used)
+            cm.round(act, chunks, seed_index=seed_index, resident=resident)   # (the library seeds: seeds.chunk's hits are not used)
         rounds += 1
     st = cm.finish()
     if st != 0:
