@@ -90,6 +90,9 @@ int rawdtw_sync(rawdtw_ctx *ctx);
  *   "debug_skip_kinds": timing experiments only -- launches of the masked kinds are not issued (results wrong)
  * The environment variable RAWDTW_OPTS="name=value,..." applies options at rawdtw_create. */
 int rawdtw_set_option(rawdtw_ctx *ctx, const char *name, int64_t value);
+/* The value of an option that callers pass on from one context to another ("chain_long_seeds": rawdtw_mapper_create gives its second
+ * group's context the first one's).  RAWDTW_ERR_INVALID for any other name. */
+int rawdtw_get_option(const rawdtw_ctx *ctx, const char *name, int64_t *value);
 /* the ctx's hipStream_t, as void* (for event timing on the stream kernels run on) */
 int rawdtw_stream(rawdtw_ctx *ctx, void **stream);
 /* the device ordinal the context was created on */
@@ -374,9 +377,15 @@ int rawdtw_sort_by_chaining_score(const float *chaining_score, uint32_t n_chains
  *   out (device, the context's, valid until its next rawdtw_chain_round): *d_anchors, *d_ref_base, *d_read_base
  * The call returns when the host arrays are filled.  Results equal rawdtw_chain_anchors list by list and
  * rawdtw_sort_by_chaining_score read by read, bit for bit.  RAWDTW_ERR_UNSUPPORTED (the out arrays hold nothing of use): a read with more than
- * 2 048 seeds, with more than 32 chains, or with more than 16 chains two of which have equal scores (std::sort's order of
- * equal elements is an insertion sort's only up to 16) -- chain that round on the host.  RAWDTW_ERR_INVALID: a chain on a key
- * that is not below n_keys. */
+ * 2 048 seeds (with the option below: more than its value), with more than 32 chains, or with more than 16 chains two of which have
+ * equal scores (std::sort's order of equal elements is an insertion sort's only up to 16) -- chain that round on the host.
+ * RAWDTW_ERR_INVALID: a chain on a key that is not below n_keys.
+ *   rawdtw_set_option(ctx, "chain_long_seeds", N)  0 (the default): as above.  N > 0 (at most 1 << 20): a read with more than 2 048 and at
+ *        most N seeds no longer declines the round; it is chained by a second path that keeps its state in device memory (21 bytes a seed
+ *        of the context's workspace), with the same results.  A read above N declines the round in _begin, before anything is enqueued;
+ *        the limits on chains decline it in _end, as without the option.
+ *   rawdtw_chain_round_stats  cumulative, a context: rounds begun, the reads and the seeds that second path chained, and its 64-candidate
+ *        steps that read a candidate from device memory because it lay behind the path's window in LDS.  Any pointer may be NULL. */
 typedef struct { uint32_t key, target_position, query_position; } rawdtw_seed_t;                       /* 12 bytes */
 typedef struct { float chaining_score; uint32_t key, start_position, end_position, n_anchors; } rawdtw_chain_rec_t; /* 20 bytes */
 int rawdtw_chain_round(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads, const uint64_t *seed_off,
@@ -394,6 +403,7 @@ int rawdtw_chain_round_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uin
                              rawdtw_anchor_t *anchors);
 int rawdtw_chain_round_end(rawdtw_ctx *ctx, const rawdtw_anchor_t **d_anchors, const uint64_t **d_ref_base,
                            const uint32_t **d_read_base);
+int rawdtw_chain_round_stats(const rawdtw_ctx *ctx, uint64_t *rounds, uint64_t *long_reads, uint64_t *long_seeds, uint64_t *far_steps);
 
 /* Batched forms over many reads (what rmap.cpp's per-read worker does for every read of a
  * mini-batch, hoisted around one GPU submission).  Chains are listed read by read, each read's
@@ -838,7 +848,8 @@ int rawdtw_mapper_round_seeded(rawdtw_mapper *m, const rawdtw_seed_index *six, u
  *       into seed_off[r] ..; a read with sits_out[r] != 0 (its chunk is below min_events, rmap.cpp:569-572) gets nothing and must
  *       have an empty stretch and no previous seeds.  RAWDTW_ERR_INVALID: no ended resident seeding, n_reads other than its
  *       chunks, or a seed_off stretch that is not previous + hits.  Caps, RAWDTW_ERR_UNSUPPORTED and rawdtw_chain_round_end as for
- *       rawdtw_chain_round_begin; the arrays must stay valid until _end.
+ *       rawdtw_chain_round_begin -- with "chain_long_seeds" at N a read of more than 2 048 and at most N seeds is chained on the device
+ *       here too, from the seeds the device laid down, and only a read above N declines the round; the arrays must stay valid until _end.
  *   rawdtw_mapper_round_seeded_resident  rawdtw_mapper_round_seeded through the three above: append the events, seed from the
  *       arena, size the round by hit_off, chain, and from there the unchanged round.  Only for a mapper that chains on the
  *       device (device_chain, a context, no scorer; with or without a DTW stage) with one read group and a w == 0 index: anything else is

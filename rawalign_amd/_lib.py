@@ -270,6 +270,8 @@ SYMBOLS = {
     "rawdtw_chain_round_begin_resident": (I32, [VP, C.POINTER(ChainOpt), U64, VP, VP, VP, VP, VP, VP, U32, VP, VP, VP, VP, U64, VP]),
     "rawdtw_mapper_round_seeded_resident": (I32, [VP, VP, U32, VP, VP, VP]),
     "rawdtw_mapper_resident_stats": (I32, [VP, VP, VP, VP, VP]),
+    "rawdtw_chain_round_stats": (I32, [VP, VP, VP, VP, VP]),
+    "rawdtw_get_option": (I32, [VP, C.c_char_p, C.POINTER(C.c_int64)]),
 }
 
 

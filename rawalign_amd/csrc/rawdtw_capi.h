@@ -146,6 +146,7 @@ struct rawdtw_ctx {
     struct rawdtw_detect_ws *detect_ws = nullptr; // rawdtw_detect_begin's device block (rawdtw_events.hip), grow-only
     struct rawdtw_seed_ws *seed_ws = nullptr;     // rawdtw_seed_index_upload's table and rawdtw_seed_begin's device block (rawdtw_seed.hip), grow-only
     uint32_t chain_max_seeds = 0; // tests: RAWDTW_CHAIN_MAX_SEEDS lowers rawdtw_chain_round's cap on seeds a read, so that small rounds take the declined path (0: no)
+    uint32_t chain_long_seeds = 0; // "chain_long_seeds": reads above the cap with at most this many seeds are chained by rawdtw_chain.hip's long path (0: declined)
     std::string err;
 };
 

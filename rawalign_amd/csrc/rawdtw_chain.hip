@@ -23,11 +23,17 @@
 // What the device declines (the caller chains that round on the host, same results): a read with more seeds than the wave's piece of LDS
 // holds (2 048), more than 32 chains, or more than 16 chains with two equal scores among them (std::sort's order of equal elements is its
 // own beyond 16; up to 16 it is an insertion sort and stable).
+//
+// THE LONG PATH ("chain_long_seeds", off by default).  A read above the wave's piece of LDS is chained with its state in device memory: a
+// workgroup sorts its seeds into scratch (k_chain_sort_long), then a wave runs the same DP over them (k_chain_long) with the trailing window of
+// candidates in an LDS ring and everything older read back from scratch.  Same results, same flags; with the option on only a read above the
+// option's value still declines the round.
 #include "rawdtw_capi.h"
 
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
 namespace rawdtw {
 namespace {
@@ -235,6 +241,278 @@ __global__ __launch_bounds__(64) void k_chain(const ChainArgs a)
     }
 }
 
+// ---- the long path: reads above k_chain's cap, state in device memory ----
+// Scratch a long seed: K1 8 + Q 4 (the sorted seeds), SC 4 + PR 4 + FL 1 (the DP's state) = 21 bytes; a read's stretch starts on a multiple of
+// 64 elements (at most 63 * 21 bytes of padding a read) and each of the five arrays on a multiple of 256 bytes.
+constexpr uint32_t kSortBlock = 4096;   // elements sorted in LDS at a time: 48 KiB
+constexpr uint32_t kRing = 1024;        // the DP's LDS ring: 12 bytes an entry
+constexpr uint32_t kNear = kRing - 64;  // candidates at most this far behind the current anchor are read from the ring (see k_chain_long)
+
+struct LongRead { uint32_t r, pad; uint64_t off; }; // the read, and where its stretch of the scratch arrays starts (in elements)
+struct LongArgs {
+    const LongRead *reads;
+    unsigned long long *K1; // key << 32 | target, sorted
+    uint32_t *Q;
+    float *SC;
+    uint32_t *PR;
+    unsigned char *FL;
+    unsigned long long *far_steps; // the round's totals[4]
+};
+
+__device__ __forceinline__ void sort_cmp(unsigned long long &ka, uint32_t &qa, unsigned long long &kb, uint32_t &qb)
+{
+    if (ka > kb || (ka == kb && qa > qb)) { const unsigned long long k = ka; ka = kb; kb = k; const uint32_t q = qa; qa = qb; qb = q; }
+}
+// the workgroup's writes to device memory, for its own later reads: the waves share the CU's L1, the agent-scope fences are belt and braces
+__device__ __forceinline__ void wg_global_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+}
+
+// A workgroup a long read: rmap.cpp:396-401, ascending by (key, target, query), into the read's stretch of K1 / Q.  A bitonic network whose
+// comparators all point upwards (each merge starts with the mirrored step i <-> i ^ (k - 1), then half-cleaners i <-> i + j), so that any n
+// sorts as if padded with +infinity behind it: a comparator whose upper element is at or past n would find infinity there and is left out.
+// Merges up to 4 096 elements, and the tail of every wider merge, run on blocks in LDS; the wider steps run in device memory.
+__global__ __launch_bounds__(256) void k_chain_sort_long(const ChainArgs a, const LongArgs la)
+{
+    __shared__ unsigned long long s_k[kSortBlock];
+    __shared__ uint32_t s_q[kSortBlock];
+    const LongRead lr = la.reads[blockIdx.x];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t s0 = a.seed_off[lr.r];
+    const uint32_t n = (uint32_t)(a.seed_off[lr.r + 1] - s0);
+    unsigned long long *K1 = la.K1 + lr.off;
+    uint32_t *Q = la.Q + lr.off;
+    for (uint32_t b0 = 0; b0 < n; b0 += kSortBlock) {
+        for (uint32_t i = tid; i < kSortBlock; i += 256) {
+            if (b0 + i < n) { const rawdtw_seed_t s = a.seeds[s0 + b0 + i]; s_k[i] = ((unsigned long long)s.key << 32) | s.target_position; s_q[i] = s.query_position; }
+            else { s_k[i] = ~0ull; s_q[i] = ~0u; }
+        }
+        __syncthreads();
+        for (uint32_t k = 2; k <= kSortBlock; k <<= 1)
+            for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+                for (uint32_t t = tid; t < kSortBlock / 2; t += 256) {
+                    const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = (j == (k >> 1)) ? (i ^ (k - 1)) : (i | j);
+                    sort_cmp(s_k[i], s_q[i], s_k[p], s_q[p]);
+                }
+                __syncthreads();
+            }
+        for (uint32_t i = tid; i < kSortBlock && b0 + i < n; i += 256) { K1[b0 + i] = s_k[i]; Q[b0 + i] = s_q[i]; }
+        __syncthreads();
+    }
+    if (n <= kSortBlock) return;
+    uint32_t n2 = kSortBlock;
+    while (n2 < n) n2 <<= 1;
+    wg_global_sync();
+    for (uint32_t k = 2 * kSortBlock; k <= n2; k <<= 1) {
+        for (uint32_t j = k >> 1; j >= kSortBlock; j >>= 1) {
+            for (uint32_t t = tid; t < n2 / 2; t += 256) {
+                const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = (j == (k >> 1)) ? (i ^ (k - 1)) : (i | j);
+                if (p < n) { // (i < p)
+                    unsigned long long ka = K1[i], kb = K1[p];
+                    uint32_t qa = Q[i], qb = Q[p];
+                    if (ka > kb || (ka == kb && qa > qb)) { K1[i] = kb; K1[p] = ka; Q[i] = qb; Q[p] = qa; }
+                }
+            }
+            wg_global_sync();
+        }
+        for (uint32_t b0 = 0; b0 < n; b0 += kSortBlock) { // the half-cleaners below the block size
+            for (uint32_t i = tid; i < kSortBlock; i += 256) {
+                if (b0 + i < n) { s_k[i] = K1[b0 + i]; s_q[i] = Q[b0 + i]; }
+                else { s_k[i] = ~0ull; s_q[i] = ~0u; }
+            }
+            __syncthreads();
+            for (uint32_t j = kSortBlock >> 1; j > 0; j >>= 1) {
+                for (uint32_t t = tid; t < kSortBlock / 2; t += 256) {
+                    const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                    sort_cmp(s_k[i], s_q[i], s_k[i | j], s_q[i | j]);
+                }
+                __syncthreads();
+            }
+            for (uint32_t i = tid; i < kSortBlock && b0 + i < n; i += 256) { K1[b0 + i] = s_k[i]; Q[b0 + i] = s_q[i]; }
+            __syncthreads();
+        }
+        wg_global_sync();
+    }
+}
+
+// A wave a long read: k_chain's DP, ends, traceback and order over the sorted seeds in scratch.
+//   * The anchors come 64 at a time into registers (lane l: anchor blk + l) and, with their targets and queries, into the LDS ring at slot
+//     index & (kRing - 1); an anchor's score joins its slot when it is final.  Loading a block overwrites the slots of anchors blk - kRing ..
+//     blk - kRing + 63, so the ring is good for candidates no more than kNear = kRing - 64 behind the current anchor.
+//   * SC, PR and FL of a block are kept in registers and go to scratch when the block (or the list) ends: `flushed` anchors are in scratch.
+//   * A candidate further back than kNear -- reached only through a run of pass-over candidates longer than that -- is read from scratch:
+//     the far path.  It is at least kNear - 63 > 0 anchors behind the last flush, so what it reads was stored by this wave at least one flush
+//     earlier; every flush ends in an agent-scope release (the stores are complete at L2 before the wave goes on), and the scores, the only
+//     array of the three that this launch wrote, are loaded with agent-scope atomic loads, which do not take a line from L1.  That holds for
+//     any kRing >= 128, not by the distance of 960.
+//   * Ends and traceback read and mark scratch: a release and an acquire at agent scope stand between lane 0's marks and the wave's next look.
+__global__ __launch_bounds__(64) void k_chain_long(const ChainArgs a, const LongArgs la)
+{
+    __shared__ uint32_t r_t[kRing], r_q[kRing];
+    __shared__ float r_s[kRing];
+    __shared__ ChainRecDev s_rec[kChainCap];
+    __shared__ uint32_t s_perm[kChainCap];
+    const LongRead lr = la.reads[blockIdx.x];
+    const uint32_t lane = threadIdx.x, r = lr.r;
+    const uint64_t s0 = a.seed_off[r];
+    const uint32_t n = (uint32_t)(a.seed_off[r + 1] - s0);
+    const unsigned long long *K1 = la.K1 + lr.off;
+    const uint32_t *Q = la.Q + lr.off;
+    float *SC = la.SC + lr.off;
+    uint32_t *PR = la.PR + lr.off;
+    unsigned char *FL = la.FL + lr.off;
+    if (n == 0) { if (lane == 0) a.cnt[r] = ChainCnt{0u, 0u, 0u, 0u}; return; }
+    auto slot = [](const uint32_t i) { return i & (kRing - 1); };
+    const rawdtw_chain_opt_t &o = a.opt;
+    const float e_f = (float)o.e;
+    float maxs = 0.0f;
+    uint32_t nc = 0, na = 0, flags = 0, far = 0, flushed = 0;
+    uint32_t b_t = 0, b_q = 0, b_pr = 0, b_fl = 0; // this lane's anchor of the current block, and its state
+    float b_sc = 0.0f;
+    auto flush = [&](const uint32_t upto) { // anchors [flushed, upto) -- inside one block -- to scratch
+        const uint32_t x = (flushed & ~63u) + lane;
+        if (x >= flushed && x < upto) { SC[x] = b_sc; PR[x] = b_pr; FL[x] = (unsigned char)b_fl; }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        flushed = upto;
+    };
+    for (uint32_t g0 = 0; g0 < n;) {
+        // the (sequence, strand) list [g0, g1)
+        const uint32_t key = (uint32_t)(K1[g0] >> 32);
+        uint32_t g1 = n;
+        for (uint32_t i = g0; i < n; i += 64) {
+            const uint32_t x = i + lane;
+            const unsigned long long diff = __ballot(x < n && (uint32_t)(K1[x < n ? x : g0] >> 32) != key);
+            if (diff) { g1 = i + (uint32_t)__builtin_ctzll(diff); break; }
+        }
+        // ---- rmap.cpp:436-494 ----
+        for (uint32_t ai = g0; ai < g1; ai++) {
+            if (ai == 0 || (ai & 63u) == 0) { // the next block: registers and ring
+                const uint32_t x = ai + lane;
+                if (x < n) { b_t = (uint32_t)K1[x]; b_q = Q[x]; r_t[slot(x)] = b_t; r_q[slot(x)] = b_q; }
+                lds_sync();
+            }
+            const int32_t ct = (int32_t)lane_of(b_t, ai & 63u), cq = (int32_t)lane_of(b_q, ai & 63u);
+            float best = e_f;
+            uint32_t pred = ai;
+            int32_t skips = 0;
+            const int32_t lo = (ai - g0 > (uint32_t)o.chaining_band_length) ? (int32_t)ai - o.chaining_band_length : (int32_t)g0;
+            for (int32_t base = (int32_t)ai - 1; base >= lo; base -= 64) {
+                const int32_t pi = base - (int32_t)lane;
+                const bool valid = pi >= lo;
+                const uint32_t x = (uint32_t)(valid ? pi : lo);
+                const bool is_far = x + kNear < ai;
+                int32_t pt, pq;
+                float sp;
+                if (!is_far) { pt = (int32_t)r_t[slot(x)]; pq = (int32_t)r_q[slot(x)]; sp = r_s[slot(x)]; }
+                else { pt = (int32_t)(uint32_t)K1[x]; pq = (int32_t)Q[x]; sp = __hip_atomic_load(SC + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+                if (__ballot(valid && is_far)) far++;
+                const bool pass12 = pq == cq || pt == ct;                                   // rmap.cpp:458-459
+                const bool stop_gap = valid && !pass12 && pt + o.max_target_gap_length < ct; // rmap.cpp:460
+                const int32_t td = ct - pt, qd = cq - pq;
+                const bool active = valid && !pass12 && !stop_gap && qd >= 0;               // rmap.cpp:467
+                float cur = 0.0f;
+                {
+                    const float matching = (float)min(min(td, qd), o.e);                    // rmap.cpp:469
+                    const int gap = abs(td - qd);
+                    const float scale = td > 0 ? __fdiv_rn((float)qd, (float)td) : 1.0f;
+                    if (gap < o.max_gap_length && scale < 5.0f && scale > 0.75f) cur = sp + matching; // rmap.cpp:474-476
+                }
+                const float cv = active ? cur : -1.0f;
+                const float incl = scan_max(cv);
+                const float before = fmaxf(best, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, -1.0f), __builtin_bit_cast(int, incl), 0x138, 0xf, 0xf, false)));
+                const bool improver = active && cur > before;                               // rmap.cpp:478
+                const int32_t moves = scan_add(improver ? -1 : (active ? 1 : 0));
+                const bool stop_skip = active && !improver && skips + moves > o.max_num_skips; // rmap.cpp:482-484
+                const unsigned long long stop = __ballot(!valid || stop_gap || stop_skip);
+                const uint32_t first = stop ? (uint32_t)__builtin_ctzll(stop) : 64u;
+                const unsigned long long live = first >= 64u ? ~0ull : ((1ull << first) - 1ull);
+                const unsigned long long imp = __ballot(improver) & live;
+                if (imp) { // (the improvers' values ascend: the last one stands)
+                    const uint32_t last = 63u - (uint32_t)__builtin_clzll(imp);
+                    best = __builtin_bit_cast(float, lane_of(__builtin_bit_cast(uint32_t, cur), last));
+                    pred = (uint32_t)(base - (int32_t)last);
+                }
+                if (first > 0) skips += (int32_t)lane_of((uint32_t)moves, first - 1u);
+                if (first < 64u) break;
+            }
+            if (best > maxs) maxs = best;                                                   // rmap.cpp:486-488
+            const bool is_end = o.disable_score_filtering || (best >= o.min_chaining_score && best > maxs / 2); // rmap.cpp:489-493
+            if (lane == (ai & 63u)) { b_sc = best; b_pr = pred; b_fl = is_end ? 2u : 0u; }
+            if (lane == 0) r_s[slot(ai)] = best;
+            lds_sync();
+            if ((ai & 63u) == 63u) flush(ai + 1);
+        }
+        if (flushed < g1) flush(g1);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        // ---- the num_best_chains best ends (rmap.cpp:175-179: score descending, then index descending), traceback_chains ----
+        for (int k = 0; k < o.num_best_chains; k++) {
+            unsigned long long top = 0;
+            for (uint32_t i = g0 + lane; i < g1; i += 64)
+                if ((FL[i] & 6) == 2) top = max(top, (1ull << 63) | ((unsigned long long)__builtin_bit_cast(uint32_t, SC[i]) << 32) | i); // (scores are positive: their bits ascend with them)
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(top >> 32), d), lw = (uint32_t)__shfl_xor((int)(uint32_t)top, d);
+                top = max(top, ((unsigned long long)hi << 32) | lw);
+            }
+            if (!(top >> 63)) break;
+            const uint32_t end = (uint32_t)top;
+            bool below = false;
+            if (lane == 0) {
+                FL[end] |= 4;
+                if (!(FL[end] & 1)) {
+                    const uint64_t out0 = s0 + na;
+                    uint32_t cur = end, len = 1;
+                    bool stop_at_used = false;
+                    a.tmp_anchors[out0] = rawdtw_anchor_t{(uint32_t)K1[cur], Q[cur]};
+                    if (PR[cur] != cur && (FL[PR[cur]] & 1)) stop_at_used = true;
+                    FL[cur] |= 1;
+                    while (PR[cur] != cur && !(FL[PR[cur]] & 1)) {
+                        cur = PR[cur];
+                        a.tmp_anchors[out0 + len] = rawdtw_anchor_t{(uint32_t)K1[cur], Q[cur]};
+                        len++;
+                        if (PR[cur] != cur && (FL[PR[cur]] & 1)) stop_at_used = true;
+                        FL[cur] |= 1;
+                    }
+                    if (len >= (uint32_t)o.min_num_anchors) {
+                        float adj = SC[end];
+                        if (stop_at_used) adj -= SC[PR[cur]];
+                        if (nc < kChainCap) s_rec[nc] = ChainRecDev{adj, key, (uint32_t)K1[cur], (uint32_t)K1[end], len, na};
+                        else flags |= 2u;
+                        nc++; na += len;
+                    }
+                }
+                below = !o.disable_score_filtering && SC[end] < maxs / 2;                  // rmap.cpp:502-504
+            }
+            nc = uni(nc); na = uni(na); flags = uni(flags);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            lds_sync();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            if (uni(below ? 1u : 0u)) break;
+        }
+        g0 = g1;
+    }
+    // ---- rmap.cpp:512: by chaining score, descending; equal scores keep their order (std::sort up to 16 elements) ----
+    if (lane == 0) {
+        const uint32_t m = min(nc, kChainCap);
+        bool ties = false;
+        for (uint32_t i = 0; i < m; i++) {
+            const float v = s_rec[i].score;
+            uint32_t j = i;
+            while (j > 0 && v > s_rec[s_perm[j - 1]].score) { s_perm[j] = s_perm[j - 1]; j--; }
+            if (j > 0 && v == s_rec[s_perm[j - 1]].score) ties = true;
+            s_perm[j] = i;
+        }
+        if (nc > kChainStable && ties) flags |= 4u;
+        for (uint32_t i = 0; i < m; i++) a.tmp_recs[(uint64_t)r * kChainCap + i] = s_rec[s_perm[i]];
+        a.cnt[r] = ChainCnt{nc, na, flags, 0u};
+        if (far) atomicAdd(la.far_steps, (unsigned long long)far);
+    }
+}
+
+
 // the reads' chains and anchors before each read; the round's totals and its flags
 __global__ __launch_bounds__(1024) void k_chain_scan(const ChainCnt *__restrict__ cnt, const uint32_t n_reads, uint64_t *__restrict__ chain_off,
                                                      uint64_t *__restrict__ read_anchor0, uint64_t *__restrict__ totals /* chains, anchors, flags */)
@@ -301,7 +579,7 @@ struct ChainWs {
     hipEvent_t done = nullptr; // behind a round's last copy: what rawdtw_chain_round_end waits for (not for what the caller enqueued behind the round)
     // a round begun and not ended
     bool pending = false, direct = false;
-    uint64_t n_reads = 0, chains_cap = 0;
+    uint64_t n_reads = 0, chains_cap = 0, n_long = 0;
     uint64_t *h_anchor_off = nullptr;
     rawdtw_chain_rec_t *h_recs = nullptr;
     rawdtw_anchor_t *h_anchors = nullptr;
@@ -310,6 +588,9 @@ struct ChainWs {
     const rawdtw_anchor_t *d_anch = nullptr;
     const uint64_t *d_refb = nullptr;
     const uint32_t *d_rbc = nullptr;
+    // the long path: the round's long reads (kept here until the round's end: their upload reads them), and rawdtw_chain_round_stats' counters
+    std::vector<LongRead> long_reads;
+    uint64_t st_rounds = 0, st_long_reads = 0, st_long_seeds = 0, st_far_steps = 0;
 };
 
 } // namespace
@@ -360,13 +641,20 @@ int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint64_t n_seeds = seed_off[n_reads];
-    uint32_t most = 0;
+    const uint32_t seed_cap = ctx->chain_max_seeds ? std::min(kChainMaxSeeds, ctx->chain_max_seeds) : kChainMaxSeeds;
+    const uint64_t long_cap = ctx->chain_long_seeds; // ("chain_long_seeds"; 0: no long path)
+    uint32_t most = 0; // (of the reads k_chain takes)
+    uint64_t n_long = 0, long_elems = 0;
+    bool too_long = false;
     for (uint64_t r = 0; r < n_reads; r++) {
         if (seed_off[r + 1] < seed_off[r]) return fail(ctx, RAWDTW_ERR_INVALID, "offsets do not ascend");
-        most = (uint32_t)std::max<uint64_t>(most, std::min<uint64_t>(seed_off[r + 1] - seed_off[r], 0xffffffffull));
+        const uint64_t nr = seed_off[r + 1] - seed_off[r];
+        if (nr <= seed_cap) most = std::max(most, (uint32_t)nr);
+        else if (nr <= long_cap) { n_long++; long_elems += (nr + 63) & ~63ull; }
+        else too_long = true;
     }
-    const uint32_t seed_cap = ctx->chain_max_seeds ? std::min(kChainMaxSeeds, ctx->chain_max_seeds) : kChainMaxSeeds;
-    if (most > seed_cap) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, "a read has more seeds than the device chains (2048): chain this round on the host");
+    if (too_long) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, long_cap ? "a read has more seeds than \"chain_long_seeds\" allows: chain this round on the host"
+                                                                   : "a read has more seeds than the device chains (2048): chain this round on the host");
     uint32_t n2 = 64;
     while (n2 < most) n2 <<= 1;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -378,10 +666,22 @@ int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads
     // (a resident round: the previous anchors, dense, their offsets, the chunk starts and the sits-out flags, behind everything else)
     const size_t b_prev = res ? al((size_t)n_prev * sizeof(rawdtw_seed_t) + 16) : 0, b_poff = res ? al((n_reads + 1) * 8) : 0, b_cs = res ? al(n_reads * 4) : 0,
                  b_so = res ? al(n_reads) : 0;
-    const size_t need = b_soff + b_seeds + b_rb + b_kb + b_tmpa + b_trec + b_cnt + b_coff + b_ra0 + b_tot + b_aoff + b_anch + b_refb + b_rbc + b_recs + b_prev + b_poff + b_cs + b_so;
+    // (the long reads' list and their scratch, behind that: 21 bytes a seed -- K1 8, Q 4, SC 4, PR 4, FL 1 -- each read's stretch rounded up to 64 seeds)
+    const size_t b_lr = n_long ? al(n_long * sizeof(LongRead)) : 0, b_lk = n_long ? al(long_elems * 8) : 0, b_l4 = n_long ? al(long_elems * 4) : 0,
+                 b_l1 = n_long ? al(long_elems) : 0;
+    const size_t need = b_soff + b_seeds + b_rb + b_kb + b_tmpa + b_trec + b_cnt + b_coff + b_ra0 + b_tot + b_aoff + b_anch + b_refb + b_rbc + b_recs + b_prev + b_poff + b_cs + b_so +
+                        b_lr + b_lk + 3 * b_l4 + b_l1;
     if (!ctx->chain_ws) ctx->chain_ws = new (std::nothrow) rawdtw_chain_ws;
     if (!ctx->chain_ws) return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed");
     ChainWs &w = ctx->chain_ws->w;
+    if (n_long) {
+        try { w.long_reads.resize(n_long); } catch (const std::bad_alloc &) { return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed"); }
+        uint64_t k = 0, at = 0;
+        for (uint64_t r = 0; r < n_reads; r++) {
+            const uint64_t nr = seed_off[r + 1] - seed_off[r];
+            if (nr > seed_cap) { w.long_reads[k++] = LongRead{(uint32_t)r, 0u, at}; at += (nr + 63) & ~63ull; }
+        }
+    }
     if (w.dev_bytes < need) {
         if (w.dev) (void)hipFree(w.dev);
         w.dev = nullptr; w.dev_bytes = 0;
@@ -409,7 +709,15 @@ int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads
     rawdtw_seed_t *d_prev = reinterpret_cast<rawdtw_seed_t *>(p); p += b_prev;
     uint64_t *d_poff = reinterpret_cast<uint64_t *>(p); p += b_poff;
     uint32_t *d_cs = reinterpret_cast<uint32_t *>(p); p += b_cs;
-    uint8_t *d_so = reinterpret_cast<uint8_t *>(p);
+    uint8_t *d_so = reinterpret_cast<uint8_t *>(p); p += b_so;
+    LongArgs la{};
+    la.reads = reinterpret_cast<LongRead *>(p); p += b_lr;
+    la.K1 = reinterpret_cast<unsigned long long *>(p); p += b_lk;
+    la.Q = reinterpret_cast<uint32_t *>(p); p += b_l4;
+    la.SC = reinterpret_cast<float *>(p); p += b_l4;
+    la.PR = reinterpret_cast<uint32_t *>(p); p += b_l4;
+    la.FL = reinterpret_cast<unsigned char *>(p);
+    la.far_steps = reinterpret_cast<unsigned long long *>(d_tot) + 4;
     hipStream_t s = ctx->stream;
     HIP_TRY(ctx, hipMemcpyAsync(d_soff, seed_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, s));
     if (res) { // only the previous anchors go up; rawdtw_seed.hip's writer puts them and the hits in place
@@ -425,6 +733,12 @@ int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads
     ChainArgs a{d_soff, d_seeds, (uint32_t)n_reads, n2, *opt, d_tmpa, d_trec, d_cnt};
     const size_t lds = (size_t)n2 * 21 + 16;
     hipLaunchKernelGGL(k_chain, dim3((uint32_t)n_reads), dim3(64), lds, s, a);
+    if (n_long) { // behind k_chain, which has flagged these reads as too long for it: the long launch writes their cnt over that
+        HIP_TRY(ctx, hipMemcpyAsync(const_cast<LongRead *>(la.reads), w.long_reads.data(), n_long * sizeof(LongRead), hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemsetAsync(la.far_steps, 0, 8, s));
+        hipLaunchKernelGGL(k_chain_sort_long, dim3((uint32_t)n_long), dim3(256), 0, s, a, la);
+        hipLaunchKernelGGL(k_chain_long, dim3((uint32_t)n_long), dim3(64), 0, s, a, la);
+    }
     hipLaunchKernelGGL(k_chain_scan, dim3(1), dim3(1024), 0, s, d_cnt, (uint32_t)n_reads, d_coff, d_ra0, d_tot);
     // the caller's arrays: written by the compaction launch itself when they are page-locked (rawdtw_host_alloc) -- no copy command, no second
     // wait for sizes only the device knows; else copied at the round's end
@@ -438,11 +752,14 @@ int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads
                        direct ? anchor_off : nullptr, direct ? recs : nullptr, direct ? anchors : nullptr, chains_cap);
     HIP_TRY(ctx, hipGetLastError());
     uint64_t *h_tot = static_cast<uint64_t *>(w.pin);
-    HIP_TRY(ctx, hipMemcpyAsync(h_tot, d_tot, 32, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(h_tot, d_tot, n_long ? 40 : 32, hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipMemcpyAsync(chain_off, d_coff, (n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
     if (!w.done) HIP_TRY(ctx, hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
     HIP_TRY(ctx, hipEventRecord(w.done, s));
     w.pending = true; w.direct = direct; w.n_reads = n_reads; w.chains_cap = chains_cap;
+    w.n_long = n_long;
+    w.st_rounds++; w.st_long_reads += n_long;
+    for (uint64_t k = 0; k < n_long; k++) w.st_long_seeds += seed_off[w.long_reads[k].r + 1] - seed_off[w.long_reads[k].r];
     w.h_anchor_off = anchor_off; w.h_recs = recs; w.h_anchors = anchors;
     w.d_aoff = d_aoff; w.d_recs = d_recs; w.d_anch = d_anch; w.d_refb = d_refb; w.d_rbc = d_rbc;
     return RAWDTW_OK;
@@ -480,6 +797,7 @@ int rawdtw_chain_round_end(rawdtw_ctx *ctx, const rawdtw_anchor_t **d_anchors, c
     HIP_TRY(ctx, hipEventSynchronize(w.done)); // (the round's own work: what was enqueued behind it -- the caller's next uploads -- goes on)
     const uint64_t *h_tot = static_cast<const uint64_t *>(w.pin);
     const uint64_t nc = h_tot[0], na = h_tot[1], flags = h_tot[2];
+    if (w.n_long) w.st_far_steps += h_tot[4];
     if (h_tot[3]) return fail(ctx, RAWDTW_ERR_INVALID, "a seed's key is not below n_keys");
     if (flags) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, flags & 4 ? "a read with more than 16 chains, two of them with equal scores: chain this round on the host"
                                                                : "a read with more than 32 chains (or more seeds than the device chains): chain this round on the host");
@@ -491,6 +809,18 @@ int rawdtw_chain_round_end(rawdtw_ctx *ctx, const rawdtw_anchor_t **d_anchors, c
         HIP_TRY(ctx, hipStreamSynchronize(s));
     }
     *d_anchors = w.d_anch; *d_ref_base = w.d_refb; *d_read_base = w.d_rbc;
+    return RAWDTW_OK;
+}
+
+int rawdtw_chain_round_stats(const rawdtw_ctx *ctx, uint64_t *rounds, uint64_t *long_reads, uint64_t *long_seeds, uint64_t *far_steps)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    const ChainWs none;
+    const ChainWs &w = ctx->chain_ws ? ctx->chain_ws->w : none;
+    if (rounds) *rounds = w.st_rounds;
+    if (long_reads) *long_reads = w.st_long_reads;
+    if (long_seeds) *long_seeds = w.st_long_seeds;
+    if (far_steps) *far_steps = w.st_far_steps;
     return RAWDTW_OK;
 }
 

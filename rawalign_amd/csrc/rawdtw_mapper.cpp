@@ -1021,6 +1021,9 @@ int rawdtw_mapper_create(rawdtw_ctx *ctx, const rawdtw_mapper_opt_t *opt, uint32
         st = rawdtw_context_device(ctx, &dev);
         if (st == RAWDTW_OK) st = rawdtw_create(dev, &m->groups[1].ctx);
         if (st == RAWDTW_OK) { m->groups[1].own_ctx = true; st = rawdtw_share_reference(m->groups[1].ctx, ctx); }
+        int64_t chain_long = 0; // (both groups chain the same reads on the device)
+        if (st == RAWDTW_OK) st = rawdtw_get_option(ctx, "chain_long_seeds", &chain_long);
+        if (st == RAWDTW_OK) st = rawdtw_set_option(m->groups[1].ctx, "chain_long_seeds", chain_long);
     }
     const uint64_t per_group = ((uint64_t)opt->max_reads + (uint64_t)m->opt.groups - 1) / (uint64_t)m->opt.groups;
     for (Group &g : m->groups)

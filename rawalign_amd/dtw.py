@@ -176,6 +176,13 @@ class Engine:
     def set_option(self, name: str, value: int):
         self._check(self.lib.rawdtw_set_option(self._ctx, name.encode(), int(value)))
 
+    def chain_round_stats(self) -> dict:
+        """rawdtw_chain_round_stats: chaining rounds begun on this context, the reads and seeds its long path ("chain_long_seeds") chained, and
+        the long path's 64-candidate steps that read beyond its LDS ring -- cumulative"""
+        v = [C.c_uint64() for _ in range(4)]
+        self._check(self.lib.rawdtw_chain_round_stats(self._ctx, *[C.byref(x) for x in v]))
+        return dict(zip(("rounds", "long_reads", "long_seeds", "far_steps"), (int(x.value) for x in v)))
+
     def stream_handle(self) -> int:
         s = C.c_void_p()
         self._check(self.lib.rawdtw_stream(self._ctx, C.byref(s)))
