@@ -483,6 +483,15 @@ int rawdtw_batch_wide_ms(rawdtw_ctx *ctx, rawdtw_batch *batch, float *ms);
  * returns -1 for a name it does not know.  *n_out = 0 for a batch planned on the host. */
 int rawdtw_batch_stream_counter_index(const char *name);
 int rawdtw_batch_stream_counters(rawdtw_ctx *ctx, rawdtw_batch *batch, uint64_t *out, uint32_t cap, uint32_t *n_out);
+/* Diagnostics of a device-planned batch (waits for its planning kernels): how the tile launch's waves are filled.  A pass's
+ * sorted job records are taken in chunks (sixteen radius-3 records, four lanes a job; then 64 records a wave, the radius-1
+ * records from a chunk boundary of their own); a chunk runs the body its radii ask for, for as many columns as its longest
+ * job has.  out[4 c .. 4 c + 3] for body class c = 0 quad radius 3, 1 radius 2, 2 radii 1 and 2 mixed, 3 radius 1,
+ * 4 generic: jobs, chunks, the sum of the chunks' columns, the sum of the jobs' own columns; out[20] = passes.  Lane
+ * occupancy of a class = job columns / (64 (class 0: 16) x chunk columns).  flat_map != 0 counts the chunks cut every
+ * 64 records with no boundary at the first radius-1 record (the map of earlier versions), from the same records.
+ * *n_out = 0 for a batch planned on the host or declined by the stream path. */
+int rawdtw_batch_chunk_profile(rawdtw_ctx *ctx, rawdtw_batch *batch, int flat_map, uint64_t *out, uint32_t cap, uint32_t *n_out);
 int rawdtw_batch_destroy(rawdtw_batch *batch);
 /* ---- compact hand-over of the anchor lists.  A mini-batch's anchors are its largest array (8 bytes an anchor: as much
  * as the round's new events), and consecutive anchors of a chain differ by little: the chaining DP bounds the gaps

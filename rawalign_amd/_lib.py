@@ -208,6 +208,7 @@ SYMBOLS = {
     "rawdtw_batch_plan_ms": (I32, [VP, VP, C.POINTER(F32)]),
     "rawdtw_batch_wide_ms": (I32, [VP, VP, C.POINTER(F32)]),
     "rawdtw_batch_stream_counters": (I32, [VP, VP, VP, U32, VP]),
+    "rawdtw_batch_chunk_profile": (I32, [VP, VP, C.c_int, VP, U32, VP]),
     "rawdtw_batch_destroy": (I32, [VP]),
     "rawdtw_batch_submit": (I32, [VP, VP, U64, VP, VP, VP, VP, VP, VP]),
     "rawdtw_batch_submit_device": (I32, [VP, VP, U64, VP, VP, VP, VP, VP, VP]),

@@ -341,6 +341,25 @@ class Batch:
             raise RawDTWError(st, msg.value.decode())
         return bool(dev.value)
 
+    CHUNK_CLASSES = ("quad_r3", "lane_r2", "lane_r12", "lane_r1", "lane_gen")
+
+    def chunk_profile(self, flat_map: bool = False) -> dict:
+        """rawdtw_batch_chunk_profile: how the tile launch's waves are filled, per body class -- jobs, chunks, the chunks'
+        columns, the jobs' own columns, and the lane occupancy they give; {} for a batch not planned on the device.
+        flat_map: the chunks cut every 64 records with no boundary of their own for the radius-1 records."""
+        w = (C.c_uint64 * 21)()
+        n = C.c_uint32()
+        self.engine._check(self.engine.lib.rawdtw_batch_chunk_profile(self.engine._ctx, self._h, int(flat_map), w, 21, C.byref(n)))
+        if n.value != 21:
+            return {}
+        d = {"passes": int(w[20])}
+        for c, name in enumerate(self.CHUNK_CLASSES):
+            jobs, chunks, ccols, jcols = (int(w[4 * c + k]) for k in range(4))
+            lanes = 16 if c == 0 else 64
+            d[name] = {"jobs": jobs, "chunks": chunks, "chunk_columns": ccols, "job_columns": jcols,
+                       "occupancy": round(jcols / (lanes * ccols), 4) if ccols else None}
+        return d
+
     def run(self):
         if self._submitted:  # (a compact batch was enqueued by its submit call)
             self._submitted = False

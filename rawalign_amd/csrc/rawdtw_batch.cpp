@@ -641,9 +641,9 @@ int rawdtw_batch_verify_plan(rawdtw_ctx *ctx, const rawdtw_batch *batch, const r
             std::vector<uint4> ords(2 * kStreamMaxSeg);
             for (uint64_t q = 0; q < n_todo && e.empty(); q++) {
                 const uint4 t = todo[q];
-                const uint32_t nj = t.z & 0xffffu, nr = t.z >> 16, region = t.w & 0xffffu, rec0 = t.w >> 16;
-                if (t.x >= a.n_tiles || t.y >= a.n_slots || slot_used[t.y] || nj > kStreamTile || nr > kStreamMaxSeg || (nj && !nr) || (rec0 & 1u) || rec0 + nj > kStreamRecStride) {
-                    e = "work list entry " + S(q) + ": tile " + S(t.x) + ", slot " + S(t.y) + ", " + S(nj) + " jobs, " + S(nr) + " runs"; break;
+                const uint32_t nj = t.z & 0xffffu, nr = (t.z >> 16) & 63u, n_hi = t.z >> 22, region = t.w & 0xffffu, rec0 = t.w >> 16;
+                if (t.x >= a.n_tiles || t.y >= a.n_slots || slot_used[t.y] || nj > kStreamTile || nr > kStreamMaxSeg || (nj && !nr) || n_hi > nj || (rec0 & 1u) || rec0 + nj > kStreamRecStride) {
+                    e = "work list entry " + S(q) + ": tile " + S(t.x) + ", slot " + S(t.y) + ", " + S(nj) + " jobs, " + S(nr) + " runs, first radius-1 record " + S(n_hi); break;
                 }
                 slot_used[t.y] = 1;
                 if (!nj) continue;
@@ -656,7 +656,7 @@ int rawdtw_batch_verify_plan(rawdtw_ctx *ctx, const rawdtw_batch *batch, const r
                         e = "pass " + S(q) + " (tile " + S(t.x) + ", " + S(nj) + " jobs, " + S(nr) + " runs, event region " + S(region) + " of " + S(a.lds_floats) +
                             " floats): copy order " + S(o) + " = pieces [" + S(od.x) + ", " + S(od.y) + ") outside its region of the image";
                 }
-                uint32_t prev_bin = 0;
+                uint32_t prev_bin = 0, n_wide = 0; // (n_wide: the pass's records of radius >= 2 -- the entry's n_hi, where the chunks of k_runs change class)
                 for (uint32_t r = 0; r < nj && e.empty(); r++) {
                     const uint2 rc = recs[r];
                     const uint32_t N = rc.y & 127u, M = (rc.y >> 7) & 127u, R = (rc.y >> 14) & 3u, ex = (rc.y >> 16) & 1u, u = (rc.y >> 17) & (kStreamTile - 1u);
@@ -672,6 +672,9 @@ int rawdtw_batch_verify_plan(rawdtw_ctx *ctx, const rawdtw_batch *batch, const r
                     const uint32_t bin = (3u - R) * 64u + (63u - std::min(N, 63u));
                     if (bin < prev_bin) { e = who + ": out of the lanes' order"; break; }
                     prev_bin = bin;
+                    if (R >= 2u) n_wide++;
+                    else if (r < n_hi) { e = who + ": radius 1 ahead of the pass's first radius-1 record " + S(n_hi); break; }
+                    if (r >= n_hi && R != 1u) { e = who + ": radius " + S(R) + " at or behind the pass's first radius-1 record " + S(n_hi); break; }
                     const uint32_t p_long = rc.x & 0xffffu, p_short = rc.x >> 16;
                     const uint32_t p_ev = swap ? p_short : p_long, p_rf = swap ? p_long : p_short;
                     for (int w = 0; w < 2 && e.empty(); w++) {
@@ -687,6 +690,7 @@ int rawdtw_batch_verify_plan(rawdtw_ctx *ctx, const rawdtw_batch *batch, const r
                     }
                     tseen[k] = 1;
                 }
+                if (e.empty() && n_wide != n_hi) e = "pass " + S(q) + ": " + S(n_wide) + " records of radius >= 2, its entry says " + S(n_hi);
             }
             if (e.empty() && cnt[kCntReused] == 0) // (a round that took costs over leaves the carried parts out)
                 for (uint64_t k = 0; k < n_jobs && e.empty(); k++)
@@ -733,6 +737,55 @@ int rawdtw_batch_verify_plan(rawdtw_ctx *ctx, const rawdtw_batch *batch, const r
     }
     say(e);
     return e.empty() ? RAWDTW_OK : RAWDTW_ERR_DEVICE + 100;
+}
+
+int rawdtw_batch_chunk_profile(rawdtw_ctx *ctx, rawdtw_batch *batch, int flat_map, uint64_t *out, uint32_t cap, uint32_t *n_out)
+{
+    if (!ctx || !batch || batch->ctx != ctx || !n_out || batch_dead(batch)) return fail(ctx, RAWDTW_ERR_INVALID, "bad arguments to batch_chunk_profile");
+    *n_out = 0;
+    if (!batch->stream) return RAWDTW_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const int st = stream_counters(ctx, batch);
+    if (st != RAWDTW_OK) return st;
+    if (stream_declined(batch)) return RAWDTW_OK;
+    // The tile launch's chunks, counted from the plan as k_runs walks it (run_dp, stream_lane_job): per body class -- 0 quad_dp_r3,
+    // 1 lane_dp_r2, 2 lane_dp_r12, 3 lane_dp_r1, 4 lane_dp_gen -- jobs, chunks, the chunks' columns (a chunk runs for its longest
+    // side) and the jobs' own columns; word 20 the passes.
+    const StreamArgs &a = batch->sa;
+    const uint64_t n_first = batch->h_cnt[kCntTodo], n_pool = batch->h_cnt[kCntPool];
+    if (n_first > a.n_tiles || n_pool > a.n_slots - a.n_tiles) return fail(ctx, RAWDTW_ERR_DEVICE, "work list longer than the slots");
+    std::vector<uint4> todo(n_first + n_pool);
+    if (n_first) HIP_TRY(ctx, hipMemcpy(todo.data(), a.todo, n_first * sizeof(uint4), hipMemcpyDeviceToHost));
+    if (n_pool) HIP_TRY(ctx, hipMemcpy(todo.data() + n_first, a.todo + a.n_tiles, n_pool * sizeof(uint4), hipMemcpyDeviceToHost));
+    std::vector<uint2> recs((size_t)a.n_tiles * kStreamRecStride); // (one copy: a bench batch has ten thousand passes)
+    if (!recs.empty()) HIP_TRY(ctx, hipMemcpy(recs.data(), a.recs, recs.size() * sizeof(uint2), hipMemcpyDeviceToHost));
+    uint64_t w[21] = {0};
+    for (const uint4 &t : todo) {
+        const uint32_t nj = t.z & 0xffffu, rec0 = t.w >> 16;
+        if (t.x >= a.n_tiles || nj > kStreamTile || rec0 + nj > kStreamRecStride || (t.z >> 22) > nj) return fail(ctx, RAWDTW_ERR_DEVICE, "work list entry out of range");
+        if (!nj) continue;
+        const uint2 *rc = recs.data() + (size_t)t.x * kStreamRecStride + rec0;
+        uint32_t n3 = 0;
+        for (uint32_t r = 0; r < nj && r < 64u; r++) n3 += ((rc[r].y >> 14) & 3u) == 3u;
+        const uint32_t n_hi = flat_map ? nj : std::max(t.z >> 22, n3);
+        const uint32_t n_chunks = chunk_map_count(n3, n_hi, nj);
+        for (uint32_t c = 0; c < n_chunks; c++) {
+            const ChunkRange cr = chunk_map_range(n3, n_hi, nj, c);
+            uint32_t n_max = 0, radii = 0;
+            uint64_t cols = 0;
+            for (uint32_t r = cr.first; r < cr.end; r++) {
+                const uint32_t N = rc[r].y & 127u;
+                n_max = std::max(n_max, N); cols += N; radii |= 1u << ((rc[r].y >> 14) & 3u);
+            }
+            const uint32_t cls = cr.quad ? 0u : radii == 4u ? 1u : radii == 2u ? 3u : !(radii & ~6u) ? 2u : 4u;
+            w[4 * cls] += cr.end - cr.first; w[4 * cls + 1]++; w[4 * cls + 2] += n_max; w[4 * cls + 3] += cols;
+        }
+        w[20]++;
+    }
+    *n_out = 21;
+    for (uint32_t i = 0; i < 21 && i < cap && out; i++) out[i] = w[i];
+    return RAWDTW_OK;
 }
 
 int rawdtw_batch_info(const rawdtw_batch *batch, rawdtw_plan_info_t *info, uint64_t *n_chains)

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/rawdtw.h"
+#include "rawdtw_chunks.h"
 
 namespace rawdtw {
 
@@ -108,6 +109,7 @@ struct FullAux {
 constexpr uint32_t kStreamTile = 512;         // anchors (= candidate parts) of a tile: what one wave of the scan plans (eight a lane)
 constexpr uint32_t kStreamRecStride = 576;    // job records of a tile: its passes' records one behind the other, each pass on a 16-byte boundary
 constexpr uint32_t kStreamMaxSeg = 32;        // runs of one pass over a tile's image (more: the tile takes another pass)
+static_assert(kStreamMaxSeg < 64 && kStreamTile < 1024, "a list entry's third word: jobs (16 bits), runs (6), first radius-1 record (10)");
 // side-list classes, in launch order: wave-per-job by longer side (>= 1024, >= 256, >= 64, shorter), 16-lane groups, 8-lane groups
 constexpr uint32_t kStreamClasses = 21, kClsW0 = 0, kClsG16 = 4, kClsL0 = 5, kClsLCount = 8, kClsM0 = 13, kClsMCount = 8;
 // Side-list classes 13..20: bands of up to 8 slots (radius <= 7) that are not in the classes below: one lane per job too
@@ -134,7 +136,8 @@ enum StreamCounter : int {
     kCntReused,         // (unused: the parts taken over are counted from the carry records on the host -- a counter every chain's wave adds to
                         // is forty thousand same-address atomics, 0.3 ms)
     kCntPool,           // record slots handed out beyond one a tile (tiles whose image takes several passes)
-    kCntStamp0,         // 10 words: cycles per phase of k_runs, summed over waves ("stream_debug" 256: diagnostic runs only)
+    kCntStamp0,         // 10 words: cycles per phase of k_runs, summed over waves ("stream_debug" 256: diagnostic runs only); words 7, 8:
+                        // the lane chunks its waves ran, and those among them whose lanes held more than one radius
     kCntHeads = 64,     // tile queue: 8 heads, one per 128-byte line (head h deals the tiles t with t % 8 == h)
     kStreamCounters = kCntHeads + 8 * 16
 };
@@ -187,8 +190,9 @@ struct StreamArgs {
     uint2 *tlist;                // the scan's tile list: (tile, the chain its first anchor belongs to) of every tile that has a part for the
                                  // lane bodies; cnt[kCntTodo] entries, at most n_tiles
     uint4 *todo;                 // the DTW launch's work list (k_plan): one entry a PASS -- a tile's tile-class parts, or as many of them
-                                 // as fit the image budget and the run table: (tile, copy-order slot, jobs | runs << 16, floats of
-                                 // the image's event region | first record << 16), at the index of its slot: [0, cnt[kCntTodo]) the listed
+                                 // as fit the image budget and the run table: (tile, copy-order slot, jobs | runs << 16 | the pass's
+                                 // first radius-1 record << 22 (rawdtw_chunks.h: n_hi), floats of the image's event region |
+                                 // first record << 16), at the index of its slot: [0, cnt[kCntTodo]) the listed
                                  // tiles' first passes, [n_tiles, n_tiles + cnt[kCntPool]) the others
     uint2 *recs;                 // n_tiles x kStreamRecStride job records, a pass's in the order the lanes take them (radius class, then longer
                                  // side, descending): x = event window | reference window << 16 (float offsets into the pass's

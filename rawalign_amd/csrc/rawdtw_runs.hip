@@ -290,8 +290,10 @@ __device__ __forceinline__ void fold_order_body(const uint64_t n_chains, const u
 // k_scan: the pass over the anchor list ahead of the DTW launch.  Roles by workgroup: [0, n_tiles) one tile each,
 // n_tiles the fold order, the rest the chain records.
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr uint32_t kSortBins = 192; // bin = (3 - radius) * 64 + (63 - longer side): radius 3 first, then 2, then 1 (waves of one radius take the
-                                     // shortest body), each run longest first (sides of 63 and more share a bin)
+constexpr uint32_t kSortBins = 192; // bin = (3 - radius) * 64 + (63 - longer side): radius 3 first, then 2, then 1, each run longest first (sides
+                                     // of 63 and more share a bin).  The first place of bin 128 -- the pass's first radius-1 record -- goes into
+                                     // the pass's list entry: k_runs starts the radius-1 run on a chunk boundary of its own, so that no wave
+                                     // holds parts of both radius 2 and radius 1 (rawdtw_chunks.h)
 
 // A tile's items in the order the image is laid out in: item u is the part that ends at anchor (tile end - 1 - u), so that
 // along a chain (stored end-first) u ascends with the positions -- a run's first part is the one with the lowest addresses,
@@ -822,6 +824,9 @@ __global__ __launch_bounds__(kPlanT, 3) void k_plan(const StreamArgs a)
             const uint32_t hsum = h0 + h1 + h2, hincl = wave_scan_incl(hsum);
             const uint32_t n_jobs = (uint32_t)__builtin_amdgcn_readlane((int)hincl, 63);
             hist[3 * lane] = hincl - hsum; hist[3 * lane + 1] = hincl - hsum + h0; hist[3 * lane + 2] = hincl - hsum + h0 + h1;
+            // the pass's first radius-1 record = the first place of bin 128 (lane 42's third bin): the chunks of k_runs do not cross it
+            static_assert(kSortBins == 192 && 128 == 3 * 42 + 2, "bin 128 is lane 42's third");
+            const uint32_t n_hi = (uint32_t)__builtin_amdgcn_readlane((int)(hincl - hsum + h0 + h1), 42);
             wave_lds_sync();
             // the records, in the order the lanes of the DTW launch take them (a bin's jobs in any order: they are alike)
             {
@@ -848,7 +853,7 @@ __global__ __launch_bounds__(kPlanT, 3) void k_plan(const StreamArgs a)
                     make_uint4(rt.lo[w][g] >> 2, (rt.end[w][g] + (uint32_t)rt.D[w][g] + 3u) >> 2, (uint32_t)(unsigned long long)src, (uint32_t)((unsigned long long)src >> 32));
             }
             wave_lds_sync(); // (the run table and the bins are read: the next pass writes them again)
-            if (lane == 0) a.todo[slot] = make_uint4(tile, slot, n_jobs | (n_runs << 16), region | (rec_off << 16)); // (a pass's list entry sits at its slot)
+            if (lane == 0) a.todo[slot] = make_uint4(tile, slot, n_jobs | (n_runs << 16) | (n_hi << 22), region | (rec_off << 16)); // (a pass's list entry sits at its slot)
             if (last) break;
             rec_off += (n_jobs + 1u) & ~1u; // (passes start on 16-byte boundaries)
             if (rec_off + (kStreamTile - u1) > kStreamRecStride) { if (lane == 0) atomicMin(&a.cnt[kCntOverflow], (unsigned long long)tile); break; } // (> 64 passes)
@@ -912,8 +917,14 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t n_max)
     return (uint32_t)__builtin_amdgcn_readlane((int)n_max, 63);
 }
 
-// One sorted chunk of a tile: 64 lanes, one job each.  The chunks of a tile are cut from one order -- the jobs of radius 3
-// first, then 2, then 1, each run by longer side, descending; a wave takes the shortest body that covers its radii.
+// One sorted chunk of a pass: 64 lanes, one job each.  The chunks are cut from one order -- the jobs of radius 3 first, then 2,
+// then 1, each run by longer side, descending -- and never across the first radius-1 record (run_dp, rawdtw_chunks.h): a chunk
+// of the tiles is of radius 2 alone (lane_dp_r2), of radius 1 alone (lane_dp_r1: 15 instructions a column against 36.5), or
+// holds the radius-3 records the quads did not take (lane_dp_gen).  Cut every 64 records, one chunk of nearly every pass
+// held the pass's shortest radius-2 parts (2-3 columns) and its longest radius-1 parts (~19) and ran lane_dp_r12 for the
+// longest of them: a sixth of the column loop's instructions.  The inactive lanes of a partly filled chunk hold a copy of
+// the chunk's own last record, so the ballots and the longest side below show the chunk's class alone.  (lane_dp_r12 stays for
+// a chunk that does hold both: the choice below goes by what the lanes hold, not by the map.)
 __device__ __forceinline__ float stream_lane_job(const float *LA, const float *LB, uint32_t N, uint32_t M, uint32_t R, bool excl, bool act)
 {
     const unsigned long long r12 = __ballot(R <= 2u), r1 = __ballot(R == 1u), r2 = __ballot(R == 2u);
@@ -1088,12 +1099,13 @@ __global__ __launch_bounds__(TT, 4) void k_runs(const StreamArgs a, const uint32
     };
     // ... and its copy orders, which the staging itself reads: a pass ahead, into buffer `buf` (one wave)
     auto fetch_orders = [&](const uint4 e, const uint32_t buf) {
-        const uint32_t n_ord = 2u * (e.z >> 16);
+        const uint32_t n_ord = 2u * ((e.z >> 16) & 63u);
         if ((uint32_t)lane < n_ord) dma16(a.runtab + (uint64_t)e.y * kRT + lane, rtab + buf * kRT);
     };
 
     // diagnostic build of the launch ("stream_debug" 256): where a wave's cycles go, phase by phase (s_memtime around the
-    // phases, summed per wave in LDS and added to the counter block's words kCntStamp0.. at the end; it perturbs the run)
+    // phases, summed per wave in LDS and added to the counter block's words kCntStamp0.. at the end; it perturbs the run);
+    // words 7 and 8: the lane chunks the waves ran, and those whose lanes held more than one radius (run_dp)
     __shared__ unsigned long long s_stamp[kWaves][kStamps];
     unsigned long long t_prev = 0;
     const bool stamps = DIAG && (dbg & 256u) != 0u;
@@ -1153,24 +1165,29 @@ __global__ __launch_bounds__(TT, 4) void k_runs(const StreamArgs a, const uint32
     __syncthreads();
     // the DP of one pass: waves pull chunks of the sorted records (the heavy class first), so the waves of the workgroup
     // finish together whatever the mix
-    auto run_dp = [&](const uint2 *rc_base, const uint32_t n_jobs, const uint32_t end_nom) {
-        // The radius-3 records come first in the order: those among the pass's first 64 go sixteen to a wave, four lanes a
-        // job (quad_dp_r3) -- chunks 0 .. q3 - 1; the records behind them 64 to a wave as ever (a tile with more than 64
-        // radius-3 parts leaves the others to the lanes' generic body).
+    auto run_dp = [&](const uint2 *rc_base, const uint32_t n_jobs, const uint32_t n_hi_e, const uint32_t end_nom) {
+        // The chunk map (rawdtw_chunks.h).  The radius-3 records come first in the order: those among the pass's first 64 go
+        // sixteen to a wave, four lanes a job (quad_dp_r3); the records behind them 64 to a wave, first those of radius 2
+        // (a tile with more than 64 radius-3 parts leaves the others to the lanes' generic body, in these chunks), then,
+        // from a chunk boundary of their own, those of radius 1 -- the entry says where they start.
         uint32_t n3;
         {
             const uint2 r0 = rc_base[min((uint32_t)lane, n_jobs - 1u)];
             n3 = (uint32_t)__popcll(__ballot((uint32_t)lane < n_jobs && ((r0.y >> 14) & 3u) == 3u));
         }
-        const uint32_t q3 = (n3 + 15u) >> 4, n_chunks = q3 + ((n_jobs - n3 + 63u) >> 6);
+        const uint32_t n_hi = min(max(n_hi_e, n3), n_jobs); // (the planner's value lies there: no record index leaves the pass whatever the entry says)
+        const uint32_t n_chunks = chunk_map_count(n3, n_hi, n_jobs);
         for (uint32_t c = wv; !(dbg & 1u);) { // (a wave's first chunk is its own number: no round trip through the counter)
             if (c >= n_chunks) break;
             if ((dbg & 512u) && c == 0u) { uint32_t cn0 = 0; if (lane == 0) cn0 = atomicAdd(&s_seq, 1u); c = (uint32_t)__builtin_amdgcn_readfirstlane((int)cn0); continue; } // (timing: a pass without its first chunk)
             if ((dbg & 1024u) && c != 0u) break; // (timing: a pass's first chunk only)
-            if (c < q3) {
-                const uint32_t r = c * 16u + ((uint32_t)lane >> 2);
-                const bool act = r < n3;
-                const uint2 rc = rc_base[act ? r : n3 - 1u];
+            // a lane is active iff its record lies in the chunk's range; an inactive lane reads the last record of that range: the
+            // wave's longest side and its radius ballots (stream_lane_job) show the chunk's class alone
+            const ChunkRange cr = chunk_map_range(n3, n_hi, n_jobs, c);
+            if (cr.quad) {
+                const uint32_t r = cr.first + ((uint32_t)lane >> 2);
+                const bool act = r < cr.end;
+                const uint2 rc = rc_base[act ? r : cr.end - 1u];
                 const uint32_t N = rc.y & 127u, M = (rc.y >> 7) & 127u, u = (rc.y >> 17) & (kStreamTile - 1u);
                 const float *LA = win + (rc.x & 0xffffu), *LB = win + (rc.x >> 16);
                 float res = quad_dp_r3(LA, LB, N, M, lane, wave_max_u32(N));
@@ -1179,12 +1196,16 @@ __global__ __launch_bounds__(TT, 4) void k_runs(const StreamArgs a, const uint32
                     a.out[end_nom - 1u - u] = res;
                 }
             } else {
-                const uint32_t r = n3 + (c - q3) * 64u + lane;
-                const bool act = r < n_jobs;
-                const uint2 rc = rc_base[act ? r : n_jobs - 1u];
+                const uint32_t r = cr.first + (uint32_t)lane;
+                const bool act = r < cr.end;
+                const uint2 rc = rc_base[act ? r : cr.end - 1u];
                 const uint32_t N = rc.y & 127u, M = (rc.y >> 7) & 127u, R = (rc.y >> 14) & 3u, u = (rc.y >> 17) & (kStreamTile - 1u);
                 const float res = stream_lane_job(win + (rc.x & 0xffffu), win + (rc.x >> 16), N, M, R, (rc.y >> 16) & 1u, act);
                 if (act) a.out[end_nom - 1u - u] = res; // the part that ends at anchor (tile end - 1 - u)
+                if (stamps) { // (diagnostic: the lane chunks this wave ran, and those among them whose lanes held more than one radius)
+                    const bool mixed = __ballot(R != (uint32_t)__builtin_amdgcn_readfirstlane((int)R)) != 0ull;
+                    if (lane == 0) { s_stamp[wv][7] += 1ull; s_stamp[wv][8] += mixed ? 1ull : 0ull; }
+                }
             }
             uint32_t cn = 0;
             if (lane == 0) cn = atomicAdd(&s_seq, 1u);
@@ -1195,7 +1216,7 @@ __global__ __launch_bounds__(TT, 4) void k_runs(const StreamArgs a, const uint32
     for (;;) {
         const uint4 e = s_ent[cur];
         if (e.x == 0xffffffffu) break;
-        const uint32_t n_jobs = e.z & 0xffffu, n_ord = 2u * (e.z >> 16);
+        const uint32_t n_jobs = e.z & 0xffffu, n_ord = 2u * ((e.z >> 16) & 63u), n_hi = e.z >> 22;
         // thread 0: the next pass's entry is published before this pass's first barrier; the pass after that gets its list
         // index (the ticket drawn a pass ago) and wave 0 asks for its entry; the ticket of the pass after THAT is drawn
         uint32_t i2 = 0xffffffffu;
@@ -1244,7 +1265,7 @@ __global__ __launch_bounds__(TT, 4) void k_runs(const StreamArgs a, const uint32
         stamp(2);
         __syncthreads(); // B1: the image is staged; the next pass's entry is published
         stamp(3);
-        run_dp(rec, n_jobs, (e.x + 1u) * kStreamTile);
+        run_dp(rec, n_jobs, n_hi, (e.x + 1u) * kStreamTile);
         stamp(4);
         if (wv == 0) e_next = e_load; // (asked for at this pass's start)
         stamp(5);

@@ -45,7 +45,7 @@ for cfg in configs:
     print("%-28s create %.3f ms  plan(gpu) %.3f ms  launches %s" % (cfg or "default", t_create, pm.value, ["%.4f" % m[2] for m in ms]), flush=True)
     s0 = eng.lib.rawdtw_batch_stream_counter_index(b"stamp0")
     if any(cnt[s0:s0 + 10]):  # "stream_debug" 256: cycles per phase of k_runs, summed over waves and runs
-        tot = float(sum(cnt[s0:s0 + 10]))
+        tot = float(sum(cnt[s0:s0 + 7]))  # (words 7, 8: chunk counts, not cycles)
         names = ["entry", "stage issue", "stage wait", "B1", "DP + next records", "ticket + wait", "B2"]
         print("   phase shares: " + "  ".join("%s %.1f%%" % (n, 100.0 * c / tot) for n, c in zip(names, cnt[s0:s0 + 10])), flush=True)
     b.close()

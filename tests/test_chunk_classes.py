@@ -1,0 +1,206 @@
+"""k_runs takes a pass's sorted job records in chunks that do not cross the radius classes (rawalign_amd/csrc/rawdtw_chunks.h:
+sixteen radius-3 records to a wave of quads, then the radius-2 run 64 records to a wave, then -- from a chunk boundary of its
+own, published by k_plan in the pass's list entry -- the radius-1 run).  Hand-built anchor lists whose tiles have an exact
+composition, against the oracle as tests/test_stream_path.py does it: every part cost, every score and every keep flag bit
+for bit, and the plan's self-check (which also checks the entry's new field).
+
+What proves what: the results are bit-identical under ANY chunk map, so the oracle comparison shows that the kernel scores
+every record once and correctly, not which map it walks.  The chunk counts asserted from chunk_profile() are counted on the
+host from the plan (the entry's n_hi, through the same rawdtw_chunks.h): they pin the planner's field and the case's
+composition.  That the KERNEL walks the map is shown by the diagnostic instance's own counters ("stream_debug" 256: the
+lane chunks its waves ran and those whose lanes held more than one radius, counted in run_dp from the lanes' records):
+test_mixed_wave_is_taken_apart[debug256] and test_kernel_counts_its_chunks.
+
+Shapes (band radius fraction 0.1: r0 = max(1, int(0.1 n)), slanted radius r0 + ceil((N - M) r0 / N), dtw.cpp:298-300):
+radius 1 = square parts of sides 2..19; radius 2 = n != m with a read side below 20; radius 3 = read side 20..29 a little
+slanted, or 30..39 square.  A chain of k + 1 anchors has k parts, part i ending at anchor i: a chain of 513 anchors at the
+head of the list is exactly one tile of 512 parts."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+try:  # PyTorch bundles its own HIP runtime: when both live in one process, torch has to come up first
+    import torch
+
+    torch.cuda.is_available()
+except Exception:  # pragma: no cover
+    torch = None
+
+import rawalign_amd as ra
+from rawalign_amd.align import CandidateBatch
+from tests.test_stream_path import _oracle_check
+
+pytestmark = pytest.mark.gpu
+
+REF_LEN = 60000
+
+
+def _radius(n, m, frac=0.1):
+    r0 = max(1, int(np.float32(n) * np.float32(frac)))
+    N, M = max(n, m), min(n, m)
+    return r0 + ((N - M) * r0 + N - 1) // N
+
+
+def _r1(k):
+    """k radius-1 parts: square, sides 2..19: one in sixteen of the longest (19), the others short as a mapper's are (a tile of
+    512 parts has to fit the image budget of 5 800 floats in one pass: 8 floats a part)"""
+    sides = [2, 3, 4, 5, 2, 3, 6, 2, 3, 4, 8, 2, 3, 12, 4]
+    return [(19, 19) if i % 16 == 0 else (sides[i % 15], sides[i % 15]) for i in range(k)]
+
+
+def _r2(k):
+    """k radius-2 parts: read side below 20, n != m; three in four of the shortest (sides 2 / 3), the others up to 30 long"""
+    long_ones = [(12, 25), (19, 30), (19, 12), (7, 9), (15, 14), (4, 11), (18, 19), (9, 5)]
+    return [long_ones[(i // 4) % len(long_ones)] if i % 4 == 3 else ((2, 3) if i % 2 == 0 else (3, 2)) for i in range(k)]
+
+
+def _r3(k):
+    """k radius-3 parts: read side 20..39"""
+    kinds = [(20, 21), (21, 20), (22, 23), (20, 19), (29, 27), (21, 22), (30, 30), (39, 39)]
+    return [kinds[i % len(kinds)] for i in range(k)]
+
+
+def _tile(n3, n2, n1, seed):
+    """the parts of one tile, in a fixed shuffled order (the planner sorts them: where they lie along the chain decides the runs
+    of the image, not the chunks)"""
+    parts = _r3(n3) + _r2(n2) + _r1(n1)
+    assert [_radius(n, m) for n, m in parts] == [3] * n3 + [2] * n2 + [1] * n1
+    rng = np.random.default_rng(seed)
+    return [parts[i] for i in rng.permutation(len(parts))]
+
+
+def _batch(chains):
+    """One read; `chains` = lists of parts (n, m) in anchor-list order: part i of a chain ends at its anchor i and starts at i + 1
+    (chains are stored end-first, rmap.cpp:193-196)."""
+    rng = np.random.default_rng(len(chains) * 1000 + sum(len(c) for c in chains))
+    anchor_off, anchors, read_base, slot = [0], [], [], []
+    read_len = 0
+    for parts in chains:
+        dq = np.array([n - 1 for n, _ in parts][::-1], np.int64)  # ascending along the positions: the list's last part first
+        dt = np.array([m - 1 for _, m in parts][::-1], np.int64)
+        q = np.concatenate([[3], 3 + np.cumsum(dq)])
+        t0 = int(rng.integers(0, REF_LEN - int(dt.sum()) - 2))
+        t = np.concatenate([[t0], t0 + np.cumsum(dt)])
+        a = np.zeros(len(q), ra.ANCHOR_DTYPE)
+        a["query_position"] = q[::-1]
+        a["target_position"] = t[::-1]
+        anchors.append(a)
+        anchor_off.append(anchor_off[-1] + len(a))
+        read_base.append(0)
+        slot.append(len(slot) & 1)
+        read_len = max(read_len, int(q[-1]) + 1)
+    events = rng.normal(size=read_len).astype(np.float32)
+    return (events, np.array([0, len(chains)], np.uint64), np.array(anchor_off, np.uint64), np.concatenate(anchors), slot,
+            np.array(read_base, np.uint32))
+
+
+@pytest.fixture(scope="module")
+def reference():
+    rng = np.random.default_rng(20240611)
+    return [rng.normal(size=REF_LEN).astype(np.float32), rng.normal(size=REF_LEN).astype(np.float32)]
+
+
+def _run(oracle, reference, chains, opts):
+    eng = ra.Engine(0)
+    for k, v in opts.items():
+        eng.set_option(k, v)
+    eng.upload_reference([reference[0]], [reference[1]])
+    events, chain_off, anchor_off, anchors, slot, read_base = _batch(chains)
+    strand_of = [1 if s == 0 else 0 for s in slot]  # slot 0 = forward array (strand 1, rmap.cpp:182-188)
+    ref_base = np.array([eng.reference_offset(0, st) for st in strand_of], np.uint64)
+    cb = CandidateBatch(events, chain_off, anchor_off, anchors, ref_base, read_base)
+    eng.upload_events(events)
+    opt = ra.MapOpt(dtw_min_score=5.0)
+    b = ra.Batch(eng, opt, cb)
+    assert b.verify_plan() is True  # planned on the device; every entry's first radius-1 record is where the records say
+    prof, flat = b.chunk_profile(), b.chunk_profile(flat_map=True)
+    b.run()
+    score, keep, jc = b.fetch(with_job_costs=True)
+    assert len(jc) == sum(len(c) for c in chains)
+    if opts.get("stream_debug", 0) & 256:  # what the kernel itself counted while it ran (one run): lane chunks, mixed ones
+        cnt, ncnt = (C.c_uint64 * 64)(), C.c_uint32()
+        eng._check(eng.lib.rawdtw_batch_stream_counters(eng._ctx, b._h, cnt, 64, C.byref(ncnt)))
+        s0 = eng.lib.rawdtw_batch_stream_counter_index(b"stamp0")
+        ran = (int(cnt[s0 + 7]), int(cnt[s0 + 8]))
+    _oracle_check(oracle, cb, {1: reference[0], 0: reference[1]}, strand_of, score, keep, jc, opt)
+    n_parts = sum(len(c) for c in chains)
+    for p in (prof, flat):
+        assert sum(p[c]["jobs"] for c in ra.Batch.CHUNK_CLASSES) == n_parts
+    assert prof["lane_r12"]["chunks"] == 0  # no wave holds both radius-2 and radius-1 parts
+    if opts.get("stream_debug", 0) & 256:
+        lane_chunks = sum(prof[c]["chunks"] for c in ra.Batch.CHUNK_CLASSES[1:])
+        assert ran == (lane_chunks, prof["lane_gen"]["chunks"]), (ran, prof)  # the kernel ran the map's chunks; none mixes radii 1 and 2
+    b.close()
+    eng.close()
+    return prof, flat
+
+
+# the wave the chunk map takes apart: 129 = 1 (mod 64) radius-2 parts and 383 = 63 (mod 64) radius-1 parts in one tile -- cut every
+# 64 records, the third chunk held the last radius-2 part (sides 2 / 3) and 63 radius-1 parts, the longest (19) first
+SPLIT = (0, 129, 383)
+
+
+@pytest.mark.parametrize("opts", [{}, {"tile_lds_floats": 2048}, {"stream_threads": 512}, {"stream_debug": 128}, {"stream_debug": 256}],
+                         ids=["default", "lds2048", "threads512", "debug128", "debug256"])
+def test_mixed_wave_is_taken_apart(oracle, reference, opts):
+    prof, flat = _run(oracle, reference, [_tile(*SPLIT, seed=1)], opts)
+    if "tile_lds_floats" not in opts:  # one pass: the chunks are the map's
+        assert prof["passes"] == 1
+        assert (prof["lane_r2"]["chunks"], prof["lane_r1"]["chunks"]) == (3, 6)
+        assert (flat["lane_r2"]["chunks"], flat["lane_r12"]["chunks"], flat["lane_r1"]["chunks"]) == (2, 1, 5)
+        # the mixed wave ran for the longest radius-1 side; on its own the last radius-2 part runs for three columns
+        assert prof["lane_r2"]["chunk_columns"] == flat["lane_r2"]["chunk_columns"] + 3
+    else:  # several passes a tile, each with a first radius-1 record of its own
+        assert prof["passes"] > 1
+
+
+@pytest.mark.parametrize("n3,n2,n1", [(0, 128, 384), (0, 0, 512), (0, 512, 0)], ids=["multiple_of_64", "only_r1", "only_r2"])
+def test_map_equals_the_flat_one(oracle, reference, n3, n2, n1):
+    """the radius-2 run ends on a multiple of 64 records, or one of the runs is empty: the same chunks as without the boundary"""
+    prof, flat = _run(oracle, reference, [_tile(n3, n2, n1, seed=2)], {})
+    assert prof == flat and prof["passes"] == 1
+    assert (prof["lane_r2"]["chunks"], prof["lane_r1"]["chunks"]) == ((n2 + 63) // 64, (n1 + 63) // 64)
+
+
+def test_small_tile_two_partial_waves(oracle, reference):
+    """a tile of fewer than 64 parts with both classes (behind a full tile: the second chain starts at anchor 513): two partly
+    filled waves, where it was one"""
+    prof, flat = _run(oracle, reference, [_tile(0, 0, 512, seed=3), _tile(0, 5, 20, seed=4)], {})
+    assert prof["passes"] == 2
+    assert (prof["lane_r2"]["chunks"], prof["lane_r1"]["chunks"]) == (1, 8 + 1)
+    assert (flat["lane_r12"]["chunks"], flat["lane_r1"]["chunks"]) == (1, 8)
+
+
+@pytest.mark.parametrize("n3", [0, 1, 16, 17, 64, 70])
+def test_radius3_counts(oracle, reference, n3):
+    """the quads take the radius-3 records among a pass's first 64, sixteen a wave; beyond 64 they stay with the radius-2 run
+    (the generic body).  Both other classes present, the radius-2 run = 1 and the radius-1 run = 63 (mod 64) again; the tile
+    (behind a full one of radius 1) is kept to 192 + n3 parts so that seventy radius-3 parts fit one pass's image."""
+    prof, flat = _run(oracle, reference, [_tile(0, 0, 512, seed=3), _tile(n3, 65, 127, seed=5 + n3)], {})
+    assert prof["passes"] == 2
+    assert prof["quad_r3"] == flat["quad_r3"]
+    assert prof["quad_r3"]["jobs"] == min(n3, 64) and prof["quad_r3"]["chunks"] == (min(n3, 64) + 15) // 16
+    assert prof["lane_gen"]["jobs"] == (64 if n3 > 64 else 0)  # the wave with the six radius-3 records beyond the quads'
+    assert prof["lane_r2"]["chunks"] + prof["lane_gen"]["chunks"] == (65 + max(n3 - 64, 0) + 63) // 64
+    assert prof["lane_r1"]["chunks"] == 8 + 2
+    # cut every 64 records the tile's third lane chunk on is of radius 1 alone; the second held the last radius-2 parts with them
+    assert flat["lane_r1"]["chunks"] == 8 + (192 + max(n3 - 64, 0) + 63) // 64 - 2 and flat["lane_r12"]["chunks"] == 1
+
+
+@pytest.mark.parametrize("n3", [0, 17, 70])
+def test_kernel_counts_its_chunks(oracle, reference, n3):
+    """the diagnostic instance's counters on two tiles with all classes: as many lane chunks as the map has, mixed ones only
+    where radius-3 records beyond the quads' 64 share a wave with the radius-2 run (cut every 64 records the kernel would
+    count one chunk less a tile and one mixed chunk more)"""
+    _run(oracle, reference, [_tile(0, 129, 383, seed=30), _tile(n3, 65, 127, seed=31 + n3)], {"stream_debug": 256})
+
+
+def test_chain_boundary_and_list_end_inside_tiles(oracle, reference):
+    """two chains of 520 anchors: the second tile has a chain boundary (no part ends at a chain's last entry), the third holds
+    the list's last 16 anchors"""
+    a = _tile(4, 130, 385, seed=20)
+    b = _tile(3, 129, 387, seed=21)
+    assert len(a) + 1 == 520 and len(b) + 1 == 520
+    prof, _ = _run(oracle, reference, [a, b], {})
+    assert prof["passes"] >= 3
