@@ -11,9 +11,22 @@
  * Threading: a rawdtw_ctx owns one HIP stream and is NOT re-entrant; use one
  * ctx per host thread (or serialise).  Different ctxs are independent.
  *
- * Arithmetic contract: fp32, local distance |x-y|, cell = min3 + dist, sentinel
- * = float(1e10); device code is built with -ffp-contract=off.  Costs are
- * bit-identical to the reference for finite inputs (NaN inputs: unspecified).
+ * Arithmetic contract: fp32, local distance |x-y|, cell = min3 + dist; device
+ * code is built with -ffp-contract=off and flushes nothing.  Costs, paths and
+ * scores are bit-identical to the reference for finite inputs whose sums stay
+ * finite (NaN or infinite inputs, and sums that overflow: unspecified).
+ *  - The banded functions (DTW_global_slantedbanded_antidiagonalwise,
+ *    dtw.cpp:273-520) read every absent neighbour -- guarded, clipped or outside
+ *    the band -- as float(1e10), as the reference does: it is an operand of the
+ *    min like any other, and costs may exceed it (it then wins the min, there
+ *    as here).
+ *  - The full-matrix functions (DTW_global, DTW_global_tb: dtw.cpp:37-66,
+ *    595-667) have no sentinel: row 0 and column 0 are running sums, whatever
+ *    they pass.
+ *  - Subnormal inputs, distances and sums are preserved, and -0.0 inputs cost
+ *    +0.0, in every body.
+ * tests/test_value_domain_gpu.py holds every body to this on costs below, around
+ * and far above 1e10, on subnormals and on zeros of either sign.
  */
 #ifndef RAWDTW_H
 #define RAWDTW_H

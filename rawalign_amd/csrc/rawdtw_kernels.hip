@@ -379,6 +379,11 @@ __global__ __launch_bounds__(64 * WAVES) void k_full_wave(const DevJob *__restri
                                                   uint8_t *__restrict__ dir_ws)
 {
     using word_t = typename DirWord<RPL>::type;
+    // DTW_global and DTW_global_tb have no sentinel (dtw.cpp:37-66, 595-667: row 0 and column 0 are running sums, whatever they
+    // pass), so what lies beyond the matrix must lose every min: +inf, not the banded DP's 1e10 -- a border sum above 1e10 would
+    // otherwise be replaced by it, and the direction codes of the interior decided from the replaced values.  Every cell has a
+    // finite neighbour or the corner's 0, so no cell of the matrix is ever +inf itself.
+    constexpr float kNone = __builtin_inff();
     const DevJob jb = jobs[blockIdx.x];
     const FullAux ax = aux[blockIdx.x];
     const int lane = threadIdx.x & 63;
@@ -418,7 +423,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_full_wave(const DevJob *__restri
         for (int k = 0; k < RPL; k++) {
             uint32_t y = y0 + k;
             yv[k] = Y[y < NY ? y : NY - 1];
-            v[k] = kInf; // column -1
+            v[k] = kNone; // column -1
         }
         const uint32_t rows_here = (NY - s * STRIP) < STRIP ? (NY - s * STRIP) : STRIP;
         const uint32_t lanes_here = (rows_here + RPL - 1) / RPL;
@@ -426,8 +431,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_full_wave(const DevJob *__restri
         const bool has_rows = y0 < NY;
         const bool hands_down = (s + 1 < nstrips); // then the strip is full and lane 63 owns its last row
         // virtual row above row 0 is +inf, its corner D[-1][-1] is 0 so that D[0][0] = dist
-        float diag_in = (s == 0 && lane == 0) ? 0.0f : kInf;
-        float last_out = kInf, xval = 0.0f, xchunk = 0.0f, bchunk = kInf, wchunk = 0.0f;
+        float diag_in = (s == 0 && lane == 0) ? 0.0f : kNone;
+        float last_out = kNone, xval = 0.0f, xchunk = 0.0f, bchunk = kNone, wchunk = 0.0f;
         // (bit of the 2-bit code each plane sets: "up" bit 0 and "lf" bit 1, the other way round for a swapped job)
 
         for (uint32_t t = 0; t < steps; t++) {
@@ -442,7 +447,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_full_wave(const DevJob *__restri
                             __builtin_amdgcn_s_sleep(1);
                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                     }
-                    bchunk = idx < NX ? bnd_in[idx] : kInf;
+                    bchunk = idx < NX ? bnd_in[idx] : kNone;
                 }
             }
             const float x0 = read_lane(xchunk, (int)(t & 63u));

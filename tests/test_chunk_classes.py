@@ -70,8 +70,8 @@ def _tile(n3, n2, n1, seed):
     return [parts[i] for i in rng.permutation(len(parts))]
 
 
-def _batch(chains):
-    """One read; `chains` = lists of parts (n, m) in anchor-list order: part i of a chain ends at its anchor i and starts at i + 1
+def _batch(chains, draw=None):
+    """`draw`(rng, size) gives the events (default: rng.normal).  One read; `chains` = lists of parts (n, m) in anchor-list order: part i of a chain ends at its anchor i and starts at i + 1
     (chains are stored end-first, rmap.cpp:193-196)."""
     rng = np.random.default_rng(len(chains) * 1000 + sum(len(c) for c in chains))
     anchor_off, anchors, read_base, slot = [0], [], [], []
@@ -90,7 +90,7 @@ def _batch(chains):
         read_base.append(0)
         slot.append(len(slot) & 1)
         read_len = max(read_len, int(q[-1]) + 1)
-    events = rng.normal(size=read_len).astype(np.float32)
+    events = rng.normal(size=read_len).astype(np.float32) if draw is None else draw(rng, read_len)
     return (events, np.array([0, len(chains)], np.uint64), np.array(anchor_off, np.uint64), np.concatenate(anchors), slot,
             np.array(read_base, np.uint32))
 

@@ -21,8 +21,9 @@ from tests.golden_util import bits
 pytestmark = pytest.mark.gpu
 
 
-def _chains(rng, n_reads, ref_len, shapes, parts_range=(1, 40)):
-    """One read per chain group; every chain's parts draw (dq, dt) from `shapes`(rng) -> anchors end-first."""
+def _chains(rng, n_reads, ref_len, shapes, parts_range=(1, 40), draw=None):
+    """One read per chain group; every chain's parts draw (dq, dt) from `shapes`(rng) -> anchors end-first.  `draw`(rng, size)
+    gives the events (default: rng.normal)."""
     events, chain_off, anchor_off, anchors, ref_base, read_base = [], [0], [0], [], [], []
     ev_at = 0
     for r in range(n_reads):
@@ -38,7 +39,7 @@ def _chains(rng, n_reads, ref_len, shapes, parts_range=(1, 40)):
             t = np.concatenate([[t0], t0 + np.cumsum(dt)]).astype(np.int64)
             per.append((q, t))
             read_len = max(read_len, int(q[-1]) + 1)
-        events.append(rng.normal(size=read_len).astype(np.float32))
+        events.append(rng.normal(size=read_len).astype(np.float32) if draw is None else draw(rng, read_len))
         for q, t in per:
             a = np.zeros(len(q), ra.ANCHOR_DTYPE)
             a["query_position"] = q[::-1]
@@ -452,11 +453,11 @@ def test_compact_hand_over_equals_plain(oracle, shapes, n_reads, parts_range):
 CARRY_DTYPE = np.dtype([("prev_src", "<u8"), ("parts", "<u4"), ("flags", "<u4"), ("start_t", "<u4"), ("start_q", "<u4")])  # rawdtw_carry_t
 
 
-def _two_rounds(rng, eng, n_reads=300):
+def _two_rounds(rng, eng, n_reads=300, draw=None):
     """Round 2 = round 1's chains: 0 grown at the end (the usual case), 1 unchanged, 2 an interior anchor moved, 3 a chain round 1
     did not have, 4 cut back at the end (its last part was not the last one then).  Returns (cb1, cb2, prev_read, expected
     parts taken over per chain of round 2, events)."""
-    events, chain_off, anchor_off, anchors, slot, read_base = _chains(rng, n_reads, 90000, _medium, (3, 90))
+    events, chain_off, anchor_off, anchors, slot, read_base = _chains(rng, n_reads, 90000, _medium, (3, 90), draw=draw)
     strand_of = [1 if s == 0 else 0 for s in slot]
     ref_base = np.array([eng.reference_offset(0, st) for st in strand_of], np.uint64)
     nc = len(anchor_off) - 1
