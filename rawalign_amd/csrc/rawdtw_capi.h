@@ -254,6 +254,13 @@ template <typename T> T *carve(char *&p, uint64_t count)
     p += (count * sizeof(T) + 255) & ~(size_t)255;
     return q;
 }
+// (the same on an address, for a layout that is first laid from 0 to learn its size)
+template <typename T> T *carve(uintptr_t &p, uint64_t count)
+{
+    T *q = reinterpret_cast<T *>(p);
+    p += (count * sizeof(T) + 255) & ~(size_t)255;
+    return q;
+}
 
 inline int fail(rawdtw_ctx *ctx, int status, const std::string &msg)
 {

@@ -28,6 +28,14 @@
 // workgroup sorts its seeds into scratch (k_chain_sort_long), then a wave runs the same DP over them (k_chain_long) with the trailing window of
 // candidates in an LDS ring and everything older read back from scratch.  Same results, same flags; with the option on only a read above the
 // option's value still declines the round.
+//
+// ONE DP BODY.  What restates the reference is written once, as inlined device functions both kernels call: list_end (where a list ends),
+// chain_step (64 candidates of the predecessor loop, rmap.cpp:458-484), chain_ends (the best ends and traceback_chains, rmap.cpp:175-179, 130-173,
+// 502-504) and chain_order (rmap.cpp:512, the tie flag, the read's records and counts).  A kernel supplies where the state lives: k_chain loads a
+// candidate's (target, query, score) from LDS and writes an anchor's score, predecessor and flags there; k_chain_long loads them from its ring or
+// from scratch behind it (counting the far steps), keeps a block's state in registers, flushes it to scratch, and asks chain_ends for the fences
+// that marks in device memory need.  The anchor loop, the band's lower end, the running maximum and the end filter (rmap.cpp:486-493) stay in the
+// kernels.  The round's workspace is described once too (ChainLayout): laid from 0 it gives the size, from the block's base the pointers.
 #include "rawdtw_capi.h"
 
 #include <algorithm>
@@ -84,6 +92,124 @@ __device__ __forceinline__ float scan_max(float v)
 __device__ __forceinline__ uint32_t uni(const uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
 __device__ __forceinline__ uint32_t lane_of(const uint32_t x, const uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)x, (int)uni(l)); }
 
+// ---- what k_chain and k_chain_long share: rmap.cpp:430-507, 130-173 and 512 on a wave.  The arrays come as plain pointers -- LDS from k_chain,
+// scratch from k_chain_long -- and every function is inlined into its kernel, where the compiler sees which of the two they are. ----
+// the (sequence, strand) list of `key` that starts at g0: the first index whose key differs
+__device__ __forceinline__ uint32_t list_end(const unsigned long long *K1, const uint32_t key, const uint32_t g0, const uint32_t n, const uint32_t lane)
+{
+    for (uint32_t i = g0; i < n; i += 64) {
+        const uint32_t x = i + lane;
+        const unsigned long long diff = __ballot(x < n && (uint32_t)(K1[x < n ? x : g0] >> 32) != key);
+        if (diff) return i + (uint32_t)__builtin_ctzll(diff);
+    }
+    return n;
+}
+// 64 candidates of the predecessor loop of the anchor (ct, cq): lane l has candidate base - l, inside the band when `valid`, with its target, query
+// and final score (pt, pq, sp) as the kernel loaded them from where it keeps them.  true: the loop ends among these.
+__device__ __forceinline__ bool chain_step(const rawdtw_chain_opt_t &o, const int32_t ct, const int32_t cq, const int32_t base, const bool valid, const int32_t pt,
+                                           const int32_t pq, const float sp, float &best, uint32_t &pred, int32_t &skips)
+{
+    const bool pass12 = pq == cq || pt == ct;                                   // rmap.cpp:458-459
+    const bool stop_gap = valid && !pass12 && pt + o.max_target_gap_length < ct; // rmap.cpp:460
+    const int32_t td = ct - pt, qd = cq - pq;
+    const bool active = valid && !pass12 && !stop_gap && qd >= 0;               // rmap.cpp:467
+    float cur = 0.0f;
+    {
+        const float matching = (float)min(min(td, qd), o.e);                    // rmap.cpp:469
+        const int gap = abs(td - qd);
+        const float scale = td > 0 ? __fdiv_rn((float)qd, (float)td) : 1.0f;
+        if (gap < o.max_gap_length && scale < 5.0f && scale > 0.75f) cur = sp + matching; // rmap.cpp:474-476
+    }
+    const float cv = active ? cur : -1.0f;
+    // the candidates before this one, in loop order = lane order: their largest value, and `best` as it stood at the loop's entry
+    const float incl = scan_max(cv);
+    const float before = fmaxf(best, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, -1.0f), __builtin_bit_cast(int, incl), 0x138, 0xf, 0xf, false)));
+    const bool improver = active && cur > before;                               // rmap.cpp:478
+    const int32_t moves = scan_add(improver ? -1 : (active ? 1 : 0));
+    const bool stop_skip = active && !improver && skips + moves > o.max_num_skips; // rmap.cpp:482-484
+    const unsigned long long stop = __ballot(!valid || stop_gap || stop_skip);
+    const uint32_t first = stop ? (uint32_t)__builtin_ctzll(stop) : 64u;
+    const unsigned long long live = first >= 64u ? ~0ull : ((1ull << first) - 1ull);
+    const unsigned long long imp = __ballot(improver) & live;
+    if (imp) { // (the improvers' values ascend: the last one stands)
+        const uint32_t last = 63u - (uint32_t)__builtin_clzll(imp);
+        best = __builtin_bit_cast(float, lane_of(__builtin_bit_cast(uint32_t, cur), last));
+        pred = (uint32_t)(base - (int32_t)last);
+    }
+    if (first > 0) skips += (int32_t)lane_of((uint32_t)moves, first - 1u);
+    return first < 64u;
+}
+// The num_best_chains best ends of the list [g0, g1) (rmap.cpp:175-179: score descending, then index descending) with traceback_chains on lane 0:
+// the chains' anchors to tmp_anchors behind the read's `na` so far, their records to s_rec[nc ..].  kScratch: the arrays are device memory --
+// a release and an acquire at agent scope stand between lane 0's marks and the wave's next look.
+template <bool kScratch> __device__ __forceinline__ void chain_ends(const ChainArgs &a, const unsigned long long *K1, const uint32_t *Q, const float *SC, const uint32_t *PR, unsigned char *FL,
+                                           const uint32_t key, const uint32_t g0, const uint32_t g1, const uint64_t s0, const float maxs, const uint32_t lane,
+                                           ChainRecDev *s_rec, uint32_t &nc, uint32_t &na, uint32_t &flags)
+{
+    const rawdtw_chain_opt_t &o = a.opt;
+    for (int k = 0; k < o.num_best_chains; k++) {
+        unsigned long long top = 0;
+        for (uint32_t i = g0 + lane; i < g1; i += 64)
+            if ((FL[i] & 6) == 2) top = max(top, (1ull << 63) | ((unsigned long long)__builtin_bit_cast(uint32_t, SC[i]) << 32) | i); // (scores are positive: their bits ascend with them)
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(top >> 32), d), lw = (uint32_t)__shfl_xor((int)(uint32_t)top, d);
+            top = max(top, ((unsigned long long)hi << 32) | lw);
+        }
+        if (!(top >> 63)) break;
+        const uint32_t end = (uint32_t)top;
+        bool below = false;
+        if (lane == 0) {
+            FL[end] |= 4;
+            if (!(FL[end] & 1)) {
+                const uint64_t out0 = s0 + na;
+                uint32_t cur = end, len = 1;
+                bool stop_at_used = false;
+                a.tmp_anchors[out0] = rawdtw_anchor_t{(uint32_t)K1[cur], Q[cur]};
+                if (PR[cur] != cur && (FL[PR[cur]] & 1)) stop_at_used = true;
+                FL[cur] |= 1;
+                while (PR[cur] != cur && !(FL[PR[cur]] & 1)) {
+                    cur = PR[cur];
+                    a.tmp_anchors[out0 + len] = rawdtw_anchor_t{(uint32_t)K1[cur], Q[cur]};
+                    len++;
+                    if (PR[cur] != cur && (FL[PR[cur]] & 1)) stop_at_used = true;
+                    FL[cur] |= 1;
+                }
+                if (len >= (uint32_t)o.min_num_anchors) {
+                    float adj = SC[end];
+                    if (stop_at_used) adj -= SC[PR[cur]];
+                    if (nc < kChainCap) s_rec[nc] = ChainRecDev{adj, key, (uint32_t)K1[cur], (uint32_t)K1[end], len, na};
+                    else flags |= 2u;
+                    nc++; na += len;
+                }
+            }
+            below = !o.disable_score_filtering && SC[end] < maxs / 2;                  // rmap.cpp:502-504
+        }
+        nc = uni(nc); na = uni(na); flags = uni(flags);
+        if (kScratch) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        lds_sync();
+        if (kScratch) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        if (uni(below ? 1u : 0u)) break;
+    }
+}
+// rmap.cpp:512 on one lane: read r's chains by chaining score, descending; equal scores keep their order (std::sort up to 16 elements, the tie
+// flag beyond); its records to tmp_recs in that order, its counts and flags to cnt
+__device__ __forceinline__ void chain_order(const ChainArgs &a, const uint32_t r, const uint32_t nc, const uint32_t na, uint32_t flags, const ChainRecDev *s_rec, uint32_t *s_perm)
+{
+    const uint32_t m = min(nc, kChainCap);
+    bool ties = false;
+    for (uint32_t i = 0; i < m; i++) {
+        const float v = s_rec[i].score;
+        uint32_t j = i;
+        while (j > 0 && v > s_rec[s_perm[j - 1]].score) { s_perm[j] = s_perm[j - 1]; j--; }
+        if (j > 0 && v == s_rec[s_perm[j - 1]].score) ties = true;
+        s_perm[j] = i;
+    }
+    if (nc > kChainStable && ties) flags |= 4u;
+    for (uint32_t i = 0; i < m; i++) a.tmp_recs[(uint64_t)r * kChainCap + i] = s_rec[s_perm[i]];
+    a.cnt[r] = ChainCnt{nc, na, flags, 0u};
+}
+
 __global__ __launch_bounds__(64) void k_chain(const ChainArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -124,14 +250,7 @@ __global__ __launch_bounds__(64) void k_chain(const ChainArgs a)
     float maxs = 0.0f;
     uint32_t nc = 0, na = 0, flags = 0;
     for (uint32_t g0 = 0; g0 < n;) {
-        // the (sequence, strand) list [g0, g1)
-        const uint32_t key = (uint32_t)(K1[g0] >> 32);
-        uint32_t g1 = n;
-        for (uint32_t i = g0; i < n; i += 64) {
-            const uint32_t x = i + lane;
-            const unsigned long long diff = __ballot(x < n && (uint32_t)(K1[x < n ? x : g0] >> 32) != key);
-            if (diff) { g1 = i + (uint32_t)__builtin_ctzll(diff); break; }
-        }
+        const uint32_t key = (uint32_t)(K1[g0] >> 32), g1 = list_end(K1, key, g0, n, lane); // the (sequence, strand) list [g0, g1)
         // ---- rmap.cpp:436-494 ----
         for (uint32_t ai = g0; ai < g1; ai++) {
             const int32_t ct = (int32_t)(uint32_t)K1[ai], cq = (int32_t)Q[ai];
@@ -144,101 +263,17 @@ __global__ __launch_bounds__(64) void k_chain(const ChainArgs a)
                 const bool valid = pi >= lo;
                 const int32_t pt = (int32_t)(uint32_t)K1[valid ? pi : lo], pq = (int32_t)Q[valid ? pi : lo];
                 const float sp = SC[valid ? pi : lo];
-                const bool pass12 = pq == cq || pt == ct;                                   // rmap.cpp:458-459
-                const bool stop_gap = valid && !pass12 && pt + o.max_target_gap_length < ct; // rmap.cpp:460
-                const int32_t td = ct - pt, qd = cq - pq;
-                const bool active = valid && !pass12 && !stop_gap && qd >= 0;               // rmap.cpp:467
-                float cur = 0.0f;
-                {
-                    const float matching = (float)min(min(td, qd), o.e);                    // rmap.cpp:469
-                    const int gap = abs(td - qd);
-                    const float scale = td > 0 ? __fdiv_rn((float)qd, (float)td) : 1.0f;
-                    if (gap < o.max_gap_length && scale < 5.0f && scale > 0.75f) cur = sp + matching; // rmap.cpp:474-476
-                }
-                const float cv = active ? cur : -1.0f;
-                // the candidates before this one, in loop order = lane order: their largest value, and `best` as it stood at the loop's entry
-                const float incl = scan_max(cv);
-                const float before = fmaxf(best, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, -1.0f), __builtin_bit_cast(int, incl), 0x138, 0xf, 0xf, false)));
-                const bool improver = active && cur > before;                               // rmap.cpp:478
-                const int32_t moves = scan_add(improver ? -1 : (active ? 1 : 0));
-                const bool stop_skip = active && !improver && skips + moves > o.max_num_skips; // rmap.cpp:482-484
-                const unsigned long long stop = __ballot(!valid || stop_gap || stop_skip);
-                const uint32_t first = stop ? (uint32_t)__builtin_ctzll(stop) : 64u;
-                const unsigned long long live = first >= 64u ? ~0ull : ((1ull << first) - 1ull);
-                const unsigned long long imp = __ballot(improver) & live;
-                if (imp) { // (the improvers' values ascend: the last one stands)
-                    const uint32_t last = 63u - (uint32_t)__builtin_clzll(imp);
-                    best = __builtin_bit_cast(float, lane_of(__builtin_bit_cast(uint32_t, cur), last));
-                    pred = (uint32_t)(base - (int32_t)last);
-                }
-                if (first > 0) skips += (int32_t)lane_of((uint32_t)moves, first - 1u);
-                if (first < 64u) break;
+                if (chain_step(o, ct, cq, base, valid, pt, pq, sp, best, pred, skips)) break;
             }
             if (best > maxs) maxs = best;                                                   // rmap.cpp:486-488
             const bool is_end = o.disable_score_filtering || (best >= o.min_chaining_score && best > maxs / 2); // rmap.cpp:489-493
             if (lane == 0) { SC[ai] = best; PR[ai] = pred; FL[ai] = is_end ? 2 : 0; }
             lds_sync();
         }
-        // ---- the num_best_chains best ends (rmap.cpp:175-179: score descending, then index descending), traceback_chains ----
-        for (int k = 0; k < o.num_best_chains; k++) {
-            unsigned long long top = 0;
-            for (uint32_t i = g0 + lane; i < g1; i += 64)
-                if ((FL[i] & 6) == 2) top = max(top, (1ull << 63) | ((unsigned long long)__builtin_bit_cast(uint32_t, SC[i]) << 32) | i); // (scores are positive: their bits ascend with them)
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(top >> 32), d), lw = (uint32_t)__shfl_xor((int)(uint32_t)top, d);
-                top = max(top, ((unsigned long long)hi << 32) | lw);
-            }
-            if (!(top >> 63)) break;
-            const uint32_t end = (uint32_t)top;
-            bool below = false;
-            if (lane == 0) {
-                FL[end] |= 4;
-                if (!(FL[end] & 1)) {
-                    const uint64_t out0 = s0 + na;
-                    uint32_t cur = end, len = 1;
-                    bool stop_at_used = false;
-                    a.tmp_anchors[out0] = rawdtw_anchor_t{(uint32_t)K1[cur], Q[cur]};
-                    if (PR[cur] != cur && (FL[PR[cur]] & 1)) stop_at_used = true;
-                    FL[cur] |= 1;
-                    while (PR[cur] != cur && !(FL[PR[cur]] & 1)) {
-                        cur = PR[cur];
-                        a.tmp_anchors[out0 + len] = rawdtw_anchor_t{(uint32_t)K1[cur], Q[cur]};
-                        len++;
-                        if (PR[cur] != cur && (FL[PR[cur]] & 1)) stop_at_used = true;
-                        FL[cur] |= 1;
-                    }
-                    if (len >= (uint32_t)o.min_num_anchors) {
-                        float adj = SC[end];
-                        if (stop_at_used) adj -= SC[PR[cur]];
-                        if (nc < kChainCap) s_rec[nc] = ChainRecDev{adj, key, (uint32_t)K1[cur], (uint32_t)K1[end], len, na};
-                        else flags |= 2u;
-                        nc++; na += len;
-                    }
-                }
-                below = !o.disable_score_filtering && SC[end] < maxs / 2;                  // rmap.cpp:502-504
-            }
-            nc = uni(nc); na = uni(na); flags = uni(flags);
-            lds_sync();
-            if (uni(below ? 1u : 0u)) break;
-        }
+        chain_ends<false>(a, K1, Q, SC, PR, FL, key, g0, g1, s0, maxs, lane, s_rec, nc, na, flags);
         g0 = g1;
     }
-    // ---- rmap.cpp:512: by chaining score, descending; equal scores keep their order (std::sort up to 16 elements) ----
-    if (lane == 0) {
-        const uint32_t m = min(nc, kChainCap);
-        bool ties = false;
-        for (uint32_t i = 0; i < m; i++) {
-            const float v = s_rec[i].score;
-            uint32_t j = i;
-            while (j > 0 && v > s_rec[s_perm[j - 1]].score) { s_perm[j] = s_perm[j - 1]; j--; }
-            if (j > 0 && v == s_rec[s_perm[j - 1]].score) ties = true;
-            s_perm[j] = i;
-        }
-        if (nc > kChainStable && ties) flags |= 4u;
-        for (uint32_t i = 0; i < m; i++) a.tmp_recs[(uint64_t)r * kChainCap + i] = s_rec[s_perm[i]];
-        a.cnt[r] = ChainCnt{nc, na, flags, 0u};
-    }
+    if (lane == 0) chain_order(a, r, nc, na, flags, s_rec, s_perm);
 }
 
 // ---- the long path: reads above k_chain's cap, state in device memory ----
@@ -379,14 +414,7 @@ __global__ __launch_bounds__(64) void k_chain_long(const ChainArgs a, const Long
         flushed = upto;
     };
     for (uint32_t g0 = 0; g0 < n;) {
-        // the (sequence, strand) list [g0, g1)
-        const uint32_t key = (uint32_t)(K1[g0] >> 32);
-        uint32_t g1 = n;
-        for (uint32_t i = g0; i < n; i += 64) {
-            const uint32_t x = i + lane;
-            const unsigned long long diff = __ballot(x < n && (uint32_t)(K1[x < n ? x : g0] >> 32) != key);
-            if (diff) { g1 = i + (uint32_t)__builtin_ctzll(diff); break; }
-        }
+        const uint32_t key = (uint32_t)(K1[g0] >> 32), g1 = list_end(K1, key, g0, n, lane); // the (sequence, strand) list [g0, g1)
         // ---- rmap.cpp:436-494 ----
         for (uint32_t ai = g0; ai < g1; ai++) {
             if (ai == 0 || (ai & 63u) == 0) { // the next block: registers and ring
@@ -409,34 +437,7 @@ __global__ __launch_bounds__(64) void k_chain_long(const ChainArgs a, const Long
                 if (!is_far) { pt = (int32_t)r_t[slot(x)]; pq = (int32_t)r_q[slot(x)]; sp = r_s[slot(x)]; }
                 else { pt = (int32_t)(uint32_t)K1[x]; pq = (int32_t)Q[x]; sp = __hip_atomic_load(SC + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
                 if (__ballot(valid && is_far)) far++;
-                const bool pass12 = pq == cq || pt == ct;                                   // rmap.cpp:458-459
-                const bool stop_gap = valid && !pass12 && pt + o.max_target_gap_length < ct; // rmap.cpp:460
-                const int32_t td = ct - pt, qd = cq - pq;
-                const bool active = valid && !pass12 && !stop_gap && qd >= 0;               // rmap.cpp:467
-                float cur = 0.0f;
-                {
-                    const float matching = (float)min(min(td, qd), o.e);                    // rmap.cpp:469
-                    const int gap = abs(td - qd);
-                    const float scale = td > 0 ? __fdiv_rn((float)qd, (float)td) : 1.0f;
-                    if (gap < o.max_gap_length && scale < 5.0f && scale > 0.75f) cur = sp + matching; // rmap.cpp:474-476
-                }
-                const float cv = active ? cur : -1.0f;
-                const float incl = scan_max(cv);
-                const float before = fmaxf(best, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, -1.0f), __builtin_bit_cast(int, incl), 0x138, 0xf, 0xf, false)));
-                const bool improver = active && cur > before;                               // rmap.cpp:478
-                const int32_t moves = scan_add(improver ? -1 : (active ? 1 : 0));
-                const bool stop_skip = active && !improver && skips + moves > o.max_num_skips; // rmap.cpp:482-484
-                const unsigned long long stop = __ballot(!valid || stop_gap || stop_skip);
-                const uint32_t first = stop ? (uint32_t)__builtin_ctzll(stop) : 64u;
-                const unsigned long long live = first >= 64u ? ~0ull : ((1ull << first) - 1ull);
-                const unsigned long long imp = __ballot(improver) & live;
-                if (imp) { // (the improvers' values ascend: the last one stands)
-                    const uint32_t last = 63u - (uint32_t)__builtin_clzll(imp);
-                    best = __builtin_bit_cast(float, lane_of(__builtin_bit_cast(uint32_t, cur), last));
-                    pred = (uint32_t)(base - (int32_t)last);
-                }
-                if (first > 0) skips += (int32_t)lane_of((uint32_t)moves, first - 1u);
-                if (first < 64u) break;
+                if (chain_step(o, ct, cq, base, valid, pt, pq, sp, best, pred, skips)) break;
             }
             if (best > maxs) maxs = best;                                                   // rmap.cpp:486-488
             const bool is_end = o.disable_score_filtering || (best >= o.min_chaining_score && best > maxs / 2); // rmap.cpp:489-493
@@ -447,71 +448,14 @@ __global__ __launch_bounds__(64) void k_chain_long(const ChainArgs a, const Long
         }
         if (flushed < g1) flush(g1);
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        // ---- the num_best_chains best ends (rmap.cpp:175-179: score descending, then index descending), traceback_chains ----
-        for (int k = 0; k < o.num_best_chains; k++) {
-            unsigned long long top = 0;
-            for (uint32_t i = g0 + lane; i < g1; i += 64)
-                if ((FL[i] & 6) == 2) top = max(top, (1ull << 63) | ((unsigned long long)__builtin_bit_cast(uint32_t, SC[i]) << 32) | i); // (scores are positive: their bits ascend with them)
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(top >> 32), d), lw = (uint32_t)__shfl_xor((int)(uint32_t)top, d);
-                top = max(top, ((unsigned long long)hi << 32) | lw);
-            }
-            if (!(top >> 63)) break;
-            const uint32_t end = (uint32_t)top;
-            bool below = false;
-            if (lane == 0) {
-                FL[end] |= 4;
-                if (!(FL[end] & 1)) {
-                    const uint64_t out0 = s0 + na;
-                    uint32_t cur = end, len = 1;
-                    bool stop_at_used = false;
-                    a.tmp_anchors[out0] = rawdtw_anchor_t{(uint32_t)K1[cur], Q[cur]};
-                    if (PR[cur] != cur && (FL[PR[cur]] & 1)) stop_at_used = true;
-                    FL[cur] |= 1;
-                    while (PR[cur] != cur && !(FL[PR[cur]] & 1)) {
-                        cur = PR[cur];
-                        a.tmp_anchors[out0 + len] = rawdtw_anchor_t{(uint32_t)K1[cur], Q[cur]};
-                        len++;
-                        if (PR[cur] != cur && (FL[PR[cur]] & 1)) stop_at_used = true;
-                        FL[cur] |= 1;
-                    }
-                    if (len >= (uint32_t)o.min_num_anchors) {
-                        float adj = SC[end];
-                        if (stop_at_used) adj -= SC[PR[cur]];
-                        if (nc < kChainCap) s_rec[nc] = ChainRecDev{adj, key, (uint32_t)K1[cur], (uint32_t)K1[end], len, na};
-                        else flags |= 2u;
-                        nc++; na += len;
-                    }
-                }
-                below = !o.disable_score_filtering && SC[end] < maxs / 2;                  // rmap.cpp:502-504
-            }
-            nc = uni(nc); na = uni(na); flags = uni(flags);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            lds_sync();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            if (uni(below ? 1u : 0u)) break;
-        }
+        chain_ends<true>(a, K1, Q, SC, PR, FL, key, g0, g1, s0, maxs, lane, s_rec, nc, na, flags);
         g0 = g1;
     }
-    // ---- rmap.cpp:512: by chaining score, descending; equal scores keep their order (std::sort up to 16 elements) ----
     if (lane == 0) {
-        const uint32_t m = min(nc, kChainCap);
-        bool ties = false;
-        for (uint32_t i = 0; i < m; i++) {
-            const float v = s_rec[i].score;
-            uint32_t j = i;
-            while (j > 0 && v > s_rec[s_perm[j - 1]].score) { s_perm[j] = s_perm[j - 1]; j--; }
-            if (j > 0 && v == s_rec[s_perm[j - 1]].score) ties = true;
-            s_perm[j] = i;
-        }
-        if (nc > kChainStable && ties) flags |= 4u;
-        for (uint32_t i = 0; i < m; i++) a.tmp_recs[(uint64_t)r * kChainCap + i] = s_rec[s_perm[i]];
-        a.cnt[r] = ChainCnt{nc, na, flags, 0u};
+        chain_order(a, r, nc, na, flags, s_rec, s_perm);
         if (far) atomicAdd(la.far_steps, (unsigned long long)far);
     }
 }
-
 
 // the reads' chains and anchors before each read; the round's totals and its flags
 __global__ __launch_bounds__(1024) void k_chain_scan(const ChainCnt *__restrict__ cnt, const uint32_t n_reads, uint64_t *__restrict__ chain_off,
@@ -571,6 +515,38 @@ __global__ __launch_bounds__(64) void k_chain_compact(const ChainArgs a, const u
     }
     if (r == 0 && lane == 0) { anchor_off[totals[0]] = totals[1]; if (host) h_anchor_off[totals[0]] = totals[1]; }
 }
+
+using capi::carve;
+// A round's workspace, described once: lay(0) gives the bytes it needs, lay(the block's base) the round's pointers.  Every array starts on a
+// multiple of 256 bytes; the arrays of a resident round and of the long path take no space in a round that has none.
+struct ChainLayout {
+    uint64_t n_reads, n_seeds, n_keys;
+    bool resident;
+    uint64_t n_prev, n_long, long_elems; // (long_elems: the long reads' seeds, each read's stretch rounded up to 64)
+    uint64_t *soff; rawdtw_seed_t *seeds; uint32_t *rb; uint64_t *kb;                          // inputs
+    rawdtw_anchor_t *tmpa; ChainRecDev *trec; ChainCnt *cnt; uint64_t *coff, *ra0;             // per-read scratch
+    uint64_t *tot;                                                                             // chains, anchors, flags, bad keys; [4]: the long path's far steps
+    uint64_t *aoff; rawdtw_anchor_t *anch; uint64_t *refb; uint32_t *rbc; rawdtw_chain_rec_t *recs; // the batch's arrays
+    rawdtw_seed_t *prev; uint64_t *poff; uint32_t *cs; uint8_t *so; // a resident round: the previous anchors, dense, their offsets, the chunk starts, the sits-out flags
+    LongArgs la;                                               // the long reads' list and their scratch: 21 bytes a seed -- K1 8, Q 4, SC 4, PR 4, FL 1
+
+    size_t lay(void *base)
+    {
+        uintptr_t p = reinterpret_cast<uintptr_t>(base);
+        const uint64_t nc = n_reads * kChainCap, nres = resident ? n_reads : 0;
+        soff = carve<uint64_t>(p, n_reads + 1); seeds = carve<rawdtw_seed_t>(p, n_seeds + 2); rb = carve<uint32_t>(p, n_reads); kb = carve<uint64_t>(p, n_keys + 1);
+        tmpa = carve<rawdtw_anchor_t>(p, n_seeds + 2); trec = carve<ChainRecDev>(p, nc); cnt = carve<ChainCnt>(p, n_reads);
+        coff = carve<uint64_t>(p, n_reads + 1); ra0 = carve<uint64_t>(p, n_reads); tot = carve<uint64_t>(p, 5);
+        aoff = carve<uint64_t>(p, nc + 1); anch = carve<rawdtw_anchor_t>(p, n_seeds + 2); refb = carve<uint64_t>(p, nc + 1); rbc = carve<uint32_t>(p, nc + 2);
+        recs = carve<rawdtw_chain_rec_t>(p, nc + 1);
+        prev = carve<rawdtw_seed_t>(p, resident ? n_prev + 2 : 0); poff = carve<uint64_t>(p, resident ? n_reads + 1 : 0); cs = carve<uint32_t>(p, nres);
+        so = carve<uint8_t>(p, nres);
+        la.reads = carve<LongRead>(p, n_long); la.K1 = carve<unsigned long long>(p, long_elems); la.Q = carve<uint32_t>(p, long_elems);
+        la.SC = carve<float>(p, long_elems); la.PR = carve<uint32_t>(p, long_elems); la.FL = carve<unsigned char>(p, long_elems);
+        la.far_steps = reinterpret_cast<unsigned long long *>(tot) + 4;
+        return (size_t)(p - reinterpret_cast<uintptr_t>(base));
+    }
+};
 
 struct ChainWs {
     void *dev = nullptr;
@@ -657,20 +633,9 @@ int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads
                                                                    : "a read has more seeds than the device chains (2048): chain this round on the host");
     uint32_t n2 = 64;
     while (n2 < most) n2 <<= 1;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    // one block of device memory, grow-only: inputs, per-read scratch, the batch's arrays
-    const size_t b_soff = al((n_reads + 1) * 8), b_seeds = al((size_t)n_seeds * sizeof(rawdtw_seed_t) + 16), b_rb = al(n_reads * 4), b_kb = al((size_t)n_keys * 8 + 8),
-                 b_tmpa = al((size_t)n_seeds * 8 + 16), b_trec = al(n_reads * kChainCap * sizeof(ChainRecDev)), b_cnt = al(n_reads * sizeof(ChainCnt)),
-                 b_coff = al((n_reads + 1) * 8), b_ra0 = al(n_reads * 8), b_tot = al(32), b_aoff = al((n_reads * kChainCap + 1) * 8), b_anch = al((size_t)n_seeds * 8 + 16),
-                 b_refb = al(n_reads * kChainCap * 8 + 8), b_rbc = al(n_reads * kChainCap * 4 + 8), b_recs = al(n_reads * kChainCap * sizeof(rawdtw_chain_rec_t) + 8);
-    // (a resident round: the previous anchors, dense, their offsets, the chunk starts and the sits-out flags, behind everything else)
-    const size_t b_prev = res ? al((size_t)n_prev * sizeof(rawdtw_seed_t) + 16) : 0, b_poff = res ? al((n_reads + 1) * 8) : 0, b_cs = res ? al(n_reads * 4) : 0,
-                 b_so = res ? al(n_reads) : 0;
-    // (the long reads' list and their scratch, behind that: 21 bytes a seed -- K1 8, Q 4, SC 4, PR 4, FL 1 -- each read's stretch rounded up to 64 seeds)
-    const size_t b_lr = n_long ? al(n_long * sizeof(LongRead)) : 0, b_lk = n_long ? al(long_elems * 8) : 0, b_l4 = n_long ? al(long_elems * 4) : 0,
-                 b_l1 = n_long ? al(long_elems) : 0;
-    const size_t need = b_soff + b_seeds + b_rb + b_kb + b_tmpa + b_trec + b_cnt + b_coff + b_ra0 + b_tot + b_aoff + b_anch + b_refb + b_rbc + b_recs + b_prev + b_poff + b_cs + b_so +
-                        b_lr + b_lk + 3 * b_l4 + b_l1;
+    // one block of device memory, grow-only: laid out from 0 for its size, from the block's base for the round's pointers
+    ChainLayout L{n_reads, n_seeds, n_keys, res != nullptr, n_prev, n_long, long_elems};
+    const size_t need = L.lay(nullptr);
     if (!ctx->chain_ws) ctx->chain_ws = new (std::nothrow) rawdtw_chain_ws;
     if (!ctx->chain_ws) return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed");
     ChainWs &w = ctx->chain_ws->w;
@@ -690,56 +655,29 @@ int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads
         w.dev_bytes = want;
     }
     if (!w.pin && hipHostMalloc(&w.pin, 64, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); w.pin = nullptr; return fail(ctx, RAWDTW_ERR_OOM, "pinned allocation failed"); }
-    char *p = static_cast<char *>(w.dev);
-    uint64_t *d_soff = reinterpret_cast<uint64_t *>(p); p += b_soff;
-    rawdtw_seed_t *d_seeds = reinterpret_cast<rawdtw_seed_t *>(p); p += b_seeds;
-    uint32_t *d_rb = reinterpret_cast<uint32_t *>(p); p += b_rb;
-    uint64_t *d_kb = reinterpret_cast<uint64_t *>(p); p += b_kb;
-    rawdtw_anchor_t *d_tmpa = reinterpret_cast<rawdtw_anchor_t *>(p); p += b_tmpa;
-    ChainRecDev *d_trec = reinterpret_cast<ChainRecDev *>(p); p += b_trec;
-    ChainCnt *d_cnt = reinterpret_cast<ChainCnt *>(p); p += b_cnt;
-    uint64_t *d_coff = reinterpret_cast<uint64_t *>(p); p += b_coff;
-    uint64_t *d_ra0 = reinterpret_cast<uint64_t *>(p); p += b_ra0;
-    uint64_t *d_tot = reinterpret_cast<uint64_t *>(p); p += b_tot;
-    uint64_t *d_aoff = reinterpret_cast<uint64_t *>(p); p += b_aoff;
-    rawdtw_anchor_t *d_anch = reinterpret_cast<rawdtw_anchor_t *>(p); p += b_anch;
-    uint64_t *d_refb = reinterpret_cast<uint64_t *>(p); p += b_refb;
-    uint32_t *d_rbc = reinterpret_cast<uint32_t *>(p); p += b_rbc;
-    rawdtw_chain_rec_t *d_recs = reinterpret_cast<rawdtw_chain_rec_t *>(p); p += b_recs;
-    rawdtw_seed_t *d_prev = reinterpret_cast<rawdtw_seed_t *>(p); p += b_prev;
-    uint64_t *d_poff = reinterpret_cast<uint64_t *>(p); p += b_poff;
-    uint32_t *d_cs = reinterpret_cast<uint32_t *>(p); p += b_cs;
-    uint8_t *d_so = reinterpret_cast<uint8_t *>(p); p += b_so;
-    LongArgs la{};
-    la.reads = reinterpret_cast<LongRead *>(p); p += b_lr;
-    la.K1 = reinterpret_cast<unsigned long long *>(p); p += b_lk;
-    la.Q = reinterpret_cast<uint32_t *>(p); p += b_l4;
-    la.SC = reinterpret_cast<float *>(p); p += b_l4;
-    la.PR = reinterpret_cast<uint32_t *>(p); p += b_l4;
-    la.FL = reinterpret_cast<unsigned char *>(p);
-    la.far_steps = reinterpret_cast<unsigned long long *>(d_tot) + 4;
+    (void)L.lay(w.dev);
     hipStream_t s = ctx->stream;
-    HIP_TRY(ctx, hipMemcpyAsync(d_soff, seed_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(L.soff, seed_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, s));
     if (res) { // only the previous anchors go up; rawdtw_seed.hip's writer puts them and the hits in place
-        if (n_prev) HIP_TRY(ctx, hipMemcpyAsync(d_prev, res->prev_seeds, (size_t)n_prev * sizeof(rawdtw_seed_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemcpyAsync(d_poff, res->prev_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemcpyAsync(d_cs, res->chunk_start, n_reads * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemcpyAsync(d_so, res->sits_out, n_reads, hipMemcpyHostToDevice, s));
-        seed_resident_write_chain(ctx, d_seeds, d_soff, d_poff, d_prev, d_cs, d_so);
+        if (n_prev) HIP_TRY(ctx, hipMemcpyAsync(L.prev, res->prev_seeds, (size_t)n_prev * sizeof(rawdtw_seed_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(L.poff, res->prev_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(L.cs, res->chunk_start, n_reads * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(L.so, res->sits_out, n_reads, hipMemcpyHostToDevice, s));
+        seed_resident_write_chain(ctx, L.seeds, L.soff, L.poff, L.prev, L.cs, L.so);
         HIP_TRY(ctx, hipGetLastError());
-    } else if (n_seeds) HIP_TRY(ctx, hipMemcpyAsync(d_seeds, seeds, (size_t)n_seeds * sizeof(rawdtw_seed_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d_rb, read_base, n_reads * 4, hipMemcpyHostToDevice, s));
-    if (n_keys) HIP_TRY(ctx, hipMemcpyAsync(d_kb, key_base, (size_t)n_keys * 8, hipMemcpyHostToDevice, s));
-    ChainArgs a{d_soff, d_seeds, (uint32_t)n_reads, n2, *opt, d_tmpa, d_trec, d_cnt};
+    } else if (n_seeds) HIP_TRY(ctx, hipMemcpyAsync(L.seeds, seeds, (size_t)n_seeds * sizeof(rawdtw_seed_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(L.rb, read_base, n_reads * 4, hipMemcpyHostToDevice, s));
+    if (n_keys) HIP_TRY(ctx, hipMemcpyAsync(L.kb, key_base, (size_t)n_keys * 8, hipMemcpyHostToDevice, s));
+    ChainArgs a{L.soff, L.seeds, (uint32_t)n_reads, n2, *opt, L.tmpa, L.trec, L.cnt};
     const size_t lds = (size_t)n2 * 21 + 16;
     hipLaunchKernelGGL(k_chain, dim3((uint32_t)n_reads), dim3(64), lds, s, a);
     if (n_long) { // behind k_chain, which has flagged these reads as too long for it: the long launch writes their cnt over that
-        HIP_TRY(ctx, hipMemcpyAsync(const_cast<LongRead *>(la.reads), w.long_reads.data(), n_long * sizeof(LongRead), hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemsetAsync(la.far_steps, 0, 8, s));
-        hipLaunchKernelGGL(k_chain_sort_long, dim3((uint32_t)n_long), dim3(256), 0, s, a, la);
-        hipLaunchKernelGGL(k_chain_long, dim3((uint32_t)n_long), dim3(64), 0, s, a, la);
+        HIP_TRY(ctx, hipMemcpyAsync(const_cast<LongRead *>(L.la.reads), w.long_reads.data(), n_long * sizeof(LongRead), hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemsetAsync(L.la.far_steps, 0, 8, s));
+        hipLaunchKernelGGL(k_chain_sort_long, dim3((uint32_t)n_long), dim3(256), 0, s, a, L.la);
+        hipLaunchKernelGGL(k_chain_long, dim3((uint32_t)n_long), dim3(64), 0, s, a, L.la);
     }
-    hipLaunchKernelGGL(k_chain_scan, dim3(1), dim3(1024), 0, s, d_cnt, (uint32_t)n_reads, d_coff, d_ra0, d_tot);
+    hipLaunchKernelGGL(k_chain_scan, dim3(1), dim3(1024), 0, s, L.cnt, (uint32_t)n_reads, L.coff, L.ra0, L.tot);
     // the caller's arrays: written by the compaction launch itself when they are page-locked (rawdtw_host_alloc) -- no copy command, no second
     // wait for sizes only the device knows; else copied at the round's end
     auto page_locked = [](const void *q) {
@@ -748,12 +686,12 @@ int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads
         return at.type == hipMemoryTypeHost;
     };
     const bool direct = page_locked(anchor_off) && page_locked(recs) && (!anchors || page_locked(anchors)) && page_locked(chain_off);
-    hipLaunchKernelGGL(k_chain_compact, dim3((uint32_t)n_reads), dim3(64), 0, s, a, d_coff, d_ra0, d_rb, d_kb, n_keys, d_aoff, d_anch, d_refb, d_rbc, d_recs, d_tot,
+    hipLaunchKernelGGL(k_chain_compact, dim3((uint32_t)n_reads), dim3(64), 0, s, a, L.coff, L.ra0, L.rb, L.kb, n_keys, L.aoff, L.anch, L.refb, L.rbc, L.recs, L.tot,
                        direct ? anchor_off : nullptr, direct ? recs : nullptr, direct ? anchors : nullptr, chains_cap);
     HIP_TRY(ctx, hipGetLastError());
     uint64_t *h_tot = static_cast<uint64_t *>(w.pin);
-    HIP_TRY(ctx, hipMemcpyAsync(h_tot, d_tot, n_long ? 40 : 32, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipMemcpyAsync(chain_off, d_coff, (n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(h_tot, L.tot, n_long ? 40 : 32, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(chain_off, L.coff, (n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
     if (!w.done) HIP_TRY(ctx, hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
     HIP_TRY(ctx, hipEventRecord(w.done, s));
     w.pending = true; w.direct = direct; w.n_reads = n_reads; w.chains_cap = chains_cap;
@@ -761,7 +699,7 @@ int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads
     w.st_rounds++; w.st_long_reads += n_long;
     for (uint64_t k = 0; k < n_long; k++) w.st_long_seeds += seed_off[w.long_reads[k].r + 1] - seed_off[w.long_reads[k].r];
     w.h_anchor_off = anchor_off; w.h_recs = recs; w.h_anchors = anchors;
-    w.d_aoff = d_aoff; w.d_recs = d_recs; w.d_anch = d_anch; w.d_refb = d_refb; w.d_rbc = d_rbc;
+    w.d_aoff = L.aoff; w.d_recs = L.recs; w.d_anch = L.anch; w.d_refb = L.refb; w.d_rbc = L.rbc;
     return RAWDTW_OK;
 }
 

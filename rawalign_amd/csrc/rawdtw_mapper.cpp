@@ -299,11 +299,9 @@ struct rawdtw_mapper {
     bool su_closed_any = false;   // a batch has been closed (the parameters are fixed from then on)
     bool su_stopped = false;
     uint32_t su_mapped = 0;       // mapped reads of closed batches before the gate
-    // rawdtw_mapper_round_seeded: the round's hits, page-locked when the mapper has a context (the device writes them itself), grow-only
-    uint64_t *seed_off = nullptr;
-    rawdtw_seed_hit_t *seed_hits = nullptr;
-    uint64_t seed_off_cap = 0, seed_hits_cap = 0;
-    bool seed_pinned = false;
+    // rawdtw_mapper_round_seeded: the round's hits, page-locked when the mapper has a context (the device writes them itself: seed_room)
+    PinBuf<uint64_t> seed_off;
+    PinBuf<rawdtw_seed_hit_t> seed_hits;
     // rawdtw_mapper_round_seeded_resident (rawdtw_mapper_resident_stats)
     uint64_t res_rounds = 0, res_fallbacks = 0, res_hit_bytes = 0, res_seed_bytes = 0;
 };
@@ -348,26 +346,11 @@ int fail(rawdtw_mapper *m, int st, const std::string &msg)
     return st;
 }
 
-void seed_buffers_free(rawdtw_mapper *m)
+// room for `count` records in one of the seeding's buffers (contents are not kept).  With a context the device writes into them: page-locked,
+// or no room -- PinBuf's fall-back to plain memory does not reach them.
+template <typename T> bool seed_room(const rawdtw_mapper *m, PinBuf<T> &b, uint64_t count)
 {
-    for (void *p : {(void *)m->seed_off, (void *)m->seed_hits})
-        if (p) { if (m->seed_pinned) rawdtw_host_free(p); else free(p); }
-    m->seed_off = nullptr; m->seed_hits = nullptr; m->seed_off_cap = m->seed_hits_cap = 0;
-}
-
-// room for `count` records in one of the seeding's buffers (contents are not kept)
-template <typename T> int seed_buffer(rawdtw_mapper *m, T **p, uint64_t *cap, uint64_t count)
-{
-    if (*cap >= count) return RAWDTW_OK;
-    if (*p) { if (m->seed_pinned) rawdtw_host_free(*p); else free(*p); }
-    *p = nullptr; *cap = 0;
-    const uint64_t want = count + count / 4 + 64;
-    void *q = nullptr;
-    if (m->seed_pinned) { if (rawdtw_host_alloc(want * sizeof(T), &q) != RAWDTW_OK) q = nullptr; }
-    else q = malloc(want * sizeof(T));
-    if (!q) return RAWDTW_ERR_OOM;
-    *p = static_cast<T *>(q); *cap = want;
-    return RAWDTW_OK;
+    return b.ensure(count, m->ctx != nullptr) && (b.pinned || !m->ctx);
 }
 
 void drop_batches(rawdtw_mapper *m) // (and with them what a round could carry from)
@@ -626,11 +609,9 @@ struct Round {
             const uint32_t k = ra.ks[i];
             if (append_events(k)) rr[k].n_seeds = seed_count(read(k), hit_off[k + 1] - hit_off[k]);
         });
-        uint64_t ns = 0, nev = 0, nseg = 0;
-        for (uint32_t k : ra.ks) { RoundRead &r = rr[k]; r.seed0 = ns; ns += r.n_seeds; r.ev0 = nev; nev += r.ne; nseg += r.ne ? 1 : 0; }
-        const Sizes n{nr, 0, 0, 0, nev, nseg, ns};
-        if (!size_arrays(g, n, true)) return true;
-        write_segments(ra, events_in_place);
+        Sizes n{nr};
+        for (uint32_t k : ra.ks) { rr[k].seed0 = n.seeds; n.seeds += rr[k].n_seeds; }
+        if (!stage_events(g, n, true, events_in_place)) return true;
         ra.seed_off[nr] = n.seeds;
         m->pool->run(nr, 64, [&](size_t i) {
             const uint32_t k = ra.ks[i];
@@ -638,7 +619,7 @@ struct Round {
             ra.seed_off[i] = r.seed0;
             ra.read_base[i] = arena_base(read(k));
             if (!r.skipped) write_seeds(read(k), hits + hit_off[k], hit_off[k + 1] - hit_off[k], r.chunk_start, ra.seeds.p + r.seed0);
-            if (r.ne && !events_in_place) memcpy(ra.new_events.p + r.ev0, events + event_off[k], r.ne * sizeof(float));
+            if (!events_in_place) stage_chunk(ra, k);
         });
         lap(0);
         // the chaining first, the events behind it: the sort + DP does not read them, and rawdtw_chain_round_end waits for the round's own work only
@@ -647,9 +628,7 @@ struct Round {
                                           ra.chain_off.p, ra.anchor_off.p, ra.recs.p, g.hw_chains, ra.anchors.p);
         const bool declined = st == RAWDTW_ERR_UNSUPPORTED;
         if (st == RAWDTW_OK || declined) {
-            int se = RAWDTW_OK;
-            if (n.seg && events_in_place) se = rawdtw_events_append(g.ctx, events, event_off[n_reads], (uint32_t)nr, event_off, ra.seg_dst.p);
-            else if (n.seg) se = rawdtw_events_append(g.ctx, ra.new_events.p, n.events, (uint32_t)n.seg, ra.seg_src.p, ra.seg_dst.p);
+            const int se = upload_events(g, n, events_in_place);
             if (se != RAWDTW_OK && st == RAWDTW_OK) discard_chain_round(g.ctx);
             if (se != RAWDTW_OK) st = se;
         }
@@ -669,32 +648,29 @@ struct Round {
         ra.carried = false; ra.round_id = id; ra.n_reads = ra.ks.size();
         const size_t nr = ra.ks.size();
         m->pool->run(nr, 64, [&](size_t i) { append_events(ra.ks[i]); });
-        uint64_t nev = 0, nseg = 0;
-        for (uint32_t k : ra.ks) { RoundRead &r = rr[k]; r.ev0 = nev; nev += r.ne; nseg += r.ne ? 1 : 0; }
-        if (!size_arrays(g, Sizes{nr, 0, 0, 0, nev, nseg, 0}, true)) return;
+        Sizes n{nr};
+        if (!stage_events(g, n, true, events_in_place)) return;
+        const uint64_t nev = n.events, nseg = n.seg;
         for (int b = 0; b < 2; b++) {
             RoundArrays &x = g.buf[g.cur ^ b];
             if (!(x.prev_off.ensure(g.hw_reads + 1, true) && x.ev_start.ensure(g.hw_reads + 1, true) && x.ev_len.ensure(g.hw_reads + 1, true) &&
                   x.chunk_start.ensure(g.hw_reads + 1, true) && x.sits_out.ensure(g.hw_reads + 1, true)))
                 return failed(RAWDTW_ERR_OOM, "host allocation failed");
         }
-        write_segments(ra, events_in_place);
         m->pool->run(nr, 64, [&](size_t i) {
             const uint32_t k = ra.ks[i];
             const RoundRead &r = rr[k];
             ra.ev_start[i] = (uint64_t)arena_base(read(k)) + r.ev_before;
             ra.ev_len[i] = (uint32_t)r.ne;
-            if (r.ne && !events_in_place) memcpy(ra.new_events.p + r.ev0, events + event_off[k], r.ne * sizeof(float));
+            if (!events_in_place) stage_chunk(ra, k);
         });
         lap(0);
-        int st = RAWDTW_OK;
-        if (nseg && events_in_place) st = rawdtw_events_append(g.ctx, events, event_off[n_reads], (uint32_t)nr, event_off, ra.seg_dst.p);
-        else if (nseg) st = rawdtw_events_append(g.ctx, ra.new_events.p, nev, (uint32_t)nseg, ra.seg_src.p, ra.seg_dst.p);
-        if (st == RAWDTW_OK) st = rawdtw_seed_resident_begin(g.ctx, (uint32_t)nr, ra.ev_start.p, ra.ev_len.p, m->seed_off);
+        int st = upload_events(g, n, events_in_place);
+        if (st == RAWDTW_OK) st = rawdtw_seed_resident_begin(g.ctx, (uint32_t)nr, ra.ev_start.p, ra.ev_len.p, m->seed_off.p);
         if (st == RAWDTW_OK) st = rawdtw_seed_resident_end(g.ctx, nullptr);
         lap(2);
         if (st != RAWDTW_OK) return failed(st, rawdtw_last_error(g.ctx));
-        const uint64_t *hoff = m->seed_off; // (chunk i is read ks[i]: one group, the round's reads in order)
+        const uint64_t *hoff = m->seed_off.p; // (chunk i is read ks[i]: one group, the round's reads in order)
         uint64_t ns = 0, np = 0;
         for (size_t i = 0; i < nr; i++) {
             RoundRead &r = rr[ra.ks[i]];
@@ -734,10 +710,10 @@ struct Round {
     bool fetch_resident_hits(uint32_t gi)
     {
         const uint64_t tot = m->seed_off[n_reads];
-        if (seed_buffer(m, &m->seed_hits, &m->seed_hits_cap, tot + 1) != RAWDTW_OK) { failed(RAWDTW_ERR_OOM, "no page-locked memory for the round's hits"); return false; }
-        const int st = rawdtw_seed_resident_fetch(m->groups[gi].ctx, m->seed_hits, m->seed_hits_cap);
+        if (!seed_room(m, m->seed_hits, tot + 1)) { failed(RAWDTW_ERR_OOM, "no page-locked memory for the round's hits"); return false; }
+        const int st = rawdtw_seed_resident_fetch(m->groups[gi].ctx, m->seed_hits.p, m->seed_hits.cap);
         if (st != RAWDTW_OK) { failed(st, rawdtw_last_error(m->groups[gi].ctx)); return false; }
-        hit_off = m->seed_off; hits = m->seed_hits;
+        hit_off = m->seed_off.p; hits = m->seed_hits.p;
         fell_back = true; res_hits = tot;
         lap(2);
         return true;
@@ -810,25 +786,22 @@ struct Round {
         Sizes n{nr};
         for (uint32_t k : ra.ks) {
             RoundRead &r = rr[k];
-            r.chain0 = n.chains; r.anchor0 = n.anchors; r.new0 = n.new_anchors; r.ev0 = n.events;
+            r.chain0 = n.chains; r.anchor0 = n.anchors; r.new0 = n.new_anchors;
             n.chains += r.chains.size();
             for (size_t c = 0; c < r.chains.size(); c++) {
                 n.anchors += r.chains[c].anchors.size();
                 n.new_anchors += r.chains[c].anchors.size() - r.carry[c].parts; // (the new entries and, when a stretch is taken over, the junction)
             }
-            n.events += events_done ? 0 : r.ne;
-            n.seg += !events_done && r.ne ? 1 : 0;
         }
         const uint64_t nc = n.chains, na = n.anchors;
         ra.n_chains = nc; ra.n_anchors = na;
-        if (!size_arrays(g, n, false)) return;
+        const bool stage = on_device && !events_done; // (an external scorer reads the host's copy of the events)
+        if (!(stage ? stage_events(g, n, false, false) : size_arrays(g, n, false))) return;
         if (m->scorer) { ra.chain_seq.resize(nc); ra.chain_strand.resize(nc); }
         ra.chain_off[nr] = nc; ra.anchor_off[nc] = na;
         if (ra.carried) ra.new_off[nc] = n.new_anchors;
         ra.ref_base[nc] = 0; ra.read_base[nc] = 0; // (non-null, initialised arrays for a round without chains)
         ra.anchors[na] = rawdtw_anchor_t{0, 0};
-        const bool stage = on_device && !events_done;
-        if (stage) write_segments(ra, false);
         m->pool->run(nr, 32, [&](size_t i) {
             const uint32_t k = ra.ks[i];
             const RoundRead &r = rr[k];
@@ -852,13 +825,12 @@ struct Round {
                 }
                 at += an.size();
             }
-            if (stage && r.ne) memcpy(ra.new_events.p + r.ev0, events + event_off[k], r.ne * sizeof(float));
+            if (stage) stage_chunk(ra, k);
         });
         lap(1);
         // ---- submit: the DTW block of gen_chains for every read of the group (rmap.cpp:509-530), one device submission ----
         if (on_device) {
-            int st = RAWDTW_OK;
-            if (n.seg) st = rawdtw_events_append(g.ctx, ra.new_events.p, n.events, (uint32_t)n.seg, ra.seg_src.p, ra.seg_dst.p);
+            int st = upload_events(g, n, false);
             if (st == RAWDTW_OK && ra.carried) {
                 st = rawdtw_batch_submit_carry(g.ctx, &m->opt.align, nr, ra.chain_off.p, ra.anchor_off.p, ra.anchors.p, ra.new_off.p, ra.new_anchors.p,
                                                ra.ref_base.p, ra.read_base.p, g.buf[g.cur ^ 1].batch, ra.carry.p, &ra.batch);
@@ -879,6 +851,30 @@ struct Round {
                 failed(RAWDTW_ERR_DEVICE, "the external scorer failed");
         }
         lap(2);
+    }
+
+    // ---- the staged events, shared by every path that sends a round's events up ----
+    // A group's chunks laid out: every read's place in the staging (ev0), their sums into n.events / n.seg, the group's arrays sized by `n`, and
+    // the segments written.  The chunks' copies are left to the caller's pass over the reads on the pool (stage_chunk).  false: no memory.
+    bool stage_events(Group &g, Sizes &n, bool dev, bool in_place)
+    {
+        RoundArrays &ra = g.buf[g.cur];
+        for (uint32_t k : ra.ks) { RoundRead &r = rr[k]; r.ev0 = n.events; n.events += r.ne; n.seg += r.ne ? 1 : 0; }
+        if (!size_arrays(g, n, dev)) return false;
+        write_segments(ra, in_place);
+        return true;
+    }
+    void stage_chunk(RoundArrays &ra, uint32_t k) const
+    {
+        if (rr[k].ne) memcpy(ra.new_events.p + rr[k].ev0, events + event_off[k], rr[k].ne * sizeof(float));
+    }
+    // ... and sent to the group's arena: the caller's array in place (every read a segment), or the staging
+    int upload_events(Group &g, const Sizes &n, bool in_place) const
+    {
+        const RoundArrays &ra = g.buf[g.cur];
+        if (!n.seg) return RAWDTW_OK;
+        if (in_place) return rawdtw_events_append(g.ctx, events, event_off[n_reads], (uint32_t)ra.ks.size(), event_off, ra.seg_dst.p);
+        return rawdtw_events_append(g.ctx, ra.new_events.p, n.events, (uint32_t)n.seg, ra.seg_src.p, ra.seg_dst.p);
     }
 
     // the new events' segments: where each stretch of the staged events goes in the group's event arena -- the reads with a chunk this
@@ -1041,11 +1037,11 @@ int rawdtw_mapper_destroy(rawdtw_mapper *m)
 {
     if (!m) return RAWDTW_OK;
     drop_batches(m);
+    m->seed_off.release(); m->seed_hits.release();
     for (Group &g : m->groups) {
         for (RoundArrays &ra : g.buf) ra = RoundArrays(); // (pinned memory goes before the context that may own the device)
         if (g.own_ctx && g.ctx) rawdtw_destroy(g.ctx);
     }
-    seed_buffers_free(m);
     rawdtw_su_destroy(m->su);
     delete m->pool;
     delete m;
@@ -1192,13 +1188,12 @@ int rawdtw_mapper_round_seeded(rawdtw_mapper *m, const rawdtw_seed_index *six, u
     if (six_seq != m->seq_len.size()) return fail(m, RAWDTW_ERR_INVALID, "the seed index and the mapper hold different numbers of sequences");
     if (n_reads == 0) return RAWDTW_OK;
     const bool on_device = m->ctx && pars.w == 0; // (the minimizer sketch is the host's)
-    if (!m->seed_off && !m->seed_hits) m->seed_pinned = m->ctx != nullptr;
-    if (seed_buffer(m, &m->seed_off, &m->seed_off_cap, (uint64_t)n_reads + 1) != RAWDTW_OK) return fail(m, RAWDTW_ERR_OOM, "no memory for the round's hit offsets");
+    if (!seed_room(m, m->seed_off, (uint64_t)n_reads + 1)) return fail(m, RAWDTW_ERR_OOM, "no memory for the round's hit offsets");
     if (!on_device) {
-        int st = rawdtw_seed_hits_host(six, n_reads, event_off, events, m->seed_off, nullptr, 0, m->opt.threads); // (counts)
+        int st = rawdtw_seed_hits_host(six, n_reads, event_off, events, m->seed_off.p, nullptr, 0, m->opt.threads); // (counts)
         if (st != RAWDTW_OK && st != RAWDTW_ERR_RANGE) return fail(m, st, "seeding: bad event offsets");
-        if (seed_buffer(m, &m->seed_hits, &m->seed_hits_cap, m->seed_off[n_reads]) != RAWDTW_OK) return fail(m, RAWDTW_ERR_OOM, "no memory for the round's hits");
-        st = rawdtw_seed_hits_host(six, n_reads, event_off, events, m->seed_off, m->seed_hits, m->seed_hits_cap, m->opt.threads);
+        if (!seed_room(m, m->seed_hits, m->seed_off[n_reads])) return fail(m, RAWDTW_ERR_OOM, "no memory for the round's hits");
+        st = rawdtw_seed_hits_host(six, n_reads, event_off, events, m->seed_off.p, m->seed_hits.p, m->seed_hits.cap, m->opt.threads);
         if (st != RAWDTW_OK) return fail(m, st, "seeding failed");
     } else {
         // (every round: the context knows its table by the index's serial and does nothing when this index is there already --
@@ -1206,17 +1201,17 @@ int rawdtw_mapper_round_seeded(rawdtw_mapper *m, const rawdtw_seed_index *six, u
         const int up = rawdtw_seed_index_upload(m->ctx, six);
         if (up != RAWDTW_OK) return fail(m, up, rawdtw_last_error(m->ctx));
         // the first guess: what the buffer holds, or four hits an event; a round with more says how many and is seeded once more
-        uint64_t want = std::max<uint64_t>(m->seed_hits_cap, 4 * (event_off[n_reads] - event_off[0]) + 1024);
+        uint64_t want = std::max<uint64_t>(m->seed_hits.cap, 4 * (event_off[n_reads] - event_off[0]) + 1024);
         for (int attempt = 0;; attempt++) {
-            if (seed_buffer(m, &m->seed_hits, &m->seed_hits_cap, want) != RAWDTW_OK) return fail(m, RAWDTW_ERR_OOM, "no page-locked memory for the round's hits");
-            int st = rawdtw_seed_begin(m->ctx, n_reads, event_off, events, m->seed_off, m->seed_hits, m->seed_hits_cap);
+            if (!seed_room(m, m->seed_hits, want)) return fail(m, RAWDTW_ERR_OOM, "no page-locked memory for the round's hits");
+            int st = rawdtw_seed_begin(m->ctx, n_reads, event_off, events, m->seed_off.p, m->seed_hits.p, m->seed_hits.cap);
             if (st == RAWDTW_OK) st = rawdtw_seed_end(m->ctx, nullptr);
-            if (st == RAWDTW_ERR_RANGE && attempt == 0 && m->seed_off[n_reads] > m->seed_hits_cap) { want = m->seed_off[n_reads]; continue; }
+            if (st == RAWDTW_ERR_RANGE && attempt == 0 && m->seed_off[n_reads] > m->seed_hits.cap) { want = m->seed_off[n_reads]; continue; }
             if (st != RAWDTW_OK) return fail(m, st, rawdtw_last_error(m->ctx));
             break;
         }
     }
-    return rawdtw_mapper_round(m, n_reads, read_ids, event_off, events, m->seed_off, m->seed_hits);
+    return rawdtw_mapper_round(m, n_reads, read_ids, event_off, events, m->seed_off.p, m->seed_hits.p);
 }
 
 // rawdtw_mapper_round_seeded with the hits left on the device: the events are appended, the seeding reads them in the arena, and the
@@ -1236,8 +1231,7 @@ int rawdtw_mapper_round_seeded_resident(rawdtw_mapper *m, const rawdtw_seed_inde
     const double t0 = now_ms();
     const int chk = check_round(m, n_reads, read_ids, event_off, nullptr, nullptr);
     if (chk != RAWDTW_OK) return chk;
-    if (!m->seed_off && !m->seed_hits) m->seed_pinned = true;
-    if (seed_buffer(m, &m->seed_off, &m->seed_off_cap, (uint64_t)n_reads + 1) != RAWDTW_OK) return fail(m, RAWDTW_ERR_OOM, "no memory for the round's hit offsets");
+    if (!seed_room(m, m->seed_off, (uint64_t)n_reads + 1)) return fail(m, RAWDTW_ERR_OOM, "no memory for the round's hit offsets");
     const int up = rawdtw_seed_index_upload(m->ctx, six);
     // (the one thing the upload refuses here: a seeding somebody began on the mapper's context and has not ended)
     if (up == RAWDTW_ERR_INVALID) return fail(m, RAWDTW_ERR_UNSUPPORTED, rawdtw_last_error(m->ctx));

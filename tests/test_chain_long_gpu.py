@@ -10,7 +10,7 @@ import pytest
 import rawalign_amd as ra
 from rawalign_amd import mapping as M
 from rawalign_amd.dtw import ANCHOR_DTYPE
-from tests.test_device_chain import REC_DTYPE, SEED_DTYPE, compare, device_round, host_chains, random_read, vp
+from tests.test_device_chain import REC_DTYPE, SEED_DTYPE, compare, device_round, host_chains, lists_of_one_little_chain, random_read, vp, y_shaped_round
 
 pytestmark = pytest.mark.gpu
 UNSUPPORTED = 5
@@ -80,6 +80,38 @@ def test_a_lowered_cap_routes_reads_of_61_seeds_to_the_long_path(monkeypatch):
             assert e1.chain_round_stats()["long_reads"] == 5
         finally:
             e1.close()
+    finally:
+        eng.close()
+
+
+def test_a_chain_that_runs_into_a_used_anchor_in_the_long_path(monkeypatch):
+    monkeypatch.setenv("RAWDTW_CHAIN_MAX_SEEDS", "1")
+    eng = ra.Engine(0)
+    try:
+        eng.set_option("chain_long_seeds", 4096)
+        copt = M.default_chain_opt(6)
+        per_read = y_shaped_round(eng.lib, copt)
+        compare(eng.lib, copt, per_read, device_round(eng, copt, per_read))
+        assert eng.chain_round_stats()["long_reads"] == 2   # (the empty read is k_chain's)
+    finally:
+        eng.close()
+
+
+def test_the_tie_rule_in_the_long_path(monkeypatch):
+    """more than 16 chains with two equal scores among them decline the round (std::sort's order is its own there), 16 are ordered as the host
+    orders them, and the context goes on after the declined round"""
+    monkeypatch.setenv("RAWDTW_CHAIN_MAX_SEEDS", "1")
+    rng = np.random.default_rng(75)
+    eng = ra.Engine(0)
+    try:
+        eng.set_option("chain_long_seeds", 4096)
+        copt = M.default_chain_opt(6)
+        assert device_round(eng, copt, [lists_of_one_little_chain(20)], n_keys=32)[0] == UNSUPPORTED
+        ok16 = [lists_of_one_little_chain(16)]
+        compare(eng.lib, copt, ok16, device_round(eng, copt, ok16, n_keys=32))
+        plain = [random_read(rng, 100, 2, 5000)]
+        compare(eng.lib, copt, plain, device_round(eng, copt, plain))
+        assert eng.chain_round_stats()["long_reads"] == 3
     finally:
         eng.close()
 

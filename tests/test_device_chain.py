@@ -95,6 +95,41 @@ def compare(lib, copt, per_read, out):
     assert int(anchor_off[int(chain_off[-1])]) == sum(int(x) for x in recs["n_anchors"][:int(chain_off[-1])])
 
 
+def y_shaped_round(lib, copt):
+    """Three reads: one list of 52 anchors in a Y -- a trunk of 10 and two branches of 20 and 22 that both continue it --, an empty read and a
+    random one of 64 seeds.  The best chain takes the trunk with branch A; the second starts on branch B's first anchor, whose predecessor is the
+    trunk's last, used by then: its score is its end's less that anchor's (rmap.cpp:130-173).  Checked here, so that no change of the inputs
+    can empty the test."""
+    i = np.arange(22)
+    s = np.zeros(52, SEED_DTYPE)
+    s["target_position"] = np.concatenate([1000 + 3 * i[:10], 1030 + 3 * i[:20], 1040 + 3 * i])
+    s["query_position"] = np.concatenate([3 * i[:10], 30 + 3 * i[:20], 34 + 3 * i])
+    rng = np.random.default_rng(31)
+    y = s[rng.permutation(52)]
+    got = [(float(score), start, end, len(an)) for score, _, start, end, an in host_chains(lib, copt, y)]
+    assert got == [(93.0, 1000, 1087, 30), (69.0, 1040, 1103, 22)], got
+    return [y, np.zeros(0, SEED_DTYPE), random_read(rng, 64, 2, 2000)]
+
+
+def lists_of_one_little_chain(k):
+    """k lists with the same chain of four anchors each: k chains of equal score (test_round_arrays_in_device_memory_and_what_the_device_declines)"""
+    s = np.zeros(4 * k, SEED_DTYPE)
+    s["key"] = np.repeat(np.arange(k), 4)
+    s["target_position"], s["query_position"] = np.tile([100, 110, 120, 130], k), np.tile([5, 15, 25, 35], k)
+    return s
+
+
+@pytest.mark.gpu
+def test_a_chain_that_runs_into_a_used_anchor():
+    eng = ra.Engine(0)
+    try:
+        copt = M.default_chain_opt(6)
+        per_read = y_shaped_round(eng.lib, copt)
+        compare(eng.lib, copt, per_read, device_round(eng, copt, per_read))
+    finally:
+        eng.close()
+
+
 @pytest.mark.gpu
 def test_chains_of_random_reads_equal_the_host_restatement():
     rng = np.random.default_rng(11)
