@@ -792,7 +792,8 @@ int rawdtw_mapper_destroy(rawdtw_mapper *m);
  *                                      under the 32-bit mask (rsketch.c:6-15); from the e-th kept event on, every kept event
  *                                      emits (hash, i), i = the position of the LAST event of the e-mer
  *   sketch, w > 0   rsketch.c:146-221  the minimizer sketch: no RI_MASK_SIGNAL test, the position is the e-mer's first event,
- *                                      and of each window of w e-mers the smallest hash is emitted.  Host only.
+ *                                      and of each window of w e-mers the smallest hash is emitted (ties and the first window
+ *                                      as rsketch.c:193-219 has them).  On the host; on the device under "seed_minimizer" (below).
  *   lookup          rmap.cpp:371-391   per sketch element in order, per position y of its hash in the index's order:
  *                                      ref_seq = y >> 32, strand = y & 1, target_position = (y >> 1) & 0x7fffffff,
  *                                      query_position = i (inside the chunk; the mapper adds the chunk's start)
@@ -836,8 +837,15 @@ int rawdtw_seed_hits_host(const rawdtw_seed_index *six, uint32_t n_chunks, const
  * returns, the arrays must stay valid until _end; page-locked hit_off / hits (rawdtw_host_alloc) the device writes itself, others
  * are copied in _end (through a device array of hits_cap entries: keep hits_cap near the need).  A total above hits_cap:
  * RAWDTW_ERR_RANGE from _end with hit_off filled; the device checks the total before it writes a single hit.  An index with
- * w > 0 is RAWDTW_ERR_UNSUPPORTED from _begin (seed such chunks with rawdtw_seed_hits_host); no table on the context is
- * RAWDTW_ERR_INVALID.  No w == 0 input is declined for its size or its repeats. */
+ * w > 0 is RAWDTW_ERR_UNSUPPORTED from _begin (seed such chunks with rawdtw_seed_hits_host) unless "seed_minimizer" is on; no
+ * table on the context is RAWDTW_ERR_INVALID.  No w == 0 input is declined for its size or its repeats.
+ *   rawdtw_set_option(ctx, "seed_minimizer", V)  0 (the default): as above.  1: a w > 0 table on this context is seeded on the device
+ *        (a further launch between the filter and the probe runs the reference's window over every chunk, rsketch.c:193-219; 32
+ *        bytes of workspace an event instead of 24) by rawdtw_seed_begin / _end, rawdtw_seed_resident_begin / _end / _fetch, and by
+ *        rawdtw_mapper_round_seeded / _seeded_resident of a mapper on this context: the same hits as rawdtw_seed_hits_host, in
+ *        its order.  It never changes what a w == 0 table does.  rawdtw_get_option reads it back.  A chunk whose sketch had more
+ *        elements than the chunk has events (an e-mer can be emitted twice; not seen on any input) is RAWDTW_ERR_UNSUPPORTED from
+ *        _end with no hit written and hit_off not to be used: seed that round with rawdtw_seed_hits_host. */
 int rawdtw_seed_index_upload(rawdtw_ctx *ctx, const rawdtw_seed_index *six);
 int rawdtw_seed_begin(rawdtw_ctx *ctx, uint32_t n_chunks, const uint64_t *event_off, const float *events,
                       uint64_t *hit_off /* n_chunks+1 */, rawdtw_seed_hit_t *hits, uint64_t hits_cap);
@@ -847,7 +855,7 @@ int rawdtw_seed_end(rawdtw_ctx *ctx, float *kernel_ms /* may be NULL: the launch
  * with a context seeds on the device (the table of `six` is uploaded at the first round and whenever the context holds another index's; the
  * whole round is seeded on the mapper's own context, whichever group a read belongs to, so a second group needs no table) into
  * a page-locked buffer of its own; a mapper without one (a scorer's), and an index with
- * w > 0, seed on the host with opt.threads.  `six` must hold as many sequences as the mapper (RAWDTW_ERR_INVALID).  A failed
+ * w > 0 unless the context's "seed_minimizer" option is on, seed on the host with opt.threads.  `six` must hold as many sequences as the mapper (RAWDTW_ERR_INVALID).  A failed
  * seeding changes nothing in the mapper. */
 int rawdtw_mapper_round_seeded(rawdtw_mapper *m, const rawdtw_seed_index *six, uint32_t n_reads, const uint32_t *read_ids,
                                const uint64_t *event_off, const float *events);
@@ -860,7 +868,7 @@ int rawdtw_mapper_round_seeded(rawdtw_mapper *m, const rawdtw_seed_index *six, u
  *       hit_off (n_chunks + 1 entries, 8 bytes a chunk) comes home; the hits stay in the seeding's workspace until the context's
  *       next seeding of either kind, or its next rawdtw_seed_index_upload of another index.  The rules are rawdtw_seed_begin's:
  *       refused before anything is enqueued, one seeding a context at a time (of either kind; a resident one is ended by
- *       rawdtw_seed_resident_end only), w > 0 RAWDTW_ERR_UNSUPPORTED, no table RAWDTW_ERR_INVALID, a chunk outside the arena
+ *       rawdtw_seed_resident_end only), w > 0 RAWDTW_ERR_UNSUPPORTED unless "seed_minimizer" is on, no table RAWDTW_ERR_INVALID, a chunk outside the arena
  *       RAWDTW_ERR_RANGE, 64-bit counts.
  *   rawdtw_seed_resident_fetch  the ended resident seeding's hits into hits[0 .. hit_off[n_chunks]), in rawdtw_seed_begin's order
  *       (page-locked: written by the device itself); RAWDTW_ERR_RANGE when hits_cap is below the total.  For fall-backs and tests.
@@ -874,7 +882,8 @@ int rawdtw_mapper_round_seeded(rawdtw_mapper *m, const rawdtw_seed_index *six, u
  *       here too, from the seeds the device laid down, and only a read above N declines the round; the arrays must stay valid until _end.
  *   rawdtw_mapper_round_seeded_resident  rawdtw_mapper_round_seeded through the three above: append the events, seed from the
  *       arena, size the round by hit_off, chain, and from there the unchanged round.  Only for a mapper that chains on the
- *       device (device_chain, a context, no scorer; with or without a DTW stage) with one read group and a w == 0 index: anything else is
+ *       device (device_chain, a context, no scorer; with or without a DTW stage) with one read group and a w == 0 index (or a w > 0 one
+ *       with "seed_minimizer" on on that context): anything else is
  *       RAWDTW_ERR_UNSUPPORTED with nothing changed (use rawdtw_mapper_round_seeded).  A round the device chaining declines (its
  *       caps) fetches the hits once and is chained on the host: the same lines.  A failed round leaves the mapper as it was.
  *   rawdtw_mapper_resident_stats  rounds that stayed resident, rounds that fell back, bytes of hits fetched to the host (16 a hit

@@ -147,6 +147,7 @@ struct rawdtw_ctx {
     struct rawdtw_seed_ws *seed_ws = nullptr;     // rawdtw_seed_index_upload's table and rawdtw_seed_begin's device block (rawdtw_seed.hip), grow-only
     uint32_t chain_max_seeds = 0; // tests: RAWDTW_CHAIN_MAX_SEEDS lowers rawdtw_chain_round's cap on seeds a read, so that small rounds take the declined path (0: no)
     uint32_t chain_long_seeds = 0; // "chain_long_seeds": reads above the cap with at most this many seeds are chained by rawdtw_chain.hip's long path (0: declined)
+    bool seed_minimizer = false;   // "seed_minimizer": rawdtw_seed.hip seeds a w > 0 table on the device (k_seed_min) rather than refusing it
     std::string err;
 };
 

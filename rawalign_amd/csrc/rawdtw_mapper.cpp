@@ -1176,6 +1176,12 @@ int rawdtw_mapper_round(rawdtw_mapper *m, uint32_t n_reads, const uint32_t *read
     return RAWDTW_OK;
 }
 
+static bool minimizer_on_device(const rawdtw_ctx *ctx)
+{
+    int64_t v = 0;
+    return rawdtw_get_option(ctx, "seed_minimizer", &v) == RAWDTW_OK && v != 0;
+}
+
 // The seeding of gen_chains (rmap.cpp:364-391) in front of the round.  Everything the seeding touches is the mapper's own buffers:
 // the reads change only inside rawdtw_mapper_round, which runs on the finished hits or not at all.
 int rawdtw_mapper_round_seeded(rawdtw_mapper *m, const rawdtw_seed_index *six, uint32_t n_reads, const uint32_t *read_ids,
@@ -1187,7 +1193,7 @@ int rawdtw_mapper_round_seeded(rawdtw_mapper *m, const rawdtw_seed_index *six, u
     if (rawdtw_seed_index_info(six, &six_seq, nullptr, nullptr, nullptr, &pars) != RAWDTW_OK) return RAWDTW_ERR_INVALID;
     if (six_seq != m->seq_len.size()) return fail(m, RAWDTW_ERR_INVALID, "the seed index and the mapper hold different numbers of sequences");
     if (n_reads == 0) return RAWDTW_OK;
-    const bool on_device = m->ctx && pars.w == 0; // (the minimizer sketch is the host's)
+    const bool on_device = m->ctx && (pars.w == 0 || minimizer_on_device(m->ctx)); // (the minimizer sketch is the host's unless "seed_minimizer" is on)
     if (!seed_room(m, m->seed_off, (uint64_t)n_reads + 1)) return fail(m, RAWDTW_ERR_OOM, "no memory for the round's hit offsets");
     if (!on_device) {
         int st = rawdtw_seed_hits_host(six, n_reads, event_off, events, m->seed_off.p, nullptr, 0, m->opt.threads); // (counts)
@@ -1224,9 +1230,9 @@ int rawdtw_mapper_round_seeded_resident(rawdtw_mapper *m, const rawdtw_seed_inde
     rawdtw_seed_pars_t pars;
     if (rawdtw_seed_index_info(six, &six_seq, nullptr, nullptr, nullptr, &pars) != RAWDTW_OK) return RAWDTW_ERR_INVALID;
     if (six_seq != m->seq_len.size()) return fail(m, RAWDTW_ERR_INVALID, "the seed index and the mapper hold different numbers of sequences");
-    if (!m->ctx || m->scorer || !m->opt.device_chain || m->groups.size() != 1 || pars.w != 0)
-        return fail(m, RAWDTW_ERR_UNSUPPORTED, "a resident round needs a context, device chaining, one read group, no external scorer and a w == 0 index "
-                                               "(rawdtw_mapper_round_seeded maps the round)");
+    if (!m->ctx || m->scorer || !m->opt.device_chain || m->groups.size() != 1 || (pars.w != 0 && !minimizer_on_device(m->ctx)))
+        return fail(m, RAWDTW_ERR_UNSUPPORTED, "a resident round needs a context, device chaining, one read group, no external scorer and a w == 0 index, "
+                                               "or a w > 0 one with the context's \"seed_minimizer\" option on (rawdtw_mapper_round_seeded maps the round)");
     if (n_reads == 0) return RAWDTW_OK;
     const double t0 = now_ms();
     const int chk = check_round(m, n_reads, read_ids, event_off, nullptr, nullptr);

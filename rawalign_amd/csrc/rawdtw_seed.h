@@ -62,6 +62,13 @@ RAWDTW_HD inline bool skipped(float x, float last, bool first)
     return (!first && (d < 0.0f ? -d : d) < kLastSigDiff) || x == kMaskSignal;
 }
 
+// rsketch.c:172: the minimizer sketch's form of the same test -- no RI_MASK_SIGNAL clause: a masked value is kept and coded
+RAWDTW_HD inline bool skipped_min(float x, float last, bool first)
+{
+    const float d = x - last;
+    return !first && (d < 0.0f ? -d : d) < kLastSigDiff;
+}
+
 // w, e, n, q, lq, k as ri_idx_t keeps them; RAWDTW_ERR_INVALID where the reference asserts or shifts out of range
 int check_pars(const rawdtw_seed_pars_t *p);
 

@@ -1,6 +1,7 @@
 // rawdtw_seed.hip -- seeding for a whole chunk round on the device: ri_sketch_reg (src/rsketch.c:223-274) and the lookup and hit
 // loop of gen_chains (src/rmap.cpp:371-391), equal to the host restatement (rawdtw_seed_host.cpp) hit for hit and in its order.  The
-// minimizer sketch (w > 0) stays on the host.
+// minimizer sketch (w > 0, ri_sketch_min, rsketch.c:146-221) is refused unless the context's "seed_minimizer" option is on; with it
+// a fifth launch, k_seed_min, stands between the filter and the probe (below).
 //
 // One recurrence is serial per chunk: an event is compared with the last KEPT one.  Everything else is parallel.  Four launches:
 //   k_seed_filter  a lane per chunk, 64 chunks a wave: events staged through LDS in 64 x 64 tiles (coalesced loads), each lane
@@ -16,6 +17,12 @@
 //                  reference: a repeat gives one element thousands of positions, which one lane must not write alone).  One
 //                  16-byte store a hit -- into device memory, or straight into the caller's page-locked array.  Nothing is
 //                  written unless the round's total fits.
+// With w > 0 ("seed_minimizer"): the filter has no RI_MASK_SIGNAL test (rsketch.c:172), and
+//   k_seed_min     a wave per chunk: 64 e-mers a step are hashed by the lanes (e-mer m = the kept events m .. m + e - 1) into registers
+//                  and an LDS ring of the last 512; the wave then walks them in order with the reference's window state (the minimum's
+//                  hash and e-mer index, wave-uniform) and writes the chosen elements -- the hash, and the position of the e-mer's
+//                  FIRST event -- densely at the chunk's offset, one slot an event at the most.  The probe then takes every element's
+//                  hash as given; scan and write see the sketch's count and positions where they saw the kept events'.
 // A RESIDENT seeding (rawdtw_seed_resident_begin) runs filter, probe and scan on events that are in the context's event arena already
 // (a source start a chunk, apart from the dense workspace offset) and stops there: the hit counts go home, the per-element words
 // stay in the workspace.  Two launches read them afterwards:
@@ -68,7 +75,8 @@ __device__ __forceinline__ uint64_t lane_u64(uint64_t x, int c)
 }
 
 // rsketch.c:242-247.  kSrc: the chunks' events are read from a.src[k] on (the event arena) rather than from the dense offset.
-template <bool kSrc> __global__ __launch_bounds__(64) void k_seed_filter(SeedArgs a)
+// kMask: the w == 0 rule (rsketch.c:243); without it ri_sketch_min's (rsketch.c:172), which keeps a masked value.
+template <bool kSrc, bool kMask = true> __global__ __launch_bounds__(64) void k_seed_filter(SeedArgs a)
 {
     __shared__ float tx[kW * kPad];
     __shared__ uint32_t tr[kW * kPad];
@@ -101,7 +109,7 @@ template <bool kSrc> __global__ __launch_bounds__(64) void k_seed_filter(SeedArg
         const uint32_t lim = len > t0 ? min(kW, len - t0) : 0u;
         for (uint32_t j = 0; j < lim; j++) {
             const float x = tx[lane * kPad + j];
-            const bool skip = seed::skipped(x, last, t0 + j == 0);
+            const bool skip = kMask ? seed::skipped(x, last, t0 + j == 0) : seed::skipped_min(x, last, t0 + j == 0);
             tr[lane * kPad + j] = skip ? kNone : rank;
             // ev[l_sigpos] with l_sigpos = 0 until an event is kept (rsketch.c:233,243-245): a chunk whose event 0 is RI_MASK_SIGNAL
             // compares what follows with that value, not with nothing
@@ -122,8 +130,87 @@ template <bool kSrc> __global__ __launch_bounds__(64) void k_seed_filter(SeedArg
     if (lane < nc) a.kept[me] = rank;
 }
 
-// rsketch.c:254-255, rawindex.cpp:256-273
-__global__ __launch_bounds__(64) void k_seed_probe(SeedArgs a)
+// ---- the minimizer sketch: ri_sketch_min's window (rsketch.c:193-219) over the filter's kept events ----
+struct MinArgs {
+    const uint64_t *off;                 // n + 1
+    const uint32_t *code, *fpos, *fkept; // the filter's: per chunk dense from off[k], and the kept events a chunk
+    uint32_t *hash, *pos, *count;        // the sketch: per chunk dense from off[k], and the elements a chunk
+    uint64_t *over;                      // set when a chunk's sketch has more elements than the chunk has events
+    uint32_t e, qb, w;
+};
+
+constexpr uint32_t kRing = 512; // e-mer hashes kept in LDS: a window of up to 255 behind a step of 64
+
+// The reference's buf[] at e-mer m is exactly the e-mers m - w + 1 .. m (slots below 0 are its empty UINT64_MAX entries, which lose
+// every compare against a real one), so no ring of (x, y) is kept: the minimum is (hash, e-mer index), "buf_pos == min_pos" is "the
+// minimum sits w e-mers back", and l = m + e.  x = hash << RI_HASH_SHIFT | span with one span: hashes compare as x does.  y differs
+// exactly where the e-mer index does.
+__global__ __launch_bounds__(64) void k_seed_min(MinArgs a)
+{
+    __shared__ uint32_t ring[kRing];
+    const uint32_t k = blockIdx.x, lane = threadIdx.x, e = a.e, w = a.w;
+    const uint64_t b = a.off[k];
+    const uint32_t room = (uint32_t)(a.off[k + 1] - b), kept = a.fkept[k];
+    const uint32_t M = kept >= e ? kept - e + 1 : 0; // e-mers
+    const uint64_t mask_events = (1ull << (a.qb * e)) - 1;
+    const uint64_t below = (1ull << lane) - 1;
+    uint32_t out = 0;                // elements so far (wave-uniform, like the minimum)
+    uint32_t mn_h = 0, mn_i = kNone; // kNone: no minimum yet (min.x == UINT64_MAX)
+    auto push = [&](uint32_t h, uint32_t i) { // every store inside the chunk's own stretch of `room` slots
+        if (lane == 0 && out < room) { a.hash[b + out] = h; a.pos[b + out] = a.fpos[b + i]; }
+        out++;
+    };
+    // the e-mers lo .. hi whose hash is the minimum's, the minimum itself apart, oldest first (rsketch.c:195-198, 210-213)
+    auto ties = [&](uint32_t lo, uint32_t hi) {
+        for (uint32_t s0 = lo; s0 <= hi; s0 += kW) {
+            const uint32_t i = s0 + lane;
+            const bool f = i <= hi && i != mn_i && ring[i & (kRing - 1)] == mn_h;
+            const unsigned long long bal = __ballot(f);
+            const uint32_t at = out + (uint32_t)__popcll(bal & below);
+            if (f && at < room) { a.hash[b + at] = mn_h; a.pos[b + at] = a.fpos[b + i]; }
+            out += (uint32_t)__popcll(bal);
+        }
+    };
+    for (uint32_t m0 = 0; m0 < M; m0 += kW) {
+        uint32_t h = 0;
+        if (m0 + lane < M) {
+            uint64_t quant = 0;
+            for (uint32_t j = 0; j < e; j++) quant = quant << a.qb | a.code[b + m0 + lane + j]; // (m + e - 1 < kept)
+            h = seed::hash32((uint32_t)(quant & mask_events));
+            ring[(m0 + lane) & (kRing - 1)] = h;
+        }
+        __syncthreads();
+        const uint32_t lim = min(kW, M - m0);
+        for (uint32_t j = 0; j < lim; j++) {
+            const uint32_t m = m0 + j, hm = (uint32_t)__builtin_amdgcn_readlane((int)h, (int)j);
+            if (m + 1 == w && mn_i != kNone) ties(0, m - 1); // the first window: the e-mers before this one
+            if (mn_i == kNone || hm <= mn_h) { // a new minimum: the old one goes out
+                if (m >= w && mn_i != kNone) push(mn_h, mn_i);
+                mn_h = hm; mn_i = m;
+            } else if (m - mn_i == w) { // the old minimum has left the window (so m >= w: every l >= w + e - 1 test holds)
+                push(mn_h, mn_i);
+                const uint32_t lo = m - w + 1; // >= 1
+                uint64_t best = ~0ull;         // hash, then the NEWEST of equal ones (rsketch.c:206 ">="): ~index in the low half
+                for (uint32_t s0 = lo; s0 <= m; s0 += kW) {
+                    const uint32_t i = s0 + lane;
+                    if (i <= m) best = min(best, (uint64_t)ring[i & (kRing - 1)] << 32 | (uint32_t)~i);
+                }
+                for (int o = 32; o; o >>= 1) best = min(best, lane_u64(best, (int)(lane ^ (uint32_t)o)));
+                mn_h = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(best >> 32));
+                mn_i = ~(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)best);
+                ties(lo, m);
+            }
+        }
+    }
+    if (mn_i != kNone) push(mn_h, mn_i); // rsketch.c:218
+    if (lane == 0) {
+        a.count[k] = min(out, room);
+        if (out > room) a.over[0] = 1;
+    }
+}
+
+// rsketch.c:254-255, rawindex.cpp:256-273.  kGiven (w > 0): every element r < kept has its hash in a.code already (k_seed_min).
+template <bool kGiven> __global__ __launch_bounds__(64) void k_seed_probe(SeedArgs a)
 {
     const uint32_t k = blockIdx.x, lane = threadIdx.x, kept = a.kept[k], e = a.e, qb = a.lq + 2;
     const uint64_t b = a.off[k];
@@ -133,10 +220,14 @@ __global__ __launch_bounds__(64) void k_seed_probe(SeedArgs a)
     for (uint32_t r = lane; r < kept; r += kW) {
         uint32_t c = 0;
         uint64_t v = 0;
-        if (r + 1 >= e) {
-            uint64_t quant = 0;
-            for (uint32_t j = 0; j < e; j++) quant = quant << qb | a.code[b + r + 1 - e + j];
-            const uint32_t h = seed::hash32((uint32_t)(quant & mask_events));
+        if (kGiven || r + 1 >= e) {
+            uint32_t h;
+            if (kGiven) h = a.code[b + r];
+            else {
+                uint64_t quant = 0;
+                for (uint32_t j = 0; j < e; j++) quant = quant << qb | a.code[b + r + 1 - e + j];
+                h = seed::hash32((uint32_t)(quant & mask_events));
+            }
             uint32_t at = seed::first_slot(h, a.log2_slots);
             for (uint32_t tries = 0; tries <= smask; tries++, at = (at + 1) & smask) { // (the table is at most half full: an empty slot ends it)
                 const uint4 s = *reinterpret_cast<const uint4 *>(a.slots + at);
@@ -187,10 +278,10 @@ __device__ __forceinline__ uint4 hit_of(uint64_t y, uint32_t query)
 }
 
 // rmap.cpp:385-389.  Nothing is written unless the whole round's hits fit below `bound` (the caller's hits_cap, and the device
-// array's size).
+// array's size) and no chunk's sketch overflowed its stretch.
 __global__ __launch_bounds__(64) void k_seed_write(SeedArgs a, uint64_t bound, uint4 *out)
 {
-    if (a.tot[0] > bound) return;
+    if (a.tot[0] > bound || a.tot[1]) return; // ([1]: k_seed_min's overflow flag, zero without it)
     const uint32_t k = blockIdx.x, lane = threadIdx.x, kept = a.kept[k];
     if (!a.chits[k]) return;
     const uint64_t b = a.off[k];
@@ -331,6 +422,26 @@ void *device_view(void *p, size_t bytes)
     return at.devicePointer;
 }
 
+// filter -> (min) -> probe -> scan on `a`.  With w > 0 the filter's output goes to `mn`'s inputs and `a` is re-pointed at the sketch: the
+// launches behind (and whoever keeps `a`) see the sketch's elements where they saw the kept events.
+template <bool kSrc> void launch_seeding(SeedArgs &a, MinArgs mn, uint32_t w, hipStream_t s, uint64_t *dv_hoff)
+{
+    const dim3 tiles((a.n + kW - 1) / kW), chunks(a.n), wave(kW);
+    if (w == 0) {
+        hipLaunchKernelGGL((k_seed_filter<kSrc, true>), tiles, wave, 0, s, a);
+        hipLaunchKernelGGL(k_seed_probe<false>, chunks, wave, 0, s, a);
+    } else {
+        SeedArgs f = a;
+        f.code = const_cast<uint32_t *>(mn.code); f.pos = const_cast<uint32_t *>(mn.fpos); f.kept = const_cast<uint32_t *>(mn.fkept);
+        hipLaunchKernelGGL((k_seed_filter<kSrc, false>), tiles, wave, 0, s, f);
+        hipLaunchKernelGGL(k_seed_min, chunks, wave, 0, s, mn);
+        hipLaunchKernelGGL(k_seed_probe<true>, chunks, wave, 0, s, a);
+    }
+    hipLaunchKernelGGL(k_seed_scan, dim3(1), dim3(1024), 0, s, a.chits, a.n, a.hoff, a.tot, dv_hoff);
+}
+
+const char *const kOverflow = "a chunk's minimizer sketch has more elements than the chunk has events: seed this round on the host (rawdtw_seed_hits_host)";
+
 } // namespace
 } // namespace rawdtw
 
@@ -393,13 +504,14 @@ int rawdtw_seed_begin(rawdtw_ctx *ctx, uint32_t n_chunks, const uint64_t *event_
     if (!wp || !wp->has_table) return fail(ctx, RAWDTW_ERR_INVALID, "no seed index on this context (rawdtw_seed_index_upload)");
     SeedWs &w = *wp;
     if (w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "a seeding is begun on this context and not ended");
-    if (w.pars.w) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, "the minimizer sketch (w > 0) is seeded on the host (rawdtw_seed_hits_host)");
+    if (w.pars.w && !ctx->seed_minimizer) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, "the minimizer sketch (w > 0) is seeded on the host (rawdtw_seed_hits_host)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     w.ready = false; w.resident = false; // (the workspace is this seeding's from here on: an ended resident seeding's words are gone)
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    // offsets, events, codes, positions, counts (4 bytes an event each) and list words (8): 24 bytes an event
+    // offsets, events, codes, positions, counts (4 bytes an event each) and list words (8): 24 bytes an event; with w > 0 the sketch's
+    // hashes and positions as well: 32
     const size_t b_off = al((n + 1) * 8), b_ev = al(N * 4), b_val = al(N * 8), b_cnt = al(n * 4), b_tot = al(32);
-    const size_t need = 3 * b_off + 4 * b_ev + b_val + b_cnt + b_tot;
+    const size_t need = 3 * b_off + 4 * b_ev + b_val + b_cnt + b_tot + (w.pars.w ? 2 * b_ev + b_cnt : 0);
     if (w.dev_bytes < need) {
         if (w.dev) (void)hipFree(w.dev);
         w.dev = nullptr; w.dev_bytes = 0;
@@ -447,10 +559,17 @@ int rawdtw_seed_begin(rawdtw_ctx *ctx, uint32_t n_chunks, const uint64_t *event_
     a.kept = reinterpret_cast<uint32_t *>(p); p += b_cnt;
     a.chits = reinterpret_cast<uint64_t *>(p); p += b_off;
     a.hoff = reinterpret_cast<uint64_t *>(p); p += b_off;
-    a.tot = reinterpret_cast<uint64_t *>(p);
+    a.tot = reinterpret_cast<uint64_t *>(p); p += b_tot;
     a.off = d_off; a.ev = d_ev; a.n = n_chunks;
     a.e = w.pars.e; a.q = w.pars.q; a.lq = w.pars.lq;
     a.slots = w.d_slots; a.list = w.d_list; a.log2_slots = w.log2_slots;
+    MinArgs mn{};
+    if (w.pars.w) { // the filter's three arrays become k_seed_min's input; the sketch takes their place in `a`
+        mn = MinArgs{d_off, a.code, a.pos, a.kept, nullptr, nullptr, nullptr, a.tot + 1, w.pars.e, w.pars.lq + 2, w.pars.w};
+        mn.hash = a.code = reinterpret_cast<uint32_t *>(p); p += b_ev;
+        mn.pos = a.pos = reinterpret_cast<uint32_t *>(p); p += b_ev;
+        mn.count = a.kept = reinterpret_cast<uint32_t *>(p);
+    }
     uint64_t *h_off = w.pin + 2;
     for (uint64_t k = 0; k <= n; k++) h_off[k] = event_off[k] - event_off[0];
     w.direct_off = dv_hoff != nullptr; w.direct_hits = dv_hits != nullptr;
@@ -461,13 +580,11 @@ int rawdtw_seed_begin(rawdtw_ctx *ctx, uint32_t n_chunks, const uint64_t *event_
         hipMemcpyAsync(d_ev, events + event_off[0], N * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemsetAsync(a.tot, 0, 32, s) != hipSuccess || hipEventRecord(w.ev0, s) != hipSuccess)
         return undo(hip_fail(ctx, hipGetLastError(), "seeding upload"));
-    hipLaunchKernelGGL(k_seed_filter<false>, dim3((uint32_t)((n + kW - 1) / kW)), dim3(kW), 0, s, a);
-    hipLaunchKernelGGL(k_seed_probe, dim3(n_chunks), dim3(kW), 0, s, a);
-    hipLaunchKernelGGL(k_seed_scan, dim3(1), dim3(1024), 0, s, a.chits, n_chunks, a.hoff, a.tot, dv_hoff);
+    launch_seeding<false>(a, mn, w.pars.w, s, dv_hoff);
     if (hits_cap) hipLaunchKernelGGL(k_seed_write, dim3(n_chunks), dim3(kW), 0, s, a, hits_cap, dv_hits ? dv_hits : static_cast<uint4 *>(w.d_hits));
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipEventRecord(w.ev1, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(w.pin, a.tot, 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(w.pin, a.tot, 16, hipMemcpyDeviceToHost, s); // ([1]: k_seed_min's overflow flag)
     if (e == hipSuccess) e = hipEventRecord(w.done, s);
     if (e != hipSuccess) return undo(hip_fail(ctx, e, "seeding launches"));
     return RAWDTW_OK;
@@ -494,6 +611,7 @@ int rawdtw_seed_end(rawdtw_ctx *ctx, float *kernel_ms)
         HIP_TRY(ctx, hipStreamSynchronize(s));
     }
     if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, w.ev0, w.ev1));
+    if (w.pin[1]) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, kOverflow); // (no hit was written)
     if (tot > w.cap) return fail(ctx, RAWDTW_ERR_RANGE, "hits_cap is below the round's hits (hit_off is filled)");
     if (!w.direct_hits && tot) {
         HIP_TRY(ctx, hipMemcpyAsync(w.h_hits, w.d_hits, tot * sizeof(rawdtw_seed_hit_t), hipMemcpyDeviceToHost, s));
@@ -512,7 +630,7 @@ int rawdtw_seed_resident_begin(rawdtw_ctx *ctx, uint32_t n_chunks, const uint64_
     if (!wp || !wp->has_table) return fail(ctx, RAWDTW_ERR_INVALID, "no seed index on this context (rawdtw_seed_index_upload)");
     SeedWs &w = *wp;
     if (w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "a seeding is begun on this context and not ended");
-    if (w.pars.w) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, "the minimizer sketch (w > 0) is seeded on the host (rawdtw_seed_hits_host)");
+    if (w.pars.w && !ctx->seed_minimizer) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, "the minimizer sketch (w > 0) is seeded on the host (rawdtw_seed_hits_host)");
     const uint64_t n = n_chunks;
     uint64_t N = 0;
     for (uint64_t k = 0; k < n; k++) {
@@ -523,9 +641,10 @@ int rawdtw_seed_resident_begin(rawdtw_ctx *ctx, uint32_t n_chunks, const uint64_
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     w.ready = false; w.resident = false;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    // as rawdtw_seed_begin's block without the events: offsets, source starts, codes, positions, counts (4 bytes an event each), list words (8)
+    // as rawdtw_seed_begin's block without the events: offsets, source starts, codes, positions, counts (4 bytes an event each), list words (8);
+    // with w > 0 the sketch's hashes and positions as well
     const size_t b_off = al((n + 1) * 8), b_ev = al(N * 4), b_val = al(N * 8), b_cnt = al(n * 4), b_tot = al(32);
-    const size_t need = 4 * b_off + 3 * b_ev + b_val + b_cnt + b_tot;
+    const size_t need = 4 * b_off + 3 * b_ev + b_val + b_cnt + b_tot + (w.pars.w ? 2 * b_ev + b_cnt : 0);
     if (w.dev_bytes < need) {
         if (w.dev) (void)hipFree(w.dev);
         w.dev = nullptr; w.dev_bytes = 0;
@@ -552,7 +671,7 @@ int rawdtw_seed_resident_begin(rawdtw_ctx *ctx, uint32_t n_chunks, const uint64_
     h_off[0] = 0;
     for (uint64_t k = 0; k < n; k++) { h_off[k + 1] = h_off[k] + ev_len[k]; h_src[k] = ev_start[k]; }
     for (uint64_t k = 0; k <= n; k++) h_hoff[k] = 0;
-    w.pin[0] = 0;
+    w.pin[0] = w.pin[1] = 0;
     w.pending = true; w.resident = true; w.n = n_chunks; w.n_events = N; w.cap = 0;
     w.h_hoff = hit_off; w.h_hits = nullptr; w.direct_off = w.direct_hits = false;
     w.r_hoff = h_hoff; w.r_total = 0;
@@ -568,23 +687,29 @@ int rawdtw_seed_resident_begin(rawdtw_ctx *ctx, uint32_t n_chunks, const uint64_
     a.kept = reinterpret_cast<uint32_t *>(p); p += b_cnt;
     a.chits = reinterpret_cast<uint64_t *>(p); p += b_off;
     a.hoff = reinterpret_cast<uint64_t *>(p); p += b_off;
-    a.tot = reinterpret_cast<uint64_t *>(p);
+    a.tot = reinterpret_cast<uint64_t *>(p); p += b_tot;
     a.off = d_off; a.src = d_src; a.ev = ctx->d_ev; a.n = n_chunks;
     a.e = w.pars.e; a.q = w.pars.q; a.lq = w.pars.lq;
     a.slots = w.d_slots; a.list = w.d_list; a.log2_slots = w.log2_slots;
-    w.ra = a; w.d_hoff = a.hoff;
+    MinArgs mn{};
+    if (w.pars.w) { // (as in rawdtw_seed_begin)
+        mn = MinArgs{d_off, a.code, a.pos, a.kept, nullptr, nullptr, nullptr, a.tot + 1, w.pars.e, w.pars.lq + 2, w.pars.w};
+        mn.hash = a.code = reinterpret_cast<uint32_t *>(p); p += b_ev;
+        mn.pos = a.pos = reinterpret_cast<uint32_t *>(p); p += b_ev;
+        mn.count = a.kept = reinterpret_cast<uint32_t *>(p);
+    }
+    w.ra = a; w.d_hoff = a.hoff; // (the retained words are the sketch's)
     hipStream_t s = ctx->stream;
     auto undo = [&](int st) { w.pending = false; w.resident = false; return st; };
     if (hipMemcpyAsync(d_off, h_off, (n + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(d_src, h_src, n * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemsetAsync(a.tot, 0, 32, s) != hipSuccess || hipEventRecord(w.ev0, s) != hipSuccess)
         return undo(hip_fail(ctx, hipGetLastError(), "seeding upload"));
-    hipLaunchKernelGGL(k_seed_filter<true>, dim3((uint32_t)((n + kW - 1) / kW)), dim3(kW), 0, s, a);
-    hipLaunchKernelGGL(k_seed_probe, dim3(n_chunks), dim3(kW), 0, s, a);
-    hipLaunchKernelGGL(k_seed_scan, dim3(1), dim3(1024), 0, s, a.chits, n_chunks, a.hoff, a.tot, static_cast<uint64_t *>(nullptr));
+    launch_seeding<true>(a, mn, w.pars.w, s, nullptr);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipEventRecord(w.ev1, s);
     if (e == hipSuccess) e = hipMemcpyAsync(h_hoff, a.hoff, (n + 1) * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(w.pin + 1, a.tot + 1, 8, hipMemcpyDeviceToHost, s); // (k_seed_min's overflow flag)
     if (e == hipSuccess) e = hipEventRecord(w.done, s);
     if (e != hipSuccess) return undo(hip_fail(ctx, e, "seeding launches"));
     return RAWDTW_OK;
@@ -602,6 +727,7 @@ int rawdtw_seed_resident_end(rawdtw_ctx *ctx, float *kernel_ms)
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         HIP_TRY(ctx, hipEventSynchronize(w.done));
         if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, w.ev0, w.ev1));
+        if (w.pin[1]) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, kOverflow); // (nothing written, nothing readable)
     }
     for (uint64_t k = 0; k <= w.n; k++) w.h_hoff[k] = w.r_hoff[k];
     w.r_total = w.r_hoff[w.n];

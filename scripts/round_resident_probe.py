@@ -11,7 +11,9 @@ Prints one JSON line (profiles/round_resident_probe.json):
                             anchor up, the events' bytes once, the same PAF lines from both paths
 --ref-bp sets the reference: 500 kb keeps every read below the chaining's 2 048-seed cap (checked here on the host); 4.6 Mb, the
 reference of scripts/seed_probe.py, puts most reads above it and every round falls back -- the cost of that cap.
-python scripts/round_resident_probe.py [--reads N] [--ref-bp B] [--reps R] [--resident-only] [--out PATH]"""
+--w N builds the index (and so seeds the chunks) at a minimizer window of N; the mapper seeds such a round on its context only with
+--opts seed_minimizer=1 (without it rawdtw_mapper_round_seeded seeds on the host and the resident round is refused).
+python scripts/round_resident_probe.py [--reads N] [--ref-bp B] [--reps R] [--w N] [--opts name=value,...] [--resident-only] [--out PATH]"""
 import argparse
 import json
 import os
@@ -49,6 +51,8 @@ def main():
     ap.add_argument("--ref-bp", type=int, default=500_000)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--resident-only", action="store_true", help="the resident rounds alone, a few times (for a profiler run)")
+    ap.add_argument("--w", type=int, default=0, help="the minimizer window of the index (0: every e-mer)")
+    ap.add_argument("--opts", default="", help="context options, name=value,name=value (rawdtw_set_option)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
 
@@ -59,7 +63,7 @@ def main():
 
     rng = np.random.default_rng(20241101)
     ref = synth.make_reference([a.ref_bp], seed=20241017)
-    six = seeding.SeedIndex.from_signals(ref.forward, ref.reverse, threads=16)
+    six = seeding.SeedIndex.from_signals(ref.forward, ref.reverse, seeding.SeedParams(w=a.w), threads=16)
     say("index built: %d keys, %d positions" % (six.n_keys, six.n_positions))
     n = a.reads
     reads = make_reads(ref, n, rng)
@@ -75,6 +79,9 @@ def main():
         say("round %d: %d events, %d hits, %.0f a chunk, at most %d" % (c + 1, N, int(hoff[-1]), hoff[-1] / n, int(np.diff(hoff).max())))
     so_far = rounds[0]["hits"] + rounds[1]["hits"]   # (a read's seeds in round 2 are at most its hits so far)
     eng = ra.Engine(0)
+    for item in filter(None, a.opts.split(",")):
+        name, value = item.split("=")
+        eng.set_option(name, int(value))
     eng.upload_reference(ref.forward, ref.reverse)
     eng.upload_seed_index(six)
     opt = ra.MapOpt()

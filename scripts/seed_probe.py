@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Seeding on the device against its own copies, the host path and the reference's own code: 16 384 chunks of about 400 events,
 noisy stretches (a few events dropped or doubled) of both strands of a 4.6 Mb synthetic reference, at the parameters of
-ri_idxopt_init (e 6, q 9, lq 3, w 0).  Prints one JSON line (profiles/seed_probe.json):
+ri_idxopt_init (e 6, q 9, lq 3, w 0; --w N: the index and the chunks' sketches at a minimizer window of N, which the device seeds
+only with --opts seed_minimizer=1).  Prints one JSON line (profiles/seed_probe.json):
   kernel_ms        the four launches' device time (HIP events, rawdtw_seed_end)
   call_ms          rawdtw_seed_begin ... rawdtw_seed_end from and into page-locked memory, host wall time
   h2d_ms, d2h_ms   plain copies of the events up and of as many bytes as the hits down, page-locked, timed in the same run
@@ -9,7 +10,7 @@ ri_idxopt_init (e 6, q 9, lq 3, w 0).  Prints one JSON line (profiles/seed_probe
   ref_1t_ms        the reference's own ri_sketch + ri_idx_get (oracle.loader.RefMap.hits, oracle/_ref) on one thread over the first
                    --ref-chunks chunks, scaled to the whole batch by hits (not code under test: the baseline)
 each the median of --reps runs after a warm-up of at least 200 ms (the host's and the reference's legs: fewer runs, no warm-up).
-python scripts/seed_probe.py [--chunks N] [--ref-bp B] [--reps R] [--ref-chunks K] [--out PATH]"""
+python scripts/seed_probe.py [--chunks N] [--ref-bp B] [--reps R] [--ref-chunks K] [--w N] [--opts name=value,...] [--out PATH]"""
 import argparse
 import ctypes as C
 import json
@@ -59,6 +60,8 @@ def main():
     ap.add_argument("--ref-chunks", type=int, default=1024)
     ap.add_argument("--no-host1", action="store_true")
     ap.add_argument("--device-only", action="store_true", help="the device call alone, a few times (for a profiler run)")
+    ap.add_argument("--w", type=int, default=0, help="the minimizer window of the index and the sketches (0: every e-mer)")
+    ap.add_argument("--opts", default="", help="context options, name=value,name=value (rawdtw_set_option)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
 
@@ -74,7 +77,8 @@ def main():
     ref = synth.make_reference([a.ref_bp], seed=20241017)
     say("reference made")
     t = time.perf_counter()
-    six = seeding.SeedIndex.from_signals(ref.forward, ref.reverse, threads=16)
+    pars = seeding.SeedParams(w=a.w)
+    six = seeding.SeedIndex.from_signals(ref.forward, ref.reverse, pars, threads=16)
     build_ms = (time.perf_counter() - t) * 1e3
     say("index built: %d keys, %d positions, %.0f MB" % (six.n_keys, six.n_positions, six.table_bytes / 1e6))
     chunks = make_chunks(ref, a.chunks, rng)
@@ -91,6 +95,9 @@ def main():
     say("host: %d hits, %.1f ms on 16 threads" % (H, host16_ms))
     hoff, hits = PinnedArray(n + 1, np.uint64), PinnedArray(H, seeding.HIT_DTYPE)
     eng = ra.Engine(0)
+    for item in filter(None, a.opts.split(",")):
+        name, value = item.split("=")
+        eng.set_option(name, int(value))
     t = time.perf_counter()
     eng.upload_seed_index(six)
     upload_ms = (time.perf_counter() - t) * 1e3
@@ -140,7 +147,7 @@ def main():
     from oracle.loader import RefMap
 
     if RefMap.available() and a.ref_chunks:
-        rm = RefMap(ref.forward, ref.reverse)
+        rm = RefMap(ref.forward, ref.reverse, w=a.w)
         k = min(a.ref_chunks, n)
         say("reference index built")
 
@@ -153,9 +160,9 @@ def main():
         w16 = want[:int(want_off[16])]
         ref_same = bool(np.array_equal(got, np.stack([w16["ref_seq"], w16["strand"].astype(np.uint32), w16["target_position"], w16["query_position"]], 1)))
         ref_scaled = ref_ms * H / max(int(want_off[k]), 1)
-    lookups = int(sum(max(0, len(seeding.sketch(c)[0])) for c in chunks[:256])) * n / 256   # (estimated from the first 256 chunks)
+    lookups = int(sum(max(0, len(seeding.sketch(c, pars)[0])) for c in chunks[:256])) * n / 256   # (estimated from the first 256 chunks)
     rec = {
-        "probe": "seed", "chunks": n, "events": N, "hits": H, "hits_per_chunk": round(H / n, 1), "lookups_est": int(lookups),
+        "probe": "seed", "w": a.w, "opts": a.opts, "elements_per_event": round(lookups / N, 4), "chunks": n, "events": N, "hits": H, "hits_per_chunk": round(H / n, 1), "lookups_est": int(lookups),
         "reference_bp": a.ref_bp, "keys": six.n_keys, "positions": six.n_positions, "table_bytes": six.table_bytes,
         "index_build_16t_ms": round(build_ms, 1), "table_upload_ms": round(upload_ms, 1), "equal_to_host": same,
         "kernel_ms": round(kernel_ms, 4), "call_ms": round(call_ms, 4), "h2d_ms": round(h2d_ms, 4), "d2h_ms": round(d2h_ms, 4),
