@@ -101,10 +101,19 @@ int rawdtw_sync(rawdtw_ctx *ctx);
  *   wave for each chain of at least "fold_long_parts" (768) parts (3), or (default 4) device-planned batches fold and select
  *   in one launch out of LDS and job-list batches as 3; a batch keeps the form it was created under
  *   "debug_skip_kinds": timing experiments only -- launches of the masked kinds are not issued (results wrong)
+ *   "tb_workspace_mb": the direction-buffer budget of one traceback sub-batch in MiB (rawdtw_traceback_batch*).  0 (the
+ *   default): the environment variable RAWDTW_TB_WORKSPACE_MB if set, else 16 384.  A non-zero value goes before the
+ *   variable, which is read at every call.  A call whose jobs' direction buffers (plus 256 bytes a job) pass the budget is
+ *   cut, in job order, into sub-batches that each fit -- a job over the budget goes alone -- and these run as a two-deep
+ *   pipeline; the results do not depend on the cut.
  * The environment variable RAWDTW_OPTS="name=value,..." applies options at rawdtw_create. */
 int rawdtw_set_option(rawdtw_ctx *ctx, const char *name, int64_t value);
 /* The value of an option that callers pass on from one context to another ("chain_long_seeds": rawdtw_mapper_create gives its second
- * group's context the first one's).  RAWDTW_ERR_INVALID for any other name. */
+ * group's context the first one's), "seed_minimizer" and "tb_workspace_mb" as they were set, and the read-only
+ *   "tb_sub_batches": the number of sub-batches of this context's most recent rawdtw_traceback_batch* call; 0 before any.
+ *   It is known once the call has cut its jobs, before the first plan is built: a call refused while it plans (a banded
+ *   job, say) reports its cut all the same.  rawdtw_set_option refuses the name.
+ * RAWDTW_ERR_INVALID for any other name. */
 int rawdtw_get_option(const rawdtw_ctx *ctx, const char *name, int64_t *value);
 /* the ctx's hipStream_t, as void* (for event timing on the stream kernels run on) */
 int rawdtw_stream(rawdtw_ctx *ctx, void **stream);

@@ -117,6 +117,8 @@ struct rawdtw_ctx {
     hipStream_t tb_copy = nullptr;                      // traceback: the paths' way home, beside the next sub-batch's kernels
     float tb_fill_ms = 0.f, tb_walk_ms = 0.f;          // device time of the most recent rawdtw_traceback_batch
     uint64_t tb_dir_written = 0, tb_path_elems = 0;
+    uint64_t tb_workspace_mb = 0; // "tb_workspace_mb": direction-buffer budget of a traceback sub-batch in MiB (0: RAWDTW_TB_WORKSPACE_MB, else 16 GiB)
+    uint64_t tb_sub_batches = 0;  // "tb_sub_batches" (read-only): sub-batches of the most recent traceback call, known before its first plan is built
     bool merge_small = true; // tile + 16-lane-row + register-wave launches of a batch as one launch (k_band_merged)
     int fold_mode = 4; // 0: wave per chain, 1/2: lane per chain (16/32 parts per round; 30x less VALU work), 3: lanes + a wave for each long chain,
                        // 4: sync-free batches fold and select in one launch out of LDS (k_fold_select), job-list batches as 3

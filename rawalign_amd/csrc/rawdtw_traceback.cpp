@@ -38,7 +38,9 @@ static int traceback_core(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_
     ctx->tb_fill_ms = ctx->tb_walk_ms = 0.f; ctx->tb_dir_written = 0; ctx->tb_path_elems = 0;
 
     uint64_t budget = 16ull << 30;
-    if (const char *e = getenv("RAWDTW_TB_WORKSPACE_MB")) budget = std::max<uint64_t>(1, strtoull(e, nullptr, 10)) << 20;
+    if (ctx->tb_workspace_mb) budget = ctx->tb_workspace_mb << 20; // (the option goes before the variable)
+    else if (const char *e = getenv("RAWDTW_TB_WORKSPACE_MB")) budget = std::max<uint64_t>(1, strtoull(e, nullptr, 10)) << 20;
+    ctx->tb_sub_batches = 0;
     for (uint64_t k = 0; k < n_jobs; k++)
         if (jobs[k].n == 0 || jobs[k].m == 0) return fail(ctx, RAWDTW_ERR_INVALID, "zero-length traceback job");
     struct Sub {
@@ -73,8 +75,7 @@ static int traceback_core(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_
     auto dev_need = [&](uint64_t cnt, uint64_t acc) { return al(cnt * 8) + al(cnt * 4) + 3 * al((size_t)acc * 4) + al((size_t)acc); };
     auto host_need = [&](uint64_t cnt, uint64_t acc) { return al((size_t)acc * 4) + al((size_t)acc) + 2 * al(cnt * 4); };
 
-    // ---- all sub-batches planned first (host planner, device allocations, job records' upload: while nothing is in flight) ----
-    size_t dn = 0, hn = 0;
+    // the split: a job joins the current sub-batch unless that passes the budget (a job over the budget goes alone)
     for (uint64_t begin = 0; begin < n_jobs;) {
         uint64_t end = begin, bytes = 0;
         while (end < n_jobs) {
@@ -85,8 +86,14 @@ static int traceback_core(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_
             end++;
         }
         subs.emplace_back();
-        Sub &sb = subs.back();
-        sb.begin = begin; sb.cnt = end - begin; sb.slot = (int)((subs.size() - 1) & 1);
+        subs.back().begin = begin; subs.back().cnt = end - begin; subs.back().slot = (int)((subs.size() - 1) & 1);
+        begin = end;
+    }
+    ctx->tb_sub_batches = subs.size();
+    // ---- all sub-batches planned first (host planner, device allocations, job records' upload: while nothing is in flight) ----
+    size_t dn = 0, hn = 0;
+    for (Sub &sb : subs) {
+        const uint64_t begin = sb.begin, end = sb.begin + sb.cnt;
         st = build_plan(ctx, jobs + begin, sb.cnt, true, &sb.pl);
         if (st != RAWDTW_OK) { sb.pl = nullptr; return st; }
         for (hipEvent_t &e : sb.ev) HIP_TRY(ctx, hipEventCreate(&e));
@@ -103,7 +110,6 @@ static int traceback_core(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_
             for (uint64_t p = 0; p < sb.cnt; p++) { sb.poff[p] = acc; acc += (uint64_t)sb.pl->h_jobs[p].n + sb.pl->h_jobs[p].m - 1; }
         sb.acc = acc;
         dn = std::max(dn, dev_need(sb.cnt, acc)); hn = std::max(hn, host_need(sb.cnt, acc));
-        begin = end;
     }
     for (Sub &sb : subs) sb.pl->d_dir = ctx->d_tb_dir; // (the context's direction workspace may have grown while the later ones were planned)
     // grow-only buffers of the context, two slots each

@@ -176,6 +176,12 @@ class Engine:
     def set_option(self, name: str, value: int):
         self._check(self.lib.rawdtw_set_option(self._ctx, name.encode(), int(value)))
 
+    def get_option(self, name: str) -> int:
+        """rawdtw_get_option: the options that can be read back, and the read-only "tb_sub_batches" """
+        v = C.c_int64()
+        self._check(self.lib.rawdtw_get_option(self._ctx, name.encode(), C.byref(v)))
+        return int(v.value)
+
     def chain_round_stats(self) -> dict:
         """rawdtw_chain_round_stats: chaining rounds begun on this context, the reads and seeds its long path ("chain_long_seeds") chained, and
         the long path's 64-candidate steps that read beyond its LDS ring -- cumulative"""
