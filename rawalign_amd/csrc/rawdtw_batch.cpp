@@ -4,6 +4,7 @@
 // modes and for what the stream path declines, run / fetch / diagnostics, and chunk rounds (rawdtw_batch_submit_carry).
 // Host code only.
 #include "rawdtw_capi.h"
+#include "rawdtw_plan_check.h"
 
 using namespace rawdtw;
 using namespace rawdtw::capi;
@@ -559,6 +560,44 @@ int rawdtw_batch_round_stats(rawdtw_ctx *ctx, rawdtw_batch *batch, uint64_t *par
     return RAWDTW_OK;
 }
 
+// A device-planned batch's plan on the host, downloaded once (its counters are home: stream_counters): the work list's entries
+// in use -- both stretches --, all job records, the copy-order slots in use, the side list.  A work list longer than the slots
+// leaves the arrays empty (StreamPlanView::fits_slots: the readers say so).
+struct StreamPlanHost {
+    StreamPlanView v;
+    std::vector<PassEntry> todo;
+    std::vector<JobRec> recs;
+    std::vector<CopyOrder> runtab;
+    std::vector<DevJob> side;
+};
+static_assert(sizeof(PassEntry) == sizeof(uint4) && sizeof(JobRec) == sizeof(uint2) && sizeof(CopyOrder) == sizeof(uint4), "the host's records are the device's words");
+static int stream_plan_download(rawdtw_ctx *ctx, const rawdtw_batch *batch, StreamPlanHost &h)
+{
+    const StreamArgs &a = batch->sa;
+    const unsigned long long *cnt = batch->h_cnt;
+    StreamPlanView &v = h.v;
+    v.n_anchors = a.n_anchors; v.n_chains = batch->n_chains;
+    v.n_tiles = a.n_tiles; v.n_slots = a.n_slots; v.lds_floats = a.lds_floats; v.lane_max_n = a.lane_max_n; v.lane_max_radius = a.lane_max_radius;
+    v.n_first = cnt[kCntTodo]; v.n_pool = cnt[kCntPool]; v.n_other = cnt[kCntOthers]; v.n_reused = cnt[kCntReused];
+    v.anchor_off = batch->in_anchor_off;
+    if (!v.fits_slots()) return RAWDTW_OK;
+    constexpr size_t kRT = 2 * kStreamMaxSeg;
+    h.todo.resize(v.n_todo()); h.runtab.resize(v.n_todo() * kRT);
+    h.recs.resize((size_t)a.n_tiles * kStreamRecStride); h.side.resize(v.n_other);
+    if (v.n_first) {
+        HIP_TRY(ctx, hipMemcpy(h.todo.data(), a.todo, v.n_first * sizeof(uint4), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(h.runtab.data(), a.runtab, v.n_first * kRT * sizeof(uint4), hipMemcpyDeviceToHost));
+    }
+    if (v.n_pool) {
+        HIP_TRY(ctx, hipMemcpy(h.todo.data() + v.n_first, a.todo + a.n_tiles, v.n_pool * sizeof(uint4), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(h.runtab.data() + v.n_first * kRT, a.runtab + (size_t)a.n_tiles * kRT, v.n_pool * kRT * sizeof(uint4), hipMemcpyDeviceToHost));
+    }
+    if (!h.recs.empty()) HIP_TRY(ctx, hipMemcpy(h.recs.data(), a.recs, h.recs.size() * sizeof(uint2), hipMemcpyDeviceToHost));
+    if (v.n_other) HIP_TRY(ctx, hipMemcpy(h.side.data(), a.ojobs, v.n_other * sizeof(DevJob), hipMemcpyDeviceToHost));
+    v.todo = h.todo.data(); v.recs = h.recs.data(); v.runtab = h.runtab.data(); v.side = h.side.data();
+    return RAWDTW_OK;
+}
+
 int rawdtw_batch_verify_plan(rawdtw_ctx *ctx, const rawdtw_batch *batch, const rawdtw_job_t *jobs, uint64_t n_jobs,
                              int *device_planned, char *message, uint32_t message_cap)
 {
@@ -573,135 +612,28 @@ int rawdtw_batch_verify_plan(rawdtw_ctx *ctx, const rawdtw_batch *batch, const r
     auto S = [](uint64_t v) { return std::to_string(v); };
     std::string e;
     if (batch->stream) {
-        // What the scan left behind for the DTW launch, against the job list the host builds from the same chains
-        // (rawdtw_batch_build_jobs): every job either of the tile class by the class rule, then in exactly one pass's
-        // records with its shape, radius, flag and windows, or in the side list exactly once with the job's windows,
-        // shape, slanted radius and flag; the statistics.
+        // what the scan and k_plan left behind for the DTW launch, against the job list the host builds from the same chains
+        // (check_stream_plan); then the statistics, which the device sums
         rawdtw_batch *mb = const_cast<rawdtw_batch *>(batch);
         int st = stream_counters(ctx, mb);
         if (st != RAWDTW_OK) return st;
-        const StreamArgs &a = batch->sa;
-        const unsigned long long *cnt = batch->h_cnt;
         if (stream_declined(batch)) {
             if (device_planned) *device_planned = 0;
             say("the stream path declined this batch (it is redone through the job list at fetch)");
             return RAWDTW_OK;
         }
-        const uint64_t nc = batch->n_chains, na = a.n_anchors;
-        const uint64_t *aoff = batch->in_anchor_off;
-        // the work list: one entry a pass (checked below, once the jobs' classes are known)
-        const uint64_t n_first = cnt[kCntTodo], n_pool = cnt[kCntPool], n_todo = n_first + n_pool;
-        std::vector<uint4> todo(n_todo);
-        if (n_first > a.n_tiles || n_pool > a.n_slots - a.n_tiles) e = "work list longer than the slots";
-        else {
-            if (n_first) HIP_TRY(ctx, hipMemcpy(todo.data(), a.todo, n_first * sizeof(uint4), hipMemcpyDeviceToHost));
-            if (n_pool) HIP_TRY(ctx, hipMemcpy(todo.data() + n_first, a.todo + a.n_tiles, n_pool * sizeof(uint4), hipMemcpyDeviceToHost));
-        }
-        const uint64_t n_other = cnt[kCntOthers];
-        std::vector<DevJob> oj(n_other);
-        if (n_other) HIP_TRY(ctx, hipMemcpy(oj.data(), a.ojobs, n_other * sizeof(DevJob), hipMemcpyDeviceToHost));
-        // job k of chain c's part p lives at anchor index a1 - 2 - p
-        std::vector<uint64_t> slot_job(na, ~0ull);
-        {
-            uint64_t k = 0;
-            for (uint64_t c = 0; c < nc; c++) {
-                const uint64_t a0 = aoff[c], a1 = aoff[c + 1];
-                for (uint64_t pidx = 0; a1 > a0 && pidx + 1 < a1 - a0; pidx++) slot_job[a1 - 2 - pidx] = k++;
-            }
-            if (k != n_jobs) e = "job count";
-        }
-        uint64_t tile_jobs = 0, tile_bytes = 0, other_bytes = 0;
-        std::vector<uint8_t> is_tile(n_jobs, 0);
-        for (uint64_t k = 0; k < n_jobs && e.empty(); k++) {
-            const rawdtw_job_t &j = jobs[k];
-            const int R = slanted_radius(j.n, j.m, j.band_radius);
-            const uint32_t N = std::max(j.n, j.m);
-            is_tile[k] = R <= a.lane_max_radius && N <= a.lane_max_n;
-            tile_jobs += is_tile[k];
-            (is_tile[k] ? tile_bytes : other_bytes) += 4ull * ((uint64_t)j.n + j.m) + 36ull;
-        }
-        std::vector<uint8_t> oseen(n_jobs, 0);
-        for (uint64_t q = 0; q < n_other && e.empty(); q++) {
-            const DevJob &d = oj[q];
-            const uint64_t k = d.aux < na ? slot_job[d.aux] : ~0ull;
-            if (k == ~0ull || oseen[k] || is_tile[k]) e = "side-list entry " + S(q) + " (anchor " + S(d.aux) + ") duplicated, of the tile class or no job at all";
-            else if (d.n != jobs[k].n || d.m != jobs[k].m || d.ref_off != jobs[k].ref_off || d.read_off != jobs[k].read_off ||
-                     d.R != slanted_radius(d.n, d.m, jobs[k].band_radius) || ((d.flags & kFlagExcludeLast) != 0) != (jobs[k].exclude_last != 0))
-                e = "side-list record of job " + S(k) + " differs from the job";
-            else oseen[k] = 1;
-        }
-        for (uint64_t k = 0; k < n_jobs && e.empty(); k++)
-            if (!is_tile[k] && !oseen[k]) e = "job " + S(k) + " is in no launch";
-        // Every pass: its records name tile-class jobs of its tile, each job once over all passes, with the job's shape,
-        // slanted radius and flag, in the order the lanes take them (radius class, longer side); a record's windows lie in the
-        // image, inside one of the pass's copy orders, and that order maps them onto the job's windows in the arenas.
+        StreamPlanHost h;
+        st = stream_plan_download(ctx, batch, h);
+        if (st != RAWDTW_OK) return st;
+        StreamPlanStats want;
+        e = check_stream_plan(h.v, jobs, n_jobs, &want);
         if (e.empty()) {
-            std::vector<uint8_t> tseen(n_jobs, 0), slot_used(a.n_slots, 0);
-            std::vector<uint2> recs(kStreamTile);
-            std::vector<uint4> ords(2 * kStreamMaxSeg);
-            for (uint64_t q = 0; q < n_todo && e.empty(); q++) {
-                const uint4 t = todo[q];
-                const uint32_t nj = t.z & 0xffffu, nr = (t.z >> 16) & 63u, n_hi = t.z >> 22, region = t.w & 0xffffu, rec0 = t.w >> 16;
-                if (t.x >= a.n_tiles || t.y >= a.n_slots || slot_used[t.y] || nj > kStreamTile || nr > kStreamMaxSeg || (nj && !nr) || n_hi > nj || (rec0 & 1u) || rec0 + nj > kStreamRecStride) {
-                    e = "work list entry " + S(q) + ": tile " + S(t.x) + ", slot " + S(t.y) + ", " + S(nj) + " jobs, " + S(nr) + " runs, first radius-1 record " + S(n_hi); break;
-                }
-                slot_used[t.y] = 1;
-                if (!nj) continue;
-                HIP_TRY(ctx, hipMemcpy(recs.data(), a.recs + (uint64_t)t.x * kStreamRecStride + rec0, nj * sizeof(uint2), hipMemcpyDeviceToHost));
-                HIP_TRY(ctx, hipMemcpy(ords.data(), a.runtab + (uint64_t)t.y * 2 * kStreamMaxSeg, 2 * nr * sizeof(uint4), hipMemcpyDeviceToHost));
-                for (uint32_t o = 0; o < 2 * nr && e.empty(); o++) {
-                    const uint4 &od = ords[o];
-                    const bool evs = (o & 1u) == 0;
-                    if (od.x >= od.y || 4ull * od.y > a.lds_floats || (evs ? 4ull * od.y > region : 4ull * od.x < region))
-                        e = "pass " + S(q) + " (tile " + S(t.x) + ", " + S(nj) + " jobs, " + S(nr) + " runs, event region " + S(region) + " of " + S(a.lds_floats) +
-                            " floats): copy order " + S(o) + " = pieces [" + S(od.x) + ", " + S(od.y) + ") outside its region of the image";
-                }
-                uint32_t prev_bin = 0, n_wide = 0; // (n_wide: the pass's records of radius >= 2 -- the entry's n_hi, where the chunks of k_runs change class)
-                for (uint32_t r = 0; r < nj && e.empty(); r++) {
-                    const uint2 rc = recs[r];
-                    const uint32_t N = rc.y & 127u, M = (rc.y >> 7) & 127u, R = (rc.y >> 14) & 3u, ex = (rc.y >> 16) & 1u, u = (rc.y >> 17) & (kStreamTile - 1u);
-                    const uint64_t i = ((uint64_t)t.x + 1) * kStreamTile - 1 - u;
-                    const uint64_t k = i < na ? slot_job[i] : ~0ull;
-                    const std::string who = "pass " + S(q) + " record " + S(r) + " (anchor " + S(i) + ")";
-                    if (k == ~0ull || !is_tile[k] || tseen[k]) { e = who + ": no job, not of the tile class, or in two passes"; break; }
-                    const rawdtw_job_t &j = jobs[k];
-                    const bool swap = j.n < j.m;
-                    if (N != std::max(j.n, j.m) || M != std::min(j.n, j.m) || (int)R != slanted_radius(j.n, j.m, j.band_radius) || (ex != 0) != (j.exclude_last != 0)) {
-                        e = who + ": shape, radius or flag differ from job " + S(k); break;
-                    }
-                    const uint32_t bin = (3u - R) * 64u + (63u - std::min(N, 63u));
-                    if (bin < prev_bin) { e = who + ": out of the lanes' order"; break; }
-                    prev_bin = bin;
-                    if (R >= 2u) n_wide++;
-                    else if (r < n_hi) { e = who + ": radius 1 ahead of the pass's first radius-1 record " + S(n_hi); break; }
-                    if (r >= n_hi && R != 1u) { e = who + ": radius " + S(R) + " at or behind the pass's first radius-1 record " + S(n_hi); break; }
-                    const uint32_t p_long = rc.x & 0xffffu, p_short = rc.x >> 16;
-                    const uint32_t p_ev = swap ? p_short : p_long, p_rf = swap ? p_long : p_short;
-                    for (int w = 0; w < 2 && e.empty(); w++) {
-                        const uint32_t pw = w ? p_rf : p_ev, len = w ? j.m : j.n;
-                        const uint64_t want = w ? j.ref_off : (uint64_t)j.read_off;
-                        bool ok = false;
-                        for (uint32_t g = 0; g < nr && !ok; g++) {
-                            const uint4 &od = ords[2 * g + w];
-                            const long long src = (long long)((unsigned long long)od.z | ((unsigned long long)od.w << 32));
-                            ok = 4ull * od.x <= pw && (uint64_t)pw + len <= 4ull * od.y && (long long)pw + src == (long long)want;
-                        }
-                        if (!ok) e = who + ": its " + (w ? "reference" : "event") + " window is in no copy order of the pass";
-                    }
-                    tseen[k] = 1;
-                }
-                if (e.empty() && n_wide != n_hi) e = "pass " + S(q) + ": " + S(n_wide) + " records of radius >= 2, its entry says " + S(n_hi);
-            }
-            if (e.empty() && cnt[kCntReused] == 0) // (a round that took costs over leaves the carried parts out)
-                for (uint64_t k = 0; k < n_jobs && e.empty(); k++)
-                    if (is_tile[k] && !tseen[k]) e = "tile-class job " + S(k) + " is in no pass";
-        }
-        if (e.empty()) {
+            const StreamArgs &a = batch->sa;
             HIP_TRY(ctx, stream_sum_stats(a, ctx->stream));
             unsigned long long st3[3];
             HIP_TRY(ctx, hipMemcpyAsync(st3, a.cnt + kCntTileJobs, 24, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (st3[0] != tile_jobs || st3[1] != tile_bytes || st3[2] != other_bytes) e = "tile statistics";
+            if (st3[0] != want.tile_jobs || st3[1] != want.tile_bytes || st3[2] != want.other_bytes) e = "tile statistics";
         }
         say(e);
         return e.empty() ? RAWDTW_OK : RAWDTW_ERR_DEVICE + 100;
@@ -749,40 +681,12 @@ int rawdtw_batch_chunk_profile(rawdtw_ctx *ctx, rawdtw_batch *batch, int flat_ma
     const int st = stream_counters(ctx, batch);
     if (st != RAWDTW_OK) return st;
     if (stream_declined(batch)) return RAWDTW_OK;
-    // The tile launch's chunks, counted from the plan as k_runs walks it (run_dp, stream_lane_job): per body class -- 0 quad_dp_r3,
-    // 1 lane_dp_r2, 2 lane_dp_r12, 3 lane_dp_r1, 4 lane_dp_gen -- jobs, chunks, the chunks' columns (a chunk runs for its longest
-    // side) and the jobs' own columns; word 20 the passes.
-    const StreamArgs &a = batch->sa;
-    const uint64_t n_first = batch->h_cnt[kCntTodo], n_pool = batch->h_cnt[kCntPool];
-    if (n_first > a.n_tiles || n_pool > a.n_slots - a.n_tiles) return fail(ctx, RAWDTW_ERR_DEVICE, "work list longer than the slots");
-    std::vector<uint4> todo(n_first + n_pool);
-    if (n_first) HIP_TRY(ctx, hipMemcpy(todo.data(), a.todo, n_first * sizeof(uint4), hipMemcpyDeviceToHost));
-    if (n_pool) HIP_TRY(ctx, hipMemcpy(todo.data() + n_first, a.todo + a.n_tiles, n_pool * sizeof(uint4), hipMemcpyDeviceToHost));
-    std::vector<uint2> recs((size_t)a.n_tiles * kStreamRecStride); // (one copy: a bench batch has ten thousand passes)
-    if (!recs.empty()) HIP_TRY(ctx, hipMemcpy(recs.data(), a.recs, recs.size() * sizeof(uint2), hipMemcpyDeviceToHost));
-    uint64_t w[21] = {0};
-    for (const uint4 &t : todo) {
-        const uint32_t nj = t.z & 0xffffu, rec0 = t.w >> 16;
-        if (t.x >= a.n_tiles || nj > kStreamTile || rec0 + nj > kStreamRecStride || (t.z >> 22) > nj) return fail(ctx, RAWDTW_ERR_DEVICE, "work list entry out of range");
-        if (!nj) continue;
-        const uint2 *rc = recs.data() + (size_t)t.x * kStreamRecStride + rec0;
-        uint32_t n3 = 0;
-        for (uint32_t r = 0; r < nj && r < 64u; r++) n3 += ((rc[r].y >> 14) & 3u) == 3u;
-        const uint32_t n_hi = flat_map ? nj : std::max(t.z >> 22, n3);
-        const uint32_t n_chunks = chunk_map_count(n3, n_hi, nj);
-        for (uint32_t c = 0; c < n_chunks; c++) {
-            const ChunkRange cr = chunk_map_range(n3, n_hi, nj, c);
-            uint32_t n_max = 0, radii = 0;
-            uint64_t cols = 0;
-            for (uint32_t r = cr.first; r < cr.end; r++) {
-                const uint32_t N = rc[r].y & 127u;
-                n_max = std::max(n_max, N); cols += N; radii |= 1u << ((rc[r].y >> 14) & 3u);
-            }
-            const uint32_t cls = cr.quad ? 0u : radii == 4u ? 1u : radii == 2u ? 3u : !(radii & ~6u) ? 2u : 4u;
-            w[4 * cls] += cr.end - cr.first; w[4 * cls + 1]++; w[4 * cls + 2] += n_max; w[4 * cls + 3] += cols;
-        }
-        w[20]++;
-    }
+    StreamPlanHost h;
+    const int sd = stream_plan_download(ctx, batch, h);
+    if (sd != RAWDTW_OK) return sd;
+    if (!h.v.fits_slots()) return fail(ctx, RAWDTW_ERR_DEVICE, "work list longer than the slots");
+    uint64_t w[21];
+    if (!stream_chunk_profile(h.v, flat_map != 0, w)) return fail(ctx, RAWDTW_ERR_DEVICE, "work list entry out of range");
     *n_out = 21;
     for (uint32_t i = 0; i < 21 && i < cap && out; i++) out[i] = w[i];
     return RAWDTW_OK;

@@ -4,6 +4,7 @@
 //   rawdtw_planner.cpp    the host planner of the job-list path, its launch sequences, rawdtw_plan_*, rawdtw_score_batch
 //   rawdtw_batch.cpp      candidate batches: the stream path's set-up (sync-free, planned on the device), the job-list form,
 //                         run / fetch / diagnostics, chunk rounds
+//   rawdtw_plan_check.cpp the readers of a device-planned batch's plan behind those diagnostics (no HIP: rawdtw_plan_check.h)
 //   rawdtw_traceback.cpp  rawdtw_traceback_batch*, the single-call drop-ins
 //   rawdtw_index.cpp      the .ind reader
 // There is NO CPU fallback in any of them: every scoring entry point runs the HIP kernels or returns an error status.
@@ -291,14 +292,6 @@ void seed_resident_write_chain(rawdtw_ctx *ctx, rawdtw_seed_t *d_seeds, const ui
         hipError_t e_ = (expr);                                                                       \
         if (e_ != hipSuccess) return hip_fail((ctx), e_, #expr);                                      \
     } while (0)
-
-// post-slant radius, dtw.cpp:298-300 (unsigned 32-bit arithmetic for the correction)
-inline int slanted_radius(uint32_t n, uint32_t m, int r0)
-{
-    uint32_t N = n > m ? n : m, M = n > m ? m : n;
-    uint32_t extra = ((N - M) * (uint32_t)r0 + N - 1u) / N;
-    return r0 + (int)extra;
-}
 
 // exact size of the band's cell set (same walk as the kernels; host side, for reporting)
 inline uint64_t banded_cells(uint32_t n, uint32_t m, int R)

@@ -1,6 +1,6 @@
 // The chunk map of a pass of k_runs: which of the pass's sorted job records a wave takes together.  Shared by the kernel
-// (rawdtw_runs.hip: run_dp), the plan's self-check and profile (rawdtw_batch.cpp) and a plain C++ test program
-// (tests/abi/chunk_map.cpp): no HIP include here.
+// (rawdtw_runs.hip: run_dp), the plan's profile (rawdtw_plan_check.cpp) and plain C++ test programs
+// (tests/abi/chunk_map.cpp, tests/abi/plan_fmt.cpp): no HIP include here.  The records themselves: rawdtw_plan_fmt.h.
 //
 // A pass's records are sorted radius 3 first, then 2, then 1, each run by longer side, descending (k_plan).  With
 //   n3      the radius-3 records the quads take: those among the pass's first 64,

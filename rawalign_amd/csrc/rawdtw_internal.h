@@ -5,24 +5,11 @@
 
 #include "../../include/rawdtw.h"
 #include "rawdtw_chunks.h"
+#include "rawdtw_plan_fmt.h" // DevJob, kFlagExcludeLast, the stream plan's constants and packed records
 
 namespace rawdtw {
 
 constexpr float kInf = 1e10f; // dtw.cpp:38,310-313: the float nearest 1e10
-
-// Device job record, 32 bytes, in PLAN order.  Written by the planner.
-struct DevJob {
-    uint64_t ref_off;  // element offset of b[0] in the reference arena
-    uint32_t read_off; // element offset of a[0] in the event arena
-    uint32_t n;        // a_length
-    uint32_t m;        // b_length
-    int32_t R;         // banded: radius AFTER the slant correction (dtw.cpp:298-300); full: -1
-    uint32_t flags;    // bit0: exclude_last_element
-    uint32_t aux;      // the job's index in the caller's batch: kernels store their cost at out[aux]
-};
-static_assert(sizeof(DevJob) == 32, "DevJob must stay 32 bytes");
-
-enum : uint32_t { kFlagExcludeLast = 1u };
 
 // launch kinds (also reported by rawdtw_plan_run_timed)
 enum LaunchKind : uint32_t {
@@ -63,17 +50,15 @@ struct ChainDesc {
 };
 static_assert(sizeof(ChainDesc) == 24, "ChainDesc must stay 24 bytes");
 
-constexpr int kMaxLaneRadius = 3;      // lane-per-job DP is instantiated for R in [0, 3]: a sweep showed that the rare
-                                       // jobs with larger radii (0.4 % of a sparse batch) cost half of the tile kernel's
-                                       // time through divergence and register pressure; they go to k_band_wreg<1>
+// (kMaxLaneRadius, kLaneMaxN -- the lane-per-job class -- are in rawdtw_plan_fmt.h: the records' widths depend on them)
 constexpr int kMaxLaneRadiusHi = 8;    // second tile-kernel instance: radii kMaxLaneRadius+1 .. 8
-constexpr int kLaneMaxN = 73;          // ... and for jobs whose longer side is at most this
 // tile kernel: a tile = consecutive lane-eligible jobs whose windows fit this much LDS
 constexpr uint32_t kTileLdsFloats = 4800;  // job-list tile kernel: 8 workgroups per CU
 constexpr uint32_t kStreamTileFloats = 5800; // k_runs: image + the pass's records + two passes' copy orders = 29 KB a workgroup: five workgroups per
                                              // CU, and 13 KB of the CU's 160 KB stay free for a planner workgroup of the batches behind (at 7000 floats
                                              // and two record buffers it was four workgroups and 5 KB: nothing fitted beside them; the bench batch's
                                              // tiles average 5 200 floats: below 5 400 every other tile takes two passes and the planning doubles)
+static_assert(kStreamTileFloats <= kStreamMaxImageFloats, "the default image is one the option admits");
 constexpr uint32_t kTileMaxJobs = 1024;
 constexpr uint32_t kTileHiLdsFloats = 14336, kTileHiMaxJobs = 64; // wide-band instance: one wave per tile
 constexpr uint32_t kTileMaxSpans = 96;
@@ -106,10 +91,7 @@ struct FullAux {
 //             parts p = 0 .. n - 2 in the reference's order are out[a1 - 2 - p]: the fold walks it downwards.
 //   side list parts the lane-per-job bodies do not take (radius > lane_max_radius or longer side > lane_max_n), found
 //             by k_scan ahead of the DTW launch and scored there first, wave-cooperatively, longest first.
-constexpr uint32_t kStreamTile = 512;         // anchors (= candidate parts) of a tile: what one wave of the scan plans (eight a lane)
-constexpr uint32_t kStreamRecStride = 576;    // job records of a tile: its passes' records one behind the other, each pass on a 16-byte boundary
-constexpr uint32_t kStreamMaxSeg = 32;        // runs of one pass over a tile's image (more: the tile takes another pass)
-static_assert(kStreamMaxSeg < 64 && kStreamTile < 1024, "a list entry's third word: jobs (16 bits), runs (6), first radius-1 record (10)");
+// (kStreamTile, kStreamRecStride, kStreamMaxSeg: rawdtw_plan_fmt.h)
 // side-list classes, in launch order: wave-per-job by longer side (>= 1024, >= 256, >= 64, shorter), 16-lane groups, 8-lane groups
 constexpr uint32_t kStreamClasses = 21, kClsW0 = 0, kClsG16 = 4, kClsL0 = 5, kClsLCount = 8, kClsM0 = 13, kClsMCount = 8;
 // Side-list classes 13..20: bands of up to 8 slots (radius <= 7) that are not in the classes below: one lane per job too
@@ -189,17 +171,9 @@ struct StreamArgs {
     // workspace and outputs (device)
     uint2 *tlist;                // the scan's tile list: (tile, the chain its first anchor belongs to) of every tile that has a part for the
                                  // lane bodies; cnt[kCntTodo] entries, at most n_tiles
-    uint4 *todo;                 // the DTW launch's work list (k_plan): one entry a PASS -- a tile's tile-class parts, or as many of them
-                                 // as fit the image budget and the run table: (tile, copy-order slot, jobs | runs << 16 | the pass's
-                                 // first radius-1 record << 22 (rawdtw_chunks.h: n_hi), floats of the image's event region |
-                                 // first record << 16), at the index of its slot: [0, cnt[kCntTodo]) the listed
-                                 // tiles' first passes, [n_tiles, n_tiles + cnt[kCntPool]) the others
-    uint2 *recs;                 // n_tiles x kStreamRecStride job records, a pass's in the order the lanes take them (radius class, then longer
-                                 // side, descending): x = event window | reference window << 16 (float offsets into the pass's
-                                 // image, longer sequence first), y = N | M << 7 | R << 14 | exclude_last << 16 | item << 17
-                                 // (item u = the part that ends at anchor (tile end - 1 - u): its cost goes to out[that anchor])
-    uint4 *runtab;               // n_slots x 2 kStreamMaxSeg copy orders of 16-byte pieces, entry 2 g + w = run g of arena w (0 events,
-                                 // 1 reference): pieces [x, y) of the image come from arena float index (4 piece + (int64)(z | w << 32))
+    uint4 *todo;                 // the DTW launch's work list (k_plan), one entry a pass: rawdtw_plan_fmt.h, "pass entry"
+    uint2 *recs;                 // n_tiles x kStreamRecStride job records: rawdtw_plan_fmt.h, "job record"
+    uint4 *runtab;               // n_slots x 2 kStreamMaxSeg copy orders: rawdtw_plan_fmt.h, "copy order"
     unsigned long long *tile_stats; // per scan unit (8192 anchors): tile-class parts, their algorithmic bytes, the side list's bytes
     DevJob *omix, *ojobs;
     uint8_t *ocls;

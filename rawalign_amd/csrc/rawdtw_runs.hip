@@ -290,11 +290,6 @@ __device__ __forceinline__ void fold_order_body(const uint64_t n_chains, const u
 // k_scan: the pass over the anchor list ahead of the DTW launch.  Roles by workgroup: [0, n_tiles) one tile each,
 // n_tiles the fold order, the rest the chain records.
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr uint32_t kSortBins = 192; // bin = (3 - radius) * 64 + (63 - longer side): radius 3 first, then 2, then 1, each run longest first (sides
-                                     // of 63 and more share a bin).  The first place of bin 128 -- the pass's first radius-1 record -- goes into
-                                     // the pass's list entry: k_runs starts the radius-1 run on a chunk boundary of its own, so that no wave
-                                     // holds parts of both radius 2 and radius 1 (rawdtw_chunks.h)
-
 // A tile's items in the order the image is laid out in: item u is the part that ends at anchor (tile end - 1 - u), so that
 // along a chain (stored end-first) u ascends with the positions -- a run's first part is the one with the lowest addresses,
 // and the scan that places the runs meets it first.
@@ -679,7 +674,7 @@ __global__ __launch_bounds__(kPlanT, 3) void k_plan(const StreamArgs a)
     wave_lds_sync();
     // the chain of the anchor at position p of the tile: c0 + the chain starts in positions 1 .. p
     auto chain_at = [&](uint32_t p) { return c0 + (pre[p >> 5] + __popc(mask[p >> 5] & (0xffffffffu >> (31u - (p & 31u)))) - (mask[0] & 1u)); };
-    // the tile parts: N | M << 7 | R << 14 | exclude_last << 16 | swapped << 17 | 1 << 20 (0: the lane bodies do not take it)
+    // the tile parts: the item words (rawdtw_plan_fmt.h; 0: the lane bodies do not take it)
     uint32_t tm[KI];
 #pragma unroll
     for (int k = 0; k < KI; k++) {
@@ -689,27 +684,27 @@ __global__ __launch_bounds__(kPlanT, 3) void k_plan(const StreamArgs a)
         const Part pt = classify(a, an[k + 1], an[k]);
         if (!pt.tile) continue;
         const uint32_t N = pt.n > pt.m ? pt.n : pt.m, M = pt.n > pt.m ? pt.m : pt.n;
-        tm[k] = N | (M << 7) | ((uint32_t)pt.R << 14) | ((mask_bit(mask, p) ? 0u : 1u) << 16) | ((pt.n < pt.m ? 1u : 0u) << 17) | (1u << 20);
+        tm[k] = rec_shape(N, M, (uint32_t)pt.R, mask_bit(mask, p) ? 0u : 1u) | ((pt.n < pt.m ? 1u : 0u) << kItemSwapped) | (1u << kItemTile);
     }
     {
-        const int t_first = (int)((tm[0] >> 20) & 1u), t_last = (int)((tm[KI - 1] >> 20) & 1u);
+        const int t_first = (int)((tm[0] >> kItemTile) & 1u), t_last = (int)((tm[KI - 1] >> kItemTile) & 1u);
         const bool below = __builtin_amdgcn_update_dpp(0, t_last, 0x138, 0xf, 0xf, false) != 0;  // lane - 1's last item (lane 0: none)
         const bool above = __builtin_amdgcn_update_dpp(0, t_first, 0x130, 0xf, 0xf, false) != 0; // lane + 1's first item (lane 63: none)
-        // an item's contributions to the regions' running sums (events | run start << 20; reference), from its record
+        // an item's contributions to the regions' running sums (events | run start << kSumRunShift; reference), from its record
         // (kept short on registers: recomputed where needed rather than held for the eight items)
         auto contrib = [](const uint32_t t, uint32_t &c_r, uint32_t &c_f) {
-            const bool tl = (t >> 20) & 1u, starts = (t >> 18) & 1u, ends = (t >> 19) & 1u, swap = (t >> 17) & 1u;
-            const uint32_t N = t & 127u, M = (t >> 7) & 127u, n = swap ? M : N, m = swap ? N : M;
-            c_r = tl ? ((starts ? n + 3u : n - 1u) + (ends ? 3u : 0u)) | ((starts ? 1u : 0u) << 20) : 0u;
+            const bool tl = (t >> kItemTile) & 1u, starts = (t >> kItemRunStart) & 1u, ends = (t >> kItemRunEnd) & 1u, swap = (t >> kItemSwapped) & 1u;
+            const uint32_t N = rec_n(t), M = rec_m(t), n = swap ? M : N, m = swap ? N : M;
+            c_r = tl ? ((starts ? n + 3u : n - 1u) + (ends ? 3u : 0u)) | ((starts ? 1u : 0u) << kSumRunShift) : 0u;
             c_f = tl ? (starts ? m + 3u : m - 1u) + (ends ? 3u : 0u) : 0u;
         };
         uint32_t lr = 0, lf = 0;
 #pragma unroll
         for (int k = 0; k < KI; k++) {
-            const bool t = (tm[k] >> 20) & 1u;
-            const bool pred = k + 1 < KI ? ((tm[k + 1 < KI ? k + 1 : k] >> 20) & 1u) != 0u : above;
-            const bool succ = k > 0 ? ((tm[k > 0 ? k - 1 : 0] >> 20) & 1u) != 0u : below;
-            tm[k] |= ((t && !pred ? 1u : 0u) << 18) | ((t && !succ ? 1u : 0u) << 19);
+            const bool t = (tm[k] >> kItemTile) & 1u;
+            const bool pred = k + 1 < KI ? ((tm[k + 1 < KI ? k + 1 : k] >> kItemTile) & 1u) != 0u : above;
+            const bool succ = k > 0 ? ((tm[k > 0 ? k - 1 : 0] >> kItemTile) & 1u) != 0u : below;
+            tm[k] |= ((t && !pred ? 1u : 0u) << kItemRunStart) | ((t && !succ ? 1u : 0u) << kItemRunEnd);
             uint32_t c_r, c_f;
             contrib(tm[k], c_r, c_f);
             lr += c_r; lf += c_f;
@@ -726,8 +721,8 @@ __global__ __launch_bounds__(kPlanT, 3) void k_plan(const StreamArgs a)
             // the items that fit: while the image of the parts so far stays inside the budget and their runs in the table (+ 4 + 4
             // floats and one run when the first item continues a run); the sums ascend with u: the fitting items are a prefix
             // (the rule: everything that is left fits -- the totals say so, and no item has to be looked at)
-            const bool all_fit = ((((tot_r & 0xfffffu) - b0r + 7u) & ~3u) + ((tot_f - b0f + 7u) & ~3u) <= budget) && ((tot_r >> 20) - b0s + 1u <= kStreamMaxSeg);
-            uint32_t u1 = kStreamTile, e_r = tot_r & 0xfffffu, e_f = tot_f, e_s = tot_r >> 20;
+            const bool all_fit = ((((tot_r & kSumFloatsMask) - b0r + 7u) & ~3u) + ((tot_f - b0f + 7u) & ~3u) <= budget) && ((tot_r >> kSumRunShift) - b0s + 1u <= kStreamMaxSeg);
+            uint32_t u1 = kStreamTile, e_r = tot_r & kSumFloatsMask, e_f = tot_f, e_s = tot_r >> kSumRunShift;
             bool cut_run = false;
             if (!all_fit || u0 != 0u) {
                 uint32_t fits = 0;
@@ -737,7 +732,7 @@ __global__ __launch_bounds__(kPlanT, 3) void k_plan(const StreamArgs a)
                     for (int k = 0; k < KI; k++) {
                         uint32_t c_r, c_f;
                         contrib(tm[k], c_r, c_f);
-                        const uint32_t u = kStreamTile - 1u - ((uint32_t)lane * KI + k), sr = xr & 0xfffffu, ss = xr >> 20;
+                        const uint32_t u = kStreamTile - 1u - ((uint32_t)lane * KI + k), sr = xr & kSumFloatsMask, ss = xr >> kSumRunShift;
                         if (u >= u0 && ((sr - b0r + 7u) & ~3u) + ((xf - b0f + 7u) & ~3u) <= budget && ss - b0s + 1u <= kStreamMaxSeg) fits++;
                         xr -= c_r; xf -= c_f;
                     }
@@ -753,8 +748,8 @@ __global__ __launch_bounds__(kPlanT, 3) void k_plan(const StreamArgs a)
                         uint32_t c_r, c_f;
                         contrib(tm[k], c_r, c_f);
                         const uint32_t u = kStreamTile - 1u - ((uint32_t)lane * KI + k);
-                        if (u == u1 - 1u) { tmp[0] = xr & 0xfffffu; tmp[1] = xf; tmp[2] = xr >> 20; }
-                        if (u == u0) tmp[3] = ((tm[k] >> 20) & 1u) && !((tm[k] >> 18) & 1u) ? 1u : 0u;
+                        if (u == u1 - 1u) { tmp[0] = xr & kSumFloatsMask; tmp[1] = xf; tmp[2] = xr >> kSumRunShift; }
+                        if (u == u0) tmp[3] = ((tm[k] >> kItemTile) & 1u) && !((tm[k] >> kItemRunStart) & 1u) ? 1u : 0u;
                         xr -= c_r; xf -= c_f;
                     }
                 }
@@ -783,12 +778,12 @@ __global__ __launch_bounds__(kPlanT, 3) void k_plan(const StreamArgs a)
                     uint32_t c_r, c_f;
                     contrib(tm[k], c_r, c_f);
                     const uint32_t u = kStreamTile - 1u - ((uint32_t)lane * KI + k);
-                    const uint32_t sr = xr & 0xfffffu, sf = xf, ss = xr >> 20;
+                    const uint32_t sr = xr & kSumFloatsMask, sf = xf, ss = xr >> kSumRunShift;
                     xr -= c_r; xf -= c_f;
-                    if (!((tm[k] >> 20) & 1u) || u < u0 || u >= u1) continue;
-                    const uint32_t N = tm[k] & 127u, R = (tm[k] >> 14) & 3u;
-                    const bool starts = ((tm[k] >> 18) & 1u) || u == u0, ends = ((tm[k] >> 19) & 1u) || u == u1 - 1u;
-                    atomicAdd(&hist[(3u - R) * 64u + (63u - min(N, 63u))], 1u);
+                    if (!((tm[k] >> kItemTile) & 1u) || u < u0 || u >= u1) continue;
+                    const uint32_t N = rec_n(tm[k]), R = rec_radius(tm[k]);
+                    const bool starts = ((tm[k] >> kItemRunStart) & 1u) || u == u0, ends = ((tm[k] >> kItemRunEnd) & 1u) || u == u1 - 1u;
+                    atomicAdd(&hist[sort_bin(R, N)], 1u);
                     const uint32_t adj = (cut_run && u > u0) ? 1u : 0u;
                     const uint32_t g = ss - b0s + (cut_run ? 1u : 0u) - 1u; // the item's run in this pass
                     if (starts) {
@@ -797,7 +792,7 @@ __global__ __launch_bounds__(kPlanT, 3) void k_plan(const StreamArgs a)
                         // position -- in the entry's words; lane g makes the entry of it below, once for all runs (here the
                         // chain's bases would be fetched in eight divergent rounds, one per item of a lane)
                         const rawdtw_anchor_t sa = an[k + 1];
-                        rt.lo[0][g] = sr - (c_r & 0xfffffu) - b0r + 4u * adj; rt.lo[1][g] = sf - c_f - b0f + 4u * adj;
+                        rt.lo[0][g] = sr - (c_r & kSumFloatsMask) - b0r + 4u * adj; rt.lo[1][g] = sf - c_f - b0f + 4u * adj;
                         rt.D[0][g] = (int32_t)sa.query_position; rt.D[1][g] = (int32_t)sa.target_position;
                         rt.src[0][g] = (long long)((uint32_t)lane * KI + k);
                     }
@@ -824,25 +819,25 @@ __global__ __launch_bounds__(kPlanT, 3) void k_plan(const StreamArgs a)
             const uint32_t hsum = h0 + h1 + h2, hincl = wave_scan_incl(hsum);
             const uint32_t n_jobs = (uint32_t)__builtin_amdgcn_readlane((int)hincl, 63);
             hist[3 * lane] = hincl - hsum; hist[3 * lane + 1] = hincl - hsum + h0; hist[3 * lane + 2] = hincl - hsum + h0 + h1;
-            // the pass's first radius-1 record = the first place of bin 128 (lane 42's third bin): the chunks of k_runs do not cross it
-            static_assert(kSortBins == 192 && 128 == 3 * 42 + 2, "bin 128 is lane 42's third");
-            const uint32_t n_hi = (uint32_t)__builtin_amdgcn_readlane((int)(hincl - hsum + h0 + h1), 42);
+            // the pass's first radius-1 record = the first place of bin kSortBinRadius1 (lane 42's third bin): the chunks of k_runs do not cross it
+            static_assert(kSortBins == 3 * 64 && kSortBinRadius1 % 3 == 2, "three bins a lane; the first radius-1 bin is a lane's third");
+            const uint32_t n_hi = (uint32_t)__builtin_amdgcn_readlane((int)(hincl - hsum + h0 + h1), kSortBinRadius1 / 3);
             wave_lds_sync();
             // the records, in the order the lanes of the DTW launch take them (a bin's jobs in any order: they are alike)
             {
-                uint32_t xs = base_r >> 20;
+                uint32_t xs = base_r >> kSumRunShift;
 #pragma unroll
                 for (int k = 0; k < KI; k++) {
                     const uint32_t u = kStreamTile - 1u - ((uint32_t)lane * KI + k), ss = xs;
-                    xs -= (tm[k] >> 18) & (tm[k] >> 20) & 1u; // (a run start counts once)
-                    if (!((tm[k] >> 20) & 1u) || u < u0 || u >= u1) continue;
-                    const uint32_t N = tm[k] & 127u, R = (tm[k] >> 14) & 3u;
-                    const uint32_t place = atomicAdd(&hist[(3u - R) * 64u + (63u - min(N, 63u))], 1u);
+                    xs -= (tm[k] >> kItemRunStart) & (tm[k] >> kItemTile) & 1u; // (a run start counts once)
+                    if (!((tm[k] >> kItemTile) & 1u) || u < u0 || u >= u1) continue;
+                    const uint32_t N = rec_n(tm[k]), R = rec_radius(tm[k]);
+                    const uint32_t place = atomicAdd(&hist[sort_bin(R, N)], 1u);
                     const uint32_t g = ss - b0s + (cut_run ? 1u : 0u) - 1u;
                     const rawdtw_anchor_t sa = an[k + 1];
                     const uint32_t p_r = sa.query_position + (uint32_t)rt.D[0][g], p_f = sa.target_position + (uint32_t)rt.D[1][g];
-                    const bool swap = (tm[k] >> 17) & 1u;
-                    a.recs[(uint64_t)tile * kStreamRecStride + rec_off + place] = make_uint2((swap ? p_f : p_r) | ((swap ? p_r : p_f) << 16), (tm[k] & 0x1ffffu) | (u << 17));
+                    const bool swap = (tm[k] >> kItemSwapped) & 1u;
+                    a.recs[(uint64_t)tile * kStreamRecStride + rec_off + place] = make_uint2(rec_windows(swap ? p_f : p_r, swap ? p_r : p_f), rec_with_item(tm[k], u));
                 }
             }
             // the copy orders: a run's range of 16-byte pieces, per arena
@@ -850,10 +845,10 @@ __global__ __launch_bounds__(kPlanT, 3) void k_plan(const StreamArgs a)
                 const uint32_t g = (uint32_t)lane >> 1, w = (uint32_t)lane & 1u;
                 const long long src = rt.src[w][g];
                 a.runtab[(uint64_t)slot * (2u * kStreamMaxSeg) + lane] =
-                    make_uint4(rt.lo[w][g] >> 2, (rt.end[w][g] + (uint32_t)rt.D[w][g] + 3u) >> 2, (uint32_t)(unsigned long long)src, (uint32_t)((unsigned long long)src >> 32));
+                    make_uint4(rt.lo[w][g] >> 2, (rt.end[w][g] + (uint32_t)rt.D[w][g] + 3u) >> 2, order_src_lo(src), order_src_hi(src));
             }
             wave_lds_sync(); // (the run table and the bins are read: the next pass writes them again)
-            if (lane == 0) a.todo[slot] = make_uint4(tile, slot, n_jobs | (n_runs << 16) | (n_hi << 22), region | (rec_off << 16)); // (a pass's list entry sits at its slot)
+            if (lane == 0) a.todo[slot] = make_uint4(tile, slot, pass_counts(n_jobs, n_runs, n_hi), pass_place(region, rec_off)); // (a pass's list entry sits at its slot)
             if (last) break;
             rec_off += (n_jobs + 1u) & ~1u; // (passes start on 16-byte boundaries)
             if (rec_off + (kStreamTile - u1) > kStreamRecStride) { if (lane == 0) atomicMin(&a.cnt[kCntOverflow], (unsigned long long)tile); break; } // (> 64 passes)
@@ -1092,14 +1087,14 @@ __global__ __launch_bounds__(TT, 4) void k_runs(const StreamArgs a, const uint32
     // a pass's records (all waves: two records a piece): asked for with the pass's image and landed with it -- the lanes read
     // them behind B1 only, so they need no buffer of their own a pass ahead (4 KB of LDS a workgroup: a fifth workgroup a CU)
     auto fetch_recs = [&](const uint4 e) {
-        const uint32_t n_jobs = e.z & 0xffffu, pieces = (n_jobs + 1u) >> 1;
-        const uint2 *src = a.recs + (uint64_t)e.x * kStreamRecStride + (e.w >> 16);
+        const uint32_t n_jobs = pass_jobs(e.z), pieces = (n_jobs + 1u) >> 1;
+        const uint2 *src = a.recs + (uint64_t)e.x * kStreamRecStride + pass_rec0(e.w);
         for (uint32_t q0 = wv * 64u; q0 < pieces; q0 += (uint32_t)TT)
             if (q0 + (uint32_t)lane < pieces) dma16(src + 2u * (q0 + (uint32_t)lane), rec + 2u * q0);
     };
     // ... and its copy orders, which the staging itself reads: a pass ahead, into buffer `buf` (one wave)
     auto fetch_orders = [&](const uint4 e, const uint32_t buf) {
-        const uint32_t n_ord = 2u * ((e.z >> 16) & 63u);
+        const uint32_t n_ord = 2u * pass_runs(e.z);
         if ((uint32_t)lane < n_ord) dma16(a.runtab + (uint64_t)e.y * kRT + lane, rtab + buf * kRT);
     };
 
@@ -1172,8 +1167,8 @@ __global__ __launch_bounds__(TT, 4) void k_runs(const StreamArgs a, const uint32
         // from a chunk boundary of their own, those of radius 1 -- the entry says where they start.
         uint32_t n3;
         {
-            const uint2 r0 = rc_base[min((uint32_t)lane, n_jobs - 1u)];
-            n3 = (uint32_t)__popcll(__ballot((uint32_t)lane < n_jobs && ((r0.y >> 14) & 3u) == 3u));
+            const uint32_t R0 = rec_radius(rc_base[min((uint32_t)lane, n_jobs - 1u)].y); // (read ahead of the && below: behind it the accessor's read is branched around)
+            n3 = (uint32_t)__popcll(__ballot((uint32_t)lane < n_jobs && R0 == 3u));
         }
         const uint32_t n_hi = min(max(n_hi_e, n3), n_jobs); // (the planner's value lies there: no record index leaves the pass whatever the entry says)
         const uint32_t n_chunks = chunk_map_count(n3, n_hi, n_jobs);
@@ -1188,19 +1183,19 @@ __global__ __launch_bounds__(TT, 4) void k_runs(const StreamArgs a, const uint32
                 const uint32_t r = cr.first + ((uint32_t)lane >> 2);
                 const bool act = r < cr.end;
                 const uint2 rc = rc_base[act ? r : cr.end - 1u];
-                const uint32_t N = rc.y & 127u, M = (rc.y >> 7) & 127u, u = (rc.y >> 17) & (kStreamTile - 1u);
-                const float *LA = win + (rc.x & 0xffffu), *LB = win + (rc.x >> 16);
+                const uint32_t N = rec_n(rc.y), M = rec_m(rc.y), u = rec_item(rc.y);
+                const float *LA = win + rec_long(rc.x), *LB = win + rec_short(rc.x);
                 float res = quad_dp_r3(LA, LB, N, M, lane, wave_max_u32(N));
                 if (act && ((lane & 3) == 2)) {
-                    if ((rc.y >> 16) & 1u) res = res - dist(LA[N - 1], LB[M - 1]);
+                    if (rec_excl(rc.y)) res = res - dist(LA[N - 1], LB[M - 1]);
                     a.out[end_nom - 1u - u] = res;
                 }
             } else {
                 const uint32_t r = cr.first + (uint32_t)lane;
                 const bool act = r < cr.end;
                 const uint2 rc = rc_base[act ? r : cr.end - 1u];
-                const uint32_t N = rc.y & 127u, M = (rc.y >> 7) & 127u, R = (rc.y >> 14) & 3u, u = (rc.y >> 17) & (kStreamTile - 1u);
-                const float res = stream_lane_job(win + (rc.x & 0xffffu), win + (rc.x >> 16), N, M, R, (rc.y >> 16) & 1u, act);
+                const uint32_t N = rec_n(rc.y), M = rec_m(rc.y), R = rec_radius(rc.y), u = rec_item(rc.y);
+                const float res = stream_lane_job(win + rec_long(rc.x), win + rec_short(rc.x), N, M, R, rec_excl(rc.y), act);
                 if (act) a.out[end_nom - 1u - u] = res; // the part that ends at anchor (tile end - 1 - u)
                 if (stamps) { // (diagnostic: the lane chunks this wave ran, and those among them whose lanes held more than one radius)
                     const bool mixed = __ballot(R != (uint32_t)__builtin_amdgcn_readfirstlane((int)R)) != 0ull;
@@ -1216,7 +1211,7 @@ __global__ __launch_bounds__(TT, 4) void k_runs(const StreamArgs a, const uint32
     for (;;) {
         const uint4 e = s_ent[cur];
         if (e.x == 0xffffffffu) break;
-        const uint32_t n_jobs = e.z & 0xffffu, n_ord = 2u * ((e.z >> 16) & 63u), n_hi = e.z >> 22;
+        const uint32_t n_jobs = pass_jobs(e.z), n_ord = 2u * pass_runs(e.z), n_hi = pass_n_hi(e.z);
         // thread 0: the next pass's entry is published before this pass's first barrier; the pass after that gets its list
         // index (the ticket drawn a pass ago) and wave 0 asks for its entry; the ticket of the pass after THAT is drawn
         uint32_t i2 = 0xffffffffu;
@@ -1252,8 +1247,7 @@ __global__ __launch_bounds__(TT, 4) void k_runs(const StreamArgs a, const uint32
             const uint4 o_all = (uint32_t)lane < n_ord ? rtab[cur * kRT + lane] : make_uint4(0u, 0u, 0u, 0u);
             for (uint32_t it = wv; it < n_ord; it += kWaves) {
                 const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)o_all.x, (int)it), hi = (uint32_t)__builtin_amdgcn_readlane((int)o_all.y, (int)it);
-                const long long off = (long long)((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)o_all.z, (int)it) |
-                                                  ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)o_all.w, (int)it) << 32));
+                const long long off = order_src((uint32_t)__builtin_amdgcn_readlane((int)o_all.z, (int)it), (uint32_t)__builtin_amdgcn_readlane((int)o_all.w, (int)it));
                 const float4 *src = reinterpret_cast<const float4 *>(((it & 1u) ? a.ref : a.ev) + off);
                 for (uint32_t q0 = lo; q0 < hi; q0 += 64u)
                     if (q0 + (uint32_t)lane < hi) dma16(src + q0 + lane, win + 4u * q0);

@@ -6,7 +6,7 @@ for bit, and the plan's self-check (which also checks the entry's new field).
 
 What proves what: the results are bit-identical under ANY chunk map, so the oracle comparison shows that the kernel scores
 every record once and correctly, not which map it walks.  The chunk counts asserted from chunk_profile() are counted on the
-host from the plan (the entry's n_hi, through the same rawdtw_chunks.h): they pin the planner's field and the case's
+host from the plan (rawdtw_plan_check.cpp: the entry's n_hi, through the same rawdtw_chunks.h): they pin the planner's field and the case's
 composition.  That the KERNEL walks the map is shown by the diagnostic instance's own counters ("stream_debug" 256: the
 lane chunks its waves ran and those whose lanes held more than one radius, counted in run_dp from the lanes' records):
 test_mixed_wave_is_taken_apart[debug256] and test_kernel_counts_its_chunks.
