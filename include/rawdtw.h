@@ -911,6 +911,65 @@ int rawdtw_mapper_round_seeded_resident(rawdtw_mapper *m, const rawdtw_seed_inde
 int rawdtw_mapper_resident_stats(const rawdtw_mapper *m, uint64_t *resident_rounds, uint64_t *fallback_rounds,
                                  uint64_t *hit_bytes_to_host, uint64_t *seed_bytes_to_device);
 
+/* ---- a chunk round from signal: the events never leave the device.  A caller of rawdtw_mapper_round_seeded_resident still brings every
+ * event home from the detection and sends it up again; the entries below run detection, seeding and chaining one behind the other on the
+ * context's stream, and what comes home is 4 bytes a chunk (its event count) and the hit offsets.
+ *   rawdtw_detect_resident_begin / rawdtw_detect_raw_resident_begin  rawdtw_detect_begin / rawdtw_detect_raw_begin with the events'
+ *       destination in the context's event arena (the library's own after rawdtw_events_reserve, or the caller's after
+ *       rawdtw_set_events_device): chunk k's normalised events go to the arena at dst_start[k] .., at most room[k] of them.  The write is
+ *       all or nothing and decided on the device before a single event is written: when any chunk has more events than its room, or the
+ *       total is above events_cap, nothing is written anywhere and _end returns RAWDTW_ERR_RANGE (its message says which).  Refused before
+ *       anything is enqueued: RAWDTW_ERR_INVALID for a null argument, no arena on the context, a detection of any kind already begun, and
+ *       the plain entries' rules on offsets and window lengths -- except that an EMPTY window is allowed in both (ev_len 0, nothing
+ *       written; so is an all-outlier raw window); RAWDTW_ERR_RANGE for dst_start[k] + room[k] beyond the arena.  One detection at a time
+ *       a context, of any of the four kinds.
+ *   rawdtw_detect_resident_end  waits for the detection's own work and fills ev_len (n_chunks counts), *total and, when s_len is not NULL,
+ *       the samples a chunk kept (the window's length for the pA entry); also when it returns RAWDTW_ERR_RANGE.  No event comes home.  The
+ *       dense offsets and the counts stay in the detection's workspace.  rawdtw_detect_end does not end a resident detection, nor this a
+ *       plain one (RAWDTW_ERR_INVALID, the detection stays begun).
+ *   rawdtw_seed_detected_begin  valid while a resident detection is begun and not ended on the context: rawdtw_seed_resident_begin on
+ *       that detection's chunks, enqueued directly behind it with no host step between -- the offsets and the places are the detection's,
+ *       on the device; the workspace is sized by the detection's events_cap (24 bytes an event, 32 with w > 0), for no count has come home.
+ *       The rules are rawdtw_seed_resident_begin's.  rawdtw_seed_resident_end ends it (in either order with rawdtw_detect_resident_end):
+ *       RAWDTW_ERR_RANGE when the detection declined -- every launch of the seeding then did nothing, and hit_off is not to be used --,
+ *       RAWDTW_ERR_UNSUPPORTED for the minimizer overflow as before; rawdtw_seed_resident_fetch and rawdtw_chain_round_begin_resident
+ *       work on the retained hits unchanged.
+ *   rawdtw_mapper_round_signal_resident / rawdtw_mapper_round_raw_resident  one chunk round from the signal itself: window k (pA samples
+ *       sig[sig_off[k] .. sig_off[k+1]), or int16 samples raw[raw_off[k] .. raw_off[k+1]) with channel chan[k], cut with
+ *       rawdtw_signal_chunk_table) is read read_ids[k]'s next chunk; ev_opt NULL = the defaults.  The chunk's events are detected into the
+ *       read's slot behind its committed events, seeded there, and the round goes on as rawdtw_mapper_round_seeded_resident's from the hit
+ *       counts on (a round the device chaining declines fetches the hits -- not the events -- and is chained on the host: same lines).
+ *       One upload (the samples), one launch sequence and one wait in front of the chaining.  Preconditions: those of
+ *       rawdtw_mapper_round_seeded_resident, and nothing may read the host's copy of a read's events later -- no --dtw-output-cigar
+ *       (flag 0x4; rawdtw_mapper_finish uploads that copy) and no external scorer, neither then nor afterwards (rawdtw_mapper_set_scorer is
+ *       refused once such a round has run); a mapper with no DTW stage is served.  Anything else: RAWDTW_ERR_UNSUPPORTED with nothing
+ *       changed (rawdtw_detect_raw_begin + rawdtw_mapper_round_seeded_resident map the round).  events_cap is the mapper's guess -- what
+ *       the seeding's workspace holds already, or a quarter of the round's samples + 1 024 --, and a round with more events runs once more
+ *       with the total the device reported.  A chunk that does not fit its read's slot: RAWDTW_ERR_RANGE, "a read outgrew its slot in the
+ *       event arena".  A failed round leaves reads and mapper as they were; what the device wrote above a read's committed events is
+ *       scratch and overwritten by the next attempt.
+ *   rawdtw_set_option(ctx, "signal_events_cap", N)  N > 0: the first try's events_cap of the mapper's rounds from signal on this context
+ *       (tests of the retry); 0, the default: the guess.  rawdtw_get_option reads it back.
+ *   rawdtw_mapper_signal_stats  rounds from signal that were committed, how many of them ran twice, bytes of samples sent up (both tries
+ *       of a retried round), and the bytes of events that crossed PCIe in either direction over all of the mapper's rounds (what
+ *       rawdtw_mapper_timing's slot 6 counts: 0 for a mapper that only ran rounds from signal).  Any pointer may be NULL. ---- */
+int rawdtw_detect_resident_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint32_t n_chunks, const uint64_t *sig_off,
+                                 const float *sig, const uint64_t *dst_start /* n_chunks */, const uint32_t *room /* n_chunks */,
+                                 uint64_t events_cap);
+int rawdtw_detect_raw_resident_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint32_t n_chunks, const uint64_t *raw_off,
+                                     const int16_t *raw, const rawdtw_channel_t *chan /* n_chunks */,
+                                     const uint64_t *dst_start /* n_chunks */, const uint32_t *room /* n_chunks */, uint64_t events_cap);
+int rawdtw_detect_resident_end(rawdtw_ctx *ctx, uint32_t *s_len /* n_chunks, may be NULL */, uint32_t *ev_len /* n_chunks */,
+                               uint64_t *total, float *kernel_ms /* may be NULL */);
+int rawdtw_seed_detected_begin(rawdtw_ctx *ctx, uint64_t *hit_off /* n_chunks+1 */);
+int rawdtw_mapper_round_signal_resident(rawdtw_mapper *m, const rawdtw_seed_index *six, const rawdtw_event_opt_t *ev_opt,
+                                        uint32_t n_reads, const uint32_t *read_ids, const uint64_t *sig_off, const float *sig);
+int rawdtw_mapper_round_raw_resident(rawdtw_mapper *m, const rawdtw_seed_index *six, const rawdtw_event_opt_t *ev_opt, uint32_t n_reads,
+                                     const uint32_t *read_ids, const uint64_t *raw_off, const int16_t *raw,
+                                     const rawdtw_channel_t *chan /* n_reads */);
+int rawdtw_mapper_signal_stats(const rawdtw_mapper *m, uint64_t *rounds, uint64_t *retried_rounds, uint64_t *sample_bytes_to_device,
+                               uint64_t *event_bytes_crossed);
+
 #ifdef __cplusplus
 }
 #endif

@@ -273,6 +273,13 @@ SYMBOLS = {
     "rawdtw_mapper_resident_stats": (I32, [VP, VP, VP, VP, VP]),
     "rawdtw_chain_round_stats": (I32, [VP, VP, VP, VP, VP]),
     "rawdtw_get_option": (I32, [VP, C.c_char_p, C.POINTER(C.c_int64)]),
+    "rawdtw_detect_resident_begin": (I32, [VP, C.POINTER(EventOpt), U32, VP, VP, VP, VP, U64]),
+    "rawdtw_detect_raw_resident_begin": (I32, [VP, C.POINTER(EventOpt), U32, VP, VP, VP, VP, VP, U64]),
+    "rawdtw_detect_resident_end": (I32, [VP, VP, VP, C.POINTER(U64), C.POINTER(F32)]),
+    "rawdtw_seed_detected_begin": (I32, [VP, VP]),
+    "rawdtw_mapper_round_signal_resident": (I32, [VP, VP, C.POINTER(EventOpt), U32, VP, VP, VP]),
+    "rawdtw_mapper_round_raw_resident": (I32, [VP, VP, C.POINTER(EventOpt), U32, VP, VP, VP, VP]),
+    "rawdtw_mapper_signal_stats": (I32, [VP, VP, VP, VP, VP]),
 }
 
 

@@ -151,6 +151,7 @@ struct rawdtw_ctx {
     uint32_t chain_max_seeds = 0; // tests: RAWDTW_CHAIN_MAX_SEEDS lowers rawdtw_chain_round's cap on seeds a read, so that small rounds take the declined path (0: no)
     uint32_t chain_long_seeds = 0; // "chain_long_seeds": reads above the cap with at most this many seeds are chained by rawdtw_chain.hip's long path (0: declined)
     bool seed_minimizer = false;   // "seed_minimizer": rawdtw_seed.hip seeds a w > 0 table on the device (k_seed_min) rather than refusing it
+    uint64_t signal_events_cap = 0; // "signal_events_cap": the events_cap of a round from signal's first try (rawdtw_mapper.cpp; 0: the mapper's guess)
     std::string err;
 };
 
@@ -281,6 +282,18 @@ inline int hip_fail(rawdtw_ctx *ctx, hipError_t e, const char *what)
 void chain_ws_free(rawdtw_ctx *ctx); // rawdtw_chain.hip
 void detect_ws_free(rawdtw_ctx *ctx); // rawdtw_events.hip
 void seed_ws_free(rawdtw_ctx *ctx);   // rawdtw_seed.hip
+// A resident detection begun on the context and not ended (rawdtw_events.hip), as rawdtw_seed_detected_begin reads it: everything the
+// seeding needs is in the detection's workspace on the device.  `enqueued` false: no launch went out (no chunk, or no sample).
+struct DetectView {
+    bool enqueued = false;
+    uint32_t n = 0;                  // chunks
+    uint64_t cap = 0;                // the detection's events_cap: the total of events is at most this, or the flag is set
+    uint64_t n_samples = 0;          // the samples that went up (a chunk never has more events than samples)
+    const uint64_t *d_eoff = nullptr; // n + 1 dense event offsets
+    const uint64_t *d_dst = nullptr;  // per chunk: where its events start in the context's event arena
+    const uint64_t *d_flag = nullptr; // [0] != 0: the detection declined (a chunk over its room, or the total over the cap) and wrote nothing
+};
+bool detect_resident_view(const rawdtw_ctx *ctx, DetectView *v);
 // the context's ended resident seeding (rawdtw_seed.hip) as rawdtw_chain_round_begin_resident uses it: its hit offsets on the host
 // (null: there is none), and the launch that lays reads' previous anchors and hits down as the chaining's seed list, on the context's stream
 const uint64_t *seed_resident_hit_off(const rawdtw_ctx *ctx, uint64_t *n_chunks);

@@ -20,6 +20,10 @@
 //                 out lane by lane (coalesced) at the chunk's offset
 // after which EvArgs.off means what it always means; k_ev_tstat, which takes the sample total from the host, reads it from device
 // memory instead (EvArgs.n_dev) under a grid sized by the raw total.
+// A RESIDENT detection (rawdtw_detect_resident_begin / _raw_resident_begin) runs the same launches and writes chunk k's normalised
+// events into the context's event arena at dst_start[k] instead, where the seeding and the DTW read them: no event goes home.
+//   k_ev_room     one workgroup behind k_ev_scan: a chunk with more events than its room, or a total above events_cap, raises the
+//                 flag word; k_ev_events<true> then writes nothing anywhere (all or nothing, decided before the first store)
 // A batch lasts as long as its longest chunk's serial chain: ~4 000 steps for the mapper's chunks; a whole read passed as one
 // chunk works but costs its full length.
 //
@@ -53,6 +57,8 @@ struct EvArgs {
     uint32_t n;
     uint64_t n_samples;
     const uint64_t *n_dev; // the raw entry: the kept samples' total, known to the device alone (n_samples then bounds it)
+    const uint64_t *dst;   // a resident detection: per chunk, where its events go in the event arena; else null
+    const uint64_t *flag;  // ... and its flag word (k_ev_room); else null
     rawdtw_event_opt_t opt;
 };
 
@@ -263,13 +269,26 @@ __global__ __launch_bounds__(1024) void k_ev_scan(const uint32_t *nev, uint32_t 
     }
 }
 
+// A resident detection's go or no-go, before a single event is written: bit 0 a chunk has more events than its room in the arena,
+// bit 1 the round's total is above the caller's events_cap.
+__global__ __launch_bounds__(1024) void k_ev_room(const uint32_t *nev, const uint32_t *room, uint32_t n, const uint64_t *tot, uint64_t cap, uint64_t *flag)
+{
+    int over = 0;
+    for (uint32_t k = threadIdx.x; k < n; k += 1024) over |= nev[k] > room[k] ? 1 : 0;
+    over = __syncthreads_or(over);
+    if (threadIdx.x == 0) flag[0] = (over ? 1u : 0u) | (tot[0] > cap ? 2u : 0u);
+}
+
 // revent.c:140-188.  Nothing is written unless the whole round's events fit below `bound` (the caller's events_cap, and the
-// device array's size).
-__global__ __launch_bounds__(64) void k_ev_events(EvArgs a, uint64_t bound, float *out)
+// device array's size).  kArena (a resident detection): nothing is written either when k_ev_room raised the flag, and the
+// normalised events go to out + a.dst[k] (the event arena; the host checked dst + room against its size, k_ev_room the count
+// against the room); the raw means still go to the workspace.
+template <bool kArena> __global__ __launch_bounds__(64) void k_ev_events(EvArgs a, uint64_t bound, float *out)
 {
     __shared__ double stat[2];
     __shared__ float se[kEvLds]; // the chunk's events for the serial sums, when they fit
     if (a.tot[0] > bound) return;
+    if (kArena && a.flag[0]) return;
     const uint32_t k = blockIdx.x, lane = threadIdx.x, nev = a.nev[k];
     if (!nev) return;
     const uint64_t b = a.off[k], eo = a.eoff[k];
@@ -299,7 +318,7 @@ __global__ __launch_bounds__(64) void k_ev_events(EvArgs a, uint64_t bound, floa
     }
     __syncthreads();
     const double mean = stat[0], sd = stat[1];
-    float *dst = (out ? out : a.ev) + eo;
+    float *dst = kArena ? out + a.dst[k] : (out ? out : a.ev) + eo;
     for (uint32_t p = lane; p < nev; p += kW) dst[p] = (float)(((double)ev[p] - mean) / sd);
 }
 
@@ -410,6 +429,11 @@ struct DetectWs {
     bool direct_slen = false;
     uint32_t *h_slen = nullptr;
     const uint32_t *d_slen = nullptr;
+    // a resident detection: what comes home lands in `pin` (the counts, and the raw entry's s_len); what the seeding reads stays here
+    bool arena = false, enqueued = false, raw = false;
+    const uint64_t *h_off = nullptr;  // (pin) the rebased offsets
+    const uint32_t *h_nev = nullptr, *h_cnt = nullptr;
+    const uint64_t *d_dst = nullptr, *d_flag = nullptr;
 };
 
 // what a detection reads: pA chunks (sig), or raw windows with a channel each
@@ -418,6 +442,9 @@ struct Input {
     const int16_t *raw = nullptr;
     const rawdtw_channel_t *chan = nullptr;
     uint32_t *s_len = nullptr;
+    // a resident detection: the chunks' places and room in the context's event arena
+    const uint64_t *dst_start = nullptr;
+    const uint32_t *room = nullptr;
 };
 
 // the device address of a page-locked host array of `bytes` bytes, or null (pageable memory, or an allocation that does not
@@ -456,7 +483,7 @@ int detect_enqueue(rawdtw_ctx *ctx, const rawdtw_event_opt_t &o, uint32_t n_chun
 {
     if (n_chunks >= 0x7fffffffu) return fail(ctx, RAWDTW_ERR_INVALID, "2^31 chunks or more");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const bool is_raw = in.raw != nullptr;
+    const bool is_raw = in.raw != nullptr, arena = in.dst_start != nullptr;
     const uint64_t n = n_chunks, N = off[n] - off[0];
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t b_off = al((n + 1) * 8), b_sig = al(N * 4), b_ps = al((N + n) * 4), b_t = al(N * 4), b_cnt = al(n * 4), b_eoff = al((n + 1) * 8),
@@ -465,8 +492,9 @@ int detect_enqueue(rawdtw_ctx *ctx, const rawdtw_event_opt_t &o, uint32_t n_chun
     // the channels, s_len
     const size_t b_raw = is_raw ? al(N * 2 + 16) : 0, b_roff = is_raw ? b_off : 0, b_chan = is_raw ? al(n * sizeof(rawdtw_channel_t)) : 0,
                  b_slen = is_raw ? b_cnt : 0;
+    const size_t b_dst = arena ? b_off : 0, b_room = arena ? b_cnt : 0; // a resident detection's own: the places and the room
     // sig, ps, pss, t1, t2, peaks, events: 28 bytes a sample (30 a raw sample)
-    const size_t need = b_off + b_sig + 2 * b_ps + 2 * b_t + b_t + 2 * b_cnt + b_eoff + b_tot + b_t + b_raw + b_roff + b_chan + b_slen;
+    const size_t need = b_off + b_sig + 2 * b_ps + 2 * b_t + b_t + 2 * b_cnt + b_eoff + b_tot + b_t + b_raw + b_roff + b_chan + b_slen + b_dst + b_room;
     if (!ctx->detect_ws) ctx->detect_ws = new (std::nothrow) rawdtw_detect_ws;
     if (!ctx->detect_ws) return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed");
     DetectWs &w = ctx->detect_ws->w;
@@ -477,7 +505,8 @@ int detect_enqueue(rawdtw_ctx *ctx, const rawdtw_event_opt_t &o, uint32_t n_chun
         if (hipMalloc(&w.dev, want) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, RAWDTW_ERR_OOM, "detection workspace allocation failed"); }
         w.dev_bytes = want;
     }
-    const size_t pin_need = (n + 2) * 8;
+    // (a resident detection: behind the offsets the places and the room going up, the counts and s_len coming home)
+    const size_t pin_need = arena ? (4 * n + 4) * 8 : (n + 2) * 8;
     if (w.pin_bytes < pin_need) {
         if (w.pin) (void)hipHostFree(w.pin);
         w.pin = nullptr; w.pin_bytes = 0;
@@ -494,6 +523,21 @@ int detect_enqueue(rawdtw_ctx *ctx, const rawdtw_event_opt_t &o, uint32_t n_chun
     w.pending = true; w.n = n_chunks; w.n_samples = N; w.cap = events_cap;
     w.h_eoff = event_off; w.h_ev = events; w.h_slen = in.s_len;
     w.direct_off = w.direct_ev = w.direct_slen = false;
+    w.arena = arena; w.enqueued = false; w.raw = is_raw;
+    uint64_t *const h_off = w.pin + (arena ? 2 : 1);
+    uint64_t *const h_dst = h_off + (n + 1);
+    uint32_t *const h_room = reinterpret_cast<uint32_t *>(h_dst + n), *const h_nev = h_room + n, *const h_cnt = h_nev + n;
+    for (uint64_t k = 0; k <= n; k++) h_off[k] = off[k] - off[0];
+    if (arena) { // the tables are checked in the very copy that goes up
+        w.h_off = h_off; w.h_nev = h_nev; w.h_cnt = h_cnt;
+        for (uint64_t k = 0; k < n; k++) {
+            h_dst[k] = in.dst_start[k]; h_room[k] = in.room[k];
+            if (h_dst[k] > ctx->n_ev || ctx->n_ev - h_dst[k] < h_room[k]) {
+                w.pending = false;
+                return fail(ctx, RAWDTW_ERR_RANGE, "a chunk's stretch (dst_start + room) is beyond the context's event arena");
+            }
+        }
+    }
     if (n == 0 || N == 0) return RAWDTW_OK; // (N == 0: every raw window is empty; rawdtw_detect_end fills the zeros)
     char *p = static_cast<char *>(w.dev);
     EvArgs a{};
@@ -513,21 +557,25 @@ int detect_enqueue(rawdtw_ctx *ctx, const rawdtw_event_opt_t &o, uint32_t n_chun
     int16_t *d_raw = reinterpret_cast<int16_t *>(p); p += b_raw;
     uint64_t *d_roff = reinterpret_cast<uint64_t *>(p); p += b_roff;
     rawdtw_channel_t *d_chan = reinterpret_cast<rawdtw_channel_t *>(p); p += b_chan;
-    r.cnt = reinterpret_cast<uint32_t *>(p);
+    r.cnt = reinterpret_cast<uint32_t *>(p); p += b_slen;
+    uint64_t *d_dst = reinterpret_cast<uint64_t *>(p); p += b_dst;
+    uint32_t *d_room = reinterpret_cast<uint32_t *>(p);
+    if (arena) { a.dst = d_dst; a.flag = a.tot + 2; w.d_dst = d_dst; w.d_flag = a.tot + 2; }
     a.off = d_off; a.sig = d_sig; a.n = n_chunks; a.n_samples = N; a.opt = o;
     a.n_dev = is_raw ? a.tot + 1 : nullptr;
-    uint64_t *h_off = w.pin + 1;
-    for (uint64_t k = 0; k <= n; k++) h_off[k] = off[k] - off[0];
-    uint64_t *dv_eoff = static_cast<uint64_t *>(device_view(event_off, (n + 1) * 8));
-    float *dv_ev = static_cast<float *>(device_view(events, events_cap * 4));
+    uint64_t *dv_eoff = arena ? nullptr : static_cast<uint64_t *>(device_view(event_off, (n + 1) * 8));
+    float *dv_ev = arena ? nullptr : static_cast<float *>(device_view(events, events_cap * 4));
     w.direct_off = dv_eoff != nullptr; w.direct_ev = dv_ev != nullptr;
     w.d_eoff = a.eoff; w.d_ev = a.ev;
     hipStream_t s = ctx->stream;
     auto undo = [&](int st) { w.pending = false; return st; };
+    if (arena && (hipMemcpyAsync(d_dst, h_dst, n * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+                  hipMemcpyAsync(d_room, h_room, n * 4, hipMemcpyHostToDevice, s) != hipSuccess))
+        return undo(hip_fail(ctx, hipGetLastError(), "detection upload"));
     const uint32_t waves = (uint32_t)((n + kW - 1) / kW);
     if (is_raw) {
         r.roff = d_roff; r.raw = d_raw; r.chan = d_chan; r.off = d_off; r.sig = d_sig;
-        r.h_cnt = static_cast<uint32_t *>(device_view(in.s_len, n * 4));
+        r.h_cnt = arena ? nullptr : static_cast<uint32_t *>(device_view(in.s_len, n * 4));
         w.direct_slen = r.h_cnt != nullptr; w.d_slen = r.cnt;
         if (hipMemcpyAsync(d_roff, h_off, (n + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
             hipMemcpyAsync(d_chan, in.chan, n * sizeof(rawdtw_channel_t), hipMemcpyHostToDevice, s) != hipSuccess ||
@@ -545,12 +593,31 @@ int detect_enqueue(rawdtw_ctx *ctx, const rawdtw_event_opt_t &o, uint32_t n_chun
     hipLaunchKernelGGL(k_ev_tstat, dim3((uint32_t)((N + 255) / 256)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_ev_peaks, dim3(waves), dim3(kW), 0, s, a);
     hipLaunchKernelGGL(k_ev_scan, dim3(1), dim3(1024), 0, s, a.nev, n_chunks, a.eoff, a.tot, dv_eoff);
-    hipLaunchKernelGGL(k_ev_events, dim3(n_chunks), dim3(kW), 0, s, a, std::min<uint64_t>(events_cap, N), dv_ev);
+    if (arena) {
+        hipLaunchKernelGGL(k_ev_room, dim3(1), dim3(1024), 0, s, a.nev, d_room, n_chunks, a.tot, events_cap, a.tot + 2);
+        hipLaunchKernelGGL(k_ev_events<true>, dim3(n_chunks), dim3(kW), 0, s, a, N, ctx->d_ev);
+    } else
+        hipLaunchKernelGGL(k_ev_events<false>, dim3(n_chunks), dim3(kW), 0, s, a, std::min<uint64_t>(events_cap, N), dv_ev);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipEventRecord(w.ev1, s);
     if (e == hipSuccess) e = hipMemcpyAsync(w.pin, a.tot, 8, hipMemcpyDeviceToHost, s);
+    if (arena) { // the flag, the counts and the raw entry's s_len: all that comes home
+        if (e == hipSuccess) e = hipMemcpyAsync(w.pin + 1, a.tot + 2, 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_nev, a.nev, n * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && is_raw) e = hipMemcpyAsync(h_cnt, r.cnt, n * 4, hipMemcpyDeviceToHost, s);
+    }
     if (e == hipSuccess) e = hipEventRecord(w.done, s);
     if (e != hipSuccess) return undo(hip_fail(ctx, e, "detection launches"));
+    w.enqueued = true;
+    return RAWDTW_OK;
+}
+
+// what the two resident entries refuse alike, beyond their plain counterparts' rules
+int resident_checks(rawdtw_ctx *ctx, uint32_t n_chunks, const uint64_t *dst_start, const uint32_t *room)
+{
+    if (n_chunks && (!dst_start || !room)) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    if (!ctx->d_ev) return fail(ctx, RAWDTW_ERR_INVALID, "no event arena on this context (rawdtw_events_reserve, rawdtw_set_events_device)");
+    if (ctx->detect_ws && ctx->detect_ws->w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "a detection is begun on this context and not ended");
     return RAWDTW_OK;
 }
 
@@ -588,10 +655,68 @@ int rawdtw_detect_raw_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint
     return detect_enqueue(ctx, o, n_chunks, raw_off, in, event_off, events, events_cap);
 }
 
+int rawdtw_detect_resident_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint32_t n_chunks, const uint64_t *sig_off, const float *sig,
+                                 const uint64_t *dst_start, const uint32_t *room, uint64_t events_cap)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (!sig_off || (n_chunks && !sig)) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    if (const int st = resident_checks(ctx, n_chunks, dst_start, room)) return st;
+    rawdtw_event_opt_t o;
+    if (events::resolve_opt(opt, &o) != RAWDTW_OK) return fail(ctx, RAWDTW_ERR_INVALID, "a window length above 65535");
+    if (events::check_raw_offsets(n_chunks, sig_off) != RAWDTW_OK) // (an empty chunk is a read's all-outlier window: no events, as the raw entry has it)
+        return fail(ctx, RAWDTW_ERR_INVALID, "a chunk of 2^32 samples or more, or offsets that descend");
+    Input in;
+    in.sig = sig; in.dst_start = dst_start ? dst_start : sig_off; in.room = room; // (n_chunks == 0: any non-null table marks the kind)
+    return detect_enqueue(ctx, o, n_chunks, sig_off, in, nullptr, nullptr, events_cap);
+}
+
+int rawdtw_detect_raw_resident_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint32_t n_chunks, const uint64_t *raw_off, const int16_t *raw,
+                                     const rawdtw_channel_t *chan, const uint64_t *dst_start, const uint32_t *room, uint64_t events_cap)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (!raw_off || (n_chunks && (!raw || !chan))) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    if (const int st = resident_checks(ctx, n_chunks, dst_start, room)) return st;
+    rawdtw_event_opt_t o;
+    if (events::resolve_opt(opt, &o) != RAWDTW_OK) return fail(ctx, RAWDTW_ERR_INVALID, "a window length above 65535");
+    if (events::check_raw_offsets(n_chunks, raw_off) != RAWDTW_OK)
+        return fail(ctx, RAWDTW_ERR_INVALID, "a window of 2^32 raw samples or more, or offsets that descend");
+    Input in;
+    in.raw = raw; in.chan = chan; in.dst_start = dst_start ? dst_start : raw_off; in.room = room;
+    return detect_enqueue(ctx, o, n_chunks, raw_off, in, nullptr, nullptr, events_cap);
+}
+
+int rawdtw_detect_resident_end(rawdtw_ctx *ctx, uint32_t *s_len, uint32_t *ev_len, uint64_t *total, float *kernel_ms)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (!ctx->detect_ws || !ctx->detect_ws->w.pending || !ctx->detect_ws->w.arena)
+        return fail(ctx, RAWDTW_ERR_INVALID, "no resident detection begun on this context");
+    DetectWs &w = ctx->detect_ws->w;
+    if (!total || (w.n && !ev_len)) return fail(ctx, RAWDTW_ERR_INVALID, "null argument"); // (the detection stays begun)
+    w.pending = false;
+    if (kernel_ms) *kernel_ms = 0.0f;
+    *total = 0;
+    if (!w.enqueued) { // no chunk, or no sample
+        for (uint64_t k = 0; k < w.n; k++) { ev_len[k] = 0; if (s_len) s_len[k] = 0; }
+        return RAWDTW_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipEventSynchronize(w.done)); // (the detection's own work: the seeding enqueued behind it goes on)
+    for (uint64_t k = 0; k < w.n; k++) {
+        ev_len[k] = w.h_nev[k];
+        if (s_len) s_len[k] = w.raw ? w.h_cnt[k] : (uint32_t)(w.h_off[k + 1] - w.h_off[k]);
+    }
+    *total = w.pin[0];
+    if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, w.ev0, w.ev1));
+    if (w.pin[1] & 1) return fail(ctx, RAWDTW_ERR_RANGE, "a chunk has more events than its room in the event arena (ev_len and the total are filled, nothing was written)");
+    if (w.pin[1] & 2) return fail(ctx, RAWDTW_ERR_RANGE, "events_cap is below the round's events (ev_len and the total are filled, nothing was written)");
+    return RAWDTW_OK;
+}
+
 int rawdtw_detect_end(rawdtw_ctx *ctx, float *kernel_ms)
 {
     if (!ctx) return RAWDTW_ERR_INVALID;
     if (!ctx->detect_ws || !ctx->detect_ws->w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "no detection begun on this context");
+    if (ctx->detect_ws->w.arena) return fail(ctx, RAWDTW_ERR_INVALID, "the detection begun on this context is a resident one (rawdtw_detect_resident_end)");
     DetectWs &w = ctx->detect_ws->w;
     w.pending = false;
     if (kernel_ms) *kernel_ms = 0.0f;
@@ -625,6 +750,14 @@ int rawdtw_detect_end(rawdtw_ctx *ctx, float *kernel_ms)
 } // extern "C"
 
 namespace rawdtw { namespace capi {
+bool detect_resident_view(const rawdtw_ctx *ctx, DetectView *v)
+{
+    const DetectWs *w = ctx && ctx->detect_ws ? &ctx->detect_ws->w : nullptr;
+    if (!w || !w->pending || !w->arena) return false;
+    *v = DetectView{w->enqueued, w->n, w->cap, w->n_samples, w->d_eoff, w->d_dst, w->d_flag};
+    return true;
+}
+
 void detect_ws_free(rawdtw_ctx *ctx)
 {
     if (!ctx || !ctx->detect_ws) return;

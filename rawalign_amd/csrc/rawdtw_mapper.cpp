@@ -304,6 +304,12 @@ struct rawdtw_mapper {
     PinBuf<rawdtw_seed_hit_t> seed_hits;
     // rawdtw_mapper_round_seeded_resident (rawdtw_mapper_resident_stats)
     uint64_t res_rounds = 0, res_fallbacks = 0, res_hit_bytes = 0, res_seed_bytes = 0;
+    // rawdtw_mapper_round_signal_resident / _raw_resident (rawdtw_mapper_signal_stats): the round's tables, the counts that come home
+    PinBuf<uint64_t> sig_dst;
+    PinBuf<uint32_t> sig_room, sig_evlen;
+    std::vector<uint64_t> sig_evoff;
+    uint64_t sig_rounds = 0, sig_retried = 0, sig_sample_bytes = 0;
+    uint64_t sig_cap = 0; // the largest events_cap a round from signal ran with: what the seeding's workspace holds already
 };
 
 namespace {
@@ -509,6 +515,7 @@ struct Round {
     double t0; // (the last lap)
     // a resident round: the hits are on the device (hit_off / hits are set only by its fall-back, which fetches them)
     bool resident = false, fell_back = false;
+    bool signal = false; // a round from signal: the events are in the arena already (the device detected them there), event_off holds their counts
     uint64_t res_prev = 0, res_hits = 0; // previous anchors sent up as seeds; hits fetched by the fall-back
     uint32_t G = (uint32_t)m->groups.size(); // (1 or 2)
     uint64_t id = m->rounds + 1;
@@ -541,7 +548,7 @@ struct Round {
         RoundRead &r = rr[k];
         r.ne = event_off[k + 1] - event_off[k];
         r.ev_before = rd.n_events; r.off_before = rd.offset;
-        if (m->keep_host_events) rd.events.insert(rd.events.end(), events + event_off[k], events + event_off[k + 1]); // rmap.cpp:554-567
+        if (m->keep_host_events && !signal) rd.events.insert(rd.events.end(), events + event_off[k], events + event_off[k + 1]); // rmap.cpp:554-567
         rd.n_events += (uint32_t)r.ne;
         if (r.ne < m->opt.min_events) { r.skipped = true; return false; } // rmap.cpp:569-572: no gen_chains, reg->offset stays
         r.chunk_start = rd.offset;  // reg->offset (rmap.cpp:574)
@@ -651,12 +658,7 @@ struct Round {
         Sizes n{nr};
         if (!stage_events(g, n, true, events_in_place)) return;
         const uint64_t nev = n.events, nseg = n.seg;
-        for (int b = 0; b < 2; b++) {
-            RoundArrays &x = g.buf[g.cur ^ b];
-            if (!(x.prev_off.ensure(g.hw_reads + 1, true) && x.ev_start.ensure(g.hw_reads + 1, true) && x.ev_len.ensure(g.hw_reads + 1, true) &&
-                  x.chunk_start.ensure(g.hw_reads + 1, true) && x.sits_out.ensure(g.hw_reads + 1, true)))
-                return failed(RAWDTW_ERR_OOM, "host allocation failed");
-        }
+        if (!resident_arrays(g)) return;
         m->pool->run(nr, 64, [&](size_t i) {
             const uint32_t k = ra.ks[i];
             const RoundRead &r = rr[k];
@@ -670,6 +672,43 @@ struct Round {
         if (st == RAWDTW_OK) st = rawdtw_seed_resident_end(g.ctx, nullptr);
         lap(2);
         if (st != RAWDTW_OK) return failed(st, rawdtw_last_error(g.ctx));
+        resident_chain(gi, nev, nseg);
+    }
+
+    // a resident round's own per-read arrays, in both buffers (sized by the group's high-water mark of reads)
+    bool resident_arrays(Group &g)
+    {
+        for (int b = 0; b < 2; b++) {
+            RoundArrays &x = g.buf[g.cur ^ b];
+            if (!(x.prev_off.ensure(g.hw_reads + 1, true) && x.ev_start.ensure(g.hw_reads + 1, true) && x.ev_len.ensure(g.hw_reads + 1, true) &&
+                  x.chunk_start.ensure(g.hw_reads + 1, true) && x.sits_out.ensure(g.hw_reads + 1, true))) {
+                failed(RAWDTW_ERR_OOM, "host allocation failed");
+                return false;
+            }
+        }
+        return true;
+    }
+
+    // ---- a round from signal, first half: detection and seeding ran on the device before the round was set up (rawdtw_mapper_round_signal_*),
+    // the events are in the arena and their counts in event_off; what is left of the host phase is the bookkeeping of append_events ----
+    void signal_begin(uint32_t gi)
+    {
+        Group &g = m->groups[gi]; RoundArrays &ra = g.buf[g.cur];
+        ra.carried = false; ra.round_id = id; ra.n_reads = ra.ks.size();
+        const size_t nr = ra.ks.size();
+        m->pool->run(nr, 64, [&](size_t i) { append_events(ra.ks[i]); });
+        if (!size_arrays(g, Sizes{nr}, true) || !resident_arrays(g)) return;
+        lap(0);
+        resident_chain(gi, 0, 0); // (no event went up from the host: nothing for slot 6)
+    }
+
+    // ---- a resident round from the ended seeding on: the arrays sized by the hit counts, the chaining begun on seeds the device lays down
+    // itself, or the fall-back.  nev / nseg: the events and segments the host sent up this round (the byte counters') ----
+    void resident_chain(uint32_t gi, uint64_t nev, uint64_t nseg)
+    {
+        Group &g = m->groups[gi]; RoundArrays &ra = g.buf[g.cur];
+        const size_t nr = ra.ks.size();
+        int st = RAWDTW_OK;
         const uint64_t *hoff = m->seed_off.p; // (chunk i is read ks[i]: one group, the round's reads in order)
         uint64_t ns = 0, np = 0;
         for (size_t i = 0; i < nr; i++) {
@@ -932,6 +971,8 @@ struct Round {
     }
 
     // ---- a failed round: the reads' events cut back, each group's round before stays the round before; nothing else was written ----
+    // (A round from signal: the device has written the chunk's events into the arena above the read's committed n_events.  That stretch is
+    // scratch -- nothing reads a slot beyond n_events -- and the next attempt's detection overwrites it from the same place.)
     int rollback()
     {
         for (uint32_t k = 0; k < n_reads; k++) {
@@ -1053,9 +1094,10 @@ const char *rawdtw_mapper_last_error(const rawdtw_mapper *m) { return m ? m->err
 int rawdtw_mapper_set_scorer(rawdtw_mapper *m, rawdtw_scorer_fn fn, void *user)
 {
     if (!m) return RAWDTW_ERR_INVALID;
-    if (fn && !m->keep_host_events) { // (an external scorer reads the host's copy of the reads' events: from the first round on)
+    if (fn) { // (an external scorer reads the host's copy of the reads' events: from the first round on -- no copy is kept by a mapper that
+              // scores on the device only, nor of the chunks a round from signal detected on the device)
         for (const MRead &rd : m->reads)
-            if (rd.n_events && !rd.released) return fail(m, RAWDTW_ERR_INVALID, "set the scorer before the first round");
+            if (rd.n_events != rd.events.size() && !rd.released) return fail(m, RAWDTW_ERR_INVALID, "set the scorer before the first round");
         m->keep_host_events = true;
     }
     m->scorer = fn; m->scorer_user = user;
@@ -1126,7 +1168,8 @@ int rawdtw_mapper_log(const rawdtw_mapper *m, const char **text)
 
 namespace {
 
-// a round's reads, every one checked before anything changes (`hit_off` null: a resident round, whose hits the host never sees)
+// a round's reads, every one checked before anything changes (`hit_off` null: a resident round, whose hits the host never sees;
+// `event_off` null: a round from signal, whose event counts the device finds -- it checks them against the slots' room itself)
 int check_round(rawdtw_mapper *m, uint32_t n_reads, const uint32_t *read_ids, const uint64_t *event_off, const uint64_t *hit_off, const rawdtw_seed_hit_t *hits)
 {
     const uint32_t n_seq = (uint32_t)m->seq_len.size();
@@ -1136,13 +1179,13 @@ int check_round(rawdtw_mapper *m, uint32_t n_reads, const uint32_t *read_ids, co
         MRead &rd = m->reads[read_ids[k]];
         bool dup = rd.seen_round == stamp;
         rd.seen_round = stamp;
-        if (dup || rd.finished || rd.released || event_off[k + 1] < event_off[k] || (hit_off && hit_off[k + 1] < hit_off[k])) {
+        if (dup || rd.finished || rd.released || (event_off && event_off[k + 1] < event_off[k]) || (hit_off && hit_off[k + 1] < hit_off[k])) {
             for (uint32_t q = 0; q <= k; q++) m->reads[read_ids[q]].seen_round = 0;
             return fail(m, RAWDTW_ERR_INVALID, dup ? "a read twice in one round" : rd.finished || rd.released ? "a finished read in a round" : "offsets do not ascend");
         }
     }
     for (uint32_t k = 0; k < n_reads; k++) m->reads[read_ids[k]].seen_round = 0; // (a failed round does not count)
-    for (uint32_t k = 0; k < n_reads; k++) {
+    for (uint32_t k = 0; event_off && k < n_reads; k++) {
         const MRead &rd = m->reads[read_ids[k]];
         if ((uint64_t)rd.n_events + (event_off[k + 1] - event_off[k]) > m->opt.slot_events) return fail(m, RAWDTW_ERR_RANGE, "a read outgrew its slot in the event arena");
         for (uint64_t h = hit_off ? hit_off[k] : 0; hit_off && h < hit_off[k + 1]; h++)
@@ -1253,6 +1296,117 @@ int rawdtw_mapper_round_seeded_resident(rawdtw_mapper *m, const rawdtw_seed_inde
     r.fetch_and_end(0);
     if (!r.ok()) return r.rollback();
     r.commit();
+    return RAWDTW_OK;
+}
+
+} // extern "C"
+
+namespace {
+
+// The round from signal: detection (the pA conversion in front of it for raw windows), seeding and chaining of one chunk round with no
+// event on the host.  Detection and seeding are enqueued one behind the other and waited for once; only the counts come home.  They run
+// before the round is set up and touch nothing of the mapper's but its own buffers, so whatever they refuse leaves reads and mapper as
+// they were; from the counts on it is rawdtw_mapper_round_seeded_resident's round.
+int round_from_signal(rawdtw_mapper *m, const rawdtw_seed_index *six, const rawdtw_event_opt_t *ev_opt, uint32_t n_reads, const uint32_t *read_ids,
+                      const uint64_t *off, const float *sig, const int16_t *raw, const rawdtw_channel_t *chan, bool is_raw)
+{
+    if (!m || !six || (n_reads && (!read_ids || !off)) || (n_reads && off[n_reads] > off[0] && (is_raw ? !raw : !sig)) || (n_reads && is_raw && !chan))
+        return m ? fail(m, RAWDTW_ERR_INVALID, "null argument") : RAWDTW_ERR_INVALID;
+    uint32_t six_seq = 0;
+    rawdtw_seed_pars_t pars;
+    if (rawdtw_seed_index_info(six, &six_seq, nullptr, nullptr, nullptr, &pars) != RAWDTW_OK) return RAWDTW_ERR_INVALID;
+    if (six_seq != m->seq_len.size()) return fail(m, RAWDTW_ERR_INVALID, "the seed index and the mapper hold different numbers of sequences");
+    // rawdtw_mapper_round_seeded_resident's preconditions, and nothing may read the host's copy of a read's events later: that is the
+    // --dtw-output-cigar traceback (rawdtw_mapper_finish) and an external scorer.  A mapper with no DTW stage keeps the copy for neither.
+    if (!m->ctx || m->scorer || !m->opt.device_chain || m->groups.size() != 1 || (pars.w != 0 && !minimizer_on_device(m->ctx)) || (m->opt.flag & 0x4))
+        return fail(m, RAWDTW_ERR_UNSUPPORTED, "a round from signal needs a context, device chaining, one read group, no external scorer, no --dtw-output-cigar "
+                                               "and a w == 0 index, or a w > 0 one with the context's \"seed_minimizer\" option on "
+                                               "(rawdtw_detect_raw_begin + rawdtw_mapper_round_seeded_resident map the round)");
+    if (n_reads == 0) return RAWDTW_OK;
+    const double t0 = now_ms();
+    const int chk = check_round(m, n_reads, read_ids, nullptr, nullptr, nullptr);
+    if (chk != RAWDTW_OK) return chk;
+    const uint64_t nr = n_reads;
+    if (!seed_room(m, m->seed_off, nr + 1) || !m->sig_dst.ensure(nr, false) || !m->sig_room.ensure(nr, false) || !m->sig_evlen.ensure(nr, false))
+        return fail(m, RAWDTW_ERR_OOM, "no memory for the round's tables");
+    for (uint32_t k = 0; k < n_reads; k++) { // the chunk goes behind the read's committed events, and may fill its slot
+        const MRead &rd = m->reads[read_ids[k]];
+        m->sig_dst[k] = (uint64_t)rd.slot * m->opt.slot_events + rd.n_events;
+        m->sig_room[k] = m->opt.slot_events - std::min(rd.n_events, m->opt.slot_events);
+    }
+    const int up = rawdtw_seed_index_upload(m->ctx, six);
+    if (up == RAWDTW_ERR_INVALID) return fail(m, RAWDTW_ERR_UNSUPPORTED, rawdtw_last_error(m->ctx)); // (somebody's seeding is begun on the context)
+    if (up != RAWDTW_OK) return fail(m, up, rawdtw_last_error(m->ctx));
+    // events_cap, the first guess: what the seeding's workspace holds already, or a quarter of the samples; a round with more says how many and
+    // runs once more (as rawdtw_mapper_round_seeded does for its hits)
+    const uint64_t n_samples = off[n_reads] - off[0];
+    int64_t first_cap = 0;
+    (void)rawdtw_get_option(m->ctx, "signal_events_cap", &first_cap);
+    uint64_t cap = first_cap > 0 ? (uint64_t)first_cap : std::max<uint64_t>(m->sig_cap, n_samples / 4 + 1024);
+    uint64_t total = 0;
+    bool retried = false;
+    for (int attempt = 0;; attempt++) {
+        int st = is_raw ? rawdtw_detect_raw_resident_begin(m->ctx, ev_opt, n_reads, off, raw, chan, m->sig_dst.p, m->sig_room.p, cap)
+                        : rawdtw_detect_resident_begin(m->ctx, ev_opt, n_reads, off, sig, m->sig_dst.p, m->sig_room.p, cap);
+        if (st != RAWDTW_OK) return fail(m, st, rawdtw_last_error(m->ctx));
+        const int sb = rawdtw_seed_detected_begin(m->ctx, m->seed_off.p);
+        // the one wait: both ends (the detection's first -- it is ended whatever the seeding's begin said)
+        st = rawdtw_detect_resident_end(m->ctx, nullptr, m->sig_evlen.p, &total, nullptr);
+        std::string msg = st != RAWDTW_OK ? rawdtw_last_error(m->ctx) : "";
+        if (sb != RAWDTW_OK) return fail(m, sb, rawdtw_last_error(m->ctx));
+        const int se = rawdtw_seed_resident_end(m->ctx, nullptr);
+        if (st == RAWDTW_OK && se == RAWDTW_OK) break;
+        if (st == RAWDTW_ERR_RANGE) {
+            for (uint32_t k = 0; k < n_reads; k++)
+                if (m->sig_evlen[k] > m->sig_room[k]) return fail(m, RAWDTW_ERR_RANGE, "a read outgrew its slot in the event arena");
+            if (attempt == 0 && total > cap) { cap = total; retried = true; continue; }
+        }
+        return st != RAWDTW_OK ? fail(m, st, msg) : fail(m, se, rawdtw_last_error(m->ctx));
+    }
+    m->sig_cap = std::max(m->sig_cap, cap);
+    m->sig_evoff.resize(nr + 1);
+    m->sig_evoff[0] = 0;
+    for (uint32_t k = 0; k < n_reads; k++) m->sig_evoff[k + 1] = m->sig_evoff[k] + m->sig_evlen[k];
+    Round r{m, n_reads, read_ids, m->sig_evoff.data(), nullptr, nullptr, nullptr, t0};
+    r.resident = true; r.signal = true;
+    r.on_device = true; // (as rawdtw_mapper_round_seeded_resident)
+    r.events_in_place = false;
+    r.deal();
+    r.signal_begin(0);
+    r.end_device_chain(0);
+    r.fetch_and_end(0);
+    if (!r.ok()) return r.rollback();
+    r.commit();
+    m->sig_rounds++;
+    if (retried) m->sig_retried++;
+    m->sig_sample_bytes += n_samples * (is_raw ? sizeof(int16_t) : sizeof(float)) * (retried ? 2 : 1);
+    return RAWDTW_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int rawdtw_mapper_round_signal_resident(rawdtw_mapper *m, const rawdtw_seed_index *six, const rawdtw_event_opt_t *ev_opt, uint32_t n_reads,
+                                        const uint32_t *read_ids, const uint64_t *sig_off, const float *sig)
+{
+    return round_from_signal(m, six, ev_opt, n_reads, read_ids, sig_off, sig, nullptr, nullptr, false);
+}
+
+int rawdtw_mapper_round_raw_resident(rawdtw_mapper *m, const rawdtw_seed_index *six, const rawdtw_event_opt_t *ev_opt, uint32_t n_reads,
+                                     const uint32_t *read_ids, const uint64_t *raw_off, const int16_t *raw, const rawdtw_channel_t *chan)
+{
+    return round_from_signal(m, six, ev_opt, n_reads, read_ids, raw_off, nullptr, raw, chan, true);
+}
+
+int rawdtw_mapper_signal_stats(const rawdtw_mapper *m, uint64_t *rounds, uint64_t *retried_rounds, uint64_t *sample_bytes_to_device,
+                               uint64_t *event_bytes_crossed)
+{
+    if (!m) return RAWDTW_ERR_INVALID;
+    if (rounds) *rounds = m->sig_rounds;
+    if (retried_rounds) *retried_rounds = m->sig_retried;
+    if (sample_bytes_to_device) *sample_bytes_to_device = m->sig_sample_bytes;
+    if (event_bytes_crossed) *event_bytes_crossed = (uint64_t)m->timing[6]; // (the mapper sends events up and fetches none: slot 6 is all that crosses)
     return RAWDTW_OK;
 }
 

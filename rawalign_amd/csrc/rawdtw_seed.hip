@@ -30,6 +30,11 @@
 //   k_seed_write_chain  k_seed_write's shape, but what it lays down is the chaining's seed list (rmap.cpp:385-391 as the mapper's
 //                       write_seeds restates it): 12-byte {sequence * 2 + strand, target, query + the chunk's start} records straight
 //                       into rawdtw_chain.hip's workspace, behind the read's previous anchors -- the hits never exist in host memory
+// A seeding DETECTED (rawdtw_seed_detected_begin) is a resident one enqueued straight behind a resident detection (rawdtw_events.hip)
+// with no host step between: its dense offsets are the detection's event offsets, its source starts the detection's places in the
+// arena, both copied on the device, and its workspace is sized by the detection's events_cap because no count has come home yet.
+// Its launches are instantiations of their own (kGuard) that do nothing when the detection's flag word says it declined -- the
+// offsets would then run past the workspace; the unguarded instantiations above never read that word.
 #include "rawdtw_capi.h"
 #include "rawdtw_seed.h"
 
@@ -60,6 +65,7 @@ struct SeedArgs {
     const uint64_t *list;
     uint32_t log2_slots;
     uint32_t n, e, q, lq;
+    const uint64_t *decl; // kGuard launches alone: the detection's flag word (non-zero: do nothing); never read by the others
 };
 
 __device__ __forceinline__ uint32_t wave_max(uint32_t x)
@@ -76,12 +82,14 @@ __device__ __forceinline__ uint64_t lane_u64(uint64_t x, int c)
 
 // rsketch.c:242-247.  kSrc: the chunks' events are read from a.src[k] on (the event arena) rather than from the dense offset.
 // kMask: the w == 0 rule (rsketch.c:243); without it ri_sketch_min's (rsketch.c:172), which keeps a masked value.
-template <bool kSrc, bool kMask = true> __global__ __launch_bounds__(64) void k_seed_filter(SeedArgs a)
+// kGuard: a detected seeding's instantiation (the whole workgroup leaves when the detection declined).
+template <bool kSrc, bool kMask = true, bool kGuard = false> __global__ __launch_bounds__(64) void k_seed_filter(SeedArgs a)
 {
     __shared__ float tx[kW * kPad];
     __shared__ uint32_t tr[kW * kPad];
     __shared__ uint64_t sb[kW];
     __shared__ uint32_t sl[kW];
+    if (kGuard && a.decl[0]) return;
     const uint32_t lane = threadIdx.x, c0 = blockIdx.x * kW, me = c0 + lane, nc = min(kW, a.n - c0);
     uint64_t b = 0;
     uint32_t len = 0;
@@ -137,6 +145,7 @@ struct MinArgs {
     uint32_t *hash, *pos, *count;        // the sketch: per chunk dense from off[k], and the elements a chunk
     uint64_t *over;                      // set when a chunk's sketch has more elements than the chunk has events
     uint32_t e, qb, w;
+    const uint64_t *decl; // (as SeedArgs::decl)
 };
 
 constexpr uint32_t kRing = 512; // e-mer hashes kept in LDS: a window of up to 255 behind a step of 64
@@ -145,9 +154,10 @@ constexpr uint32_t kRing = 512; // e-mer hashes kept in LDS: a window of up to 2
 // every compare against a real one), so no ring of (x, y) is kept: the minimum is (hash, e-mer index), "buf_pos == min_pos" is "the
 // minimum sits w e-mers back", and l = m + e.  x = hash << RI_HASH_SHIFT | span with one span: hashes compare as x does.  y differs
 // exactly where the e-mer index does.
-__global__ __launch_bounds__(64) void k_seed_min(MinArgs a)
+template <bool kGuard = false> __global__ __launch_bounds__(64) void k_seed_min(MinArgs a)
 {
     __shared__ uint32_t ring[kRing];
+    if (kGuard && a.decl[0]) return;
     const uint32_t k = blockIdx.x, lane = threadIdx.x, e = a.e, w = a.w;
     const uint64_t b = a.off[k];
     const uint32_t room = (uint32_t)(a.off[k + 1] - b), kept = a.fkept[k];
@@ -210,8 +220,9 @@ __global__ __launch_bounds__(64) void k_seed_min(MinArgs a)
 }
 
 // rsketch.c:254-255, rawindex.cpp:256-273.  kGiven (w > 0): every element r < kept has its hash in a.code already (k_seed_min).
-template <bool kGiven> __global__ __launch_bounds__(64) void k_seed_probe(SeedArgs a)
+template <bool kGiven, bool kGuard = false> __global__ __launch_bounds__(64) void k_seed_probe(SeedArgs a)
 {
+    if (kGuard && a.decl[0]) return;
     const uint32_t k = blockIdx.x, lane = threadIdx.x, kept = a.kept[k], e = a.e, qb = a.lq + 2;
     const uint64_t b = a.off[k];
     const uint64_t mask_events = (1ull << (qb * e)) - 1;
@@ -244,9 +255,12 @@ template <bool kGiven> __global__ __launch_bounds__(64) void k_seed_probe(SeedAr
 }
 
 // exclusive scan of the chunks' hits (the shape of rawdtw_events.hip's k_ev_scan)
-__global__ __launch_bounds__(1024) void k_seed_scan(const uint64_t *cnt, uint32_t n, uint64_t *off, uint64_t *tot, uint64_t *h_off)
+// (kGuard: `decl` is read, and the scan left out when it is set; without it `decl` is not looked at)
+template <bool kGuard = false> __global__ __launch_bounds__(1024) void k_seed_scan(const uint64_t *cnt, uint32_t n, uint64_t *off, uint64_t *tot, uint64_t *h_off,
+                                                                                   const uint64_t *decl)
 {
     __shared__ uint64_t part[1024];
+    if (kGuard && decl[0]) return;
     const uint32_t t = threadIdx.x;
     const uint64_t per = (n + 1023ull) / 1024, lo = min((uint64_t)n, t * per), hi = min((uint64_t)n, lo + per);
     uint64_t s = 0;
@@ -397,6 +411,8 @@ struct SeedWs {
     const uint64_t *d_hoff = nullptr;
     // a resident seeding: begun (pending && resident), then ended and readable (ready) until the context's next seeding of either kind
     bool resident = false, ready = false;
+    bool enqueued = false;            // the resident seeding begun has work on the stream (its events are recorded)
+    const uint64_t *h_decl = nullptr; // a detected seeding: the detection's flag word as it came home (in `pin`); else null
     SeedArgs ra{};                // the launches' arguments: where the retained words are
     uint64_t r_total = 0;
     const uint64_t *r_hoff = nullptr; // n + 1 hit offsets, the library's own host copy (in `pin`)
@@ -424,22 +440,23 @@ void *device_view(void *p, size_t bytes)
 
 // filter -> (min) -> probe -> scan on `a`.  With w > 0 the filter's output goes to `mn`'s inputs and `a` is re-pointed at the sketch: the
 // launches behind (and whoever keeps `a`) see the sketch's elements where they saw the kept events.
-template <bool kSrc> void launch_seeding(SeedArgs &a, MinArgs mn, uint32_t w, hipStream_t s, uint64_t *dv_hoff)
+template <bool kSrc, bool kGuard = false> void launch_seeding(SeedArgs &a, MinArgs mn, uint32_t w, hipStream_t s, uint64_t *dv_hoff)
 {
     const dim3 tiles((a.n + kW - 1) / kW), chunks(a.n), wave(kW);
     if (w == 0) {
-        hipLaunchKernelGGL((k_seed_filter<kSrc, true>), tiles, wave, 0, s, a);
-        hipLaunchKernelGGL(k_seed_probe<false>, chunks, wave, 0, s, a);
+        hipLaunchKernelGGL((k_seed_filter<kSrc, true, kGuard>), tiles, wave, 0, s, a);
+        hipLaunchKernelGGL((k_seed_probe<false, kGuard>), chunks, wave, 0, s, a);
     } else {
         SeedArgs f = a;
         f.code = const_cast<uint32_t *>(mn.code); f.pos = const_cast<uint32_t *>(mn.fpos); f.kept = const_cast<uint32_t *>(mn.fkept);
-        hipLaunchKernelGGL((k_seed_filter<kSrc, false>), tiles, wave, 0, s, f);
-        hipLaunchKernelGGL(k_seed_min, chunks, wave, 0, s, mn);
-        hipLaunchKernelGGL(k_seed_probe<true>, chunks, wave, 0, s, a);
+        hipLaunchKernelGGL((k_seed_filter<kSrc, false, kGuard>), tiles, wave, 0, s, f);
+        hipLaunchKernelGGL(k_seed_min<kGuard>, chunks, wave, 0, s, mn);
+        hipLaunchKernelGGL((k_seed_probe<true, kGuard>), chunks, wave, 0, s, a);
     }
-    hipLaunchKernelGGL(k_seed_scan, dim3(1), dim3(1024), 0, s, a.chits, a.n, a.hoff, a.tot, dv_hoff);
+    hipLaunchKernelGGL(k_seed_scan<kGuard>, dim3(1), dim3(1024), 0, s, a.chits, a.n, a.hoff, a.tot, dv_hoff, a.decl);
 }
 
+const char *const kDeclined = "the detection in front of this seeding declined (a chunk over its room, or events_cap below the round's events): nothing was seeded";
 const char *const kOverflow = "a chunk's minimizer sketch has more elements than the chunk has events: seed this round on the host (rawdtw_seed_hits_host)";
 
 } // namespace
@@ -675,6 +692,7 @@ int rawdtw_seed_resident_begin(rawdtw_ctx *ctx, uint32_t n_chunks, const uint64_
     w.pending = true; w.resident = true; w.n = n_chunks; w.n_events = N; w.cap = 0;
     w.h_hoff = hit_off; w.h_hits = nullptr; w.direct_off = w.direct_hits = false;
     w.r_hoff = h_hoff; w.r_total = 0;
+    w.enqueued = false; w.h_decl = nullptr;
     if (n == 0) return RAWDTW_OK; // (nothing to enqueue)
     char *p = static_cast<char *>(w.dev);
     SeedArgs a{};
@@ -712,6 +730,105 @@ int rawdtw_seed_resident_begin(rawdtw_ctx *ctx, uint32_t n_chunks, const uint64_
     if (e == hipSuccess) e = hipMemcpyAsync(w.pin + 1, a.tot + 1, 8, hipMemcpyDeviceToHost, s); // (k_seed_min's overflow flag)
     if (e == hipSuccess) e = hipEventRecord(w.done, s);
     if (e != hipSuccess) return undo(hip_fail(ctx, e, "seeding launches"));
+    w.enqueued = true;
+    return RAWDTW_OK;
+}
+
+// A resident seeding straight behind the context's resident detection: see the head of this file.
+int rawdtw_seed_detected_begin(rawdtw_ctx *ctx, uint64_t *hit_off)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (!hit_off) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    DetectView v;
+    if (!detect_resident_view(ctx, &v)) return fail(ctx, RAWDTW_ERR_INVALID, "no resident detection begun on this context and not ended");
+    SeedWs *wp = ctx->seed_ws ? &ctx->seed_ws->w : nullptr;
+    if (!wp || !wp->has_table) return fail(ctx, RAWDTW_ERR_INVALID, "no seed index on this context (rawdtw_seed_index_upload)");
+    SeedWs &w = *wp;
+    if (w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "a seeding is begun on this context and not ended");
+    if (w.pars.w && !ctx->seed_minimizer) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, "the minimizer sketch (w > 0) is seeded on the host (rawdtw_seed_hits_host)");
+    // the host has seen no count: room for as many events as the detection may write (its events_cap; never more than it has samples)
+    const uint64_t n = v.n, N = v.enqueued ? std::min(v.cap, v.n_samples) : 0;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    w.ready = false; w.resident = false;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t b_off = al((n + 1) * 8), b_ev = al(N * 4), b_val = al(N * 8), b_cnt = al(n * 4), b_tot = al(32); // (rawdtw_seed_resident_begin's block)
+    const size_t need = 4 * b_off + 3 * b_ev + b_val + b_cnt + b_tot + (w.pars.w ? 2 * b_ev + b_cnt : 0);
+    if (w.dev_bytes < need) {
+        if (w.dev) (void)hipFree(w.dev);
+        w.dev = nullptr; w.dev_bytes = 0;
+        const size_t want = need + need / 4;
+        if (hipMalloc(&w.dev, want) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, RAWDTW_ERR_OOM, "seeding workspace allocation failed"); }
+        w.dev_bytes = want;
+    }
+    const size_t pin_need = (3 * (n + 1) + 4) * 8; // (as a resident seeding's; the flag word lands behind the hit offsets)
+    if (w.pin_bytes < pin_need) {
+        if (w.pin) (void)hipHostFree(w.pin);
+        w.pin = nullptr; w.pin_bytes = 0;
+        const size_t want = pin_need + pin_need / 4;
+        if (hipHostMalloc(reinterpret_cast<void **>(&w.pin), want, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError(); w.pin = nullptr;
+            return fail(ctx, RAWDTW_ERR_OOM, "pinned allocation failed");
+        }
+        w.pin_bytes = want;
+    }
+    if (!w.ev0) HIP_TRY(ctx, hipEventCreate(&w.ev0));
+    if (!w.ev1) HIP_TRY(ctx, hipEventCreate(&w.ev1));
+    if (!w.done) HIP_TRY(ctx, hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
+    uint64_t *h_hoff = w.pin + 2 + 2 * (n + 1), *h_decl = h_hoff + (n + 1);
+    for (uint64_t k = 0; k <= n; k++) h_hoff[k] = 0;
+    w.pin[0] = w.pin[1] = 0; *h_decl = 0;
+    w.pending = true; w.resident = true; w.n = v.n; w.n_events = N; w.cap = 0;
+    w.h_hoff = hit_off; w.h_hits = nullptr; w.direct_off = w.direct_hits = false;
+    w.r_hoff = h_hoff; w.r_total = 0;
+    w.enqueued = false; w.h_decl = h_decl;
+    if (n == 0) return RAWDTW_OK; // (nothing to enqueue)
+    char *p = static_cast<char *>(w.dev);
+    SeedArgs a{};
+    uint64_t *d_off = reinterpret_cast<uint64_t *>(p); p += b_off;
+    uint64_t *d_src = reinterpret_cast<uint64_t *>(p); p += b_off;
+    a.code = reinterpret_cast<uint32_t *>(p); p += b_ev;
+    a.pos = reinterpret_cast<uint32_t *>(p); p += b_ev;
+    a.cnt = reinterpret_cast<uint32_t *>(p); p += b_ev;
+    a.val = reinterpret_cast<uint64_t *>(p); p += b_val;
+    a.kept = reinterpret_cast<uint32_t *>(p); p += b_cnt;
+    a.chits = reinterpret_cast<uint64_t *>(p); p += b_off;
+    a.hoff = reinterpret_cast<uint64_t *>(p); p += b_off;
+    a.tot = reinterpret_cast<uint64_t *>(p); p += b_tot;
+    a.off = d_off; a.src = d_src; a.ev = ctx->d_ev; a.n = v.n;
+    a.e = w.pars.e; a.q = w.pars.q; a.lq = w.pars.lq;
+    a.slots = w.d_slots; a.list = w.d_list; a.log2_slots = w.log2_slots;
+    a.decl = v.d_flag;
+    MinArgs mn{};
+    if (w.pars.w) { // (as in rawdtw_seed_begin)
+        mn = MinArgs{d_off, a.code, a.pos, a.kept, nullptr, nullptr, nullptr, a.tot + 1, w.pars.e, w.pars.lq + 2, w.pars.w, v.d_flag};
+        mn.hash = a.code = reinterpret_cast<uint32_t *>(p); p += b_ev;
+        mn.pos = a.pos = reinterpret_cast<uint32_t *>(p); p += b_ev;
+        mn.count = a.kept = reinterpret_cast<uint32_t *>(p);
+    }
+    hipStream_t s = ctx->stream;
+    auto undo = [&](int st) { w.pending = false; w.resident = false; return st; };
+    if (hipEventRecord(w.ev0, s) != hipSuccess) return undo(hip_fail(ctx, hipGetLastError(), "seeding launches"));
+    hipError_t e = hipSuccess;
+    if (!v.enqueued) { // the detection had no sample: every chunk is empty -- zero offsets, counts and hits for whoever reads them
+        e = hipMemsetAsync(w.dev, 0, need, s);
+    } else {
+        // the offsets and the places are copied out of the detection's workspace, so that the retained words do not depend on it
+        e = hipMemcpyAsync(d_off, v.d_eoff, (n + 1) * 8, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_src, v.d_dst, n * 8, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemsetAsync(a.tot, 0, 32, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_decl, v.d_flag, 8, hipMemcpyDeviceToHost, s);
+        if (e != hipSuccess) return undo(hip_fail(ctx, e, "seeding upload"));
+        launch_seeding<true, true>(a, mn, w.pars.w, s, nullptr);
+        e = hipGetLastError();
+    }
+    a.decl = nullptr; // (what is kept serves the unguarded k_seed_write / k_seed_write_chain, after an end that saw the flag clear)
+    w.ra = a; w.d_hoff = a.hoff;
+    if (e == hipSuccess) e = hipEventRecord(w.ev1, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_hoff, a.hoff, (n + 1) * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(w.pin + 1, a.tot + 1, 8, hipMemcpyDeviceToHost, s); // (k_seed_min's overflow flag)
+    if (e == hipSuccess) e = hipEventRecord(w.done, s);
+    if (e != hipSuccess) return undo(hip_fail(ctx, e, "seeding launches"));
+    w.enqueued = true;
     return RAWDTW_OK;
 }
 
@@ -723,10 +840,11 @@ int rawdtw_seed_resident_end(rawdtw_ctx *ctx, float *kernel_ms)
     SeedWs &w = ctx->seed_ws->w;
     w.pending = false; w.resident = false;
     if (kernel_ms) *kernel_ms = 0.0f;
-    if (w.n) {
+    if (w.n && w.enqueued) {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         HIP_TRY(ctx, hipEventSynchronize(w.done));
         if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, w.ev0, w.ev1));
+        if (w.h_decl && *w.h_decl) return fail(ctx, RAWDTW_ERR_RANGE, kDeclined); // (nothing written, nothing readable)
         if (w.pin[1]) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, kOverflow); // (nothing written, nothing readable)
     }
     for (uint64_t k = 0; k <= w.n; k++) w.h_hoff[k] = w.r_hoff[k];

@@ -132,6 +132,41 @@ class ResidentSeeding:
         return hits[:n].copy()
 
 
+class ResidentDetection:
+    """A resident detection begun on an Engine (Engine.detect_resident(..., wait=False)): end() waits and returns what came home."""
+
+    def __init__(self, engine, n, keep):
+        self.engine, self.n, self._keep = engine, n, keep
+
+    def end(self, kernel_ms: bool = False):
+        """rawdtw_detect_resident_end: (ev_len, s_len, total), and the launches' device time in ms too when kernel_ms.  A declined
+        detection (a chunk over its room, or the total over events_cap) raises RawDTWError with ev_len, s_len and total set on it."""
+        e = self.engine
+        ev_len, s_len = np.zeros(max(self.n, 1), np.uint32), np.zeros(max(self.n, 1), np.uint32)
+        total, ms = C.c_uint64(), C.c_float()
+        st = e.lib.rawdtw_detect_resident_end(e._ctx, _ptr(s_len), _ptr(ev_len), C.byref(total), C.byref(ms))
+        self._keep = None
+        if st != 0:
+            err = RawDTWError(st, e.lib.rawdtw_last_error(e._ctx).decode())
+            err.ev_len, err.s_len, err.total = ev_len[:self.n], s_len[:self.n], int(total.value)
+            raise err
+        out = (ev_len[:self.n], s_len[:self.n], int(total.value))
+        return out + (float(ms.value),) if kernel_ms else out
+
+
+class DetectedSeeding:
+    """A seeding begun behind a resident detection (Engine.seed_detected(wait=False)): end() waits and returns the ResidentSeeding."""
+
+    def __init__(self, engine, hit_off):
+        self.engine, self.hit_off = engine, hit_off
+
+    def end(self):
+        e = self.engine
+        ms = C.c_float()
+        e._check(e.lib.rawdtw_seed_resident_end(e._ctx, C.byref(ms)))
+        return ResidentSeeding(e, self.hit_off, float(ms.value))
+
+
 class Engine:
     """One rawdtw_ctx (one HIP device, one stream)."""
 
@@ -296,6 +331,35 @@ class Engine:
         out = (s_len[:n].copy(), eoff[:n + 1].copy(), ev[:int(eoff[n])].copy())
         return out + (float(ms.value),) if kernel_ms else out
 
+    def detect_resident(self, data, off, dst_start, room, chan=None, opt=None, events_cap=None, wait: bool = True):
+        """Detection whose events stay on the device: window k = data[off[k] .. off[k+1]) -- pA samples (float32), or with `chan` int16
+        DAC samples and a channel a window -- is detected into the context's event arena at dst_start[k] .., at most room[k] events
+        (rawdtw_detect_resident_begin / rawdtw_detect_raw_resident_begin).  All or nothing: a chunk over its room, or a total above
+        events_cap (None: the samples' count, which always suffices), writes nothing and raises RawDTWError (status 4) from the end with
+        ev_len, s_len and total set on it.  Returns (ev_len, s_len, total); wait=False: a ResidentDetection to end() later, so that
+        seed_detected can be enqueued behind it first."""
+        from .events import _opt
+
+        off = np.ascontiguousarray(off, np.uint64)
+        n = len(off) - 1
+        dst, rm = np.ascontiguousarray(dst_start, np.uint64), np.ascontiguousarray(room, np.uint32)
+        if len(dst) != n or len(rm) != n:
+            raise ValueError("dst_start and room need one entry a window")
+        cap = int(off[-1] - off[0]) if events_cap is None else int(events_cap)
+        if chan is None:
+            data = np.ascontiguousarray(data, np.float32)
+            self._check(self.lib.rawdtw_detect_resident_begin(self._ctx, _opt(opt), n, _ptr(off), _ptr(data), _ptr(dst), _ptr(rm), cap))
+            keep = (off, data, dst, rm)
+        else:
+            from .rawsig import channels
+
+            data = np.ascontiguousarray(data, np.int16)
+            ch = channels(chan, n)
+            self._check(self.lib.rawdtw_detect_raw_resident_begin(self._ctx, _opt(opt), n, _ptr(off), _ptr(data), _ptr(ch), _ptr(dst), _ptr(rm), cap))
+            keep = (off, data, ch, dst, rm)
+        det = ResidentDetection(self, n, keep)
+        return det.end() if wait else det
+
     # -- seeding (ri_sketch + ri_idx_get, src/rmap.cpp:364-391) ---------------------
     def upload_seed_index(self, index):
         """The table of a seeding.SeedIndex into this context's device memory (replaces an earlier one)."""
@@ -361,6 +425,16 @@ class Engine:
         self._check(self.lib.rawdtw_seed_resident_begin(self._ctx, n, _ptr(start), _ptr(ln), _ptr(hoff)))
         self._check(self.lib.rawdtw_seed_resident_end(self._ctx, C.byref(ms)))
         return ResidentSeeding(self, hoff, float(ms.value))
+
+    def seed_detected(self, detection, wait: bool = True):
+        """The resident seeding of the chunks of `detection`, a ResidentDetection begun on this engine and not ended yet
+        (detect_resident(..., wait=False)), enqueued straight behind it with no host step between: rawdtw_seed_detected_begin.
+        Returns the ResidentSeeding (ended with rawdtw_seed_resident_end; RawDTWError status 4 when the detection declined), or with
+        wait=False a DetectedSeeding to end() later.  The detection is ended by its own end(), before or after."""
+        hoff = np.zeros(detection.n + 1, np.uint64)
+        self._check(self.lib.rawdtw_seed_detected_begin(self._ctx, _ptr(hoff)))
+        sd = DetectedSeeding(self, hoff)
+        return sd.end() if wait else sd
 
     # -- batches ----------------------------------------------------------------
     def plan(self, jobs) -> Plan:

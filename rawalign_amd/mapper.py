@@ -119,6 +119,38 @@ class IndexSeeds:
         return ev, list(zip(h["ref_seq"].tolist(), h["strand"].tolist(), h["target_position"].tolist(), h["query_position"].tolist()))
 
 
+class SignalReads:
+    """Whole reads as the signal file holds them, for map_reads_c(..., signal=True): reads[r] is read r's samples -- pA (float32, the
+    outliers already out), or with `channels` (one Channel for all, or one a read) the int16 DAC samples as they came.  qlen and the
+    windows come from the chunk table: for int16 reads rawsig.chunk_table (the kept samples of window c are exactly chunk c), for pA
+    reads `chunk_size` samples a window, at most `max_num_chunk` of them."""
+
+    def __init__(self, reads, seq_lens, channels=None, names=None, chunk_size: int = 4000, max_num_chunk: int = 30):
+        from . import rawsig
+
+        self.lens = np.asarray(seq_lens)
+        self.raw = channels is not None
+        self.reads = [np.ascontiguousarray(x, np.int16 if self.raw else np.float32) for x in reads]
+        self.channels = rawsig.channels(channels, len(self.reads)) if self.raw else None
+        self.names = list(names) if names is not None else [f"read_{r}" for r in range(len(self.reads))]
+        self.qlens, self.starts = [], []
+        for r, x in enumerate(self.reads):
+            if self.raw:
+                l_sig, start = rawsig.chunk_table(x, self.channels[r], chunk_size, max_num_chunk)
+            else:
+                l_sig = len(x)
+                n = min(int(max_num_chunk), -(-len(x) // int(chunk_size)))
+                start = np.minimum(np.arange(n + 1, dtype=np.uint64) * np.uint64(chunk_size), np.uint64(len(x)))
+            self.qlens.append(int(l_sig))
+            self.starts.append(start)
+
+    def read_job(self, r) -> ReadJob:
+        return ReadJob(self.names[r], qlen=self.qlens[r], n_chunks_available=len(self.starts[r]) - 1)
+
+    def window(self, r, c):
+        return self.reads[r][int(self.starts[r][c]):int(self.starts[r][c + 1])]
+
+
 def score_log_line(chain) -> str:
     """rmap.cpp:308-312: sprintf("chaining_score=%f alignment_score=%f\\n", ...)."""
     return "chaining_score=%f alignment_score=%f\n" % (float(np.float32(chain.chaining_score)),
@@ -598,6 +630,34 @@ class CMapper:
                 at += 1
         self.round_arrays(ids, eoff, ev, hoff, hits)
 
+    def round_signal(self, read_ids, windows, seed_index, channels=None, event_opt=None):
+        """One chunk round from the signal itself: windows[k] is read read_ids[k]'s next chunk as samples -- pA (float32;
+        rawdtw_mapper_round_signal_resident), or with `channels` (one a window, or one for all) int16 DAC samples
+        (rawdtw_mapper_round_raw_resident).  Detection, seeding and chaining run on the device; no event crosses PCIe."""
+        from .events import _opt
+
+        ids = np.ascontiguousarray(read_ids, np.uint32)
+        off = np.zeros(len(ids) + 1, np.uint64)
+        off[1:] = np.cumsum([len(w) for w in windows])
+        dt = np.float32 if channels is None else np.int16
+        data = np.concatenate([np.ascontiguousarray(w, dt) for w in windows] + [np.zeros(8, dt)])
+        if channels is None:
+            st = self.lib.rawdtw_mapper_round_signal_resident(self._h, seed_index._h, _opt(event_opt), len(ids), _vp(ids), _vp(off), _vp(data))
+        else:
+            from .rawsig import channels as chan_array
+
+            ch = chan_array(channels, len(ids))
+            st = self.lib.rawdtw_mapper_round_raw_resident(self._h, seed_index._h, _opt(event_opt), len(ids), _vp(ids), _vp(off), _vp(data), _vp(ch))
+        self._check(st)
+
+    def signal_stats(self):
+        """rawdtw_mapper_signal_stats: rounds from signal, those that ran twice, bytes of samples sent up, bytes of events that crossed PCIe"""
+        import ctypes as C
+
+        v = [C.c_uint64() for _ in range(4)]
+        self._check(self.lib.rawdtw_mapper_signal_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(rounds=v[0].value, retried_rounds=v[1].value, sample_bytes_to_device=v[2].value, event_bytes_crossed=v[3].value)
+
     def state(self, rid: int):
         import ctypes as C
 
@@ -736,7 +796,7 @@ class CMapper:
             self._h = None
 
 
-def map_reads_c(seeds, read_ids, cm: CMapper, batch_size=None, su=None, seed_index=None, resident=False):
+def map_reads_c(seeds, read_ids, cm: CMapper, batch_size=None, su=None, seed_index=None, resident=False, signal=False, event_opt=None):
     """map_reads through the library's mapper: chunk rounds until every read stopped; the PAF lines in read order, the rounds.
 
     The reads go in mini-batches of `batch_size` (None: one of all of them), at most two at a time -- the next batch's reads are
@@ -745,10 +805,14 @@ def map_reads_c(seeds, read_ids, cm: CMapper, batch_size=None, su=None, seed_ind
     host-side state with the interface of mapping.SequenceUntil (CSequenceUntil), is given -- through the split form a multi-rank
     host uses (batch_records, the walk of shard.sequence_until_round, su_apply).  After the stop no read is added; a read
     without a line (sequence-until dropped it, or it was never added) has "" in the list.  `resident` (with `seed_index`): the
-    rounds leave their hits on the device (CMapper.round)."""
+    rounds leave their hits on the device (CMapper.round).  `signal` (with `seed_index`): `seeds` serves window(r, c) -- samples, not
+    events (SignalReads) -- and its `channels` (None: pA samples; else int16 reads' channels, one a read); every round is
+    CMapper.round_signal with `event_opt`: the events never leave the device."""
     from . import shard
 
     read_ids = list(read_ids)
+    if signal and seed_index is None:
+        raise ValueError("rounds from signal need a seed_index")
     jobs = {r: seeds.read_job(r) for r in read_ids}
     closing = cm.sequence_until
     if su is not None and not closing:
@@ -780,17 +844,21 @@ def map_reads_c(seeds, read_ids, cm: CMapper, batch_size=None, su=None, seed_ind
                 pending.clear()   # (the mapper finished their reads: no line)
         if not stopped and nxt < len(batches) and len(pending) < 2:
             continue
-        act, chunks = [], []
+        act, chunks, src = [], [], []
         for b in pending:
             for r in b:
                 fin, done = cm.state(ids[r])
                 if fin or done >= jobs[r].n_chunks_available:
                     continue
                 act.append(ids[r])
-                chunks.append(seeds.chunk(r, done))
+                chunks.append(seeds.window(r, done) if signal else seeds.chunk(r, done))
+                src.append(r)
         if not act:
             break
-        if seed_index is None:
+        if signal:
+            ch = getattr(seeds, "channels", None)
+            cm.round_signal(act, chunks, seed_index, channels=None if ch is None else ch[src], event_opt=event_opt)
+        elif seed_index is None:
             cm.round(act, chunks)
         else:
             cm.round(act, chunks, seed_index=seed_index, resident=resident)   # (the library seeds: seeds.chunk's hits are not used)
