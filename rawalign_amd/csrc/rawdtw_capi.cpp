@@ -378,3 +378,56 @@ int rawdtw_events_append(rawdtw_ctx *ctx, const float *h_new, uint64_t n_new, ui
 }
 
 } // extern "C"
+
+namespace rawdtw { namespace capi {
+int blocks_reserve(rawdtw_ctx *ctx, WsBlocks &w, size_t need, size_t pin_need, const char *dev_oom)
+{
+    if (w.dev_bytes < need) {
+        if (w.dev) (void)hipFree(w.dev);
+        w.dev = nullptr; w.dev_bytes = 0;
+        const size_t want = need + need / 4;
+        if (hipMalloc(&w.dev, want) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, RAWDTW_ERR_OOM, dev_oom); }
+        w.dev_bytes = want;
+    }
+    if (w.pin_bytes < pin_need) {
+        if (w.pin) (void)hipHostFree(w.pin);
+        w.pin = nullptr; w.pin_bytes = 0;
+        const size_t want = pin_need + pin_need / 4;
+        if (hipHostMalloc(reinterpret_cast<void **>(&w.pin), want, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError(); w.pin = nullptr;
+            return fail(ctx, RAWDTW_ERR_OOM, "pinned allocation failed");
+        }
+        w.pin_bytes = want;
+    }
+    if (!w.ev0) HIP_TRY(ctx, hipEventCreate(&w.ev0));
+    if (!w.ev1) HIP_TRY(ctx, hipEventCreate(&w.ev1));
+    if (!w.done) HIP_TRY(ctx, hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
+    return RAWDTW_OK;
+}
+
+void blocks_release(WsBlocks &w)
+{
+    if (w.dev) (void)hipFree(w.dev);
+    if (w.pin) (void)hipHostFree(w.pin);
+    for (hipEvent_t e : {w.ev0, w.ev1, w.done}) if (e) (void)hipEventDestroy(e);
+    w = WsBlocks{};
+}
+
+void *device_view(void *p, size_t bytes)
+{
+    if (!p) return nullptr;
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (at.type != hipMemoryTypeHost || !at.devicePointer) return nullptr;
+    hipDeviceptr_t start = nullptr;
+    size_t size = 0;
+    if (hipPointerGetAttribute(&start, HIP_POINTER_ATTRIBUTE_RANGE_START_ADDR, p) != hipSuccess ||
+        hipPointerGetAttribute(&size, HIP_POINTER_ATTRIBUTE_RANGE_SIZE, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    const char *s = static_cast<const char *>(start), *q = static_cast<const char *>(p);
+    if (q < s || (size_t)(q - s) > size || size - (size_t)(q - s) < bytes) return nullptr;
+    return at.devicePointer;
+}
+} }

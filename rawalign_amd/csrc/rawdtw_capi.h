@@ -279,6 +279,22 @@ inline int hip_fail(rawdtw_ctx *ctx, hipError_t e, const char *what)
     return fail(ctx, st, std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// The grow-only blocks of a begin / end workspace (rawdtw_seed.hip, rawdtw_events.hip): a device block, a page-locked host block in
+// 8-byte words, the event pair around the launches and the event behind what comes home.
+struct WsBlocks {
+    void *dev = nullptr;
+    size_t dev_bytes = 0;
+    uint64_t *pin = nullptr;
+    size_t pin_bytes = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, done = nullptr;
+};
+// both blocks grown to at least need / pin_need bytes (a quarter more when they grow; contents are not kept), the events created on first use
+int blocks_reserve(rawdtw_ctx *ctx, WsBlocks &w, size_t need, size_t pin_need, const char *dev_oom);
+void blocks_release(WsBlocks &w);
+// the device address of a page-locked host array of `bytes` bytes, or null: null itself, pageable memory, or an allocation that does
+// not extend that far (the array is then copied by the caller's _end)
+void *device_view(void *p, size_t bytes);
+
 void chain_ws_free(rawdtw_ctx *ctx); // rawdtw_chain.hip
 void detect_ws_free(rawdtw_ctx *ctx); // rawdtw_events.hip
 void seed_ws_free(rawdtw_ctx *ctx);   // rawdtw_seed.hip

@@ -411,12 +411,7 @@ __global__ __launch_bounds__(64) void k_raw_compact(RawArgs a)
     }
 }
 
-struct DetectWs {
-    void *dev = nullptr;
-    size_t dev_bytes = 0;
-    uint64_t *pin = nullptr; // [0] the total; then the rebased offsets
-    size_t pin_bytes = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, done = nullptr;
+struct DetectWs : capi::WsBlocks { // (pin: [0] the total; then the rebased offsets)
     // a detection begun and not ended
     bool pending = false, direct_off = false, direct_ev = false;
     uint32_t n = 0;
@@ -446,25 +441,6 @@ struct Input {
     const uint64_t *dst_start = nullptr;
     const uint32_t *room = nullptr;
 };
-
-// the device address of a page-locked host array of `bytes` bytes, or null (pageable memory, or an allocation that does not
-// extend that far: then the array is copied in rawdtw_detect_end)
-void *device_view(void *p, size_t bytes)
-{
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    if (at.type != hipMemoryTypeHost || !at.devicePointer) return nullptr;
-    hipDeviceptr_t start = nullptr;
-    size_t size = 0;
-    if (hipPointerGetAttribute(&start, HIP_POINTER_ATTRIBUTE_RANGE_START_ADDR, p) != hipSuccess ||
-        hipPointerGetAttribute(&size, HIP_POINTER_ATTRIBUTE_RANGE_SIZE, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    const char *s = static_cast<const char *>(start), *q = static_cast<const char *>(p);
-    if (q < s || (size_t)(q - s) > size || size - (size_t)(q - s) < bytes) return nullptr;
-    return at.devicePointer;
-}
 
 } // namespace
 } // namespace rawdtw
@@ -498,28 +474,9 @@ int detect_enqueue(rawdtw_ctx *ctx, const rawdtw_event_opt_t &o, uint32_t n_chun
     if (!ctx->detect_ws) ctx->detect_ws = new (std::nothrow) rawdtw_detect_ws;
     if (!ctx->detect_ws) return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed");
     DetectWs &w = ctx->detect_ws->w;
-    if (w.dev_bytes < need) {
-        if (w.dev) (void)hipFree(w.dev);
-        w.dev = nullptr; w.dev_bytes = 0;
-        const size_t want = need + need / 4;
-        if (hipMalloc(&w.dev, want) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, RAWDTW_ERR_OOM, "detection workspace allocation failed"); }
-        w.dev_bytes = want;
-    }
     // (a resident detection: behind the offsets the places and the room going up, the counts and s_len coming home)
     const size_t pin_need = arena ? (4 * n + 4) * 8 : (n + 2) * 8;
-    if (w.pin_bytes < pin_need) {
-        if (w.pin) (void)hipHostFree(w.pin);
-        w.pin = nullptr; w.pin_bytes = 0;
-        const size_t want = pin_need + pin_need / 4;
-        if (hipHostMalloc(reinterpret_cast<void **>(&w.pin), want, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError(); w.pin = nullptr;
-            return fail(ctx, RAWDTW_ERR_OOM, "pinned allocation failed");
-        }
-        w.pin_bytes = want;
-    }
-    if (!w.ev0) HIP_TRY(ctx, hipEventCreate(&w.ev0));
-    if (!w.ev1) HIP_TRY(ctx, hipEventCreate(&w.ev1));
-    if (!w.done) HIP_TRY(ctx, hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
+    if (const int st = blocks_reserve(ctx, w, need, pin_need, "detection workspace allocation failed")) return st;
     w.pending = true; w.n = n_chunks; w.n_samples = N; w.cap = events_cap;
     w.h_eoff = event_off; w.h_ev = events; w.h_slen = in.s_len;
     w.direct_off = w.direct_ev = w.direct_slen = false;
@@ -761,10 +718,7 @@ bool detect_resident_view(const rawdtw_ctx *ctx, DetectView *v)
 void detect_ws_free(rawdtw_ctx *ctx)
 {
     if (!ctx || !ctx->detect_ws) return;
-    DetectWs &w = ctx->detect_ws->w;
-    if (w.dev) (void)hipFree(w.dev);
-    if (w.pin) (void)hipHostFree(w.pin);
-    for (hipEvent_t e : {w.ev0, w.ev1, w.done}) if (e) (void)hipEventDestroy(e);
+    blocks_release(ctx->detect_ws->w);
     delete ctx->detect_ws;
     ctx->detect_ws = nullptr;
 }

@@ -1023,6 +1023,19 @@ struct Round {
         });
         m->timing[4] += now_ms() - t0;
     }
+
+    // The round itself: the reads dealt, every group's first half (`begin`: with device chaining every group's is begun before the first is
+    // ended), the chains home, each group's round end (group gi's while group gi + 1's batch is on the device), then the one commit point.
+    template <typename Begin> int run(Begin begin)
+    {
+        deal();
+        for (uint32_t gi = 0; gi < G && ok(); gi++) begin(gi);
+        for (uint32_t gi = 0; gi < G; gi++) end_device_chain(gi);
+        for (uint32_t gi = 0; gi < G; gi++) fetch_and_end(gi);
+        if (!ok()) return rollback();
+        commit();
+        return RAWDTW_OK;
+    }
 };
 
 } // namespace
@@ -1210,13 +1223,7 @@ int rawdtw_mapper_round(rawdtw_mapper *m, uint32_t n_reads, const uint32_t *read
     const int chk = check_round(m, n_reads, read_ids, event_off, hit_off, hits);
     if (chk != RAWDTW_OK) return chk;
     Round r{m, n_reads, read_ids, event_off, events, hit_off, hits, t0};
-    r.deal();
-    for (uint32_t gi = 0; gi < r.G && r.ok(); gi++) r.begin_group(gi); // (with device chaining: every group's begun before the first is ended)
-    for (uint32_t gi = 0; gi < r.G; gi++) r.end_device_chain(gi);
-    for (uint32_t gi = 0; gi < r.G; gi++) r.fetch_and_end(gi);         // (group gi's round end while group gi + 1's batch is on the device)
-    if (!r.ok()) return r.rollback();
-    r.commit();
-    return RAWDTW_OK;
+    return r.run([&r](uint32_t gi) { r.begin_group(gi); });
 }
 
 static bool minimizer_on_device(const rawdtw_ctx *ctx)
@@ -1225,16 +1232,31 @@ static bool minimizer_on_device(const rawdtw_ctx *ctx)
     return rawdtw_get_option(ctx, "seed_minimizer", &v) == RAWDTW_OK && v != 0;
 }
 
+// what every seeded round asks of its index: one that can be read (its parameters out) and holds the mapper's sequences
+static int seed_index_checks(rawdtw_mapper *m, const rawdtw_seed_index *six, rawdtw_seed_pars_t *pars)
+{
+    uint32_t six_seq = 0;
+    if (rawdtw_seed_index_info(six, &six_seq, nullptr, nullptr, nullptr, pars) != RAWDTW_OK) return RAWDTW_ERR_INVALID;
+    if (six_seq != m->seq_len.size()) return fail(m, RAWDTW_ERR_INVALID, "the seed index and the mapper hold different numbers of sequences");
+    return RAWDTW_OK;
+}
+
+// a resident round's preconditions (each entry refuses in its own words).  no_cigar: nothing may read the host's copy of a read's events
+// later either, which the --dtw-output-cigar traceback (rawdtw_mapper_finish) would
+static bool resident_round_ok(const rawdtw_mapper *m, const rawdtw_seed_pars_t &pars, bool no_cigar)
+{
+    return m->ctx && !m->scorer && m->opt.device_chain && m->groups.size() == 1 && (pars.w == 0 || minimizer_on_device(m->ctx)) &&
+           !(no_cigar && (m->opt.flag & 0x4));
+}
+
 // The seeding of gen_chains (rmap.cpp:364-391) in front of the round.  Everything the seeding touches is the mapper's own buffers:
 // the reads change only inside rawdtw_mapper_round, which runs on the finished hits or not at all.
 int rawdtw_mapper_round_seeded(rawdtw_mapper *m, const rawdtw_seed_index *six, uint32_t n_reads, const uint32_t *read_ids,
                                const uint64_t *event_off, const float *events)
 {
     if (!m || !six || (n_reads && (!read_ids || !event_off)) || (n_reads && event_off[n_reads] > event_off[0] && !events)) return RAWDTW_ERR_INVALID;
-    uint32_t six_seq = 0;
     rawdtw_seed_pars_t pars;
-    if (rawdtw_seed_index_info(six, &six_seq, nullptr, nullptr, nullptr, &pars) != RAWDTW_OK) return RAWDTW_ERR_INVALID;
-    if (six_seq != m->seq_len.size()) return fail(m, RAWDTW_ERR_INVALID, "the seed index and the mapper hold different numbers of sequences");
+    if (const int st = seed_index_checks(m, six, &pars)) return st;
     if (n_reads == 0) return RAWDTW_OK;
     const bool on_device = m->ctx && (pars.w == 0 || minimizer_on_device(m->ctx)); // (the minimizer sketch is the host's unless "seed_minimizer" is on)
     if (!seed_room(m, m->seed_off, (uint64_t)n_reads + 1)) return fail(m, RAWDTW_ERR_OOM, "no memory for the round's hit offsets");
@@ -1269,11 +1291,9 @@ int rawdtw_mapper_round_seeded_resident(rawdtw_mapper *m, const rawdtw_seed_inde
                                         const uint64_t *event_off, const float *events)
 {
     if (!m || !six || (n_reads && (!read_ids || !event_off)) || (n_reads && event_off[n_reads] > event_off[0] && !events)) return RAWDTW_ERR_INVALID;
-    uint32_t six_seq = 0;
     rawdtw_seed_pars_t pars;
-    if (rawdtw_seed_index_info(six, &six_seq, nullptr, nullptr, nullptr, &pars) != RAWDTW_OK) return RAWDTW_ERR_INVALID;
-    if (six_seq != m->seq_len.size()) return fail(m, RAWDTW_ERR_INVALID, "the seed index and the mapper hold different numbers of sequences");
-    if (!m->ctx || m->scorer || !m->opt.device_chain || m->groups.size() != 1 || (pars.w != 0 && !minimizer_on_device(m->ctx)))
+    if (const int st = seed_index_checks(m, six, &pars)) return st;
+    if (!resident_round_ok(m, pars, false))
         return fail(m, RAWDTW_ERR_UNSUPPORTED, "a resident round needs a context, device chaining, one read group, no external scorer and a w == 0 index, "
                                                "or a w > 0 one with the context's \"seed_minimizer\" option on (rawdtw_mapper_round_seeded maps the round)");
     if (n_reads == 0) return RAWDTW_OK;
@@ -1290,13 +1310,7 @@ int rawdtw_mapper_round_seeded_resident(rawdtw_mapper *m, const rawdtw_seed_inde
     // (seeding and chaining run on the device whether or not a DTW follows them: the round's arrays are the device path's, page-locked)
     r.on_device = true;
     r.events_in_place = event_off[n_reads] > 0 && rawdtw_host_is_page_locked(events) == 1;
-    r.deal();
-    r.resident_begin(0);
-    r.end_device_chain(0);
-    r.fetch_and_end(0);
-    if (!r.ok()) return r.rollback();
-    r.commit();
-    return RAWDTW_OK;
+    return r.run([&r](uint32_t gi) { r.resident_begin(gi); });
 }
 
 } // extern "C"
@@ -1312,13 +1326,11 @@ int round_from_signal(rawdtw_mapper *m, const rawdtw_seed_index *six, const rawd
 {
     if (!m || !six || (n_reads && (!read_ids || !off)) || (n_reads && off[n_reads] > off[0] && (is_raw ? !raw : !sig)) || (n_reads && is_raw && !chan))
         return m ? fail(m, RAWDTW_ERR_INVALID, "null argument") : RAWDTW_ERR_INVALID;
-    uint32_t six_seq = 0;
     rawdtw_seed_pars_t pars;
-    if (rawdtw_seed_index_info(six, &six_seq, nullptr, nullptr, nullptr, &pars) != RAWDTW_OK) return RAWDTW_ERR_INVALID;
-    if (six_seq != m->seq_len.size()) return fail(m, RAWDTW_ERR_INVALID, "the seed index and the mapper hold different numbers of sequences");
+    if (const int st = seed_index_checks(m, six, &pars)) return st;
     // rawdtw_mapper_round_seeded_resident's preconditions, and nothing may read the host's copy of a read's events later: that is the
-    // --dtw-output-cigar traceback (rawdtw_mapper_finish) and an external scorer.  A mapper with no DTW stage keeps the copy for neither.
-    if (!m->ctx || m->scorer || !m->opt.device_chain || m->groups.size() != 1 || (pars.w != 0 && !minimizer_on_device(m->ctx)) || (m->opt.flag & 0x4))
+    // --dtw-output-cigar traceback and an external scorer.  A mapper with no DTW stage keeps the copy for neither.
+    if (!resident_round_ok(m, pars, true))
         return fail(m, RAWDTW_ERR_UNSUPPORTED, "a round from signal needs a context, device chaining, one read group, no external scorer, no --dtw-output-cigar "
                                                "and a w == 0 index, or a w > 0 one with the context's \"seed_minimizer\" option on "
                                                "(rawdtw_detect_raw_begin + rawdtw_mapper_round_seeded_resident map the round)");
@@ -1371,12 +1383,7 @@ int round_from_signal(rawdtw_mapper *m, const rawdtw_seed_index *six, const rawd
     r.resident = true; r.signal = true;
     r.on_device = true; // (as rawdtw_mapper_round_seeded_resident)
     r.events_in_place = false;
-    r.deal();
-    r.signal_begin(0);
-    r.end_device_chain(0);
-    r.fetch_and_end(0);
-    if (!r.ok()) return r.rollback();
-    r.commit();
+    if (const int st = r.run([&r](uint32_t gi) { r.signal_begin(gi); })) return st;
     m->sig_rounds++;
     if (retried) m->sig_retried++;
     m->sig_sample_bytes += n_samples * (is_raw ? sizeof(int16_t) : sizeof(float)) * (retried ? 2 : 1);

@@ -35,8 +35,10 @@
 // arena, both copied on the device, and its workspace is sized by the detection's events_cap because no count has come home yet.
 // Its launches are instantiations of their own (kGuard) that do nothing when the detection's flag word says it declined -- the
 // offsets would then run past the workspace; the unguarded instantiations above never read that word.
+// All three kinds are enqueued by one function, seed_enqueue, over one workspace layout (rawdtw_seed_layout.h).
 #include "rawdtw_capi.h"
 #include "rawdtw_seed.h"
+#include "rawdtw_seed_layout.h"
 
 #pragma clang fp contract(off)
 
@@ -386,7 +388,7 @@ __global__ __launch_bounds__(64) void k_seed_write_chain(SeedArgs a, ChainDst d)
     }
 }
 
-struct SeedWs {
+struct SeedWs : capi::WsBlocks { // (the seeding's own blocks: where what lies, rawdtw_seed_layout.h)
     // the table (rawdtw_seed_index_upload)
     uint64_t table_serial = 0; // the uploaded index's serial (0: none): the same index again is not uploaded twice
     Slot *d_slots = nullptr;
@@ -394,14 +396,9 @@ struct SeedWs {
     uint32_t log2_slots = 0;
     rawdtw_seed_pars_t pars{};
     bool has_table = false;
-    // the seeding's own block
-    void *dev = nullptr;
-    size_t dev_bytes = 0;
     void *d_hits = nullptr; // only for a caller whose hits are pageable
     size_t hits_bytes = 0;
-    uint64_t *pin = nullptr; // [0] the total; then the rebased offsets
-    size_t pin_bytes = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, done = nullptr;
+    seed::Layout at; // of the seeding begun last
     // a seeding begun and not ended
     bool pending = false, direct_off = false, direct_hits = false;
     uint32_t n = 0;
@@ -411,32 +408,14 @@ struct SeedWs {
     const uint64_t *d_hoff = nullptr;
     // a resident seeding: begun (pending && resident), then ended and readable (ready) until the context's next seeding of either kind
     bool resident = false, ready = false;
-    bool enqueued = false;            // the resident seeding begun has work on the stream (its events are recorded)
-    const uint64_t *h_decl = nullptr; // a detected seeding: the detection's flag word as it came home (in `pin`); else null
-    SeedArgs ra{};                // the launches' arguments: where the retained words are
+    bool enqueued = false; // the resident seeding begun has work on the stream (its events are recorded)
+    SeedArgs ra{};         // the launches' arguments: where the retained words are
     uint64_t r_total = 0;
-    const uint64_t *r_hoff = nullptr; // n + 1 hit offsets, the library's own host copy (in `pin`)
 };
 
-// the device address of a page-locked host array of `bytes` bytes, or null (rawdtw_events.hip's rule: pageable memory, or an
-// allocation that does not extend that far, is copied in _end)
-void *device_view(void *p, size_t bytes)
-{
-    if (!p) return nullptr;
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    if (at.type != hipMemoryTypeHost || !at.devicePointer) return nullptr;
-    hipDeviceptr_t start = nullptr;
-    size_t size = 0;
-    if (hipPointerGetAttribute(&start, HIP_POINTER_ATTRIBUTE_RANGE_START_ADDR, p) != hipSuccess ||
-        hipPointerGetAttribute(&size, HIP_POINTER_ATTRIBUTE_RANGE_SIZE, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    const char *s = static_cast<const char *>(start), *q = static_cast<const char *>(p);
-    if (q < s || (size_t)(q - s) > size || size - (size_t)(q - s) < bytes) return nullptr;
-    return at.devicePointer;
-}
+// the layout's one consumer: a region of the device block, and of the pinned block (8-byte words)
+template <typename T> T *dev(const SeedWs &w, const seed::Region &r) { return reinterpret_cast<T *>(static_cast<char *>(w.dev) + r.at); }
+uint64_t *pinned(const SeedWs &w, const seed::Region &r) { return reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(w.pin) + r.at); }
 
 // filter -> (min) -> probe -> scan on `a`.  With w > 0 the filter's output goes to `mn`'s inputs and `a` is re-pointed at the sketch: the
 // launches behind (and whoever keeps `a`) see the sketch's elements where they saw the kept events.
@@ -473,6 +452,133 @@ SeedWs *ws_of(rawdtw_ctx *ctx)
 {
     if (!ctx->seed_ws) ctx->seed_ws = new (std::nothrow) rawdtw_seed_ws;
     return ctx->seed_ws ? &ctx->seed_ws->w : nullptr;
+}
+
+// what every begin refuses alike: the context's workspace, or null with the refusal in *st
+SeedWs *seedable(rawdtw_ctx *ctx, int *st)
+{
+    SeedWs *w = ctx->seed_ws ? &ctx->seed_ws->w : nullptr;
+    if (!w || !w->has_table) *st = fail(ctx, RAWDTW_ERR_INVALID, "no seed index on this context (rawdtw_seed_index_upload)");
+    else if (w->pending) *st = fail(ctx, RAWDTW_ERR_INVALID, "a seeding is begun on this context and not ended");
+    else if (w->pars.w && !ctx->seed_minimizer) *st = fail(ctx, RAWDTW_ERR_UNSUPPORTED, "the minimizer sketch (w > 0) is seeded on the host (rawdtw_seed_hits_host)");
+    else return w;
+    return nullptr;
+}
+
+// where a seeding's offsets, source starts and events come from, and where its results go
+struct Source {
+    seed::Kind kind;
+    uint32_t n = 0;  // chunks
+    uint64_t N = 0;  // the events the workspace is sized for
+    uint64_t *hit_off = nullptr;
+    // plain: the caller's arrays, uploaded; the hits written on the way
+    const uint64_t *event_off = nullptr;
+    const float *events = nullptr;
+    rawdtw_seed_hit_t *hits = nullptr;
+    uint64_t hits_cap = 0;
+    // resident: the caller's tables, uploaded; the events are in the arena
+    const uint64_t *ev_start = nullptr;
+    const uint32_t *ev_len = nullptr;
+    // detected: the detection's device arrays and flag word; the host has seen no count
+    DetectView det;
+};
+
+// Everything after an entry's own checks: the workspace, the state of a seeding begun, the upload (or the copies out of the detection's
+// workspace, so that the retained words do not depend on it), the launches and what comes home.
+int seed_enqueue(rawdtw_ctx *ctx, SeedWs &w, const Source &in)
+{
+    const bool plain = in.kind == seed::Kind::plain, detected = in.kind == seed::Kind::detected;
+    const uint64_t n = in.n, N = in.N;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    w.ready = false; w.resident = false; // (the workspace is this seeding's from here on: an ended resident seeding's words are gone)
+    const seed::Layout L = w.at = seed::layout(in.kind, n, N, w.pars.w != 0);
+    if (const int st = blocks_reserve(ctx, w, L.need, L.pin_need, "seeding workspace allocation failed")) return st;
+    uint64_t *dv_hoff = nullptr;
+    uint4 *dv_hits = nullptr;
+    if (plain) {
+        dv_hoff = static_cast<uint64_t *>(device_view(in.hit_off, (n + 1) * 8));
+        dv_hits = in.hits_cap ? static_cast<uint4 *>(device_view(in.hits, in.hits_cap * sizeof(rawdtw_seed_hit_t))) : nullptr;
+        if (n && N && in.hits_cap && !dv_hits && w.hits_bytes < in.hits_cap * sizeof(rawdtw_seed_hit_t)) {
+            if (w.d_hits) (void)hipFree(w.d_hits);
+            w.d_hits = nullptr; w.hits_bytes = 0;
+            if (hipMalloc(&w.d_hits, in.hits_cap * sizeof(rawdtw_seed_hit_t)) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(ctx, RAWDTW_ERR_OOM, "no device memory for hits_cap hits (page-locked hits need none)");
+            }
+            w.hits_bytes = in.hits_cap * sizeof(rawdtw_seed_hit_t);
+        }
+    }
+    uint64_t *const h_off = pinned(w, L.p_off); // (plain and resident: the dense offsets going up)
+    if (!plain) { // the tables going up; what comes home reads as zeros until it has
+        uint64_t *const h_src = pinned(w, L.p_src), *const h_hoff = pinned(w, L.p_hoff);
+        if (!detected) {
+            h_off[0] = 0;
+            for (uint64_t k = 0; k < n; k++) { h_off[k + 1] = h_off[k] + in.ev_len[k]; h_src[k] = in.ev_start[k]; }
+        }
+        for (uint64_t k = 0; k <= n; k++) h_hoff[k] = 0;
+        *pinned(w, L.p_tot) = *pinned(w, L.p_over) = 0;
+        if (detected) *pinned(w, L.p_decl) = 0;
+        w.r_total = 0; w.enqueued = false;
+    }
+    w.pending = true; w.resident = !plain; w.n = in.n; w.n_events = N; w.cap = in.hits_cap;
+    w.h_hoff = in.hit_off; w.h_hits = in.hits; w.direct_off = w.direct_hits = false;
+    if (n == 0 || (plain && N == 0)) return RAWDTW_OK; // (nothing to enqueue: the ends fill the zeros)
+    SeedArgs a{};
+    uint64_t *const d_off = dev<uint64_t>(w, L.off), *const d_src = plain ? nullptr : dev<uint64_t>(w, L.src);
+    a.off = d_off; a.src = d_src; a.ev = plain ? dev<float>(w, L.ev) : ctx->d_ev;
+    a.code = dev<uint32_t>(w, L.code); a.pos = dev<uint32_t>(w, L.pos); a.cnt = dev<uint32_t>(w, L.cnt); a.val = dev<uint64_t>(w, L.val);
+    a.kept = dev<uint32_t>(w, L.kept); a.chits = dev<uint64_t>(w, L.chits); a.hoff = dev<uint64_t>(w, L.hoff); a.tot = dev<uint64_t>(w, L.tot);
+    a.n = in.n; a.e = w.pars.e; a.q = w.pars.q; a.lq = w.pars.lq;
+    a.slots = w.d_slots; a.list = w.d_list; a.log2_slots = w.log2_slots;
+    a.decl = detected ? in.det.d_flag : nullptr;
+    MinArgs mn{};
+    if (w.pars.w) { // the filter's three arrays become k_seed_min's input; the sketch takes their place in `a`
+        mn = MinArgs{a.off, a.code, a.pos, a.kept, dev<uint32_t>(w, L.hash), dev<uint32_t>(w, L.spos), dev<uint32_t>(w, L.count), a.tot + 1,
+                     w.pars.e, w.pars.lq + 2, w.pars.w, a.decl};
+        a.code = mn.hash; a.pos = mn.pos; a.kept = mn.count;
+    }
+    w.d_hoff = a.hoff;
+    if (plain) {
+        for (uint64_t k = 0; k <= n; k++) h_off[k] = in.event_off[k] - in.event_off[0];
+        w.direct_off = dv_hoff != nullptr; w.direct_hits = dv_hits != nullptr;
+    } else { // what is kept (the sketch's words with w > 0) serves the unguarded k_seed_write / k_seed_write_chain, after an end that saw the flag clear
+        w.ra = a; w.ra.decl = nullptr;
+    }
+    hipStream_t s = ctx->stream;
+    auto undo = [&](int st) { w.pending = false; w.resident = false; return st; };
+    hipError_t e = hipSuccess;
+    if (!detected) {
+        if (hipMemcpyAsync(d_off, h_off, (n + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+            (plain ? hipMemcpyAsync(dev<float>(w, L.ev), in.events + in.event_off[0], N * 4, hipMemcpyHostToDevice, s)
+                   : hipMemcpyAsync(d_src, pinned(w, L.p_src), n * 8, hipMemcpyHostToDevice, s)) != hipSuccess ||
+            hipMemsetAsync(a.tot, 0, 32, s) != hipSuccess || hipEventRecord(w.ev0, s) != hipSuccess)
+            return undo(hip_fail(ctx, hipGetLastError(), "seeding upload"));
+        if (plain) launch_seeding<false>(a, mn, w.pars.w, s, dv_hoff);
+        else launch_seeding<true>(a, mn, w.pars.w, s, nullptr);
+        if (in.hits_cap) hipLaunchKernelGGL(k_seed_write, dim3(in.n), dim3(kW), 0, s, a, in.hits_cap, dv_hits ? dv_hits : static_cast<uint4 *>(w.d_hits));
+        e = hipGetLastError();
+    } else { // (ev0 in front of the copies)
+        if (hipEventRecord(w.ev0, s) != hipSuccess) return undo(hip_fail(ctx, hipGetLastError(), "seeding launches"));
+        if (!in.det.enqueued) { // the detection had no sample: every chunk is empty -- zero offsets, counts and hits for whoever reads them
+            e = hipMemsetAsync(w.dev, 0, L.need, s);
+        } else {
+            e = hipMemcpyAsync(d_off, in.det.d_eoff, (n + 1) * 8, hipMemcpyDeviceToDevice, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_src, in.det.d_dst, n * 8, hipMemcpyDeviceToDevice, s);
+            if (e == hipSuccess) e = hipMemsetAsync(a.tot, 0, 32, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(pinned(w, L.p_decl), in.det.d_flag, 8, hipMemcpyDeviceToHost, s);
+            if (e != hipSuccess) return undo(hip_fail(ctx, e, "seeding upload"));
+            launch_seeding<true, true>(a, mn, w.pars.w, s, nullptr);
+            e = hipGetLastError();
+        }
+    }
+    if (e == hipSuccess) e = hipEventRecord(w.ev1, s);
+    if (e == hipSuccess) // plain: the total and k_seed_min's overflow flag; resident: the hit offsets, then that flag alone
+        e = plain ? hipMemcpyAsync(pinned(w, L.p_tot), a.tot, 16, hipMemcpyDeviceToHost, s) : hipMemcpyAsync(pinned(w, L.p_hoff), a.hoff, (n + 1) * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && !plain) e = hipMemcpyAsync(pinned(w, L.p_over), a.tot + 1, 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipEventRecord(w.done, s);
+    if (e != hipSuccess) return undo(hip_fail(ctx, e, "seeding launches"));
+    if (!plain) w.enqueued = true;
+    return RAWDTW_OK;
 }
 
 } // namespace
@@ -515,96 +621,13 @@ int rawdtw_seed_begin(rawdtw_ctx *ctx, uint32_t n_chunks, const uint64_t *event_
     for (uint32_t k = 0; k < n_chunks; k++)
         if (event_off[k + 1] < event_off[k] || event_off[k + 1] - event_off[k] > 0xffffffffull)
             return fail(ctx, RAWDTW_ERR_INVALID, "a chunk of 2^32 events or more, or offsets that descend");
-    const uint64_t n = n_chunks, N = n ? event_off[n] - event_off[0] : 0;
-    if ((N && !events) || (hits_cap && !hits)) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
-    SeedWs *wp = ctx->seed_ws ? &ctx->seed_ws->w : nullptr;
-    if (!wp || !wp->has_table) return fail(ctx, RAWDTW_ERR_INVALID, "no seed index on this context (rawdtw_seed_index_upload)");
-    SeedWs &w = *wp;
-    if (w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "a seeding is begun on this context and not ended");
-    if (w.pars.w && !ctx->seed_minimizer) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, "the minimizer sketch (w > 0) is seeded on the host (rawdtw_seed_hits_host)");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    w.ready = false; w.resident = false; // (the workspace is this seeding's from here on: an ended resident seeding's words are gone)
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    // offsets, events, codes, positions, counts (4 bytes an event each) and list words (8): 24 bytes an event; with w > 0 the sketch's
-    // hashes and positions as well: 32
-    const size_t b_off = al((n + 1) * 8), b_ev = al(N * 4), b_val = al(N * 8), b_cnt = al(n * 4), b_tot = al(32);
-    const size_t need = 3 * b_off + 4 * b_ev + b_val + b_cnt + b_tot + (w.pars.w ? 2 * b_ev + b_cnt : 0);
-    if (w.dev_bytes < need) {
-        if (w.dev) (void)hipFree(w.dev);
-        w.dev = nullptr; w.dev_bytes = 0;
-        const size_t want = need + need / 4;
-        if (hipMalloc(&w.dev, want) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, RAWDTW_ERR_OOM, "seeding workspace allocation failed"); }
-        w.dev_bytes = want;
-    }
-    const size_t pin_need = (n + 3) * 8;
-    if (w.pin_bytes < pin_need) {
-        if (w.pin) (void)hipHostFree(w.pin);
-        w.pin = nullptr; w.pin_bytes = 0;
-        const size_t want = pin_need + pin_need / 4;
-        if (hipHostMalloc(reinterpret_cast<void **>(&w.pin), want, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError(); w.pin = nullptr;
-            return fail(ctx, RAWDTW_ERR_OOM, "pinned allocation failed");
-        }
-        w.pin_bytes = want;
-    }
-    uint64_t *dv_hoff = static_cast<uint64_t *>(device_view(hit_off, (n + 1) * 8));
-    uint4 *dv_hits = hits_cap ? static_cast<uint4 *>(device_view(hits, hits_cap * sizeof(rawdtw_seed_hit_t))) : nullptr;
-    if (n && N && hits_cap && !dv_hits && w.hits_bytes < hits_cap * sizeof(rawdtw_seed_hit_t)) {
-        if (w.d_hits) (void)hipFree(w.d_hits);
-        w.d_hits = nullptr; w.hits_bytes = 0;
-        if (hipMalloc(&w.d_hits, hits_cap * sizeof(rawdtw_seed_hit_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ctx, RAWDTW_ERR_OOM, "no device memory for hits_cap hits (page-locked hits need none)");
-        }
-        w.hits_bytes = hits_cap * sizeof(rawdtw_seed_hit_t);
-    }
-    if (!w.ev0) HIP_TRY(ctx, hipEventCreate(&w.ev0));
-    if (!w.ev1) HIP_TRY(ctx, hipEventCreate(&w.ev1));
-    if (!w.done) HIP_TRY(ctx, hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
-    w.pending = true; w.n = n_chunks; w.n_events = N; w.cap = hits_cap;
-    w.h_hoff = hit_off; w.h_hits = hits;
-    w.direct_off = w.direct_hits = false;
-    if (n == 0 || N == 0) return RAWDTW_OK; // (nothing to enqueue: rawdtw_seed_end fills the zeros)
-    char *p = static_cast<char *>(w.dev);
-    SeedArgs a{};
-    uint64_t *d_off = reinterpret_cast<uint64_t *>(p); p += b_off;
-    float *d_ev = reinterpret_cast<float *>(p); p += b_ev;
-    a.code = reinterpret_cast<uint32_t *>(p); p += b_ev;
-    a.pos = reinterpret_cast<uint32_t *>(p); p += b_ev;
-    a.cnt = reinterpret_cast<uint32_t *>(p); p += b_ev;
-    a.val = reinterpret_cast<uint64_t *>(p); p += b_val;
-    a.kept = reinterpret_cast<uint32_t *>(p); p += b_cnt;
-    a.chits = reinterpret_cast<uint64_t *>(p); p += b_off;
-    a.hoff = reinterpret_cast<uint64_t *>(p); p += b_off;
-    a.tot = reinterpret_cast<uint64_t *>(p); p += b_tot;
-    a.off = d_off; a.ev = d_ev; a.n = n_chunks;
-    a.e = w.pars.e; a.q = w.pars.q; a.lq = w.pars.lq;
-    a.slots = w.d_slots; a.list = w.d_list; a.log2_slots = w.log2_slots;
-    MinArgs mn{};
-    if (w.pars.w) { // the filter's three arrays become k_seed_min's input; the sketch takes their place in `a`
-        mn = MinArgs{d_off, a.code, a.pos, a.kept, nullptr, nullptr, nullptr, a.tot + 1, w.pars.e, w.pars.lq + 2, w.pars.w};
-        mn.hash = a.code = reinterpret_cast<uint32_t *>(p); p += b_ev;
-        mn.pos = a.pos = reinterpret_cast<uint32_t *>(p); p += b_ev;
-        mn.count = a.kept = reinterpret_cast<uint32_t *>(p);
-    }
-    uint64_t *h_off = w.pin + 2;
-    for (uint64_t k = 0; k <= n; k++) h_off[k] = event_off[k] - event_off[0];
-    w.direct_off = dv_hoff != nullptr; w.direct_hits = dv_hits != nullptr;
-    w.d_hoff = a.hoff;
-    hipStream_t s = ctx->stream;
-    auto undo = [&](int st) { w.pending = false; return st; };
-    if (hipMemcpyAsync(d_off, h_off, (n + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(d_ev, events + event_off[0], N * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemsetAsync(a.tot, 0, 32, s) != hipSuccess || hipEventRecord(w.ev0, s) != hipSuccess)
-        return undo(hip_fail(ctx, hipGetLastError(), "seeding upload"));
-    launch_seeding<false>(a, mn, w.pars.w, s, dv_hoff);
-    if (hits_cap) hipLaunchKernelGGL(k_seed_write, dim3(n_chunks), dim3(kW), 0, s, a, hits_cap, dv_hits ? dv_hits : static_cast<uint4 *>(w.d_hits));
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipEventRecord(w.ev1, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(w.pin, a.tot, 16, hipMemcpyDeviceToHost, s); // ([1]: k_seed_min's overflow flag)
-    if (e == hipSuccess) e = hipEventRecord(w.done, s);
-    if (e != hipSuccess) return undo(hip_fail(ctx, e, "seeding launches"));
-    return RAWDTW_OK;
+    Source in{seed::Kind::plain, n_chunks, n_chunks ? event_off[n_chunks] - event_off[0] : 0, hit_off};
+    if ((in.N && !events) || (hits_cap && !hits)) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    int st = RAWDTW_OK;
+    SeedWs *w = seedable(ctx, &st);
+    if (!w) return st;
+    in.event_off = event_off; in.events = events; in.hits = hits; in.hits_cap = hits_cap;
+    return seed_enqueue(ctx, *w, in);
 }
 
 int rawdtw_seed_end(rawdtw_ctx *ctx, float *kernel_ms)
@@ -622,13 +645,13 @@ int rawdtw_seed_end(rawdtw_ctx *ctx, float *kernel_ms)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     HIP_TRY(ctx, hipEventSynchronize(w.done)); // (the seeding's own work: what the caller enqueued behind it goes on)
-    const uint64_t tot = w.pin[0];
+    const uint64_t tot = *pinned(w, w.at.p_tot);
     if (!w.direct_off) {
         HIP_TRY(ctx, hipMemcpyAsync(w.h_hoff, w.d_hoff, ((uint64_t)w.n + 1) * 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(ctx, hipStreamSynchronize(s));
     }
     if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, w.ev0, w.ev1));
-    if (w.pin[1]) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, kOverflow); // (no hit was written)
+    if (*pinned(w, w.at.p_over)) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, kOverflow); // (no hit was written)
     if (tot > w.cap) return fail(ctx, RAWDTW_ERR_RANGE, "hits_cap is below the round's hits (hit_off is filled)");
     if (!w.direct_hits && tot) {
         HIP_TRY(ctx, hipMemcpyAsync(w.h_hits, w.d_hits, tot * sizeof(rawdtw_seed_hit_t), hipMemcpyDeviceToHost, s));
@@ -643,95 +666,17 @@ int rawdtw_seed_resident_begin(rawdtw_ctx *ctx, uint32_t n_chunks, const uint64_
     if (!ctx) return RAWDTW_ERR_INVALID;
     if (!hit_off || (n_chunks && (!ev_start || !ev_len))) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
     if (n_chunks >= 0x7fffffffu) return fail(ctx, RAWDTW_ERR_INVALID, "2^31 chunks or more");
-    SeedWs *wp = ctx->seed_ws ? &ctx->seed_ws->w : nullptr;
-    if (!wp || !wp->has_table) return fail(ctx, RAWDTW_ERR_INVALID, "no seed index on this context (rawdtw_seed_index_upload)");
-    SeedWs &w = *wp;
-    if (w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "a seeding is begun on this context and not ended");
-    if (w.pars.w && !ctx->seed_minimizer) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, "the minimizer sketch (w > 0) is seeded on the host (rawdtw_seed_hits_host)");
-    const uint64_t n = n_chunks;
-    uint64_t N = 0;
-    for (uint64_t k = 0; k < n; k++) {
+    int st = RAWDTW_OK;
+    SeedWs *w = seedable(ctx, &st);
+    if (!w) return st;
+    Source in{seed::Kind::resident, n_chunks, 0, hit_off};
+    for (uint32_t k = 0; k < n_chunks; k++) {
         if (ev_len[k] && (!ctx->d_ev || ev_start[k] > ctx->n_ev || ctx->n_ev - ev_start[k] < ev_len[k]))
             return fail(ctx, RAWDTW_ERR_RANGE, "a chunk outside the context's event arena");
-        N += ev_len[k];
+        in.N += ev_len[k];
     }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    w.ready = false; w.resident = false;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    // as rawdtw_seed_begin's block without the events: offsets, source starts, codes, positions, counts (4 bytes an event each), list words (8);
-    // with w > 0 the sketch's hashes and positions as well
-    const size_t b_off = al((n + 1) * 8), b_ev = al(N * 4), b_val = al(N * 8), b_cnt = al(n * 4), b_tot = al(32);
-    const size_t need = 4 * b_off + 3 * b_ev + b_val + b_cnt + b_tot + (w.pars.w ? 2 * b_ev + b_cnt : 0);
-    if (w.dev_bytes < need) {
-        if (w.dev) (void)hipFree(w.dev);
-        w.dev = nullptr; w.dev_bytes = 0;
-        const size_t want = need + need / 4;
-        if (hipMalloc(&w.dev, want) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, RAWDTW_ERR_OOM, "seeding workspace allocation failed"); }
-        w.dev_bytes = want;
-    }
-    // pinned: [0] the total; the dense offsets and the source starts going up; the hit offsets coming home
-    const size_t pin_need = (3 * (n + 1) + 4) * 8;
-    if (w.pin_bytes < pin_need) {
-        if (w.pin) (void)hipHostFree(w.pin);
-        w.pin = nullptr; w.pin_bytes = 0;
-        const size_t want = pin_need + pin_need / 4;
-        if (hipHostMalloc(reinterpret_cast<void **>(&w.pin), want, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError(); w.pin = nullptr;
-            return fail(ctx, RAWDTW_ERR_OOM, "pinned allocation failed");
-        }
-        w.pin_bytes = want;
-    }
-    if (!w.ev0) HIP_TRY(ctx, hipEventCreate(&w.ev0));
-    if (!w.ev1) HIP_TRY(ctx, hipEventCreate(&w.ev1));
-    if (!w.done) HIP_TRY(ctx, hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
-    uint64_t *h_off = w.pin + 2, *h_src = h_off + (n + 1), *h_hoff = h_src + (n + 1);
-    h_off[0] = 0;
-    for (uint64_t k = 0; k < n; k++) { h_off[k + 1] = h_off[k] + ev_len[k]; h_src[k] = ev_start[k]; }
-    for (uint64_t k = 0; k <= n; k++) h_hoff[k] = 0;
-    w.pin[0] = w.pin[1] = 0;
-    w.pending = true; w.resident = true; w.n = n_chunks; w.n_events = N; w.cap = 0;
-    w.h_hoff = hit_off; w.h_hits = nullptr; w.direct_off = w.direct_hits = false;
-    w.r_hoff = h_hoff; w.r_total = 0;
-    w.enqueued = false; w.h_decl = nullptr;
-    if (n == 0) return RAWDTW_OK; // (nothing to enqueue)
-    char *p = static_cast<char *>(w.dev);
-    SeedArgs a{};
-    uint64_t *d_off = reinterpret_cast<uint64_t *>(p); p += b_off;
-    uint64_t *d_src = reinterpret_cast<uint64_t *>(p); p += b_off;
-    a.code = reinterpret_cast<uint32_t *>(p); p += b_ev;
-    a.pos = reinterpret_cast<uint32_t *>(p); p += b_ev;
-    a.cnt = reinterpret_cast<uint32_t *>(p); p += b_ev;
-    a.val = reinterpret_cast<uint64_t *>(p); p += b_val;
-    a.kept = reinterpret_cast<uint32_t *>(p); p += b_cnt;
-    a.chits = reinterpret_cast<uint64_t *>(p); p += b_off;
-    a.hoff = reinterpret_cast<uint64_t *>(p); p += b_off;
-    a.tot = reinterpret_cast<uint64_t *>(p); p += b_tot;
-    a.off = d_off; a.src = d_src; a.ev = ctx->d_ev; a.n = n_chunks;
-    a.e = w.pars.e; a.q = w.pars.q; a.lq = w.pars.lq;
-    a.slots = w.d_slots; a.list = w.d_list; a.log2_slots = w.log2_slots;
-    MinArgs mn{};
-    if (w.pars.w) { // (as in rawdtw_seed_begin)
-        mn = MinArgs{d_off, a.code, a.pos, a.kept, nullptr, nullptr, nullptr, a.tot + 1, w.pars.e, w.pars.lq + 2, w.pars.w};
-        mn.hash = a.code = reinterpret_cast<uint32_t *>(p); p += b_ev;
-        mn.pos = a.pos = reinterpret_cast<uint32_t *>(p); p += b_ev;
-        mn.count = a.kept = reinterpret_cast<uint32_t *>(p);
-    }
-    w.ra = a; w.d_hoff = a.hoff; // (the retained words are the sketch's)
-    hipStream_t s = ctx->stream;
-    auto undo = [&](int st) { w.pending = false; w.resident = false; return st; };
-    if (hipMemcpyAsync(d_off, h_off, (n + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(d_src, h_src, n * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemsetAsync(a.tot, 0, 32, s) != hipSuccess || hipEventRecord(w.ev0, s) != hipSuccess)
-        return undo(hip_fail(ctx, hipGetLastError(), "seeding upload"));
-    launch_seeding<true>(a, mn, w.pars.w, s, nullptr);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipEventRecord(w.ev1, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_hoff, a.hoff, (n + 1) * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(w.pin + 1, a.tot + 1, 8, hipMemcpyDeviceToHost, s); // (k_seed_min's overflow flag)
-    if (e == hipSuccess) e = hipEventRecord(w.done, s);
-    if (e != hipSuccess) return undo(hip_fail(ctx, e, "seeding launches"));
-    w.enqueued = true;
-    return RAWDTW_OK;
+    in.ev_start = ev_start; in.ev_len = ev_len;
+    return seed_enqueue(ctx, *w, in);
 }
 
 // A resident seeding straight behind the context's resident detection: see the head of this file.
@@ -739,97 +684,14 @@ int rawdtw_seed_detected_begin(rawdtw_ctx *ctx, uint64_t *hit_off)
 {
     if (!ctx) return RAWDTW_ERR_INVALID;
     if (!hit_off) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
-    DetectView v;
-    if (!detect_resident_view(ctx, &v)) return fail(ctx, RAWDTW_ERR_INVALID, "no resident detection begun on this context and not ended");
-    SeedWs *wp = ctx->seed_ws ? &ctx->seed_ws->w : nullptr;
-    if (!wp || !wp->has_table) return fail(ctx, RAWDTW_ERR_INVALID, "no seed index on this context (rawdtw_seed_index_upload)");
-    SeedWs &w = *wp;
-    if (w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "a seeding is begun on this context and not ended");
-    if (w.pars.w && !ctx->seed_minimizer) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, "the minimizer sketch (w > 0) is seeded on the host (rawdtw_seed_hits_host)");
+    Source in{seed::Kind::detected, 0, 0, hit_off};
+    if (!detect_resident_view(ctx, &in.det)) return fail(ctx, RAWDTW_ERR_INVALID, "no resident detection begun on this context and not ended");
+    int st = RAWDTW_OK;
+    SeedWs *w = seedable(ctx, &st);
+    if (!w) return st;
     // the host has seen no count: room for as many events as the detection may write (its events_cap; never more than it has samples)
-    const uint64_t n = v.n, N = v.enqueued ? std::min(v.cap, v.n_samples) : 0;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    w.ready = false; w.resident = false;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t b_off = al((n + 1) * 8), b_ev = al(N * 4), b_val = al(N * 8), b_cnt = al(n * 4), b_tot = al(32); // (rawdtw_seed_resident_begin's block)
-    const size_t need = 4 * b_off + 3 * b_ev + b_val + b_cnt + b_tot + (w.pars.w ? 2 * b_ev + b_cnt : 0);
-    if (w.dev_bytes < need) {
-        if (w.dev) (void)hipFree(w.dev);
-        w.dev = nullptr; w.dev_bytes = 0;
-        const size_t want = need + need / 4;
-        if (hipMalloc(&w.dev, want) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, RAWDTW_ERR_OOM, "seeding workspace allocation failed"); }
-        w.dev_bytes = want;
-    }
-    const size_t pin_need = (3 * (n + 1) + 4) * 8; // (as a resident seeding's; the flag word lands behind the hit offsets)
-    if (w.pin_bytes < pin_need) {
-        if (w.pin) (void)hipHostFree(w.pin);
-        w.pin = nullptr; w.pin_bytes = 0;
-        const size_t want = pin_need + pin_need / 4;
-        if (hipHostMalloc(reinterpret_cast<void **>(&w.pin), want, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError(); w.pin = nullptr;
-            return fail(ctx, RAWDTW_ERR_OOM, "pinned allocation failed");
-        }
-        w.pin_bytes = want;
-    }
-    if (!w.ev0) HIP_TRY(ctx, hipEventCreate(&w.ev0));
-    if (!w.ev1) HIP_TRY(ctx, hipEventCreate(&w.ev1));
-    if (!w.done) HIP_TRY(ctx, hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
-    uint64_t *h_hoff = w.pin + 2 + 2 * (n + 1), *h_decl = h_hoff + (n + 1);
-    for (uint64_t k = 0; k <= n; k++) h_hoff[k] = 0;
-    w.pin[0] = w.pin[1] = 0; *h_decl = 0;
-    w.pending = true; w.resident = true; w.n = v.n; w.n_events = N; w.cap = 0;
-    w.h_hoff = hit_off; w.h_hits = nullptr; w.direct_off = w.direct_hits = false;
-    w.r_hoff = h_hoff; w.r_total = 0;
-    w.enqueued = false; w.h_decl = h_decl;
-    if (n == 0) return RAWDTW_OK; // (nothing to enqueue)
-    char *p = static_cast<char *>(w.dev);
-    SeedArgs a{};
-    uint64_t *d_off = reinterpret_cast<uint64_t *>(p); p += b_off;
-    uint64_t *d_src = reinterpret_cast<uint64_t *>(p); p += b_off;
-    a.code = reinterpret_cast<uint32_t *>(p); p += b_ev;
-    a.pos = reinterpret_cast<uint32_t *>(p); p += b_ev;
-    a.cnt = reinterpret_cast<uint32_t *>(p); p += b_ev;
-    a.val = reinterpret_cast<uint64_t *>(p); p += b_val;
-    a.kept = reinterpret_cast<uint32_t *>(p); p += b_cnt;
-    a.chits = reinterpret_cast<uint64_t *>(p); p += b_off;
-    a.hoff = reinterpret_cast<uint64_t *>(p); p += b_off;
-    a.tot = reinterpret_cast<uint64_t *>(p); p += b_tot;
-    a.off = d_off; a.src = d_src; a.ev = ctx->d_ev; a.n = v.n;
-    a.e = w.pars.e; a.q = w.pars.q; a.lq = w.pars.lq;
-    a.slots = w.d_slots; a.list = w.d_list; a.log2_slots = w.log2_slots;
-    a.decl = v.d_flag;
-    MinArgs mn{};
-    if (w.pars.w) { // (as in rawdtw_seed_begin)
-        mn = MinArgs{d_off, a.code, a.pos, a.kept, nullptr, nullptr, nullptr, a.tot + 1, w.pars.e, w.pars.lq + 2, w.pars.w, v.d_flag};
-        mn.hash = a.code = reinterpret_cast<uint32_t *>(p); p += b_ev;
-        mn.pos = a.pos = reinterpret_cast<uint32_t *>(p); p += b_ev;
-        mn.count = a.kept = reinterpret_cast<uint32_t *>(p);
-    }
-    hipStream_t s = ctx->stream;
-    auto undo = [&](int st) { w.pending = false; w.resident = false; return st; };
-    if (hipEventRecord(w.ev0, s) != hipSuccess) return undo(hip_fail(ctx, hipGetLastError(), "seeding launches"));
-    hipError_t e = hipSuccess;
-    if (!v.enqueued) { // the detection had no sample: every chunk is empty -- zero offsets, counts and hits for whoever reads them
-        e = hipMemsetAsync(w.dev, 0, need, s);
-    } else {
-        // the offsets and the places are copied out of the detection's workspace, so that the retained words do not depend on it
-        e = hipMemcpyAsync(d_off, v.d_eoff, (n + 1) * 8, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_src, v.d_dst, n * 8, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipMemsetAsync(a.tot, 0, 32, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(h_decl, v.d_flag, 8, hipMemcpyDeviceToHost, s);
-        if (e != hipSuccess) return undo(hip_fail(ctx, e, "seeding upload"));
-        launch_seeding<true, true>(a, mn, w.pars.w, s, nullptr);
-        e = hipGetLastError();
-    }
-    a.decl = nullptr; // (what is kept serves the unguarded k_seed_write / k_seed_write_chain, after an end that saw the flag clear)
-    w.ra = a; w.d_hoff = a.hoff;
-    if (e == hipSuccess) e = hipEventRecord(w.ev1, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_hoff, a.hoff, (n + 1) * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(w.pin + 1, a.tot + 1, 8, hipMemcpyDeviceToHost, s); // (k_seed_min's overflow flag)
-    if (e == hipSuccess) e = hipEventRecord(w.done, s);
-    if (e != hipSuccess) return undo(hip_fail(ctx, e, "seeding launches"));
-    w.enqueued = true;
-    return RAWDTW_OK;
+    in.n = in.det.n; in.N = in.det.enqueued ? std::min(in.det.cap, in.det.n_samples) : 0;
+    return seed_enqueue(ctx, *w, in);
 }
 
 int rawdtw_seed_resident_end(rawdtw_ctx *ctx, float *kernel_ms)
@@ -844,11 +706,12 @@ int rawdtw_seed_resident_end(rawdtw_ctx *ctx, float *kernel_ms)
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         HIP_TRY(ctx, hipEventSynchronize(w.done));
         if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, w.ev0, w.ev1));
-        if (w.h_decl && *w.h_decl) return fail(ctx, RAWDTW_ERR_RANGE, kDeclined); // (nothing written, nothing readable)
-        if (w.pin[1]) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, kOverflow); // (nothing written, nothing readable)
+        if (w.at.p_decl.bytes && *pinned(w, w.at.p_decl)) return fail(ctx, RAWDTW_ERR_RANGE, kDeclined); // (nothing written, nothing readable)
+        if (*pinned(w, w.at.p_over)) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, kOverflow); // (nothing written, nothing readable)
     }
-    for (uint64_t k = 0; k <= w.n; k++) w.h_hoff[k] = w.r_hoff[k];
-    w.r_total = w.r_hoff[w.n];
+    const uint64_t *const r_hoff = pinned(w, w.at.p_hoff); // (the library's own host copy)
+    for (uint64_t k = 0; k <= w.n; k++) w.h_hoff[k] = r_hoff[k];
+    w.r_total = r_hoff[w.n];
     w.ready = true;
     return RAWDTW_OK;
 }
@@ -888,7 +751,7 @@ const uint64_t *seed_resident_hit_off(const rawdtw_ctx *ctx, uint64_t *n_chunks)
     const SeedWs *w = ctx && ctx->seed_ws ? &ctx->seed_ws->w : nullptr;
     if (!w || !w->ready || w->pending) return nullptr;
     *n_chunks = w->n;
-    return w->r_hoff;
+    return pinned(*w, w->at.p_hoff);
 }
 
 void seed_resident_write_chain(rawdtw_ctx *ctx, rawdtw_seed_t *d_seeds, const uint64_t *d_seed_off, const uint64_t *d_prev_off, const rawdtw_seed_t *d_prev,
@@ -902,9 +765,8 @@ void seed_ws_free(rawdtw_ctx *ctx)
 {
     if (!ctx || !ctx->seed_ws) return;
     SeedWs &w = ctx->seed_ws->w;
-    for (void *p : {(void *)w.d_slots, (void *)w.d_list, w.dev, w.d_hits}) if (p) (void)hipFree(p);
-    if (w.pin) (void)hipHostFree(w.pin);
-    for (hipEvent_t e : {w.ev0, w.ev1, w.done}) if (e) (void)hipEventDestroy(e);
+    for (void *p : {(void *)w.d_slots, (void *)w.d_list, w.d_hits}) if (p) (void)hipFree(p);
+    blocks_release(w);
     delete ctx->seed_ws;
     ctx->seed_ws = nullptr;
 }

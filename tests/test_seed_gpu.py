@@ -339,3 +339,82 @@ def test_int16_windows_detected_seeded_and_mapped_on_one_context():
     finally:
         ea.close()
         eb.close()
+
+
+# ---- 8. plain, resident and detected seedings in turn on one context ------------------------------------------------------------------
+@pytest.mark.parametrize("w", [0, 5])
+def test_the_three_seedings_share_one_workspace(ref, w):
+    """The three begins (rawdtw_seed_begin, rawdtw_seed_resident_begin, rawdtw_seed_detected_begin) carve one grow-only workspace,
+    each its own way; here they follow one another on one context, growing and re-using it, every seeding against
+    rawdtw_seed_hits_host hit for hit -- and the rules between the kinds: a later seeding of any kind ends what an ended resident
+    one left readable, a begin refused by its own argument checks does not."""
+    from rawalign_amd.seeding import SeedParams
+
+    lib = ra.load_library()
+    si = SeedIndex.from_signals(ref.forward, ref.reverse, SeedParams(w=w), threads=4)
+    wins = [np.ascontiguousarray(sig[i:i + 1000], np.float32) for sig in mc.make_raw_reads() for i in range(0, len(sig) - 999, 1000)][:65]
+    evs = [ra.detect_events(x) for x in wins]   # (the host's detection: bit for bit what the device leaves in the arena)
+    slot = 1024
+    assert len(evs) == 65 and all(6 <= len(x) <= slot for x in evs)
+    starts = np.arange(65, dtype=np.uint64) * slot
+    vp = lambda a: a.ctypes.data  # noqa: E731
+
+    def host(chunks):
+        return seeding.seed_hits_host(si, *sc.flat(chunks), threads=8)
+
+    def fetch_fails(rs):
+        with pytest.raises(RawDTWError) as ei:
+            rs.fetch()
+        return ei.value.status
+
+    e = ra.Engine(0)
+    try:
+        if w:
+            e.set_option("seed_minimizer", 1)
+        e.upload_seed_index(si)
+        e.reserve_events(66 * slot)
+        # 1. plain, one chunk
+        off1, hits1 = host(evs[3:4])
+        assert len(hits1) > 0
+        got_off, got = e.seed_hits(*sc.flat(evs[3:4]))
+        assert np.array_equal(got_off, off1)
+        same_hits(got, hits1, "1 plain")
+        # 2. resident, 65 chunks of which one is empty: both blocks grow
+        chunks = list(evs)
+        chunks[7] = chunks[7][:0]
+        ev, off = sc.flat(chunks)
+        e.append_events(ev, off, starts.astype(np.uint32))
+        want_off, want = host(chunks)
+        rs = e.seed_resident(starts, np.array([len(c) for c in chunks], np.uint32))
+        assert np.array_equal(rs.hit_off, want_off) and len(want) > 65
+        same_hits(rs.fetch(), want, "2 resident")
+        # 3. detected, 64 windows behind a resident detection
+        sig = np.concatenate(wins[:64])
+        det = e.detect_resident(sig, np.arange(65, dtype=np.uint64) * 1000, starts[:64], np.full(64, slot, np.uint32), wait=False)
+        sd = e.seed_detected(det, wait=False)
+        ev_len, _, total = det.end()
+        assert ev_len.tolist() == [len(x) for x in evs[:64]] and total == sum(len(x) for x in evs[:64])
+        rs3 = sd.end()
+        want_off, want = host(evs[:64])
+        assert np.array_equal(rs3.hit_off, want_off)
+        same_hits(rs3.fetch(), want, "3 detected")
+        # 4. plain, three chunks without an event: nothing is enqueued, and step 3's hits are gone all the same
+        got_off, got = e.seed_hits(np.zeros(0, np.float32), np.zeros(4, np.uint64))
+        want_off, want = host([evs[0][:0]] * 3)
+        assert got_off.tolist() == want_off.tolist() == [0, 0, 0, 0] and len(got) == len(want) == 0
+        assert fetch_fails(rs3) == INVALID
+        # 5. resident, one chunk: what the detection left in slot 3 of the arena
+        rs5 = e.seed_resident(starts[3:4], np.array([len(evs[3])], np.uint32))
+        assert np.array_equal(rs5.hit_off, off1)
+        same_hits(rs5.fetch(), hits1, "5 resident")
+        # two begins refused by their own argument checks leave it readable
+        hoff = np.zeros(3, np.uint64)
+        outside, some = np.array([70 * slot], np.uint64), np.array([8], np.uint32)
+        assert lib.rawdtw_seed_resident_begin(e._ctx, 1, vp(outside), vp(some), vp(hoff)) == RANGE
+        descending, few, room = np.array([0, 5, 3], np.uint64), np.zeros(8, np.float32), np.zeros(8, HIT_DTYPE)
+        assert lib.rawdtw_seed_begin(e._ctx, 2, vp(descending), vp(few), vp(hoff), vp(room), 8) == INVALID
+        assert not hoff.any()
+        same_hits(rs5.fetch(), hits1, "5 after the refusals")
+        same_hits(rs5.fetch(pinned=False), hits1, "5 after the refusals, pageable")
+    finally:
+        e.close()
