@@ -30,9 +30,14 @@
 // Exactness: the library is built with -ffp-contract=off -fno-fast-math (and the pragma below says it again for this file);
 // the contracted form names its fused operations (__fmaf_rn, __fma_rn), fp32 division is __fdiv_rn, and f64 `/` and sqrt
 // lower to correctly rounded sequences on gfx950.  Denormals are not flushed.
+//
+// The host half (from DetectWs down): four begins share begin_checks and detect_enqueue, two ends share detect_end.  Where what lies in
+// the workspace's device block and page-locked block, and the names of tot's words, is rawdtw_events_layout.h.
 #include "rawdtw_capi.h"
 #include "rawdtw_events.h"
+#include "rawdtw_events_layout.h"
 
+#include <algorithm>
 #include <cfloat>
 
 #pragma clang fp contract(off)
@@ -411,25 +416,23 @@ __global__ __launch_bounds__(64) void k_raw_compact(RawArgs a)
     }
 }
 
-struct DetectWs : capi::WsBlocks { // (pin: [0] the total; then the rebased offsets)
+struct DetectWs : capi::WsBlocks { // (the detection's own blocks: where what lies, rawdtw_events_layout.h)
+    events::Layout at; // of the detection begun last
     // a detection begun and not ended
-    bool pending = false, direct_off = false, direct_ev = false;
+    bool pending = false, enqueued = false; // enqueued: it has work on the stream (else: no chunk, or no sample)
+    bool raw = false, arena = false;        // the raw entries; a resident detection
     uint32_t n = 0;
     uint64_t n_samples = 0, cap = 0;
+    // a plain detection: the caller's arrays, and which of them the device wrote itself
+    bool direct_off = false, direct_ev = false, direct_slen = false;
     uint64_t *h_eoff = nullptr;
     float *h_ev = nullptr;
-    const uint64_t *d_eoff = nullptr;
-    const float *d_ev = nullptr;
-    // the raw entry: s_len
-    bool direct_slen = false;
-    uint32_t *h_slen = nullptr;
-    const uint32_t *d_slen = nullptr;
-    // a resident detection: what comes home lands in `pin` (the counts, and the raw entry's s_len); what the seeding reads stays here
-    bool arena = false, enqueued = false, raw = false;
-    const uint64_t *h_off = nullptr;  // (pin) the rebased offsets
-    const uint32_t *h_nev = nullptr, *h_cnt = nullptr;
-    const uint64_t *d_dst = nullptr, *d_flag = nullptr;
+    uint32_t *h_slen = nullptr; // (the raw entry)
 };
+
+// the layout's consumers: a region of the device block, and of the pinned block
+template <typename T> T *dev(const DetectWs &w, const events::Region &r) { return reinterpret_cast<T *>(static_cast<char *>(w.dev) + r.at); }
+template <typename T> T *pinned(const DetectWs &w, const events::Region &r) { return reinterpret_cast<T *>(reinterpret_cast<char *>(w.pin) + r.at); }
 
 // what a detection reads: pA chunks (sig), or raw windows with a channel each
 struct Input {
@@ -438,6 +441,7 @@ struct Input {
     const rawdtw_channel_t *chan = nullptr;
     uint32_t *s_len = nullptr;
     // a resident detection: the chunks' places and room in the context's event arena
+    bool arena = false;
     const uint64_t *dst_start = nullptr;
     const uint32_t *room = nullptr;
 };
@@ -452,6 +456,22 @@ struct rawdtw_detect_ws { DetectWs w; };
 
 namespace {
 
+// What the four begins refuse alike, in this order; the options resolved into *o.  null_arg: one of the entry's own arguments is null.
+// The offsets' rule (check) and its sentence are the entry's.
+int begin_checks(rawdtw_ctx *ctx, bool null_arg, bool arena, const rawdtw_event_opt_t *opt, rawdtw_event_opt_t *o,
+                 int (*check)(uint32_t, const uint64_t *), uint32_t n_chunks, const uint64_t *off, const char *bad_offsets)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (null_arg) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    if (arena && !ctx->d_ev) return fail(ctx, RAWDTW_ERR_INVALID, "no event arena on this context (rawdtw_events_reserve, rawdtw_set_events_device)");
+    if (ctx->detect_ws && ctx->detect_ws->w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "a detection is begun on this context and not ended");
+    if (events::resolve_opt(opt, o) != RAWDTW_OK) return fail(ctx, RAWDTW_ERR_INVALID, "a window length above 65535");
+    if (check(n_chunks, off) != RAWDTW_OK) return fail(ctx, RAWDTW_ERR_INVALID, bad_offsets);
+    return RAWDTW_OK;
+}
+
+const char *const kBadRawOffsets = "a window of 2^32 raw samples or more, or offsets that descend";
+
 // everything after the entry's own checks: the workspace, the upload and the launches.  off: the caller's n + 1 offsets (of
 // samples, or of raw samples), N = off[n] - off[0].
 int detect_enqueue(rawdtw_ctx *ctx, const rawdtw_event_opt_t &o, uint32_t n_chunks, const uint64_t *off, const Input &in,
@@ -459,34 +479,22 @@ int detect_enqueue(rawdtw_ctx *ctx, const rawdtw_event_opt_t &o, uint32_t n_chun
 {
     if (n_chunks >= 0x7fffffffu) return fail(ctx, RAWDTW_ERR_INVALID, "2^31 chunks or more");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const bool is_raw = in.raw != nullptr, arena = in.dst_start != nullptr;
+    const bool is_raw = in.raw != nullptr, arena = in.arena;
     const uint64_t n = n_chunks, N = off[n] - off[0];
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t b_off = al((n + 1) * 8), b_sig = al(N * 4), b_ps = al((N + n) * 4), b_t = al(N * 4), b_cnt = al(n * 4), b_eoff = al((n + 1) * 8),
-                 b_tot = al(32);
-    // the raw entry's own: the samples as they came (8 more, which the last window's last load may touch), the raw offsets,
-    // the channels, s_len
-    const size_t b_raw = is_raw ? al(N * 2 + 16) : 0, b_roff = is_raw ? b_off : 0, b_chan = is_raw ? al(n * sizeof(rawdtw_channel_t)) : 0,
-                 b_slen = is_raw ? b_cnt : 0;
-    const size_t b_dst = arena ? b_off : 0, b_room = arena ? b_cnt : 0; // a resident detection's own: the places and the room
-    // sig, ps, pss, t1, t2, peaks, events: 28 bytes a sample (30 a raw sample)
-    const size_t need = b_off + b_sig + 2 * b_ps + 2 * b_t + b_t + 2 * b_cnt + b_eoff + b_tot + b_t + b_raw + b_roff + b_chan + b_slen + b_dst + b_room;
     if (!ctx->detect_ws) ctx->detect_ws = new (std::nothrow) rawdtw_detect_ws;
     if (!ctx->detect_ws) return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed");
     DetectWs &w = ctx->detect_ws->w;
-    // (a resident detection: behind the offsets the places and the room going up, the counts and s_len coming home)
-    const size_t pin_need = arena ? (4 * n + 4) * 8 : (n + 2) * 8;
-    if (const int st = blocks_reserve(ctx, w, need, pin_need, "detection workspace allocation failed")) return st;
+    const events::Layout L = events::layout(is_raw, arena, n, N);
+    if (const int st = blocks_reserve(ctx, w, L.need, L.pin_need, "detection workspace allocation failed")) return st;
+    w.at = L;
     w.pending = true; w.n = n_chunks; w.n_samples = N; w.cap = events_cap;
     w.h_eoff = event_off; w.h_ev = events; w.h_slen = in.s_len;
     w.direct_off = w.direct_ev = w.direct_slen = false;
     w.arena = arena; w.enqueued = false; w.raw = is_raw;
-    uint64_t *const h_off = w.pin + (arena ? 2 : 1);
-    uint64_t *const h_dst = h_off + (n + 1);
-    uint32_t *const h_room = reinterpret_cast<uint32_t *>(h_dst + n), *const h_nev = h_room + n, *const h_cnt = h_nev + n;
+    uint64_t *const h_off = pinned<uint64_t>(w, L.p_off), *const h_dst = pinned<uint64_t>(w, L.p_dst);
+    uint32_t *const h_room = pinned<uint32_t>(w, L.p_room);
     for (uint64_t k = 0; k <= n; k++) h_off[k] = off[k] - off[0];
-    if (arena) { // the tables are checked in the very copy that goes up
-        w.h_off = h_off; w.h_nev = h_nev; w.h_cnt = h_cnt;
+    if (arena) // the tables are checked in the very copy that goes up
         for (uint64_t k = 0; k < n; k++) {
             h_dst[k] = in.dst_start[k]; h_room[k] = in.room[k];
             if (h_dst[k] > ctx->n_ev || ctx->n_ev - h_dst[k] < h_room[k]) {
@@ -494,53 +502,40 @@ int detect_enqueue(rawdtw_ctx *ctx, const rawdtw_event_opt_t &o, uint32_t n_chun
                 return fail(ctx, RAWDTW_ERR_RANGE, "a chunk's stretch (dst_start + room) is beyond the context's event arena");
             }
         }
-    }
-    if (n == 0 || N == 0) return RAWDTW_OK; // (N == 0: every raw window is empty; rawdtw_detect_end fills the zeros)
-    char *p = static_cast<char *>(w.dev);
+    if (n == 0 || N == 0) return RAWDTW_OK; // (N == 0: every raw window is empty; the end fills the zeros)
     EvArgs a{};
-    uint64_t *d_off = reinterpret_cast<uint64_t *>(p); p += b_off;
-    float *d_sig = reinterpret_cast<float *>(p); p += b_sig;
-    a.ps = reinterpret_cast<float *>(p); p += b_ps;
-    a.pss = reinterpret_cast<float *>(p); p += b_ps;
-    a.t1 = reinterpret_cast<float *>(p); p += b_t;
-    a.t2 = reinterpret_cast<float *>(p); p += b_t;
-    a.peaks = reinterpret_cast<uint32_t *>(p); p += b_t;
-    a.npk = reinterpret_cast<uint32_t *>(p); p += b_cnt;
-    a.nev = reinterpret_cast<uint32_t *>(p); p += b_cnt;
-    a.eoff = reinterpret_cast<uint64_t *>(p); p += b_eoff;
-    a.tot = reinterpret_cast<uint64_t *>(p); p += b_tot;
-    a.ev = reinterpret_cast<float *>(p); p += b_t;
-    RawArgs r{};
-    int16_t *d_raw = reinterpret_cast<int16_t *>(p); p += b_raw;
-    uint64_t *d_roff = reinterpret_cast<uint64_t *>(p); p += b_roff;
-    rawdtw_channel_t *d_chan = reinterpret_cast<rawdtw_channel_t *>(p); p += b_chan;
-    r.cnt = reinterpret_cast<uint32_t *>(p); p += b_slen;
-    uint64_t *d_dst = reinterpret_cast<uint64_t *>(p); p += b_dst;
-    uint32_t *d_room = reinterpret_cast<uint32_t *>(p);
-    if (arena) { a.dst = d_dst; a.flag = a.tot + 2; w.d_dst = d_dst; w.d_flag = a.tot + 2; }
-    a.off = d_off; a.sig = d_sig; a.n = n_chunks; a.n_samples = N; a.opt = o;
-    a.n_dev = is_raw ? a.tot + 1 : nullptr;
+    uint64_t *const d_off = dev<uint64_t>(w, L.off), *const d_dst = dev<uint64_t>(w, L.dst);
+    float *const d_sig = dev<float>(w, L.sig);
+    uint32_t *const d_room = dev<uint32_t>(w, L.room);
+    a.off = d_off; a.sig = d_sig; a.ps = dev<float>(w, L.ps); a.pss = dev<float>(w, L.pss);
+    a.t1 = dev<float>(w, L.t1); a.t2 = dev<float>(w, L.t2); a.peaks = dev<uint32_t>(w, L.peaks);
+    a.npk = dev<uint32_t>(w, L.npk); a.nev = dev<uint32_t>(w, L.nev);
+    a.eoff = dev<uint64_t>(w, L.eoff); a.tot = dev<uint64_t>(w, L.tot); a.ev = dev<float>(w, L.ev);
+    a.n = n_chunks; a.n_samples = N; a.opt = o;
+    a.n_dev = is_raw ? a.tot + events::kTotSamples : nullptr;
+    if (arena) { a.dst = d_dst; a.flag = a.tot + events::kTotFlag; }
     uint64_t *dv_eoff = arena ? nullptr : static_cast<uint64_t *>(device_view(event_off, (n + 1) * 8));
     float *dv_ev = arena ? nullptr : static_cast<float *>(device_view(events, events_cap * 4));
     w.direct_off = dv_eoff != nullptr; w.direct_ev = dv_ev != nullptr;
-    w.d_eoff = a.eoff; w.d_ev = a.ev;
     hipStream_t s = ctx->stream;
     auto undo = [&](int st) { w.pending = false; return st; };
     if (arena && (hipMemcpyAsync(d_dst, h_dst, n * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
                   hipMemcpyAsync(d_room, h_room, n * 4, hipMemcpyHostToDevice, s) != hipSuccess))
         return undo(hip_fail(ctx, hipGetLastError(), "detection upload"));
     const uint32_t waves = (uint32_t)((n + kW - 1) / kW);
+    RawArgs r{};
     if (is_raw) {
-        r.roff = d_roff; r.raw = d_raw; r.chan = d_chan; r.off = d_off; r.sig = d_sig;
+        r.roff = dev<uint64_t>(w, L.roff); r.raw = dev<int16_t>(w, L.raw); r.chan = dev<rawdtw_channel_t>(w, L.chan);
+        r.cnt = dev<uint32_t>(w, L.slen); r.off = d_off; r.sig = d_sig;
         r.h_cnt = arena ? nullptr : static_cast<uint32_t *>(device_view(in.s_len, n * 4));
-        w.direct_slen = r.h_cnt != nullptr; w.d_slen = r.cnt;
-        if (hipMemcpyAsync(d_roff, h_off, (n + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(d_chan, in.chan, n * sizeof(rawdtw_channel_t), hipMemcpyHostToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(d_raw, in.raw + off[0], N * 2, hipMemcpyHostToDevice, s) != hipSuccess ||
+        w.direct_slen = r.h_cnt != nullptr;
+        if (hipMemcpyAsync(dev<uint64_t>(w, L.roff), h_off, (n + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(dev<rawdtw_channel_t>(w, L.chan), in.chan, n * sizeof(rawdtw_channel_t), hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(dev<int16_t>(w, L.raw), in.raw + off[0], N * 2, hipMemcpyHostToDevice, s) != hipSuccess ||
             hipEventRecord(w.ev0, s) != hipSuccess)
             return undo(hip_fail(ctx, hipGetLastError(), "detection upload"));
         hipLaunchKernelGGL(k_raw_count, dim3(n_chunks), dim3(kW), 0, s, r);
-        hipLaunchKernelGGL(k_ev_scan, dim3(1), dim3(1024), 0, s, r.cnt, n_chunks, d_off, a.tot + 1, (uint64_t *)nullptr);
+        hipLaunchKernelGGL(k_ev_scan, dim3(1), dim3(1024), 0, s, r.cnt, n_chunks, d_off, a.tot + events::kTotSamples, (uint64_t *)nullptr);
         hipLaunchKernelGGL(k_raw_compact, dim3(n_chunks), dim3(kW), 0, s, r);
     } else if (hipMemcpyAsync(d_off, h_off, (n + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
                hipMemcpyAsync(d_sig, in.sig + off[0], N * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
@@ -549,19 +544,19 @@ int detect_enqueue(rawdtw_ctx *ctx, const rawdtw_event_opt_t &o, uint32_t n_chun
     hipLaunchKernelGGL(k_ev_prefix, dim3(waves), dim3(kW), 0, s, a);
     hipLaunchKernelGGL(k_ev_tstat, dim3((uint32_t)((N + 255) / 256)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_ev_peaks, dim3(waves), dim3(kW), 0, s, a);
-    hipLaunchKernelGGL(k_ev_scan, dim3(1), dim3(1024), 0, s, a.nev, n_chunks, a.eoff, a.tot, dv_eoff);
+    hipLaunchKernelGGL(k_ev_scan, dim3(1), dim3(1024), 0, s, a.nev, n_chunks, a.eoff, a.tot + events::kTotEvents, dv_eoff);
     if (arena) {
-        hipLaunchKernelGGL(k_ev_room, dim3(1), dim3(1024), 0, s, a.nev, d_room, n_chunks, a.tot, events_cap, a.tot + 2);
+        hipLaunchKernelGGL(k_ev_room, dim3(1), dim3(1024), 0, s, a.nev, d_room, n_chunks, a.tot + events::kTotEvents, events_cap, a.tot + events::kTotFlag);
         hipLaunchKernelGGL(k_ev_events<true>, dim3(n_chunks), dim3(kW), 0, s, a, N, ctx->d_ev);
     } else
         hipLaunchKernelGGL(k_ev_events<false>, dim3(n_chunks), dim3(kW), 0, s, a, std::min<uint64_t>(events_cap, N), dv_ev);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipEventRecord(w.ev1, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(w.pin, a.tot, 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(pinned<uint64_t>(w, L.p_tot), a.tot + events::kTotEvents, 8, hipMemcpyDeviceToHost, s);
     if (arena) { // the flag, the counts and the raw entry's s_len: all that comes home
-        if (e == hipSuccess) e = hipMemcpyAsync(w.pin + 1, a.tot + 2, 8, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(h_nev, a.nev, n * 4, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && is_raw) e = hipMemcpyAsync(h_cnt, r.cnt, n * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(pinned<uint64_t>(w, L.p_flag), a.tot + events::kTotFlag, 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(pinned<uint32_t>(w, L.p_nev), a.nev, n * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && is_raw) e = hipMemcpyAsync(pinned<uint32_t>(w, L.p_cnt), r.cnt, n * 4, hipMemcpyDeviceToHost, s);
     }
     if (e == hipSuccess) e = hipEventRecord(w.done, s);
     if (e != hipSuccess) return undo(hip_fail(ctx, e, "detection launches"));
@@ -569,12 +564,65 @@ int detect_enqueue(rawdtw_ctx *ctx, const rawdtw_event_opt_t &o, uint32_t n_chun
     return RAWDTW_OK;
 }
 
-// what the two resident entries refuse alike, beyond their plain counterparts' rules
-int resident_checks(rawdtw_ctx *ctx, uint32_t n_chunks, const uint64_t *dst_start, const uint32_t *room)
+// a resident end's arrays (null: the plain end, whose arrays the begin took)
+struct ResidentOut {
+    uint32_t *s_len, *ev_len;
+    uint64_t *total;
+};
+
+// Both ends: the detection begun is of the end's kind, is ended, filled with zeros when nothing was enqueued, else waited for and
+// timed; then what came home goes to the caller's arrays.
+int detect_end(rawdtw_ctx *ctx, const ResidentOut *res, float *kernel_ms)
 {
-    if (n_chunks && (!dst_start || !room)) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
-    if (!ctx->d_ev) return fail(ctx, RAWDTW_ERR_INVALID, "no event arena on this context (rawdtw_events_reserve, rawdtw_set_events_device)");
-    if (ctx->detect_ws && ctx->detect_ws->w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "a detection is begun on this context and not ended");
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    DetectWs *const wp = ctx->detect_ws ? &ctx->detect_ws->w : nullptr;
+    if (!wp || !wp->pending || (res && !wp->arena))
+        return fail(ctx, RAWDTW_ERR_INVALID, res ? "no resident detection begun on this context" : "no detection begun on this context");
+    if (!res && wp->arena) return fail(ctx, RAWDTW_ERR_INVALID, "the detection begun on this context is a resident one (rawdtw_detect_resident_end)");
+    DetectWs &w = *wp;
+    if (res && (!res->total || (w.n && !res->ev_len))) return fail(ctx, RAWDTW_ERR_INVALID, "null argument"); // (the detection stays begun)
+    const uint64_t n = w.n;
+    uint32_t *const s_len = res ? res->s_len : w.h_slen;
+    w.pending = false;
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if (res) *res->total = 0;
+    if (!w.enqueued) { // no chunk, or no sample
+        if (res) std::fill_n(res->ev_len, n, 0u);
+        else std::fill_n(w.h_eoff, n + 1, (uint64_t)0);
+        if (s_len) std::fill_n(s_len, n, 0u);
+        return RAWDTW_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipEventSynchronize(w.done)); // (the detection's own work: what the caller enqueued behind it, a seeding for one, goes on)
+    if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, w.ev0, w.ev1));
+    const uint64_t tot = *pinned<uint64_t>(w, w.at.p_tot);
+    if (res) {
+        const uint64_t *const h_off = pinned<uint64_t>(w, w.at.p_off), flag = *pinned<uint64_t>(w, w.at.p_flag);
+        const uint32_t *const h_nev = pinned<uint32_t>(w, w.at.p_nev), *const h_cnt = pinned<uint32_t>(w, w.at.p_cnt);
+        for (uint64_t k = 0; k < n; k++) {
+            res->ev_len[k] = h_nev[k];
+            if (s_len) s_len[k] = w.raw ? h_cnt[k] : (uint32_t)(h_off[k + 1] - h_off[k]);
+        }
+        *res->total = tot;
+        if (flag & 1) return fail(ctx, RAWDTW_ERR_RANGE, "a chunk has more events than its room in the event arena (ev_len and the total are filled, nothing was written)");
+        if (flag & 2) return fail(ctx, RAWDTW_ERR_RANGE, "events_cap is below the round's events (ev_len and the total are filled, nothing was written)");
+        return RAWDTW_OK;
+    }
+    hipStream_t s = ctx->stream;
+    if (!w.direct_off) {
+        HIP_TRY(ctx, hipMemcpyAsync(w.h_eoff, dev<uint64_t>(w, w.at.eoff), (n + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+    }
+    if (s_len && !w.direct_slen) {
+        HIP_TRY(ctx, hipMemcpyAsync(s_len, dev<uint32_t>(w, w.at.slen), n * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+    }
+    if (tot > w.cap) return fail(ctx, RAWDTW_ERR_RANGE, "events_cap is below the round's events (event_off is filled)");
+    if (tot > w.n_samples) return fail(ctx, RAWDTW_ERR_DEVICE, "more events than samples");
+    if (!w.direct_ev && tot) {
+        HIP_TRY(ctx, hipMemcpyAsync(w.h_ev, dev<float>(w, w.at.ev), tot * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+    }
     return RAWDTW_OK;
 }
 
@@ -585,13 +633,10 @@ extern "C" {
 int rawdtw_detect_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint32_t n_chunks, const uint64_t *sig_off, const float *sig,
                         uint64_t *event_off, float *events, uint64_t events_cap)
 {
-    if (!ctx) return RAWDTW_ERR_INVALID;
-    if (!sig_off || !event_off || (n_chunks && (!sig || !events))) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
-    if (ctx->detect_ws && ctx->detect_ws->w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "a detection is begun on this context and not ended");
     rawdtw_event_opt_t o;
-    if (events::resolve_opt(opt, &o) != RAWDTW_OK) return fail(ctx, RAWDTW_ERR_INVALID, "a window length above 65535");
-    if (events::check_offsets(n_chunks, sig_off) != RAWDTW_OK)
-        return fail(ctx, RAWDTW_ERR_INVALID, "an empty chunk (revent.c:24 asserts), a chunk of 2^32 samples or more, or offsets that descend");
+    if (const int st = begin_checks(ctx, !sig_off || !event_off || (n_chunks && (!sig || !events)), false, opt, &o, events::check_offsets, n_chunks, sig_off,
+                                    "an empty chunk (revent.c:24 asserts), a chunk of 2^32 samples or more, or offsets that descend"))
+        return st;
     Input in;
     in.sig = sig;
     return detect_enqueue(ctx, o, n_chunks, sig_off, in, event_off, events, events_cap);
@@ -600,13 +645,10 @@ int rawdtw_detect_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint32_t
 int rawdtw_detect_raw_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint32_t n_chunks, const uint64_t *raw_off, const int16_t *raw,
                             const rawdtw_channel_t *chan, uint32_t *s_len, uint64_t *event_off, float *events, uint64_t events_cap)
 {
-    if (!ctx) return RAWDTW_ERR_INVALID;
-    if (!raw_off || !event_off || (n_chunks && (!raw || !chan || !s_len || !events))) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
-    if (ctx->detect_ws && ctx->detect_ws->w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "a detection is begun on this context and not ended");
     rawdtw_event_opt_t o;
-    if (events::resolve_opt(opt, &o) != RAWDTW_OK) return fail(ctx, RAWDTW_ERR_INVALID, "a window length above 65535");
-    if (events::check_raw_offsets(n_chunks, raw_off) != RAWDTW_OK)
-        return fail(ctx, RAWDTW_ERR_INVALID, "a window of 2^32 raw samples or more, or offsets that descend");
+    if (const int st = begin_checks(ctx, !raw_off || !event_off || (n_chunks && (!raw || !chan || !s_len || !events)), false, opt, &o,
+                                    events::check_raw_offsets, n_chunks, raw_off, kBadRawOffsets))
+        return st;
     Input in;
     in.raw = raw; in.chan = chan; in.s_len = s_len;
     return detect_enqueue(ctx, o, n_chunks, raw_off, in, event_off, events, events_cap);
@@ -615,94 +657,34 @@ int rawdtw_detect_raw_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint
 int rawdtw_detect_resident_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint32_t n_chunks, const uint64_t *sig_off, const float *sig,
                                  const uint64_t *dst_start, const uint32_t *room, uint64_t events_cap)
 {
-    if (!ctx) return RAWDTW_ERR_INVALID;
-    if (!sig_off || (n_chunks && !sig)) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
-    if (const int st = resident_checks(ctx, n_chunks, dst_start, room)) return st;
-    rawdtw_event_opt_t o;
-    if (events::resolve_opt(opt, &o) != RAWDTW_OK) return fail(ctx, RAWDTW_ERR_INVALID, "a window length above 65535");
-    if (events::check_raw_offsets(n_chunks, sig_off) != RAWDTW_OK) // (an empty chunk is a read's all-outlier window: no events, as the raw entry has it)
-        return fail(ctx, RAWDTW_ERR_INVALID, "a chunk of 2^32 samples or more, or offsets that descend");
+    rawdtw_event_opt_t o; // (an empty chunk is a read's all-outlier window: no events, as the raw entry has it)
+    if (const int st = begin_checks(ctx, !sig_off || (n_chunks && (!sig || !dst_start || !room)), true, opt, &o, events::check_raw_offsets, n_chunks, sig_off,
+                                    "a chunk of 2^32 samples or more, or offsets that descend"))
+        return st;
     Input in;
-    in.sig = sig; in.dst_start = dst_start ? dst_start : sig_off; in.room = room; // (n_chunks == 0: any non-null table marks the kind)
+    in.sig = sig; in.arena = true; in.dst_start = dst_start; in.room = room;
     return detect_enqueue(ctx, o, n_chunks, sig_off, in, nullptr, nullptr, events_cap);
 }
 
 int rawdtw_detect_raw_resident_begin(rawdtw_ctx *ctx, const rawdtw_event_opt_t *opt, uint32_t n_chunks, const uint64_t *raw_off, const int16_t *raw,
                                      const rawdtw_channel_t *chan, const uint64_t *dst_start, const uint32_t *room, uint64_t events_cap)
 {
-    if (!ctx) return RAWDTW_ERR_INVALID;
-    if (!raw_off || (n_chunks && (!raw || !chan))) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
-    if (const int st = resident_checks(ctx, n_chunks, dst_start, room)) return st;
     rawdtw_event_opt_t o;
-    if (events::resolve_opt(opt, &o) != RAWDTW_OK) return fail(ctx, RAWDTW_ERR_INVALID, "a window length above 65535");
-    if (events::check_raw_offsets(n_chunks, raw_off) != RAWDTW_OK)
-        return fail(ctx, RAWDTW_ERR_INVALID, "a window of 2^32 raw samples or more, or offsets that descend");
+    if (const int st = begin_checks(ctx, !raw_off || (n_chunks && (!raw || !chan || !dst_start || !room)), true, opt, &o, events::check_raw_offsets, n_chunks,
+                                    raw_off, kBadRawOffsets))
+        return st;
     Input in;
-    in.raw = raw; in.chan = chan; in.dst_start = dst_start ? dst_start : raw_off; in.room = room;
+    in.raw = raw; in.chan = chan; in.arena = true; in.dst_start = dst_start; in.room = room;
     return detect_enqueue(ctx, o, n_chunks, raw_off, in, nullptr, nullptr, events_cap);
 }
 
 int rawdtw_detect_resident_end(rawdtw_ctx *ctx, uint32_t *s_len, uint32_t *ev_len, uint64_t *total, float *kernel_ms)
 {
-    if (!ctx) return RAWDTW_ERR_INVALID;
-    if (!ctx->detect_ws || !ctx->detect_ws->w.pending || !ctx->detect_ws->w.arena)
-        return fail(ctx, RAWDTW_ERR_INVALID, "no resident detection begun on this context");
-    DetectWs &w = ctx->detect_ws->w;
-    if (!total || (w.n && !ev_len)) return fail(ctx, RAWDTW_ERR_INVALID, "null argument"); // (the detection stays begun)
-    w.pending = false;
-    if (kernel_ms) *kernel_ms = 0.0f;
-    *total = 0;
-    if (!w.enqueued) { // no chunk, or no sample
-        for (uint64_t k = 0; k < w.n; k++) { ev_len[k] = 0; if (s_len) s_len[k] = 0; }
-        return RAWDTW_OK;
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipEventSynchronize(w.done)); // (the detection's own work: the seeding enqueued behind it goes on)
-    for (uint64_t k = 0; k < w.n; k++) {
-        ev_len[k] = w.h_nev[k];
-        if (s_len) s_len[k] = w.raw ? w.h_cnt[k] : (uint32_t)(w.h_off[k + 1] - w.h_off[k]);
-    }
-    *total = w.pin[0];
-    if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, w.ev0, w.ev1));
-    if (w.pin[1] & 1) return fail(ctx, RAWDTW_ERR_RANGE, "a chunk has more events than its room in the event arena (ev_len and the total are filled, nothing was written)");
-    if (w.pin[1] & 2) return fail(ctx, RAWDTW_ERR_RANGE, "events_cap is below the round's events (ev_len and the total are filled, nothing was written)");
-    return RAWDTW_OK;
+    const ResidentOut res{s_len, ev_len, total};
+    return detect_end(ctx, &res, kernel_ms);
 }
 
-int rawdtw_detect_end(rawdtw_ctx *ctx, float *kernel_ms)
-{
-    if (!ctx) return RAWDTW_ERR_INVALID;
-    if (!ctx->detect_ws || !ctx->detect_ws->w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "no detection begun on this context");
-    if (ctx->detect_ws->w.arena) return fail(ctx, RAWDTW_ERR_INVALID, "the detection begun on this context is a resident one (rawdtw_detect_resident_end)");
-    DetectWs &w = ctx->detect_ws->w;
-    w.pending = false;
-    if (kernel_ms) *kernel_ms = 0.0f;
-    if (w.n == 0 || w.n_samples == 0) { // nothing was enqueued
-        for (uint64_t k = 0; k <= w.n; k++) w.h_eoff[k] = 0;
-        for (uint64_t k = 0; w.h_slen && k < w.n; k++) w.h_slen[k] = 0;
-        return RAWDTW_OK;
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    HIP_TRY(ctx, hipEventSynchronize(w.done)); // (the detection's own work: what the caller enqueued behind it goes on)
-    const uint64_t tot = w.pin[0];
-    if (!w.direct_off) {
-        HIP_TRY(ctx, hipMemcpyAsync(w.h_eoff, w.d_eoff, ((uint64_t)w.n + 1) * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(ctx, hipStreamSynchronize(s));
-    }
-    if (w.h_slen && !w.direct_slen) {
-        HIP_TRY(ctx, hipMemcpyAsync(w.h_slen, w.d_slen, (uint64_t)w.n * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(ctx, hipStreamSynchronize(s));
-    }
-    if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, w.ev0, w.ev1));
-    if (tot > w.cap) return fail(ctx, RAWDTW_ERR_RANGE, "events_cap is below the round's events (event_off is filled)");
-    if (tot > w.n_samples) return fail(ctx, RAWDTW_ERR_DEVICE, "more events than samples");
-    if (!w.direct_ev && tot) {
-        HIP_TRY(ctx, hipMemcpyAsync(w.h_ev, w.d_ev, tot * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(ctx, hipStreamSynchronize(s));
-    }
-    return RAWDTW_OK;
-}
+int rawdtw_detect_end(rawdtw_ctx *ctx, float *kernel_ms) { return detect_end(ctx, nullptr, kernel_ms); }
 
 } // extern "C"
 
@@ -711,7 +693,8 @@ bool detect_resident_view(const rawdtw_ctx *ctx, DetectView *v)
 {
     const DetectWs *w = ctx && ctx->detect_ws ? &ctx->detect_ws->w : nullptr;
     if (!w || !w->pending || !w->arena) return false;
-    *v = DetectView{w->enqueued, w->n, w->cap, w->n_samples, w->d_eoff, w->d_dst, w->d_flag};
+    *v = DetectView{w->enqueued, w->n, w->cap, w->n_samples, dev<uint64_t>(*w, w->at.eoff), dev<uint64_t>(*w, w->at.dst),
+                    dev<uint64_t>(*w, w->at.tot) + events::kTotFlag};
     return true;
 }
 

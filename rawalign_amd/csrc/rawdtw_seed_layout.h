@@ -22,15 +22,15 @@
 //   decl   the detection's flag word, behind hoff       -          -          comes home
 // A region the kind does not use has `bytes` 0 (its `at` is where the next one starts).
 #pragma once
-#include <cstddef>
-#include <cstdint>
+#include "rawdtw_layout.h"
 
 namespace rawdtw {
 namespace seed {
 
 enum class Kind { plain, resident, detected };
 
-struct Region { size_t at = 0, bytes = 0; };
+using ws::Region;
+using ws::al;
 
 struct Layout {
     Region off, src, ev, code, pos, cnt, val, kept, chits, hoff, tot, hash, spos, count; // the device block, in this order
@@ -39,20 +39,17 @@ struct Layout {
     size_t pin_need = 0;
 };
 
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 inline Layout layout(Kind kind, uint64_t n, uint64_t N, bool sketch)
 {
     const bool plain = kind == Kind::plain;
     const size_t b_off = al((n + 1) * 8), b_ev = al(N * 4), b_val = al(N * 8), b_cnt = al(n * 4), b_tot = al(32);
     Layout L;
-    size_t p = 0;
-    auto take = [&p](size_t bytes) { const Region r{p, bytes}; p += bytes; return r; };
+    ws::Take take;
     L.off = take(b_off); L.src = take(plain ? 0 : b_off); L.ev = take(plain ? b_ev : 0);
     L.code = take(b_ev); L.pos = take(b_ev); L.cnt = take(b_ev); L.val = take(b_val);
     L.kept = take(b_cnt); L.chits = take(b_off); L.hoff = take(b_off); L.tot = take(b_tot);
     L.hash = take(sketch ? b_ev : 0); L.spos = take(sketch ? b_ev : 0); L.count = take(sketch ? b_cnt : 0);
-    L.need = p;
+    L.need = take.p;
     const size_t row = (n + 1) * 8;
     L.p_tot = Region{0, 8}; L.p_over = Region{8, 8};
     L.p_off = Region{16, kind == Kind::detected ? 0 : row};

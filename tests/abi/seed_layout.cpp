@@ -7,33 +7,10 @@
 //   pinned block  the same: the regions disjoint, inside pin_need, where the begins and ends used to find them by hand
 //                 (pin + 2, + (n + 1), + 2 (n + 1), the flag word behind the hit offsets), pin_need as it was
 // Prints "ok <cases>"; the first failure otherwise.
-#include <cstdio>
-#include <vector>
-
+#include "layout_check.h"
 #include "rawdtw_seed_layout.h"
 
 using namespace rawdtw::seed;
-
-struct Named { const char *name; Region r; size_t least; bool used; };
-
-static size_t al256(size_t x) { return (x + 255) / 256 * 256; }
-
-static bool regions_ok(const char *block, const std::vector<Named> &rs, size_t total, size_t align)
-{
-    for (size_t i = 0; i < rs.size(); i++) {
-        const Named &a = rs[i];
-        if (!a.used && a.r.bytes) { printf("FAIL %s: %s is not used but has %zu bytes\n", block, a.name, a.r.bytes); return false; }
-        if (a.used && a.r.bytes < a.least) { printf("FAIL %s: %s has %zu bytes, needs %zu\n", block, a.name, a.r.bytes, a.least); return false; }
-        if (a.r.at % align) { printf("FAIL %s: %s at %zu is not aligned to %zu\n", block, a.name, a.r.at, align); return false; }
-        if (!a.r.bytes) continue;
-        if (a.r.at > total || a.r.bytes > total - a.r.at) { printf("FAIL %s: %s [%zu, +%zu) leaves the block of %zu\n", block, a.name, a.r.at, a.r.bytes, total); return false; }
-        for (size_t j = 0; j < i; j++) {
-            const Named &b = rs[j];
-            if (b.r.bytes && a.r.at < b.r.at + b.r.bytes && b.r.at < a.r.at + a.r.bytes) { printf("FAIL %s: %s and %s overlap\n", block, a.name, b.name); return false; }
-        }
-    }
-    return true;
-}
 
 int main()
 {

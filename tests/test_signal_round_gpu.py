@@ -253,6 +253,52 @@ def test_begin_refusals_enqueue_nothing(windows, host):
         bare.close()
 
 
+def test_the_four_detections_share_one_workspace(windows, host):
+    """Float and raw, plain and resident, one after another on one context: every kind follows one of the other family (a plain end reads
+    what a resident begin laid out before it, and the reverse), the blocks grow after a smaller detection, and n crosses the 64-chunk
+    wave both ways.  Each against the host's answer, bit for bit."""
+    s_len, eoff, ev = host[False]
+    every = len(windows[0])
+    eng = ra.Engine(0)
+
+    def plain(kind, n):
+        if kind == "raw":
+            data, off, ch = inputs(kind, windows, host, n)
+            got_len, got_off, got = eng.detect_events_raw(data, off, ch)
+            assert np.array_equal(got_len, s_len[:n]) and np.array_equal(got_off, eoff[:n + 1]), (kind, n)
+            assert np.array_equal(canon(got), canon(ev[:int(eoff[n])])), (kind, n)
+            return
+        keep = [k for k in range(n) if len(host["pa"][k])]   # (the plain float entry refuses an empty chunk)
+        assert len(keep) == n - sum(1 for k in (9, 30) if k < n)
+        pa = [host["pa"][k] for k in keep]
+        off = np.concatenate([[0], np.cumsum([len(x) for x in pa])]).astype(np.uint64)
+        want = [ev[int(eoff[k]):int(eoff[k + 1])] for k in keep]
+        got_off, got = eng.detect_events(np.concatenate(pa), off)
+        assert np.array_equal(got_off, np.concatenate([[0], np.cumsum([len(x) for x in want])]).astype(np.uint64)), (kind, n)
+        assert np.array_equal(canon(got), canon(np.concatenate(want))), (kind, n)
+
+    def resident(kind, n):
+        counts = np.diff(eoff[:n + 1].astype(np.int64))
+        dst, room, size = layout(counts, seed=40 + n)
+        ar = Arena(eng, size)
+        data, off, ch = inputs(kind, windows, host, n)
+        ev_len, got_len, total = eng.detect_resident(data, off, dst, room, chan=ch)
+        assert np.array_equal(ev_len, counts) and np.array_equal(got_len, s_len[:n]) and total == int(eoff[n]), (kind, n)
+        got, want = arena_bits(ar), expected_arena(size, dst, eoff[:n + 1], ev)
+        bad = np.nonzero(got != want)[0]
+        assert len(bad) == 0, (kind, n, bad[:8], got[bad[:8]], want[bad[:8]])
+
+    try:
+        plain("pa", 65)
+        resident("raw", 1)
+        plain("raw", 64)
+        resident("pa", every)
+        plain("pa", 1)
+        resident("raw", every)
+    finally:
+        eng.close()
+
+
 # ---- 3. seeding behind the detection ----------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def ref():
