@@ -970,6 +970,58 @@ int rawdtw_mapper_round_raw_resident(rawdtw_mapper *m, const rawdtw_seed_index *
 int rawdtw_mapper_signal_stats(const rawdtw_mapper *m, uint64_t *rounds, uint64_t *retried_rounds, uint64_t *sample_bytes_to_device,
                                uint64_t *event_bytes_crossed);
 
+/* ---- a round's end for all its reads at once: gen_primary_chains (rmap.cpp:90-128, comparator rmap.h:41-45), comp_mapq (65-88) and
+ * is_mapped_with_high_confidence (594-665) -- the three steps between a batch's score / keep and "this read is finished".
+ * Read r's candidates are its chains in evaluation order, [chain_off[r], chain_off[r+1]); recs[c].key = sequence * 2 + strand;
+ * score[c] / keep[c] are rawdtw_batch_fetch's (score[c] is the chain's alignment_score whatever the flags; keep may be NULL without
+ * evaluate_chains).  Chain c takes part when !opt->evaluate_chains || keep[c] (rmap.cpp:525).
+ *   out[r].n_primary            the read's primary chains
+ *   primary[chain_off[r] + k]   k < n_primary: the index within the read of the k-th primary chain, best first; RAWDTW_NO_PRIMARY behind them
+ *   out[r].mapq                 comp_mapq's value for the first primary chain
+ *   out[r].flags                bit 0: mapped with high confidence; bit 1: declined (device forms only; the other outputs are void)
+ * A read with no chain taking part reads {0, 0, 0}.
+ *   rawdtw_round_end_host        the batched restatement over rawdtw_gen_primary_chains and rawdtw_is_mapped_with_high_confidence.  Never
+ *        declines: the fall-back for declined reads (a read at a time: n_reads = 1, chain_off + r, out + r, the other arrays as they are)
+ *        and what the device forms are tested against, bit for bit.
+ *   rawdtw_round_end             the host arrays go up, one launch (a wave a read, a lane a candidate), the results come home.
+ *   rawdtw_batch_round_end_begin enqueued on the batch's stream behind its last run: reads the batch's score, keep and chain offsets where
+ *        they lie in device memory.  `recs`: a host array (copied up) or, with recs_on_device, a device array of the batch's n_chains
+ *        records that stays as it is until _fetch (rawdtw_chain_round_recs gives the chaining workspace's).  One round end at a time a context.
+ *   rawdtw_batch_round_end_fetch waits and copies out[n_reads] and primary[n_chains] home.  A batch the device-planned path declined is
+ *        scored again through the job list first (as rawdtw_batch_fetch does) and its round end runs again on those scores.
+ *   rawdtw_chain_round_recs      the device address of the context's ended chaining round's recs (valid until its next chaining round).
+ * A read is declined -- the caller runs rawdtw_round_end_host on it alone; a declined read never declines the round -- when
+ *   - more than 64 of its chains take part;
+ *   - two chains taking part are equal on all seven keys (std::sort's choice between them is not the comparator's, and it decides
+ *     whose anchors survive);
+ *   - a chaining or alignment score of a chain taking part is NaN;
+ *   - a quotient that is evaluated -- comp_mapq's s1 / s0, the stop rule's s0 / s1 -- is not finite, or comp_mapq's product
+ *     40 * (1 - s1 / s0) is not in [-2^31, 2^31) (the host's conversion to int there is x86's, the device's saturates).
+ * The arithmetic is fp32 with IEEE division, no contraction, denormals kept; the stop rule's mean is a serial sum in primary order.
+ *   rawdtw_set_option(ctx, "device_round_end", 1)  on the context a mapper was created with: its rounds that are chained on the device
+ *        and run the DTW enqueue the round end behind rawdtw_batch_submit_device and take primary, mapq and the stop rule's answer
+ *        from it; reads that sat the round out and declined reads end on the host as before.  0 (the default): no such call is made.
+ *        Lines and logs are the same either way.  rawdtw_get_option reads it back.
+ *   rawdtw_get_option(ctx, "round_end_kernel_us")  read-only: the launch of the context's most recently FETCHED round end between its
+ *        HIP events, in microseconds; 0 before any.  (What scripts/round_end_probe.py reports as the kernel's time.)
+ * n_reads == 0: rawdtw_round_end_host and rawdtw_round_end return RAWDTW_OK and do nothing; a batch without reads has no round end
+ * (rawdtw_batch_round_end_begin: RAWDTW_ERR_INVALID).  A batch destroyed between _begin and _fetch takes its round end with it: the
+ * launch is waited for, its results are dropped, and the context is free for the next round end.
+ *   rawdtw_mapper_round_end_stats  committed rounds that used it, the reads it ended, the reads it declined.  Any pointer may be NULL. ---- */
+typedef struct { uint32_t n_primary, mapq, flags; } rawdtw_round_out_t;
+#define RAWDTW_ROUND_HIGH 1u
+#define RAWDTW_ROUND_DECLINED 2u
+#define RAWDTW_NO_PRIMARY 0xffffffffu
+int rawdtw_round_end_host(const rawdtw_select_opt_t *opt, uint64_t n_reads, const uint64_t *chain_off, const rawdtw_chain_rec_t *recs,
+                          const float *score, const uint8_t *keep, rawdtw_round_out_t *out, uint32_t *primary);
+int rawdtw_round_end(rawdtw_ctx *ctx, const rawdtw_select_opt_t *opt, uint64_t n_reads, const uint64_t *chain_off,
+                     const rawdtw_chain_rec_t *recs, const float *score, const uint8_t *keep, rawdtw_round_out_t *out, uint32_t *primary);
+int rawdtw_batch_round_end_begin(rawdtw_ctx *ctx, rawdtw_batch *batch, const rawdtw_select_opt_t *opt, const rawdtw_chain_rec_t *recs,
+                                 int recs_on_device);
+int rawdtw_batch_round_end_fetch(rawdtw_ctx *ctx, rawdtw_batch *batch, rawdtw_round_out_t *out, uint32_t *primary);
+int rawdtw_chain_round_recs(rawdtw_ctx *ctx, const rawdtw_chain_rec_t **d_recs);
+int rawdtw_mapper_round_end_stats(const rawdtw_mapper *m, uint64_t *rounds, uint64_t *reads_device, uint64_t *reads_declined);
+
 #ifdef __cplusplus
 }
 #endif

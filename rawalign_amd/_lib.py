@@ -106,6 +106,11 @@ class Channel(C.Structure):
     _fields_ = [("digitisation", C.c_float), ("range", C.c_float), ("offset", C.c_float)]
 
 
+class RoundOut(C.Structure):
+    """rawdtw_round_out_t"""
+    _fields_ = [("n_primary", C.c_uint32), ("mapq", C.c_uint32), ("flags", C.c_uint32)]
+
+
 RAWDTW_SU_NO_STOP = 0xFFFFFFFF  # rawdtw_mapper_su_apply: no stop
 
 
@@ -280,6 +285,12 @@ SYMBOLS = {
     "rawdtw_mapper_round_signal_resident": (I32, [VP, VP, C.POINTER(EventOpt), U32, VP, VP, VP]),
     "rawdtw_mapper_round_raw_resident": (I32, [VP, VP, C.POINTER(EventOpt), U32, VP, VP, VP, VP]),
     "rawdtw_mapper_signal_stats": (I32, [VP, VP, VP, VP, VP]),
+    "rawdtw_round_end_host": (I32, [C.POINTER(SelectOpt), U64, VP, VP, VP, VP, VP, VP]),
+    "rawdtw_round_end": (I32, [VP, C.POINTER(SelectOpt), U64, VP, VP, VP, VP, VP, VP]),
+    "rawdtw_batch_round_end_begin": (I32, [VP, VP, C.POINTER(SelectOpt), VP, I32]),
+    "rawdtw_batch_round_end_fetch": (I32, [VP, VP, VP, VP]),
+    "rawdtw_chain_round_recs": (I32, [VP, C.POINTER(VP)]),
+    "rawdtw_mapper_round_end_stats": (I32, [VP, VP, VP, VP]),
 }
 
 

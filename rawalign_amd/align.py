@@ -425,6 +425,27 @@ class Batch:
                                                               _ptr(jc) if jc is not None else None))
         return (score, keep, jc) if with_job_costs else (score, keep)
 
+    def round_end_begin(self, select_opt, recs, device_ptr=None):
+        """rawdtw_batch_round_end_begin: the round's end enqueued behind the batch's last run, on its score / keep / chain offsets where
+        they lie.  `recs`: the chains' CHAIN_REC_DTYPE records, or None with `device_ptr` the address of such an array in device memory
+        (Engine.chain_round_recs)."""
+        from .dtw import CHAIN_REC_DTYPE
+
+        if device_ptr is None:
+            self._recs = np.ascontiguousarray(recs, CHAIN_REC_DTYPE)
+            if len(self._recs) < self.cb.n_chains:
+                raise ValueError("recs holds a record a chain")
+        p = _ptr(self._recs) if device_ptr is None else C.c_void_p(device_ptr)
+        self.engine._check(self.engine.lib.rawdtw_batch_round_end_begin(self.engine._ctx, self._h, C.byref(select_opt), p, int(device_ptr is not None)))
+
+    def round_end_fetch(self):
+        """rawdtw_batch_round_end_fetch: (out: ROUND_OUT_DTYPE a read, primary: uint32 a chain)"""
+        from .dtw import ROUND_OUT_DTYPE
+
+        out, primary = np.zeros(max(self.cb.n_reads, 1), ROUND_OUT_DTYPE), np.zeros(max(self.cb.n_chains, 1), np.uint32)
+        self.engine._check(self.engine.lib.rawdtw_batch_round_end_fetch(self.engine._ctx, self._h, _ptr(out), _ptr(primary)))
+        return out[:self.cb.n_reads], primary[:self.cb.n_chains]
+
     def close(self):
         if getattr(self, "_h", None) is not None:
             self.engine.lib.rawdtw_batch_destroy(self._h)  # (safe in any order: rawdtw_destroy detaches live batches)

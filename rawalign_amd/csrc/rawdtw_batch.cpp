@@ -1090,12 +1090,25 @@ int rawdtw_batch_fetch_destroy(rawdtw_ctx *ctx, rawdtw_batch *batch, float *scor
 namespace rawdtw { namespace capi {
 void batch_detach(rawdtw_ctx *ctx, rawdtw_batch *b)
 {
+    round_end_forget(ctx, b); // (before the arrays a pending round end reads go)
     for (auto &e : b->ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : b->ev_plan) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     b->ev.clear(); b->ev_runs = 0;
     batch_release_device(b); // (also destroys the job-list plan, which unregisters itself)
     ws_release(ctx, b->ws);
     b->stream = false;       // neither form left: every entry point but destroy refuses the batch (batch_dead)
+}
+
+int batch_settle(rawdtw_ctx *ctx, rawdtw_batch *b, bool *redone)
+{
+    *redone = false;
+    if (!b->stream) return RAWDTW_OK;
+    int st = stream_counters(ctx, b);
+    if (st != RAWDTW_OK || !stream_declined(b)) return st;
+    *redone = true;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // (the counters may have come home earlier: nothing may still read the workspace the fall-back gives back)
+    b->dirty = false;
+    return stream_fallback(ctx, b);
 }
 } } // namespace rawdtw::capi
 extern "C" {

@@ -118,6 +118,7 @@ int rawdtw_destroy(rawdtw_ctx *ctx)
     chain_ws_free(ctx);
     detect_ws_free(ctx);
     seed_ws_free(ctx);
+    round_end_ws_free(ctx);
     for (StreamWs &w : ctx->ws_free) { if (w.d) (void)hipFree(w.d); if (w.h) (void)hipHostFree(w.h); }
     if (ctx->d_append) (void)hipFree(ctx->d_append);
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
@@ -178,6 +179,7 @@ int rawdtw_set_option(rawdtw_ctx *ctx, const char *name, int64_t value)
     if (!strcmp(name, "stream_tile_radius")) { ctx->stream_tile_radius = value < 1 ? 1 : (value > kMaxLaneRadius ? kMaxLaneRadius : (int)value); return RAWDTW_OK; }
     if (!strcmp(name, "chain_long_seeds")) { ctx->chain_long_seeds = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 1 << 20); return RAWDTW_OK; }
     if (!strcmp(name, "seed_minimizer")) { ctx->seed_minimizer = value != 0; return RAWDTW_OK; }
+    if (!strcmp(name, "device_round_end")) { ctx->device_round_end = value != 0; return RAWDTW_OK; }
     if (!strcmp(name, "signal_events_cap")) { ctx->signal_events_cap = (uint64_t)std::max<int64_t>(value, 0); return RAWDTW_OK; }
     if (!strcmp(name, "tb_workspace_mb")) { ctx->tb_workspace_mb = (uint64_t)std::min<int64_t>(std::max<int64_t>(value, 0), 1 << 30); return RAWDTW_OK; }
     if (!strcmp(name, "lane_max_radius")) {
@@ -192,6 +194,8 @@ int rawdtw_get_option(const rawdtw_ctx *ctx, const char *name, int64_t *value)
     if (!ctx || !name || !value) return RAWDTW_ERR_INVALID;
     if (!strcmp(name, "chain_long_seeds")) { *value = ctx->chain_long_seeds; return RAWDTW_OK; }
     if (!strcmp(name, "seed_minimizer")) { *value = ctx->seed_minimizer ? 1 : 0; return RAWDTW_OK; }
+    if (!strcmp(name, "device_round_end")) { *value = ctx->device_round_end ? 1 : 0; return RAWDTW_OK; }
+    if (!strcmp(name, "round_end_kernel_us")) { *value = round_end_kernel_us(ctx); return RAWDTW_OK; }
     if (!strcmp(name, "signal_events_cap")) { *value = (int64_t)ctx->signal_events_cap; return RAWDTW_OK; }
     if (!strcmp(name, "tb_workspace_mb")) { *value = (int64_t)ctx->tb_workspace_mb; return RAWDTW_OK; }
     if (!strcmp(name, "tb_sub_batches")) { *value = (int64_t)ctx->tb_sub_batches; return RAWDTW_OK; }

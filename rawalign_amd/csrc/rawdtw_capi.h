@@ -148,6 +148,8 @@ struct rawdtw_ctx {
     struct rawdtw_chain_ws *chain_ws = nullptr; // rawdtw_chain_round's device block (rawdtw_chain.hip), grow-only
     struct rawdtw_detect_ws *detect_ws = nullptr; // rawdtw_detect_begin's device block (rawdtw_events.hip), grow-only
     struct rawdtw_seed_ws *seed_ws = nullptr;     // rawdtw_seed_index_upload's table and rawdtw_seed_begin's device block (rawdtw_seed.hip), grow-only
+    struct rawdtw_round_end_ws *round_end_ws = nullptr; // rawdtw_round_end's device block (rawdtw_round_end.hip), grow-only
+    bool device_round_end = false; // "device_round_end": a mapper created with this context ends its device-chained rounds on the device
     uint32_t chain_max_seeds = 0; // tests: RAWDTW_CHAIN_MAX_SEEDS lowers rawdtw_chain_round's cap on seeds a read, so that small rounds take the declined path (0: no)
     uint32_t chain_long_seeds = 0; // "chain_long_seeds": reads above the cap with at most this many seeds are chained by rawdtw_chain.hip's long path (0: declined)
     bool seed_minimizer = false;   // "seed_minimizer": rawdtw_seed.hip seeds a w > 0 table on the device (k_seed_min) rather than refusing it
@@ -298,6 +300,9 @@ void *device_view(void *p, size_t bytes);
 void chain_ws_free(rawdtw_ctx *ctx); // rawdtw_chain.hip
 void detect_ws_free(rawdtw_ctx *ctx); // rawdtw_events.hip
 void seed_ws_free(rawdtw_ctx *ctx);   // rawdtw_seed.hip
+void round_end_ws_free(rawdtw_ctx *ctx); // rawdtw_round_end.hip
+void round_end_forget(rawdtw_ctx *ctx, const rawdtw_batch *b); // (rawdtw_batch.cpp's batch_detach)
+int64_t round_end_kernel_us(const rawdtw_ctx *ctx); // the most recent fetched round end's launch, from its event pair ("round_end_kernel_us", read-only)
 // A resident detection begun on the context and not ended (rawdtw_events.hip), as rawdtw_seed_detected_begin reads it: everything the
 // seeding needs is in the detection's workspace on the device.  `enqueued` false: no launch went out (no chunk, or no sample).
 struct DetectView {
@@ -449,6 +454,9 @@ std::string verify_uploaded_tiles(const rawdtw_ctx *ctx, const rawdtw_job_t *job
                                   size_t n_tiles, const TileSpan *spans, size_t n_spans, const TileJob *tjobs, size_t n_tjobs, std::vector<uint8_t> &seen);
 // ---- rawdtw_batch.cpp ----
 void batch_detach(rawdtw_ctx *ctx, rawdtw_batch *b);
+// the batch's results as they will stand: a device-planned batch's counters home (a wait for its stream), and a batch that path declined
+// scored again through the job list (*redone: its device arrays are others now)
+int batch_settle(rawdtw_ctx *ctx, rawdtw_batch *b, bool *redone);
 
 } // namespace capi
 } // namespace rawdtw

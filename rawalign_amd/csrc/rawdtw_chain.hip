@@ -750,6 +750,16 @@ int rawdtw_chain_round_end(rawdtw_ctx *ctx, const rawdtw_anchor_t **d_anchors, c
     return RAWDTW_OK;
 }
 
+int rawdtw_chain_round_recs(rawdtw_ctx *ctx, const rawdtw_chain_rec_t **d_recs)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (!d_recs) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    *d_recs = nullptr;
+    if (!ctx->chain_ws || ctx->chain_ws->w.pending || !ctx->chain_ws->w.d_recs) return fail(ctx, RAWDTW_ERR_INVALID, "no ended chaining round on this context");
+    *d_recs = ctx->chain_ws->w.d_recs;
+    return RAWDTW_OK;
+}
+
 int rawdtw_chain_round_stats(const rawdtw_ctx *ctx, uint64_t *rounds, uint64_t *long_reads, uint64_t *long_seeds, uint64_t *far_steps)
 {
     if (!ctx) return RAWDTW_ERR_INVALID;

@@ -208,6 +208,38 @@ int rawdtw_is_mapped_with_high_confidence(const rawdtw_chain_t *c, uint32_t n_ch
     return (n_chains == 1 && c[0].n_anchors >= opt->min_chain_anchor) ? 1 : 0; // rmap.cpp:620, 659
 }
 
+// The round's end of many reads (include/rawdtw.h): the two functions above, a read at a time.  A chain's index within its read rides
+// through the sort in `tag`.
+int rawdtw_round_end_host(const rawdtw_select_opt_t *opt, uint64_t n_reads, const uint64_t *chain_off, const rawdtw_chain_rec_t *recs,
+                          const float *score, const uint8_t *keep, rawdtw_round_out_t *out, uint32_t *primary)
+{
+    if (!opt || !chain_off || !out || (n_reads && chain_off[n_reads] > chain_off[0] && (!recs || !score || !primary))) return RAWDTW_ERR_INVALID;
+    if (opt->evaluate_chains && !keep && n_reads && chain_off[n_reads] > chain_off[0]) return RAWDTW_ERR_INVALID;
+    std::vector<rawdtw_chain_t> rec, prim;
+    std::vector<uint32_t> kept;
+    for (uint64_t r = 0; r < n_reads; r++) {
+        const uint64_t c0 = chain_off[r], c1 = chain_off[r + 1];
+        if (c1 < c0 || c1 - c0 > 0xffffffffull) return RAWDTW_ERR_INVALID;
+        rec.clear();
+        for (uint64_t c = c0; c < c1; c++) {
+            primary[c] = RAWDTW_NO_PRIMARY;
+            if (opt->evaluate_chains && !keep[c]) continue; // rmap.cpp:525
+            rec.push_back(rawdtw_chain_t{recs[c].chaining_score, score[c], recs[c].key >> 1, recs[c].start_position, recs[c].end_position,
+                                         recs[c].n_anchors, (int32_t)(recs[c].key & 1u), 0u, (uint32_t)(c - c0)});
+        }
+        out[r] = rawdtw_round_out_t{0u, 0u, 0u};
+        if (rec.empty()) continue;
+        kept.resize(rec.size());
+        const uint32_t nk = rawdtw_gen_primary_chains(rec.data(), (uint32_t)rec.size(), opt, kept.data());
+        prim.resize(nk);
+        for (uint32_t k = 0; k < nk; k++) { prim[k] = rec[kept[k]]; primary[c0 + k] = prim[k].tag; }
+        out[r].n_primary = nk;
+        out[r].mapq = prim[0].mapq;
+        out[r].flags = rawdtw_is_mapped_with_high_confidence(prim.data(), nk, opt) ? RAWDTW_ROUND_HIGH : 0u;
+    }
+    return RAWDTW_OK;
+}
+
 // sequence_until.c:5-19.  The source is one rounded product and one rounded add per element, summed in order;
 // `contracted_tail` selects what the reference's own default build (GCC -O3 with FMA available) computes instead:
 // the same in-order sum, but the elements after the last full group of four go through one fused multiply-add each

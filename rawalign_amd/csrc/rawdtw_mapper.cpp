@@ -121,6 +121,8 @@ struct RoundArrays {
     PinBuf<uint64_t> prev_off, ev_start;  // a resident round (rawdtw_mapper_round_seeded_resident): the previous anchors' offsets (the anchors themselves, dense, in
     PinBuf<uint32_t> chunk_start, ev_len; // `seeds`), the chunks' places in the event arena, and what the device's writer needs per read
     PinBuf<uint8_t> sits_out;
+    PinBuf<rawdtw_round_out_t> re_out;    // the round's end from the device ("device_round_end"): per read, and per chain the primaries' indices
+    PinBuf<uint32_t> re_primary;
     std::vector<uint32_t> chain_seq; // (the external scorer's view)
     std::vector<int32_t> chain_strand;
     uint64_t n_reads = 0, n_chains = 0, n_anchors = 0; // (the sizes the next round's matching reads again)
@@ -309,6 +311,7 @@ struct rawdtw_mapper {
     PinBuf<uint32_t> sig_room, sig_evlen;
     std::vector<uint64_t> sig_evoff;
     uint64_t sig_rounds = 0, sig_retried = 0, sig_sample_bytes = 0;
+    uint64_t re_rounds = 0, re_reads = 0, re_declined = 0; // rawdtw_mapper_round_end_stats
     uint64_t sig_cap = 0; // the largest events_cap a round from signal ran with: what the seeding's workspace holds already
 };
 
@@ -502,6 +505,13 @@ void discard_chain_round(rawdtw_ctx *ctx)
     (void)rawdtw_chain_round_end(ctx, &a, &rb, &qb);
 }
 
+// "device_round_end" on the context the mapper was created with
+bool round_end_on_device(const rawdtw_mapper *m)
+{
+    int64_t v = 0;
+    return m->ctx && rawdtw_get_option(m->ctx, "device_round_end", &v) == RAWDTW_OK && v != 0;
+}
+
 // a round's sizes in one group (0 where its path does not know them)
 struct Sizes { uint64_t reads = 0, chains = 0, anchors = 0, new_anchors = 0, events = 0, seg = 0, seeds = 0; };
 
@@ -524,7 +534,9 @@ struct Round {
     // its reads' chunks ARE the segments, in order -- no copy into the mapper's own staging (a third of the host phase)
     bool events_in_place = on_device && m->opt.device_chain && G == 1 && event_off[n_reads] > 0 && rawdtw_host_is_page_locked(events) == 1;
     std::vector<RoundRead> rr = std::vector<RoundRead>(n_reads);
-    struct PerGroup { bool chaining = false; uint64_t ns = 0, nev = 0, nseg = 0, scored = 0, reused = 0, extra = 0; } per[2]; // (ns: seeds sent up; extra: other bytes)
+    struct PerGroup { bool chaining = false; uint64_t ns = 0, nev = 0, nseg = 0, scored = 0, reused = 0, extra = 0; // (ns: seeds sent up; extra: other bytes)
+                      bool round_end = false; uint64_t re_reads = 0, re_declined = 0; } per[2]; // (the round's end enqueued on the device; the reads it ended / declined)
+    bool device_round_end = round_end_on_device(m); // (read once a round)
     int status = RAWDTW_OK;
     std::string msg;
 
@@ -782,6 +794,8 @@ struct Round {
         // (a resident round of a mapper that runs no DTW -- neither EVALUATE_CHAINS nor LOG_SCORES -- ends with the chains: rmap.cpp:509)
         if (runs_dtw) st = rawdtw_batch_submit_device(g.ctx, &m->opt.align, nr, ra.chain_off.p, ra.anchor_off.p, d_anchors, d_ref_base, d_read_base, &ra.batch);
         if (st != RAWDTW_OK) return failed(st, rawdtw_last_error(g.ctx));
+        if (runs_dtw && device_round_end && ra.batch) st = begin_round_end(g, ra, p);
+        if (st != RAWDTW_OK) return failed(st, rawdtw_last_error(g.ctx));
         m->timing[6] += (double)(p.nev * sizeof(float));
         m->timing[7] += (double)(p.ns * sizeof(rawdtw_seed_t) + (nr + 1) * 16 + nr * 4 + (nc + 1) * 8 + p.nseg * 12 + p.extra);
         lap(2);
@@ -799,6 +813,18 @@ struct Round {
             }
         });
         lap(1);
+    }
+
+    // "device_round_end": the round's end enqueued right behind the batch, on the chaining workspace's records where they lie
+    int begin_round_end(Group &g, RoundArrays &ra, PerGroup &p)
+    {
+        if (!ra.re_out.ensure(g.hw_reads + 1, false) || !ra.re_primary.ensure(g.hw_chains + 1, false)) { failed(RAWDTW_ERR_OOM, "host allocation failed"); return RAWDTW_ERR_OOM; }
+        const rawdtw_chain_rec_t *d_recs = nullptr;
+        int st = rawdtw_chain_round_recs(g.ctx, &d_recs);
+        const rawdtw_select_opt_t so = select_opt(m);
+        if (st == RAWDTW_OK) st = rawdtw_batch_round_end_begin(g.ctx, ra.batch, &so, d_recs, 1);
+        p.round_end = st == RAWDTW_OK;
+        return st;
     }
 
     // ---- a group's round with the chains made on the host: host phase, lay-out, submit (`events_done`: a round the device declined to chain --
@@ -939,14 +965,39 @@ struct Round {
             if (st != RAWDTW_OK) failed(st, rawdtw_last_error(g.ctx));
             uint64_t sc = 0, ru = 0;
             if (ok() && rawdtw_batch_round_stats(g.ctx, ra.batch, &sc, &ru) == RAWDTW_OK) { per[gi].scored = sc; per[gi].reused = ru; }
+            if (per[gi].round_end) { // (also after a failure: the context's round end is begun and must be ended)
+                const int se = rawdtw_batch_round_end_fetch(g.ctx, ra.batch, ra.re_out.p, ra.re_primary.p);
+                if (se != RAWDTW_OK) failed(se, rawdtw_last_error(g.ctx));
+            }
         }
         lap(3);
         if (!ok()) return;
         const bool evaluate = (m->opt.flag & 0x2) != 0, log_scores = (m->opt.flag & 0x8) != 0;
+        const bool from_device = per[gi].round_end;
         m->pool->run(ra.ks.size(), 16, [&](size_t i) {
             const uint32_t k = ra.ks[i];
             RoundRead &r = rr[k];
             if (r.skipped) { r.high = high_confidence(m, read(k).chains); return; } // rmap.cpp:569-572: the chains stay as they were
+            if (from_device && !(ra.re_out[i].flags & RAWDTW_ROUND_DECLINED)) { // primary, mapq and the stop rule's answer are the device's: the chains are moved
+                const rawdtw_round_out_t &o = ra.re_out[i];
+                if (log_scores)
+                    for (size_t c = 0; c < r.chains.size(); c++) {
+                        const float as = ra.score[r.chain0 + c];
+                        if (as == -1e10f) continue;
+                        char line[128];
+                        snprintf(line, sizeof line, "chaining_score=%f alignment_score=%f\n", (double)r.chains[c].chaining_score, (double)as);
+                        r.log += line;
+                    }
+                r.primary.reserve(o.n_primary);
+                for (uint32_t p = 0; p < o.n_primary; p++) {
+                    const uint32_t c = ra.re_primary[r.chain0 + p];
+                    r.chains[c].alignment_score = ra.score[r.chain0 + c];
+                    r.primary.push_back(std::move(r.chains[c]));
+                }
+                if (o.n_primary) r.primary[0].mapq = o.mapq;
+                r.high = (o.flags & RAWDTW_ROUND_HIGH) != 0;
+                return;
+            }
             std::vector<MChain> post;
             post.reserve(r.chains.size());
             for (size_t c = 0; c < r.chains.size(); c++) {
@@ -967,6 +1018,11 @@ struct Round {
             r.primary = primary_chains(m, post);
             r.high = high_confidence(m, r.primary);
         });
+        if (from_device) // (counted here, not by the pool's threads: sixteen of them adding to one counter cost the round more than its end)
+            for (size_t i = 0; i < ra.ks.size(); i++) {
+                if (rr[ra.ks[i]].skipped) continue;
+                if (ra.re_out[i].flags & RAWDTW_ROUND_DECLINED) per[gi].re_declined++; else per[gi].re_reads++;
+            }
         lap(4);
     }
 
@@ -994,6 +1050,7 @@ struct Round {
     void commit()
     {
         m->rounds = id;
+        if (per[0].round_end || per[1].round_end) m->re_rounds++;
         if (resident) {
             if (fell_back) { m->res_fallbacks++; m->res_hit_bytes += res_hits * sizeof(rawdtw_seed_hit_t); }
             else m->res_rounds++;
@@ -1006,6 +1063,7 @@ struct Round {
             g.has_prev = on_device && m->opt.carry && !m->opt.device_chain && ra.batch != nullptr;
             if (!g.has_prev && ra.batch) { rawdtw_batch_destroy(ra.batch); ra.batch = nullptr; }
             m->parts_scored += per[gi].scored; m->parts_reused += per[gi].reused;
+            m->re_reads += per[gi].re_reads; m->re_declined += per[gi].re_declined;
             for (size_t i = 0; i < ra.ks.size(); i++) { read(ra.ks[i]).last_round = id; read(ra.ks[i]).last_pos = i; }
         }
         for (uint32_t k = 0; k < n_reads; k++) {
@@ -1414,6 +1472,15 @@ int rawdtw_mapper_signal_stats(const rawdtw_mapper *m, uint64_t *rounds, uint64_
     if (retried_rounds) *retried_rounds = m->sig_retried;
     if (sample_bytes_to_device) *sample_bytes_to_device = m->sig_sample_bytes;
     if (event_bytes_crossed) *event_bytes_crossed = (uint64_t)m->timing[6]; // (the mapper sends events up and fetches none: slot 6 is all that crosses)
+    return RAWDTW_OK;
+}
+
+int rawdtw_mapper_round_end_stats(const rawdtw_mapper *m, uint64_t *rounds, uint64_t *reads_device, uint64_t *reads_declined)
+{
+    if (!m) return RAWDTW_ERR_INVALID;
+    if (rounds) *rounds = m->re_rounds;
+    if (reads_device) *reads_device = m->re_reads;
+    if (reads_declined) *reads_declined = m->re_declined;
     return RAWDTW_OK;
 }
 

@@ -27,6 +27,10 @@ JOB_DTYPE = np.dtype(
 assert JOB_DTYPE.itemsize == 32
 # ri_anchor_t (src/rmap.h:21-27)
 ANCHOR_DTYPE = np.dtype([("target_position", "<u4"), ("query_position", "<u4")])
+# rawdtw_chain_rec_t (a chain's record as rawdtw_chain_round leaves it: key = sequence * 2 + strand) and rawdtw_round_out_t
+CHAIN_REC_DTYPE = np.dtype([("chaining_score", "<f4"), ("key", "<u4"), ("start_position", "<u4"), ("end_position", "<u4"), ("n_anchors", "<u4")])
+ROUND_OUT_DTYPE = np.dtype([("n_primary", "<u4"), ("mapq", "<u4"), ("flags", "<u4")])
+ROUND_HIGH, ROUND_DECLINED, NO_PRIMARY = 1, 2, 0xFFFFFFFF
 
 
 @dataclass
@@ -48,6 +52,27 @@ def _ptr(a: np.ndarray):
 
 def _f32(x) -> np.ndarray:
     return np.ascontiguousarray(x, dtype=np.float32)
+
+
+def _round_end(lib, ctx, check, select_opt, chain_off, recs, score, keep):
+    chain_off = np.ascontiguousarray(chain_off, np.uint64)
+    n, nc = len(chain_off) - 1, int(chain_off[-1])
+    recs, score = np.ascontiguousarray(recs, CHAIN_REC_DTYPE), np.ascontiguousarray(score, np.float32)
+    keep = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+    if len(recs) < nc or len(score) < nc or (keep is not None and len(keep) < nc):
+        raise ValueError("recs, score and keep hold chain_off[-1] chains")
+    out, primary = np.zeros(max(n, 1), ROUND_OUT_DTYPE), np.zeros(max(nc, 1), np.uint32)
+    args = (C.byref(select_opt), n, _ptr(chain_off), _ptr(recs), _ptr(score), _ptr(keep) if keep is not None else None, _ptr(out), _ptr(primary))
+    check(lib.rawdtw_round_end_host(*args) if ctx is None else lib.rawdtw_round_end(ctx, *args))
+    return out[:n], primary[:nc]
+
+
+def round_end_host(select_opt, chain_off, recs, score, keep=None):
+    """rawdtw_round_end_host: the host restatement of Engine.round_end (never declines); no device is touched"""
+    def check(st):
+        if st != 0:
+            raise RawDTWError(st, "rawdtw_round_end_host")
+    return _round_end(load_library(), None, check, select_opt, chain_off, recs, score, keep)
 
 
 def plan_dry_run(jobs: np.ndarray, n_events: int, n_reference: int, threads: int = 0, options=None):
@@ -223,6 +248,19 @@ class Engine:
         v = [C.c_uint64() for _ in range(4)]
         self._check(self.lib.rawdtw_chain_round_stats(self._ctx, *[C.byref(x) for x in v]))
         return dict(zip(("rounds", "long_reads", "long_seeds", "far_steps"), (int(x.value) for x in v)))
+
+    def round_end(self, select_opt, chain_off, recs, score, keep=None):
+        """rawdtw_round_end: gen_primary_chains, comp_mapq and the stop rule for every read of a round in one launch.  `select_opt` is a
+        SelectOpt (mapping.StopOpt.c_struct); read r's candidates are [chain_off[r], chain_off[r+1]) of recs (CHAIN_REC_DTYPE), score and
+        keep.  Returns (out: ROUND_OUT_DTYPE a read, primary: uint32 a chain); a read with flag ROUND_DECLINED is the caller's to end with
+        round_end_host."""
+        return _round_end(self.lib, self._ctx, self._check, select_opt, chain_off, recs, score, keep)
+
+    def chain_round_recs(self) -> int:
+        """rawdtw_chain_round_recs: the device address of the ended chaining round's records (valid until the next chaining round)"""
+        p = C.c_void_p()
+        self._check(self.lib.rawdtw_chain_round_recs(self._ctx, C.byref(p)))
+        return p.value or 0
 
     def stream_handle(self) -> int:
         s = C.c_void_p()

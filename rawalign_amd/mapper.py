@@ -702,6 +702,15 @@ class CMapper:
         self._check(self.lib.rawdtw_mapper_resident_stats(self._h, *[C.byref(x) for x in v]))
         return dict(resident_rounds=v[0].value, fallback_rounds=v[1].value, hit_bytes_to_host=v[2].value, seed_bytes_to_device=v[3].value)
 
+    def round_end_stats(self):
+        """rawdtw_mapper_round_end_stats: with the context's "device_round_end" on -- committed rounds whose end ran on the device, the reads
+        it ended, the reads it declined (ended on the host)"""
+        import ctypes as C
+
+        v = [C.c_uint64() for _ in range(3)]
+        self._check(self.lib.rawdtw_mapper_round_end_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(rounds=v[0].value, reads_device=v[1].value, reads_declined=v[2].value)
+
     def timing(self):
         t = np.zeros(8, np.float64)
         self._check(self.lib.rawdtw_mapper_timing(self._h, _vp(t)))
