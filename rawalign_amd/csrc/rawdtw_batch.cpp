@@ -5,9 +5,15 @@
 // Host code only.
 #include "rawdtw_capi.h"
 #include "rawdtw_plan_check.h"
+#include "rawdtw_stream_layout.h"
 
 using namespace rawdtw;
 using namespace rawdtw::capi;
+
+static_assert(stream::kCounterBytes == kStreamCounters * 8 && stream::kChainDescBytes == sizeof(ChainDesc), "the two sizes rawdtw_stream_layout.h names");
+
+// a region of a workspace block as a pointer
+template <typename T> static T *at(char *block, const ws::Region &r) { return reinterpret_cast<T *>(block + r.at); }
 
 extern "C" {
 
@@ -19,12 +25,6 @@ extern "C" {
 //   job list (everything else, and the rare batch the stream path declines): the jobs are built on the host and go
 //           through plan_host / build_plan like any rawdtw_plan.
 namespace {
-
-struct StreamLayout { // sizes in bytes of one batch's device workspace and pinned host block
-    size_t dev = 0, host = 0, tmp = 0;
-    uint64_t others_cap = 0;
-    uint32_t tiles_cap = 0;
-};
 
 // LDS image of a device-planned batch's tiles, in floats.  With four workgroups a CU (stream_blocks_per_cu) a SIMD keeps
 // 128 registers free beside the DTW launch's waves -- room for a wave of the next batches' planning kernels or of the
@@ -104,8 +104,15 @@ int batch_create_stream(rawdtw_ctx *ctx, rawdtw_batch *b, const uint64_t *chain_
     // give the fold its offsets)
     const rawdtw_batch *prev = b->in_prev;
     const bool round = prev != nullptr; // (rawdtw_batch_submit_carry checked that it can serve: rawdtw_batch_can_carry)
+    const bool compact = b->in_steps != nullptr;
     const uint64_t nc = b->n_chains, nr = b->n_reads, n_full = anchor_off[nc], na = round ? b->in_new_off[nc] : n_full;
     const uint32_t lds_floats = stream_tile_floats(ctx);
+    // where everything lies: rawdtw_stream_layout.h
+    const stream::Layout L = stream::layout({nr, nc, na, n_full, compact ? stream::Kind::compact : round ? stream::Kind::round : stream::Kind::plain,
+                                             b->in_n_wide, ctx->pass_pool});
+    int st = ws_acquire(ctx, L.need, L.pin_need, &b->ws);
+    if (st != RAWDTW_OK) return st;
+    char *const d = b->ws.d, *const h = b->ws.h;
     StreamArgs &a = b->sa;
     a = StreamArgs{};
     a.n_anchors = na; a.n_chains = nc; a.n_reads = nr; a.n_ev = ctx->n_ev; a.n_ref = ctx->n_ref;
@@ -114,100 +121,60 @@ int batch_create_stream(rawdtw_ctx *ctx, rawdtw_batch *b, const uint64_t *chain_
     // list's lane classes
     a.lane_max_radius = std::min(ctx->lane_max_radius, ctx->stream_tile_radius); a.side_lane_radius = ctx->lane_max_radius;
     a.lane_max_n = ctx->lane_max_n;
-    a.tile_anchors = kStreamTile;
-    a.n_tiles = (uint32_t)((na + a.tile_anchors - 1) / a.tile_anchors);
-    // (a tile over the image budget or the run table takes further passes, a slot of copy orders each: rare in a mapper's
-    // batch, the rule for tiles of very short chains; a batch that runs out of slots is redone through the job list)
-    a.n_slots = ctx->pass_pool >= 0 ? a.n_tiles + (uint32_t)ctx->pass_pool : 4 * a.n_tiles + 64;
+    // (a batch that runs out of slots is redone through the job list)
+    a.tile_anchors = kStreamTile; a.n_tiles = L.n_tiles; a.n_slots = L.n_slots; a.others_cap = L.others_cap;
     a.lds_floats = lds_floats;
-    a.others_cap = std::min<uint64_t>(na, na / 4 + 4096);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const bool compact = b->in_steps != nullptr;
-    const uint64_t n_units = (na + RAWDTW_COMPACT_STRIDE - 1) / RAWDTW_COMPACT_STRIDE;
-    const size_t compact_bytes = compact ? al(nc * 8) + al(n_units * 8) + al(n_units * RAWDTW_COMPACT_STRIDE * 2) + al(b->in_n_wide * sizeof(rawdtw_wide_step_t)) : 0;
-    const size_t round_bytes = round ? al(nc * sizeof(rawdtw_carry_t)) + al((nc + 1) * 8) + al(n_full * 4) : 0;
-    const size_t dev_bytes = compact_bytes + round_bytes +
-                             al(kStreamCounters * 8) + al((nc + 1) * 8) + al(na * 8) + al(nc * 8) + al(nc * 4) + al((nr + 1) * 8) + // counters, inputs
-                             al((size_t)a.n_tiles * 8) + al((size_t)a.n_slots * 16) + al((size_t)a.n_tiles * 24) +               // tile list, work list, statistics
-                             al((size_t)a.n_tiles * kStreamRecStride * 8) + al((size_t)a.n_slots * 2 * kStreamMaxSeg * 16) +         // job records, copy orders
-                             2 * al(a.others_cap * sizeof(DevJob)) + al(a.others_cap) +                                           // side list
-                             al(nc * sizeof(ChainDesc)) + 4 * al(nc * 4) + al(nc) + al(na * 4);                                   // fold, results
-    const size_t host_bytes = al(kStreamCounters * 8) + al(nc * 4) + al(nc);
-    int st = ws_acquire(ctx, dev_bytes, host_bytes, &b->ws);
-    if (st != RAWDTW_OK) return st;
-    char *p = b->ws.d;
-    a.cnt = carve<unsigned long long>(p, kStreamCounters);
-    b->d_score = carve<float>(p, nc); b->d_keep = carve<uint8_t>(p, nc); // (right behind the counters: one copy brings all three home)
-    b->res_bytes = (size_t)(reinterpret_cast<char *>(b->d_keep) - reinterpret_cast<char *>(a.cnt)) + nc;
-    uint64_t *d_anchor_off = carve<uint64_t>(p, nc + 1);
-    rawdtw_anchor_t *d_anchors = carve<rawdtw_anchor_t>(p, na);
-    uint64_t *d_ref_base = carve<uint64_t>(p, nc);
-    uint32_t *d_read_base = carve<uint32_t>(p, nc);
-    b->d_chain_off = carve<uint64_t>(p, nr + 1);
-    a.tlist = carve<uint2>(p, a.n_tiles);
-    a.todo = carve<uint4>(p, a.n_slots);
-    a.recs = carve<uint2>(p, (uint64_t)a.n_tiles * kStreamRecStride);
-    a.runtab = carve<uint4>(p, (uint64_t)a.n_slots * 2 * kStreamMaxSeg);
-    a.tile_stats = carve<unsigned long long>(p, 3ull * a.n_tiles);
-    a.omix = carve<DevJob>(p, a.others_cap); a.ojobs = carve<DevJob>(p, a.others_cap); a.ocls = carve<uint8_t>(p, a.others_cap);
-    b->d_chains = carve<ChainDesc>(p, nc);
-    b->d_fold_order = carve<uint32_t>(p, nc);
-    b->d_full = carve<float>(p, nc); b->d_gate = carve<float>(p, nc);
-    a.out = carve<float>(p, na);
     a.debug = ctx->stream_debug;
-    a.anchor_off = d_anchor_off; a.anchors = d_anchors; a.ref_base = d_ref_base; a.read_base = d_read_base;
-    if (b->in_resident) { a.anchors = round ? b->in_new_anchors : anchors; a.ref_base = ref_base; a.read_base = read_base; } // used in place
-    rawdtw_anchor_t *d_heads = nullptr, *d_unit_abs = nullptr;
-    uint16_t *d_steps = nullptr;
-    rawdtw_wide_step_t *d_wide = nullptr;
-    if (compact) { // the packed lists; k_scan decodes them into d_anchors
-        d_heads = carve<rawdtw_anchor_t>(p, nc); d_unit_abs = carve<rawdtw_anchor_t>(p, n_units);
-        d_steps = carve<uint16_t>(p, n_units * RAWDTW_COMPACT_STRIDE); d_wide = carve<rawdtw_wide_step_t>(p, b->in_n_wide);
-        a.heads = d_heads; a.unit_abs = d_unit_abs; a.steps = d_steps; a.wide = d_wide; a.n_wide = b->in_n_wide; a.anchors_w = d_anchors;
-    }
     a.ev = ctx->d_ev; a.ref = ctx->d_ref;
-    rawdtw_carry_t *d_carry = nullptr;
-    uint64_t *d_full_off = nullptr;
-    a.full_off = d_anchor_off; a.n_full = n_full; a.out_full = a.out; // (no predecessor: the lists are the full ones)
+    a.cnt = at<unsigned long long>(d, L.cnt);
+    b->d_score = at<float>(d, L.score); b->d_keep = at<uint8_t>(d, L.keep); b->res_bytes = L.res_bytes; // (right behind the counters: one copy brings all three home)
+    b->d_chain_off = at<uint64_t>(d, L.chain_off);
+    a.tlist = at<uint2>(d, L.tlist); a.todo = at<uint4>(d, L.todo); a.recs = at<uint2>(d, L.recs); a.runtab = at<uint4>(d, L.runtab);
+    a.tile_stats = at<unsigned long long>(d, L.tile_stats);
+    a.omix = at<DevJob>(d, L.omix); a.ojobs = at<DevJob>(d, L.ojobs); a.ocls = at<uint8_t>(d, L.ocls);
+    b->d_chains = at<ChainDesc>(d, L.chains); b->d_fold_order = at<uint32_t>(d, L.fold_order);
+    b->d_full = at<float>(d, L.full); b->d_gate = at<float>(d, L.gate);
+    a.out = at<float>(d, L.out);
+    a.anchor_off = at<uint64_t>(d, L.anchor_off);
+    // ("resident_arrays": the three big arrays are device pointers, used in place; their regions stay unused)
+    const rawdtw_anchor_t *const lists = round ? b->in_new_anchors : anchors; // (a round: only its NEW anchors, and the junctions, cross the bus)
+    a.anchors = b->in_resident ? lists : at<rawdtw_anchor_t>(d, L.anchors);
+    a.ref_base = b->in_resident ? ref_base : at<uint64_t>(d, L.ref_base);
+    a.read_base = b->in_resident ? read_base : at<uint32_t>(d, L.read_base);
+    if (compact) { // the packed lists; k_scan decodes them into the anchors' region
+        a.heads = at<rawdtw_anchor_t>(d, L.heads); a.unit_abs = at<rawdtw_anchor_t>(d, L.unit_abs);
+        a.steps = at<uint16_t>(d, L.steps); a.wide = at<rawdtw_wide_step_t>(d, L.wide); a.n_wide = b->in_n_wide;
+        a.anchors_w = at<rawdtw_anchor_t>(d, L.anchors);
+    }
+    a.full_off = a.anchor_off; a.n_full = n_full; a.out_full = a.out; // (no predecessor: the lists are the full ones)
     if (round) { // (the previous batch's cost array is read by this batch's k_gather: stream order keeps it alive that long)
-        d_carry = carve<rawdtw_carry_t>(p, nc); d_full_off = carve<uint64_t>(p, nc + 1);
-        a.out_full = carve<float>(p, n_full);
-        a.carry = d_carry; a.full_off = d_full_off;
+        a.carry = at<rawdtw_carry_t>(d, L.carry); a.full_off = at<uint64_t>(d, L.full_off); a.out_full = at<float>(d, L.out_full);
         a.prev_out_full = prev->sa.out_full; a.prev_n_full = prev->sa.n_full;
         a.prev_cnt = prev->sa.cnt; a.prev_others_cap = prev->sa.others_cap;
     }
-    char *hp = b->ws.h;
-    b->h_cnt = carve<unsigned long long>(hp, kStreamCounters);
-    b->h_score = carve<float>(hp, nc); b->h_keep = carve<uint8_t>(hp, nc); // (same offsets as on the device)
+    b->h_cnt = at<unsigned long long>(h, L.p_cnt); b->h_score = at<float>(h, L.p_score); b->h_keep = at<uint8_t>(h, L.p_keep); // (same offsets as on the device)
     unsigned long long *h_init = b->h_cnt; // the counters' initial values travel from the pinned block
     for (int i = 0; i < kStreamCounters; i++) h_init[i] = 0;
     h_init[kCntBad] = h_init[kCntOverflow] = ~0ull;
     hipStream_t s = ctx->stream;
     if (ctx->time_plan) for (hipEvent_t &pe : b->ev_plan) if (!pe) HIP_TRY(ctx, hipEventCreate(&pe));
-    HIP_TRY(ctx, hipMemcpyAsync(a.cnt, h_init, kStreamCounters * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d_anchor_off, round ? b->in_new_off : anchor_off, (nc + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d + L.cnt.at, h_init, stream::kCounterBytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d + L.anchor_off.at, round ? b->in_new_off : anchor_off, (nc + 1) * 8, hipMemcpyHostToDevice, s));
     if (compact) {
-        HIP_TRY(ctx, hipMemcpyAsync(d_heads, b->in_heads, nc * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemcpyAsync(d_unit_abs, b->in_unit_abs, n_units * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemcpyAsync(d_steps, b->in_steps, na * 2, hipMemcpyHostToDevice, s));
-        if (b->in_n_wide) HIP_TRY(ctx, hipMemcpyAsync(d_wide, b->in_wide, b->in_n_wide * sizeof(rawdtw_wide_step_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemcpyAsync(d_ref_base, ref_base, nc * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemcpyAsync(d_read_base, read_base, nc * 4, hipMemcpyHostToDevice, s));
-    } else if (round) { // only the round's NEW anchors (and the junctions) cross the bus
-        HIP_TRY(ctx, hipMemcpyAsync(d_carry, b->in_carry, nc * sizeof(rawdtw_carry_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemcpyAsync(d_full_off, anchor_off, (nc + 1) * 8, hipMemcpyHostToDevice, s));
-        if (b->in_resident) a.anchors = b->in_new_anchors; // ("resident_arrays": the three big arrays are device pointers, used in place)
-        else {
-            if (na) HIP_TRY(ctx, hipMemcpyAsync(d_anchors, b->in_new_anchors, na * sizeof(rawdtw_anchor_t), hipMemcpyHostToDevice, s));
-            HIP_TRY(ctx, hipMemcpyAsync(d_ref_base, ref_base, nc * 8, hipMemcpyHostToDevice, s));
-            HIP_TRY(ctx, hipMemcpyAsync(d_read_base, read_base, nc * 4, hipMemcpyHostToDevice, s));
-        }
-    } else if (!b->in_resident) {
-        HIP_TRY(ctx, hipMemcpyAsync(d_anchors, anchors, na * sizeof(rawdtw_anchor_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemcpyAsync(d_ref_base, ref_base, nc * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemcpyAsync(d_read_base, read_base, nc * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d + L.heads.at, b->in_heads, nc * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d + L.unit_abs.at, b->in_unit_abs, L.n_units * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d + L.steps.at, b->in_steps, na * 2, hipMemcpyHostToDevice, s));
+        if (b->in_n_wide) HIP_TRY(ctx, hipMemcpyAsync(d + L.wide.at, b->in_wide, b->in_n_wide * sizeof(rawdtw_wide_step_t), hipMemcpyHostToDevice, s));
+    } else if (round) {
+        HIP_TRY(ctx, hipMemcpyAsync(d + L.carry.at, b->in_carry, nc * sizeof(rawdtw_carry_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d + L.full_off.at, anchor_off, (nc + 1) * 8, hipMemcpyHostToDevice, s));
     }
-    HIP_TRY(ctx, hipMemcpyAsync(b->d_chain_off, chain_off, (nr + 1) * 8, hipMemcpyHostToDevice, s));
+    if (!b->in_resident) { // what the three kinds share (a compact batch's anchors are decoded on the device)
+        if (!compact && na) HIP_TRY(ctx, hipMemcpyAsync(d + L.anchors.at, lists, na * sizeof(rawdtw_anchor_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d + L.ref_base.at, ref_base, nc * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d + L.read_base.at, read_base, nc * 4, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(d + L.chain_off.at, chain_off, (nr + 1) * 8, hipMemcpyHostToDevice, s));
     b->fold_fused = ctx->fold_mode == 4; // (no fold order then: the one-workgroup sort stays off the scan's critical path)
     if (ctx->time_plan) HIP_TRY(ctx, hipEventRecord(b->ev_plan[0], s)); // ("time_plan": the planning LAUNCHES, behind the hand-over's copies)
     hipError_t e = stream_plan(a, b->d_chains, b->fold_fused ? nullptr : b->d_fold_order, s);
@@ -241,7 +208,7 @@ int batch_create_stream(rawdtw_ctx *ctx, rawdtw_batch *b, const uint64_t *chain_
     b->n_jobs = 0; b->jobs_counted = false;
     b->cnt_valid = false;
     b->dirty = true;
-    b->ws_bytes = dev_bytes;
+    b->ws_bytes = L.need;
     return RAWDTW_OK;
 }
 
@@ -374,6 +341,13 @@ int batch_create_joblist(rawdtw_ctx *ctx, rawdtw_batch *b, const uint64_t *chain
     return RAWDTW_OK;
 }
 
+// forget the device pointers: into the workspace, or at the job-list form's own arrays (handed back or freed by the caller)
+void batch_forget_arrays(rawdtw_batch *b)
+{
+    b->d_chains = nullptr; b->d_chain_off = nullptr; b->d_fold_order = nullptr;
+    b->d_full = b->d_gate = b->d_score = nullptr; b->d_keep = nullptr;
+}
+
 void batch_release_device(rawdtw_batch *b)
 {
     if (b->plan) { rawdtw_plan_destroy(b->plan); b->plan = nullptr; }
@@ -386,8 +360,7 @@ void batch_release_device(rawdtw_batch *b)
         if (b->d_score) (void)hipFree(b->d_score);
         if (b->d_keep) (void)hipFree(b->d_keep);
     }
-    b->d_chains = nullptr; b->d_chain_off = nullptr; b->d_fold_order = nullptr;
-    b->d_full = b->d_gate = b->d_score = nullptr; b->d_keep = nullptr;
+    batch_forget_arrays(b);
     b->own_chain_arrays = false;
 }
 
@@ -395,7 +368,7 @@ void batch_release_device(rawdtw_batch *b)
 int stream_counters(rawdtw_ctx *ctx, rawdtw_batch *b)
 {
     if (b->cnt_valid) return RAWDTW_OK;
-    HIP_TRY(ctx, hipMemcpyAsync(b->h_cnt, b->sa.cnt, kStreamCounters * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(b->h_cnt, b->sa.cnt, stream::kCounterBytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     b->cnt_valid = true;
     b->dirty = false;
@@ -423,8 +396,7 @@ int stream_fallback(rawdtw_ctx *ctx, rawdtw_batch *b)
     b->stream = false; b->jobs_counted = true; // (batch_create_joblist sets n_jobs)
     ws_release(ctx, b->ws);
     b->h_cnt = nullptr; b->h_score = nullptr; b->h_keep = nullptr; b->res_bytes = 0; // (they lay in the workspace)
-    b->d_chains = nullptr; b->d_chain_off = nullptr; b->d_fold_order = nullptr;
-    b->d_full = b->d_gate = b->d_score = nullptr; b->d_keep = nullptr;
+    batch_forget_arrays(b);
     st = batch_create_joblist(ctx, b, b->in_chain_off, b->in_anchor_off, b->in_anchors, b->in_ref_base, b->in_read_base, job_off, n_jobs);
     if (st != RAWDTW_OK) { batch_release_device(b); return st; }
     return rawdtw_batch_run(ctx, b);
@@ -581,7 +553,7 @@ static int stream_plan_download(rawdtw_ctx *ctx, const rawdtw_batch *batch, Stre
     v.n_first = cnt[kCntTodo]; v.n_pool = cnt[kCntPool]; v.n_other = cnt[kCntOthers]; v.n_reused = cnt[kCntReused];
     v.anchor_off = batch->in_anchor_off;
     if (!v.fits_slots()) return RAWDTW_OK;
-    constexpr size_t kRT = 2 * kStreamMaxSeg;
+    constexpr size_t kRT = stream::kSlotOrders;
     h.todo.resize(v.n_todo()); h.runtab.resize(v.n_todo() * kRT);
     h.recs.resize((size_t)a.n_tiles * kStreamRecStride); h.side.resize(v.n_other);
     if (v.n_first) {
@@ -978,7 +950,7 @@ int rawdtw_batch_fetch(rawdtw_ctx *ctx, rawdtw_batch *batch, float *score, uint8
         } else if (job_cost && !batch->stream && batch->n_jobs)
             HIP_TRY(ctx, hipMemcpyAsync(job_cost, d_cost, batch->n_jobs * 4, hipMemcpyDeviceToHost, ctx->stream));
         if (batch->stream && !batch->cnt_valid && !block)
-            HIP_TRY(ctx, hipMemcpyAsync(batch->h_cnt, batch->sa.cnt, kStreamCounters * 8, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(batch->h_cnt, batch->sa.cnt, stream::kCounterBytes, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         batch->dirty = false;
         if (!batch->stream) return RAWDTW_OK;

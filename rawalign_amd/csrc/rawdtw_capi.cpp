@@ -3,6 +3,7 @@
 //
 // There is NO CPU fallback in here: every scoring entry point runs the HIP kernels or returns an error status.
 #include "rawdtw_capi.h"
+#include "rawdtw_stream_layout.h"
 
 using namespace rawdtw;
 using namespace rawdtw::capi;
@@ -362,18 +363,18 @@ int rawdtw_events_append(rawdtw_ctx *ctx, const float *h_new, uint64_t n_new, ui
             return fail(ctx, RAWDTW_ERR_RANGE, "segment outside the reserved event arena");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // staging on the device: the round's events and the two segment tables (grow-only)
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t need = al(n_new * 4) + al(((size_t)n_segments + 1) * 8) + al((size_t)n_segments * 4);
+    const stream::AppendLayout L = stream::append_layout(n_new, n_segments);
+    const size_t need = L.need;
     if (ctx->append_bytes < need) {
         if (ctx->d_append) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->d_append); }
         ctx->d_append = nullptr; ctx->append_bytes = 0;
         HIP_TRY(ctx, hipMalloc(&ctx->d_append, need + need / 4));
         ctx->append_bytes = need + need / 4;
     }
-    char *p = static_cast<char *>(ctx->d_append);
-    float *d_new = carve<float>(p, n_new);
-    uint64_t *d_src = carve<uint64_t>(p, (uint64_t)n_segments + 1);
-    uint32_t *d_dst = carve<uint32_t>(p, n_segments);
+    char *const p = static_cast<char *>(ctx->d_append);
+    float *d_new = reinterpret_cast<float *>(p + L.ev.at);
+    uint64_t *d_src = reinterpret_cast<uint64_t *>(p + L.src.at);
+    uint32_t *d_dst = reinterpret_cast<uint32_t *>(p + L.dst.at);
     if (n_new) HIP_TRY(ctx, hipMemcpyAsync(d_new, h_new, n_new * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_src, seg_src_off, ((size_t)n_segments + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_dst, seg_dst_off, (size_t)n_segments * 4, hipMemcpyHostToDevice, ctx->stream));

@@ -592,3 +592,121 @@ def test_round_carry_takes_over_unchanged_parts(oracle):
         lib.rawdtw_batch_destroy(hb)
     lib.rawdtw_batch_destroy(h)
     eng.close()
+
+
+def _first_anchors(arrays, n):
+    """The batch's first `n` anchors: the chain that holds anchor n - 1 keeps its list's entries up to it (lists are end-first: it
+    loses parts at its start), the chains and reads behind it go."""
+    events, chain_off, anchor_off, anchors, slot, read_base = arrays
+    nc = int(np.searchsorted(anchor_off, n, side="left"))
+    nr = int(np.searchsorted(chain_off, nc, side="left"))
+    anchor_off, chain_off = anchor_off[:nc + 1].copy(), chain_off[:nr + 1].copy()
+    anchor_off[-1], chain_off[-1] = n, nc
+    return events, chain_off, anchor_off, anchors[:n], slot[:nc], read_base[:nc]
+
+
+def test_pooled_workspace_taken_again_by_another_kind():
+    """One context, its pooled workspaces handed from kind to kind: a compact batch, a plain one, a carried round on top of the plain
+    one and a resident-arrays batch, twice round, the inputs' sizes changing from one batch to the next -- 513 anchors (two tiles, the
+    second with one anchor), a round of some 1 000 and its next of some 1 500, a single chain -- so that a block laid out for one kind is taken again, from the pool, for
+    another (rawdtw_stream_layout.h: every kind's regions from one description).  Every batch's scores, keeps and part costs equal,
+    bit for bit, a plain batch of the same input on a fresh context (which the cases above pin to the oracle); the plan's self-check
+    holds for the forms that ra.Batch drives."""
+    if torch is None:
+        pytest.skip("torch not importable")
+    rng = np.random.default_rng(513)
+    ref = [rng.normal(size=90000).astype(np.float32), rng.normal(size=90000).astype(np.float32)]
+    owner = ra.Engine(0)
+    owner.upload_reference([ref[0]], [ref[1]])
+    opt = ra.MapOpt(dtw_min_score=5.0)
+    copt = opt.c_struct()
+    vp = lambda x: C.c_void_p(x.ctypes.data)  # noqa: E731
+
+    def sharing():
+        e = ra.Engine(0)
+        e._check(e.lib.rawdtw_share_reference(e._ctx, owner._ctx))
+        return e
+
+    def batch_of(arrays):
+        events, chain_off, anchor_off, anchors, slot, read_base = arrays
+        ref_base = np.array([owner.reference_offset(0, 1 if s == 0 else 0) for s in slot], np.uint64)
+        return CandidateBatch(events, chain_off, anchor_off, anchors, ref_base, read_base)
+
+    def fresh(cb):  # the reference: a plain batch on a context that has seen nothing else
+        e = sharing()
+        e.upload_events(cb.events)
+        b = ra.Batch(e, opt, cb)
+        b.run()
+        want = b.fetch(with_job_costs=True)
+        b.close()
+        e.close()
+        return want
+
+    def same(got, want):
+        for x, y in zip(got, want):
+            assert np.array_equal(np.asarray(x).view(np.uint8), np.asarray(y).view(np.uint8))
+
+    cb513 = batch_of(_first_anchors(_chains(rng, 12, 90000, _medium, (20, 60)), 513))
+    one = _chains(rng, 1, 90000, _medium, (30, 60))
+    cb_one = batch_of(_first_anchors(one, int(one[2][1])))
+    eng = sharing()
+    lib = eng.lib
+    cb1, cb2, prev_read, expect = _two_rounds(rng, eng, n_reads=22)
+    assert len(cb513.anchors) == 513 and cb_one.n_chains == 1 and 1400 < len(cb2.anchors) < 1600 and int(expect.sum()) > 100
+    want = {id(cb): fresh(cb) for cb in (cb513, cb_one, cb1, cb2)}
+
+    def compact(cb):
+        eng.upload_events(cb.events)
+        b = ra.Batch(eng, opt, cb, compact=True)
+        assert b.verify_plan() is True
+        same(b.fetch(with_job_costs=True), want[id(cb)])
+        b.close()
+
+    def plain_then_carried():
+        eng.upload_events(cb2.events)
+        b1 = ra.Batch(eng, opt, cb1)
+        assert b1.verify_plan() is True
+        b1.run()
+        same(b1.fetch(with_job_costs=True), want[id(cb1)])
+        arr, carry, new_off, new_anchors = _match(lib, cb2, cb1, prev_read)
+        assert np.array_equal(carry["parts"].astype(np.int64), expect)
+        h = C.c_void_p()
+        eng._check(lib.rawdtw_batch_submit_carry(eng._ctx, C.byref(copt), cb2.n_reads, vp(arr[0]), vp(arr[1]), vp(arr[2]), vp(new_off), vp(new_anchors),
+                                                 vp(arr[3]), vp(arr[4]), b1._h, vp(carry), C.byref(h)))
+        w = want[id(cb2)]
+        score, keep, jc = np.zeros(cb2.n_chains, np.float32), np.zeros(cb2.n_chains, np.uint8), np.zeros(len(w[2]), np.float32)
+        eng._check(lib.rawdtw_batch_fetch(eng._ctx, h, vp(score), vp(keep), vp(jc)))
+        ru = C.c_uint64()
+        eng._check(lib.rawdtw_batch_round_stats(eng._ctx, h, None, C.byref(ru)))
+        assert ru.value == int(expect.sum())   # (scored on the device-planned path, its parts taken over: not redone through the job list)
+        same((score, keep, jc), w)
+        lib.rawdtw_batch_destroy(h)
+        b1.close()
+
+    def resident(cb):
+        eng.upload_events(cb.events)
+        t = [torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).copy()).cuda()
+             for x in (cb.anchors, np.asarray(cb.ref_base, np.uint64), np.asarray(cb.read_base, np.uint32))]
+        torch.cuda.synchronize()
+        co, ao = np.ascontiguousarray(cb.chain_off, np.uint64), np.ascontiguousarray(cb.anchor_off, np.uint64)
+        h = C.c_void_p()
+        eng.set_option("resident_arrays", 1)
+        eng._check(lib.rawdtw_batch_create(eng._ctx, C.byref(copt), cb.n_reads, vp(co), vp(ao), C.c_void_p(t[0].data_ptr()), C.c_void_p(t[1].data_ptr()),
+                                           C.c_void_p(t[2].data_ptr()), C.byref(h)))
+        eng.set_option("resident_arrays", 0)   # (a batch keeps the form it was created under)
+        eng._check(lib.rawdtw_batch_run(eng._ctx, h))
+        w = want[id(cb)]
+        score, keep, jc = np.zeros(cb.n_chains, np.float32), np.zeros(cb.n_chains, np.uint8), np.zeros(len(w[2]), np.float32)
+        eng._check(lib.rawdtw_batch_fetch(eng._ctx, h, vp(score), vp(keep), vp(jc)))
+        same((score, keep, jc), w)
+        n_cnt = C.c_uint32()
+        eng._check(lib.rawdtw_batch_stream_counters(eng._ctx, h, None, 0, C.byref(n_cnt)))
+        assert n_cnt.value > 0   # (still the device-planned form after its fetch: not redone through the job list, whose batch has no counters)
+        lib.rawdtw_batch_destroy(h)
+
+    for small, smaller in ((cb513, cb_one), (cb_one, cb513)):
+        compact(small)
+        plain_then_carried()
+        resident(smaller)
+    eng.close()
+    owner.close()
