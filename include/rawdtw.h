@@ -1022,6 +1022,75 @@ int rawdtw_batch_round_end_fetch(rawdtw_ctx *ctx, rawdtw_batch *batch, rawdtw_ro
 int rawdtw_chain_round_recs(rawdtw_ctx *ctx, const rawdtw_chain_rec_t **d_recs);
 int rawdtw_mapper_round_end_stats(const rawdtw_mapper *m, uint64_t *rounds, uint64_t *reads_device, uint64_t *reads_declined);
 
+/* ---- the kept chains: a round's primary chains stay on the device as the next round's previous seeds.  gen_chains re-seeds a round with
+ * the anchors of the chains the read kept from the round before (rmap.cpp:344-357); a round that ends on the device has them in the
+ * chaining workspace and knows which are primary, so they need not come up from the host again (12 bytes each).
+ * THE STORE, one a context: n_slots x 2 halves of N rawdtw_seed_t each and one uint32_t count a half.  A store address is slot * 2 + half.
+ * Two halves a slot, so that a round writes the half a read is NOT seeded from and a failed round leaves the other as it was.
+ *   rawdtw_chain_keep_reserve     grow-only: at least n_slots slots of at least seeds_per_half (1 .. 2^20) seeds.  A store that grows loses
+ *        its contents (every half reads RAWDTW_NOT_KEPT again); RAWDTW_ERR_OOM with nothing changed when the allocation fails; freed with
+ *        the context.
+ * WHAT IS KEPT for read r (its primary chains p = 0 .. out[r].n_primary - 1, best first; chain c = chain_off[r] + primary[chain_off[r] + p]):
+ * the chains one after the other, each chain's anchors in the order they lie, as {recs[c].key, target_position, query_position} -- the
+ * list the mapper builds from a read's chains for the next round.  Nothing is kept and the count reads RAWDTW_NOT_KEPT for a read the
+ * round end declined (RAWDTW_ROUND_DECLINED), a read whose total is above the cap (N), and a read with dst[r] == RAWDTW_NO_KEEP; such a
+ * half's seeds are left as they are.  A read without a primary chain keeps a count of 0.
+ *   rawdtw_round_keep_host        the host restatement, what the device forms are tested against byte for byte: kept_count[n_reads],
+ *        seed_off_out[n_reads + 1] and the kept reads' seeds, dense, in seeds_out (room for every anchor of the round; NULL: counts and
+ *        offsets only).  RAWDTW_ERR_INVALID for a null argument, offsets that descend, or a primary index outside its read.
+ *   rawdtw_round_keep             the host arrays go up, one launch (a wave a read), kept_count[n_reads] comes home; read r's seeds go to
+ *        the store's half dst[r].  For tests on constructed rounds.  RAWDTW_ERR_INVALID as the host form, and for no store, a dst outside
+ *        it, the same address twice, or a chain whose anchor_off stretch is not its n_anchors.
+ *   rawdtw_batch_round_end_keep   enqueued on the context's stream behind a begun rawdtw_batch_round_end_begin of a batch from
+ *        rawdtw_batch_submit_device whose records are the context's ended chaining round's (rawdtw_chain_round_recs): reads out, primary,
+ *        recs, anchor_off and anchors where they lie.  RAWDTW_ERR_INVALID before anything is enqueued: no round end begun for this batch,
+ *        no ended chaining round, no store, a dst outside the store, the same address twice.
+ *   rawdtw_batch_round_keep_fetch after rawdtw_batch_round_end_fetch: kept_count[n_reads] (4 bytes a read).  When the round end ran again
+ *        at its fetch (a batch the device-planned path declined), the keep launch runs again behind it first.  The context keeps a host
+ *        mirror of every half's count, updated here; a half is RAWDTW_NOT_KEPT in the mirror from the keep's enqueue until this call.
+ *   rawdtw_chain_kept_fetch       for tests: the half's count into *n (RAWDTW_NOT_KEPT included) and its first `cap` seeds (cap <= N)
+ *        into `seeds`, whatever the count says.
+ *   rawdtw_chain_round_begin_resident_kept  rawdtw_chain_round_begin_resident with a source per read: prev_src[r] == RAWDTW_PREV_HOST takes
+ *        the read's prev_off stretch of prev_seeds as before; a store address takes the half's seeds -- the read's prev_off stretch must
+ *        be empty and its seed_off stretch the mirror's count of that half plus its chunk's hits.  RAWDTW_ERR_INVALID before anything is
+ *        enqueued: an address outside the store, a half whose mirror count is RAWDTW_NOT_KEPT (or that was never written), a read that
+ *        sits out and has a source, a wrong stretch.  The keep launch of round N and this round's writer launch are on the context's
+ *        stream, in that order.
+ *   rawdtw_get_option(ctx, "round_keep_kernel_us")  read-only: the context's most recently fetched keep launch between its HIP events.
+ *   rawdtw_set_option(ctx, "resident_chains", N)  on the context a mapper was created with, N = 1 .. 2^20 seeds a read: a resident round
+ *        (rawdtw_mapper_round_seeded_resident, _signal_resident, _raw_resident) whose end is enqueued on the device ("device_round_end")
+ *        keeps every read's primary chains in the store (reserved for the mapper's max_reads slots at the first such round; a failed
+ *        reserve fails the round) and the next such round takes the read's previous seeds from there.  The host's copy of the chains
+ *        stays as it is: fall-backs, rawdtw_mapper_finish and the lines read it, and lines, logs and counters are the same either way
+ *        -- except rawdtw_mapper_resident_stats' seed_bytes_to_device, which counts what is actually sent up.  A read is seeded from the
+ *        host again after anything else changed its chains: a round chained or ended on the host, a read the round end declined or
+ *        whose anchors are more than N, rawdtw_mapper_round and rawdtw_mapper_round_seeded.  A read that sits a round out keeps its
+ *        half; a failed round changes nothing.  Should a read's kept count ever differ from its chains on the host, the round fails with
+ *        RAWDTW_ERR_DEVICE.  0 (the default): no such call is made.  The option is read once a round.  The store's slots are the
+ *        mapper's read slots: one mapper a context uses it at a time.
+ *   rawdtw_mapper_kept_stats  over committed rounds that used the store: reads with at least one previous seed that took them from the
+ *        device / from the host, those seeds, and reads whose chains a keep launch did not keep.  Any pointer may be NULL. ---- */
+#define RAWDTW_NOT_KEPT 0xffffffffu
+#define RAWDTW_NO_KEEP 0xffffffffu
+#define RAWDTW_PREV_HOST 0xffffffffu
+int rawdtw_chain_keep_reserve(rawdtw_ctx *ctx, uint64_t n_slots, uint64_t seeds_per_half);
+int rawdtw_mapper_kept_stats(const rawdtw_mapper *m, uint64_t *reads_from_device, uint64_t *reads_from_host, uint64_t *seeds_from_device,
+                             uint64_t *seeds_from_host, uint64_t *reads_not_kept);
+int rawdtw_round_keep_host(uint64_t n_reads, const uint64_t *chain_off, const rawdtw_chain_rec_t *recs, const uint64_t *anchor_off,
+                           const rawdtw_anchor_t *anchors, const rawdtw_round_out_t *out, const uint32_t *primary, uint32_t cap,
+                           uint32_t *kept_count, uint64_t *seed_off_out, rawdtw_seed_t *seeds_out);
+int rawdtw_round_keep(rawdtw_ctx *ctx, uint64_t n_reads, const uint64_t *chain_off, const rawdtw_chain_rec_t *recs,
+                      const uint64_t *anchor_off, const rawdtw_anchor_t *anchors, const rawdtw_round_out_t *out, const uint32_t *primary,
+                      const uint32_t *dst, uint32_t *kept_count);
+int rawdtw_batch_round_end_keep(rawdtw_ctx *ctx, rawdtw_batch *batch, const uint32_t *dst);
+int rawdtw_batch_round_keep_fetch(rawdtw_ctx *ctx, rawdtw_batch *batch, uint32_t *kept_count);
+int rawdtw_chain_kept_fetch(rawdtw_ctx *ctx, uint32_t addr, rawdtw_seed_t *seeds, uint32_t cap, uint32_t *n);
+int rawdtw_chain_round_begin_resident_kept(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads, const uint64_t *seed_off,
+                                           const uint64_t *prev_off, const rawdtw_seed_t *prev_seeds, const uint32_t *prev_src,
+                                           const uint32_t *chunk_start, const uint8_t *sits_out, const uint32_t *read_base,
+                                           uint32_t n_keys, const uint64_t *key_base, uint64_t *chain_off, uint64_t *anchor_off,
+                                           rawdtw_chain_rec_t *recs, uint64_t chains_cap, rawdtw_anchor_t *anchors);
+
 #ifdef __cplusplus
 }
 #endif

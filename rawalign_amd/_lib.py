@@ -291,6 +291,14 @@ SYMBOLS = {
     "rawdtw_batch_round_end_fetch": (I32, [VP, VP, VP, VP]),
     "rawdtw_chain_round_recs": (I32, [VP, C.POINTER(VP)]),
     "rawdtw_mapper_round_end_stats": (I32, [VP, VP, VP, VP]),
+    "rawdtw_chain_keep_reserve": (I32, [VP, U64, U64]),
+    "rawdtw_round_keep_host": (I32, [U64, VP, VP, VP, VP, VP, VP, U32, VP, VP, VP]),
+    "rawdtw_round_keep": (I32, [VP, U64, VP, VP, VP, VP, VP, VP, VP, VP]),
+    "rawdtw_batch_round_end_keep": (I32, [VP, VP, VP]),
+    "rawdtw_batch_round_keep_fetch": (I32, [VP, VP, VP]),
+    "rawdtw_chain_kept_fetch": (I32, [VP, U32, VP, U32, VP]),
+    "rawdtw_chain_round_begin_resident_kept": (I32, [VP, VP, U64, VP, VP, VP, VP, VP, VP, VP, U32, VP, VP, VP, VP, U64, VP]),
+    "rawdtw_mapper_kept_stats": (I32, [VP, VP, VP, VP, VP, VP]),
 }
 
 

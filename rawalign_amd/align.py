@@ -446,6 +446,20 @@ class Batch:
         self.engine._check(self.engine.lib.rawdtw_batch_round_end_fetch(self.engine._ctx, self._h, _ptr(out), _ptr(primary)))
         return out[:self.cb.n_reads], primary[:self.cb.n_chains]
 
+    def round_end_keep(self, dst):
+        """rawdtw_batch_round_end_keep: behind a begun round end of a device-chained batch, read r's primary chains' anchors kept as seeds
+        in the half dst[r] of the context's store (NO_KEEP: nowhere)"""
+        self._keep_dst = np.ascontiguousarray(dst, np.uint32)
+        if len(self._keep_dst) < self.cb.n_reads:
+            raise ValueError("dst holds an entry a read")
+        self.engine._check(self.engine.lib.rawdtw_batch_round_end_keep(self.engine._ctx, self._h, _ptr(self._keep_dst)))
+
+    def round_keep_fetch(self):
+        """rawdtw_batch_round_keep_fetch, after round_end_fetch: kept_count (uint32 a read)"""
+        kept = np.zeros(max(self.cb.n_reads, 1), np.uint32)
+        self.engine._check(self.engine.lib.rawdtw_batch_round_keep_fetch(self.engine._ctx, self._h, _ptr(kept)))
+        return kept[:self.cb.n_reads]
+
     def close(self):
         if getattr(self, "_h", None) is not None:
             self.engine.lib.rawdtw_batch_destroy(self._h)  # (safe in any order: rawdtw_destroy detaches live batches)

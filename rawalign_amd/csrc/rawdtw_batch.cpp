@@ -1063,6 +1063,7 @@ namespace rawdtw { namespace capi {
 void batch_detach(rawdtw_ctx *ctx, rawdtw_batch *b)
 {
     round_end_forget(ctx, b); // (before the arrays a pending round end reads go)
+    keep_forget(ctx, b);      // (... and a pending keep launch)
     for (auto &e : b->ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : b->ev_plan) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     b->ev.clear(); b->ev_runs = 0;

@@ -120,6 +120,7 @@ int rawdtw_destroy(rawdtw_ctx *ctx)
     detect_ws_free(ctx);
     seed_ws_free(ctx);
     round_end_ws_free(ctx);
+    keep_ws_free(ctx);
     for (StreamWs &w : ctx->ws_free) { if (w.d) (void)hipFree(w.d); if (w.h) (void)hipHostFree(w.h); }
     if (ctx->d_append) (void)hipFree(ctx->d_append);
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
@@ -181,6 +182,7 @@ int rawdtw_set_option(rawdtw_ctx *ctx, const char *name, int64_t value)
     if (!strcmp(name, "chain_long_seeds")) { ctx->chain_long_seeds = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 1 << 20); return RAWDTW_OK; }
     if (!strcmp(name, "seed_minimizer")) { ctx->seed_minimizer = value != 0; return RAWDTW_OK; }
     if (!strcmp(name, "device_round_end")) { ctx->device_round_end = value != 0; return RAWDTW_OK; }
+    if (!strcmp(name, "resident_chains")) { ctx->resident_chains = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 1 << 20); return RAWDTW_OK; }
     if (!strcmp(name, "signal_events_cap")) { ctx->signal_events_cap = (uint64_t)std::max<int64_t>(value, 0); return RAWDTW_OK; }
     if (!strcmp(name, "tb_workspace_mb")) { ctx->tb_workspace_mb = (uint64_t)std::min<int64_t>(std::max<int64_t>(value, 0), 1 << 30); return RAWDTW_OK; }
     if (!strcmp(name, "lane_max_radius")) {
@@ -197,6 +199,8 @@ int rawdtw_get_option(const rawdtw_ctx *ctx, const char *name, int64_t *value)
     if (!strcmp(name, "seed_minimizer")) { *value = ctx->seed_minimizer ? 1 : 0; return RAWDTW_OK; }
     if (!strcmp(name, "device_round_end")) { *value = ctx->device_round_end ? 1 : 0; return RAWDTW_OK; }
     if (!strcmp(name, "round_end_kernel_us")) { *value = round_end_kernel_us(ctx); return RAWDTW_OK; }
+    if (!strcmp(name, "resident_chains")) { *value = ctx->resident_chains; return RAWDTW_OK; }
+    if (!strcmp(name, "round_keep_kernel_us")) { *value = round_keep_kernel_us(ctx); return RAWDTW_OK; }
     if (!strcmp(name, "signal_events_cap")) { *value = (int64_t)ctx->signal_events_cap; return RAWDTW_OK; }
     if (!strcmp(name, "tb_workspace_mb")) { *value = (int64_t)ctx->tb_workspace_mb; return RAWDTW_OK; }
     if (!strcmp(name, "tb_sub_batches")) { *value = (int64_t)ctx->tb_sub_batches; return RAWDTW_OK; }

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "rawdtw_internal.h"
+#include "rawdtw_keep_layout.h"
 
 using namespace rawdtw;
 
@@ -149,6 +150,8 @@ struct rawdtw_ctx {
     struct rawdtw_detect_ws *detect_ws = nullptr; // rawdtw_detect_begin's device block (rawdtw_events.hip), grow-only
     struct rawdtw_seed_ws *seed_ws = nullptr;     // rawdtw_seed_index_upload's table and rawdtw_seed_begin's device block (rawdtw_seed.hip), grow-only
     struct rawdtw_round_end_ws *round_end_ws = nullptr; // rawdtw_round_end's device block (rawdtw_round_end.hip), grow-only
+    struct rawdtw_keep_ws *keep_ws = nullptr;           // the store of kept chains and its launch's block (rawdtw_keep.hip), grow-only
+    uint32_t resident_chains = 0;  // "resident_chains": a mapper created with this context keeps a resident round's primary chains on the device, at most this many seeds a read (0: no)
     bool device_round_end = false; // "device_round_end": a mapper created with this context ends its device-chained rounds on the device
     uint32_t chain_max_seeds = 0; // tests: RAWDTW_CHAIN_MAX_SEEDS lowers rawdtw_chain_round's cap on seeds a read, so that small rounds take the declined path (0: no)
     uint32_t chain_long_seeds = 0; // "chain_long_seeds": reads above the cap with at most this many seeds are chained by rawdtw_chain.hip's long path (0: declined)
@@ -303,6 +306,27 @@ void seed_ws_free(rawdtw_ctx *ctx);   // rawdtw_seed.hip
 void round_end_ws_free(rawdtw_ctx *ctx); // rawdtw_round_end.hip
 void round_end_forget(rawdtw_ctx *ctx, const rawdtw_batch *b); // (rawdtw_batch.cpp's batch_detach)
 int64_t round_end_kernel_us(const rawdtw_ctx *ctx); // the most recent fetched round end's launch, from its event pair ("round_end_kernel_us", read-only)
+// The context's round end as rawdtw_keep.hip reads it: begun and not fetched (`pending`) or the most recently fetched one; out and primary
+// where its launch left them in the round end's workspace, valid until the context's next round end.  `serial` counts the launches: a
+// round end that ran again at its fetch has another.
+struct RoundEndView {
+    bool pending = false;
+    const rawdtw_batch *batch = nullptr;
+    uint64_t n_reads = 0, n_chains = 0, serial = 0;
+    const rawdtw_round_out_t *d_out = nullptr;
+    const uint32_t *d_primary = nullptr;
+    const rawdtw_chain_rec_t *d_recs = nullptr;
+};
+bool round_end_view(const rawdtw_ctx *ctx, RoundEndView *v); // rawdtw_round_end.hip; false: the context has had no round end
+// the context's ended chaining round's records, anchor offsets and anchors in its workspace (rawdtw_chain.hip); false: there is none
+struct ChainKeptView { const rawdtw_chain_rec_t *d_recs = nullptr; const uint64_t *d_aoff = nullptr; const rawdtw_anchor_t *d_anch = nullptr; };
+bool chain_kept_view(const rawdtw_ctx *ctx, ChainKeptView *v);
+// the store of kept chains (rawdtw_keep.hip): its block, its layout and the host mirror of the halves' counts; false: there is none
+struct KeepStoreView { const char *store = nullptr; keep::Layout L; const uint32_t *mirror = nullptr; };
+bool keep_store_view(const rawdtw_ctx *ctx, KeepStoreView *v);
+void keep_ws_free(rawdtw_ctx *ctx);
+void keep_forget(rawdtw_ctx *ctx, const rawdtw_batch *b); // (rawdtw_batch.cpp's batch_detach)
+int64_t round_keep_kernel_us(const rawdtw_ctx *ctx); // the most recent fetched keep launch, from its event pair ("round_keep_kernel_us", read-only)
 // A resident detection begun on the context and not ended (rawdtw_events.hip), as rawdtw_seed_detected_begin reads it: everything the
 // seeding needs is in the detection's workspace on the device.  `enqueued` false: no launch went out (no chunk, or no sample).
 struct DetectView {
@@ -318,8 +342,9 @@ bool detect_resident_view(const rawdtw_ctx *ctx, DetectView *v);
 // the context's ended resident seeding (rawdtw_seed.hip) as rawdtw_chain_round_begin_resident uses it: its hit offsets on the host
 // (null: there is none), and the launch that lays reads' previous anchors and hits down as the chaining's seed list, on the context's stream
 const uint64_t *seed_resident_hit_off(const rawdtw_ctx *ctx, uint64_t *n_chunks);
+// (d_prev_src null: every read's previous anchors come from d_prev; else per read RAWDTW_PREV_HOST or a half of the store of kept chains)
 void seed_resident_write_chain(rawdtw_ctx *ctx, rawdtw_seed_t *d_seeds, const uint64_t *d_seed_off, const uint64_t *d_prev_off, const rawdtw_seed_t *d_prev,
-                               const uint32_t *d_chunk_start, const uint8_t *d_sits_out);
+                               const uint32_t *d_chunk_start, const uint8_t *d_sits_out, const uint32_t *d_prev_src);
 
 #define HIP_TRY(ctx, expr)                                                                            \
     do {                                                                                              \

@@ -528,6 +528,7 @@ struct ChainLayout {
     uint64_t *tot;                                                                             // chains, anchors, flags, bad keys; [4]: the long path's far steps
     uint64_t *aoff; rawdtw_anchor_t *anch; uint64_t *refb; uint32_t *rbc; rawdtw_chain_rec_t *recs; // the batch's arrays
     rawdtw_seed_t *prev; uint64_t *poff; uint32_t *cs; uint8_t *so; // a resident round: the previous anchors, dense, their offsets, the chunk starts, the sits-out flags
+    uint32_t *psrc;                                            // ... and per read where its previous anchors come from: RAWDTW_PREV_HOST (the dense upload) or a half of the kept chains' store
     LongArgs la;                                               // the long reads' list and their scratch: 21 bytes a seed -- K1 8, Q 4, SC 4, PR 4, FL 1
 
     size_t lay(void *base)
@@ -540,7 +541,7 @@ struct ChainLayout {
         aoff = carve<uint64_t>(p, nc + 1); anch = carve<rawdtw_anchor_t>(p, n_seeds + 2); refb = carve<uint64_t>(p, nc + 1); rbc = carve<uint32_t>(p, nc + 2);
         recs = carve<rawdtw_chain_rec_t>(p, nc + 1);
         prev = carve<rawdtw_seed_t>(p, resident ? n_prev + 2 : 0); poff = carve<uint64_t>(p, resident ? n_reads + 1 : 0); cs = carve<uint32_t>(p, nres);
-        so = carve<uint8_t>(p, nres);
+        so = carve<uint8_t>(p, nres); psrc = carve<uint32_t>(p, nres);
         la.reads = carve<LongRead>(p, n_long); la.K1 = carve<unsigned long long>(p, long_elems); la.Q = carve<uint32_t>(p, long_elems);
         la.SC = carve<float>(p, long_elems); la.PR = carve<uint32_t>(p, long_elems); la.FL = carve<unsigned char>(p, long_elems);
         la.far_steps = reinterpret_cast<unsigned long long *>(tot) + 4;
@@ -586,6 +587,7 @@ struct ResidentSeeds {
     const rawdtw_seed_t *prev_seeds;
     const uint32_t *chunk_start;
     const uint8_t *sits_out;
+    const uint32_t *prev_src; // (null: every read's from the host -- rawdtw_chain_round_begin_resident)
 };
 
 // rawdtw_chain_round_begin; `res`: the seed list is not the caller's `seeds` but laid down on the device
@@ -606,9 +608,20 @@ int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads
         if (!hoff) return fail(ctx, RAWDTW_ERR_INVALID, "no ended resident seeding on this context (rawdtw_seed_resident_begin / _end)");
         if (nc != n_reads) return fail(ctx, RAWDTW_ERR_INVALID, "the resident seeding's chunks are not this round's reads");
         if (seed_off[0] != 0 || res->prev_off[0] != 0) return fail(ctx, RAWDTW_ERR_INVALID, "offsets do not start at 0");
+        KeepStoreView kv;
+        const bool store = res->prev_src && keep_store_view(ctx, &kv);
         for (uint64_t r = 0; r < n_reads; r++) {
             if (seed_off[r + 1] < seed_off[r] || res->prev_off[r + 1] < res->prev_off[r]) return fail(ctx, RAWDTW_ERR_INVALID, "offsets do not ascend");
-            const uint64_t pv = res->prev_off[r + 1] - res->prev_off[r], want = res->sits_out[r] ? 0 : pv + (hoff[r + 1] - hoff[r]);
+            uint64_t pv = res->prev_off[r + 1] - res->prev_off[r];
+            if (res->prev_src && res->prev_src[r] != RAWDTW_PREV_HOST) { // from the store: the half's count as the last fetched keep left it
+                const uint32_t addr = res->prev_src[r];
+                if (!store || addr >= kv.L.halves()) return fail(ctx, RAWDTW_ERR_INVALID, "a read's source is outside the store of kept chains (or there is none)");
+                if (kv.mirror[addr] == RAWDTW_NOT_KEPT) return fail(ctx, RAWDTW_ERR_INVALID, "a read's source is a half that holds no kept chains");
+                if (res->sits_out[r]) return fail(ctx, RAWDTW_ERR_INVALID, "a read that sits out has a source in the store of kept chains");
+                if (pv) return fail(ctx, RAWDTW_ERR_INVALID, "a read seeded from the store of kept chains has previous seeds from the host too");
+                pv = kv.mirror[addr];
+            }
+            const uint64_t want = res->sits_out[r] ? 0 : pv + (hoff[r + 1] - hoff[r]);
             if ((res->sits_out[r] && pv) || seed_off[r + 1] - seed_off[r] != want)
                 return fail(ctx, RAWDTW_ERR_INVALID, "a read's seed_off stretch is not its previous anchors plus its chunk's hits (empty for a read that sits out)");
         }
@@ -663,7 +676,10 @@ int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads
         HIP_TRY(ctx, hipMemcpyAsync(L.poff, res->prev_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, s));
         HIP_TRY(ctx, hipMemcpyAsync(L.cs, res->chunk_start, n_reads * 4, hipMemcpyHostToDevice, s));
         HIP_TRY(ctx, hipMemcpyAsync(L.so, res->sits_out, n_reads, hipMemcpyHostToDevice, s));
-        seed_resident_write_chain(ctx, L.seeds, L.soff, L.poff, L.prev, L.cs, L.so);
+        if (res->prev_src) HIP_TRY(ctx, hipMemcpyAsync(L.psrc, res->prev_src, n_reads * 4, hipMemcpyHostToDevice, s));
+        // THE ORDER the store is read in: the keep launch that wrote a half (rawdtw_keep.hip, the round before) and this writer launch are both on
+        // the context's stream, the keep first -- the half's count and seeds are complete when the writer reads them, and the count is the mirror's
+        seed_resident_write_chain(ctx, L.seeds, L.soff, L.poff, L.prev, L.cs, L.so, res->prev_src ? L.psrc : nullptr);
         HIP_TRY(ctx, hipGetLastError());
     } else if (n_seeds) HIP_TRY(ctx, hipMemcpyAsync(L.seeds, seeds, (size_t)n_seeds * sizeof(rawdtw_seed_t), hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemcpyAsync(L.rb, read_base, n_reads * 4, hipMemcpyHostToDevice, s));
@@ -719,7 +735,17 @@ int rawdtw_chain_round_begin_resident(rawdtw_ctx *ctx, const rawdtw_chain_opt_t 
                                       uint32_t n_keys, const uint64_t *key_base, uint64_t *chain_off, uint64_t *anchor_off, rawdtw_chain_rec_t *recs,
                                       uint64_t chains_cap, rawdtw_anchor_t *anchors)
 {
-    const ResidentSeeds res{prev_off, prev_seeds, chunk_start, sits_out};
+    const ResidentSeeds res{prev_off, prev_seeds, chunk_start, sits_out, nullptr};
+    return chain_begin(ctx, opt, n_reads, seed_off, nullptr, &res, read_base, n_keys, key_base, chain_off, anchor_off, recs, chains_cap, anchors);
+}
+
+int rawdtw_chain_round_begin_resident_kept(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads, const uint64_t *seed_off, const uint64_t *prev_off,
+                                           const rawdtw_seed_t *prev_seeds, const uint32_t *prev_src, const uint32_t *chunk_start, const uint8_t *sits_out,
+                                           const uint32_t *read_base, uint32_t n_keys, const uint64_t *key_base, uint64_t *chain_off, uint64_t *anchor_off,
+                                           rawdtw_chain_rec_t *recs, uint64_t chains_cap, rawdtw_anchor_t *anchors)
+{
+    if (ctx && !prev_src) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    const ResidentSeeds res{prev_off, prev_seeds, chunk_start, sits_out, prev_src};
     return chain_begin(ctx, opt, n_reads, seed_off, nullptr, &res, read_base, n_keys, key_base, chain_off, anchor_off, recs, chains_cap, anchors);
 }
 
@@ -785,6 +811,12 @@ int rawdtw_chain_round(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t 
 } // extern "C"
 
 namespace rawdtw { namespace capi {
+bool chain_kept_view(const rawdtw_ctx *ctx, ChainKeptView *v)
+{
+    if (!ctx || !ctx->chain_ws || ctx->chain_ws->w.pending || !ctx->chain_ws->w.d_recs) return false;
+    v->d_recs = ctx->chain_ws->w.d_recs; v->d_aoff = ctx->chain_ws->w.d_aoff; v->d_anch = ctx->chain_ws->w.d_anch;
+    return true;
+}
 void chain_ws_free(rawdtw_ctx *ctx)
 {
     if (!ctx || !ctx->chain_ws) return;

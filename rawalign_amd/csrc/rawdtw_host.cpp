@@ -240,6 +240,44 @@ int rawdtw_round_end_host(const rawdtw_select_opt_t *opt, uint64_t n_reads, cons
     return RAWDTW_OK;
 }
 
+// What a round leaves as the next round's previous seeds (rmap.cpp:344-357 as the mapper's write_seeds restates it): per read the anchors of
+// its primary chains, best first, each chain's in the order they lie, as {key, target, query}.  A declined read and a read whose total is
+// above `cap` keep nothing (RAWDTW_NOT_KEPT).  What rawdtw_keep.hip's launch is tested against, byte for byte.
+int rawdtw_round_keep_host(uint64_t n_reads, const uint64_t *chain_off, const rawdtw_chain_rec_t *recs, const uint64_t *anchor_off,
+                           const rawdtw_anchor_t *anchors, const rawdtw_round_out_t *out, const uint32_t *primary, uint32_t cap,
+                           uint32_t *kept_count, uint64_t *seed_off_out, rawdtw_seed_t *seeds_out)
+{
+    if (!chain_off || !out || !kept_count || !seed_off_out) return RAWDTW_ERR_INVALID;
+    const bool chains = n_reads && chain_off[n_reads] > chain_off[0];
+    if (chains && (!recs || !anchor_off || !primary)) return RAWDTW_ERR_INVALID;
+    uint64_t at = 0;
+    seed_off_out[0] = 0;
+    for (uint64_t r = 0; r < n_reads; r++) {
+        const uint64_t c0 = chain_off[r], c1 = chain_off[r + 1];
+        if (c1 < c0 || out[r].n_primary > c1 - c0) return RAWDTW_ERR_INVALID;
+        uint64_t total = 0;
+        for (uint32_t p = 0; p < out[r].n_primary; p++) {
+            if (primary[c0 + p] >= c1 - c0) return RAWDTW_ERR_INVALID;
+            total += recs[c0 + primary[c0 + p]].n_anchors;
+        }
+        const bool kept = !(out[r].flags & RAWDTW_ROUND_DECLINED) && total <= cap;
+        kept_count[r] = kept ? (uint32_t)total : RAWDTW_NOT_KEPT;
+        if (kept && total) {
+            if (seeds_out && !anchors) return RAWDTW_ERR_INVALID;
+            for (uint32_t p = 0; p < out[r].n_primary && seeds_out; p++) {
+                const uint64_t c = c0 + primary[c0 + p];
+                for (uint32_t k = 0; k < recs[c].n_anchors; k++) {
+                    const rawdtw_anchor_t &a = anchors[anchor_off[c] + k];
+                    seeds_out[at++] = rawdtw_seed_t{recs[c].key, a.target_position, a.query_position};
+                }
+            }
+            if (!seeds_out) at += total;
+        }
+        seed_off_out[r + 1] = at;
+    }
+    return RAWDTW_OK;
+}
+
 // sequence_until.c:5-19.  The source is one rounded product and one rounded add per element, summed in order;
 // `contracted_tail` selects what the reference's own default build (GCC -O3 with FMA available) computes instead:
 // the same in-order sum, but the elements after the last full group of four go through one fused multiply-add each

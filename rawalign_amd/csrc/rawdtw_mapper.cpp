@@ -68,6 +68,9 @@ struct MRead {
     uint64_t last_pos = 0;
     uint64_t seen_round = 0;     // (duplicate check)
     bool closed = false;         // sequence-until: in a closed mini-batch
+    // "resident_chains": the half of its slot in the context's store of kept chains that holds its chains' anchors as seeds (rawdtw_keep.hip),
+    // and how many.  Written in a round's commit block only; cleared wherever the chains change without a keep launch behind them.
+    struct Kept { bool valid = false; uint8_t half = 0; uint32_t count = 0; } kept;
     bool gated = false;          // ... at or after the stop point of its batch (rmap.cpp:960: a mapped read's line loses its fields)
     bool dropped = false;        // ... added but in no closed batch when the stop fired, or added after it: finished, no line
 };
@@ -121,6 +124,7 @@ struct RoundArrays {
     PinBuf<uint64_t> prev_off, ev_start;  // a resident round (rawdtw_mapper_round_seeded_resident): the previous anchors' offsets (the anchors themselves, dense, in
     PinBuf<uint32_t> chunk_start, ev_len; // `seeds`), the chunks' places in the event arena, and what the device's writer needs per read
     PinBuf<uint8_t> sits_out;
+    PinBuf<uint32_t> prev_src, keep_dst, kept_count; // "resident_chains": per read where its previous seeds come from, where its chains are kept, and what was kept
     PinBuf<rawdtw_round_out_t> re_out;    // the round's end from the device ("device_round_end"): per read, and per chain the primaries' indices
     PinBuf<uint32_t> re_primary;
     std::vector<uint32_t> chain_seq; // (the external scorer's view)
@@ -156,6 +160,8 @@ struct RoundRead {
     uint64_t chain0 = 0, anchor0 = 0, new0 = 0, ev0 = 0; // its first chain / anchor / new anchor / new event in the group's arrays
     uint64_t seed0 = 0, n_seeds = 0;     // device chaining: its seeds in the group's list
     uint32_t chunk_start = 0;
+    bool from_store = false;             // "resident_chains": its previous seeds were taken from the store of kept chains
+    uint64_t n_prev = 0;                 // ... and how many it had, from either side
     int err = RAWDTW_OK;
 };
 
@@ -312,6 +318,11 @@ struct rawdtw_mapper {
     std::vector<uint64_t> sig_evoff;
     uint64_t sig_rounds = 0, sig_retried = 0, sig_sample_bytes = 0;
     uint64_t re_rounds = 0, re_reads = 0, re_declined = 0; // rawdtw_mapper_round_end_stats
+    // rawdtw_mapper_kept_stats ("resident_chains"): reads with previous seeds taken from the device / sent up from the host, those seeds, and
+    // reads whose chains a keep launch did not keep; the store's N as this mapper reserved it
+    uint64_t kp_reads_dev = 0, kp_reads_host = 0, kp_seeds_dev = 0, kp_seeds_host = 0, kp_not_kept = 0;
+    uint32_t kp_reserved = 0;
+    bool kp_any = false; // some read may hold kept chains
     uint64_t sig_cap = 0; // the largest events_cap a round from signal ran with: what the seeding's workspace holds already
 };
 
@@ -512,6 +523,13 @@ bool round_end_on_device(const rawdtw_mapper *m)
     return m->ctx && rawdtw_get_option(m->ctx, "device_round_end", &v) == RAWDTW_OK && v != 0;
 }
 
+// "resident_chains" on the context the mapper was created with (0: off)
+uint32_t resident_chains_option(const rawdtw_mapper *m)
+{
+    int64_t v = 0;
+    return m->ctx && rawdtw_get_option(m->ctx, "resident_chains", &v) == RAWDTW_OK && v > 0 ? (uint32_t)v : 0u;
+}
+
 // a round's sizes in one group (0 where its path does not know them)
 struct Sizes { uint64_t reads = 0, chains = 0, anchors = 0, new_anchors = 0, events = 0, seg = 0, seeds = 0; };
 
@@ -535,8 +553,13 @@ struct Round {
     bool events_in_place = on_device && m->opt.device_chain && G == 1 && event_off[n_reads] > 0 && rawdtw_host_is_page_locked(events) == 1;
     std::vector<RoundRead> rr = std::vector<RoundRead>(n_reads);
     struct PerGroup { bool chaining = false; uint64_t ns = 0, nev = 0, nseg = 0, scored = 0, reused = 0, extra = 0; // (ns: seeds sent up; extra: other bytes)
-                      bool round_end = false; uint64_t re_reads = 0, re_declined = 0; } per[2]; // (the round's end enqueued on the device; the reads it ended / declined)
+                      bool round_end = false; uint64_t re_reads = 0, re_declined = 0; // (the round's end enqueued on the device; the reads it ended / declined)
+                      bool keep = false; } per[2];                                    // (... and the keep launch behind it)
     bool device_round_end = round_end_on_device(m); // (read once a round)
+    uint32_t resident_chains = resident_chains_option(m); // (so is this)
+    // the round takes previous seeds from the store of kept chains and keeps its own there: a resident round with the option on whose end
+    // is enqueued on the device
+    bool use_store() const { return resident && resident_chains != 0 && device_round_end && runs_dtw; }
     int status = RAWDTW_OK;
     std::string msg;
 
@@ -723,10 +746,18 @@ struct Round {
         int st = RAWDTW_OK;
         const uint64_t *hoff = m->seed_off.p; // (chunk i is read ks[i]: one group, the round's reads in order)
         uint64_t ns = 0, np = 0;
+        const bool store = use_store();
+        if (store && !reserve_store(g)) return;
         for (size_t i = 0; i < nr; i++) {
             RoundRead &r = rr[ra.ks[i]];
-            const uint64_t pv = r.skipped ? 0 : seed_count(read(ra.ks[i]), 0);
-            r.seed0 = np; np += pv;
+            const MRead &rd = read(ra.ks[i]);
+            const uint64_t pv = r.skipped ? 0 : seed_count(rd, 0);
+            r.from_store = store && !r.skipped && rd.kept.valid;
+            r.n_prev = pv;
+            if (r.from_store && rd.kept.count != pv) // (the half holds another list than write_seeds would build: never go on with it)
+                return failed(RAWDTW_ERR_DEVICE, "a read's kept chains on the device (" + std::to_string(rd.kept.count) + " seeds) are not its chains on the host (" +
+                                                     std::to_string(pv) + " anchors)");
+            r.seed0 = np; np += r.from_store ? 0 : pv; // (a read seeded from the store sends nothing up)
             r.n_seeds = r.skipped ? 0 : pv + (hoff[i + 1] - hoff[i]);
             ns += r.n_seeds;
         }
@@ -740,11 +771,21 @@ struct Round {
             ra.read_base[i] = arena_base(read(k));
             ra.chunk_start[i] = r.chunk_start;
             ra.sits_out[i] = r.skipped ? 1 : 0;
-            if (!r.skipped) write_seeds(read(k), nullptr, 0, 0, ra.seeds.p + r.seed0); // (the previous chains' anchors only)
+            if (!r.skipped && !r.from_store) write_seeds(read(k), nullptr, 0, 0, ra.seeds.p + r.seed0); // (the previous chains' anchors only)
+            if (store) { // its previous seeds from the half it holds; its chains into the other one (half 0 for a read that holds none)
+                const MRead &rd = read(k);
+                ra.prev_src[i] = r.from_store ? rd.slot * 2u + rd.kept.half : RAWDTW_PREV_HOST;
+                ra.keep_dst[i] = r.skipped ? RAWDTW_NO_KEEP : rd.slot * 2u + (rd.kept.valid ? (rd.kept.half ^ 1u) : 0u);
+            }
         });
         lap(0);
-        st = rawdtw_chain_round_begin_resident(g.ctx, &m->opt.chain, nr, ra.seed_off.p, ra.prev_off.p, ra.seeds.p, ra.chunk_start.p, ra.sits_out.p, ra.read_base.p,
-                                               (uint32_t)m->ref_off.size(), m->ref_off.data(), ra.chain_off.p, ra.anchor_off.p, ra.recs.p, g.hw_chains, ra.anchors.p);
+        if (store)
+            st = rawdtw_chain_round_begin_resident_kept(g.ctx, &m->opt.chain, nr, ra.seed_off.p, ra.prev_off.p, ra.seeds.p, ra.prev_src.p, ra.chunk_start.p, ra.sits_out.p,
+                                                        ra.read_base.p, (uint32_t)m->ref_off.size(), m->ref_off.data(), ra.chain_off.p, ra.anchor_off.p, ra.recs.p,
+                                                        g.hw_chains, ra.anchors.p);
+        else
+            st = rawdtw_chain_round_begin_resident(g.ctx, &m->opt.chain, nr, ra.seed_off.p, ra.prev_off.p, ra.seeds.p, ra.chunk_start.p, ra.sits_out.p, ra.read_base.p,
+                                                   (uint32_t)m->ref_off.size(), m->ref_off.data(), ra.chain_off.p, ra.anchor_off.p, ra.recs.p, g.hw_chains, ra.anchors.p);
         lap(2);
         if (st == RAWDTW_ERR_UNSUPPORTED) { // a read above the device's cap on seeds: nothing was enqueued
             m->timing[6] += (double)(nev * sizeof(float));
@@ -755,6 +796,26 @@ struct Round {
         res_prev = np;
         // (beside the chaining's own arrays: prev_off, chunk_start, sits_out; the seeding's offsets and source starts)
         per[gi] = PerGroup{true, np, nev, nseg, 0, 0, (nr + 1) * 8 + nr * 5 + (nr + 1) * 8 + nr * 8};
+    }
+
+    // "resident_chains": the context's store reserved for every slot of the mapper at the first round that uses it, and this round's
+    // per-read arrays.  A store that had to grow (the option was raised) has lost its contents: no read holds kept chains any more.
+    bool reserve_store(Group &g)
+    {
+        if (m->kp_reserved < resident_chains) {
+            const int st = rawdtw_chain_keep_reserve(g.ctx, m->opt.max_reads, resident_chains);
+            if (st != RAWDTW_OK) { failed(st, rawdtw_last_error(g.ctx)); return false; }
+            if (m->kp_reserved) for (MRead &rd : m->reads) rd.kept.valid = false;
+            m->kp_reserved = resident_chains;
+        }
+        for (int b = 0; b < 2; b++) {
+            RoundArrays &x = g.buf[g.cur ^ b];
+            if (!(x.prev_src.ensure(g.hw_reads + 1, true) && x.keep_dst.ensure(g.hw_reads + 1, false) && x.kept_count.ensure(g.hw_reads + 1, false))) {
+                failed(RAWDTW_ERR_OOM, "host allocation failed");
+                return false;
+            }
+        }
+        return true;
     }
 
     // the fall-back of a resident round: its hits to the host, once, where host_round reads them
@@ -824,6 +885,8 @@ struct Round {
         const rawdtw_select_opt_t so = select_opt(m);
         if (st == RAWDTW_OK) st = rawdtw_batch_round_end_begin(g.ctx, ra.batch, &so, d_recs, 1);
         p.round_end = st == RAWDTW_OK;
+        // "resident_chains": the primary chains' anchors into the reads' other halves, right behind the round end that names them
+        if (st == RAWDTW_OK && use_store()) { st = rawdtw_batch_round_end_keep(g.ctx, ra.batch, ra.keep_dst.p); p.keep = st == RAWDTW_OK; }
         return st;
     }
 
@@ -968,6 +1031,10 @@ struct Round {
             if (per[gi].round_end) { // (also after a failure: the context's round end is begun and must be ended)
                 const int se = rawdtw_batch_round_end_fetch(g.ctx, ra.batch, ra.re_out.p, ra.re_primary.p);
                 if (se != RAWDTW_OK) failed(se, rawdtw_last_error(g.ctx));
+                if (se == RAWDTW_OK && per[gi].keep) { // (a keep whose round end failed goes with the batch)
+                    const int sk = rawdtw_batch_round_keep_fetch(g.ctx, ra.batch, ra.kept_count.p);
+                    if (sk != RAWDTW_OK) failed(sk, rawdtw_last_error(g.ctx));
+                }
             }
         }
         lap(3);
@@ -1065,6 +1132,18 @@ struct Round {
             m->parts_scored += per[gi].scored; m->parts_reused += per[gi].reused;
             m->re_reads += per[gi].re_reads; m->re_declined += per[gi].re_declined;
             for (size_t i = 0; i < ra.ks.size(); i++) { read(ra.ks[i]).last_round = id; read(ra.ks[i]).last_pos = i; }
+            // "resident_chains": the one place a read's kept state changes.  A read that sat out keeps its chains and its state; a read whose
+            // chains were kept is seeded from that half from now on; every other read's chains are new and not on the device
+            // (a mapper that never had the option on has no read to clear: the loop is skipped)
+            for (size_t i = 0; (use_store() || m->kp_any) && i < ra.ks.size(); i++) {
+                MRead &rd = read(ra.ks[i]); const RoundRead &r = rr[ra.ks[i]];
+                if (r.skipped) continue;
+                if (use_store() && !fell_back && r.n_prev) { // (a round that fell back was chained on the host, from the host's chains)
+                    if (r.from_store) { m->kp_reads_dev++; m->kp_seeds_dev += r.n_prev; } else { m->kp_reads_host++; m->kp_seeds_host += r.n_prev; }
+                }
+                if (per[gi].keep && ra.kept_count[i] != RAWDTW_NOT_KEPT) { rd.kept = MRead::Kept{true, (uint8_t)(ra.keep_dst[i] & 1u), ra.kept_count[i]}; m->kp_any = true; }
+                else { rd.kept.valid = false; if (per[gi].keep) m->kp_not_kept++; }
+            }
         }
         for (uint32_t k = 0; k < n_reads; k++) {
             MRead &rd = read(k); RoundRead &r = rr[k];
@@ -1481,6 +1560,18 @@ int rawdtw_mapper_round_end_stats(const rawdtw_mapper *m, uint64_t *rounds, uint
     if (rounds) *rounds = m->re_rounds;
     if (reads_device) *reads_device = m->re_reads;
     if (reads_declined) *reads_declined = m->re_declined;
+    return RAWDTW_OK;
+}
+
+int rawdtw_mapper_kept_stats(const rawdtw_mapper *m, uint64_t *reads_from_device, uint64_t *reads_from_host, uint64_t *seeds_from_device,
+                             uint64_t *seeds_from_host, uint64_t *reads_not_kept)
+{
+    if (!m) return RAWDTW_ERR_INVALID;
+    if (reads_from_device) *reads_from_device = m->kp_reads_dev;
+    if (reads_from_host) *reads_from_host = m->kp_reads_host;
+    if (seeds_from_device) *seeds_from_device = m->kp_seeds_dev;
+    if (seeds_from_host) *seeds_from_host = m->kp_seeds_host;
+    if (reads_not_kept) *reads_not_kept = m->kp_not_kept;
     return RAWDTW_OK;
 }
 

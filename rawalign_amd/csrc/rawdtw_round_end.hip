@@ -192,6 +192,9 @@ struct rawdtw_round_end_ws {
     const rawdtw_batch *batch = nullptr; // (null: rawdtw_round_end's own)
     bool batch_was_stream = false;
     const rawdtw_chain_rec_t *d_recs = nullptr;
+    const rawdtw_round_out_t *d_out = nullptr; // out and primary in the workspace, for what is enqueued behind the launch (rawdtw_keep.hip)
+    const uint32_t *d_primary = nullptr;
+    uint64_t serial = 0;                       // launches so far
     size_t home_at = 0, home_bytes = 0, primary_at = 0; // where out lies in the block, what comes home, primary's place in it
     float kernel_ms = 0.0f;
 };
@@ -233,7 +236,7 @@ int round_end_begin(rawdtw_ctx *ctx, const rawdtw_select_opt_t *opt, uint64_t n_
     HIP_TRY(ctx, hipEventRecord(ws.w.done, s));
     ws.pending = true; ws.n_reads = n_reads; ws.n_chains = n_chains; ws.opt = *opt; ws.batch = batch;
     ws.batch_was_stream = batch && batch->stream;
-    ws.d_recs = a.recs;
+    ws.d_recs = a.recs; ws.d_out = L.out; ws.d_primary = L.primary; ws.serial++;
     ws.home_bytes = L.home_bytes;
     ws.primary_at = (size_t)(reinterpret_cast<uintptr_t>(L.primary) - reinterpret_cast<uintptr_t>(L.out));
     return RAWDTW_OK;
@@ -323,6 +326,14 @@ void round_end_forget(rawdtw_ctx *ctx, const rawdtw_batch *b)
     (void)hipEventSynchronize(ctx->round_end_ws->w.done);
     ctx->round_end_ws->pending = false;
     ctx->round_end_ws->batch = nullptr;
+}
+bool round_end_view(const rawdtw_ctx *ctx, RoundEndView *v)
+{
+    if (!ctx || !ctx->round_end_ws || !ctx->round_end_ws->serial) return false;
+    const rawdtw_round_end_ws &ws = *ctx->round_end_ws;
+    v->pending = ws.pending; v->batch = ws.batch; v->n_reads = ws.n_reads; v->n_chains = ws.n_chains; v->serial = ws.serial;
+    v->d_out = ws.d_out; v->d_primary = ws.d_primary; v->d_recs = ws.d_recs;
+    return true;
 }
 int64_t round_end_kernel_us(const rawdtw_ctx *ctx) { return ctx->round_end_ws ? (int64_t)std::lround(ctx->round_end_ws->kernel_ms * 1000.0f) : 0; }
 } }

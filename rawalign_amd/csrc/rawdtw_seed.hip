@@ -338,6 +338,9 @@ struct ChainDst {
     const rawdtw_seed_t *prev;
     const uint32_t *chunk_start;   // per read: reg->offset before this chunk (rmap.cpp:574)
     const uint8_t *sits_out;       // per read: the chunk is below min_events -- nothing is written (rmap.cpp:569-572)
+    const uint32_t *prev_src;      // per read: RAWDTW_PREV_HOST, or the half of the kept chains' store its previous anchors lie in (null: all from `prev`)
+    const char *store;             // the store (rawdtw_keep_layout.h)
+    keep::Layout KL;
 };
 
 __device__ __forceinline__ rawdtw_seed_t seed_of(uint64_t y, uint32_t query)
@@ -353,9 +356,18 @@ __global__ __launch_bounds__(64) void k_seed_write_chain(SeedArgs a, ChainDst d)
     const uint32_t k = blockIdx.x, lane = threadIdx.x;
     if (d.sits_out[k]) return;
     const uint64_t p0 = d.prev_off[k];
-    const uint32_t np = (uint32_t)(d.prev_off[k + 1] - p0);
-    rawdtw_seed_t *dst = d.seeds + d.seed_off[k];
-    for (uint32_t i = lane; i < np; i += kW) dst[i] = d.prev[p0 + i];
+    uint32_t np = (uint32_t)(d.prev_off[k + 1] - p0);
+    const rawdtw_seed_t *src = d.prev + p0;
+    const uint64_t s0 = d.seed_off[k];
+    rawdtw_seed_t *dst = d.seeds + s0;
+    const uint32_t addr = d.prev_src ? d.prev_src[k] : RAWDTW_PREV_HOST;
+    if (addr != RAWDTW_PREV_HOST) { // from the store: the half the keep launch of the round before wrote, earlier on this stream.  The host has
+                                    // checked the stretch against its mirror of the count; the count is taken as at most a half and the stretch all the same
+        np = (uint32_t)min(min((unsigned long long)*reinterpret_cast<const uint32_t *>(d.store + d.KL.count_at(addr)), (unsigned long long)d.KL.n_seeds),
+                           (unsigned long long)(d.seed_off[k + 1] - s0));
+        src = reinterpret_cast<const rawdtw_seed_t *>(d.store + d.KL.seeds_at(addr));
+    }
+    for (uint32_t i = lane; i < np; i += kW) dst[i] = src[i];
     if (!a.chits[k]) return;
     dst += np;
     const uint32_t kept = a.kept[k], start = d.chunk_start[k];
@@ -755,10 +767,12 @@ const uint64_t *seed_resident_hit_off(const rawdtw_ctx *ctx, uint64_t *n_chunks)
 }
 
 void seed_resident_write_chain(rawdtw_ctx *ctx, rawdtw_seed_t *d_seeds, const uint64_t *d_seed_off, const uint64_t *d_prev_off, const rawdtw_seed_t *d_prev,
-                               const uint32_t *d_chunk_start, const uint8_t *d_sits_out)
+                               const uint32_t *d_chunk_start, const uint8_t *d_sits_out, const uint32_t *d_prev_src)
 {
     const SeedWs &w = ctx->seed_ws->w;
-    hipLaunchKernelGGL(k_seed_write_chain, dim3(w.n), dim3(kW), 0, ctx->stream, w.ra, ChainDst{d_seeds, d_seed_off, d_prev_off, d_prev, d_chunk_start, d_sits_out});
+    KeepStoreView kv;
+    if (!d_prev_src || !keep_store_view(ctx, &kv)) { d_prev_src = nullptr; kv = KeepStoreView{}; } // (the chaining's begin has checked that a source has its store)
+    hipLaunchKernelGGL(k_seed_write_chain, dim3(w.n), dim3(kW), 0, ctx->stream, w.ra, ChainDst{d_seeds, d_seed_off, d_prev_off, d_prev, d_chunk_start, d_sits_out, d_prev_src, kv.store, kv.L});
 }
 
 void seed_ws_free(rawdtw_ctx *ctx)

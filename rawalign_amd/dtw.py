@@ -31,6 +31,9 @@ ANCHOR_DTYPE = np.dtype([("target_position", "<u4"), ("query_position", "<u4")])
 CHAIN_REC_DTYPE = np.dtype([("chaining_score", "<f4"), ("key", "<u4"), ("start_position", "<u4"), ("end_position", "<u4"), ("n_anchors", "<u4")])
 ROUND_OUT_DTYPE = np.dtype([("n_primary", "<u4"), ("mapq", "<u4"), ("flags", "<u4")])
 ROUND_HIGH, ROUND_DECLINED, NO_PRIMARY = 1, 2, 0xFFFFFFFF
+# rawdtw_seed_t (a chaining seed: key = sequence * 2 + strand) and the kept chains' sentinels (include/rawdtw.h)
+SEED_DTYPE = np.dtype([("key", "<u4"), ("target_position", "<u4"), ("query_position", "<u4")])
+NOT_KEPT = NO_KEEP = PREV_HOST = 0xFFFFFFFF
 
 
 @dataclass
@@ -73,6 +76,28 @@ def round_end_host(select_opt, chain_off, recs, score, keep=None):
         if st != 0:
             raise RawDTWError(st, "rawdtw_round_end_host")
     return _round_end(load_library(), None, check, select_opt, chain_off, recs, score, keep)
+
+
+def _keep_arrays(chain_off, recs, anchor_off, anchors, out, primary):
+    chain_off = np.ascontiguousarray(chain_off, np.uint64)
+    n, nc = len(chain_off) - 1, int(chain_off[-1])
+    recs, anchor_off = np.ascontiguousarray(recs, CHAIN_REC_DTYPE), np.ascontiguousarray(anchor_off, np.uint64)
+    anchors, out, primary = np.ascontiguousarray(anchors, ANCHOR_DTYPE), np.ascontiguousarray(out, ROUND_OUT_DTYPE), np.ascontiguousarray(primary, np.uint32)
+    if len(recs) < nc or len(primary) < nc or len(anchor_off) < nc + 1 or len(out) < n or len(anchors) < int(anchor_off[nc]):
+        raise ValueError("recs and primary hold chain_off[-1] chains, anchor_off one more, out a read, anchors anchor_off[-1]")
+    return n, nc, chain_off, recs, anchor_off, anchors, out, primary
+
+
+def round_keep_host(chain_off, recs, anchor_off, anchors, out, primary, cap):
+    """rawdtw_round_keep_host: what a round keeps as the next round's previous seeds, on the host: (kept_count: uint32 a read, NOT_KEPT for
+    a declined read and one above `cap`; seed_off: uint64, n + 1; seeds: SEED_DTYPE, the kept reads' lists, dense)"""
+    n, nc, chain_off, recs, anchor_off, anchors, out, primary = _keep_arrays(chain_off, recs, anchor_off, anchors, out, primary)
+    kept, soff, seeds = np.zeros(max(n, 1), np.uint32), np.zeros(n + 1, np.uint64), np.zeros(max(int(anchor_off[nc]), 1), SEED_DTYPE)
+    st = load_library().rawdtw_round_keep_host(n, _ptr(chain_off), _ptr(recs), _ptr(anchor_off), _ptr(anchors), _ptr(out), _ptr(primary), int(cap),
+                                               _ptr(kept), _ptr(soff), _ptr(seeds))
+    if st != 0:
+        raise RawDTWError(st, "rawdtw_round_keep_host")
+    return kept[:n], soff, seeds[:int(soff[n])]
 
 
 def plan_dry_run(jobs: np.ndarray, n_events: int, n_reference: int, threads: int = 0, options=None):
@@ -255,6 +280,28 @@ class Engine:
         keep.  Returns (out: ROUND_OUT_DTYPE a read, primary: uint32 a chain); a read with flag ROUND_DECLINED is the caller's to end with
         round_end_host."""
         return _round_end(self.lib, self._ctx, self._check, select_opt, chain_off, recs, score, keep)
+
+    def chain_keep_reserve(self, n_slots: int, seeds_per_half: int):
+        """rawdtw_chain_keep_reserve: the context's store of kept chains, grow-only (a store that grows loses its contents)"""
+        self._check(self.lib.rawdtw_chain_keep_reserve(self._ctx, int(n_slots), int(seeds_per_half)))
+
+    def round_keep(self, chain_off, recs, anchor_off, anchors, out, primary, dst):
+        """rawdtw_round_keep: the host arrays go up, one launch keeps read r's primary chains' anchors as seeds in the store's half dst[r]
+        (NO_KEEP: nowhere).  Returns kept_count (uint32 a read; NOT_KEPT: declined, above the store's seeds a half, or no destination)."""
+        n, nc, chain_off, recs, anchor_off, anchors, out, primary = _keep_arrays(chain_off, recs, anchor_off, anchors, out, primary)
+        dst = np.ascontiguousarray(dst, np.uint32)
+        if len(dst) < n:
+            raise ValueError("dst holds an entry a read")
+        kept = np.zeros(max(n, 1), np.uint32)
+        self._check(self.lib.rawdtw_round_keep(self._ctx, n, _ptr(chain_off), _ptr(recs), _ptr(anchor_off), _ptr(anchors), _ptr(out), _ptr(primary), _ptr(dst),
+                                               _ptr(kept)))
+        return kept[:n]
+
+    def chain_kept_fetch(self, addr: int, cap: int):
+        """rawdtw_chain_kept_fetch: (the half's count, NOT_KEPT included; its first `cap` seeds as SEED_DTYPE, whatever the count says)"""
+        seeds, n = np.zeros(max(int(cap), 1), SEED_DTYPE), C.c_uint32()
+        self._check(self.lib.rawdtw_chain_kept_fetch(self._ctx, int(addr), _ptr(seeds), int(cap), C.byref(n)))
+        return n.value, seeds[:int(cap)]
 
     def chain_round_recs(self) -> int:
         """rawdtw_chain_round_recs: the device address of the ended chaining round's records (valid until the next chaining round)"""

@@ -711,6 +711,16 @@ class CMapper:
         self._check(self.lib.rawdtw_mapper_round_end_stats(self._h, *[C.byref(x) for x in v]))
         return dict(rounds=v[0].value, reads_device=v[1].value, reads_declined=v[2].value)
 
+    def kept_stats(self):
+        """rawdtw_mapper_kept_stats: with the context's "resident_chains" on, over committed rounds that used the store -- reads with previous
+        seeds that took them from the device / from the host, those seeds, and reads whose chains were not kept"""
+        import ctypes as C
+
+        v = [C.c_uint64() for _ in range(5)]
+        self._check(self.lib.rawdtw_mapper_kept_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(reads_from_device=v[0].value, reads_from_host=v[1].value, seeds_from_device=v[2].value, seeds_from_host=v[3].value,
+                    reads_not_kept=v[4].value)
+
     def timing(self):
         t = np.zeros(8, np.float64)
         self._check(self.lib.rawdtw_mapper_timing(self._h, _vp(t)))
