@@ -384,6 +384,11 @@ int rawdtw_chain_anchors(const rawdtw_chain_opt_t *opt, const rawdtw_anchor_t *a
 /* The evaluation order of one read's chains: the permutation std::sort (libstdc++, unstable)
  * produces for the comparator a.chaining_score > b.chaining_score (rmap.cpp:512). */
 int rawdtw_sort_by_chaining_score(const float *chaining_score, uint32_t n_chains, uint32_t *perm_out);
+/* The same permutation without std::sort: libstdc++'s introsort restated (rawdtw_sort_order.h: introsort loop with the median-of-three
+ * partition, heap sort where the depth budget runs out, one final insertion sort), the function the device's chaining orders a read's
+ * chains with under "chain_max_chains".  The function above stays on std::sort and is what this one is tested against.
+ * *phases_out (may be NULL): bit 0 a partition ran, bit 1 the heap sort ran. */
+int rawdtw_sort_by_chaining_score_restated(const float *chaining_score, uint32_t n_chains, uint32_t *perm_out, uint32_t *phases_out);
 
 /* ---- the same on the device for a whole chunk round (rawdtw_chain.hip): per read the anchor sort
  * (rmap.cpp:396-401), the chaining DP and traceback_chains per (sequence, strand) list (rmap.cpp:430-507, 130-173) with the
@@ -393,21 +398,33 @@ int rawdtw_sort_by_chaining_score(const float *chaining_score, uint32_t n_chains
  *   in  (host): read r's seeds seeds[seed_off[r] .. seed_off[r+1]), UNSORTED (key = sequence * 2 + strand as the caller numbers
  *        its reference arrays); read_base[r] = the read's first event in the event arena; key_base[key] = the arena offset of
  *        that key's reference array (rawdtw_reference_offset)
- *   out (host): chain_off[n_reads + 1]; anchor_off[n_chains + 1] and recs[n_chains] (at most chains_cap chains; 32 a read is the
+ *   out (host): chain_off[n_reads + 1]; anchor_off[n_chains + 1] and recs[n_chains] (at most chains_cap chains; 32 a read -- or "chain_max_chains", below -- is the
  *        device's own limit), chains of a read in evaluation order; anchors[...] (end-first per chain; may be NULL: room for
  *        seed_off[n_reads] entries)
  *   out (device, the context's, valid until its next rawdtw_chain_round): *d_anchors, *d_ref_base, *d_read_base
  * The call returns when the host arrays are filled.  Results equal rawdtw_chain_anchors list by list and
  * rawdtw_sort_by_chaining_score read by read, bit for bit.  RAWDTW_ERR_UNSUPPORTED (the out arrays hold nothing of use): a read with more than
  * 2 048 seeds (with the option below: more than its value), with more than 32 chains, or with more than 16 chains two of which have
- * equal scores (std::sort's order of equal elements is an insertion sort's only up to 16) -- chain that round on the host.
+ * equal scores (std::sort's order of equal elements is an insertion sort's only up to 16) -- chain that round on the host, or see
+ * "chain_max_chains" below, which lifts the last two.
  * RAWDTW_ERR_INVALID: a chain on a key that is not below n_keys.
  *   rawdtw_set_option(ctx, "chain_long_seeds", N)  0 (the default): as above.  N > 0 (at most 1 << 20): a read with more than 2 048 and at
  *        most N seeds no longer declines the round; it is chained by a second path that keeps its state in device memory (21 bytes a seed
  *        of the context's workspace), with the same results.  A read above N declines the round in _begin, before anything is enqueued;
  *        the limits on chains decline it in _end, as without the option.
  *   rawdtw_chain_round_stats  cumulative, a context: rounds begun, the reads and the seeds that second path chained, and its 64-candidate
- *        steps that read a candidate from device memory because it lay behind the path's window in LDS.  Any pointer may be NULL. */
+ *        steps that read a candidate from device memory because it lay behind the path's window in LDS.  Any pointer may be NULL.
+ *   rawdtw_set_option(ctx, "chain_max_chains", N)  0 (the default): as above.  1 <= N <= 4096 (anything else: RAWDTW_ERR_INVALID): a read
+ *        with up to N chains no longer declines the round, however many of them have equal scores -- its chains are ordered on the device by
+ *        std::sort's own algorithm (rawdtw_sort_by_chaining_score_restated), with the same results.  chains_cap and the out arrays must
+ *        then hold min(n_reads * N, seed_off[n_reads] / max(1, min_num_anchors) + 1) chains (chains of a read share no anchor), and the
+ *        context's workspace grows by 68 bytes for each of them instead of 64 * 32 bytes a read.
+ *        WHAT STILL DECLINES with it (RAWDTW_ERR_UNSUPPORTED from _end): a read with more than N chains; from _begin, as before, a read with
+ *        more seeds than 2 048 / "chain_long_seeds".  Further down the flow k_round_end ("device_round_end") leaves a read with more than 64
+ *        chains taking part to the host on its own, read by read; that is not this call's limit and does not decline the round.
+ *   rawdtw_chain_order_stats  cumulative, a context, over the rounds that were not declined: the reads with more than 32 chains, the reads with
+ *        more than 16 chains that "chain_max_chains" ordered with the restated sort (up to 16 it is the insertion sort it always was), and
+ *        the most chains a read had.  Any pointer may be NULL. */
 typedef struct { uint32_t key, target_position, query_position; } rawdtw_seed_t;                       /* 12 bytes */
 typedef struct { float chaining_score; uint32_t key, start_position, end_position, n_anchors; } rawdtw_chain_rec_t; /* 20 bytes */
 int rawdtw_chain_round(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads, const uint64_t *seed_off,
@@ -426,6 +443,7 @@ int rawdtw_chain_round_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uin
 int rawdtw_chain_round_end(rawdtw_ctx *ctx, const rawdtw_anchor_t **d_anchors, const uint64_t **d_ref_base,
                            const uint32_t **d_read_base);
 int rawdtw_chain_round_stats(const rawdtw_ctx *ctx, uint64_t *rounds, uint64_t *long_reads, uint64_t *long_seeds, uint64_t *far_steps);
+int rawdtw_chain_order_stats(const rawdtw_ctx *ctx, uint64_t *reads_above_32, uint64_t *reads_ordered_restated, uint64_t *max_chains_a_read);
 
 /* Batched forms over many reads (what rmap.cpp's per-read worker does for every read of a
  * mini-batch, hoisted around one GPU submission).  Chains are listed read by read, each read's

@@ -277,6 +277,8 @@ SYMBOLS = {
     "rawdtw_mapper_round_seeded_resident": (I32, [VP, VP, U32, VP, VP, VP]),
     "rawdtw_mapper_resident_stats": (I32, [VP, VP, VP, VP, VP]),
     "rawdtw_chain_round_stats": (I32, [VP, VP, VP, VP, VP]),
+    "rawdtw_chain_order_stats": (I32, [VP, VP, VP, VP]),
+    "rawdtw_sort_by_chaining_score_restated": (I32, [VP, U32, VP, VP]),
     "rawdtw_get_option": (I32, [VP, C.c_char_p, C.POINTER(C.c_int64)]),
     "rawdtw_detect_resident_begin": (I32, [VP, C.POINTER(EventOpt), U32, VP, VP, VP, VP, U64]),
     "rawdtw_detect_raw_resident_begin": (I32, [VP, C.POINTER(EventOpt), U32, VP, VP, VP, VP, VP, U64]),

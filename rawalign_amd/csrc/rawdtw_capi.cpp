@@ -180,6 +180,11 @@ int rawdtw_set_option(rawdtw_ctx *ctx, const char *name, int64_t value)
     if (!strcmp(name, "lane_max_n")) { ctx->lane_max_n = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 8), kLaneMaxN); return RAWDTW_OK; }
     if (!strcmp(name, "stream_tile_radius")) { ctx->stream_tile_radius = value < 1 ? 1 : (value > kMaxLaneRadius ? kMaxLaneRadius : (int)value); return RAWDTW_OK; }
     if (!strcmp(name, "chain_long_seeds")) { ctx->chain_long_seeds = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 1 << 20); return RAWDTW_OK; }
+    if (!strcmp(name, "chain_max_chains")) { // (a count that sizes device arrays: a value outside its range is refused, not clamped)
+        if (value < 0 || value > 4096) return fail(ctx, RAWDTW_ERR_INVALID, "\"chain_max_chains\" is 0 (off) or 1 .. 4096");
+        ctx->chain_max_chains = (uint32_t)value;
+        return RAWDTW_OK;
+    }
     if (!strcmp(name, "seed_minimizer")) { ctx->seed_minimizer = value != 0; return RAWDTW_OK; }
     if (!strcmp(name, "device_round_end")) { ctx->device_round_end = value != 0; return RAWDTW_OK; }
     if (!strcmp(name, "resident_chains")) { ctx->resident_chains = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 1 << 20); return RAWDTW_OK; }
@@ -196,6 +201,7 @@ int rawdtw_get_option(const rawdtw_ctx *ctx, const char *name, int64_t *value)
 {
     if (!ctx || !name || !value) return RAWDTW_ERR_INVALID;
     if (!strcmp(name, "chain_long_seeds")) { *value = ctx->chain_long_seeds; return RAWDTW_OK; }
+    if (!strcmp(name, "chain_max_chains")) { *value = ctx->chain_max_chains; return RAWDTW_OK; }
     if (!strcmp(name, "seed_minimizer")) { *value = ctx->seed_minimizer ? 1 : 0; return RAWDTW_OK; }
     if (!strcmp(name, "device_round_end")) { *value = ctx->device_round_end ? 1 : 0; return RAWDTW_OK; }
     if (!strcmp(name, "round_end_kernel_us")) { *value = round_end_kernel_us(ctx); return RAWDTW_OK; }

@@ -155,6 +155,7 @@ struct rawdtw_ctx {
     bool device_round_end = false; // "device_round_end": a mapper created with this context ends its device-chained rounds on the device
     uint32_t chain_max_seeds = 0; // tests: RAWDTW_CHAIN_MAX_SEEDS lowers rawdtw_chain_round's cap on seeds a read, so that small rounds take the declined path (0: no)
     uint32_t chain_long_seeds = 0; // "chain_long_seeds": reads above the cap with at most this many seeds are chained by rawdtw_chain.hip's long path (0: declined)
+    uint32_t chain_max_chains = 0; // "chain_max_chains": a read with up to this many chains, ties or not, is ordered on the device by rawdtw_sort_order.h (0: 32 chains, 16 with ties)
     bool seed_minimizer = false;   // "seed_minimizer": rawdtw_seed.hip seeds a w > 0 table on the device (k_seed_min) rather than refusing it
     uint64_t signal_events_cap = 0; // "signal_events_cap": the events_cap of a round from signal's first try (rawdtw_mapper.cpp; 0: the mapper's guess)
     std::string err;

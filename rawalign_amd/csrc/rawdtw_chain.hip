@@ -29,6 +29,12 @@
 // candidates in an LDS ring and everything older read back from scratch.  Same results, same flags; with the option on only a read above the
 // option's value still declines the round.
 //
+// MANY CHAINS A READ ("chain_max_chains" = N, off by default).  The two limits on chains are those of the order: 32 records in LDS, and an insertion
+// sort that is std::sort only up to 16 elements.  With the option on the kernels run as k_chain<true> / k_chain_long<true>: a read's records go
+// to its stretch of the round's workspace as they are generated, their scores to LDS, and the order is std::sort's own algorithm restated
+// (rawdtw_sort_order.h) over a permutation that k_chain_compact reads the records through.  Only a read with more than N chains still
+// declines the round.  The <false> instantiations are the kernels as they were.
+//
 // ONE DP BODY.  What restates the reference is written once, as inlined device functions both kernels call: list_end (where a list ends),
 // chain_step (64 candidates of the predecessor loop, rmap.cpp:458-484), chain_ends (the best ends and traceback_chains, rmap.cpp:175-179, 130-173,
 // 502-504) and chain_order (rmap.cpp:512, the tie flag, the read's records and counts).  A kernel supplies where the state lives: k_chain loads a
@@ -37,6 +43,7 @@
 // that marks in device memory need.  The anchor loop, the band's lower end, the running maximum and the end filter (rmap.cpp:486-493) stay in the
 // kernels.  The round's workspace is described once too (ChainLayout): laid from 0 it gives the size, from the block's base the pointers.
 #include "rawdtw_capi.h"
+#include "rawdtw_sort_order.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -61,7 +68,15 @@ struct ChainArgs {
     rawdtw_anchor_t *tmp_anchors; // read r's chains, as generated: [seed_off[r], seed_off[r + 1])
     ChainRecDev *tmp_recs;        // [r * kChainCap ..): in evaluation order
     ChainCnt *cnt;
+    // many chains a read ("chain_max_chains"; MANY CHAINS A READ below).  Off: cap = kChainCap, the rest 0.
+    uint32_t cap;        // chains a read the round records
+    uint32_t rec_div;    // max(1, min_num_anchors): a read of n seeds has at most n / rec_div chains
+    uint32_t by_seeds;   // read r's records start at seed_off[r] / rec_div (0: at r * cap)
+    uint32_t lds_chains; // k_chain's LDS behind the seeds holds the scores and the order of this many chains
+    uint32_t *tmp_perm;  // the evaluation order: a permutation of the read's records, which stay in tmp_recs as generated
 };
+// where read r's records start in tmp_recs (and its order in tmp_perm)
+__device__ __forceinline__ uint64_t rec_start(const ChainArgs &a, const uint32_t r) { return a.by_seeds ? a.seed_off[r] / a.rec_div : (uint64_t)r * a.cap; }
 
 __device__ __forceinline__ void lds_sync()
 {
@@ -142,10 +157,12 @@ __device__ __forceinline__ bool chain_step(const rawdtw_chain_opt_t &o, const in
 // The num_best_chains best ends of the list [g0, g1) (rmap.cpp:175-179: score descending, then index descending) with traceback_chains on lane 0:
 // the chains' anchors to tmp_anchors behind the read's `na` so far, their records to s_rec[nc ..].  kScratch: the arrays are device memory --
 // a release and an acquire at agent scope stand between lane 0's marks and the wave's next look.
-template <bool kScratch> __device__ __forceinline__ void chain_ends(const ChainArgs &a, const unsigned long long *K1, const uint32_t *Q, const float *SC, const uint32_t *PR, unsigned char *FL,
+// kMany: s_rec is the read's stretch of tmp_recs, `room` entries of it are the read's, and a chain's score goes to m_score as well, for chain_order_many.
+template <bool kScratch, bool kMany> __device__ __forceinline__ void chain_ends(const ChainArgs &a, const unsigned long long *K1, const uint32_t *Q, const float *SC, const uint32_t *PR, unsigned char *FL,
                                            const uint32_t key, const uint32_t g0, const uint32_t g1, const uint64_t s0, const float maxs, const uint32_t lane,
-                                           ChainRecDev *s_rec, uint32_t &nc, uint32_t &na, uint32_t &flags)
+                                           ChainRecDev *s_rec, uint32_t &nc, uint32_t &na, uint32_t &flags, float *m_score = nullptr, const uint32_t many_room = 0)
 {
+    const uint32_t room = kMany ? many_room : kChainCap;
     const rawdtw_chain_opt_t &o = a.opt;
     for (int k = 0; k < o.num_best_chains; k++) {
         unsigned long long top = 0;
@@ -178,8 +195,10 @@ template <bool kScratch> __device__ __forceinline__ void chain_ends(const ChainA
                 if (len >= (uint32_t)o.min_num_anchors) {
                     float adj = SC[end];
                     if (stop_at_used) adj -= SC[PR[cur]];
-                    if (nc < kChainCap) s_rec[nc] = ChainRecDev{adj, key, (uint32_t)K1[cur], (uint32_t)K1[end], len, na};
-                    else flags |= 2u;
+                    if (nc < room) {
+                        s_rec[nc] = ChainRecDev{adj, key, (uint32_t)K1[cur], (uint32_t)K1[end], len, na};
+                        if (kMany) m_score[nc] = adj;
+                    } else flags |= 2u;
                     nc++; na += len;
                 }
             }
@@ -209,8 +228,30 @@ __device__ __forceinline__ void chain_order(const ChainArgs &a, const uint32_t r
     for (uint32_t i = 0; i < m; i++) a.tmp_recs[(uint64_t)r * kChainCap + i] = s_rec[s_perm[i]];
     a.cnt[r] = ChainCnt{nc, na, flags, 0u};
 }
+// MANY CHAINS A READ ("chain_max_chains").  rmap.cpp:512 for a read of up to a.cap chains, ties or not: std::sort's own order, restated in
+// rawdtw_sort_order.h, on lane 0 over the scores (m_score) and a permutation (m_perm) in LDS, `room` entries each; its right parts wait on
+// s_stack.  The records stay where chain_ends put them, as generated; the permutation goes to the read's stretch of tmp_perm, which
+// k_chain_compact reads them through.  Called by the whole wave.  room <= the read's stretch and <= the LDS arrays: nothing is stored past either.
+__device__ __forceinline__ void chain_order_many(const ChainArgs &a, const uint32_t r, const uint32_t nc, const uint32_t na, uint32_t flags, const uint32_t room,
+                                                 const float *m_score, uint32_t *m_perm, sort_order::Range *s_stack, const uint32_t lane)
+{
+    const uint32_t m = min(nc, room);
+    for (uint32_t i = lane; i < m; i += 64) m_perm[i] = i;
+    lds_sync();
+    uint32_t ok = 1;
+    if (lane == 0) ok = sort_order::sort_order_desc(m_score, m_perm, m, s_stack, sort_order::kStackCap, nullptr) ? 1u : 0u;
+    lds_sync();
+    if (!uni(ok)) flags |= 2u; // (the stack did not hold: not with kStackCap entries for up to 4 096 chains)
+    const uint64_t t0 = rec_start(a, r);
+    for (uint32_t i = lane; i < m; i += 64) a.tmp_perm[t0 + i] = m_perm[i];
+    if (lane == 0) a.cnt[r] = ChainCnt{nc, na, flags, 0u};
+}
+// what a read of n seeds may record with the option on: no more than the option, than its seeds can make, than the LDS arrays hold
+__device__ __forceinline__ uint32_t many_room(const ChainArgs &a, const uint32_t n, const uint32_t lds_chains) { return min(min(a.cap, n / a.rec_div), lds_chains); }
 
-__global__ __launch_bounds__(64) void k_chain(const ChainArgs a)
+// kMany: the round's cap on chains a read is the option's, not kChainCap -- the instantiation that is launched when the option is off is the
+// kernel as it was, LDS and registers
+template <bool kMany> __global__ __launch_bounds__(64) void k_chain(const ChainArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint32_t n2 = a.n2, lane = threadIdx.x, r = blockIdx.x;
@@ -219,10 +260,15 @@ __global__ __launch_bounds__(64) void k_chain(const ChainArgs a)
     float *SC = reinterpret_cast<float *>(Q + n2);
     uint32_t *PR = reinterpret_cast<uint32_t *>(SC + n2);
     unsigned char *FL = reinterpret_cast<unsigned char *>(PR + n2); // 1 used, 2 end candidate, 4 taken
-    __shared__ ChainRecDev s_rec[kChainCap];
-    __shared__ uint32_t s_perm[kChainCap];
+    __shared__ ChainRecDev s_rec[kMany ? 1 : kChainCap];
+    __shared__ uint32_t s_perm[kMany ? 1 : kChainCap];
+    __shared__ sort_order::Range s_stack[kMany ? sort_order::kStackCap : 1];
+    float *m_score = reinterpret_cast<float *>(FL + n2); // (kMany: a.lds_chains scores, then as many entries of the order; n2 is a multiple of 64)
+    uint32_t *m_perm = reinterpret_cast<uint32_t *>(m_score + a.lds_chains);
     const uint64_t s0 = a.seed_off[r];
     const uint32_t n = (uint32_t)(a.seed_off[r + 1] - s0);
+    const uint32_t room = kMany ? many_room(a, n, a.lds_chains) : kChainCap;
+    ChainRecDev *rec_out = kMany ? a.tmp_recs + rec_start(a, r) : s_rec;
     if (n == 0 || n > n2) { // (no seeds: no chains.  Too many: declined -- the host sizes n2 by the round's largest read, so only past the cap)
         if (lane == 0) a.cnt[r] = ChainCnt{0u, 0u, n > n2 ? 1u : 0u, 0u};
         return;
@@ -270,10 +316,11 @@ __global__ __launch_bounds__(64) void k_chain(const ChainArgs a)
             if (lane == 0) { SC[ai] = best; PR[ai] = pred; FL[ai] = is_end ? 2 : 0; }
             lds_sync();
         }
-        chain_ends<false>(a, K1, Q, SC, PR, FL, key, g0, g1, s0, maxs, lane, s_rec, nc, na, flags);
+        chain_ends<false, kMany>(a, K1, Q, SC, PR, FL, key, g0, g1, s0, maxs, lane, rec_out, nc, na, flags, m_score, room);
         g0 = g1;
     }
-    if (lane == 0) chain_order(a, r, nc, na, flags, s_rec, s_perm);
+    if (kMany) chain_order_many(a, r, nc, na, flags, room, m_score, m_perm, s_stack, lane);
+    else if (lane == 0) chain_order(a, r, nc, na, flags, s_rec, s_perm);
 }
 
 // ---- the long path: reads above k_chain's cap, state in device memory ----
@@ -292,6 +339,7 @@ struct LongArgs {
     uint32_t *PR;
     unsigned char *FL;
     unsigned long long *far_steps; // the round's totals[4]
+    uint32_t lds_chains;           // "chain_max_chains": k_chain_long's dynamic LDS holds the scores and the order of this many chains (0: none)
 };
 
 __device__ __forceinline__ void sort_cmp(unsigned long long &ka, uint32_t &qa, unsigned long long &kb, uint32_t &qb)
@@ -384,16 +432,22 @@ __global__ __launch_bounds__(256) void k_chain_sort_long(const ChainArgs a, cons
 //     array of the three that this launch wrote, are loaded with agent-scope atomic loads, which do not take a line from L1.  That holds for
 //     any kRing >= 128, not by the distance of 960.
 //   * Ends and traceback read and mark scratch: a release and an acquire at agent scope stand between lane 0's marks and the wave's next look.
-__global__ __launch_bounds__(64) void k_chain_long(const ChainArgs a, const LongArgs la)
+template <bool kMany> __global__ __launch_bounds__(64) void k_chain_long(const ChainArgs a, const LongArgs la)
 {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[]; // (kMany only: la.lds_chains scores, then as many entries of the order)
     __shared__ uint32_t r_t[kRing], r_q[kRing];
     __shared__ float r_s[kRing];
-    __shared__ ChainRecDev s_rec[kChainCap];
-    __shared__ uint32_t s_perm[kChainCap];
+    __shared__ ChainRecDev s_rec[kMany ? 1 : kChainCap];
+    __shared__ uint32_t s_perm[kMany ? 1 : kChainCap];
+    __shared__ sort_order::Range s_stack[kMany ? sort_order::kStackCap : 1];
     const LongRead lr = la.reads[blockIdx.x];
     const uint32_t lane = threadIdx.x, r = lr.r;
     const uint64_t s0 = a.seed_off[r];
     const uint32_t n = (uint32_t)(a.seed_off[r + 1] - s0);
+    float *m_score = kMany ? reinterpret_cast<float *>(smem) : nullptr;
+    uint32_t *m_perm = kMany ? reinterpret_cast<uint32_t *>(m_score + la.lds_chains) : nullptr;
+    const uint32_t room = kMany ? many_room(a, n, la.lds_chains) : kChainCap;
+    ChainRecDev *rec_out = kMany ? a.tmp_recs + rec_start(a, r) : s_rec;
     const unsigned long long *K1 = la.K1 + lr.off;
     const uint32_t *Q = la.Q + lr.off;
     float *SC = la.SC + lr.off;
@@ -448,26 +502,36 @@ __global__ __launch_bounds__(64) void k_chain_long(const ChainArgs a, const Long
         }
         if (flushed < g1) flush(g1);
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        chain_ends<true>(a, K1, Q, SC, PR, FL, key, g0, g1, s0, maxs, lane, s_rec, nc, na, flags);
+        chain_ends<true, kMany>(a, K1, Q, SC, PR, FL, key, g0, g1, s0, maxs, lane, rec_out, nc, na, flags, m_score, room);
         g0 = g1;
     }
-    if (lane == 0) {
-        chain_order(a, r, nc, na, flags, s_rec, s_perm);
-        if (far) atomicAdd(la.far_steps, (unsigned long long)far);
-    }
+    if (kMany) chain_order_many(a, r, nc, na, flags, room, m_score, m_perm, s_stack, lane);
+    else if (lane == 0) chain_order(a, r, nc, na, flags, s_rec, s_perm);
+    if (lane == 0 && far) atomicAdd(la.far_steps, (unsigned long long)far);
 }
 
-// the reads' chains and anchors before each read; the round's totals and its flags
-__global__ __launch_bounds__(1024) void k_chain_scan(const ChainCnt *__restrict__ cnt, const uint32_t n_reads, uint64_t *__restrict__ chain_off,
+// the reads' chains and anchors before each read; the round's totals and its flags; totals[5 .. 7]: the reads with more than kChainCap chains,
+// with more than kChainStable, and the most chains a read has (rawdtw_chain_order_stats).  cap: chains a read the round records.
+__global__ __launch_bounds__(1024) void k_chain_scan(const ChainCnt *__restrict__ cnt, const uint32_t n_reads, const uint32_t cap, uint64_t *__restrict__ chain_off,
                                                      uint64_t *__restrict__ read_anchor0, uint64_t *__restrict__ totals /* chains, anchors, flags */)
 {
     __shared__ uint64_t s_c[1024], s_a[1024];
     __shared__ uint32_t s_f[1024];
+    __shared__ uint32_t s_st[3];
     const uint32_t t = threadIdx.x, per = (n_reads + 1023u) / 1024u, lo = min(n_reads, t * per), hi = min(n_reads, lo + per);
     uint64_t c = 0, x = 0;
-    uint32_t f = 0;
-    for (uint32_t r = lo; r < hi; r++) { c += min(cnt[r].nc, kChainCap); x += cnt[r].na; f |= cnt[r].flags; }
+    uint32_t f = 0, above_cap = 0, above_stable = 0, most = 0;
+    if (t < 3) s_st[t] = 0;
+    __syncthreads();
+    for (uint32_t r = lo; r < hi; r++) {
+        const uint32_t nc = cnt[r].nc;
+        c += min(nc, cap); x += cnt[r].na; f |= cnt[r].flags;
+        above_cap += nc > kChainCap; above_stable += nc > kChainStable; most = max(most, nc);
+    }
     s_c[t] = c; s_a[t] = x; s_f[t] = f;
+    if (above_cap) atomicAdd(&s_st[0], above_cap);
+    if (above_stable) atomicAdd(&s_st[1], above_stable);
+    if (most) atomicMax(&s_st[2], most);
     __syncthreads();
     for (uint32_t d = 1; d < 1024; d <<= 1) {
         const uint64_t pc = t >= d ? s_c[t - d] : 0, pa = t >= d ? s_a[t - d] : 0;
@@ -477,8 +541,11 @@ __global__ __launch_bounds__(1024) void k_chain_scan(const ChainCnt *__restrict_
         __syncthreads();
     }
     uint64_t bc = s_c[t] - c, ba = s_a[t] - x;
-    for (uint32_t r = lo; r < hi; r++) { chain_off[r] = bc; read_anchor0[r] = ba; bc += min(cnt[r].nc, kChainCap); ba += cnt[r].na; }
-    if (t == 1023) { chain_off[n_reads] = s_c[t]; totals[0] = s_c[t]; totals[1] = s_a[t]; totals[2] = s_f[t]; totals[3] = 0; }
+    for (uint32_t r = lo; r < hi; r++) { chain_off[r] = bc; read_anchor0[r] = ba; bc += min(cnt[r].nc, cap); ba += cnt[r].na; }
+    if (t == 1023) {
+        chain_off[n_reads] = s_c[t]; totals[0] = s_c[t]; totals[1] = s_a[t]; totals[2] = s_f[t]; totals[3] = 0;
+        totals[5] = s_st[0]; totals[6] = s_st[1]; totals[7] = s_st[2];
+    }
 }
 
 // a wave a read: its chains, in evaluation order, into the batch's arrays
@@ -491,12 +558,13 @@ __global__ __launch_bounds__(64) void k_chain_compact(const ChainArgs a, const u
                                                       const uint64_t h_chains_cap)
 {
     const uint32_t r = blockIdx.x, lane = threadIdx.x;
-    const uint32_t nc = min(a.cnt[r].nc, kChainCap);
-    const uint64_t c0 = chain_off[r], s0 = a.seed_off[r];
+    const uint64_t c0 = chain_off[r], s0 = a.seed_off[r], t0 = rec_start(a, r);
+    uint32_t nc = min(a.cnt[r].nc, a.cap);
+    if (a.rec_div) nc = (uint32_t)min((uint64_t)nc, (a.seed_off[r + 1] - s0) / a.rec_div); // (many chains a read: the stretch the kernels recorded into; a read has no more chains than that)
     const bool host = h_anchor_off && totals[2] == 0 && totals[0] <= h_chains_cap; // (a declined round leaves the host arrays alone)
     uint64_t dst = read_anchor0[r];
     for (uint32_t i = 0; i < nc; i++) {
-        const ChainRecDev rec = a.tmp_recs[(uint64_t)r * kChainCap + i];
+        const ChainRecDev rec = a.tmp_recs[t0 + (a.tmp_perm ? min(a.tmp_perm[t0 + i], nc - 1u) : i)]; // (many chains a read: through the order, inside the read's records)
         for (uint32_t k = lane; k < rec.n; k += 64) {
             const rawdtw_anchor_t v = a.tmp_anchors[s0 + rec.a_off + k];
             anchors[dst + k] = v;
@@ -523,21 +591,33 @@ struct ChainLayout {
     uint64_t n_reads, n_seeds, n_keys;
     bool resident;
     uint64_t n_prev, n_long, long_elems; // (long_elems: the long reads' seeds, each read's stretch rounded up to 64)
+    // "chain_max_chains" (0: off -- kChainCap chains a read) and max(1, min_num_anchors).  With the option on the chain-sized arrays hold
+    // min(n_reads * max_chains, n_seeds / rec_div + 1) entries: chains of a read share no anchor and a recorded chain has at least min_num_anchors,
+    // so a read of n seeds records at most n / rec_div chains and the round n_seeds / rec_div.  A read's records then start at seed_off[r] / rec_div
+    // (by_seeds) -- floor(x / d) + floor(n / d) <= floor((x + n) / d): the stretches do not overlap -- or, where n_reads * max_chains is the
+    // smaller bound, at r * max_chains.  68 bytes a chain: trec 24, tperm 4, aoff 8, refb 8, rbc 4, recs 20.
+    uint64_t max_chains = 0, rec_div = 1;
     uint64_t *soff; rawdtw_seed_t *seeds; uint32_t *rb; uint64_t *kb;                          // inputs
     rawdtw_anchor_t *tmpa; ChainRecDev *trec; ChainCnt *cnt; uint64_t *coff, *ra0;             // per-read scratch
-    uint64_t *tot;                                                                             // chains, anchors, flags, bad keys; [4]: the long path's far steps
+    uint64_t *tot;                                                                             // chains, anchors, flags, bad keys; [4]: the long path's far steps; [5 .. 7]: k_chain_scan's counts
     uint64_t *aoff; rawdtw_anchor_t *anch; uint64_t *refb; uint32_t *rbc; rawdtw_chain_rec_t *recs; // the batch's arrays
     rawdtw_seed_t *prev; uint64_t *poff; uint32_t *cs; uint8_t *so; // a resident round: the previous anchors, dense, their offsets, the chunk starts, the sits-out flags
     uint32_t *psrc;                                            // ... and per read where its previous anchors come from: RAWDTW_PREV_HOST (the dense upload) or a half of the kept chains' store
     LongArgs la;                                               // the long reads' list and their scratch: 21 bytes a seed -- K1 8, Q 4, SC 4, PR 4, FL 1
+    uint32_t *tperm;                                           // "chain_max_chains": the reads' evaluation orders (ChainArgs::tmp_perm)
+
+    uint64_t cap() const { return max_chains ? max_chains : kChainCap; }
+    uint64_t chains_by_seeds() const { return n_seeds / rec_div + 1; }
+    bool by_seeds() const { return max_chains && chains_by_seeds() <= n_reads * max_chains; }
+    uint64_t chain_entries() const { return by_seeds() ? chains_by_seeds() : n_reads * cap(); } // what the chain-sized arrays hold
 
     size_t lay(void *base)
     {
         uintptr_t p = reinterpret_cast<uintptr_t>(base);
-        const uint64_t nc = n_reads * kChainCap, nres = resident ? n_reads : 0;
+        const uint64_t nc = chain_entries(), nres = resident ? n_reads : 0;
         soff = carve<uint64_t>(p, n_reads + 1); seeds = carve<rawdtw_seed_t>(p, n_seeds + 2); rb = carve<uint32_t>(p, n_reads); kb = carve<uint64_t>(p, n_keys + 1);
         tmpa = carve<rawdtw_anchor_t>(p, n_seeds + 2); trec = carve<ChainRecDev>(p, nc); cnt = carve<ChainCnt>(p, n_reads);
-        coff = carve<uint64_t>(p, n_reads + 1); ra0 = carve<uint64_t>(p, n_reads); tot = carve<uint64_t>(p, 5);
+        coff = carve<uint64_t>(p, n_reads + 1); ra0 = carve<uint64_t>(p, n_reads); tot = carve<uint64_t>(p, 8);
         aoff = carve<uint64_t>(p, nc + 1); anch = carve<rawdtw_anchor_t>(p, n_seeds + 2); refb = carve<uint64_t>(p, nc + 1); rbc = carve<uint32_t>(p, nc + 2);
         recs = carve<rawdtw_chain_rec_t>(p, nc + 1);
         prev = carve<rawdtw_seed_t>(p, resident ? n_prev + 2 : 0); poff = carve<uint64_t>(p, resident ? n_reads + 1 : 0); cs = carve<uint32_t>(p, nres);
@@ -545,6 +625,7 @@ struct ChainLayout {
         la.reads = carve<LongRead>(p, n_long); la.K1 = carve<unsigned long long>(p, long_elems); la.Q = carve<uint32_t>(p, long_elems);
         la.SC = carve<float>(p, long_elems); la.PR = carve<uint32_t>(p, long_elems); la.FL = carve<unsigned char>(p, long_elems);
         la.far_steps = reinterpret_cast<unsigned long long *>(tot) + 4;
+        tperm = carve<uint32_t>(p, max_chains ? nc : 0);
         return (size_t)(p - reinterpret_cast<uintptr_t>(base));
     }
 };
@@ -568,6 +649,9 @@ struct ChainWs {
     // the long path: the round's long reads (kept here until the round's end: their upload reads them), and rawdtw_chain_round_stats' counters
     std::vector<LongRead> long_reads;
     uint64_t st_rounds = 0, st_long_reads = 0, st_long_seeds = 0, st_far_steps = 0;
+    // rawdtw_chain_order_stats' counters, over the rounds that were not declined
+    bool many = false; // (the round begun ran with "chain_max_chains" on)
+    uint64_t st_above_32 = 0, st_restated = 0, st_max_chains = 0;
 };
 
 } // namespace
@@ -632,14 +716,16 @@ int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads
     const uint64_t n_seeds = seed_off[n_reads];
     const uint32_t seed_cap = ctx->chain_max_seeds ? std::min(kChainMaxSeeds, ctx->chain_max_seeds) : kChainMaxSeeds;
     const uint64_t long_cap = ctx->chain_long_seeds; // ("chain_long_seeds"; 0: no long path)
+    const uint32_t max_chains = ctx->chain_max_chains; // ("chain_max_chains"; 0: kChainCap a read, kChainStable with ties)
+    const uint32_t rec_div = (uint32_t)std::max(1, opt->min_num_anchors);
     uint32_t most = 0; // (of the reads k_chain takes)
-    uint64_t n_long = 0, long_elems = 0;
+    uint64_t n_long = 0, long_elems = 0, most_long = 0;
     bool too_long = false;
     for (uint64_t r = 0; r < n_reads; r++) {
         if (seed_off[r + 1] < seed_off[r]) return fail(ctx, RAWDTW_ERR_INVALID, "offsets do not ascend");
         const uint64_t nr = seed_off[r + 1] - seed_off[r];
         if (nr <= seed_cap) most = std::max(most, (uint32_t)nr);
-        else if (nr <= long_cap) { n_long++; long_elems += (nr + 63) & ~63ull; }
+        else if (nr <= long_cap) { n_long++; long_elems += (nr + 63) & ~63ull; most_long = std::max(most_long, nr); }
         else too_long = true;
     }
     if (too_long) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, long_cap ? "a read has more seeds than \"chain_long_seeds\" allows: chain this round on the host"
@@ -647,7 +733,7 @@ int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads
     uint32_t n2 = 64;
     while (n2 < most) n2 <<= 1;
     // one block of device memory, grow-only: laid out from 0 for its size, from the block's base for the round's pointers
-    ChainLayout L{n_reads, n_seeds, n_keys, res != nullptr, n_prev, n_long, long_elems};
+    ChainLayout L{n_reads, n_seeds, n_keys, res != nullptr, n_prev, n_long, long_elems, max_chains, rec_div};
     const size_t need = L.lay(nullptr);
     if (!ctx->chain_ws) ctx->chain_ws = new (std::nothrow) rawdtw_chain_ws;
     if (!ctx->chain_ws) return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed");
@@ -684,16 +770,23 @@ int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads
     } else if (n_seeds) HIP_TRY(ctx, hipMemcpyAsync(L.seeds, seeds, (size_t)n_seeds * sizeof(rawdtw_seed_t), hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemcpyAsync(L.rb, read_base, n_reads * 4, hipMemcpyHostToDevice, s));
     if (n_keys) HIP_TRY(ctx, hipMemcpyAsync(L.kb, key_base, (size_t)n_keys * 8, hipMemcpyHostToDevice, s));
-    ChainArgs a{L.soff, L.seeds, (uint32_t)n_reads, n2, *opt, L.tmpa, L.trec, L.cnt};
+    // many chains a read: the scores and the order of a read's chains lie in LDS, 8 bytes a chain, for as many as the option and the launch's
+    // largest read allow (k_chain: at most 2 048 / rec_div, 16 KiB behind 42 KiB of seeds; k_chain_long: at most 4 096, 32 KiB behind its ring)
+    auto lds_chains = [&](const uint64_t seeds_most) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(max_chains, seeds_most / rec_div)); };
+    ChainArgs a{L.soff, L.seeds, (uint32_t)n_reads, n2, *opt, L.tmpa, L.trec, L.cnt, (uint32_t)L.cap(), max_chains ? rec_div : 0u, L.by_seeds() ? 1u : 0u,
+                max_chains ? lds_chains(most) : 0u, max_chains ? L.tperm : nullptr};
     const size_t lds = (size_t)n2 * 21 + 16;
-    hipLaunchKernelGGL(k_chain, dim3((uint32_t)n_reads), dim3(64), lds, s, a);
+    if (max_chains) hipLaunchKernelGGL(k_chain<true>, dim3((uint32_t)n_reads), dim3(64), lds + (size_t)a.lds_chains * 8, s, a);
+    else hipLaunchKernelGGL(k_chain<false>, dim3((uint32_t)n_reads), dim3(64), lds, s, a);
     if (n_long) { // behind k_chain, which has flagged these reads as too long for it: the long launch writes their cnt over that
         HIP_TRY(ctx, hipMemcpyAsync(const_cast<LongRead *>(L.la.reads), w.long_reads.data(), n_long * sizeof(LongRead), hipMemcpyHostToDevice, s));
         HIP_TRY(ctx, hipMemsetAsync(L.la.far_steps, 0, 8, s));
         hipLaunchKernelGGL(k_chain_sort_long, dim3((uint32_t)n_long), dim3(256), 0, s, a, L.la);
-        hipLaunchKernelGGL(k_chain_long, dim3((uint32_t)n_long), dim3(64), 0, s, a, L.la);
+        L.la.lds_chains = max_chains ? lds_chains(most_long) : 0u;
+        if (max_chains) hipLaunchKernelGGL(k_chain_long<true>, dim3((uint32_t)n_long), dim3(64), (size_t)L.la.lds_chains * 8, s, a, L.la);
+        else hipLaunchKernelGGL(k_chain_long<false>, dim3((uint32_t)n_long), dim3(64), 0, s, a, L.la);
     }
-    hipLaunchKernelGGL(k_chain_scan, dim3(1), dim3(1024), 0, s, L.cnt, (uint32_t)n_reads, L.coff, L.ra0, L.tot);
+    hipLaunchKernelGGL(k_chain_scan, dim3(1), dim3(1024), 0, s, L.cnt, (uint32_t)n_reads, a.cap, L.coff, L.ra0, L.tot);
     // the caller's arrays: written by the compaction launch itself when they are page-locked (rawdtw_host_alloc) -- no copy command, no second
     // wait for sizes only the device knows; else copied at the round's end
     auto page_locked = [](const void *q) {
@@ -706,12 +799,12 @@ int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads
                        direct ? anchor_off : nullptr, direct ? recs : nullptr, direct ? anchors : nullptr, chains_cap);
     HIP_TRY(ctx, hipGetLastError());
     uint64_t *h_tot = static_cast<uint64_t *>(w.pin);
-    HIP_TRY(ctx, hipMemcpyAsync(h_tot, L.tot, n_long ? 40 : 32, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(h_tot, L.tot, 64, hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipMemcpyAsync(chain_off, L.coff, (n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
     if (!w.done) HIP_TRY(ctx, hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
     HIP_TRY(ctx, hipEventRecord(w.done, s));
     w.pending = true; w.direct = direct; w.n_reads = n_reads; w.chains_cap = chains_cap;
-    w.n_long = n_long;
+    w.n_long = n_long; w.many = max_chains != 0;
     w.st_rounds++; w.st_long_reads += n_long;
     for (uint64_t k = 0; k < n_long; k++) w.st_long_seeds += seed_off[w.long_reads[k].r + 1] - seed_off[w.long_reads[k].r];
     w.h_anchor_off = anchor_off; w.h_recs = recs; w.h_anchors = anchors;
@@ -763,8 +856,11 @@ int rawdtw_chain_round_end(rawdtw_ctx *ctx, const rawdtw_anchor_t **d_anchors, c
     const uint64_t nc = h_tot[0], na = h_tot[1], flags = h_tot[2];
     if (w.n_long) w.st_far_steps += h_tot[4];
     if (h_tot[3]) return fail(ctx, RAWDTW_ERR_INVALID, "a seed's key is not below n_keys");
-    if (flags) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, flags & 4 ? "a read with more than 16 chains, two of them with equal scores: chain this round on the host"
-                                                               : "a read with more than 32 chains (or more seeds than the device chains): chain this round on the host");
+    if (flags) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, w.many ? "a read with more chains than \"chain_max_chains\" allows: chain this round on the host"
+                                                        : flags & 4 ? "a read with more than 16 chains, two of them with equal scores: chain this round on the host, or set \"chain_max_chains\""
+                                                                    : "a read with more than 32 chains (or more seeds than the device chains): chain this round on the host, or set \"chain_max_chains\"");
+    w.st_above_32 += h_tot[5]; w.st_max_chains = std::max<uint64_t>(w.st_max_chains, h_tot[7]);
+    if (w.many) w.st_restated += h_tot[6];
     if (nc > w.chains_cap) return fail(ctx, RAWDTW_ERR_RANGE, "chain output arrays too small");
     if (!w.direct) {
         HIP_TRY(ctx, hipMemcpyAsync(w.h_anchor_off, w.d_aoff, (nc + 1) * 8, hipMemcpyDeviceToHost, s));
@@ -795,6 +891,17 @@ int rawdtw_chain_round_stats(const rawdtw_ctx *ctx, uint64_t *rounds, uint64_t *
     if (long_reads) *long_reads = w.st_long_reads;
     if (long_seeds) *long_seeds = w.st_long_seeds;
     if (far_steps) *far_steps = w.st_far_steps;
+    return RAWDTW_OK;
+}
+
+int rawdtw_chain_order_stats(const rawdtw_ctx *ctx, uint64_t *reads_above_32, uint64_t *reads_ordered_restated, uint64_t *max_chains_a_read)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    const ChainWs none;
+    const ChainWs &w = ctx->chain_ws ? ctx->chain_ws->w : none;
+    if (reads_above_32) *reads_above_32 = w.st_above_32;
+    if (reads_ordered_restated) *reads_ordered_restated = w.st_restated;
+    if (max_chains_a_read) *max_chains_a_read = w.st_max_chains;
     return RAWDTW_OK;
 }
 

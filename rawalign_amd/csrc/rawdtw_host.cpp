@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/rawdtw.h"
+#include "rawdtw_sort_order.h"
 
 namespace {
 
@@ -397,6 +398,18 @@ int rawdtw_sort_by_chaining_score(const float *chaining_score, uint32_t n_chains
     std::sort(v.begin(), v.end(), [](const Item &a, const Item &b) { return a.score > b.score; });
     for (uint32_t c = 0; c < n_chains; c++) perm_out[c] = v[c].idx;
     return RAWDTW_OK;
+}
+
+// the same order from rawdtw_sort_order.h, the restatement the device's chaining runs: checked against the function above permutation for permutation
+int rawdtw_sort_by_chaining_score_restated(const float *chaining_score, uint32_t n_chains, uint32_t *perm_out, uint32_t *phases_out)
+{
+    if ((!chaining_score || !perm_out) && n_chains) return RAWDTW_ERR_INVALID;
+    for (uint32_t c = 0; c < n_chains; c++) perm_out[c] = c;
+    rawdtw::sort_order::Range stack[2 * 32 + 1]; // (2 * floor(log2 n) for any 32-bit n)
+    uint32_t phases = 0;
+    const bool ok = rawdtw::sort_order::sort_order_desc(chaining_score, perm_out, n_chains, stack, 2 * 32 + 1, &phases);
+    if (phases_out) *phases_out = phases;
+    return ok ? RAWDTW_OK : RAWDTW_ERR_RANGE;
 }
 
 int rawdtw_batch_build_jobs(const rawdtw_align_opt_t *opt, uint64_t n_chains, const uint64_t *anchor_off,

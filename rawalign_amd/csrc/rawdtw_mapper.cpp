@@ -600,7 +600,12 @@ struct Round {
         g.hw_reads = std::max(g.hw_reads, n.reads); g.hw_chains = std::max(g.hw_chains, n.chains); g.hw_anchors = std::max(g.hw_anchors, n.anchors);
         g.hw_new = std::max(g.hw_new, n.new_anchors); g.hw_events = std::max(g.hw_events, n.events); g.hw_seg = std::max(g.hw_seg, n.seg);
         g.hw_seeds = std::max(g.hw_seeds, n.seeds);
-        if (dev) g.hw_chains = std::max<uint64_t>(g.hw_chains, g.hw_reads * 32); // (the device's cap on chains a read)
+        if (dev) { // the device's cap on chains a read: 32, or "chain_max_chains" -- then no more than the seeds can make, min_num_anchors a chain
+            int64_t many = 0;
+            (void)rawdtw_get_option(g.ctx, "chain_max_chains", &many);
+            const uint64_t by_seeds = g.hw_seeds / (uint64_t)std::max(1, m->opt.chain.min_num_anchors) + 1;
+            g.hw_chains = std::max<uint64_t>(g.hw_chains, many > 0 ? std::min<uint64_t>(g.hw_reads * (uint64_t)many, by_seeds) : g.hw_reads * 32);
+        }
         const uint64_t nr = g.hw_reads + 1, nc = g.hw_chains + 1;
         for (int b = 0; b < 2; b++) {
             RoundArrays &x = g.buf[g.cur ^ b];
@@ -1211,6 +1216,9 @@ int rawdtw_mapper_create(rawdtw_ctx *ctx, const rawdtw_mapper_opt_t *opt, uint32
         int64_t chain_long = 0; // (both groups chain the same reads on the device)
         if (st == RAWDTW_OK) st = rawdtw_get_option(ctx, "chain_long_seeds", &chain_long);
         if (st == RAWDTW_OK) st = rawdtw_set_option(m->groups[1].ctx, "chain_long_seeds", chain_long);
+        int64_t chain_many = 0;
+        if (st == RAWDTW_OK) st = rawdtw_get_option(ctx, "chain_max_chains", &chain_many);
+        if (st == RAWDTW_OK) st = rawdtw_set_option(m->groups[1].ctx, "chain_max_chains", chain_many);
     }
     const uint64_t per_group = ((uint64_t)opt->max_reads + (uint64_t)m->opt.groups - 1) / (uint64_t)m->opt.groups;
     for (Group &g : m->groups)

@@ -274,6 +274,13 @@ class Engine:
         self._check(self.lib.rawdtw_chain_round_stats(self._ctx, *[C.byref(x) for x in v]))
         return dict(zip(("rounds", "long_reads", "long_seeds", "far_steps"), (int(x.value) for x in v)))
 
+    def chain_order_stats(self) -> dict:
+        """rawdtw_chain_order_stats: over this context's chaining rounds that were not declined, the reads with more than 32 chains, the reads
+        with more than 16 that "chain_max_chains" ordered with the restated std::sort, and the most chains a read had -- cumulative"""
+        v = [C.c_uint64() for _ in range(3)]
+        self._check(self.lib.rawdtw_chain_order_stats(self._ctx, *[C.byref(x) for x in v]))
+        return dict(zip(("reads_above_32", "reads_ordered_restated", "max_chains_a_read"), (int(x.value) for x in v)))
+
     def round_end(self, select_opt, chain_off, recs, score, keep=None):
         """rawdtw_round_end: gen_primary_chains, comp_mapq and the stop rule for every read of a round in one launch.  `select_opt` is a
         SelectOpt (mapping.StopOpt.c_struct); read r's candidates are [chain_off[r], chain_off[r+1]) of recs (CHAIN_REC_DTYPE), score and
