@@ -166,6 +166,15 @@ int rawdtw_set_events_device(rawdtw_ctx *ctx, const float *d_events, uint64_t n_
 int rawdtw_events_reserve(rawdtw_ctx *ctx, uint64_t n_floats);
 int rawdtw_events_append(rawdtw_ctx *ctx, const float *h_new, uint64_t n_new, uint32_t n_segments,
                          const uint64_t *seg_src_off, const uint32_t *seg_dst_off);
+/* The way back: stretches of the arena to the host.  Segment q is arena[seg_start[q] .. seg_start[q] + seg_len[q]); the segments
+ * (overlapping or empty ones too) arrive densely in order in out, out_off[0 .. n_segments] is written with their prefix sum.  One
+ * gather launch; the call waits for it.  An `out` from rawdtw_host_alloc is written by the device itself, any other memory takes a
+ * staging block of the context and one copy.  Before anything is enqueued: RAWDTW_ERR_INVALID for a null argument, a context without
+ * an arena, a segment that ends beyond the arena's logical size, and a page-locked `out` whose allocation does not hold out_cap
+ * floats from `out` on; RAWDTW_ERR_RANGE when the segments' total is above out_cap -- out_off is filled then too, out is not
+ * touched.  Nothing is written behind the total. */
+int rawdtw_events_fetch(rawdtw_ctx *ctx, uint32_t n_segments, const uint32_t *seg_start, const uint32_t *seg_len,
+                        uint64_t *out_off /* n_segments+1, written */, float *out, uint64_t out_cap);
 /* Page-locked host memory for the arrays handed to rawdtw_batch_create / rawdtw_events_append and for the result
  * arrays of rawdtw_batch_fetch.  Any host memory works; with pinned memory the copies do not block the caller. */
 int rawdtw_host_alloc(uint64_t bytes, void **out);
@@ -237,6 +246,14 @@ int rawdtw_traceback_batch(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n
  * order (the aln:s: writer, rmap.cpp:580-592) needs nothing else. */
 int rawdtw_traceback_batch_steps(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs,
                                  const float *h_events, uint64_t n_events, float *out_cost,
+                                 const uint64_t *path_off, uint32_t *path_len, uint8_t *path_step, float *path_d);
+
+/* rawdtw_traceback_batch_steps over the context's event arena AS IT LIES: the jobs' read_off index the arena whatever filled it
+ * (rawdtw_upload_events, rawdtw_set_events_device, rawdtw_events_reserve / _append, a resident detection).  Nothing is uploaded and
+ * nothing is written into the arena.  RAWDTW_ERR_INVALID before anything is enqueued for a context without an arena and for a job
+ * whose read_off + n lies beyond the arena's logical size; otherwise the statuses, the path layout, the sub-batches
+ * ("tb_workspace_mb") and the timing counters are those of the steps form. */
+int rawdtw_traceback_arena_steps(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, float *out_cost,
                                  const uint64_t *path_off, uint32_t *path_len, uint8_t *path_step, float *path_d);
 
 /* Device time of the most recent rawdtw_traceback_batch on this context (HIP events on its stream, summed over its
@@ -959,7 +976,7 @@ int rawdtw_mapper_resident_stats(const rawdtw_mapper *m, uint64_t *resident_roun
  *       counts on (a round the device chaining declines fetches the hits -- not the events -- and is chained on the host: same lines).
  *       One upload (the samples), one launch sequence and one wait in front of the chaining.  Preconditions: those of
  *       rawdtw_mapper_round_seeded_resident, and nothing may read the host's copy of a read's events later -- no --dtw-output-cigar
- *       (flag 0x4; rawdtw_mapper_finish uploads that copy) and no external scorer, neither then nor afterwards (rawdtw_mapper_set_scorer is
+ *       (flag 0x4; rawdtw_mapper_finish uploads that copy -- unless "signal_cigar" below is on) and no external scorer, neither then nor afterwards (rawdtw_mapper_set_scorer is
  *       refused once such a round has run); a mapper with no DTW stage is served.  Anything else: RAWDTW_ERR_UNSUPPORTED with nothing
  *       changed (rawdtw_detect_raw_begin + rawdtw_mapper_round_seeded_resident map the round).  events_cap is the mapper's guess -- what
  *       the seeding's workspace holds already, or a quarter of the round's samples + 1 024 --, and a round with more events runs once more
@@ -968,6 +985,18 @@ int rawdtw_mapper_resident_stats(const rawdtw_mapper *m, uint64_t *resident_roun
  *       scratch and overwritten by the next attempt.
  *   rawdtw_set_option(ctx, "signal_events_cap", N)  N > 0: the first try's events_cap of the mapper's rounds from signal on this context
  *       (tests of the retry); 0, the default: the guess.  rawdtw_get_option reads it back.
+ *   rawdtw_set_option(ctx, "signal_cigar", 0 | 1)  opt-in, default 0 (any other value: RAWDTW_ERR_INVALID); read once a round, and read
+ *       back by rawdtw_get_option.  1: the two rounds from signal no longer refuse a mapper for flag 0x4 (--dtw-output-cigar) alone --
+ *       every other refusal stays, an external scorer set later included.  Once such a round is committed, rawdtw_mapper_finish takes
+ *       EVERY mapped read's events from its slot of the arena (a context mapper's rounds of every kind put them there): the jobs are built
+ *       over the slot's base and go to rawdtw_traceback_arena_steps; the arena is not replaced, no event is uploaded and
+ *       event_bytes_crossed stays what it was.  On any other mapper, whatever the option says, rawdtw_mapper_finish is unchanged.  The
+ *       one thing it cannot serve: a read that got events in a round of a mapper without a DTW stage chained on the host (those never
+ *       reach the arena) -- RAWDTW_ERR_UNSUPPORTED from rawdtw_mapper_finish, nothing changed.
+ *   rawdtw_mapper_read_events  read read_id's committed events: from its slot of the arena through rawdtw_events_fetch on a mapper with a
+ *       context, from the host's copy otherwise (also after a rawdtw_mapper_finish that uploaded the host's copies over the arena, and for
+ *       a read with events from a round that ran nothing on the device).  *n is always written with their number (0 for a read with no round yet);
+ *       cap < *n: RAWDTW_ERR_RANGE, out untouched.  out may be NULL when cap is 0.
  *   rawdtw_mapper_signal_stats  rounds from signal that were committed, how many of them ran twice, bytes of samples sent up (both tries
  *       of a retried round), and the bytes of events that crossed PCIe in either direction over all of the mapper's rounds (what
  *       rawdtw_mapper_timing's slot 6 counts: 0 for a mapper that only ran rounds from signal).  Any pointer may be NULL. ---- */
@@ -987,6 +1016,7 @@ int rawdtw_mapper_round_raw_resident(rawdtw_mapper *m, const rawdtw_seed_index *
                                      const rawdtw_channel_t *chan /* n_reads */);
 int rawdtw_mapper_signal_stats(const rawdtw_mapper *m, uint64_t *rounds, uint64_t *retried_rounds, uint64_t *sample_bytes_to_device,
                                uint64_t *event_bytes_crossed);
+int rawdtw_mapper_read_events(rawdtw_mapper *m, uint32_t read_id, float *out, uint32_t cap, uint32_t *n);
 
 /* ---- a round's end for all its reads at once: gen_primary_chains (rmap.cpp:90-128, comparator rmap.h:41-45), comp_mapq (65-88) and
  * is_mapped_with_high_confidence (594-665) -- the three steps between a batch's score / keep and "this read is finished".

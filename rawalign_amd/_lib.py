@@ -168,6 +168,7 @@ SYMBOLS = {
     "rawdtw_set_events_device": (I32, [VP, VP, U64]),
     "rawdtw_events_reserve": (I32, [VP, U64]),
     "rawdtw_events_append": (I32, [VP, VP, U64, U32, VP, VP]),
+    "rawdtw_events_fetch": (I32, [VP, U32, VP, VP, VP, VP, U64]),
     "rawdtw_host_alloc": (I32, [U64, C.POINTER(VP)]),
     "rawdtw_host_free": (I32, [VP]),
     "rawdtw_host_is_page_locked": (I32, [VP]),
@@ -182,6 +183,7 @@ SYMBOLS = {
     "rawdtw_plan_destroy": (I32, [VP]),
     "rawdtw_traceback_batch": (I32, [VP, VP, U64, VP, U64, VP, VP, VP, VP, VP, VP]),
     "rawdtw_traceback_batch_steps": (I32, [VP, VP, U64, VP, U64, VP, VP, VP, VP, VP]),
+    "rawdtw_traceback_arena_steps": (I32, [VP, VP, U64, VP, VP, VP, VP, VP]),
     "rawdtw_dtw_global": (I32, [VP, VP, U32, VP, U32, I32, C.POINTER(F32)]),
     "rawdtw_dtw_global_slantedbanded_antidiagonalwise": (I32, [VP, VP, U32, VP, U32, I32, I32, C.POINTER(F32)]),
     "rawdtw_dtw_global_tb": (I32, [VP, VP, U32, VP, U32, I32, C.POINTER(F32), C.POINTER(U32), VP, VP, VP]),
@@ -287,6 +289,7 @@ SYMBOLS = {
     "rawdtw_mapper_round_signal_resident": (I32, [VP, VP, C.POINTER(EventOpt), U32, VP, VP, VP]),
     "rawdtw_mapper_round_raw_resident": (I32, [VP, VP, C.POINTER(EventOpt), U32, VP, VP, VP, VP]),
     "rawdtw_mapper_signal_stats": (I32, [VP, VP, VP, VP, VP]),
+    "rawdtw_mapper_read_events": (I32, [VP, U32, VP, U32, VP]),
     "rawdtw_round_end_host": (I32, [C.POINTER(SelectOpt), U64, VP, VP, VP, VP, VP, VP]),
     "rawdtw_round_end": (I32, [VP, C.POINTER(SelectOpt), U64, VP, VP, VP, VP, VP, VP]),
     "rawdtw_batch_round_end_begin": (I32, [VP, VP, C.POINTER(SelectOpt), VP, I32]),

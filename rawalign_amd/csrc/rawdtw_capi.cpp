@@ -123,6 +123,7 @@ int rawdtw_destroy(rawdtw_ctx *ctx)
     keep_ws_free(ctx);
     for (StreamWs &w : ctx->ws_free) { if (w.d) (void)hipFree(w.d); if (w.h) (void)hipHostFree(w.h); }
     if (ctx->d_append) (void)hipFree(ctx->d_append);
+    if (ctx->d_fetch) (void)hipFree(ctx->d_fetch);
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
     for (hipEvent_t &e : ctx->tb_ev) if (e) (void)hipEventDestroy(e);
     if (ctx->tb_copy) (void)hipStreamDestroy(ctx->tb_copy);
@@ -189,6 +190,11 @@ int rawdtw_set_option(rawdtw_ctx *ctx, const char *name, int64_t value)
     if (!strcmp(name, "device_round_end")) { ctx->device_round_end = value != 0; return RAWDTW_OK; }
     if (!strcmp(name, "resident_chains")) { ctx->resident_chains = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 1 << 20); return RAWDTW_OK; }
     if (!strcmp(name, "signal_events_cap")) { ctx->signal_events_cap = (uint64_t)std::max<int64_t>(value, 0); return RAWDTW_OK; }
+    if (!strcmp(name, "signal_cigar")) { // (an opt-in that changes what a mapper accepts: a value that is neither is refused, not read as "on")
+        if (value != 0 && value != 1) return fail(ctx, RAWDTW_ERR_INVALID, "\"signal_cigar\" is 0 (off) or 1");
+        ctx->signal_cigar = value == 1;
+        return RAWDTW_OK;
+    }
     if (!strcmp(name, "tb_workspace_mb")) { ctx->tb_workspace_mb = (uint64_t)std::min<int64_t>(std::max<int64_t>(value, 0), 1 << 30); return RAWDTW_OK; }
     if (!strcmp(name, "lane_max_radius")) {
         ctx->lane_max_radius = value < 0 ? 0 : (value > kMaxLaneRadius ? kMaxLaneRadius : (int)value);
@@ -208,6 +214,7 @@ int rawdtw_get_option(const rawdtw_ctx *ctx, const char *name, int64_t *value)
     if (!strcmp(name, "resident_chains")) { *value = ctx->resident_chains; return RAWDTW_OK; }
     if (!strcmp(name, "round_keep_kernel_us")) { *value = round_keep_kernel_us(ctx); return RAWDTW_OK; }
     if (!strcmp(name, "signal_events_cap")) { *value = (int64_t)ctx->signal_events_cap; return RAWDTW_OK; }
+    if (!strcmp(name, "signal_cigar")) { *value = ctx->signal_cigar ? 1 : 0; return RAWDTW_OK; }
     if (!strcmp(name, "tb_workspace_mb")) { *value = (int64_t)ctx->tb_workspace_mb; return RAWDTW_OK; }
     if (!strcmp(name, "tb_sub_batches")) { *value = (int64_t)ctx->tb_sub_batches; return RAWDTW_OK; }
     return RAWDTW_ERR_INVALID;
@@ -389,6 +396,48 @@ int rawdtw_events_append(rawdtw_ctx *ctx, const float *h_new, uint64_t n_new, ui
     HIP_TRY(ctx, hipMemcpyAsync(d_src, seg_src_off, ((size_t)n_segments + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_dst, seg_dst_off, (size_t)n_segments * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, launch_events_scatter(d_new, ctx->d_ev, d_src, d_dst, n_segments, ctx->stream));
+    return RAWDTW_OK;
+}
+
+int rawdtw_events_fetch(rawdtw_ctx *ctx, uint32_t n_segments, const uint32_t *seg_start, const uint32_t *seg_len, uint64_t *out_off,
+                        float *out, uint64_t out_cap)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (!out_off || (n_segments && (!seg_start || !seg_len)) || (out_cap && !out)) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    if (!ctx->d_ev) return fail(ctx, RAWDTW_ERR_INVALID, "the context has no event arena");
+    for (uint32_t q = 0; q < n_segments; q++)
+        if ((uint64_t)seg_start[q] + seg_len[q] > ctx->n_ev) return fail(ctx, RAWDTW_ERR_INVALID, "segment outside the event arena");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // a page-locked `out` is written by the device itself, through the allocation's DEVICE address, and only when out_cap floats from `out`
+    // on lie inside that allocation; one that does not hold them is the caller's mistake, not a reason to take the staging
+    float *dv = out_cap ? static_cast<float *>(device_view(out, out_cap * 4)) : nullptr;
+    if (out_cap && !dv && rawdtw_host_is_page_locked(out) == 1)
+        return fail(ctx, RAWDTW_ERR_INVALID, "the page-locked allocation behind out does not hold out_cap floats");
+    out_off[0] = 0;
+    for (uint32_t q = 0; q < n_segments; q++) out_off[q + 1] = out_off[q] + seg_len[q];
+    const uint64_t total = out_off[n_segments];
+    if (total > out_cap) return fail(ctx, RAWDTW_ERR_RANGE, "out_cap is below the segments' total");
+    if (total == 0) return RAWDTW_OK;
+    // the context's block: the two tables, and the staging behind them for an `out` the device cannot write (grow-only)
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t at_start = al(((size_t)n_segments + 1) * 8), at_stage = at_start + al((size_t)n_segments * 4);
+    const size_t need = at_stage + (dv ? 0 : al((size_t)total * 4));
+    if (ctx->fetch_bytes < need) {
+        if (ctx->d_fetch) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->d_fetch); }
+        ctx->d_fetch = nullptr; ctx->fetch_bytes = 0;
+        if (hipMalloc(&ctx->d_fetch, need + need / 4) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, RAWDTW_ERR_OOM, "no device memory for the fetch"); }
+        ctx->fetch_bytes = need + need / 4;
+    }
+    char *const p = static_cast<char *>(ctx->d_fetch);
+    uint64_t *d_off = reinterpret_cast<uint64_t *>(p);
+    uint32_t *d_start = reinterpret_cast<uint32_t *>(p + at_start);
+    float *d_stage = reinterpret_cast<float *>(p + at_stage);
+    hipStream_t s = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(d_off, out_off, ((size_t)n_segments + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_start, seg_start, (size_t)n_segments * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, launch_events_gather(ctx->d_ev, dv ? dv : d_stage, d_start, d_off, n_segments, total, s));
+    if (!dv) HIP_TRY(ctx, hipMemcpyAsync(out, d_stage, (size_t)total * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
     return RAWDTW_OK;
 }
 

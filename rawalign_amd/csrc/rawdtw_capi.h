@@ -109,6 +109,8 @@ struct rawdtw_ctx {
     std::vector<uint64_t> job_off_scratch;
     void *d_append = nullptr;          // rawdtw_events_append staging, grow-only
     size_t append_bytes = 0;
+    void *d_fetch = nullptr;           // rawdtw_events_fetch: the segment tables and, for an `out` the device cannot write, the staging; grow-only
+    size_t fetch_bytes = 0;
     uint8_t *d_tb_dir = nullptr; // traceback direction workspace, grow-only (hipFree of 600 MB per call costs 1 ms)
     uint64_t tb_dir_bytes = 0;
     void *d_tb_paths = nullptr;  // traceback path buffers (offsets, lengths, i/j end-first, i/j/d start-first), grow-only
@@ -157,6 +159,7 @@ struct rawdtw_ctx {
     uint32_t chain_long_seeds = 0; // "chain_long_seeds": reads above the cap with at most this many seeds are chained by rawdtw_chain.hip's long path (0: declined)
     uint32_t chain_max_chains = 0; // "chain_max_chains": a read with up to this many chains, ties or not, is ordered on the device by rawdtw_sort_order.h (0: 32 chains, 16 with ties)
     bool seed_minimizer = false;   // "seed_minimizer": rawdtw_seed.hip seeds a w > 0 table on the device (k_seed_min) rather than refusing it
+    bool signal_cigar = false;     // "signal_cigar": a mapper created with this context takes --dtw-output-cigar through its rounds from signal; its finish reads the arena
     uint64_t signal_events_cap = 0; // "signal_events_cap": the events_cap of a round from signal's first try (rawdtw_mapper.cpp; 0: the mapper's guess)
     std::string err;
 };

@@ -192,6 +192,8 @@ hipError_t stream_count_cells(const StreamArgs &a, unsigned long long *d_total, 
 hipError_t stream_sum_stats(const StreamArgs &a, hipStream_t s);
 hipError_t launch_events_scatter(const float *d_src, float *d_dst, const uint64_t *d_seg_src, const uint32_t *d_seg_dst,
                                  uint32_t n_seg, hipStream_t s);
+hipError_t launch_events_gather(const float *d_arena, float *d_out, const uint32_t *d_seg_start, const uint64_t *d_out_off, uint32_t n_seg,
+                                uint64_t total, hipStream_t s);
 
 hipError_t launch_band_merged(const TileDesc *tiles, uint64_t n_tiles, const TileSpan *spans, const TileJob *tjobs,
                               const unsigned long long *masks, uint32_t lds_floats, const DevJob *wjobs, uint64_t n_w,

@@ -73,6 +73,8 @@ struct MRead {
     struct Kept { bool valid = false; uint8_t half = 0; uint32_t count = 0; } kept;
     bool gated = false;          // ... at or after the stop point of its batch (rmap.cpp:960: a mapped read's line loses its fields)
     bool dropped = false;        // ... added but in no closed batch when the stop fired, or added after it: finished, no line
+    bool host_only = false;      // some of its events never reached the arena: a round that ran nothing on the device (no DTW stage and the chains
+                                 // made on the host, an external scorer, no context) -- the host's copy is then complete up to that round
 };
 
 // growable array in page-locked memory (plain memory for a mapper without a device); contents are NOT kept over a growth
@@ -324,6 +326,9 @@ struct rawdtw_mapper {
     uint32_t kp_reserved = 0;
     bool kp_any = false; // some read may hold kept chains
     uint64_t sig_cap = 0; // the largest events_cap a round from signal ran with: what the seeding's workspace holds already
+    bool arena_replaced = false;    // rawdtw_mapper_finish has uploaded the host's copies over the event arena: no slot holds its read's events any more
+    bool finish_from_arena = false; // "signal_cigar": a --dtw-output-cigar mapper has committed a round from signal -- the host's copy of a read's
+                                    // events is incomplete from then on, and rawdtw_mapper_finish reads every read's events in its slot of the arena
 };
 
 namespace {
@@ -528,6 +533,21 @@ uint32_t resident_chains_option(const rawdtw_mapper *m)
 {
     int64_t v = 0;
     return m->ctx && rawdtw_get_option(m->ctx, "resident_chains", &v) == RAWDTW_OK && v > 0 ? (uint32_t)v : 0u;
+}
+
+// "signal_cigar" on the context the mapper was created with
+bool signal_cigar_option(const rawdtw_mapper *m)
+{
+    int64_t v = 0;
+    return m->ctx && rawdtw_get_option(m->ctx, "signal_cigar", &v) == RAWDTW_OK && v != 0;
+}
+
+// a read's slot in its group's event arena: the group's context and the slot's first float
+rawdtw_ctx *slot_of(const rawdtw_mapper *m, const MRead &rd, uint32_t *base)
+{
+    const uint32_t G = (uint32_t)m->groups.size();
+    *base = (G == 2 ? rd.slot / 2 : rd.slot) * m->opt.slot_events;
+    return m->groups[rd.slot % G].ctx;
 }
 
 // a round's sizes in one group (0 where its path does not know them)
@@ -1154,6 +1174,7 @@ struct Round {
             MRead &rd = read(k); RoundRead &r = rr[k];
             if (!r.log.empty()) m->log += r.log;
             rd.chunks_done++;
+            if (!on_device && r.ne) rd.host_only = true; // (none of this round's paths sent its events up)
             if (r.high) { rd.finished = true; rd.broke_early = true; } // rmap.cpp:692 (evaluated with the round's end, per read on the pool)
             else if (rd.chunks_done >= std::min(rd.n_chunks, m->opt.max_num_chunk)) rd.finished = true;
         }
@@ -1475,10 +1496,15 @@ int round_from_signal(rawdtw_mapper *m, const rawdtw_seed_index *six, const rawd
     if (const int st = seed_index_checks(m, six, &pars)) return st;
     // rawdtw_mapper_round_seeded_resident's preconditions, and nothing may read the host's copy of a read's events later: that is the
     // --dtw-output-cigar traceback and an external scorer.  A mapper with no DTW stage keeps the copy for neither.
-    if (!resident_round_ok(m, pars, true))
-        return fail(m, RAWDTW_ERR_UNSUPPORTED, "a round from signal needs a context, device chaining, one read group, no external scorer, no --dtw-output-cigar "
-                                               "and a w == 0 index, or a w > 0 one with the context's \"seed_minimizer\" option on "
-                                               "(rawdtw_detect_raw_begin + rawdtw_mapper_round_seeded_resident map the round)");
+    // With the context's "signal_cigar" on (read once a round) the traceback reads the arena instead, and flag 0x4 alone refuses nothing.
+    const bool cigar_from_arena = signal_cigar_option(m);
+    if (!resident_round_ok(m, pars, !cigar_from_arena))
+        return fail(m, RAWDTW_ERR_UNSUPPORTED, cigar_from_arena
+                        ? "a round from signal needs a context, device chaining, one read group, no external scorer and a w == 0 index, or a w > 0 one "
+                          "with the context's \"seed_minimizer\" option on (rawdtw_detect_raw_begin + rawdtw_mapper_round_seeded_resident map the round)"
+                        : "a round from signal needs a context, device chaining, one read group, no external scorer, no --dtw-output-cigar "
+                          "and a w == 0 index, or a w > 0 one with the context's \"seed_minimizer\" option on "
+                          "(rawdtw_detect_raw_begin + rawdtw_mapper_round_seeded_resident map the round)");
     if (n_reads == 0) return RAWDTW_OK;
     const double t0 = now_ms();
     const int chk = check_round(m, n_reads, read_ids, nullptr, nullptr, nullptr);
@@ -1530,6 +1556,7 @@ int round_from_signal(rawdtw_mapper *m, const rawdtw_seed_index *six, const rawd
     r.events_in_place = false;
     if (const int st = r.run([&r](uint32_t gi) { r.signal_begin(gi); })) return st;
     m->sig_rounds++;
+    if (m->opt.flag & 0x4) m->finish_from_arena = true; // (only with "signal_cigar" on does such a mapper get here)
     if (retried) m->sig_retried++;
     m->sig_sample_bytes += n_samples * (is_raw ? sizeof(int16_t) : sizeof(float)) * (retried ? 2 : 1);
     return RAWDTW_OK;
@@ -1559,6 +1586,33 @@ int rawdtw_mapper_signal_stats(const rawdtw_mapper *m, uint64_t *rounds, uint64_
     if (retried_rounds) *retried_rounds = m->sig_retried;
     if (sample_bytes_to_device) *sample_bytes_to_device = m->sig_sample_bytes;
     if (event_bytes_crossed) *event_bytes_crossed = (uint64_t)m->timing[6]; // (the mapper sends events up and fetches none: slot 6 is all that crosses)
+    return RAWDTW_OK;
+}
+
+// A read's committed events: where the mapper's rounds put them -- its slot of its group's arena (one segment of rawdtw_events_fetch) on a
+// mapper with a context, the host's copy on one without, for a read some of whose rounds ran nothing on the device, and once a finish
+// through the host's copies has replaced the arena (such a mapper kept every read's copy).
+int rawdtw_mapper_read_events(rawdtw_mapper *m, uint32_t read_id, float *out, uint32_t cap, uint32_t *n)
+{
+    if (!m || !n) return RAWDTW_ERR_INVALID;
+    *n = 0;
+    if (read_id >= m->reads.size()) return fail(m, RAWDTW_ERR_INVALID, "unknown read id");
+    const MRead &rd = m->reads[read_id];
+    if (rd.released) return fail(m, RAWDTW_ERR_INVALID, "a released read has no events");
+    *n = rd.n_events;
+    if (cap < rd.n_events) return fail(m, RAWDTW_ERR_RANGE, "cap is below the read's events");
+    if (rd.n_events == 0) return RAWDTW_OK;
+    if (!out) return fail(m, RAWDTW_ERR_INVALID, "null argument");
+    if (m->ctx && !rd.host_only && !m->arena_replaced) {
+        uint32_t start = 0;
+        rawdtw_ctx *ctx = slot_of(m, rd, &start);
+        const uint32_t len = rd.n_events;
+        uint64_t off[2];
+        const int st = rawdtw_events_fetch(ctx, 1, &start, &len, off, out, cap);
+        return st == RAWDTW_OK ? RAWDTW_OK : fail(m, st, rawdtw_last_error(ctx));
+    }
+    if (rd.events.size() != rd.n_events) return fail(m, RAWDTW_ERR_UNSUPPORTED, "the read's events are neither all in the arena nor all on the host");
+    memcpy(out, rd.events.data(), (size_t)rd.n_events * sizeof(float));
     return RAWDTW_OK;
 }
 
@@ -1603,7 +1657,15 @@ int rawdtw_mapper_finish(rawdtw_mapper *m)
     if (!m) return RAWDTW_ERR_INVALID;
     if (!(m->opt.flag & 0x4)) return RAWDTW_OK;
     if (!m->ctx) return fail(m, RAWDTW_ERR_NO_DEVICE, "--dtw-output-cigar needs a device context");
-    drop_batches(m); // (the traceback call replaces the event arena's contents: the mapper's rounds are over)
+    // Where a read's events are: in the host's copy, laid one read behind the other and uploaded by the traceback call -- or, once a round from
+    // signal has been committed ("signal_cigar": no host copy of its chunks exists), where every round of a context mapper put them: the read's slot
+    // of the arena, which the traceback then reads as it lies.  The event base of a read's jobs and the traceback entry are all that differs.
+    const bool arena = m->finish_from_arena;
+    if (arena)
+        for (const MRead &rd : m->reads)
+            if (rd.host_only && !rd.released && !rd.dropped && high_confidence(m, rd.chains))
+                return fail(m, RAWDTW_ERR_UNSUPPORTED, "a mapped read has events from a round that ran nothing on the device: they are not in the event arena");
+    if (!arena) drop_batches(m); // (the traceback call replaces the event arena's contents: the mapper's rounds are over)
     struct Item { uint32_t read; uint64_t job0; uint32_t nj; uint64_t ev0; };
     std::vector<Item> items;
     std::vector<rawdtw_job_t> jobs;
@@ -1614,15 +1676,17 @@ int rawdtw_mapper_finish(rawdtw_mapper *m)
         MChain &ch = rd.chains[0];
         const uint32_t na = (uint32_t)ch.anchors.size();
         const uint32_t nj = rawdtw_chain_job_count(&m->opt.align, na);
-        if ((uint64_t)events.size() + rd.events.size() >= (1ull << 32)) return fail(m, RAWDTW_ERR_RANGE, "the mapped reads' events exceed one event arena");
+        if (!arena && (uint64_t)events.size() + rd.events.size() >= (1ull << 32)) return fail(m, RAWDTW_ERR_RANGE, "the mapped reads' events exceed one event arena");
+        uint32_t ev_base = (uint32_t)events.size();
+        if (arena) (void)slot_of(m, rd, &ev_base); // (one read group: the arena is the mapper's context's)
         const uint64_t j0 = jobs.size();
         jobs.resize(j0 + std::max<uint32_t>(nj, 1));
         const uint64_t rb = m->ref_off[ch.ref * 2u + (uint32_t)ch.strand];
-        const int st = rawdtw_chain_build_jobs(&m->opt.align, ch.anchors.data(), na, rb, (uint32_t)events.size(), 1, jobs.data() + j0);
+        const int st = rawdtw_chain_build_jobs(&m->opt.align, ch.anchors.data(), na, rb, ev_base, 1, jobs.data() + j0);
         if (st != RAWDTW_OK) return fail(m, st, st == RAWDTW_ERR_UNSUPPORTED ? "banded global alignment with --dtw-output-cigar is not implemented (rmap.cpp:223-225)" : "job building failed");
         jobs.resize(j0 + nj);
-        items.push_back(Item{r, j0, nj, events.size()});
-        events.insert(events.end(), rd.events.begin(), rd.events.end());
+        items.push_back(Item{r, j0, nj, ev_base});
+        if (!arena) events.insert(events.end(), rd.events.begin(), rd.events.end());
     }
     if (items.empty()) return RAWDTW_OK;
     const uint64_t nj_all = jobs.size();
@@ -1632,7 +1696,9 @@ int rawdtw_mapper_finish(rawdtw_mapper *m)
     std::vector<uint8_t> step(poff[nj_all] + 1);
     std::vector<float> pd(poff[nj_all] + 1), cost(nj_all);
     if (nj_all) {
-        const int st = rawdtw_traceback_batch_steps(m->ctx, jobs.data(), nj_all, events.data(), events.size(), cost.data(), poff.data(), plen.data(), step.data(), pd.data());
+        if (!arena) m->arena_replaced = true;
+        const int st = arena ? rawdtw_traceback_arena_steps(m->ctx, jobs.data(), nj_all, cost.data(), poff.data(), plen.data(), step.data(), pd.data())
+                             : rawdtw_traceback_batch_steps(m->ctx, jobs.data(), nj_all, events.data(), events.size(), cost.data(), poff.data(), plen.data(), step.data(), pd.data());
         if (st != RAWDTW_OK) return fail(m, st, rawdtw_last_error(m->ctx));
     }
     std::vector<std::string> logs(items.size());

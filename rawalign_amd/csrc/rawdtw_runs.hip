@@ -1339,6 +1339,36 @@ __global__ __launch_bounds__(kT) void k_events_scatter(const float *__restrict__
     }
 }
 
+// ... and its inverse, the way back (rawdtw_events_fetch): segment q, arena[seg_start[q] .. seg_start[q] + its length), goes to
+// out[out_off[q] .. out_off[q + 1]) -- out_off is the lengths' prefix sum, so the segments arrive densely in order.  The grid is cut from
+// the OUTPUT: a workgroup takes kGatherPer * kT consecutive output floats, whatever segments they fall into, so one long segment and
+// many empty ones load the waves alike.  A lane finds its element's segment by bisection over out_off (the table is a few cache lines)
+// and carries it on as a lower bound: its elements ascend.  Consecutive lanes read consecutive floats of a segment and write consecutive
+// floats of out: both sides coalesced, 256 bytes a wave instruction.  A segment starts at ANY float offset of the arena and lands at
+// any float offset of out, so a 16-byte access would need source and destination offsets that agree mod 4 plus four elements of one
+// segment: a third path for what is at most 34 MB a round -- the accesses stay 4 bytes a lane.  The host has checked every segment
+// against the arena and the total against out's room (rawdtw_capi.cpp).
+constexpr uint32_t kGatherPer = 4;
+__global__ __launch_bounds__(kT) void k_events_gather(const float *__restrict__ arena, float *__restrict__ out,
+                                                      const uint32_t *__restrict__ seg_start, const uint64_t *__restrict__ out_off,
+                                                      uint32_t n_seg)
+{
+    const uint64_t total = out_off[n_seg];
+    const uint64_t base = (uint64_t)blockIdx.x * (kGatherPer * kT) + threadIdx.x;
+    uint32_t q = 0; // out_off[q] <= o holds for every element o of the lane from here on
+    for (uint32_t r = 0; r < kGatherPer; r++) {
+        const uint64_t o = base + (uint64_t)r * kT;
+        if (o >= total) return;
+        uint32_t lo = q + 1, hi = n_seg; // the first entry above o lies in [lo, hi]: out_off[n_seg] = total > o
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (out_off[mid] > o) hi = mid; else lo = mid + 1;
+        }
+        q = lo - 1; // (behind any empty segments that share its offset)
+        out[o] = arena[(uint64_t)seg_start[q] + (o - out_off[q])];
+    }
+}
+
 
 // ---------------------------------------------------------------------------------------------------------------------
 // k_fold_select: the fold of align_chain (rmap.cpp:238-306) and the accept/cut loop of gen_chains (rmap.cpp:515-524) for
@@ -1590,6 +1620,17 @@ hipError_t launch_events_scatter(const float *d_src, float *d_dst, const uint64_
     if (n_seg == 0) return hipSuccess;
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n_seg * 64 + kT - 1) / kT, 4096);
     hipLaunchKernelGGL(k_events_scatter, dim3(blocks), dim3(kT), 0, s, d_src, d_dst, d_seg_src, d_seg_dst, n_seg);
+    return hipGetLastError();
+}
+
+// (total = the host's out_off[n_seg]: it sizes the grid)
+hipError_t launch_events_gather(const float *d_arena, float *d_out, const uint32_t *d_seg_start, const uint64_t *d_out_off, uint32_t n_seg,
+                                uint64_t total, hipStream_t s)
+{
+    if (n_seg == 0 || total == 0) return hipSuccess;
+    const uint64_t blocks = (total + kGatherPer * kT - 1) / (kGatherPer * kT);
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_events_gather, dim3((uint32_t)blocks), dim3(kT), 0, s, d_arena, d_out, d_seg_start, d_out_off, n_seg);
     return hipGetLastError();
 }
 

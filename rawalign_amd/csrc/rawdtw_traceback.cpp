@@ -15,13 +15,20 @@ extern "C" {
 // k + 1 fills and walks.  (Cutting a batch that fits into quarters to hide the download behind the kernels was tried and
 // cost more than it hid: a fill or walk launch takes as long as its longest job -- fill 9.0 -> 18.8 ms, walk 1.9 -> 7.4 ms
 // for 8 080 paths in five launches each.)
-static int traceback_core(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events,
+// `arena`: the jobs' read_off index the context's event arena as it lies (rawdtw_traceback_arena_steps) -- nothing is uploaded and
+// h_events / n_events are not looked at; else the arena is replaced by h_events first.  That is the one difference.
+static int traceback_core(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, bool arena, const float *h_events,
                           uint64_t n_events, float *out_cost, const uint64_t *path_off, uint32_t *path_len,
                           uint32_t *path_i, uint32_t *path_j, uint8_t *path_step, float *path_d)
 {
     if (!ctx) return RAWDTW_ERR_INVALID;
     if (n_jobs && (!jobs || !out_cost || !path_off || !path_len || !path_d || (!path_step && (!path_i || !path_j))))
         return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    if (arena) { // (before anything is enqueued)
+        if (!ctx->d_ev) return fail(ctx, RAWDTW_ERR_INVALID, "the context has no event arena");
+        for (uint64_t k = 0; k < n_jobs; k++)
+            if ((uint64_t)jobs[k].read_off + jobs[k].n > ctx->n_ev) return fail(ctx, RAWDTW_ERR_INVALID, "a traceback job reads beyond the event arena");
+    }
     static const bool timing = getenv("RAWDTW_PLAN_TIMING") != nullptr;
     auto t_prev = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) {
@@ -30,7 +37,7 @@ static int traceback_core(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_
         fprintf(stderr, "[traceback] %-14s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(t - t_prev).count());
         t_prev = t;
     };
-    int st = rawdtw_upload_events(ctx, h_events, n_events);
+    int st = arena ? RAWDTW_OK : rawdtw_upload_events(ctx, h_events, n_events);
     if (st != RAWDTW_OK) return st;
     lap("events H2D");
     for (hipEvent_t &e : ctx->tb_ev) if (!e) HIP_TRY(ctx, hipEventCreate(&e));
@@ -232,7 +239,7 @@ int rawdtw_traceback_batch(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n
                            uint32_t *path_i, uint32_t *path_j, float *path_d)
 {
     if (n_jobs && (!path_i || !path_j)) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
-    return traceback_core(ctx, jobs, n_jobs, h_events, n_events, out_cost, path_off, path_len, path_i, path_j, nullptr, path_d);
+    return traceback_core(ctx, jobs, n_jobs, false, h_events, n_events, out_cost, path_off, path_len, path_i, path_j, nullptr, path_d);
 }
 
 int rawdtw_traceback_batch_steps(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events,
@@ -240,7 +247,14 @@ int rawdtw_traceback_batch_steps(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint
                                  uint8_t *path_step, float *path_d)
 {
     if (n_jobs && !path_step) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
-    return traceback_core(ctx, jobs, n_jobs, h_events, n_events, out_cost, path_off, path_len, nullptr, nullptr, path_step, path_d);
+    return traceback_core(ctx, jobs, n_jobs, false, h_events, n_events, out_cost, path_off, path_len, nullptr, nullptr, path_step, path_d);
+}
+
+int rawdtw_traceback_arena_steps(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, float *out_cost, const uint64_t *path_off,
+                                 uint32_t *path_len, uint8_t *path_step, float *path_d)
+{
+    if (n_jobs && !path_step) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    return traceback_core(ctx, jobs, n_jobs, true, nullptr, 0, out_cost, path_off, path_len, nullptr, nullptr, path_step, path_d);
 }
 
 // ---- single-call drop-ins ----------------------------------------------------------------------

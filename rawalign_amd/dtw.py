@@ -566,6 +566,40 @@ class Engine:
             res.append(DtwResult(cost[k], pi[s:e].copy(), pj[s:e].copy(), pd[s:e].copy()))
         return res
 
+    def traceback_arena_steps(self, jobs, path_off=None):
+        """rawdtw_traceback_arena_steps: full-matrix tracebacks whose read_off index the event arena as it lies -- nothing is uploaded,
+        nothing in the arena is written.  Returns (cost, path_off, path_len, step, distance): job k's path is the path_len[k] elements
+        from path_off[k] on, one step byte (bit 0: i advanced, bit 1: j advanced) and one distance an element.  path_off: the caller's
+        layout (n + m - 1 elements of room a job), default dense in job order."""
+        jobs = np.ascontiguousarray(jobs, dtype=JOB_DTYPE)
+        caps = jobs["n"].astype(np.uint64) + jobs["m"].astype(np.uint64) - 1
+        if path_off is None:
+            off = np.zeros(len(jobs) + 1, np.uint64)
+            np.cumsum(caps, out=off[1:])
+            total = int(off[-1])
+        else:
+            off = np.ascontiguousarray(path_off, np.uint64)
+            if len(off) < len(jobs):
+                raise ValueError("path_off is shorter than the job list")
+            total = int((off[:len(jobs)] + caps).max()) if len(jobs) else 0
+        cost = np.empty(len(jobs), np.float32)
+        plen = np.zeros(len(jobs), np.uint32)
+        step = np.zeros(max(total, 1), np.uint8)
+        pd = np.zeros(max(total, 1), np.float32)
+        self._check(self.lib.rawdtw_traceback_arena_steps(self._ctx, _ptr(jobs), len(jobs), _ptr(cost), _ptr(off), _ptr(plen), _ptr(step), _ptr(pd)))
+        return cost, off, plen, step, pd
+
+    def events_fetch(self, starts, lens):
+        """rawdtw_events_fetch: the arena's stretches [starts[q], starts[q] + lens[q]) as one array a segment, in order"""
+        start, ln = np.ascontiguousarray(starts, np.uint32), np.ascontiguousarray(lens, np.uint32)
+        if len(start) != len(ln):
+            raise ValueError("starts and lens differ in length")
+        off = np.zeros(len(ln) + 1, np.uint64)
+        cap = int(ln.astype(np.uint64).sum())
+        out = np.empty(max(cap, 1), np.float32)
+        self._check(self.lib.rawdtw_events_fetch(self._ctx, len(ln), _ptr(start), _ptr(ln), _ptr(off), _ptr(out), cap))
+        return [out[int(off[q]):int(off[q + 1])].copy() for q in range(len(ln))]
+
     # -- the reference's own function names (src/dtw.hpp:21,25,28) -----------------
     def DTW_global(self, a_values, b_values, exclude_last_element=False) -> np.float32:
         a, b = _f32(a_values), _f32(b_values)

@@ -658,6 +658,19 @@ class CMapper:
         self._check(self.lib.rawdtw_mapper_signal_stats(self._h, *[C.byref(x) for x in v]))
         return dict(rounds=v[0].value, retried_rounds=v[1].value, sample_bytes_to_device=v[2].value, event_bytes_crossed=v[3].value)
 
+    def read_events(self, rid: int) -> np.ndarray:
+        """rawdtw_mapper_read_events: the read's committed events -- out of its slot of the event arena on a mapper with an engine, the
+        host's copy otherwise"""
+        import ctypes as C
+
+        n = C.c_uint32()
+        st = self.lib.rawdtw_mapper_read_events(self._h, int(rid), None, 0, C.byref(n))
+        if st not in (0, 4):  # (RAWDTW_ERR_RANGE: the count, no room yet)
+            self._check(st)
+        out = np.empty(max(n.value, 1), np.float32)
+        self._check(self.lib.rawdtw_mapper_read_events(self._h, int(rid), _vp(out), n.value, C.byref(n)))
+        return out[:n.value].copy()
+
     def state(self, rid: int):
         import ctypes as C
 
