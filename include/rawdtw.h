@@ -423,7 +423,7 @@ int rawdtw_sort_by_chaining_score_restated(const float *chaining_score, uint32_t
  * rawdtw_sort_by_chaining_score read by read, bit for bit.  RAWDTW_ERR_UNSUPPORTED (the out arrays hold nothing of use): a read with more than
  * 2 048 seeds (with the option below: more than its value), with more than 32 chains, or with more than 16 chains two of which have
  * equal scores (std::sort's order of equal elements is an insertion sort's only up to 16) -- chain that round on the host, or see
- * "chain_max_chains" below, which lifts the last two.
+ * "chain_max_chains" below, which lifts the last two, and "chain_decline_reads" further down, under which such a read is declined alone.
  * RAWDTW_ERR_INVALID: a chain on a key that is not below n_keys.
  *   rawdtw_set_option(ctx, "chain_long_seeds", N)  0 (the default): as above.  N > 0 (at most 1 << 20): a read with more than 2 048 and at
  *        most N seeds no longer declines the round; it is chained by a second path that keeps its state in device memory (21 bytes a seed
@@ -461,6 +461,42 @@ int rawdtw_chain_round_end(rawdtw_ctx *ctx, const rawdtw_anchor_t **d_anchors, c
                            const uint32_t **d_read_base);
 int rawdtw_chain_round_stats(const rawdtw_ctx *ctx, uint64_t *rounds, uint64_t *long_reads, uint64_t *long_seeds, uint64_t *far_steps);
 int rawdtw_chain_order_stats(const rawdtw_ctx *ctx, uint64_t *reads_above_32, uint64_t *reads_ordered_restated, uint64_t *max_chains_a_read);
+
+/* ---- declining a read, not the round: rawdtw_set_option(ctx, "chain_decline_reads", 1).  0 (the default): everything above, launch for launch.
+ * 1 (anything but 0 and 1: RAWDTW_ERR_INVALID): a read the device cannot chain is declined alone -- the rest of the round is chained as before, and
+ * rawdtw_chain_round_begin* / _end never return RAWDTW_ERR_UNSUPPORTED (RAWDTW_ERR_RANGE and RAWDTW_ERR_INVALID stay as they are).  A declined read's
+ * stretch of chain_off is empty.  The reason is a set of bits: 1 more seeds than 2 048 / "chain_long_seeds" (or than RAWDTW_CHAIN_MAX_SEEDS, the
+ * tests' lowered cap), 2 more chains than 32 / "chain_max_chains", 4 more than 16 chains with two equal scores among the first 32 as generated
+ * (never with "chain_max_chains").  The caller chains those reads on the host and puts their chains behind the device's own:
+ *   rawdtw_chain_round_declined  after a successful _end: the declined reads, ascending, and their reasons -- the context's arrays, valid until
+ *        its next chaining begin.  *n_declined = 0 with the option off.  reads / why may be NULL.
+ *   rawdtw_chain_round_declined_seeds  the declined reads' seed lists from the device, as the round laid them down (what a resident round's
+ *        seeds are made of never was on the host: the kept store, the previous anchors and the hits; a round whose seeds the caller sent up has
+ *        them already).  seed_off_out[n_declined + 1] from 0, seeds_out[cap]: written by a kernel, a wave a read, straight into seeds_out when it
+ *        is page-locked.  RAWDTW_ERR_RANGE, with the offsets filled, when cap is below seed_off_out[n_declined].
+ *   rawdtw_chain_round_append  once a round, n_declined = the round's (anything else: RAWDTW_ERR_INVALID, as is a call after the context's next
+ *        begin): the declined reads' chains, read by read in the list's order and each read's in evaluation order -- chain_off[n_declined + 1]
+ *        and anchor_off[n_chains + 1] from 0, recs, anchors end-first.  They go up behind the round's chains in the five device arrays
+ *        (ref_base from the round's key_base, read_base from the read's).  A round never has more than seed_off[n_reads] / max(1,
+ *        min_num_anchors) chains, whoever made them (chains of a read share no anchor), and with the option on the context's workspace is
+ *        sized for that (40 bytes for each of them): RAWDTW_ERR_RANGE, with nothing written, for more chains or anchors than that.  Out,
+ *        the caller's: chain_off_ext[n_reads + n_declined + 1], the batch's read list -- the round's reads, the declined ones with their
+ *        empty stretches, then one pseudo-read for each declined read, in the list's order, which owns its chains --, and
+ *        anchor_off_ext[round's chains + n_chains + 1], the round's anchor_off continued (the chain_off and anchor_off _begin was given are
+ *        read here and must still be the round's; anchor_off_ext may be that anchor_off itself where it has the room).  The host's recs and
+ *        anchors of the appended chains are the caller's own.  rawdtw_batch_submit_device takes n_reads + n_declined reads, chain_off_ext,
+ *        anchor_off_ext and the three device pointers, which are those _end gave.
+ *   rawdtw_chain_decline_host  no device: which reads of a round the device declines, and why (why_out[n_reads], 0: chained; n_chains_out, may be
+ *        NULL: the read's chains, 0 for a read declined for its seeds), from the seed lists, the chaining options and the three caps -- seeds a
+ *        read (0: 2 048), "chain_long_seeds" and "chain_max_chains" as the context has them.  Made of rawdtw_chain_anchors, list by list in key
+ *        order; what the tests predict the device with, and a debugging aid. */
+int rawdtw_chain_round_declined(rawdtw_ctx *ctx, uint64_t *n_declined, const uint32_t **reads, const uint32_t **why);
+int rawdtw_chain_round_declined_seeds(rawdtw_ctx *ctx, uint64_t *seed_off_out, rawdtw_seed_t *seeds_out, uint64_t cap);
+int rawdtw_chain_round_append(rawdtw_ctx *ctx, uint64_t n_declined, const uint64_t *chain_off, const rawdtw_chain_rec_t *recs,
+                              const uint64_t *anchor_off, const rawdtw_anchor_t *anchors, uint64_t *chain_off_ext, uint64_t *anchor_off_ext,
+                              const rawdtw_anchor_t **d_anchors, const uint64_t **d_ref_base, const uint32_t **d_read_base);
+int rawdtw_chain_decline_host(const rawdtw_chain_opt_t *opt, uint64_t n_reads, const uint64_t *seed_off, const rawdtw_seed_t *seeds,
+                              uint32_t seed_cap, uint32_t long_seeds, uint32_t max_chains, uint32_t *why_out, uint32_t *n_chains_out);
 
 /* Batched forms over many reads (what rmap.cpp's per-read worker does for every read of a
  * mini-batch, hoisted around one GPU submission).  Chains are listed read by read, each read's
@@ -1117,11 +1153,25 @@ int rawdtw_mapper_round_end_stats(const rawdtw_mapper *m, uint64_t *rounds, uint
  *        RAWDTW_ERR_DEVICE.  0 (the default): no such call is made.  The option is read once a round.  The store's slots are the
  *        mapper's read slots: one mapper a context uses it at a time.
  *   rawdtw_mapper_kept_stats  over committed rounds that used the store: reads with at least one previous seed that took them from the
- *        device / from the host, those seeds, and reads whose chains a keep launch did not keep.  Any pointer may be NULL. ---- */
+ *        device / from the host, those seeds, and reads whose chains a keep launch did not keep.  Any pointer may be NULL.
+ *   rawdtw_set_option(ctx, "chain_decline_reads", 1)  on the context a mapper was created with (its second group's context takes it over): a
+ *        device-chained round -- plain, resident or from signal -- no longer goes to the host whole because the chaining cannot take one
+ *        read.  The reads rawdtw_chain_round_declined names are chained by the host's own code on the mapper's threads (a resident round
+ *        fetches their seeds alone, rawdtw_chain_round_declined_seeds, not the round's hits), appended (rawdtw_chain_round_append), and the
+ *        DTW, the round end and the keep run on one batch.  Lines, logs and rounds are those of the mapper that chains on the host.  Such a
+ *        round is no fall-back: rawdtw_mapper_resident_stats' fallback_rounds and hit_bytes_to_host do not move.  A declined read is not
+ *        kept in the store of "resident_chains" (reads_not_kept counts it) and is seeded from the host in the round after; every other
+ *        read keeps its half.  The option is read once a round and group.
+ *   rawdtw_mapper_decline_stats  over committed rounds in which the chaining declined at least one read alone: those rounds; the reads declined
+ *        for their seeds (reason bit 1) and for their chains (bits 2, 4); the other reads that took part in those rounds, counted for each read
+ *        group that declined one of its own (the device chained them where a fall-back would have chained them on the host); and the bytes of declined reads' seeds brought home in resident
+ *        rounds.  Any pointer may be NULL. ---- */
 #define RAWDTW_NOT_KEPT 0xffffffffu
 #define RAWDTW_NO_KEEP 0xffffffffu
 #define RAWDTW_PREV_HOST 0xffffffffu
 int rawdtw_chain_keep_reserve(rawdtw_ctx *ctx, uint64_t n_slots, uint64_t seeds_per_half);
+int rawdtw_mapper_decline_stats(const rawdtw_mapper *m, uint64_t *rounds_with_declines, uint64_t *reads_declined_seeds,
+                                uint64_t *reads_declined_chains, uint64_t *reads_chained_device, uint64_t *seed_bytes_to_host);
 int rawdtw_mapper_kept_stats(const rawdtw_mapper *m, uint64_t *reads_from_device, uint64_t *reads_from_host, uint64_t *seeds_from_device,
                              uint64_t *seeds_from_host, uint64_t *reads_not_kept);
 int rawdtw_round_keep_host(uint64_t n_reads, const uint64_t *chain_off, const rawdtw_chain_rec_t *recs, const uint64_t *anchor_off,

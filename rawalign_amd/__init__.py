@@ -8,7 +8,7 @@ There is no CPU fallback: importing works anywhere, but every compute call needs
 ``librawdtw.so`` and a HIP device and raises otherwise.
 """
 from ._lib import LibraryMissing, RawDTWError, load_library, library_path  # noqa: F401
-from .dtw import ANCHOR_DTYPE, CHAIN_REC_DTYPE, JOB_DTYPE, RAWDTW_FULL, ROUND_OUT_DTYPE, SEED_DTYPE, DtwResult, Engine, Plan, round_end_host, round_keep_host  # noqa: F401
+from .dtw import ANCHOR_DTYPE, CHAIN_REC_DTYPE, JOB_DTYPE, RAWDTW_FULL, ROUND_OUT_DTYPE, SEED_DTYPE, DtwResult, Engine, Plan, chain_decline_host, round_end_host, round_keep_host  # noqa: F401
 from .align import (  # noqa: F401
     RI_M_DTW_BORDER_CONSTRAINT_GLOBAL,
     RI_M_DTW_BORDER_CONSTRAINT_SPARSE,
@@ -34,7 +34,7 @@ __all__ = [
     "EventOptions", "detect_events", "detect_events_host", "chunks_of",
     "Channel", "CHANNEL_DTYPE", "to_pa", "chunk_table", "detect_events_raw_host",
     "SeedIndex", "SeedParams", "HIT_DTYPE", "sketch", "seed_hits_host",
-    "CHAIN_REC_DTYPE", "ROUND_OUT_DTYPE", "round_end_host", "SEED_DTYPE", "round_keep_host",
+    "CHAIN_REC_DTYPE", "ROUND_OUT_DTYPE", "round_end_host", "SEED_DTYPE", "round_keep_host", "chain_decline_host",
 ]
 
 DEFAULT_FOLD_MODE = 4  # rawdtw_set_option("fold_mode"): the library's default chain-fold kernel

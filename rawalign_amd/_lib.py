@@ -304,6 +304,11 @@ SYMBOLS = {
     "rawdtw_chain_kept_fetch": (I32, [VP, U32, VP, U32, VP]),
     "rawdtw_chain_round_begin_resident_kept": (I32, [VP, VP, U64, VP, VP, VP, VP, VP, VP, VP, U32, VP, VP, VP, VP, U64, VP]),
     "rawdtw_mapper_kept_stats": (I32, [VP, VP, VP, VP, VP, VP]),
+    "rawdtw_mapper_decline_stats": (I32, [VP, VP, VP, VP, VP, VP]),
+    "rawdtw_chain_round_declined": (I32, [VP, C.POINTER(U64), C.POINTER(VP), C.POINTER(VP)]),
+    "rawdtw_chain_round_declined_seeds": (I32, [VP, VP, VP, U64]),
+    "rawdtw_chain_round_append": (I32, [VP, U64, VP, VP, VP, VP, VP, VP, C.POINTER(VP), C.POINTER(VP), C.POINTER(VP)]),
+    "rawdtw_chain_decline_host": (I32, [C.POINTER(ChainOpt), U64, VP, VP, U32, U32, U32, VP, VP]),
 }
 
 

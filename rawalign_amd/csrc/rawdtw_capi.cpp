@@ -186,6 +186,11 @@ int rawdtw_set_option(rawdtw_ctx *ctx, const char *name, int64_t value)
         ctx->chain_max_chains = (uint32_t)value;
         return RAWDTW_OK;
     }
+    if (!strcmp(name, "chain_decline_reads")) { // (an opt-in that changes what a chaining round returns: a value that is neither is refused)
+        if (value != 0 && value != 1) return fail(ctx, RAWDTW_ERR_INVALID, "\"chain_decline_reads\" is 0 (off) or 1");
+        ctx->chain_decline_reads = value == 1;
+        return RAWDTW_OK;
+    }
     if (!strcmp(name, "seed_minimizer")) { ctx->seed_minimizer = value != 0; return RAWDTW_OK; }
     if (!strcmp(name, "device_round_end")) { ctx->device_round_end = value != 0; return RAWDTW_OK; }
     if (!strcmp(name, "resident_chains")) { ctx->resident_chains = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 1 << 20); return RAWDTW_OK; }
@@ -208,6 +213,7 @@ int rawdtw_get_option(const rawdtw_ctx *ctx, const char *name, int64_t *value)
     if (!ctx || !name || !value) return RAWDTW_ERR_INVALID;
     if (!strcmp(name, "chain_long_seeds")) { *value = ctx->chain_long_seeds; return RAWDTW_OK; }
     if (!strcmp(name, "chain_max_chains")) { *value = ctx->chain_max_chains; return RAWDTW_OK; }
+    if (!strcmp(name, "chain_decline_reads")) { *value = ctx->chain_decline_reads ? 1 : 0; return RAWDTW_OK; }
     if (!strcmp(name, "seed_minimizer")) { *value = ctx->seed_minimizer ? 1 : 0; return RAWDTW_OK; }
     if (!strcmp(name, "device_round_end")) { *value = ctx->device_round_end ? 1 : 0; return RAWDTW_OK; }
     if (!strcmp(name, "round_end_kernel_us")) { *value = round_end_kernel_us(ctx); return RAWDTW_OK; }

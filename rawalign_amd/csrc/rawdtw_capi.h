@@ -157,6 +157,7 @@ struct rawdtw_ctx {
     bool device_round_end = false; // "device_round_end": a mapper created with this context ends its device-chained rounds on the device
     uint32_t chain_max_seeds = 0; // tests: RAWDTW_CHAIN_MAX_SEEDS lowers rawdtw_chain_round's cap on seeds a read, so that small rounds take the declined path (0: no)
     uint32_t chain_long_seeds = 0; // "chain_long_seeds": reads above the cap with at most this many seeds are chained by rawdtw_chain.hip's long path (0: declined)
+    bool chain_decline_reads = false; // "chain_decline_reads": a read the device chaining cannot take is declined alone (rawdtw_chain_round_declined), not its round
     uint32_t chain_max_chains = 0; // "chain_max_chains": a read with up to this many chains, ties or not, is ordered on the device by rawdtw_sort_order.h (0: 32 chains, 16 with ties)
     bool seed_minimizer = false;   // "seed_minimizer": rawdtw_seed.hip seeds a w > 0 table on the device (k_seed_min) rather than refusing it
     bool signal_cigar = false;     // "signal_cigar": a mapper created with this context takes --dtw-output-cigar through its rounds from signal; its finish reads the arena

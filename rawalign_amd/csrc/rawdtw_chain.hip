@@ -22,7 +22,8 @@
 //
 // What the device declines (the caller chains that round on the host, same results): a read with more seeds than the wave's piece of LDS
 // holds (2 048), more than 32 chains, or more than 16 chains with two equal scores among them (std::sort's order of equal elements is its
-// own beyond 16; up to 16 it is an insertion sort and stable).
+// own beyond 16; up to 16 it is an insertion sort and stable).  With "chain_decline_reads" on it declines such a read alone and chains the
+// rest of the round (DECLINING A READ, at k_chain_scan).
 //
 // THE LONG PATH ("chain_long_seeds", off by default).  A read above the wave's piece of LDS is chained with its state in device memory: a
 // workgroup sorts its seeds into scratch (k_chain_sort_long), then a wave runs the same DP over them (k_chain_long) with the trailing window of
@@ -43,6 +44,7 @@
 // that marks in device memory need.  The anchor loop, the band's lower end, the running maximum and the end filter (rmap.cpp:486-493) stay in the
 // kernels.  The round's workspace is described once too (ChainLayout): laid from 0 it gives the size, from the block's base the pointers.
 #include "rawdtw_capi.h"
+#include "rawdtw_chain_append.h"
 #include "rawdtw_sort_order.h"
 
 #include <algorithm>
@@ -510,25 +512,53 @@ template <bool kMany> __global__ __launch_bounds__(64) void k_chain_long(const C
     if (lane == 0 && far) atomicAdd(la.far_steps, (unsigned long long)far);
 }
 
+// DECLINING A READ ("chain_decline_reads", off by default).  A read the device cannot chain -- more seeds than the caps (marked by the host at
+// begin: reason 1), or what k_chain / k_chain_long flag in its count (1 too many seeds, 2 too many chains, 4 an order only std::sort knows) -- no
+// longer declines its round.  The declining instantiations of the scan and the compaction give it an empty stretch of chain_off, its reason in
+// why[r] and an entry of the compact list of declined reads, ascending; the round's flags stay 0.  The host chains those reads and puts their
+// chains behind the device's (rawdtw_chain_round_append).  The <false> instantiations are the kernels as they were.
+struct DeclRec { uint32_t r, why; uint64_t seed0; }; // a declined read, its reason, and the declined reads' seeds before it
+struct DeclArgs {
+    const uint8_t *mark; // per read: declined at begin
+    uint32_t *why;       // per read: 0, or the reason's bits
+    DeclRec *list;       // the declined reads, ascending
+    const uint64_t *seed_off;
+};
+
 // the reads' chains and anchors before each read; the round's totals and its flags; totals[5 .. 7]: the reads with more than kChainCap chains,
 // with more than kChainStable, and the most chains a read has (rawdtw_chain_order_stats).  cap: chains a read the round records.
-__global__ __launch_bounds__(1024) void k_chain_scan(const ChainCnt *__restrict__ cnt, const uint32_t n_reads, const uint32_t cap, uint64_t *__restrict__ chain_off,
-                                                     uint64_t *__restrict__ read_anchor0, uint64_t *__restrict__ totals /* chains, anchors, flags */)
+// kDecline: totals has 16 words -- [8] the declined reads, [9 .. 11] those with reason bit 1, 2, 4, [12] their seeds; [2] stays 0, and
+// [5 .. 7] count the reads that were not declined.
+template <bool kDecline> __global__ __launch_bounds__(1024) void k_chain_scan(const ChainCnt *__restrict__ cnt, const uint32_t n_reads, const uint32_t cap, uint64_t *__restrict__ chain_off,
+                                                     uint64_t *__restrict__ read_anchor0, uint64_t *__restrict__ totals /* chains, anchors, flags */, const DeclArgs dd)
 {
     __shared__ uint64_t s_c[1024], s_a[1024];
     __shared__ uint32_t s_f[1024];
     __shared__ uint32_t s_st[3];
+    __shared__ uint32_t s_d[kDecline ? 1024 : 1], s_why[kDecline ? 3 : 1];
+    __shared__ uint64_t s_ds[kDecline ? 1024 : 1];
     const uint32_t t = threadIdx.x, per = (n_reads + 1023u) / 1024u, lo = min(n_reads, t * per), hi = min(n_reads, lo + per);
-    uint64_t c = 0, x = 0;
-    uint32_t f = 0, above_cap = 0, above_stable = 0, most = 0;
+    uint64_t c = 0, x = 0, ds = 0;
+    uint32_t f = 0, above_cap = 0, above_stable = 0, most = 0, nd = 0;
     if (t < 3) s_st[t] = 0;
+    if (kDecline && t < 3) s_why[t] = 0;
     __syncthreads();
     for (uint32_t r = lo; r < hi; r++) {
         const uint32_t nc = cnt[r].nc;
+        if (kDecline) {
+            const uint32_t why = dd.mark[r] ? 1u : (cnt[r].flags & 7u);
+            dd.why[r] = why;
+            if (why) {
+                nd++; ds += dd.seed_off[r + 1] - dd.seed_off[r];
+                for (uint32_t b = 0; b < 3; b++) if (why >> b & 1u) atomicAdd(&s_why[b], 1u);
+                continue;
+            }
+        }
         c += min(nc, cap); x += cnt[r].na; f |= cnt[r].flags;
         above_cap += nc > kChainCap; above_stable += nc > kChainStable; most = max(most, nc);
     }
     s_c[t] = c; s_a[t] = x; s_f[t] = f;
+    if (kDecline) { s_d[t] = nd; s_ds[t] = ds; }
     if (above_cap) atomicAdd(&s_st[0], above_cap);
     if (above_stable) atomicAdd(&s_st[1], above_stable);
     if (most) atomicMax(&s_st[2], most);
@@ -536,30 +566,41 @@ __global__ __launch_bounds__(1024) void k_chain_scan(const ChainCnt *__restrict_
     for (uint32_t d = 1; d < 1024; d <<= 1) {
         const uint64_t pc = t >= d ? s_c[t - d] : 0, pa = t >= d ? s_a[t - d] : 0;
         const uint32_t pf = t >= d ? s_f[t - d] : 0;
+        const uint32_t pd = kDecline && t >= d ? s_d[t - d] : 0;
+        const uint64_t ps = kDecline && t >= d ? s_ds[t - d] : 0;
         __syncthreads();
         s_c[t] += pc; s_a[t] += pa; s_f[t] |= pf;
+        if (kDecline) { s_d[t] += pd; s_ds[t] += ps; }
         __syncthreads();
     }
     uint64_t bc = s_c[t] - c, ba = s_a[t] - x;
-    for (uint32_t r = lo; r < hi; r++) { chain_off[r] = bc; read_anchor0[r] = ba; bc += min(cnt[r].nc, cap); ba += cnt[r].na; }
+    uint32_t bd = kDecline ? s_d[t] - nd : 0;  // (the declined reads before this thread's: its reads ascend, so does the list)
+    uint64_t bs = kDecline ? s_ds[t] - ds : 0;
+    for (uint32_t r = lo; r < hi; r++) {
+        chain_off[r] = bc; read_anchor0[r] = ba;
+        if (kDecline && dd.why[r]) { dd.list[bd++] = DeclRec{r, dd.why[r], bs}; bs += dd.seed_off[r + 1] - dd.seed_off[r]; continue; }
+        bc += min(cnt[r].nc, cap); ba += cnt[r].na;
+    }
     if (t == 1023) {
         chain_off[n_reads] = s_c[t]; totals[0] = s_c[t]; totals[1] = s_a[t]; totals[2] = s_f[t]; totals[3] = 0;
         totals[5] = s_st[0]; totals[6] = s_st[1]; totals[7] = s_st[2];
+        if (kDecline) { totals[8] = s_d[t]; totals[9] = s_why[0]; totals[10] = s_why[1]; totals[11] = s_why[2]; totals[12] = s_ds[t]; }
     }
 }
 
-// a wave a read: its chains, in evaluation order, into the batch's arrays
-__global__ __launch_bounds__(64) void k_chain_compact(const ChainArgs a, const uint64_t *__restrict__ chain_off, const uint64_t *__restrict__ read_anchor0,
+// a wave a read: its chains, in evaluation order, into the batch's arrays.  kDecline: nothing for a declined read (why[r] != 0).
+template <bool kDecline> __global__ __launch_bounds__(64) void k_chain_compact(const ChainArgs a, const uint64_t *__restrict__ chain_off, const uint64_t *__restrict__ read_anchor0,
                                                       const uint32_t *__restrict__ read_base, const uint64_t *__restrict__ key_base, const uint32_t n_keys,
                                                       uint64_t *__restrict__ anchor_off, rawdtw_anchor_t *__restrict__ anchors, uint64_t *__restrict__ ref_base,
                                                       uint32_t *__restrict__ read_base_c, rawdtw_chain_rec_t *__restrict__ recs, uint64_t *__restrict__ totals,
                                                       // the caller's page-locked host arrays, written from here (null: they are copied afterwards)
                                                       uint64_t *__restrict__ h_anchor_off, rawdtw_chain_rec_t *__restrict__ h_recs, rawdtw_anchor_t *__restrict__ h_anchors,
-                                                      const uint64_t h_chains_cap)
+                                                      const uint64_t h_chains_cap, const uint32_t *__restrict__ why)
 {
     const uint32_t r = blockIdx.x, lane = threadIdx.x;
     const uint64_t c0 = chain_off[r], s0 = a.seed_off[r], t0 = rec_start(a, r);
     uint32_t nc = min(a.cnt[r].nc, a.cap);
+    if (kDecline && why[r]) nc = 0;
     if (a.rec_div) nc = (uint32_t)min((uint64_t)nc, (a.seed_off[r + 1] - s0) / a.rec_div); // (many chains a read: the stretch the kernels recorded into; a read has no more chains than that)
     const bool host = h_anchor_off && totals[2] == 0 && totals[0] <= h_chains_cap; // (a declined round leaves the host arrays alone)
     uint64_t dst = read_anchor0[r];
@@ -584,6 +625,19 @@ __global__ __launch_bounds__(64) void k_chain_compact(const ChainArgs a, const u
     if (r == 0 && lane == 0) { anchor_off[totals[0]] = totals[1]; if (host) h_anchor_off[totals[0]] = totals[1]; }
 }
 
+// "chain_decline_reads": a wave a declined read -- its stretch of the round's seed list as it was laid down (in a resident round by the seeding's
+// writer launch, from the kept store, the host's previous anchors and the hits), 12 bytes a seed, to out[list[j].seed0 ..).  The host launches
+// one block for each entry of the list and has checked that `out` holds the list's seeds (totals[12]).
+__global__ __launch_bounds__(64) void k_declined_seeds(const DeclRec *__restrict__ list, const uint64_t *__restrict__ seed_off, const rawdtw_seed_t *__restrict__ seeds,
+                                                       rawdtw_seed_t *__restrict__ out)
+{
+    const DeclRec d = list[blockIdx.x];
+    const uint64_t s0 = seed_off[d.r], words = (seed_off[d.r + 1] - s0) * 3;
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(seeds + s0);
+    uint32_t *dst = reinterpret_cast<uint32_t *>(out + d.seed0);
+    for (uint64_t i = threadIdx.x; i < words; i += 64) dst[i] = src[i];
+}
+
 using capi::carve;
 // A round's workspace, described once: lay(0) gives the bytes it needs, lay(the block's base) the round's pointers.  Every array starts on a
 // multiple of 256 bytes; the arrays of a resident round and of the long path take no space in a round that has none.
@@ -596,7 +650,15 @@ struct ChainLayout {
     // so a read of n seeds records at most n / rec_div chains and the round n_seeds / rec_div.  A read's records then start at seed_off[r] / rec_div
     // (by_seeds) -- floor(x / d) + floor(n / d) <= floor((x + n) / d): the stretches do not overlap -- or, where n_reads * max_chains is the
     // smaller bound, at r * max_chains.  68 bytes a chain: trec 24, tperm 4, aoff 8, refb 8, rbc 4, recs 20.
+    // "chain_decline_reads": the host's chains of the declined reads are appended behind the device's, in the batch's arrays.  Chains of a read
+    // share no anchor and a recorded chain has at least max(1, min_num_anchors) anchors, whoever made it: a read of n seeds has at most
+    // n / rec_div chains and the ROUND AT MOST n_seeds / rec_div, device-made and appended together -- chains_by_seeds().  The batch's chain-sized
+    // arrays (aoff, refb, rbc, recs) then hold max(chain_entries(), chains_by_seeds()) entries, and the anchors' n_seeds + 2 hold every chain's
+    // anchors as they always did; rawdtw_chain_round_append checks both before it writes.  The per-read arrays of the option (mark, why, dlist) and
+    // the second half of the totals take no space with the option off.
     uint64_t max_chains = 0, rec_div = 1;
+    bool decline = false;
+    uint8_t *mark; uint32_t *why; DeclRec *dlist;
     uint64_t *soff; rawdtw_seed_t *seeds; uint32_t *rb; uint64_t *kb;                          // inputs
     rawdtw_anchor_t *tmpa; ChainRecDev *trec; ChainCnt *cnt; uint64_t *coff, *ra0;             // per-read scratch
     uint64_t *tot;                                                                             // chains, anchors, flags, bad keys; [4]: the long path's far steps; [5 .. 7]: k_chain_scan's counts
@@ -610,22 +672,25 @@ struct ChainLayout {
     uint64_t chains_by_seeds() const { return n_seeds / rec_div + 1; }
     bool by_seeds() const { return max_chains && chains_by_seeds() <= n_reads * max_chains; }
     uint64_t chain_entries() const { return by_seeds() ? chains_by_seeds() : n_reads * cap(); } // what the chain-sized arrays hold
+    uint64_t batch_entries() const { return decline ? std::max(chain_entries(), chains_by_seeds()) : chain_entries(); } // ... and the batch's, which take the append
+    uint64_t tot_words() const { return decline ? 16 : 8; }
 
     size_t lay(void *base)
     {
         uintptr_t p = reinterpret_cast<uintptr_t>(base);
-        const uint64_t nc = chain_entries(), nres = resident ? n_reads : 0;
+        const uint64_t nc = chain_entries(), nb = batch_entries(), nres = resident ? n_reads : 0, ndec = decline ? n_reads : 0;
         soff = carve<uint64_t>(p, n_reads + 1); seeds = carve<rawdtw_seed_t>(p, n_seeds + 2); rb = carve<uint32_t>(p, n_reads); kb = carve<uint64_t>(p, n_keys + 1);
         tmpa = carve<rawdtw_anchor_t>(p, n_seeds + 2); trec = carve<ChainRecDev>(p, nc); cnt = carve<ChainCnt>(p, n_reads);
-        coff = carve<uint64_t>(p, n_reads + 1); ra0 = carve<uint64_t>(p, n_reads); tot = carve<uint64_t>(p, 8);
-        aoff = carve<uint64_t>(p, nc + 1); anch = carve<rawdtw_anchor_t>(p, n_seeds + 2); refb = carve<uint64_t>(p, nc + 1); rbc = carve<uint32_t>(p, nc + 2);
-        recs = carve<rawdtw_chain_rec_t>(p, nc + 1);
+        coff = carve<uint64_t>(p, n_reads + 1); ra0 = carve<uint64_t>(p, n_reads); tot = carve<uint64_t>(p, tot_words());
+        aoff = carve<uint64_t>(p, nb + 1); anch = carve<rawdtw_anchor_t>(p, n_seeds + 2); refb = carve<uint64_t>(p, nb + 1); rbc = carve<uint32_t>(p, nb + 2);
+        recs = carve<rawdtw_chain_rec_t>(p, nb + 1);
         prev = carve<rawdtw_seed_t>(p, resident ? n_prev + 2 : 0); poff = carve<uint64_t>(p, resident ? n_reads + 1 : 0); cs = carve<uint32_t>(p, nres);
         so = carve<uint8_t>(p, nres); psrc = carve<uint32_t>(p, nres);
         la.reads = carve<LongRead>(p, n_long); la.K1 = carve<unsigned long long>(p, long_elems); la.Q = carve<uint32_t>(p, long_elems);
         la.SC = carve<float>(p, long_elems); la.PR = carve<uint32_t>(p, long_elems); la.FL = carve<unsigned char>(p, long_elems);
         la.far_steps = reinterpret_cast<unsigned long long *>(tot) + 4;
         tperm = carve<uint32_t>(p, max_chains ? nc : 0);
+        mark = carve<uint8_t>(p, ndec); why = carve<uint32_t>(p, ndec); dlist = carve<DeclRec>(p, ndec);
         return (size_t)(p - reinterpret_cast<uintptr_t>(base));
     }
 };
@@ -652,7 +717,25 @@ struct ChainWs {
     // rawdtw_chain_order_stats' counters, over the rounds that were not declined
     bool many = false; // (the round begun ran with "chain_max_chains" on)
     uint64_t st_above_32 = 0, st_restated = 0, st_max_chains = 0;
+    // "chain_decline_reads": the round begun ran with it; what the append and the declined reads' seeds need of the round after its end
+    bool decline = false, ended = false, appendable = false; // (ended: a declining round's _end succeeded and no round was begun since)
+    size_t pin_bytes = 0;
+    uint64_t n_seeds = 0, batch_room = 0, nc = 0, na = 0, decl_seeds = 0;
+    uint64_t *h_chain_off = nullptr;
+    std::vector<uint8_t> marks;
+    std::vector<uint32_t> h_read_base, decl_reads, decl_why, app_rbc;
+    std::vector<uint64_t> h_key_base, decl_seed0, app_refb;
+    std::vector<DeclRec> decl;
+    const uint64_t *d_soff = nullptr; const rawdtw_seed_t *d_seeds = nullptr; const DeclRec *d_list = nullptr;
+    void *pin_seeds = nullptr; size_t pin_seeds_bytes = 0; // the declined reads' seeds on their way to an array that is not page-locked
 };
+
+bool page_locked(const void *q)
+{
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, q) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return at.type == hipMemoryTypeHost;
+}
 
 } // namespace
 } // namespace rawdtw
@@ -684,6 +767,10 @@ int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads
         return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
     if (res && (!res->prev_off || !res->chunk_start || !res->sits_out)) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
     if (ctx->chain_ws && ctx->chain_ws->w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "a chaining round is begun on this context and not ended");
+    if (ctx->chain_ws) { // (any begin, refused or not, ends what the round before left for rawdtw_chain_round_declined / _append)
+        ChainWs &w0 = ctx->chain_ws->w;
+        w0.ended = false; w0.appendable = false; w0.decl_reads.clear(); w0.decl_why.clear(); w0.decl_seed0.clear(); w0.decl_seeds = 0;
+    }
     if (n_reads == 0 || n_reads > 0xffffffffull) return fail(ctx, RAWDTW_ERR_INVALID, "no reads, or more than 2^32");
     uint64_t n_prev = 0;
     if (res) { // every read's stretch is its previous anchors plus its chunk's hits, or empty: the device writes exactly that and nothing else
@@ -720,20 +807,21 @@ int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads
     const uint32_t rec_div = (uint32_t)std::max(1, opt->min_num_anchors);
     uint32_t most = 0; // (of the reads k_chain takes)
     uint64_t n_long = 0, long_elems = 0, most_long = 0;
+    const bool decline = ctx->chain_decline_reads; // ("chain_decline_reads": a read above the caps is declined alone, and left out of `most` and the long list)
     bool too_long = false;
     for (uint64_t r = 0; r < n_reads; r++) {
         if (seed_off[r + 1] < seed_off[r]) return fail(ctx, RAWDTW_ERR_INVALID, "offsets do not ascend");
         const uint64_t nr = seed_off[r + 1] - seed_off[r];
         if (nr <= seed_cap) most = std::max(most, (uint32_t)nr);
         else if (nr <= long_cap) { n_long++; long_elems += (nr + 63) & ~63ull; most_long = std::max(most_long, nr); }
-        else too_long = true;
+        else if (!decline) too_long = true;
     }
     if (too_long) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, long_cap ? "a read has more seeds than \"chain_long_seeds\" allows: chain this round on the host"
                                                                    : "a read has more seeds than the device chains (2048): chain this round on the host");
     uint32_t n2 = 64;
     while (n2 < most) n2 <<= 1;
     // one block of device memory, grow-only: laid out from 0 for its size, from the block's base for the round's pointers
-    ChainLayout L{n_reads, n_seeds, n_keys, res != nullptr, n_prev, n_long, long_elems, max_chains, rec_div};
+    ChainLayout L{n_reads, n_seeds, n_keys, res != nullptr, n_prev, n_long, long_elems, max_chains, rec_div, decline};
     const size_t need = L.lay(nullptr);
     if (!ctx->chain_ws) ctx->chain_ws = new (std::nothrow) rawdtw_chain_ws;
     if (!ctx->chain_ws) return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed");
@@ -743,7 +831,18 @@ int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads
         uint64_t k = 0, at = 0;
         for (uint64_t r = 0; r < n_reads; r++) {
             const uint64_t nr = seed_off[r + 1] - seed_off[r];
-            if (nr > seed_cap) { w.long_reads[k++] = LongRead{(uint32_t)r, 0u, at}; at += (nr + 63) & ~63ull; }
+            if (nr > seed_cap && nr <= long_cap) { w.long_reads[k++] = LongRead{(uint32_t)r, 0u, at}; at += (nr + 63) & ~63ull; }
+        }
+    }
+    if (decline) { // the marks, and the host's copies of what the append needs after the caller's arrays may be gone
+        try {
+            w.marks.assign(n_reads, 0);
+            w.h_read_base.assign(read_base, read_base + n_reads);
+            w.h_key_base.assign(key_base, key_base + n_keys);
+        } catch (const std::bad_alloc &) { return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed"); }
+        for (uint64_t r = 0; r < n_reads; r++) {
+            const uint64_t nr = seed_off[r + 1] - seed_off[r];
+            w.marks[r] = nr > seed_cap && nr > long_cap;
         }
     }
     if (w.dev_bytes < need) {
@@ -753,7 +852,10 @@ int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads
         if (hipMalloc(&w.dev, want) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, RAWDTW_ERR_OOM, "chaining workspace allocation failed"); }
         w.dev_bytes = want;
     }
-    if (!w.pin && hipHostMalloc(&w.pin, 64, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); w.pin = nullptr; return fail(ctx, RAWDTW_ERR_OOM, "pinned allocation failed"); }
+    const size_t tot_bytes = (size_t)L.tot_words() * 8; // (64, as it was, until a round declines reads: 128)
+    if (w.pin && w.pin_bytes < tot_bytes) { (void)hipHostFree(w.pin); w.pin = nullptr; }
+    if (!w.pin && hipHostMalloc(&w.pin, tot_bytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); w.pin = nullptr; return fail(ctx, RAWDTW_ERR_OOM, "pinned allocation failed"); }
+    w.pin_bytes = std::max(w.pin_bytes, tot_bytes);
     (void)L.lay(w.dev);
     hipStream_t s = ctx->stream;
     HIP_TRY(ctx, hipMemcpyAsync(L.soff, seed_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, s));
@@ -786,20 +888,23 @@ int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads
         if (max_chains) hipLaunchKernelGGL(k_chain_long<true>, dim3((uint32_t)n_long), dim3(64), (size_t)L.la.lds_chains * 8, s, a, L.la);
         else hipLaunchKernelGGL(k_chain_long<false>, dim3((uint32_t)n_long), dim3(64), 0, s, a, L.la);
     }
-    hipLaunchKernelGGL(k_chain_scan, dim3(1), dim3(1024), 0, s, L.cnt, (uint32_t)n_reads, a.cap, L.coff, L.ra0, L.tot);
+    const DeclArgs da{L.mark, L.why, L.dlist, L.soff};
+    if (decline) {
+        HIP_TRY(ctx, hipMemcpyAsync(L.mark, w.marks.data(), n_reads, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_chain_scan<true>, dim3(1), dim3(1024), 0, s, L.cnt, (uint32_t)n_reads, a.cap, L.coff, L.ra0, L.tot, da);
+    } else hipLaunchKernelGGL(k_chain_scan<false>, dim3(1), dim3(1024), 0, s, L.cnt, (uint32_t)n_reads, a.cap, L.coff, L.ra0, L.tot, DeclArgs{});
     // the caller's arrays: written by the compaction launch itself when they are page-locked (rawdtw_host_alloc) -- no copy command, no second
     // wait for sizes only the device knows; else copied at the round's end
-    auto page_locked = [](const void *q) {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, q) != hipSuccess) { (void)hipGetLastError(); return false; }
-        return at.type == hipMemoryTypeHost;
-    };
     const bool direct = page_locked(anchor_off) && page_locked(recs) && (!anchors || page_locked(anchors)) && page_locked(chain_off);
-    hipLaunchKernelGGL(k_chain_compact, dim3((uint32_t)n_reads), dim3(64), 0, s, a, L.coff, L.ra0, L.rb, L.kb, n_keys, L.aoff, L.anch, L.refb, L.rbc, L.recs, L.tot,
-                       direct ? anchor_off : nullptr, direct ? recs : nullptr, direct ? anchors : nullptr, chains_cap);
+    if (decline)
+        hipLaunchKernelGGL(k_chain_compact<true>, dim3((uint32_t)n_reads), dim3(64), 0, s, a, L.coff, L.ra0, L.rb, L.kb, n_keys, L.aoff, L.anch, L.refb, L.rbc, L.recs, L.tot,
+                           direct ? anchor_off : nullptr, direct ? recs : nullptr, direct ? anchors : nullptr, chains_cap, L.why);
+    else
+        hipLaunchKernelGGL(k_chain_compact<false>, dim3((uint32_t)n_reads), dim3(64), 0, s, a, L.coff, L.ra0, L.rb, L.kb, n_keys, L.aoff, L.anch, L.refb, L.rbc, L.recs, L.tot,
+                           direct ? anchor_off : nullptr, direct ? recs : nullptr, direct ? anchors : nullptr, chains_cap, nullptr);
     HIP_TRY(ctx, hipGetLastError());
     uint64_t *h_tot = static_cast<uint64_t *>(w.pin);
-    HIP_TRY(ctx, hipMemcpyAsync(h_tot, L.tot, 64, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(h_tot, L.tot, tot_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipMemcpyAsync(chain_off, L.coff, (n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
     if (!w.done) HIP_TRY(ctx, hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
     HIP_TRY(ctx, hipEventRecord(w.done, s));
@@ -809,6 +914,8 @@ int chain_begin(rawdtw_ctx *ctx, const rawdtw_chain_opt_t *opt, uint64_t n_reads
     for (uint64_t k = 0; k < n_long; k++) w.st_long_seeds += seed_off[w.long_reads[k].r + 1] - seed_off[w.long_reads[k].r];
     w.h_anchor_off = anchor_off; w.h_recs = recs; w.h_anchors = anchors;
     w.d_aoff = L.aoff; w.d_recs = L.recs; w.d_anch = L.anch; w.d_refb = L.refb; w.d_rbc = L.rbc;
+    w.decline = decline; w.n_seeds = n_seeds; w.batch_room = L.batch_entries(); w.h_chain_off = chain_off;
+    w.d_soff = L.soff; w.d_seeds = L.seeds; w.d_list = L.dlist;
     return RAWDTW_OK;
 }
 
@@ -862,12 +969,118 @@ int rawdtw_chain_round_end(rawdtw_ctx *ctx, const rawdtw_anchor_t **d_anchors, c
     w.st_above_32 += h_tot[5]; w.st_max_chains = std::max<uint64_t>(w.st_max_chains, h_tot[7]);
     if (w.many) w.st_restated += h_tot[6];
     if (nc > w.chains_cap) return fail(ctx, RAWDTW_ERR_RANGE, "chain output arrays too small");
+    if (w.decline) { // the declined reads, ascending, with their reasons and where their seeds start among the declined reads' seeds
+        const uint64_t nd = h_tot[8];
+        if (nd > w.n_reads) return fail(ctx, RAWDTW_ERR_DEVICE, "the chaining's count of declined reads is not one of this round");
+        try { w.decl.resize(nd); w.decl_reads.resize(nd); w.decl_why.resize(nd); w.decl_seed0.resize(nd + 1); }
+        catch (const std::bad_alloc &) { return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed"); }
+        if (nd) {
+            HIP_TRY(ctx, hipMemcpyAsync(w.decl.data(), w.d_list, nd * sizeof(DeclRec), hipMemcpyDeviceToHost, s));
+            HIP_TRY(ctx, hipStreamSynchronize(s));
+        }
+        for (uint64_t j = 0; j < nd; j++) { w.decl_reads[j] = w.decl[j].r; w.decl_why[j] = w.decl[j].why; w.decl_seed0[j] = w.decl[j].seed0; }
+        w.decl_seed0[nd] = w.decl_seeds = h_tot[12];
+        w.nc = nc; w.na = na;
+    }
     if (!w.direct) {
         HIP_TRY(ctx, hipMemcpyAsync(w.h_anchor_off, w.d_aoff, (nc + 1) * 8, hipMemcpyDeviceToHost, s));
         if (nc) HIP_TRY(ctx, hipMemcpyAsync(w.h_recs, w.d_recs, nc * sizeof(rawdtw_chain_rec_t), hipMemcpyDeviceToHost, s));
         if (w.h_anchors && na) HIP_TRY(ctx, hipMemcpyAsync(w.h_anchors, w.d_anch, na * sizeof(rawdtw_anchor_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(ctx, hipStreamSynchronize(s));
     }
+    *d_anchors = w.d_anch; *d_ref_base = w.d_refb; *d_read_base = w.d_rbc;
+    w.ended = w.appendable = w.decline;
+    return RAWDTW_OK;
+}
+
+int rawdtw_chain_round_declined(rawdtw_ctx *ctx, uint64_t *n_declined, const uint32_t **reads, const uint32_t **why)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (!n_declined) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    *n_declined = 0;
+    if (reads) *reads = nullptr;
+    if (why) *why = nullptr;
+    if (!ctx->chain_ws) return RAWDTW_OK;
+    const ChainWs &w = ctx->chain_ws->w;
+    if (w.pending) return fail(ctx, RAWDTW_ERR_INVALID, "a chaining round is begun on this context and not ended");
+    if (!w.ended) return RAWDTW_OK; // (the option was off, or the round's end failed: nobody was declined alone)
+    *n_declined = w.decl_reads.size();
+    if (reads) *reads = w.decl_reads.data();
+    if (why) *why = w.decl_why.data();
+    return RAWDTW_OK;
+}
+
+int rawdtw_chain_round_declined_seeds(rawdtw_ctx *ctx, uint64_t *seed_off_out, rawdtw_seed_t *seeds_out, uint64_t cap)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (!seed_off_out || (!seeds_out && cap)) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    if (!ctx->chain_ws || ctx->chain_ws->w.pending || !ctx->chain_ws->w.ended)
+        return fail(ctx, RAWDTW_ERR_INVALID, "no ended chaining round with \"chain_decline_reads\" on this context");
+    ChainWs &w = ctx->chain_ws->w;
+    const uint64_t nd = w.decl_reads.size(), total = w.decl_seeds;
+    memcpy(seed_off_out, w.decl_seed0.data(), (nd + 1) * 8);
+    if (total > cap) return fail(ctx, RAWDTW_ERR_RANGE, "the declined reads' seeds do not fit the array (the offsets are filled)");
+    if (nd == 0 || total == 0) return RAWDTW_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    rawdtw_seed_t *dst = seeds_out;
+    if (!page_locked(seeds_out)) { // through page-locked memory of the workspace's own, grow-only
+        const size_t need = (size_t)total * sizeof(rawdtw_seed_t);
+        if (w.pin_seeds_bytes < need) {
+            if (w.pin_seeds) (void)hipHostFree(w.pin_seeds);
+            w.pin_seeds = nullptr; w.pin_seeds_bytes = 0;
+            if (hipHostMalloc(&w.pin_seeds, need + need / 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); w.pin_seeds = nullptr; return fail(ctx, RAWDTW_ERR_OOM, "pinned allocation failed"); }
+            w.pin_seeds_bytes = need + need / 4;
+        }
+        dst = static_cast<rawdtw_seed_t *>(w.pin_seeds);
+    }
+    hipLaunchKernelGGL(k_declined_seeds, dim3((uint32_t)nd), dim3(64), 0, s, w.d_list, w.d_soff, w.d_seeds, dst);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    if (dst != seeds_out) memcpy(seeds_out, dst, (size_t)total * sizeof(rawdtw_seed_t));
+    return RAWDTW_OK;
+}
+
+int rawdtw_chain_round_append(rawdtw_ctx *ctx, uint64_t n_declined, const uint64_t *chain_off, const rawdtw_chain_rec_t *recs, const uint64_t *anchor_off,
+                              const rawdtw_anchor_t *anchors, uint64_t *chain_off_ext, uint64_t *anchor_off_ext, const rawdtw_anchor_t **d_anchors,
+                              const uint64_t **d_ref_base, const uint32_t **d_read_base)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (!chain_off || !anchor_off || !chain_off_ext || !anchor_off_ext || !d_anchors || !d_ref_base || !d_read_base) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    if (!ctx->chain_ws || ctx->chain_ws->w.pending || !ctx->chain_ws->w.appendable)
+        return fail(ctx, RAWDTW_ERR_INVALID, "no ended chaining round with \"chain_decline_reads\" on this context that waits for its declined reads' chains");
+    ChainWs &w = ctx->chain_ws->w;
+    if (n_declined != w.decl_reads.size()) return fail(ctx, RAWDTW_ERR_INVALID, "the appended reads are not the round's declined reads");
+    const uint64_t nc0 = w.nc, na0 = w.na;
+    // every check before the first write
+    for (uint64_t j = 0; j < n_declined; j++) if (chain_off[j + 1] < chain_off[j]) return fail(ctx, RAWDTW_ERR_INVALID, "offsets do not ascend");
+    const uint64_t nca = chain_off[n_declined];
+    if ((nca && (!recs || !anchors))) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    for (uint64_t c = 0; c < nca; c++) {
+        if (anchor_off[c + 1] < anchor_off[c] || anchor_off[c + 1] - anchor_off[c] != recs[c].n_anchors) return fail(ctx, RAWDTW_ERR_INVALID, "a chain's anchor_off stretch is not its record's n_anchors");
+        if (recs[c].key >= w.h_key_base.size()) return fail(ctx, RAWDTW_ERR_INVALID, "a seed's key is not below n_keys");
+    }
+    // room: the workspace's batch arrays (ChainLayout: what the round's seeds can make) -- the caller sized chain_off_ext and anchor_off_ext itself
+    const int st = chain_append::extend_offsets(w.n_reads, w.h_chain_off, w.h_anchor_off, nc0, na0, n_declined, chain_off, anchor_off, w.batch_room, w.n_seeds,
+                                                chain_off_ext, anchor_off_ext);
+    if (st == chain_append::kBadOffsets) return fail(ctx, RAWDTW_ERR_INVALID, "offsets do not start at 0, or the round's chain_off / anchor_off are no longer the round's");
+    if (st == chain_append::kNoRoom) return fail(ctx, RAWDTW_ERR_RANGE, "more chains or anchors than the round's seeds can make");
+    const uint64_t naa = anchor_off[nca];
+    try { w.app_refb.resize(nca); w.app_rbc.resize(nca); } catch (const std::bad_alloc &) { return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed"); }
+    for (uint64_t j = 0; j < n_declined; j++)
+        for (uint64_t c = chain_off[j]; c < chain_off[j + 1]; c++) { w.app_refb[c] = w.h_key_base[recs[c].key]; w.app_rbc[c] = w.h_read_base[w.decl_reads[j]]; }
+    w.appendable = false;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(const_cast<uint64_t *>(w.d_aoff) + nc0, anchor_off_ext + nc0, (nca + 1) * 8, hipMemcpyHostToDevice, s));
+    if (nca) {
+        HIP_TRY(ctx, hipMemcpyAsync(const_cast<rawdtw_chain_rec_t *>(w.d_recs) + nc0, recs, nca * sizeof(rawdtw_chain_rec_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(const_cast<uint64_t *>(w.d_refb) + nc0, w.app_refb.data(), nca * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(const_cast<uint32_t *>(w.d_rbc) + nc0, w.app_rbc.data(), nca * 4, hipMemcpyHostToDevice, s));
+    }
+    if (naa) HIP_TRY(ctx, hipMemcpyAsync(const_cast<rawdtw_anchor_t *>(w.d_anch) + na0, anchors, naa * sizeof(rawdtw_anchor_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s)); // (the caller's arrays and the workspace's staging are free again)
+    w.nc = nc0 + nca; w.na = na0 + naa;
     *d_anchors = w.d_anch; *d_ref_base = w.d_refb; *d_read_base = w.d_rbc;
     return RAWDTW_OK;
 }
@@ -929,6 +1142,7 @@ void chain_ws_free(rawdtw_ctx *ctx)
     if (!ctx || !ctx->chain_ws) return;
     if (ctx->chain_ws->w.dev) (void)hipFree(ctx->chain_ws->w.dev);
     if (ctx->chain_ws->w.pin) (void)hipHostFree(ctx->chain_ws->w.pin);
+    if (ctx->chain_ws->w.pin_seeds) (void)hipHostFree(ctx->chain_ws->w.pin_seeds);
     if (ctx->chain_ws->w.done) (void)hipEventDestroy(ctx->chain_ws->w.done);
     delete ctx->chain_ws;
     ctx->chain_ws = nullptr;

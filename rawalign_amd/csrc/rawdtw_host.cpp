@@ -412,6 +412,53 @@ int rawdtw_sort_by_chaining_score_restated(const float *chaining_score, uint32_t
     return ok ? RAWDTW_OK : RAWDTW_ERR_RANGE;
 }
 
+// which reads of a round the device chaining declines under "chain_decline_reads", and why -- the host's prediction, no device: the counts come from
+// rawdtw_chain_anchors list by list in key order (the order the device generates a read's chains in), the tie rule is the device's insertion order's
+int rawdtw_chain_decline_host(const rawdtw_chain_opt_t *opt, uint64_t n_reads, const uint64_t *seed_off, const rawdtw_seed_t *seeds, uint32_t seed_cap,
+                              uint32_t long_seeds, uint32_t max_chains, uint32_t *why_out, uint32_t *n_chains_out)
+{
+    if (!opt || !seed_off || !why_out || (!seeds && n_reads && seed_off[n_reads])) return RAWDTW_ERR_INVALID;
+    const uint64_t cap = seed_cap ? std::min<uint32_t>(seed_cap, 2048u) : 2048u;
+    std::vector<rawdtw_seed_t> s;
+    std::vector<rawdtw_anchor_t> an, out_an;
+    std::vector<rawdtw_chain_out_t> out(std::max(1, opt->num_best_chains));
+    std::vector<uint64_t> out_off(out.size() + 1);
+    std::vector<float> score;
+    for (uint64_t r = 0; r < n_reads; r++) {
+        if (seed_off[r + 1] < seed_off[r]) return RAWDTW_ERR_INVALID;
+        const uint64_t n = seed_off[r + 1] - seed_off[r];
+        why_out[r] = 0;
+        if (n_chains_out) n_chains_out[r] = 0;
+        if (n > cap && n > long_seeds) { why_out[r] = 1; continue; }
+        s.assign(seeds + seed_off[r], seeds + seed_off[r + 1]);
+        std::sort(s.begin(), s.end(), [](const rawdtw_seed_t &a, const rawdtw_seed_t &b) {
+            return std::tie(a.key, a.target_position, a.query_position) < std::tie(b.key, b.target_position, b.query_position);
+        });
+        score.clear();
+        float maxs = 0.0f;
+        for (size_t g0 = 0; g0 < s.size();) {
+            size_t g1 = g0;
+            while (g1 < s.size() && s[g1].key == s[g0].key) g1++;
+            an.resize(g1 - g0); out_an.resize(g1 - g0);
+            for (size_t i = g0; i < g1; i++) an[i - g0] = rawdtw_anchor_t{s[i].target_position, s[i].query_position};
+            const int nc = rawdtw_chain_anchors(opt, an.data(), (uint32_t)an.size(), &maxs, out.data(), out_off.data(), out_an.data(), (uint32_t)out.size(), an.size());
+            if (nc < 0) return RAWDTW_ERR_RANGE;
+            for (int c = 0; c < nc; c++) score.push_back(out[c].chaining_score);
+            g0 = g1;
+        }
+        const size_t nc = score.size();
+        if (n_chains_out) n_chains_out[r] = (uint32_t)nc;
+        if (max_chains) { if (nc > max_chains) why_out[r] = 2; continue; } // ("chain_max_chains": ties or not)
+        // 32 records a read; beyond 16 chains the order of equal scores is std::sort's own -- equal scores as the device's insertion sort meets
+        // them, among the first 32 chains as generated
+        bool ties = false;
+        for (size_t i = 0; i < std::min<size_t>(nc, 32) && !ties; i++)
+            for (size_t j = 0; j < i; j++) if (score[j] == score[i]) { ties = true; break; }
+        why_out[r] = (nc > 32 ? 2u : 0u) | (nc > 16 && ties ? 4u : 0u);
+    }
+    return RAWDTW_OK;
+}
+
 int rawdtw_batch_build_jobs(const rawdtw_align_opt_t *opt, uint64_t n_chains, const uint64_t *anchor_off,
                             const rawdtw_anchor_t *anchors, const uint64_t *ref_base, const uint32_t *read_base,
                             uint64_t *job_off, rawdtw_job_t *jobs_out, uint64_t jobs_cap, uint64_t *n_jobs_out)

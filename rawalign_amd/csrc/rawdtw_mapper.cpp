@@ -129,9 +129,12 @@ struct RoundArrays {
     PinBuf<uint32_t> prev_src, keep_dst, kept_count; // "resident_chains": per read where its previous seeds come from, where its chains are kept, and what was kept
     PinBuf<rawdtw_round_out_t> re_out;    // the round's end from the device ("device_round_end"): per read, and per chain the primaries' indices
     PinBuf<uint32_t> re_primary;
+    PinBuf<uint64_t> chain_off_ext, anchor_off_ext; // "chain_decline_reads", a round that declined reads: the batch's read list -- the group's reads, then a pseudo-read
+                                          // for each declined read -- and the chains' anchor offsets with the host's chains behind the device's; grown on demand
     std::vector<uint32_t> chain_seq; // (the external scorer's view)
     std::vector<int32_t> chain_strand;
     uint64_t n_reads = 0, n_chains = 0, n_anchors = 0; // (the sizes the next round's matching reads again)
+    uint64_t n_reads_batch = 0;          // the reads of the round's batch: n_reads, and with "chain_decline_reads" the declined reads' pseudo-reads
     rawdtw_batch *batch = nullptr;
     uint64_t round_id = 0;
     bool carried = false;
@@ -164,6 +167,8 @@ struct RoundRead {
     uint32_t chunk_start = 0;
     bool from_store = false;             // "resident_chains": its previous seeds were taken from the store of kept chains
     uint64_t n_prev = 0;                 // ... and how many it had, from either side
+    bool declined = false;               // "chain_decline_reads": the device chaining declined it alone; its chains are the host's, behind the device's
+    uint64_t bpos = 0;                   // its read in the group's batch: its position, or a declined read's pseudo-read behind the group's reads
     int err = RAWDTW_OK;
 };
 
@@ -325,6 +330,11 @@ struct rawdtw_mapper {
     uint64_t kp_reads_dev = 0, kp_reads_host = 0, kp_seeds_dev = 0, kp_seeds_host = 0, kp_not_kept = 0;
     uint32_t kp_reserved = 0;
     bool kp_any = false; // some read may hold kept chains
+    // rawdtw_mapper_decline_stats ("chain_decline_reads"): rounds in which the device chaining declined reads alone, those reads by reason, the reads
+    // it chained in such rounds' place of a fall-back or not, and the declined reads' seeds a resident round brought home
+    uint64_t dc_rounds = 0, dc_reads_seeds = 0, dc_reads_chains = 0, dc_reads_device = 0, dc_seed_bytes = 0;
+    PinBuf<uint64_t> decl_soff;     // the declined reads' seeds from the device (rawdtw_chain_round_declined_seeds), page-locked
+    PinBuf<rawdtw_seed_t> decl_seeds;
     uint64_t sig_cap = 0; // the largest events_cap a round from signal ran with: what the seeding's workspace holds already
     bool arena_replaced = false;    // rawdtw_mapper_finish has uploaded the host's copies over the event arena: no slot holds its read's events any more
     bool finish_from_arena = false; // "signal_cigar": a --dtw-output-cigar mapper has committed a round from signal -- the host's copy of a read's
@@ -407,10 +417,22 @@ void write_seeds(const MRead &rd, const rawdtw_seed_hit_t *hits, uint64_t n_hits
 
 // The host phase of one read after its events: the round's anchors, chaining, evaluation order, carry records -- the round's chains
 // in rr.chains.  `pv` = the arrays of the round before of the read's group (null: none, or the read was not in it).
+void host_chain_seeds(rawdtw_mapper *m, RoundRead &rr, std::vector<rawdtw_seed_t> &seeds, bool runs_dtw);
+void host_phase_carry(const MRead &rd, RoundRead &rr, const RoundArrays *pv);
+
 void host_phase_chain(rawdtw_mapper *m, const MRead &rd, RoundRead &rr, const rawdtw_seed_hit_t *hits, uint64_t n_hits, const RoundArrays *pv, bool runs_dtw)
 {
     std::vector<rawdtw_seed_t> seeds(seed_count(rd, n_hits));
     write_seeds(rd, hits, n_hits, rr.chunk_start, seeds.data());
+    host_chain_seeds(m, rr, seeds, runs_dtw);
+    if (rr.err != RAWDTW_OK || !runs_dtw || !pv) return;
+    host_phase_carry(rd, rr, pv);
+}
+
+// a read's seeds, in any order, to its round's chains in evaluation order (rr.chains, rr.ref_base): what host_phase_chain does with the seeds
+// it builds, and what a round does with the seeds of a read the device chaining declined alone ("chain_decline_reads") -- one code, the same chains
+void host_chain_seeds(rawdtw_mapper *m, RoundRead &rr, std::vector<rawdtw_seed_t> &seeds, bool runs_dtw)
+{
     // by (sequence, strand), then (target, query): rmap.cpp:396-401 sorts every list; rmap.cpp:432-433 walks them sequence-major,
     // strand 0 then 1
     std::sort(seeds.begin(), seeds.end(), [](const rawdtw_seed_t &a, const rawdtw_seed_t &b) {
@@ -454,7 +476,10 @@ void host_phase_chain(rawdtw_mapper *m, const MRead &rd, RoundRead &rr, const ra
     rr.ref_base.resize(rr.chains.size());
     rr.carry.assign(rr.chains.size(), rawdtw_carry_t{RAWDTW_NO_CHAIN, 0u, 0u, rawdtw_anchor_t{0u, 0u}});
     for (size_t c = 0; c < rr.chains.size(); c++) rr.ref_base[c] = m->ref_off[rr.chains[c].ref * 2u + (uint32_t)rr.chains[c].strand];
-    if (!pv) return;
+}
+
+void host_phase_carry(const MRead &rd, RoundRead &rr, const RoundArrays *pv)
+{
     // chunk rounds: the chain of the round before this chain continues -- same strand array, same start anchor, the longest
     // common tail, compared anchor by anchor -- and the leading parts taken over (as rawdtw_round_match_chains)
     const uint64_t pr = rd.last_pos;
@@ -574,7 +599,8 @@ struct Round {
     std::vector<RoundRead> rr = std::vector<RoundRead>(n_reads);
     struct PerGroup { bool chaining = false; uint64_t ns = 0, nev = 0, nseg = 0, scored = 0, reused = 0, extra = 0; // (ns: seeds sent up; extra: other bytes)
                       bool round_end = false; uint64_t re_reads = 0, re_declined = 0; // (the round's end enqueued on the device; the reads it ended / declined)
-                      bool keep = false; } per[2];                                    // (... and the keep launch behind it)
+                      bool keep = false;                                              // (... and the keep launch behind it)
+                      uint64_t dc_reads = 0, dc_seeds = 0, dc_chains = 0, dc_device = 0, dc_bytes = 0; } per[2]; // ("chain_decline_reads": the reads declined alone, by reason; the others; seed bytes home)
     bool device_round_end = round_end_on_device(m); // (read once a round)
     uint32_t resident_chains = resident_chains_option(m); // (so is this)
     // the round takes previous seeds from the store of kept chains and keeps its own there: a resident round with the option on whose end
@@ -586,6 +612,7 @@ struct Round {
     MRead &read(uint32_t k) const { return m->reads[read_ids[k]]; }
     uint32_t arena_base(const MRead &rd) const { return (G == 2 ? rd.slot / 2 : rd.slot) * m->opt.slot_events; } // its slot in its group's event arena
     bool ok() const { return status == RAWDTW_OK; }
+    static bool decline_reads(const Group &g) { int64_t v = 0; return rawdtw_get_option(g.ctx, "chain_decline_reads", &v) == RAWDTW_OK && v != 0; }
     void failed(int st, const std::string &s) { if (ok()) { status = st; msg = s; } }
     void lap(int slot) { const double t = now_ms(); m->timing[slot] += t - t0; t0 = t; } // (include/rawdtw.h: rawdtw_mapper_timing)
 
@@ -875,10 +902,17 @@ struct Round {
             return host_round(gi, nullptr, true);
         }
         if (st != RAWDTW_OK) return failed(st, rawdtw_last_error(g.ctx));
-        const uint64_t nc = ra.chain_off[nr], na = ra.anchor_off[nc];
-        ra.n_chains = nc; ra.n_anchors = na;
+        // "chain_decline_reads": the reads the device declined alone are chained here, their chains appended behind the device's
+        uint64_t nd = 0;
+        const uint64_t *batch_off = ra.chain_off.p, *batch_aoff = ra.anchor_off.p;
+        if (decline_reads(g)) {
+            if (!append_declined(gi, &nd, &d_anchors, &d_ref_base, &d_read_base)) return;
+            if (nd) { batch_off = ra.chain_off_ext.p; batch_aoff = ra.anchor_off_ext.p; }
+        }
+        const uint64_t nc = batch_off[nr + nd], na = batch_aoff[nc];
+        ra.n_chains = nc; ra.n_anchors = na; ra.n_reads_batch = nr + nd;
         // (a resident round of a mapper that runs no DTW -- neither EVALUATE_CHAINS nor LOG_SCORES -- ends with the chains: rmap.cpp:509)
-        if (runs_dtw) st = rawdtw_batch_submit_device(g.ctx, &m->opt.align, nr, ra.chain_off.p, ra.anchor_off.p, d_anchors, d_ref_base, d_read_base, &ra.batch);
+        if (runs_dtw) st = rawdtw_batch_submit_device(g.ctx, &m->opt.align, nr + nd, batch_off, batch_aoff, d_anchors, d_ref_base, d_read_base, &ra.batch);
         if (st != RAWDTW_OK) return failed(st, rawdtw_last_error(g.ctx));
         if (runs_dtw && device_round_end && ra.batch) st = begin_round_end(g, ra, p);
         if (st != RAWDTW_OK) return failed(st, rawdtw_last_error(g.ctx));
@@ -887,6 +921,8 @@ struct Round {
         lap(2);
         m->pool->run(nr, 32, [&](size_t i) {
             RoundRead &r = rr[ra.ks[i]];
+            if (r.declined) return; // (its chains are the host's already, and chain0 / bpos its pseudo-read's)
+            r.bpos = i;
             r.chain0 = ra.chain_off[i];
             r.chains.resize(ra.chain_off[i + 1] - ra.chain_off[i]);
             for (uint64_t c = 0; c < r.chains.size(); c++) {
@@ -901,10 +937,85 @@ struct Round {
         lap(1);
     }
 
+    // "chain_decline_reads", after a successful rawdtw_chain_round_end: the declined reads' seeds (from the device in a resident round, whose
+    // seed list was laid down there; from the group's own list otherwise), their chains by the host's code on the pool, and the append.  Each
+    // declined read gets a pseudo-read at the end of the batch's read list (bpos): the batch's score and keep, k_round_end's record and primaries
+    // are read there, and its own empty stretch is never looked at.  It is not kept in the store (RAWDTW_NO_KEEP on both).  false: failed.
+    bool append_declined(uint32_t gi, uint64_t *n_declined, const rawdtw_anchor_t **d_anchors, const uint64_t **d_ref_base, const uint32_t **d_read_base)
+    {
+        Group &g = m->groups[gi]; RoundArrays &ra = g.buf[g.cur];
+        PerGroup &p = per[gi];
+        const size_t nr = ra.ks.size();
+        uint64_t nd = 0;
+        const uint32_t *dreads = nullptr, *dwhy = nullptr;
+        int st = rawdtw_chain_round_declined(g.ctx, &nd, &dreads, &dwhy);
+        if (st != RAWDTW_OK) { failed(st, rawdtw_last_error(g.ctx)); return false; }
+        *n_declined = nd;
+        for (size_t i = 0; i < nr; i++) p.dc_device += rr[ra.ks[i]].skipped ? 0 : 1;
+        if (nd == 0) return true;
+        const uint64_t *soff = ra.seed_off.p; // (a declined read's seeds: [soff[x], soff[x + 1]) of `seeds`, x its position in the group or in the list)
+        const rawdtw_seed_t *seeds = ra.seeds.p;
+        if (resident) {
+            if (!seed_room(m, m->decl_soff, nd + 1)) { failed(RAWDTW_ERR_OOM, "no page-locked memory for the declined reads' seeds"); return false; }
+            st = rawdtw_chain_round_declined_seeds(g.ctx, m->decl_soff.p, m->decl_seeds.p, m->decl_seeds.p ? m->decl_seeds.cap : 0);
+            if (st == RAWDTW_ERR_RANGE) { // (the offsets are filled: room for what they say, then again)
+                if (!seed_room(m, m->decl_seeds, m->decl_soff[nd] + 1)) { failed(RAWDTW_ERR_OOM, "no page-locked memory for the declined reads' seeds"); return false; }
+                st = rawdtw_chain_round_declined_seeds(g.ctx, m->decl_soff.p, m->decl_seeds.p, m->decl_seeds.cap);
+            }
+            if (st != RAWDTW_OK) { failed(st, rawdtw_last_error(g.ctx)); return false; }
+            soff = m->decl_soff.p; seeds = m->decl_seeds.p;
+            p.dc_bytes += m->decl_soff[nd] * sizeof(rawdtw_seed_t);
+        }
+        m->pool->run(nd, 1, [&](size_t j) {
+            const size_t x = resident ? j : dreads[j];
+            RoundRead &r = rr[ra.ks[dreads[j]]];
+            std::vector<rawdtw_seed_t> mine(seeds + soff[x], seeds + soff[x + 1]);
+            host_chain_seeds(m, r, mine, runs_dtw);
+            r.declined = true; r.bpos = nr + j;
+        });
+        std::vector<uint64_t> coff(nd + 1, 0), aoff(1, 0);
+        for (uint64_t j = 0; j < nd; j++) {
+            const RoundRead &r = rr[ra.ks[dreads[j]]];
+            if (r.err != RAWDTW_OK) { failed(r.err, "chaining failed (chain output buffers too small)"); return false; }
+            coff[j + 1] = coff[j] + r.chains.size();
+            p.dc_reads++; p.dc_seeds += dwhy[j] & 1u; p.dc_chains += (dwhy[j] & 6u) ? 1 : 0;
+        }
+        p.dc_device -= nd;
+        std::vector<rawdtw_chain_rec_t> recs(coff[nd] + 1);
+        std::vector<rawdtw_anchor_t> anchors;
+        for (uint64_t j = 0; j < nd; j++) {
+            const RoundRead &r = rr[ra.ks[dreads[j]]];
+            for (size_t c = 0; c < r.chains.size(); c++) {
+                const MChain &ch = r.chains[c];
+                recs[coff[j] + c] = rawdtw_chain_rec_t{ch.chaining_score, ch.ref * 2u + (uint32_t)ch.strand, ch.start_position, ch.end_position, (uint32_t)ch.anchors.size()};
+                anchors.insert(anchors.end(), ch.anchors.begin(), ch.anchors.end());
+                aoff.push_back(anchors.size());
+            }
+        }
+        anchors.push_back(rawdtw_anchor_t{0, 0}); // (never a null array)
+        // room, on demand -- a round nobody is declined in allocates nothing: the batch's two offset arrays, its per-chain results, and with the
+        // store its per-read destinations (whose first nr entries are written already)
+        const uint64_t nc = ra.chain_off[nr] + coff[nd], nb = nr + nd;
+        bool room = ra.chain_off_ext.ensure(nb + 1, on_device) && ra.anchor_off_ext.ensure(nc + 1, on_device) && ra.score.ensure(nc + 1, on_device) &&
+                    ra.keep.ensure(nc + 1, on_device);
+        if (use_store()) room = room && ra.keep_dst.ensure(nb + 1, false, nr) && ra.kept_count.ensure(nb + 1, false);
+        if (!room) { failed(RAWDTW_ERR_OOM, "host allocation failed"); return false; }
+        st = rawdtw_chain_round_append(g.ctx, nd, coff.data(), recs.data(), aoff.data(), anchors.data(), ra.chain_off_ext.p, ra.anchor_off_ext.p, d_anchors, d_ref_base,
+                                       d_read_base);
+        if (st != RAWDTW_OK) { failed(st, rawdtw_last_error(g.ctx)); return false; }
+        for (uint64_t j = 0; j < nd; j++) {
+            rr[ra.ks[dreads[j]]].chain0 = ra.chain_off_ext[nr + j];
+            if (use_store()) { ra.keep_dst[dreads[j]] = RAWDTW_NO_KEEP; ra.keep_dst[nr + j] = RAWDTW_NO_KEEP; }
+        }
+        p.extra += (nd + 1) * 8 + coff[nd] * (sizeof(rawdtw_chain_rec_t) + 20) + (anchors.size() - 1) * sizeof(rawdtw_anchor_t);
+        return true;
+    }
+
     // "device_round_end": the round's end enqueued right behind the batch, on the chaining workspace's records where they lie
     int begin_round_end(Group &g, RoundArrays &ra, PerGroup &p)
     {
-        if (!ra.re_out.ensure(g.hw_reads + 1, false) || !ra.re_primary.ensure(g.hw_chains + 1, false)) { failed(RAWDTW_ERR_OOM, "host allocation failed"); return RAWDTW_ERR_OOM; }
+        // (a round that declined reads alone has a pseudo-read for each of them, and their chains behind the device's: ra.n_reads_batch / n_chains)
+        if (!ra.re_out.ensure(std::max<uint64_t>(g.hw_reads, ra.n_reads_batch) + 1, false) || !ra.re_primary.ensure(std::max<uint64_t>(g.hw_chains, ra.n_chains) + 1, false)) { failed(RAWDTW_ERR_OOM, "host allocation failed"); return RAWDTW_ERR_OOM; }
         const rawdtw_chain_rec_t *d_recs = nullptr;
         int st = rawdtw_chain_round_recs(g.ctx, &d_recs);
         const rawdtw_select_opt_t so = select_opt(m);
@@ -1070,8 +1181,8 @@ struct Round {
             const uint32_t k = ra.ks[i];
             RoundRead &r = rr[k];
             if (r.skipped) { r.high = high_confidence(m, read(k).chains); return; } // rmap.cpp:569-572: the chains stay as they were
-            if (from_device && !(ra.re_out[i].flags & RAWDTW_ROUND_DECLINED)) { // primary, mapq and the stop rule's answer are the device's: the chains are moved
-                const rawdtw_round_out_t &o = ra.re_out[i];
+            if (from_device && !(ra.re_out[r.bpos].flags & RAWDTW_ROUND_DECLINED)) { // primary, mapq and the stop rule's answer are the device's: the chains are moved
+                const rawdtw_round_out_t &o = ra.re_out[r.bpos]; // (its read in the batch: a read the chaining declined alone has a pseudo-read)
                 if (log_scores)
                     for (size_t c = 0; c < r.chains.size(); c++) {
                         const float as = ra.score[r.chain0 + c];
@@ -1113,7 +1224,7 @@ struct Round {
         if (from_device) // (counted here, not by the pool's threads: sixteen of them adding to one counter cost the round more than its end)
             for (size_t i = 0; i < ra.ks.size(); i++) {
                 if (rr[ra.ks[i]].skipped) continue;
-                if (ra.re_out[i].flags & RAWDTW_ROUND_DECLINED) per[gi].re_declined++; else per[gi].re_reads++;
+                if (ra.re_out[rr[ra.ks[i]].bpos].flags & RAWDTW_ROUND_DECLINED) per[gi].re_declined++; else per[gi].re_reads++;
             }
         lap(4);
     }
@@ -1143,6 +1254,7 @@ struct Round {
     {
         m->rounds = id;
         if (per[0].round_end || per[1].round_end) m->re_rounds++;
+        if (per[0].dc_reads || per[1].dc_reads) m->dc_rounds++;
         if (resident) {
             if (fell_back) { m->res_fallbacks++; m->res_hit_bytes += res_hits * sizeof(rawdtw_seed_hit_t); }
             else m->res_rounds++;
@@ -1156,6 +1268,10 @@ struct Round {
             if (!g.has_prev && ra.batch) { rawdtw_batch_destroy(ra.batch); ra.batch = nullptr; }
             m->parts_scored += per[gi].scored; m->parts_reused += per[gi].reused;
             m->re_reads += per[gi].re_reads; m->re_declined += per[gi].re_declined;
+            if (per[gi].dc_reads) {
+                m->dc_reads_seeds += per[gi].dc_seeds; m->dc_reads_chains += per[gi].dc_chains; m->dc_reads_device += per[gi].dc_device;
+                m->dc_seed_bytes += per[gi].dc_bytes;
+            }
             for (size_t i = 0; i < ra.ks.size(); i++) { read(ra.ks[i]).last_round = id; read(ra.ks[i]).last_pos = i; }
             // "resident_chains": the one place a read's kept state changes.  A read that sat out keeps its chains and its state; a read whose
             // chains were kept is seeded from that half from now on; every other read's chains are new and not on the device
@@ -1240,6 +1356,9 @@ int rawdtw_mapper_create(rawdtw_ctx *ctx, const rawdtw_mapper_opt_t *opt, uint32
         int64_t chain_many = 0;
         if (st == RAWDTW_OK) st = rawdtw_get_option(ctx, "chain_max_chains", &chain_many);
         if (st == RAWDTW_OK) st = rawdtw_set_option(m->groups[1].ctx, "chain_max_chains", chain_many);
+        int64_t chain_decline = 0;
+        if (st == RAWDTW_OK) st = rawdtw_get_option(ctx, "chain_decline_reads", &chain_decline);
+        if (st == RAWDTW_OK) st = rawdtw_set_option(m->groups[1].ctx, "chain_decline_reads", chain_decline);
     }
     const uint64_t per_group = ((uint64_t)opt->max_reads + (uint64_t)m->opt.groups - 1) / (uint64_t)m->opt.groups;
     for (Group &g : m->groups)
@@ -1634,6 +1753,18 @@ int rawdtw_mapper_kept_stats(const rawdtw_mapper *m, uint64_t *reads_from_device
     if (seeds_from_device) *seeds_from_device = m->kp_seeds_dev;
     if (seeds_from_host) *seeds_from_host = m->kp_seeds_host;
     if (reads_not_kept) *reads_not_kept = m->kp_not_kept;
+    return RAWDTW_OK;
+}
+
+int rawdtw_mapper_decline_stats(const rawdtw_mapper *m, uint64_t *rounds_with_declines, uint64_t *reads_declined_seeds, uint64_t *reads_declined_chains,
+                                uint64_t *reads_chained_device, uint64_t *seed_bytes_to_host)
+{
+    if (!m) return RAWDTW_ERR_INVALID;
+    if (rounds_with_declines) *rounds_with_declines = m->dc_rounds;
+    if (reads_declined_seeds) *reads_declined_seeds = m->dc_reads_seeds;
+    if (reads_declined_chains) *reads_declined_chains = m->dc_reads_chains;
+    if (reads_chained_device) *reads_chained_device = m->dc_reads_device;
+    if (seed_bytes_to_host) *seed_bytes_to_host = m->dc_seed_bytes;
     return RAWDTW_OK;
 }
 

@@ -100,6 +100,23 @@ def round_keep_host(chain_off, recs, anchor_off, anchors, out, primary, cap):
     return kept[:n], soff, seeds[:int(soff[n])]
 
 
+def chain_decline_host(chain_opt, per_read, seed_cap: int = 0, long_seeds: int = 0, max_chains: int = 0):
+    """rawdtw_chain_decline_host: which reads of a round (`per_read`: a SEED_DTYPE array a read) the device chaining declines under
+    "chain_decline_reads", and why, without a device.  chain_opt: a ChainOpt (mapping.default_chain_opt); seed_cap: the cap on seeds a read
+    (0: 2 048; the tests' RAWDTW_CHAIN_MAX_SEEDS); long_seeds, max_chains: the context's "chain_long_seeds" and "chain_max_chains".
+    Returns (why: uint32 a read -- 0 chained, bit 1 seeds, 2 chains, 4 ties --, n_chains: uint32 a read)."""
+    n = len(per_read)
+    seed_off = np.zeros(n + 1, np.uint64)
+    seed_off[1:] = np.cumsum([len(s) for s in per_read])
+    seeds = np.ascontiguousarray(np.concatenate([np.asarray(s, SEED_DTYPE) for s in per_read] + [np.zeros(1, SEED_DTYPE)]))
+    why, n_chains = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+    st = load_library().rawdtw_chain_decline_host(C.byref(chain_opt), n, _ptr(seed_off), _ptr(seeds), int(seed_cap), int(long_seeds), int(max_chains),
+                                                  _ptr(why), _ptr(n_chains))
+    if st != 0:
+        raise RawDTWError(st, "rawdtw_chain_decline_host")
+    return why[:n], n_chains[:n]
+
+
 def plan_dry_run(jobs: np.ndarray, n_events: int, n_reference: int, threads: int = 0, options=None):
     """Host half of plan creation only (include/rawdtw.h: rawdtw_plan_dry_run): bins `jobs`, checks the plan's
     invariants and returns (info dict, n_tiles).  Touches no device and scores nothing."""
@@ -280,6 +297,43 @@ class Engine:
         v = [C.c_uint64() for _ in range(3)]
         self._check(self.lib.rawdtw_chain_order_stats(self._ctx, *[C.byref(x) for x in v]))
         return dict(zip(("reads_above_32", "reads_ordered_restated", "max_chains_a_read"), (int(x.value) for x in v)))
+
+    def chain_round_declined(self):
+        """rawdtw_chain_round_declined: (reads, why) of the ended chaining round -- the reads "chain_decline_reads" declined alone, ascending,
+        and their reasons' bits (1 seeds, 2 chains, 4 an order only std::sort knows); copies.  Empty with the option off."""
+        n, reads, why = C.c_uint64(), C.c_void_p(), C.c_void_p()
+        self._check(self.lib.rawdtw_chain_round_declined(self._ctx, C.byref(n), C.byref(reads), C.byref(why)))
+        if not n.value:
+            return np.zeros(0, np.uint32), np.zeros(0, np.uint32)
+        get = lambda p: np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(n.value,)).copy()  # noqa: E731
+        return get(reads), get(why)
+
+    def chain_round_declined_seeds(self, cap=None):
+        """rawdtw_chain_round_declined_seeds: (seed_off, seeds as SEED_DTYPE) of the declined reads, from the device's seed list.  cap: the
+        array's size in seeds (default: what the reads need; a smaller one raises with the status RAWDTW_ERR_RANGE)."""
+        reads, _ = self.chain_round_declined()
+        seed_off = np.zeros(len(reads) + 1, np.uint64)
+        if cap is None:  # (the offsets are filled whatever the cap)
+            st = self.lib.rawdtw_chain_round_declined_seeds(self._ctx, _ptr(seed_off), None, 0)
+            if st not in (0, 4):
+                self._check(st)
+            cap = int(seed_off[-1])
+        seeds = np.zeros(max(int(cap), 1), SEED_DTYPE)
+        self._check(self.lib.rawdtw_chain_round_declined_seeds(self._ctx, _ptr(seed_off), _ptr(seeds), int(cap)))
+        return seed_off, seeds[:int(seed_off[-1])]
+
+    def chain_round_append(self, n_reads: int, n_chains: int, chain_off, recs, anchor_off, anchors):
+        """rawdtw_chain_round_append: the host's chains of the declined reads (chain_off / anchor_off from 0, CHAIN_REC_DTYPE records, anchors
+        end-first) behind the round's own n_chains in device memory.  Returns (chain_off_ext of n_reads + n_declined + 1 entries,
+        anchor_off_ext of n_chains + the appended chains + 1, (d_anchors, d_ref_base, d_read_base)): what rawdtw_batch_submit_device takes."""
+        chain_off, anchor_off = np.ascontiguousarray(chain_off, np.uint64), np.ascontiguousarray(anchor_off, np.uint64)
+        recs, anchors = np.ascontiguousarray(recs), np.ascontiguousarray(anchors)
+        n = len(chain_off) - 1
+        ext, aext = np.zeros(int(n_reads) + n + 1, np.uint64), np.zeros(int(n_chains) + int(chain_off[-1]) + 1, np.uint64)
+        d = [C.c_void_p() for _ in range(3)]
+        self._check(self.lib.rawdtw_chain_round_append(self._ctx, n, _ptr(chain_off), _ptr(recs), _ptr(anchor_off), _ptr(anchors), _ptr(ext), _ptr(aext),
+                                                       *[C.byref(x) for x in d]))
+        return ext, aext, tuple(d)
 
     def round_end(self, select_opt, chain_off, recs, score, keep=None):
         """rawdtw_round_end: gen_primary_chains, comp_mapq and the stop rule for every read of a round in one launch.  `select_opt` is a

@@ -734,6 +734,17 @@ class CMapper:
         return dict(reads_from_device=v[0].value, reads_from_host=v[1].value, seeds_from_device=v[2].value, seeds_from_host=v[3].value,
                     reads_not_kept=v[4].value)
 
+    def decline_stats(self):
+        """rawdtw_mapper_decline_stats: with the context's "chain_decline_reads" on, over committed rounds in which the device chaining declined
+        reads alone -- those rounds, the reads declined for their seeds and for their chains, the rounds' other reads that took part, and the
+        bytes of declined reads' seeds a resident round brought home"""
+        import ctypes as C
+
+        v = [C.c_uint64() for _ in range(5)]
+        self._check(self.lib.rawdtw_mapper_decline_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(rounds_with_declines=v[0].value, reads_declined_seeds=v[1].value, reads_declined_chains=v[2].value,
+                    reads_chained_device=v[3].value, seed_bytes_to_host=v[4].value)
+
     def timing(self):
         t = np.zeros(8, np.float64)
         self._check(self.lib.rawdtw_mapper_timing(self._h, _vp(t)))
