@@ -234,7 +234,8 @@ template <> __device__ __forceinline__ void wband_loop_asm<{C}>(uint32_t &va, ui
 """
 
 
-def main():
+def header_text():
+    """the text of rawalign_amd/csrc/rawdtw_wband_asm.h"""
     out = ["// rawdtw_wband_asm.h -- GENERATED by scripts/gen_wband_asm.py (edit that, not this): the main loop of wband_gen<C> (rawdtw_dp.h).",
            "#pragma once", "namespace rawdtw {", "",
            "// the extents of a band's antidiagonals as lane masks of the blocked layout (lane l holds slots l C .. l C + C - 1): register c's lanes",
@@ -247,9 +248,13 @@ def main():
     for C in (1, 2, 3, 4, 5, 7, 8, 9):
         out.append(gen(C))
     out.append("} // namespace rawdtw")
+    return "\n".join(out)
+
+
+def main():
     path = os.path.join(ROOT, "rawalign_amd", "csrc", "rawdtw_wband_asm.h")
     with open(path, "w") as f:
-        f.write("\n".join(out))
+        f.write(header_text())
     print("wrote", path)
 
 
