@@ -1189,6 +1189,48 @@ int rawdtw_chain_round_begin_resident_kept(rawdtw_ctx *ctx, const rawdtw_chain_o
                                            uint32_t n_keys, const uint64_t *key_base, uint64_t *chain_off, uint64_t *anchor_off,
                                            rawdtw_chain_rec_t *recs, uint64_t chains_cap, rawdtw_anchor_t *anchors);
 
+/* ---- the reference from bases: ri_seq_to_sig (src/rsig.cpp:7-41) as rawindex.cpp:132-149 calls it, bit for bit.
+ * The forward array of a sequence is strand 1 (the bases from the last to the first, each as 3 ^ code), the reverse array strand 0.
+ * Codes are seq_nt4_table's (rutils.c:5-16): ACGTacgt, any other byte shifts 00 into the k-mer on either strand.  A strand has
+ * s_len = len - k + 1 values (0 for len < k): the model's level of each k-mer, normalised by the mean and the standard deviation of
+ * the strand's levels, whose sums are sequential double additions in emission order.  `contracted` 0: one rounding an operation;
+ * 1: std_dev = sqrt(fma(-mean, mean, sum2 / j)), what an -O3 build of the reference for an FMA host computes (the only operation of the
+ * function a compiler can fuse with an effect).  A strand of equal levels is NaN throughout (0 / 0); a NaN's sign and payload are not
+ * part of the contract.
+ *   rawdtw_pore_model_load   PoreModel::Load (pore_model.cpp:50-84) as main.cpp:349-351 uses it: lines that start with '#' or "kmer" are
+ *        skipped (blank ones too), *k is the first k-mer's length, a row's slot is GenerateSeedFromSequence's (N -> A, lower case
+ *        accepted), level_mean its second column; slots never named are 0.  RAWDTW_ERR_INVALID for an unreadable file, one without a
+ *        k-mer, a k-mer of another length or k > 12; RAWDTW_ERR_RANGE with *k set when cap < 4^k floats (level_mean NULL, cap 0: ask k).
+ *   rawdtw_seq_to_sig_host   one strand on the host: out has room for len - k + 1 floats.  The device's comparator; needs no GPU.
+ *   rawdtw_seq_sums_restated the two sums alone, as both paths advance them: 64 values a step, each step one exact integer reduction
+ *        where that equals the 64 roundings (every addend in [0, 2^(p+1)) for the sum's binade p, no rounding tie, no binade left),
+ *        else 64 additions in order.  fast / slow count the steps of sum [0] and of sum2 [1]; either may be NULL.  For tests.
+ *   rawdtw_reference_from_bases   what rawdtw_upload_reference does, from bases: the same arena layout, sequence table and
+ *        rawdtw_reference_offset answers, the arena counted and shared as any other.  pore_vals has 4^k floats.  The bases cross as they
+ *        are, a byte each; the codes are taken on the device.  A sequence shorter than k has length 0 on both strands.
+ *        RAWDTW_ERR_INVALID for k outside 1 .. 12, a len of 2^31 or more and null arguments.  A failed call leaves the context's
+ *        previous reference in place.
+ *   rawdtw_reference_fetch   one strand of the context's reference (however it got there) comes home; RAWDTW_ERR_RANGE when cap is
+ *        below its length, RAWDTW_ERR_INVALID for a sequence the context's table does not have.
+ *   rawdtw_reference_build_stats   of the context's most recent rawdtw_reference_from_bases: the steps over all strands that went fast
+ *        and slow, for sum [0] and sum2 [1], and the device time of the sums' and of the write's launch.  Any pointer may be NULL.
+ *   rawdtw_seed_index_build_device   rawdtw_seed_index_build from the arrays the context's reference holds (rawdtw_upload_reference,
+ *        rawdtw_index_upload or rawdtw_reference_from_bases), built on the device: the same keys in the same order, the same
+ *        rawdtw_seed_index_get answers and rawdtw_seed_index_info numbers.  w > 0: RAWDTW_ERR_UNSUPPORTED and nothing changed (build on
+ *        the host); no reference with a sequence table on the context, or bad pars: RAWDTW_ERR_INVALID.
+ *   rawdtw_seed_index_build_stats   milliseconds of the context's most recent device build: filter, emit, sort (device time), the
+ *        entries' way home and the table's build (host time). ---- */
+int rawdtw_pore_model_load(const char *path, uint32_t *k, float *level_mean, uint64_t cap);
+int rawdtw_seq_to_sig_host(const char *bases, uint32_t len, const float *pore_vals, uint32_t k, int strand, int contracted, float *out,
+                           uint32_t *s_len);
+int rawdtw_seq_sums_restated(const float *values, uint64_t n, double *sum, double *sum2, uint64_t fast[2], uint64_t slow[2]);
+int rawdtw_reference_from_bases(rawdtw_ctx *ctx, uint32_t n_seq, const char *const *bases, const uint64_t *len, const float *pore_vals,
+                                uint32_t k, int contracted);
+int rawdtw_reference_fetch(rawdtw_ctx *ctx, uint32_t seq, int strand, float *out, uint64_t cap);
+int rawdtw_reference_build_stats(const rawdtw_ctx *ctx, uint64_t fast_steps[2], uint64_t slow_steps[2], float kernel_ms[2]);
+int rawdtw_seed_index_build_device(rawdtw_ctx *ctx, const rawdtw_seed_pars_t *pars, rawdtw_seed_index **out);
+int rawdtw_seed_index_build_stats(const rawdtw_ctx *ctx, float phase_ms[5]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -309,6 +309,14 @@ SYMBOLS = {
     "rawdtw_chain_round_declined_seeds": (I32, [VP, VP, VP, U64]),
     "rawdtw_chain_round_append": (I32, [VP, U64, VP, VP, VP, VP, VP, VP, C.POINTER(VP), C.POINTER(VP), C.POINTER(VP)]),
     "rawdtw_chain_decline_host": (I32, [C.POINTER(ChainOpt), U64, VP, VP, U32, U32, U32, VP, VP]),
+    "rawdtw_pore_model_load": (I32, [C.c_char_p, C.POINTER(U32), VP, U64]),
+    "rawdtw_seq_to_sig_host": (I32, [VP, U32, VP, U32, I32, I32, VP, C.POINTER(U32)]),
+    "rawdtw_seq_sums_restated": (I32, [VP, U64, C.POINTER(C.c_double), C.POINTER(C.c_double), VP, VP]),
+    "rawdtw_reference_from_bases": (I32, [VP, U32, VP, VP, VP, U32, I32]),
+    "rawdtw_reference_fetch": (I32, [VP, U32, I32, VP, U64]),
+    "rawdtw_reference_build_stats": (I32, [VP, VP, VP, VP]),
+    "rawdtw_seed_index_build_device": (I32, [VP, C.POINTER(SeedPars), C.POINTER(VP)]),
+    "rawdtw_seed_index_build_stats": (I32, [VP, VP]),
 }
 
 

@@ -144,6 +144,12 @@ struct rawdtw_ctx {
     std::vector<rawdtw_batch *> live_batches;
     std::vector<uint64_t> ref_off; // 2*n_seq entries: [seq*2 + 0] = forward (strand 1), [seq*2 + 1] = reverse
     std::vector<uint32_t> ref_len;
+    // the most recent rawdtw_reference_from_bases (rawdtw_refsig.hip): steps of sum [0] and sum2 [1], the sums' and the write's launch
+    bool refsig_built = false;
+    uint64_t refsig_fast[2] = {0, 0}, refsig_slow[2] = {0, 0};
+    float refsig_ms[2] = {0.f, 0.f};
+    // the most recent rawdtw_seed_index_build_device (rawdtw_seed_build.hip): filter, emit, sort, entries home, fill_table
+    float seed_build_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     // event arena
     float *d_ev = nullptr;
     uint64_t n_ev = 0, cap_ev = 0;

@@ -72,6 +72,12 @@ RAWDTW_HD inline bool skipped_min(float x, float last, bool first)
 // w, e, n, q, lq, k as ri_idx_t keeps them; RAWDTW_ERR_INVALID where the reference asserts or shifts out of range
 int check_pars(const rawdtw_seed_pars_t *p);
 
+// What the builders of an index share (rawdtw_seed_host.cpp defines them; rawdtw_seed_build.hip is the second user): an entry of the
+// sketch, the table from entries grouped by hash with each hash's positions in the order ri_idx_get gives them, and an index's serial.
+struct Entry { uint32_t hash; uint64_t y; };
+int fill_table(rawdtw_seed_index *six, const std::vector<Entry> &a);
+uint64_t next_serial();
+
 } // namespace seed
 } // namespace rawdtw
 

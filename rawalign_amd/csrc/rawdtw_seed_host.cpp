@@ -31,6 +31,52 @@ int check_pars(const rawdtw_seed_pars_t *p)
     return RAWDTW_OK;
 }
 
+uint64_t next_serial()
+{
+    static std::atomic<uint64_t> n{0};
+    return ++n;
+}
+
+// the table from entries grouped by hash, each hash's positions in the order ri_idx_get gives them
+int fill_table(rawdtw_seed_index *six, const std::vector<Entry> &a)
+{
+    uint64_t n_keys = 0, n_multi = 0;
+    for (size_t j = 0; j < a.size();) {
+        size_t k = j + 1;
+        while (k < a.size() && a[k].hash == a[j].hash) k++;
+        n_keys++;
+        if (k - j > 1) n_multi += k - j;
+        j = k;
+    }
+    uint32_t lg = 4;
+    while (lg < 31 && (1ull << lg) < 2 * n_keys) lg++; // (2^31 slots: 32 GiB; the probe's slot number is 32 bits)
+    if ((1ull << lg) < 2 * n_keys) return RAWDTW_ERR_RANGE;
+    try {
+        six->slots.assign((size_t)1 << lg, Slot{0, 0, 0});
+        six->pos.clear();
+        six->pos.reserve(n_multi);
+    } catch (const std::bad_alloc &) { return RAWDTW_ERR_OOM; }
+    six->log2_slots = lg;
+    const uint32_t mask = (uint32_t)six->slots.size() - 1;
+    for (size_t j = 0; j < a.size();) {
+        size_t k = j + 1;
+        while (k < a.size() && a[k].hash == a[j].hash) k++;
+        uint32_t at = first_slot(a[j].hash, lg);
+        while (six->slots[at].count) at = (at + 1) & mask;
+        if (k - j > 0xffffffffull) return RAWDTW_ERR_RANGE;
+        Slot &s = six->slots[at];
+        s.key = a[j].hash; s.count = (uint32_t)(k - j);
+        if (k - j == 1) s.val = a[j].y;
+        else {
+            s.val = six->pos.size();
+            for (size_t t = j; t < k; t++) six->pos.push_back(a[t].y);
+        }
+        j = k;
+    }
+    six->n_keys = n_keys; six->n_positions = a.size();
+    return RAWDTW_OK;
+}
+
 } // namespace seed
 } // namespace rawdtw
 
@@ -123,12 +169,6 @@ template <typename F> void sketch(const rawdtw_seed_pars_t &p, const float *s, u
     else sketch_reg(p, s, len, emit);
 }
 
-uint64_t next_serial()
-{
-    static std::atomic<uint64_t> n{0};
-    return ++n;
-}
-
 const Slot *find(const rawdtw_seed_index *six, uint32_t hash)
 {
     if (six->slots.empty()) return nullptr;
@@ -138,48 +178,6 @@ const Slot *find(const rawdtw_seed_index *six, uint32_t hash)
         if (s.count == 0) return nullptr;
         if (s.key == hash) return &s;
     }
-}
-
-struct Entry { uint32_t hash; uint64_t y; };
-
-// the table from entries grouped by hash, each hash's positions in the order ri_idx_get gives them
-int fill_table(rawdtw_seed_index *six, const std::vector<Entry> &a)
-{
-    uint64_t n_keys = 0, n_multi = 0;
-    for (size_t j = 0; j < a.size();) {
-        size_t k = j + 1;
-        while (k < a.size() && a[k].hash == a[j].hash) k++;
-        n_keys++;
-        if (k - j > 1) n_multi += k - j;
-        j = k;
-    }
-    uint32_t lg = 4;
-    while (lg < 31 && (1ull << lg) < 2 * n_keys) lg++; // (2^31 slots: 32 GiB; the probe's slot number is 32 bits)
-    if ((1ull << lg) < 2 * n_keys) return RAWDTW_ERR_RANGE;
-    try {
-        six->slots.assign((size_t)1 << lg, Slot{0, 0, 0});
-        six->pos.clear();
-        six->pos.reserve(n_multi);
-    } catch (const std::bad_alloc &) { return RAWDTW_ERR_OOM; }
-    six->log2_slots = lg;
-    const uint32_t mask = (uint32_t)six->slots.size() - 1;
-    for (size_t j = 0; j < a.size();) {
-        size_t k = j + 1;
-        while (k < a.size() && a[k].hash == a[j].hash) k++;
-        uint32_t at = first_slot(a[j].hash, lg);
-        while (six->slots[at].count) at = (at + 1) & mask;
-        if (k - j > 0xffffffffull) return RAWDTW_ERR_RANGE;
-        Slot &s = six->slots[at];
-        s.key = a[j].hash; s.count = (uint32_t)(k - j);
-        if (k - j == 1) s.val = a[j].y;
-        else {
-            s.val = six->pos.size();
-            for (size_t t = j; t < k; t++) six->pos.push_back(a[t].y);
-        }
-        j = k;
-    }
-    six->n_keys = n_keys; six->n_positions = a.size();
-    return RAWDTW_OK;
 }
 
 bool by_hash_then_position(const Entry &a, const Entry &b) { return a.hash != b.hash ? a.hash < b.hash : a.y < b.y; }

@@ -392,6 +392,43 @@ class Engine:
         self._check(self.lib.rawdtw_reference_offset(self._ctx, seq, strand, C.byref(off)))
         return off.value
 
+    def reference_from_bases(self, seqs, pore, k: int, contracted: bool = True):
+        """rawdtw_reference_from_bases: upload_reference from bases (str, bytes or uint8 arrays) and a model of 4^k levels -- ri_seq_to_sig
+        for both strands of every sequence on the device, straight into the arena"""
+        from .refsig import as_bases
+
+        b = [as_bases(s) for s in seqs]
+        pore = _f32(pore)
+        if len(pore) < 4 ** int(k) and 1 <= int(k) <= 12:
+            raise ValueError("the model has 4^k levels")
+        n = len(b)
+        bp = (C.c_void_p * max(n, 1))(*[x.ctypes.data for x in b])
+        ln = np.array([len(x) for x in b] or [0], np.uint64)
+        self._check(self.lib.rawdtw_reference_from_bases(self._ctx, n, bp, _ptr(ln), _ptr(pore), int(k), int(bool(contracted))))
+        self._ref_lens = [max(len(x) - int(k) + 1, 0) for x in b]
+
+    def reference_fetch(self, seq: int, strand: int, length=None) -> np.ndarray:
+        """rawdtw_reference_fetch: one strand of the context's reference (`length`: the strand's, where the reference did not come
+        from reference_from_bases)"""
+        if length is None:
+            length = self._ref_lens[seq]
+        out = np.zeros(max(int(length), 1), np.float32)
+        self._check(self.lib.rawdtw_reference_fetch(self._ctx, int(seq), int(strand), _ptr(out), int(length)))
+        return out[:int(length)]
+
+    def reference_build_stats(self) -> dict:
+        """rawdtw_reference_build_stats: the most recent reference_from_bases -- steps of sum [0] and sum2 [1] that went fast and slow,
+        and the two launches' device time"""
+        fast, slow, ms = np.zeros(2, np.uint64), np.zeros(2, np.uint64), np.zeros(2, np.float32)
+        self._check(self.lib.rawdtw_reference_build_stats(self._ctx, _ptr(fast), _ptr(slow), _ptr(ms)))
+        return {"fast_steps": fast, "slow_steps": slow, "sums_ms": float(ms[0]), "write_ms": float(ms[1])}
+
+    def seed_build_stats(self) -> dict:
+        """rawdtw_seed_index_build_stats: the phases of the most recent SeedIndex.from_device on this engine, in ms"""
+        ms = np.zeros(5, np.float32)
+        self._check(self.lib.rawdtw_seed_index_build_stats(self._ctx, _ptr(ms)))
+        return dict(zip(("filter_ms", "emit_ms", "sort_ms", "home_ms", "fill_table_ms"), (float(x) for x in ms)))
+
     def set_reference_device(self, data_ptr: int, n_floats: int, keepalive=None):
         self._check(self.lib.rawdtw_set_reference_device(self._ctx, C.c_void_p(data_ptr), n_floats))
         self._keep_ref = keepalive

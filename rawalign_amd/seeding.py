@@ -70,6 +70,13 @@ class SeedIndex:
         _check(load_library().rawdtw_seed_index_load(index._h, C.byref(h)))
         return cls(h)
 
+    @classmethod
+    def from_device(cls, engine, pars=None) -> "SeedIndex":
+        """rawdtw_seed_index_build_device: from_signals of the arrays the engine's reference holds, built on the device (w = 0 only)"""
+        h = C.c_void_p()
+        engine._check(engine.lib.rawdtw_seed_index_build_device(engine._ctx, C.byref(_pars(pars)), C.byref(h)))
+        return cls(h)
+
     def get(self, hash_value: int) -> np.ndarray:
         """ri_idx_get: the packed positions id << 32 | pos << 1 | strand of a hash, in the index's order (empty: not there)"""
         p, n = C.c_void_p(), C.c_uint32()
