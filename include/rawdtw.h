@@ -79,41 +79,78 @@ int rawdtw_destroy(rawdtw_ctx *ctx);
 const char *rawdtw_last_error(const rawdtw_ctx *ctx);
 const char *rawdtw_status_string(int status);
 int rawdtw_sync(rawdtw_ctx *ctx);
-/* tuning knobs (results never depend on them; tests/test_gpu_parity.py checks that):
- *   "plan_threads"    host threads of the batch planner (0 = from the job count and the machine, <= 16)
- *   "serial_launches" 0/1: with side streams, run a batch's launches in sequence anyway
- *   "lane_max_radius" 0..3: largest post-slant radius on the tile kernel; "lane_max_n": longest side there
- *   "lane_hi", "lane_hi_max_n": optional second tile instance for radii up to 8
- *   "micro_max_n" 0/4/8, "grp16" 0/1, "grp8" 0/1, "full_wg" 0/1, "tile_lds_floats", "tile_max_jobs", "tile_max_spans",
- *   "tile_threads" 256/512/1024: kernel selection
- *   "sort_n", "sort_r1_n", "sort_r3", "sorted_tile_jobs": optional by-shape tiles for long / rare tile jobs (default off)
- *   "device_plan" 0/1, "device_plan_min_jobs": rawdtw_batch_create takes the sync-free path (planning on the device, in LDS)
- *   "stream_tile_radius" 1..3 (default 3), "stream_threads" 256/512, "stream_blocks_per_cu" (default 0 = as many as fit:
- *   4): the device-planned batch's DTW launch over the tiles' passes (k_runs) -- tiles (512 consecutive anchors) take radii up
- *   to stream_tile_radius, the radii between that and lane_max_radius are scored a lane per job from the side list, bucketed
- *   by length over the whole batch; a pass's LDS image is 5800 floats unless "tile_lds_floats" is given
- *   "wide_blocks" (default 256): workgroups of the side list's launch (k_wide); "wide_beside" 0/1 (default 0): that launch
- *   on the context's second stream beside the tiles' launch instead of in line (measured slower)
- *   "resident_arrays" 0/1: rawdtw_batch_create's anchors / ref_base / read_base are device pointers, used in place
- *   "time_plan" 0/1: event pair around a batch's planning kernels
- *   "merge_small" 0/1: a sparse batch's tile, 16-lane-row and register-wave kernels as ONE launch (default 1)
- *   "fold_mode" 0..4: chain fold as a wave per chain, a lane per chain with 16 / 32 parts per round, a lane per chain plus a
- *   wave for each chain of at least "fold_long_parts" (768) parts (3), or (default 4) device-planned batches fold and select
- *   in one launch out of LDS and job-list batches as 3; a batch keeps the form it was created under
- *   "debug_skip_kinds": timing experiments only -- launches of the masked kinds are not issued (results wrong)
- *   "tb_workspace_mb": the direction-buffer budget of one traceback sub-batch in MiB (rawdtw_traceback_batch*).  0 (the
- *   default): the environment variable RAWDTW_TB_WORKSPACE_MB if set, else 16 384.  A non-zero value goes before the
- *   variable, which is read at every call.  A call whose jobs' direction buffers (plus 256 bytes a job) pass the budget is
- *   cut, in job order, into sub-batches that each fit -- a job over the budget goes alone -- and these run as a two-deep
- *   pipeline; the results do not depend on the cut.
- * The environment variable RAWDTW_OPTS="name=value,..." applies options at rawdtw_create. */
+/* ---- options: a context's named integer settings.  Every one is listed here once, with the values it takes and its default, and is a row of
+ * rawalign_amd/csrc/rawdtw_options.h, which is where its rule lives.  rawdtw_set_option passes the value through the option's rule: a range
+ * written lo..hi CLAMPS a value outside it, a list a/b/c takes the largest entry that is at most the value (the first one below them all), 0/1
+ * stores value != 0, and `refuses' means RAWDTW_ERR_INVALID with nothing stored and the reason in rawdtw_last_error.  A name that is not
+ * listed, or is read-only, is refused with "unknown option NAME".
+ * Tuning knobs -- results never depend on them (tests/test_gpu_parity.py checks that):
+ *   "plan_threads"  0..64 (default 0 = from the job count and the machine, <= 16): host threads of the batch planner
+ *   "serial_launches"  0/1 (default 0): with side streams, run a batch's launches in sequence anyway
+ *   "lane_max_radius"  0..3 (default 3): largest post-slant radius on the tile kernel
+ *   "lane_max_n"  8..73 (default 73): longest side there
+ *   "lane_hi"  0/1 (default 0): an optional second tile instance for radii up to 8 ...
+ *   "lane_hi_max_n"  8..200 (default 96): ... and sides up to this
+ *   "micro_max_n"  0/4/8 (default 8): shapes with a longer side up to this take the micro paths
+ *   "grp16"  0/1 (default 1): bands of at most 16 offsets, four jobs a wave
+ *   "grp8"  0/1 (default 1): bands of at most 8 offsets, eight jobs a wave
+ *   "full_wg"  0/1 (default 1): full-matrix jobs of three strips and more, four waves a job
+ *   "tile_lds_floats"  1024..40000 (default 4800): the LDS image of a job-list tile; once given, also that of a device-planned batch's pass
+ *       (5800 otherwise)
+ *   "tile_max_jobs"  64..65535 (default 1024): jobs of a job-list tile
+ *   "tile_max_spans"  8..4096 (default 96): arena spans of a job-list tile
+ *   "tile_threads"  256/512/1024 (default 256): workgroup size of the tile kernel
+ *   "sort_n"  0..255 (default 0 = never): tile jobs with a longer side from this on are tiled by shape, not in job order
+ *   "sort_r1_n"  0..255 (default 0 = never): so are those of radius 1 with a longer side from this on
+ *   "sort_r3"  0/1 (default 0): and those of radius 3
+ *   "sorted_tile_jobs"  16..1024 (default 64): jobs of a by-shape tile
+ *   "merge_small"  0/1 (default 1): a sparse batch's tile, 16-lane-row and register-wave kernels as ONE launch
+ *   "fold_mode"  0..4 (default 4): chain fold as a wave per chain (0), a lane per chain with 16 / 32 parts per round (1, 2), a lane per chain
+ *       plus a wave for each long chain (3), or device-planned batches fold and select in one launch out of LDS and job-list batches as 3
+ *       (4); a batch keeps the form it was created under
+ *   "fold_long_parts"  1..2^30 (default 768): fold mode 3, the parts from which a chain is a long one
+ *   "device_plan"  0/1 (default 1): rawdtw_batch_create takes the sync-free path (planning on the device, in LDS)
+ *   "device_plan_min_jobs"  0.. (default 0): smaller batches go through the job list
+ *   "stream_tile_radius"  1..3 (default 3): the device-planned batch's tiles (512 consecutive anchors) take radii up to this; the radii between
+ *       it and "lane_max_radius" are scored a lane per job from the side list, bucketed by length over the whole batch
+ *   "stream_threads"  256/512 (default 256): workgroup size of that batch's DTW launch over the tiles' passes (k_runs)
+ *   "stream_blocks_per_cu"  0..16 (default 4; 0 = as many as fit): its workgroups a CU
+ *   "pass_pool"  -1..2^24 (default -1 = three a tile + 64): copy-order slots beyond one a tile; a batch that runs out is redone through the
+ *       job list (tests)
+ *   "wide_blocks"  1..65535 (default 256): workgroups of the side list's launch (k_wide)
+ *   "wide_beside"  0/1 (default 0): that launch on the context's second stream beside the tiles' launch instead of in line (measured slower)
+ *   "wide_order"  0..2 (default 0): that launch between the scan and the pass planning, in front of k_runs, or behind it
+ *   "wide_at_create"  0/1 (default 0): that launch goes out with a plain rawdtw_batch_create's planning too (the arenas stay as they are
+ *       until the run)
+ *   "resident_arrays"  0/1 (default 0): rawdtw_batch_create's anchors / ref_base / read_base are device pointers, used in place
+ *   "time_plan"  0/1 (default 0): event pair around a batch's planning kernels (rawdtw_batch_plan_ms)
+ *   "debug_skip_kinds"  a mask, cut to 32 bits (default 0): timing experiments only -- launches of the masked kinds are not issued (results wrong)
+ *   "debug_skip_tail"  a mask, cut to 32 bits (default 0): the same for a device-planned batch's fold (1) and select (2) launches
+ *   "stream_debug"  a mask, cut to 32 bits (default 0): k_runs' debug word
+ *   "tb_workspace_mb"  0..2^30 (default 0): the direction-buffer budget of one traceback sub-batch in MiB (rawdtw_traceback_batch*).  0: the
+ *       environment variable RAWDTW_TB_WORKSPACE_MB if set, else 16 384.  A non-zero value goes before the variable, which is read at
+ *       every call.  A call whose jobs' direction buffers (plus 256 bytes a job) pass the budget is cut, in job order, into sub-batches
+ *       that each fit -- a job over the budget goes alone -- and these run as a two-deep pipeline; the results do not depend on the cut.
+ * Opt-ins, each described beside the entry points it changes:
+ *   "seed_minimizer"  0/1 (default 0): see rawdtw_seed_begin
+ *   "chain_long_seeds"  0..2^20 (default 0): see rawdtw_chain_round
+ *   "chain_max_chains"  0..4096 (default 0), refuses any other value: see rawdtw_chain_round
+ *   "chain_decline_reads"  0 or 1 (default 0), refuses any other value: see rawdtw_chain_round_declined
+ *   "device_round_end"  0/1 (default 0): see rawdtw_batch_round_end_begin
+ *   "resident_chains"  0..2^20 (default 0): see rawdtw_batch_round_end_keep
+ *   "signal_cigar"  0 or 1 (default 0), refuses any other value: see rawdtw_mapper_round_signal_resident
+ *   "signal_events_cap"  0.. (default 0 = the mapper's guess): see rawdtw_mapper_round_signal_resident
+ * Read-only, computed by the library:
+ *   "tb_sub_batches"  read-only: the number of sub-batches of this context's most recent rawdtw_traceback_batch* call; 0 before any.  It is
+ *       known once the call has cut its jobs, before the first plan is built: a call refused while it plans (a banded job, say) reports
+ *       its cut all the same.
+ *   "round_end_kernel_us"  read-only: see rawdtw_batch_round_end_fetch
+ *   "round_keep_kernel_us"  read-only: see rawdtw_batch_round_keep_fetch
+ * The environment variable RAWDTW_OPTS="name=value,..." applies options at rawdtw_create through rawdtw_set_option; a pair it refuses is
+ * ignored.  RAWDTW_LANE_HI, RAWDTW_LANE_HI_MAX_N and RAWDTW_LANE_MAX_R are older spellings of their options, applied the same way before it. */
 int rawdtw_set_option(rawdtw_ctx *ctx, const char *name, int64_t value);
-/* The value of an option that callers pass on from one context to another ("chain_long_seeds": rawdtw_mapper_create gives its second
- * group's context the first one's), "seed_minimizer" and "tb_workspace_mb" as they were set, and the read-only
- *   "tb_sub_batches": the number of sub-batches of this context's most recent rawdtw_traceback_batch* call; 0 before any.
- *   It is known once the call has cut its jobs, before the first plan is built: a call refused while it plans (a banded
- *   job, say) reports its cut all the same.  rawdtw_set_option refuses the name.
- * RAWDTW_ERR_INVALID for any other name. */
+/* The value of any option above: a settable one as it is stored -- what rawdtw_set_option made of the value it was given, or the default --,
+ * a read-only one as the library computes it.  RAWDTW_ERR_INVALID for a null argument or any other name. */
 int rawdtw_get_option(const rawdtw_ctx *ctx, const char *name, int64_t *value);
 /* the ctx's hipStream_t, as void* (for event timing on the stream kernels run on) */
 int rawdtw_stream(rawdtw_ctx *ctx, void **stream);

@@ -62,12 +62,9 @@ int rawdtw_create(int device_ordinal, rawdtw_ctx **out)
         ok = hipStreamCreateWithFlags(&ctx->side[k], hipStreamNonBlocking) == hipSuccess &&
              hipEventCreateWithFlags(&ctx->ev_join[k], hipEventDisableTiming) == hipSuccess;
     if (!ok) { rawdtw_destroy(ctx); return RAWDTW_ERR_DEVICE; }
-    if (const char *e = getenv("RAWDTW_LANE_HI")) ctx->lane_hi = atoi(e) != 0;
-    if (const char *e = getenv("RAWDTW_LANE_HI_MAX_N")) ctx->lane_hi_max_n = (uint32_t)std::min(std::max(atoi(e), 8), 200);
-    if (const char *e = getenv("RAWDTW_LANE_MAX_R")) {
-        int v = atoi(e);
-        ctx->lane_max_radius = v < 0 ? 0 : (v > kMaxLaneRadius ? kMaxLaneRadius : v);
-    }
+    const char *const older[][2] = {{"RAWDTW_LANE_HI", "lane_hi"}, {"RAWDTW_LANE_HI_MAX_N", "lane_hi_max_n"}, {"RAWDTW_LANE_MAX_R", "lane_max_radius"}};
+    for (const auto &o : older) // (spellings from before RAWDTW_OPTS)
+        if (const char *e = getenv(o[0])) (void)rawdtw_set_option(ctx, o[1], atoi(e));
     if (const char *e = getenv("RAWDTW_CHAIN_MAX_SEEDS")) ctx->chain_max_seeds = (uint32_t)std::max(1l, strtol(e, nullptr, 10));
     if (const char *e = getenv("RAWDTW_OPTS")) { // "name=value,name=value": rawdtw_set_option for each (tuning runs)
         std::string all(e);
@@ -145,85 +142,24 @@ int rawdtw_sync(rawdtw_ctx *ctx)
 int rawdtw_set_option(rawdtw_ctx *ctx, const char *name, int64_t value)
 {
     if (!ctx || !name) return RAWDTW_ERR_INVALID;
-    if (!strcmp(name, "serial_launches")) { ctx->serial_launches = value != 0; return RAWDTW_OK; }
-    if (!strcmp(name, "tile_lds_floats")) { ctx->tile_lds_floats = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1024), kStreamMaxImageFloats); ctx->tile_lds_set = true; return RAWDTW_OK; }
-    if (!strcmp(name, "tile_max_jobs")) { ctx->tile_max_jobs = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 64), 65535); return RAWDTW_OK; }
-    if (!strcmp(name, "plan_threads")) { ctx->plan_threads = (int)std::min<int64_t>(std::max<int64_t>(value, 0), 64); return RAWDTW_OK; }
-    if (!strcmp(name, "debug_skip_kinds")) { ctx->debug_skip_kinds = (uint32_t)value; return RAWDTW_OK; }
-    if (!strcmp(name, "pass_pool")) { ctx->pass_pool = (int)std::min<int64_t>(std::max<int64_t>(value, -1), 1 << 24); return RAWDTW_OK; }
-    if (!strcmp(name, "wide_at_create")) { ctx->wide_at_create = value != 0; return RAWDTW_OK; }
-    if (!strcmp(name, "wide_order")) { ctx->wide_order = (int)std::min<int64_t>(std::max<int64_t>(value, 0), 2); return RAWDTW_OK; }
-    if (!strcmp(name, "wide_beside")) { ctx->wide_beside = value != 0; return RAWDTW_OK; }
-    if (!strcmp(name, "wide_blocks")) { ctx->wide_blocks = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1), 65535); return RAWDTW_OK; }
-    if (!strcmp(name, "debug_skip_tail")) { ctx->debug_skip_tail = (uint32_t)value; return RAWDTW_OK; }
-    if (!strcmp(name, "sort_n")) { ctx->sort_n = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 255); return RAWDTW_OK; }
-    if (!strcmp(name, "sort_r1_n")) { ctx->sort_r1_n = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 255); return RAWDTW_OK; }
-    if (!strcmp(name, "sort_r3")) { ctx->sort_r3 = value != 0; return RAWDTW_OK; }
-    if (!strcmp(name, "sorted_tile_jobs")) { ctx->sorted_tile_jobs = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 16), 1024); return RAWDTW_OK; }
-    if (!strcmp(name, "device_plan")) { ctx->device_plan = value != 0; return RAWDTW_OK; }
-    if (!strcmp(name, "device_plan_min_jobs")) { ctx->device_plan_min_jobs = (uint64_t)std::max<int64_t>(value, 0); return RAWDTW_OK; }
-    if (!strcmp(name, "stream_blocks_per_cu")) { ctx->stream_blocks_per_cu = (int)std::min<int64_t>(std::max<int64_t>(value, 0), 16); return RAWDTW_OK; }
-    if (!strcmp(name, "stream_threads")) { ctx->stream_threads = value >= 512 ? 512 : 256; return RAWDTW_OK; }
-    if (!strcmp(name, "stream_debug")) { ctx->stream_debug = (uint32_t)value; return RAWDTW_OK; }
-    if (!strcmp(name, "resident_arrays")) { ctx->resident_arrays = value != 0; return RAWDTW_OK; }
-    if (!strcmp(name, "time_plan")) { ctx->time_plan = value != 0; return RAWDTW_OK; }
-    if (!strcmp(name, "merge_small")) { ctx->merge_small = value != 0; return RAWDTW_OK; }
-    if (!strcmp(name, "fold_mode")) { ctx->fold_mode = (int)std::min<int64_t>(std::max<int64_t>(value, 0), 4); return RAWDTW_OK; }
-    if (!strcmp(name, "fold_long_parts")) { ctx->fold_long_parts = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1), 1 << 30); return RAWDTW_OK; }
-    if (!strcmp(name, "tile_threads")) { ctx->tile_threads = value >= 1024 ? 1024 : (value >= 512 ? 512 : 256); return RAWDTW_OK; }
-    if (!strcmp(name, "tile_max_spans")) { ctx->tile_max_spans = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 8), 4096); return RAWDTW_OK; }
-    if (!strcmp(name, "full_wg")) { ctx->full_wg = value != 0; return RAWDTW_OK; }
-    if (!strcmp(name, "grp16")) { ctx->grp16 = value != 0; return RAWDTW_OK; }
-    if (!strcmp(name, "grp8")) { ctx->grp8 = value != 0; return RAWDTW_OK; }
-    if (!strcmp(name, "micro_max_n")) { ctx->micro_max_n = value >= 8 ? 8 : (value >= 4 ? 4 : 0); return RAWDTW_OK; }
-    if (!strcmp(name, "lane_hi_max_n")) { ctx->lane_hi_max_n = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 8), 200); return RAWDTW_OK; }
-    if (!strcmp(name, "lane_hi")) { ctx->lane_hi = value != 0; return RAWDTW_OK; }
-    if (!strcmp(name, "lane_max_n")) { ctx->lane_max_n = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 8), kLaneMaxN); return RAWDTW_OK; }
-    if (!strcmp(name, "stream_tile_radius")) { ctx->stream_tile_radius = value < 1 ? 1 : (value > kMaxLaneRadius ? kMaxLaneRadius : (int)value); return RAWDTW_OK; }
-    if (!strcmp(name, "chain_long_seeds")) { ctx->chain_long_seeds = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 1 << 20); return RAWDTW_OK; }
-    if (!strcmp(name, "chain_max_chains")) { // (a count that sizes device arrays: a value outside its range is refused, not clamped)
-        if (value < 0 || value > 4096) return fail(ctx, RAWDTW_ERR_INVALID, "\"chain_max_chains\" is 0 (off) or 1 .. 4096");
-        ctx->chain_max_chains = (uint32_t)value;
-        return RAWDTW_OK;
-    }
-    if (!strcmp(name, "chain_decline_reads")) { // (an opt-in that changes what a chaining round returns: a value that is neither is refused)
-        if (value != 0 && value != 1) return fail(ctx, RAWDTW_ERR_INVALID, "\"chain_decline_reads\" is 0 (off) or 1");
-        ctx->chain_decline_reads = value == 1;
-        return RAWDTW_OK;
-    }
-    if (!strcmp(name, "seed_minimizer")) { ctx->seed_minimizer = value != 0; return RAWDTW_OK; }
-    if (!strcmp(name, "device_round_end")) { ctx->device_round_end = value != 0; return RAWDTW_OK; }
-    if (!strcmp(name, "resident_chains")) { ctx->resident_chains = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 1 << 20); return RAWDTW_OK; }
-    if (!strcmp(name, "signal_events_cap")) { ctx->signal_events_cap = (uint64_t)std::max<int64_t>(value, 0); return RAWDTW_OK; }
-    if (!strcmp(name, "signal_cigar")) { // (an opt-in that changes what a mapper accepts: a value that is neither is refused, not read as "on")
-        if (value != 0 && value != 1) return fail(ctx, RAWDTW_ERR_INVALID, "\"signal_cigar\" is 0 (off) or 1");
-        ctx->signal_cigar = value == 1;
-        return RAWDTW_OK;
-    }
-    if (!strcmp(name, "tb_workspace_mb")) { ctx->tb_workspace_mb = (uint64_t)std::min<int64_t>(std::max<int64_t>(value, 0), 1 << 30); return RAWDTW_OK; }
-    if (!strcmp(name, "lane_max_radius")) {
-        ctx->lane_max_radius = value < 0 ? 0 : (value > kMaxLaneRadius ? kMaxLaneRadius : (int)value);
-        return RAWDTW_OK;
-    }
-    return fail(ctx, RAWDTW_ERR_INVALID, std::string("unknown option ") + name);
+    std::string err;
+    const int st = opt::set(*ctx, name, value, err);
+    return st == RAWDTW_OK ? st : fail(ctx, st, err);
 }
+
+// the computed rows' values, in the rows' order
+static int64_t tb_sub_batches(const rawdtw_ctx *ctx) { return (int64_t)ctx->tb_sub_batches; }
+#define X(name) &name,
+static int64_t (*const kComputed[])(const rawdtw_ctx *) = {RAWDTW_COMPUTED_OPTIONS(X)};
+#undef X
 
 int rawdtw_get_option(const rawdtw_ctx *ctx, const char *name, int64_t *value)
 {
     if (!ctx || !name || !value) return RAWDTW_ERR_INVALID;
-    if (!strcmp(name, "chain_long_seeds")) { *value = ctx->chain_long_seeds; return RAWDTW_OK; }
-    if (!strcmp(name, "chain_max_chains")) { *value = ctx->chain_max_chains; return RAWDTW_OK; }
-    if (!strcmp(name, "chain_decline_reads")) { *value = ctx->chain_decline_reads ? 1 : 0; return RAWDTW_OK; }
-    if (!strcmp(name, "seed_minimizer")) { *value = ctx->seed_minimizer ? 1 : 0; return RAWDTW_OK; }
-    if (!strcmp(name, "device_round_end")) { *value = ctx->device_round_end ? 1 : 0; return RAWDTW_OK; }
-    if (!strcmp(name, "round_end_kernel_us")) { *value = round_end_kernel_us(ctx); return RAWDTW_OK; }
-    if (!strcmp(name, "resident_chains")) { *value = ctx->resident_chains; return RAWDTW_OK; }
-    if (!strcmp(name, "round_keep_kernel_us")) { *value = round_keep_kernel_us(ctx); return RAWDTW_OK; }
-    if (!strcmp(name, "signal_events_cap")) { *value = (int64_t)ctx->signal_events_cap; return RAWDTW_OK; }
-    if (!strcmp(name, "signal_cigar")) { *value = ctx->signal_cigar ? 1 : 0; return RAWDTW_OK; }
-    if (!strcmp(name, "tb_workspace_mb")) { *value = (int64_t)ctx->tb_workspace_mb; return RAWDTW_OK; }
-    if (!strcmp(name, "tb_sub_batches")) { *value = (int64_t)ctx->tb_sub_batches; return RAWDTW_OK; }
-    return RAWDTW_ERR_INVALID;
+    const opt::Row *r = opt::find(name);
+    if (!r) return RAWDTW_ERR_INVALID;
+    *value = r->load ? r->load(*ctx) : kComputed[r - opt::kRows - opt::kNumSettable](ctx);
+    return RAWDTW_OK;
 }
 
 int rawdtw_context_device(const rawdtw_ctx *ctx, int *device_ordinal)

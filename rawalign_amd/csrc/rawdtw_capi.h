@@ -1,6 +1,6 @@
 // rawdtw_capi.h -- what the translation units behind the C ABI (include/rawdtw.h) share: the records behind the opaque
 // handles, small helpers, and the planner's entry points.  Internal: nothing here is part of the ABI.
-//   rawdtw_capi.cpp       contexts, options, arenas, pinned memory, incremental event upload
+//   rawdtw_capi.cpp       contexts, options (their table: rawdtw_options.h), arenas, pinned memory, incremental event upload
 //   rawdtw_planner.cpp    the host planner of the job-list path, its launch sequences, rawdtw_plan_*, rawdtw_score_batch
 //   rawdtw_batch.cpp      candidate batches: the stream path's set-up (sync-free, planned on the device), the job-list form,
 //                         run / fetch / diagnostics, chunk rounds
@@ -22,6 +22,7 @@
 
 #include "rawdtw_internal.h"
 #include "rawdtw_keep_layout.h"
+#include "rawdtw_options.h"
 
 using namespace rawdtw;
 
@@ -63,7 +64,7 @@ struct RefHold {
     std::atomic<int> refs{1};
 };
 
-struct rawdtw_ctx {
+struct rawdtw_ctx : rawdtw::Options { // (every option is a field of Options: rawdtw_options.h)
     int device = 0;
     hipStream_t stream = nullptr;
     // side streams: independent launches of one batch run concurrently (fork/join around the main stream)
@@ -72,40 +73,14 @@ struct rawdtw_ctx {
     hipEvent_t ev_fork = nullptr, ev_join[kSide] = {nullptr, nullptr, nullptr};
     hipStream_t wide = nullptr;                 // sync-free batches: the side list's launch runs here, beside the tiles' launch
     hipEvent_t ev_wide_fork = nullptr, ev_wide_join = nullptr;
-    bool serial_launches = false;
     int n_side = 0; // side streams used to fork the launches of one batch (RAWDTW_SIDE_STREAMS, 0..kSide). 0: the
                     // launches of a batch run in sequence on its one stream and overlap comes from several batches in
                     // flight on several contexts (swept: best throughput and cleaner per-kernel timings)
-    uint32_t lane_hi_max_n = 96;
-    int micro_max_n = 8; // shapes with longer side <= this use the micro paths (0: none, 4: micro4 only)
-    bool grp16 = true; // bands of at most 16 offsets: four jobs per wave (else one job per wave)
-    bool grp8 = true;  // ... and of at most 8 offsets: eight jobs per wave
-    bool full_wg = true; // full-matrix jobs with >= 3 strips: four waves per job, pipelined strips
-    bool lane_hi = false; // radii 4..8 on the second tile-kernel instance (else on k_band_wreg<1>)
-    uint32_t tile_lds_floats = kTileLdsFloats, tile_max_jobs = kTileMaxJobs;
-    bool tile_lds_set = false;                  // "tile_lds_floats" was given: it also sizes the device-planned batches' tiles
-    uint32_t lane_max_n = kLaneMaxN;
-    uint32_t debug_skip_kinds = 0; // timing experiments: launches of these kinds are not issued (results are then wrong)
-    uint32_t debug_skip_tail = 0;  // timing experiments on the sync-free path: 1 no fold launch, 2 no select launch (results are then wrong)
-    uint32_t sort_n = 0, sort_r1_n = 0, sort_r3 = 0, sorted_tile_jobs = 64; // see PlanCfg
-    bool device_plan = true;  // rawdtw_batch_create takes the sync-free stream path (rawdtw_stream.hip) for sparse + banded batches
-    uint64_t device_plan_min_jobs = 0; // smaller batches go through the job list
     std::vector<StreamWs> ws_free;     // workspaces of destroyed batches, reused by the next ones (no hipMalloc in the steady state)
     uint32_t stream_lds = 0, stream_blocks = 0; // persistent grid of k_stream at the current tile size
-    int stream_threads = 256;                   // workgroup size of k_runs (256 or 512)
-    uint32_t wide_blocks = 256;                 // workgroups (four waves each) of the side list's launch
-    int pass_pool = -1;                         // copy-order slots beyond one a tile (tests: a batch that runs out is redone through the job list); -1: 3 a tile + 64
-    int wide_at_create = 0;                     // 1: also after a plain rawdtw_batch_create (the caller leaves the arenas alone until the run)
     bool in_submit = false;                     // inside rawdtw_batch_submit*: create and run are one call
-    int wide_order = 0;                         // 0: k_wide between the scan and the pass planning (first run), 1: in front of k_runs, 2: behind it
-    int wide_beside = 0;                        // 1: that launch on the context's second stream, beside the tiles' launch; 0: in line (measured:
-                                                // the fork and join cost the fresh-batch pipeline 8 % and the PCIe loop 17 %)
     int stream_threads_cached = 0;
-    int stream_blocks_per_cu = 4;               // 0: what the occupancy query gives; else at most this many (leaves room for other streams' kernels)
     int stream_bpc_cached = -1;
-    uint32_t stream_debug = 0;         // StreamArgs::debug
-    bool resident_arrays = false;      // rawdtw_batch_create: anchors / ref_base / read_base are DEVICE pointers (used in place)
-    bool time_plan = false;            // record an event pair around a batch's planning kernels (rawdtw_batch_plan_ms)
     std::vector<uint64_t> job_off_scratch;
     void *d_append = nullptr;          // rawdtw_events_append staging, grow-only
     size_t append_bytes = 0;
@@ -121,17 +96,7 @@ struct rawdtw_ctx {
     hipStream_t tb_copy = nullptr;                      // traceback: the paths' way home, beside the next sub-batch's kernels
     float tb_fill_ms = 0.f, tb_walk_ms = 0.f;          // device time of the most recent rawdtw_traceback_batch
     uint64_t tb_dir_written = 0, tb_path_elems = 0;
-    uint64_t tb_workspace_mb = 0; // "tb_workspace_mb": direction-buffer budget of a traceback sub-batch in MiB (0: RAWDTW_TB_WORKSPACE_MB, else 16 GiB)
     uint64_t tb_sub_batches = 0;  // "tb_sub_batches" (read-only): sub-batches of the most recent traceback call, known before its first plan is built
-    bool merge_small = true; // tile + 16-lane-row + register-wave launches of a batch as one launch (k_band_merged)
-    int fold_mode = 4; // 0: wave per chain, 1/2: lane per chain (16/32 parts per round; 30x less VALU work), 3: lanes + a wave for each long chain,
-                       // 4: sync-free batches fold and select in one launch out of LDS (k_fold_select), job-list batches as 3
-    uint32_t fold_long_parts = 768; // fold_mode 3: chains of at least this many parts are folded a wave each
-    int tile_threads = 256; // workgroup size of the tile kernel (256, 512, 1024)
-    uint32_t tile_max_spans = kTileMaxSpans;
-    int plan_threads = 0; // planner threads (0: from the job count and the machine, at most 16)
-    int lane_max_radius = kMaxLaneRadius; // radii above this go to the register-resident wave kernel (RAWDTW_LANE_MAX_R)
-    int stream_tile_radius = 3;           // device-planned batches: the tiles' radius limit ("stream_tile_radius")
     // reference arena.  An arena the library allocated (rawdtw_upload_reference, rawdtw_index_upload) is held through a
     // counted RefHold, shared by every context that adopted it with rawdtw_share_reference: it is freed when the last of
     // them lets go, so the owner may upload another reference or be destroyed while sharers still run on the old one.
@@ -159,15 +124,7 @@ struct rawdtw_ctx {
     struct rawdtw_seed_ws *seed_ws = nullptr;     // rawdtw_seed_index_upload's table and rawdtw_seed_begin's device block (rawdtw_seed.hip), grow-only
     struct rawdtw_round_end_ws *round_end_ws = nullptr; // rawdtw_round_end's device block (rawdtw_round_end.hip), grow-only
     struct rawdtw_keep_ws *keep_ws = nullptr;           // the store of kept chains and its launch's block (rawdtw_keep.hip), grow-only
-    uint32_t resident_chains = 0;  // "resident_chains": a mapper created with this context keeps a resident round's primary chains on the device, at most this many seeds a read (0: no)
-    bool device_round_end = false; // "device_round_end": a mapper created with this context ends its device-chained rounds on the device
     uint32_t chain_max_seeds = 0; // tests: RAWDTW_CHAIN_MAX_SEEDS lowers rawdtw_chain_round's cap on seeds a read, so that small rounds take the declined path (0: no)
-    uint32_t chain_long_seeds = 0; // "chain_long_seeds": reads above the cap with at most this many seeds are chained by rawdtw_chain.hip's long path (0: declined)
-    bool chain_decline_reads = false; // "chain_decline_reads": a read the device chaining cannot take is declined alone (rawdtw_chain_round_declined), not its round
-    uint32_t chain_max_chains = 0; // "chain_max_chains": a read with up to this many chains, ties or not, is ordered on the device by rawdtw_sort_order.h (0: 32 chains, 16 with ties)
-    bool seed_minimizer = false;   // "seed_minimizer": rawdtw_seed.hip seeds a w > 0 table on the device (k_seed_min) rather than refusing it
-    bool signal_cigar = false;     // "signal_cigar": a mapper created with this context takes --dtw-output-cigar through its rounds from signal; its finish reads the arena
-    uint64_t signal_events_cap = 0; // "signal_events_cap": the events_cap of a round from signal's first try (rawdtw_mapper.cpp; 0: the mapper's guess)
     std::string err;
 };
 

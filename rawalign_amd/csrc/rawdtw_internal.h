@@ -52,16 +52,13 @@ static_assert(sizeof(ChainDesc) == 24, "ChainDesc must stay 24 bytes");
 
 // (kMaxLaneRadius, kLaneMaxN -- the lane-per-job class -- are in rawdtw_plan_fmt.h: the records' widths depend on them)
 constexpr int kMaxLaneRadiusHi = 8;    // second tile-kernel instance: radii kMaxLaneRadius+1 .. 8
-// tile kernel: a tile = consecutive lane-eligible jobs whose windows fit this much LDS
-constexpr uint32_t kTileLdsFloats = 4800;  // job-list tile kernel: 8 workgroups per CU
+// (kTileLdsFloats, kTileMaxJobs, kTileMaxSpans -- the job-list tile kernel's tiles -- are in rawdtw_options.h: options' defaults)
 constexpr uint32_t kStreamTileFloats = 5800; // k_runs: image + the pass's records + two passes' copy orders = 29 KB a workgroup: five workgroups per
                                              // CU, and 13 KB of the CU's 160 KB stay free for a planner workgroup of the batches behind (at 7000 floats
                                              // and two record buffers it was four workgroups and 5 KB: nothing fitted beside them; the bench batch's
                                              // tiles average 5 200 floats: below 5 400 every other tile takes two passes and the planning doubles)
 static_assert(kStreamTileFloats <= kStreamMaxImageFloats, "the default image is one the option admits");
-constexpr uint32_t kTileMaxJobs = 1024;
 constexpr uint32_t kTileHiLdsFloats = 14336, kTileHiMaxJobs = 64; // wide-band instance: one wave per tile
-constexpr uint32_t kTileMaxSpans = 96;
 constexpr uint32_t kSpanGapFloats = 48; // a window starting this close behind a span extends it instead of opening a new one
 constexpr int kFullWgWaves = 4;        // waves per job in the pipelined-strip variant of the full-matrix kernel
 constexpr int kMaxWregChunks = 32;     // register-resident wave kernel: radius + 1 <= 64 * 32

@@ -546,25 +546,11 @@ void discard_chain_round(rawdtw_ctx *ctx)
     (void)rawdtw_chain_round_end(ctx, &a, &rb, &qb);
 }
 
-// "device_round_end" on the context the mapper was created with
-bool round_end_on_device(const rawdtw_mapper *m)
+// a context's option as the mapper reads it, through the public ABI: 0 for no context or a refusal
+int64_t ctx_option(const rawdtw_ctx *ctx, const char *name)
 {
     int64_t v = 0;
-    return m->ctx && rawdtw_get_option(m->ctx, "device_round_end", &v) == RAWDTW_OK && v != 0;
-}
-
-// "resident_chains" on the context the mapper was created with (0: off)
-uint32_t resident_chains_option(const rawdtw_mapper *m)
-{
-    int64_t v = 0;
-    return m->ctx && rawdtw_get_option(m->ctx, "resident_chains", &v) == RAWDTW_OK && v > 0 ? (uint32_t)v : 0u;
-}
-
-// "signal_cigar" on the context the mapper was created with
-bool signal_cigar_option(const rawdtw_mapper *m)
-{
-    int64_t v = 0;
-    return m->ctx && rawdtw_get_option(m->ctx, "signal_cigar", &v) == RAWDTW_OK && v != 0;
+    return ctx && rawdtw_get_option(ctx, name, &v) == RAWDTW_OK ? v : 0;
 }
 
 // a read's slot in its group's event arena: the group's context and the slot's first float
@@ -597,12 +583,21 @@ struct Round {
     // its reads' chunks ARE the segments, in order -- no copy into the mapper's own staging (a third of the host phase)
     bool events_in_place = on_device && m->opt.device_chain && G == 1 && event_off[n_reads] > 0 && rawdtw_host_is_page_locked(events) == 1;
     std::vector<RoundRead> rr = std::vector<RoundRead>(n_reads);
-    struct PerGroup { bool chaining = false; uint64_t ns = 0, nev = 0, nseg = 0, scored = 0, reused = 0, extra = 0; // (ns: seeds sent up; extra: other bytes)
+    struct GroupOpt { bool decline_reads = false; uint32_t max_chains = 0; }; // the group's context's "chain_decline_reads" and "chain_max_chains"
+    static GroupOpt group_opt(const rawdtw_mapper *m, size_t gi)
+    {
+        const rawdtw_ctx *ctx = gi < m->groups.size() ? m->groups[gi].ctx : nullptr;
+        return GroupOpt{ctx_option(ctx, "chain_decline_reads") != 0, (uint32_t)ctx_option(ctx, "chain_max_chains")};
+    }
+    struct PerGroup { GroupOpt opt; // (read once, when the round is built: a phase that starts the group's record over keeps it)
+                      bool chaining = false; uint64_t ns = 0, nev = 0, nseg = 0, scored = 0, reused = 0, extra = 0; // (ns: seeds sent up; extra: other bytes)
                       bool round_end = false; uint64_t re_reads = 0, re_declined = 0; // (the round's end enqueued on the device; the reads it ended / declined)
                       bool keep = false;                                              // (... and the keep launch behind it)
-                      uint64_t dc_reads = 0, dc_seeds = 0, dc_chains = 0, dc_device = 0, dc_bytes = 0; } per[2]; // ("chain_decline_reads": the reads declined alone, by reason; the others; seed bytes home)
-    bool device_round_end = round_end_on_device(m); // (read once a round)
-    uint32_t resident_chains = resident_chains_option(m); // (so is this)
+                      uint64_t dc_reads = 0, dc_seeds = 0, dc_chains = 0, dc_device = 0, dc_bytes = 0; // ("chain_decline_reads": the reads declined alone, by reason; the others; seed bytes home)
+    } per[2] = {{group_opt(m, 0)}, {group_opt(m, 1)}};
+    const GroupOpt &opt_of(const Group &g) const { return per[&g - m->groups.begin()].opt; }
+    bool device_round_end = ctx_option(m->ctx, "device_round_end") != 0;         // (the mapper's own context's, read once a round)
+    uint32_t resident_chains = (uint32_t)ctx_option(m->ctx, "resident_chains"); // (so is this)
     // the round takes previous seeds from the store of kept chains and keeps its own there: a resident round with the option on whose end
     // is enqueued on the device
     bool use_store() const { return resident && resident_chains != 0 && device_round_end && runs_dtw; }
@@ -612,7 +607,6 @@ struct Round {
     MRead &read(uint32_t k) const { return m->reads[read_ids[k]]; }
     uint32_t arena_base(const MRead &rd) const { return (G == 2 ? rd.slot / 2 : rd.slot) * m->opt.slot_events; } // its slot in its group's event arena
     bool ok() const { return status == RAWDTW_OK; }
-    static bool decline_reads(const Group &g) { int64_t v = 0; return rawdtw_get_option(g.ctx, "chain_decline_reads", &v) == RAWDTW_OK && v != 0; }
     void failed(int st, const std::string &s) { if (ok()) { status = st; msg = s; } }
     void lap(int slot) { const double t = now_ms(); m->timing[slot] += t - t0; t0 = t; } // (include/rawdtw.h: rawdtw_mapper_timing)
 
@@ -648,8 +642,7 @@ struct Round {
         g.hw_new = std::max(g.hw_new, n.new_anchors); g.hw_events = std::max(g.hw_events, n.events); g.hw_seg = std::max(g.hw_seg, n.seg);
         g.hw_seeds = std::max(g.hw_seeds, n.seeds);
         if (dev) { // the device's cap on chains a read: 32, or "chain_max_chains" -- then no more than the seeds can make, min_num_anchors a chain
-            int64_t many = 0;
-            (void)rawdtw_get_option(g.ctx, "chain_max_chains", &many);
+            const uint32_t many = opt_of(g).max_chains;
             const uint64_t by_seeds = g.hw_seeds / (uint64_t)std::max(1, m->opt.chain.min_num_anchors) + 1;
             g.hw_chains = std::max<uint64_t>(g.hw_chains, many > 0 ? std::min<uint64_t>(g.hw_reads * (uint64_t)many, by_seeds) : g.hw_reads * 32);
         }
@@ -729,7 +722,7 @@ struct Round {
         lap(2);
         if (declined && st == RAWDTW_ERR_UNSUPPORTED) return false;
         if (st != RAWDTW_OK) { failed(st, rawdtw_last_error(g.ctx)); return true; }
-        per[gi] = PerGroup{true, n.seeds, n.events, n.seg};
+        per[gi] = PerGroup{per[gi].opt, true, n.seeds, n.events, n.seg};
         return true;
     }
 
@@ -847,7 +840,7 @@ struct Round {
         if (st != RAWDTW_OK) return failed(st, rawdtw_last_error(g.ctx));
         res_prev = np;
         // (beside the chaining's own arrays: prev_off, chunk_start, sits_out; the seeding's offsets and source starts)
-        per[gi] = PerGroup{true, np, nev, nseg, 0, 0, (nr + 1) * 8 + nr * 5 + (nr + 1) * 8 + nr * 8};
+        per[gi] = PerGroup{per[gi].opt, true, np, nev, nseg, 0, 0, (nr + 1) * 8 + nr * 5 + (nr + 1) * 8 + nr * 8};
     }
 
     // "resident_chains": the context's store reserved for every slot of the mapper at the first round that uses it, and this round's
@@ -905,7 +898,7 @@ struct Round {
         // "chain_decline_reads": the reads the device declined alone are chained here, their chains appended behind the device's
         uint64_t nd = 0;
         const uint64_t *batch_off = ra.chain_off.p, *batch_aoff = ra.anchor_off.p;
-        if (decline_reads(g)) {
+        if (opt_of(g).decline_reads) {
             if (!append_declined(gi, &nd, &d_anchors, &d_ref_base, &d_read_base)) return;
             if (nd) { batch_off = ra.chain_off_ext.p; batch_aoff = ra.anchor_off_ext.p; }
         }
@@ -1350,15 +1343,8 @@ int rawdtw_mapper_create(rawdtw_ctx *ctx, const rawdtw_mapper_opt_t *opt, uint32
         st = rawdtw_context_device(ctx, &dev);
         if (st == RAWDTW_OK) st = rawdtw_create(dev, &m->groups[1].ctx);
         if (st == RAWDTW_OK) { m->groups[1].own_ctx = true; st = rawdtw_share_reference(m->groups[1].ctx, ctx); }
-        int64_t chain_long = 0; // (both groups chain the same reads on the device)
-        if (st == RAWDTW_OK) st = rawdtw_get_option(ctx, "chain_long_seeds", &chain_long);
-        if (st == RAWDTW_OK) st = rawdtw_set_option(m->groups[1].ctx, "chain_long_seeds", chain_long);
-        int64_t chain_many = 0;
-        if (st == RAWDTW_OK) st = rawdtw_get_option(ctx, "chain_max_chains", &chain_many);
-        if (st == RAWDTW_OK) st = rawdtw_set_option(m->groups[1].ctx, "chain_max_chains", chain_many);
-        int64_t chain_decline = 0;
-        if (st == RAWDTW_OK) st = rawdtw_get_option(ctx, "chain_decline_reads", &chain_decline);
-        if (st == RAWDTW_OK) st = rawdtw_set_option(m->groups[1].ctx, "chain_decline_reads", chain_decline);
+        for (const char *name : {"chain_long_seeds", "chain_max_chains", "chain_decline_reads"}) // (both groups chain the same reads on the device)
+            if (st == RAWDTW_OK) st = rawdtw_set_option(m->groups[1].ctx, name, ctx_option(ctx, name));
     }
     const uint64_t per_group = ((uint64_t)opt->max_reads + (uint64_t)m->opt.groups - 1) / (uint64_t)m->opt.groups;
     for (Group &g : m->groups)
@@ -1511,12 +1497,6 @@ int rawdtw_mapper_round(rawdtw_mapper *m, uint32_t n_reads, const uint32_t *read
     return r.run([&r](uint32_t gi) { r.begin_group(gi); });
 }
 
-static bool minimizer_on_device(const rawdtw_ctx *ctx)
-{
-    int64_t v = 0;
-    return rawdtw_get_option(ctx, "seed_minimizer", &v) == RAWDTW_OK && v != 0;
-}
-
 // what every seeded round asks of its index: one that can be read (its parameters out) and holds the mapper's sequences
 static int seed_index_checks(rawdtw_mapper *m, const rawdtw_seed_index *six, rawdtw_seed_pars_t *pars)
 {
@@ -1530,7 +1510,7 @@ static int seed_index_checks(rawdtw_mapper *m, const rawdtw_seed_index *six, raw
 // later either, which the --dtw-output-cigar traceback (rawdtw_mapper_finish) would
 static bool resident_round_ok(const rawdtw_mapper *m, const rawdtw_seed_pars_t &pars, bool no_cigar)
 {
-    return m->ctx && !m->scorer && m->opt.device_chain && m->groups.size() == 1 && (pars.w == 0 || minimizer_on_device(m->ctx)) &&
+    return m->ctx && !m->scorer && m->opt.device_chain && m->groups.size() == 1 && (pars.w == 0 || ctx_option(m->ctx, "seed_minimizer") != 0) &&
            !(no_cigar && (m->opt.flag & 0x4));
 }
 
@@ -1543,7 +1523,7 @@ int rawdtw_mapper_round_seeded(rawdtw_mapper *m, const rawdtw_seed_index *six, u
     rawdtw_seed_pars_t pars;
     if (const int st = seed_index_checks(m, six, &pars)) return st;
     if (n_reads == 0) return RAWDTW_OK;
-    const bool on_device = m->ctx && (pars.w == 0 || minimizer_on_device(m->ctx)); // (the minimizer sketch is the host's unless "seed_minimizer" is on)
+    const bool on_device = m->ctx && (pars.w == 0 || ctx_option(m->ctx, "seed_minimizer") != 0); // (the minimizer sketch is the host's unless "seed_minimizer" is on)
     if (!seed_room(m, m->seed_off, (uint64_t)n_reads + 1)) return fail(m, RAWDTW_ERR_OOM, "no memory for the round's hit offsets");
     if (!on_device) {
         int st = rawdtw_seed_hits_host(six, n_reads, event_off, events, m->seed_off.p, nullptr, 0, m->opt.threads); // (counts)
@@ -1616,7 +1596,7 @@ int round_from_signal(rawdtw_mapper *m, const rawdtw_seed_index *six, const rawd
     // rawdtw_mapper_round_seeded_resident's preconditions, and nothing may read the host's copy of a read's events later: that is the
     // --dtw-output-cigar traceback and an external scorer.  A mapper with no DTW stage keeps the copy for neither.
     // With the context's "signal_cigar" on (read once a round) the traceback reads the arena instead, and flag 0x4 alone refuses nothing.
-    const bool cigar_from_arena = signal_cigar_option(m);
+    const bool cigar_from_arena = ctx_option(m->ctx, "signal_cigar") != 0;
     if (!resident_round_ok(m, pars, !cigar_from_arena))
         return fail(m, RAWDTW_ERR_UNSUPPORTED, cigar_from_arena
                         ? "a round from signal needs a context, device chaining, one read group, no external scorer and a w == 0 index, or a w > 0 one "
@@ -1642,8 +1622,7 @@ int round_from_signal(rawdtw_mapper *m, const rawdtw_seed_index *six, const rawd
     // events_cap, the first guess: what the seeding's workspace holds already, or a quarter of the samples; a round with more says how many and
     // runs once more (as rawdtw_mapper_round_seeded does for its hits)
     const uint64_t n_samples = off[n_reads] - off[0];
-    int64_t first_cap = 0;
-    (void)rawdtw_get_option(m->ctx, "signal_events_cap", &first_cap);
+    const int64_t first_cap = ctx_option(m->ctx, "signal_events_cap");
     uint64_t cap = first_cap > 0 ? (uint64_t)first_cap : std::max<uint64_t>(m->sig_cap, n_samples / 4 + 1024);
     uint64_t total = 0;
     bool retried = false;

@@ -14,20 +14,9 @@ namespace capi {
 // checked without a GPU (rawdtw_plan_dry_run) and spread over threads: at the bench's 5 M jobs per
 // mini-batch a one-thread planner costs a thousand times the kernels it feeds.
 
-struct PlanCfg {
+struct PlanCfg : Options { // (the planner reads the rows flagged kPlanner: rawdtw_options.h)
     uint64_t n_ev = 0, n_ref = 0;
-    int lane_max_radius = kMaxLaneRadius;
-    uint32_t lane_max_n = kLaneMaxN, lane_hi_max_n = 96;
-    bool lane_hi = false, grp16 = true, grp8 = true, full_wg = true;
-    int micro_max_n = 8;
-    uint32_t tile_lds_floats = kTileLdsFloats, tile_max_jobs = kTileMaxJobs, tile_max_spans = kTileMaxSpans;
     int threads = 0; // 0: pick from the job count and the machine
-    // Optional: tile-eligible jobs that are rare inside a tile (long, or of a radius few neighbours share) leave the job
-    // order and are tiled by shape instead: longer side >= sort_n, radius 1 with longer side >= sort_r1_n, radius 3
-    // (0 = never).  Measured on the bench workload with sort_n = 17: the tile kernel's VALU work drops 40 % (full waves of
-    // one shape), but every such job then fetches its own cache lines (+130 MB of scattered reads per batch); alone the
-    // kernel breaks even, with several batches in flight throughput falls 5-15 %.  Off by default.
-    uint32_t sort_n = 0, sort_r1_n = 0, sort_r3 = 0, sorted_tile_jobs = 64;
 };
 
 // tile records built on the host (uploaded by build_plan)
@@ -41,12 +30,8 @@ struct HostTiles {
 PlanCfg cfg_of(const rawdtw_ctx *ctx)
 {
     PlanCfg c;
-    c.n_ev = ctx->n_ev; c.n_ref = ctx->n_ref;
-    c.lane_max_radius = ctx->lane_max_radius; c.lane_max_n = ctx->lane_max_n; c.lane_hi_max_n = ctx->lane_hi_max_n;
-    c.lane_hi = ctx->lane_hi; c.grp16 = ctx->grp16; c.grp8 = ctx->grp8; c.full_wg = ctx->full_wg; c.micro_max_n = ctx->micro_max_n;
-    c.tile_lds_floats = ctx->tile_lds_floats; c.tile_max_jobs = ctx->tile_max_jobs; c.threads = ctx->plan_threads;
-    c.tile_max_spans = ctx->tile_max_spans;
-    c.sort_n = ctx->sort_n; c.sort_r1_n = ctx->sort_r1_n; c.sort_r3 = ctx->sort_r3; c.sorted_tile_jobs = ctx->sorted_tile_jobs;
+    static_cast<Options &>(c) = *ctx;
+    c.n_ev = ctx->n_ev; c.n_ref = ctx->n_ref; c.threads = ctx->plan_threads;
     return c;
 }
 
@@ -795,22 +780,7 @@ int rawdtw_plan_dry_run(uint64_t n_events, uint64_t n_reference, const rawdtw_jo
         const char *nm = option_names[i];
         const int64_t v = option_values[i];
         if (!strcmp(nm, "verify")) verify = v != 0; // dry run only: skip the self-check (to time the planner alone)
-        else if (!strcmp(nm, "tile_lds_floats")) cfg.tile_lds_floats = (uint32_t)std::min<int64_t>(std::max<int64_t>(v, 1024), 40000);
-        else if (!strcmp(nm, "tile_max_jobs")) cfg.tile_max_jobs = (uint32_t)std::min<int64_t>(std::max<int64_t>(v, 64), 65535);
-        else if (!strcmp(nm, "tile_max_spans")) cfg.tile_max_spans = (uint32_t)std::min<int64_t>(std::max<int64_t>(v, 8), 4096);
-        else if (!strcmp(nm, "sort_n")) cfg.sort_n = (uint32_t)std::min<int64_t>(std::max<int64_t>(v, 0), 255);
-        else if (!strcmp(nm, "sort_r1_n")) cfg.sort_r1_n = (uint32_t)std::min<int64_t>(std::max<int64_t>(v, 0), 255);
-        else if (!strcmp(nm, "sort_r3")) cfg.sort_r3 = v != 0;
-        else if (!strcmp(nm, "sorted_tile_jobs")) cfg.sorted_tile_jobs = (uint32_t)std::min<int64_t>(std::max<int64_t>(v, 16), 1024);
-        else if (!strcmp(nm, "full_wg")) cfg.full_wg = v != 0;
-        else if (!strcmp(nm, "grp16")) cfg.grp16 = v != 0;
-        else if (!strcmp(nm, "grp8")) cfg.grp8 = v != 0;
-        else if (!strcmp(nm, "micro_max_n")) cfg.micro_max_n = v >= 8 ? 8 : (v >= 4 ? 4 : 0);
-        else if (!strcmp(nm, "lane_hi")) cfg.lane_hi = v != 0;
-        else if (!strcmp(nm, "lane_hi_max_n")) cfg.lane_hi_max_n = (uint32_t)std::min<int64_t>(std::max<int64_t>(v, 8), 200);
-        else if (!strcmp(nm, "lane_max_n")) cfg.lane_max_n = (uint32_t)std::min<int64_t>(std::max<int64_t>(v, 8), kLaneMaxN);
-        else if (!strcmp(nm, "lane_max_radius")) cfg.lane_max_radius = v < 0 ? 0 : (v > kMaxLaneRadius ? kMaxLaneRadius : (int)v);
-        else { say(std::string("unknown option ") + nm); return RAWDTW_ERR_INVALID; }
+        else if (std::string err; opt::set(cfg, nm, v, err, opt::kPlanner) != RAWDTW_OK) { say(err); return RAWDTW_ERR_INVALID; }
     }
     rawdtw_plan pl;
     HostTiles ht;

@@ -279,7 +279,8 @@ class Engine:
         self._check(self.lib.rawdtw_set_option(self._ctx, name.encode(), int(value)))
 
     def get_option(self, name: str) -> int:
-        """rawdtw_get_option: the options that can be read back, and the read-only "tb_sub_batches" """
+        """rawdtw_get_option: any option of include/rawdtw.h's option block -- a settable one as it is stored (what set_option made of its
+        value, or the default), and the read-only "tb_sub_batches", "round_end_kernel_us" and "round_keep_kernel_us" """
         v = C.c_int64()
         self._check(self.lib.rawdtw_get_option(self._ctx, name.encode(), C.byref(v)))
         return int(v.value)
