@@ -106,7 +106,7 @@ int rawdtw_sync(rawdtw_ctx *ctx);
  *   "sorted_tile_jobs"  16..1024 (default 64): jobs of a by-shape tile
  *   "merge_small"  0/1 (default 1): a sparse batch's tile, 16-lane-row and register-wave kernels as ONE launch
  *   "fold_mode"  0..4 (default 4): chain fold as a wave per chain (0), a lane per chain with 16 / 32 parts per round (1, 2), a lane per chain
- *       plus a wave for each long chain (3), or device-planned batches fold and select in one launch out of LDS and job-list batches as 3
+ *       plus a wave for each long chain (3), or device-planned batches fold and select in one launch (a read a lane) and job-list batches as 3
  *       (4); a batch keeps the form it was created under
  *   "fold_long_parts"  1..2^30 (default 768): fold mode 3, the parts from which a chain is a long one
  *   "device_plan"  0/1 (default 1): rawdtw_batch_create takes the sync-free path (planning on the device, in LDS)

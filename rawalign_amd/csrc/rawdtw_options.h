@@ -64,7 +64,7 @@ enum Flags : uint32_t {
     X(merge_small, bool, true, RAWDTW_OPT_FLAG, 0)                     /* tile + 16-lane-row + register-wave launches of a batch as one launch (k_band_merged) */ \
     X(tile_threads, int, 256, RAWDTW_OPT_SNAP(256, 512, 1024), 0)      /* workgroup size of the tile kernel */ \
     /* 0: wave per chain, 1/2: lane per chain (16/32 parts per round; 30x less VALU work), 3: lanes + a wave for each long chain, */ \
-    /* 4: sync-free batches fold and select in one launch out of LDS (k_fold_select), job-list batches as 3 */ \
+    /* 4: sync-free batches fold and select in one launch, a read a lane (k_fold_select), job-list batches as 3 */ \
     X(fold_mode, int, 4, RAWDTW_OPT_CLAMP(0, 4), 0) \
     X(fold_long_parts, uint32_t, 768, RAWDTW_OPT_CLAMP(1, 1 << 30), 0) /* fold_mode 3: chains of at least this many parts are folded a wave each */ \
     X(debug_skip_kinds, uint32_t, 0, RAWDTW_OPT_RAW, 0)                /* timing experiments: launches of these kinds are not issued (results are then wrong) */ \

@@ -26,7 +26,8 @@
 //   k_gather       chunk rounds only (rawdtw_batch_submit_carry): the lists above are then the round's SHORT lists (new entries +
 //                  one junction a chain); this launch lays every chain's costs out in full -- the stretch taken over from the
 //                  previous batch's cost array, then the new parts' -- for the fold
-//   k_fold_select  fold (rmap.cpp:279-280, 306) and accept / cut loop (rmap.cpp:515-524) out of LDS, a wave per 8 reads
+//   k_fold_select  fold (rmap.cpp:279-280, 306) and accept / cut loop (rmap.cpp:515-524): two waves per 64 reads, a read a lane --
+//                  one wave folds the reads' first chains, the other the rest
 //
 // No step needs a number on the host: grids are sized by the anchor count or are persistent, every count lives in a
 // device counter block.  rawdtw_batch_create only enqueues; errors and the rare shapes this path does not take (band wider
@@ -985,9 +986,10 @@ __device__ __forceinline__ uint32_t next_tile(const StreamArgs &a, const uint32_
 
 // k_wide: the side list -- the one part in two hundred whose band the lane bodies of the tiles do not take -- as a launch of
 // its own (inside k_runs its waves kept a third of the workgroups from the tiles for a third of the launch): wave-
-// cooperative jobs, longest first, dealt over the waves of the grid.  It needs no LDS and ends with its longest job
-// (a wave per job: 163 ns a column).  In line on the batch's stream, between the scan and the pass planning
-// (rawdtw_batch.cpp: stream_wide_fork; on a second stream beside the tiles it cost more in fork / join than it hid).
+// cooperative jobs, longest first, dealt over the waves of the grid.  Its LDS is the wave-per-job bands' operand windows
+// (s_w: kWbandLdsFloats a wave) and the workgroup's item counter; it ends with its longest job (a wave per job: 163 ns a
+// column).  In line on the batch's stream, between the scan and the pass planning -- in front of the tiles' launch, not
+// beside it (rawdtw_batch.cpp: stream_wide_fork; on a second stream beside the tiles it cost more in fork / join than it hid).
 __global__ __launch_bounds__(256) void k_wide(const StreamArgs a)
 {
     const uint32_t dbg = a.debug;
@@ -999,7 +1001,7 @@ __global__ __launch_bounds__(256) void k_wide(const StreamArgs a)
     // (a batch the scan declined is redone through the job list)
     if (a.cnt[kCntBad] != ~0ull || a.cnt[kCntUnsupported] != 0ull || a.cnt[kCntOthers] > a.others_cap) return;
     // ---- the side list: wave-cooperative jobs dealt over ALL waves of the grid, wave-per-job classes (longest first) to the
-    // first waves: a long job starts at once and runs next to the tiles instead of behind them ----
+    // first waves: a long job starts at once, and the launch ends with the short items instead of with one long job ----
     if (!(dbg & 4u)) {
         uint64_t n_w = 0;
 #pragma unroll
@@ -1372,132 +1374,124 @@ __global__ __launch_bounds__(kT) void k_events_gather(const float *__restrict__ 
 
 // ---------------------------------------------------------------------------------------------------------------------
 // k_fold_select: the fold of align_chain (rmap.cpp:238-306) and the accept/cut loop of gen_chains (rmap.cpp:515-524) for
-// kFoldReads consecutive reads a wave.  A sync-free batch keeps one cost per ANCHOR (part p of a chain at out[a1 - 2 - p]),
-// and a read's chains are consecutive stretches of the anchor list.  The wave sweeps its reads' stretch from the top down
-// in windows of kFoldWin floats: a window comes into LDS in whole 16-byte pieces (coalesced), then every lane folds the
-// parts of its chain that lie in the window -- in the reference's order, one packed fp32 add a part (the fold is
-// inherently sequential) -- and carries its sums into the next window.  Going down the addresses meets the chains last to
-// first and every chain's parts first to last, so a lane with several chains (more than 64 chains a wave) finishes one
-// before it meets the next, and a chain of any length is folded out of LDS.  The first lanes then run their reads'
-// accept/cut loops over scores that never left the workgroup.
-// (The lane-per-chain fold over the arena read 4 bytes a lane from 64 different lines per instruction and needed the chains
-// sorted by length -- a one-workgroup sort on the scan's critical path; this one needs no order.)
+// kFoldReads consecutive reads a workgroup of two waves: lane l of both waves belongs to read r0 + l.  A sync-free batch
+// keeps one cost per ANCHOR (part p of a chain at out[a1 - 2 - p]); a lane folds a chain straight from that array, in the
+// reference's order (the fold is inherently sequential: two dependent fp32 adds a part).  Wave 0 folds every read's FIRST
+// chain, wave 1 the read's other chains one after the other: the chains arrive sorted by chaining score (rmap.cpp:509-530),
+// so the first is the long one and the lanes of a wave have similar work -- nothing but the speed depends on that order.
+// After one barrier, lane l of wave 1 runs read l's accept/cut loop: the first chain's score and gate come from wave 0
+// through LDS, the others' from a small LDS cache of the lane's own (beyond its capacity from memory).
+// (The windowed form before -- a wave sweeps 8 reads' stretch through LDS in windows of 2 048 costs, a chain a lane -- issued
+// its inner loop for the longest segment in the window with a handful of lanes busy: twenty times the instructions the
+// adds need.  profiles/fold_lanes.json has both forms' lane occupancy.)
 // ---------------------------------------------------------------------------------------------------------------------
-// (windows of 2 048 floats: 10 KB of LDS a workgroup -- a fold workgroup of the batch in front fits into the 13 KB five workgroups of
-// k_runs leave on a CU; at 4 096 the launch alone is a quarter faster and the pipeline half a per cent slower, at 1 024 both are slower)
-constexpr uint32_t kFoldReads = 8, kFoldWin = 2048, kFoldCap = 256;
-__global__ __launch_bounds__(64) void k_fold_select(const StreamArgs a, const ChainDesc *__restrict__ chains, const uint64_t *__restrict__ chain_off,
-                                                    const uint64_t n_reads, const float bonus, const int fused, const float min_score,
-                                                    float *__restrict__ full_score, float *__restrict__ att_last, float *__restrict__ score,
-                                                    uint8_t *__restrict__ keep)
+// kFoldCache: chains behind the first whose {score, gate} the lane keeps in LDS (the bench batch has 2.4 chains a read):
+// 4.5 KB of LDS a workgroup.  A lane has two rounds of sixteen parts on their way while it adds a third: the launch runs
+// at the latency of its longest chain's loads, not at its 32 adds a round (three buffers are what 80 registers hold).
+constexpr uint32_t kFoldReads = 64, kFoldCache = 8;
+
+// One chain by one lane: {score, gate}.  gate: the attainable sum before the last (or only) DTW call (rmap.cpp:265-268);
+// a chain without a part has no check.  Every address read is a part of this chain: single parts until the address ends a
+// 16-byte piece, then whole pieces while sixteen parts of the body remain -- a piece never reaches below the chain's last
+// part or above its first, so none leaves the cost array at anchor 0 or at the list's end, whatever the array's length.
+__device__ __forceinline__ v2f fold_chain(const float *__restrict__ out, const ChainDesc &d, const float bonus, const int fused)
 {
-    __shared__ __attribute__((aligned(16))) float s_win[kFoldWin + 4];
-    __shared__ float s_full[kFoldCap], s_gate[kFoldCap];
-    const uint32_t lane = threadIdx.x;
+    float cost = 0.0f, att = (float)d.span * bonus; // rmap.cpp:205,246
+    float gate = __builtin_inff();
+    if (d.n_jobs) {
+        const float *w = out + d.job_first; // part q: w[-q]
+        const uint32_t body = d.n_jobs - 1u; // cost += sub (rmap.cpp:279), attainable -= sub (rmap.cpp:280); the last part only adds to the cost
+        uint32_t q = 0;
+        for (; q < body && ((uintptr_t)(w - (ptrdiff_t)q) & 15u) != 12u; q++) { const float x = w[-(ptrdiff_t)q]; cost += x; att -= x; }
+        const uint32_t nr = (body - q) >> 4; // whole rounds of sixteen parts: round r's piece u is pc[-(4 r + u)], its parts from .w down to .x
+        const float4 *pc = reinterpret_cast<const float4 *>(w - (ptrdiff_t)q - 3);
+        auto ld = [&](float4 (&x)[4], const uint32_t r) {
+#pragma unroll
+            for (int u = 0; u < 4; u++) x[u] = pc[-(ptrdiff_t)(4u * r + (uint32_t)u)];
+        };
+        // (two dependent chains, cost up and attainable down: interleaved they never wait for each other)
+        auto add = [&](const float4 (&x)[4]) {
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                cost += x[u].w; att -= x[u].w; cost += x[u].z; att -= x[u].z;
+                cost += x[u].y; att -= x[u].y; cost += x[u].x; att -= x[u].x;
+            }
+        };
+        // Three buffers in turn: the round after next is on its way before this round's adds.  (The order is pinned: left to
+        // itself the scheduler sinks two of three rounds' loads behind the adds of the round before them.)
+        float4 x0[4] = {}, x1[4] = {}, x2[4] = {};
+        if (nr > 0u) ld(x0, 0u);
+        if (nr > 1u) ld(x1, 1u);
+        uint32_t r = 0;
+        for (; r + 5u <= nr; r += 3u) {
+            ld(x2, r + 2u); __builtin_amdgcn_sched_barrier(0); add(x0); __builtin_amdgcn_sched_barrier(0);
+            ld(x0, r + 3u); __builtin_amdgcn_sched_barrier(0); add(x1); __builtin_amdgcn_sched_barrier(0);
+            ld(x1, r + 4u); __builtin_amdgcn_sched_barrier(0); add(x2); __builtin_amdgcn_sched_barrier(0);
+        }
+        // (up to four rounds are left, the first two of them loaded)
+        if (r + 2u < nr) ld(x2, r + 2u);
+        if (r < nr) add(x0);
+        if (r + 3u < nr) ld(x0, r + 3u);
+        if (r + 1u < nr) add(x1);
+        if (r + 2u < nr) add(x2);
+        if (r + 3u < nr) add(x0);
+        q += nr << 4;
+        for (; q < body; q++) { const float x = w[-(ptrdiff_t)q]; cost += x; att -= x; }
+        gate = att;
+        cost = cost + w[-(ptrdiff_t)body];
+    }
+    float sc;
+    if (fused) sc = __builtin_fmaf((float)d.num_aligned, bonus, -cost);
+    else { const float prod = (float)d.num_aligned * bonus; sc = prod - cost; }
+    return v2f{sc, gate};
+}
+
+// (80 registers: its two waves fit beside k_runs' four a SIMD)
+__global__ __launch_bounds__(2 * kFoldReads) __attribute__((amdgpu_num_vgpr(80))) void k_fold_select(const StreamArgs a, const ChainDesc *__restrict__ chains, const uint64_t *__restrict__ chain_off,
+                                                                const uint64_t n_reads, const float bonus, const int fused, const float min_score,
+                                                                float *__restrict__ full_score, float *__restrict__ att_last, float *__restrict__ score,
+                                                                uint8_t *__restrict__ keep)
+{
+    __shared__ float s_first[2][kFoldReads];            // the first chains' score and gate (wave 0 to wave 1)
+    __shared__ float s_rest[2][kFoldCache][kFoldReads]; // the others': a column a lane, wave 1's own
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     // (a batch the scan or the DTW launch declined is redone through the job list: nothing here may be derived from it)
     const bool declined = a.cnt[kCntBad] != ~0ull || a.cnt[kCntOverflow] != ~0ull || a.cnt[kCntUnsupported] != 0ull || a.cnt[kCntOthers] > a.others_cap;
-    const uint64_t r0 = (uint64_t)blockIdx.x * kFoldReads, r1 = min(r0 + (uint64_t)kFoldReads, n_reads);
-    const uint32_t nr = (uint32_t)(r1 - r0);
-    const uint64_t co = chain_off[r0 + min(lane, nr)], co1 = chain_off[r0 + min(lane + 1u, nr)]; // lane < nr: its read's chains
+    const uint64_t r = (uint64_t)blockIdx.x * kFoldReads + lane;
+    const bool live = r < n_reads;
+    const uint64_t co = live ? chain_off[r] : 0ull, co1 = live ? chain_off[r + 1] : 0ull; // the read's chains (none: the lane does nothing)
     if (declined) return;
-    const uint64_t cA = __shfl((unsigned long long)co, 0), cB = __shfl((unsigned long long)co, (int)nr);
-    if (cB <= cA) return;
-    const uint64_t aA = a.anchor_off[cA], aB = a.anchor_off[cB];
-    // the lane's chains: cA + lane + 64 k, the highest first
-    const uint64_t n_ch = cB - cA;
-    long long c = lane < n_ch ? (long long)(cA + lane + ((n_ch - 1u - lane) & ~63ull)) : -1; // (-1: none)
-    ChainDesc d = chains[c >= 0 ? (uint64_t)c : cA];
-    uint32_t p = 0; // parts of chain c folded so far
-    v2f acc = {0.0f, (float)d.span * bonus}; // {cost, attainable}  (rmap.cpp:205,246)
-    auto finish = [&](const float last) {
-        const float gate = d.n_jobs ? acc.y : __builtin_inff(); // tested before the last (or only) DTW call; none: no check
-        const float cost = d.n_jobs ? acc.x + last : acc.x;    // the last part only adds to the cost (rmap.cpp:279-280)
-        float sc;
-        if (fused) sc = __builtin_fmaf((float)d.num_aligned, bonus, -cost);
-        else { const float prod = (float)d.num_aligned * bonus; sc = prod - cost; }
-        full_score[c] = sc; att_last[c] = gate;
-        if ((uint64_t)c - cA < kFoldCap) { s_full[(uint64_t)c - cA] = sc; s_gate[(uint64_t)c - cA] = gate; }
-        c = (uint64_t)c >= cA + 64u ? c - 64 : -1;
-        if (c >= 0) { d = chains[c]; p = 0; acc = v2f{0.0f, (float)d.span * bonus}; }
-    };
-    for (uint64_t hi = aB; hi > aA;) { // (uniform)
-        const uint64_t lo4 = (hi > aA + kFoldWin ? hi - kFoldWin : aA) & ~3ull;
-        // LDS-DMA: 16 bytes a lane straight into LDS, every piece of the window in flight at once (the last piece of the
-        // list may reach past its end: element by element)
-        for (uint64_t i0 = lo4; i0 < hi; i0 += 256ull) { // (uniform)
-            const uint64_t i = i0 + 4ull * lane;
-            if (i < hi) {
-                if (i + 4 <= a.n_anchors)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(a.out + i),
-                                                     (__attribute__((address_space(3))) void *)(s_win + (i0 - lo4)), 16, 0, 0);
-                else
-                    for (uint64_t j = i; j < a.n_anchors; j++) s_win[j - lo4] = a.out[j];
-            }
+    if (wave == 0u) {
+        if (co < co1) {
+            const v2f f = fold_chain(a.out, chains[co], bonus, fused);
+            full_score[co] = f.x; att_last[co] = f.y;
+            s_first[0][lane] = f.x; s_first[1][lane] = f.y;
         }
-        __builtin_amdgcn_s_waitcnt(0x0f70); // vmcnt(0)
-        __syncthreads();
-        while (c >= 0) {
-            if (d.n_jobs == 0) { finish(0.0f); continue; }
-            const uint64_t idx = d.job_first - p; // the next part: out[job_first - p]
-            if (idx < lo4) break;                 // the rest lies in the windows below
-            const float *w = s_win + (idx - lo4);
-            const uint32_t body = d.n_jobs - 1u;
-            // parts of the body in this window: cost += sub (rmap.cpp:279), attainable -= sub (rmap.cpp:280), one packed add a part
-            const uint32_t nb = p < body ? (uint32_t)min<uint64_t>(body - p, idx - lo4 + 1ull) : 0u;
-            // The adds are two dependent chains (cost up, attainable down: 4 cycles an add, interleaved they never wait for
-            // each other); the parts come out of LDS sixteen at a time in 16-byte pieces, the next sixteen on their way
-            // while these are added.  Part q of this stretch is w[-q]: single parts until a piece ends on one.
-            uint32_t q = 0;
-            float cost = acc.x, att = acc.y;
-            const uint32_t j0 = (uint32_t)(idx - lo4); // w = s_win + j0
-            for (; q < nb && ((j0 - q) & 3u) != 3u; q++) { const float x = w[-(int)q]; cost += x; att -= x; }
-            if (q + 16u <= nb) {
-                float4 x[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) x[u] = *reinterpret_cast<const float4 *>(w - (int)(q + 4u * u) - 3);
-#pragma unroll 2
-                for (; q + 32u <= nb; q += 16u) {
-                    float4 y[4];
-#pragma unroll
-                    for (int u = 0; u < 4; u++) y[u] = *reinterpret_cast<const float4 *>(w - (int)(q + 16u + 4u * u) - 3);
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        cost += x[u].w; att -= x[u].w; cost += x[u].z; att -= x[u].z;
-                        cost += x[u].y; att -= x[u].y; cost += x[u].x; att -= x[u].x;
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; u++) x[u] = y[u];
-                }
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    cost += x[u].w; att -= x[u].w; cost += x[u].z; att -= x[u].z;
-                    cost += x[u].y; att -= x[u].y; cost += x[u].x; att -= x[u].x;
-                }
-                q += 16u;
-            }
-            for (; q < nb; q++) { const float x = w[-(int)q]; cost += x; att -= x; }
-            acc = v2f{cost, att};
-            p += nb;
-            if (p == body && idx - nb >= lo4 && idx >= nb) finish(w[-(int)nb]); // the last part is in this window too
-            else break;
+    } else {
+        for (uint64_t c = co + 1u; c < co1; c++) {
+            const v2f f = fold_chain(a.out, chains[c], bonus, fused);
+            full_score[c] = f.x; att_last[c] = f.y;
+            const uint64_t k = c - co - 1u;
+            if (k < kFoldCache) { s_rest[0][k][lane] = f.x; s_rest[1][k][lane] = f.y; }
         }
-        __syncthreads();
-        hi = lo4;
     }
-    if (lane < nr) {
+    __syncthreads();
+    if (wave == 1u) {
         float best = 0.0f; // rmap.cpp:515
-        for (uint64_t cc = co; cc < co1; cc++) {
+        for (uint64_t c = co; c < co1; c++) {
+            const uint64_t k = c - co;
             float f, g;
-            if (cc - cA < kFoldCap) { f = s_full[cc - cA]; g = s_gate[cc - cA]; }
-            else { // (written by another lane of this wave: read past the vector cache)
-                f = __hip_atomic_load(&full_score[cc], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                g = __hip_atomic_load(&att_last[cc], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (k == 0u) { f = s_first[0][lane]; g = s_first[1][lane]; }
+            else if (k <= kFoldCache) { f = s_rest[0][k - 1u][lane]; g = s_rest[1][k - 1u][lane]; }
+            else { // (beyond the cache: back from memory, past the vector cache)
+                f = __hip_atomic_load(&full_score[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                g = __hip_atomic_load(&att_last[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             const float sv = (g < best) ? -1e10f : f; // rmap.cpp:206-209, 265-268
-            const bool k = sv >= min_score;           // rmap.cpp:518
-            if (k && sv > best) best = sv;            // rmap.cpp:519-521
-            score[cc] = sv;
-            keep[cc] = k ? 1 : 0;
+            const bool kp = sv >= min_score;          // rmap.cpp:518
+            if (kp && sv > best) best = sv;           // rmap.cpp:519-521
+            score[c] = sv;
+            keep[c] = kp ? 1 : 0;
         }
     }
 }
@@ -1563,7 +1557,7 @@ hipError_t stream_fold_select(const StreamArgs &a, const ChainDesc *chains, cons
 {
     if (n_reads == 0) return hipSuccess;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(k_fold_select, dim3((uint32_t)((n_reads + kFoldReads - 1) / kFoldReads)), dim3(64), 0, s, a, chains, chain_off, n_reads, bonus,
+    hipLaunchKernelGGL(k_fold_select, dim3((uint32_t)((n_reads + kFoldReads - 1) / kFoldReads)), dim3(2 * kFoldReads), 0, s, a, chains, chain_off, n_reads, bonus,
                        fused, min_score, full_score, att_last, score, keep);
     return hipGetLastError();
 }
