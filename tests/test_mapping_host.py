@@ -172,9 +172,12 @@ def test_sequence_until_state_machine():
 
 
 def py_chain(anchors, e=6, max_gap=2000, max_tgap=5000, band=5000, max_skips=25, min_anchors=2, nbest=3,
-             min_score=10.0, maxs=0.0, dp_out=None):
+             min_score=10.0, maxs=0.0, dp_out=None, trace=None, trace_from=0):
     """Plain-Python restatement of the chaining DP + traceback (rmap.cpp:430-507, 130-173), fp32 scores.  `dp_out`, a list, receives
-    every anchor's DP value."""
+    every anchor's DP value.  `trace`, a list, receives for every anchor from `trace_from` on how its predecessor loop (rmap.cpp:452-484)
+    went, in offsets behind the anchor (candidate ai - 1 is offset 0): why and where it ended ("gap", "skip", or "band" -- the band's end or
+    the list's start, at the offset of the first candidate that is not there), the improvers' offsets, the last of them (None: none), the
+    skip counter on entry to every further 64 candidates, the score and the predecessor (tests/chain_lattice_cases.py)."""
     n = len(anchors)
     score = [f32(e)] * n
     pred = list(range(n))
@@ -186,10 +189,18 @@ def py_chain(anchors, e=6, max_gap=2000, max_tgap=5000, band=5000, max_skips=25,
     for ai in range(n):
         start = ai - band if ai > band else 0
         skips = 0
+        tr = None
+        if trace is not None and ai >= trace_from:
+            tr = {"ai": ai, "exit": "band", "exit_off": ai - start, "improvers": [], "carry": []}
+            trace.append(tr)
         for pi in range(ai - 1, start - 1, -1):
+            if tr is not None and pi != ai - 1 and (ai - 1 - pi) % 64 == 0:
+                tr["carry"].append(skips)
             if Q[pi] == Q[ai] or T[pi] == T[ai]:
                 continue
             if T[pi] + max_tgap < T[ai]:
+                if tr is not None:
+                    tr["exit"], tr["exit_off"] = "gap", ai - 1 - pi
                 break
             td, qd = T[ai] - T[pi], Q[ai] - Q[pi]
             if qd < 0:
@@ -201,10 +212,17 @@ def py_chain(anchors, e=6, max_gap=2000, max_tgap=5000, band=5000, max_skips=25,
             if cur > score[ai]:
                 score[ai], pred[ai] = cur, pi
                 skips -= 1
+                if tr is not None:
+                    tr["improvers"].append(ai - 1 - pi)
             else:
                 skips += 1
                 if skips > max_skips:
+                    if tr is not None:
+                        tr["exit"], tr["exit_off"] = "skip", ai - 1 - pi
                     break
+        if tr is not None:
+            tr["last"] = tr["improvers"][-1] if tr["improvers"] else None
+            tr["score"], tr["pred"] = score[ai], pred[ai]
         if score[ai] > maxs:
             maxs = score[ai]
         if score[ai] >= f32(min_score) and score[ai] > f32(maxs / f32(2)):
