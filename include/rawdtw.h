@@ -46,7 +46,8 @@ typedef enum {
     RAWDTW_ERR_OOM = 3,
     RAWDTW_ERR_RANGE = 4,       /* a job window lies outside the uploaded arenas */
     RAWDTW_ERR_UNSUPPORTED = 5, /* e.g. traceback of a banded global job (rmap.cpp:223-225 assert(false)) */
-    RAWDTW_ERR_NO_DEVICE = 6
+    RAWDTW_ERR_NO_DEVICE = 6,
+    RAWDTW_ERR_INTERNAL = 7     /* a check the library makes on its own device work failed: nothing was built */
 } rawdtw_status;
 
 #define RAWDTW_FULL (-1) /* band_radius value selecting DTW_global (dtw.hpp:21) */
@@ -1256,7 +1257,19 @@ int rawdtw_chain_round_begin_resident_kept(rawdtw_ctx *ctx, const rawdtw_chain_o
  *        rawdtw_seed_index_get answers and rawdtw_seed_index_info numbers.  w > 0: RAWDTW_ERR_UNSUPPORTED and nothing changed (build on
  *        the host); no reference with a sequence table on the context, or bad pars: RAWDTW_ERR_INVALID.
  *   rawdtw_seed_index_build_stats   milliseconds of the context's most recent device build: filter, emit, sort (device time), the
- *        entries' way home and the table's build (host time). ---- */
+ *        entries' way home and the table's build (host time).  After a w > 0 build the emit slot is the sum of the three selection launches.
+ *   rawdtw_seed_index_build_device_min   rawdtw_seed_index_build_device's contract for w in 0 .. 255.  w = 0 runs that function's path
+ *        unchanged.  w > 0: ri_sketch_min's windows (rsketch.c:146-221) over whole strands, as a count, a scan and a write of every
+ *        e-mer's step on its own (rawdtw_seed_min.h) -- the table equals rawdtw_seed_index_build's from the same arrays: keys, key order,
+ *        rawdtw_seed_index_get answers, rawdtw_seed_index_info numbers.  The entry arrays are sized by the scan's total (more entries than
+ *        e-mers is legal).  RAWDTW_ERR_INVALID for bad pars (w >= 256, e < 2) or no reference with a sequence table, RAWDTW_ERR_OOM,
+ *        RAWDTW_ERR_INTERNAL when the write launch's element count is not the scan's total; a failed call changes nothing.
+ *        rawdtw_seed_index_build_device itself still refuses w > 0.
+ *   rawdtw_seed_sketch_windowed   the host restatement of that parallel form for one strand or chunk: the kept events, every e-mer's hash,
+ *        then the shared step for every e-mer independently.  Equal to rawdtw_seed_sketch, element for element (w = 0: ri_sketch_reg).
+ *        *n is the true count; with cap too small RAWDTW_ERR_RANGE, *n still set and the first cap elements written.  Needs no GPU.  For tests.
+ *   rawdtw_seed_index_build_min_stats   of the context's most recent w > 0 build: the e-mers over all strands, the entries emitted, and
+ *        the device time in ms of the hash, count + scan and write launches.  Any pointer may be NULL. ---- */
 int rawdtw_pore_model_load(const char *path, uint32_t *k, float *level_mean, uint64_t cap);
 int rawdtw_seq_to_sig_host(const char *bases, uint32_t len, const float *pore_vals, uint32_t k, int strand, int contracted, float *out,
                            uint32_t *s_len);
@@ -1267,6 +1280,10 @@ int rawdtw_reference_fetch(rawdtw_ctx *ctx, uint32_t seq, int strand, float *out
 int rawdtw_reference_build_stats(const rawdtw_ctx *ctx, uint64_t fast_steps[2], uint64_t slow_steps[2], float kernel_ms[2]);
 int rawdtw_seed_index_build_device(rawdtw_ctx *ctx, const rawdtw_seed_pars_t *pars, rawdtw_seed_index **out);
 int rawdtw_seed_index_build_stats(const rawdtw_ctx *ctx, float phase_ms[5]);
+int rawdtw_seed_index_build_device_min(rawdtw_ctx *ctx, const rawdtw_seed_pars_t *pars, rawdtw_seed_index **out);
+int rawdtw_seed_sketch_windowed(const rawdtw_seed_pars_t *pars, const float *events, uint32_t len, uint32_t *hash, uint32_t *pos, uint32_t cap,
+                                uint32_t *n);
+int rawdtw_seed_index_build_min_stats(const rawdtw_ctx *ctx, uint64_t *emers, uint64_t *entries, float select_ms[3]);
 
 #ifdef __cplusplus
 }

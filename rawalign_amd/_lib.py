@@ -317,6 +317,9 @@ SYMBOLS = {
     "rawdtw_reference_build_stats": (I32, [VP, VP, VP, VP]),
     "rawdtw_seed_index_build_device": (I32, [VP, C.POINTER(SeedPars), C.POINTER(VP)]),
     "rawdtw_seed_index_build_stats": (I32, [VP, VP]),
+    "rawdtw_seed_index_build_device_min": (I32, [VP, C.POINTER(SeedPars), C.POINTER(VP)]),
+    "rawdtw_seed_sketch_windowed": (I32, [C.POINTER(SeedPars), VP, U32, VP, VP, U32, C.POINTER(U32)]),
+    "rawdtw_seed_index_build_min_stats": (I32, [VP, C.POINTER(U64), C.POINTER(U64), VP]),
 }
 
 

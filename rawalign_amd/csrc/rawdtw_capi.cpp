@@ -23,6 +23,7 @@ const char *rawdtw_status_string(int status)
     case RAWDTW_ERR_RANGE: return "job window out of range";
     case RAWDTW_ERR_UNSUPPORTED: return "unsupported";
     case RAWDTW_ERR_NO_DEVICE: return "no HIP device";
+    case RAWDTW_ERR_INTERNAL: return "internal check failed";
     default: return "unknown status";
     }
 }

@@ -115,6 +115,10 @@ struct rawdtw_ctx : rawdtw::Options { // (every option is a field of Options: ra
     float refsig_ms[2] = {0.f, 0.f};
     // the most recent rawdtw_seed_index_build_device (rawdtw_seed_build.hip): filter, emit, sort, entries home, fill_table
     float seed_build_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    // the most recent w > 0 build of rawdtw_seed_index_build_device_min: e-mers over all strands, entries emitted, and the device time
+    // of the hash, count + scan and write launches (their sum is seed_build_ms's emit slot)
+    uint64_t seed_min_emers = 0, seed_min_entries = 0;
+    float seed_min_ms[3] = {0.f, 0.f, 0.f};
     // event arena
     float *d_ev = nullptr;
     uint64_t n_ev = 0, cap_ev = 0;

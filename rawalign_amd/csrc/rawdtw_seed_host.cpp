@@ -14,6 +14,7 @@
 
 #include "rawdtw_capi.h"
 #include "rawdtw_seed.h"
+#include "rawdtw_seed_min.h"
 
 using namespace rawdtw;
 using namespace rawdtw::seed;
@@ -333,6 +334,45 @@ int rawdtw_seed_sketch(const rawdtw_seed_pars_t *pars, const float *events, uint
     });
     *n_out = k;
     return k <= n ? RAWDTW_OK : RAWDTW_ERR_RANGE;
+}
+
+// The parallel form of the minimizer sketch, as rawdtw_seed_build.hip runs it: the kept events (k_sb_filter), every e-mer's hash
+// (k_sb_hash), then rawdtw_seed_min.h's step for every m on its own (k_sb_min_count / k_sb_min_write).  w == 0 has no window: ri_sketch_reg.
+int rawdtw_seed_sketch_windowed(const rawdtw_seed_pars_t *pars, const float *events, uint32_t len, uint32_t *hash, uint32_t *pos, uint32_t cap,
+                                uint32_t *n)
+{
+    if (check_pars(pars) != RAWDTW_OK || !n || (len && !events) || (cap && (!hash || !pos))) return RAWDTW_ERR_INVALID;
+    uint32_t k = 0;
+    auto put = [&](uint32_t h, uint32_t i) {
+        if (k < cap) { hash[k] = h; pos[k] = i; }
+        k++;
+    };
+    if (pars->w == 0) sketch_reg(*pars, events, len, put);
+    else {
+        const uint32_t e = pars->e, quant_bit = pars->lq + 2;
+        const uint64_t mask_events = (1ULL << (quant_bit * e)) - 1;
+        std::vector<uint32_t> kept_pos, kept_code, h;
+        try {
+            float last = len ? events[0] : 0.0f;
+            for (uint32_t i = 0; i < len; i++) {
+                if (skipped_min(events[i], last, i == 0)) continue;
+                last = events[i];
+                kept_pos.push_back(i);
+                kept_code.push_back(code_of(bits_of(events[i]), pars->q, pars->lq));
+            }
+            const uint32_t M = kept_pos.size() >= e ? (uint32_t)kept_pos.size() - e + 1 : 0;
+            h.resize(M);
+            for (uint32_t m = 0; m < M; m++) {
+                uint64_t quant = 0;
+                for (uint32_t a = 0; a < e; a++) quant = quant << quant_bit | kept_code[m + a];
+                h[m] = hash32((uint32_t)(quant & mask_events));
+            }
+            for (uint32_t m = 0; m < M; m++)
+                min_step_walk(MinHashes{h.data(), 0}, m, M, pars->w, [&](uint32_t i) { put(h[i], kept_pos[i]); });
+        } catch (const std::bad_alloc &) { return RAWDTW_ERR_OOM; }
+    }
+    *n = k;
+    return k <= cap ? RAWDTW_OK : RAWDTW_ERR_RANGE;
 }
 
 int rawdtw_seed_hits_host(const rawdtw_seed_index *six, uint32_t n_chunks, const uint64_t *event_off, const float *events, uint64_t *hit_off,

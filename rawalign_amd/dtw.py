@@ -430,6 +430,13 @@ class Engine:
         self._check(self.lib.rawdtw_seed_index_build_stats(self._ctx, _ptr(ms)))
         return dict(zip(("filter_ms", "emit_ms", "sort_ms", "home_ms", "fill_table_ms"), (float(x) for x in ms)))
 
+    def seed_build_min_stats(self) -> dict:
+        """rawdtw_seed_index_build_min_stats: the most recent SeedIndex.from_device(minimizer=True) with w > 0 on this engine -- e-mers over
+        all strands, entries emitted, and the device time of the hash, count + scan and write launches in ms"""
+        emers, entries, ms = C.c_uint64(), C.c_uint64(), np.zeros(3, np.float32)
+        self._check(self.lib.rawdtw_seed_index_build_min_stats(self._ctx, C.byref(emers), C.byref(entries), _ptr(ms)))
+        return {"emers": emers.value, "entries": entries.value, "hash_ms": float(ms[0]), "count_scan_ms": float(ms[1]), "write_ms": float(ms[2])}
+
     def set_reference_device(self, data_ptr: int, n_floats: int, keepalive=None):
         self._check(self.lib.rawdtw_set_reference_device(self._ctx, C.c_void_p(data_ptr), n_floats))
         self._keep_ref = keepalive

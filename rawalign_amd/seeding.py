@@ -71,10 +71,12 @@ class SeedIndex:
         return cls(h)
 
     @classmethod
-    def from_device(cls, engine, pars=None) -> "SeedIndex":
-        """rawdtw_seed_index_build_device: from_signals of the arrays the engine's reference holds, built on the device (w = 0 only)"""
+    def from_device(cls, engine, pars=None, minimizer: bool = False) -> "SeedIndex":
+        """rawdtw_seed_index_build_device: from_signals of the arrays the engine's reference holds, built on the device (w = 0 only).
+        `minimizer`: rawdtw_seed_index_build_device_min, which takes w > 0 too (ri_sketch_min's windows over whole strands)."""
         h = C.c_void_p()
-        engine._check(engine.lib.rawdtw_seed_index_build_device(engine._ctx, C.byref(_pars(pars)), C.byref(h)))
+        build = engine.lib.rawdtw_seed_index_build_device_min if minimizer else engine.lib.rawdtw_seed_index_build_device
+        engine._check(build(engine._ctx, C.byref(_pars(pars)), C.byref(h)))
         return cls(h)
 
     def get(self, hash_value: int) -> np.ndarray:
@@ -108,6 +110,26 @@ def sketch(events, pars=None):
     ev = np.ascontiguousarray(events, np.float32)
     h, p, n = np.zeros(max(len(ev), 1), np.uint32), np.zeros(max(len(ev), 1), np.uint32), C.c_uint32()
     _check(lib.rawdtw_seed_sketch(C.byref(_pars(pars)), ev.ctypes.data, len(ev), h.ctypes.data, p.ctypes.data, C.byref(n)))
+    return h[:n.value].copy(), p[:n.value].copy()
+
+
+def sketch_windowed(events, pars=None, cap=None):
+    """rawdtw_seed_sketch_windowed: the sketch of one strand or chunk in the form the device build of a minimizer table runs -- every
+    e-mer's step on its own.  Equal to sketch().  With `cap` too small the RawDTWError carries the true count as .n."""
+    lib = load_library()
+    ev = np.ascontiguousarray(events, np.float32)
+    n = C.c_uint32()
+    if cap is None:  # count first: the minimizer sketch may emit more elements than events
+        st = lib.rawdtw_seed_sketch_windowed(C.byref(_pars(pars)), ev.ctypes.data, len(ev), None, None, 0, C.byref(n))
+        if st not in (0, 4):
+            _check(st)
+        cap = n.value
+    h, p = np.zeros(max(int(cap), 1), np.uint32), np.zeros(max(int(cap), 1), np.uint32)
+    st = lib.rawdtw_seed_sketch_windowed(C.byref(_pars(pars)), ev.ctypes.data, len(ev), h.ctypes.data, p.ctypes.data, int(cap), C.byref(n))
+    if st != 0:
+        err = RawDTWError(st, lib.rawdtw_status_string(st).decode())
+        err.n = n.value
+        raise err
     return h[:n.value].copy(), p[:n.value].copy()
 
 

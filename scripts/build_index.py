@@ -1,6 +1,6 @@
 """FASTA + k-mer pore model -> a complete .ind (signals and hash buckets, ri_idx_dump's layout) with the signals and the seed table
 built on the device: Engine.reference_from_bases, SeedIndex.from_device, then index.write_index(buckets=).  A table with minimizer
-windows (-w above 0) is built on the host from the fetched signals, as rawdtw_seed_index_build_device asks.
+windows (-w above 0) is built on the device too (rawdtw_seed_index_build_device_min); the signals are fetched for the file alone.
 Usage: python scripts/build_index.py FASTA MODEL OUT.ind [-w 0 -e 6 -q 9 --lq 3] [--plain] [--device 0]"""
 import argparse
 import os
@@ -25,7 +25,7 @@ def build_index(fasta: str, model: str, out: str, w=0, e=6, n=0, q=9, lq=3, cont
         eng.reference_from_bases([s for _, s in records], pore, k, contracted)
         fwd = [eng.reference_fetch(i, 1) for i in range(len(records))]
         rev = [eng.reference_fetch(i, 0) for i in range(len(records))]
-        six = SeedIndex.from_device(eng, pars) if w == 0 else SeedIndex.from_signals(fwd, rev, pars, threads=threads)
+        six = SeedIndex.from_device(eng, pars, minimizer=w > 0)
         # ri_idx_dump writes l_seq floats a strand (rawindex.cpp:293-295): the s_len values, then the k - 1 zeros ri_kcalloc left
         pad = [np.zeros(len(s) - len(x), np.float32) for (_, s), x in zip(records, fwd)]
         index.write_index(out, [name for name, _ in records], [np.concatenate([x, z]) for x, z in zip(fwd, pad)],
