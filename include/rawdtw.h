@@ -1285,6 +1285,45 @@ int rawdtw_seed_sketch_windowed(const rawdtw_seed_pars_t *pars, const float *eve
                                 uint32_t *n);
 int rawdtw_seed_index_build_min_stats(const rawdtw_ctx *ctx, uint64_t *emers, uint64_t *entries, float select_ms[3]);
 
+/* ---- The seed index built and kept on the device (rawdtw_seed_build.hip, rawdtw_seed_tile.h): from the context's reference to a table
+ * the seeding kernels read, without the entries, the slots or the lists crossing the link.
+ *   rawdtw_seed_index_build_resident   rawdtw_seed_index_build_device_min's checks and refusals, w in 0 .. 255.  The kept events come
+ *        from three launches with no chain over events (a tile of `tile` events a workgroup: every element's next kept element and its
+ *        chain's last; a wave a strand, one step a tile: the tile's entry against the carried value; a tile again: the chain written
+ *        out), then the unchanged emit or selection launches and the two sorts; the table's slots and lists are built from the sorted
+ *        entries on the device, byte for byte what fill_table makes (keys inserted by rank with an atomic minimum a slot), and installed
+ *        as the context's seed table under a fresh serial behind the last check.  A failed call leaves the context's table, and an ended
+ *        resident seeding, as they were.  RAWDTW_ERR_INVALID while a seeding is begun on the context, as rawdtw_seed_index_upload.
+ *        *out carries the header alone (rawdtw_seed_index_info answers as for a host-built index) and no host copy.
+ *   rawdtw_seed_index_is_resident   1 while the index has no host copy, else 0 (NULL: 0).
+ *        Such an index: rawdtw_seed_index_upload on the context that built it is the same-serial no-op, so every seeding and mapper
+ *        entry that uploads works unchanged there.  What needs the host copy -- rawdtw_seed_index_get, _keys, rawdtw_seed_hits_host, the
+ *        mapper's host seeding, rawdtw_seed_index_upload to another context -- returns RAWDTW_ERR_UNSUPPORTED: call
+ *        rawdtw_seed_index_fetch first.  Once the context's table has been replaced, _upload there and _fetch return RAWDTW_ERR_INVALID.
+ *        rawdtw_seed_index_destroy frees the handle only: the context owns the table.
+ *   rawdtw_seed_index_fetch   the slots and lists come home into the handle: from then on an ordinary index with the same serial.  An
+ *        index that has its host copy: RAWDTW_OK and nothing done.
+ *   rawdtw_seed_index_from_entries   the table of n entries (hash[i], y[i]) sorted by (hash, y), through fill_table on the host;
+ *        RAWDTW_ERR_INVALID for entries out of order.  Needs no GPU.
+ *   rawdtw_seed_table_from_entries   the same entries through the device's table launches alone: a resident index on ctx.
+ *        Both let chosen hashes meet in the slots.  For tests.
+ *   rawdtw_seed_index_build_resident_stats   of the context's most recent resident build or rawdtw_seed_table_from_entries: the tile
+ *        size, the tiles, kept events, entries and keys, the keys that do not lie in their home slot (counted on the finished table),
+ *        and device milliseconds of the per-tile pass, the chain, the mark, emit or selection, the sorts and the table launches. ---- */
+typedef struct {
+    uint32_t tile, log2_slots;
+    uint64_t tiles, kept, entries, keys, displaced;
+    float next_ms, chain_ms, mark_ms, emit_ms, sort_ms, table_ms;
+} rawdtw_seed_resident_stats_t;
+int rawdtw_seed_index_build_resident(rawdtw_ctx *ctx, const rawdtw_seed_pars_t *pars, rawdtw_seed_index **out);
+int rawdtw_seed_index_is_resident(const rawdtw_seed_index *six);
+int rawdtw_seed_index_fetch(rawdtw_ctx *ctx, rawdtw_seed_index *six);
+int rawdtw_seed_index_from_entries(const rawdtw_seed_pars_t *pars, uint32_t n_seq, uint64_t n, const uint32_t *hash, const uint64_t *y,
+                                   rawdtw_seed_index **out);
+int rawdtw_seed_table_from_entries(rawdtw_ctx *ctx, const rawdtw_seed_pars_t *pars, uint32_t n_seq, uint64_t n, const uint32_t *hash,
+                                   const uint64_t *y, rawdtw_seed_index **out);
+int rawdtw_seed_index_build_resident_stats(const rawdtw_ctx *ctx, rawdtw_seed_resident_stats_t *out);
+
 #ifdef __cplusplus
 }
 #endif

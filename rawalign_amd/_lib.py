@@ -124,6 +124,13 @@ class SeedPars(C.Structure):
     _fields_ = [("w", C.c_uint32), ("e", C.c_uint32), ("n", C.c_uint32), ("q", C.c_uint32), ("lq", C.c_uint32), ("k", C.c_uint32)]
 
 
+class SeedResidentStats(C.Structure):
+    """rawdtw_seed_resident_stats_t (rawdtw_seed_index_build_resident_stats)"""
+    _fields_ = [("tile", C.c_uint32), ("log2_slots", C.c_uint32), ("tiles", C.c_uint64), ("kept", C.c_uint64), ("entries", C.c_uint64),
+                ("keys", C.c_uint64), ("displaced", C.c_uint64), ("next_ms", C.c_float), ("chain_ms", C.c_float), ("mark_ms", C.c_float),
+                ("emit_ms", C.c_float), ("sort_ms", C.c_float), ("table_ms", C.c_float)]
+
+
 # rawdtw_scorer_fn (rawdtw_mapper_set_scorer)
 SCORER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                         C.c_void_p, C.c_void_p)
@@ -320,6 +327,12 @@ SYMBOLS = {
     "rawdtw_seed_index_build_device_min": (I32, [VP, C.POINTER(SeedPars), C.POINTER(VP)]),
     "rawdtw_seed_sketch_windowed": (I32, [C.POINTER(SeedPars), VP, U32, VP, VP, U32, C.POINTER(U32)]),
     "rawdtw_seed_index_build_min_stats": (I32, [VP, C.POINTER(U64), C.POINTER(U64), VP]),
+    "rawdtw_seed_index_build_resident": (I32, [VP, C.POINTER(SeedPars), C.POINTER(VP)]),
+    "rawdtw_seed_index_is_resident": (I32, [VP]),
+    "rawdtw_seed_index_fetch": (I32, [VP, VP]),
+    "rawdtw_seed_index_from_entries": (I32, [C.POINTER(SeedPars), U32, U64, VP, VP, C.POINTER(VP)]),
+    "rawdtw_seed_table_from_entries": (I32, [VP, C.POINTER(SeedPars), U32, U64, VP, VP, C.POINTER(VP)]),
+    "rawdtw_seed_index_build_resident_stats": (I32, [VP, C.POINTER(SeedResidentStats)]),
 }
 
 

@@ -119,6 +119,8 @@ struct rawdtw_ctx : rawdtw::Options { // (every option is a field of Options: ra
     // of the hash, count + scan and write launches (their sum is seed_build_ms's emit slot)
     uint64_t seed_min_emers = 0, seed_min_entries = 0;
     float seed_min_ms[3] = {0.f, 0.f, 0.f};
+    // the most recent rawdtw_seed_index_build_resident / rawdtw_seed_table_from_entries (rawdtw_seed_index_build_resident_stats)
+    rawdtw_seed_resident_stats_t seed_resident{};
     // event arena
     float *d_ev = nullptr;
     uint64_t n_ev = 0, cap_ev = 0;
@@ -275,6 +277,13 @@ void *device_view(void *p, size_t bytes);
 void chain_ws_free(rawdtw_ctx *ctx); // rawdtw_chain.hip
 void detect_ws_free(rawdtw_ctx *ctx); // rawdtw_events.hip
 void seed_ws_free(rawdtw_ctx *ctx);   // rawdtw_seed.hip
+// The context's seed table for rawdtw_seed_build.hip's resident builds (rawdtw_seed.hip owns it).  installable: RAWDTW_OK, or what
+// rawdtw_seed_index_upload would refuse (a seeding begun and not ended).  install: a finished table in device memory takes the place of
+// the context's (the stream is idle; the blocks are the context's from here on).  view: the table's blocks while the context's table is
+// the index `serial`; false: it has been replaced.
+int seed_table_installable(rawdtw_ctx *ctx);
+void seed_table_install(rawdtw_ctx *ctx, void *d_slots, uint64_t *d_list, uint32_t log2_slots, const rawdtw_seed_pars_t &pars, uint64_t serial);
+bool seed_table_view(const rawdtw_ctx *ctx, uint64_t serial, const void **d_slots, const uint64_t **d_list);
 void round_end_ws_free(rawdtw_ctx *ctx); // rawdtw_round_end.hip
 void round_end_forget(rawdtw_ctx *ctx, const rawdtw_batch *b); // (rawdtw_batch.cpp's batch_detach)
 int64_t round_end_kernel_us(const rawdtw_ctx *ctx); // the most recent fetched round end's launch, from its event pair ("round_end_kernel_us", read-only)

@@ -1526,6 +1526,7 @@ int rawdtw_mapper_round_seeded(rawdtw_mapper *m, const rawdtw_seed_index *six, u
     const bool on_device = m->ctx && (pars.w == 0 || ctx_option(m->ctx, "seed_minimizer") != 0); // (the minimizer sketch is the host's unless "seed_minimizer" is on)
     if (!seed_room(m, m->seed_off, (uint64_t)n_reads + 1)) return fail(m, RAWDTW_ERR_OOM, "no memory for the round's hit offsets");
     if (!on_device) {
+        if (rawdtw_seed_index_is_resident(six)) return fail(m, RAWDTW_ERR_UNSUPPORTED, "host seeding needs the index's host copy: rawdtw_seed_index_fetch first");
         int st = rawdtw_seed_hits_host(six, n_reads, event_off, events, m->seed_off.p, nullptr, 0, m->opt.threads); // (counts)
         if (st != RAWDTW_OK && st != RAWDTW_ERR_RANGE) return fail(m, st, "seeding: bad event offsets");
         if (!seed_room(m, m->seed_hits, m->seed_off[n_reads])) return fail(m, RAWDTW_ERR_OOM, "no memory for the round's hits");

@@ -77,6 +77,7 @@ int check_pars(const rawdtw_seed_pars_t *p);
 struct Entry { uint32_t hash; uint64_t y; };
 int fill_table(rawdtw_seed_index *six, const std::vector<Entry> &a);
 uint64_t next_serial();
+bool entries_sorted(uint64_t n, const uint32_t *hash, const uint64_t *y); // by (hash, y), equal entries allowed
 
 } // namespace seed
 } // namespace rawdtw
@@ -89,4 +90,9 @@ struct rawdtw_seed_index {
     std::vector<rawdtw::seed::Slot> slots; // 1 << log2_slots, load at most 0.5
     std::vector<uint64_t> pos;             // the lists of the keys with more than one position, each ascending
     uint64_t n_keys = 0, n_positions = 0;  // (n_positions: every key's, single ones included)
+    // A resident index (rawdtw_seed_index_build_resident, rawdtw_seed_table_from_entries) has no host copy until rawdtw_seed_index_fetch:
+    // slots and pos are empty, the table is the context's (rawdtw_seed.hip: SeedWs) under this serial, and n_list counts its list words.
+    bool resident = false;
+    uint64_t n_list = 0;
+    const rawdtw_ctx *owner = nullptr; // (compared, never followed: the context may be gone)
 };

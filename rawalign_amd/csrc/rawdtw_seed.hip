@@ -605,6 +605,9 @@ int rawdtw_seed_index_upload(rawdtw_ctx *ctx, const rawdtw_seed_index *six)
     if (!w) return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed");
     if (w->pending) return fail(ctx, RAWDTW_ERR_INVALID, "a seeding is begun on this context and not ended");
     if (w->has_table && w->table_serial == six->serial) return RAWDTW_OK; // (this very index is there already)
+    if (six->resident) // (no host copy to send: the table lives, or lived, on the context that built it)
+        return six->owner == ctx ? fail(ctx, RAWDTW_ERR_INVALID, "the resident index's table on this context has been replaced")
+                                 : fail(ctx, RAWDTW_ERR_UNSUPPORTED, "a resident index has no host copy for another context: rawdtw_seed_index_fetch first");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // (an earlier table may still be read)
     if (w->d_slots) (void)hipFree(w->d_slots);
@@ -621,6 +624,27 @@ int rawdtw_seed_index_upload(rawdtw_ctx *ctx, const rawdtw_seed_index *six)
     w->pars = six->pars;
     w->table_serial = six->serial;
     w->has_table = true;
+    return RAWDTW_OK;
+}
+
+int rawdtw_seed_index_fetch(rawdtw_ctx *ctx, rawdtw_seed_index *six)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (!six) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    if (!six->resident) return RAWDTW_OK;
+    const void *d_slots = nullptr;
+    const uint64_t *d_list = nullptr;
+    if (six->owner != ctx || !seed_table_view(ctx, six->serial, &d_slots, &d_list))
+        return fail(ctx, RAWDTW_ERR_INVALID, "the resident index's table is not on this context (built elsewhere, or replaced since)");
+    std::vector<Slot> slots;
+    std::vector<uint64_t> pos;
+    try { slots.resize((size_t)1 << six->log2_slots); pos.resize(six->n_list); } catch (const std::bad_alloc &) { return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed"); }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(slots.data(), d_slots, slots.size() * sizeof(Slot), hipMemcpyDeviceToHost, ctx->stream));
+    if (!pos.empty()) HIP_TRY(ctx, hipMemcpyAsync(pos.data(), d_list, pos.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    six->slots.swap(slots); six->pos.swap(pos);
+    six->resident = false; // (an ordinary index from here on, under the same serial)
     return RAWDTW_OK;
 }
 
@@ -773,6 +797,32 @@ void seed_resident_write_chain(rawdtw_ctx *ctx, rawdtw_seed_t *d_seeds, const ui
     KeepStoreView kv;
     if (!d_prev_src || !keep_store_view(ctx, &kv)) { d_prev_src = nullptr; kv = KeepStoreView{}; } // (the chaining's begin has checked that a source has its store)
     hipLaunchKernelGGL(k_seed_write_chain, dim3(w.n), dim3(kW), 0, ctx->stream, w.ra, ChainDst{d_seeds, d_seed_off, d_prev_off, d_prev, d_chunk_start, d_sits_out, d_prev_src, kv.store, kv.L});
+}
+
+int seed_table_installable(rawdtw_ctx *ctx)
+{
+    SeedWs *w = ws_of(ctx);
+    if (!w) return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed");
+    if (w->pending) return fail(ctx, RAWDTW_ERR_INVALID, "a seeding is begun on this context and not ended");
+    return RAWDTW_OK;
+}
+
+void seed_table_install(rawdtw_ctx *ctx, void *d_slots, uint64_t *d_list, uint32_t log2_slots, const rawdtw_seed_pars_t &pars, uint64_t serial)
+{
+    SeedWs &w = ctx->seed_ws->w; // (seed_table_installable made it)
+    if (w.d_slots) (void)hipFree(w.d_slots);
+    if (w.d_list) (void)hipFree(w.d_list);
+    w.ready = false; // (an ended resident seeding's list words point into the table that went)
+    w.d_slots = static_cast<Slot *>(d_slots); w.d_list = d_list;
+    w.log2_slots = log2_slots; w.pars = pars; w.table_serial = serial; w.has_table = true;
+}
+
+bool seed_table_view(const rawdtw_ctx *ctx, uint64_t serial, const void **d_slots, const uint64_t **d_list)
+{
+    const SeedWs *w = ctx && ctx->seed_ws ? &ctx->seed_ws->w : nullptr;
+    if (!w || !w->has_table || w->table_serial != serial) return false;
+    *d_slots = w->d_slots; *d_list = w->d_list;
+    return true;
 }
 
 void seed_ws_free(rawdtw_ctx *ctx)

@@ -32,6 +32,13 @@ int check_pars(const rawdtw_seed_pars_t *p)
     return RAWDTW_OK;
 }
 
+bool entries_sorted(uint64_t n, const uint32_t *hash, const uint64_t *y)
+{
+    for (uint64_t i = 1; i < n; i++)
+        if (hash[i] < hash[i - 1] || (hash[i] == hash[i - 1] && y[i] < y[i - 1])) return false;
+    return true;
+}
+
 uint64_t next_serial()
 {
     static std::atomic<uint64_t> n{0};
@@ -288,6 +295,7 @@ int rawdtw_seed_index_get(const rawdtw_seed_index *six, uint64_t hash, const uin
 {
     if (!six || !pos || !n) return RAWDTW_ERR_INVALID;
     *pos = nullptr; *n = 0;
+    if (six->resident) return RAWDTW_ERR_UNSUPPORTED; // (no host copy, and "no hit" would be a lie: rawdtw_seed_index_fetch first)
     if (hash >> 32) return RAWDTW_OK; // (no sketch emits such a hash)
     const Slot *s = find(six, (uint32_t)hash);
     if (!s) return RAWDTW_OK;
@@ -303,7 +311,7 @@ int rawdtw_seed_index_info(const rawdtw_seed_index *six, uint32_t *n_seq, uint64
     if (n_seq) *n_seq = six->n_seq;
     if (n_keys) *n_keys = six->n_keys;
     if (n_positions) *n_positions = six->n_positions;
-    if (table_bytes) *table_bytes = six->slots.size() * sizeof(Slot) + six->pos.size() * 8;
+    if (table_bytes) *table_bytes = six->resident ? ((uint64_t)1 << six->log2_slots) * sizeof(Slot) + six->n_list * 8 : six->slots.size() * sizeof(Slot) + six->pos.size() * 8;
     if (pars) *pars = six->pars;
     return RAWDTW_OK;
 }
@@ -311,9 +319,36 @@ int rawdtw_seed_index_info(const rawdtw_seed_index *six, uint32_t *n_seq, uint64
 int rawdtw_seed_index_keys(const rawdtw_seed_index *six, uint32_t *hashes)
 {
     if (!six || (six->n_keys && !hashes)) return RAWDTW_ERR_INVALID;
+    if (six->resident) return RAWDTW_ERR_UNSUPPORTED; // (rawdtw_seed_index_fetch first)
     uint64_t k = 0;
     for (const Slot &s : six->slots)
         if (s.count) hashes[k++] = s.key;
+    return RAWDTW_OK;
+}
+
+int rawdtw_seed_index_is_resident(const rawdtw_seed_index *six)
+{
+    return six && six->resident ? 1 : 0;
+}
+
+int rawdtw_seed_index_from_entries(const rawdtw_seed_pars_t *pars, uint32_t n_seq, uint64_t n, const uint32_t *hash, const uint64_t *y,
+                                   rawdtw_seed_index **out)
+{
+    if (!out) return RAWDTW_ERR_INVALID;
+    *out = nullptr;
+    if (check_pars(pars) != RAWDTW_OK || (n && (!hash || !y)) || !entries_sorted(n, hash, y)) return RAWDTW_ERR_INVALID;
+    rawdtw_seed_index *six = new (std::nothrow) rawdtw_seed_index;
+    if (!six) return RAWDTW_ERR_OOM;
+    six->pars = *pars; six->n_seq = n_seq; six->serial = next_serial();
+    int st = RAWDTW_OK;
+    std::vector<Entry> all;
+    try {
+        all.resize(n);
+        for (uint64_t i = 0; i < n; i++) all[i] = Entry{hash[i], y[i]};
+    } catch (const std::bad_alloc &) { st = RAWDTW_ERR_OOM; }
+    if (st == RAWDTW_OK) st = fill_table(six, all);
+    if (st != RAWDTW_OK) { delete six; return st; }
+    *out = six;
     return RAWDTW_OK;
 }
 
@@ -379,6 +414,7 @@ int rawdtw_seed_hits_host(const rawdtw_seed_index *six, uint32_t n_chunks, const
                           rawdtw_seed_hit_t *hits, uint64_t hits_cap, int threads)
 {
     if (!six || !hit_off || (n_chunks && !event_off)) return RAWDTW_ERR_INVALID;
+    if (six->resident) return RAWDTW_ERR_UNSUPPORTED; // (rawdtw_seed_index_fetch first)
     for (uint32_t k = 0; k < n_chunks; k++)
         if (event_off[k + 1] < event_off[k] || event_off[k + 1] - event_off[k] > 0xffffffffull) return RAWDTW_ERR_INVALID;
     if (n_chunks && event_off[n_chunks] > event_off[0] && !events) return RAWDTW_ERR_INVALID;

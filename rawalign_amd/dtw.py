@@ -437,6 +437,15 @@ class Engine:
         self._check(self.lib.rawdtw_seed_index_build_min_stats(self._ctx, C.byref(emers), C.byref(entries), _ptr(ms)))
         return {"emers": emers.value, "entries": entries.value, "hash_ms": float(ms[0]), "count_scan_ms": float(ms[1]), "write_ms": float(ms[2])}
 
+    def seed_build_resident_stats(self) -> dict:
+        """rawdtw_seed_index_build_resident_stats: the most recent SeedIndex.from_device(resident=True) or from_entries(engine=...) on
+        this engine -- the filter's tile size and tiles, kept events, entries, keys, the keys not in their home slot, and device ms"""
+        from ._lib import SeedResidentStats
+
+        st = SeedResidentStats()
+        self._check(self.lib.rawdtw_seed_index_build_resident_stats(self._ctx, C.byref(st)))
+        return {name: getattr(st, name) for name, _ in SeedResidentStats._fields_}
+
     def set_reference_device(self, data_ptr: int, n_floats: int, keepalive=None):
         self._check(self.lib.rawdtw_set_reference_device(self._ctx, C.c_void_p(data_ptr), n_floats))
         self._keep_ref = keepalive

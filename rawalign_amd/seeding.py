@@ -71,13 +71,39 @@ class SeedIndex:
         return cls(h)
 
     @classmethod
-    def from_device(cls, engine, pars=None, minimizer: bool = False) -> "SeedIndex":
+    def from_device(cls, engine, pars=None, minimizer: bool = False, resident: bool = False) -> "SeedIndex":
         """rawdtw_seed_index_build_device: from_signals of the arrays the engine's reference holds, built on the device (w = 0 only).
-        `minimizer`: rawdtw_seed_index_build_device_min, which takes w > 0 too (ri_sketch_min's windows over whole strands)."""
+        `minimizer`: rawdtw_seed_index_build_device_min, which takes w > 0 too (ri_sketch_min's windows over whole strands).
+        `resident`: rawdtw_seed_index_build_resident (any w): the table is built and kept on the device as the engine's seed table;
+        the index has no host copy until fetch()."""
         h = C.c_void_p()
-        build = engine.lib.rawdtw_seed_index_build_device_min if minimizer else engine.lib.rawdtw_seed_index_build_device
+        lib = engine.lib
+        build = lib.rawdtw_seed_index_build_resident if resident else lib.rawdtw_seed_index_build_device_min if minimizer else lib.rawdtw_seed_index_build_device
         engine._check(build(engine._ctx, C.byref(_pars(pars)), C.byref(h)))
         return cls(h)
+
+    @classmethod
+    def from_entries(cls, pars, n_seq: int, hashes, ys, engine=None) -> "SeedIndex":
+        """The table of entries (hash, y) sorted by (hash, y): rawdtw_seed_index_from_entries on the host, or with an engine
+        rawdtw_seed_table_from_entries -- the device's table launches alone, a resident index on that engine."""
+        hs, y = np.ascontiguousarray(hashes, np.uint32), np.ascontiguousarray(ys, np.uint64)
+        assert hs.ndim == y.ndim == 1 and len(hs) == len(y)
+        h = C.c_void_p()
+        if engine is None:
+            _check(load_library().rawdtw_seed_index_from_entries(C.byref(_pars(pars)), int(n_seq), len(hs), hs.ctypes.data, y.ctypes.data, C.byref(h)))
+        else:
+            engine._check(engine.lib.rawdtw_seed_table_from_entries(engine._ctx, C.byref(_pars(pars)), int(n_seq), len(hs), hs.ctypes.data, y.ctypes.data, C.byref(h)))
+        return cls(h)
+
+    @property
+    def resident(self) -> bool:
+        """the index has no host copy: its table is the seed table of the engine that built it"""
+        return bool(self.lib.rawdtw_seed_index_is_resident(self._h))
+
+    def fetch(self, engine) -> "SeedIndex":
+        """rawdtw_seed_index_fetch: a resident index's slots and lists come home; from then on an ordinary index"""
+        engine._check(self.lib.rawdtw_seed_index_fetch(engine._ctx, self._h))
+        return self
 
     def get(self, hash_value: int) -> np.ndarray:
         """ri_idx_get: the packed positions id << 32 | pos << 1 | strand of a hash, in the index's order (empty: not there)"""
