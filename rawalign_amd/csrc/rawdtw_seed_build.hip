@@ -25,9 +25,16 @@
 //                 rawdtw_seed_tile.h's step), k_tb_slots (a thread a slot: Slot{key, count, val} from the rank), and a second select that
 //                 compacts the y of the groups with more than one entry into the lists.  The slots and lists stay: the context's table.
 //
-// The device block: per strand a row (below); per event of the arena a kept position and a kept code (4 bytes each); per entry a hash
-// and a y, twice over for the sort's double buffer, and rocPRIM's temporary storage.  w > 0 adds a hash per event of the arena (4 bytes),
-// a count and an offset a tile (8 bytes each), the scan's temporary storage and the word the write counts in.
+// The device arrays, each a hipMalloc of its own, for their sizes become known in three stages (after the host's pass over the sequence
+// table, after the filter, after the selection's scan): per strand a row (below); per event of the arena a kept position and a kept code
+// (4 bytes each); per entry a hash and a y, twice over for the sort's double buffer, and rocPRIM's temporary storage.  w > 0 adds a hash
+// per event of the arena (4 bytes), a count and an offset a tile (8 bytes each), the scan's temporary storage and the word the write counts
+// in; the tiled filter a next | steps word and a last value an event, an entry and a kept count a tile.
+//
+// The host side: every array and event is the Owner's, whose destructor frees them whatever way a call ends.  A build is phases over one
+// Build -- the checks, the strands' rows, the filter, the entries, the two sorts, the end on the host or the resident end -- each returning
+// at its first error, with the statistics written at one commit point (commit_stats) behind the last check.  What an asynchronous copy
+// brings home lands in the Build or its DeviceTable, never in a phase's frame.
 #include "rawdtw_capi.h"
 #include "rawdtw_seed.h"
 #include "rawdtw_seed_min.h"
@@ -35,6 +42,8 @@
 
 #include <algorithm>
 #include <chrono>
+#include <memory>
+#include <vector>
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -94,7 +103,7 @@ __global__ __launch_bounds__(256) void k_sb_emit(const StrandRow *__restrict__ r
 {
     const uint32_t pair = blockIdx.x;
     const StrandRow row = rows[pair];
-    const uint32_t n = row.kept >= e ? row.kept - e + 1 : 0, strand = (pair & 1) ? 0u : 1u;
+    const uint32_t n = strand_emers(row.kept, e), strand = (pair & 1) ? 0u : 1u;
     const uint64_t mask_events = (1ULL << (quant_bit * e)) - 1, seq = pair >> 1;
     for (uint64_t t = (uint64_t)blockIdx.y * blockDim.x + threadIdx.x; t < n; t += (uint64_t)gridDim.y * blockDim.x) {
         uint64_t quant = 0;
@@ -116,7 +125,7 @@ __global__ __launch_bounds__(256) void k_sb_hash(const StrandRow *__restrict__ r
                                                  uint32_t quant_bit, uint32_t *__restrict__ h_out)
 {
     const StrandRow row = rows[blockIdx.x];
-    const uint32_t n = row.kept >= e ? row.kept - e + 1 : 0;
+    const uint32_t n = strand_emers(row.kept, e);
     const uint64_t mask_events = (1ULL << (quant_bit * e)) - 1;
     for (uint64_t t = (uint64_t)blockIdx.y * blockDim.x + threadIdx.x; t < n; t += (uint64_t)gridDim.y * blockDim.x) {
         uint64_t quant = 0;
@@ -148,7 +157,7 @@ __global__ __launch_bounds__(256) void k_sb_min_count(const StrandRow *__restric
 {
     __shared__ uint32_t sh[kMinStage], part[4];
     const StrandRow row = rows[blockIdx.x];
-    const uint32_t M = row.kept >= e ? row.kept - e + 1 : 0, tiles = (M + kMinTile - 1) / kMinTile;
+    const uint32_t M = strand_emers(row.kept, e), tiles = (M + kMinTile - 1) / kMinTile;
     for (uint32_t t = blockIdx.y; t < tiles; t += gridDim.y) {
         const uint32_t m0 = t * kMinTile, m = m0 + threadIdx.x;
         const uint32_t base = min_stage(h + row.kept_base, M, m0, w, sh);
@@ -168,7 +177,7 @@ __global__ __launch_bounds__(256) void k_sb_min_write(const StrandRow *__restric
     __shared__ uint32_t sh[kMinStage], scan[kMinTile], part[4];
     const uint32_t pair = blockIdx.x, strand = (pair & 1) ? 0u : 1u;
     const StrandRow row = rows[pair];
-    const uint32_t M = row.kept >= e ? row.kept - e + 1 : 0, tiles = (M + kMinTile - 1) / kMinTile;
+    const uint32_t M = strand_emers(row.kept, e), tiles = (M + kMinTile - 1) / kMinTile;
     const uint64_t seq = pair >> 1;
     uint32_t done = 0;
     for (uint32_t t = blockIdx.y; t < tiles; t += gridDim.y) {
@@ -215,7 +224,7 @@ __global__ __launch_bounds__(256) void k_sb_next(const float *__restrict__ arena
     __shared__ float x[kFilterTile];
     __shared__ uint16_t jmp[kFilterTile], cnt[kFilterTile];
     const StrandRow row = rows[blockIdx.x];
-    const uint32_t tiles = (uint32_t)(((uint64_t)row.len + kFilterTile - 1) / kFilterTile);
+    const uint32_t tiles = filter_tiles(row.len);
     for (uint32_t t = blockIdx.y; t < tiles; t += gridDim.y) {
         const uint64_t i0 = (uint64_t)t * kFilterTile;
         const uint32_t n = (uint32_t)(row.len - i0 < kFilterTile ? row.len - i0 : kFilterTile);
@@ -268,7 +277,7 @@ __global__ __launch_bounds__(64) void k_sb_chain(const float *__restrict__ arena
     const uint32_t pair = blockIdx.x, lane = threadIdx.x;
     const StrandRow row = rows[pair];
     const float *s = arena + row.arena_off;
-    const uint32_t n = row.len, tiles = (uint32_t)(((uint64_t)n + kFilterTile - 1) / kFilterTile);
+    const uint32_t n = row.len, tiles = filter_tiles(n);
     const uint64_t tb = tile0[pair];
     uint32_t kept = 0;
     float v = n ? s[0] : 0.0f; // (s[last] with last = 0, as rsketch.c starts)
@@ -302,7 +311,7 @@ __global__ __launch_bounds__(64) void k_sb_mark(const float *__restrict__ arena,
     __shared__ uint16_t nx[kFilterTile], list[kFilterTile];
     __shared__ uint32_t on_chain;
     const StrandRow row = rows[blockIdx.x];
-    const uint32_t tiles = (uint32_t)(((uint64_t)row.len + kFilterTile - 1) / kFilterTile), lane = threadIdx.x;
+    const uint32_t tiles = filter_tiles(row.len), lane = threadIdx.x;
     const uint64_t tb = tile0[blockIdx.x];
     for (uint32_t t = blockIdx.y; t < tiles; t += gridDim.y) {
         const uint32_t entry = tile_entry[tb + t];
@@ -397,115 +406,207 @@ using namespace rawdtw;
 using namespace rawdtw::capi;
 using namespace rawdtw::seed;
 
+namespace {
+
+// The one owner of what a build has on the device: every array is a hipMalloc of its own, taken here, and every event is created here.
+// Whatever way a build ends, the destructor frees and destroys them all -- behind a wait for the stream where a call has failed with
+// work enqueued.  release() takes out an array that outlives the build: the resident table's slots and list.
+struct Owner {
+    rawdtw_ctx *ctx;
+    const char *what;              // the entry point a failed HIP call is reported under
+    hipError_t err = hipSuccess;   // the first HIP call that failed
+    std::vector<void *> arrays;
+    std::vector<hipEvent_t> events;
+
+    Owner(rawdtw_ctx *c, const char *w) : ctx(c), what(w) {}
+    Owner(const Owner &) = delete;
+    Owner &operator=(const Owner &) = delete;
+    ~Owner()
+    {
+        if (err != hipSuccess && !(arrays.empty() && events.empty())) (void)hipStreamSynchronize(ctx->stream);
+        for (void *p : arrays) (void)hipFree(p);
+        for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
+    }
+    bool ok(hipError_t r)
+    {
+        if (err == hipSuccess) err = r;
+        return err == hipSuccess;
+    }
+    int failed() const { return hip_fail(ctx, err, what); }
+    // (no room on the host to remember x: the same answer as no room on the device)
+    template <typename V, typename X> bool remember(V &list, X x)
+    {
+        try { list.push_back(x); } catch (const std::bad_alloc &) { err = hipErrorOutOfMemory; }
+        return err == hipSuccess;
+    }
+    template <typename T> hipError_t take(T *&p, uint64_t count)
+    {
+        void *q = nullptr;
+        if (err == hipSuccess && ok(hipMalloc(&q, count * sizeof(T))) && !remember(arrays, q)) { (void)hipFree(q); q = nullptr; }
+        p = static_cast<T *>(q);
+        return err;
+    }
+    hipEvent_t event()
+    {
+        hipEvent_t ev = nullptr;
+        if (err == hipSuccess && ok(hipEventCreate(&ev)) && !remember(events, ev)) { (void)hipEventDestroy(ev); ev = nullptr; }
+        return ev;
+    }
+    template <typename T> T *release(T *p)
+    {
+        arrays.erase(std::remove(arrays.begin(), arrays.end(), static_cast<void *>(p)), arrays.end());
+        return p;
+    }
+};
+
+// A HIP or rocPRIM call of a phase: the first that fails ends the phase, reported under the entry point's name.  Nothing is enqueued behind it.
+#define SB_HIP(own, expr)                                                                             \
+    do {                                                                                              \
+        if (!(own).ok(expr)) return (own).failed();                                                   \
+    } while (0)
+#define SB_LAUNCH(own, kernel, grid, block, ...)                                                      \
+    do {                                                                                              \
+        hipLaunchKernelGGL(kernel, grid, block, 0, (own).ctx->stream, __VA_ARGS__);                   \
+        SB_HIP(own, hipGetLastError());                                                               \
+    } while (0)
+// a phase inside a phase
+#define SB_TRY(expr)                                                                                  \
+    do {                                                                                              \
+        const int st_ = (expr);                                                                       \
+        if (st_ != RAWDTW_OK) return st_;                                                             \
+    } while (0)
+
+// rocPRIM's two-call form, call(storage, bytes): with no storage the call says how many bytes it wants.  prim_take: the storage for an
+// answer, 16 bytes at least; prim_run: the question, the storage, the call.  (Where launches lie between the question and the call -- the
+// selection's scan, the two sorts, which share one storage of the larger size -- the call is written once and made twice.)
+hipError_t prim_take(Owner &own, void *&tmp, size_t bytes)
+{
+    char *p = nullptr;
+    const hipError_t e = own.take(p, std::max<size_t>(bytes, 16));
+    tmp = p;
+    return e;
+}
+template <typename F> hipError_t prim_run(Owner &own, void *&tmp, F call)
+{
+    size_t bytes = 0;
+    if (!own.ok(call(nullptr, bytes)) || prim_take(own, tmp, bytes) != hipSuccess) return own.err;
+    return call(tmp, bytes);
+}
+
 // The table of n sorted entries in device memory, built there: on success the slots and lists are the caller's to install or free.
 struct DeviceTable {
     Slot *d_slots = nullptr;
     uint64_t *d_list = nullptr;
     uint32_t lg = 0;
     uint64_t n_keys = 0, n_list = 0, displaced = 0;
+    unsigned long long flags[3] = {0, 0, 0}; // (k_tb_insert's and k_tb_slots')
     float ms = 0.f;
 };
 
-static int table_on_device(rawdtw_ctx *ctx, const uint32_t *d_hash, const uint64_t *d_y, uint64_t n, DeviceTable *out)
+// What the phases of a build hand to each other.  Every destination of an asynchronous copy to the host -- rows, N, written, and
+// DeviceTable's n_keys, n_list and flags -- lives here, never in the frame of a phase: a phase may return before the copy has landed, and
+// the owner, declared last and so destroyed first, waits for the stream before any of this goes.
+struct Build {
+    rawdtw_ctx *ctx;
+    const rawdtw_seed_pars_t *pars;
+    rawdtw_seed_index **out;
+    const bool resident;      // the filter is the three tiled launches, nothing comes home, the table is built on the device and installed
+    const bool windowed;      // w > 0: the minimizers of the e-mers
+    const bool from_entries;  // rawdtw_seed_table_from_entries: the entries are the caller's, the build's times are not this call's to write
+    std::unique_ptr<rawdtw_seed_index> six;
+    // the strands: a row each, and (for the tiled filter) each one's first tile of kFilterTile events among all strands' tiles
+    std::vector<StrandRow> rows;
+    std::vector<uint64_t> tile0;
+    uint32_t n_seq = 0, seq_bits = 0;
+    uint64_t total_len = 0, max_len = 0, f_tiles = 0, kept_total = 0;
+    // the owner's arrays that more than one phase uses: the rows, the kept events' positions and codes, the entries twice over for the
+    // sorts' double buffer, the sorts' temporary storage and what each sort asked for
+    StrandRow *d_rows = nullptr;
+    uint32_t *d_kpos = nullptr, *d_kcode = nullptr, *d_hash[2] = {nullptr, nullptr};
+    uint64_t *d_y[2] = {nullptr, nullptr};
+    void *d_tmp = nullptr;
+    size_t tmp_a = 0, tmp_b = 0;
+    // filter | emit | sort; w > 0: hash | count + scan, write.  evf: between the three tiled launches (ev[0] and ev[1] lie around them)
+    hipEvent_t ev[8] = {}, evf[2] = {}, sort_from = nullptr, sort_done = nullptr;
+    uint64_t N = 0, emers = 0;           // the entries in d_hash[0] / d_y[0]; w > 0: the e-mers over all strands
+    unsigned long long written = 0;      // w > 0: what k_sb_min_write put down
+    float ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, min_ms[3] = {0.f, 0.f, 0.f}, filter_ms[3] = {0.f, 0.f, 0.f};
+    std::vector<uint32_t> h_hash;        // the sorted entries at home (not resident)
+    std::vector<uint64_t> h_y;
+    DeviceTable table;
+    Owner own;
+
+    Build(rawdtw_ctx *c, const rawdtw_seed_pars_t *p, rawdtw_seed_index **o, const char *what, bool res, bool from)
+        : ctx(c), pars(p), out(o), resident(res), windowed(!from && p->w > 0), from_entries(from), own(c, what)
+    {
+    }
+};
+
+// ---- the table's launches (rawdtw_seed_index_build_resident, rawdtw_seed_table_from_entries) ----------------------------------------------
+// t: the caller's, for n_keys, n_list and the flags come home into it.  A failed call leaves nothing on the device.
+int table_on_device(rawdtw_ctx *ctx, const uint32_t *d_hash, const uint64_t *d_y, uint64_t n, DeviceTable &t)
 {
-    DeviceTable t;
-    uint64_t *d_start = nullptr, *d_loff = nullptr, *d_count = nullptr;
+    Owner own(ctx, "the seed table's device build");
+    const hipStream_t s = ctx->stream;
+    const rocprim::counting_iterator<uint64_t> index(0);
+    uint64_t *d_start = nullptr, *d_count = nullptr, *d_loff = nullptr, *d_list = nullptr;
     unsigned long long *d_flags = nullptr;
     uint32_t *d_tab = nullptr;
-    void *d_tmp = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    unsigned long long flags[3] = {0, 0, 0};
-    int st = RAWDTW_OK;
-    hipError_t e = hipSuccess;
-    auto hip_ok = [&](hipError_t r) { if (e == hipSuccess) e = r; return e == hipSuccess; };
-    hipStream_t s = ctx->stream;
-    const rocprim::counting_iterator<uint64_t> index(0);
-    for (int i = 0; i < 2; i++) hip_ok(hipEventCreate(&ev[i]));
-    hip_ok(hipMalloc((void **)&d_count, 16));
-    hip_ok(hipMalloc((void **)&d_flags, sizeof(flags)));
-    if (e == hipSuccess) hip_ok(hipMemsetAsync(d_flags, 0, sizeof(flags), s));
-    if (e == hipSuccess) hip_ok(hipEventRecord(ev[0], s));
+    Slot *d_slots = nullptr;
+    void *tmp = nullptr;
+    t = DeviceTable{};
+    const hipEvent_t ev0 = own.event(), ev1 = own.event();
+    SB_HIP(own, own.err);
+    SB_HIP(own, own.take(d_count, 2));
+    SB_HIP(own, own.take(d_flags, 3));
+    SB_HIP(own, hipMemsetAsync(d_flags, 0, sizeof(t.flags), s));
+    SB_HIP(own, hipEventRecord(ev0, s));
     if (n) { // the groups' starts, compacted in order; their number comes home
-        size_t bytes = 0;
-        hip_ok(hipMalloc((void **)&d_start, n * 8));
-        if (e == hipSuccess) hip_ok(rocprim::select(nullptr, bytes, index, d_start, d_count, (size_t)n, GroupHead{d_hash}, s));
-        if (e == hipSuccess) hip_ok(hipMalloc(&d_tmp, std::max<size_t>(bytes, 16)));
-        if (e == hipSuccess) hip_ok(rocprim::select(d_tmp, bytes, index, d_start, d_count, (size_t)n, GroupHead{d_hash}, s));
-        if (e == hipSuccess) hip_ok(hipMemcpyAsync(&t.n_keys, d_count, 8, hipMemcpyDeviceToHost, s));
-        if (e == hipSuccess) hip_ok(hipStreamSynchronize(s));
-        if (d_tmp) { (void)hipFree(d_tmp); d_tmp = nullptr; }
+        SB_HIP(own, own.take(d_start, n));
+        SB_HIP(own, prim_run(own, tmp, [&](void *p, size_t &bytes) { return rocprim::select(p, bytes, index, d_start, d_count, (size_t)n, GroupHead{d_hash}, s); }));
+        SB_HIP(own, hipMemcpyAsync(&t.n_keys, d_count, 8, hipMemcpyDeviceToHost, s));
+        SB_HIP(own, hipStreamSynchronize(s));
+        (void)hipFree(own.release(tmp));
     }
-    if (e == hipSuccess) {
-        t.lg = table_log2_slots(t.n_keys);
-        if (!t.lg) st = RAWDTW_ERR_RANGE;
+    t.lg = table_log2_slots(t.n_keys);
+    if (!t.lg) return fail(ctx, RAWDTW_ERR_RANGE, "more keys than 2^30, or a key with 2^32 positions or more");
+    const uint64_t n_slots = 1ull << t.lg;
+    SB_HIP(own, own.take(d_slots, n_slots));
+    if (t.n_keys) { // each list's start: the exclusive scan of the lists' lengths in ascending hash order; the total behind the last
+        const auto len = rocprim::make_transform_iterator(index, ListLen{d_start, t.n_keys, n});
+        SB_HIP(own, own.take(d_loff, t.n_keys + 1));
+        SB_HIP(own, own.take(d_tab, n_slots));
+        SB_HIP(own, prim_run(own, tmp, [&](void *p, size_t &bytes) {
+                   return rocprim::exclusive_scan(p, bytes, len, d_loff, (uint64_t)0, (size_t)(t.n_keys + 1), rocprim::plus<uint64_t>(), s);
+               }));
+        SB_HIP(own, hipMemcpyAsync(&t.n_list, d_loff + t.n_keys, 8, hipMemcpyDeviceToHost, s));
+        SB_HIP(own, hipMemsetAsync(d_tab, 0xff, n_slots * 4, s)); // (kNoEntry in every slot)
+        const uint32_t by_key = (uint32_t)std::min<uint64_t>((t.n_keys + 255) / 256, 1u << 20), by_slot = (uint32_t)std::min<uint64_t>((n_slots + 255) / 256, 1u << 20);
+        SB_LAUNCH(own, k_tb_insert, dim3(by_key), dim3(256), d_hash, d_start, (uint32_t)t.n_keys, t.lg, d_tab, d_flags);
+        SB_LAUNCH(own, k_tb_slots, dim3(by_slot), dim3(256), d_hash, d_y, d_start, d_loff, t.n_keys, n, t.lg, d_tab, d_slots, d_flags);
+        SB_HIP(own, hipStreamSynchronize(s)); // (the lists' total is home)
+        (void)hipFree(own.release(tmp));
+    } else SB_HIP(own, hipMemsetAsync(d_slots, 0, n_slots * sizeof(Slot), s));
+    SB_HIP(own, own.take(d_list, std::max<uint64_t>(t.n_list, 1)));
+    if (t.n_list) { // pos: the y of the groups with more than one entry, compacted in sorted order
+        const auto in_list = rocprim::make_transform_iterator(index, InList{d_hash, n});
+        SB_HIP(own, prim_run(own, tmp, [&](void *p, size_t &bytes) { return rocprim::select(p, bytes, d_y, in_list, d_list, d_count + 1, (size_t)n, s); }));
     }
-    if (e == hipSuccess && st == RAWDTW_OK) {
-        const uint64_t n_slots = 1ull << t.lg;
-        hip_ok(hipMalloc((void **)&t.d_slots, n_slots * sizeof(Slot)));
-        if (t.n_keys) { // each list's start: the exclusive scan of the lists' lengths in ascending hash order; the total behind the last
-            size_t bytes = 0;
-            const auto len = rocprim::make_transform_iterator(index, ListLen{d_start, t.n_keys, n});
-            hip_ok(hipMalloc((void **)&d_loff, (t.n_keys + 1) * 8));
-            hip_ok(hipMalloc((void **)&d_tab, n_slots * 4));
-            if (e == hipSuccess) hip_ok(rocprim::exclusive_scan(nullptr, bytes, len, d_loff, (uint64_t)0, (size_t)(t.n_keys + 1), rocprim::plus<uint64_t>(), s));
-            if (e == hipSuccess) hip_ok(hipMalloc(&d_tmp, std::max<size_t>(bytes, 16)));
-            if (e == hipSuccess) hip_ok(rocprim::exclusive_scan(d_tmp, bytes, len, d_loff, (uint64_t)0, (size_t)(t.n_keys + 1), rocprim::plus<uint64_t>(), s));
-            if (e == hipSuccess) hip_ok(hipMemcpyAsync(&t.n_list, d_loff + t.n_keys, 8, hipMemcpyDeviceToHost, s));
-            if (e == hipSuccess) hip_ok(hipMemsetAsync(d_tab, 0xff, n_slots * 4, s)); // (kNoEntry in every slot)
-            if (e == hipSuccess) {
-                const uint32_t blocks = (uint32_t)std::min<uint64_t>((t.n_keys + 255) / 256, 1u << 20);
-                hipLaunchKernelGGL(k_tb_insert, dim3(blocks), dim3(256), 0, s, d_hash, d_start, (uint32_t)t.n_keys, t.lg, d_tab, d_flags);
-                hip_ok(hipGetLastError());
-            }
-            if (e == hipSuccess) {
-                const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_slots + 255) / 256, 1u << 20);
-                hipLaunchKernelGGL(k_tb_slots, dim3(blocks), dim3(256), 0, s, d_hash, d_y, d_start, d_loff, t.n_keys, n, t.lg, d_tab, t.d_slots, d_flags);
-                hip_ok(hipGetLastError());
-            }
-            if (e == hipSuccess) hip_ok(hipStreamSynchronize(s)); // (the lists' total is home)
-            if (d_tmp) { (void)hipFree(d_tmp); d_tmp = nullptr; }
-        } else if (e == hipSuccess) hip_ok(hipMemsetAsync(t.d_slots, 0, n_slots * sizeof(Slot), s));
-        if (e == hipSuccess) hip_ok(hipMalloc((void **)&t.d_list, std::max<uint64_t>(t.n_list, 1) * 8));
-        if (e == hipSuccess && t.n_list) { // pos: the y of the groups with more than one entry, compacted in sorted order
-            size_t bytes = 0;
-            const auto in_list = rocprim::make_transform_iterator(index, InList{d_hash, n});
-            hip_ok(rocprim::select(nullptr, bytes, d_y, in_list, t.d_list, d_count + 1, (size_t)n, s));
-            if (e == hipSuccess) hip_ok(hipMalloc(&d_tmp, std::max<size_t>(bytes, 16)));
-            if (e == hipSuccess) hip_ok(rocprim::select(d_tmp, bytes, d_y, in_list, t.d_list, d_count + 1, (size_t)n, s));
-        }
-        if (e == hipSuccess) hip_ok(hipEventRecord(ev[1], s));
-        if (e == hipSuccess) hip_ok(hipMemcpyAsync(flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost, s));
-        if (e == hipSuccess) hip_ok(hipStreamSynchronize(s));
-        if (e == hipSuccess) (void)hipEventElapsedTime(&t.ms, ev[0], ev[1]);
-    }
-    if (e != hipSuccess) (void)hipStreamSynchronize(s);
-    for (void *p : {(void *)d_start, (void *)d_loff, (void *)d_count, (void *)d_flags, (void *)d_tab, d_tmp}) if (p) (void)hipFree(p);
-    for (int i = 0; i < 2; i++) if (ev[i]) (void)hipEventDestroy(ev[i]);
-    if (e == hipSuccess && st == RAWDTW_OK && flags[0]) st = RAWDTW_ERR_INTERNAL;
-    if (e == hipSuccess && st == RAWDTW_OK && flags[1]) st = RAWDTW_ERR_RANGE;
-    if (e != hipSuccess || st != RAWDTW_OK) {
-        if (t.d_slots) (void)hipFree(t.d_slots);
-        if (t.d_list) (void)hipFree(t.d_list);
-        if (e != hipSuccess) return hip_fail(ctx, e, "the seed table's device build");
-        return fail(ctx, st, st == RAWDTW_ERR_INTERNAL ? "a key found no free slot in a table at most half full" : "more keys than 2^30, or a key with 2^32 positions or more");
-    }
-    t.displaced = flags[2];
-    *out = t;
+    SB_HIP(own, hipEventRecord(ev1, s));
+    SB_HIP(own, hipMemcpyAsync(t.flags, d_flags, sizeof(t.flags), hipMemcpyDeviceToHost, s));
+    SB_HIP(own, hipStreamSynchronize(s));
+    (void)hipEventElapsedTime(&t.ms, ev0, ev1);
+    if (t.flags[0]) return fail(ctx, RAWDTW_ERR_INTERNAL, "a key found no free slot in a table at most half full");
+    if (t.flags[1]) return fail(ctx, RAWDTW_ERR_RANGE, "more keys than 2^30, or a key with 2^32 positions or more");
+    t.displaced = t.flags[2];
+    t.d_slots = own.release(d_slots);
+    t.d_list = own.release(d_list);
     return RAWDTW_OK;
 }
 
-// a resident index's handle: the header alone
-static rawdtw_seed_index *resident_handle(rawdtw_ctx *ctx, rawdtw_seed_index *six, const DeviceTable &t, uint64_t n_positions)
-{
-    six->log2_slots = t.lg; six->n_keys = t.n_keys; six->n_positions = n_positions; six->n_list = t.n_list;
-    six->resident = true; six->owner = ctx;
-    return six;
-}
-
-// All three entries: the checks, the filter, then the entries -- k_sb_emit for w == 0, the hash / count / scan / write launches for w > 0
-// (min_ok: the entry takes them) -- the two sorts, the entries' way home and fill_table.  resident: the filter is the three tiled
-// launches, nothing comes home, and the table is built on the device and installed as the context's behind the last check.
-static int build_device(rawdtw_ctx *ctx, const rawdtw_seed_pars_t *pars, rawdtw_seed_index **out, bool min_ok, bool resident = false)
+// ---- the phases of a build ---------------------------------------------------------------------------------------------------------------
+// 1. everything a build refuses (min_ok: the entry takes w > 0)
+int build_checks(rawdtw_ctx *ctx, const rawdtw_seed_pars_t *pars, rawdtw_seed_index **out, bool min_ok, bool resident)
 {
     if (!ctx || !out) return RAWDTW_ERR_INVALID;
     *out = nullptr;
@@ -515,270 +616,306 @@ static int build_device(rawdtw_ctx *ctx, const rawdtw_seed_pars_t *pars, rawdtw_
     if (pars->w > 0 && !min_ok) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, "w > 0: minimizer windows over whole strands are built on the host");
     if (resident)
         if (const int no = seed_table_installable(ctx)) return no;
-    const bool windowed = pars->w > 0;
-    const uint32_t n_seq = (uint32_t)ctx->ref_len.size();
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::vector<StrandRow> rows;
-    std::vector<uint64_t> tile0; // resident: a strand's first tile of kFilterTile events among all strands' tiles
-    uint64_t total_len = 0, max_len = 0, f_tiles = 0;
-    try { rows.resize(2ull * n_seq); tile0.resize(2ull * n_seq); } catch (const std::bad_alloc &) { return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed"); }
-    for (uint32_t s = 0; s < n_seq; s++)
+    return RAWDTW_OK;
+}
+
+// the handle the call will return: the parameters, the sequences and a fresh serial
+int new_handle(Build &b, uint32_t n_seq)
+{
+    b.six.reset(new (std::nothrow) rawdtw_seed_index);
+    if (!b.six) return fail(b.ctx, RAWDTW_ERR_OOM, "host allocation failed");
+    b.six->pars = *b.pars; b.six->n_seq = n_seq; b.six->serial = next_serial();
+    return RAWDTW_OK;
+}
+
+// 2. a row a strand, on the host
+int strand_rows(Build &b)
+{
+    const rawdtw_ctx *ctx = b.ctx;
+    b.n_seq = (uint32_t)ctx->ref_len.size();
+    try { b.rows.resize(2ull * b.n_seq); b.tile0.resize(2ull * b.n_seq); } catch (const std::bad_alloc &) { return fail(b.ctx, RAWDTW_ERR_OOM, "host allocation failed"); }
+    for (uint32_t s = 0; s < b.n_seq; s++)
         for (int slot = 0; slot < 2; slot++) { // slot 0: forward (strand 1)
-            rows[2 * s + slot] = StrandRow{ctx->ref_off[2 * s + slot], total_len, 0, ctx->ref_len[s], 0};
-            tile0[2 * s + slot] = f_tiles;
-            f_tiles += ((uint64_t)ctx->ref_len[s] + kFilterTile - 1) / kFilterTile;
-            total_len += ctx->ref_len[s];
-            max_len = std::max<uint64_t>(max_len, ctx->ref_len[s]);
+            b.rows[2 * s + slot] = StrandRow{ctx->ref_off[2 * s + slot], b.total_len, 0, ctx->ref_len[s], 0};
+            b.tile0[2 * s + slot] = b.f_tiles;
+            b.f_tiles += filter_tiles(ctx->ref_len[s]);
+            b.total_len += ctx->ref_len[s];
+            b.max_len = std::max<uint64_t>(b.max_len, ctx->ref_len[s]);
         }
-    rawdtw_seed_index *six = new (std::nothrow) rawdtw_seed_index;
-    if (!six) return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed");
-    six->pars = *pars; six->n_seq = n_seq; six->serial = next_serial();
-    StrandRow *d_rows = nullptr;
-    uint32_t *d_kpos = nullptr, *d_kcode = nullptr, *d_hash[2] = {nullptr, nullptr};
-    uint64_t *d_y[2] = {nullptr, nullptr};
-    void *d_tmp = nullptr;
-    // w > 0: the e-mers' hashes, a count a tile (and a 0 behind the last), their exclusive scan (the total behind the last), the word
-    // k_sb_min_write counts its elements in, the scan's temporary storage
+    while (b.seq_bits < 32 && (1ull << b.seq_bits) < b.n_seq) b.seq_bits++;
+    return RAWDTW_OK;
+}
+
+// 3. the filter's launches between ev[0] and ev[1]: k_sb_filter, a wave a strand, or the three tiled launches with their words (a next |
+// steps word and a last value an event, an entry and a kept count a tile)
+template <bool kMask> int filter_launches(Build &b)
+{
+    Owner &own = b.own;
+    const hipStream_t s = b.ctx->stream;
+    const uint32_t pairs = 2 * b.n_seq;
+    if (!b.resident) {
+        SB_HIP(own, hipEventRecord(b.ev[0], s));
+        SB_LAUNCH(own, k_sb_filter<kMask>, dim3(pairs), dim3(64), b.ctx->d_ref, b.d_rows, b.pars->q, b.pars->lq, b.d_kpos, b.d_kcode);
+        return RAWDTW_OK;
+    }
+    uint32_t *d_nc = nullptr, *d_tentry = nullptr, *d_tkept = nullptr;
+    float *d_xe = nullptr;
+    uint64_t *d_tile0 = nullptr;
+    SB_HIP(own, own.take(d_nc, b.total_len));
+    SB_HIP(own, own.take(d_xe, b.total_len));
+    SB_HIP(own, own.take(d_tile0, b.tile0.size()));
+    SB_HIP(own, own.take(d_tentry, b.f_tiles));
+    SB_HIP(own, own.take(d_tkept, b.f_tiles));
+    SB_HIP(own, hipMemcpyAsync(d_tile0, b.tile0.data(), b.tile0.size() * 8, hipMemcpyHostToDevice, s));
+    SB_HIP(own, hipEventRecord(b.ev[0], s));
+    const dim3 by_tile(pairs, std::min(filter_tiles((uint32_t)b.max_len), kTileGridY));
+    SB_LAUNCH(own, k_sb_next<kMask>, by_tile, dim3(256), b.ctx->d_ref, b.d_rows, d_nc, d_xe);
+    SB_HIP(own, hipEventRecord(b.evf[0], s));
+    SB_LAUNCH(own, k_sb_chain<kMask>, dim3(pairs), dim3(64), b.ctx->d_ref, b.d_rows, d_tile0, d_nc, d_xe, d_tentry, d_tkept);
+    SB_HIP(own, hipEventRecord(b.evf[1], s));
+    SB_LAUNCH(own, k_sb_mark, by_tile, dim3(64), b.ctx->d_ref, b.d_rows, d_tile0, d_nc, d_tentry, d_tkept, b.pars->q, b.pars->lq, b.d_kpos, b.d_kcode);
+    return RAWDTW_OK;
+}
+
+// the kept events' positions and codes in d_kpos / d_kcode; the rows come home with every strand's kept events
+int filter(Build &b)
+{
+    Owner &own = b.own;
+    const hipStream_t s = b.ctx->stream;
+    const size_t rows_bytes = b.rows.size() * sizeof(StrandRow);
+    SB_HIP(own, own.take(b.d_rows, b.rows.size()));
+    SB_HIP(own, own.take(b.d_kpos, b.total_len));
+    SB_HIP(own, own.take(b.d_kcode, b.total_len));
+    SB_HIP(own, hipMemcpyAsync(b.d_rows, b.rows.data(), rows_bytes, hipMemcpyHostToDevice, s));
+    SB_TRY(b.windowed ? filter_launches<false>(b) : filter_launches<true>(b));
+    SB_HIP(own, hipEventRecord(b.ev[1], s));
+    SB_HIP(own, hipMemcpyAsync(b.rows.data(), b.d_rows, rows_bytes, hipMemcpyDeviceToHost, s));
+    SB_HIP(own, hipStreamSynchronize(s));
+    (void)hipEventElapsedTime(&b.ms[0], b.ev[0], b.ev[1]);
+    if (b.resident) {
+        (void)hipEventElapsedTime(&b.filter_ms[0], b.ev[0], b.evf[0]);
+        (void)hipEventElapsedTime(&b.filter_ms[1], b.evf[0], b.evf[1]);
+        (void)hipEventElapsedTime(&b.filter_ms[2], b.evf[1], b.ev[1]);
+        for (const StrandRow &r : b.rows) b.kept_total += r.kept;
+    }
+    return RAWDTW_OK;
+}
+
+// the two sorts of the N entries in d_hash[0] / d_y[0]: stable by y over its used bits, then stable by hash -- the order of
+// by_hash_then_position.  With no storage: what each asks for.
+int two_sorts(Build &b, void *tmp)
+{
+    SB_HIP(b.own, rocprim::radix_sort_pairs(tmp, b.tmp_a, b.d_y[0], b.d_y[1], b.d_hash[0], b.d_hash[1], (size_t)b.N, 0u, 32u + b.seq_bits, b.ctx->stream));
+    SB_HIP(b.own, rocprim::radix_sort_pairs(tmp, b.tmp_b, b.d_hash[1], b.d_hash[0], b.d_y[1], b.d_y[0], (size_t)b.N, 0u, 32u, b.ctx->stream));
+    return RAWDTW_OK;
+}
+
+// the entry arrays for N entries, twice over, and the sorts' temporary storage
+int sort_arrays(Build &b)
+{
+    for (int i = 0; i < 2; i++) {
+        SB_HIP(b.own, b.own.take(b.d_hash[i], b.N));
+        SB_HIP(b.own, b.own.take(b.d_y[i], b.N));
+    }
+    SB_TRY(two_sorts(b, nullptr));
+    SB_HIP(b.own, prim_take(b.own, b.d_tmp, std::max(b.tmp_a, b.tmp_b)));
+    return RAWDTW_OK;
+}
+
+// 4. the entries, w == 0: every e-mer of every strand, a row's entry_base its first
+int entries_all(Build &b)
+{
+    Owner &own = b.own;
+    const hipStream_t s = b.ctx->stream;
+    uint64_t max_n = 0;
+    for (StrandRow &r : b.rows) {
+        r.entry_base = b.N;
+        const uint64_t n = strand_emers(r.kept, b.pars->e);
+        b.N += n; max_n = std::max(max_n, n);
+    }
+    if (!b.N) return RAWDTW_OK;
+    SB_TRY(sort_arrays(b));
+    SB_HIP(own, hipMemcpyAsync(b.d_rows, b.rows.data(), b.rows.size() * sizeof(StrandRow), hipMemcpyHostToDevice, s));
+    SB_HIP(own, hipEventRecord(b.ev[2], s));
+    const uint32_t gy = (uint32_t)std::min<uint64_t>((max_n + 255) / 256, 1024);
+    SB_LAUNCH(own, k_sb_emit, dim3(2 * b.n_seq, gy), dim3(256), b.d_rows, b.d_kpos, b.d_kcode, b.pars->e, b.pars->lq + 2, b.d_hash[0], b.d_y[0]);
+    SB_HIP(own, hipEventRecord(b.ev[3], s));
+    b.sort_from = b.ev[3]; b.sort_done = b.ev[4];
+    return RAWDTW_OK;
+}
+
+// 4. the entries, w > 0: the e-mers' hashes, a count a tile of kMinTile e-mers (and a 0 behind the last), their exclusive scan (the total
+// behind the last), and the write at the scan's places, which counts what it puts down in a word.  A row's entry_base is its first tile.
+int entries_minimizers(Build &b)
+{
+    Owner &own = b.own;
+    const hipStream_t s = b.ctx->stream;
+    const rawdtw_seed_pars_t &p = *b.pars;
+    uint64_t n_tiles = 0, max_tiles = 0;
+    for (StrandRow &r : b.rows) {
+        r.entry_base = n_tiles;
+        const uint64_t n = strand_emers(r.kept, p.e), tiles = (n + kMinTile - 1) / kMinTile;
+        b.emers += n; n_tiles += tiles; max_tiles = std::max(max_tiles, tiles);
+    }
+    if (!n_tiles) return RAWDTW_OK;
+    const dim3 grid(2 * b.n_seq, (uint32_t)std::min<uint64_t>(max_tiles, 1024)); // (a hash launch's blocks take kMinTile e-mers at a time too)
     uint32_t *d_h = nullptr;
     uint64_t *d_cnt = nullptr, *d_off = nullptr;
     unsigned long long *d_written = nullptr;
     void *d_scan_tmp = nullptr;
-    // resident: the tiled filter's words (a next | steps word and a last value an event, an entry and a kept count a tile) and its events
-    uint32_t *d_nc = nullptr, *d_tentry = nullptr, *d_tkept = nullptr;
-    float *d_xe = nullptr;
-    uint64_t *d_tile0 = nullptr;
-    hipEvent_t evf[2] = {nullptr, nullptr}; // between the three launches (ev[0] and ev[1] lie around them)
-    float filter_ms[3] = {0.f, 0.f, 0.f};
-    DeviceTable table;
-    uint64_t kept_total = 0;
-    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // filter | emit | sort; w > 0: hash | count + scan, write
-    float ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, min_ms[3] = {0.f, 0.f, 0.f};
-    int st = RAWDTW_OK;
-    std::vector<uint32_t> h_hash;
-    std::vector<uint64_t> h_y;
-    std::vector<Entry> all;
-    uint64_t N = 0, emers = 0;
-    hipError_t e = hipSuccess;
-    auto hip_ok = [&](hipError_t r) { if (e == hipSuccess) e = r; return e == hipSuccess; };
-    size_t tmp_a = 0, tmp_b = 0;
-    uint32_t seq_bits = 0;
-    while (seq_bits < 32 && (1ull << seq_bits) < n_seq) seq_bits++;
-    // the entry arrays for N entries, twice over, and the sorts' temporary storage
-    auto sort_arrays = [&]() {
-        for (int i = 0; i < 2; i++) { hip_ok(hipMalloc((void **)&d_hash[i], N * 4)); hip_ok(hipMalloc((void **)&d_y[i], N * 8)); }
-        if (e == hipSuccess) hip_ok(rocprim::radix_sort_pairs(nullptr, tmp_a, d_y[0], d_y[1], d_hash[0], d_hash[1], (size_t)N, 0u, 32u + seq_bits, ctx->stream));
-        if (e == hipSuccess) hip_ok(rocprim::radix_sort_pairs(nullptr, tmp_b, d_hash[1], d_hash[0], d_y[1], d_y[0], (size_t)N, 0u, 32u, ctx->stream));
-        if (e == hipSuccess) hip_ok(hipMalloc(&d_tmp, std::max<size_t>(std::max(tmp_a, tmp_b), 16)));
+    size_t scan_bytes = 0;
+    SB_HIP(own, own.take(d_h, b.total_len));
+    SB_HIP(own, own.take(d_cnt, n_tiles + 1));
+    SB_HIP(own, own.take(d_off, n_tiles + 1));
+    SB_HIP(own, own.take(d_written, 1));
+    const auto scan = [&](void *tmp, size_t &bytes) {
+        return rocprim::exclusive_scan(tmp, bytes, d_cnt, d_off, (uint64_t)0, (size_t)(n_tiles + 1), rocprim::plus<uint64_t>(), s);
     };
-    // the entries in d_hash[0] / d_y[0]: stable by y, then stable by hash, then home (from: the event at the sorts' start, done: at their end)
-    auto sort_and_home = [&](hipEvent_t from, hipEvent_t done) {
-        if (e == hipSuccess) hip_ok(rocprim::radix_sort_pairs(d_tmp, tmp_a, d_y[0], d_y[1], d_hash[0], d_hash[1], (size_t)N, 0u, 32u + seq_bits, ctx->stream));
-        if (e == hipSuccess) hip_ok(rocprim::radix_sort_pairs(d_tmp, tmp_b, d_hash[1], d_hash[0], d_y[1], d_y[0], (size_t)N, 0u, 32u, ctx->stream));
-        if (e == hipSuccess) hip_ok(hipEventRecord(done, ctx->stream));
-        if (e == hipSuccess) hip_ok(hipEventSynchronize(done));
-        const double t0 = now_ms();
-        if (!resident) try { h_hash.resize(N); h_y.resize(N); } catch (const std::bad_alloc &) { st = RAWDTW_ERR_OOM; }
-        if (!resident && st == RAWDTW_OK && e == hipSuccess) {
-            hip_ok(hipMemcpyAsync(h_hash.data(), d_hash[0], N * 4, hipMemcpyDeviceToHost, ctx->stream));
-            hip_ok(hipMemcpyAsync(h_y.data(), d_y[0], N * 8, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        hip_ok(hipStreamSynchronize(ctx->stream));
-        if (e == hipSuccess && st == RAWDTW_OK) {
-            (void)hipEventElapsedTime(&ms[2], from, done);
-            ms[3] = (float)(now_ms() - t0);
-        }
-    };
-    for (int i = 0; i < 8; i++) hip_ok(hipEventCreate(&ev[i]));
-    if (resident) for (int i = 0; i < 2; i++) hip_ok(hipEventCreate(&evf[i]));
-    if (n_seq && total_len) {
-        hip_ok(hipMalloc((void **)&d_rows, rows.size() * sizeof(StrandRow)));
-        hip_ok(hipMalloc((void **)&d_kpos, total_len * 4));
-        hip_ok(hipMalloc((void **)&d_kcode, total_len * 4));
-        if (e == hipSuccess) hip_ok(hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(StrandRow), hipMemcpyHostToDevice, ctx->stream));
-        if (resident) {
-            hip_ok(hipMalloc((void **)&d_nc, total_len * 4));
-            hip_ok(hipMalloc((void **)&d_xe, total_len * 4));
-            hip_ok(hipMalloc((void **)&d_tile0, tile0.size() * 8));
-            hip_ok(hipMalloc((void **)&d_tentry, f_tiles * 4));
-            hip_ok(hipMalloc((void **)&d_tkept, f_tiles * 4));
-            if (e == hipSuccess) hip_ok(hipMemcpyAsync(d_tile0, tile0.data(), tile0.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-        }
-        if (e == hipSuccess) hip_ok(hipEventRecord(ev[0], ctx->stream));
-        if (e == hipSuccess && resident) {
-            const dim3 by_tile(2 * n_seq, (uint32_t)std::min<uint64_t>((max_len + kFilterTile - 1) / kFilterTile, kTileGridY));
-            if (windowed) hipLaunchKernelGGL(k_sb_next<false>, by_tile, dim3(256), 0, ctx->stream, ctx->d_ref, d_rows, d_nc, d_xe);
-            else hipLaunchKernelGGL(k_sb_next<true>, by_tile, dim3(256), 0, ctx->stream, ctx->d_ref, d_rows, d_nc, d_xe);
-            hip_ok(hipGetLastError());
-            if (e == hipSuccess) hip_ok(hipEventRecord(evf[0], ctx->stream));
-            if (e == hipSuccess) {
-                if (windowed) hipLaunchKernelGGL(k_sb_chain<false>, dim3(2 * n_seq), dim3(64), 0, ctx->stream, ctx->d_ref, d_rows, d_tile0, d_nc, d_xe, d_tentry, d_tkept);
-                else hipLaunchKernelGGL(k_sb_chain<true>, dim3(2 * n_seq), dim3(64), 0, ctx->stream, ctx->d_ref, d_rows, d_tile0, d_nc, d_xe, d_tentry, d_tkept);
-                hip_ok(hipGetLastError());
-            }
-            if (e == hipSuccess) hip_ok(hipEventRecord(evf[1], ctx->stream));
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(k_sb_mark, by_tile, dim3(64), 0, ctx->stream, ctx->d_ref, d_rows, d_tile0, d_nc, d_tentry, d_tkept, pars->q, pars->lq, d_kpos, d_kcode);
-                hip_ok(hipGetLastError());
-            }
-        }
-        if (e == hipSuccess && !resident) {
-            if (windowed) hipLaunchKernelGGL(k_sb_filter<false>, dim3(2 * n_seq), dim3(64), 0, ctx->stream, ctx->d_ref, d_rows, pars->q, pars->lq, d_kpos, d_kcode);
-            else hipLaunchKernelGGL(k_sb_filter<true>, dim3(2 * n_seq), dim3(64), 0, ctx->stream, ctx->d_ref, d_rows, pars->q, pars->lq, d_kpos, d_kcode);
-            hip_ok(hipGetLastError());
-        }
-        if (e == hipSuccess) hip_ok(hipEventRecord(ev[1], ctx->stream));
-        if (e == hipSuccess) hip_ok(hipMemcpyAsync(rows.data(), d_rows, rows.size() * sizeof(StrandRow), hipMemcpyDeviceToHost, ctx->stream));
-        if (e == hipSuccess) hip_ok(hipStreamSynchronize(ctx->stream));
-        if (e == hipSuccess && !windowed) {
-            uint64_t max_n = 0;
-            for (StrandRow &r : rows) {
-                r.entry_base = N;
-                const uint64_t n = r.kept >= pars->e ? r.kept - pars->e + 1 : 0;
-                N += n; max_n = std::max(max_n, n);
-            }
-            if (N) {
-                sort_arrays();
-                if (e == hipSuccess) hip_ok(hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(StrandRow), hipMemcpyHostToDevice, ctx->stream));
-                if (e == hipSuccess) hip_ok(hipEventRecord(ev[2], ctx->stream));
-                if (e == hipSuccess) {
-                    const uint32_t gy = (uint32_t)std::min<uint64_t>((max_n + 255) / 256, 1024);
-                    hipLaunchKernelGGL(k_sb_emit, dim3(2 * n_seq, gy), dim3(256), 0, ctx->stream, d_rows, d_kpos, d_kcode, pars->e, pars->lq + 2, d_hash[0],
-                                       d_y[0]);
-                    hip_ok(hipGetLastError());
-                }
-                if (e == hipSuccess) hip_ok(hipEventRecord(ev[3], ctx->stream));
-                sort_and_home(ev[3], ev[4]);
-                if (e == hipSuccess && st == RAWDTW_OK) (void)hipEventElapsedTime(&ms[1], ev[2], ev[3]);
-            }
-        }
-        if (e == hipSuccess && windowed) {
-            uint64_t n_tiles = 0, max_tiles = 0;
-            for (StrandRow &r : rows) {
-                r.entry_base = n_tiles; // (the strand's first tile)
-                const uint64_t n = r.kept >= pars->e ? r.kept - pars->e + 1 : 0, tiles = (n + kMinTile - 1) / kMinTile;
-                emers += n; n_tiles += tiles; max_tiles = std::max(max_tiles, tiles);
-            }
-            if (n_tiles) {
-                size_t scan_bytes = 0;
-                const uint32_t gy = (uint32_t)std::min<uint64_t>(max_tiles, 1024); // (a hash launch's blocks take kMinTile e-mers at a time too)
-                hip_ok(hipMalloc((void **)&d_h, total_len * 4));
-                hip_ok(hipMalloc((void **)&d_cnt, (n_tiles + 1) * 8));
-                hip_ok(hipMalloc((void **)&d_off, (n_tiles + 1) * 8));
-                hip_ok(hipMalloc((void **)&d_written, 8));
-                if (e == hipSuccess) hip_ok(rocprim::exclusive_scan(nullptr, scan_bytes, d_cnt, d_off, (uint64_t)0, (size_t)(n_tiles + 1), rocprim::plus<uint64_t>(), ctx->stream));
-                if (e == hipSuccess) hip_ok(hipMalloc(&d_scan_tmp, std::max<size_t>(scan_bytes, 16)));
-                if (e == hipSuccess) hip_ok(hipMemsetAsync(d_cnt + n_tiles, 0, 8, ctx->stream));
-                if (e == hipSuccess) hip_ok(hipMemsetAsync(d_written, 0, 8, ctx->stream));
-                if (e == hipSuccess) hip_ok(hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(StrandRow), hipMemcpyHostToDevice, ctx->stream));
-                if (e == hipSuccess) hip_ok(hipEventRecord(ev[2], ctx->stream));
-                if (e == hipSuccess) {
-                    hipLaunchKernelGGL(k_sb_hash, dim3(2 * n_seq, gy), dim3(256), 0, ctx->stream, d_rows, d_kcode, pars->e, pars->lq + 2, d_h);
-                    hip_ok(hipGetLastError());
-                }
-                if (e == hipSuccess) hip_ok(hipEventRecord(ev[3], ctx->stream));
-                if (e == hipSuccess) {
-                    hipLaunchKernelGGL(k_sb_min_count, dim3(2 * n_seq, gy), dim3(kMinTile), 0, ctx->stream, d_rows, d_h, pars->e, pars->w, d_cnt);
-                    hip_ok(hipGetLastError());
-                }
-                if (e == hipSuccess) hip_ok(rocprim::exclusive_scan(d_scan_tmp, scan_bytes, d_cnt, d_off, (uint64_t)0, (size_t)(n_tiles + 1), rocprim::plus<uint64_t>(), ctx->stream));
-                if (e == hipSuccess) hip_ok(hipEventRecord(ev[4], ctx->stream));
-                // the total comes home and sizes the entry arrays exactly (no cap: more entries than e-mers is legal)
-                if (e == hipSuccess) hip_ok(hipMemcpyAsync(&N, d_off + n_tiles, 8, hipMemcpyDeviceToHost, ctx->stream));
-                if (e == hipSuccess) hip_ok(hipStreamSynchronize(ctx->stream));
-                if (e != hipSuccess) N = 0;
-                if (N) {
-                    unsigned long long written = 0;
-                    sort_arrays();
-                    if (e == hipSuccess) hip_ok(hipEventRecord(ev[5], ctx->stream));
-                    if (e == hipSuccess) {
-                        hipLaunchKernelGGL(k_sb_min_write, dim3(2 * n_seq, gy), dim3(kMinTile), 0, ctx->stream, d_rows, d_h, d_kpos, pars->e, pars->w, d_off, N,
-                                           d_hash[0], d_y[0], d_written);
-                        hip_ok(hipGetLastError());
-                    }
-                    if (e == hipSuccess) hip_ok(hipEventRecord(ev[6], ctx->stream));
-                    if (e == hipSuccess) hip_ok(hipMemcpyAsync(&written, d_written, 8, hipMemcpyDeviceToHost, ctx->stream));
-                    sort_and_home(ev[6], ev[7]);
-                    if (e == hipSuccess && st == RAWDTW_OK) {
-                        (void)hipEventElapsedTime(&min_ms[0], ev[2], ev[3]);
-                        (void)hipEventElapsedTime(&min_ms[1], ev[3], ev[4]);
-                        (void)hipEventElapsedTime(&min_ms[2], ev[5], ev[6]);
-                        ms[1] = min_ms[0] + min_ms[1] + min_ms[2];
-                        if (written != N) st = RAWDTW_ERR_INTERNAL; // the write did not put down what the count counted: no table
-                    }
-                }
-            }
-        }
-        if (e == hipSuccess) (void)hipEventElapsedTime(&ms[0], ev[0], ev[1]);
-        if (e == hipSuccess && resident) {
-            (void)hipEventElapsedTime(&filter_ms[0], ev[0], evf[0]);
-            (void)hipEventElapsedTime(&filter_ms[1], evf[0], evf[1]);
-            (void)hipEventElapsedTime(&filter_ms[2], evf[1], ev[1]);
-            for (const StrandRow &r : rows) kept_total += r.kept;
-        }
-    }
-    // resident: the table from the sorted entries where they lie (no entry: 16 empty slots), before the entries are let go
-    int table_st = RAWDTW_OK;
-    if (resident && e == hipSuccess && st == RAWDTW_OK) table_st = table_on_device(ctx, d_hash[0], d_y[0], N, &table);
-    if (e != hipSuccess) (void)hipStreamSynchronize(ctx->stream);
-    for (int i = 0; i < 2; i++) if (evf[i]) (void)hipEventDestroy(evf[i]);
-    for (void *p : {(void *)d_nc, (void *)d_xe, (void *)d_tile0, (void *)d_tentry, (void *)d_tkept}) if (p) (void)hipFree(p);
-    for (int i = 0; i < 8; i++) if (ev[i]) (void)hipEventDestroy(ev[i]);
-    for (int i = 0; i < 2; i++) { if (d_hash[i]) (void)hipFree(d_hash[i]); if (d_y[i]) (void)hipFree(d_y[i]); }
-    if (d_tmp) (void)hipFree(d_tmp);
-    if (d_scan_tmp) (void)hipFree(d_scan_tmp);
-    if (d_written) (void)hipFree(d_written);
-    if (d_off) (void)hipFree(d_off);
-    if (d_cnt) (void)hipFree(d_cnt);
-    if (d_h) (void)hipFree(d_h);
-    if (d_kpos) (void)hipFree(d_kpos);
-    if (d_kcode) (void)hipFree(d_kcode);
-    if (d_rows) (void)hipFree(d_rows);
-    if (e != hipSuccess) { delete six; return hip_fail(ctx, e, resident ? "rawdtw_seed_index_build_resident" : windowed ? "rawdtw_seed_index_build_device_min" : "rawdtw_seed_index_build_device"); }
-    if (st == RAWDTW_ERR_INTERNAL) { delete six; return fail(ctx, st, "the write launch's element count is not the scan's total"); }
-    if (resident) { // behind the last check: the table becomes the context's, the handle carries the header
-        if (table_st != RAWDTW_OK) { delete six; return table_st; } // (table_on_device has said why, and freed what it made)
-        seed_table_install(ctx, table.d_slots, table.d_list, table.lg, *pars, six->serial);
-        memcpy(ctx->seed_build_ms, ms, sizeof(ms));
-        if (windowed) {
-            ctx->seed_min_emers = emers; ctx->seed_min_entries = N;
-            memcpy(ctx->seed_min_ms, min_ms, sizeof(min_ms));
-        }
-        ctx->seed_resident = rawdtw_seed_resident_stats_t{kFilterTile, table.lg, f_tiles, kept_total, N, table.n_keys, table.displaced,
-                                                          filter_ms[0], filter_ms[1], filter_ms[2], ms[1], ms[2], table.ms};
-        *out = resident_handle(ctx, six, table, N);
-        return RAWDTW_OK;
-    }
-    const double t1 = now_ms();
-    if (st == RAWDTW_OK) {
-        try {
-            all.resize(N);
-            for (uint64_t i = 0; i < N; i++) all[i] = Entry{h_hash[i], h_y[i]};
-            std::vector<uint32_t>().swap(h_hash);
-            std::vector<uint64_t>().swap(h_y);
-        } catch (const std::bad_alloc &) { st = RAWDTW_ERR_OOM; }
-    }
-    if (st == RAWDTW_OK) st = fill_table(six, all);
-    ms[4] = (float)(now_ms() - t1);
-    if (st != RAWDTW_OK) { delete six; return fail(ctx, st, "building the table failed"); }
-    memcpy(ctx->seed_build_ms, ms, sizeof(ms));
-    if (windowed) {
-        ctx->seed_min_emers = emers; ctx->seed_min_entries = N;
-        memcpy(ctx->seed_min_ms, min_ms, sizeof(min_ms));
-    }
-    *out = six;
+    SB_HIP(own, scan(nullptr, scan_bytes));
+    SB_HIP(own, prim_take(own, d_scan_tmp, scan_bytes));
+    SB_HIP(own, hipMemsetAsync(d_cnt + n_tiles, 0, 8, s));
+    SB_HIP(own, hipMemsetAsync(d_written, 0, 8, s));
+    SB_HIP(own, hipMemcpyAsync(b.d_rows, b.rows.data(), b.rows.size() * sizeof(StrandRow), hipMemcpyHostToDevice, s));
+    SB_HIP(own, hipEventRecord(b.ev[2], s));
+    SB_LAUNCH(own, k_sb_hash, grid, dim3(256), b.d_rows, b.d_kcode, p.e, p.lq + 2, d_h);
+    SB_HIP(own, hipEventRecord(b.ev[3], s));
+    SB_LAUNCH(own, k_sb_min_count, grid, dim3(kMinTile), b.d_rows, d_h, p.e, p.w, d_cnt);
+    SB_HIP(own, scan(d_scan_tmp, scan_bytes));
+    SB_HIP(own, hipEventRecord(b.ev[4], s));
+    // the total comes home and sizes the entry arrays exactly (no cap: more entries than e-mers is legal)
+    SB_HIP(own, hipMemcpyAsync(&b.N, d_off + n_tiles, 8, hipMemcpyDeviceToHost, s));
+    SB_HIP(own, hipStreamSynchronize(s));
+    if (!b.N) return RAWDTW_OK;
+    SB_TRY(sort_arrays(b));
+    SB_HIP(own, hipEventRecord(b.ev[5], s));
+    SB_LAUNCH(own, k_sb_min_write, grid, dim3(kMinTile), b.d_rows, d_h, b.d_kpos, p.e, p.w, d_off, b.N, b.d_hash[0], b.d_y[0], d_written);
+    SB_HIP(own, hipEventRecord(b.ev[6], s));
+    SB_HIP(own, hipMemcpyAsync(&b.written, d_written, 8, hipMemcpyDeviceToHost, s)); // (home behind the sorts' wait)
+    b.sort_from = b.ev[6]; b.sort_done = b.ev[7];
     return RAWDTW_OK;
 }
+
+// 5. the sorts where the entries lie; behind the wait the events of the entries' launches have passed too
+int sorts(Build &b)
+{
+    Owner &own = b.own;
+    SB_TRY(two_sorts(b, b.d_tmp));
+    SB_HIP(own, hipEventRecord(b.sort_done, b.ctx->stream));
+    SB_HIP(own, hipEventSynchronize(b.sort_done));
+    (void)hipEventElapsedTime(&b.ms[2], b.sort_from, b.sort_done);
+    if (!b.windowed) {
+        (void)hipEventElapsedTime(&b.ms[1], b.ev[2], b.ev[3]);
+        return RAWDTW_OK;
+    }
+    (void)hipEventElapsedTime(&b.min_ms[0], b.ev[2], b.ev[3]);
+    (void)hipEventElapsedTime(&b.min_ms[1], b.ev[3], b.ev[4]);
+    (void)hipEventElapsedTime(&b.min_ms[2], b.ev[5], b.ev[6]);
+    b.ms[1] = b.min_ms[0] + b.min_ms[1] + b.min_ms[2];
+    return RAWDTW_OK;
+}
+
+// the sorted entries' way home; a resident build brings nothing and waits alone (the `home` slot of the times is this wait either way)
+int entries_home(Build &b)
+{
+    Owner &own = b.own;
+    const hipStream_t s = b.ctx->stream;
+    const double t0 = now_ms();
+    if (!b.resident) {
+        try { b.h_hash.resize(b.N); b.h_y.resize(b.N); } catch (const std::bad_alloc &) { return fail(b.ctx, RAWDTW_ERR_OOM, "building the table failed"); }
+        SB_HIP(own, hipMemcpyAsync(b.h_hash.data(), b.d_hash[0], b.N * 4, hipMemcpyDeviceToHost, s));
+        SB_HIP(own, hipMemcpyAsync(b.h_y.data(), b.d_y[0], b.N * 8, hipMemcpyDeviceToHost, s));
+    }
+    SB_HIP(own, hipStreamSynchronize(s));
+    b.ms[3] = (float)(now_ms() - t0);
+    return RAWDTW_OK;
+}
+
+// 7. the one commit point, behind the last check: the statistics of the call become the context's.  The build's times and the w > 0
+// numbers are a build's to write, the resident statistics a resident build's and rawdtw_seed_table_from_entries'.
+void commit_stats(const Build &b)
+{
+    rawdtw_ctx *ctx = b.ctx;
+    if (!b.from_entries) memcpy(ctx->seed_build_ms, b.ms, sizeof(b.ms));
+    if (b.windowed) {
+        ctx->seed_min_emers = b.emers; ctx->seed_min_entries = b.N;
+        memcpy(ctx->seed_min_ms, b.min_ms, sizeof(b.min_ms));
+    }
+    if (b.resident)
+        ctx->seed_resident = rawdtw_seed_resident_stats_t{kFilterTile, b.table.lg, b.f_tiles, b.kept_total, b.N, b.table.n_keys, b.table.displaced,
+                                                          b.filter_ms[0], b.filter_ms[1], b.filter_ms[2], b.ms[1], b.ms[2], b.table.ms};
+}
+
+// 6. the end on the host: fill_table builds the slots from the entries, as for every other index
+int end_on_host(Build &b)
+{
+    const double t1 = now_ms();
+    int st = RAWDTW_OK;
+    try {
+        std::vector<Entry> all(b.N);
+        for (uint64_t i = 0; i < b.N; i++) all[i] = Entry{b.h_hash[i], b.h_y[i]};
+        std::vector<uint32_t>().swap(b.h_hash);
+        std::vector<uint64_t>().swap(b.h_y);
+        st = fill_table(b.six.get(), all);
+    } catch (const std::bad_alloc &) { st = RAWDTW_ERR_OOM; }
+    b.ms[4] = (float)(now_ms() - t1);
+    if (st != RAWDTW_OK) return fail(b.ctx, st, "building the table failed");
+    commit_stats(b);
+    *b.out = b.six.release();
+    return RAWDTW_OK;
+}
+
+// 6. the resident end: the table from the sorted entries where they lie (no entry: 16 empty slots) becomes the context's, and the handle
+// carries the header alone
+int end_resident(Build &b)
+{
+    SB_TRY(table_on_device(b.ctx, b.d_hash[0], b.d_y[0], b.N, b.table)); // (it has said why, and freed what it made)
+    const DeviceTable &t = b.table;
+    seed_table_install(b.ctx, t.d_slots, t.d_list, t.lg, *b.pars, b.six->serial);
+    commit_stats(b);
+    rawdtw_seed_index *six = b.six.release();
+    six->log2_slots = t.lg; six->n_keys = t.n_keys; six->n_positions = b.N; six->n_list = t.n_list;
+    six->resident = true; six->owner = b.ctx;
+    *b.out = six;
+    return RAWDTW_OK;
+}
+
+// All three builds: the checks, the strands' rows, the filter, the entries (N of them in d_hash[0] / d_y[0]), the two sorts, and the end.
+int build_device(rawdtw_ctx *ctx, const rawdtw_seed_pars_t *pars, rawdtw_seed_index **out, bool min_ok, bool resident)
+{
+    SB_TRY(build_checks(ctx, pars, out, min_ok, resident));
+    Build b(ctx, pars, out, resident ? "rawdtw_seed_index_build_resident" : pars->w > 0 ? "rawdtw_seed_index_build_device_min" : "rawdtw_seed_index_build_device",
+            resident, false);
+    SB_TRY(strand_rows(b));
+    SB_TRY(new_handle(b, b.n_seq));
+    for (int i = 0; i < 8; i++) b.ev[i] = b.own.event();
+    if (resident) for (int i = 0; i < 2; i++) b.evf[i] = b.own.event();
+    SB_HIP(b.own, b.own.err);
+    if (b.n_seq && b.total_len) {
+        SB_TRY(filter(b));
+        SB_TRY(b.windowed ? entries_minimizers(b) : entries_all(b));
+        if (b.N) {
+            SB_TRY(sorts(b));
+            // the write did not put down what the count counted: no table
+            if (b.windowed && b.written != b.N) return fail(ctx, RAWDTW_ERR_INTERNAL, "the write launch's element count is not the scan's total");
+            SB_TRY(entries_home(b));
+        }
+    }
+    return resident ? end_resident(b) : end_on_host(b);
+}
+
+} // namespace
 
 extern "C" {
 
 int rawdtw_seed_index_build_device(rawdtw_ctx *ctx, const rawdtw_seed_pars_t *pars, rawdtw_seed_index **out)
 {
-    return build_device(ctx, pars, out, false);
+    return build_device(ctx, pars, out, false, false);
 }
 
 int rawdtw_seed_index_build_device_min(rawdtw_ctx *ctx, const rawdtw_seed_pars_t *pars, rawdtw_seed_index **out)
 {
-    return build_device(ctx, pars, out, true);
+    return build_device(ctx, pars, out, true, false);
 }
 
 int rawdtw_seed_index_build_resident(rawdtw_ctx *ctx, const rawdtw_seed_pars_t *pars, rawdtw_seed_index **out)
@@ -786,6 +923,7 @@ int rawdtw_seed_index_build_resident(rawdtw_ctx *ctx, const rawdtw_seed_pars_t *
     return build_device(ctx, pars, out, true, true);
 }
 
+// the checks, the entries up, the resident end
 int rawdtw_seed_table_from_entries(rawdtw_ctx *ctx, const rawdtw_seed_pars_t *pars, uint32_t n_seq, uint64_t n, const uint32_t *hash,
                                    const uint64_t *y, rawdtw_seed_index **out)
 {
@@ -796,28 +934,17 @@ int rawdtw_seed_table_from_entries(rawdtw_ctx *ctx, const rawdtw_seed_pars_t *pa
     if (!entries_sorted(n, hash, y)) return fail(ctx, RAWDTW_ERR_INVALID, "the entries are not sorted by (hash, y)");
     if (const int no = seed_table_installable(ctx)) return no;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rawdtw_seed_index *six = new (std::nothrow) rawdtw_seed_index;
-    if (!six) return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed");
-    six->pars = *pars; six->n_seq = n_seq; six->serial = next_serial();
-    uint32_t *d_hash = nullptr;
-    uint64_t *d_y = nullptr;
-    hipError_t e = hipSuccess;
+    Build b(ctx, pars, out, "rawdtw_seed_table_from_entries", true, true);
+    SB_TRY(new_handle(b, n_seq));
+    b.N = n;
     if (n) {
-        e = hipMalloc((void **)&d_hash, n * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_y, n * 8);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_hash, hash, n * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_y, y, n * 8, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        SB_HIP(b.own, b.own.take(b.d_hash[0], n));
+        SB_HIP(b.own, b.own.take(b.d_y[0], n));
+        SB_HIP(b.own, hipMemcpyAsync(b.d_hash[0], hash, n * 4, hipMemcpyHostToDevice, ctx->stream));
+        SB_HIP(b.own, hipMemcpyAsync(b.d_y[0], y, n * 8, hipMemcpyHostToDevice, ctx->stream));
+        SB_HIP(b.own, hipStreamSynchronize(ctx->stream));
     }
-    DeviceTable table;
-    const int st = e == hipSuccess ? table_on_device(ctx, d_hash, d_y, n, &table) : hip_fail(ctx, e, "rawdtw_seed_table_from_entries");
-    if (d_hash) (void)hipFree(d_hash);
-    if (d_y) (void)hipFree(d_y);
-    if (st != RAWDTW_OK) { delete six; return st; }
-    seed_table_install(ctx, table.d_slots, table.d_list, table.lg, *pars, six->serial);
-    ctx->seed_resident = rawdtw_seed_resident_stats_t{kFilterTile, table.lg, 0, 0, n, table.n_keys, table.displaced, 0.f, 0.f, 0.f, 0.f, 0.f, table.ms};
-    *out = resident_handle(ctx, six, table, n);
-    return RAWDTW_OK;
+    return end_resident(b);
 }
 
 int rawdtw_seed_index_build_resident_stats(const rawdtw_ctx *ctx, rawdtw_seed_resident_stats_t *out)

@@ -28,6 +28,12 @@
 namespace rawdtw {
 namespace seed {
 
+// M: the e-mers of a strand with `kept` kept events
+RAWDTW_HD inline uint32_t strand_emers(uint32_t kept, uint32_t e)
+{
+    return kept >= e ? kept - e + 1 : 0;
+}
+
 // The hashes come as a pointer and the index of the e-mer that h[0] belongs to: h[i - base] is e-mer i's hash, for every i a step reads
 // (max(0, m-w) .. m).  A kernel's staged tile and a whole strand's array are both that.
 struct MinHashes {

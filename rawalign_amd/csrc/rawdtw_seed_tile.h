@@ -31,6 +31,12 @@ constexpr uint32_t kFilterTile = 2048;    // T: the events of a tile (next and t
 constexpr uint32_t kNoEntry = 0xffffffffu; // a tile that keeps nothing; an empty slot of the rank table
 static_assert(kFilterTile >= 64 && kFilterTile < 65536 && kFilterTile % 256 == 0, "a tile's offsets are 16 bits; a workgroup of 256 takes it in whole rounds");
 
+// the tiles of a strand of len events
+RAWDTW_HD inline uint32_t filter_tiles(uint32_t len)
+{
+    return (uint32_t)(((uint64_t)len + kFilterTile - 1) / kFilterTile);
+}
+
 // the rule switch: kMask is the w == 0 rule (rsketch.c:243), without it ri_sketch_min's (rsketch.c:172)
 template <bool kMask> RAWDTW_HD inline bool tile_skipped(float x, float last, bool first)
 {
