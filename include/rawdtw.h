@@ -589,12 +589,15 @@ int rawdtw_batch_run_reps(rawdtw_ctx *ctx, rawdtw_batch *batch, uint32_t reps, f
  * event pair per launch when timed != 0), call it as often as wanted, also alternating between
  * batches of different contexts so that several mini-batches are in flight (the reference keeps two,
  * rmap.cpp:1033); then, after rawdtw_sync(), collect the mean per-launch durations of all runs
- * enqueued since the last collect. */
+ * enqueued since the last collect.  launch_kind names the launches as rawdtw_batch_launch_stats does (the tile launch that
+ * carries the small banded classes as kind 10).  A batch that rawdtw_batch_fetch redid through the job list reports that
+ * form's launches and no runs: the timed runs enqueued before timed the form it no longer has. */
 int rawdtw_batch_enqueue(rawdtw_ctx *ctx, rawdtw_batch *batch, int timed);
 int rawdtw_batch_collect(rawdtw_ctx *ctx, rawdtw_batch *batch, float *launch_ms, uint32_t *launch_kind,
                          uint32_t cap, uint32_t *n_launches, uint32_t *n_runs);
 /* static facts about launch i of the batch (same indexing as launch_ms): kind, parameter
- * (band radius / rows per lane / LDS floats), jobs, their algorithmic bytes and DP cells */
+ * (band radius / rows per lane / LDS floats), jobs, their algorithmic bytes and DP cells.  Every job and cell is counted in
+ * one launch: a sync-free batch's launch 0 is the side list's (kind 8), launch 1 the tiles' passes (kind 10) */
 int rawdtw_batch_launch_stats(const rawdtw_batch *batch, uint32_t i, uint32_t *kind, int32_t *param,
                               uint64_t *n_jobs, uint64_t *algorithmic_bytes, uint64_t *cells);
 /* job_cost may be NULL; otherwise receives the per-job costs too */

@@ -277,9 +277,10 @@ def unpack_anchors(lib, anchor_off, ca: CompactAnchors) -> np.ndarray:
 
 class Batch:
     """rawdtw_batch: DTW scoring + align_chain fold + per-read selection, all on the device.  compact=True hands the anchor
-    lists over in the compact form (rawdtw_batch_submit_compact: the batch is then already running when this returns)."""
+    lists over in the compact form (rawdtw_batch_submit_compact: the batch is then already running when this returns);
+    submit=True creates and enqueues the first run in one call (rawdtw_batch_submit), as a pipelined host does."""
 
-    def __init__(self, engine: Engine, opt: MapOpt, cb: CandidateBatch, compact: bool = False):
+    def __init__(self, engine: Engine, opt: MapOpt, cb: CandidateBatch, compact: bool = False, submit: bool = False):
         self.engine = engine
         self.cb = cb
         self._copt = opt.c_struct()
@@ -296,6 +297,10 @@ class Batch:
             engine._check(engine.lib.rawdtw_batch_submit_compact(engine._ctx, C.byref(self._copt), cb.n_reads, _ptr(a[0]), _ptr(a[1]),
                                                                  _ptr(ca.heads), _ptr(ca.unit_abs), _ptr(ca.steps), _ptr(ca.wide), len(ca.wide),
                                                                  _ptr(a[3]), _ptr(a[4]), C.byref(h)))
+            self._submitted = True
+        elif submit:
+            engine._check(engine.lib.rawdtw_batch_submit(engine._ctx, C.byref(self._copt), cb.n_reads, _ptr(a[0]),
+                                                         _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), _ptr(a[4]), C.byref(h)))
             self._submitted = True
         else:
             engine._check(engine.lib.rawdtw_batch_create(engine._ctx, C.byref(self._copt), cb.n_reads, _ptr(a[0]),
@@ -361,7 +366,7 @@ class Batch:
         return d
 
     def run(self):
-        if self._submitted:  # (a compact batch was enqueued by its submit call)
+        if self._submitted:  # (a compact or submitted batch was enqueued by its submit call)
             self._submitted = False
             return
         self.engine._check(self.engine.lib.rawdtw_batch_run(self.engine._ctx, self._h))
@@ -415,6 +420,32 @@ class Batch:
                         "algorithmic_bytes": int(ab.value), "cells": int(cl.value)})
             i += 1
         return out
+
+    def plan_ms(self) -> float:
+        """rawdtw_batch_plan_ms: the planning launches of a sync-free batch created under "time_plan" (0 otherwise)"""
+        ms = C.c_float(-1.0)
+        self.engine._check(self.engine.lib.rawdtw_batch_plan_ms(self.engine._ctx, self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def wide_ms(self) -> float:
+        """rawdtw_batch_wide_ms: what lay between the scan and the pass planning of such a batch (the side list's launch, when it went
+        out there)"""
+        ms = C.c_float(-1.0)
+        self.engine._check(self.engine.lib.rawdtw_batch_wide_ms(self.engine._ctx, self._h, C.byref(ms)))
+        return float(ms.value)
+
+    STREAM_COUNTERS = ("bad", "overflow", "unsupported", "side_jobs", "cells", "tile_jobs", "tile_bytes", "side_bytes", "todo", "pool")
+
+    def stream_counters(self) -> dict:
+        """rawdtw_batch_stream_counters by name (rawdtw_batch_stream_counter_index); {} for a job-list batch"""
+        lib = self.engine.lib
+        n = C.c_uint32()
+        self.engine._check(lib.rawdtw_batch_stream_counters(self.engine._ctx, self._h, None, 0, C.byref(n)))
+        if n.value == 0:
+            return {}
+        w = np.zeros(n.value, np.uint64)
+        self.engine._check(lib.rawdtw_batch_stream_counters(self.engine._ctx, self._h, _ptr(w), len(w), C.byref(n)))
+        return {name: int(w[lib.rawdtw_batch_stream_counter_index(name.encode())]) for name in self.STREAM_COUNTERS}
 
     def fetch(self, with_job_costs=False):
         nc = self.cb.n_chains

@@ -394,6 +394,10 @@ int stream_fallback(rawdtw_ctx *ctx, rawdtw_batch *b)
                                      job_off.data(), nullptr, 0, &n_jobs);
     if (st != RAWDTW_OK) return fail(ctx, st, "job counting failed");
     b->stream = false; b->jobs_counted = true; // (batch_create_joblist sets n_jobs)
+    // (event pairs of timed runs enqueued so far were laid out for the declined form's launches: rawdtw_batch_collect walks them by
+    // the launch count of the form the batch has, so they go with the form they timed)
+    for (auto &e : b->ev) if (e) (void)hipEventDestroy(e);
+    b->ev.clear(); b->ev_runs = 0;
     ws_release(ctx, b->ws);
     b->h_cnt = nullptr; b->h_score = nullptr; b->h_keep = nullptr; b->res_bytes = 0; // (they lay in the workspace)
     batch_forget_arrays(b);
@@ -809,13 +813,17 @@ int rawdtw_batch_enqueue(rawdtw_ctx *ctx, rawdtw_batch *batch, int timed)
 int rawdtw_batch_collect(rawdtw_ctx *ctx, rawdtw_batch *batch, float *launch_ms, uint32_t *launch_kind, uint32_t cap,
                          uint32_t *n_launches, uint32_t *n_runs)
 {
-    if (!ctx || !batch || batch->ctx != ctx) return fail(ctx, RAWDTW_ERR_INVALID, "batch does not belong to this context");
+    if (n_launches) *n_launches = 0;
+    if (n_runs) *n_runs = 0;
+    // (a batch whose redo through the job list failed at fetch has no launches left to report: refused like everywhere else)
+    if (!ctx || !batch || batch->ctx != ctx || batch_dead(batch)) return fail(ctx, RAWDTW_ERR_INVALID, "batch does not belong to this context");
     const uint32_t np = batch_dtw_launches(batch), nl = np + 2;
     if (n_launches) *n_launches = nl;
     if (n_runs) *n_runs = batch->ev_runs;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     batch->dirty = false;
     int st = RAWDTW_OK;
+    const MergeSel mg = batch->stream ? MergeSel{} : merge_of(ctx, batch->plan); // (kinds as rawdtw_batch_launch_stats names them)
     for (uint32_t i = 0; i < nl && i < cap; i++) {
         double acc = 0;
         for (uint32_t r = 0; r < batch->ev_runs; r++) {
@@ -828,7 +836,7 @@ int rawdtw_batch_collect(rawdtw_ctx *ctx, rawdtw_batch *batch, float *launch_ms,
         if (launch_kind) {
             if (i >= np) launch_kind[i] = i == np ? kKindChainFold : kKindReadSelect;
             else if (batch->stream) launch_kind[i] = i == 0 ? (uint32_t)kKindBandWreg : (kKindBandMerged | ((uint32_t)batch->stream_lds << 8));
-            else launch_kind[i] = batch->plan->launches[i].kind | ((uint32_t)batch->plan->launches[i].param << 8);
+            else launch_kind[i] = (mg.on() && (int)i == mg.tile ? (uint32_t)kKindBandMerged : batch->plan->launches[i].kind) | ((uint32_t)batch->plan->launches[i].param << 8);
         }
     }
     for (auto &e : batch->ev) if (e) (void)hipEventDestroy(e);
@@ -841,7 +849,7 @@ int rawdtw_batch_collect(rawdtw_ctx *ctx, rawdtw_batch *batch, float *launch_ms,
 int rawdtw_batch_run_reps(rawdtw_ctx *ctx, rawdtw_batch *batch, uint32_t reps, float *launch_ms, uint32_t *launch_kind,
                           uint32_t cap, uint32_t *n_launches)
 {
-    if (!ctx || !batch || batch->ctx != ctx) return fail(ctx, RAWDTW_ERR_INVALID, "batch does not belong to this context");
+    if (!ctx || !batch || batch->ctx != ctx || batch_dead(batch)) return fail(ctx, RAWDTW_ERR_INVALID, "batch does not belong to this context");
     if (n_launches) *n_launches = batch_dtw_launches(batch) + 2;
     int st = RAWDTW_OK;
     for (uint32_t r = 0; r < reps && st == RAWDTW_OK; r++) st = rawdtw_batch_enqueue(ctx, batch, launch_ms != nullptr);
@@ -888,12 +896,23 @@ int rawdtw_batch_launch_stats(const rawdtw_batch *batch, uint32_t i, uint32_t *k
             I.algorithmic_bytes = b->h_cnt[kCntTileBytes] + b->h_cnt[kCntOtherBytes];
         }
         if (batch->stream) { // (rawdtw_batch_info may have moved the batch to the job-list path)
-            if (kind) *kind = kKindBandMerged;
-            if (param) *param = (int32_t)batch->stream_lds;
-            batch_count_jobs(const_cast<rawdtw_batch *>(batch));
-            if (n_jobs) *n_jobs = batch->n_jobs;
-            if (algorithmic_bytes) *algorithmic_bytes = I.algorithmic_bytes;
-            if (cells) *cells = I.cells;
+            // launch 0 is the side list's (k_wide), launch 1 the tiles' passes (k_runs) -- the kinds rawdtw_batch_collect reports -- and
+            // every job, byte and cell is counted in exactly one of them
+            rawdtw_batch *b = const_cast<rawdtw_batch *>(batch);
+            batch_count_jobs(b);
+            const uint64_t n_side = std::min<uint64_t>(b->h_cnt[kCntOthers], b->sa.others_cap);
+            uint64_t side_cells = 0;
+            if (cells && n_side) {
+                std::vector<DevJob> side(n_side);
+                if (hipMemcpy(side.data(), b->sa.ojobs, n_side * sizeof(DevJob), hipMemcpyDeviceToHost) != hipSuccess) return RAWDTW_ERR_DEVICE;
+                for (const DevJob &d : side) side_cells += banded_cells(d.n, d.m, d.R);
+            }
+            const bool wide = i == 0;
+            if (kind) *kind = wide ? kKindBandWreg : kKindBandMerged;
+            if (param) *param = wide ? 0 : (int32_t)batch->stream_lds;
+            if (n_jobs) *n_jobs = wide ? n_side : batch->n_jobs - std::min<uint64_t>(n_side, batch->n_jobs);
+            if (algorithmic_bytes) *algorithmic_bytes = wide ? b->h_cnt[kCntOtherBytes] : I.algorithmic_bytes - b->h_cnt[kCntOtherBytes];
+            if (cells) *cells = wide ? side_cells : I.cells - std::min<uint64_t>(side_cells, I.cells);
             return RAWDTW_OK;
         }
         if (i >= batch_dtw_launches(batch)) return RAWDTW_ERR_INVALID;
