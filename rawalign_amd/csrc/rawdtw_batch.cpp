@@ -97,19 +97,19 @@ static hipError_t stream_wide_fork(rawdtw_ctx *ctx, const StreamArgs &a)
 
 // the stream path: everything rawdtw_batch_create does for a sparse + banded batch -- O(1) host work: a workspace from the
 // pool, five copies and three launches enqueued
-int batch_create_stream(rawdtw_ctx *ctx, rawdtw_batch *b, const uint64_t *chain_off, const uint64_t *anchor_off,
-                        const rawdtw_anchor_t *anchors, const uint64_t *ref_base, const uint32_t *read_base)
+int batch_create_stream(rawdtw_ctx *ctx, rawdtw_batch *b)
 {
+    const BatchIn &in = b->in;
     // (a chunk round: the device's lists are the SHORT ones -- new entries + junction -- and `na` their length; the full lists only
     // give the fold its offsets)
-    const rawdtw_batch *prev = b->in_prev;
+    const rawdtw_batch *prev = in.prev;
     const bool round = prev != nullptr; // (rawdtw_batch_submit_carry checked that it can serve: rawdtw_batch_can_carry)
-    const bool compact = b->in_steps != nullptr;
-    const uint64_t nc = b->n_chains, nr = b->n_reads, n_full = anchor_off[nc], na = round ? b->in_new_off[nc] : n_full;
+    const bool compact = in.compact;
+    const uint64_t nc = b->n_chains, nr = b->n_reads, n_full = in.anchor_off[nc], na = round ? in.new_off[nc] : n_full;
     const uint32_t lds_floats = stream_tile_floats(ctx);
     // where everything lies: rawdtw_stream_layout.h
     const stream::Layout L = stream::layout({nr, nc, na, n_full, compact ? stream::Kind::compact : round ? stream::Kind::round : stream::Kind::plain,
-                                             b->in_n_wide, ctx->pass_pool});
+                                             in.n_wide, ctx->pass_pool});
     int st = ws_acquire(ctx, L.need, L.pin_need, &b->ws);
     if (st != RAWDTW_OK) return st;
     char *const d = b->ws.d, *const h = b->ws.h;
@@ -137,13 +137,13 @@ int batch_create_stream(rawdtw_ctx *ctx, rawdtw_batch *b, const uint64_t *chain_
     a.out = at<float>(d, L.out);
     a.anchor_off = at<uint64_t>(d, L.anchor_off);
     // ("resident_arrays": the three big arrays are device pointers, used in place; their regions stay unused)
-    const rawdtw_anchor_t *const lists = round ? b->in_new_anchors : anchors; // (a round: only its NEW anchors, and the junctions, cross the bus)
-    a.anchors = b->in_resident ? lists : at<rawdtw_anchor_t>(d, L.anchors);
-    a.ref_base = b->in_resident ? ref_base : at<uint64_t>(d, L.ref_base);
-    a.read_base = b->in_resident ? read_base : at<uint32_t>(d, L.read_base);
+    const rawdtw_anchor_t *const lists = round ? in.new_anchors : in.anchors; // (a round: only its NEW anchors, and the junctions, cross the bus)
+    a.anchors = in.resident ? lists : at<rawdtw_anchor_t>(d, L.anchors);
+    a.ref_base = in.resident ? in.ref_base : at<uint64_t>(d, L.ref_base);
+    a.read_base = in.resident ? in.read_base : at<uint32_t>(d, L.read_base);
     if (compact) { // the packed lists; k_scan decodes them into the anchors' region
         a.heads = at<rawdtw_anchor_t>(d, L.heads); a.unit_abs = at<rawdtw_anchor_t>(d, L.unit_abs);
-        a.steps = at<uint16_t>(d, L.steps); a.wide = at<rawdtw_wide_step_t>(d, L.wide); a.n_wide = b->in_n_wide;
+        a.steps = at<uint16_t>(d, L.steps); a.wide = at<rawdtw_wide_step_t>(d, L.wide); a.n_wide = in.n_wide;
         a.anchors_w = at<rawdtw_anchor_t>(d, L.anchors);
     }
     a.full_off = a.anchor_off; a.n_full = n_full; a.out_full = a.out; // (no predecessor: the lists are the full ones)
@@ -159,22 +159,22 @@ int batch_create_stream(rawdtw_ctx *ctx, rawdtw_batch *b, const uint64_t *chain_
     hipStream_t s = ctx->stream;
     if (ctx->time_plan) for (hipEvent_t &pe : b->ev_plan) if (!pe) HIP_TRY(ctx, hipEventCreate(&pe));
     HIP_TRY(ctx, hipMemcpyAsync(d + L.cnt.at, h_init, stream::kCounterBytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d + L.anchor_off.at, round ? b->in_new_off : anchor_off, (nc + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d + L.anchor_off.at, round ? in.new_off : in.anchor_off, (nc + 1) * 8, hipMemcpyHostToDevice, s));
     if (compact) {
-        HIP_TRY(ctx, hipMemcpyAsync(d + L.heads.at, b->in_heads, nc * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemcpyAsync(d + L.unit_abs.at, b->in_unit_abs, L.n_units * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemcpyAsync(d + L.steps.at, b->in_steps, na * 2, hipMemcpyHostToDevice, s));
-        if (b->in_n_wide) HIP_TRY(ctx, hipMemcpyAsync(d + L.wide.at, b->in_wide, b->in_n_wide * sizeof(rawdtw_wide_step_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d + L.heads.at, in.heads, nc * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d + L.unit_abs.at, in.unit_abs, L.n_units * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d + L.steps.at, in.steps, na * 2, hipMemcpyHostToDevice, s));
+        if (in.n_wide) HIP_TRY(ctx, hipMemcpyAsync(d + L.wide.at, in.wide, in.n_wide * sizeof(rawdtw_wide_step_t), hipMemcpyHostToDevice, s));
     } else if (round) {
-        HIP_TRY(ctx, hipMemcpyAsync(d + L.carry.at, b->in_carry, nc * sizeof(rawdtw_carry_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemcpyAsync(d + L.full_off.at, anchor_off, (nc + 1) * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d + L.carry.at, in.carry, nc * sizeof(rawdtw_carry_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d + L.full_off.at, in.anchor_off, (nc + 1) * 8, hipMemcpyHostToDevice, s));
     }
-    if (!b->in_resident) { // what the three kinds share (a compact batch's anchors are decoded on the device)
+    if (!in.resident) { // what the three kinds share (a compact batch's anchors are decoded on the device)
         if (!compact && na) HIP_TRY(ctx, hipMemcpyAsync(d + L.anchors.at, lists, na * sizeof(rawdtw_anchor_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemcpyAsync(d + L.ref_base.at, ref_base, nc * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemcpyAsync(d + L.read_base.at, read_base, nc * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d + L.ref_base.at, in.ref_base, nc * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d + L.read_base.at, in.read_base, nc * 4, hipMemcpyHostToDevice, s));
     }
-    HIP_TRY(ctx, hipMemcpyAsync(d + L.chain_off.at, chain_off, (nr + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d + L.chain_off.at, in.chain_off, (nr + 1) * 8, hipMemcpyHostToDevice, s));
     b->fold_fused = ctx->fold_mode == 4; // (no fold order then: the one-workgroup sort stays off the scan's critical path)
     if (ctx->time_plan) HIP_TRY(ctx, hipEventRecord(b->ev_plan[0], s)); // ("time_plan": the planning LAUNCHES, behind the hand-over's copies)
     hipError_t e = stream_plan(a, b->d_chains, b->fold_fused ? nullptr : b->d_fold_order, s);
@@ -185,7 +185,7 @@ int batch_create_stream(rawdtw_ctx *ctx, rawdtw_batch *b, const uint64_t *chain_
     b->wide_out = false;
     // (only inside rawdtw_batch_submit*: between a separate create and run the caller may upload new events, and a run reads
     // the arenas as they are then)
-    if (e == hipSuccess && !(ctx->stream_debug & 4u) && ctx->wide_order == 0 && (ctx->in_submit || ctx->wide_at_create)) { e = stream_wide_fork(ctx, a); b->wide_out = e == hipSuccess; }
+    if (e == hipSuccess && !(ctx->stream_debug & 4u) && ctx->wide_order == 0 && (in.submit || ctx->wide_at_create)) { e = stream_wide_fork(ctx, a); b->wide_out = e == hipSuccess; }
     if (e == hipSuccess && ctx->time_plan) e = hipEventRecord(b->ev_plan[2], s);
     if (e == hipSuccess) e = stream_plan_passes(a, s);
     if (e != hipSuccess) return hip_fail(ctx, e, "batch planning launches");
@@ -206,7 +206,7 @@ int batch_create_stream(rawdtw_ctx *ctx, rawdtw_batch *b, const uint64_t *chain_
     b->stream_lds = lds_floats;
     b->stream_threads = ctx->stream_threads;
     b->n_jobs = 0; b->jobs_counted = false;
-    b->cnt_valid = false;
+    b->cnt_valid = false; b->stats_home = false;
     b->dirty = true;
     b->ws_bytes = L.need;
     return RAWDTW_OK;
@@ -214,73 +214,74 @@ int batch_create_stream(rawdtw_ctx *ctx, rawdtw_batch *b, const uint64_t *chain_
 
 // DTW jobs of a sync-free batch (align_chain issues n_anchors - 1 per chain, rmap.cpp:248): counted from the caller's
 // chain offsets the first time somebody asks -- rawdtw_batch_create itself does not walk the chains
-void batch_count_jobs(rawdtw_batch *b)
+void batch_count_jobs(const rawdtw_batch *b)
 {
     if (b->jobs_counted || !b->stream) return;
     uint64_t n = 0;
     for (uint64_t c = 0; c < b->n_chains; c++) {
-        const uint64_t k = b->in_anchor_off[c + 1] - b->in_anchor_off[c];
+        const uint64_t k = b->in.anchor_off[c + 1] - b->in.anchor_off[c];
         n += k ? k - 1 : 0;
     }
     b->n_jobs = n;
     b->jobs_counted = true;
 }
 
-// "resident_arrays": bring the three device-resident arrays to the host (the job-list path reads them there)
-int materialise_host_arrays(rawdtw_ctx *ctx, rawdtw_batch *b)
+// the two base arrays from the caller's device memory into the batch's host copies: the last of a resident hand-over to come home
+static int bases_home(rawdtw_ctx *ctx, rawdtw_batch *b)
 {
-    if (b->in_steps) { // the compact form: the job list is built from plain anchors
-        const uint64_t nc = b->n_chains, na = b->in_anchor_off[nc];
-        try { b->host_anchors.resize(na); } catch (const std::bad_alloc &) { return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed"); }
-        if (rawdtw_anchors_unpack(nc, b->in_anchor_off, b->in_heads, b->in_unit_abs, b->in_steps, b->in_wide, b->in_n_wide, b->host_anchors.data()) != RAWDTW_OK)
-            return fail(ctx, RAWDTW_ERR_INVALID, "malformed compact anchor lists");
-        b->in_anchors = b->host_anchors.data();
-        b->in_steps = nullptr;
-        return RAWDTW_OK;
-    }
-    if (b->in_carried) { // a chunk round: the device only has the short lists; the full ones are the caller's, for exactly this
-        if (!b->in_anchors) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, "a carried round the device-planned path declined, and no full anchor lists to redo it from: submit the round whole");
-        b->in_carried = false;
-        if (b->in_resident) { // (the bases are the caller's device arrays)
-            const uint64_t nc = b->n_chains;
-            try { b->host_ref_base.resize(nc); b->host_read_base.resize(nc); } catch (const std::bad_alloc &) { return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed"); }
-            if (nc) HIP_TRY(ctx, hipMemcpy(b->host_ref_base.data(), b->in_ref_base, nc * 8, hipMemcpyDeviceToHost));
-            if (nc) HIP_TRY(ctx, hipMemcpy(b->host_read_base.data(), b->in_read_base, nc * 4, hipMemcpyDeviceToHost));
-            b->in_ref_base = b->host_ref_base.data(); b->in_read_base = b->host_read_base.data();
-            b->in_resident = false;
-        }
-        return RAWDTW_OK;
-    }
-    if (!b->in_resident) return RAWDTW_OK;
-    const uint64_t nc = b->n_chains, na = b->in_anchor_off[nc];
-    try { b->host_anchors.resize(na + 1); b->host_ref_base.resize(nc + 1); b->host_read_base.resize(nc + 1); } // (+ 1: non-null arrays for a round without chains)
+    const uint64_t nc = b->n_chains;
+    try { b->host_ref_base.resize(nc + 1); b->host_read_base.resize(nc + 1); } // (+ 1: non-null arrays for a round without chains)
     catch (const std::bad_alloc &) { return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed"); }
-    if (na) HIP_TRY(ctx, hipMemcpy(b->host_anchors.data(), b->in_anchors, na * sizeof(rawdtw_anchor_t), hipMemcpyDeviceToHost));
-    if (nc) HIP_TRY(ctx, hipMemcpy(b->host_ref_base.data(), b->in_ref_base, nc * 8, hipMemcpyDeviceToHost));
-    if (nc) HIP_TRY(ctx, hipMemcpy(b->host_read_base.data(), b->in_read_base, nc * 4, hipMemcpyDeviceToHost));
-    b->in_anchors = b->host_anchors.data(); b->in_ref_base = b->host_ref_base.data(); b->in_read_base = b->host_read_base.data();
-    b->in_resident = false;
+    if (nc) HIP_TRY(ctx, hipMemcpy(b->host_ref_base.data(), b->in.ref_base, nc * 8, hipMemcpyDeviceToHost));
+    if (nc) HIP_TRY(ctx, hipMemcpy(b->host_read_base.data(), b->in.read_base, nc * 4, hipMemcpyDeviceToHost));
+    b->in.ref_base = b->host_ref_base.data(); b->in.read_base = b->host_read_base.data();
+    b->in.resident = false;
     return RAWDTW_OK;
 }
 
-// the job-list path: jobs built on the host (chain ranges spread over the planner's threads), plan_host, chain records
-int batch_create_joblist(rawdtw_ctx *ctx, rawdtw_batch *b, const uint64_t *chain_off, const uint64_t *anchor_off,
-                         const rawdtw_anchor_t *anchors, const uint64_t *ref_base, const uint32_t *read_base,
-                         const std::vector<uint64_t> &job_off, uint64_t n_jobs)
+// what the job-list path reads on the host: the compact lists unpacked, device-resident arrays brought home
+int materialise_host_arrays(rawdtw_ctx *ctx, rawdtw_batch *b)
 {
+    BatchIn &in = b->in;
+    const uint64_t nc = b->n_chains, na = in.anchor_off[nc];
+    if (in.compact) { // the job list is built from plain anchors
+        try { b->host_anchors.resize(na); } catch (const std::bad_alloc &) { return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed"); }
+        if (rawdtw_anchors_unpack(nc, in.anchor_off, in.heads, in.unit_abs, in.steps, in.wide, in.n_wide, b->host_anchors.data()) != RAWDTW_OK)
+            return fail(ctx, RAWDTW_ERR_INVALID, "malformed compact anchor lists");
+        in.anchors = b->host_anchors.data();
+        in.compact = false;
+        return RAWDTW_OK;
+    }
+    if (b->in_carried) { // a chunk round: the device only has the short lists; the full ones are the caller's, for exactly this
+        if (!in.anchors) return fail(ctx, RAWDTW_ERR_UNSUPPORTED, "a carried round the device-planned path declined, and no full anchor lists to redo it from: submit the round whole");
+        b->in_carried = false;
+        return in.resident ? bases_home(ctx, b) : RAWDTW_OK; // (the bases are the caller's device arrays)
+    }
+    if (!in.resident) return RAWDTW_OK;
+    try { b->host_anchors.resize(na + 1); } catch (const std::bad_alloc &) { return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed"); }
+    if (na) HIP_TRY(ctx, hipMemcpy(b->host_anchors.data(), in.anchors, na * sizeof(rawdtw_anchor_t), hipMemcpyDeviceToHost));
+    const int st = bases_home(ctx, b);
+    if (st == RAWDTW_OK) in.anchors = b->host_anchors.data();
+    return st;
+}
+
+// the job-list path: jobs built on the host (chain ranges spread over the planner's threads), plan_host, chain records
+int batch_create_joblist(rawdtw_ctx *ctx, rawdtw_batch *b, const std::vector<uint64_t> &job_off, uint64_t n_jobs)
+{
+    const BatchIn &in = b->in; // (its arrays are on the host: materialise_host_arrays)
     const uint64_t n_chains = b->n_chains, n_reads = b->n_reads;
     const rawdtw_align_opt_t *opt = &b->opt;
     // chain descriptors: from the anchors alone.  The parts' read regions telescope (consecutive parts share their
     // anchor event), so sum(n) = (last.q - first.q) + parts in the reference's uint32 arithmetic (rmap.cpp:236,292).
     std::vector<ChainDesc> desc(n_chains);
     for (uint64_t c = 0; c < n_chains; c++) {
-        const uint64_t a0 = anchor_off[c], a1 = anchor_off[c + 1];
+        const uint64_t a0 = in.anchor_off[c], a1 = in.anchor_off[c + 1];
         ChainDesc &d = desc[c];
         d.job_first = job_off[c];
         d.n_jobs = (uint32_t)(job_off[c + 1] - job_off[c]);
         d.descending = 0;
         if (a1 == a0) { d.span = 0; d.num_aligned = 0; continue; }
-        const rawdtw_anchor_t &first = anchors[a1 - 1], &last = anchors[a0];
+        const rawdtw_anchor_t &first = in.anchors[a1 - 1], &last = in.anchors[a0];
         d.span = last.query_position - first.query_position + 1; // rmap.cpp:202,245
         d.num_aligned = opt->border_constraint == 0 ? d.span : (last.query_position - first.query_position) + d.n_jobs;
     }
@@ -300,10 +301,10 @@ int batch_create_joblist(rawdtw_ctx *ctx, rawdtw_batch *b, const uint64_t *chain
         const uint64_t c_hi = t + 1 == T ? n_chains
                                          : std::lower_bound(job_off.begin(), job_off.begin() + n_chains, j_hi) - job_off.begin();
         for (uint64_t c = c_lo; c < c_hi; c++) {
-            const uint64_t a0 = anchor_off[c], a1 = anchor_off[c + 1];
+            const uint64_t a0 = in.anchor_off[c], a1 = in.anchor_off[c + 1];
             const uint32_t nj = (uint32_t)(job_off[c + 1] - job_off[c]);
             if (!nj) continue;
-            int s2 = rawdtw_chain_build_jobs(opt, anchors + a0, (uint32_t)(a1 - a0), ref_base[c], read_base[c], 0,
+            int s2 = rawdtw_chain_build_jobs(opt, in.anchors + a0, (uint32_t)(a1 - a0), in.ref_base[c], in.read_base[c], 0,
                                              jobs.data() + job_off[c]);
             if (s2 != RAWDTW_OK) { status[t] = s2; return; }
         }
@@ -335,7 +336,7 @@ int batch_create_joblist(rawdtw_ctx *ctx, rawdtw_batch *b, const uint64_t *chain
     if (n_chains) e = hipMemcpyAsync(b->d_chains, desc.data(), n_chains * sizeof(ChainDesc), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess && n_chains)
         e = hipMemcpyAsync(b->d_fold_order, fold_order.data(), n_chains * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(b->d_chain_off, chain_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(b->d_chain_off, in.chain_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream); // (the staging vectors above die with this scope)
     if (e != hipSuccess) return hip_fail(ctx, e, "uploading chain descriptors");
     return RAWDTW_OK;
@@ -365,7 +366,7 @@ void batch_release_device(rawdtw_batch *b)
 }
 
 // The counters of a stream batch, read once (after its planning kernels have run).
-int stream_counters(rawdtw_ctx *ctx, rawdtw_batch *b)
+int stream_counters(rawdtw_ctx *ctx, const rawdtw_batch *b)
 {
     if (b->cnt_valid) return RAWDTW_OK;
     HIP_TRY(ctx, hipMemcpyAsync(b->h_cnt, b->sa.cnt, stream::kCounterBytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -382,17 +383,40 @@ bool stream_declined(const rawdtw_batch *b)
     return c[kCntBad] != ~0ull || c[kCntOverflow] != ~0ull || c[kCntUnsupported] != 0 || c[kCntOthers] > b->sa.others_cap;
 }
 
+// The statistics the device sums on request -- tile jobs, tile bytes, side-list bytes; with_cells: the cell count in front of them --
+// in h_cnt: what is missing is summed and brought home, once a batch (the planning launches wrote what is summed; runs do not change it).
+int stream_stats_home(rawdtw_ctx *ctx, const rawdtw_batch *b, bool with_cells)
+{
+    if (b->cells_counted || (b->stats_home && !with_cells)) return RAWDTW_OK;
+    const int first = with_cells ? kCntCells : kCntTileJobs;
+    static_assert(kCntTileJobs == kCntCells + 1 && kCntOtherBytes == kCntCells + 3, "the four reporting counters lie one behind the other");
+    if (with_cells) HIP_TRY(ctx, stream_count_cells(b->sa, b->sa.cnt + kCntCells, ctx->stream));
+    if (!b->stats_home) HIP_TRY(ctx, stream_sum_stats(b->sa, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&b->h_cnt[first], b->sa.cnt + first, (kCntOtherBytes + 1 - first) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    b->stats_home = true;
+    b->cells_counted = with_cells;
+    return RAWDTW_OK;
+}
+
+// what the job-list form starts from: the caller's arrays on the host and the chains' job offsets
+int joblist_count(rawdtw_ctx *ctx, rawdtw_batch *b, std::vector<uint64_t> &job_off, uint64_t *n_jobs)
+{
+    const int st = materialise_host_arrays(ctx, b);
+    if (st != RAWDTW_OK) return st;
+    job_off.resize(b->n_chains + 1);
+    if (rawdtw_batch_build_jobs(&b->opt, b->n_chains, b->in.anchor_off, b->in.anchors, b->in.ref_base, b->in.read_base, job_off.data(), nullptr, 0, n_jobs) != RAWDTW_OK)
+        return fail(ctx, RAWDTW_ERR_INVALID, "job counting failed");
+    return RAWDTW_OK;
+}
+
 // Redo a stream batch through the job-list path (which also words the error of an invalid batch).
 int stream_fallback(rawdtw_ctx *ctx, rawdtw_batch *b)
 {
-    const uint64_t nc = b->n_chains;
-    std::vector<uint64_t> job_off(nc + 1);
+    std::vector<uint64_t> job_off;
     uint64_t n_jobs = 0;
-    int st = materialise_host_arrays(ctx, b);
+    int st = joblist_count(ctx, b, job_off, &n_jobs);
     if (st != RAWDTW_OK) return st;
-    st = rawdtw_batch_build_jobs(&b->opt, nc, b->in_anchor_off, b->in_anchors, b->in_ref_base, b->in_read_base,
-                                     job_off.data(), nullptr, 0, &n_jobs);
-    if (st != RAWDTW_OK) return fail(ctx, st, "job counting failed");
     b->stream = false; b->jobs_counted = true; // (batch_create_joblist sets n_jobs)
     // (event pairs of timed runs enqueued so far were laid out for the declined form's launches: rawdtw_batch_collect walks them by
     // the launch count of the form the batch has, so they go with the form they timed)
@@ -401,92 +425,118 @@ int stream_fallback(rawdtw_ctx *ctx, rawdtw_batch *b)
     ws_release(ctx, b->ws);
     b->h_cnt = nullptr; b->h_score = nullptr; b->h_keep = nullptr; b->res_bytes = 0; // (they lay in the workspace)
     batch_forget_arrays(b);
-    st = batch_create_joblist(ctx, b, b->in_chain_off, b->in_anchor_off, b->in_anchors, b->in_ref_base, b->in_read_base, job_off, n_jobs);
+    st = batch_create_joblist(ctx, b, job_off, n_jobs);
     if (st != RAWDTW_OK) { batch_release_device(b); return st; }
     return rawdtw_batch_run(ctx, b);
 }
 
 } // namespace
 
-// a batch whose (deferred) planning failed has neither form left: every entry point but destroy refuses it
-static bool batch_dead(const rawdtw_batch *b) { return !b->stream && !b->plan; }
+// the guard of the entry points that take a context and a batch: the batch is this context's and has a form left (batch_dead)
+static bool batch_ok(const rawdtw_ctx *ctx, const rawdtw_batch *batch) { return ctx && batch && batch->ctx == ctx && !batch_dead(batch); }
+static int batch_check(rawdtw_ctx *ctx, const rawdtw_batch *batch)
+{
+    return batch_ok(ctx, batch) ? RAWDTW_OK : fail(ctx, RAWDTW_ERR_INVALID, "batch does not belong to this context");
+}
 
-struct CompactIn {
-    const rawdtw_anchor_t *heads, *unit_abs;
-    const uint16_t *steps;
-    const rawdtw_wide_step_t *wide;
-    uint64_t n_wide;
-};
+// The context's own handle of a batch that came in through a const pointer (rawdtw_batch_info redoes a declined batch: more than a cache).
+static rawdtw_batch *batch_owned(const rawdtw_batch *batch)
+{
+    for (rawdtw_batch *b : batch->ctx->live_batches) if (b == batch) return b;
+    return nullptr;
+}
 
-static int batch_create_any(rawdtw_ctx *ctx, const rawdtw_align_opt_t *opt, uint64_t n_reads, const uint64_t *chain_off,
-                            const uint64_t *anchor_off, const rawdtw_anchor_t *anchors, const CompactIn *cin, const uint64_t *ref_base,
-                            const uint32_t *read_base, rawdtw_batch **out, const rawdtw_batch *prev = nullptr, const rawdtw_carry_t *carry = nullptr,
-                            const uint64_t *new_off = nullptr, const rawdtw_anchor_t *new_anchors = nullptr)
+static int batch_create_any(rawdtw_ctx *ctx, const rawdtw_align_opt_t *opt, uint64_t n_reads, const BatchIn &in, rawdtw_batch **out)
 {
     if (!out) return RAWDTW_ERR_INVALID;
     *out = nullptr;
-    if (!ctx || !opt || !chain_off || !anchor_off || (!anchors && !cin && !prev && n_reads) || !ref_base || !read_base)
+    if (!ctx || !opt || !in.chain_off || !in.anchor_off || (!in.anchors && !in.compact && !in.prev && n_reads) || !in.ref_base || !in.read_base)
         return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
-    if (cin && (!cin->heads || !cin->unit_abs || !cin->steps || (!cin->wide && cin->n_wide)))
+    if (in.compact && (!in.heads || !in.unit_abs || !in.steps || (!in.wide && in.n_wide)))
         return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
     if (opt->border_constraint != 0 && opt->border_constraint != 1)
         return fail(ctx, RAWDTW_ERR_INVALID, "invalid border constraint (rmap.cpp:301-304)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint64_t n_chains = chain_off[n_reads];
+    const uint64_t n_chains = in.chain_off[n_reads];
     int st = RAWDTW_OK;
     rawdtw_batch *b = new (std::nothrow) rawdtw_batch;
     if (!b) return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed");
     b->ctx = ctx; b->opt = *opt; b->n_reads = n_reads; b->n_chains = n_chains;
     ctx->live_batches.push_back(b);
-    b->in_chain_off = chain_off; b->in_anchor_off = anchor_off; b->in_anchors = anchors; b->in_ref_base = ref_base; b->in_read_base = read_base;
-    b->in_resident = ctx->resident_arrays && !cin;
-    b->in_prev = prev; b->in_carry = carry; b->in_new_off = new_off;
-    if (prev) {
-        b->in_new_anchors = new_anchors; b->in_carried = true;
-        for (uint64_t c = 0; c < n_chains; c++) b->parts_carried += carry[c].parts;
+    b->in = in;
+    if (in.prev) {
+        b->in_carried = true;
+        for (uint64_t c = 0; c < n_chains; c++) b->parts_carried += in.carry[c].parts;
     }
-    if (cin) { b->in_heads = cin->heads; b->in_unit_abs = cin->unit_abs; b->in_steps = cin->steps; b->in_wide = cin->wide; b->in_n_wide = cin->n_wide; }
-    if (stream_eligible(ctx, opt, anchor_off[n_chains]))
-        st = batch_create_stream(ctx, b, chain_off, anchor_off, anchors, ref_base, read_base);
+    if (stream_eligible(ctx, opt, in.anchor_off[n_chains]))
+        st = batch_create_stream(ctx, b);
     else {
-        st = materialise_host_arrays(ctx, b);
-        std::vector<uint64_t> &job_off = ctx->job_off_scratch; // (a context is not re-entrant)
-        job_off.resize(n_chains + 1);
         uint64_t n_jobs = 0;
-        if (st == RAWDTW_OK && rawdtw_batch_build_jobs(opt, n_chains, anchor_off, b->in_anchors, b->in_ref_base, b->in_read_base, job_off.data(),
-                                                        nullptr, 0, &n_jobs) != RAWDTW_OK)
-            st = fail(ctx, RAWDTW_ERR_INVALID, "job counting failed");
-        if (st == RAWDTW_OK)
-            st = batch_create_joblist(ctx, b, chain_off, anchor_off, b->in_anchors, b->in_ref_base, b->in_read_base, job_off, n_jobs);
+        st = joblist_count(ctx, b, ctx->job_off_scratch, &n_jobs); // (a context is not re-entrant)
+        if (st == RAWDTW_OK) st = batch_create_joblist(ctx, b, ctx->job_off_scratch, n_jobs);
     }
-    b->in_prev = nullptr; // (read at create only)
+    b->in.prev = nullptr; // (read at create only)
     if (st != RAWDTW_OK) { rawdtw_batch_destroy(b); return st; }
     *out = b;
     return RAWDTW_OK;
+}
+
+// the five arrays every hand-over has, under the context's "resident_arrays"
+static BatchIn batch_in(const rawdtw_ctx *ctx, const uint64_t *chain_off, const uint64_t *anchor_off, const rawdtw_anchor_t *anchors,
+                        const uint64_t *ref_base, const uint32_t *read_base)
+{
+    BatchIn in;
+    in.chain_off = chain_off; in.anchor_off = anchor_off; in.anchors = anchors; in.ref_base = ref_base; in.read_base = read_base;
+    in.resident = ctx && ctx->resident_arrays;
+    return in;
 }
 
 int rawdtw_batch_create(rawdtw_ctx *ctx, const rawdtw_align_opt_t *opt, uint64_t n_reads, const uint64_t *chain_off,
                         const uint64_t *anchor_off, const rawdtw_anchor_t *anchors, const uint64_t *ref_base,
                         const uint32_t *read_base, rawdtw_batch **out)
 {
-    return batch_create_any(ctx, opt, n_reads, chain_off, anchor_off, anchors, nullptr, ref_base, read_base, out);
+    return batch_create_any(ctx, opt, n_reads, batch_in(ctx, chain_off, anchor_off, anchors, ref_base, read_base), out);
 }
 
-static int batch_enqueue_one(rawdtw_ctx *ctx, rawdtw_batch *batch, hipEvent_t *e);
+static int batch_enqueue_one(rawdtw_ctx *ctx, rawdtw_batch *batch, hipEvent_t *e, uint32_t nl);
+
+// rawdtw_batch_submit*: create and the first run in one call; no batch is left behind a failure
+static int batch_submit_any(rawdtw_ctx *ctx, const rawdtw_align_opt_t *opt, uint64_t n_reads, BatchIn in, rawdtw_batch **out)
+{
+    in.submit = true;
+    int st = batch_create_any(ctx, opt, n_reads, in, out);
+    if (st != RAWDTW_OK) return st;
+    st = batch_enqueue_one(ctx, *out, nullptr, 0);
+    if (st != RAWDTW_OK) { rawdtw_batch_destroy(*out); *out = nullptr; }
+    return st;
+}
+
+int rawdtw_batch_submit(rawdtw_ctx *ctx, const rawdtw_align_opt_t *opt, uint64_t n_reads, const uint64_t *chain_off,
+                        const uint64_t *anchor_off, const rawdtw_anchor_t *anchors, const uint64_t *ref_base,
+                        const uint32_t *read_base, rawdtw_batch **out)
+{
+    return batch_submit_any(ctx, opt, n_reads, batch_in(ctx, chain_off, anchor_off, anchors, ref_base, read_base), out);
+}
+
+int rawdtw_batch_submit_device(rawdtw_ctx *ctx, const rawdtw_align_opt_t *opt, uint64_t n_reads, const uint64_t *chain_off,
+                               const uint64_t *anchor_off, const rawdtw_anchor_t *d_anchors, const uint64_t *d_ref_base,
+                               const uint32_t *d_read_base, rawdtw_batch **out)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    BatchIn in = batch_in(ctx, chain_off, anchor_off, d_anchors, d_ref_base, d_read_base);
+    in.resident = true; // (the option's meaning, for this one batch: a batch keeps the form it was created under)
+    return batch_submit_any(ctx, opt, n_reads, in, out);
+}
 
 int rawdtw_batch_submit_compact(rawdtw_ctx *ctx, const rawdtw_align_opt_t *opt, uint64_t n_reads, const uint64_t *chain_off,
                                 const uint64_t *anchor_off, const rawdtw_anchor_t *heads, const rawdtw_anchor_t *unit_abs,
                                 const uint16_t *steps, const rawdtw_wide_step_t *wide, uint64_t n_wide, const uint64_t *ref_base,
                                 const uint32_t *read_base, rawdtw_batch **out)
 {
-    const CompactIn cin{heads, unit_abs, steps, wide, n_wide};
-    if (ctx) ctx->in_submit = true;
-    int st = batch_create_any(ctx, opt, n_reads, chain_off, anchor_off, nullptr, &cin, ref_base, read_base, out);
-    if (ctx) ctx->in_submit = false;
-    if (st != RAWDTW_OK) return st;
-    st = batch_enqueue_one(ctx, *out, nullptr);
-    if (st != RAWDTW_OK) { rawdtw_batch_destroy(*out); *out = nullptr; }
-    return st;
+    BatchIn in = batch_in(ctx, chain_off, anchor_off, nullptr, ref_base, read_base);
+    in.compact = true; in.heads = heads; in.unit_abs = unit_abs; in.steps = steps; in.wide = wide; in.n_wide = n_wide;
+    in.resident = false; // (the packed lists are host arrays: k_scan decodes them on the device)
+    return batch_submit_any(ctx, opt, n_reads, in, out);
 }
 
 // can `prev` serve as the previous batch of a chunk round with options `opt`?  (include/rawdtw.h)
@@ -511,18 +561,14 @@ int rawdtw_batch_submit_carry(rawdtw_ctx *ctx, const rawdtw_align_opt_t *opt, ui
     if (!rawdtw_batch_can_carry(ctx, prev, opt) || !stream_eligible(ctx, opt, new_off[nc]))
         return fail(ctx, RAWDTW_ERR_UNSUPPORTED, "the previous batch cannot serve this round (another context or options, never run, or not on the device-planned path): submit the round whole");
     if (new_off[nc] > anchor_off[nc] || (!new_anchors && new_off[nc])) return fail(ctx, RAWDTW_ERR_INVALID, "more new anchors than anchors");
-    ctx->in_submit = true;
-    int st = batch_create_any(ctx, opt, n_reads, chain_off, anchor_off, anchors, nullptr, ref_base, read_base, out, prev, carry, new_off, new_anchors);
-    ctx->in_submit = false;
-    if (st != RAWDTW_OK) return st;
-    st = batch_enqueue_one(ctx, *out, nullptr);
-    if (st != RAWDTW_OK) { rawdtw_batch_destroy(*out); *out = nullptr; }
-    return st;
+    BatchIn in = batch_in(ctx, chain_off, anchor_off, anchors, ref_base, read_base);
+    in.prev = prev; in.carry = carry; in.new_off = new_off; in.new_anchors = new_anchors;
+    return batch_submit_any(ctx, opt, n_reads, in, out);
 }
 
 int rawdtw_batch_round_stats(rawdtw_ctx *ctx, rawdtw_batch *batch, uint64_t *parts_scored, uint64_t *parts_reused)
 {
-    if (!ctx || !batch || batch->ctx != ctx || batch_dead(batch)) return fail(ctx, RAWDTW_ERR_INVALID, "batch does not belong to this context");
+    if (const int bad = batch_check(ctx, batch)) return bad;
     batch_count_jobs(batch);
     uint64_t reused = 0;
     if (batch->stream) {
@@ -555,7 +601,7 @@ static int stream_plan_download(rawdtw_ctx *ctx, const rawdtw_batch *batch, Stre
     v.n_anchors = a.n_anchors; v.n_chains = batch->n_chains;
     v.n_tiles = a.n_tiles; v.n_slots = a.n_slots; v.lds_floats = a.lds_floats; v.lane_max_n = a.lane_max_n; v.lane_max_radius = a.lane_max_radius;
     v.n_first = cnt[kCntTodo]; v.n_pool = cnt[kCntPool]; v.n_other = cnt[kCntOthers]; v.n_reused = cnt[kCntReused];
-    v.anchor_off = batch->in_anchor_off;
+    v.anchor_off = batch->in.anchor_off;
     if (!v.fits_slots()) return RAWDTW_OK;
     constexpr size_t kRT = stream::kSlotOrders;
     h.todo.resize(v.n_todo()); h.runtab.resize(v.n_todo() * kRT);
@@ -579,9 +625,9 @@ int rawdtw_batch_verify_plan(rawdtw_ctx *ctx, const rawdtw_batch *batch, const r
 {
     auto say = [&](const std::string &m) { if (message && message_cap) snprintf(message, message_cap, "%s", m.c_str()); };
     say("");
-    if (!ctx || !batch || batch->ctx != ctx || (n_jobs && !jobs) || batch_dead(batch)) return RAWDTW_ERR_INVALID;
+    if (!batch_ok(ctx, batch) || (n_jobs && !jobs)) return RAWDTW_ERR_INVALID;
     if (device_planned) *device_planned = batch->stream ? 1 : 0;
-    batch_count_jobs(const_cast<rawdtw_batch *>(batch));
+    batch_count_jobs(batch);
     if (n_jobs != batch->n_jobs) { say("job count differs from the batch's"); return RAWDTW_ERR_INVALID; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -590,8 +636,7 @@ int rawdtw_batch_verify_plan(rawdtw_ctx *ctx, const rawdtw_batch *batch, const r
     if (batch->stream) {
         // what the scan and k_plan left behind for the DTW launch, against the job list the host builds from the same chains
         // (check_stream_plan); then the statistics, which the device sums
-        rawdtw_batch *mb = const_cast<rawdtw_batch *>(batch);
-        int st = stream_counters(ctx, mb);
+        int st = stream_counters(ctx, batch);
         if (st != RAWDTW_OK) return st;
         if (stream_declined(batch)) {
             if (device_planned) *device_planned = 0;
@@ -604,12 +649,10 @@ int rawdtw_batch_verify_plan(rawdtw_ctx *ctx, const rawdtw_batch *batch, const r
         StreamPlanStats want;
         e = check_stream_plan(h.v, jobs, n_jobs, &want);
         if (e.empty()) {
-            const StreamArgs &a = batch->sa;
-            HIP_TRY(ctx, stream_sum_stats(a, ctx->stream));
-            unsigned long long st3[3];
-            HIP_TRY(ctx, hipMemcpyAsync(st3, a.cnt + kCntTileJobs, 24, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (st3[0] != want.tile_jobs || st3[1] != want.tile_bytes || st3[2] != want.other_bytes) e = "tile statistics";
+            st = stream_stats_home(ctx, batch, false);
+            if (st != RAWDTW_OK) return st;
+            const unsigned long long *c = batch->h_cnt;
+            if (c[kCntTileJobs] != want.tile_jobs || c[kCntTileBytes] != want.tile_bytes || c[kCntOtherBytes] != want.other_bytes) e = "tile statistics";
         }
         say(e);
         return e.empty() ? RAWDTW_OK : RAWDTW_ERR_DEVICE + 100;
@@ -649,7 +692,7 @@ int rawdtw_batch_verify_plan(rawdtw_ctx *ctx, const rawdtw_batch *batch, const r
 
 int rawdtw_batch_chunk_profile(rawdtw_ctx *ctx, rawdtw_batch *batch, int flat_map, uint64_t *out, uint32_t cap, uint32_t *n_out)
 {
-    if (!ctx || !batch || batch->ctx != ctx || !n_out || batch_dead(batch)) return fail(ctx, RAWDTW_ERR_INVALID, "bad arguments to batch_chunk_profile");
+    if (!batch_ok(ctx, batch) || !n_out) return fail(ctx, RAWDTW_ERR_INVALID, "bad arguments to batch_chunk_profile");
     *n_out = 0;
     if (!batch->stream) return RAWDTW_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -674,27 +717,21 @@ int rawdtw_batch_info(const rawdtw_batch *batch, rawdtw_plan_info_t *info, uint6
     if (n_chains) *n_chains = batch->n_chains;
     if (!info) return RAWDTW_OK;
     if (!batch->stream) return rawdtw_plan_info(batch->plan, info);
-    rawdtw_batch *b = const_cast<rawdtw_batch *>(batch);
-    rawdtw_ctx *ctx = b->ctx;
+    rawdtw_ctx *ctx = batch->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int st = stream_counters(ctx, b);
+    int st = stream_counters(ctx, batch);
     if (st != RAWDTW_OK) return st;
-    if (stream_declined(b)) { // what the job-list path will run
-        st = stream_fallback(ctx, b);
+    if (stream_declined(batch)) { // what the job-list path will run
+        st = stream_fallback(ctx, batch_owned(batch));
         if (st != RAWDTW_OK) return st;
-        return rawdtw_plan_info(b->plan, info);
+        return rawdtw_plan_info(batch->plan, info);
     }
-    if (!b->cells_counted) {
-        HIP_TRY(ctx, stream_count_cells(b->sa, b->sa.cnt + kCntCells, ctx->stream));
-        HIP_TRY(ctx, stream_sum_stats(b->sa, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(&b->h_cnt[kCntCells], b->sa.cnt + kCntCells, 4 * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        b->cells_counted = true;
-    }
-    batch_count_jobs(b);
-    const unsigned long long *c = b->h_cnt;
+    st = stream_stats_home(ctx, batch, true);
+    if (st != RAWDTW_OK) return st;
+    batch_count_jobs(batch);
+    const unsigned long long *c = batch->h_cnt;
     rawdtw_plan_info_t I{};
-    I.n_jobs = b->n_jobs;
+    I.n_jobs = batch->n_jobs;
     I.cells = c[kCntCells];
     I.algorithmic_bytes = c[kCntTileBytes] + c[kCntOtherBytes];
     unsigned long long side_lane = 0; // the side list's lane-per-job classes count with the tiles' jobs: same body, same class rule
@@ -702,16 +739,18 @@ int rawdtw_batch_info(const rawdtw_batch *batch, rawdtw_plan_info_t *info, uint6
     I.n_lane_jobs = c[kCntTileJobs] + side_lane;
     I.n_wave_band_jobs = c[kCntOthers] - side_lane;
     I.n_full_jobs = 0;
-    I.workspace_bytes = b->ws_bytes;
+    I.workspace_bytes = batch->ws_bytes;
     I.n_launches = 1;
     *info = I;
     return RAWDTW_OK;
 }
 
-static int batch_tail(rawdtw_ctx *ctx, rawdtw_batch *b, int which)
+// the chain fold (kKindChainFold) or the read select (kKindReadSelect) of a batch enqueued
+static int batch_tail(rawdtw_ctx *ctx, rawdtw_batch *b, LaunchKind kind)
 {
     hipError_t e;
-    if (ctx->debug_skip_kinds & (1u << (which == 0 ? kKindChainFold : kKindReadSelect))) return RAWDTW_OK;
+    const int which = kind == kKindChainFold ? 0 : 1;
+    if (ctx->debug_skip_kinds & (1u << kind)) return RAWDTW_OK;
     if (ctx->debug_skip_tail & (1u << which)) return RAWDTW_OK;
     const float *job_cost = b->stream ? b->sa.out_full : b->plan->d_cost;
     if (b->stream && b->fold_fused) {
@@ -731,14 +770,17 @@ static int batch_tail(rawdtw_ctx *ctx, rawdtw_batch *b, int which)
     return RAWDTW_OK;
 }
 
-// launches of a batch's DTW part (before fold and select): the job-list plan's, or the stream path's one
-static uint32_t batch_dtw_launches(const rawdtw_batch *b) { return b->stream ? 2u : b->plan ? (uint32_t)b->plan->launches.size() : 0u; }
-
-
-static int batch_enqueue_one(rawdtw_ctx *ctx, rawdtw_batch *batch, hipEvent_t *e)
+// The batch's reported launches (rawdtw_launches.h) under the form it has and the context's settings now: what is timed, collected and
+// reported reads this and nothing else.  (An untimed run needs no table.)
+static std::vector<BatchLaunch> batch_table(const rawdtw_batch *b)
 {
-    const uint32_t np = batch_dtw_launches(batch);
-    int st = RAWDTW_OK;
+    return b->stream ? batch_launches(b->stream_lds, nullptr, MergeSel{}) : batch_launches(0, &b->plan->launches, merge_of(b->ctx, b->plan));
+}
+
+// One run of the batch enqueued.  `e`, when given, holds the run's event pairs: pair i of the `nl` entries of the batch's table.
+static int batch_enqueue_one(rawdtw_ctx *ctx, rawdtw_batch *batch, hipEvent_t *e, uint32_t nl)
+{
+    auto mark = [&](uint32_t i, int stop) { return !e || hipEventRecord(e[event_slot(0, i, nl) + stop], ctx->stream) == hipSuccess; };
     batch->dirty = true;
     if (batch->stream) {
         // The arenas may have been re-uploaded, grown or swapped since the batch was planned (rawdtw_upload_events,
@@ -747,67 +789,62 @@ static int batch_enqueue_one(rawdtw_ctx *ctx, rawdtw_batch *batch, hipEvent_t *e
         if (ctx->n_ev < batch->sa.n_ev || ctx->n_ref < batch->sa.n_ref)
             return fail(ctx, RAWDTW_ERR_INVALID, "an arena shrank after the batch was created: create the batch again");
         batch->sa.ev = ctx->d_ev; batch->sa.ref = ctx->d_ref;
-        // launch 0: the side list (k_wide) -- in line, or (option "wide_beside") forked onto the context's second stream and
-        // joined before the fold; launch 1: the tiles' passes (k_runs)
+        // entry 0: the side list (k_wide) -- in line, or (option "wide_beside") forked onto the context's second stream and
+        // joined before the fold; entry 1: the tiles' passes (k_runs)
         const bool wide = !(ctx->stream_debug & 4u);
-        if (e && hipEventRecord(e[0], ctx->stream) != hipSuccess) st = RAWDTW_ERR_DEVICE;
         const bool wide_now = wide && !batch->wide_out; // (the first run's went out with the planning launches)
-        if (st == RAWDTW_OK && wide_now && ctx->wide_order != 2) {
-            const hipError_t he = stream_wide_fork(ctx, batch->sa);
-            if (he != hipSuccess) st = hip_fail(ctx, he, "side list launch");
-        }
         batch->wide_out = false;
-        if (st == RAWDTW_OK && e && hipEventRecord(e[1], ctx->stream) != hipSuccess) st = RAWDTW_ERR_DEVICE;
-        if (st == RAWDTW_OK && e && hipEventRecord(e[2], ctx->stream) != hipSuccess) st = RAWDTW_ERR_DEVICE;
-        if (st == RAWDTW_OK) {
-            hipError_t he = stream_run(batch->sa, ctx->stream_blocks, batch->stream_lds, batch->stream_threads, batch->stream_runs++ > 0, ctx->stream);
-            if (he != hipSuccess) st = hip_fail(ctx, he, "batch kernel launch");
-        }
-        if (st == RAWDTW_OK && e && hipEventRecord(e[3], ctx->stream) != hipSuccess) st = RAWDTW_ERR_DEVICE;
-        if (st == RAWDTW_OK && wide_now && ctx->wide_order == 2) { // (timing experiments: the side list behind the tiles)
+        if (!mark(0, 0)) return RAWDTW_ERR_DEVICE;
+        if (wide_now && ctx->wide_order != 2) {
             const hipError_t he = stream_wide_fork(ctx, batch->sa);
-            if (he != hipSuccess) st = hip_fail(ctx, he, "side list launch");
+            if (he != hipSuccess) return hip_fail(ctx, he, "side list launch");
         }
-        if (st == RAWDTW_OK && wide && ctx->wide_beside && hipStreamWaitEvent(ctx->stream, ctx->ev_wide_join, 0) != hipSuccess) st = RAWDTW_ERR_DEVICE;
-    } else st = run_all_launches(ctx, batch->plan, e);
-    for (int k = 0; k < 2 && st == RAWDTW_OK; k++) {
-        if (e && hipEventRecord(e[2 * (np + k)], ctx->stream) != hipSuccess) st = RAWDTW_ERR_DEVICE;
-        if (st == RAWDTW_OK) st = batch_tail(ctx, batch, k);
-        if (st == RAWDTW_OK && e && hipEventRecord(e[2 * (np + k) + 1], ctx->stream) != hipSuccess) st = RAWDTW_ERR_DEVICE;
-    }
-    return st;
+        if (!mark(0, 1) || !mark(1, 0)) return RAWDTW_ERR_DEVICE;
+        hipError_t he = stream_run(batch->sa, ctx->stream_blocks, batch->stream_lds, batch->stream_threads, batch->stream_runs++ > 0, ctx->stream);
+        if (he != hipSuccess) return hip_fail(ctx, he, "batch kernel launch");
+        if (!mark(1, 1)) return RAWDTW_ERR_DEVICE;
+        if (wide_now && ctx->wide_order == 2) { // (timing experiments: the side list behind the tiles -- and behind entry 1's stop: in no bracket)
+            he = stream_wide_fork(ctx, batch->sa);
+            if (he != hipSuccess) return hip_fail(ctx, he, "side list launch");
+        }
+        if (wide && ctx->wide_beside && hipStreamWaitEvent(ctx->stream, ctx->ev_wide_join, 0) != hipSuccess) return RAWDTW_ERR_DEVICE;
+    } else if (const int st = run_all_launches(ctx, batch->plan, e)) return st; // (pair i around the plan's launch i: the table keeps the plan's order)
+    auto tail = [&](uint32_t i, LaunchKind kind) {
+        if (!mark(i, 0)) return (int)RAWDTW_ERR_DEVICE;
+        const int st = batch_tail(ctx, batch, kind);
+        return st == RAWDTW_OK && !mark(i, 1) ? (int)RAWDTW_ERR_DEVICE : st;
+    };
+    if (const int st = tail(nl - 2, kKindChainFold)) return st; // the table's last two entries
+    return tail(nl - 1, kKindReadSelect);
 }
 
 int rawdtw_batch_run(rawdtw_ctx *ctx, rawdtw_batch *batch)
 {
-    if (!ctx || !batch || batch->ctx != ctx || batch_dead(batch)) return fail(ctx, RAWDTW_ERR_INVALID, "batch does not belong to this context");
+    if (const int bad = batch_check(ctx, batch)) return bad;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return batch_enqueue_one(ctx, batch, nullptr);
+    return batch_enqueue_one(ctx, batch, nullptr, 0);
 }
 
 int rawdtw_batch_run_timed(rawdtw_ctx *ctx, rawdtw_batch *batch, float *launch_ms, uint32_t *launch_kind, uint32_t cap,
                            uint32_t *n_launches)
 {
-    std::vector<float> tmp(64, 0.f);
-    int st = rawdtw_batch_run_reps(ctx, batch, 1, launch_ms ? launch_ms : tmp.data(), launch_kind,
-                                   launch_ms ? cap : 64, n_launches);
-    return st;
+    if (launch_ms) return rawdtw_batch_run_reps(ctx, batch, 1, launch_ms, launch_kind, cap, n_launches);
+    if (const int bad = batch_check(ctx, batch)) return bad;
+    std::vector<float> unread(batch_table(batch).size()); // (a timed run all the same: its collect names the kinds)
+    return rawdtw_batch_run_reps(ctx, batch, 1, unread.data(), launch_kind, cap, n_launches);
 }
 
 int rawdtw_batch_enqueue(rawdtw_ctx *ctx, rawdtw_batch *batch, int timed)
 {
-    if (!ctx || !batch || batch->ctx != ctx || batch_dead(batch)) return fail(ctx, RAWDTW_ERR_INVALID, "batch does not belong to this context");
+    if (const int bad = batch_check(ctx, batch)) return bad;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint32_t nl = batch_dtw_launches(batch) + 2;
-    hipEvent_t *e = nullptr;
-    if (timed) {
-        const size_t base = batch->ev.size();
-        batch->ev.resize(base + 2 * nl, nullptr);
-        for (size_t k = base; k < batch->ev.size(); k++) HIP_TRY(ctx, hipEventCreate(&batch->ev[k]));
-        e = &batch->ev[base];
-        batch->ev_runs++;
-    }
-    return batch_enqueue_one(ctx, batch, e);
+    if (!timed) return batch_enqueue_one(ctx, batch, nullptr, 0);
+    const uint32_t nl = (uint32_t)batch_table(batch).size();
+    const size_t base = event_slot(batch->ev_runs, 0, nl);
+    batch->ev.resize(event_slot(batch->ev_runs + 1, 0, nl), nullptr);
+    for (size_t k = base; k < batch->ev.size(); k++) if (!batch->ev[k]) HIP_TRY(ctx, hipEventCreate(&batch->ev[k]));
+    batch->ev_runs++;
+    return batch_enqueue_one(ctx, batch, &batch->ev[base], nl);
 }
 
 int rawdtw_batch_collect(rawdtw_ctx *ctx, rawdtw_batch *batch, float *launch_ms, uint32_t *launch_kind, uint32_t cap,
@@ -816,28 +853,24 @@ int rawdtw_batch_collect(rawdtw_ctx *ctx, rawdtw_batch *batch, float *launch_ms,
     if (n_launches) *n_launches = 0;
     if (n_runs) *n_runs = 0;
     // (a batch whose redo through the job list failed at fetch has no launches left to report: refused like everywhere else)
-    if (!ctx || !batch || batch->ctx != ctx || batch_dead(batch)) return fail(ctx, RAWDTW_ERR_INVALID, "batch does not belong to this context");
-    const uint32_t np = batch_dtw_launches(batch), nl = np + 2;
+    if (const int bad = batch_check(ctx, batch)) return bad;
+    const std::vector<BatchLaunch> t = batch_table(batch);
+    const uint32_t nl = (uint32_t)t.size();
     if (n_launches) *n_launches = nl;
     if (n_runs) *n_runs = batch->ev_runs;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     batch->dirty = false;
     int st = RAWDTW_OK;
-    const MergeSel mg = batch->stream ? MergeSel{} : merge_of(ctx, batch->plan); // (kinds as rawdtw_batch_launch_stats names them)
     for (uint32_t i = 0; i < nl && i < cap; i++) {
         double acc = 0;
         for (uint32_t r = 0; r < batch->ev_runs; r++) {
             float ms = 0.f;
-            const size_t b = (size_t)r * 2 * nl + 2 * i;
+            const size_t b = event_slot(r, i, nl);
             if (hipEventElapsedTime(&ms, batch->ev[b], batch->ev[b + 1]) != hipSuccess) st = RAWDTW_ERR_DEVICE;
             acc += ms;
         }
         if (launch_ms) launch_ms[i] = batch->ev_runs ? (float)(acc / batch->ev_runs) : 0.f;
-        if (launch_kind) {
-            if (i >= np) launch_kind[i] = i == np ? kKindChainFold : kKindReadSelect;
-            else if (batch->stream) launch_kind[i] = i == 0 ? (uint32_t)kKindBandWreg : (kKindBandMerged | ((uint32_t)batch->stream_lds << 8));
-            else launch_kind[i] = (mg.on() && (int)i == mg.tile ? (uint32_t)kKindBandMerged : batch->plan->launches[i].kind) | ((uint32_t)batch->plan->launches[i].param << 8);
-        }
+        if (launch_kind) launch_kind[i] = t[i].word();
     }
     for (auto &e : batch->ev) if (e) (void)hipEventDestroy(e);
     batch->ev.clear();
@@ -849,8 +882,8 @@ int rawdtw_batch_collect(rawdtw_ctx *ctx, rawdtw_batch *batch, float *launch_ms,
 int rawdtw_batch_run_reps(rawdtw_ctx *ctx, rawdtw_batch *batch, uint32_t reps, float *launch_ms, uint32_t *launch_kind,
                           uint32_t cap, uint32_t *n_launches)
 {
-    if (!ctx || !batch || batch->ctx != ctx || batch_dead(batch)) return fail(ctx, RAWDTW_ERR_INVALID, "batch does not belong to this context");
-    if (n_launches) *n_launches = batch_dtw_launches(batch) + 2;
+    if (const int bad = batch_check(ctx, batch)) return bad;
+    if (n_launches) *n_launches = (uint32_t)batch_table(batch).size();
     int st = RAWDTW_OK;
     for (uint32_t r = 0; r < reps && st == RAWDTW_OK; r++) st = rawdtw_batch_enqueue(ctx, batch, launch_ms != nullptr);
     if (launch_ms) {
@@ -867,80 +900,58 @@ int rawdtw_batch_launch_stats(const rawdtw_batch *batch, uint32_t i, uint32_t *k
                               uint64_t *algorithmic_bytes, uint64_t *cells)
 {
     if (!batch || batch_dead(batch)) return RAWDTW_ERR_INVALID;
-    const uint32_t nl = batch_dtw_launches(batch);
-    if (i >= nl + 2) return RAWDTW_ERR_INVALID;
-    if (i >= nl) {
-        if (kind) *kind = i == nl ? kKindChainFold : kKindReadSelect;
-        if (param) *param = 0;
-        batch_count_jobs(const_cast<rawdtw_batch *>(batch));
-        if (n_jobs) *n_jobs = i == nl ? batch->n_chains : batch->n_reads;
+    std::vector<BatchLaunch> t = batch_table(batch);
+    if (i >= t.size()) return RAWDTW_ERR_INVALID;
+    const bool tail = i + 2 >= t.size(); // fold or select
+    rawdtw_plan_info_t I{};
+    if (batch->stream && !tail) { // the device's statistics (every job, byte and cell is counted in exactly one of the two launches)
+        int st = cells ? rawdtw_batch_info(batch, &I, nullptr) : stream_counters(batch->ctx, batch);
+        if (st == RAWDTW_OK && !cells) st = stream_stats_home(batch->ctx, batch, false);
+        if (st != RAWDTW_OK) return st;
+        if (!batch->stream) { // (rawdtw_batch_info has moved the batch to the job-list path)
+            t = batch_table(batch);
+            if (i + 2 >= t.size()) return RAWDTW_ERR_INVALID;
+        }
+    }
+    const BatchLaunch &E = t[i];
+    uint64_t bytes = 0, cl = 0, nj = 0;
+    if (tail) {
+        const bool fold = E.kind == kKindChainFold;
+        batch_count_jobs(batch);
+        nj = fold ? batch->n_chains : batch->n_reads;
         // fold: one 4-byte cost per job + a 24-byte descriptor and two 4-byte results per chain;
         // select: 8 bytes read and 5 written per chain
-        if (algorithmic_bytes)
-            *algorithmic_bytes = i == nl ? batch->n_jobs * 4 + batch->n_chains * 32 : batch->n_chains * 13 + batch->n_reads * 8;
-        if (cells) *cells = 0;
-        return RAWDTW_OK;
-    }
-    if (batch->stream) {
-        rawdtw_plan_info_t I{};
-        if (cells) { int st = rawdtw_batch_info(batch, &I, nullptr); if (st != RAWDTW_OK) return st; }
-        else {
-            rawdtw_batch *b = const_cast<rawdtw_batch *>(batch);
-            int st = stream_counters(b->ctx, b);
-            if (st != RAWDTW_OK) return st;
-            if (!b->cells_counted) {
-                if (stream_sum_stats(b->sa, b->ctx->stream) != hipSuccess ||
-                    hipMemcpyAsync(&b->h_cnt[kCntTileJobs], b->sa.cnt + kCntTileJobs, 3 * 8, hipMemcpyDeviceToHost, b->ctx->stream) != hipSuccess ||
-                    hipStreamSynchronize(b->ctx->stream) != hipSuccess) return RAWDTW_ERR_DEVICE;
+        bytes = fold ? batch->n_jobs * 4 + batch->n_chains * 32 : batch->n_chains * 13 + batch->n_reads * 8;
+    } else if (batch->stream) {
+        const unsigned long long *c = batch->h_cnt;
+        batch_count_jobs(batch);
+        const uint64_t n_side = std::min<uint64_t>(c[kCntOthers], batch->sa.others_cap);
+        uint64_t side_cells = 0;
+        if (cells && n_side) {
+            std::vector<DevJob> side(n_side);
+            if (hipMemcpy(side.data(), batch->sa.ojobs, n_side * sizeof(DevJob), hipMemcpyDeviceToHost) != hipSuccess) return RAWDTW_ERR_DEVICE;
+            for (const DevJob &d : side) side_cells += banded_cells(d.n, d.m, d.R);
+        }
+        const bool wide = i == 0; // (entry 0 is the side list's launch)
+        nj = wide ? n_side : batch->n_jobs - std::min<uint64_t>(n_side, batch->n_jobs);
+        bytes = wide ? c[kCntOtherBytes] : c[kCntTileBytes];
+        cl = wide ? side_cells : I.cells - std::min<uint64_t>(side_cells, I.cells);
+    } else {
+        const rawdtw_plan *pl = batch->plan;
+        auto add = [&](const Launch &X) {
+            for (uint64_t p = X.first; p < X.first + X.count; p++) {
+                const DevJob &d = pl->h_jobs[p];
+                bytes += 4ull * ((uint64_t)d.n + d.m) + 4 + 32;
             }
-            I.algorithmic_bytes = b->h_cnt[kCntTileBytes] + b->h_cnt[kCntOtherBytes];
-        }
-        if (batch->stream) { // (rawdtw_batch_info may have moved the batch to the job-list path)
-            // launch 0 is the side list's (k_wide), launch 1 the tiles' passes (k_runs) -- the kinds rawdtw_batch_collect reports -- and
-            // every job, byte and cell is counted in exactly one of them
-            rawdtw_batch *b = const_cast<rawdtw_batch *>(batch);
-            batch_count_jobs(b);
-            const uint64_t n_side = std::min<uint64_t>(b->h_cnt[kCntOthers], b->sa.others_cap);
-            uint64_t side_cells = 0;
-            if (cells && n_side) {
-                std::vector<DevJob> side(n_side);
-                if (hipMemcpy(side.data(), b->sa.ojobs, n_side * sizeof(DevJob), hipMemcpyDeviceToHost) != hipSuccess) return RAWDTW_ERR_DEVICE;
-                for (const DevJob &d : side) side_cells += banded_cells(d.n, d.m, d.R);
-            }
-            const bool wide = i == 0;
-            if (kind) *kind = wide ? kKindBandWreg : kKindBandMerged;
-            if (param) *param = wide ? 0 : (int32_t)batch->stream_lds;
-            if (n_jobs) *n_jobs = wide ? n_side : batch->n_jobs - std::min<uint64_t>(n_side, batch->n_jobs);
-            if (algorithmic_bytes) *algorithmic_bytes = wide ? b->h_cnt[kCntOtherBytes] : I.algorithmic_bytes - b->h_cnt[kCntOtherBytes];
-            if (cells) *cells = wide ? side_cells : I.cells - std::min<uint64_t>(side_cells, I.cells);
-            return RAWDTW_OK;
-        }
-        if (i >= batch_dtw_launches(batch)) return RAWDTW_ERR_INVALID;
+            if (cells) cl += count_cells(pl, X.first, X.first + X.count);
+            nj += X.count;
+        };
+        // the merged launch reports the classes it carries; a carried launch nothing of its own
+        if (E.kind == kKindBandMerged) { for (const BatchLaunch &X : t) if (X.carried || X.plan == E.plan) add(pl->launches[X.plan]); }
+        else if (!E.carried) add(pl->launches[E.plan]);
     }
-    const rawdtw_plan *pl = batch->plan;
-    const Launch &L = pl->launches[i];
-    const MergeSel mg = merge_of(batch->ctx, pl);
-    uint64_t bytes = 0, cl = 0, nj = 0;
-    auto add = [&](const Launch &X) {
-        for (uint64_t p = X.first; p < X.first + X.count; p++) {
-            const DevJob &d = pl->h_jobs[p];
-            bytes += 4ull * ((uint64_t)d.n + d.m) + 4 + 32;
-        }
-        if (cells) cl += count_cells(pl, X.first, X.first + X.count);
-        nj += X.count;
-    };
-    uint32_t k = L.kind;
-    if (mg.on() && (int)i == mg.tile) { // the merged launch reports the three classes it carries
-        k = kKindBandMerged;
-        add(L);
-        if (mg.grp16 >= 0) add(pl->launches[mg.grp16]);
-        if (mg.grp8 >= 0) add(pl->launches[mg.grp8]);
-        if (mg.wreg >= 0) add(pl->launches[mg.wreg]);
-    } else if (mg.on() && ((int)i == mg.grp16 || (int)i == mg.grp8 || (int)i == mg.wreg)) {
-        /* folded into the merged launch: nothing of its own */
-    } else add(L);
-    if (kind) *kind = k;
-    if (param) *param = L.param;
+    if (kind) *kind = E.kind;
+    if (param) *param = E.param;
     if (n_jobs) *n_jobs = nj;
     if (algorithmic_bytes) *algorithmic_bytes = bytes;
     if (cells) *cells = cl;
@@ -949,7 +960,7 @@ int rawdtw_batch_launch_stats(const rawdtw_batch *batch, uint32_t i, uint32_t *k
 
 int rawdtw_batch_fetch(rawdtw_ctx *ctx, rawdtw_batch *batch, float *score, uint8_t *keep, float *job_cost)
 {
-    if (!ctx || !batch || batch->ctx != ctx || batch_dead(batch)) return fail(ctx, RAWDTW_ERR_INVALID, "batch does not belong to this context");
+    if (const int bad = batch_check(ctx, batch)) return bad;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     for (int attempt = 0; attempt < 2; attempt++) {
         const float *d_cost = batch->stream ? batch->sa.out_full : batch->plan->d_cost;
@@ -980,7 +991,7 @@ int rawdtw_batch_fetch(rawdtw_ctx *ctx, rawdtw_batch *batch, float *score, uint8
                 if (keep) memcpy(keep, batch->h_keep, batch->n_chains);
             }
             if (job_cost) { // chain c's part p (rmap.cpp:248-293) ends at anchor a1 - 2 - p
-                const uint64_t *aoff = batch->in_anchor_off;
+                const uint64_t *aoff = batch->in.anchor_off;
                 uint64_t k = 0;
                 for (uint64_t c = 0; c < batch->n_chains; c++) {
                     const uint64_t a0 = aoff[c], a1 = aoff[c + 1];
@@ -1043,31 +1054,6 @@ int rawdtw_batch_stream_counters(rawdtw_ctx *ctx, rawdtw_batch *batch, uint64_t 
     return RAWDTW_OK;
 }
 
-
-int rawdtw_batch_submit(rawdtw_ctx *ctx, const rawdtw_align_opt_t *opt, uint64_t n_reads, const uint64_t *chain_off,
-                        const uint64_t *anchor_off, const rawdtw_anchor_t *anchors, const uint64_t *ref_base,
-                        const uint32_t *read_base, rawdtw_batch **out)
-{
-    if (ctx) ctx->in_submit = true;
-    int st = rawdtw_batch_create(ctx, opt, n_reads, chain_off, anchor_off, anchors, ref_base, read_base, out);
-    if (ctx) ctx->in_submit = false;
-    if (st != RAWDTW_OK) return st;
-    st = batch_enqueue_one(ctx, *out, nullptr);
-    if (st != RAWDTW_OK) { rawdtw_batch_destroy(*out); *out = nullptr; }
-    return st;
-}
-
-int rawdtw_batch_submit_device(rawdtw_ctx *ctx, const rawdtw_align_opt_t *opt, uint64_t n_reads, const uint64_t *chain_off,
-                               const uint64_t *anchor_off, const rawdtw_anchor_t *d_anchors, const uint64_t *d_ref_base,
-                               const uint32_t *d_read_base, rawdtw_batch **out)
-{
-    if (!ctx) return RAWDTW_ERR_INVALID;
-    const bool was = ctx->resident_arrays; // (the option's meaning, for this one batch: a batch keeps the form it was created under)
-    ctx->resident_arrays = true;
-    const int st = rawdtw_batch_submit(ctx, opt, n_reads, chain_off, anchor_off, d_anchors, d_ref_base, d_read_base, out);
-    ctx->resident_arrays = was;
-    return st;
-}
 
 int rawdtw_batch_fetch_destroy(rawdtw_ctx *ctx, rawdtw_batch *batch, float *score, uint8_t *keep)
 {

@@ -3,7 +3,7 @@
 //   rawdtw_capi.cpp       contexts, options (their table: rawdtw_options.h), arenas, pinned memory, incremental event upload
 //   rawdtw_planner.cpp    the host planner of the job-list path, its launch sequences, rawdtw_plan_*, rawdtw_score_batch
 //   rawdtw_batch.cpp      candidate batches: the stream path's set-up (sync-free, planned on the device), the job-list form,
-//                         run / fetch / diagnostics, chunk rounds
+//                         run / fetch / diagnostics, chunk rounds (a batch's launches by name and count: rawdtw_launches.h)
 //   rawdtw_plan_check.cpp the readers of a device-planned batch's plan behind those diagnostics (no HIP: rawdtw_plan_check.h)
 //   rawdtw_traceback.cpp  rawdtw_traceback_batch*, the single-call drop-ins
 //   rawdtw_index.cpp      the .ind reader
@@ -78,7 +78,6 @@ struct rawdtw_ctx : rawdtw::Options { // (every option is a field of Options: ra
                     // flight on several contexts (swept: best throughput and cleaner per-kernel timings)
     std::vector<StreamWs> ws_free;     // workspaces of destroyed batches, reused by the next ones (no hipMalloc in the steady state)
     uint32_t stream_lds = 0, stream_blocks = 0; // persistent grid of k_stream at the current tile size
-    bool in_submit = false;                     // inside rawdtw_batch_submit*: create and run are one call
     int stream_threads_cached = 0;
     int stream_bpc_cached = -1;
     std::vector<uint64_t> job_off_scratch;
@@ -171,12 +170,39 @@ struct rawdtw_index {
     uint64_t bucket_pos = 0;       // file offset of the first hash bucket (rawdtw_seed_index_load reads from there)
 };
 
+// What a caller hands to rawdtw_batch_create / rawdtw_batch_submit*: its arrays stay valid until fetch (a declined batch is redone from
+// them through the job list), and the two properties of this one batch that are no setting of the context.
+struct BatchIn {
+    const uint64_t *chain_off = nullptr, *anchor_off = nullptr;
+    const rawdtw_anchor_t *anchors = nullptr;
+    const uint64_t *ref_base = nullptr;
+    const uint32_t *read_base = nullptr;
+    // compact hand-over (rawdtw_batch_submit_compact): the lists in packed form instead of `anchors`
+    bool compact = false;
+    const rawdtw_anchor_t *heads = nullptr, *unit_abs = nullptr;
+    const uint16_t *steps = nullptr;
+    const rawdtw_wide_step_t *wide = nullptr;
+    uint64_t n_wide = 0;
+    // chunk rounds (rawdtw_batch_submit_carry): the batch of the round before, the per-chain carry records and the round's SHORT
+    // lists (new entries + junction); anchor_off / anchors stay the FULL lists' (anchors: the fallback's, may be null)
+    const rawdtw_batch *prev = nullptr;
+    const rawdtw_carry_t *carry = nullptr;
+    const uint64_t *new_off = nullptr;
+    const rawdtw_anchor_t *new_anchors = nullptr;
+    bool resident = false; // anchors / ref_base / read_base (a round: new_anchors) are DEVICE pointers, used in place ("resident_arrays", rawdtw_batch_submit_device)
+    bool submit = false;   // create and first run are one call: the side list's launch may go out between the planning launches
+};
+
 struct rawdtw_batch {
     rawdtw_ctx *ctx = nullptr;
     rawdtw_plan *plan = nullptr;   // job-list path
     rawdtw_align_opt_t opt{};
-    uint64_t n_reads = 0, n_chains = 0, n_jobs = 0; // (n_jobs of a sync-free batch: counted on first use, see batch_count_jobs)
-    bool jobs_counted = false;
+    uint64_t n_reads = 0, n_chains = 0;
+    // filled the first time somebody asks, also through a const handle (the diagnostics): the job count of a sync-free batch (batch_count_jobs),
+    // its counters (stream_counters; `dirty` goes with the wait) and its statistics (stream_stats_home)
+    mutable uint64_t n_jobs = 0;
+    mutable bool jobs_counted = false, cnt_valid = false, stats_home = false, cells_counted = false;
+    mutable bool dirty = false;          // work enqueued since the last host synchronisation
     ChainDesc *d_chains = nullptr;
     uint64_t *d_chain_off = nullptr;
     uint32_t *d_fold_order = nullptr; // chain ids, longest chain first
@@ -196,32 +222,14 @@ struct rawdtw_batch {
     float *h_score = nullptr;            // ... and, behind it at the device block's offsets, of the scores and the keep flags: counters, scores
     uint8_t *h_keep = nullptr;           // and flags lie one behind the other in the workspace and come home in ONE copy (rawdtw_batch_fetch:
     size_t res_bytes = 0;                // every operation on a batch's stream is a step of its latency through the pipeline: three copies -> one, + 2 %)
-    bool cnt_valid = false, cells_counted = false;
     uint32_t stream_runs = 0;                // DTW launches issued for this batch (the tile queue needs a reset from the second on)
-    bool dirty = false;                  // work enqueued since the last host synchronisation
     size_t ws_bytes = 0;
     hipEvent_t ev_plan[4] = {nullptr, nullptr, nullptr, nullptr}; // ("time_plan") around scan + side list order, the side list's launch, the pass planning
     bool wide_out = false;            // the side list's launch for the next run went out with the planning launches
-    // the caller's arrays (valid until fetch: a declined batch is redone from them through the job list)
-    const uint64_t *in_chain_off = nullptr, *in_anchor_off = nullptr;
-    const rawdtw_anchor_t *in_anchors = nullptr;
-    const uint64_t *in_ref_base = nullptr;
-    const uint32_t *in_read_base = nullptr;
-    // compact hand-over (rawdtw_batch_submit_compact): the lists in packed form instead of in_anchors
-    const rawdtw_anchor_t *in_heads = nullptr, *in_unit_abs = nullptr;
-    const uint16_t *in_steps = nullptr;
-    const rawdtw_wide_step_t *in_wide = nullptr;
-    uint64_t in_n_wide = 0;
-    // chunk rounds (rawdtw_batch_submit_carry): the batch of the round before, the per-chain carry records and the round's SHORT
-    // lists (new entries + junction); in_anchor_off / in_anchors stay the FULL lists' (in_anchors: the fallback's, may be null)
-    const rawdtw_batch *in_prev = nullptr;
-    const rawdtw_carry_t *in_carry = nullptr;
-    const uint64_t *in_new_off = nullptr;
-    const rawdtw_anchor_t *in_new_anchors = nullptr;
+    BatchIn in;                          // what the caller handed over (in.prev: read at create only)
     bool in_carried = false;             // a chunk round: the device works on the short lists
     uint64_t parts_carried = 0;          // (summed from the carry records at create)
-    // "resident_arrays": the three big arrays are device pointers; host copies are made only if the job list is needed
-    bool in_resident = false;
+    // host copies of in.anchors / in.ref_base / in.read_base, made only if the job list is needed: of resident arrays, or the compact lists unpacked
     std::vector<rawdtw_anchor_t> host_anchors;
     std::vector<uint64_t> host_ref_base;
     std::vector<uint32_t> host_read_base;
@@ -451,14 +459,15 @@ template <typename F> void parallel_for(int T, F fn)
 }
 int build_plan(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, bool traceback, rawdtw_plan **out);
 uint64_t count_cells(const rawdtw_plan *pl, uint64_t p0, uint64_t p1);
-struct MergeSel { int tile = -1, grp16 = -1, grp8 = -1, wreg = -1; bool on() const { return tile >= 0; } };
-MergeSel merge_of(const rawdtw_ctx *ctx, const rawdtw_plan *pl);
+MergeSel merge_of(const rawdtw_ctx *ctx, const rawdtw_plan *pl); // (merge_select, rawdtw_launches.h, under the context's settings)
 int run_all_launches(rawdtw_ctx *ctx, rawdtw_plan *pl, hipEvent_t *ev);
 void plan_release_device(rawdtw_plan *plan);
 // the tile records as downloaded from the device against the job list (rawdtw_batch_verify_plan): "" or what is wrong
 std::string verify_uploaded_tiles(const rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const rawdtw_plan *pl, const TileDesc *tiles,
                                   size_t n_tiles, const TileSpan *spans, size_t n_spans, const TileJob *tjobs, size_t n_tjobs, std::vector<uint8_t> &seen);
 // ---- rawdtw_batch.cpp ----
+// a batch whose (deferred) planning failed has neither form left: every entry point but destroy refuses it
+inline bool batch_dead(const rawdtw_batch *b) { return !b->stream && !b->plan; }
 void batch_detach(rawdtw_ctx *ctx, rawdtw_batch *b);
 // the batch's results as they will stand: a device-planned batch's counters home (a wait for its stream), and a batch that path declined
 // scored again through the job list (*redone: its device arrays are others now)

@@ -5,25 +5,12 @@
 
 #include "../../include/rawdtw.h"
 #include "rawdtw_chunks.h"
+#include "rawdtw_launches.h" // LaunchKind, Launch, the merge selection, a batch's launch table
 #include "rawdtw_plan_fmt.h" // DevJob, kFlagExcludeLast, the stream plan's constants and packed records
 
 namespace rawdtw {
 
 constexpr float kInf = 1e10f; // dtw.cpp:38,310-313: the float nearest 1e10
-
-// launch kinds (also reported by rawdtw_plan_run_timed)
-enum LaunchKind : uint32_t {
-    kKindBandLane = 1,  // lane-per-job banded DP inside the tile kernel (one launch for all eligible jobs)
-    kKindBandWave = 2,  // wave-per-job banded kernel
-    kKindFullWave = 3,  // wave-per-job full-matrix wavefront (score only)
-    kKindFullTb = 4,    // same, writing packed directions
-    kKindTbWalk = 5,    // traceback walk
-    kKindChainFold = 6, // per-chain fold of the part costs (align_chain)
-    kKindReadSelect = 7, // per-read accept/cut loop (gen_chains DTW block)
-    kKindBandWreg = 8,   // wave-per-job banded kernel, band in registers (param = registers per lane per buffer)
-    kKindBandLaneHi = 9, // tile kernel instance for the wider bands (radius 4..8)
-    kKindBandMerged = 10 // reporting only: the tile launch when it also carries the two small banded classes (k_band_merged)
-};
 
 // Tile kernel records (planner output)
 struct TileDesc { uint32_t job_first, n_jobs, span_first, n_spans; }; // n_spans bit 31: many short spans (a by-shape tile)
@@ -63,13 +50,6 @@ constexpr uint32_t kSpanGapFloats = 48; // a window starting this close behind a
 constexpr int kFullWgWaves = 4;        // waves per job in the pipelined-strip variant of the full-matrix kernel
 constexpr int kMaxWregChunks = 32;     // register-resident wave kernel: radius + 1 <= 64 * 32
 constexpr int kMaxWaveBandK = 13000;   // 3*K floats of LDS must fit 160 KiB
-
-struct Launch {
-    uint32_t kind;
-    int32_t param;      // band tile: LDS floats ; wreg: registers per lane ; full: rows per lane ; band wave: LDS floats
-    uint64_t first;     // first plan-order job
-    uint64_t count;     // jobs in this launch
-};
 
 // per-job workspace for the full-matrix kernels
 struct FullAux {

@@ -681,24 +681,8 @@ int run_launch(rawdtw_ctx *ctx, rawdtw_plan *pl, const Launch &L, hipStream_t st
     return RAWDTW_OK;
 }
 
-// Which launches of a plan travel as one k_band_merged launch (indices into pl->launches, -1 = none).
-
-MergeSel merge_of(const rawdtw_ctx *ctx, const rawdtw_plan *pl)
-{
-    MergeSel m;
-    if (!ctx->merge_small || ctx->tile_threads != 256 || (ctx->n_side > 0 && !ctx->serial_launches)) return m;
-    int tile = -1;
-    for (size_t i = 0; i < pl->launches.size(); i++) {
-        const Launch &L = pl->launches[i];
-        if (L.kind == kKindBandLane) tile = (int)i;
-        else if (L.kind == kKindBandWreg && L.param == -16) m.grp16 = (int)i;
-        else if (L.kind == kKindBandWreg && L.param == -8) m.grp8 = (int)i;
-        else if (L.kind == kKindBandWreg && L.param == 0) m.wreg = (int)i;
-    }
-    if (tile >= 0 && (m.grp16 >= 0 || m.grp8 >= 0 || m.wreg >= 0)) m.tile = tile;
-    else m = MergeSel{};
-    return m;
-}
+// Which launches of a plan travel as one k_band_merged launch under the context's settings (merge_select: rawdtw_launches.h).
+MergeSel merge_of(const rawdtw_ctx *ctx, const rawdtw_plan *pl) { return merge_select(ctx->merge_small, ctx->tile_threads, ctx->n_side, ctx->serial_launches, pl->launches); }
 
 int run_merged(rawdtw_ctx *ctx, rawdtw_plan *pl, const MergeSel &m, hipStream_t stream)
 {
@@ -834,7 +818,7 @@ int rawdtw_plan_run_timed(rawdtw_ctx *ctx, rawdtw_plan *plan, float *launch_ms, 
         if (hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]) != hipSuccess) { st = RAWDTW_ERR_DEVICE; break; }
         if (i < cap) {
             if (launch_ms) launch_ms[i] = ms;
-            if (launch_kind) launch_kind[i] = plan->launches[i].kind | ((uint32_t)plan->launches[i].param << 8);
+            if (launch_kind) launch_kind[i] = launch_word(plan->launches[i].kind, plan->launches[i].param); // (a plan's raw kinds: never kKindBandMerged)
         }
     }
     for (auto &e : ev) (void)hipEventDestroy(e);

@@ -280,7 +280,7 @@ int rawdtw_round_end(rawdtw_ctx *ctx, const rawdtw_select_opt_t *opt, uint64_t n
 int rawdtw_batch_round_end_begin(rawdtw_ctx *ctx, rawdtw_batch *batch, const rawdtw_select_opt_t *opt, const rawdtw_chain_rec_t *recs, int recs_on_device)
 {
     if (!ctx) return RAWDTW_ERR_INVALID;
-    if (!batch || batch->ctx != ctx || (!batch->stream && !batch->plan)) return fail(ctx, RAWDTW_ERR_INVALID, "batch does not belong to this context");
+    if (!batch || batch->ctx != ctx || batch_dead(batch)) return fail(ctx, RAWDTW_ERR_INVALID, "batch does not belong to this context");
     if (!opt || (!recs && batch->n_chains)) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
     if (round_end_busy(ctx)) return fail(ctx, RAWDTW_ERR_INVALID, "a round end is begun on this context and not fetched");
     const RoundEndIn in{batch->d_chain_off, batch->d_score, batch->d_keep, true, recs, recs_on_device != 0};
