@@ -118,7 +118,7 @@ def main():
     med = lambda res, c: float(np.median([r[0][c] for r in runs[res]]))  # noqa: E731
     s_stats, r_stats = runs[False][-1][1], runs[True][-1][1]
     nr = n
-    extra = (nr + 1) * 8 + nr * 5 + (nr + 1) * 8 + nr * 8   # a resident round's own small arrays (rawdtw_mapper.cpp, resident_begin)
+    extra = (nr + 1) * 8 + nr * 5 + (nr + 1) * 8 + nr * 8   # a resident round's own small arrays (rawdtw_mapper_round.cpp, resident_bytes)
     checks = {}
     capped = bool(so_far.max() <= 2048)
     last = r_stats[-1]
