@@ -23,6 +23,12 @@
  *  - The full-matrix functions (DTW_global, DTW_global_tb: dtw.cpp:37-66,
  *    595-667) have no sentinel: row 0 and column 0 are running sums, whatever
  *    they pass.
+ *  - The semiglobal functions (DTW_semiglobal, DTW_semiglobal_slow,
+ *    DTW_semiglobal_tb: dtw.cpp:526-593, 669-753) run the sentinel-free
+ *    recurrence of _slow and _tb: row 0 is ASSIGNED the distance, column 0 is
+ *    a running sum.  DTW_semiglobal itself carries a float(1e10) in its first
+ *    column and its running best; the device equals it wherever every prefix
+ *    sum of column 0 and the result stay below 1e10.
  *  - Subnormal inputs, distances and sums are preserved, and -0.0 inputs cost
  *    +0.0, in every body.
  * tests/test_value_domain_gpu.py holds every body to this on costs below, around
@@ -310,6 +316,43 @@ int rawdtw_dtw_global_slantedbanded_antidiagonalwise(rawdtw_ctx *ctx, const floa
 int rawdtw_dtw_global_tb(rawdtw_ctx *ctx, const float *a, uint32_t n, const float *b, uint32_t m,
                          int exclude_last, float *cost, uint32_t *path_len, uint32_t *path_i,
                          uint32_t *path_j, float *path_d);
+
+/* ---- semiglobal (subsequence) DTW: replaces DTW_semiglobal, DTW_semiglobal_slow and DTW_semiglobal_tb (dtw.hpp; dtw.cpp:526-593,
+ * 669-753).  a (the job's read window) is aligned end to end against the best-matching substring of b (its reference window):
+ *   D(0, j) = d(0, j);  D(i, 0) = D(i-1, 0) + d(i, 0);  D(i, j) = min(min(D(i-1, j), D(i, j-1)), D(i-1, j-1)) + d(i, j)
+ * in fp32 with d = |a[i] - b[j]|.  The cost is the minimum of row n - 1 and end_j the FIRST column that attains it.  The path starts
+ * at (n - 1, end_j), walks by the three-way rule of the global traceback (at j == 0 it moves up) and stops as soon as i == 0: its
+ * first element is (0, j0), it has at most n + m - 1 elements.  Jobs are rawdtw_job_t with band_radius == RAWDTW_FULL; they are
+ * bucketed by n alone (a always lies over the lanes of the kernel, also when n > m) and every (n, m) with n, m >= 1 runs.
+ * h_events == NULL: the jobs' read_off index the context's event arena as it lies (as rawdtw_traceback_arena_steps) and n_events is
+ * not looked at; else the arena is replaced by h_events first.  Refused before anything is enqueued: RAWDTW_ERR_INVALID for n == 0,
+ * m == 0, a banded job, a null argument and a context without the arena it needs; RAWDTW_ERR_RANGE for a window outside the arenas.
+ * n_jobs == 0 is RAWDTW_OK and touches nothing.
+ *   rawdtw_semiglobal_batch            cost and end_j of every job.  exclude_last subtracts d(n - 1, end_j), as DTW_semiglobal_slow
+ *        and DTW_semiglobal_tb do (DTW_semiglobal takes the argument and ignores it).
+ *   rawdtw_semiglobal_traceback_steps  the paths too, in the step form of rawdtw_traceback_batch_steps: room for n + m - 1 elements a
+ *        job from path_off[k] on, start first; per element its distance and one byte (bit 0: i advanced, bit 1: j advanced; element
+ *        0 is (0, out_j0[k]), its byte is 0).  With exclude_last the last element is dropped and the cost reduced by its distance.
+ *        Sub-batches under "tb_workspace_mb" ("tb_sub_batches" says how many) as the global traceback.
+ *   rawdtw_semiglobal_timing           device time of the most recent of those two calls on the context: the fill kernels, and the
+ *        walk and finish kernels (0 for a cost-only call); the direction bytes written and the path elements that came home.
+ *   rawdtw_dtw_semiglobal, rawdtw_dtw_semiglobal_tb   the single-call drop-ins (host pointers; convenient, not fast).  The first
+ *        ignores exclude_last as its namesake does; the second writes (path_i, path_j, path_d) like rawdtw_dtw_global_tb.
+ *   rawdtw_semiglobal_host, rawdtw_semiglobal_tb_host   the recurrence restated on the host (no device work): the yardstick of the
+ *        tests where a shape is too large for a recorded answer.  end_j and the path arrays may be NULL. ---- */
+int rawdtw_semiglobal_batch(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events, uint64_t n_events,
+                            float *out_cost, uint32_t *out_end_j);
+int rawdtw_semiglobal_traceback_steps(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events,
+                                      uint64_t n_events, float *out_cost, uint32_t *out_j0, const uint64_t *path_off,
+                                      uint32_t *path_len, uint8_t *path_step, float *path_d);
+int rawdtw_semiglobal_timing(const rawdtw_ctx *ctx, float *fill_ms, float *walk_ms, uint64_t *direction_bytes,
+                             uint64_t *path_elements);
+int rawdtw_dtw_semiglobal(rawdtw_ctx *ctx, const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, float *cost);
+int rawdtw_dtw_semiglobal_tb(rawdtw_ctx *ctx, const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, float *cost,
+                             uint32_t *path_len, uint32_t *path_i, uint32_t *path_j, float *path_d);
+int rawdtw_semiglobal_host(const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, float *cost, uint32_t *end_j);
+int rawdtw_semiglobal_tb_host(const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, float *cost, uint32_t *end_j,
+                              uint32_t *path_len, uint32_t *path_i, uint32_t *path_j, float *path_d);
 
 /* ---- host-side mirror of align_chain / the DTW block of gen_chains
  * (src/rmap.cpp:181-313, 509-530): job decomposition and exact replay.  Pure

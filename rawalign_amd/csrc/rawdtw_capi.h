@@ -6,6 +6,7 @@
 //                         run / fetch / diagnostics, chunk rounds (a batch's launches by name and count: rawdtw_launches.h)
 //   rawdtw_plan_check.cpp the readers of a device-planned batch's plan behind those diagnostics (no HIP: rawdtw_plan_check.h)
 //   rawdtw_traceback.cpp  rawdtw_traceback_batch*, the single-call drop-ins
+//   rawdtw_semiglobal.cpp subsequence DTW: rawdtw_semiglobal_*, its drop-ins (kernels: rawdtw_semiglobal_kernels.hip)
 //   rawdtw_index.cpp      the .ind reader
 // There is NO CPU fallback in any of them: every scoring entry point runs the HIP kernels or returns an error status.
 #pragma once
@@ -96,6 +97,8 @@ struct rawdtw_ctx : rawdtw::Options { // (every option is a field of Options: ra
     float tb_fill_ms = 0.f, tb_walk_ms = 0.f;          // device time of the most recent rawdtw_traceback_batch
     uint64_t tb_dir_written = 0, tb_path_elems = 0;
     uint64_t tb_sub_batches = 0;  // "tb_sub_batches" (read-only): sub-batches of the most recent traceback call, known before its first plan is built
+    float semi_fill_ms = 0.f, semi_walk_ms = 0.f;      // device time of the most recent semiglobal call (rawdtw_semiglobal.cpp)
+    uint64_t semi_dir_written = 0, semi_path_elems = 0;
     // reference arena.  An arena the library allocated (rawdtw_upload_reference, rawdtw_index_upload) is held through a
     // counted RefHold, shared by every context that adopted it with rawdtw_share_reference: it is freed when the last of
     // them lets go, so the owner may upload another reference or be destroyed while sharers still run on the old one.

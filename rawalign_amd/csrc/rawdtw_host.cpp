@@ -613,3 +613,69 @@ extern "C" int rawdtw_round_match_chains(uint64_t n_reads, const uint64_t *chain
     new_off[chain_off[n_reads]] = at;
     return RAWDTW_OK;
 }
+
+// ---- semiglobal DTW restated (DTW_semiglobal_slow / DTW_semiglobal_tb, dtw.cpp:552-593, 669-753): row 0 assigned, column 0 a running
+// sum, the first minimum of the last row; two rolling rows, and for the path one direction byte a cell decided while the cell's
+// three neighbours are at hand (the rule of dtw.cpp:717-730).  fp32, one rounded subtract and one rounded add a cell.
+namespace {
+int semiglobal_host(const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, float *cost, uint32_t *end_j,
+                    uint32_t *path_len, uint32_t *path_i, uint32_t *path_j, float *path_d)
+{
+    if (!a || !b || !cost || n == 0 || m == 0) return RAWDTW_ERR_INVALID;
+    const bool tb = path_len != nullptr;
+    if (tb && (!path_i || !path_j || !path_d)) return RAWDTW_ERR_INVALID;
+    auto dist = [](float x, float y) { return std::fabs(x - y); };
+    std::vector<float> prev(m), cur(m);
+    std::vector<uint8_t> dir;
+    if (tb) dir.assign((size_t)n * m, 0);
+    for (uint32_t j = 0; j < m; j++) prev[j] = dist(a[0], b[j]);
+    for (uint32_t i = 1; i < n; i++) {
+        cur[0] = prev[0] + dist(a[i], b[0]);
+        for (uint32_t j = 1; j < m; j++) {
+            const float left = prev[j], top = cur[j - 1], topleft = prev[j - 1]; // the traceback's names (dtw.cpp:717-719)
+            cur[j] = std::min(std::min(left, top), topleft) + dist(a[i], b[j]);
+            if (tb) dir[(size_t)i * m + j] = left < std::min(top, topleft) ? 1 : top < std::min(left, topleft) ? 2 : 0;
+        }
+        prev.swap(cur);
+    }
+    float best = prev[0];
+    uint32_t best_j = 0;
+    for (uint32_t j = 1; j < m; j++)
+        if (prev[j] < best) { best = prev[j]; best_j = j; }
+    *cost = exclude_last ? best - dist(a[n - 1], b[best_j]) : best;
+    if (end_j) *end_j = best_j;
+    if (!tb) return RAWDTW_OK;
+    std::vector<uint32_t> ri, rj;
+    uint32_t i = n - 1, j = best_j;
+    ri.push_back(i); rj.push_back(j);
+    while (i > 0) {
+        if (j == 0) i--;
+        else {
+            const uint8_t c = dir[(size_t)i * m + j];
+            if (c == 1) i--;
+            else if (c == 2) j--;
+            else { i--; j--; }
+        }
+        ri.push_back(i); rj.push_back(j);
+    }
+    const uint32_t len = (uint32_t)ri.size() - (exclude_last ? 1u : 0u); // start first; the last element is popped (dtw.cpp:744-748)
+    for (uint32_t q = 0; q < len; q++) {
+        path_i[q] = ri[ri.size() - 1 - q]; path_j[q] = rj[ri.size() - 1 - q];
+        path_d[q] = dist(a[path_i[q]], b[path_j[q]]);
+    }
+    *path_len = len;
+    return RAWDTW_OK;
+}
+} // namespace
+
+extern "C" int rawdtw_semiglobal_host(const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, float *cost, uint32_t *end_j)
+{
+    return semiglobal_host(a, n, b, m, exclude_last, cost, end_j, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int rawdtw_semiglobal_tb_host(const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, float *cost, uint32_t *end_j,
+                                         uint32_t *path_len, uint32_t *path_i, uint32_t *path_j, float *path_d)
+{
+    if (!path_len) return RAWDTW_ERR_INVALID;
+    return semiglobal_host(a, n, b, m, exclude_last, cost, end_j, path_len, path_i, path_j, path_d);
+}

@@ -1,0 +1,342 @@
+// rawdtw_semiglobal.cpp -- subsequence DTW behind the C ABI: rawdtw_semiglobal_batch, rawdtw_semiglobal_traceback_steps and the
+// single-call drop-ins for DTW_semiglobal / DTW_semiglobal_tb (dtw.hpp; dtw.cpp:526-593, 669-753).  Host code only: validation,
+// the jobs' classes, their launches and the traceback's sub-batches.  The job-list planner (rawdtw_planner.cpp) knows nothing of
+// these jobs: they are bucketed here, by the class rawdtw_semiglobal.h defines, longest first inside a class (a launch takes as
+// long as its longest job).  There is no CPU fallback: the kernels run or the call returns an error status.
+#include "rawdtw_capi.h"
+#include "rawdtw_semiglobal.h"
+
+using namespace rawdtw;
+using namespace rawdtw::capi;
+
+namespace {
+
+struct SemiLaunch { int cls; uint64_t first, count; };
+
+// the jobs [begin, begin + cnt) in launch order; a record's aux is the job's index inside the stretch
+struct SemiPlan {
+    std::vector<uint32_t> order; // position -> index inside the stretch
+    std::vector<DevJob> jobs;
+    std::vector<FullAux> aux;
+    std::vector<SemiLaunch> launches;
+    uint64_t bnd_floats = 0, dir_bytes = 0;
+};
+
+void semi_plan(const rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t cnt, bool traceback, SemiPlan &pl)
+{
+    struct Keyed { uint64_t key; uint32_t idx; };
+    std::vector<Keyed> keyed(cnt);
+    const uint64_t lim = (1ull << 28) - 1;
+    for (uint64_t k = 0; k < cnt; k++) {
+        const rawdtw_job_t &j = jobs[k];
+        const uint64_t c = (uint64_t)semi_class(j.n, j.m, ctx->full_wg);
+        keyed[k] = Keyed{(c << 56) | ((lim - std::min<uint64_t>(j.m, lim)) << 28) | (lim - std::min<uint64_t>(j.n, lim)), (uint32_t)k};
+    }
+    std::sort(keyed.begin(), keyed.end(), [](const Keyed &x, const Keyed &y) { return x.key != y.key ? x.key < y.key : x.idx < y.idx; });
+    pl.order.resize(cnt); pl.jobs.resize(cnt); pl.aux.assign(cnt, FullAux{0, 0});
+    for (uint64_t p = 0; p < cnt; p++) {
+        const uint32_t k = keyed[p].idx;
+        const rawdtw_job_t &j = jobs[k];
+        const int c = (int)(keyed[p].key >> 56);
+        pl.order[p] = k;
+        DevJob &d = pl.jobs[p];
+        d.ref_off = j.ref_off; d.read_off = j.read_off; d.n = j.n; d.m = j.m; d.R = -1;
+        d.flags = j.exclude_last ? kFlagExcludeLast : 0u; d.aux = k;
+        pl.aux[p].bnd_off = pl.bnd_floats;
+        pl.bnd_floats += semi_bnd_floats(j.n, j.m, c);
+        if (traceback) {
+            pl.aux[p].dir_off = pl.dir_bytes;
+            pl.dir_bytes += (semi_dir_bytes(j.n, j.m, c) + 255) & ~255ull;
+        }
+        if (pl.launches.empty() || pl.launches.back().cls != c) pl.launches.push_back(SemiLaunch{c, p, 0});
+        pl.launches.back().count++;
+    }
+}
+
+// a device block that goes when the call ends (behind the context's stream)
+struct DevBlock {
+    rawdtw_ctx *ctx; char *p = nullptr;
+    explicit DevBlock(rawdtw_ctx *c) : ctx(c) {}
+    ~DevBlock() { if (p) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(p); } }
+    int reserve(size_t bytes)
+    {
+        if (hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(bytes, 256)) != hipSuccess) {
+            p = nullptr; (void)hipGetLastError();
+            return fail(ctx, RAWDTW_ERR_OOM, "semiglobal workspace allocation failed");
+        }
+        return RAWDTW_OK;
+    }
+};
+struct EventPair {
+    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    ~EventPair() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Every refusal, before anything is enqueued: INVALID for a zero length or a banded job, RANGE for a window outside the arenas.
+int semi_check(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, bool arena, uint64_t n_events)
+{
+    if (arena && !ctx->d_ev) return fail(ctx, RAWDTW_ERR_INVALID, "the context has no event arena");
+    if (!ctx->d_ref) return fail(ctx, RAWDTW_ERR_INVALID, "the context has no reference arena");
+    const uint64_t n_ev = arena ? ctx->n_ev : n_events;
+    for (uint64_t k = 0; k < n_jobs; k++) {
+        const rawdtw_job_t &j = jobs[k];
+        if (j.n == 0 || j.m == 0 || j.n >= 0x7fffffffu || j.m >= 0x7fffffffu)
+            return fail(ctx, RAWDTW_ERR_INVALID, "job " + std::to_string(k) + ": zero length (dtw.cpp:527-528, 670 assert)");
+        if (j.band_radius != RAWDTW_FULL)
+            return fail(ctx, RAWDTW_ERR_INVALID, "job " + std::to_string(k) + ": a semiglobal job has no band (band_radius must be RAWDTW_FULL)");
+        if ((uint64_t)j.read_off + j.n > n_ev || j.ref_off > ctx->n_ref || j.ref_off + j.m > ctx->n_ref)
+            return fail(ctx, RAWDTW_ERR_RANGE, "job " + std::to_string(k) + ": window outside the arenas");
+    }
+    return RAWDTW_OK;
+}
+
+// records up, fill launches of one plan; cost and end_j are left on the device (indexed inside the stretch)
+int semi_fill(rawdtw_ctx *ctx, const SemiPlan &pl, bool traceback, DevJob *d_jobs, FullAux *d_aux, float *d_cost, uint32_t *d_endj,
+              float *d_bnd, uint8_t *d_dir)
+{
+    const uint64_t cnt = pl.jobs.size();
+    HIP_TRY(ctx, hipMemcpyAsync(d_jobs, pl.jobs.data(), cnt * sizeof(DevJob), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_aux, pl.aux.data(), cnt * sizeof(FullAux), hipMemcpyHostToDevice, ctx->stream));
+    for (const SemiLaunch &L : pl.launches) {
+        hipError_t e = launch_semi_wave(L.cls, traceback, d_jobs + L.first, L.count, d_aux + L.first, ctx->d_ev, ctx->d_ref, d_cost,
+                                        d_endj, d_bnd, d_dir, ctx->stream);
+        if (e != hipSuccess) return hip_fail(ctx, e, "semiglobal fill launch");
+    }
+    return RAWDTW_OK;
+}
+
+int semi_batch(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events, uint64_t n_events, float *out_cost,
+               uint32_t *out_end_j)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (n_jobs == 0) return RAWDTW_OK;
+    if (!jobs || !out_cost || !out_end_j) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    if (n_jobs >= 0x7fffffffull) return fail(ctx, RAWDTW_ERR_INVALID, "too many jobs for one call");
+    const bool arena = h_events == nullptr;
+    int st = semi_check(ctx, jobs, n_jobs, arena, n_events);
+    if (st != RAWDTW_OK) return st;
+    if (!arena && (st = rawdtw_upload_events(ctx, h_events, n_events)) != RAWDTW_OK) return st;
+    SemiPlan pl;
+    semi_plan(ctx, jobs, n_jobs, false, pl);
+    DevBlock blk(ctx);
+    const size_t need = al256(n_jobs * sizeof(DevJob)) + al256(n_jobs * sizeof(FullAux)) + 2 * al256(n_jobs * 4) + al256(pl.bnd_floats * 4);
+    if ((st = blk.reserve(need)) != RAWDTW_OK) return st;
+    char *p = blk.p;
+    DevJob *d_jobs = carve<DevJob>(p, n_jobs);
+    FullAux *d_aux = carve<FullAux>(p, n_jobs);
+    float *d_cost = carve<float>(p, n_jobs);
+    uint32_t *d_endj = carve<uint32_t>(p, n_jobs);
+    float *d_bnd = carve<float>(p, pl.bnd_floats);
+    EventPair ev;
+    for (int k = 0; k < 2; k++) HIP_TRY(ctx, hipEventCreate(&ev.e[k]));
+    ctx->semi_fill_ms = ctx->semi_walk_ms = 0.f; ctx->semi_dir_written = 0; ctx->semi_path_elems = 0;
+    HIP_TRY(ctx, hipEventRecord(ev.e[0], ctx->stream));
+    if ((st = semi_fill(ctx, pl, false, d_jobs, d_aux, d_cost, d_endj, d_bnd, nullptr)) != RAWDTW_OK) return st;
+    HIP_TRY(ctx, hipEventRecord(ev.e[1], ctx->stream));
+    // (a record's aux is the caller's job index: the results come home in job order)
+    HIP_TRY(ctx, hipMemcpyAsync(out_cost, d_cost, n_jobs * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out_end_j, d_endj, n_jobs * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ev.e[0], ev.e[1]) == hipSuccess) ctx->semi_fill_ms = ms;
+    return RAWDTW_OK;
+}
+
+// Traceback: sub-batches under the direction-buffer budget ("tb_workspace_mb", as rawdtw_traceback_batch*), one after another --
+// fill, walk, finish, paths home, written into the caller's arrays.  Exactly one of path_step and (path_i, path_j) is given.
+int semi_traceback(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events, uint64_t n_events, float *out_cost,
+                   uint32_t *out_j0, const uint64_t *path_off, uint32_t *path_len, uint8_t *path_step, uint32_t *path_i, uint32_t *path_j,
+                   float *path_d)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (n_jobs == 0) return RAWDTW_OK;
+    if (!jobs || !out_cost || !out_j0 || !path_off || !path_len || !path_d || (!path_step && (!path_i || !path_j)))
+        return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    if (n_jobs >= 0x7fffffffull) return fail(ctx, RAWDTW_ERR_INVALID, "too many jobs for one call");
+    const bool arena = h_events == nullptr;
+    int st = semi_check(ctx, jobs, n_jobs, arena, n_events);
+    if (st != RAWDTW_OK) return st;
+    if (!arena && (st = rawdtw_upload_events(ctx, h_events, n_events)) != RAWDTW_OK) return st;
+
+    uint64_t budget = 16ull << 30;
+    if (ctx->tb_workspace_mb) budget = ctx->tb_workspace_mb << 20; // (the option goes before the variable)
+    else if (const char *e = getenv("RAWDTW_TB_WORKSPACE_MB")) budget = std::max<uint64_t>(1, strtoull(e, nullptr, 10)) << 20;
+    // the split: a job joins the current sub-batch unless that passes the budget (a job over the budget goes alone)
+    struct Sub { uint64_t begin, cnt, acc; SemiPlan pl; };
+    std::vector<Sub> subs;
+    for (uint64_t begin = 0; begin < n_jobs;) {
+        uint64_t end = begin, bytes = 0;
+        while (end < n_jobs) {
+            const rawdtw_job_t &j = jobs[end];
+            const uint64_t b = semi_dir_bytes(j.n, j.m, semi_class(j.n, j.m, ctx->full_wg)) + 256;
+            if (end > begin && bytes + b > budget) break;
+            bytes += b;
+            end++;
+        }
+        subs.push_back(Sub{begin, end - begin, 0, SemiPlan{}});
+        begin = end;
+    }
+    ctx->tb_sub_batches = subs.size();
+    size_t dev_need = 0;
+    uint64_t dir_need = 0, acc_max = 0, cnt_max = 0;
+    std::vector<std::vector<uint64_t>> poff(subs.size());
+    for (size_t q = 0; q < subs.size(); q++) {
+        Sub &sb = subs[q];
+        semi_plan(ctx, jobs + sb.begin, sb.cnt, true, sb.pl);
+        poff[q].resize(sb.cnt);
+        for (uint64_t p = 0; p < sb.cnt; p++) { poff[q][p] = sb.acc; sb.acc += (uint64_t)sb.pl.jobs[p].n + sb.pl.jobs[p].m - 1; }
+        const size_t need = al256(sb.cnt * sizeof(DevJob)) + al256(sb.cnt * sizeof(FullAux)) + 4 * al256(sb.cnt * 4) + al256(sb.cnt * 8) +
+                            al256(sb.pl.bnd_floats * 4) + 3 * al256(sb.acc * 4) + al256(sb.acc);
+        dev_need = std::max(dev_need, need); dir_need = std::max(dir_need, sb.pl.dir_bytes);
+        acc_max = std::max(acc_max, sb.acc); cnt_max = std::max(cnt_max, sb.cnt);
+    }
+    if (ctx->tb_dir_bytes < dir_need) { // the context's direction workspace, grow-only (one traceback at a time per context)
+        if (ctx->d_tb_dir) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->d_tb_dir); }
+        ctx->d_tb_dir = nullptr; ctx->tb_dir_bytes = 0;
+        const uint64_t want = dir_need + dir_need / 8;
+        if ((st = dev_alloc(ctx, &ctx->d_tb_dir, want)) != RAWDTW_OK) return st;
+        ctx->tb_dir_bytes = want;
+    }
+    DevBlock blk(ctx);
+    if ((st = blk.reserve(dev_need)) != RAWDTW_OK) return st;
+    EventPair ev;
+    for (hipEvent_t &e : ev.e) HIP_TRY(ctx, hipEventCreate(&e));
+    ctx->semi_fill_ms = ctx->semi_walk_ms = 0.f; ctx->semi_dir_written = 0; ctx->semi_path_elems = 0;
+    std::vector<float> h_cost(cnt_max), h_pd(acc_max);
+    std::vector<uint32_t> h_len(cnt_max), h_j0(cnt_max);
+    std::vector<uint8_t> h_mv(acc_max);
+
+    for (size_t q = 0; q < subs.size(); q++) {
+        const Sub &sb = subs[q];
+        char *p = blk.p;
+        DevJob *d_jobs = carve<DevJob>(p, sb.cnt);
+        FullAux *d_aux = carve<FullAux>(p, sb.cnt);
+        float *d_cost = carve<float>(p, sb.cnt);
+        uint32_t *d_endj = carve<uint32_t>(p, sb.cnt);
+        uint32_t *d_plen = carve<uint32_t>(p, sb.cnt);
+        uint32_t *d_j0 = carve<uint32_t>(p, sb.cnt);
+        uint64_t *d_poff = carve<uint64_t>(p, sb.cnt);
+        float *d_bnd = carve<float>(p, sb.pl.bnd_floats);
+        uint32_t *d_ti = carve<uint32_t>(p, sb.acc);
+        uint32_t *d_tj = carve<uint32_t>(p, sb.acc);
+        float *d_pd = carve<float>(p, sb.acc);
+        uint8_t *d_mv = carve<uint8_t>(p, sb.acc);
+        HIP_TRY(ctx, hipMemcpyAsync(d_poff, poff[q].data(), sb.cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(ev.e[0], ctx->stream));
+        if ((st = semi_fill(ctx, sb.pl, true, d_jobs, d_aux, d_cost, d_endj, d_bnd, ctx->d_tb_dir)) != RAWDTW_OK) return st;
+        HIP_TRY(ctx, hipEventRecord(ev.e[1], ctx->stream));
+        for (const SemiLaunch &L : sb.pl.launches) {
+            hipError_t e = launch_semi_walk(L.cls, d_jobs + L.first, L.count, d_aux + L.first, ctx->d_ev, ctx->d_ref, ctx->d_tb_dir, d_endj,
+                                            d_poff + L.first, d_plen + L.first, d_j0 + L.first, d_ti, d_tj, d_mv, d_pd, ctx->stream);
+            if (e != hipSuccess) return hip_fail(ctx, e, "semiglobal walk launch");
+        }
+        HIP_TRY(ctx, hipEventRecord(ev.e[2], ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h_cost.data(), d_cost, sb.cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h_len.data(), d_plen, sb.cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h_j0.data(), d_j0, sb.cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h_pd.data(), d_pd, sb.acc * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h_mv.data(), d_mv, sb.acc, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ev.e[0], ev.e[1]) == hipSuccess) ctx->semi_fill_ms += ms;
+        if (hipEventElapsedTime(&ms, ev.e[1], ev.e[2]) == hipSuccess) ctx->semi_walk_ms += ms;
+        ctx->semi_dir_written += sb.pl.dir_bytes;
+        for (uint64_t pp = 0; pp < sb.cnt; pp++) {
+            const uint64_t k = sb.begin + sb.pl.order[pp];
+            out_cost[k] = h_cost[sb.pl.order[pp]]; // (cost and end_j are indexed inside the stretch, lengths and j0 by position)
+            out_j0[k] = h_j0[pp];
+            const uint32_t len = h_len[pp];
+            // start-first already (k_semi_finish); the reference pops the last element when exclude_last_element is set (dtw.cpp:744-748)
+            const uint32_t outlen = jobs[k].exclude_last ? len - 1 : len;
+            const uint64_t src = poff[q][pp], dst = path_off[k];
+            if (path_step) memcpy(path_step + dst, h_mv.data() + src, outlen);
+            else {
+                uint32_t i = 0, j = h_j0[pp];
+                for (uint32_t e = 0; e < outlen; e++) { i += h_mv[src + e] & 1u; j += h_mv[src + e] >> 1; path_i[dst + e] = i; path_j[dst + e] = j; }
+            }
+            memcpy(path_d + dst, h_pd.data() + src, (size_t)outlen * 4);
+            path_len[k] = outlen;
+            ctx->semi_path_elems += outlen;
+        }
+    }
+    return RAWDTW_OK;
+}
+
+// b goes to a private reference arena for the duration of a single call (the hold on the context's own arena stays)
+struct PrivateRef {
+    rawdtw_ctx *ctx; float *saved; uint64_t saved_n; float *d_b = nullptr;
+    explicit PrivateRef(rawdtw_ctx *c) : ctx(c), saved(c->d_ref), saved_n(c->n_ref) {}
+    int put(const float *b, uint32_t m)
+    {
+        int st = dev_alloc(ctx, &d_b, ((uint64_t)m + 3) & ~3ull);
+        if (st != RAWDTW_OK) return st;
+        hipError_t e = hipMemcpyAsync(d_b, b, (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) return hip_fail(ctx, e, "operand upload");
+        ctx->d_ref = d_b; ctx->n_ref = m;
+        return RAWDTW_OK;
+    }
+    ~PrivateRef()
+    {
+        ctx->d_ref = saved; ctx->n_ref = saved_n;
+        if (d_b) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(d_b); }
+    }
+};
+
+} // namespace
+
+extern "C" {
+
+int rawdtw_semiglobal_batch(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events, uint64_t n_events,
+                            float *out_cost, uint32_t *out_end_j)
+{
+    return semi_batch(ctx, jobs, n_jobs, h_events, n_events, out_cost, out_end_j);
+}
+
+int rawdtw_semiglobal_traceback_steps(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events, uint64_t n_events,
+                                      float *out_cost, uint32_t *out_j0, const uint64_t *path_off, uint32_t *path_len, uint8_t *path_step,
+                                      float *path_d)
+{
+    if (ctx && n_jobs && !path_step) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    return semi_traceback(ctx, jobs, n_jobs, h_events, n_events, out_cost, out_j0, path_off, path_len, path_step, nullptr, nullptr, path_d);
+}
+
+int rawdtw_semiglobal_timing(const rawdtw_ctx *ctx, float *fill_ms, float *walk_ms, uint64_t *direction_bytes, uint64_t *path_elements)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (fill_ms) *fill_ms = ctx->semi_fill_ms;
+    if (walk_ms) *walk_ms = ctx->semi_walk_ms;
+    if (direction_bytes) *direction_bytes = ctx->semi_dir_written;
+    if (path_elements) *path_elements = ctx->semi_path_elems;
+    return RAWDTW_OK;
+}
+
+int rawdtw_dtw_semiglobal(rawdtw_ctx *ctx, const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, float *cost)
+{
+    (void)exclude_last; // DTW_semiglobal takes the argument and never reads it (dtw.cpp:526-550)
+    if (!ctx || !a || !b || !cost) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    if (n == 0 || m == 0) return fail(ctx, RAWDTW_ERR_INVALID, "zero length (dtw.cpp:527-528 assert)");
+    PrivateRef pr(ctx);
+    int st = pr.put(b, m);
+    if (st != RAWDTW_OK) return st;
+    rawdtw_job_t j{0, 0, n, m, RAWDTW_FULL, 0u, 0};
+    uint32_t end_j = 0;
+    return semi_batch(ctx, &j, 1, a, n, cost, &end_j);
+}
+
+int rawdtw_dtw_semiglobal_tb(rawdtw_ctx *ctx, const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, float *cost,
+                             uint32_t *path_len, uint32_t *path_i, uint32_t *path_j, float *path_d)
+{
+    if (!ctx || !a || !b || !cost || !path_len || !path_i || !path_j || !path_d) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    if (n == 0 || m == 0) return fail(ctx, RAWDTW_ERR_INVALID, "zero length (dtw.cpp:670 asserts)");
+    PrivateRef pr(ctx);
+    int st = pr.put(b, m);
+    if (st != RAWDTW_OK) return st;
+    rawdtw_job_t j{0, 0, n, m, RAWDTW_FULL, exclude_last ? 1u : 0u, 0};
+    uint64_t off = 0;
+    uint32_t j0 = 0;
+    return semi_traceback(ctx, &j, 1, a, n, cost, &j0, &off, path_len, nullptr, path_i, path_j, path_d);
+}
+
+} // extern "C"

@@ -1,0 +1,43 @@
+// rawdtw_semiglobal.h -- what rawdtw_semiglobal_kernels.hip (the kernels) and rawdtw_semiglobal.cpp (validation, classes, launches, sub-batches)
+// share: a job's class, the sizes of its boundary rows and of its packed directions, and the launchers.
+#pragma once
+#include <cstdint>
+
+#include "rawdtw_internal.h"
+
+namespace rawdtw {
+
+// A semiglobal job's class: 0..3 = 1, 2, 4, 8 rows a lane on one wave, by n ALONE (a always lies over the lanes: the rule of the
+// full-matrix classes, full_rpl, applied to n), 4 = 8 rows a lane on four pipelined waves: three strips or more, under the guards of
+// the progress word (m < 2^21 columns, fewer than 2^11 strips) and the context's "full_wg".
+constexpr int kSemiClasses = 5;
+inline int semi_rpl(int cls) { return cls >= 3 ? 8 : 1 << cls; }
+inline int semi_class(uint32_t n, uint32_t m, bool full_wg)
+{
+    const int c = n <= 64 ? 0 : n <= 128 ? 1 : n <= 256 ? 2 : 3;
+    if (c == 3 && n > 2 * 512u && full_wg && m < (1u << 21) && (n + 511u) / 512u < (1u << 11)) return 4;
+    return c;
+}
+// floats of boundary rows (none for a one-strip job; a ring of kFullWgWaves rows for the pipelined class)
+inline uint64_t semi_bnd_floats(uint32_t n, uint32_t m, int cls)
+{
+    if (n <= 64u * (uint32_t)semi_rpl(cls)) return 0;
+    return (uint64_t)(cls == 4 ? kFullWgWaves : 1) * (((uint64_t)m + 63) & ~63ull);
+}
+// bytes of packed directions: [strip][block][lane][step in block], blocks of 16 bytes a lane (k_semi_wave)
+inline uint64_t semi_dir_bytes(uint32_t n, uint32_t m, int cls)
+{
+    const uint64_t rpl = (uint64_t)semi_rpl(cls);
+    const uint64_t strips = (n + 64 * rpl - 1) / (64 * rpl);
+    const uint64_t spb = rpl == 8 ? 8 : 16;
+    return strips * (((uint64_t)m + 63 + spb - 1) / spb) * 64 * 16;
+}
+
+hipError_t launch_semi_wave(int cls, bool traceback, const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev,
+                            const float *ref, float *out_cost, uint32_t *out_end_j, float *bnd_ws, uint8_t *dir_ws, hipStream_t s);
+// the walk from (n - 1, end_j) to row 0 (end-first (i, j) into tmp_i / tmp_j), then start-first steps, distances and j0
+hipError_t launch_semi_walk(int cls, const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev, const float *ref,
+                            const uint8_t *dir_ws, const uint32_t *end_j, const uint64_t *path_off, uint32_t *path_len,
+                            uint32_t *path_j0, uint32_t *tmp_i, uint32_t *tmp_j, uint8_t *path_mv, float *path_d, hipStream_t s);
+
+} // namespace rawdtw

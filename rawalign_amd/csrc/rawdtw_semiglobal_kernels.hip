@@ -1,0 +1,357 @@
+// rawdtw_semiglobal_kernels.hip -- gfx950 kernels for subsequence DTW: a aligned end to end against the best-matching substring of b.
+//
+// What they replace (reference file:line):
+//   k_semi_wave<.,false>                                   : DTW_semiglobal, DTW_semiglobal_slow   src/dtw.cpp:526-593
+//   k_semi_wave<.,true> + k_semi_walk_wave + k_semi_finish : DTW_semiglobal_tb                     src/dtw.cpp:669-753
+//
+// k_semi_wave is the sibling of k_full_wave (rawdtw_kernels.hip): the same skewed wavefront, rows over the lanes, RPL rows a lane,
+// strips of 64 * RPL rows, boundary rows in HBM, the same packed 2-bit directions in the same buffer layout.  What differs:
+//   no transposition  the recurrence is not symmetric: a ALWAYS lies over the lanes and b is swept, also when n > m, so a
+//                     direction code never changes its meaning (1: i - 1, 2: j - 1, 0: both).
+//   borders           row 0 is assigned, D(0, j) = d(0, j): the lane that holds it takes the distance itself, no minimum with a made-up
+//                     neighbour.  Column 0 is the running sum as in the full matrix (beyond the matrix lies +inf, which loses every min).
+//   result            the minimum of the last row and the FIRST column that attains it: the lane that owns row n - 1 keeps a running
+//                     (minimum, column) pair over the columns it finishes, replaced on strict < only -- columns ascend in a lane, so
+//                     the first one wins as in dtw.cpp:577-585.  No reduction over lanes, no second pass.  The register that holds
+//                     row n - 1 is chosen OUTSIDE the column loop (a copy of the loop for each of the RPL places), so the loop
+//                     pays one vector compare a column for it; the pair itself is kept by the scalar unit.
+// Cell values do not depend on evaluation order (min is exact, each cell is one rounded subtract and one rounded add); built with
+// -ffp-contract=off.  The sentinel-free recurrence: include/rawdtw.h, arithmetic contract.
+#include <type_traits>
+
+#include "rawdtw_internal.h"
+#include "rawdtw_dp.h"
+#include "rawdtw_semiglobal.h"
+
+namespace rawdtw {
+
+template <int RPL> struct SemiDirWord { using type = uint8_t; };
+template <> struct SemiDirWord<8> { using type = uint16_t; };
+
+// WAVES = 1: one wave per job, strips in sequence.  WAVES = 4 (jobs of three strips or more): the workgroup's waves take strips
+// w, w + 4, ... as a pipeline, strip s + 1 trailing strip s by at least one 64-column chunk; boundary rows are a ring of WAVES rows
+// and a strip publishes the columns it has flushed through an LDS progress word, (strip << 21) | columns -- so m < 2^21 and fewer
+// than 2^11 strips (semi_class sees to it).
+template <int RPL, bool TB, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void k_semi_wave(const DevJob *__restrict__ jobs, const FullAux *__restrict__ aux,
+                                                          const float *__restrict__ ev, const float *__restrict__ ref,
+                                                          float *__restrict__ out_cost, uint32_t *__restrict__ out_end_j,
+                                                          float *__restrict__ bnd_ws, uint8_t *__restrict__ dir_ws)
+{
+    using word_t = typename SemiDirWord<RPL>::type;
+    constexpr float kNone = __builtin_inff(); // beyond the matrix: loses every min (no sentinel, as in k_full_wave)
+    const DevJob jb = jobs[blockIdx.x];
+    const FullAux ax = aux[blockIdx.x];
+    const int lane = threadIdx.x & 63;
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); // (wave-uniform, and known to be)
+    const float *Y = ev + jb.read_off; // a: over the lanes
+    const float *X = ref + jb.ref_off; // b: swept
+    const uint32_t NY = jb.n, NX = jb.m;
+    constexpr uint32_t STRIP = 64u * RPL;
+    const uint32_t nstrips = (NY + STRIP - 1) / STRIP;
+    // direction words in blocks of SPB steps, [strip][block][lane][step in block]: k_full_wave's layout
+    constexpr uint32_t SPB = 16u / sizeof(word_t);
+    const uint32_t TXB = (NX + 63 + SPB - 1) / SPB;
+    const uint32_t row_stride = (NX + 63u) & ~63u; // floats per boundary row (semi_bnd_floats)
+    float *bnd_base = bnd_ws + ax.bnd_off;
+    uint4 *dirs = reinterpret_cast<uint4 *>(dir_ws + ax.dir_off);
+    __shared__ __attribute__((aligned(16))) word_t tbuf_all[TB ? WAVES * 64 * SPB : 1];
+    word_t *tbuf = tbuf_all + (TB ? wv * 64 * SPB : 0);
+    __shared__ uint32_t progress[WAVES]; // progress[s % WAVES] = (s << 21) | columns of strip s flushed
+    if (WAVES > 1) {
+        if (threadIdx.x < WAVES) progress[threadIdx.x] = 0;
+        __syncthreads();
+    }
+
+    // the lane that owns row n - 1, the running minimum of that row (its bits: wave-uniform), and the step at which the minimum last improved (strictly):
+    // lane l works on column t - l at step t, so the first column that attains the minimum is best_t - owner
+    const uint32_t owner = (uint32_t)__builtin_amdgcn_readfirstlane((int)(((NY - 1) / RPL) & 63u));
+    const uint64_t owner_bit = 1ull << owner;
+    uint32_t best_bits = 0x7f800000u; // +inf
+    uint32_t best_t = owner;
+    for (uint32_t s = wv; s < nstrips; s += WAVES) {
+        const float *bnd_in = bnd_base + (uint64_t)((s + WAVES - 1) % WAVES) * row_stride; // written by strip s-1
+        float *bnd = bnd_base + (uint64_t)(s % WAVES) * row_stride;                          // read by strip s+1
+        const uint32_t y0 = (s * 64u + lane) * RPL;
+        const uint32_t rows_here = (NY - s * STRIP) < STRIP ? (NY - s * STRIP) : STRIP;
+        const uint32_t lanes_here = (rows_here + RPL - 1) / RPL;
+        const uint32_t steps = NX + lanes_here - 1;
+        const bool has_rows = y0 < NY;
+        const bool hands_down = (s + 1 < nstrips); // then the strip is full and lane 63 owns its last row
+        const bool row0 = (s == 0 && lane == 0);   // this lane's first register is row 0: assigned, not minimised
+
+        // The strip's column loop.  KK: the register of its lane in which row n - 1 lies (the last strip), -1: a strip above the last.
+        auto strip = [&](auto kk_c) {
+            constexpr int KK = decltype(kk_c)::value;
+            float yv[RPL], v[RPL];
+#pragma unroll
+            for (int k = 0; k < RPL; k++) {
+                uint32_t y = y0 + k;
+                yv[k] = Y[y < NY ? y : NY - 1];
+                v[k] = kNone; // column -1
+            }
+            float diag_in = kNone; // (row 0 has no corner to start from: it is assigned)
+            float last_out = kNone, xval = 0.0f, xchunk = 0.0f, bchunk = kNone, wchunk = 0.0f;
+            for (uint32_t t = 0; t < steps; t++) {
+                if ((t & 63u) == 0) {
+                    const uint32_t idx = t + lane;
+                    xchunk = X[idx < NX ? idx : NX - 1];
+                    if (s > 0) {
+                        if (WAVES > 1) {
+                            // wait until strip s-1 has flushed the columns of this chunk
+                            const uint32_t need = ((s - 1) << 21) | ((t + 64u < NX) ? t + 64u : NX);
+                            while (__hip_atomic_load(&progress[(s - 1) % WAVES], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < need)
+                                __builtin_amdgcn_s_sleep(1);
+                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                        }
+                        bchunk = idx < NX ? bnd_in[idx] : kNone;
+                    }
+                }
+                const float x0 = read_lane(xchunk, (int)(t & 63u));
+                const float b0 = read_lane(bchunk, (int)(t & 63u));
+                const float up_in = wave_shr1(last_out, b0);
+                xval = wave_shr1(xval, x0);
+                const uint32_t x = t - (uint32_t)lane;
+                if (x < NX) {
+                    float d = diag_in, ab = up_in;
+                    uint32_t code = 0;
+#pragma unroll
+                    for (int k = 0; k < RPL; k++) {
+                        const float left = v[k];
+                        const float dd = dist(xval, yv[k]);
+                        float nv = min3f(ab, left, d) + dd;
+                        if (k == 0) nv = row0 ? dd : nv; // D(0, j) = d(0, j)  (dtw.cpp:566-568, 679-681)
+                        if (TB) {
+                            // dtw.cpp:717-730 with left = D[i-1][j] (here `ab`), top = D[i][j-1] (here `left`):
+                            //   ab < min(left, d) -> 1 (i-1) ; else left < min(ab, d) -> 2 (j-1) ; else 0.
+                            // Two bit planes shifted in from below, as k_full_wave does it (v_min_f32 as the instruction: fminf would
+                            // quiet signalling NaNs first).  Row 0's codes are never read: the walk ends there.
+                            float t_up, t_lf;
+                            asm("v_min_f32 %0, %1, %2" : "=v"(t_up) : "v"(left), "v"(d));
+                            asm volatile("v_cmp_lt_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(code) : "v"(ab), "v"(t_up) : "vcc");
+                            asm("v_min_f32 %0, %1, %2" : "=v"(t_lf) : "v"(ab), "v"(d));
+                            asm volatile("v_cmp_lt_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(code) : "v"(left), "v"(t_lf) : "vcc");
+                        }
+                        d = left; ab = nv; v[k] = nv;
+                    }
+                    diag_in = up_in;
+                    last_out = v[RPL - 1];
+                    if (TB) {
+                        // bit reversal puts cell k at bits 2k ("i - 1", shifted in first) and 2k + 1 ("j - 1")
+                        const uint32_t w = __builtin_bitreverse32(code) >> (32 - 2 * RPL);
+                        tbuf[lane * SPB + (t % SPB)] = (word_t)w;
+                    }
+                }
+                if constexpr (KK >= 0) {
+                    // (outside the lanes' `x < NX` block: a scalar register written under a divergent branch is no scalar to the compiler.  A lane
+                    // outside its columns holds +inf or its last value in v[KK]: neither is below its minimum.)
+                    // The running minimum of row n - 1 lives in a SCALAR register, and so does the step of its last strict improvement:
+                    // one vector compare a column against the scalar, its mask cut down to the owner's bit; the scalar unit (which
+                    // issues beside the other waves' vector work -- the loop is bound by the vector unit) branches over the update,
+                    // a v_readlane of the new minimum and a move of the step, which a job takes a handful of times.  One vector
+                    // instruction a column.  (As `if (cand < best)` on vector values the compiler built a branch around two moves.)
+                    asm volatile("v_cmp_gt_f32 vcc, %0, %2\n\t"
+                                 "s_and_b64 vcc, vcc, %3\n\t"
+                                 "s_cmp_lg_u64 vcc, 0\n\t"
+                                 "s_cbranch_scc0 .Lsemi_keep_%=\n\t"
+                                 "v_readlane_b32 %0, %2, %5\n\t"
+                                 "s_mov_b32 %1, %4\n"
+                                 ".Lsemi_keep_%=:"
+                                 : "+s"(best_bits), "+s"(best_t)
+                                 : "v"(v[KK]), "s"(owner_bit), "s"(t), "s"(owner)
+                                 : "vcc", "scc");
+                }
+                if (TB && ((t % SPB) == SPB - 1 || t + 1 == steps)) {
+                    // same wave wrote and reads the buffer; LDS operations of a wave complete in order, the
+                    // fence keeps the compiler from reordering the differently typed accesses
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                    const uint4 blk = *reinterpret_cast<const uint4 *>(&tbuf[lane * SPB]);
+                    if (has_rows) dirs[((uint64_t)s * TXB + t / SPB) * 64u + lane] = blk;
+                }
+                if (hands_down && t >= 63u) {
+                    // lane 63 finished column c = t-63 in this step; gather 64 of them, store coalesced
+                    const uint32_t c = t - 63u;
+                    const float v63 = read_lane(last_out, 63);
+                    if ((uint32_t)lane == (c & 63u)) wchunk = v63;
+                    if ((c & 63u) == 63u || c == NX - 1) {
+                        const uint32_t base = c & ~63u;
+                        if (base + lane <= c) bnd[base + lane] = wchunk;
+                        if (WAVES > 1) {
+                            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                            if (lane == 0)
+                                __hip_atomic_store(&progress[s % WAVES], (s << 21) | (c + 1u), __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_WORKGROUP);
+                        }
+                    }
+                }
+            }
+        };
+        if (hands_down) strip(std::integral_constant<int, -1>{});
+        else {
+            const uint32_t kk = (NY - 1) % RPL; // wave-uniform
+            if constexpr (RPL == 1) strip(std::integral_constant<int, 0>{});
+            else if constexpr (RPL == 2) {
+                if (kk == 0) strip(std::integral_constant<int, 0>{});
+                else strip(std::integral_constant<int, 1>{});
+            } else if constexpr (RPL == 4) {
+                switch (kk) {
+                case 0: strip(std::integral_constant<int, 0>{}); break;
+                case 1: strip(std::integral_constant<int, 1>{}); break;
+                case 2: strip(std::integral_constant<int, 2>{}); break;
+                default: strip(std::integral_constant<int, 3>{}); break;
+                }
+            } else {
+                switch (kk) {
+                case 0: strip(std::integral_constant<int, 0>{}); break;
+                case 1: strip(std::integral_constant<int, 1>{}); break;
+                case 2: strip(std::integral_constant<int, 2>{}); break;
+                case 3: strip(std::integral_constant<int, 3>{}); break;
+                case 4: strip(std::integral_constant<int, 4>{}); break;
+                case 5: strip(std::integral_constant<int, 5>{}); break;
+                case 6: strip(std::integral_constant<int, 6>{}); break;
+                default: strip(std::integral_constant<int, 7>{}); break;
+                }
+            }
+        }
+        __threadfence_block();
+    }
+    // the wave that ran the last strip owns the result, its lane that holds row n - 1 the pair
+    if (nstrips > 0 && ((nstrips - 1) % WAVES) == wv) {
+        float result = __builtin_bit_cast(float, best_bits);
+        const uint32_t end_j = best_t - owner;
+        if (lane == 0) {
+            if (jb.flags & kFlagExcludeLast) result = result - dist(Y[NY - 1], X[end_j]); // dtw.cpp:587-589, 744-746
+            out_cost[jb.aux] = result;
+            out_end_j[jb.aux] = end_j;
+        }
+    }
+}
+
+// The walk, one wave per job: k_tb_walk_wave's (a block row of directions in LDS, all lanes in lockstep on uniform values, steps
+// buffered one a lane and stored 64 at a time) from (n - 1, end_j) until i == 0 (dtw.cpp:709-738; at j == 0 it moves up).
+// Output: (i, j) end-first, at most n + m - 1 elements.
+template <int RPL>
+__global__ __launch_bounds__(64) void k_semi_walk_wave(const DevJob *__restrict__ jobs, const FullAux *__restrict__ aux,
+                                                       const uint8_t *__restrict__ dir_ws, const uint32_t *__restrict__ end_j,
+                                                       const uint64_t *__restrict__ path_off, uint32_t *__restrict__ path_len,
+                                                       uint32_t *__restrict__ tmp_i, uint32_t *__restrict__ tmp_j)
+{
+    using word_t = typename SemiDirWord<RPL>::type;
+    constexpr uint32_t SPB = 16u / sizeof(word_t);
+    __shared__ __attribute__((aligned(16))) word_t row[64 * SPB]; // one block row: [lane][step in block]
+    const int lane = threadIdx.x;
+    const DevJob jb = jobs[blockIdx.x];
+    const FullAux ax = aux[blockIdx.x];
+    const uint64_t TXB = ((uint64_t)jb.m + 63u + SPB - 1) / SPB; // blocks per strip
+    const uint4 *dirs = reinterpret_cast<const uint4 *>(dir_ws + ax.dir_off);
+    const uint64_t po = path_off[blockIdx.x];
+    uint32_t i = jb.n - 1, j = end_j[jb.aux], k = 0;
+    if (j >= jb.m) j = jb.m - 1; // (never: the fill wrote a column of the matrix)
+    uint32_t bi = i, bj = j; // this lane's slot of the 64-step output buffer (lane = step & 63)
+    uint64_t cur = ~0ull;    // block row held in LDS
+    auto flush = [&](uint32_t upto) { // steps [upto - ((upto - 1) & 63) - 1 .. upto) sit in lanes 0..(upto-1)&63
+        const uint32_t base = (upto - 1) & ~63u;
+        if ((uint32_t)lane <= ((upto - 1) & 63u)) { tmp_i[po + base + lane] = bi; tmp_j[po + base + lane] = bj; }
+    };
+    k = 1; // step 0: the end cell (lane 0's slot holds it)
+    while (i > 0) {
+        if (j == 0) i--;
+        else {
+            const uint32_t sidx = i / (64u * RPL), l = (i / RPL) & 63u, kk = i % RPL;
+            const uint32_t t = j + l;
+            const uint64_t key = (uint64_t)sidx * TXB + t / SPB;
+            if (key != cur) {
+                reinterpret_cast<uint4 *>(row)[lane] = dirs[key * 64u + lane];
+                cur = key;
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                __builtin_amdgcn_s_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            }
+            uint32_t word = row[l * SPB + (t % SPB)];
+            word = (uint32_t)__builtin_amdgcn_readfirstlane((int)word);
+            const uint32_t code = (word >> (2 * kk)) & 3u;
+            if (code == 1u) i--;
+            else if (code == 2u) j--;
+            else { i--; j--; }
+            // (the next block row overwrites `row` only behind the barrier above, which all lanes reach together)
+        }
+        if ((uint32_t)lane == (k & 63u)) { bi = i; bj = j; }
+        k++;
+        if ((k & 63u) == 0) flush(k);
+    }
+    if ((k & 63u) != 0) flush(k);
+    if (lane == 0) path_len[blockIdx.x] = k;
+}
+
+// Start-first order, the step byte of rawdtw_traceback_batch_steps (bit 0: i advanced, bit 1: j advanced; element 0's is 0), the
+// distance, and the column j0 the path starts in: one thread per path element.
+__global__ __launch_bounds__(256) void k_semi_finish(const DevJob *__restrict__ jobs, uint32_t count, const float *__restrict__ ev,
+                                                     const float *__restrict__ ref, const uint64_t *__restrict__ path_off,
+                                                     const uint32_t *__restrict__ path_len, const uint32_t *__restrict__ tmp_i,
+                                                     const uint32_t *__restrict__ tmp_j, uint32_t *__restrict__ path_j0,
+                                                     uint8_t *__restrict__ path_mv, float *__restrict__ path_d)
+{
+    const uint32_t g = blockIdx.x;
+    if (g >= count) return;
+    const DevJob jb = jobs[g];
+    const float *a = ev + jb.read_off;
+    const float *b = ref + jb.ref_off;
+    const uint64_t po = path_off[g];
+    const uint32_t len = path_len[g];
+    for (uint32_t q = threadIdx.x; q < len; q += 256) {
+        const uint32_t i = tmp_i[po + len - 1 - q], j = tmp_j[po + len - 1 - q];
+        uint32_t mv = 0;
+        if (q) mv = (i - tmp_i[po + len - q]) | ((j - tmp_j[po + len - q]) << 1);
+        else path_j0[g] = j;
+        path_mv[po + q] = (uint8_t)mv; path_d[po + q] = dist(a[i], b[j]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// launchers
+// ---------------------------------------------------------------------------------------------
+template <int RPL, int WAVES>
+static hipError_t launch_semi_t(bool tb, const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev, const float *ref,
+                                float *out_cost, uint32_t *out_end_j, float *bnd_ws, uint8_t *dir_ws, hipStream_t s)
+{
+    if (tb) hipLaunchKernelGGL((k_semi_wave<RPL, true, WAVES>), dim3((uint32_t)count), dim3(64 * WAVES), 0, s, jobs, aux, ev, ref,
+                               out_cost, out_end_j, bnd_ws, dir_ws);
+    else hipLaunchKernelGGL((k_semi_wave<RPL, false, WAVES>), dim3((uint32_t)count), dim3(64 * WAVES), 0, s, jobs, aux, ev, ref,
+                            out_cost, out_end_j, bnd_ws, dir_ws);
+    return hipGetLastError();
+}
+
+hipError_t launch_semi_wave(int cls, bool tb, const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev,
+                            const float *ref, float *out_cost, uint32_t *out_end_j, float *bnd_ws, uint8_t *dir_ws, hipStream_t s)
+{
+    if (count == 0) return hipSuccess;
+    switch (cls) {
+    case 0: return launch_semi_t<1, 1>(tb, jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, s);
+    case 1: return launch_semi_t<2, 1>(tb, jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, s);
+    case 2: return launch_semi_t<4, 1>(tb, jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, s);
+    case 3: return launch_semi_t<8, 1>(tb, jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, s);
+    case 4: return launch_semi_t<8, kFullWgWaves>(tb, jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_semi_walk(int cls, const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev, const float *ref,
+                            const uint8_t *dir_ws, const uint32_t *end_j, const uint64_t *path_off, uint32_t *path_len,
+                            uint32_t *path_j0, uint32_t *tmp_i, uint32_t *tmp_j, uint8_t *path_mv, float *path_d, hipStream_t s)
+{
+    if (count == 0) return hipSuccess;
+    const dim3 grid((uint32_t)count), block(64);
+    switch (cls) {
+    case 0: hipLaunchKernelGGL(k_semi_walk_wave<1>, grid, block, 0, s, jobs, aux, dir_ws, end_j, path_off, path_len, tmp_i, tmp_j); break;
+    case 1: hipLaunchKernelGGL(k_semi_walk_wave<2>, grid, block, 0, s, jobs, aux, dir_ws, end_j, path_off, path_len, tmp_i, tmp_j); break;
+    case 2: hipLaunchKernelGGL(k_semi_walk_wave<4>, grid, block, 0, s, jobs, aux, dir_ws, end_j, path_off, path_len, tmp_i, tmp_j); break;
+    default: hipLaunchKernelGGL(k_semi_walk_wave<8>, grid, block, 0, s, jobs, aux, dir_ws, end_j, path_off, path_len, tmp_i, tmp_j); break;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_semi_finish, grid, dim3(256), 0, s, jobs, (uint32_t)count, ev, ref, path_off, path_len, tmp_i, tmp_j,
+                       path_j0, path_mv, path_d);
+    return hipGetLastError();
+}
+
+} // namespace rawdtw

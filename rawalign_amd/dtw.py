@@ -737,3 +737,92 @@ class Engine:
                                                   _ptr(pi), _ptr(pj), _ptr(pd)))
         k = ln.value
         return DtwResult(np.float32(c.value), pi[:k].copy(), pj[:k].copy(), pd[:k].copy())
+
+    def DTW_semiglobal(self, a_values, b_values, exclude_last_element=False) -> DtwResult:
+        """DTW_semiglobal (src/dtw.cpp:526-550): a end to end against the best-matching substring of b.  The cost (the flag is ignored, as
+        its namesake ignores it); no path: i, j and difference are empty."""
+        a, b = _f32(a_values), _f32(b_values)
+        c = C.c_float()
+        self._check(self.lib.rawdtw_dtw_semiglobal(self._ctx, _ptr(a), len(a), _ptr(b), len(b), int(exclude_last_element), C.byref(c)))
+        return DtwResult(np.float32(c.value), np.zeros(0, np.uint32), np.zeros(0, np.uint32), np.zeros(0, np.float32))
+
+    def DTW_semiglobal_tb(self, a_values, b_values, exclude_last_element=False) -> DtwResult:
+        """DTW_semiglobal_tb (src/dtw.cpp:669-753): the cost and the path from (0, j0) to (n - 1, end_j)"""
+        a, b = _f32(a_values), _f32(b_values)
+        cap = len(a) + len(b) - 1
+        pi = np.zeros(max(cap, 1), np.uint32)
+        pj = np.zeros(max(cap, 1), np.uint32)
+        pd = np.zeros(max(cap, 1), np.float32)
+        c = C.c_float()
+        ln = C.c_uint32()
+        self._check(self.lib.rawdtw_dtw_semiglobal_tb(self._ctx, _ptr(a), len(a), _ptr(b), len(b), int(exclude_last_element), C.byref(c),
+                                                      C.byref(ln), _ptr(pi), _ptr(pj), _ptr(pd)))
+        k = ln.value
+        return DtwResult(np.float32(c.value), pi[:k].copy(), pj[:k].copy(), pd[:k].copy())
+
+    def semiglobal_batch(self, jobs, events=None):
+        """rawdtw_semiglobal_batch -> (cost, end_j), one of each a job (band_radius must be -1).  events None: the jobs' read_off index
+        the context's event arena as it lies; else the arena is replaced by `events` first."""
+        jobs = np.ascontiguousarray(jobs, dtype=JOB_DTYPE)
+        ev = None if events is None else _f32(events)
+        cost = np.empty(len(jobs), np.float32)
+        end_j = np.zeros(len(jobs), np.uint32)
+        self._check(self.lib.rawdtw_semiglobal_batch(self._ctx, _ptr(jobs), len(jobs), None if ev is None else _ptr(ev),
+                                                     0 if ev is None else len(ev), _ptr(cost), _ptr(end_j)))
+        return cost, end_j
+
+    def semiglobal_traceback(self, jobs, events=None):
+        """rawdtw_semiglobal_traceback_steps -> (cost, j0, path_off, path_len, step, distance): job k's path is the path_len[k] elements
+        from path_off[k] on, start first -- element 0 is (0, j0[k]) with step byte 0, then one byte an element (bit 0: i advanced,
+        bit 1: j advanced) -- and one distance an element.  `expand_steps` turns a path into (i, j).  events: as semiglobal_batch."""
+        jobs = np.ascontiguousarray(jobs, dtype=JOB_DTYPE)
+        ev = None if events is None else _f32(events)
+        caps = jobs["n"].astype(np.uint64) + jobs["m"].astype(np.uint64) - 1
+        off = np.zeros(len(jobs) + 1, np.uint64)
+        np.cumsum(caps, out=off[1:])
+        total = int(off[-1])
+        cost = np.empty(len(jobs), np.float32)
+        j0 = np.zeros(len(jobs), np.uint32)
+        plen = np.zeros(len(jobs), np.uint32)
+        step = np.zeros(max(total, 1), np.uint8)
+        pd = np.zeros(max(total, 1), np.float32)
+        self._check(self.lib.rawdtw_semiglobal_traceback_steps(self._ctx, _ptr(jobs), len(jobs), None if ev is None else _ptr(ev),
+                                                               0 if ev is None else len(ev), _ptr(cost), _ptr(j0), _ptr(off), _ptr(plen),
+                                                               _ptr(step), _ptr(pd)))
+        return cost, j0, off, plen, step, pd
+
+    def semiglobal_timing(self) -> dict:
+        """device time of the context's most recent semiglobal call: its fill kernels, its walk and finish kernels (0 without paths)"""
+        f, w, d, e = C.c_float(), C.c_float(), C.c_uint64(), C.c_uint64()
+        self._check(self.lib.rawdtw_semiglobal_timing(self._ctx, C.byref(f), C.byref(w), C.byref(d), C.byref(e)))
+        return {"fill_ms": f.value, "walk_ms": w.value, "direction_bytes": d.value, "path_elements": e.value}
+
+
+def expand_steps(step, j0: int = 0):
+    """a path's step bytes (bit 0: i advanced, bit 1: j advanced; element 0's byte is 0) -> (i, j), starting at (0, j0)"""
+    s = np.asarray(step, np.uint8)
+    i = np.cumsum(s & 1, dtype=np.uint64).astype(np.uint32)
+    j = (np.cumsum(s >> 1, dtype=np.uint64) + np.uint64(j0)).astype(np.uint32)
+    return i, j
+
+
+def semiglobal_host(a_values, b_values, exclude_last_element=False, traceback=False):
+    """rawdtw_semiglobal_host / rawdtw_semiglobal_tb_host: the recurrence restated on the host, no device.  -> (cost, end_j), with
+    traceback (DtwResult, end_j)."""
+    lib = load_library()
+    a, b = _f32(a_values), _f32(b_values)
+    c, ej = C.c_float(), C.c_uint32()
+    if not traceback:
+        st = lib.rawdtw_semiglobal_host(_ptr(a), len(a), _ptr(b), len(b), int(exclude_last_element), C.byref(c), C.byref(ej))
+        if st != 0:
+            raise RawDTWError(st, "rawdtw_semiglobal_host refused its arguments")
+        return np.float32(c.value), ej.value
+    cap = max(len(a) + len(b) - 1, 1)
+    pi, pj, pd = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.float32)
+    ln = C.c_uint32()
+    st = lib.rawdtw_semiglobal_tb_host(_ptr(a), len(a), _ptr(b), len(b), int(exclude_last_element), C.byref(c), C.byref(ej), C.byref(ln),
+                                       _ptr(pi), _ptr(pj), _ptr(pd))
+    if st != 0:
+        raise RawDTWError(st, "rawdtw_semiglobal_tb_host refused its arguments")
+    k = ln.value
+    return DtwResult(np.float32(c.value), pi[:k].copy(), pj[:k].copy(), pd[:k].copy()), ej.value
