@@ -354,6 +354,43 @@ int rawdtw_semiglobal_host(const float *a, uint32_t n, const float *b, uint32_t 
 int rawdtw_semiglobal_tb_host(const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, float *cost, uint32_t *end_j,
                               uint32_t *path_len, uint32_t *path_i, uint32_t *path_j, float *path_d);
 
+/* ---- banded traceback: the path of a banded global job.  The reference has none (rmap.cpp:223-225 is assert(false)); this is the
+ * one definition that agrees with both reference functions it sits between.  For a job (a, n, b, m, R), R = band_radius >= 0, i
+ * indexing a and j indexing b, also when n < m and the reference swaps the two:
+ *   cell set S(n, m, R)  the cells DTW_global_slantedbanded_antidiagonalwise evaluates (dtw.cpp:273-520).
+ *   matrix   B(0, 0) = d(0, 0); every other cell of S is min(min(B(i-1, j), B(i, j-1)), B(i-1, j-1)) + d(i, j) in fp32,
+ *            d = |a[i] - b[j]|; a neighbour outside the matrix or outside S is read as float(1e10).  These are the values of the
+ *            reference's three rotating buffers.
+ *   cost     B(n-1, m-1): the reference's banded cost, bit for bit.
+ *   walk     from (n-1, m-1) until (0, 0), by dtw.cpp:625-647 with absent neighbours read as 1e10: if i == 0, j--; else if j == 0,
+ *            i--; else with L = B(i-1, j), T = B(i, j-1), X = B(i-1, j-1): L < min(T, X) moves i--; else T < min(L, X) moves j--;
+ *            else both (the reference's quirk included: L == T < X steps diagonally).  With a band that holds the whole matrix
+ *            (R = n + m) cost and path are DTW_global_tb's, below 1e10.
+ *   no path  a step that lands on a cell outside S: path_len = 0, nothing is written to the job's path stretch, the cost is still
+ *            written.  It happens only where sums reach 1e10 (a smallest case: a = [0, 0, 0], b = [0, 3e10, 0], R = 1); it is no error status.
+ *   exclude_last  as DTW_global_tb: the last element is dropped and the cost reduced by its distance.
+ *
+ *   rawdtw_banded_traceback_steps   the step form and path room (n + m - 1 a job) of rawdtw_traceback_batch_steps.  h_events == NULL:
+ *        the jobs' read_off index the event arena as it lies; else the arena is replaced by h_events first.  Sub-batches under
+ *        "tb_workspace_mb" by the jobs' direction bytes ("tb_sub_batches" says how many).  Refused before anything is enqueued, the
+ *        out arrays untouched: RAWDTW_ERR_INVALID for n == 0, m == 0, band_radius < 0 (RAWDTW_FULL included: rawdtw_traceback_batch*
+ *        serves it), a null argument, a missing arena; RAWDTW_ERR_RANGE for a window outside the arenas; RAWDTW_ERR_UNSUPPORTED for
+ *        a slant-corrected radius + 1 above 13 000 slots (the planner's limit and wording).  n_jobs == 0 is RAWDTW_OK.
+ *   rawdtw_banded_traceback_timing  device time of the most recent such call: the fill kernel, the walk and finish kernels; the
+ *        direction bytes its jobs took and the path elements that came home.
+ *   rawdtw_dtw_global_banded_tb     the single-call drop-in (host pointers; convenient, not fast), arrays as rawdtw_dtw_global_tb.
+ *   rawdtw_banded_tb_host           the definition restated on the host, O((n + m) K) memory, no device: the tests' yardstick where a
+ *        shape is too large for a matrix.  RAWDTW_ERR_INVALID for a null argument, a zero length or a negative radius,
+ *        RAWDTW_ERR_UNSUPPORTED above the device entry's 13 000 slots, RAWDTW_ERR_OOM where its memory cannot be had. ---- */
+int rawdtw_banded_traceback_steps(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events, uint64_t n_events,
+                                  float *out_cost, const uint64_t *path_off, uint32_t *path_len, uint8_t *path_step, float *path_d);
+int rawdtw_banded_traceback_timing(const rawdtw_ctx *ctx, float *fill_ms, float *walk_ms, uint64_t *direction_bytes,
+                                   uint64_t *path_elements);
+int rawdtw_dtw_global_banded_tb(rawdtw_ctx *ctx, const float *a, uint32_t n, const float *b, uint32_t m, int band_radius,
+                                int exclude_last, float *cost, uint32_t *path_len, uint32_t *path_i, uint32_t *path_j, float *path_d);
+int rawdtw_banded_tb_host(const float *a, uint32_t n, const float *b, uint32_t m, int band_radius, int exclude_last, float *cost,
+                          uint32_t *path_len, uint32_t *path_i, uint32_t *path_j, float *path_d);
+
 /* ---- host-side mirror of align_chain / the DTW block of gen_chains
  * (src/rmap.cpp:181-313, 509-530): job decomposition and exact replay.  Pure
  * host code, no device work. ---- */
@@ -894,6 +931,13 @@ int rawdtw_mapper_round(rawdtw_mapper *m, uint32_t n_reads, const uint32_t *read
  * copy into the mapper's own staging.) */
 int rawdtw_mapper_read_state(const rawdtw_mapper *m, uint32_t read_id, int *finished, uint32_t *chunks_done);
 int rawdtw_mapper_finish(rawdtw_mapper *m);
+/* --dtw-output-cigar at the reference's default fill.  Off (the default): rawdtw_mapper_finish of a global + banded mapper with flag
+ * 0x4 fails with RAWDTW_ERR_UNSUPPORTED as the reference asserts (rmap.cpp:223-225).  On: it takes every mapped read's best chain
+ * through rawdtw_banded_traceback_steps ("banded traceback" above) -- the job rawdtw_chain_build_jobs(..., cigar = 0) builds, radius
+ * max(1, (int)(n * frac)); from the host's events or, under "signal_cigar", from the arena -- and writes alns:f: from that cost and
+ * aln:s: with the global mode's quirk as the full-matrix branch does; a job without a path gives an empty aln:s:.  Sparse and
+ * full-matrix mappers are untouched by it.  A setter, not a context option: the option table stays as recorded. */
+int rawdtw_mapper_set_banded_cigar(rawdtw_mapper *m, int on);
 /* *len = the line's length; RAWDTW_ERR_RANGE when buf (cap bytes) is too small for it and its terminator.  With flag 0x20 a
  * mapped line ends in anchors:s: (rmap.cpp:745-747).  A read sequence-until dropped has no line: *len = 0, "". */
 int rawdtw_mapper_paf(const rawdtw_mapper *m, uint32_t read_id, char *buf, uint32_t cap, uint32_t *len);

@@ -99,6 +99,8 @@ struct rawdtw_ctx : rawdtw::Options { // (every option is a field of Options: ra
     uint64_t tb_sub_batches = 0;  // "tb_sub_batches" (read-only): sub-batches of the most recent traceback call, known before its first plan is built
     float semi_fill_ms = 0.f, semi_walk_ms = 0.f;      // device time of the most recent semiglobal call (rawdtw_semiglobal.cpp)
     uint64_t semi_dir_written = 0, semi_path_elems = 0;
+    float band_tb_fill_ms = 0.f, band_tb_walk_ms = 0.f; // device time of the most recent banded traceback call (rawdtw_band_tb.cpp)
+    uint64_t band_tb_dir_written = 0, band_tb_path_elems = 0;
     // reference arena.  An arena the library allocated (rawdtw_upload_reference, rawdtw_index_upload) is held through a
     // counted RefHold, shared by every context that adopted it with rawdtw_share_reference: it is freed when the last of
     // them lets go, so the owner may upload another reference or be destroyed while sharers still run on the old one.
@@ -432,6 +434,73 @@ template <typename T> int dev_alloc(rawdtw_ctx *ctx, T **p, uint64_t count)
     if (count == 0) return RAWDTW_OK;
     HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(p), count * sizeof(T)));
     return RAWDTW_OK;
+}
+
+// ---- what the call-scoped units (rawdtw_semiglobal.cpp, rawdtw_band_tb.cpp) share ----
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// a device block that goes when the call ends (behind the context's stream); `what` names the unit in the failure's message
+struct DevBlock {
+    rawdtw_ctx *ctx; const char *what; char *p = nullptr;
+    DevBlock(rawdtw_ctx *c, const char *w) : ctx(c), what(w) {}
+    DevBlock(const DevBlock &) = delete;
+    DevBlock &operator=(const DevBlock &) = delete;
+    ~DevBlock() { if (p) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(p); } }
+    int reserve(size_t bytes)
+    {
+        if (hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(bytes, 256)) != hipSuccess) {
+            p = nullptr; (void)hipGetLastError();
+            return fail(ctx, RAWDTW_ERR_OOM, std::string(what) + " workspace allocation failed");
+        }
+        return RAWDTW_OK;
+    }
+};
+// the events around a call's fill and walk launches
+struct EventPair {
+    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    EventPair() = default;
+    EventPair(const EventPair &) = delete;
+    EventPair &operator=(const EventPair &) = delete;
+    ~EventPair() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
+// b goes to a private reference arena for the duration of a single call (the hold on the context's own arena stays)
+struct PrivateRef {
+    rawdtw_ctx *ctx; float *saved; uint64_t saved_n; float *d_b = nullptr;
+    explicit PrivateRef(rawdtw_ctx *c) : ctx(c), saved(c->d_ref), saved_n(c->n_ref) {}
+    PrivateRef(const PrivateRef &) = delete;
+    PrivateRef &operator=(const PrivateRef &) = delete;
+    int put(const float *b, uint32_t m)
+    {
+        int st = dev_alloc(ctx, &d_b, ((uint64_t)m + 3) & ~3ull);
+        if (st != RAWDTW_OK) return st;
+        hipError_t e = hipMemcpyAsync(d_b, b, (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) return hip_fail(ctx, e, "operand upload");
+        ctx->d_ref = d_b; ctx->n_ref = m;
+        return RAWDTW_OK;
+    }
+    ~PrivateRef()
+    {
+        ctx->d_ref = saved; ctx->n_ref = saved_n;
+        if (d_b) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(d_b); }
+    }
+};
+// the context's direction workspace, grow-only (one traceback at a time per context)
+inline int ensure_tb_dir(rawdtw_ctx *ctx, uint64_t need)
+{
+    if (ctx->tb_dir_bytes >= need) return RAWDTW_OK;
+    if (ctx->d_tb_dir) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->d_tb_dir); }
+    ctx->d_tb_dir = nullptr; ctx->tb_dir_bytes = 0;
+    const uint64_t want = need + need / 8;
+    if (int st = dev_alloc(ctx, &ctx->d_tb_dir, want)) return st;
+    ctx->tb_dir_bytes = want;
+    return RAWDTW_OK;
+}
+// "tb_workspace_mb" (the option goes before the variable RAWDTW_TB_WORKSPACE_MB) in bytes
+inline uint64_t tb_budget_bytes(const rawdtw_ctx *ctx)
+{
+    if (ctx->tb_workspace_mb) return ctx->tb_workspace_mb << 20;
+    if (const char *e = getenv("RAWDTW_TB_WORKSPACE_MB")) return std::max<uint64_t>(1, strtoull(e, nullptr, 10)) << 20;
+    return 16ull << 30;
 }
 
 inline int ensure_events_capacity(rawdtw_ctx *ctx, uint64_t n)

@@ -15,6 +15,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <new>
 #include <tuple>
 #include <utility>
 #include <vector>
@@ -678,4 +679,110 @@ extern "C" int rawdtw_semiglobal_tb_host(const float *a, uint32_t n, const float
 {
     if (!path_len) return RAWDTW_ERR_INVALID;
     return semiglobal_host(a, n, b, m, exclude_last, cost, end_j, path_len, path_i, path_j, path_d);
+}
+
+// ---- the banded global traceback restated (include/rawdtw.h, "banded traceback"): the three rotating antidiagonals of
+// DTW_global_slantedbanded_antidiagonalwise (dtw.cpp:273-520) with every slot that is no evaluated cell written as 1e10, one direction
+// byte a slot decided by the walk's rule (dtw.cpp:633-646) while the cell's three neighbours are at hand, and per antidiagonal sum
+// s = I + J where its slots lie; then DTW_global_tb's walk (dtw.cpp:625-647).  O((n + m) K) memory, K = slanted radius + 1.
+namespace { constexpr int64_t kBandedTbHostMaxK = 13000; } // kMaxWaveBandK (rawdtw_internal.h): slant-corrected radius + 1
+extern "C" int rawdtw_banded_tb_host(const float *a, uint32_t n, const float *b, uint32_t m, int band_radius, int exclude_last, float *cost,
+                                     uint32_t *path_len, uint32_t *path_i, uint32_t *path_j, float *path_d)
+{
+    if (!a || !b || !cost || !path_len || !path_i || !path_j || !path_d || n == 0 || m == 0 || band_radius < 0) return RAWDTW_ERR_INVALID;
+    const float inf = 1e10f;
+    auto dist = [](float x, float y) { return std::fabs(x - y); };
+    const bool swapped = n < m; // dtw.cpp:284-292: A is the longer one; the directions stay in the caller's i (a) and j (b)
+    const float *A = swapped ? b : a, *B = swapped ? a : b;
+    const uint32_t N = swapped ? m : n, M = swapped ? n : m;
+    const uint32_t extra = ((N - M) * (uint32_t)band_radius + N - 1u) / N; // dtw.cpp:298, unsigned 32-bit
+    const int64_t R64 = (int64_t)band_radius + (int64_t)extra;
+    if (R64 + 1 > kBandedTbHostMaxK) return RAWDTW_ERR_UNSUPPORTED; // (the device entry's limit: no wider band has a device answer to hold)
+    const int R = (int)R64;
+    const int P = R + ((R % 2 == 0) ? 1 : 0), S = R + ((R % 2 == 1) ? 1 : 0);
+    const int K = P > S ? P : S, SH = P > S ? 0 : 1;
+    struct Rec { int si, sj, lo, hi; }; // slot x of antidiagonal s is the cell (si - x, sj + x); evaluated iff lo <= x < hi
+    const uint64_t n_s = (uint64_t)N + M - 1;
+    std::vector<Rec> recs;
+    std::vector<uint8_t> codes;
+    std::vector<float> store;
+    std::vector<uint32_t> ri, rj;
+    try { // (no exception crosses the C boundary)
+        recs.resize(n_s); codes.assign(n_s * (uint64_t)K, 0); store.assign((size_t)3 * K, inf); ri.reserve(n_s); rj.reserve(n_s);
+    } catch (const std::bad_alloc &) { return RAWDTW_ERR_OOM; }
+    float *d0 = store.data(), *d1 = d0 + K, *d2 = d0 + 2 * K;
+    const int centre = P / 2 + SH;
+    d1[centre] = dist(A[0], B[0]); // column 0: the corner alone (dtw.cpp:317-347)
+    recs[0] = Rec{centre, -centre, centre, centre + 1};
+    int row = 0, prev_adv = 0;
+    for (uint32_t col = 1; col < N; col++) {
+        const int adv = ((int64_t)(row + 1) * (int64_t)N) <= ((int64_t)M * (int64_t)col); // dtw.cpp:352-359
+        if (adv) row++;
+        for (int pass = adv ? 0 : 1; pass < 2; pass++) {
+            const int len = pass == 0 ? S : P;
+            const int si = pass == 0 ? (int)col + S / 2 - 1 : (int)col + P / 2;
+            const int sj = pass == 0 ? row - S / 2 : row - P / 2;
+            int lo = 0, hi = len;
+            if (si - (int)N + 1 > lo) lo = si - (int)N + 1;
+            if (-sj > lo) lo = -sj;
+            if (si + 1 < hi) hi = si + 1;
+            if ((int)M - sj < hi) hi = (int)M - sj;
+            int dt, dtl, dl, ds, g_top_first, g_tl_first, g_left_last; // the antidiagonal kind's neighbour rule (dtw.cpp:368-485)
+            if (SH == 0) {
+                if (pass == 0) { dt = 0; dtl = 0; dl = 1; ds = 0; g_top_first = 0; g_tl_first = 0; g_left_last = 0; }
+                else if (adv)  { dt = -1; dtl = 0; dl = 0; ds = 0; g_top_first = 1; g_tl_first = 0; g_left_last = 1; }
+                else           { dt = -1; dtl = -1; dl = 0; ds = 0; g_top_first = 1; g_tl_first = 1; g_left_last = 0; }
+            } else {
+                if (pass == 0) { dt = 0; dtl = 0; dl = 1; ds = 0; g_top_first = 1; g_tl_first = !prev_adv; g_left_last = 1; }
+                else if (adv)  { dt = 0; dtl = 1; dl = 1; ds = 1; g_top_first = 0; g_tl_first = 0; g_left_last = 0; }
+                else           { dt = 0; dtl = 0; dl = 1; ds = 1; g_top_first = 1; g_tl_first = !prev_adv; g_left_last = 0; }
+            }
+            const uint64_t s = (uint64_t)(si + sj);
+            recs[s] = Rec{si + ds, sj - ds, lo + ds, hi + ds};
+            uint8_t *crow = codes.data() + s * (uint64_t)K;
+            for (int x = 0; x < K; x++) {
+                const int o = x - ds;
+                float v = inf;
+                if (o >= lo && o < hi) {
+                    const bool first = o == 0, last = o == len - 1;
+                    const float top = (g_top_first && first) ? inf : d1[o + dt];  // (I, J - 1)
+                    const float tl = (g_tl_first && first) ? inf : d0[o + dtl];   // (I - 1, J - 1)
+                    const float left = (g_left_last && last) ? inf : d1[o + dl];  // (I - 1, J)
+                    v = std::min(std::min(top, left), tl) + dist(A[si - o], B[sj + o]);
+                    const float L = swapped ? top : left, T = swapped ? left : top; // L = (i - 1, j), T = (i, j - 1)
+                    crow[x] = L < std::min(T, tl) ? 1 : T < std::min(L, tl) ? 2 : 0;
+                }
+                d2[x] = v;
+            }
+            float *t = d0; d0 = d1; d1 = d2; d2 = t;
+        }
+        prev_adv = adv;
+    }
+    const float total = d1[centre]; // dtw.cpp:506-512
+    *cost = exclude_last ? total - dist(A[N - 1], B[M - 1]) : total;
+    uint32_t i = n - 1, j = m - 1;
+    for (;;) {
+        const int I = (int)(swapped ? j : i);
+        const uint64_t s = (uint64_t)i + j;
+        const Rec &rc = recs[s];
+        const int x = rc.si - I;
+        if (x < rc.lo || x >= rc.hi) { *path_len = 0; return RAWDTW_OK; } // the walk left the cell set: no path
+        ri.push_back(i); rj.push_back(j);
+        if (i == 0 && j == 0) break;
+        if (i == 0) j--;
+        else if (j == 0) i--;
+        else {
+            const uint8_t c = codes[s * (uint64_t)K + (uint64_t)x];
+            if (c == 1) i--;
+            else if (c == 2) j--;
+            else { i--; j--; }
+        }
+    }
+    const uint32_t len = (uint32_t)ri.size() - (exclude_last ? 1u : 0u); // start first; the last element is popped (dtw.cpp:659-663)
+    for (uint32_t q = 0; q < len; q++) {
+        path_i[q] = ri[ri.size() - 1 - q]; path_j[q] = rj[ri.size() - 1 - q];
+        path_d[q] = dist(a[path_i[q]], b[path_j[q]]);
+    }
+    *path_len = len;
+    return RAWDTW_OK;
 }

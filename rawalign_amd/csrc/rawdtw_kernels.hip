@@ -972,4 +972,15 @@ hipError_t launch_tb_walk_wave(const DevJob *jobs, uint64_t count, const FullAux
     return hipGetLastError();
 }
 
+// k_tb_finish alone, behind a walk of another unit (rawdtw_band_tb.hip); a job whose path_len is 0 gets nothing written
+hipError_t launch_tb_finish(const DevJob *jobs, uint64_t count, const float *ev, const float *ref, const uint64_t *path_off,
+                            const uint32_t *path_len, const uint32_t *tmp_i, const uint32_t *tmp_j, uint8_t *path_mv, float *path_d,
+                            hipStream_t s)
+{
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_tb_finish, dim3((uint32_t)count), dim3(256), 0, s, jobs, (uint32_t)count, ev, ref, path_off, path_len, tmp_i, tmp_j,
+                       path_mv, path_d);
+    return hipGetLastError();
+}
+
 } // namespace rawdtw

@@ -278,6 +278,18 @@ int rawdtw_mapper_resident_stats(const rawdtw_mapper *m, uint64_t *resident_roun
     return RAWDTW_OK;
 }
 
+// The banded path of a global + banded --dtw-output-cigar mapper (include/rawdtw.h, "banded traceback"; the reference stops at
+// rmap.cpp:223-225).  Off by default: the refusal, its status and its wording stay.  Sparse mappers are untouched by it
+// (rmap.cpp:283-284 always calls DTW_global_tb).  It is NOT faster than switching the run to the full matrix: on 1 024 windows of
+// 3 000 x 3 000 at radius 300 the banded call took 1.7 times the full-matrix call ("Banded traceback", Speed); what it
+// saves is workspace, a quarter of the direction bytes.
+int rawdtw_mapper_set_banded_cigar(rawdtw_mapper *m, int on)
+{
+    if (!m) return RAWDTW_ERR_INVALID;
+    m->banded_cigar = on != 0;
+    return RAWDTW_OK;
+}
+
 // --dtw-output-cigar (rmap.cpp:715-717): the best chain of every mapped read through DTW_global_tb once more, its path as the
 // aln:s: string with the reference's two quirks (rmap.cpp:230-233, 283-289).  All reads' jobs go to the device in ONE call;
 // the paths come back as steps and distances (rawdtw_traceback_batch_steps: 5 bytes an element) and every read's string is
@@ -291,6 +303,8 @@ int rawdtw_mapper_finish(rawdtw_mapper *m)
     // signal has been committed ("signal_cigar": no host copy of its chunks exists), where every round of a context mapper put them: the read's slot
     // of the arena, which the traceback then reads as it lies.  The event base of a read's jobs and the traceback entry are all that differs.
     const bool arena = m->finish_from_arena;
+    // the banded path (rawdtw_mapper_set_banded_cigar): the job the scoring built (radius max(1, (int)(n * frac))), walked as well
+    const bool banded = m->banded_cigar && m->opt.align.border_constraint == 0 && m->opt.align.fill_method != 0;
     if (arena)
         for (const MRead &rd : m->reads)
             if (rd.host_only && !rd.released && !rd.dropped && high_confidence(m, rd.chains))
@@ -312,7 +326,7 @@ int rawdtw_mapper_finish(rawdtw_mapper *m)
         const uint64_t j0 = jobs.size();
         jobs.resize(j0 + std::max<uint32_t>(nj, 1));
         const uint64_t rb = m->ref_off[ch.ref * 2u + (uint32_t)ch.strand];
-        const int st = rawdtw_chain_build_jobs(&m->opt.align, ch.anchors.data(), na, rb, ev_base, 1, jobs.data() + j0);
+        const int st = rawdtw_chain_build_jobs(&m->opt.align, ch.anchors.data(), na, rb, ev_base, banded ? 0 : 1, jobs.data() + j0);
         if (st != RAWDTW_OK) return fail(m, st, st == RAWDTW_ERR_UNSUPPORTED ? "banded global alignment with --dtw-output-cigar is not implemented (rmap.cpp:223-225)" : "job building failed");
         jobs.resize(j0 + nj);
         items.push_back(Item{r, j0, nj, ev_base});
@@ -327,7 +341,9 @@ int rawdtw_mapper_finish(rawdtw_mapper *m)
     std::vector<float> pd(poff[nj_all] + 1), cost(nj_all);
     if (nj_all) {
         if (!arena) m->arena_replaced = true;
-        const int st = arena ? rawdtw_traceback_arena_steps(m->ctx, jobs.data(), nj_all, cost.data(), poff.data(), plen.data(), step.data(), pd.data())
+        const int st = banded ? rawdtw_banded_traceback_steps(m->ctx, jobs.data(), nj_all, arena ? nullptr : events.data(), events.size(), cost.data(),
+                                                              poff.data(), plen.data(), step.data(), pd.data())
+                       : arena ? rawdtw_traceback_arena_steps(m->ctx, jobs.data(), nj_all, cost.data(), poff.data(), plen.data(), step.data(), pd.data())
                              : rawdtw_traceback_batch_steps(m->ctx, jobs.data(), nj_all, events.data(), events.size(), cost.data(), poff.data(), plen.data(), step.data(), pd.data());
         if (st != RAWDTW_OK) return fail(m, st, rawdtw_last_error(m->ctx));
     }

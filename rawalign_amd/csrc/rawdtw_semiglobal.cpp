@@ -53,27 +53,6 @@ void semi_plan(const rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t cnt, bo
     }
 }
 
-// a device block that goes when the call ends (behind the context's stream)
-struct DevBlock {
-    rawdtw_ctx *ctx; char *p = nullptr;
-    explicit DevBlock(rawdtw_ctx *c) : ctx(c) {}
-    ~DevBlock() { if (p) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(p); } }
-    int reserve(size_t bytes)
-    {
-        if (hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(bytes, 256)) != hipSuccess) {
-            p = nullptr; (void)hipGetLastError();
-            return fail(ctx, RAWDTW_ERR_OOM, "semiglobal workspace allocation failed");
-        }
-        return RAWDTW_OK;
-    }
-};
-struct EventPair {
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    ~EventPair() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
-
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // Every refusal, before anything is enqueued: INVALID for a zero length or a banded job, RANGE for a window outside the arenas.
 int semi_check(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, bool arena, uint64_t n_events)
 {
@@ -120,7 +99,7 @@ int semi_batch(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const
     if (!arena && (st = rawdtw_upload_events(ctx, h_events, n_events)) != RAWDTW_OK) return st;
     SemiPlan pl;
     semi_plan(ctx, jobs, n_jobs, false, pl);
-    DevBlock blk(ctx);
+    DevBlock blk(ctx, "semiglobal");
     const size_t need = al256(n_jobs * sizeof(DevJob)) + al256(n_jobs * sizeof(FullAux)) + 2 * al256(n_jobs * 4) + al256(pl.bnd_floats * 4);
     if ((st = blk.reserve(need)) != RAWDTW_OK) return st;
     char *p = blk.p;
@@ -160,9 +139,7 @@ int semi_traceback(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, c
     if (st != RAWDTW_OK) return st;
     if (!arena && (st = rawdtw_upload_events(ctx, h_events, n_events)) != RAWDTW_OK) return st;
 
-    uint64_t budget = 16ull << 30;
-    if (ctx->tb_workspace_mb) budget = ctx->tb_workspace_mb << 20; // (the option goes before the variable)
-    else if (const char *e = getenv("RAWDTW_TB_WORKSPACE_MB")) budget = std::max<uint64_t>(1, strtoull(e, nullptr, 10)) << 20;
+    const uint64_t budget = tb_budget_bytes(ctx);
     // the split: a job joins the current sub-batch unless that passes the budget (a job over the budget goes alone)
     struct Sub { uint64_t begin, cnt, acc; SemiPlan pl; };
     std::vector<Sub> subs;
@@ -192,14 +169,8 @@ int semi_traceback(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, c
         dev_need = std::max(dev_need, need); dir_need = std::max(dir_need, sb.pl.dir_bytes);
         acc_max = std::max(acc_max, sb.acc); cnt_max = std::max(cnt_max, sb.cnt);
     }
-    if (ctx->tb_dir_bytes < dir_need) { // the context's direction workspace, grow-only (one traceback at a time per context)
-        if (ctx->d_tb_dir) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->d_tb_dir); }
-        ctx->d_tb_dir = nullptr; ctx->tb_dir_bytes = 0;
-        const uint64_t want = dir_need + dir_need / 8;
-        if ((st = dev_alloc(ctx, &ctx->d_tb_dir, want)) != RAWDTW_OK) return st;
-        ctx->tb_dir_bytes = want;
-    }
-    DevBlock blk(ctx);
+    if ((st = ensure_tb_dir(ctx, dir_need)) != RAWDTW_OK) return st;
+    DevBlock blk(ctx, "semiglobal");
     if ((st = blk.reserve(dev_need)) != RAWDTW_OK) return st;
     EventPair ev;
     for (hipEvent_t &e : ev.e) HIP_TRY(ctx, hipEventCreate(&e));
@@ -263,26 +234,6 @@ int semi_traceback(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, c
     }
     return RAWDTW_OK;
 }
-
-// b goes to a private reference arena for the duration of a single call (the hold on the context's own arena stays)
-struct PrivateRef {
-    rawdtw_ctx *ctx; float *saved; uint64_t saved_n; float *d_b = nullptr;
-    explicit PrivateRef(rawdtw_ctx *c) : ctx(c), saved(c->d_ref), saved_n(c->n_ref) {}
-    int put(const float *b, uint32_t m)
-    {
-        int st = dev_alloc(ctx, &d_b, ((uint64_t)m + 3) & ~3ull);
-        if (st != RAWDTW_OK) return st;
-        hipError_t e = hipMemcpyAsync(d_b, b, (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) return hip_fail(ctx, e, "operand upload");
-        ctx->d_ref = d_b; ctx->n_ref = m;
-        return RAWDTW_OK;
-    }
-    ~PrivateRef()
-    {
-        ctx->d_ref = saved; ctx->n_ref = saved_n;
-        if (d_b) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(d_b); }
-    }
-};
 
 } // namespace
 

@@ -797,6 +797,54 @@ class Engine:
         self._check(self.lib.rawdtw_semiglobal_timing(self._ctx, C.byref(f), C.byref(w), C.byref(d), C.byref(e)))
         return {"fill_ms": f.value, "walk_ms": w.value, "direction_bytes": d.value, "path_elements": e.value}
 
+    def DTW_global_banded_tb(self, a_values, b_values, band_radius, exclude_last=False) -> DtwResult:
+        """The banded cost of DTW_global_slantedbanded_antidiagonalwise and the path DTW_global_tb's walk takes through the band's cells
+        (include/rawdtw.h, "banded traceback"); a job without a path has empty i, j and difference"""
+        a, b = _f32(a_values), _f32(b_values)
+        cap = len(a) + len(b) - 1
+        pi = np.zeros(max(cap, 1), np.uint32)
+        pj = np.zeros(max(cap, 1), np.uint32)
+        pd = np.zeros(max(cap, 1), np.float32)
+        c = C.c_float()
+        ln = C.c_uint32()
+        self._check(self.lib.rawdtw_dtw_global_banded_tb(self._ctx, _ptr(a), len(a), _ptr(b), len(b), int(band_radius), int(exclude_last),
+                                                         C.byref(c), C.byref(ln), _ptr(pi), _ptr(pj), _ptr(pd)))
+        k = ln.value
+        return DtwResult(np.float32(c.value), pi[:k].copy(), pj[:k].copy(), pd[:k].copy())
+
+    def banded_traceback(self, jobs, events=None, path_off=None, out=None):
+        """rawdtw_banded_traceback_steps -> (cost, path_off, path_len, step, distance): job k's path is the path_len[k] elements from
+        path_off[k] on, start first at (0, 0), one step byte (bit 0: i advanced, bit 1: j advanced) and one distance an element;
+        path_len 0: the job has no path.  events None: the jobs' read_off index the event arena as it lies.  path_off: the caller's
+        layout (n + m - 1 elements of room a job), default dense in job order.  out: (cost, path_len, step, distance) to write into."""
+        jobs = np.ascontiguousarray(jobs, dtype=JOB_DTYPE)
+        ev = None if events is None else _f32(events)
+        caps = jobs["n"].astype(np.uint64) + jobs["m"].astype(np.uint64) - 1
+        if path_off is None:
+            off = np.zeros(len(jobs) + 1, np.uint64)
+            np.cumsum(caps, out=off[1:])
+            total = int(off[-1])
+        else:
+            off = np.ascontiguousarray(path_off, np.uint64)
+            if len(off) < len(jobs):
+                raise ValueError("path_off is shorter than the job list")
+            total = int((off[:len(jobs)] + caps).max()) if len(jobs) else 0
+        if out is None:
+            cost, plen = np.empty(len(jobs), np.float32), np.zeros(len(jobs), np.uint32)
+            step, pd = np.zeros(max(total, 1), np.uint8), np.zeros(max(total, 1), np.float32)
+        else:
+            cost, plen, step, pd = out
+        self._check(self.lib.rawdtw_banded_traceback_steps(self._ctx, _ptr(jobs), len(jobs), None if ev is None else _ptr(ev),
+                                                           0 if ev is None else len(ev), _ptr(cost), _ptr(off), _ptr(plen), _ptr(step),
+                                                           _ptr(pd)))
+        return cost, off, plen, step, pd
+
+    def banded_traceback_timing(self) -> dict:
+        """device time of the context's most recent banded traceback call: its fill kernel, its walk and finish kernels"""
+        f, w, d, e = C.c_float(), C.c_float(), C.c_uint64(), C.c_uint64()
+        self._check(self.lib.rawdtw_banded_traceback_timing(self._ctx, C.byref(f), C.byref(w), C.byref(d), C.byref(e)))
+        return {"fill_ms": f.value, "walk_ms": w.value, "direction_bytes": d.value, "path_elements": e.value}
+
 
 def expand_steps(step, j0: int = 0):
     """a path's step bytes (bit 0: i advanced, bit 1: j advanced; element 0's byte is 0) -> (i, j), starting at (0, j0)"""
@@ -826,3 +874,19 @@ def semiglobal_host(a_values, b_values, exclude_last_element=False, traceback=Fa
         raise RawDTWError(st, "rawdtw_semiglobal_tb_host refused its arguments")
     k = ln.value
     return DtwResult(np.float32(c.value), pi[:k].copy(), pj[:k].copy(), pd[:k].copy()), ej.value
+
+
+def banded_tb_host(a_values, b_values, band_radius, exclude_last=False) -> DtwResult:
+    """rawdtw_banded_tb_host: the banded traceback's definition (include/rawdtw.h) restated on the host, no device.  A job without a
+    path has empty i, j and difference; its cost is still the banded cost."""
+    lib = load_library()
+    a, b = _f32(a_values), _f32(b_values)
+    cap = max(len(a) + len(b) - 1, 1)
+    pi, pj, pd = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.float32)
+    c, ln = C.c_float(), C.c_uint32()
+    st = lib.rawdtw_banded_tb_host(_ptr(a), len(a), _ptr(b), len(b), int(band_radius), int(exclude_last), C.byref(c), C.byref(ln),
+                                   _ptr(pi), _ptr(pj), _ptr(pd))
+    if st != 0:
+        raise RawDTWError(st, "rawdtw_banded_tb_host refused its arguments")
+    k = ln.value
+    return DtwResult(np.float32(c.value), pi[:k].copy(), pj[:k].copy(), pd[:k].copy())
