@@ -334,12 +334,27 @@ int rawdtw_dtw_global_tb(rawdtw_ctx *ctx, const float *a, uint32_t n, const floa
  *        job from path_off[k] on, start first; per element its distance and one byte (bit 0: i advanced, bit 1: j advanced; element
  *        0 is (0, out_j0[k]), its byte is 0).  With exclude_last the last element is dropped and the cost reduced by its distance.
  *        Sub-batches under "tb_workspace_mb" ("tb_sub_batches" says how many) as the global traceback.
- *   rawdtw_semiglobal_timing           device time of the most recent of those two calls on the context: the fill kernels, and the
+ *   rawdtw_semiglobal_timing           device time of the most recent of those calls (or of a span call, below) on the context: the fill kernels, and the
  *        walk and finish kernels (0 for a cost-only call); the direction bytes written and the path elements that came home.
  *   rawdtw_dtw_semiglobal, rawdtw_dtw_semiglobal_tb   the single-call drop-ins (host pointers; convenient, not fast).  The first
  *        ignores exclude_last as its namesake does; the second writes (path_i, path_j, path_d) like rawdtw_dtw_global_tb.
  *   rawdtw_semiglobal_host, rawdtw_semiglobal_tb_host   the recurrence restated on the host (no device work): the yardstick of the
- *        tests where a shape is too large for a recorded answer.  end_j and the path arrays may be NULL. ---- */
+ *        tests where a shape is too large for a recorded answer.  end_j and the path arrays may be NULL.
+ *
+ * The span of a job is (cost, j0, end_j): both ends of the matched substring of b, without a direction matrix.  cost and end_j are
+ * exactly rawdtw_semiglobal_batch's, the exclude_last subtraction included.  j0 is the column of element 0 of the path that
+ * DTW_semiglobal_tb (dtw.cpp:669-753) returns: bit for bit out_j0 of rawdtw_semiglobal_traceback_steps; exclude_last does not change
+ * it.  Stated forwards, with S(i, j) the start column of the path that ends in (i, j):
+ *   S(0, j) = j;  S(i, 0) = 0, whatever the values (at j == 0 the walk moves up without reading a neighbour);  elsewhere, with
+ *   up = D(i-1, j), lf = D(i, j-1), dg = D(i-1, j-1):  up < min(lf, dg) -> S(i-1, j);  else lf < min(up, dg) -> S(i, j-1);  else
+ *   S(i-1, j-1) (the reference's quirk included: up == lf < dg takes the diagonal);  j0 = S(n-1, end_j).
+ * The comparisons are the walk's own, so j0 equals the traceback's on every value domain.  One pass, O(m) boundary state a job.
+ *   rawdtw_semiglobal_span_batch   cost, j0 and end_j of every job: rawdtw_semiglobal_batch's contract word for word (h_events == NULL,
+ *        the refusals and their statuses, n_jobs == 0).  No sub-batches: there is no direction workspace, "tb_sub_batches" is not
+ *        touched.  rawdtw_semiglobal_timing afterwards: the span launches as fill_ms, 0 for the walk, the bytes and the elements.
+ *   rawdtw_dtw_semiglobal_span     the single-call drop-in (host pointers; convenient, not fast).
+ *   rawdtw_semiglobal_span_host    the definition restated on the host in O(m) memory (two rows of cost and of start): the yardstick
+ *        where rawdtw_semiglobal_tb_host's n x m matrix is too large.  cost, j0 and end_j may be NULL. ---- */
 int rawdtw_semiglobal_batch(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events, uint64_t n_events,
                             float *out_cost, uint32_t *out_end_j);
 int rawdtw_semiglobal_traceback_steps(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events,
@@ -353,6 +368,12 @@ int rawdtw_dtw_semiglobal_tb(rawdtw_ctx *ctx, const float *a, uint32_t n, const 
 int rawdtw_semiglobal_host(const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, float *cost, uint32_t *end_j);
 int rawdtw_semiglobal_tb_host(const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, float *cost, uint32_t *end_j,
                               uint32_t *path_len, uint32_t *path_i, uint32_t *path_j, float *path_d);
+int rawdtw_semiglobal_span_batch(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events, uint64_t n_events,
+                                 float *out_cost, uint32_t *out_j0, uint32_t *out_end_j);
+int rawdtw_dtw_semiglobal_span(rawdtw_ctx *ctx, const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, float *cost,
+                               uint32_t *j0, uint32_t *end_j);
+int rawdtw_semiglobal_span_host(const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, float *cost, uint32_t *j0,
+                                uint32_t *end_j);
 
 /* ---- banded traceback: the path of a banded global job.  The reference has none (rmap.cpp:223-225 is assert(false)); this is the
  * one definition that agrees with both reference functions it sits between.  For a job (a, n, b, m, R), R = band_radius >= 0, i

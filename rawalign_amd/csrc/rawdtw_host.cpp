@@ -681,6 +681,36 @@ extern "C" int rawdtw_semiglobal_tb_host(const float *a, uint32_t n, const float
     return semiglobal_host(a, n, b, m, exclude_last, cost, end_j, path_len, path_i, path_j, path_d);
 }
 
+// The span (include/rawdtw.h, "span") restated forwards in O(m) memory: two rows of cost and two of S(i, j), the column in which the path
+// ending in (i, j) starts -- row 0 in its own column, column 0 at 0, elsewhere the start of the neighbour the walk steps to.
+extern "C" int rawdtw_semiglobal_span_host(const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, float *cost, uint32_t *j0,
+                                           uint32_t *end_j)
+{
+    if (!a || !b || n == 0 || m == 0) return RAWDTW_ERR_INVALID;
+    auto dist = [](float x, float y) { return std::fabs(x - y); };
+    std::vector<float> prev(m), cur(m);
+    std::vector<uint32_t> sprev(m), scur(m);
+    for (uint32_t j = 0; j < m; j++) { prev[j] = dist(a[0], b[j]); sprev[j] = j; }
+    for (uint32_t i = 1; i < n; i++) {
+        cur[0] = prev[0] + dist(a[i], b[0]);
+        scur[0] = 0;
+        for (uint32_t j = 1; j < m; j++) {
+            const float left = prev[j], top = cur[j - 1], topleft = prev[j - 1]; // the traceback's names (dtw.cpp:717-719)
+            cur[j] = std::min(std::min(left, top), topleft) + dist(a[i], b[j]);
+            scur[j] = left < std::min(top, topleft) ? sprev[j] : top < std::min(left, topleft) ? scur[j - 1] : sprev[j - 1];
+        }
+        prev.swap(cur); sprev.swap(scur);
+    }
+    float best = prev[0];
+    uint32_t best_j = 0;
+    for (uint32_t j = 1; j < m; j++)
+        if (prev[j] < best) { best = prev[j]; best_j = j; }
+    if (cost) *cost = exclude_last ? best - dist(a[n - 1], b[best_j]) : best;
+    if (j0) *j0 = sprev[best_j];
+    if (end_j) *end_j = best_j;
+    return RAWDTW_OK;
+}
+
 // ---- the banded global traceback restated (include/rawdtw.h, "banded traceback"): the three rotating antidiagonals of
 // DTW_global_slantedbanded_antidiagonalwise (dtw.cpp:273-520) with every slot that is no evaluated cell written as 1e10, one direction
 // byte a slot decided by the walk's rule (dtw.cpp:633-646) while the cell's three neighbours are at hand, and per antidiagonal sum

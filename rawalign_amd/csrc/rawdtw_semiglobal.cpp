@@ -1,5 +1,6 @@
-// rawdtw_semiglobal.cpp -- subsequence DTW behind the C ABI: rawdtw_semiglobal_batch, rawdtw_semiglobal_traceback_steps and the
-// single-call drop-ins for DTW_semiglobal / DTW_semiglobal_tb (dtw.hpp; dtw.cpp:526-593, 669-753).  Host code only: validation,
+// rawdtw_semiglobal.cpp -- subsequence DTW behind the C ABI: rawdtw_semiglobal_batch, rawdtw_semiglobal_span_batch,
+// rawdtw_semiglobal_traceback_steps and the single-call drop-ins for DTW_semiglobal / DTW_semiglobal_tb (dtw.hpp; dtw.cpp:526-593,
+// 669-753) and for the span.  Host code only: validation,
 // the jobs' classes, their launches and the traceback's sub-batches.  The job-list planner (rawdtw_planner.cpp) knows nothing of
 // these jobs: they are bucketed here, by the class rawdtw_semiglobal.h defines, longest first inside a class (a launch takes as
 // long as its longest job).  There is no CPU fallback: the kernels run or the call returns an error status.
@@ -22,7 +23,9 @@ struct SemiPlan {
     uint64_t bnd_floats = 0, dir_bytes = 0;
 };
 
-void semi_plan(const rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t cnt, bool traceback, SemiPlan &pl)
+enum class SemiForm { Cost, Traceback, Span };
+
+void semi_plan(const rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t cnt, SemiForm form, SemiPlan &pl)
 {
     struct Keyed { uint64_t key; uint32_t idx; };
     std::vector<Keyed> keyed(cnt);
@@ -43,8 +46,8 @@ void semi_plan(const rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t cnt, bo
         d.ref_off = j.ref_off; d.read_off = j.read_off; d.n = j.n; d.m = j.m; d.R = -1;
         d.flags = j.exclude_last ? kFlagExcludeLast : 0u; d.aux = k;
         pl.aux[p].bnd_off = pl.bnd_floats;
-        pl.bnd_floats += semi_bnd_floats(j.n, j.m, c);
-        if (traceback) {
+        pl.bnd_floats += form == SemiForm::Span ? semi_span_bnd_floats(j.n, j.m, c) : semi_bnd_floats(j.n, j.m, c);
+        if (form == SemiForm::Traceback) {
             pl.aux[p].dir_off = pl.dir_bytes;
             pl.dir_bytes += (semi_dir_bytes(j.n, j.m, c) + 255) & ~255ull;
         }
@@ -71,52 +74,60 @@ int semi_check(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, bool 
     return RAWDTW_OK;
 }
 
-// records up, fill launches of one plan; cost and end_j are left on the device (indexed inside the stretch)
-int semi_fill(rawdtw_ctx *ctx, const SemiPlan &pl, bool traceback, DevJob *d_jobs, FullAux *d_aux, float *d_cost, uint32_t *d_endj,
-              float *d_bnd, uint8_t *d_dir)
+// records up, fill launches of one plan; cost and end_j (the span form: and j0) are left on the device (indexed inside the stretch)
+int semi_fill(rawdtw_ctx *ctx, const SemiPlan &pl, SemiForm form, DevJob *d_jobs, FullAux *d_aux, float *d_cost, uint32_t *d_j0,
+              uint32_t *d_endj, float *d_bnd, uint8_t *d_dir)
 {
     const uint64_t cnt = pl.jobs.size();
     HIP_TRY(ctx, hipMemcpyAsync(d_jobs, pl.jobs.data(), cnt * sizeof(DevJob), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_aux, pl.aux.data(), cnt * sizeof(FullAux), hipMemcpyHostToDevice, ctx->stream));
     for (const SemiLaunch &L : pl.launches) {
-        hipError_t e = launch_semi_wave(L.cls, traceback, d_jobs + L.first, L.count, d_aux + L.first, ctx->d_ev, ctx->d_ref, d_cost,
-                                        d_endj, d_bnd, d_dir, ctx->stream);
+        hipError_t e = form == SemiForm::Span
+                           ? launch_semi_span_wave(L.cls, d_jobs + L.first, L.count, d_aux + L.first, ctx->d_ev, ctx->d_ref, d_cost, d_j0,
+                                                   d_endj, d_bnd, ctx->stream)
+                           : launch_semi_wave(L.cls, form == SemiForm::Traceback, d_jobs + L.first, L.count, d_aux + L.first, ctx->d_ev,
+                                              ctx->d_ref, d_cost, d_endj, d_bnd, d_dir, ctx->stream);
         if (e != hipSuccess) return hip_fail(ctx, e, "semiglobal fill launch");
     }
     return RAWDTW_OK;
 }
 
-int semi_batch(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events, uint64_t n_events, float *out_cost,
-               uint32_t *out_end_j)
+// the cost form (out_j0 unused) and the span form: one pass, no sub-batches, nothing but boundary rows in the workspace
+int semi_batch(rawdtw_ctx *ctx, SemiForm form, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events, uint64_t n_events,
+               float *out_cost, uint32_t *out_j0, uint32_t *out_end_j)
 {
+    const bool span = form == SemiForm::Span;
     if (!ctx) return RAWDTW_ERR_INVALID;
     if (n_jobs == 0) return RAWDTW_OK;
-    if (!jobs || !out_cost || !out_end_j) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    if (!jobs || !out_cost || !out_end_j || (span && !out_j0)) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
     if (n_jobs >= 0x7fffffffull) return fail(ctx, RAWDTW_ERR_INVALID, "too many jobs for one call");
     const bool arena = h_events == nullptr;
     int st = semi_check(ctx, jobs, n_jobs, arena, n_events);
     if (st != RAWDTW_OK) return st;
     if (!arena && (st = rawdtw_upload_events(ctx, h_events, n_events)) != RAWDTW_OK) return st;
     SemiPlan pl;
-    semi_plan(ctx, jobs, n_jobs, false, pl);
+    semi_plan(ctx, jobs, n_jobs, form, pl);
     DevBlock blk(ctx, "semiglobal");
-    const size_t need = al256(n_jobs * sizeof(DevJob)) + al256(n_jobs * sizeof(FullAux)) + 2 * al256(n_jobs * 4) + al256(pl.bnd_floats * 4);
+    const size_t need = al256(n_jobs * sizeof(DevJob)) + al256(n_jobs * sizeof(FullAux)) + (span ? 3 : 2) * al256(n_jobs * 4) +
+                        al256(pl.bnd_floats * 4);
     if ((st = blk.reserve(need)) != RAWDTW_OK) return st;
     char *p = blk.p;
     DevJob *d_jobs = carve<DevJob>(p, n_jobs);
     FullAux *d_aux = carve<FullAux>(p, n_jobs);
     float *d_cost = carve<float>(p, n_jobs);
     uint32_t *d_endj = carve<uint32_t>(p, n_jobs);
+    uint32_t *d_j0 = span ? carve<uint32_t>(p, n_jobs) : nullptr;
     float *d_bnd = carve<float>(p, pl.bnd_floats);
     EventPair ev;
     for (int k = 0; k < 2; k++) HIP_TRY(ctx, hipEventCreate(&ev.e[k]));
     ctx->semi_fill_ms = ctx->semi_walk_ms = 0.f; ctx->semi_dir_written = 0; ctx->semi_path_elems = 0;
     HIP_TRY(ctx, hipEventRecord(ev.e[0], ctx->stream));
-    if ((st = semi_fill(ctx, pl, false, d_jobs, d_aux, d_cost, d_endj, d_bnd, nullptr)) != RAWDTW_OK) return st;
+    if ((st = semi_fill(ctx, pl, form, d_jobs, d_aux, d_cost, d_j0, d_endj, d_bnd, nullptr)) != RAWDTW_OK) return st;
     HIP_TRY(ctx, hipEventRecord(ev.e[1], ctx->stream));
     // (a record's aux is the caller's job index: the results come home in job order)
     HIP_TRY(ctx, hipMemcpyAsync(out_cost, d_cost, n_jobs * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(out_end_j, d_endj, n_jobs * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (span) HIP_TRY(ctx, hipMemcpyAsync(out_j0, d_j0, n_jobs * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, ev.e[0], ev.e[1]) == hipSuccess) ctx->semi_fill_ms = ms;
@@ -161,7 +172,7 @@ int semi_traceback(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, c
     std::vector<std::vector<uint64_t>> poff(subs.size());
     for (size_t q = 0; q < subs.size(); q++) {
         Sub &sb = subs[q];
-        semi_plan(ctx, jobs + sb.begin, sb.cnt, true, sb.pl);
+        semi_plan(ctx, jobs + sb.begin, sb.cnt, SemiForm::Traceback, sb.pl);
         poff[q].resize(sb.cnt);
         for (uint64_t p = 0; p < sb.cnt; p++) { poff[q][p] = sb.acc; sb.acc += (uint64_t)sb.pl.jobs[p].n + sb.pl.jobs[p].m - 1; }
         const size_t need = al256(sb.cnt * sizeof(DevJob)) + al256(sb.cnt * sizeof(FullAux)) + 4 * al256(sb.cnt * 4) + al256(sb.cnt * 8) +
@@ -196,7 +207,7 @@ int semi_traceback(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, c
         uint8_t *d_mv = carve<uint8_t>(p, sb.acc);
         HIP_TRY(ctx, hipMemcpyAsync(d_poff, poff[q].data(), sb.cnt * 8, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipEventRecord(ev.e[0], ctx->stream));
-        if ((st = semi_fill(ctx, sb.pl, true, d_jobs, d_aux, d_cost, d_endj, d_bnd, ctx->d_tb_dir)) != RAWDTW_OK) return st;
+        if ((st = semi_fill(ctx, sb.pl, SemiForm::Traceback, d_jobs, d_aux, d_cost, nullptr, d_endj, d_bnd, ctx->d_tb_dir)) != RAWDTW_OK) return st;
         HIP_TRY(ctx, hipEventRecord(ev.e[1], ctx->stream));
         for (const SemiLaunch &L : sb.pl.launches) {
             hipError_t e = launch_semi_walk(L.cls, d_jobs + L.first, L.count, d_aux + L.first, ctx->d_ev, ctx->d_ref, ctx->d_tb_dir, d_endj,
@@ -242,7 +253,13 @@ extern "C" {
 int rawdtw_semiglobal_batch(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events, uint64_t n_events,
                             float *out_cost, uint32_t *out_end_j)
 {
-    return semi_batch(ctx, jobs, n_jobs, h_events, n_events, out_cost, out_end_j);
+    return semi_batch(ctx, SemiForm::Cost, jobs, n_jobs, h_events, n_events, out_cost, nullptr, out_end_j);
+}
+
+int rawdtw_semiglobal_span_batch(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events, uint64_t n_events,
+                                 float *out_cost, uint32_t *out_j0, uint32_t *out_end_j)
+{
+    return semi_batch(ctx, SemiForm::Span, jobs, n_jobs, h_events, n_events, out_cost, out_j0, out_end_j);
 }
 
 int rawdtw_semiglobal_traceback_steps(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events, uint64_t n_events,
@@ -273,7 +290,19 @@ int rawdtw_dtw_semiglobal(rawdtw_ctx *ctx, const float *a, uint32_t n, const flo
     if (st != RAWDTW_OK) return st;
     rawdtw_job_t j{0, 0, n, m, RAWDTW_FULL, 0u, 0};
     uint32_t end_j = 0;
-    return semi_batch(ctx, &j, 1, a, n, cost, &end_j);
+    return semi_batch(ctx, SemiForm::Cost, &j, 1, a, n, cost, nullptr, &end_j);
+}
+
+int rawdtw_dtw_semiglobal_span(rawdtw_ctx *ctx, const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, float *cost,
+                               uint32_t *j0, uint32_t *end_j)
+{
+    if (!ctx || !a || !b || !cost || !j0 || !end_j) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+    if (n == 0 || m == 0) return fail(ctx, RAWDTW_ERR_INVALID, "zero length (dtw.cpp:670 asserts)");
+    PrivateRef pr(ctx);
+    int st = pr.put(b, m);
+    if (st != RAWDTW_OK) return st;
+    rawdtw_job_t j{0, 0, n, m, RAWDTW_FULL, exclude_last ? 1u : 0u, 0};
+    return semi_batch(ctx, SemiForm::Span, &j, 1, a, n, cost, j0, end_j);
 }
 
 int rawdtw_dtw_semiglobal_tb(rawdtw_ctx *ctx, const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, float *cost,

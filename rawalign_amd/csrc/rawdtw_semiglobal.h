@@ -1,5 +1,6 @@
 // rawdtw_semiglobal.h -- what rawdtw_semiglobal_kernels.hip (the kernels) and rawdtw_semiglobal.cpp (validation, classes, launches, sub-batches)
-// share: a job's class, the sizes of its boundary rows and of its packed directions, and the launchers.
+// share: a job's class, the sizes of its boundary rows (the cost and traceback forms', the span form's) and of its packed directions,
+// and the launchers.
 #pragma once
 #include <cstdint>
 
@@ -24,6 +25,8 @@ inline uint64_t semi_bnd_floats(uint32_t n, uint32_t m, int cls)
     if (n <= 64u * (uint32_t)semi_rpl(cls)) return 0;
     return (uint64_t)(cls == 4 ? kFullWgWaves : 1) * (((uint64_t)m + 63) & ~63ull);
 }
+// the span form's boundary rows, in floats: a slot holds the row of costs and behind it the row of start columns
+inline uint64_t semi_span_bnd_floats(uint32_t n, uint32_t m, int cls) { return 2 * semi_bnd_floats(n, m, cls); }
 // bytes of packed directions: [strip][block][lane][step in block], blocks of 16 bytes a lane (k_semi_wave)
 inline uint64_t semi_dir_bytes(uint32_t n, uint32_t m, int cls)
 {
@@ -35,6 +38,9 @@ inline uint64_t semi_dir_bytes(uint32_t n, uint32_t m, int cls)
 
 hipError_t launch_semi_wave(int cls, bool traceback, const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev,
                             const float *ref, float *out_cost, uint32_t *out_end_j, float *bnd_ws, uint8_t *dir_ws, hipStream_t s);
+// the span form (k_semi_span_wave): cost, j0 and end_j; bnd_ws laid out by semi_span_bnd_floats
+hipError_t launch_semi_span_wave(int cls, const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev, const float *ref,
+                                 float *out_cost, uint32_t *out_j0, uint32_t *out_end_j, float *bnd_ws, hipStream_t s);
 // the walk from (n - 1, end_j) to row 0 (end-first (i, j) into tmp_i / tmp_j), then start-first steps, distances and j0
 hipError_t launch_semi_walk(int cls, const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev, const float *ref,
                             const uint8_t *dir_ws, const uint32_t *end_j, const uint64_t *path_off, uint32_t *path_len,

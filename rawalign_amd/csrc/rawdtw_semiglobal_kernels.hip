@@ -3,6 +3,7 @@
 // What they replace (reference file:line):
 //   k_semi_wave<.,false>                                   : DTW_semiglobal, DTW_semiglobal_slow   src/dtw.cpp:526-593
 //   k_semi_wave<.,true> + k_semi_walk_wave + k_semi_finish : DTW_semiglobal_tb                     src/dtw.cpp:669-753
+//   k_semi_span_wave                                       : cost, end_j and path[0].j of DTW_semiglobal_tb, no direction matrix
 //
 // k_semi_wave is the sibling of k_full_wave (rawdtw_kernels.hip): the same skewed wavefront, rows over the lanes, RPL rows a lane,
 // strips of 64 * RPL rows, boundary rows in HBM, the same packed 2-bit directions in the same buffer layout.  What differs:
@@ -28,16 +29,54 @@ namespace rawdtw {
 template <int RPL> struct SemiDirWord { using type = uint8_t; };
 template <> struct SemiDirWord<8> { using type = uint16_t; };
 
+// a start column travels between lanes as a value does (rawdtw_dp.h)
+__device__ __forceinline__ uint32_t wave_shr1(uint32_t v, uint32_t fill)
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x138, 0xf, 0xf, false);
+}
+__device__ __forceinline__ uint32_t read_lane(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
+
+// The span form's choice of a cell's start: ab < t_up ? s_up : (left < t_lf ? s_left : s_diag), with t_up = min(left, diag) and
+// t_lf = min(ab, diag) -- the TB form's two comparisons, each into a lane mask, and two selects on the masks.  One statement, because
+// the compiler does not look inside an asm string: on gfx950 a vector instruction that writes a scalar register (the compare's mask)
+// needs two wait states before a vector instruction reads that register, and here they are there by construction -- between the
+// first compare and its select lie the second compare and the s_nop, between the second compare and its select the s_nop and the
+// first select.  (As four statements the compiler's scheduler decided the distance, and padded it to one state only.)
+__device__ __forceinline__ uint32_t span_pick(float ab, float t_up, float left, float t_lf, uint32_t s_up, uint32_t s_left, uint32_t s_diag)
+{
+    uint32_t r;
+    lmask m_up, m_lf;
+    asm("v_cmp_lt_f32_e64 %[mlf], %[left], %[tlf]\n\t"
+        "v_cmp_lt_f32_e64 %[mup], %[ab], %[tup]\n\t"
+        "s_nop 0\n\t"
+        "v_cndmask_b32_e64 %[r], %[sdiag], %[sleft], %[mlf]\n\t"
+        "v_cndmask_b32_e64 %[r], %[r], %[sup], %[mup]"
+        : [r] "=&v"(r), [mlf] "=&s"(m_lf), [mup] "=&s"(m_up)
+        : [ab] "v"(ab), [tup] "v"(t_up), [left] "v"(left), [tlf] "v"(t_lf), [sup] "v"(s_up), [sleft] "v"(s_left), [sdiag] "v"(s_diag));
+    return r;
+}
+
 // WAVES = 1: one wave per job, strips in sequence.  WAVES = 4 (jobs of three strips or more): the workgroup's waves take strips
 // w, w + 4, ... as a pipeline, strip s + 1 trailing strip s by at least one 64-column chunk; boundary rows are a ring of WAVES rows
 // and a strip publishes the columns it has flushed through an LDS progress word, (strip << 21) | columns -- so m < 2^21 and fewer
 // than 2^11 strips (semi_class sees to it).
-template <int RPL, bool TB, int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void k_semi_wave(const DevJob *__restrict__ jobs, const FullAux *__restrict__ aux,
-                                                          const float *__restrict__ ev, const float *__restrict__ ref,
-                                                          float *__restrict__ out_cost, uint32_t *__restrict__ out_end_j,
-                                                          float *__restrict__ bnd_ws, uint8_t *__restrict__ dir_ws)
+//
+// SPAN (never with TB): every cell also carries S(i, j), the column in which the path that the walk would take from it starts
+// (include/rawdtw.h, "span").  One more register a row register, chosen from the three neighbours' starts by the very
+// comparisons the TB form packs into its 2-bit code; the start travels wherever the value travels -- to the next lane beside
+// last_out, along the diagonal beside diag_in, down to the next strip in a second boundary row behind the row of costs
+// ([costs: row_stride][starts: row_stride] a ring slot, semi_span_bnd_floats), both stored before the one release fence and the
+// one progress word.  Column -1's starts are 0 and so is every start a column-0 cell can choose from (the cell above it lies in
+// column 0, the other two in column -1): S(i, 0) = 0 whatever the values.  The scalar (minimum, step) pair gains the owner
+// lane's start of the cell that improved the minimum, read by the same branch.
+template <int RPL, bool TB, bool SPAN, int WAVES>
+__device__ __forceinline__ void semi_wave_body(const DevJob *__restrict__ jobs, const FullAux *__restrict__ aux,
+                                               const float *__restrict__ ev, const float *__restrict__ ref,
+                                               float *__restrict__ out_cost, uint32_t *__restrict__ out_j0,
+                                               uint32_t *__restrict__ out_end_j, float *__restrict__ bnd_ws,
+                                               uint8_t *__restrict__ dir_ws)
 {
+    static_assert(!(TB && SPAN), "the span form writes no directions");
     using word_t = typename SemiDirWord<RPL>::type;
     constexpr float kNone = __builtin_inff(); // beyond the matrix: loses every min (no sentinel, as in k_full_wave)
     const DevJob jb = jobs[blockIdx.x];
@@ -53,6 +92,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_semi_wave(const DevJob *__restri
     constexpr uint32_t SPB = 16u / sizeof(word_t);
     const uint32_t TXB = (NX + 63 + SPB - 1) / SPB;
     const uint32_t row_stride = (NX + 63u) & ~63u; // floats per boundary row (semi_bnd_floats)
+    const uint32_t slot_stride = SPAN ? 2u * row_stride : row_stride; // (a span slot: the costs, then the starts)
     float *bnd_base = bnd_ws + ax.bnd_off;
     uint4 *dirs = reinterpret_cast<uint4 *>(dir_ws + ax.dir_off);
     __shared__ __attribute__((aligned(16))) word_t tbuf_all[TB ? WAVES * 64 * SPB : 1];
@@ -69,9 +109,12 @@ __global__ __launch_bounds__(64 * WAVES) void k_semi_wave(const DevJob *__restri
     const uint64_t owner_bit = 1ull << owner;
     uint32_t best_bits = 0x7f800000u; // +inf
     uint32_t best_t = owner;
+    uint32_t best_s = 0; // SPAN: the start of the cell that holds the minimum
     for (uint32_t s = wv; s < nstrips; s += WAVES) {
-        const float *bnd_in = bnd_base + (uint64_t)((s + WAVES - 1) % WAVES) * row_stride; // written by strip s-1
-        float *bnd = bnd_base + (uint64_t)(s % WAVES) * row_stride;                          // read by strip s+1
+        const float *bnd_in = bnd_base + (uint64_t)((s + WAVES - 1) % WAVES) * slot_stride; // written by strip s-1
+        float *bnd = bnd_base + (uint64_t)(s % WAVES) * slot_stride;                          // read by strip s+1
+        const uint32_t *sbnd_in = reinterpret_cast<const uint32_t *>(bnd_in) + row_stride;   // SPAN: the starts behind the costs
+        uint32_t *sbnd = reinterpret_cast<uint32_t *>(bnd) + row_stride;
         const uint32_t y0 = (s * 64u + lane) * RPL;
         const uint32_t rows_here = (NY - s * STRIP) < STRIP ? (NY - s * STRIP) : STRIP;
         const uint32_t lanes_here = (rows_here + RPL - 1) / RPL;
@@ -84,14 +127,17 @@ __global__ __launch_bounds__(64 * WAVES) void k_semi_wave(const DevJob *__restri
         auto strip = [&](auto kk_c) {
             constexpr int KK = decltype(kk_c)::value;
             float yv[RPL], v[RPL];
+            uint32_t vs[RPL]; // SPAN: the starts of v[] (dead otherwise)
 #pragma unroll
             for (int k = 0; k < RPL; k++) {
                 uint32_t y = y0 + k;
                 yv[k] = Y[y < NY ? y : NY - 1];
                 v[k] = kNone; // column -1
+                if (SPAN) vs[k] = 0;
             }
             float diag_in = kNone; // (row 0 has no corner to start from: it is assigned)
             float last_out = kNone, xval = 0.0f, xchunk = 0.0f, bchunk = kNone, wchunk = 0.0f;
+            uint32_t sdiag_in = 0, slast_out = 0, sbchunk = 0, swchunk = 0; // SPAN: the starts beside diag_in, last_out, bchunk, wchunk
             for (uint32_t t = 0; t < steps; t++) {
                 if ((t & 63u) == 0) {
                     const uint32_t idx = t + lane;
@@ -105,15 +151,19 @@ __global__ __launch_bounds__(64 * WAVES) void k_semi_wave(const DevJob *__restri
                             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                         }
                         bchunk = idx < NX ? bnd_in[idx] : kNone;
+                        if (SPAN) sbchunk = idx < NX ? sbnd_in[idx] : 0u;
                     }
                 }
                 const float x0 = read_lane(xchunk, (int)(t & 63u));
                 const float b0 = read_lane(bchunk, (int)(t & 63u));
                 const float up_in = wave_shr1(last_out, b0);
+                uint32_t sup_in = 0;
+                if (SPAN) sup_in = wave_shr1(slast_out, read_lane(sbchunk, (int)(t & 63u)));
                 xval = wave_shr1(xval, x0);
                 const uint32_t x = t - (uint32_t)lane;
                 if (x < NX) {
                     float d = diag_in, ab = up_in;
+                    uint32_t sd = sdiag_in, sab = sup_in;
                     uint32_t code = 0;
 #pragma unroll
                     for (int k = 0; k < RPL; k++) {
@@ -132,10 +182,21 @@ __global__ __launch_bounds__(64 * WAVES) void k_semi_wave(const DevJob *__restri
                             asm("v_min_f32 %0, %1, %2" : "=v"(t_lf) : "v"(ab), "v"(d));
                             asm volatile("v_cmp_lt_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(code) : "v"(left), "v"(t_lf) : "vcc");
                         }
+                        if (SPAN) {
+                            // the TB form's two comparisons, each into a lane mask, and the start of the neighbour the walk would step
+                            // to (else: the diagonal, the reference's quirk ab == left < d included).  Row 0 starts in its own column.
+                            float t_up, t_lf;
+                            asm("v_min_f32 %0, %1, %2" : "=v"(t_up) : "v"(left), "v"(d));
+                            asm("v_min_f32 %0, %1, %2" : "=v"(t_lf) : "v"(ab), "v"(d));
+                            uint32_t ns = span_pick(ab, t_up, left, t_lf, sab, vs[k], sd);
+                            if (k == 0) ns = row0 ? x : ns;
+                            sd = vs[k]; sab = ns; vs[k] = ns;
+                        }
                         d = left; ab = nv; v[k] = nv;
                     }
                     diag_in = up_in;
                     last_out = v[RPL - 1];
+                    if (SPAN) { sdiag_in = sup_in; slast_out = vs[RPL - 1]; }
                     if (TB) {
                         // bit reversal puts cell k at bits 2k ("i - 1", shifted in first) and 2k + 1 ("j - 1")
                         const uint32_t w = __builtin_bitreverse32(code) >> (32 - 2 * RPL);
@@ -150,16 +211,32 @@ __global__ __launch_bounds__(64 * WAVES) void k_semi_wave(const DevJob *__restri
                     // issues beside the other waves' vector work -- the loop is bound by the vector unit) branches over the update,
                     // a v_readlane of the new minimum and a move of the step, which a job takes a handful of times.  One vector
                     // instruction a column.  (As `if (cand < best)` on vector values the compiler built a branch around two moves.)
-                    asm volatile("v_cmp_gt_f32 vcc, %0, %2\n\t"
-                                 "s_and_b64 vcc, vcc, %3\n\t"
-                                 "s_cmp_lg_u64 vcc, 0\n\t"
-                                 "s_cbranch_scc0 .Lsemi_keep_%=\n\t"
-                                 "v_readlane_b32 %0, %2, %5\n\t"
-                                 "s_mov_b32 %1, %4\n"
-                                 ".Lsemi_keep_%=:"
-                                 : "+s"(best_bits), "+s"(best_t)
-                                 : "v"(v[KK]), "s"(owner_bit), "s"(t), "s"(owner)
-                                 : "vcc", "scc");
+                    // The two statements below are one sequence; the span form's has two operands more (%2: the pair's start, %4: the
+                    // starts' register), so its operand numbers differ from the other's: %3 there is %2 here, %5..%7 are %3..%5.
+                    if constexpr (SPAN)
+                        // (the same, and the owner lane's start of that cell)
+                        asm volatile("v_cmp_gt_f32 vcc, %0, %3\n\t"
+                                     "s_and_b64 vcc, vcc, %5\n\t"
+                                     "s_cmp_lg_u64 vcc, 0\n\t"
+                                     "s_cbranch_scc0 .Lsemi_keep_%=\n\t"
+                                     "v_readlane_b32 %0, %3, %7\n\t"
+                                     "v_readlane_b32 %2, %4, %7\n\t"
+                                     "s_mov_b32 %1, %6\n"
+                                     ".Lsemi_keep_%=:"
+                                     : "+s"(best_bits), "+s"(best_t), "+s"(best_s)
+                                     : "v"(v[KK]), "v"(vs[KK]), "s"(owner_bit), "s"(t), "s"(owner)
+                                     : "vcc", "scc");
+                    else
+                        asm volatile("v_cmp_gt_f32 vcc, %0, %2\n\t"
+                                     "s_and_b64 vcc, vcc, %3\n\t"
+                                     "s_cmp_lg_u64 vcc, 0\n\t"
+                                     "s_cbranch_scc0 .Lsemi_keep_%=\n\t"
+                                     "v_readlane_b32 %0, %2, %5\n\t"
+                                     "s_mov_b32 %1, %4\n"
+                                     ".Lsemi_keep_%=:"
+                                     : "+s"(best_bits), "+s"(best_t)
+                                     : "v"(v[KK]), "s"(owner_bit), "s"(t), "s"(owner)
+                                     : "vcc", "scc");
                 }
                 if (TB && ((t % SPB) == SPB - 1 || t + 1 == steps)) {
                     // same wave wrote and reads the buffer; LDS operations of a wave complete in order, the
@@ -173,9 +250,14 @@ __global__ __launch_bounds__(64 * WAVES) void k_semi_wave(const DevJob *__restri
                     const uint32_t c = t - 63u;
                     const float v63 = read_lane(last_out, 63);
                     if ((uint32_t)lane == (c & 63u)) wchunk = v63;
+                    if (SPAN) {
+                        const uint32_t s63 = read_lane(slast_out, 63);
+                        if ((uint32_t)lane == (c & 63u)) swchunk = s63;
+                    }
                     if ((c & 63u) == 63u || c == NX - 1) {
                         const uint32_t base = c & ~63u;
                         if (base + lane <= c) bnd[base + lane] = wchunk;
+                        if (SPAN && base + lane <= c) sbnd[base + lane] = swchunk; // (before the one fence and the one progress word)
                         if (WAVES > 1) {
                             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                             if (lane == 0)
@@ -223,8 +305,28 @@ __global__ __launch_bounds__(64 * WAVES) void k_semi_wave(const DevJob *__restri
             if (jb.flags & kFlagExcludeLast) result = result - dist(Y[NY - 1], X[end_j]); // dtw.cpp:587-589, 744-746
             out_cost[jb.aux] = result;
             out_end_j[jb.aux] = end_j;
+            if (SPAN) out_j0[jb.aux] = best_s;
         }
     }
+}
+
+template <int RPL, bool TB, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void k_semi_wave(const DevJob *__restrict__ jobs, const FullAux *__restrict__ aux,
+                                                          const float *__restrict__ ev, const float *__restrict__ ref,
+                                                          float *__restrict__ out_cost, uint32_t *__restrict__ out_end_j,
+                                                          float *__restrict__ bnd_ws, uint8_t *__restrict__ dir_ws)
+{
+    semi_wave_body<RPL, TB, false, WAVES>(jobs, aux, ev, ref, out_cost, nullptr, out_end_j, bnd_ws, dir_ws);
+}
+
+// the span form: (cost, j0, end_j), no directions
+template <int RPL, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void k_semi_span_wave(const DevJob *__restrict__ jobs, const FullAux *__restrict__ aux,
+                                                               const float *__restrict__ ev, const float *__restrict__ ref,
+                                                               float *__restrict__ out_cost, uint32_t *__restrict__ out_j0,
+                                                               uint32_t *__restrict__ out_end_j, float *__restrict__ bnd_ws)
+{
+    semi_wave_body<RPL, false, true, WAVES>(jobs, aux, ev, ref, out_cost, out_j0, out_end_j, bnd_ws, nullptr);
 }
 
 // The walk, one wave per job: k_tb_walk_wave's (a block row of directions in LDS, all lanes in lockstep on uniform values, steps
@@ -331,6 +433,29 @@ hipError_t launch_semi_wave(int cls, bool tb, const DevJob *jobs, uint64_t count
     case 2: return launch_semi_t<4, 1>(tb, jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, s);
     case 3: return launch_semi_t<8, 1>(tb, jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, s);
     case 4: return launch_semi_t<8, kFullWgWaves>(tb, jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+template <int RPL, int WAVES>
+static hipError_t launch_semi_span_t(const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev, const float *ref,
+                                     float *out_cost, uint32_t *out_j0, uint32_t *out_end_j, float *bnd_ws, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_semi_span_wave<RPL, WAVES>), dim3((uint32_t)count), dim3(64 * WAVES), 0, s, jobs, aux, ev, ref, out_cost,
+                       out_j0, out_end_j, bnd_ws);
+    return hipGetLastError();
+}
+
+hipError_t launch_semi_span_wave(int cls, const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev, const float *ref,
+                                 float *out_cost, uint32_t *out_j0, uint32_t *out_end_j, float *bnd_ws, hipStream_t s)
+{
+    if (count == 0) return hipSuccess;
+    switch (cls) {
+    case 0: return launch_semi_span_t<1, 1>(jobs, count, aux, ev, ref, out_cost, out_j0, out_end_j, bnd_ws, s);
+    case 1: return launch_semi_span_t<2, 1>(jobs, count, aux, ev, ref, out_cost, out_j0, out_end_j, bnd_ws, s);
+    case 2: return launch_semi_span_t<4, 1>(jobs, count, aux, ev, ref, out_cost, out_j0, out_end_j, bnd_ws, s);
+    case 3: return launch_semi_span_t<8, 1>(jobs, count, aux, ev, ref, out_cost, out_j0, out_end_j, bnd_ws, s);
+    case 4: return launch_semi_span_t<8, kFullWgWaves>(jobs, count, aux, ev, ref, out_cost, out_j0, out_end_j, bnd_ws, s);
     default: return hipErrorInvalidValue;
     }
 }

@@ -797,6 +797,42 @@ class Engine:
         self._check(self.lib.rawdtw_semiglobal_timing(self._ctx, C.byref(f), C.byref(w), C.byref(d), C.byref(e)))
         return {"fill_ms": f.value, "walk_ms": w.value, "direction_bytes": d.value, "path_elements": e.value}
 
+    def semiglobal_span(self, jobs, events=None):
+        """rawdtw_semiglobal_span_batch -> (cost, j0, end_j), one of each a job: cost and end_j as semiglobal_batch, j0 the column in which
+        DTW_semiglobal_tb's path starts (semiglobal_traceback's j0), from one pass without a direction matrix.  events: as semiglobal_batch."""
+        jobs = np.ascontiguousarray(jobs, dtype=JOB_DTYPE)
+        ev = None if events is None else _f32(events)
+        cost = np.empty(len(jobs), np.float32)
+        j0 = np.zeros(len(jobs), np.uint32)
+        end_j = np.zeros(len(jobs), np.uint32)
+        self._check(self.lib.rawdtw_semiglobal_span_batch(self._ctx, _ptr(jobs), len(jobs), None if ev is None else _ptr(ev),
+                                                          0 if ev is None else len(ev), _ptr(cost), _ptr(j0), _ptr(end_j)))
+        return cost, j0, end_j
+
+    def DTW_semiglobal_span(self, a_values, b_values, exclude_last_element=False):
+        """rawdtw_dtw_semiglobal_span -> (cost, j0, end_j): DTW_semiglobal_tb's cost and the columns of its path's first and last element"""
+        a, b = _f32(a_values), _f32(b_values)
+        c, j0, ej = C.c_float(), C.c_uint32(), C.c_uint32()
+        self._check(self.lib.rawdtw_dtw_semiglobal_span(self._ctx, _ptr(a), len(a), _ptr(b), len(b), int(exclude_last_element), C.byref(c),
+                                                        C.byref(j0), C.byref(ej)))
+        return np.float32(c.value), j0.value, ej.value
+
+    def semiglobal_place(self, reads, targets, exclude_last=False) -> dict:
+        """Seed-free placement: every read window (read_off, n) of the event arena against every target window (ref_off, m) of the
+        reference arena (both strands of every sequence, say) in one semiglobal_span call of len(reads) x len(targets) jobs, read-major;
+        then, on the host, `semiglobal_place_reduce` over each read's row -> {target, cost, j0, end_j, second}, one of each a read."""
+        reads = np.asarray(reads, np.int64).reshape(-1, 2)
+        targets = np.asarray(targets, np.int64).reshape(-1, 2)
+        jobs = np.zeros(len(reads) * len(targets), JOB_DTYPE)
+        jobs["read_off"] = np.repeat(reads[:, 0], len(targets))
+        jobs["n"] = np.repeat(reads[:, 1], len(targets))
+        jobs["ref_off"] = np.tile(targets[:, 0], len(reads))
+        jobs["m"] = np.tile(targets[:, 1], len(reads))
+        jobs["band_radius"], jobs["exclude_last"] = RAWDTW_FULL, int(bool(exclude_last))
+        shape = (len(reads), len(targets))
+        cost, j0, end_j = self.semiglobal_span(jobs)
+        return semiglobal_place_reduce(cost.reshape(shape), j0.reshape(shape), end_j.reshape(shape))
+
     def DTW_global_banded_tb(self, a_values, b_values, band_radius, exclude_last=False) -> DtwResult:
         """The banded cost of DTW_global_slantedbanded_antidiagonalwise and the path DTW_global_tb's walk takes through the band's cells
         (include/rawdtw.h, "banded traceback"); a job without a path has empty i, j and difference"""
@@ -874,6 +910,41 @@ def semiglobal_host(a_values, b_values, exclude_last_element=False, traceback=Fa
         raise RawDTWError(st, "rawdtw_semiglobal_tb_host refused its arguments")
     k = ln.value
     return DtwResult(np.float32(c.value), pi[:k].copy(), pj[:k].copy(), pd[:k].copy()), ej.value
+
+
+def semiglobal_span_host(a_values, b_values, exclude_last_element=False):
+    """rawdtw_semiglobal_span_host: the span's definition (include/rawdtw.h) restated on the host in O(m) memory, no device
+    -> (cost, j0, end_j)"""
+    lib = load_library()
+    a, b = _f32(a_values), _f32(b_values)
+    c, j0, ej = C.c_float(), C.c_uint32(), C.c_uint32()
+    st = lib.rawdtw_semiglobal_span_host(_ptr(a), len(a), _ptr(b), len(b), int(exclude_last_element), C.byref(c), C.byref(j0), C.byref(ej))
+    if st != 0:
+        raise RawDTWError(st, "rawdtw_semiglobal_span_host refused its arguments")
+    return np.float32(c.value), j0.value, ej.value
+
+
+def semiglobal_place_reduce(cost, j0, end_j) -> dict:
+    """The reduction of Engine.semiglobal_place over tables [read, target]: per read the target of the lowest cost -- compared with <,
+    so the lowest target index wins a tie; a NaN cost never wins, a read whose costs are all NaN gets target -1 (cost NaN, j0 and
+    end_j 0) -- that target's cost, j0 and end_j, and `second`, the smallest non-NaN cost among the other targets (+inf without one)."""
+    cost = np.asarray(cost, np.float32)
+    j0, end_j = np.asarray(j0, np.uint32), np.asarray(end_j, np.uint32)
+    n_reads, n_targets = cost.shape
+    target = np.full(n_reads, -1, np.int32)
+    best = np.full(n_reads, np.nan, np.float32)
+    for t in range(n_targets):
+        c = cost[:, t]
+        with np.errstate(invalid="ignore"):
+            take = ~np.isnan(c) & ((target < 0) | (c < best))
+        target[take], best[take] = t, c[take]
+    rows, col = np.arange(n_reads), np.maximum(target, 0)
+    found = target >= 0
+    others = np.where(np.isnan(cost), np.float32(np.inf), cost)
+    others[rows[found], col[found]] = np.inf
+    second = others.min(axis=1) if n_targets else np.full(n_reads, np.inf, np.float32)
+    pick = lambda table: np.where(found, table[rows, col], 0).astype(np.uint32) if n_targets else np.zeros(n_reads, np.uint32)  # noqa: E731
+    return {"target": target, "cost": best, "j0": pick(j0), "end_j": pick(end_j), "second": second.astype(np.float32)}
 
 
 def banded_tb_host(a_values, b_values, band_radius, exclude_last=False) -> DtwResult:
