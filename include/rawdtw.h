@@ -421,13 +421,43 @@ typedef struct {
 } rawdtw_anchor_t; /* ri_anchor_t, rmap.h:21-27; stored end-first like the reference */
 
 typedef struct {
-    int border_constraint;  /* 0 global, 1 sparse (roptions.h:21-23) */
+    int border_constraint;  /* 0 global, 1 sparse, 2 local (roptions.h:21-23; 2: "local border" below) */
     int fill_method;        /* 0 full, 1 banded (roptions.h:25-26) */
     float band_radius_frac; /* roptions.c:51 */
     float match_bonus;      /* roptions.c:52 */
     float min_score;        /* roptions.c:53 */
     int fused_score;        /* 1: score = fmaf(n, bonus, -cost) as the reference's -O3 -march=native build contracts it */
 } rawdtw_align_opt_t;
+
+/* ---- local border: border_constraint == 2.  The reference's command line offers --dtw-border-constraint local and align_chain exits on
+ * it ("invalid border constraint", rmap.cpp:301-304); this is the one definition the library gives it.  For a chain with anchors
+ * end-first, s = anchors[n_anchors - 1], e = anchors[0]:
+ *   windows   the global branch's (rmap.cpp:198-202): a = read events s.q .. e.q, n = e.q - s.q + 1; b = the strand's signals
+ *             s.t .. e.t, m = e.t - s.t + 1.  No flanks.  The read window stays pinned, the reference ends are free.
+ *   jobs      one a chain (rawdtw_chain_job_count is 1): the global job with band_radius = RAWDTW_FULL and exclude_last = 0, with and
+ *             without `cigar`.  fill_method and band_radius_frac are NOT looked at: dtw.hpp has no banded semiglobal.
+ *   cost      DTW_semiglobal_slow(a, n, b, m, false), i.e. rawdtw_semiglobal_batch's cost: the sentinel-free recurrence, end_j the
+ *             first minimum of the last row.
+ *   score     the global branch's: the early exit (float)n * match_bonus < min_score gives -1e10 (rmap.cpp:205-209), num_aligned = n,
+ *             the final score by rmap.cpp:306 under fused_score.  rawdtw_chain_replay takes the global branch.
+ *   cigar     DTW_semiglobal_tb(a, n, b, m): every element offset by (s.q, s.t), the sparse branch's way (rmap.cpp:285-289; the global
+ *             branch's add-to-back() quirk is not used); the first element is (s.q, s.t + j0), the last (e.q, s.t + end_j); the cost
+ *             bits are the score-only job's.
+ *   after     the sequential accept/cut of gen_chains, primary chains, MAPQ, the stop rule and the PAF columns (the chain's own start
+ *             and end) are unchanged.
+ *   property  for finite inputs a chain's local cost is at most its global full-matrix cost, bit for bit as floats: both run the same
+ *             recurrence, row 0 of the local one is cell by cell at most the global one's running sum, the last row's minimum is at
+ *             most its last cell -- min is exact and fp32 add is monotone.  The two are equal when m == 1.
+ * Opt-in: off (the default) every entry point that takes a context refuses 2 with the status and the wording it always had.  After
+ * rawdtw_set_border_local(ctx, 1), rawdtw_batch_create / _submit / _submit_device / _submit_compact and rawdtw_mapper_create on that
+ * context accept 2 (a mapper's second read group copies the setting); rawdtw_batch_submit_carry and rawdtw_batch_can_carry answer as
+ * they do for global.  rawdtw_mapper_create without a context (a scorer-only mapper) and the functions that take no context --
+ * rawdtw_chain_job_count, _build_jobs, _replay, rawdtw_batch_build_jobs, rawdtw_batch_replay -- accept 2 always.  Any other value is
+ * refused as before.  A local batch is a job-list batch whose launches are semiglobal fills (launch kind 11, param = rows a lane);
+ * from device arrays its job records are written on the device (two anchors a chain are read, none comes home).  A setter, not a
+ * context option. ---- */
+int rawdtw_set_border_local(rawdtw_ctx *ctx, int on);
+int rawdtw_get_border_local(const rawdtw_ctx *ctx, int *on);
 
 /* Number of DTW jobs align_chain issues for a chain (before any early exit). */
 uint32_t rawdtw_chain_job_count(const rawdtw_align_opt_t *opt, uint32_t n_anchors);
@@ -704,6 +734,12 @@ int rawdtw_batch_launch_stats(const rawdtw_batch *batch, uint32_t i, uint32_t *k
 /* job_cost may be NULL; otherwise receives the per-job costs too */
 int rawdtw_batch_fetch(rawdtw_ctx *ctx, rawdtw_batch *batch, float *score, uint8_t *keep,
                        float *job_cost);
+/* What the hand-over of a batch from device arrays (rawdtw_batch_submit_device, "resident_arrays") that is not planned on the device moved
+ * over the link, beside the plan's own records: the job records the device wrote (a local batch: one a chain, k_local_jobs; else 0), the
+ * bytes that went up for them (8 a chain of offsets) and the bytes that came home (32 a chain of records -- or, where the anchors are
+ * brought home instead, 8 an anchor and 12 a chain of bases).  The environment variable RAWDTW_LOCAL_JOBS=host, read when a context is
+ * created, makes a local batch take the second way (tests, A/B measurements). */
+int rawdtw_batch_hand_over_stats(const rawdtw_batch *batch, uint64_t *records_on_device, uint64_t *bytes_to_device, uint64_t *bytes_to_host);
 /* GPU time of the batch's planning kernels (HIP events; 0 unless the option "time_plan" was set before create): the scan of
  * the anchor list, the side list's class order, the passes' records and copy orders.  The wide bands' launch that goes out
  * between them for the batch's first run is DTW work: rawdtw_batch_wide_ms. */

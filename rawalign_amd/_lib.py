@@ -209,6 +209,9 @@ SYMBOLS = {
     "rawdtw_dtw_global_banded_tb": (I32, [VP, VP, U32, VP, U32, I32, I32, C.POINTER(F32), C.POINTER(U32), VP, VP, VP]),
     "rawdtw_banded_tb_host": (I32, [VP, U32, VP, U32, I32, I32, C.POINTER(F32), C.POINTER(U32), VP, VP, VP]),
     "rawdtw_mapper_set_banded_cigar": (I32, [VP, I32]),
+    "rawdtw_set_border_local": (I32, [VP, I32]),
+    "rawdtw_get_border_local": (I32, [VP, VP]),
+    "rawdtw_batch_hand_over_stats": (I32, [VP, VP, VP, VP]),
     "rawdtw_chain_job_count": (U32, [C.POINTER(AlignOpt), U32]),
     "rawdtw_chain_build_jobs": (I32, [C.POINTER(AlignOpt), VP, U32, U64, U32, I32, VP]),
     "rawdtw_chain_replay": (F32, [C.POINTER(AlignOpt), VP, U32, VP, F32]),

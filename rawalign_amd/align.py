@@ -39,7 +39,7 @@ class MapOpt:
     fused_score: bool = True
 
     def c_struct(self) -> AlignOpt:
-        if self.dtw_border_constraint not in (0, 1):
+        if self.dtw_border_constraint not in (0, 1, 2):  # (2, local: include/rawdtw.h, "local border")
             # rmap.cpp:301-304: fprintf(stderr, "ERROR: invalid border constraint") + exit(EXIT_FAILURE)
             raise SystemExit("ERROR: invalid border constraint")
         return AlignOpt(self.dtw_border_constraint, self.dtw_fill_method, self.dtw_band_radius_frac,
@@ -123,7 +123,8 @@ def evaluate_reads(engine: Engine, reads, opt: MapOpt):
     engine._check(lib.rawdtw_batch_build_jobs(C.byref(copt), n_chains, _ptr(anchor_off), _ptr(anchors),
                                               _ptr(ref_base), _ptr(rbase), _ptr(job_off), _ptr(jobs),
                                               len(jobs), C.byref(n_jobs)))
-    cost = engine.score_batch(jobs, events)
+    local = opt.dtw_border_constraint == RI_M_DTW_BORDER_CONSTRAINT_LOCAL
+    cost = engine.semiglobal_batch(jobs, events)[0] if local else engine.score_batch(jobs, events)
     score = np.zeros(n_chains, np.float32)
     keep = np.zeros(n_chains, np.uint8)
     engine._check(lib.rawdtw_batch_replay(C.byref(copt), len(reads), _ptr(chain_off), _ptr(anchor_off),
@@ -160,8 +161,21 @@ def align_chain(engine: Engine, chain: Chain, read_events, opt: MapOpt, cigar: b
     engine._check(st)
     jobs = jobs[:nj]
     ev = np.ascontiguousarray(read_events, dtype=np.float32)
+    local = opt.dtw_border_constraint == RI_M_DTW_BORDER_CONSTRAINT_LOCAL
+    if local and cigar:
+        # DTW_semiglobal_tb over the chain's window, every element offset by the start anchor (the sparse branch's way); the walk starts at (0, j0)
+        from .dtw import expand_steps
+
+        cost, j0, off, plen, step, pd = engine.semiglobal_traceback(jobs, ev)
+        chain.alignment_score = float(lib.rawdtw_chain_replay(C.byref(copt), _ptr(anchors), na, _ptr(cost), C.c_float(-1e10)))
+        sl = slice(int(off[0]), int(off[0]) + int(plen[0]))
+        pi, pj = expand_steps(step[sl], int(j0[0]))
+        s = anchors[na - 1]
+        chain.dtw_result = DtwResult(np.float32(cost[0]), pi.astype(np.uint64) + np.uint64(s["query_position"]),
+                                     pj.astype(np.uint64) + np.uint64(s["target_position"]), pd[sl].copy())
+        return chain
     if not cigar:
-        cost = engine.score_batch(jobs, ev)
+        cost = engine.semiglobal_batch(jobs, ev)[0] if local else engine.score_batch(jobs, ev)
         chain.alignment_score = float(lib.rawdtw_chain_replay(C.byref(copt), _ptr(anchors), na, _ptr(cost),
                                                                C.c_float(min_score)))
         return chain
@@ -278,9 +292,11 @@ def unpack_anchors(lib, anchor_off, ca: CompactAnchors) -> np.ndarray:
 class Batch:
     """rawdtw_batch: DTW scoring + align_chain fold + per-read selection, all on the device.  compact=True hands the anchor
     lists over in the compact form (rawdtw_batch_submit_compact: the batch is then already running when this returns);
-    submit=True creates and enqueues the first run in one call (rawdtw_batch_submit), as a pipelined host does."""
+    submit=True creates and enqueues the first run in one call (rawdtw_batch_submit), as a pipelined host does.  device_ptrs: the device
+    addresses of copies of cb's anchors, ref_base and read_base that the caller keeps alive (rawdtw_batch_submit_device; cb's own arrays
+    are then only read for their offsets).  A local batch (opt.dtw_border_constraint == 2) needs Engine.set_border_local first."""
 
-    def __init__(self, engine: Engine, opt: MapOpt, cb: CandidateBatch, compact: bool = False, submit: bool = False):
+    def __init__(self, engine: Engine, opt: MapOpt, cb: CandidateBatch, compact: bool = False, submit: bool = False, device_ptrs=None):
         self.engine = engine
         self.cb = cb
         self._copt = opt.c_struct()
@@ -292,7 +308,11 @@ class Batch:
         h = C.c_void_p()
         a = self._arrays
         self._submitted = False
-        if compact:
+        if device_ptrs is not None:
+            engine._check(engine.lib.rawdtw_batch_submit_device(engine._ctx, C.byref(self._copt), cb.n_reads, _ptr(a[0]), _ptr(a[1]),
+                                                                *(C.c_void_p(int(p)) for p in device_ptrs), C.byref(h)))
+            self._submitted = True
+        elif compact:
             self.compact = ca = pack_anchors(engine.lib, a[1], a[2])
             engine._check(engine.lib.rawdtw_batch_submit_compact(engine._ctx, C.byref(self._copt), cb.n_reads, _ptr(a[0]), _ptr(a[1]),
                                                                  _ptr(ca.heads), _ptr(ca.unit_abs), _ptr(ca.steps), _ptr(ca.wide), len(ca.wide),
@@ -420,6 +440,12 @@ class Batch:
                         "algorithmic_bytes": int(ab.value), "cells": int(cl.value)})
             i += 1
         return out
+
+    def hand_over_stats(self) -> dict:
+        """rawdtw_batch_hand_over_stats: job records written on the device (k_local_jobs), bytes up and bytes home of the hand-over"""
+        v = [C.c_uint64() for _ in range(3)]
+        self.engine._check(self.engine.lib.rawdtw_batch_hand_over_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("records_on_device", "bytes_to_device", "bytes_to_host"), (int(x.value) for x in v)))
 
     def plan_ms(self) -> float:
         """rawdtw_batch_plan_ms: the planning launches of a sync-free batch created under "time_plan" (0 otherwise)"""

@@ -234,6 +234,7 @@ static int bases_home(rawdtw_ctx *ctx, rawdtw_batch *b)
     catch (const std::bad_alloc &) { return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed"); }
     if (nc) HIP_TRY(ctx, hipMemcpy(b->host_ref_base.data(), b->in.ref_base, nc * 8, hipMemcpyDeviceToHost));
     if (nc) HIP_TRY(ctx, hipMemcpy(b->host_read_base.data(), b->in.read_base, nc * 4, hipMemcpyDeviceToHost));
+    b->link_home += nc * 12;
     b->in.ref_base = b->host_ref_base.data(); b->in.read_base = b->host_read_base.data();
     b->in.resident = false;
     return RAWDTW_OK;
@@ -260,16 +261,19 @@ int materialise_host_arrays(rawdtw_ctx *ctx, rawdtw_batch *b)
     if (!in.resident) return RAWDTW_OK;
     try { b->host_anchors.resize(na + 1); } catch (const std::bad_alloc &) { return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed"); }
     if (na) HIP_TRY(ctx, hipMemcpy(b->host_anchors.data(), in.anchors, na * sizeof(rawdtw_anchor_t), hipMemcpyDeviceToHost));
+    b->link_home += na * sizeof(rawdtw_anchor_t);
     const int st = bases_home(ctx, b);
     if (st == RAWDTW_OK) in.anchors = b->host_anchors.data();
     return st;
 }
 
+int batch_finish_joblist(rawdtw_ctx *ctx, rawdtw_batch *b, const rawdtw_job_t *jobs, uint64_t n_jobs, const std::vector<ChainDesc> &desc);
+
 // the job-list path: jobs built on the host (chain ranges spread over the planner's threads), plan_host, chain records
 int batch_create_joblist(rawdtw_ctx *ctx, rawdtw_batch *b, const std::vector<uint64_t> &job_off, uint64_t n_jobs)
 {
     const BatchIn &in = b->in; // (its arrays are on the host: materialise_host_arrays)
-    const uint64_t n_chains = b->n_chains, n_reads = b->n_reads;
+    const uint64_t n_chains = b->n_chains;
     const rawdtw_align_opt_t *opt = &b->opt;
     // chain descriptors: from the anchors alone.  The parts' read regions telescope (consecutive parts share their
     // anchor event), so sum(n) = (last.q - first.q) + parts in the reference's uint32 arithmetic (rmap.cpp:236,292).
@@ -283,7 +287,7 @@ int batch_create_joblist(rawdtw_ctx *ctx, rawdtw_batch *b, const std::vector<uin
         if (a1 == a0) { d.span = 0; d.num_aligned = 0; continue; }
         const rawdtw_anchor_t &first = in.anchors[a1 - 1], &last = in.anchors[a0];
         d.span = last.query_position - first.query_position + 1; // rmap.cpp:202,245
-        d.num_aligned = opt->border_constraint == 0 ? d.span : (last.query_position - first.query_position) + d.n_jobs;
+        d.num_aligned = opt->border_constraint != 1 ? d.span : (last.query_position - first.query_position) + d.n_jobs; // (global and local: n)
     }
     RawVec<rawdtw_job_t> jobs;
     try { jobs.resize(n_jobs); } catch (const std::bad_alloc &) { return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed"); }
@@ -310,7 +314,15 @@ int batch_create_joblist(rawdtw_ctx *ctx, rawdtw_batch *b, const std::vector<uin
         }
     });
     for (int t = 0; t < T; t++) if (status[t] != RAWDTW_OK) return fail(ctx, status[t], "job building failed");
-    int st = build_plan(ctx, jobs.data(), n_jobs, false, &b->plan);
+    return batch_finish_joblist(ctx, b, jobs.data(), n_jobs, desc);
+}
+
+// the second half of the job-list form: the plan -- the planner's, or for a local batch the semiglobal launches (build_semi_plan) --, the
+// chain records and the fold order on the device
+int batch_finish_joblist(rawdtw_ctx *ctx, rawdtw_batch *b, const rawdtw_job_t *jobs, uint64_t n_jobs, const std::vector<ChainDesc> &desc)
+{
+    const uint64_t n_chains = b->n_chains, n_reads = b->n_reads;
+    int st = b->opt.border_constraint == 2 ? build_semi_plan(ctx, jobs, n_jobs, &b->plan) : build_plan(ctx, jobs, n_jobs, false, &b->plan);
     if (st != RAWDTW_OK) return st;
     b->n_jobs = n_jobs;
     st = dev_alloc(ctx, &b->d_chains, n_chains);
@@ -336,10 +348,43 @@ int batch_create_joblist(rawdtw_ctx *ctx, rawdtw_batch *b, const std::vector<uin
     if (n_chains) e = hipMemcpyAsync(b->d_chains, desc.data(), n_chains * sizeof(ChainDesc), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess && n_chains)
         e = hipMemcpyAsync(b->d_fold_order, fold_order.data(), n_chains * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(b->d_chain_off, in.chain_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(b->d_chain_off, b->in.chain_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream); // (the staging vectors above die with this scope)
     if (e != hipSuccess) return hip_fail(ctx, e, "uploading chain descriptors");
     return RAWDTW_OK;
+}
+
+// A local batch whose anchor arrays are on the device (rawdtw_batch_submit_device, "resident_arrays"): k_local_jobs (rawdtw_local.hip)
+// writes a record a chain from the chain's two end anchors and its bases; the offsets go up (8 bytes a chain), the records come home
+// (32 bytes a chain) and the host plans the launches' classes from them.  No anchor crosses the link.
+int batch_create_local_device(rawdtw_ctx *ctx, rawdtw_batch *b)
+{
+    const BatchIn &in = b->in;
+    const uint64_t n_chains = b->n_chains;
+    std::vector<rawdtw_job_t> recs;
+    std::vector<ChainDesc> desc;
+    try { recs.resize(n_chains); desc.resize(n_chains); } catch (const std::bad_alloc &) { return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed"); }
+    if (n_chains) {
+        DevBlock blk(ctx, "local batch"); // (freed behind the stream when this scope ends)
+        const int st = blk.reserve(al256((n_chains + 1) * 8) + n_chains * sizeof(rawdtw_job_t));
+        if (st != RAWDTW_OK) return st;
+        char *p = blk.p;
+        uint64_t *d_off = carve<uint64_t>(p, n_chains + 1);
+        rawdtw_job_t *d_recs = carve<rawdtw_job_t>(p, n_chains);
+        HIP_TRY(ctx, hipMemcpyAsync(d_off, in.anchor_off, (n_chains + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        const hipError_t e = launch_local_jobs(d_off, in.anchors, in.ref_base, in.read_base, n_chains, d_recs, ctx->stream);
+        if (e != hipSuccess) return hip_fail(ctx, e, "local job records launch");
+        HIP_TRY(ctx, hipMemcpyAsync(recs.data(), d_recs, n_chains * sizeof(rawdtw_job_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        b->local_records = n_chains; b->link_up += (n_chains + 1) * 8; b->link_home += n_chains * sizeof(rawdtw_job_t);
+    }
+    uint64_t n_jobs = 0; // an empty chain has no job: the records are compacted in place, chain order kept
+    for (uint64_t c = 0; c < n_chains; c++) {
+        const bool empty = in.anchor_off[c + 1] == in.anchor_off[c];
+        desc[c] = ChainDesc{n_jobs, empty ? 0u : 1u, empty ? 0u : recs[c].n, empty ? 0u : recs[c].n, 0u}; // span = num_aligned = n
+        if (!empty) recs[n_jobs++] = recs[c];
+    }
+    return batch_finish_joblist(ctx, b, recs.data(), n_jobs, desc);
 }
 
 // forget the device pointers: into the workspace, or at the job-list form's own arrays (handed back or freed by the caller)
@@ -454,7 +499,8 @@ static int batch_create_any(rawdtw_ctx *ctx, const rawdtw_align_opt_t *opt, uint
         return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
     if (in.compact && (!in.heads || !in.unit_abs || !in.steps || (!in.wide && in.n_wide)))
         return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
-    if (opt->border_constraint != 0 && opt->border_constraint != 1)
+    // (2, local: only on a context that opted in -- rawdtw_set_border_local; off, the refusal, its status and its wording stay)
+    if (opt->border_constraint != 0 && opt->border_constraint != 1 && !(opt->border_constraint == 2 && ctx->border_local))
         return fail(ctx, RAWDTW_ERR_INVALID, "invalid border constraint (rmap.cpp:301-304)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint64_t n_chains = in.chain_off[n_reads];
@@ -470,6 +516,8 @@ static int batch_create_any(rawdtw_ctx *ctx, const rawdtw_align_opt_t *opt, uint
     }
     if (stream_eligible(ctx, opt, in.anchor_off[n_chains]))
         st = batch_create_stream(ctx, b);
+    else if (opt->border_constraint == 2 && b->in.resident && !b->in.compact && ctx->local_jobs_device)
+        st = batch_create_local_device(ctx, b); // (two anchors a chain are all a local batch needs: they are read where they lie)
     else {
         uint64_t n_jobs = 0;
         st = joblist_count(ctx, b, ctx->job_off_scratch, &n_jobs); // (a context is not re-entrant)
@@ -1003,6 +1051,15 @@ int rawdtw_batch_fetch(rawdtw_ctx *ctx, rawdtw_batch *batch, float *score, uint8
         int st = stream_fallback(ctx, batch); // invalid anchors (the job-list path words the error) or a shape it does not take
         if (st != RAWDTW_OK) return st;
     }
+    return RAWDTW_OK;
+}
+
+int rawdtw_batch_hand_over_stats(const rawdtw_batch *batch, uint64_t *records_on_device, uint64_t *bytes_to_device, uint64_t *bytes_to_host)
+{
+    if (!batch) return RAWDTW_ERR_INVALID;
+    if (records_on_device) *records_on_device = batch->local_records;
+    if (bytes_to_device) *bytes_to_device = batch->link_up;
+    if (bytes_to_host) *bytes_to_host = batch->link_home;
     return RAWDTW_OK;
 }
 

@@ -67,6 +67,7 @@ int rawdtw_create(int device_ordinal, rawdtw_ctx **out)
     for (const auto &o : older) // (spellings from before RAWDTW_OPTS)
         if (const char *e = getenv(o[0])) (void)rawdtw_set_option(ctx, o[1], atoi(e));
     if (const char *e = getenv("RAWDTW_CHAIN_MAX_SEEDS")) ctx->chain_max_seeds = (uint32_t)std::max(1l, strtol(e, nullptr, 10));
+    if (const char *e = getenv("RAWDTW_LOCAL_JOBS")) ctx->local_jobs_device = strcmp(e, "host") != 0; // tests: "host" / "device" (rawdtw_batch.cpp, local batches)
     if (const char *e = getenv("RAWDTW_OPTS")) { // "name=value,name=value": rawdtw_set_option for each (tuning runs)
         std::string all(e);
         size_t pos = 0;
@@ -160,6 +161,21 @@ int rawdtw_get_option(const rawdtw_ctx *ctx, const char *name, int64_t *value)
     const opt::Row *r = opt::find(name);
     if (!r) return RAWDTW_ERR_INVALID;
     *value = r->load ? r->load(*ctx) : kComputed[r - opt::kRows - opt::kNumSettable](ctx);
+    return RAWDTW_OK;
+}
+
+// the opt-in of the local border constraint (include/rawdtw.h, "local border"): a setter, not a row of the option table
+int rawdtw_set_border_local(rawdtw_ctx *ctx, int on)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    ctx->border_local = on != 0;
+    return RAWDTW_OK;
+}
+
+int rawdtw_get_border_local(const rawdtw_ctx *ctx, int *on)
+{
+    if (!ctx || !on) return RAWDTW_ERR_INVALID;
+    *on = ctx->border_local ? 1 : 0;
     return RAWDTW_OK;
 }
 

@@ -135,6 +135,8 @@ struct rawdtw_ctx : rawdtw::Options { // (every option is a field of Options: ra
     struct rawdtw_round_end_ws *round_end_ws = nullptr; // rawdtw_round_end's device block (rawdtw_round_end.hip), grow-only
     struct rawdtw_keep_ws *keep_ws = nullptr;           // the store of kept chains and its launch's block (rawdtw_keep.hip), grow-only
     uint32_t chain_max_seeds = 0; // tests: RAWDTW_CHAIN_MAX_SEEDS lowers rawdtw_chain_round's cap on seeds a read, so that small rounds take the declined path (0: no)
+    bool border_local = false;      // rawdtw_set_border_local: border_constraint 2 is accepted by the batch entry points and rawdtw_mapper_create
+    bool local_jobs_device = true;  // a local batch from device arrays builds its job records on the device (k_local_jobs); tests: RAWDTW_LOCAL_JOBS=host
     std::string err;
 };
 
@@ -155,6 +157,8 @@ struct rawdtw_plan {
     uint32_t tile_lds_floats = 0, tile_hi_lds_floats = 0;
     FullAux *d_aux = nullptr;      // indexed like d_jobs (only meaningful for full-matrix jobs)
     float *d_cost = nullptr;
+    uint32_t *d_end_j = nullptr;   // semiglobal launches (a local batch's plan): the last row's first minimum, job order
+    uint64_t need_ev = 0, need_ref = 0; // ... and how far its windows reach into the arenas: checked again at every run (the arenas are the context's current ones)
     float *d_bnd = nullptr;
     uint8_t *d_dir = nullptr;
     uint64_t bnd_floats = 0, dir_bytes = 0;
@@ -238,6 +242,9 @@ struct rawdtw_batch {
     std::vector<rawdtw_anchor_t> host_anchors;
     std::vector<uint64_t> host_ref_base;
     std::vector<uint32_t> host_read_base;
+    // a batch from device arrays that is no device-planned one (rawdtw_batch_hand_over_stats): job records k_local_jobs wrote, and what the
+    // hand-over moved over the link -- offsets up and records home, or all anchors and bases home
+    uint64_t local_records = 0, link_up = 0, link_home = 0;
 };
 
 namespace rawdtw {
@@ -534,6 +541,15 @@ uint64_t count_cells(const rawdtw_plan *pl, uint64_t p0, uint64_t p1);
 MergeSel merge_of(const rawdtw_ctx *ctx, const rawdtw_plan *pl); // (merge_select, rawdtw_launches.h, under the context's settings)
 int run_all_launches(rawdtw_ctx *ctx, rawdtw_plan *pl, hipEvent_t *ev);
 void plan_release_device(rawdtw_plan *plan);
+// ---- rawdtw_semiglobal.cpp ----
+// A plan whose launches are semiglobal fills (kKindSemiWave), one class a launch: what a local batch owns in the planner's place.  Records,
+// aux and boundary rows on the device, costs in job order; run_all_launches runs it against the context's current arenas.
+int build_semi_plan(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, rawdtw_plan **out);
+// ---- rawdtw_local.hip ----
+// k_local_jobs: chain c's job record of a local batch from anchors[anchor_off[c + 1] - 1], anchors[anchor_off[c]], ref_base[c], read_base[c]
+// (all device arrays), written in chain order; an empty chain gets n = m = 0
+hipError_t launch_local_jobs(const uint64_t *anchor_off, const rawdtw_anchor_t *anchors, const uint64_t *ref_base, const uint32_t *read_base,
+                             uint64_t n_chains, rawdtw_job_t *jobs_out, hipStream_t s);
 // the tile records as downloaded from the device against the job list (rawdtw_batch_verify_plan): "" or what is wrong
 std::string verify_uploaded_tiles(const rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const rawdtw_plan *pl, const TileDesc *tiles,
                                   size_t n_tiles, const TileSpan *spans, size_t n_spans, const TileJob *tjobs, size_t n_tjobs, std::vector<uint8_t> &seen);

@@ -48,15 +48,29 @@ extern "C" {
 uint32_t rawdtw_chain_job_count(const rawdtw_align_opt_t *opt, uint32_t n_anchors)
 {
     if (!opt || n_anchors == 0) return 0;
-    return opt->border_constraint == 0 ? 1u : n_anchors - 1;
+    return opt->border_constraint == 1 ? n_anchors - 1 : 1u; // (global and local: one job a chain)
 }
 
 int rawdtw_chain_build_jobs(const rawdtw_align_opt_t *opt, const rawdtw_anchor_t *anchors, uint32_t n_anchors,
                             uint64_t ref_base, uint32_t read_base, int cigar, rawdtw_job_t *jobs_out)
 {
     if (!opt || !anchors || n_anchors == 0 || !jobs_out) return RAWDTW_ERR_INVALID;
-    if (opt->border_constraint != 0 && opt->border_constraint != 1)
+    if (opt->border_constraint != 0 && opt->border_constraint != 1 && opt->border_constraint != 2)
         return RAWDTW_ERR_INVALID; // rmap.cpp:301-304: "invalid border constraint" -> exit
+    if (opt->border_constraint == 2) {
+        // local (include/rawdtw.h, "local border"): the global branch's windows, one semiglobal job; dtw.hpp has no banded semiglobal, so
+        // fill_method and band_radius_frac are not looked at, with `cigar` or without
+        const rawdtw_anchor_t &s = anchors[n_anchors - 1], &e = anchors[0];
+        rawdtw_job_t &j = jobs_out[0];
+        j.ref_off = ref_base + s.target_position;
+        j.read_off = read_base + s.query_position;
+        j.m = e.target_position - s.target_position + 1;
+        j.n = e.query_position - s.query_position + 1;
+        j.band_radius = RAWDTW_FULL;
+        j.exclude_last = 0;
+        j.reserved = 0;
+        return RAWDTW_OK;
+    }
     const bool banded = opt->fill_method != 0;
     if (opt->border_constraint == 0) {
         const rawdtw_anchor_t &s = anchors[n_anchors - 1]; // chain start (rmap.cpp:195)
@@ -105,7 +119,7 @@ float rawdtw_chain_replay(const rawdtw_align_opt_t *opt, const rawdtw_anchor_t *
     uint32_t num_aligned = 0;
     const rawdtw_anchor_t &first = anchors[n_anchors - 1];
     const rawdtw_anchor_t &last = anchors[0];
-    if (opt->border_constraint == 0) {
+    if (opt->border_constraint != 1) { // (local takes the global branch: one cost, num_aligned = n)
         const uint32_t rn = last.query_position - first.query_position + 1;
         const float attainable = (float)rn * opt->match_bonus; // rmap.cpp:205
         if (attainable < min_score) return -1e10f;             // rmap.cpp:206-209

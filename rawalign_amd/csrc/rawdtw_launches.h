@@ -21,7 +21,8 @@ enum LaunchKind : uint32_t {
     kKindReadSelect = 7, // per-read accept/cut loop (gen_chains DTW block)
     kKindBandWreg = 8,   // wave-per-job banded kernel, band in registers (param = registers per lane per buffer)
     kKindBandLaneHi = 9, // tile kernel instance for the wider bands (radius 4..8)
-    kKindBandMerged = 10 // reporting only: the tile launch when it also carries the two small banded classes (k_band_merged)
+    kKindBandMerged = 10, // reporting only: the tile launch when it also carries the two small banded classes (k_band_merged)
+    kKindSemiWave = 11   // wave-per-job semiglobal fill of a local batch (param = rows per lane, + 256 for the pipelined-strip class)
 };
 
 struct Launch {

@@ -64,7 +64,10 @@ int rawdtw_mapper_create(rawdtw_ctx *ctx, const rawdtw_mapper_opt_t *opt, uint32
     if (!out) return RAWDTW_ERR_INVALID;
     *out = nullptr;
     if (!opt || (n_seq && (!seq_names || !seq_len)) || opt->slot_events == 0 || opt->max_reads == 0) return RAWDTW_ERR_INVALID;
-    if (opt->align.border_constraint != 0 && opt->align.border_constraint != 1) return RAWDTW_ERR_INVALID; // rmap.cpp:301-304
+    // rmap.cpp:301-304; 2 (local) where the context opted in (rawdtw_set_border_local) and on a scorer-only mapper, which scores nothing here
+    int local_on = 1;
+    if (ctx && rawdtw_get_border_local(ctx, &local_on) != RAWDTW_OK) return RAWDTW_ERR_INVALID;
+    if (opt->align.border_constraint != 0 && opt->align.border_constraint != 1 && !(opt->align.border_constraint == 2 && local_on)) return RAWDTW_ERR_INVALID;
     rawdtw_mapper *m = new (std::nothrow) rawdtw_mapper;
     if (!m) return RAWDTW_ERR_OOM;
     m->ctx = ctx; m->opt = *opt;
@@ -89,6 +92,7 @@ int rawdtw_mapper_create(rawdtw_ctx *ctx, const rawdtw_mapper_opt_t *opt, uint32
         if (st == RAWDTW_OK) { m->groups[1].own_ctx = true; st = rawdtw_share_reference(m->groups[1].ctx, ctx); }
         for (const char *name : {"chain_long_seeds", "chain_max_chains", "chain_decline_reads"}) // (both groups chain the same reads on the device)
             if (st == RAWDTW_OK) st = rawdtw_set_option(m->groups[1].ctx, name, ctx_option(ctx, name));
+        if (st == RAWDTW_OK) st = rawdtw_set_border_local(m->groups[1].ctx, local_on); // (... under the same border constraints)
     }
     const uint64_t per_group = ((uint64_t)opt->max_reads + (uint64_t)m->opt.groups - 1) / (uint64_t)m->opt.groups;
     for (Group &g : m->groups)
@@ -305,6 +309,8 @@ int rawdtw_mapper_finish(rawdtw_mapper *m)
     const bool arena = m->finish_from_arena;
     // the banded path (rawdtw_mapper_set_banded_cigar): the job the scoring built (radius max(1, (int)(n * frac))), walked as well
     const bool banded = m->banded_cigar && m->opt.align.border_constraint == 0 && m->opt.align.fill_method != 0;
+    // local (include/rawdtw.h, "local border"): the chain's one job through DTW_semiglobal_tb; the walk starts at (0, j0)
+    const bool local = m->opt.align.border_constraint == 2;
     if (arena)
         for (const MRead &rd : m->reads)
             if (rd.host_only && !rd.released && !rd.dropped && high_confidence(m, rd.chains))
@@ -339,9 +345,12 @@ int rawdtw_mapper_finish(rawdtw_mapper *m)
     std::vector<uint32_t> plen(nj_all);
     std::vector<uint8_t> step(poff[nj_all] + 1);
     std::vector<float> pd(poff[nj_all] + 1), cost(nj_all);
+    std::vector<uint32_t> j0(local ? nj_all : 0);
     if (nj_all) {
         if (!arena) m->arena_replaced = true;
-        const int st = banded ? rawdtw_banded_traceback_steps(m->ctx, jobs.data(), nj_all, arena ? nullptr : events.data(), events.size(), cost.data(),
+        const int st = local ? rawdtw_semiglobal_traceback_steps(m->ctx, jobs.data(), nj_all, arena ? nullptr : events.data(), events.size(), cost.data(),
+                                                                 j0.data(), poff.data(), plen.data(), step.data(), pd.data())
+                       : banded ? rawdtw_banded_traceback_steps(m->ctx, jobs.data(), nj_all, arena ? nullptr : events.data(), events.size(), cost.data(),
                                                               poff.data(), plen.data(), step.data(), pd.data())
                        : arena ? rawdtw_traceback_arena_steps(m->ctx, jobs.data(), nj_all, cost.data(), poff.data(), plen.data(), step.data(), pd.data())
                              : rawdtw_traceback_batch_steps(m->ctx, jobs.data(), nj_all, events.data(), events.size(), cost.data(), poff.data(), plen.data(), step.data(), pd.data());
@@ -360,14 +369,14 @@ int rawdtw_mapper_finish(rawdtw_mapper *m)
         for (uint32_t k = 0; k < nj; k++) {
             // sparse: every element offset by its part's start anchor (rmap.cpp:286-289); global: the offsets are added to
             // alignment.back() once per element (rmap.cpp:230-233), i.e. only the last tuple moves
-            const rawdtw_anchor_t &s0 = m->opt.align.border_constraint == 0 ? ch.anchors[na - 1] : ch.anchors[parts - k];
+            const rawdtw_anchor_t &s0 = m->opt.align.border_constraint != 1 ? ch.anchors[na - 1] : ch.anchors[parts - k];
             const uint64_t p0 = poff[it.job0 + k];
             const uint32_t len = plen[it.job0 + k];
-            unsigned long long pi = 0, pj = 0; // (i, j) from the steps: a global path starts at (0, 0)
+            unsigned long long pi = 0, pj = local ? j0[it.job0 + k] : 0u; // (i, j) from the steps: a global path starts at (0, 0), a local one at (0, j0)
             for (uint32_t q = 0; q < len; q++) {
                 pi += step[p0 + q] & 1u; pj += step[p0 + q] >> 1;
                 unsigned long long i = pi, j = pj;
-                if (m->opt.align.border_constraint != 0) { i += s0.query_position; j += s0.target_position; }
+                if (m->opt.align.border_constraint != 0) { i += s0.query_position; j += s0.target_position; } // (sparse, and local: the sparse branch's way)
                 else if (q + 1 == len) { i += (unsigned long long)len * s0.query_position; j += (unsigned long long)len * s0.target_position; }
                 snprintf(el, sizeof el, "(%llu,%llu,%g)", i, j, (double)pd[p0 + q]); // ostream << float == %g (rmap.cpp:580-592)
                 s += el;

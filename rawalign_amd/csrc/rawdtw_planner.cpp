@@ -2,6 +2,7 @@
 // stream path declines, the tests), its launch sequences, and the rawdtw_plan_* / rawdtw_score_batch entry points
 // (include/rawdtw.h).  Host code only; kernels live in rawdtw_kernels.hip.
 #include "rawdtw_capi.h"
+#include "rawdtw_semiglobal.h" // (launch_semi_wave: the launches of a local batch's plan)
 
 using namespace rawdtw;
 using namespace rawdtw::capi;
@@ -674,6 +675,12 @@ int run_launch(rawdtw_ctx *ctx, rawdtw_plan *pl, const Launch &L, hipStream_t st
         e = launch_full_wave(L.param, L.kind == kKindFullTb, jobs, L.count, aux, ctx->d_ev,
                              ctx->d_ref, out, pl->d_bnd, pl->d_dir, stream);
         break;
+    case kKindSemiWave: // (a local batch's plan: build_semi_plan; param = rows a lane, + 256 for class 4)
+        if (!ctx->d_ev || !ctx->d_ref || ctx->n_ev < pl->need_ev || ctx->n_ref < pl->need_ref)
+            return fail(ctx, RAWDTW_ERR_INVALID, "an arena shrank after the batch was created: create the batch again");
+        e = launch_semi_wave(L.param >= 256 ? 4 : L.param == 8 ? 3 : L.param == 4 ? 2 : L.param == 2 ? 1 : 0, false, jobs, L.count, aux, ctx->d_ev, ctx->d_ref, out,
+                             pl->d_end_j, pl->d_bnd, nullptr, stream);
+        break;
     default:
         return fail(ctx, RAWDTW_ERR_INVALID, "unknown launch kind");
     }
@@ -851,7 +858,7 @@ void plan_release_device(rawdtw_plan *plan)
 {
     auto drop = [](auto *&p) { if (p) (void)hipFree(p); p = nullptr; };
     drop(plan->d_jobs); drop(plan->d_aux); drop(plan->d_tiles); drop(plan->d_spans); drop(plan->d_tjobs);
-    drop(plan->d_masks); drop(plan->d_cost); drop(plan->d_bnd);
+    drop(plan->d_masks); drop(plan->d_cost); drop(plan->d_bnd); drop(plan->d_end_j);
     if (plan->d_dir && !plan->dir_borrowed) (void)hipFree(plan->d_dir);
     plan->d_dir = nullptr;
 }

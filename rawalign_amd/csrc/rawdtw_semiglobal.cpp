@@ -248,6 +248,59 @@ int semi_traceback(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, c
 
 } // namespace
 
+// semi_plan and semi_fill in the form a batch owns (rawdtw_capi.h): the cost form's plan laid into a rawdtw_plan, so that a local batch is a
+// job-list batch in everything but its launches -- run, timed runs, launch statistics, fetch and the fold read the plan as they read the
+// planner's.  Refusals as rawdtw_semiglobal_batch's, before anything is enqueued.
+namespace rawdtw { namespace capi {
+int build_semi_plan(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, rawdtw_plan **out)
+{
+    *out = nullptr;
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (n_jobs > 0 && !jobs) return fail(ctx, RAWDTW_ERR_INVALID, "jobs is NULL");
+    if (n_jobs >= 0x7fffffffull) return fail(ctx, RAWDTW_ERR_INVALID, "too many jobs for one call");
+    int st = n_jobs ? semi_check(ctx, jobs, n_jobs, true, 0) : RAWDTW_OK;
+    if (st != RAWDTW_OK) return st;
+    rawdtw_plan *pl = new (std::nothrow) rawdtw_plan;
+    if (!pl) return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed");
+    pl->ctx = ctx;
+    SemiPlan sp;
+    try {
+        semi_plan(ctx, jobs, n_jobs, SemiForm::Cost, sp);
+        pl->order.resize(n_jobs); pl->h_jobs.resize(n_jobs);
+        pl->h_aux = sp.aux;
+        pl->run_order.resize(sp.launches.size());
+    } catch (const std::bad_alloc &) { delete pl; return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed"); }
+    pl->n_jobs = n_jobs;
+    pl->bnd_floats = sp.bnd_floats;
+    for (uint64_t p = 0; p < n_jobs; p++) {
+        pl->order[p] = sp.order[p]; pl->h_jobs[p] = sp.jobs[p];
+        pl->need_ev = std::max<uint64_t>(pl->need_ev, (uint64_t)sp.jobs[p].read_off + sp.jobs[p].n);
+        pl->need_ref = std::max<uint64_t>(pl->need_ref, sp.jobs[p].ref_off + sp.jobs[p].m);
+        pl->info.algorithmic_bytes += 4ull * ((uint64_t)sp.jobs[p].n + sp.jobs[p].m) + 4 + 32;
+    }
+    for (const SemiLaunch &L : sp.launches) // (class order is longest last: the launches run in that order, as semi_fill's)
+        pl->launches.push_back(Launch{kKindSemiWave, L.cls == 4 ? 8 + 256 : semi_rpl(L.cls), L.first, L.count});
+    for (uint32_t i = 0; i < pl->run_order.size(); i++) pl->run_order[i] = i;
+    pl->info.n_jobs = n_jobs; pl->info.n_full_jobs = n_jobs; pl->info.n_launches = (uint32_t)pl->launches.size();
+    pl->info.workspace_bytes = n_jobs * (sizeof(DevJob) + sizeof(FullAux) + 8) + sp.bnd_floats * 4;
+    ctx->live_plans.push_back(pl);
+    if ((st = dev_alloc(ctx, &pl->d_jobs, n_jobs)) != RAWDTW_OK || (st = dev_alloc(ctx, &pl->d_aux, n_jobs)) != RAWDTW_OK ||
+        (st = dev_alloc(ctx, &pl->d_cost, n_jobs)) != RAWDTW_OK || (st = dev_alloc(ctx, &pl->d_end_j, n_jobs)) != RAWDTW_OK ||
+        (st = dev_alloc(ctx, &pl->d_bnd, pl->bnd_floats)) != RAWDTW_OK) {
+        rawdtw_plan_destroy(pl);
+        return st;
+    }
+    if (n_jobs) {
+        hipError_t e = hipMemcpyAsync(pl->d_jobs, pl->h_jobs.data(), n_jobs * sizeof(DevJob), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(pl->d_aux, pl->h_aux.data(), n_jobs * sizeof(FullAux), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) { rawdtw_plan_destroy(pl); return hip_fail(ctx, e, "uploading job descriptors"); }
+    }
+    *out = pl;
+    return RAWDTW_OK;
+}
+} } // namespace rawdtw::capi
+
 extern "C" {
 
 int rawdtw_semiglobal_batch(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events, uint64_t n_events,

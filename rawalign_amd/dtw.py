@@ -238,7 +238,7 @@ class Engine:
     """One rawdtw_ctx (one HIP device, one stream)."""
 
     KIND_NAMES = {1: "band_lane", 2: "band_wave_lds", 3: "full_wave", 4: "full_tb", 5: "tb_walk", 6: "chain_fold",
-                  7: "read_select", 8: "band_wreg", 9: "band_lane_hi", 10: "band_merged"}
+                  7: "read_select", 8: "band_wreg", 9: "band_lane_hi", 10: "band_merged", 11: "semi_wave"}
 
     def __init__(self, device: int = 0):
         self.lib = load_library()
@@ -277,6 +277,16 @@ class Engine:
 
     def set_option(self, name: str, value: int):
         self._check(self.lib.rawdtw_set_option(self._ctx, name.encode(), int(value)))
+
+    def set_border_local(self, on: bool = True):
+        """rawdtw_set_border_local: the batch entry points and rawdtw_mapper_create on this context accept border constraint 2 (local:
+        include/rawdtw.h, "local border").  A setter, not an option; off by default."""
+        self._check(self.lib.rawdtw_set_border_local(self._ctx, int(bool(on))))
+
+    def get_border_local(self) -> bool:
+        v = C.c_int()
+        self._check(self.lib.rawdtw_get_border_local(self._ctx, C.byref(v)))
+        return bool(v.value)
 
     def get_option(self, name: str) -> int:
         """rawdtw_get_option: any option of include/rawdtw.h's option block -- a settable one as it is stored (what set_option made of its
