@@ -306,6 +306,54 @@ int rawdtw_traceback_arena_steps(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint
 int rawdtw_traceback_timing(const rawdtw_ctx *ctx, float *fill_ms, float *walk_ms, uint64_t *direction_bytes,
                             uint64_t *path_elements);
 
+/* ---- aln text: the aln:s: string of paths (dtwresult_to_string, rmap.cpp:580-592), defined once and made on the device.
+ * Element q of job k is (i, j, d).  (pi, pj) starts at (0, j0) and advances by bits 0 and 1 of the element's step byte before the
+ * element is read (element 0's step byte is 0).  mode 1 (the sparse and the local way, rmap.cpp:286-289): i = pi + off_i,
+ * j = pj + off_j on every element.  mode 0 (the global branch's quirk, rmap.cpp:230-233): only the job's last element moves, by
+ * len * off_i and len * off_j, len the job's element count; the arithmetic is unsigned 64-bit and wraps.  The element's text is
+ *     "(" i "," j "," g ")"     i, j in decimal, g the bytes of snprintf("%g", (double)d) under the C locale (= ostream << float)
+ * for EVERY bit pattern of d (0, -0, inf, -inf, nan, -nan, denormals; nothing is declined).  Jobs' texts are packed in job order with
+ * no separator and no terminating NUL: job k occupies text[text_off[k] .. text_off[k + 1]), text_off has n_jobs + 1 entries, a job of
+ * 0 elements occupies nothing.  rawalign_amd/csrc/rawdtw_fmt_g.h is the one formatter behind all of the entry points below. ---- */
+typedef struct {
+    uint64_t off_i, off_j;
+    uint32_t j0;
+    uint32_t mode; /* 0 or 1 */
+    uint64_t pad;  /* not read */
+} rawdtw_aln_rec_t; /* 32 bytes */
+
+/* The definition restated on host threads (threads 0: as many as the machine has, at most 16); needs no GPU.  Job k's path is the
+ * path_len[k] step bytes and distances from path_off[k] on (the layout of rawdtw_traceback_batch_steps).  text_off (n_jobs + 1
+ * entries) and *text_bytes are always written; text == NULL: sizes only.  RAWDTW_ERR_RANGE when text_cap is below *text_bytes: text is
+ * not written at all.  RAWDTW_ERR_INVALID for a null argument or a mode other than 0 and 1. */
+int rawdtw_aln_text_host(const uint8_t *path_step, const float *path_d, const uint64_t *path_off, const uint32_t *path_len,
+                         const rawdtw_aln_rec_t *recs, uint64_t n_jobs, int threads, uint64_t *text_off, char *text,
+                         uint64_t text_cap, uint64_t *text_bytes);
+/* An upper bound on the text of these jobs' paths whatever the paths are: n + m - 1 elements a job, the digits of the largest i and j
+ * an element of that job can have, 12 bytes for the distance, 4 of punctuation.  A buffer of this size is never too small. */
+uint64_t rawdtw_aln_text_bound(const rawdtw_job_t *jobs, const rawdtw_aln_rec_t *recs, uint64_t n_jobs);
+/* The same contract as rawdtw_aln_text_host on the device, from host arrays: upload, k_aln_count, k_aln_scan, k_aln_write, text
+ * home.  The kernels alone; statuses as the host form, and RAWDTW_ERR_OOM / RAWDTW_ERR_DEVICE. */
+int rawdtw_aln_text_steps(rawdtw_ctx *ctx, const uint8_t *path_step, const float *path_d, const uint64_t *path_off,
+                          const uint32_t *path_len, const rawdtw_aln_rec_t *recs, uint64_t n_jobs, uint64_t *text_off, char *text,
+                          uint64_t text_cap, uint64_t *text_bytes);
+/* rawdtw_traceback_batch_steps / rawdtw_traceback_arena_steps whose paths never leave the device: the jobs, events, arena, refusals,
+ * statuses and sub-batches ("tb_workspace_mb") of those, and one rec a job.  What comes home a sub-batch is its costs and lengths,
+ * 8 bytes a job of text offsets, and the text, behind the walk.  path_len[k] is the path's element count after exclude_last dropped
+ * its last element -- the text is made of those elements, and under mode 0 len is that count.  The text does not depend on how the
+ * batch was cut.  text == NULL: sizes only.  RAWDTW_ERR_RANGE, with out_cost, path_len, text_off and *text_bytes filled, when text_cap
+ * is below *text_bytes; a text buffer of rawdtw_aln_text_bound bytes never is.  A null recs, text_off or text_bytes is refused as a
+ * null argument of the steps form is. */
+int rawdtw_traceback_batch_text(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events, uint64_t n_events,
+                                const rawdtw_aln_rec_t *recs, float *out_cost, uint32_t *path_len, uint64_t *text_off, char *text,
+                                uint64_t text_cap, uint64_t *text_bytes);
+int rawdtw_traceback_arena_text(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const rawdtw_aln_rec_t *recs,
+                                float *out_cost, uint32_t *path_len, uint64_t *text_off, char *text, uint64_t text_cap,
+                                uint64_t *text_bytes);
+/* Device time of the text launches of the most recent of the three calls above on this context (HIP events, summed over
+ * sub-batches): count_ms = k_aln_count and k_aln_scan, write_ms = k_aln_write; text_bytes = the text they made. */
+int rawdtw_aln_text_timing(const rawdtw_ctx *ctx, float *count_ms, float *write_ms, uint64_t *text_bytes);
+
 /* ---- single-call drop-ins with the reference's own signatures flattened
  * (dtw.hpp:21,25,28).  Host pointers; convenient, not fast. ---- */
 int rawdtw_dtw_global(rawdtw_ctx *ctx, const float *a, uint32_t n, const float *b, uint32_t m,
@@ -995,6 +1043,13 @@ int rawdtw_mapper_finish(rawdtw_mapper *m);
  * aln:s: with the global mode's quirk as the full-matrix branch does; a job without a path gives an empty aln:s:.  Sparse and
  * full-matrix mappers are untouched by it.  A setter, not a context option: the option table stays as recorded. */
 int rawdtw_mapper_set_banded_cigar(rawdtw_mapper *m, int on);
+/* aln:s: made on the device ("aln text" above).  Off (the default): rawdtw_mapper_finish is what it was.  On: where the finish takes
+ * the full-matrix traceback (global + full, and sparse; from the host's events or, under "signal_cigar", from the arena) it builds one
+ * rec a job -- a sparse part mode 1 with its part's start anchor, a global chain mode 0 with the chain's start anchor --, calls
+ * rawdtw_traceback_batch_text / _arena_text with rawdtw_aln_text_bound bytes of room and hands every read its stretch of the text;
+ * alns:f: comes from the costs as before.  The tags are byte for byte those of the setter off.  The banded finish
+ * (rawdtw_mapper_set_banded_cigar) and the local finish keep the host formatter whatever this says. */
+int rawdtw_mapper_set_device_text(rawdtw_mapper *m, int on);
 /* *len = the line's length; RAWDTW_ERR_RANGE when buf (cap bytes) is too small for it and its terminator.  With flag 0x20 a
  * mapped line ends in anchors:s: (rmap.cpp:745-747).  A read sequence-until dropped has no line: *len = 0, "". */
 int rawdtw_mapper_paf(const rawdtw_mapper *m, uint32_t read_id, char *buf, uint32_t cap, uint32_t *len);

@@ -209,6 +209,13 @@ SYMBOLS = {
     "rawdtw_dtw_global_banded_tb": (I32, [VP, VP, U32, VP, U32, I32, I32, C.POINTER(F32), C.POINTER(U32), VP, VP, VP]),
     "rawdtw_banded_tb_host": (I32, [VP, U32, VP, U32, I32, I32, C.POINTER(F32), C.POINTER(U32), VP, VP, VP]),
     "rawdtw_mapper_set_banded_cigar": (I32, [VP, I32]),
+    "rawdtw_mapper_set_device_text": (I32, [VP, I32]),
+    "rawdtw_aln_text_host": (I32, [VP, VP, VP, VP, VP, U64, I32, VP, VP, U64, C.POINTER(U64)]),
+    "rawdtw_aln_text_bound": (U64, [VP, VP, U64]),
+    "rawdtw_aln_text_steps": (I32, [VP, VP, VP, VP, VP, VP, U64, VP, VP, U64, C.POINTER(U64)]),
+    "rawdtw_traceback_batch_text": (I32, [VP, VP, U64, VP, U64, VP, VP, VP, VP, VP, U64, C.POINTER(U64)]),
+    "rawdtw_traceback_arena_text": (I32, [VP, VP, U64, VP, VP, VP, VP, VP, U64, C.POINTER(U64)]),
+    "rawdtw_aln_text_timing": (I32, [VP, C.POINTER(F32), C.POINTER(F32), C.POINTER(U64)]),
     "rawdtw_set_border_local": (I32, [VP, I32]),
     "rawdtw_get_border_local": (I32, [VP, VP]),
     "rawdtw_batch_hand_over_stats": (I32, [VP, VP, VP, VP]),

@@ -128,6 +128,8 @@ int rawdtw_destroy(rawdtw_ctx *ctx)
     if (ctx->tb_copy) (void)hipStreamDestroy(ctx->tb_copy);
     if (ctx->d_tb_dir) (void)hipFree(ctx->d_tb_dir);
     if (ctx->d_tb_paths) (void)hipFree(ctx->d_tb_paths);
+    if (ctx->tb_text) (void)hipStreamDestroy(ctx->tb_text);
+    if (ctx->d_tb_text) (void)hipFree(ctx->d_tb_text);
     delete ctx;
     return RAWDTW_OK;
 }

@@ -96,6 +96,13 @@ struct rawdtw_ctx : rawdtw::Options { // (every option is a field of Options: ra
     hipStream_t tb_copy = nullptr;                      // traceback: the paths' way home, beside the next sub-batch's kernels
     float tb_fill_ms = 0.f, tb_walk_ms = 0.f;          // device time of the most recent rawdtw_traceback_batch
     uint64_t tb_dir_written = 0, tb_path_elems = 0;
+    // the aln text (rawdtw_aln_text.hip): a traceback's text form keeps its records, totals, offsets and the text itself here, two slots, grow-only;
+    // the text goes home on a stream of its own (tb_copy already holds the next sub-batch's copies when a sub-batch's total is known)
+    void *d_tb_text = nullptr;
+    size_t tb_text_bytes = 0;
+    hipStream_t tb_text = nullptr;
+    float aln_count_ms = 0.f, aln_write_ms = 0.f;      // device time of the most recent text call's launches (rawdtw_aln_text_timing)
+    uint64_t aln_text_bytes = 0;
     uint64_t tb_sub_batches = 0;  // "tb_sub_batches" (read-only): sub-batches of the most recent traceback call, known before its first plan is built
     float semi_fill_ms = 0.f, semi_walk_ms = 0.f;      // device time of the most recent semiglobal call (rawdtw_semiglobal.cpp)
     uint64_t semi_dir_written = 0, semi_path_elems = 0;

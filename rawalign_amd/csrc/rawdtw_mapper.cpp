@@ -6,6 +6,7 @@
 // rawalign_amd/mapper.py is the Python mirror of the control flow; tests/test_mapper.py and tests/test_abi_shim.py compare the two and
 // the oracle-scored flow line by line.  Pure host code above the C ABI: no kernel is launched from here directly.
 #include <cmath>
+#include <memory>
 #include <new>
 
 #include "rawdtw_mapper_state.h"
@@ -294,6 +295,15 @@ int rawdtw_mapper_set_banded_cigar(rawdtw_mapper *m, int on)
     return RAWDTW_OK;
 }
 
+// aln:s: from the device (include/rawdtw.h, "aln text").  Off by default: the finish below is then what it was.  The banded and the local
+// finish have traceback units of their own and keep the host formatter whatever this says.
+int rawdtw_mapper_set_device_text(rawdtw_mapper *m, int on)
+{
+    if (!m) return RAWDTW_ERR_INVALID;
+    m->device_text = on != 0;
+    return RAWDTW_OK;
+}
+
 // --dtw-output-cigar (rmap.cpp:715-717): the best chain of every mapped read through DTW_global_tb once more, its path as the
 // aln:s: string with the reference's two quirks (rmap.cpp:230-233, 283-289).  All reads' jobs go to the device in ONE call;
 // the paths come back as steps and distances (rawdtw_traceback_batch_steps: 5 bytes an element) and every read's string is
@@ -340,6 +350,44 @@ int rawdtw_mapper_finish(rawdtw_mapper *m)
     }
     if (items.empty()) return RAWDTW_OK;
     const uint64_t nj_all = jobs.size();
+    if (m->device_text && !local && !banded && nj_all) {
+        // rawdtw_mapper_set_device_text: the same jobs through the traceback's text form (include/rawdtw.h, "aln text").  One rec a job says what
+        // the loop below says per element: a sparse part's elements all move by its part's start anchor (mode 1), a global chain's last element
+        // moves by len times the chain's start anchor (mode 0).  The jobs of a read are consecutive, so its aln:s: is one stretch of the text.
+        std::vector<rawdtw_aln_rec_t> recs(nj_all);
+        for (const Item &it : items) {
+            const MChain &ch = m->reads[it.read].chains[0];
+            const uint32_t na = (uint32_t)ch.anchors.size(), parts = na - 1;
+            const bool sparse = m->opt.align.border_constraint != 0;
+            for (uint32_t k = 0; k < it.nj; k++) {
+                const rawdtw_anchor_t &s0 = sparse ? ch.anchors[parts - k] : ch.anchors[na - 1];
+                recs[it.job0 + k] = rawdtw_aln_rec_t{s0.query_position, s0.target_position, 0u, sparse ? 1u : 0u, 0};
+            }
+        }
+        const uint64_t cap = rawdtw_aln_text_bound(jobs.data(), recs.data(), nj_all);
+        std::vector<uint64_t> toff(nj_all + 1, 0);
+        std::vector<uint32_t> plen(nj_all);
+        std::vector<float> cost(nj_all);
+        std::unique_ptr<char[]> text(new (std::nothrow) char[cap + 1]); // (not value-initialised: the bound is a few times the text)
+        if (!text) return fail(m, RAWDTW_ERR_OOM, "no memory for the aln:s: text");
+        uint64_t bytes = 0;
+        if (!arena) m->arena_replaced = true;
+        const int st = arena ? rawdtw_traceback_arena_text(m->ctx, jobs.data(), nj_all, recs.data(), cost.data(), plen.data(), toff.data(), text.get(), cap, &bytes)
+                             : rawdtw_traceback_batch_text(m->ctx, jobs.data(), nj_all, events.data(), events.size(), recs.data(), cost.data(), plen.data(),
+                                                           toff.data(), text.get(), cap, &bytes);
+        if (st != RAWDTW_OK) return fail(m, st, rawdtw_last_error(m->ctx));
+        std::vector<std::string> logs(items.size());
+        m->pool->run(items.size(), 4, [&](size_t x) {
+            const Item &it = items[x];
+            MChain &ch = m->reads[it.read].chains[0];
+            ch.alignment_score = rawdtw_chain_replay(&m->opt.align, ch.anchors.data(), (uint32_t)ch.anchors.size(), cost.data() + it.job0, -1e10f); // rmap.cpp:306 on the summed costs
+            ch.aln.assign(text.get() + toff[it.job0], toff[it.job0 + it.nj] - toff[it.job0]);
+            ch.has_aln = true;
+            if (m->opt.flag & 0x8) logs[x] = log_scores_line(ch.chaining_score, ch.alignment_score);
+        });
+        for (const std::string &l : logs) m->log += l; // (read order)
+        return RAWDTW_OK;
+    }
     std::vector<uint64_t> poff(nj_all + 1, 0);
     for (uint64_t k = 0; k < nj_all; k++) poff[k + 1] = poff[k] + jobs[k].n + jobs[k].m - 1;
     std::vector<uint32_t> plen(nj_all);

@@ -220,7 +220,8 @@ struct rawdtw_mapper {
     bool arena_replaced = false;    // rawdtw_mapper_finish has uploaded the host's copies over the event arena: no slot holds its read's events any more
     bool finish_from_arena = false; // "signal_cigar": a --dtw-output-cigar mapper has committed a round from signal -- the host's copy of a read's
                                     // events is incomplete from then on, and rawdtw_mapper_finish reads every read's events in its slot of the arena
-    bool banded_cigar = false;      // rawdtw_mapper_set_banded_cigar: a global + banded --dtw-output-cigar mapper finishes through the banded traceback
+    bool device_text = false;       // rawdtw_mapper_set_device_text: the full-matrix finish gets aln:s: as text from the device (include/rawdtw.h, "aln text")
+    bool banded_cigar = false;     // rawdtw_mapper_set_banded_cigar: a global + banded --dtw-output-cigar mapper finishes through the banded traceback
 };
 
 namespace rawdtw_map {

@@ -1,5 +1,6 @@
 // rawdtw_traceback.cpp -- DTW_global_tb for batches (rawdtw_traceback_batch*: dtw.hpp:28 at rmap.cpp:221,284) and the
 // single-call drop-ins with the reference's own signatures (dtw.hpp:21,25,28).  Host code only.
+#include "rawdtw_aln_text.h"
 #include "rawdtw_capi.h"
 
 using namespace rawdtw;
@@ -17,12 +18,28 @@ extern "C" {
 // for 8 080 paths in five launches each.)
 // `arena`: the jobs' read_off index the context's event arena as it lies (rawdtw_traceback_arena_steps) -- nothing is uploaded and
 // h_events / n_events are not looked at; else the arena is replaced by h_events first.  That is the one difference.
+// `tx`: the text form (include/rawdtw.h, "aln text"; rawdtw_traceback_batch_text / _arena_text).  Steps and distances stay on the device: behind a
+// sub-batch's walk go k_aln_count, k_aln_scan and k_aln_write (rawdtw_aln_text.hip), the text into a block sized by rawdtw_aln_text_bound -- so
+// the write needs no word from the host --, and what comes home with the costs and lengths is 8 bytes a job of text offsets.  The text
+// itself is copied once those have landed and say how long it is, straight to its final place, on a stream of its own beside the next
+// sub-batch's fill.  Sub-batches hold whole jobs in job order, so a sub-batch's text is one stretch behind the one before it.
+struct TextOut {
+    const rawdtw_aln_rec_t *recs;
+    uint64_t *text_off;
+    char *text;
+    uint64_t cap;
+    uint64_t *bytes;
+};
 static int traceback_core(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, bool arena, const float *h_events,
                           uint64_t n_events, float *out_cost, const uint64_t *path_off, uint32_t *path_len,
-                          uint32_t *path_i, uint32_t *path_j, uint8_t *path_step, float *path_d)
+                          uint32_t *path_i, uint32_t *path_j, uint8_t *path_step, float *path_d, const TextOut *tx = nullptr)
 {
     if (!ctx) return RAWDTW_ERR_INVALID;
-    if (n_jobs && (!jobs || !out_cost || !path_off || !path_len || !path_d || (!path_step && (!path_i || !path_j))))
+    if (tx) {
+        if (!tx->text_off || !tx->bytes || (n_jobs && (!jobs || !out_cost || !path_len || !tx->recs))) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
+        for (uint64_t k = 0; k < n_jobs; k++)
+            if (tx->recs[k].mode > 1) return fail(ctx, RAWDTW_ERR_INVALID, "a rec's mode is neither 0 nor 1");
+    } else if (n_jobs && (!jobs || !out_cost || !path_off || !path_len || !path_d || (!path_step && (!path_i || !path_j))))
         return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
     if (arena) { // (before anything is enqueued)
         if (!ctx->d_ev) return fail(ctx, RAWDTW_ERR_INVALID, "the context has no event arena");
@@ -42,6 +59,8 @@ static int traceback_core(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_
     lap("events H2D");
     for (hipEvent_t &e : ctx->tb_ev) if (!e) HIP_TRY(ctx, hipEventCreate(&e));
     if (!ctx->tb_copy) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->tb_copy, hipStreamNonBlocking));
+    if (tx && !ctx->tb_text) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->tb_text, hipStreamNonBlocking));
+    if (tx) { ctx->aln_count_ms = ctx->aln_write_ms = 0.f; ctx->aln_text_bytes = 0; }
     ctx->tb_fill_ms = ctx->tb_walk_ms = 0.f; ctx->tb_dir_written = 0; ctx->tb_path_elems = 0;
 
     uint64_t budget = 16ull << 30;
@@ -54,7 +73,10 @@ static int traceback_core(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_
         rawdtw_plan *pl = nullptr;
         uint64_t begin = 0, cnt = 0, acc = 0;
         std::vector<uint64_t> poff;
-        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // fill start, fill end, walk end, download end
+        hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // fill start, fill end, walk end, download end; text form: count + scan end, write end
+        std::vector<AlnDevRec> hrec; // text form: the paths' records, plan order; where the slot's text block keeps them, the totals, the offsets and the text
+        uint64_t text_bound = 0;
+        AlnDevRec *d_rec = nullptr; uint64_t *d_tot = nullptr, *d_toff = nullptr; char *d_text = nullptr;
         int slot = 0;
         bool in_flight = false;
         bool dense = false;   // steps form, and the caller's offsets of these jobs are one dense ascending stretch: the device writes the paths
@@ -74,13 +96,16 @@ static int traceback_core(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_
         {
             (void)hipStreamSynchronize(c->stream);
             if (c->tb_copy) (void)hipStreamSynchronize(c->tb_copy);
+            if (c->tb_text) (void)hipStreamSynchronize(c->tb_text);
             for (Sub &sb : v) { if (sb.pl) rawdtw_plan_destroy(sb.pl); for (hipEvent_t &e : sb.ev) if (e) (void)hipEventDestroy(e); }
         }
     } guard{subs, ctx};
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     // per slot: device path buffers {offsets, lengths, i/j end-first, distances, steps} and the pinned landing zone {distances, steps, costs, lengths}
     auto dev_need = [&](uint64_t cnt, uint64_t acc) { return al(cnt * 8) + al(cnt * 4) + 3 * al((size_t)acc * 4) + al((size_t)acc); };
-    auto host_need = [&](uint64_t cnt, uint64_t acc) { return al((size_t)acc * 4) + al((size_t)acc) + 2 * al(cnt * 4); };
+    auto hacc = [&](uint64_t acc) { return tx ? (size_t)0 : (size_t)acc; }; // (the text form lands no path in the pinned zone)
+    auto host_need = [&](uint64_t cnt, uint64_t acc) { return al(hacc(acc) * 4) + al(hacc(acc)) + 2 * al(cnt * 4) + (tx ? al((cnt + 1) * 8) : 0); };
+    auto text_need = [&](uint64_t cnt, uint64_t bound) { return al(cnt * sizeof(AlnDevRec)) + al(cnt * 8) + al((cnt + 1) * 8) + al((size_t)bound + 16); };
 
     // the split: a job joins the current sub-batch unless that passes the budget (a job over the budget goes alone)
     for (uint64_t begin = 0; begin < n_jobs;) {
@@ -98,7 +123,7 @@ static int traceback_core(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_
     }
     ctx->tb_sub_batches = subs.size();
     // ---- all sub-batches planned first (host planner, device allocations, job records' upload: while nothing is in flight) ----
-    size_t dn = 0, hn = 0;
+    size_t dn = 0, hn = 0, tn = 0;
     for (Sub &sb : subs) {
         const uint64_t begin = sb.begin, end = sb.begin + sb.cnt;
         st = build_plan(ctx, jobs + begin, sb.cnt, true, &sb.pl);
@@ -117,6 +142,15 @@ static int traceback_core(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_
             for (uint64_t p = 0; p < sb.cnt; p++) { sb.poff[p] = acc; acc += (uint64_t)sb.pl->h_jobs[p].n + sb.pl->h_jobs[p].m - 1; }
         sb.acc = acc;
         dn = std::max(dn, dev_need(sb.cnt, acc)); hn = std::max(hn, host_need(sb.cnt, acc));
+        if (tx) {
+            sb.hrec.resize(sb.cnt);
+            for (uint64_t p = 0; p < sb.cnt; p++) {
+                const uint64_t k = begin + sb.pl->order[p];
+                sb.hrec[p] = aln_dev_rec(tx->recs[k], jobs[k].exclude_last != 0, sb.pl->order[p]);
+            }
+            sb.text_bound = rawdtw_aln_text_bound(jobs + begin, tx->recs + begin, sb.cnt);
+            tn = std::max(tn, text_need(sb.cnt, sb.text_bound));
+        }
     }
     for (Sub &sb : subs) sb.pl->d_dir = ctx->d_tb_dir; // (the context's direction workspace may have grown while the later ones were planned)
     // grow-only buffers of the context, two slots each
@@ -127,6 +161,13 @@ static int traceback_core(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_
         if (hipMalloc(&ctx->d_tb_paths, want) != hipSuccess) return fail(ctx, RAWDTW_ERR_OOM, "path buffer allocation failed");
         ctx->tb_paths_bytes = want;
     }
+    if (ctx->tb_text_bytes < 2 * tn) {
+        if (ctx->d_tb_text) (void)hipFree(ctx->d_tb_text);
+        ctx->d_tb_text = nullptr; ctx->tb_text_bytes = 0;
+        const size_t want = 2 * (tn + tn / 8);
+        if (hipMalloc(&ctx->d_tb_text, want) != hipSuccess) return fail(ctx, RAWDTW_ERR_OOM, "text buffer allocation failed");
+        ctx->tb_text_bytes = want;
+    }
     if (ctx->pinned_bytes < 2 * hn) {
         if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
         ctx->h_pinned = nullptr; ctx->pinned_bytes = 0;
@@ -136,6 +177,8 @@ static int traceback_core(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_
     }
     lap("plans + alloc");
 
+    uint64_t text_base = 0;  // text form: the bytes of the sub-batches finished so far
+    bool text_short = false; // ... and one of them did not fit text_cap: sizes are still filled, no more text is copied
     // the second half of a sub-batch: wait for its download, write the caller's arrays
     auto finish = [&](Sub &sb) -> int {
         if (!sb.in_flight) return RAWDTW_OK;
@@ -150,8 +193,8 @@ static int traceback_core(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_
         const char *hp = static_cast<const char *>(ctx->h_pinned) + (size_t)sb.slot * (ctx->pinned_bytes / 2);
         const float *h_pd = reinterpret_cast<const float *>(hp);
         const uint8_t *h_mv = reinterpret_cast<const uint8_t *>(hp + al((size_t)sb.acc * 4));
-        const float *h_cost = reinterpret_cast<const float *>(hp + al((size_t)sb.acc * 4) + al((size_t)sb.acc));
-        const uint32_t *h_plen = reinterpret_cast<const uint32_t *>(hp + al((size_t)sb.acc * 4) + al((size_t)sb.acc) + al(sb.cnt * 4));
+        const float *h_cost = reinterpret_cast<const float *>(hp + al(hacc(sb.acc) * 4) + al(hacc(sb.acc)));
+        const uint32_t *h_plen = reinterpret_cast<const uint32_t *>(hp + al(hacc(sb.acc) * 4) + al(hacc(sb.acc)) + al(sb.cnt * 4));
         // into the caller's arrays (pageable memory: spread over a few threads); (i, j) from the steps
         int T = ctx->plan_threads > 0 ? ctx->plan_threads : (int)std::min<uint64_t>(std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 8u), sb.acc / (1u << 20) + 1);
         T = std::max(1, std::min(T, 16));
@@ -165,16 +208,16 @@ static int traceback_core(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_
                 // device paths are start-first already (k_tb_finish, dtw.cpp:656-657); the reference pops the last
                 // element when exclude_last_element is set (dtw.cpp:659-663)
                 const uint32_t outlen = jobs[k].exclude_last ? len - 1 : len;
-                const uint64_t src = sb.poff[p], dst = path_off[k];
+                const uint64_t src = sb.poff[p], dst = tx ? 0 : path_off[k];
                 const uint8_t *mv = h_mv + src;
-                if (sb.dense) { /* (the stretch is copied whole below, or came home in place) */ }
+                if (sb.dense || tx) { /* (the stretch is copied whole below, or came home in place; the text form's paths stay on the device) */ }
                 else if (path_step) memcpy(path_step + dst, mv, outlen);
                 else {
                     uint32_t i = 0, j = 0;
                     uint32_t *pi = path_i + dst, *pj = path_j + dst;
                     for (uint32_t q = 0; q < outlen; q++) { i += mv[q] & 1u; j += mv[q] >> 1; pi[q] = i; pj[q] = j; }
                 }
-                if (!sb.dense) memcpy(path_d + dst, h_pd + src, (size_t)outlen * 4);
+                if (!sb.dense && !tx) memcpy(path_d + dst, h_pd + src, (size_t)outlen * 4);
                 path_len[k] = outlen;
                 elems[t] += outlen;
             }
@@ -186,6 +229,22 @@ static int traceback_core(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_
         });
         for (int t = 0; t < T; t++) ctx->tb_path_elems += elems[t];
         lap("copy out");
+        if (tx) {
+            const uint64_t *h_toff = reinterpret_cast<const uint64_t *>(hp + al(hacc(sb.acc) * 4) + al(hacc(sb.acc)) + 2 * al(sb.cnt * 4));
+            const uint64_t total = h_toff[sb.cnt];
+            for (uint64_t q = 0; q <= sb.cnt; q++) tx->text_off[sb.begin + q] = text_base + h_toff[q];
+            if (total > sb.text_bound) return fail(ctx, RAWDTW_ERR_INTERNAL, "a sub-batch's text is longer than its bound");
+            if (text_base + total > tx->cap) text_short = true;
+            if (tx->text && total && !text_short) {
+                e = hipMemcpyAsync(tx->text + text_base, sb.d_text, total, hipMemcpyDeviceToHost, ctx->tb_text);
+                if (e == hipSuccess) e = hipStreamSynchronize(ctx->tb_text);
+                if (e != hipSuccess) return hip_fail(ctx, e, "text download");
+            }
+            text_base += total;
+            if (hipEventElapsedTime(&ms, sb.ev[2], sb.ev[4]) == hipSuccess) ctx->aln_count_ms += ms;
+            if (hipEventElapsedTime(&ms, sb.ev[4], sb.ev[5]) == hipSuccess) ctx->aln_write_ms += ms;
+            lap("text home");
+        }
         return RAWDTW_OK;
     };
 
@@ -203,6 +262,13 @@ static int traceback_core(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_
         uint8_t *d_mv = reinterpret_cast<uint8_t *>(pb);
         hipError_t e = hipMemcpyAsync(d_poff, sb.poff.data(), sb.cnt * 8, hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) return hip_fail(ctx, e, "path offsets upload");
+        if (tx) {
+            char *tb = static_cast<char *>(ctx->d_tb_text) + (size_t)sb.slot * (ctx->tb_text_bytes / 2);
+            sb.d_rec = carve<AlnDevRec>(tb, sb.cnt); sb.d_tot = carve<uint64_t>(tb, sb.cnt); sb.d_toff = carve<uint64_t>(tb, sb.cnt + 1);
+            sb.d_text = tb;
+            e = hipMemcpyAsync(sb.d_rec, sb.hrec.data(), sb.cnt * sizeof(AlnDevRec), hipMemcpyHostToDevice, ctx->stream);
+            if (e != hipSuccess) return hip_fail(ctx, e, "text records upload");
+        }
         (void)hipEventRecord(sb.ev[0], ctx->stream);
         st = rawdtw_plan_run(ctx, pl);
         if (st != RAWDTW_OK) return st;
@@ -214,15 +280,24 @@ static int traceback_core(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_
             if (e != hipSuccess) return hip_fail(ctx, e, "traceback walk launch");
         }
         (void)hipEventRecord(sb.ev[2], ctx->stream);
+        if (tx) { // measure, scan, write: all behind the walk, none of them waits for the host
+            e = launch_aln_count(d_mv, d_pd, d_poff, d_plen, sb.d_rec, sb.cnt, sb.d_tot, ctx->stream);
+            if (e == hipSuccess) e = launch_aln_scan(sb.d_tot, sb.cnt, sb.d_toff, ctx->stream);
+            if (e == hipSuccess) e = hipEventRecord(sb.ev[4], ctx->stream);
+            if (e == hipSuccess) e = launch_aln_write(d_mv, d_pd, d_poff, d_plen, sb.d_rec, sb.cnt, sb.d_toff, sb.d_text, ctx->stream);
+            if (e == hipSuccess) e = hipEventRecord(sb.ev[5], ctx->stream);
+            if (e != hipSuccess) return hip_fail(ctx, e, "aln text launch");
+        }
         // the download: on the second stream, behind the walk; everything lands in pinned memory (a download into pageable
         // memory makes the call wait for the kernels in front of it)
         char *hp = static_cast<char *>(ctx->h_pinned) + (size_t)sb.slot * (ctx->pinned_bytes / 2);
-        char *hc = hp + al((size_t)acc * 4) + al((size_t)acc);
-        e = hipStreamWaitEvent(ctx->tb_copy, sb.ev[2], 0);
+        char *hc = hp + al(hacc(acc) * 4) + al(hacc(acc));
+        e = hipStreamWaitEvent(ctx->tb_copy, sb.ev[tx ? 5 : 2], 0);
         if (e == hipSuccess) e = hipMemcpyAsync(hc, pl->d_cost, sb.cnt * 4, hipMemcpyDeviceToHost, ctx->tb_copy);
         if (e == hipSuccess) e = hipMemcpyAsync(hc + al(sb.cnt * 4), d_plen, sb.cnt * 4, hipMemcpyDeviceToHost, ctx->tb_copy);
-        if (e == hipSuccess && acc) e = hipMemcpyAsync(sb.direct ? static_cast<void *>(path_d + sb.lo) : static_cast<void *>(hp), d_pd, acc * 4, hipMemcpyDeviceToHost, ctx->tb_copy);
-        if (e == hipSuccess && acc) e = hipMemcpyAsync(sb.direct ? static_cast<void *>(path_step + sb.lo) : static_cast<void *>(hp + al((size_t)acc * 4)), d_mv, acc, hipMemcpyDeviceToHost, ctx->tb_copy);
+        if (e == hipSuccess && tx) e = hipMemcpyAsync(hc + 2 * al(sb.cnt * 4), sb.d_toff, (sb.cnt + 1) * 8, hipMemcpyDeviceToHost, ctx->tb_copy);
+        if (e == hipSuccess && acc && !tx) e = hipMemcpyAsync(sb.direct ? static_cast<void *>(path_d + sb.lo) : static_cast<void *>(hp), d_pd, acc * 4, hipMemcpyDeviceToHost, ctx->tb_copy);
+        if (e == hipSuccess && acc && !tx) e = hipMemcpyAsync(sb.direct ? static_cast<void *>(path_step + sb.lo) : static_cast<void *>(hp + al((size_t)acc * 4)), d_mv, acc, hipMemcpyDeviceToHost, ctx->tb_copy);
         if (e == hipSuccess) e = hipEventRecord(sb.ev[3], ctx->tb_copy);
         if (e != hipSuccess) return hip_fail(ctx, e, "traceback download");
         sb.in_flight = true;
@@ -231,6 +306,11 @@ static int traceback_core(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_
         if (k >= 1) { st = finish(subs[k - 1]); if (st != RAWDTW_OK) return st; }
     }
     for (size_t k = subs.size() >= 2 ? subs.size() - 2 : 0; k < subs.size(); k++) { st = finish(subs[k]); if (st != RAWDTW_OK) return st; }
+    if (tx) {
+        if (n_jobs == 0) tx->text_off[0] = 0;
+        *tx->bytes = text_base; ctx->aln_text_bytes = text_base;
+        if (tx->text && text_short) return fail(ctx, RAWDTW_ERR_RANGE, "text_cap is below the text's size");
+    }
     return RAWDTW_OK;
 }
 
@@ -255,6 +335,21 @@ int rawdtw_traceback_arena_steps(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint
 {
     if (n_jobs && !path_step) return fail(ctx, RAWDTW_ERR_INVALID, "null argument");
     return traceback_core(ctx, jobs, n_jobs, true, nullptr, 0, out_cost, path_off, path_len, nullptr, nullptr, path_step, path_d);
+}
+
+int rawdtw_traceback_batch_text(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events, uint64_t n_events,
+                                const rawdtw_aln_rec_t *recs, float *out_cost, uint32_t *path_len, uint64_t *text_off, char *text, uint64_t text_cap,
+                                uint64_t *text_bytes)
+{
+    const TextOut tx{recs, text_off, text, text_cap, text_bytes};
+    return traceback_core(ctx, jobs, n_jobs, false, h_events, n_events, out_cost, nullptr, path_len, nullptr, nullptr, nullptr, nullptr, &tx);
+}
+
+int rawdtw_traceback_arena_text(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const rawdtw_aln_rec_t *recs, float *out_cost,
+                                uint32_t *path_len, uint64_t *text_off, char *text, uint64_t text_cap, uint64_t *text_bytes)
+{
+    const TextOut tx{recs, text_off, text, text_cap, text_bytes};
+    return traceback_core(ctx, jobs, n_jobs, true, nullptr, 0, out_cost, nullptr, path_len, nullptr, nullptr, nullptr, nullptr, &tx);
 }
 
 // ---- single-call drop-ins ----------------------------------------------------------------------

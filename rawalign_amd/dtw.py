@@ -707,6 +707,39 @@ class Engine:
         self._check(self.lib.rawdtw_traceback_arena_steps(self._ctx, _ptr(jobs), len(jobs), _ptr(cost), _ptr(off), _ptr(plen), _ptr(step), _ptr(pd)))
         return cost, off, plen, step, pd
 
+    def aln_text(self, step, distance, path_off, path_len, recs, cap=None, sizes_only=False):
+        """rawdtw_aln_text_steps: the aln:s: text of paths given as steps and distances (include/rawdtw.h, "aln text"), made by the device's
+        count, scan and write launches -> (text_off, text): job k's text is text[text_off[k]:text_off[k + 1]] (bytes).  cap: the text
+        buffer's size (default: exactly what a first, sizes-only call reports); sizes_only: text is None."""
+        a = _aln_args(step, distance, path_off, path_len, recs)
+        return _aln_call(lambda toff, text, tcap, nb: self.lib.rawdtw_aln_text_steps(self._ctx, *[_ptr(x) for x in a], len(a[4]), toff, text, tcap, nb), len(a[4]), cap, sizes_only, self._check)
+
+    def traceback_text(self, jobs, recs, events=None, cap=None, sizes_only=False):
+        """rawdtw_traceback_batch_text (events None: rawdtw_traceback_arena_text, over the arena as it lies) -> (cost, path_len, text_off,
+        text): full-matrix tracebacks whose paths stay on the device and come home as the aln:s: text.  cap: the text buffer's size
+        (default aln_text_bound(jobs, recs)); sizes_only: text is None."""
+        jobs = np.ascontiguousarray(jobs, dtype=JOB_DTYPE)
+        recs = np.ascontiguousarray(recs, dtype=ALN_REC_DTYPE)
+        if len(recs) != len(jobs):
+            raise ValueError("one rec a job")
+        ev = None if events is None else _f32(events)
+        cost = np.empty(len(jobs), np.float32)
+        plen = np.zeros(len(jobs), np.uint32)
+
+        def call(toff, text, tcap, nb):
+            if ev is None:
+                return self.lib.rawdtw_traceback_arena_text(self._ctx, _ptr(jobs), len(jobs), _ptr(recs), _ptr(cost), _ptr(plen), toff, text, tcap, nb)
+            return self.lib.rawdtw_traceback_batch_text(self._ctx, _ptr(jobs), len(jobs), _ptr(ev), len(ev), _ptr(recs), _ptr(cost), _ptr(plen), toff, text, tcap, nb)
+
+        toff, text = _aln_call(call, len(jobs), aln_text_bound(jobs, recs) if cap is None else cap, sizes_only, self._check)
+        return cost, plen, toff, text
+
+    def aln_text_timing(self) -> dict:
+        """device time of the text launches of the context's most recent aln_text / traceback_text call, and the bytes they made"""
+        c, w, b = C.c_float(), C.c_float(), C.c_uint64()
+        self._check(self.lib.rawdtw_aln_text_timing(self._ctx, C.byref(c), C.byref(w), C.byref(b)))
+        return {"count_ms": c.value, "write_ms": w.value, "text_bytes": b.value}
+
     def events_fetch(self, starts, lens):
         """rawdtw_events_fetch: the arena's stretches [starts[q], starts[q] + lens[q]) as one array a segment, in order"""
         start, ln = np.ascontiguousarray(starts, np.uint32), np.ascontiguousarray(lens, np.uint32)
@@ -890,6 +923,66 @@ class Engine:
         f, w, d, e = C.c_float(), C.c_float(), C.c_uint64(), C.c_uint64()
         self._check(self.lib.rawdtw_banded_traceback_timing(self._ctx, C.byref(f), C.byref(w), C.byref(d), C.byref(e)))
         return {"fill_ms": f.value, "walk_ms": w.value, "direction_bytes": d.value, "path_elements": e.value}
+
+
+# rawdtw_aln_rec_t (include/rawdtw.h, "aln text")
+ALN_REC_DTYPE = np.dtype([("off_i", np.uint64), ("off_j", np.uint64), ("j0", np.uint32), ("mode", np.uint32), ("pad", np.uint64)])
+assert ALN_REC_DTYPE.itemsize == 32
+
+
+def _aln_args(step, distance, path_off, path_len, recs):
+    step = np.ascontiguousarray(step, np.uint8)
+    pd = np.ascontiguousarray(distance, np.float32)
+    off = np.ascontiguousarray(path_off, np.uint64)
+    plen = np.ascontiguousarray(path_len, np.uint32)
+    recs = np.ascontiguousarray(recs, dtype=ALN_REC_DTYPE)
+    if len(off) < len(plen) or len(recs) != len(plen) or len(step) != len(pd):
+        raise ValueError("one offset, one length and one rec a job; one step byte a distance")
+    if len(plen) and int((off[:len(plen)] + plen)[plen > 0].max(initial=0)) > len(step):
+        raise ValueError("a path lies beyond the step array")
+    return step, pd, off, plen, recs
+
+
+def _aln_call(call, n_jobs, cap, sizes_only, check):
+    """(text_off, text) of one of the aln text entry points: `call(text_off, text, text_cap, text_bytes)`.  cap None: sized by a first,
+    sizes-only call.  The text buffer is exactly cap bytes."""
+    toff = np.zeros(n_jobs + 1, np.uint64)
+    nb = C.c_uint64(0)
+    if cap is None or sizes_only:
+        check(call(_ptr(toff), None, 0, C.byref(nb)))
+        if sizes_only:
+            return toff, None
+        cap = nb.value
+    text = np.zeros(max(int(cap), 1), np.uint8)
+    check(call(_ptr(toff), _ptr(text), int(cap), C.byref(nb)))
+    return toff, text[:nb.value]
+
+
+def aln_text_host(step, distance, path_off, path_len, recs, threads: int = 0, cap=None, sizes_only=False):
+    """rawdtw_aln_text_host: the aln text's definition (include/rawdtw.h) restated on host threads, no device -> (text_off, text) as
+    Engine.aln_text"""
+    from ._lib import load_library
+
+    lib = load_library()
+    a = _aln_args(step, distance, path_off, path_len, recs)
+
+    def check(st):
+        if st != 0:
+            raise RawDTWError(st, "rawdtw_aln_text_host")
+
+    return _aln_call(lambda toff, text, tcap, nb: lib.rawdtw_aln_text_host(*[_ptr(x) for x in a], len(a[4]), threads, toff, text, tcap, nb),
+                     len(a[4]), cap, sizes_only, check)
+
+
+def aln_text_bound(jobs, recs) -> int:
+    """rawdtw_aln_text_bound: an upper bound on the text of these jobs' paths, whatever the paths are"""
+    from ._lib import load_library
+
+    jobs = np.ascontiguousarray(jobs, dtype=JOB_DTYPE)
+    recs = np.ascontiguousarray(recs, dtype=ALN_REC_DTYPE)
+    if len(recs) != len(jobs):
+        raise ValueError("one rec a job")
+    return int(load_library().rawdtw_aln_text_bound(_ptr(jobs), _ptr(recs), len(jobs)))
 
 
 def expand_steps(step, j0: int = 0):

@@ -686,6 +686,11 @@ class CMapper:
         refused, as the reference asserts)"""
         self._check(self.lib.rawdtw_mapper_set_banded_cigar(self._h, int(bool(on))))
 
+    def set_device_text(self, on: bool = True):
+        """rawdtw_mapper_set_device_text: the full-matrix finish (global + full, sparse) gets aln:s: as text from the device
+        (include/rawdtw.h, "aln text"); the banded and the local finish keep the host formatter"""
+        self._check(self.lib.rawdtw_mapper_set_device_text(self._h, int(bool(on))))
+
     def paf(self, rid: int) -> str:
         import ctypes as C
 
@@ -845,7 +850,7 @@ class CMapper:
 
 
 def map_reads_c(seeds, read_ids, cm: CMapper, batch_size=None, su=None, seed_index=None, resident=False, signal=False, event_opt=None,
-                banded_cigar=False):
+                banded_cigar=False, device_text=False):
     """map_reads through the library's mapper: chunk rounds until every read stopped; the PAF lines in read order, the rounds.
 
     The reads go in mini-batches of `batch_size` (None: one of all of them), at most two at a time -- the next batch's reads are
@@ -856,11 +861,14 @@ def map_reads_c(seeds, read_ids, cm: CMapper, batch_size=None, su=None, seed_ind
     without a line (sequence-until dropped it, or it was never added) has "" in the list.  `resident` (with `seed_index`): the
     rounds leave their hits on the device (CMapper.round).  `signal` (with `seed_index`): `seeds` serves window(r, c) -- samples, not
     events (SignalReads) -- and its `channels` (None: pA samples; else int16 reads' channels, one a read); every round is
-    CMapper.round_signal with `event_opt`: the events never leave the device.  `banded_cigar`: CMapper.set_banded_cigar before the finish."""
+    CMapper.round_signal with `event_opt`: the events never leave the device.  `banded_cigar`: CMapper.set_banded_cigar before the finish.  `device_text`: CMapper.set_device_text before the
+    finish."""
     from . import shard
 
     if banded_cigar:
         cm.set_banded_cigar(True)
+    if device_text:
+        cm.set_device_text(True)
     read_ids = list(read_ids)
     if signal and seed_index is None:
         raise ValueError("rounds from signal need a seed_index")
