@@ -124,7 +124,6 @@ int rawdtw_destroy(rawdtw_ctx *ctx)
     if (ctx->d_append) (void)hipFree(ctx->d_append);
     if (ctx->d_fetch) (void)hipFree(ctx->d_fetch);
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
-    for (hipEvent_t &e : ctx->tb_ev) if (e) (void)hipEventDestroy(e);
     if (ctx->tb_copy) (void)hipStreamDestroy(ctx->tb_copy);
     if (ctx->d_tb_dir) (void)hipFree(ctx->d_tb_dir);
     if (ctx->d_tb_paths) (void)hipFree(ctx->d_tb_paths);

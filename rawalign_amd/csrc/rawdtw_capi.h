@@ -6,6 +6,7 @@
 //                         run / fetch / diagnostics, chunk rounds (a batch's launches by name and count: rawdtw_launches.h)
 //   rawdtw_plan_check.cpp the readers of a device-planned batch's plan behind those diagnostics (no HIP: rawdtw_plan_check.h)
 //   rawdtw_traceback.cpp  rawdtw_traceback_batch*, the single-call drop-ins
+//   rawdtw_tb_driver.cpp  the one sub-batch driver of the three tracebacks (full matrix, banded, semiglobal)
 //   rawdtw_semiglobal.cpp subsequence DTW: rawdtw_semiglobal_*, its drop-ins (kernels: rawdtw_semiglobal_kernels.hip)
 //   rawdtw_index.cpp      the .ind reader
 // There is NO CPU fallback in any of them: every scoring entry point runs the HIP kernels or returns an error status.
@@ -65,6 +66,13 @@ struct RefHold {
     std::atomic<int> refs{1};
 };
 
+// what a traceback call leaves for its timing getter: device time of its fill and walk launches, direction bytes written, path
+// elements handed to the caller (rawdtw_tb_driver.cpp)
+struct TbTiming {
+    float fill_ms = 0.f, walk_ms = 0.f;
+    uint64_t dir_written = 0, path_elems = 0;
+};
+
 struct rawdtw_ctx : rawdtw::Options { // (every option is a field of Options: rawdtw_options.h)
     int device = 0;
     hipStream_t stream = nullptr;
@@ -88,14 +96,12 @@ struct rawdtw_ctx : rawdtw::Options { // (every option is a field of Options: ra
     size_t fetch_bytes = 0;
     uint8_t *d_tb_dir = nullptr; // traceback direction workspace, grow-only (hipFree of 600 MB per call costs 1 ms)
     uint64_t tb_dir_bytes = 0;
-    void *d_tb_paths = nullptr;  // traceback path buffers (offsets, lengths, i/j end-first, i/j/d start-first), grow-only
+    void *d_tb_paths = nullptr;  // traceback path buffers, two slots (rawdtw_tb_layout.h), grow-only
     size_t tb_paths_bytes = 0;
-    void *h_pinned = nullptr;  // pinned host staging (traceback paths), grow-only
+    void *h_pinned = nullptr;  // pinned landing zone of the traceback's paths, two slots, grow-only
     size_t pinned_bytes = 0;
-    hipEvent_t tb_ev[3] = {nullptr, nullptr, nullptr}; // (kept for ABI of the struct's users; a traceback sub-batch has events of its own)
     hipStream_t tb_copy = nullptr;                      // traceback: the paths' way home, beside the next sub-batch's kernels
-    float tb_fill_ms = 0.f, tb_walk_ms = 0.f;          // device time of the most recent rawdtw_traceback_batch
-    uint64_t tb_dir_written = 0, tb_path_elems = 0;
+    TbTiming tb, band_tb, semi; // the most recent full-matrix, banded and semiglobal traceback call (semi: any semiglobal call)
     // the aln text (rawdtw_aln_text.hip): a traceback's text form keeps its records, totals, offsets and the text itself here, two slots, grow-only;
     // the text goes home on a stream of its own (tb_copy already holds the next sub-batch's copies when a sub-batch's total is known)
     void *d_tb_text = nullptr;
@@ -104,10 +110,6 @@ struct rawdtw_ctx : rawdtw::Options { // (every option is a field of Options: ra
     float aln_count_ms = 0.f, aln_write_ms = 0.f;      // device time of the most recent text call's launches (rawdtw_aln_text_timing)
     uint64_t aln_text_bytes = 0;
     uint64_t tb_sub_batches = 0;  // "tb_sub_batches" (read-only): sub-batches of the most recent traceback call, known before its first plan is built
-    float semi_fill_ms = 0.f, semi_walk_ms = 0.f;      // device time of the most recent semiglobal call (rawdtw_semiglobal.cpp)
-    uint64_t semi_dir_written = 0, semi_path_elems = 0;
-    float band_tb_fill_ms = 0.f, band_tb_walk_ms = 0.f; // device time of the most recent banded traceback call (rawdtw_band_tb.cpp)
-    uint64_t band_tb_dir_written = 0, band_tb_path_elems = 0;
     // reference arena.  An arena the library allocated (rawdtw_upload_reference, rawdtw_index_upload) is held through a
     // counted RefHold, shared by every context that adopted it with rawdtw_share_reference: it is freed when the last of
     // them lets go, so the owner may upload another reference or be destroyed while sharers still run on the old one.

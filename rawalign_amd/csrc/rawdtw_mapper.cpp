@@ -306,8 +306,8 @@ int rawdtw_mapper_set_device_text(rawdtw_mapper *m, int on)
 
 // --dtw-output-cigar (rmap.cpp:715-717): the best chain of every mapped read through DTW_global_tb once more, its path as the
 // aln:s: string with the reference's two quirks (rmap.cpp:230-233, 283-289).  All reads' jobs go to the device in ONE call;
-// the paths come back as steps and distances (rawdtw_traceback_batch_steps: 5 bytes an element) and every read's string is
-// written on the pool while the steps are walked.
+// the paths come back as steps and distances (rawdtw_traceback_batch_steps: 5 bytes an element) and the one host formatter
+// (rawdtw_aln_text_host) makes every job's text of them -- or, under rawdtw_mapper_set_device_text, the text itself comes back.
 int rawdtw_mapper_finish(rawdtw_mapper *m)
 {
     if (!m) return RAWDTW_ERR_INVALID;
@@ -350,87 +350,62 @@ int rawdtw_mapper_finish(rawdtw_mapper *m)
     }
     if (items.empty()) return RAWDTW_OK;
     const uint64_t nj_all = jobs.size();
-    if (m->device_text && !local && !banded && nj_all) {
-        // rawdtw_mapper_set_device_text: the same jobs through the traceback's text form (include/rawdtw.h, "aln text").  One rec a job says what
-        // the loop below says per element: a sparse part's elements all move by its part's start anchor (mode 1), a global chain's last element
-        // moves by len times the chain's start anchor (mode 0).  The jobs of a read are consecutive, so its aln:s: is one stretch of the text.
-        std::vector<rawdtw_aln_rec_t> recs(nj_all);
-        for (const Item &it : items) {
-            const MChain &ch = m->reads[it.read].chains[0];
-            const uint32_t na = (uint32_t)ch.anchors.size(), parts = na - 1;
-            const bool sparse = m->opt.align.border_constraint != 0;
-            for (uint32_t k = 0; k < it.nj; k++) {
-                const rawdtw_anchor_t &s0 = sparse ? ch.anchors[parts - k] : ch.anchors[na - 1];
-                recs[it.job0 + k] = rawdtw_aln_rec_t{s0.query_position, s0.target_position, 0u, sparse ? 1u : 0u, 0};
-            }
+    // One rec a job says what every element of its text moves by (include/rawdtw.h, "aln text"): a sparse part's elements all move by
+    // its part's start anchor (mode 1, rmap.cpp:286-289); a global chain's last element moves by len times the chain's start anchor
+    // (mode 0: the offsets are added to alignment.back() once per element, rmap.cpp:230-233), the banded path alike; a local chain's
+    // elements move by the chain's start anchor, the sparse branch's way, and its walk starts at (0, j0).
+    std::vector<rawdtw_aln_rec_t> recs(nj_all);
+    for (const Item &it : items) {
+        const MChain &ch = m->reads[it.read].chains[0];
+        const uint32_t na = (uint32_t)ch.anchors.size(), parts = na - 1;
+        for (uint32_t k = 0; k < it.nj; k++) {
+            const rawdtw_anchor_t &s0 = m->opt.align.border_constraint == 1 ? ch.anchors[parts - k] : ch.anchors[na - 1];
+            recs[it.job0 + k] = rawdtw_aln_rec_t{s0.query_position, s0.target_position, 0u, m->opt.align.border_constraint != 0 ? 1u : 0u, 0};
         }
+    }
+    std::vector<uint64_t> toff(nj_all + 1, 0);
+    std::vector<uint32_t> plen(nj_all);
+    std::vector<float> cost(nj_all);
+    std::unique_ptr<char[]> text; // (not value-initialised: the bound is a few times the text)
+    uint64_t bytes = 0;
+    if (nj_all && !arena) m->arena_replaced = true;
+    if (m->device_text && !local && !banded && nj_all) {
+        // rawdtw_mapper_set_device_text: the jobs through the traceback's text form, the paths stay on the device
         const uint64_t cap = rawdtw_aln_text_bound(jobs.data(), recs.data(), nj_all);
-        std::vector<uint64_t> toff(nj_all + 1, 0);
-        std::vector<uint32_t> plen(nj_all);
-        std::vector<float> cost(nj_all);
-        std::unique_ptr<char[]> text(new (std::nothrow) char[cap + 1]); // (not value-initialised: the bound is a few times the text)
+        text.reset(new (std::nothrow) char[cap + 1]);
         if (!text) return fail(m, RAWDTW_ERR_OOM, "no memory for the aln:s: text");
-        uint64_t bytes = 0;
-        if (!arena) m->arena_replaced = true;
         const int st = arena ? rawdtw_traceback_arena_text(m->ctx, jobs.data(), nj_all, recs.data(), cost.data(), plen.data(), toff.data(), text.get(), cap, &bytes)
                              : rawdtw_traceback_batch_text(m->ctx, jobs.data(), nj_all, events.data(), events.size(), recs.data(), cost.data(), plen.data(),
                                                            toff.data(), text.get(), cap, &bytes);
         if (st != RAWDTW_OK) return fail(m, st, rawdtw_last_error(m->ctx));
-        std::vector<std::string> logs(items.size());
-        m->pool->run(items.size(), 4, [&](size_t x) {
-            const Item &it = items[x];
-            MChain &ch = m->reads[it.read].chains[0];
-            ch.alignment_score = rawdtw_chain_replay(&m->opt.align, ch.anchors.data(), (uint32_t)ch.anchors.size(), cost.data() + it.job0, -1e10f); // rmap.cpp:306 on the summed costs
-            ch.aln.assign(text.get() + toff[it.job0], toff[it.job0 + it.nj] - toff[it.job0]);
-            ch.has_aln = true;
-            if (m->opt.flag & 0x8) logs[x] = log_scores_line(ch.chaining_score, ch.alignment_score);
-        });
-        for (const std::string &l : logs) m->log += l; // (read order)
-        return RAWDTW_OK;
-    }
-    std::vector<uint64_t> poff(nj_all + 1, 0);
-    for (uint64_t k = 0; k < nj_all; k++) poff[k + 1] = poff[k] + jobs[k].n + jobs[k].m - 1;
-    std::vector<uint32_t> plen(nj_all);
-    std::vector<uint8_t> step(poff[nj_all] + 1);
-    std::vector<float> pd(poff[nj_all] + 1), cost(nj_all);
-    std::vector<uint32_t> j0(local ? nj_all : 0);
-    if (nj_all) {
-        if (!arena) m->arena_replaced = true;
-        const int st = local ? rawdtw_semiglobal_traceback_steps(m->ctx, jobs.data(), nj_all, arena ? nullptr : events.data(), events.size(), cost.data(),
-                                                                 j0.data(), poff.data(), plen.data(), step.data(), pd.data())
-                       : banded ? rawdtw_banded_traceback_steps(m->ctx, jobs.data(), nj_all, arena ? nullptr : events.data(), events.size(), cost.data(),
-                                                              poff.data(), plen.data(), step.data(), pd.data())
-                       : arena ? rawdtw_traceback_arena_steps(m->ctx, jobs.data(), nj_all, cost.data(), poff.data(), plen.data(), step.data(), pd.data())
-                             : rawdtw_traceback_batch_steps(m->ctx, jobs.data(), nj_all, events.data(), events.size(), cost.data(), poff.data(), plen.data(), step.data(), pd.data());
+    } else if (nj_all) {
+        // the paths come home as steps and distances, and the host formatter (rawdtw_aln_text_host) makes the text of them
+        std::vector<uint64_t> poff(nj_all + 1, 0);
+        for (uint64_t k = 0; k < nj_all; k++) poff[k + 1] = poff[k] + jobs[k].n + jobs[k].m - 1;
+        std::vector<uint8_t> step(poff[nj_all] + 1);
+        std::vector<float> pd(poff[nj_all] + 1);
+        std::vector<uint32_t> j0(local ? nj_all : 0);
+        int st = local ? rawdtw_semiglobal_traceback_steps(m->ctx, jobs.data(), nj_all, arena ? nullptr : events.data(), events.size(), cost.data(),
+                                                           j0.data(), poff.data(), plen.data(), step.data(), pd.data())
+                 : banded ? rawdtw_banded_traceback_steps(m->ctx, jobs.data(), nj_all, arena ? nullptr : events.data(), events.size(), cost.data(),
+                                                        poff.data(), plen.data(), step.data(), pd.data())
+                 : arena ? rawdtw_traceback_arena_steps(m->ctx, jobs.data(), nj_all, cost.data(), poff.data(), plen.data(), step.data(), pd.data())
+                       : rawdtw_traceback_batch_steps(m->ctx, jobs.data(), nj_all, events.data(), events.size(), cost.data(), poff.data(), plen.data(), step.data(), pd.data());
         if (st != RAWDTW_OK) return fail(m, st, rawdtw_last_error(m->ctx));
+        for (uint64_t k = 0; k < j0.size(); k++) recs[k].j0 = j0[k];
+        const uint64_t cap = rawdtw_aln_text_bound(jobs.data(), recs.data(), nj_all);
+        text.reset(new (std::nothrow) char[cap + 1]);
+        if (!text) return fail(m, RAWDTW_ERR_OOM, "no memory for the aln:s: text");
+        st = rawdtw_aln_text_host(step.data(), pd.data(), poff.data(), plen.data(), recs.data(), nj_all, m->pool->threads(), toff.data(), text.get(), cap, &bytes);
+        if (st != RAWDTW_OK) return fail(m, st, "the aln:s: text does not fit its bound");
     }
+    // The jobs of a read are consecutive, so its aln:s: is one stretch of the text.
     std::vector<std::string> logs(items.size());
     m->pool->run(items.size(), 4, [&](size_t x) {
         const Item &it = items[x];
-        MRead &rd = m->reads[it.read];
-        MChain &ch = rd.chains[0];
-        const uint32_t na = (uint32_t)ch.anchors.size(), nj = it.nj;
-        ch.alignment_score = rawdtw_chain_replay(&m->opt.align, ch.anchors.data(), na, cost.data() + it.job0, -1e10f); // rmap.cpp:306 on the summed costs
-        std::string s;
-        const uint32_t parts = na - 1;
-        char el[96];
-        for (uint32_t k = 0; k < nj; k++) {
-            // sparse: every element offset by its part's start anchor (rmap.cpp:286-289); global: the offsets are added to
-            // alignment.back() once per element (rmap.cpp:230-233), i.e. only the last tuple moves
-            const rawdtw_anchor_t &s0 = m->opt.align.border_constraint != 1 ? ch.anchors[na - 1] : ch.anchors[parts - k];
-            const uint64_t p0 = poff[it.job0 + k];
-            const uint32_t len = plen[it.job0 + k];
-            unsigned long long pi = 0, pj = local ? j0[it.job0 + k] : 0u; // (i, j) from the steps: a global path starts at (0, 0), a local one at (0, j0)
-            for (uint32_t q = 0; q < len; q++) {
-                pi += step[p0 + q] & 1u; pj += step[p0 + q] >> 1;
-                unsigned long long i = pi, j = pj;
-                if (m->opt.align.border_constraint != 0) { i += s0.query_position; j += s0.target_position; } // (sparse, and local: the sparse branch's way)
-                else if (q + 1 == len) { i += (unsigned long long)len * s0.query_position; j += (unsigned long long)len * s0.target_position; }
-                snprintf(el, sizeof el, "(%llu,%llu,%g)", i, j, (double)pd[p0 + q]); // ostream << float == %g (rmap.cpp:580-592)
-                s += el;
-            }
-        }
-        ch.aln = std::move(s);
+        MChain &ch = m->reads[it.read].chains[0];
+        ch.alignment_score = rawdtw_chain_replay(&m->opt.align, ch.anchors.data(), (uint32_t)ch.anchors.size(), cost.data() + it.job0, -1e10f); // rmap.cpp:306 on the summed costs
+        ch.aln.assign(it.nj ? text.get() + toff[it.job0] : "", toff[it.job0 + it.nj] - toff[it.job0]);
         ch.has_aln = true;
         if (m->opt.flag & 0x8) logs[x] = log_scores_line(ch.chaining_score, ch.alignment_score);
     });

@@ -1,33 +1,22 @@
 // rawdtw_semiglobal.cpp -- subsequence DTW behind the C ABI: rawdtw_semiglobal_batch, rawdtw_semiglobal_span_batch,
 // rawdtw_semiglobal_traceback_steps and the single-call drop-ins for DTW_semiglobal / DTW_semiglobal_tb (dtw.hpp; dtw.cpp:526-593,
-// 669-753) and for the span.  Host code only: validation,
-// the jobs' classes, their launches and the traceback's sub-batches.  The job-list planner (rawdtw_planner.cpp) knows nothing of
-// these jobs: they are bucketed here, by the class rawdtw_semiglobal.h defines, longest first inside a class (a launch takes as
-// long as its longest job).  There is no CPU fallback: the kernels run or the call returns an error status.
+// 669-753) and for the span.  Host code only: validation, the jobs' classes and their launches; the traceback's sub-batches are the
+// driver's (rawdtw_tb_driver.cpp).  The job-list planner (rawdtw_planner.cpp) knows nothing of these jobs: they are bucketed here, by
+// the class rawdtw_semiglobal.h defines, longest first inside a class (a launch takes as long as its longest job).  There is no CPU
+// fallback: the kernels run or the call returns an error status.
 #include "rawdtw_capi.h"
 #include "rawdtw_semiglobal.h"
+#include "rawdtw_tb_driver.h"
 
 using namespace rawdtw;
 using namespace rawdtw::capi;
 
 namespace {
 
-struct SemiLaunch { int cls; uint64_t first, count; };
-
-// the jobs [begin, begin + cnt) in launch order; a record's aux is the job's index inside the stretch
-struct SemiPlan {
-    std::vector<uint32_t> order; // position -> index inside the stretch
-    std::vector<DevJob> jobs;
-    std::vector<FullAux> aux;
-    std::vector<SemiLaunch> launches;
-    uint64_t bnd_floats = 0, dir_bytes = 0;
-};
-
 enum class SemiForm { Cost, Traceback, Span };
 
-void semi_plan(const rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t cnt, SemiForm form, SemiPlan &pl)
+void semi_plan(const rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t cnt, SemiForm form, ClassPlan &pl)
 {
-    struct Keyed { uint64_t key; uint32_t idx; };
     std::vector<Keyed> keyed(cnt);
     const uint64_t lim = (1ull << 28) - 1;
     for (uint64_t k = 0; k < cnt; k++) {
@@ -35,7 +24,7 @@ void semi_plan(const rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t cnt, Se
         const uint64_t c = (uint64_t)semi_class(j.n, j.m, ctx->full_wg);
         keyed[k] = Keyed{(c << 56) | ((lim - std::min<uint64_t>(j.m, lim)) << 28) | (lim - std::min<uint64_t>(j.n, lim)), (uint32_t)k};
     }
-    std::sort(keyed.begin(), keyed.end(), [](const Keyed &x, const Keyed &y) { return x.key != y.key ? x.key < y.key : x.idx < y.idx; });
+    sort_keyed(keyed);
     pl.order.resize(cnt); pl.jobs.resize(cnt); pl.aux.assign(cnt, FullAux{0, 0});
     for (uint64_t p = 0; p < cnt; p++) {
         const uint32_t k = keyed[p].idx;
@@ -51,7 +40,7 @@ void semi_plan(const rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t cnt, Se
             pl.aux[p].dir_off = pl.dir_bytes;
             pl.dir_bytes += (semi_dir_bytes(j.n, j.m, c) + 255) & ~255ull;
         }
-        if (pl.launches.empty() || pl.launches.back().cls != c) pl.launches.push_back(SemiLaunch{c, p, 0});
+        if (pl.launches.empty() || pl.launches.back().cls != c) pl.launches.push_back(ClassLaunch{c, p, 0, 0});
         pl.launches.back().count++;
     }
 }
@@ -74,19 +63,19 @@ int semi_check(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, bool 
     return RAWDTW_OK;
 }
 
-// records up, fill launches of one plan; cost and end_j (the span form: and j0) are left on the device (indexed inside the stretch)
-int semi_fill(rawdtw_ctx *ctx, const SemiPlan &pl, SemiForm form, DevJob *d_jobs, FullAux *d_aux, float *d_cost, uint32_t *d_j0,
-              uint32_t *d_endj, float *d_bnd, uint8_t *d_dir)
+// records up, fill launches of one plan; cost and end_j (the span form: and j0, in the slot's extra word) are left on the device (indexed
+// inside the stretch)
+int semi_fill(rawdtw_ctx *ctx, const ClassPlan &pl, SemiForm form, const TbSlot &slot, uint8_t *d_dir)
 {
     const uint64_t cnt = pl.jobs.size();
-    HIP_TRY(ctx, hipMemcpyAsync(d_jobs, pl.jobs.data(), cnt * sizeof(DevJob), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_aux, pl.aux.data(), cnt * sizeof(FullAux), hipMemcpyHostToDevice, ctx->stream));
-    for (const SemiLaunch &L : pl.launches) {
+    HIP_TRY(ctx, hipMemcpyAsync(slot.jobs, pl.jobs.data(), cnt * sizeof(DevJob), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(slot.aux, pl.aux.data(), cnt * sizeof(FullAux), hipMemcpyHostToDevice, ctx->stream));
+    for (const ClassLaunch &L : pl.launches) {
         hipError_t e = form == SemiForm::Span
-                           ? launch_semi_span_wave(L.cls, d_jobs + L.first, L.count, d_aux + L.first, ctx->d_ev, ctx->d_ref, d_cost, d_j0,
-                                                   d_endj, d_bnd, ctx->stream)
-                           : launch_semi_wave(L.cls, form == SemiForm::Traceback, d_jobs + L.first, L.count, d_aux + L.first, ctx->d_ev,
-                                              ctx->d_ref, d_cost, d_endj, d_bnd, d_dir, ctx->stream);
+                           ? launch_semi_span_wave(L.cls, slot.jobs + L.first, L.count, slot.aux + L.first, ctx->d_ev, ctx->d_ref, slot.cost, slot.extra,
+                                                   slot.endj, slot.bnd, ctx->stream)
+                           : launch_semi_wave(L.cls, form == SemiForm::Traceback, slot.jobs + L.first, L.count, slot.aux + L.first, ctx->d_ev,
+                                              ctx->d_ref, slot.cost, slot.endj, slot.bnd, d_dir, ctx->stream);
         if (e != hipSuccess) return hip_fail(ctx, e, "semiglobal fill launch");
     }
     return RAWDTW_OK;
@@ -105,37 +94,56 @@ int semi_batch(rawdtw_ctx *ctx, SemiForm form, const rawdtw_job_t *jobs, uint64_
     int st = semi_check(ctx, jobs, n_jobs, arena, n_events);
     if (st != RAWDTW_OK) return st;
     if (!arena && (st = rawdtw_upload_events(ctx, h_events, n_events)) != RAWDTW_OK) return st;
-    SemiPlan pl;
+    ClassPlan pl;
     semi_plan(ctx, jobs, n_jobs, form, pl);
     DevBlock blk(ctx, "semiglobal");
-    const size_t need = al256(n_jobs * sizeof(DevJob)) + al256(n_jobs * sizeof(FullAux)) + (span ? 3 : 2) * al256(n_jobs * 4) +
-                        al256(pl.bnd_floats * 4);
-    if ((st = blk.reserve(need)) != RAWDTW_OK) return st;
-    char *p = blk.p;
-    DevJob *d_jobs = carve<DevJob>(p, n_jobs);
-    FullAux *d_aux = carve<FullAux>(p, n_jobs);
-    float *d_cost = carve<float>(p, n_jobs);
-    uint32_t *d_endj = carve<uint32_t>(p, n_jobs);
-    uint32_t *d_j0 = span ? carve<uint32_t>(p, n_jobs) : nullptr;
-    float *d_bnd = carve<float>(p, pl.bnd_floats);
+    const tb::Recs R = tb::recs(n_jobs, sizeof(DevJob), sizeof(FullAux), true, span, pl.bnd_floats);
+    if ((st = blk.reserve(R.need)) != RAWDTW_OK) return st;
+    const TbSlot slot{reinterpret_cast<DevJob *>(blk.p + R.jobs.at), reinterpret_cast<FullAux *>(blk.p + R.aux.at), reinterpret_cast<float *>(blk.p + R.cost.at),
+                      reinterpret_cast<uint32_t *>(blk.p + R.endj.at), reinterpret_cast<float *>(blk.p + R.bnd.at), nullptr, nullptr,
+                      reinterpret_cast<uint32_t *>(blk.p + R.j0.at), nullptr, nullptr, nullptr, nullptr}; // (no paths; extra: the span form's j0)
     EventPair ev;
     for (int k = 0; k < 2; k++) HIP_TRY(ctx, hipEventCreate(&ev.e[k]));
-    ctx->semi_fill_ms = ctx->semi_walk_ms = 0.f; ctx->semi_dir_written = 0; ctx->semi_path_elems = 0;
+    ctx->semi = TbTiming{};
     HIP_TRY(ctx, hipEventRecord(ev.e[0], ctx->stream));
-    if ((st = semi_fill(ctx, pl, form, d_jobs, d_aux, d_cost, d_j0, d_endj, d_bnd, nullptr)) != RAWDTW_OK) return st;
+    if ((st = semi_fill(ctx, pl, form, slot, nullptr)) != RAWDTW_OK) return st;
     HIP_TRY(ctx, hipEventRecord(ev.e[1], ctx->stream));
     // (a record's aux is the caller's job index: the results come home in job order)
-    HIP_TRY(ctx, hipMemcpyAsync(out_cost, d_cost, n_jobs * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(out_end_j, d_endj, n_jobs * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (span) HIP_TRY(ctx, hipMemcpyAsync(out_j0, d_j0, n_jobs * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out_cost, slot.cost, n_jobs * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out_end_j, slot.endj, n_jobs * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (span) HIP_TRY(ctx, hipMemcpyAsync(out_j0, slot.extra, n_jobs * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ev.e[0], ev.e[1]) == hipSuccess) ctx->semi_fill_ms = ms;
+    if (hipEventElapsedTime(&ms, ev.e[0], ev.e[1]) == hipSuccess) ctx->semi.fill_ms = ms;
     return RAWDTW_OK;
 }
 
-// Traceback: sub-batches under the direction-buffer budget ("tb_workspace_mb", as rawdtw_traceback_batch*), one after another --
-// fill, walk, finish, paths home, written into the caller's arrays.  Exactly one of path_step and (path_i, path_j) is given.
+// The semiglobal path as the driver takes it (rawdtw_tb_driver.h): a stretch's records (job, aux, cost, end_j, boundary rows) lie in the
+// slot; the extra word a job is j0, the path's first column.
+uint64_t semi_job_dir_bytes(const rawdtw_ctx *ctx, const rawdtw_job_t &j) { return semi_dir_bytes(j.n, j.m, semi_class(j.n, j.m, ctx->full_wg)) + 256; }
+int semi_stretch(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t cnt, TbStretch *out)
+{
+    ClassPlan *pl = new ClassPlan;
+    semi_plan(ctx, jobs, cnt, SemiForm::Traceback, *pl);
+    *out = class_stretch(pl, true);
+    return RAWDTW_OK;
+}
+int semi_tb_fill(rawdtw_ctx *ctx, const TbStretch &s, const TbSlot &slot)
+{
+    return semi_fill(ctx, *static_cast<const ClassPlan *>(s.plan), SemiForm::Traceback, slot, ctx->d_tb_dir);
+}
+int semi_tb_walk(rawdtw_ctx *ctx, const TbStretch &s, const TbSlot &slot)
+{
+    const ClassPlan &pl = *static_cast<const ClassPlan *>(s.plan);
+    for (const ClassLaunch &L : pl.launches) {
+        hipError_t e = launch_semi_walk(L.cls, slot.jobs + L.first, L.count, slot.aux + L.first, ctx->d_ev, ctx->d_ref, ctx->d_tb_dir, slot.endj,
+                                        slot.poff + L.first, slot.plen + L.first, slot.extra + L.first, slot.ti, slot.tj, slot.mv, slot.pd, ctx->stream);
+        if (e != hipSuccess) return hip_fail(ctx, e, "semiglobal walk launch");
+    }
+    return RAWDTW_OK;
+}
+
+// Exactly one of path_step and (path_i, path_j) is given.
 int semi_traceback(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events, uint64_t n_events, float *out_cost,
                    uint32_t *out_j0, const uint64_t *path_off, uint32_t *path_len, uint8_t *path_step, uint32_t *path_i, uint32_t *path_j,
                    float *path_d)
@@ -149,101 +157,9 @@ int semi_traceback(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, c
     int st = semi_check(ctx, jobs, n_jobs, arena, n_events);
     if (st != RAWDTW_OK) return st;
     if (!arena && (st = rawdtw_upload_events(ctx, h_events, n_events)) != RAWDTW_OK) return st;
-
-    const uint64_t budget = tb_budget_bytes(ctx);
-    // the split: a job joins the current sub-batch unless that passes the budget (a job over the budget goes alone)
-    struct Sub { uint64_t begin, cnt, acc; SemiPlan pl; };
-    std::vector<Sub> subs;
-    for (uint64_t begin = 0; begin < n_jobs;) {
-        uint64_t end = begin, bytes = 0;
-        while (end < n_jobs) {
-            const rawdtw_job_t &j = jobs[end];
-            const uint64_t b = semi_dir_bytes(j.n, j.m, semi_class(j.n, j.m, ctx->full_wg)) + 256;
-            if (end > begin && bytes + b > budget) break;
-            bytes += b;
-            end++;
-        }
-        subs.push_back(Sub{begin, end - begin, 0, SemiPlan{}});
-        begin = end;
-    }
-    ctx->tb_sub_batches = subs.size();
-    size_t dev_need = 0;
-    uint64_t dir_need = 0, acc_max = 0, cnt_max = 0;
-    std::vector<std::vector<uint64_t>> poff(subs.size());
-    for (size_t q = 0; q < subs.size(); q++) {
-        Sub &sb = subs[q];
-        semi_plan(ctx, jobs + sb.begin, sb.cnt, SemiForm::Traceback, sb.pl);
-        poff[q].resize(sb.cnt);
-        for (uint64_t p = 0; p < sb.cnt; p++) { poff[q][p] = sb.acc; sb.acc += (uint64_t)sb.pl.jobs[p].n + sb.pl.jobs[p].m - 1; }
-        const size_t need = al256(sb.cnt * sizeof(DevJob)) + al256(sb.cnt * sizeof(FullAux)) + 4 * al256(sb.cnt * 4) + al256(sb.cnt * 8) +
-                            al256(sb.pl.bnd_floats * 4) + 3 * al256(sb.acc * 4) + al256(sb.acc);
-        dev_need = std::max(dev_need, need); dir_need = std::max(dir_need, sb.pl.dir_bytes);
-        acc_max = std::max(acc_max, sb.acc); cnt_max = std::max(cnt_max, sb.cnt);
-    }
-    if ((st = ensure_tb_dir(ctx, dir_need)) != RAWDTW_OK) return st;
-    DevBlock blk(ctx, "semiglobal");
-    if ((st = blk.reserve(dev_need)) != RAWDTW_OK) return st;
-    EventPair ev;
-    for (hipEvent_t &e : ev.e) HIP_TRY(ctx, hipEventCreate(&e));
-    ctx->semi_fill_ms = ctx->semi_walk_ms = 0.f; ctx->semi_dir_written = 0; ctx->semi_path_elems = 0;
-    std::vector<float> h_cost(cnt_max), h_pd(acc_max);
-    std::vector<uint32_t> h_len(cnt_max), h_j0(cnt_max);
-    std::vector<uint8_t> h_mv(acc_max);
-
-    for (size_t q = 0; q < subs.size(); q++) {
-        const Sub &sb = subs[q];
-        char *p = blk.p;
-        DevJob *d_jobs = carve<DevJob>(p, sb.cnt);
-        FullAux *d_aux = carve<FullAux>(p, sb.cnt);
-        float *d_cost = carve<float>(p, sb.cnt);
-        uint32_t *d_endj = carve<uint32_t>(p, sb.cnt);
-        uint32_t *d_plen = carve<uint32_t>(p, sb.cnt);
-        uint32_t *d_j0 = carve<uint32_t>(p, sb.cnt);
-        uint64_t *d_poff = carve<uint64_t>(p, sb.cnt);
-        float *d_bnd = carve<float>(p, sb.pl.bnd_floats);
-        uint32_t *d_ti = carve<uint32_t>(p, sb.acc);
-        uint32_t *d_tj = carve<uint32_t>(p, sb.acc);
-        float *d_pd = carve<float>(p, sb.acc);
-        uint8_t *d_mv = carve<uint8_t>(p, sb.acc);
-        HIP_TRY(ctx, hipMemcpyAsync(d_poff, poff[q].data(), sb.cnt * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipEventRecord(ev.e[0], ctx->stream));
-        if ((st = semi_fill(ctx, sb.pl, SemiForm::Traceback, d_jobs, d_aux, d_cost, nullptr, d_endj, d_bnd, ctx->d_tb_dir)) != RAWDTW_OK) return st;
-        HIP_TRY(ctx, hipEventRecord(ev.e[1], ctx->stream));
-        for (const SemiLaunch &L : sb.pl.launches) {
-            hipError_t e = launch_semi_walk(L.cls, d_jobs + L.first, L.count, d_aux + L.first, ctx->d_ev, ctx->d_ref, ctx->d_tb_dir, d_endj,
-                                            d_poff + L.first, d_plen + L.first, d_j0 + L.first, d_ti, d_tj, d_mv, d_pd, ctx->stream);
-            if (e != hipSuccess) return hip_fail(ctx, e, "semiglobal walk launch");
-        }
-        HIP_TRY(ctx, hipEventRecord(ev.e[2], ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(h_cost.data(), d_cost, sb.cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(h_len.data(), d_plen, sb.cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(h_j0.data(), d_j0, sb.cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(h_pd.data(), d_pd, sb.acc * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(h_mv.data(), d_mv, sb.acc, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ev.e[0], ev.e[1]) == hipSuccess) ctx->semi_fill_ms += ms;
-        if (hipEventElapsedTime(&ms, ev.e[1], ev.e[2]) == hipSuccess) ctx->semi_walk_ms += ms;
-        ctx->semi_dir_written += sb.pl.dir_bytes;
-        for (uint64_t pp = 0; pp < sb.cnt; pp++) {
-            const uint64_t k = sb.begin + sb.pl.order[pp];
-            out_cost[k] = h_cost[sb.pl.order[pp]]; // (cost and end_j are indexed inside the stretch, lengths and j0 by position)
-            out_j0[k] = h_j0[pp];
-            const uint32_t len = h_len[pp];
-            // start-first already (k_semi_finish); the reference pops the last element when exclude_last_element is set (dtw.cpp:744-748)
-            const uint32_t outlen = jobs[k].exclude_last ? len - 1 : len;
-            const uint64_t src = poff[q][pp], dst = path_off[k];
-            if (path_step) memcpy(path_step + dst, h_mv.data() + src, outlen);
-            else {
-                uint32_t i = 0, j = h_j0[pp];
-                for (uint32_t e = 0; e < outlen; e++) { i += h_mv[src + e] & 1u; j += h_mv[src + e] >> 1; path_i[dst + e] = i; path_j[dst + e] = j; }
-            }
-            memcpy(path_d + dst, h_pd.data() + src, (size_t)outlen * 4);
-            path_len[k] = outlen;
-            ctx->semi_path_elems += outlen;
-        }
-    }
-    return RAWDTW_OK;
+    static const TbPath semiglobal{&rawdtw_ctx::semi, false, true, "semiglobal workspace allocation failed", semi_job_dir_bytes, semi_stretch, semi_tb_fill,
+                                   semi_tb_walk, class_release};
+    return tb_run(ctx, semiglobal, jobs, n_jobs, TbOut{out_cost, out_j0, path_off, path_len, path_step, path_i, path_j, path_d}, nullptr);
 }
 
 } // namespace
@@ -263,7 +179,7 @@ int build_semi_plan(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, 
     rawdtw_plan *pl = new (std::nothrow) rawdtw_plan;
     if (!pl) return fail(ctx, RAWDTW_ERR_OOM, "host allocation failed");
     pl->ctx = ctx;
-    SemiPlan sp;
+    ClassPlan sp;
     try {
         semi_plan(ctx, jobs, n_jobs, SemiForm::Cost, sp);
         pl->order.resize(n_jobs); pl->h_jobs.resize(n_jobs);
@@ -278,7 +194,7 @@ int build_semi_plan(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, 
         pl->need_ref = std::max<uint64_t>(pl->need_ref, sp.jobs[p].ref_off + sp.jobs[p].m);
         pl->info.algorithmic_bytes += 4ull * ((uint64_t)sp.jobs[p].n + sp.jobs[p].m) + 4 + 32;
     }
-    for (const SemiLaunch &L : sp.launches) // (class order is longest last: the launches run in that order, as semi_fill's)
+    for (const ClassLaunch &L : sp.launches) // (class order is longest last: the launches run in that order, as semi_fill's)
         pl->launches.push_back(Launch{kKindSemiWave, L.cls == 4 ? 8 + 256 : semi_rpl(L.cls), L.first, L.count});
     for (uint32_t i = 0; i < pl->run_order.size(); i++) pl->run_order[i] = i;
     pl->info.n_jobs = n_jobs; pl->info.n_full_jobs = n_jobs; pl->info.n_launches = (uint32_t)pl->launches.size();
@@ -325,12 +241,7 @@ int rawdtw_semiglobal_traceback_steps(rawdtw_ctx *ctx, const rawdtw_job_t *jobs,
 
 int rawdtw_semiglobal_timing(const rawdtw_ctx *ctx, float *fill_ms, float *walk_ms, uint64_t *direction_bytes, uint64_t *path_elements)
 {
-    if (!ctx) return RAWDTW_ERR_INVALID;
-    if (fill_ms) *fill_ms = ctx->semi_fill_ms;
-    if (walk_ms) *walk_ms = ctx->semi_walk_ms;
-    if (direction_bytes) *direction_bytes = ctx->semi_dir_written;
-    if (path_elements) *path_elements = ctx->semi_path_elems;
-    return RAWDTW_OK;
+    return tb_timing_get(ctx, &rawdtw_ctx::semi, fill_ms, walk_ms, direction_bytes, path_elements);
 }
 
 int rawdtw_dtw_semiglobal(rawdtw_ctx *ctx, const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, float *cost)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """aln:s: made on the device (include/rawdtw.h, "aln text"; rawdtw_mapper_set_device_text): what rawdtw_mapper_finish costs with the
-setter off -- the parent's code: steps and distances home, snprintf an element on the pool -- and on, on the benchmark's cigar workload:
+setter off -- steps and distances home, the host formatter (rawdtw_aln_text_host) over them -- and on, on the benchmark's cigar workload:
 bench.py's reference (the S. cerevisiae chromosome lengths) and its synthetic reads (synth.SynthParams(max_chunks=6)), global border
 constraint + full fill, flag 0x4, mapped by the library's mapper until every read stopped; the finish alone is timed.
 Method: fresh mappers, off and on alternating in one process; one of each as a warm-up, then seven of each; the figure is the median of

@@ -393,6 +393,38 @@ def test_mapper_banded_cigar(orc, workload, plain_lines):
     assert subs == len(bc.sub_batches(jobs, 1)) >= 3 and small == lines
 
 
+class Spiked:
+    """the workload's reads with 3e10 in every 50th event of the first mappable read's chunks: its job's sums pass 1e10 at once, the walk leaves the
+    band's cells (rawdtw_banded_tb_host says so below) and the read has no path"""
+    def __init__(self, seeds):
+        self.seeds, self.reads = seeds, seeds.reads
+        self.SPIKED = next(r for r, rd in enumerate(seeds.reads) if rd["mappable"])
+
+    def read_job(self, r):
+        return self.seeds.read_job(r)
+
+    def chunk(self, r, c):
+        ev, hits = self.seeds.chunk(r, c)
+        if r == self.SPIKED:
+            ev = np.array(ev, np.float32)
+            ev[1::50] = 3e10
+        return ev, hits
+
+
+def test_mapper_banded_cigar_of_a_read_without_a_path(orc, workload):
+    """a mapped read whose banded job has no path: an empty aln:s:, alns:f: from the cost as ever.  dtw_min_score is lowered so that the
+    chain is kept at a cost beyond 1e10."""
+    ref, seeds = workload
+    spiked = (ref, Spiked(seeds))
+    opt = ra.MapOpt(flag=0x2 | 0x4, dtw_min_score=-1e30, **GLOBAL_BANDED)
+    plain = run_mapper(spiked, ra.MapOpt(flag=0x2, dtw_min_score=-1e30, **GLOBAL_BANDED), False)[0]
+    lines, events, _ = run_mapper(spiked, opt, True)
+    check_cigar_lines(orc, spiked, opt, lines, events, plain)
+    f = lines[spiked[1].SPIKED].split("\t")
+    assert "aln:s:" in f and any(x.startswith("alns:f:-") for x in f), [x[:40] for x in f if x.startswith("al")]
+    assert sum("\taln:s:(" in x for x in lines) >= 12
+
+
 def test_sparse_cigar_mapper_is_untouched_by_the_setter(workload):
     opt = ra.MapOpt(flag=0x2 | 0x4, dtw_border_constraint=1, dtw_fill_method=1)
     off = run_mapper(workload, opt, False)[0]

@@ -452,6 +452,48 @@ def test_mapper_cigar_from_host_events(ref, wr, mirror):
     same_lines(got, mirror["cigar"], "flag 0x4 from host events")
 
 
+class ShiftedHits:
+    """the whole reads with every seed hit D columns further left on the reference: the chains are the same (chaining sees differences
+    only), a chain's window starts D columns early, and its path starts at column j0 = D"""
+    D = 7
+
+    def __init__(self, wr):
+        self.wr, self.n_reads, self.lens, self.ref = wr, wr.n_reads, wr.lens, wr.ref
+
+    def n_chunks(self, r):
+        return self.wr.n_chunks(r)
+
+    def read_job(self, r):
+        return self.wr.read_job(r)
+
+    def chunk(self, r, c):
+        ev, hits = self.wr.chunk(r, c)
+        return ev, [(s, st, t - self.D if t >= self.D else t, q) for s, st, t, q in hits]
+
+
+def test_mapper_cigar_of_paths_that_start_past_column_0(ref, wr, monkeypatch):
+    """the local finish seeds j with j0 and formats through the host formatter: against mapper.map_reads with LocalScorer, whose paths
+    are rawdtw_semiglobal_tb_host's"""
+    shifted, j0s, cigar = ShiftedHits(wr), [], lc.cigar
+
+    def spy(a, b, s):
+        out = cigar(a, b, s)
+        j0s.append(out[4])
+        return out
+
+    monkeypatch.setattr(lc, "cigar", spy)
+    opt, copt = mc.whole_project_opts("cigar", 0)
+    opt.dtw_border_constraint = 2
+    want = mapper.map_reads(shifted, list(range(wr.n_reads)), lc.LocalScorer(ref), opt, StopOpt(), chain_opt=copt, output_chains=True)
+    assert len(j0s) >= 3 and min(j0s) > 0, j0s
+    e, cm = local_mapper(ref, wr, "cigar", groups=1)
+    got = mapper.map_reads_c(shifted, list(range(wr.n_reads)), cm)
+    cm.close()
+    e.close()
+    same_lines(got, want, "flag 0x4 with j0 > 0")
+    assert sum("\taln:s:(" in ln for ln in got[0]) >= 3
+
+
 def test_mapper_cigar_from_the_arena_in_rounds_from_signal(ref, wr, six, mirror):
     from tests.test_signal_round_gpu import _Signal
 

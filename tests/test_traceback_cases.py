@@ -1,5 +1,5 @@
 """The case lists of tests/traceback_cases.py have the properties they are there for -- shown on the oracle's paths alone, no
-device -- and the Python model of traceback_core's split cuts them as the GPU tests rely on."""
+device -- and the Python model of the traceback driver's split cuts them as the GPU tests rely on."""
 import numpy as np
 
 from tests import traceback_cases as tc

@@ -1,4 +1,4 @@
-"""The traceback's sub-batch pipeline (rawdtw_traceback.cpp: traceback_core) with more than one sub-batch, and the walk
+"""The traceback's sub-batch pipeline (rawdtw_tb_driver.cpp: tb_run) with more than one sub-batch, and the walk
 kernel's edges, against oracle.dtw_global_tb bit for bit: the cost bits, i, j, the distance bits and the length, with
 exclude_last's pop.  The budget is lowered with the context option "tb_workspace_mb"; "tb_sub_batches" must then equal what the
 plain-Python model of the split (tests/traceback_cases.py) says.  The lists and what they are there for: traceback_cases.py."""

@@ -1,16 +1,17 @@
-"""Case lists for the traceback's sub-batch pipeline (rawdtw_traceback.cpp: traceback_core) and the walk kernel's edges
+"""Case lists for the traceback's sub-batch pipeline (rawdtw_tb_driver.cpp: tb_run) and the walk kernel's edges
 (k_full_wave<., true, .>, k_tb_walk_wave<RPL>, k_tb_finish), shared by tests/test_traceback_cases.py (CPU: the lists have the
 properties they are there for) and tests/test_traceback_pipeline_gpu.py (the device against the oracle, bit for bit).
 
-Also a plain-Python model of how traceback_core cuts a batch into sub-batches, so that the GPU tests can say how many
+Also a plain-Python model of how the driver cuts a full-matrix batch into sub-batches, so that the GPU tests can say how many
 sub-batches a call must have had ("tb_sub_batches") and which jobs sit where."""
 import numpy as np
 
 MIB = 1 << 20
-DEFAULT_BUDGET = 16 << 30  # traceback_core without "tb_workspace_mb" and without RAWDTW_TB_WORKSPACE_MB
+DEFAULT_BUDGET = 16 << 30  # tb_budget_bytes without "tb_workspace_mb" and without RAWDTW_TB_WORKSPACE_MB
 
 
-# ---- the split, restated from rawdtw_capi.h:355-366 and rawdtw_traceback.cpp:78-86 ----------------------------------
+# ---- the split, restated from rawdtw_capi.h (full_rpl, dir_bytes_for), rawdtw_traceback.cpp (full_job_dir_bytes) and
+# rawdtw_tb_layout.h (split) -------------------------------------------------------------------------------------------
 def full_rpl(ny):
     """rows of the shorter side a lane of k_full_wave holds"""
     return 1 if ny <= 64 else 2 if ny <= 128 else 4 if ny <= 256 else 8
