@@ -423,6 +423,41 @@ int rawdtw_dtw_semiglobal_span(rawdtw_ctx *ctx, const float *a, uint32_t n, cons
 int rawdtw_semiglobal_span_host(const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, float *cost, uint32_t *j0,
                                 uint32_t *end_j);
 
+/* ---- semiglobal, in windows: the traceback above without n x m directions (opt-in by rawdtw_set_semiglobal_window).  The path touches
+ * the columns j0 .. end_j only; cell values do not depend on evaluation order, row 0 is assigned, and everything left of a column
+ * reaches the cells right of it through that column alone.  For a job (a, n, b, m) and a window width C (a multiple of 64):
+ *   checkpoints   column k C - 1 of D is kept, n floats, for every k >= 1 with k C - 1 < m; the cost-only pass writes them.
+ *   window        of a walk position (i, j), i > 0: the columns c_lo .. j with c_lo = (j / C) C.  Its cells are D's own: column
+ *                 c_lo - 1 is read from the checkpoint (for c_lo == 0 there is no column -1, as above), row 0 is assigned, and a cell's
+ *                 direction is coded by the walk's own two comparisons, exactly as the n x m form codes it.
+ *   walk          the rule above; "moves up without reading a neighbour" is GLOBAL column 0 only.  A step from column c_lo to column
+ *                 c_lo - 1 (left or diagonal) is emitted, and the walk goes on in the window of the new position.  It ends at i == 0.
+ *   result        the n x m form's on every value domain -- cost, end_j, j0, the path, exclude_last: the same cell values and the same
+ *                 comparisons, nothing numeric.
+ * Direction memory is one window a job (n C / 4 bytes in place of n m / 4) and (m / C) n floats of checkpoints; the cells filled with
+ * directions are those of the windows the walk enters, rows 0 .. i of each.
+ *   rawdtw_set_semiglobal_window, rawdtw_get_semiglobal_window   the window width of the context: 0 = off, the default; else a multiple
+ *        of 64 in [64, 2^20]; anything else is RAWDTW_ERR_INVALID and nothing is stored.  A setter, not an option.  Honoured by
+ *        rawdtw_semiglobal_traceback_steps, rawdtw_dtw_semiglobal_tb and, through its context, rawdtw_mapper_finish's local finish.
+ *        Refusals, statuses, path room (n + m - 1 a job) and the out arrays' contracts are those above, word for word.  A job with
+ *        m <= C is not windowed: it takes the n x m form's records and launches, in the same call.
+ *        rawdtw_semiglobal_timing afterwards: fill_ms is every fill launch (the cost form with checkpoints, and the n x m fills of the
+ *        jobs not windowed); walk_ms is the window launches -- refill and walk are one kernel and cannot be told apart -- plus the finish
+ *        launches and the other jobs' walks; direction_bytes is the workspace the jobs took (a windowed job: its window's directions
+ *        and its checkpoints, each rounded up to 256).
+ *   rawdtw_semiglobal_window_stats   of the context's most recent semiglobal traceback call: the jobs that were windowed, the windows
+ *        they entered in all and the most one job entered, and the bytes of their checkpoints (part of direction_bytes).  Any may be NULL.
+ *   rawdtw_semiglobal_tb_window_host   the definition restated on the host in O(n m / C + n C) memory (no device work): the yardstick
+ *        where rawdtw_semiglobal_tb_host's matrix is too large.  columns as the setter's (0 or m <= columns: the n x m form, *windows 0);
+ *        end_j and windows may be NULL. ---- */
+int rawdtw_set_semiglobal_window(rawdtw_ctx *ctx, uint32_t columns);
+int rawdtw_get_semiglobal_window(const rawdtw_ctx *ctx, uint32_t *columns);
+int rawdtw_semiglobal_window_stats(const rawdtw_ctx *ctx, uint64_t *jobs_windowed, uint64_t *windows, uint64_t *max_windows_a_job,
+                                   uint64_t *checkpoint_bytes);
+int rawdtw_semiglobal_tb_window_host(const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, uint32_t columns,
+                                     float *cost, uint32_t *end_j, uint32_t *path_len, uint32_t *path_i, uint32_t *path_j, float *path_d,
+                                     uint32_t *windows);
+
 /* ---- banded traceback: the path of a banded global job.  The reference has none (rmap.cpp:223-225 is assert(false)); this is the
  * one definition that agrees with both reference functions it sits between.  For a job (a, n, b, m, R), R = band_radius >= 0, i
  * indexing a and j indexing b, also when n < m and the reference swaps the two:

@@ -8,7 +8,7 @@ There is no CPU fallback: importing works anywhere, but every compute call needs
 ``librawdtw.so`` and a HIP device and raises otherwise.
 """
 from ._lib import LibraryMissing, RawDTWError, load_library, library_path  # noqa: F401
-from .dtw import ANCHOR_DTYPE, CHAIN_REC_DTYPE, JOB_DTYPE, RAWDTW_FULL, ROUND_OUT_DTYPE, SEED_DTYPE, DtwResult, Engine, Plan, ALN_REC_DTYPE, aln_text_bound, aln_text_host, banded_tb_host, chain_decline_host, expand_steps, round_end_host, round_keep_host, semiglobal_host, semiglobal_place_reduce, semiglobal_span_host  # noqa: F401
+from .dtw import ANCHOR_DTYPE, CHAIN_REC_DTYPE, JOB_DTYPE, RAWDTW_FULL, ROUND_OUT_DTYPE, SEED_DTYPE, DtwResult, Engine, Plan, ALN_REC_DTYPE, aln_text_bound, aln_text_host, banded_tb_host, chain_decline_host, expand_steps, round_end_host, round_keep_host, semiglobal_host, semiglobal_place_reduce, semiglobal_span_host, semiglobal_tb_window_host  # noqa: F401
 from .align import (  # noqa: F401
     RI_M_DTW_BORDER_CONSTRAINT_GLOBAL,
     RI_M_DTW_BORDER_CONSTRAINT_SPARSE,

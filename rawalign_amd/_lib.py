@@ -204,6 +204,11 @@ SYMBOLS = {
     "rawdtw_semiglobal_span_batch": (I32, [VP, VP, U64, VP, U64, VP, VP, VP]),
     "rawdtw_dtw_semiglobal_span": (I32, [VP, VP, U32, VP, U32, I32, C.POINTER(F32), C.POINTER(U32), C.POINTER(U32)]),
     "rawdtw_semiglobal_span_host": (I32, [VP, U32, VP, U32, I32, C.POINTER(F32), C.POINTER(U32), C.POINTER(U32)]),
+    "rawdtw_set_semiglobal_window": (I32, [VP, U32]),
+    "rawdtw_get_semiglobal_window": (I32, [VP, C.POINTER(U32)]),
+    "rawdtw_semiglobal_window_stats": (I32, [VP, C.POINTER(U64), C.POINTER(U64), C.POINTER(U64), C.POINTER(U64)]),
+    "rawdtw_semiglobal_tb_window_host": (I32, [VP, U32, VP, U32, I32, U32, C.POINTER(F32), C.POINTER(U32), C.POINTER(U32), VP, VP, VP,
+                                              C.POINTER(U32)]),
     "rawdtw_banded_traceback_steps": (I32, [VP, VP, U64, VP, U64, VP, VP, VP, VP, VP]),
     "rawdtw_banded_traceback_timing": (I32, [VP, C.POINTER(F32), C.POINTER(F32), C.POINTER(U64), C.POINTER(U64)]),
     "rawdtw_dtw_global_banded_tb": (I32, [VP, VP, U32, VP, U32, I32, I32, C.POINTER(F32), C.POINTER(U32), VP, VP, VP]),

@@ -4,6 +4,7 @@
 // There is NO CPU fallback in here: every scoring entry point runs the HIP kernels or returns an error status.
 #include "rawdtw_capi.h"
 #include "rawdtw_stream_layout.h"
+#include "rawdtw_semi_window.h"
 
 using namespace rawdtw;
 using namespace rawdtw::capi;
@@ -126,6 +127,7 @@ int rawdtw_destroy(rawdtw_ctx *ctx)
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
     if (ctx->tb_copy) (void)hipStreamDestroy(ctx->tb_copy);
     if (ctx->d_tb_dir) (void)hipFree(ctx->d_tb_dir);
+    if (ctx->d_semi_win_stats) (void)hipFree(ctx->d_semi_win_stats);
     if (ctx->d_tb_paths) (void)hipFree(ctx->d_tb_paths);
     if (ctx->tb_text) (void)hipStreamDestroy(ctx->tb_text);
     if (ctx->d_tb_text) (void)hipFree(ctx->d_tb_text);
@@ -177,6 +179,22 @@ int rawdtw_get_border_local(const rawdtw_ctx *ctx, int *on)
 {
     if (!ctx || !on) return RAWDTW_ERR_INVALID;
     *on = ctx->border_local ? 1 : 0;
+    return RAWDTW_OK;
+}
+
+// the window width of the semiglobal traceback (include/rawdtw.h, "semiglobal, in windows"): a setter too
+int rawdtw_set_semiglobal_window(rawdtw_ctx *ctx, uint32_t columns)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (!semi_window::valid_columns(columns)) return fail(ctx, RAWDTW_ERR_INVALID, "semiglobal window: 0 or a multiple of 64 in [64, 2^20]");
+    ctx->semi_window = columns;
+    return RAWDTW_OK;
+}
+
+int rawdtw_get_semiglobal_window(const rawdtw_ctx *ctx, uint32_t *columns)
+{
+    if (!ctx || !columns) return RAWDTW_ERR_INVALID;
+    *columns = ctx->semi_window;
     return RAWDTW_OK;
 }
 

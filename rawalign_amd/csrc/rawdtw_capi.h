@@ -145,6 +145,11 @@ struct rawdtw_ctx : rawdtw::Options { // (every option is a field of Options: ra
     struct rawdtw_keep_ws *keep_ws = nullptr;           // the store of kept chains and its launch's block (rawdtw_keep.hip), grow-only
     uint32_t chain_max_seeds = 0; // tests: RAWDTW_CHAIN_MAX_SEEDS lowers rawdtw_chain_round's cap on seeds a read, so that small rounds take the declined path (0: no)
     bool border_local = false;      // rawdtw_set_border_local: border_constraint 2 is accepted by the batch entry points and rawdtw_mapper_create
+    // rawdtw_set_semiglobal_window: columns a window of the semiglobal traceback (0: off, the n x m directions), the most recent traceback
+    // call's windows (rawdtw_semiglobal_window_stats) and the two words the window kernel counts into (allocated at the first windowed call)
+    uint32_t semi_window = 0;
+    uint64_t semi_win_jobs = 0, semi_win_windows = 0, semi_win_max = 0, semi_win_ckpt_bytes = 0;
+    unsigned long long *d_semi_win_stats = nullptr;
     bool local_jobs_device = true;  // a local batch from device arrays builds its job records on the device (k_local_jobs); tests: RAWDTW_LOCAL_JOBS=host
     std::string err;
 };

@@ -22,6 +22,7 @@
 
 #include "../../include/rawdtw.h"
 #include "rawdtw_sort_order.h"
+#include "rawdtw_semi_window.h"
 
 namespace {
 
@@ -693,6 +694,80 @@ extern "C" int rawdtw_semiglobal_tb_host(const float *a, uint32_t n, const float
 {
     if (!path_len) return RAWDTW_ERR_INVALID;
     return semiglobal_host(a, n, b, m, exclude_last, cost, end_j, path_len, path_i, path_j, path_d);
+}
+
+// The traceback in windows (include/rawdtw.h, "semiglobal, in windows") restated: one cost-only pass over two rolling rows that keeps
+// column k C - 1 for every k >= 1 (rawdtw_semi_window.h), then, as often as the walk enters one, the window lo(j) .. j refilled with one
+// direction byte a cell from the checkpoint column in front of it, rows 0 .. i only (the walk never moves down).  O(n m / C + n C) memory.
+extern "C" int rawdtw_semiglobal_tb_window_host(const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, uint32_t columns,
+                                                float *cost, uint32_t *end_j, uint32_t *path_len, uint32_t *path_i, uint32_t *path_j,
+                                                float *path_d, uint32_t *windows)
+{
+    namespace sw = rawdtw::semi_window;
+    if (!a || !b || !cost || !path_len || !path_i || !path_j || !path_d || n == 0 || m == 0 || !sw::valid_columns(columns)) return RAWDTW_ERR_INVALID;
+    if (windows) *windows = 0;
+    if (!sw::windowed(m, columns)) return semiglobal_host(a, n, b, m, exclude_last, cost, end_j, path_len, path_i, path_j, path_d);
+    const uint32_t C = columns;
+    auto dist = [](float x, float y) { return std::fabs(x - y); };
+    std::vector<float> prev(m), cur(m), ck(sw::ckpt_floats(n, m, C));
+    auto keep = [&](uint32_t i, const std::vector<float> &row) {
+        for (uint32_t col = C - 1; col < m; col += C) ck[sw::ckpt_at(n, C, col) + i] = row[col];
+    };
+    for (uint32_t j = 0; j < m; j++) prev[j] = dist(a[0], b[j]);
+    keep(0, prev);
+    for (uint32_t i = 1; i < n; i++) {
+        cur[0] = prev[0] + dist(a[i], b[0]);
+        for (uint32_t j = 1; j < m; j++) cur[j] = std::min(std::min(prev[j], cur[j - 1]), prev[j - 1]) + dist(a[i], b[j]);
+        keep(i, cur);
+        prev.swap(cur);
+    }
+    float best = prev[0];
+    uint32_t best_j = 0;
+    for (uint32_t j = 1; j < m; j++)
+        if (prev[j] < best) { best = prev[j]; best_j = j; }
+    *cost = exclude_last ? best - dist(a[n - 1], b[best_j]) : best;
+    if (end_j) *end_j = best_j;
+    std::vector<uint32_t> ri, rj;
+    std::vector<uint8_t> dir;
+    uint32_t i = n - 1, j = best_j, entered = 0;
+    ri.push_back(i); rj.push_back(j);
+    while (i > 0) {
+        const uint32_t c_lo = sw::lo(j, C), w = j - c_lo + 1, rows = i + 1;
+        const float *left_col = c_lo ? ck.data() + sw::ckpt_at(n, C, c_lo - 1) : nullptr; // column c_lo - 1 of D
+        entered++;
+        dir.assign((size_t)rows * w, 0);
+        prev.resize(w); cur.resize(w);
+        for (uint32_t x = 0; x < w; x++) prev[x] = dist(a[0], b[c_lo + x]);
+        for (uint32_t r = 1; r < rows; r++) {
+            for (uint32_t x = 0; x < w; x++) {
+                const float d = dist(a[r], b[c_lo + x]);
+                if (x == 0 && !left_col) { cur[0] = prev[0] + d; continue; } // global column 0: the running sum, no direction is read there
+                const float left = prev[x], top = x ? cur[x - 1] : left_col[r], topleft = x ? prev[x - 1] : left_col[r - 1];
+                cur[x] = std::min(std::min(left, top), topleft) + d;
+                dir[(size_t)r * w + x] = left < std::min(top, topleft) ? 1 : top < std::min(left, topleft) ? 2 : 0;
+            }
+            prev.swap(cur);
+        }
+        while (i > 0) {
+            if (j == 0) i--;
+            else {
+                const uint8_t c = dir[(size_t)i * w + (j - c_lo)];
+                if (c == 1) i--;
+                else if (c == 2) j--;
+                else { i--; j--; }
+            }
+            ri.push_back(i); rj.push_back(j);
+            if (j < c_lo) break; // the step out of the window is emitted; the walk goes on in the window of the new position
+        }
+    }
+    const uint32_t len = (uint32_t)ri.size() - (exclude_last ? 1u : 0u);
+    for (uint32_t q = 0; q < len; q++) {
+        path_i[q] = ri[ri.size() - 1 - q]; path_j[q] = rj[ri.size() - 1 - q];
+        path_d[q] = dist(a[path_i[q]], b[path_j[q]]);
+    }
+    *path_len = len;
+    if (windows) *windows = entered;
+    return RAWDTW_OK;
 }
 
 // The span (include/rawdtw.h, "span") restated forwards in O(m) memory: two rows of cost and two of S(i, j), the column in which the path

@@ -6,6 +6,7 @@
 // fallback: the kernels run or the call returns an error status.
 #include "rawdtw_capi.h"
 #include "rawdtw_semiglobal.h"
+#include "rawdtw_semi_window.h"
 #include "rawdtw_tb_driver.h"
 
 using namespace rawdtw;
@@ -15,21 +16,26 @@ namespace {
 
 enum class SemiForm { Cost, Traceback, Span };
 
-void semi_plan(const rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t cnt, SemiForm form, ClassPlan &pl)
+// columns (the traceback form only; rawdtw_semi_window.h): the window width; a class's windowed jobs (m > columns) follow its other
+// jobs as a launch of their own (ClassLaunch::max_k = 1), and a windowed job's stretch of the direction workspace is one window's
+// directions and its checkpoints.  0: no job is windowed, and keys, order and launches are what they were without the argument.
+void semi_plan(const rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t cnt, SemiForm form, ClassPlan &pl, uint32_t columns = 0)
 {
     std::vector<Keyed> keyed(cnt);
     const uint64_t lim = (1ull << 28) - 1;
     for (uint64_t k = 0; k < cnt; k++) {
         const rawdtw_job_t &j = jobs[k];
         const uint64_t c = (uint64_t)semi_class(j.n, j.m, ctx->full_wg);
-        keyed[k] = Keyed{(c << 56) | ((lim - std::min<uint64_t>(j.m, lim)) << 28) | (lim - std::min<uint64_t>(j.n, lim)), (uint32_t)k};
+        const uint64_t w = form == SemiForm::Traceback && semi_window::windowed(j.m, columns) ? 1 : 0;
+        keyed[k] = Keyed{(c << 57) | (w << 56) | ((lim - std::min<uint64_t>(j.m, lim)) << 28) | (lim - std::min<uint64_t>(j.n, lim)), (uint32_t)k};
     }
     sort_keyed(keyed);
     pl.order.resize(cnt); pl.jobs.resize(cnt); pl.aux.assign(cnt, FullAux{0, 0});
     for (uint64_t p = 0; p < cnt; p++) {
         const uint32_t k = keyed[p].idx;
         const rawdtw_job_t &j = jobs[k];
-        const int c = (int)(keyed[p].key >> 56);
+        const int c = (int)(keyed[p].key >> 57);
+        const uint32_t w = (uint32_t)(keyed[p].key >> 56) & 1u;
         pl.order[p] = k;
         DevJob &d = pl.jobs[p];
         d.ref_off = j.ref_off; d.read_off = j.read_off; d.n = j.n; d.m = j.m; d.R = -1;
@@ -38,9 +44,9 @@ void semi_plan(const rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t cnt, Se
         pl.bnd_floats += form == SemiForm::Span ? semi_span_bnd_floats(j.n, j.m, c) : semi_bnd_floats(j.n, j.m, c);
         if (form == SemiForm::Traceback) {
             pl.aux[p].dir_off = pl.dir_bytes;
-            pl.dir_bytes += (semi_dir_bytes(j.n, j.m, c) + 255) & ~255ull;
+            pl.dir_bytes += w ? semi_window::job_bytes(j.n, j.m, columns, (uint32_t)semi_rpl(c)) : (semi_dir_bytes(j.n, j.m, c) + 255) & ~255ull;
         }
-        if (pl.launches.empty() || pl.launches.back().cls != c) pl.launches.push_back(ClassLaunch{c, p, 0, 0});
+        if (pl.launches.empty() || pl.launches.back().cls != c || pl.launches.back().max_k != w) pl.launches.push_back(ClassLaunch{c, p, 0, w});
         pl.launches.back().count++;
     }
 }
@@ -143,6 +149,50 @@ int semi_tb_walk(rawdtw_ctx *ctx, const TbStretch &s, const TbSlot &slot)
     return RAWDTW_OK;
 }
 
+// The windowed form of the same (include/rawdtw.h, "semiglobal, in windows"; the context's rawdtw_set_semiglobal_window): a stretch's
+// windowed launches fill with k_semi_ckpt_wave (cost, end_j and the checkpoint columns) and walk with k_semi_window + k_semi_finish; its
+// jobs with m <= columns take the launches above, records and all.  Nothing here waits for the device.
+uint64_t semi_win_job_dir_bytes(const rawdtw_ctx *ctx, const rawdtw_job_t &j)
+{
+    if (!semi_window::windowed(j.m, ctx->semi_window)) return semi_job_dir_bytes(ctx, j);
+    return semi_window::job_bytes(j.n, j.m, ctx->semi_window, (uint32_t)semi_rpl(semi_class(j.n, j.m, ctx->full_wg)));
+}
+int semi_win_stretch(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t cnt, TbStretch *out)
+{
+    ClassPlan *pl = new ClassPlan;
+    semi_plan(ctx, jobs, cnt, SemiForm::Traceback, *pl, ctx->semi_window);
+    *out = class_stretch(pl, true);
+    return RAWDTW_OK;
+}
+int semi_win_fill(rawdtw_ctx *ctx, const TbStretch &s, const TbSlot &slot)
+{
+    const ClassPlan &pl = *static_cast<const ClassPlan *>(s.plan);
+    const uint64_t cnt = pl.jobs.size();
+    HIP_TRY(ctx, hipMemcpyAsync(slot.jobs, pl.jobs.data(), cnt * sizeof(DevJob), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(slot.aux, pl.aux.data(), cnt * sizeof(FullAux), hipMemcpyHostToDevice, ctx->stream));
+    for (const ClassLaunch &L : pl.launches) {
+        hipError_t e = L.max_k ? launch_semi_ckpt_wave(L.cls, slot.jobs + L.first, L.count, slot.aux + L.first, ctx->d_ev, ctx->d_ref, slot.cost, slot.endj,
+                                                       slot.bnd, ctx->d_tb_dir, ctx->semi_window, ctx->stream)
+                               : launch_semi_wave(L.cls, true, slot.jobs + L.first, L.count, slot.aux + L.first, ctx->d_ev, ctx->d_ref, slot.cost, slot.endj,
+                                                  slot.bnd, ctx->d_tb_dir, ctx->stream);
+        if (e != hipSuccess) return hip_fail(ctx, e, "semiglobal fill launch");
+    }
+    return RAWDTW_OK;
+}
+int semi_win_walk(rawdtw_ctx *ctx, const TbStretch &s, const TbSlot &slot)
+{
+    const ClassPlan &pl = *static_cast<const ClassPlan *>(s.plan);
+    for (const ClassLaunch &L : pl.launches) {
+        hipError_t e = L.max_k ? launch_semi_window(L.cls, slot.jobs + L.first, L.count, slot.aux + L.first, ctx->d_ev, ctx->d_ref, slot.bnd, ctx->d_tb_dir, slot.endj,
+                                                    slot.poff + L.first, slot.plen + L.first, slot.extra + L.first, slot.ti, slot.tj, slot.mv, slot.pd,
+                                                    ctx->semi_window, ctx->d_semi_win_stats, ctx->stream)
+                               : launch_semi_walk(L.cls, slot.jobs + L.first, L.count, slot.aux + L.first, ctx->d_ev, ctx->d_ref, ctx->d_tb_dir, slot.endj,
+                                                  slot.poff + L.first, slot.plen + L.first, slot.extra + L.first, slot.ti, slot.tj, slot.mv, slot.pd, ctx->stream);
+        if (e != hipSuccess) return hip_fail(ctx, e, "semiglobal walk launch");
+    }
+    return RAWDTW_OK;
+}
+
 // Exactly one of path_step and (path_i, path_j) is given.
 int semi_traceback(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, const float *h_events, uint64_t n_events, float *out_cost,
                    uint32_t *out_j0, const uint64_t *path_off, uint32_t *path_len, uint8_t *path_step, uint32_t *path_i, uint32_t *path_j,
@@ -159,7 +209,26 @@ int semi_traceback(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, c
     if (!arena && (st = rawdtw_upload_events(ctx, h_events, n_events)) != RAWDTW_OK) return st;
     static const TbPath semiglobal{&rawdtw_ctx::semi, false, true, "semiglobal workspace allocation failed", semi_job_dir_bytes, semi_stretch, semi_tb_fill,
                                    semi_tb_walk, class_release};
-    return tb_run(ctx, semiglobal, jobs, n_jobs, TbOut{out_cost, out_j0, path_off, path_len, path_step, path_i, path_j, path_d}, nullptr);
+    static const TbPath windowed{&rawdtw_ctx::semi, false, true, "semiglobal workspace allocation failed", semi_win_job_dir_bytes, semi_win_stretch, semi_win_fill,
+                                 semi_win_walk, class_release};
+    ctx->semi_win_jobs = ctx->semi_win_windows = ctx->semi_win_max = ctx->semi_win_ckpt_bytes = 0;
+    const TbOut out{out_cost, out_j0, path_off, path_len, path_step, path_i, path_j, path_d};
+    uint64_t win_jobs = 0, ckpt_bytes = 0;
+    for (uint64_t k = 0; k < n_jobs; k++)
+        if (semi_window::windowed(jobs[k].m, ctx->semi_window)) {
+            win_jobs++;
+            ckpt_bytes += semi_window::ckpt_bytes(jobs[k].n, jobs[k].m, ctx->semi_window);
+        }
+    if (!win_jobs) return tb_run(ctx, semiglobal, jobs, n_jobs, out, nullptr); // (setter off, or short-b jobs only: the call as it was)
+    // the window kernel's two counters: zeroed in front of the call's first launch, read once the driver has returned (its streams are idle)
+    if (!ctx->d_semi_win_stats) HIP_TRY(ctx, hipMalloc(&ctx->d_semi_win_stats, 2 * sizeof(unsigned long long)));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_semi_win_stats, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    if ((st = tb_run(ctx, windowed, jobs, n_jobs, out, nullptr)) != RAWDTW_OK) return st;
+    unsigned long long got[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpy(got, ctx->d_semi_win_stats, sizeof(got), hipMemcpyDeviceToHost));
+    ctx->semi_win_jobs = win_jobs; ctx->semi_win_ckpt_bytes = ckpt_bytes;
+    ctx->semi_win_windows = got[0]; ctx->semi_win_max = got[1];
+    return RAWDTW_OK;
 }
 
 } // namespace
@@ -242,6 +311,16 @@ int rawdtw_semiglobal_traceback_steps(rawdtw_ctx *ctx, const rawdtw_job_t *jobs,
 int rawdtw_semiglobal_timing(const rawdtw_ctx *ctx, float *fill_ms, float *walk_ms, uint64_t *direction_bytes, uint64_t *path_elements)
 {
     return tb_timing_get(ctx, &rawdtw_ctx::semi, fill_ms, walk_ms, direction_bytes, path_elements);
+}
+
+int rawdtw_semiglobal_window_stats(const rawdtw_ctx *ctx, uint64_t *jobs_windowed, uint64_t *windows, uint64_t *max_windows_a_job, uint64_t *checkpoint_bytes)
+{
+    if (!ctx) return RAWDTW_ERR_INVALID;
+    if (jobs_windowed) *jobs_windowed = ctx->semi_win_jobs;
+    if (windows) *windows = ctx->semi_win_windows;
+    if (max_windows_a_job) *max_windows_a_job = ctx->semi_win_max;
+    if (checkpoint_bytes) *checkpoint_bytes = ctx->semi_win_ckpt_bytes;
+    return RAWDTW_OK;
 }
 
 int rawdtw_dtw_semiglobal(rawdtw_ctx *ctx, const float *a, uint32_t n, const float *b, uint32_t m, int exclude_last, float *cost)

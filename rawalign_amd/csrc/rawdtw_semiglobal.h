@@ -45,5 +45,14 @@ hipError_t launch_semi_span_wave(int cls, const DevJob *jobs, uint64_t count, co
 hipError_t launch_semi_walk(int cls, const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev, const float *ref,
                             const uint8_t *dir_ws, const uint32_t *end_j, const uint64_t *path_off, uint32_t *path_len,
                             uint32_t *path_j0, uint32_t *tmp_i, uint32_t *tmp_j, uint8_t *path_mv, float *path_d, hipStream_t s);
+// The traceback in windows (rawdtw_semi_window.h): the cost form that also keeps the checkpoint columns (k_semi_ckpt_wave; dir_ws: the
+// jobs' stretches of window directions and checkpoints), and behind it the window kernel (k_semi_window: refill and walk, end-first
+// (i, j) into tmp_i / tmp_j; stats[0] += windows entered, stats[1] = max over jobs) followed by k_semi_finish as in launch_semi_walk
+hipError_t launch_semi_ckpt_wave(int cls, const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev, const float *ref,
+                                 float *out_cost, uint32_t *out_end_j, float *bnd_ws, uint8_t *dir_ws, uint32_t columns, hipStream_t s);
+hipError_t launch_semi_window(int cls, const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev, const float *ref,
+                              float *bnd_ws, uint8_t *dir_ws, const uint32_t *end_j, const uint64_t *path_off, uint32_t *path_len,
+                              uint32_t *path_j0, uint32_t *tmp_i, uint32_t *tmp_j, uint8_t *path_mv, float *path_d, uint32_t columns,
+                              unsigned long long *stats, hipStream_t s);
 
 } // namespace rawdtw

@@ -23,6 +23,7 @@
 #include "rawdtw_internal.h"
 #include "rawdtw_dp.h"
 #include "rawdtw_semiglobal.h"
+#include "rawdtw_semi_window.h"
 
 namespace rawdtw {
 
@@ -69,14 +70,22 @@ __device__ __forceinline__ uint32_t span_pick(float ab, float t_up, float left, 
 // one progress word.  Column -1's starts are 0 and so is every start a column-0 cell can choose from (the cell above it lies in
 // column 0, the other two in column -1): S(i, 0) = 0 whatever the values.  The scalar (minimum, step) pair gains the owner
 // lane's start of the cell that improved the minimum, read by the same branch.
-template <int RPL, bool TB, bool SPAN, int WAVES>
+//
+// CKPT (the cost form only; include/rawdtw.h, "semiglobal, in windows"): a lane that finishes a column == C - 1 (mod C) stores its RPL
+// values, rows inside the job only, into the job's checkpoints (rawdtw_semi_window.h: behind its window's directions in dir_ws).
+// Which lane that is, is decided by the scalar unit: with tm = t mod C and seg = t / C kept as scalar counters (no division in the
+// loop; C is a multiple of 64 and a wave has 64 lanes), lane l works on column t - l, so a checkpoint column is finished by lane 0 at
+// tm == C - 1 (checkpoint seg) and by lane tm + 1 at tm <= 62 (checkpoint seg - 1); at every other step, C - 64 of every C, the
+// vector unit sees nothing of it.  Progress words and fences are untouched.
+template <int RPL, bool TB, bool SPAN, int WAVES, bool CKPT = false>
 __device__ __forceinline__ void semi_wave_body(const DevJob *__restrict__ jobs, const FullAux *__restrict__ aux,
                                                const float *__restrict__ ev, const float *__restrict__ ref,
                                                float *__restrict__ out_cost, uint32_t *__restrict__ out_j0,
                                                uint32_t *__restrict__ out_end_j, float *__restrict__ bnd_ws,
-                                               uint8_t *__restrict__ dir_ws)
+                                               uint8_t *__restrict__ dir_ws, uint32_t ck_columns = 0)
 {
     static_assert(!(TB && SPAN), "the span form writes no directions");
+    static_assert(!CKPT || (!TB && !SPAN), "checkpoints are the cost form's");
     using word_t = typename SemiDirWord<RPL>::type;
     constexpr float kNone = __builtin_inff(); // beyond the matrix: loses every min (no sentinel, as in k_full_wave)
     const DevJob jb = jobs[blockIdx.x];
@@ -95,6 +104,8 @@ __device__ __forceinline__ void semi_wave_body(const DevJob *__restrict__ jobs, 
     const uint32_t slot_stride = SPAN ? 2u * row_stride : row_stride; // (a span slot: the costs, then the starts)
     float *bnd_base = bnd_ws + ax.bnd_off;
     uint4 *dirs = reinterpret_cast<uint4 *>(dir_ws + ax.dir_off);
+    float *ckpt = nullptr; // CKPT: the job's checkpoint columns
+    if constexpr (CKPT) ckpt = reinterpret_cast<float *>(dir_ws + ax.dir_off + semi_window::ckpt_off(NY, NX, ck_columns, RPL));
     __shared__ __attribute__((aligned(16))) word_t tbuf_all[TB ? WAVES * 64 * SPB : 1];
     word_t *tbuf = tbuf_all + (TB ? wv * 64 * SPB : 0);
     __shared__ uint32_t progress[WAVES]; // progress[s % WAVES] = (s << 21) | columns of strip s flushed
@@ -138,6 +149,7 @@ __device__ __forceinline__ void semi_wave_body(const DevJob *__restrict__ jobs, 
             float diag_in = kNone; // (row 0 has no corner to start from: it is assigned)
             float last_out = kNone, xval = 0.0f, xchunk = 0.0f, bchunk = kNone, wchunk = 0.0f;
             uint32_t sdiag_in = 0, slast_out = 0, sbchunk = 0, swchunk = 0; // SPAN: the starts beside diag_in, last_out, bchunk, wchunk
+            uint32_t ck_tm = 0, ck_seg = 0; // CKPT: t mod C and t / C (wave-uniform)
             for (uint32_t t = 0; t < steps; t++) {
                 if ((t & 63u) == 0) {
                     const uint32_t idx = t + lane;
@@ -197,11 +209,26 @@ __device__ __forceinline__ void semi_wave_body(const DevJob *__restrict__ jobs, 
                     diag_in = up_in;
                     last_out = v[RPL - 1];
                     if (SPAN) { sdiag_in = sup_in; slast_out = vs[RPL - 1]; }
+                    if constexpr (CKPT) {
+                        const bool first = ck_tm == ck_columns - 1; // lane 0 finishes column t
+                        if (first || ck_tm < 63u) {                  // (else: no lane is on a checkpoint column)
+                            // (lane tm + 1 at seg == 0 would be in front of column 0: it is not inside `x < NX`)
+                            if ((uint32_t)lane == (first ? 0u : ck_tm + 1u)) {
+                                float *col = ckpt + (uint64_t)(first ? ck_seg : ck_seg - 1u) * NY;
+#pragma unroll
+                                for (int k = 0; k < RPL; k++)
+                                    if (y0 + k < NY) col[y0 + k] = v[k];
+                            }
+                        }
+                    }
                     if (TB) {
                         // bit reversal puts cell k at bits 2k ("i - 1", shifted in first) and 2k + 1 ("j - 1")
                         const uint32_t w = __builtin_bitreverse32(code) >> (32 - 2 * RPL);
                         tbuf[lane * SPB + (t % SPB)] = (word_t)w;
                     }
+                }
+                if constexpr (CKPT) {
+                    if (++ck_tm == ck_columns) { ck_tm = 0; ck_seg++; }
                 }
                 if constexpr (KK >= 0) {
                     // (outside the lanes' `x < NX` block: a scalar register written under a divergent branch is no scalar to the compiler.  A lane
@@ -327,6 +354,170 @@ __global__ __launch_bounds__(64 * WAVES) void k_semi_span_wave(const DevJob *__r
                                                                uint32_t *__restrict__ out_end_j, float *__restrict__ bnd_ws)
 {
     semi_wave_body<RPL, false, true, WAVES>(jobs, aux, ev, ref, out_cost, out_j0, out_end_j, bnd_ws, nullptr);
+}
+
+// the cost form that also keeps the checkpoint columns of the traceback in windows (dir_ws: the job's stretch, rawdtw_semi_window.h)
+template <int RPL, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void k_semi_ckpt_wave(const DevJob *__restrict__ jobs, const FullAux *__restrict__ aux,
+                                                               const float *__restrict__ ev, const float *__restrict__ ref,
+                                                               float *__restrict__ out_cost, uint32_t *__restrict__ out_end_j,
+                                                               float *__restrict__ bnd_ws, uint8_t *__restrict__ dir_ws, uint32_t columns)
+{
+    semi_wave_body<RPL, false, false, WAVES, true>(jobs, aux, ev, ref, out_cost, nullptr, out_end_j, bnd_ws, dir_ws, columns);
+}
+
+// The traceback in windows (include/rawdtw.h, "semiglobal, in windows"), one wave per job, behind k_semi_ckpt_wave: as long as i > 0,
+// refill the window lo(j) .. j of the current position with directions -- k_semi_wave<., true>'s cells, codes and layout over the
+// window's columns, its column -1 the checkpoint in front of the window (v[], and the diagonal input of each lane's first row, which
+// for lane 0 of a strip below the first is the row above the strip), rows down to the strip that holds i only: the walk never moves
+// down --, then walk as k_semi_walk_wave does until i == 0 or a step leaves the window on the left (that step is emitted).  Strips run
+// in sequence on the one wave, also for jobs of the pipelined class; the boundary row between them is the job's own (the cost pass is
+// done with it), indexed by the column inside the window.  No spin-wait and no progress word: every round of the outer loop takes at
+// least one step of the walk, and a walk has at most n + m - 1 elements.
+// Output as k_semi_walk_wave's: (i, j) end-first into tmp_i / tmp_j, the length; k_semi_finish follows unchanged.  stats: windows
+// entered over the launch ([0], summed) and by one job at most ([1]).
+template <int RPL>
+__global__ __launch_bounds__(64) void k_semi_window(const DevJob *__restrict__ jobs, const FullAux *__restrict__ aux,
+                                                    const float *__restrict__ ev, const float *__restrict__ ref,
+                                                    float *__restrict__ bnd_ws, uint8_t *__restrict__ dir_ws,
+                                                    const uint32_t *__restrict__ end_j, const uint64_t *__restrict__ path_off,
+                                                    uint32_t *__restrict__ path_len, uint32_t *__restrict__ tmp_i,
+                                                    uint32_t *__restrict__ tmp_j, uint32_t columns, unsigned long long *__restrict__ stats)
+{
+    using word_t = typename SemiDirWord<RPL>::type;
+    constexpr float kNone = __builtin_inff();
+    constexpr uint32_t SPB = 16u / sizeof(word_t);
+    constexpr uint32_t STRIP = 64u * RPL;
+    __shared__ __attribute__((aligned(16))) word_t tbuf[64 * SPB]; // the fill's staging: [lane][step in block]
+    __shared__ __attribute__((aligned(16))) word_t row[64 * SPB];  // the walk's block row
+    const int lane = threadIdx.x;
+    const DevJob jb = jobs[blockIdx.x];
+    const FullAux ax = aux[blockIdx.x];
+    const float *Y = ev + jb.read_off;
+    const float *X = ref + jb.ref_off;
+    const uint32_t NY = jb.n, NX = jb.m, C = columns;
+    const uint64_t TXB = ((uint64_t)semi_window::width(NX, C) + 63u + SPB - 1) / SPB; // blocks per strip of a window
+    uint4 *dirs = reinterpret_cast<uint4 *>(dir_ws + ax.dir_off);
+    const float *ckpt = reinterpret_cast<const float *>(dir_ws + ax.dir_off + semi_window::ckpt_off(NY, NX, C, RPL));
+    float *bnd = bnd_ws + ax.bnd_off;
+    const uint64_t po = path_off[blockIdx.x];
+    uint32_t i = NY - 1, j = end_j[jb.aux], k = 1; // step 0: the end cell (lane 0's slot holds it)
+    if (j >= NX) j = NX - 1; // (never: the fill wrote a column of the matrix)
+    uint32_t bi = i, bj = j;
+    uint32_t entered = 0;
+    auto flush = [&](uint32_t upto) {
+        const uint32_t base = (upto - 1) & ~63u;
+        if ((uint32_t)lane <= ((upto - 1) & 63u)) { tmp_i[po + base + lane] = bi; tmp_j[po + base + lane] = bj; }
+    };
+    while (i > 0) {
+        const uint32_t c_lo = semi_window::lo(j, C), wcols = j - c_lo + 1; // wave-uniform
+        const float *ck = c_lo ? ckpt + semi_window::ckpt_at(NY, C, c_lo - 1) : nullptr; // column c_lo - 1 of D
+        const uint32_t ns = i / STRIP + 1; // strips that hold rows 0 .. i
+        entered++;
+        // ---- the fill ----
+        for (uint32_t s = 0; s < ns; s++) {
+            const uint32_t y0 = (s * 64u + lane) * RPL;
+            const uint32_t rows_here = (NY - s * STRIP) < STRIP ? (NY - s * STRIP) : STRIP;
+            const uint32_t lanes_here = (rows_here + RPL - 1) / RPL;
+            const uint32_t steps = wcols + lanes_here - 1;
+            const bool has_rows = y0 < NY;
+            const bool hands_down = (s + 1 < ns); // then the strip is full and lane 63 owns its last row
+            const bool row0 = (s == 0 && lane == 0);
+            float yv[RPL], v[RPL];
+#pragma unroll
+            for (int q = 0; q < RPL; q++) {
+                const uint32_t y = y0 + q < NY ? y0 + q : NY - 1;
+                yv[q] = Y[y];
+                v[q] = ck ? ck[y] : kNone; // column c_lo - 1
+            }
+            float diag_in = kNone; // D(y0 - 1, c_lo - 1)
+            if (ck && y0 > 0) diag_in = ck[y0 - 1 < NY ? y0 - 1 : NY - 1];
+            float last_out = kNone, xval = 0.0f, xchunk = 0.0f, bchunk = kNone, wchunk = 0.0f;
+            for (uint32_t t = 0; t < steps; t++) {
+                if ((t & 63u) == 0) {
+                    const uint32_t idx = t + lane;
+                    xchunk = X[c_lo + (idx < wcols ? idx : wcols - 1)];
+                    if (s > 0) bchunk = idx < wcols ? bnd[idx] : kNone;
+                }
+                const float x0 = read_lane(xchunk, (int)(t & 63u));
+                const float b0 = read_lane(bchunk, (int)(t & 63u));
+                const float up_in = wave_shr1(last_out, b0);
+                xval = wave_shr1(xval, x0);
+                const uint32_t x = t - (uint32_t)lane; // the column inside the window
+                if (x < wcols) {
+                    float d = diag_in, ab = up_in;
+                    uint32_t code = 0;
+#pragma unroll
+                    for (int q = 0; q < RPL; q++) {
+                        const float left = v[q];
+                        const float dd = dist(xval, yv[q]);
+                        float nv = min3f(ab, left, d) + dd;
+                        if (q == 0) nv = row0 ? dd : nv;
+                        // k_semi_wave<., true>'s two comparisons and bit planes, instruction for instruction
+                        float t_up, t_lf;
+                        asm("v_min_f32 %0, %1, %2" : "=v"(t_up) : "v"(left), "v"(d));
+                        asm volatile("v_cmp_lt_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(code) : "v"(ab), "v"(t_up) : "vcc");
+                        asm("v_min_f32 %0, %1, %2" : "=v"(t_lf) : "v"(ab), "v"(d));
+                        asm volatile("v_cmp_lt_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(code) : "v"(left), "v"(t_lf) : "vcc");
+                        d = left; ab = nv; v[q] = nv;
+                    }
+                    diag_in = up_in;
+                    last_out = v[RPL - 1];
+                    const uint32_t w = __builtin_bitreverse32(code) >> (32 - 2 * RPL);
+                    tbuf[lane * SPB + (t % SPB)] = (word_t)w;
+                }
+                if ((t % SPB) == SPB - 1 || t + 1 == steps) {
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                    const uint4 blk = *reinterpret_cast<const uint4 *>(&tbuf[lane * SPB]);
+                    if (has_rows) dirs[((uint64_t)s * TXB + t / SPB) * 64u + lane] = blk;
+                }
+                if (hands_down && t >= 63u) {
+                    const uint32_t c = t - 63u;
+                    const float v63 = read_lane(last_out, 63);
+                    if ((uint32_t)lane == (c & 63u)) wchunk = v63;
+                    if ((c & 63u) == 63u || c == wcols - 1) {
+                        const uint32_t base = c & ~63u;
+                        if (base + lane <= c) bnd[base + lane] = wchunk;
+                    }
+                }
+            }
+            __threadfence(); // the boundary row and the directions are read back by this wave, at addresses it has read before
+        }
+        // ---- the walk inside the window ----
+        uint64_t cur = ~0ull; // block row held in LDS (a refilled window has new ones)
+        while (i > 0) {
+            if (j == 0) i--; // global column 0 only
+            else {
+                const uint32_t sidx = i / STRIP, l = (i / RPL) & 63u, kk = i % RPL;
+                const uint32_t t = (j - c_lo) + l;
+                const uint64_t key = (uint64_t)sidx * TXB + t / SPB;
+                if (key != cur) {
+                    __builtin_amdgcn_s_barrier(); // (every lane has read the row that goes)
+                    reinterpret_cast<uint4 *>(row)[lane] = dirs[key * 64u + lane];
+                    cur = key;
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                    __builtin_amdgcn_s_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                }
+                uint32_t word = row[l * SPB + (t % SPB)];
+                word = (uint32_t)__builtin_amdgcn_readfirstlane((int)word);
+                const uint32_t code = (word >> (2 * kk)) & 3u;
+                if (code == 1u) i--;
+                else if (code == 2u) j--;
+                else { i--; j--; }
+            }
+            if ((uint32_t)lane == (k & 63u)) { bi = i; bj = j; }
+            k++;
+            if ((k & 63u) == 0) flush(k);
+            if (j < c_lo) break; // the step left the window (never at c_lo == 0)
+        }
+    }
+    if ((k & 63u) != 0) flush(k);
+    if (lane == 0) {
+        path_len[blockIdx.x] = k;
+        atomicAdd(&stats[0], (unsigned long long)entered);
+        atomicMax(&stats[1], (unsigned long long)entered);
+    }
 }
 
 // The walk, one wave per job: k_tb_walk_wave's (a block row of directions in LDS, all lanes in lockstep on uniform values, steps
@@ -458,6 +649,49 @@ hipError_t launch_semi_span_wave(int cls, const DevJob *jobs, uint64_t count, co
     case 4: return launch_semi_span_t<8, kFullWgWaves>(jobs, count, aux, ev, ref, out_cost, out_j0, out_end_j, bnd_ws, s);
     default: return hipErrorInvalidValue;
     }
+}
+
+template <int RPL, int WAVES>
+static hipError_t launch_semi_ckpt_t(const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev, const float *ref,
+                                     float *out_cost, uint32_t *out_end_j, float *bnd_ws, uint8_t *dir_ws, uint32_t columns, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_semi_ckpt_wave<RPL, WAVES>), dim3((uint32_t)count), dim3(64 * WAVES), 0, s, jobs, aux, ev, ref, out_cost,
+                       out_end_j, bnd_ws, dir_ws, columns);
+    return hipGetLastError();
+}
+
+hipError_t launch_semi_ckpt_wave(int cls, const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev, const float *ref,
+                                 float *out_cost, uint32_t *out_end_j, float *bnd_ws, uint8_t *dir_ws, uint32_t columns, hipStream_t s)
+{
+    if (count == 0) return hipSuccess;
+    switch (cls) {
+    case 0: return launch_semi_ckpt_t<1, 1>(jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, columns, s);
+    case 1: return launch_semi_ckpt_t<2, 1>(jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, columns, s);
+    case 2: return launch_semi_ckpt_t<4, 1>(jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, columns, s);
+    case 3: return launch_semi_ckpt_t<8, 1>(jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, columns, s);
+    case 4: return launch_semi_ckpt_t<8, kFullWgWaves>(jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, columns, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_semi_window(int cls, const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev, const float *ref,
+                              float *bnd_ws, uint8_t *dir_ws, const uint32_t *end_j, const uint64_t *path_off, uint32_t *path_len,
+                              uint32_t *path_j0, uint32_t *tmp_i, uint32_t *tmp_j, uint8_t *path_mv, float *path_d, uint32_t columns,
+                              unsigned long long *stats, hipStream_t s)
+{
+    if (count == 0) return hipSuccess;
+    const dim3 grid((uint32_t)count), block(64);
+    switch (cls) {
+    case 0: hipLaunchKernelGGL(k_semi_window<1>, grid, block, 0, s, jobs, aux, ev, ref, bnd_ws, dir_ws, end_j, path_off, path_len, tmp_i, tmp_j, columns, stats); break;
+    case 1: hipLaunchKernelGGL(k_semi_window<2>, grid, block, 0, s, jobs, aux, ev, ref, bnd_ws, dir_ws, end_j, path_off, path_len, tmp_i, tmp_j, columns, stats); break;
+    case 2: hipLaunchKernelGGL(k_semi_window<4>, grid, block, 0, s, jobs, aux, ev, ref, bnd_ws, dir_ws, end_j, path_off, path_len, tmp_i, tmp_j, columns, stats); break;
+    default: hipLaunchKernelGGL(k_semi_window<8>, grid, block, 0, s, jobs, aux, ev, ref, bnd_ws, dir_ws, end_j, path_off, path_len, tmp_i, tmp_j, columns, stats); break;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_semi_finish, grid, dim3(256), 0, s, jobs, (uint32_t)count, ev, ref, path_off, path_len, tmp_i, tmp_j,
+                       path_j0, path_mv, path_d);
+    return hipGetLastError();
 }
 
 hipError_t launch_semi_walk(int cls, const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev, const float *ref,

@@ -288,6 +288,25 @@ class Engine:
         self._check(self.lib.rawdtw_get_border_local(self._ctx, C.byref(v)))
         return bool(v.value)
 
+    def set_semiglobal_window(self, columns: int = 0):
+        """rawdtw_set_semiglobal_window: semiglobal tracebacks on this context (semiglobal_traceback, DTW_semiglobal_tb, a mapper's local
+        finish) keep one window of `columns` columns of directions a job and checkpoint columns in place of n x m directions
+        (include/rawdtw.h, "semiglobal, in windows").  0: off, the default; else a multiple of 64 in [64, 2^20]."""
+        if not 0 <= int(columns) < 1 << 32:
+            raise RawDTWError(1, "semiglobal window: 0 or a multiple of 64 in [64, 2^20]")
+        self._check(self.lib.rawdtw_set_semiglobal_window(self._ctx, int(columns)))
+
+    def get_semiglobal_window(self) -> int:
+        v = C.c_uint32()
+        self._check(self.lib.rawdtw_get_semiglobal_window(self._ctx, C.byref(v)))
+        return int(v.value)
+
+    def semiglobal_window_stats(self) -> dict:
+        """rawdtw_semiglobal_window_stats of the context's most recent semiglobal traceback call"""
+        j, w, mx, ck = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.lib.rawdtw_semiglobal_window_stats(self._ctx, C.byref(j), C.byref(w), C.byref(mx), C.byref(ck)))
+        return {"jobs_windowed": j.value, "windows": w.value, "max_windows_a_job": mx.value, "checkpoint_bytes": ck.value}
+
     def get_option(self, name: str) -> int:
         """rawdtw_get_option: any option of include/rawdtw.h's option block -- a settable one as it is stored (what set_option made of its
         value, or the default), and the read-only "tb_sub_batches", "round_end_kernel_us" and "round_keep_kernel_us" """
@@ -860,10 +879,13 @@ class Engine:
                                                         C.byref(j0), C.byref(ej)))
         return np.float32(c.value), j0.value, ej.value
 
-    def semiglobal_place(self, reads, targets, exclude_last=False) -> dict:
+    def semiglobal_place(self, reads, targets, exclude_last=False, paths=False) -> dict:
         """Seed-free placement: every read window (read_off, n) of the event arena against every target window (ref_off, m) of the
         reference arena (both strands of every sequence, say) in one semiglobal_span call of len(reads) x len(targets) jobs, read-major;
-        then, on the host, `semiglobal_place_reduce` over each read's row -> {target, cost, j0, end_j, second}, one of each a read."""
+        then, on the host, `semiglobal_place_reduce` over each read's row -> {target, cost, j0, end_j, second}, one of each a read.
+        paths: the winners, one job a read (a read without a winner: its target 0), go through semiglobal_traceback -- in windows where
+        set_semiglobal_window is on -- and the dict gains path_off, path_len, step and distance, and the traceback's own cost and j0 as
+        tb_cost and tb_j0; nothing is compared here."""
         reads = np.asarray(reads, np.int64).reshape(-1, 2)
         targets = np.asarray(targets, np.int64).reshape(-1, 2)
         jobs = np.zeros(len(reads) * len(targets), JOB_DTYPE)
@@ -874,7 +896,13 @@ class Engine:
         jobs["band_radius"], jobs["exclude_last"] = RAWDTW_FULL, int(bool(exclude_last))
         shape = (len(reads), len(targets))
         cost, j0, end_j = self.semiglobal_span(jobs)
-        return semiglobal_place_reduce(cost.reshape(shape), j0.reshape(shape), end_j.reshape(shape))
+        placed = semiglobal_place_reduce(cost.reshape(shape), j0.reshape(shape), end_j.reshape(shape))
+        if not paths:
+            return placed
+        winners = jobs[np.arange(len(reads)) * len(targets) + np.maximum(placed["target"], 0)] if len(targets) else jobs[:0]
+        tb_cost, tb_j0, off, plen, step, pd = self.semiglobal_traceback(winners)
+        placed.update(path_off=off, path_len=plen, step=step, distance=pd, tb_cost=tb_cost, tb_j0=tb_j0)
+        return placed
 
     def DTW_global_banded_tb(self, a_values, b_values, band_radius, exclude_last=False) -> DtwResult:
         """The banded cost of DTW_global_slantedbanded_antidiagonalwise and the path DTW_global_tb's walk takes through the band's cells
@@ -1013,6 +1041,24 @@ def semiglobal_host(a_values, b_values, exclude_last_element=False, traceback=Fa
         raise RawDTWError(st, "rawdtw_semiglobal_tb_host refused its arguments")
     k = ln.value
     return DtwResult(np.float32(c.value), pi[:k].copy(), pj[:k].copy(), pd[:k].copy()), ej.value
+
+
+def semiglobal_tb_window_host(a_values, b_values, columns, exclude_last_element=False):
+    """rawdtw_semiglobal_tb_window_host: the traceback in windows (include/rawdtw.h, "semiglobal, in windows") restated on the host in
+    O(n m / C + n C) memory, no device -> (DtwResult, end_j, windows entered)"""
+    lib = load_library()
+    a, b = _f32(a_values), _f32(b_values)
+    c, ej, ln, wn = C.c_float(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    cap = max(len(a) + len(b) - 1, 1)
+    pi, pj, pd = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.float32)
+    if not 0 <= int(columns) < 1 << 32:
+        raise RawDTWError(1, "rawdtw_semiglobal_tb_window_host refused its arguments")
+    st = lib.rawdtw_semiglobal_tb_window_host(_ptr(a), len(a), _ptr(b), len(b), int(exclude_last_element), int(columns), C.byref(c), C.byref(ej),
+                                              C.byref(ln), _ptr(pi), _ptr(pj), _ptr(pd), C.byref(wn))
+    if st != 0:
+        raise RawDTWError(st, "rawdtw_semiglobal_tb_window_host refused its arguments")
+    k = ln.value
+    return DtwResult(np.float32(c.value), pi[:k].copy(), pj[:k].copy(), pd[:k].copy()), ej.value, wn.value
 
 
 def semiglobal_span_host(a_values, b_values, exclude_last_element=False):
