@@ -54,6 +54,13 @@ __device__ __forceinline__ float read_lane(float v, int l)
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
 }
 
+// (a start column travels between lanes as a value does)
+__device__ __forceinline__ uint32_t wave_shr1(uint32_t v, uint32_t fill)
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x138, 0xf, 0xf, false);
+}
+__device__ __forceinline__ uint32_t read_lane(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
+
 __device__ __forceinline__ float wave_shl1(float v, float fill)
 {
     // lane l receives lane l+1's value; lane 63 keeps `fill`  (DPP wave_shl:1 = 0x130)

@@ -47,7 +47,6 @@ constexpr uint32_t kStreamTileFloats = 5800; // k_runs: image + the pass's recor
 static_assert(kStreamTileFloats <= kStreamMaxImageFloats, "the default image is one the option admits");
 constexpr uint32_t kTileHiLdsFloats = 14336, kTileHiMaxJobs = 64; // wide-band instance: one wave per tile
 constexpr uint32_t kSpanGapFloats = 48; // a window starting this close behind a span extends it instead of opening a new one
-constexpr int kFullWgWaves = 4;        // waves per job in the pipelined-strip variant of the full-matrix kernel
 constexpr int kMaxWregChunks = 32;     // register-resident wave kernel: radius + 1 <= 64 * 32
 constexpr int kMaxWaveBandK = 13000;   // 3*K floats of LDS must fit 160 KiB
 
@@ -183,10 +182,10 @@ hipError_t launch_band_wreg(int chunks, const DevJob *jobs, uint64_t count, cons
                             const float *ref, float *out, hipStream_t s);
 hipError_t launch_band_wave(const DevJob *jobs, uint64_t count, uint32_t lds_floats,
                             const float *ev, const float *ref, float *out, hipStream_t s);
-hipError_t launch_full_wave(int rows_per_lane, bool traceback, const DevJob *jobs, uint64_t count,
+hipError_t launch_full_wave(int cls, bool traceback, const DevJob *jobs, uint64_t count,
                             const FullAux *aux, const float *ev, const float *ref, float *out,
                             float *bnd_ws, uint8_t *dir_ws, hipStream_t s);
-hipError_t launch_tb_walk_wave(const DevJob *jobs, uint64_t count, const FullAux *aux, int rpl, const float *ev,
+hipError_t launch_tb_walk_wave(const DevJob *jobs, uint64_t count, const FullAux *aux, int cls, const float *ev,
                                const float *ref, const uint8_t *dir_ws, const uint64_t *path_off, uint32_t *path_len,
                                uint32_t *tmp_i, uint32_t *tmp_j, uint8_t *path_mv, float *path_d, hipStream_t s);
 hipError_t launch_tb_finish(const DevJob *jobs, uint64_t count, const float *ev, const float *ref, const uint64_t *path_off,

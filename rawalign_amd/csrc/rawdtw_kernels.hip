@@ -12,6 +12,7 @@
 // -ffp-contract=off.
 #include "rawdtw_internal.h"
 #include "rawdtw_dp.h"
+#include "rawdtw_wavefront.h"
 
 namespace rawdtw {
 
@@ -258,17 +259,7 @@ __global__ __launch_bounds__(64) void k_band_wave(const DevJob *__restrict__ job
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// Full-matrix wavefront (DTW_global / DTW_global_tb fill).  One wave per job.  The shorter
-// sequence Y is laid over lanes, RPL consecutive rows per lane, 64*RPL rows per strip; the
-// longer sequence X is swept column by column with a one-column skew per lane (lane l works on
-// column t-l at step t), so every step advances a 64-cell-wide anti-diagonal wavefront whose
-// cells exchange values through DPP wave shifts only.  The DTW recurrence is symmetric under
-// transposition, so which operand is "a" does not change any cell value.  Strips hand their
-// last row to the next strip through a boundary row in HBM, read and written in 64-float
-// chunks.  With TB the 2-bit move of dtw.cpp:633-646 is decided at fill time from the same
-// three values and packed RPL codes per lane per step.
-// ---------------------------------------------------------------------------------------------
+// four jobs per wave for bands of at most 16 offsets (radius <= 15) ...
 __global__ __launch_bounds__(64) void k_band_grp16(const DevJob *__restrict__ jobs, uint32_t count,
                                                    const float *__restrict__ ev,
                                                    const float *__restrict__ ref,
@@ -361,15 +352,14 @@ __global__ __launch_bounds__(256) void k_band_merged(const TileDesc *__restrict_
     tile_block<0, kMaxLaneRadius, true, 256>(win, tiles[b], spans, tjobs, masks, ev, ref, out);
 }
 
-template <int RPL> struct DirWord { using type = uint8_t; };
-template <> struct DirWord<8> { using type = uint16_t; };
-
-// WAVES = 1: one wave per job, strips in sequence.  WAVES = 4 (jobs with several strips): the four waves
-// of a workgroup take strips w, w+4, ... and run them as a pipeline -- strip s+1 trails strip s by at
-// least one 64-column chunk -- so a long job finishes up to four times sooner (a launch of long jobs is
-// bounded by its longest job, not by throughput).  Boundary rows then form a ring of WAVES rows in HBM;
-// a strip publishes how many of its columns are flushed through an LDS progress word (strip index in the
-// high bits, so the word only ever grows) and its successor spins on that word before each chunk load.
+// ---------------------------------------------------------------------------------------------
+// Full-matrix wavefront (DTW_global / DTW_global_tb fill): the strip loop described in rawdtw_wavefront.h, with the global borders.  The
+// shorter sequence lies over the lanes and the longer one is swept: the DTW recurrence is symmetric under transposition, so
+// which operand is "a" does not change any cell value -- only, with TB, which bit plane of a direction code means i - 1
+// (`swapped`).  Row 0 and column 0 are running sums: the virtual row above row 0 is +inf, its corner D[-1][-1] is 0 so that
+// D[0][0] = dist.  WAVES = kFullWgWaves: jobs of three strips or more, a long job finishes up to four times sooner (a launch
+// of long jobs is bounded by its longest job, not by throughput).
+// ---------------------------------------------------------------------------------------------
 template <int RPL, bool TB, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void k_full_wave(const DevJob *__restrict__ jobs,
                                                   const FullAux *__restrict__ aux,
@@ -378,12 +368,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_full_wave(const DevJob *__restri
                                                   float *__restrict__ out, float *__restrict__ bnd_ws,
                                                   uint8_t *__restrict__ dir_ws)
 {
-    using word_t = typename DirWord<RPL>::type;
-    // DTW_global and DTW_global_tb have no sentinel (dtw.cpp:37-66, 595-667: row 0 and column 0 are running sums, whatever they
-    // pass), so what lies beyond the matrix must lose every min: +inf, not the banded DP's 1e10 -- a border sum above 1e10 would
-    // otherwise be replaced by it, and the direction codes of the interior decided from the replaced values.  Every cell has a
-    // finite neighbour or the corner's 0, so no cell of the matrix is ever +inf itself.
-    constexpr float kNone = __builtin_inff();
+    using word_t = typename wf::DirWord<RPL>::type;
+    constexpr uint32_t SPB = wf::SPB<RPL>;
+    constexpr float kNone = wf::kNone;
     const DevJob jb = jobs[blockIdx.x];
     const FullAux ax = aux[blockIdx.x];
     const int lane = threadIdx.x & 63;
@@ -397,10 +384,6 @@ __global__ __launch_bounds__(64 * WAVES) void k_full_wave(const DevJob *__restri
     const uint32_t NY = swapped ? jb.m : jb.n;
     constexpr uint32_t STRIP = 64u * RPL;
     const uint32_t nstrips = (NY + STRIP - 1) / STRIP;
-    // Direction words are written in blocks of SPB steps: a lane's SPB consecutive words are 16 contiguous
-    // bytes, so a block leaves the wave as one 1-KiB dwordx4 store ([strip][block][lane][step in block]).
-    // Per step the word goes to LDS (2 KiB transposition buffer), per block each lane reads back its 16 bytes.
-    constexpr uint32_t SPB = 16u / sizeof(word_t);
     const uint32_t TXB = (NX + 63 + SPB - 1) / SPB; // blocks per strip
     const uint32_t row_stride = (NX + 63u) & ~63u; // floats per boundary row (matches the planner)
     float *bnd_base = bnd_ws + ax.bnd_off;
@@ -430,10 +413,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_full_wave(const DevJob *__restri
         const uint32_t steps = NX + lanes_here - 1;
         const bool has_rows = y0 < NY;
         const bool hands_down = (s + 1 < nstrips); // then the strip is full and lane 63 owns its last row
-        // virtual row above row 0 is +inf, its corner D[-1][-1] is 0 so that D[0][0] = dist
-        float diag_in = (s == 0 && lane == 0) ? 0.0f : kNone;
+        float diag_in = (s == 0 && lane == 0) ? 0.0f : kNone; // the corner
         float last_out = kNone, xval = 0.0f, xchunk = 0.0f, bchunk = kNone, wchunk = 0.0f;
-        // (bit of the 2-bit code each plane sets: "up" bit 0 and "lf" bit 1, the other way round for a swapped job)
 
         for (uint32_t t = 0; t < steps; t++) {
             if ((t & 63u) == 0) {
@@ -462,41 +443,15 @@ __global__ __launch_bounds__(64 * WAVES) void k_full_wave(const DevJob *__restri
                 for (int k = 0; k < RPL; k++) {
                     const float left = v[k];
                     const float nv = min3f(ab, left, d) + dist(xval, yv[k]);
-                    if (TB) {
-                        // dtw.cpp:633-646 with left = D[i-1][j], top = D[i][j-1] (i over a, j over b):
-                        //   left < min(top, tl) -> 1 (i-1) ; else top < min(left, tl) -> 2 (j-1) ; else 0.
-                        // In kernel coordinates: up = ab (row-1), lf = left (column-1).  "up strictly best"
-                        // and "lf strictly best" exclude each other, so the code is two bit planes; Y rows
-                        // are a-indices unless swapped, which only decides which plane is bit 0.
-                        // Six instructions a cell: per plane v_min_f32 (as the instruction: through fminf the compiler quiets
-                        // signalling NaNs first, two more instructions an operand), v_cmp_lt_f32 into VCC and v_addc_co_u32
-                        // code = 2 code + VCC -- the compare's bit shifts in from below, no select, no shift-or.  The word grows
-                        // most significant cell first, "up" before "lf": turned round behind the loop (below).
-                        float t_up, t_lf;
-                        asm("v_min_f32 %0, %1, %2" : "=v"(t_up) : "v"(left), "v"(d));
-                        asm volatile("v_cmp_lt_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(code) : "v"(ab), "v"(t_up) : "vcc");
-                        asm("v_min_f32 %0, %1, %2" : "=v"(t_lf) : "v"(ab), "v"(d));
-                        asm volatile("v_cmp_lt_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(code) : "v"(left), "v"(t_lf) : "vcc");
-                    }
+                    // dtw.cpp:633-646 with left = D[i-1][j], top = D[i][j-1] (i over a, j over b): Y rows are a-indices unless swapped
+                    if (TB) code = wf::dir_code(code, ab, left, d);
                     d = left; ab = nv; v[k] = nv;
                 }
                 diag_in = up_in;
                 last_out = v[RPL - 1];
-                if (TB) {
-                    // bit reversal puts cell k at bits 2k ("up", shifted in first) and 2k + 1 ("lf"): the layout of sh_up = 0,
-                    // sh_lf = 1; a swapped job has the planes the other way round -- its adjacent bits change places
-                    uint32_t w = __builtin_bitreverse32(code) >> (32 - 2 * RPL);
-                    if (swapped) w = ((w & 0x55555555u) << 1) | ((w >> 1) & 0x55555555u);
-                    tbuf[lane * SPB + (t % SPB)] = (word_t)w;
-                }
+                if (TB) wf::dir_put<RPL>(tbuf, lane, t, code, swapped);
             }
-            if (TB && ((t % SPB) == SPB - 1 || t + 1 == steps)) {
-                // same wave wrote and reads the buffer; LDS operations of a wave complete in order, the
-                // fence keeps the compiler from reordering the differently typed accesses
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                const uint4 blk = *reinterpret_cast<const uint4 *>(&tbuf[lane * SPB]);
-                if (has_rows) dirs[((uint64_t)s * TXB + t / SPB) * 64u + lane] = blk;
-            }
+            if (TB && ((t % SPB) == SPB - 1 || t + 1 == steps)) wf::dir_flush<RPL>(tbuf, dirs, TXB, s, t, lane, has_rows);
             if (hands_down && t >= 63u) {
                 // lane 63 finished column c = t-63 in this step; gather 64 of them, store coalesced
                 const uint32_t c = t - 63u;
@@ -532,12 +487,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_full_wave(const DevJob *__restri
     }
 }
 
-// Traceback walk, one wave per job.  (A lane-per-job walk chases one direction word per step through HBM:
-// ~3.5 us per step, 5 ms for a thousand 1500-step paths.)  The direction buffer is laid out in 1-KiB block rows
-// ([strip][block][lane][step in block]) and a path moving up the diagonal stays ~7 steps inside one block row: the
-// wave fetches the block row with one coalesced load into LDS and all lanes then walk it in lockstep on uniform
-// values.  Steps are buffered one per lane and leave as coalesced 64-step stores.  Output: (i, j) end-first; the
-// distances and the start-first order are produced afterwards by k_tb_finish, one thread per path element.
+// Traceback walk, one wave per job (rawdtw_wavefront.h): from (n - 1, m - 1) to (0, 0), along row 0 and column 0 without a
+// direction word.  Output: (i, j) end-first; the distances and the start-first order are produced afterwards by k_tb_finish.
 template <int RPL>
 __global__ __launch_bounds__(64) void k_tb_walk_wave(const DevJob *__restrict__ jobs, const FullAux *__restrict__ aux,
                                                      const uint8_t *__restrict__ dir_ws,
@@ -545,64 +496,33 @@ __global__ __launch_bounds__(64) void k_tb_walk_wave(const DevJob *__restrict__ 
                                                      uint32_t *__restrict__ path_len, uint32_t *__restrict__ tmp_i,
                                                      uint32_t *__restrict__ tmp_j)
 {
-    using word_t = typename DirWord<RPL>::type;
-    constexpr uint32_t SPB = 16u / sizeof(word_t);
-    __shared__ __attribute__((aligned(16))) word_t row[64 * SPB]; // one block row: [lane][step in block]
+    using word_t = typename wf::DirWord<RPL>::type;
+    __shared__ __attribute__((aligned(16))) word_t row[64 * wf::SPB<RPL>]; // one block row: [lane][step in block]
     const int lane = threadIdx.x;
     const DevJob jb = jobs[blockIdx.x];
     const FullAux ax = aux[blockIdx.x];
     const bool swapped = jb.n > jb.m;
     const uint32_t NX = swapped ? jb.n : jb.m;
-    const uint64_t TXB = ((uint64_t)NX + 63u + SPB - 1) / SPB; // blocks per strip
+    const uint64_t TXB = wf::strip_blocks<RPL>((uint64_t)NX);
     const uint4 *dirs = reinterpret_cast<const uint4 *>(dir_ws + ax.dir_off);
     const uint64_t po = path_off[blockIdx.x];
-    uint32_t i = jb.n - 1, j = jb.m - 1, k = 0;
-    uint32_t bi = i, bj = j; // this lane's slot of the 64-step output buffer (lane = step & 63)
-    uint64_t cur = ~0ull;    // block row held in LDS (prefetching the next one was measured: no gain, the walk's own
-                             // dependent chain -- LDS read, decode, branch -- is what a step costs)
-    auto flush = [&](uint32_t upto) { // steps [upto - ((upto - 1) & 63) - 1 .. upto) sit in lanes 0..(upto-1)&63
-        const uint32_t base = (upto - 1) & ~63u;
-        if ((uint32_t)lane <= ((upto - 1) & 63u)) { tmp_i[po + base + lane] = bi; tmp_j[po + base + lane] = bj; }
-    };
-    // step 0: the end cell
-    if (lane == 0) { bi = i; bj = j; }
-    k = 1;
+    uint32_t i = jb.n - 1, j = jb.m - 1, k = 1;
+    wf::PathBuf path{tmp_i, tmp_j, po, lane, i, j};
+    uint64_t cur = ~0ull;
     while (i > 0 || j > 0) {
         if (i == 0) j--;
         else if (j == 0) i--;
         else {
-            const uint32_t y = swapped ? j : i, x = swapped ? i : j;
-            const uint32_t sidx = y / (64u * RPL), l = (y / RPL) & 63u, kk = y % RPL;
-            const uint32_t t = x + l;
-            const uint64_t key = (uint64_t)sidx * TXB + t / SPB;
-            if (key != cur) {
-                reinterpret_cast<uint4 *>(row)[lane] = dirs[key * 64u + lane];
-                cur = key;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            }
-            uint32_t word = row[l * SPB + (t % SPB)];
-            word = (uint32_t)__builtin_amdgcn_readfirstlane((int)word);
-            const uint32_t code = (word >> (2 * kk)) & 3u;
-            if (code == 1u) i--;
-            else if (code == 2u) j--;
-            else { i--; j--; }
-            // (the next block row may overwrite `row` only after every lane has read this word: the barrier above
-            // is the only writer and all lanes reach it together, the walk being uniform)
+            const wf::WalkPos p = wf::walk_step<RPL, false>({i, j, cur}, dirs, row, TXB, lane, swapped ? j : i, swapped ? i : j);
+            i = p.i; j = p.j; cur = p.cur;
         }
-        if ((uint32_t)lane == (k & 63u)) { bi = i; bj = j; }
-        k++;
-        if ((k & 63u) == 0) flush(k);
+        k = path.push(k, i, j);
     }
-    if ((k & 63u) != 0) flush(k);
+    path.finish(k);
     if (lane == 0) path_len[blockIdx.x] = k;
 }
 
-// Start-first order and the per-step distance: one thread per path element.  What leaves the device per element is its
-// distance and ONE byte: the step from the element before it (bit 0: i advanced, bit 1: j advanced; a global path starts at
-// (0, 0): dtw.cpp:640-655) -- the host rebuilds (i, j) while it writes the caller's arrays; 5 bytes an element over the bus
-// instead of 12.
+// Start-first order and the per-step distance, one thread per path element (wf::finish_body; a global path starts at (0, 0), so no j0)
 __global__ __launch_bounds__(256) void k_tb_finish(const DevJob *__restrict__ jobs, uint32_t count,
                                                    const float *__restrict__ ev, const float *__restrict__ ref,
                                                    const uint64_t *__restrict__ path_off,
@@ -610,19 +530,7 @@ __global__ __launch_bounds__(256) void k_tb_finish(const DevJob *__restrict__ jo
                                                    const uint32_t *__restrict__ tmp_i, const uint32_t *__restrict__ tmp_j,
                                                    uint8_t *__restrict__ path_mv, float *__restrict__ path_d)
 {
-    const uint32_t g = blockIdx.x;
-    if (g >= count) return;
-    const DevJob jb = jobs[g];
-    const float *a = ev + jb.read_off;
-    const float *b = ref + jb.ref_off;
-    const uint64_t po = path_off[g];
-    const uint32_t len = path_len[g];
-    for (uint32_t q = threadIdx.x; q < len; q += 256) {
-        const uint32_t i = tmp_i[po + len - 1 - q], j = tmp_j[po + len - 1 - q];
-        uint32_t mv = 0;
-        if (q) mv = (i - tmp_i[po + len - q]) | ((j - tmp_j[po + len - q]) << 1);
-        path_mv[po + q] = (uint8_t)mv; path_d[po + q] = dist(a[i], b[j]);
-    }
+    wf::finish_body<false>(jobs, count, ev, ref, path_off, path_len, tmp_i, tmp_j, nullptr, path_mv, path_d);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -917,62 +825,36 @@ hipError_t launch_band_wreg(int chunks, const DevJob *jobs, uint64_t count, cons
     }
 }
 
-template <int RPL, bool TB>
-static hipError_t launch_full_t(const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev,
-                                const float *ref, float *out, float *bnd_ws, uint8_t *dir_ws,
-                                hipStream_t s)
-{
-    hipLaunchKernelGGL((k_full_wave<RPL, TB, 1>), dim3((uint32_t)count), dim3(64), 0, s, jobs, aux, ev, ref,
-                       out, bnd_ws, dir_ws);
-    return hipGetLastError();
-}
-
-hipError_t launch_full_wave(int rpl, bool tb, const DevJob *jobs, uint64_t count, const FullAux *aux,
+hipError_t launch_full_wave(int cls, bool tb, const DevJob *jobs, uint64_t count, const FullAux *aux,
                             const float *ev, const float *ref, float *out, float *bnd_ws,
                             uint8_t *dir_ws, hipStream_t s)
 {
     if (count == 0) return hipSuccess;
-#define RAWDTW_FULL_CASE(r)                                                                           \
-    case r:                                                                                           \
-        return tb ? launch_full_t<r, true>(jobs, count, aux, ev, ref, out, bnd_ws, dir_ws, s)         \
-                  : launch_full_t<r, false>(jobs, count, aux, ev, ref, out, bnd_ws, dir_ws, s);
-    switch (rpl) {
-        RAWDTW_FULL_CASE(1)
-        RAWDTW_FULL_CASE(2)
-        RAWDTW_FULL_CASE(4)
-        RAWDTW_FULL_CASE(8)
-    case 8 + 256: // multi-strip jobs: four waves per job (kFullWgWaves)
-        if (tb) hipLaunchKernelGGL((k_full_wave<8, true, kFullWgWaves>), dim3((uint32_t)count), dim3(64 * kFullWgWaves), 0, s,
-                                   jobs, aux, ev, ref, out, bnd_ws, dir_ws);
-        else hipLaunchKernelGGL((k_full_wave<8, false, kFullWgWaves>), dim3((uint32_t)count), dim3(64 * kFullWgWaves), 0, s,
-                                jobs, aux, ev, ref, out, bnd_ws, dir_ws);
+    return with_wave_class(cls, [&](auto rpl, auto waves) {
+        constexpr int RPL = decltype(rpl)::value, WAVES = decltype(waves)::value;
+        const auto kern = tb ? k_full_wave<RPL, true, WAVES> : k_full_wave<RPL, false, WAVES>;
+        hipLaunchKernelGGL(kern, dim3((uint32_t)count), dim3(64 * WAVES), 0, s,
+                           jobs, aux, ev, ref, out, bnd_ws, dir_ws);
         return hipGetLastError();
-    default: return hipErrorInvalidValue;
-    }
-#undef RAWDTW_FULL_CASE
+    });
 }
 
 // wave-per-job walk (end-first (i, j) into tmp_i / tmp_j) followed by k_tb_finish (start-first i, j, d)
-hipError_t launch_tb_walk_wave(const DevJob *jobs, uint64_t count, const FullAux *aux, int rpl, const float *ev,
+hipError_t launch_tb_walk_wave(const DevJob *jobs, uint64_t count, const FullAux *aux, int cls, const float *ev,
                                const float *ref, const uint8_t *dir_ws, const uint64_t *path_off, uint32_t *path_len,
                                uint32_t *tmp_i, uint32_t *tmp_j, uint8_t *path_mv, float *path_d, hipStream_t s)
 {
     if (count == 0) return hipSuccess;
-    const dim3 grid((uint32_t)count), block(64);
-    switch (rpl) {
-    case 1: hipLaunchKernelGGL(k_tb_walk_wave<1>, grid, block, 0, s, jobs, aux, dir_ws, path_off, path_len, tmp_i, tmp_j); break;
-    case 2: hipLaunchKernelGGL(k_tb_walk_wave<2>, grid, block, 0, s, jobs, aux, dir_ws, path_off, path_len, tmp_i, tmp_j); break;
-    case 4: hipLaunchKernelGGL(k_tb_walk_wave<4>, grid, block, 0, s, jobs, aux, dir_ws, path_off, path_len, tmp_i, tmp_j); break;
-    default: hipLaunchKernelGGL(k_tb_walk_wave<8>, grid, block, 0, s, jobs, aux, dir_ws, path_off, path_len, tmp_i, tmp_j); break;
-    }
-    hipError_t e = hipGetLastError();
+    const hipError_t e = with_wave_rows(cls, [&](auto rpl) {
+        hipLaunchKernelGGL(k_tb_walk_wave<decltype(rpl)::value>, dim3((uint32_t)count), dim3(64), 0, s, jobs, aux, dir_ws, path_off, path_len,
+                           tmp_i, tmp_j);
+        return hipGetLastError();
+    });
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_tb_finish, grid, dim3(256), 0, s, jobs, (uint32_t)count, ev, ref, path_off, path_len, tmp_i, tmp_j,
-                       path_mv, path_d);
-    return hipGetLastError();
+    return launch_tb_finish(jobs, count, ev, ref, path_off, path_len, tmp_i, tmp_j, path_mv, path_d, s);
 }
 
-// k_tb_finish alone, behind a walk of another unit (rawdtw_band_tb.hip); a job whose path_len is 0 gets nothing written
+// k_tb_finish alone: behind the walk above or a walk of another unit (rawdtw_band_tb.hip)
 hipError_t launch_tb_finish(const DevJob *jobs, uint64_t count, const float *ev, const float *ref, const uint64_t *path_off,
                             const uint32_t *path_len, const uint32_t *tmp_i, const uint32_t *tmp_j, uint8_t *path_mv, float *path_d,
                             hipStream_t s)

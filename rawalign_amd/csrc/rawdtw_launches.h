@@ -35,6 +35,21 @@ struct Launch {
 // a launch as the timed entry points report it: the kind in the low byte, the parameter's low 24 bits above it
 inline uint32_t launch_word(uint32_t kind, int32_t param) { return kind | ((uint32_t)param << 8); }
 
+// The wave classes of the wavefront kernels (full-matrix and semiglobal: kKindFullWave, kKindFullTb, kKindSemiWave): rows a lane,
+// waves a job, and the parameter a launch of the class reports -- rows a lane, + 256 for the pipelined class.  The launchers take
+// the class; a Launch carries the parameter.
+constexpr int kFullWgWaves = 4; // waves a job of the pipelined-strip class
+struct WaveClass { int rows, waves; int32_t param; };
+constexpr int kWaveClasses = 5;
+constexpr WaveClass kWaveClass[kWaveClasses] = {{1, 1, 1}, {2, 1, 2}, {4, 1, 4}, {8, 1, 8}, {8, kFullWgWaves, 8 + 256}};
+inline int32_t wave_class_param(int cls) { return kWaveClass[cls].param; }
+inline int wave_class_of(int32_t param) // -1: no class reports it
+{
+    for (int c = 0; c < kWaveClasses; c++)
+        if (kWaveClass[c].param == param) return c;
+    return -1;
+}
+
 // Which launches of a plan travel as one k_band_merged launch (indices into the plan's launches, -1 = none).
 struct MergeSel { int tile = -1, grp16 = -1, grp8 = -1, wreg = -1; bool on() const { return tile >= 0; } };
 inline MergeSel merge_select(bool merge_small, int tile_threads, int n_side, bool serial_launches, const std::vector<Launch> &launches)

@@ -226,10 +226,10 @@ int plan_host(const PlanCfg &cfg, const rawdtw_job_t *jobs, uint64_t n_jobs, boo
             int32_t R = -1;
             if (j.band_radius == RAWDTW_FULL) {
                 const int rpl = full_rpl(NY);
-                c = 56 + (rpl == 1 ? 0 : rpl == 2 ? 1 : rpl == 4 ? 2 : 3);
+                c = 56 + wave_class_of(rpl); // (a one-wave class reports its rows a lane)
                 // >= 3 strips: four waves per job.  The pipelined kernel's progress word packs (strip << 21) | columns
                 // (k_full_wave): shapes beyond 2^21 columns or 2^11 strips stay on the one-wave variant.
-                if (rpl == 8 && NY > 2 * 512u && cfg.full_wg && N < (1u << 21) && (NY + 511u) / 512u < (1u << 11)) c = 60;
+                if (rpl == 8 && NY > 2 * 512u && cfg.full_wg && N < (1u << 21) && (NY + 511u) / 512u < (1u << 11)) c = 56 + kWaveClasses - 1;
             } else {
                 if (traceback) {
                     bad(RAWDTW_ERR_UNSUPPORTED, "traceback of a banded job is not implemented (rmap.cpp:223-225 assert(false))");
@@ -335,8 +335,8 @@ int plan_host(const PlanCfg &cfg, const rawdtw_job_t *jobs, uint64_t n_jobs, boo
         const uint64_t c = keyed[n12 + q].key >> 56;
         const DevJob &j = pl->h_jobs[p];
         if (c >= 56) {
-            const int rpl = c == 60 ? 8 : 1 << (c - 56);
-            const uint64_t rows = c == 60 ? kFullWgWaves : 1; // boundary rows: a ring for the pipelined variant
+            const int rpl = kWaveClass[c - 56].rows;
+            const uint64_t rows = kWaveClass[c - 56].waves; // boundary rows: a ring for the pipelined variant
             const uint32_t NX = std::max(j.n, j.m), NY = std::min(j.n, j.m);
             if (NY > 64u * rpl) { // multi-strip: needs a boundary row
                 pl->h_aux[q].bnd_off = bnd;
@@ -354,7 +354,7 @@ int plan_host(const PlanCfg &cfg, const rawdtw_job_t *jobs, uint64_t n_jobs, boo
             else if (c == 39) { L.kind = kKindBandWreg; L.param = -16; }
             else if (c < 48) { L.kind = kKindBandWreg; L.param = c == 40 ? 0 : 1 << (c - 40); }
             else if (c < 56) { L.kind = kKindBandWave; L.param = 3 * kMaxWaveBandK; }
-            else { L.kind = traceback ? kKindFullTb : kKindFullWave; L.param = c == 60 ? 8 + 256 : 1 << (c - 56); }
+            else { L.kind = traceback ? kKindFullTb : kKindFullWave; L.param = wave_class_param((int)c - 56); }
             pl->launches.push_back(L);
         }
         pl->launches.back().count++;
@@ -672,13 +672,13 @@ int run_launch(rawdtw_ctx *ctx, rawdtw_plan *pl, const Launch &L, hipStream_t st
         break;
     case kKindFullWave:
     case kKindFullTb:
-        e = launch_full_wave(L.param, L.kind == kKindFullTb, jobs, L.count, aux, ctx->d_ev,
+        e = launch_full_wave(wave_class_of(L.param), L.kind == kKindFullTb, jobs, L.count, aux, ctx->d_ev,
                              ctx->d_ref, out, pl->d_bnd, pl->d_dir, stream);
         break;
     case kKindSemiWave: // (a local batch's plan: build_semi_plan; param = rows a lane, + 256 for class 4)
         if (!ctx->d_ev || !ctx->d_ref || ctx->n_ev < pl->need_ev || ctx->n_ref < pl->need_ref)
             return fail(ctx, RAWDTW_ERR_INVALID, "an arena shrank after the batch was created: create the batch again");
-        e = launch_semi_wave(L.param >= 256 ? 4 : L.param == 8 ? 3 : L.param == 4 ? 2 : L.param == 2 ? 1 : 0, false, jobs, L.count, aux, ctx->d_ev, ctx->d_ref, out,
+        e = launch_semi_wave(wave_class_of(L.param), false, jobs, L.count, aux, ctx->d_ev, ctx->d_ref, out,
                              pl->d_end_j, pl->d_bnd, nullptr, stream);
         break;
     default:

@@ -264,7 +264,7 @@ int build_semi_plan(rawdtw_ctx *ctx, const rawdtw_job_t *jobs, uint64_t n_jobs, 
         pl->info.algorithmic_bytes += 4ull * ((uint64_t)sp.jobs[p].n + sp.jobs[p].m) + 4 + 32;
     }
     for (const ClassLaunch &L : sp.launches) // (class order is longest last: the launches run in that order, as semi_fill's)
-        pl->launches.push_back(Launch{kKindSemiWave, L.cls == 4 ? 8 + 256 : semi_rpl(L.cls), L.first, L.count});
+        pl->launches.push_back(Launch{kKindSemiWave, wave_class_param(L.cls), L.first, L.count});
     for (uint32_t i = 0; i < pl->run_order.size(); i++) pl->run_order[i] = i;
     pl->info.n_jobs = n_jobs; pl->info.n_full_jobs = n_jobs; pl->info.n_launches = (uint32_t)pl->launches.size();
     pl->info.workspace_bytes = n_jobs * (sizeof(DevJob) + sizeof(FullAux) + 8) + sp.bnd_floats * 4;

@@ -8,11 +8,11 @@
 
 namespace rawdtw {
 
-// A semiglobal job's class: 0..3 = 1, 2, 4, 8 rows a lane on one wave, by n ALONE (a always lies over the lanes: the rule of the
+// A semiglobal job's wave class: 0..3 = 1, 2, 4, 8 rows a lane on one wave, by n ALONE (a always lies over the lanes: the rule of the
 // full-matrix classes, full_rpl, applied to n), 4 = 8 rows a lane on four pipelined waves: three strips or more, under the guards of
 // the progress word (m < 2^21 columns, fewer than 2^11 strips) and the context's "full_wg".
-constexpr int kSemiClasses = 5;
-inline int semi_rpl(int cls) { return cls >= 3 ? 8 : 1 << cls; }
+constexpr int kSemiClasses = kWaveClasses; // (the wave classes of rawdtw_launches.h)
+inline int semi_rpl(int cls) { return kWaveClass[cls].rows; }
 inline int semi_class(uint32_t n, uint32_t m, bool full_wg)
 {
     const int c = n <= 64 ? 0 : n <= 128 ? 1 : n <= 256 ? 2 : 3;
@@ -23,7 +23,7 @@ inline int semi_class(uint32_t n, uint32_t m, bool full_wg)
 inline uint64_t semi_bnd_floats(uint32_t n, uint32_t m, int cls)
 {
     if (n <= 64u * (uint32_t)semi_rpl(cls)) return 0;
-    return (uint64_t)(cls == 4 ? kFullWgWaves : 1) * (((uint64_t)m + 63) & ~63ull);
+    return (uint64_t)kWaveClass[cls].waves * (((uint64_t)m + 63) & ~63ull);
 }
 // the span form's boundary rows, in floats: a slot holds the row of costs and behind it the row of start columns
 inline uint64_t semi_span_bnd_floats(uint32_t n, uint32_t m, int cls) { return 2 * semi_bnd_floats(n, m, cls); }

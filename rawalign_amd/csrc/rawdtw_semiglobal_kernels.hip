@@ -5,8 +5,8 @@
 //   k_semi_wave<.,true> + k_semi_walk_wave + k_semi_finish : DTW_semiglobal_tb                     src/dtw.cpp:669-753
 //   k_semi_span_wave                                       : cost, end_j and path[0].j of DTW_semiglobal_tb, no direction matrix
 //
-// k_semi_wave is the sibling of k_full_wave (rawdtw_kernels.hip): the same skewed wavefront, rows over the lanes, RPL rows a lane,
-// strips of 64 * RPL rows, boundary rows in HBM, the same packed 2-bit directions in the same buffer layout.  What differs:
+// k_semi_wave is the sibling of k_full_wave (rawdtw_kernels.hip): both run the strip loop of rawdtw_wavefront.h, with the same packed
+// 2-bit directions in the same buffer layout.  What differs:
 //   no transposition  the recurrence is not symmetric: a ALWAYS lies over the lanes and b is swept, also when n > m, so a
 //                     direction code never changes its meaning (1: i - 1, 2: j - 1, 0: both).
 //   borders           row 0 is assigned, D(0, j) = d(0, j): the lane that holds it takes the distance itself, no minimum with a made-up
@@ -24,18 +24,9 @@
 #include "rawdtw_dp.h"
 #include "rawdtw_semiglobal.h"
 #include "rawdtw_semi_window.h"
+#include "rawdtw_wavefront.h"
 
 namespace rawdtw {
-
-template <int RPL> struct SemiDirWord { using type = uint8_t; };
-template <> struct SemiDirWord<8> { using type = uint16_t; };
-
-// a start column travels between lanes as a value does (rawdtw_dp.h)
-__device__ __forceinline__ uint32_t wave_shr1(uint32_t v, uint32_t fill)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x138, 0xf, 0xf, false);
-}
-__device__ __forceinline__ uint32_t read_lane(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
 
 // The span form's choice of a cell's start: ab < t_up ? s_up : (left < t_lf ? s_left : s_diag), with t_up = min(left, diag) and
 // t_lf = min(ab, diag) -- the TB form's two comparisons, each into a lane mask, and two selects on the masks.  One statement, because
@@ -57,10 +48,8 @@ __device__ __forceinline__ uint32_t span_pick(float ab, float t_up, float left, 
     return r;
 }
 
-// WAVES = 1: one wave per job, strips in sequence.  WAVES = 4 (jobs of three strips or more): the workgroup's waves take strips
-// w, w + 4, ... as a pipeline, strip s + 1 trailing strip s by at least one 64-column chunk; boundary rows are a ring of WAVES rows
-// and a strip publishes the columns it has flushed through an LDS progress word, (strip << 21) | columns -- so m < 2^21 and fewer
-// than 2^11 strips (semi_class sees to it).
+// WAVES = kFullWgWaves: jobs of three strips or more; the progress word holds (strip << 21) | columns, so m < 2^21 and fewer than
+// 2^11 strips (semi_class sees to it).
 //
 // SPAN (never with TB): every cell also carries S(i, j), the column in which the path that the walk would take from it starts
 // (include/rawdtw.h, "span").  One more register a row register, chosen from the three neighbours' starts by the very
@@ -86,8 +75,9 @@ __device__ __forceinline__ void semi_wave_body(const DevJob *__restrict__ jobs, 
 {
     static_assert(!(TB && SPAN), "the span form writes no directions");
     static_assert(!CKPT || (!TB && !SPAN), "checkpoints are the cost form's");
-    using word_t = typename SemiDirWord<RPL>::type;
-    constexpr float kNone = __builtin_inff(); // beyond the matrix: loses every min (no sentinel, as in k_full_wave)
+    using word_t = typename wf::DirWord<RPL>::type;
+    constexpr uint32_t SPB = wf::SPB<RPL>;
+    constexpr float kNone = wf::kNone;
     const DevJob jb = jobs[blockIdx.x];
     const FullAux ax = aux[blockIdx.x];
     const int lane = threadIdx.x & 63;
@@ -97,9 +87,7 @@ __device__ __forceinline__ void semi_wave_body(const DevJob *__restrict__ jobs, 
     const uint32_t NY = jb.n, NX = jb.m;
     constexpr uint32_t STRIP = 64u * RPL;
     const uint32_t nstrips = (NY + STRIP - 1) / STRIP;
-    // direction words in blocks of SPB steps, [strip][block][lane][step in block]: k_full_wave's layout
-    constexpr uint32_t SPB = 16u / sizeof(word_t);
-    const uint32_t TXB = (NX + 63 + SPB - 1) / SPB;
+    const uint32_t TXB = (NX + 63 + SPB - 1) / SPB; // blocks per strip
     const uint32_t row_stride = (NX + 63u) & ~63u; // floats per boundary row (semi_bnd_floats)
     const uint32_t slot_stride = SPAN ? 2u * row_stride : row_stride; // (a span slot: the costs, then the starts)
     float *bnd_base = bnd_ws + ax.bnd_off;
@@ -132,7 +120,7 @@ __device__ __forceinline__ void semi_wave_body(const DevJob *__restrict__ jobs, 
         const uint32_t steps = NX + lanes_here - 1;
         const bool has_rows = y0 < NY;
         const bool hands_down = (s + 1 < nstrips); // then the strip is full and lane 63 owns its last row
-        const bool row0 = (s == 0 && lane == 0);   // this lane's first register is row 0: assigned, not minimised
+        const bool row0 = (s == 0 && lane == 0); // this lane's first register is row 0: assigned, not minimised
 
         // The strip's column loop.  KK: the register of its lane in which row n - 1 lies (the last strip), -1: a strip above the last.
         auto strip = [&](auto kk_c) {
@@ -183,24 +171,13 @@ __device__ __forceinline__ void semi_wave_body(const DevJob *__restrict__ jobs, 
                         const float dd = dist(xval, yv[k]);
                         float nv = min3f(ab, left, d) + dd;
                         if (k == 0) nv = row0 ? dd : nv; // D(0, j) = d(0, j)  (dtw.cpp:566-568, 679-681)
-                        if (TB) {
-                            // dtw.cpp:717-730 with left = D[i-1][j] (here `ab`), top = D[i][j-1] (here `left`):
-                            //   ab < min(left, d) -> 1 (i-1) ; else left < min(ab, d) -> 2 (j-1) ; else 0.
-                            // Two bit planes shifted in from below, as k_full_wave does it (v_min_f32 as the instruction: fminf would
-                            // quiet signalling NaNs first).  Row 0's codes are never read: the walk ends there.
-                            float t_up, t_lf;
-                            asm("v_min_f32 %0, %1, %2" : "=v"(t_up) : "v"(left), "v"(d));
-                            asm volatile("v_cmp_lt_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(code) : "v"(ab), "v"(t_up) : "vcc");
-                            asm("v_min_f32 %0, %1, %2" : "=v"(t_lf) : "v"(ab), "v"(d));
-                            asm volatile("v_cmp_lt_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(code) : "v"(left), "v"(t_lf) : "vcc");
-                        }
+                        // dtw.cpp:717-730 with left = D[i-1][j] (here `ab`), top = D[i][j-1] (here `left`).  Row 0's codes are never read:
+                        // the walk ends there.
+                        if (TB) code = wf::dir_code(code, ab, left, d);
                         if (SPAN) {
                             // the TB form's two comparisons, each into a lane mask, and the start of the neighbour the walk would step
                             // to (else: the diagonal, the reference's quirk ab == left < d included).  Row 0 starts in its own column.
-                            float t_up, t_lf;
-                            asm("v_min_f32 %0, %1, %2" : "=v"(t_up) : "v"(left), "v"(d));
-                            asm("v_min_f32 %0, %1, %2" : "=v"(t_lf) : "v"(ab), "v"(d));
-                            uint32_t ns = span_pick(ab, t_up, left, t_lf, sab, vs[k], sd);
+                            uint32_t ns = span_pick(ab, wf::min2f(left, d), left, wf::min2f(ab, d), sab, vs[k], sd);
                             if (k == 0) ns = row0 ? x : ns;
                             sd = vs[k]; sab = ns; vs[k] = ns;
                         }
@@ -221,11 +198,7 @@ __device__ __forceinline__ void semi_wave_body(const DevJob *__restrict__ jobs, 
                             }
                         }
                     }
-                    if (TB) {
-                        // bit reversal puts cell k at bits 2k ("i - 1", shifted in first) and 2k + 1 ("j - 1")
-                        const uint32_t w = __builtin_bitreverse32(code) >> (32 - 2 * RPL);
-                        tbuf[lane * SPB + (t % SPB)] = (word_t)w;
-                    }
+                    if (TB) wf::dir_put<RPL>(tbuf, lane, t, code);
                 }
                 if constexpr (CKPT) {
                     if (++ck_tm == ck_columns) { ck_tm = 0; ck_seg++; }
@@ -265,13 +238,7 @@ __device__ __forceinline__ void semi_wave_body(const DevJob *__restrict__ jobs, 
                                      : "v"(v[KK]), "s"(owner_bit), "s"(t), "s"(owner)
                                      : "vcc", "scc");
                 }
-                if (TB && ((t % SPB) == SPB - 1 || t + 1 == steps)) {
-                    // same wave wrote and reads the buffer; LDS operations of a wave complete in order, the
-                    // fence keeps the compiler from reordering the differently typed accesses
-                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                    const uint4 blk = *reinterpret_cast<const uint4 *>(&tbuf[lane * SPB]);
-                    if (has_rows) dirs[((uint64_t)s * TXB + t / SPB) * 64u + lane] = blk;
-                }
+                if (TB && ((t % SPB) == SPB - 1 || t + 1 == steps)) wf::dir_flush<RPL>(tbuf, dirs, TXB, s, t, lane, has_rows);
                 if (hands_down && t >= 63u) {
                     // lane 63 finished column c = t-63 in this step; gather 64 of them, store coalesced
                     const uint32_t c = t - 63u;
@@ -367,13 +334,13 @@ __global__ __launch_bounds__(64 * WAVES) void k_semi_ckpt_wave(const DevJob *__r
 }
 
 // The traceback in windows (include/rawdtw.h, "semiglobal, in windows"), one wave per job, behind k_semi_ckpt_wave: as long as i > 0,
-// refill the window lo(j) .. j of the current position with directions -- k_semi_wave<., true>'s cells, codes and layout over the
-// window's columns, its column -1 the checkpoint in front of the window (v[], and the diagonal input of each lane's first row, which
-// for lane 0 of a strip below the first is the row above the strip), rows down to the strip that holds i only: the walk never moves
-// down --, then walk as k_semi_walk_wave does until i == 0 or a step leaves the window on the left (that step is emitted).  Strips run
-// in sequence on the one wave, also for jobs of the pipelined class; the boundary row between them is the job's own (the cost pass is
-// done with it), indexed by the column inside the window.  No spin-wait and no progress word: every round of the outer loop takes at
-// least one step of the walk, and a walk has at most n + m - 1 elements.
+// refill the window lo(j) .. j of the current position with directions -- k_semi_wave<., true>'s strip loop (rawdtw_wavefront.h)
+// over the window's columns, its column -1 the checkpoint in front of the window (v[], and the diagonal input of each lane's first
+// row, which for lane 0 of a strip below the first is the row above the strip), rows down to the strip that holds i only: the walk
+// never moves down --, then walk as k_semi_walk_wave does until i == 0 or a step leaves the window on the left (that step is emitted).
+// Strips run in sequence on the one wave, also for jobs of the pipelined class; the boundary row between them is the job's own (the
+// cost pass is done with it), indexed by the column inside the window.  No spin-wait and no progress word: every round of the outer
+// loop takes at least one step of the walk, and a walk has at most n + m - 1 elements.
 // Output as k_semi_walk_wave's: (i, j) end-first into tmp_i / tmp_j, the length; k_semi_finish follows unchanged.  stats: windows
 // entered over the launch ([0], summed) and by one job at most ([1]).
 template <int RPL>
@@ -384,9 +351,9 @@ __global__ __launch_bounds__(64) void k_semi_window(const DevJob *__restrict__ j
                                                     uint32_t *__restrict__ path_len, uint32_t *__restrict__ tmp_i,
                                                     uint32_t *__restrict__ tmp_j, uint32_t columns, unsigned long long *__restrict__ stats)
 {
-    using word_t = typename SemiDirWord<RPL>::type;
-    constexpr float kNone = __builtin_inff();
-    constexpr uint32_t SPB = 16u / sizeof(word_t);
+    using word_t = typename wf::DirWord<RPL>::type;
+    constexpr uint32_t SPB = wf::SPB<RPL>;
+    constexpr float kNone = wf::kNone;
     constexpr uint32_t STRIP = 64u * RPL;
     __shared__ __attribute__((aligned(16))) word_t tbuf[64 * SPB]; // the fill's staging: [lane][step in block]
     __shared__ __attribute__((aligned(16))) word_t row[64 * SPB];  // the walk's block row
@@ -453,25 +420,16 @@ __global__ __launch_bounds__(64) void k_semi_window(const DevJob *__restrict__ j
                         const float dd = dist(xval, yv[q]);
                         float nv = min3f(ab, left, d) + dd;
                         if (q == 0) nv = row0 ? dd : nv;
-                        // k_semi_wave<., true>'s two comparisons and bit planes, instruction for instruction
-                        float t_up, t_lf;
-                        asm("v_min_f32 %0, %1, %2" : "=v"(t_up) : "v"(left), "v"(d));
-                        asm volatile("v_cmp_lt_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(code) : "v"(ab), "v"(t_up) : "vcc");
-                        asm("v_min_f32 %0, %1, %2" : "=v"(t_lf) : "v"(ab), "v"(d));
-                        asm volatile("v_cmp_lt_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(code) : "v"(left), "v"(t_lf) : "vcc");
+                        code = wf::dir_code(code, ab, left, d);
                         d = left; ab = nv; v[q] = nv;
                     }
                     diag_in = up_in;
                     last_out = v[RPL - 1];
-                    const uint32_t w = __builtin_bitreverse32(code) >> (32 - 2 * RPL);
-                    tbuf[lane * SPB + (t % SPB)] = (word_t)w;
+                    wf::dir_put<RPL>(tbuf, lane, t, code);
                 }
-                if ((t % SPB) == SPB - 1 || t + 1 == steps) {
-                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                    const uint4 blk = *reinterpret_cast<const uint4 *>(&tbuf[lane * SPB]);
-                    if (has_rows) dirs[((uint64_t)s * TXB + t / SPB) * 64u + lane] = blk;
-                }
+                if ((t % SPB) == SPB - 1 || t + 1 == steps) wf::dir_flush<RPL>(tbuf, dirs, TXB, s, t, lane, has_rows);
                 if (hands_down && t >= 63u) {
+                    // lane 63 finished column c = t-63 in this step; gather 64 of them, store coalesced
                     const uint32_t c = t - 63u;
                     const float v63 = read_lane(last_out, 63);
                     if ((uint32_t)lane == (c & 63u)) wchunk = v63;
@@ -484,27 +442,12 @@ __global__ __launch_bounds__(64) void k_semi_window(const DevJob *__restrict__ j
             __threadfence(); // the boundary row and the directions are read back by this wave, at addresses it has read before
         }
         // ---- the walk inside the window ----
-        uint64_t cur = ~0ull; // block row held in LDS (a refilled window has new ones)
+        uint64_t cur = ~0ull; // (a refilled window has new block rows)
         while (i > 0) {
             if (j == 0) i--; // global column 0 only
             else {
-                const uint32_t sidx = i / STRIP, l = (i / RPL) & 63u, kk = i % RPL;
-                const uint32_t t = (j - c_lo) + l;
-                const uint64_t key = (uint64_t)sidx * TXB + t / SPB;
-                if (key != cur) {
-                    __builtin_amdgcn_s_barrier(); // (every lane has read the row that goes)
-                    reinterpret_cast<uint4 *>(row)[lane] = dirs[key * 64u + lane];
-                    cur = key;
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                    __builtin_amdgcn_s_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                }
-                uint32_t word = row[l * SPB + (t % SPB)];
-                word = (uint32_t)__builtin_amdgcn_readfirstlane((int)word);
-                const uint32_t code = (word >> (2 * kk)) & 3u;
-                if (code == 1u) i--;
-                else if (code == 2u) j--;
-                else { i--; j--; }
+                const wf::WalkPos p = wf::walk_step<RPL, true>({i, j, cur}, dirs, row, TXB, lane, i, j, c_lo);
+                i = p.i; j = p.j; cur = p.cur;
             }
             if ((uint32_t)lane == (k & 63u)) { bi = i; bj = j; }
             k++;
@@ -520,8 +463,7 @@ __global__ __launch_bounds__(64) void k_semi_window(const DevJob *__restrict__ j
     }
 }
 
-// The walk, one wave per job: k_tb_walk_wave's (a block row of directions in LDS, all lanes in lockstep on uniform values, steps
-// buffered one a lane and stored 64 at a time) from (n - 1, end_j) until i == 0 (dtw.cpp:709-738; at j == 0 it moves up).
+// The walk, one wave per job (rawdtw_wavefront.h): from (n - 1, end_j) until i == 0 (dtw.cpp:709-738; at j == 0 it moves up).
 // Output: (i, j) end-first, at most n + m - 1 elements.
 template <int RPL>
 __global__ __launch_bounds__(64) void k_semi_walk_wave(const DevJob *__restrict__ jobs, const FullAux *__restrict__ aux,
@@ -529,149 +471,89 @@ __global__ __launch_bounds__(64) void k_semi_walk_wave(const DevJob *__restrict_
                                                        const uint64_t *__restrict__ path_off, uint32_t *__restrict__ path_len,
                                                        uint32_t *__restrict__ tmp_i, uint32_t *__restrict__ tmp_j)
 {
-    using word_t = typename SemiDirWord<RPL>::type;
-    constexpr uint32_t SPB = 16u / sizeof(word_t);
-    __shared__ __attribute__((aligned(16))) word_t row[64 * SPB]; // one block row: [lane][step in block]
+    using word_t = typename wf::DirWord<RPL>::type;
+    __shared__ __attribute__((aligned(16))) word_t row[64 * wf::SPB<RPL>]; // one block row: [lane][step in block]
     const int lane = threadIdx.x;
     const DevJob jb = jobs[blockIdx.x];
     const FullAux ax = aux[blockIdx.x];
-    const uint64_t TXB = ((uint64_t)jb.m + 63u + SPB - 1) / SPB; // blocks per strip
+    const uint64_t TXB = wf::strip_blocks<RPL>((uint64_t)jb.m);
     const uint4 *dirs = reinterpret_cast<const uint4 *>(dir_ws + ax.dir_off);
     const uint64_t po = path_off[blockIdx.x];
-    uint32_t i = jb.n - 1, j = end_j[jb.aux], k = 0;
+    uint32_t i = jb.n - 1, j = end_j[jb.aux], k = 1;
     if (j >= jb.m) j = jb.m - 1; // (never: the fill wrote a column of the matrix)
-    uint32_t bi = i, bj = j; // this lane's slot of the 64-step output buffer (lane = step & 63)
-    uint64_t cur = ~0ull;    // block row held in LDS
-    auto flush = [&](uint32_t upto) { // steps [upto - ((upto - 1) & 63) - 1 .. upto) sit in lanes 0..(upto-1)&63
-        const uint32_t base = (upto - 1) & ~63u;
-        if ((uint32_t)lane <= ((upto - 1) & 63u)) { tmp_i[po + base + lane] = bi; tmp_j[po + base + lane] = bj; }
-    };
-    k = 1; // step 0: the end cell (lane 0's slot holds it)
+    wf::PathBuf path{tmp_i, tmp_j, po, lane, i, j};
+    uint64_t cur = ~0ull;
     while (i > 0) {
         if (j == 0) i--;
         else {
-            const uint32_t sidx = i / (64u * RPL), l = (i / RPL) & 63u, kk = i % RPL;
-            const uint32_t t = j + l;
-            const uint64_t key = (uint64_t)sidx * TXB + t / SPB;
-            if (key != cur) {
-                reinterpret_cast<uint4 *>(row)[lane] = dirs[key * 64u + lane];
-                cur = key;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            }
-            uint32_t word = row[l * SPB + (t % SPB)];
-            word = (uint32_t)__builtin_amdgcn_readfirstlane((int)word);
-            const uint32_t code = (word >> (2 * kk)) & 3u;
-            if (code == 1u) i--;
-            else if (code == 2u) j--;
-            else { i--; j--; }
-            // (the next block row overwrites `row` only behind the barrier above, which all lanes reach together)
+            const wf::WalkPos p = wf::walk_step<RPL, false>({i, j, cur}, dirs, row, TXB, lane, i, j);
+            i = p.i; j = p.j; cur = p.cur;
         }
-        if ((uint32_t)lane == (k & 63u)) { bi = i; bj = j; }
-        k++;
-        if ((k & 63u) == 0) flush(k);
+        k = path.push(k, i, j);
     }
-    if ((k & 63u) != 0) flush(k);
+    path.finish(k);
     if (lane == 0) path_len[blockIdx.x] = k;
 }
 
-// Start-first order, the step byte of rawdtw_traceback_batch_steps (bit 0: i advanced, bit 1: j advanced; element 0's is 0), the
-// distance, and the column j0 the path starts in: one thread per path element.
+// k_tb_finish, and the column j0 the path starts in
 __global__ __launch_bounds__(256) void k_semi_finish(const DevJob *__restrict__ jobs, uint32_t count, const float *__restrict__ ev,
                                                      const float *__restrict__ ref, const uint64_t *__restrict__ path_off,
                                                      const uint32_t *__restrict__ path_len, const uint32_t *__restrict__ tmp_i,
                                                      const uint32_t *__restrict__ tmp_j, uint32_t *__restrict__ path_j0,
                                                      uint8_t *__restrict__ path_mv, float *__restrict__ path_d)
 {
-    const uint32_t g = blockIdx.x;
-    if (g >= count) return;
-    const DevJob jb = jobs[g];
-    const float *a = ev + jb.read_off;
-    const float *b = ref + jb.ref_off;
-    const uint64_t po = path_off[g];
-    const uint32_t len = path_len[g];
-    for (uint32_t q = threadIdx.x; q < len; q += 256) {
-        const uint32_t i = tmp_i[po + len - 1 - q], j = tmp_j[po + len - 1 - q];
-        uint32_t mv = 0;
-        if (q) mv = (i - tmp_i[po + len - q]) | ((j - tmp_j[po + len - q]) << 1);
-        else path_j0[g] = j;
-        path_mv[po + q] = (uint8_t)mv; path_d[po + q] = dist(a[i], b[j]);
-    }
+    wf::finish_body<true>(jobs, count, ev, ref, path_off, path_len, tmp_i, tmp_j, path_j0, path_mv, path_d);
 }
 
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
-template <int RPL, int WAVES>
-static hipError_t launch_semi_t(bool tb, const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev, const float *ref,
-                                float *out_cost, uint32_t *out_end_j, float *bnd_ws, uint8_t *dir_ws, hipStream_t s)
-{
-    if (tb) hipLaunchKernelGGL((k_semi_wave<RPL, true, WAVES>), dim3((uint32_t)count), dim3(64 * WAVES), 0, s, jobs, aux, ev, ref,
-                               out_cost, out_end_j, bnd_ws, dir_ws);
-    else hipLaunchKernelGGL((k_semi_wave<RPL, false, WAVES>), dim3((uint32_t)count), dim3(64 * WAVES), 0, s, jobs, aux, ev, ref,
-                            out_cost, out_end_j, bnd_ws, dir_ws);
-    return hipGetLastError();
-}
-
 hipError_t launch_semi_wave(int cls, bool tb, const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev,
                             const float *ref, float *out_cost, uint32_t *out_end_j, float *bnd_ws, uint8_t *dir_ws, hipStream_t s)
 {
     if (count == 0) return hipSuccess;
-    switch (cls) {
-    case 0: return launch_semi_t<1, 1>(tb, jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, s);
-    case 1: return launch_semi_t<2, 1>(tb, jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, s);
-    case 2: return launch_semi_t<4, 1>(tb, jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, s);
-    case 3: return launch_semi_t<8, 1>(tb, jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, s);
-    case 4: return launch_semi_t<8, kFullWgWaves>(tb, jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-template <int RPL, int WAVES>
-static hipError_t launch_semi_span_t(const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev, const float *ref,
-                                     float *out_cost, uint32_t *out_j0, uint32_t *out_end_j, float *bnd_ws, hipStream_t s)
-{
-    hipLaunchKernelGGL((k_semi_span_wave<RPL, WAVES>), dim3((uint32_t)count), dim3(64 * WAVES), 0, s, jobs, aux, ev, ref, out_cost,
-                       out_j0, out_end_j, bnd_ws);
-    return hipGetLastError();
+    return with_wave_class(cls, [&](auto rpl, auto waves) {
+        constexpr int RPL = decltype(rpl)::value, WAVES = decltype(waves)::value;
+        const auto kern = tb ? k_semi_wave<RPL, true, WAVES> : k_semi_wave<RPL, false, WAVES>;
+        hipLaunchKernelGGL(kern, dim3((uint32_t)count), dim3(64 * WAVES), 0, s,
+                           jobs, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_semi_span_wave(int cls, const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev, const float *ref,
                                  float *out_cost, uint32_t *out_j0, uint32_t *out_end_j, float *bnd_ws, hipStream_t s)
 {
     if (count == 0) return hipSuccess;
-    switch (cls) {
-    case 0: return launch_semi_span_t<1, 1>(jobs, count, aux, ev, ref, out_cost, out_j0, out_end_j, bnd_ws, s);
-    case 1: return launch_semi_span_t<2, 1>(jobs, count, aux, ev, ref, out_cost, out_j0, out_end_j, bnd_ws, s);
-    case 2: return launch_semi_span_t<4, 1>(jobs, count, aux, ev, ref, out_cost, out_j0, out_end_j, bnd_ws, s);
-    case 3: return launch_semi_span_t<8, 1>(jobs, count, aux, ev, ref, out_cost, out_j0, out_end_j, bnd_ws, s);
-    case 4: return launch_semi_span_t<8, kFullWgWaves>(jobs, count, aux, ev, ref, out_cost, out_j0, out_end_j, bnd_ws, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-template <int RPL, int WAVES>
-static hipError_t launch_semi_ckpt_t(const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev, const float *ref,
-                                     float *out_cost, uint32_t *out_end_j, float *bnd_ws, uint8_t *dir_ws, uint32_t columns, hipStream_t s)
-{
-    hipLaunchKernelGGL((k_semi_ckpt_wave<RPL, WAVES>), dim3((uint32_t)count), dim3(64 * WAVES), 0, s, jobs, aux, ev, ref, out_cost,
-                       out_end_j, bnd_ws, dir_ws, columns);
-    return hipGetLastError();
+    return with_wave_class(cls, [&](auto rpl, auto waves) {
+        constexpr int RPL = decltype(rpl)::value, WAVES = decltype(waves)::value;
+        hipLaunchKernelGGL((k_semi_span_wave<RPL, WAVES>), dim3((uint32_t)count), dim3(64 * WAVES), 0, s, jobs, aux, ev, ref, out_cost,
+                           out_j0, out_end_j, bnd_ws);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_semi_ckpt_wave(int cls, const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev, const float *ref,
                                  float *out_cost, uint32_t *out_end_j, float *bnd_ws, uint8_t *dir_ws, uint32_t columns, hipStream_t s)
 {
     if (count == 0) return hipSuccess;
-    switch (cls) {
-    case 0: return launch_semi_ckpt_t<1, 1>(jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, columns, s);
-    case 1: return launch_semi_ckpt_t<2, 1>(jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, columns, s);
-    case 2: return launch_semi_ckpt_t<4, 1>(jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, columns, s);
-    case 3: return launch_semi_ckpt_t<8, 1>(jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, columns, s);
-    case 4: return launch_semi_ckpt_t<8, kFullWgWaves>(jobs, count, aux, ev, ref, out_cost, out_end_j, bnd_ws, dir_ws, columns, s);
-    default: return hipErrorInvalidValue;
-    }
+    return with_wave_class(cls, [&](auto rpl, auto waves) {
+        constexpr int RPL = decltype(rpl)::value, WAVES = decltype(waves)::value;
+        hipLaunchKernelGGL((k_semi_ckpt_wave<RPL, WAVES>), dim3((uint32_t)count), dim3(64 * WAVES), 0, s, jobs, aux, ev, ref, out_cost,
+                           out_end_j, bnd_ws, dir_ws, columns);
+        return hipGetLastError();
+    });
+}
+
+// k_semi_finish behind a walk: start-first steps, distances and j0
+static hipError_t launch_semi_finish(hipError_t walk, const DevJob *jobs, uint64_t count, const float *ev, const float *ref,
+                                     const uint64_t *path_off, const uint32_t *path_len, const uint32_t *tmp_i, const uint32_t *tmp_j,
+                                     uint32_t *path_j0, uint8_t *path_mv, float *path_d, hipStream_t s)
+{
+    if (walk != hipSuccess) return walk;
+    hipLaunchKernelGGL(k_semi_finish, dim3((uint32_t)count), dim3(256), 0, s, jobs, (uint32_t)count, ev, ref, path_off, path_len, tmp_i, tmp_j,
+                       path_j0, path_mv, path_d);
+    return hipGetLastError();
 }
 
 hipError_t launch_semi_window(int cls, const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev, const float *ref,
@@ -680,18 +562,12 @@ hipError_t launch_semi_window(int cls, const DevJob *jobs, uint64_t count, const
                               unsigned long long *stats, hipStream_t s)
 {
     if (count == 0) return hipSuccess;
-    const dim3 grid((uint32_t)count), block(64);
-    switch (cls) {
-    case 0: hipLaunchKernelGGL(k_semi_window<1>, grid, block, 0, s, jobs, aux, ev, ref, bnd_ws, dir_ws, end_j, path_off, path_len, tmp_i, tmp_j, columns, stats); break;
-    case 1: hipLaunchKernelGGL(k_semi_window<2>, grid, block, 0, s, jobs, aux, ev, ref, bnd_ws, dir_ws, end_j, path_off, path_len, tmp_i, tmp_j, columns, stats); break;
-    case 2: hipLaunchKernelGGL(k_semi_window<4>, grid, block, 0, s, jobs, aux, ev, ref, bnd_ws, dir_ws, end_j, path_off, path_len, tmp_i, tmp_j, columns, stats); break;
-    default: hipLaunchKernelGGL(k_semi_window<8>, grid, block, 0, s, jobs, aux, ev, ref, bnd_ws, dir_ws, end_j, path_off, path_len, tmp_i, tmp_j, columns, stats); break;
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_semi_finish, grid, dim3(256), 0, s, jobs, (uint32_t)count, ev, ref, path_off, path_len, tmp_i, tmp_j,
-                       path_j0, path_mv, path_d);
-    return hipGetLastError();
+    const hipError_t e = with_wave_rows(cls, [&](auto rpl) {
+        hipLaunchKernelGGL(k_semi_window<decltype(rpl)::value>, dim3((uint32_t)count), dim3(64), 0, s, jobs, aux, ev, ref, bnd_ws, dir_ws, end_j,
+                           path_off, path_len, tmp_i, tmp_j, columns, stats);
+        return hipGetLastError();
+    });
+    return launch_semi_finish(e, jobs, count, ev, ref, path_off, path_len, tmp_i, tmp_j, path_j0, path_mv, path_d, s);
 }
 
 hipError_t launch_semi_walk(int cls, const DevJob *jobs, uint64_t count, const FullAux *aux, const float *ev, const float *ref,
@@ -699,18 +575,12 @@ hipError_t launch_semi_walk(int cls, const DevJob *jobs, uint64_t count, const F
                             uint32_t *path_j0, uint32_t *tmp_i, uint32_t *tmp_j, uint8_t *path_mv, float *path_d, hipStream_t s)
 {
     if (count == 0) return hipSuccess;
-    const dim3 grid((uint32_t)count), block(64);
-    switch (cls) {
-    case 0: hipLaunchKernelGGL(k_semi_walk_wave<1>, grid, block, 0, s, jobs, aux, dir_ws, end_j, path_off, path_len, tmp_i, tmp_j); break;
-    case 1: hipLaunchKernelGGL(k_semi_walk_wave<2>, grid, block, 0, s, jobs, aux, dir_ws, end_j, path_off, path_len, tmp_i, tmp_j); break;
-    case 2: hipLaunchKernelGGL(k_semi_walk_wave<4>, grid, block, 0, s, jobs, aux, dir_ws, end_j, path_off, path_len, tmp_i, tmp_j); break;
-    default: hipLaunchKernelGGL(k_semi_walk_wave<8>, grid, block, 0, s, jobs, aux, dir_ws, end_j, path_off, path_len, tmp_i, tmp_j); break;
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_semi_finish, grid, dim3(256), 0, s, jobs, (uint32_t)count, ev, ref, path_off, path_len, tmp_i, tmp_j,
-                       path_j0, path_mv, path_d);
-    return hipGetLastError();
+    const hipError_t e = with_wave_rows(cls, [&](auto rpl) {
+        hipLaunchKernelGGL(k_semi_walk_wave<decltype(rpl)::value>, dim3((uint32_t)count), dim3(64), 0, s, jobs, aux, dir_ws, end_j, path_off,
+                           path_len, tmp_i, tmp_j);
+        return hipGetLastError();
+    });
+    return launch_semi_finish(e, jobs, count, ev, ref, path_off, path_len, tmp_i, tmp_j, path_j0, path_mv, path_d, s);
 }
 
 } // namespace rawdtw

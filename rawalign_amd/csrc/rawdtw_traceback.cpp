@@ -28,7 +28,7 @@ static int full_walk(rawdtw_ctx *ctx, const TbStretch &s, const TbSlot &slot)
 {
     const rawdtw_plan *pl = static_cast<const rawdtw_plan *>(s.plan);
     for (const Launch &L : pl->launches) {
-        hipError_t e = launch_tb_walk_wave(pl->d_jobs + L.first, L.count, pl->d_aux + L.first, L.param & 255, ctx->d_ev, ctx->d_ref, pl->d_dir,
+        hipError_t e = launch_tb_walk_wave(pl->d_jobs + L.first, L.count, pl->d_aux + L.first, wave_class_of(L.param), ctx->d_ev, ctx->d_ref, pl->d_dir,
                                            slot.poff + L.first, slot.plen + L.first, slot.ti, slot.tj, slot.mv, slot.pd, ctx->stream);
         if (e != hipSuccess) return hip_fail(ctx, e, "traceback walk launch");
     }

@@ -9,6 +9,8 @@
 //   once         every plan launch is one entry, its own or a carried one, in plan order, under its own kind and parameter otherwise
 //   event slots  the pairs of distinct (run, launch) never overlap and stay below runs * 2 * nl
 //   launch word  the merged entry's is kKindBandMerged | param << 8 (the device-planned form's entry 1: the image's floats as param)
+// and the table of wave classes: five classes of 1, 2, 4, 8, 8 rows a lane on 1, 1, 1, 1, kFullWgWaves waves, reported as
+// 1, 2, 4, 8, 264; class -> parameter -> class round-trips, and a parameter that no class reports is rejected.
 // Prints "ok <cases>"; the first failure otherwise.
 #include <cstdio>
 #include <vector>
@@ -77,11 +79,30 @@ static bool joblist_case(const std::vector<Launch> &ls, bool merge_small, int ti
     return true;
 }
 
+static bool wave_class_case()
+{
+    const char *what = "wave classes";
+    const int rows[5] = {1, 2, 4, 8, 8}, waves[5] = {1, 1, 1, 1, kFullWgWaves}, params[5] = {1, 2, 4, 8, 264};
+    CHECK(kWaveClasses == 5 && kFullWgWaves == 4, what);
+    for (int c = 0; c < kWaveClasses; c++) {
+        CHECK(kWaveClass[c].rows == rows[c] && kWaveClass[c].waves == waves[c], what);
+        CHECK(wave_class_param(c) == params[c] && wave_class_of(wave_class_param(c)) == c, what);
+        CHECK(launch_word(kKindSemiWave, wave_class_param(c)) == (11u | (uint32_t)params[c] << 8), what);
+    }
+    for (int32_t p = -300; p <= 600; p++) {
+        bool known = false;
+        for (int c = 0; c < 5; c++) known |= p == params[c];
+        if (!known) CHECK(wave_class_of(p) == -1, what);
+    }
+    return true;
+}
+
 int main()
 {
     unsigned long cases = 0;
     if (!stream_case(5800)) return 1;
     cases++;
+    if (!wave_class_case()) return 1; // (not counted: "ok <cases>" counts launch tables)
     const Launch pool[8] = {{kKindBandLane, 6144, 0, 900}, {kKindBandWreg, -16, 900, 70}, {kKindBandWreg, -8, 970, 50},   {kKindBandWreg, 0, 1020, 40},
                             {kKindBandWreg, 4, 1060, 30},  {kKindBandWave, 9000, 1090, 5}, {kKindFullWave, 2, 1095, 3},   {kKindBandLaneHi, 14336, 1098, 20}};
     for (unsigned set = 0; set < 256; set++)

@@ -1,7 +1,8 @@
 """A batch's launch table (rawalign_amd/csrc/rawdtw_launches.h: which launches a batch reports, under which kinds, which of them travel
 inside the merged launch, and where the event pairs of timed runs lie) checked by a stand-alone C++ program, tests/abi/batch_launches.cpp:
 the header has no HIP include, a plain compiler takes it.  The device-planned form and every job-list launch list of up to one launch of
-each kind the planner emits, in two orders, under every combination of the four settings the merge reads.  Built plain and with
+each kind the planner emits, in two orders, under every combination of the four settings the merge reads; and the table of wave classes
+(rows a lane, waves a job, reported parameter; both conversions, an unknown parameter rejected).  Built plain and with
 AddressSanitizer + UndefinedBehaviorSanitizer (its own main: nothing is preloaded)."""
 import os
 import subprocess
